@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- Mpixels/s restored (FFT + Wiener + IFFT) on synthetic N x N fp32 images, MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--size 4096] [--batch 4] [--mode fast|parity]
+    python bench.py --gpus N --steps K --warmup W [--size 4096] [--batch 4] [--mode fast|parity] [--dump-outputs DIR]
 
 A "step" is one pass of the hot path (pad -> FFT2 -> Wiener -> IFFT2 -> real -> normalise -> crop)
 over one batch of `--batch` device-resident synthetic images per GPU.  Inputs and outputs stay in
@@ -50,6 +50,8 @@ PASS_BYTES = {
 }
 PIPELINE_BYTES = {("fast", "half"): 36, ("fast", "full"): 56, ("parity", "full"): 72}
 SEEDS = {1024: 0x5EED0002, 4096: 0x5EED0003, 8192: 0x5EED0004, 2048: 0x5EED0005}
+DUMP_MAX_BYTES = 64 * 10 ** 6  # --dump-outputs: all files of one run together
+DUMP_SEED = 0x5EED00D0         # --dump-outputs: which rows of a larger output are kept
 
 
 def split_pass_name(name):
@@ -100,7 +102,32 @@ def parse():
     ap.add_argument("--bcast-filter", action="store_true",
                     help="rank 0 alone prepares the PSF spectrum / filter W and broadcasts it (RCCL under nccl) instead of every rank "
                          "recomputing it: the MPI_Bcast / Scatterv of the padded PSF in the reference's MPI variant (fft/fft_mpi.cpp:334-378)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the restored images of the last timed step as DIR/restored.npy (float32; "
+                         "DIR/restored_rank<r>.npy per rank when N > 1), at most 64 MB in all: every image when they fit, else a "
+                         "fixed seeded sample of whole rows, whose row indices go to DIR/restored_rows.npy (float64)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+def dump_outputs(outs, B, S, directory, name, budget):
+    """Write what the timed path returned in its last step (outs[:B], B images of S x S float32) under `directory`:
+    the whole batch when it fits `budget` bytes, else whole rows picked by a fixed seed (the same rows in every run
+    with the same arguments) plus their indices into the (B * S, S) stack of rows.  Returns the file names."""
+    import numpy as np
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    if B * S * S * 4 <= budget:
+        np.save(os.path.join(directory, name + ".npy"), outs[:B].cpu().numpy())
+        return [name + ".npy"]
+    nrows = max(1, min(B * S, (budget - 256) // (S * 4 + 8)))  # 256: the two .npy headers
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(B * S, size=nrows, replace=False))
+    rows = outs[:B].reshape(B * S, S)[torch.from_numpy(idx).to(outs.device)].cpu().numpy()
+    np.save(os.path.join(directory, name + ".npy"), rows)
+    np.save(os.path.join(directory, name + "_rows.npy"), idx.astype(np.float64))
+    return [name + ".npy", name + "_rows.npy"]
 
 
 def cpu_baseline(size):
@@ -238,6 +265,11 @@ def main():
     for r in range(max(1, args.repeats)):
         reps.append(batch_mod.timed_steps(comm, step, torch.cuda.synchronize, args.steps, args.warmup if r == 0 else 0))
     elapsed = sorted(reps)[len(reps) // 2]
+    # outs holds the last timed step's results until the checks below overwrite parts of it: save them now
+    dumped = None
+    if args.dump_outputs and B > 0:
+        dumped = dump_outputs(outs, B, S, args.dump_outputs, "restored" if world == 1 else "restored_rank%d" % rank,
+                              DUMP_MAX_BYTES // world)
 
     # ---- consistency check over RCCL (outside the timed region) ----
     images_mine = B * args.steps  # images this rank restored in one repetition of the timed region
@@ -424,6 +456,8 @@ def main():
                                               "all %d images of a step recomputed one at a time on one stream on every rank: bit-identical required%s"
                                               % (B, "" if not differing else "; rank 0 DIFFERS at images %s" % differing[:16]))},
         }
+        if args.dump_outputs:
+            line["dump_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "rank0_files": dumped}
         if int(tot[2]) != world or images != int(tot[3]) * args.steps:
             rc = 3
         if bcast is not None and not (bcast["hash_min"] == bcast["hash_max"] == bcast["hash"]):
