@@ -126,7 +126,7 @@ struct fdr_plan {
     int device = 0, M = 0, N = 0, logM = 0, logN = 0, mode = 0;
     unsigned flags = 0;
     bool simple = false;
-    bool ppar = false;  // parity operator on a PANEL-major complex intermediate (round 4): contiguous column tiles
+    bool ppar = false;  // parity operator on a PANEL-major complex intermediate: contiguous column tiles
     bool big = false;  // a power-of-two dimension above 8192: simple sequence with the long row pass (fdr_aux.hip)
     int num_cu = 256;
     bool tables_only = false;  // FDR_FLAG_TABLES_ONLY: no workspaces, slab primitives only
@@ -183,8 +183,8 @@ struct fdr_plan {
     };
     // host-pointer batch (fdr_wiener_batch_*_f32): three streams, three images in flight; created on first use and kept --
     // a driver that calls wienerDeblur_RGB_optimized once per picture (3 channels per call) would otherwise pay three
-    // hipStreamCreate, six hipMalloc / hipFree and nine event creations per call: 16 of the 17.6 ms such a call took on a
-    // 782 x 1920 picture whose device work is under 1 ms
+    // hipStreamCreate, six hipMalloc / hipFree and nine event creations per call, most of such a call's time
+    // (LAB_NOTES "host-pointer calls")
     struct HostPipe {
         hipStream_t s_in = nullptr, s_cmp = nullptr, s_out = nullptr;
         float* d_in[3] = {nullptr, nullptr, nullptr};
@@ -467,7 +467,7 @@ int panel_stage_CE(fdr_plan* p, fdr_plan::Slot& w, int rows, int cols, float* d_
         a.src_c = w.work; a.mm_part = w.mm_part; a.mm_rows = mm_rows; a.mm_cols = mm_cols; a.M = p->M;
         a.pstride = p->pstride; a.half = 1; a.num_cu = p->num_cu;
         a.out = d_out; a.out_rows = rows; a.out_cols = cols; a.out_stride = out_stride;
-        a.n_part = rows4_minmax_partials(p->logN, p->M, p->num_cu, 1, p->half ? 1 : 0);
+        a.n_part = rows4_minmax_partials(p->logN, p->M, 1, p->half ? 1 : 0);
         if (a.n_part <= 0 || a.n_part > p->mm_part_cap) return fail(FDR_ERR_STATE, "fdr_wiener: min/max partial count out of range");
         {
             ScopedPass t(p, s, kPassRowsMinmax);
@@ -488,7 +488,7 @@ int panel_stage_CE(fdr_plan* p, fdr_plan::Slot& w, int rows, int cols, float* d_
     }
     {   // E: normalise to [0,1] and crop
         ScopedPass t(p, s, kPassNormalize);
-        const int n_part = rows4_minmax_partials(p->logN, p->M, p->num_cu, 1, p->half ? 1 : 0);
+        const int n_part = rows4_minmax_partials(p->logN, p->M, 1, p->half ? 1 : 0);
         if (n_part <= 0 || n_part > p->mm_part_cap || n_part > 4096) return fail(FDR_ERR_STATE, "fdr_wiener: min/max partial count out of range");
         FDR_HIP(launch_normalize(w.raw, p->N, w.mm_part, n_part, nullptr, d_out, rows, cols, out_stride, s));
     }
@@ -515,7 +515,7 @@ int panel_stage_CE_batch(fdr_plan* p, fdr_plan::Slot* const* ws, int n, int rows
         a.src_c = ws[0]->work; a.mm_part = ws[0]->mm_part; a.mm_rows = mm_rows; a.mm_cols = mm_cols; a.M = p->M;
         a.pstride = p->pstride; a.half = 1; a.num_cu = p->num_cu;
         a.out = d_outs[0]; a.out_rows = rows; a.out_cols = cols; a.out_stride = out_stride;
-        a.n_part = rows4_minmax_partials(p->logN, p->M, p->num_cu, n, p->half ? 1 : 0);
+        a.n_part = rows4_minmax_partials(p->logN, p->M, n, p->half ? 1 : 0);
         if (a.n_part <= 0 || a.n_part > p->mm_part_cap) return fail(FDR_ERR_STATE, "fdr_wiener: min/max partial count out of range");
         a.batch.nimg = n;
         for (int k = 0; k < kMaxGroup; ++k) {
@@ -546,7 +546,7 @@ int panel_stage_CE_batch(fdr_plan* p, fdr_plan::Slot* const* ws, int n, int rows
     }
     {
         ScopedPass t(p, s, kPassNormalizeN[n]);
-        const int n_part = rows4_minmax_partials(p->logN, p->M, p->num_cu, n, p->half ? 1 : 0);
+        const int n_part = rows4_minmax_partials(p->logN, p->M, n, p->half ? 1 : 0);
         if (n_part <= 0 || n_part > p->mm_part_cap || n_part > 4096) return fail(FDR_ERR_STATE, "fdr_wiener: min/max partial count out of range");
         NormBatch nb{};
         nb.nimg = n;
@@ -626,11 +626,11 @@ int wiener_dev_impl(fdr_plan* p, fdr_plan::Slot& w, const float* d_img, int rows
         if (n_part <= 0 || n_part > p->mm_part_cap) return fail(FDR_ERR_STATE, "fdr_wiener: min/max partial count out of range");
         const bool pp = p->ppar && p->mode == FDR_MODE_PARITY && !p->simple;  // the raw plane is panel-major then
         if (n_part <= 4096) {
-            if (pp) FDR_HIP(launch_normalize_panels(w.raw, p->M, p->N, w.mm_part, n_part, nullptr, d_out, rows, cols, out_stride, s));
+            if (pp) FDR_HIP(launch_normalize_panels(w.raw, p->M, w.mm_part, n_part, nullptr, d_out, rows, cols, out_stride, s));
             else FDR_HIP(launch_normalize(w.raw, p->N, w.mm_part, n_part, nullptr, d_out, rows, cols, out_stride, s));
         } else {  // many partials (reference-shaped path): fold them once in a separate launch
             FDR_HIP(launch_reduce_minmax(w.mm_part, n_part, w.mm, s));
-            if (pp) FDR_HIP(launch_normalize_panels(w.raw, p->M, p->N, nullptr, 0, w.mm, d_out, rows, cols, out_stride, s));
+            if (pp) FDR_HIP(launch_normalize_panels(w.raw, p->M, nullptr, 0, w.mm, d_out, rows, cols, out_stride, s));
             else FDR_HIP(launch_normalize(w.raw, p->N, nullptr, 0, w.mm, d_out, rows, cols, out_stride, s));
         }
     }
@@ -697,11 +697,10 @@ static int plan_create_impl(fdr_plan* p, int device, int M, int N, int mode, uns
         P = (size_t)p->npanels * p->pstride;
     } else if (mode == FDR_MODE_PARITY && !p->simple) {
         // the bit-identical mode keeps the reference's pass order and full complex spectrum, but its intermediate is panel-major
-        // too since round 4 (all N/4 panels): the column passes B and D read and write contiguous M x 32-byte tiles instead of
-        // 32 bytes of every row (B 169 -> 88, D 67 -> 55 us per 4096^2 image; A and C pay 9 us each for their 32-byte pieces,
-        // which they reach through an XCD-aware workgroup order, fdr_rows.hip; the raw real plane is panel-major as well and
-        // normalize_panels_kernel turns it back).  381 -> 276 us per 4096^2 image, 1767 -> 1266 at 8192^2.  Same butterflies,
-        // same tables, same bits (every parity test compares with ==).
+        // too (all N/4 panels): the column passes B and D read and write contiguous M x 32-byte tiles instead of 32 bytes of
+        // every row; A and C reach their 32-byte pieces through an XCD-aware workgroup order (fdr_rows.hip); the raw real plane
+        // is panel-major as well and normalize_panels_kernel turns it back (LAB_NOTES "parity mode layout").  Same
+        // butterflies, same tables, same bits (every parity test compares with ==).
         p->ppar = true;
         p->pstride = (size_t)M * 4 + 16;
         p->npanels = N / 4;
@@ -1028,13 +1027,10 @@ int batch_enqueue(fdr_plan* p, const float* d_imgs, size_t img_pitch, int count,
             if (rc == FDR_OK) rc = panel_stage_B(p, ws, n, s);
             // The two inverse row passes (C1: extremes; C2: the same transform again, normalised) go in CHUNKS of the group
             // when the batch alternates over two or more streams: C1 is the pass with exposed compute, and in launches of half
-            // the size it interleaves better with the memory-bound passes of the other stream's group.  Measured at 4096^2,
-            // 2 streams x 4 images, alternating runs on one box: chunks of 4 / 2 / 1 images 89.1 / 87.9 / 87.5 us per image;
-            // with ONE stream the chunks only make the launches smaller (91.5 -> 93.1 us), at 2048^2 too (21.3 -> 25.3 us), and
-            // passes A / B' lose in chunks at any size (89.3 -> 91.1 / 93.4 us).  Hence: >= 2 streams, and a chunk holds at least
-            // ce_chunk_bytes of spectrum (FDR_OPT_CE_CHUNK_MB, default 160 MiB: pairs at 4096^2, the whole group below, no
-            // split where one image alone is larger).  (Not an Infinity-Cache effect, although the 256 MiB suggest it: the
-            // passes' own durations get LONGER in chunks, C1 14.0 -> 16.4 us per image; the gain is in the overlap.)
+            // the size it interleaves better with the memory-bound passes of the other stream's group.  With ONE stream the
+            // chunks only make the launches smaller, and passes A / B' lose in chunks (LAB_NOTES "inverse row chunks").
+            // Hence: >= 2 streams, and a chunk holds at least ce_chunk_bytes of spectrum (FDR_OPT_CE_CHUNK_MB, default
+            // 160 MiB: pairs at 4096^2, the whole group below, no split where one image alone is larger).
             int chunk = n;
             if (ns > 1) {
                 const size_t spec_bytes = p->ws_elems * sizeof(float2);
@@ -1124,8 +1120,8 @@ int fdr_wiener_f32(fdr_plan* p, const float* img_host, int rows, int cols, int s
     hipError_t e;
     {
         ScopedPhase ph(p, FDR_PHASE_H2D, nullptr);
-        // (a dense image is ONE linear copy: the 2-D form of a pageable buffer goes row by row -- measured 2.9 ms against
-        // 0.8 ms for the 8 MB channel of a padded 1024 x 2048 picture)
+        // (a dense image is ONE linear copy: the 2-D form of a pageable buffer goes row by row, several times slower;
+        // LAB_NOTES "host-pointer calls")
         if (stride == cols) e = hipMemcpy(d_in, img_host, bytes, hipMemcpyHostToDevice);
         else e = hipMemcpy2D(d_in, (size_t)cols * sizeof(float), img_host, (size_t)stride * sizeof(float),
                              (size_t)cols * sizeof(float), rows, hipMemcpyHostToDevice);
@@ -1182,9 +1178,8 @@ int fdr_wiener_batch_ptrs_f32(fdr_plan* p, const float* const* imgs_host, float*
         return fail(FDR_ERR_ARG, "fdr_wiener_batch_f32: image shape does not fit the plan");
     FDR_HIP(hipSetDevice(p->device));
     // Three images in flight: one arriving, one being restored, one leaving, each on its own stream.  Pinned buffers
-    // (fdr_host_alloc) are read / written by DMA and all three stages overlap (measured 1.84 ms per 4096^2 image,
-    // 36 GB/s each way at once); with pageable buffers the runtime stages every copy itself and the copy calls
-    // block, which leaves the synchronous rate (8 ms) -- an own staging ring with one memcpy thread was slower.
+    // (fdr_host_alloc) are read / written by DMA and all three stages overlap; with pageable buffers the runtime stages
+    // every copy itself and the copy calls block, which leaves the synchronous rate (LAB_NOTES "host-pointer calls").
     constexpr int D = 3;
     const size_t bytes = (size_t)rows * cols * sizeof(float), rowb = (size_t)cols * sizeof(float);
     // streams, events and device staging live in the plan (created on first use, sized for the plan's M x N)
@@ -1584,7 +1579,7 @@ int batch_worker_run(const fdr_batch_desc* d, BatchWorker* w, std::chrono::stead
             return FDR_OK;
         }
         // synthetic, device resident
-        // defaults as bench.py's (measured): 2 streams; 8 images per launch up to 1024^2, 4 up to 4096^2, larger 2
+        // defaults as bench.py's: 2 streams; 8 images per launch up to 1024^2, 4 up to 4096^2, larger 2
         const size_t px = (size_t)d->M * (size_t)d->N;
         const int ns = d->nstreams > 0 ? d->nstreams : (d->mode == FDR_MODE_FAST ? 2 : 3);
         const int gr = d->group > 0 ? d->group : (px <= (size_t)1024 * 1024 ? 8 : (px <= (size_t)4096 * 4096 ? 4 : 2));

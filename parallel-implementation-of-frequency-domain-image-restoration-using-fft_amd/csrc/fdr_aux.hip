@@ -248,7 +248,7 @@ hipError_t launch_reduce_minmax(const float2* mm_part, int n_part, float* mm, hi
 // scale/shift exactly as OpenCV 4.x derives them for CV_32F: double min/max, scale rounded to
 // float, shift = (float)dmin - (float)(smin*scale); applied as a float multiply then a float add.
 // Every workgroup first folds the (few thousand) per-workgroup min/max partials itself -- a fixed
-// order, so the result is deterministic -- which saves a separate reduce launch (~4.4 us).
+// order, so the result is deterministic -- which saves a separate reduce launch.
 
 template <bool VEC4>
 __global__ __launch_bounds__(256) void normalize_kernel(const float* __restrict__ raw, int N, const float2* __restrict__ part,
@@ -257,7 +257,7 @@ __global__ __launch_bounds__(256) void normalize_kernel(const float* __restrict_
     if (nb.nimg > 1) {  // blockIdx.y = image
         const int i = blockIdx.y;
         // (direct member accesses: through pick_image's array reference this by-value kernel argument went to scratch
-        // memory -- 208 bytes per lane and 150 instead of 95 us per 4-image launch at 4096^2)
+        // memory; LAB_NOTES "kernel arguments in scratch")
 #define FDR_PICK8(arr) (i < 4 ? (i == 0 ? arr[0] : i == 1 ? arr[1] : i == 2 ? arr[2] : arr[3]) : (i == 4 ? arr[4] : i == 5 ? arr[5] : i == 6 ? arr[6] : arr[7]))
         static_assert(kMaxGroup == 8, "select chain written for 8 entries");
         raw = FDR_PICK8(nb.raw);
@@ -335,9 +335,9 @@ hipError_t launch_normalize(const float* raw, int N, const float2* mm_part, int 
     return hipGetLastError();
 }
 
-// ---- the same normalisation from a PANEL-major real plane (parity operator since round 4): a workgroup takes 16 rows x 64
-// columns, reads 16 panels x (16 rows x 16 bytes = 256 contiguous bytes), turns the block through LDS and writes 16 rows x
-// 256 contiguous bytes.  scale / shift and the two roundings exactly as normalize_kernel.
+// ---- the same normalisation from a PANEL-major real plane (the parity operator's layout): a workgroup takes 32 rows x 128
+// columns, reads 32 panels x (32 rows x 16 bytes = 512 contiguous bytes), turns the block through LDS and writes 32 rows x
+// 512 contiguous bytes.  scale / shift and the two roundings exactly as normalize_kernel.
 template <bool VEC4>
 __global__ __launch_bounds__(256) void normalize_panels_kernel(const float* __restrict__ raw, int M, const float2* __restrict__ part, int n_part,
                                                                const float* __restrict__ mm, float* __restrict__ out, int rows, int cols,
@@ -408,9 +408,8 @@ __global__ __launch_bounds__(256) void normalize_panels_kernel(const float* __re
     }
 }
 
-hipError_t launch_normalize_panels(const float* raw, int M, int N, const float2* mm_part, int n_part, const float* mm, float* out,
+hipError_t launch_normalize_panels(const float* raw, int M, const float2* mm_part, int n_part, const float* mm, float* out,
                                    int rows, int cols, int out_stride, hipStream_t s) {
-    (void)N;
     if (rows <= 0 || cols <= 0) return hipSuccess;
     const long long nb = (long long)((cols + 127) / 128) * ((rows + 31) / 32);
     const int grid = nb > 4096 ? 4096 : (int)nb;

@@ -47,7 +47,7 @@ __device__ __forceinline__ float2 wiener_parity(float2 g, float2 h, float K) {
     o.y = denom != 0.0f ? ni / denom : 0.0f;
     return o;
 }
-// PANEL = 1 (parity operator since round 4): the array is panel-major -- a thread group's four columns are ONE contiguous
+// PANEL = 1 (parity operator): the array is panel-major -- a thread group's four columns are ONE contiguous
 // M x 32-byte block, whole 128-byte lines per quad of lanes -- instead of 32 bytes of every row of the row-major array.
 template <int LOGM, class Pol, int KIND, int PANEL>
 __global__ __launch_bounds__(ColGeom<LOGM>::THREADS, ColGeom<LOGM>::WAVES_PER_SIMD) void fft_cols_kernel(const ColArgs a, const float2* __restrict__ tw_fwd,
@@ -102,7 +102,7 @@ __global__ __launch_bounds__(ColGeom<LOGM>::THREADS, ColGeom<LOGM>::WAVES_PER_SI
         }
     } else if (KIND == COL_FWD_WIENER) {
         // The quotient needs IEEE square roots and divisions -- a dozen temporaries each -- beside the 64 registers of the tile,
-        // and at 128 registers per lane hipcc spilled 15-39 of them (PMC: +23 % HBM writes, +12 % reads in this pass).  The
+        // and at 128 registers per lane hipcc spilled some of them (LAB_NOTES "parity Wiener pass").  The
         // exchange buffers are idle by now: the second half of the tile (slots 4..7) waits THERE while the first half is
         // divided, 64 KB of LDS traffic per tile instead of scratch memory.  Each thread reads back only what it wrote.
         constexpr int HALF = 4;
@@ -161,7 +161,7 @@ template <int LOGM, class Pol, int KIND>
 static hipError_t launch_cols_one(const ColArgs& a, const float2* twf, const float2* twi, hipStream_t s) {
     using Geo = ColGeom<LOGM>;
     const int ntiles = (a.N + Geo::COLS - 1) / Geo::COLS;
-    if constexpr (KIND == COL_FWD_WIENER || KIND == COL_INV_REAL) {  // the operator's own passes: panel-major only since round 4
+    if constexpr (KIND == COL_FWD_WIENER || KIND == COL_INV_REAL) {  // the operator's own passes: panel-major only
         if (!a.panel_c) return hipErrorInvalidValue;
         hipLaunchKernelGGL((fft_cols_kernel<LOGM, Pol, KIND, 1>), dim3(ntiles), dim3(Geo::THREADS), 0, s, a, twf, twi);
         return hipGetLastError();

@@ -24,8 +24,8 @@ namespace fdr {
 // Race fuzzer (timing-only debug builds, -DFDR_DEBUG_JITTER): every wave sleeps a pseudo-random 0..7 microseconds at the
 // points where it is about to write or read shared LDS state, so that the waves of a workgroup drift apart by more than
 // any phase lasts.  A missing barrier then corrupts data in (nearly) every workgroup instead of once in a thousand runs
-// under a second stream's load (round 2: pass A's separation buffer).  The GPU test suite is run against such a build
-// with tools/gpu_jitter.sh; product builds compile this to nothing.
+// under a second stream's load.  The GPU test suite is run against such a build with tools/gpu_jitter.sh; product builds
+// compile this to nothing.
 #ifdef FDR_DEBUG_JITTER
 __device__ __forceinline__ void fdr_jitter(unsigned salt) {
     unsigned h = (threadIdx.x >> 6) * 0x9E3779B1u + salt * 0x85EBCA77u + (blockIdx.x + 131u * blockIdx.y) * 0xC2B2AE3Du;
@@ -135,13 +135,8 @@ struct PolicyFast {
     typedef float v2f __attribute__((ext_vector_type(2)));
     static __device__ __forceinline__ void bfly(float2& u, float2& v, const float2 w) {
         // u' = u + v*w in 4 FMAs, v' = 2u - u' in 2 FMAs -- written on 2-vectors so that every butterfly becomes three
-        // v_pk_fma_f32 (left to itself hipcc packs only about half of them; the rest are six scalar v_fma each):
-        // 30 % fewer VALU instructions per transform, 1.37 -> 1.03 us per 4096-point transform per CU.  The rotated
-        // twiddle (-w.y, w.x) is a register pair per twiddle; building it from operand modifiers instead (negated
-        // broadcast of v.y) costs a v_mov per butterfly and was slower.  (Round 4: the three instructions written out as
-        // inline asm with op_sel / neg_lo on the twiddle doing the rotation -- no second pair, 254 -> 238 registers in pass B' --
-        // measured equal within noise, 33.8 / 35.3 vs 34.3 / 34.9 us per 4096^2 image: the passes are not bound by their VALU
-        // work; hipcc also pads every inline-asm def-use pair closer than three instructions with an s_nop.  Not kept.)
+        // v_pk_fma_f32 (left to itself hipcc packs only about half of them; the rest are six scalar v_fma each).  The
+        // rotated twiddle (-w.y, w.x) is a register pair per twiddle (LAB_NOTES "packed butterflies").
         const v2f uu = {u.x, u.y}, vx = {v.x, v.x}, vy = {v.y, v.y}, ww = {w.x, w.y}, wr = {-w.y, w.x};
         const v2f t = __builtin_elementwise_fma(vy, wr, uu);   // (u.x - v.y w.y, u.y + v.y w.x)
         const v2f a = __builtin_elementwise_fma(vx, ww, t);    // (.. + v.x w.x, .. + v.x w.y)
@@ -183,34 +178,14 @@ struct PolicyFast {
     }
 };
 
-// The same with scalar FMAs (what hipcc packs by itself): the 4096-point column pass keeps 128 data registers per lane,
-// where the extra register pair per rotated twiddle of the packed form spills (14 VGPRs, +15 % HBM traffic from scratch)
-// for no gain in time -- that kernel alone uses this variant.
-struct PolicyFastScalar : PolicyFast {
-    static __device__ __forceinline__ void bfly(float2& u, float2& v, const float2 w) {
-        const float ar = __builtin_fmaf(v.x, w.x, __builtin_fmaf(-v.y, w.y, u.x));
-        const float ai = __builtin_fmaf(v.x, w.y, __builtin_fmaf(v.y, w.x, u.y));
-        v.x = __builtin_fmaf(2.0f, u.x, -ar);
-        v.y = __builtin_fmaf(2.0f, u.y, -ai);
-        u.x = ar; u.y = ai;
-    }
-};
-
 // One exchange value out of LDS as ONE ds_read_b64.  Left to itself hipcc pairs the strided reads of an exchange into
 // ds_read2_b64, which the LDS serves as two 4 x 16-lane accesses: 8 cycles per wave-instruction for 1 KB, against 2 cycles
 // per ds_read_b64 for 512 B (MI355X_MICROARCH.md, LDS table: 128 vs 256 B/clk per CU) -- half the read bandwidth in the
 // phase of the transforms that is bound by the LDS.  A volatile 64-bit access is not merged.
-#ifndef FDR_LDS_READ_B64
-#define FDR_LDS_READ_B64 1
-#endif
 __device__ __forceinline__ float2 lds_read_b64(const float2* p) {
-#if FDR_LDS_READ_B64
     typedef const volatile __attribute__((address_space(3))) unsigned long long* lds_u64_ptr;  // (explicitly LDS: a volatile generic access would be a flat load)
     const unsigned long long u = *(lds_u64_ptr)(p);
     return make_float2(__uint_as_float((unsigned)u), __uint_as_float((unsigned)(u >> 32)));
-#else
-    return *p;
-#endif
 }
 
 __device__ __forceinline__ void load4(const float2* p, float2& a, float2& b, float2& c, float2& d) {
@@ -450,8 +425,8 @@ __device__ __forceinline__ void radix16_fast(float2 (&v)[B][V], float2 base) {
 // r0 = t mod T/2 and k' = t div T/2: all sources of a thread are the thread itself and its partner t +- T/2.  With the
 // logical thread index laid out so that the partners are lanes l and l + 32 of ONE wave (thread_index below), the
 // exchange is `v_permlane32_swap_b32` on the register pair (Y[..][0], Y[..][1]) of every u: V/2 x 2 swaps per transform
-// instead of a full LDS round trip with two barriers (the LDS store path, ~85 B/clk per CU, is what bounds the
-// 8192-point passes: 7 round trips per column pair of transforms before, 4 now together with permute_out_to_in).
+// instead of a full LDS round trip with two barriers (the LDS store path is what bounds the 8192-point passes;
+// LAB_NOTES "8192-point exchanges").
 // Kernels that instantiate a SWAP0 core must take their thread index from thread_index(threadIdx.x).
 template <int LOGL, int B, int NBUF, class Pol, int LOGV = 3, bool SWAP0 = false>
 struct FftCore {
@@ -635,12 +610,12 @@ struct FftCore {
 
 // ---------------------------------------------------------------------------------------------
 // min/max of the real plane: every producing workgroup writes ONE (min, max) partial; a single
-// small kernel reduces the partials (deterministic, and no same-address atomics: 65k atomics on
-// two words cost ~0.7 ms on MI355X, 15x the kernel that issued them).
+// small kernel reduces the partials (deterministic, and no same-address atomics, which serialise
+// on two words; LAB_NOTES "min / max partials").
 // ---------------------------------------------------------------------------------------------
 // min / max of three as ONE instruction.  Written as fminf / fmaxf chains hipcc quiets every operand it cannot prove
-// canonical first (`v_max_f32 x, x, x`: transform results that went through LDS, DPP or an asm tie): pass C1's 64 values per
-// lane cost 490 VALU instructions that way, 64 this way -- and that pass is bound by its VALU issue (4 waves per SIMD).
+// canonical first (`v_max_f32 x, x, x`: transform results that went through LDS, DPP or an asm tie), several instructions
+// per value in pass C1, which is bound by its VALU issue (LAB_NOTES "min / max partials").
 // NaN handling as v_min_f32 / v_max_f32 in IEEE mode (a quiet NaN operand is ignored, like fminf).
 __device__ __forceinline__ float fdr_min3(float a, float b, float c) {
 #if defined(__HIP_DEVICE_COMPILE__)

@@ -112,8 +112,8 @@ hipError_t launch_cols(int logm, int mode, ColKind kind, const ColArgs& a, const
 // fast-mode passes on the panel-major intermediate (fdr_panel.hip); tw_fwd = forward table
 // rows4: (ROW_IN_REAL -> ROW_OUT_COMPLEX[panel]) forward, (ROW_IN_COMPLEX[panel] -> ROW_OUT_REAL_MINMAX) inverse
 hipError_t launch_rows4(int logl, RowIn in, RowOut out, const RowArgs& a, const float2* tw_fwd, hipStream_t s);
-// min/max partials pass C' writes per image when `nimg` images share a launch on a device with num_cu CUs
-int rows4_minmax_partials(int logl, int M, int num_cu, int nimg, int half);
+// min/max partials pass C' writes per image when `nimg` images share a launch
+int rows4_minmax_partials(int logl, int M, int nimg, int half);
 // cols_panel: COL_FWD_FILTER (PSF spectrum -> W, in place) or COL_FUSED (FFT . W . IFFT)
 hipError_t launch_cols_panel(int logm, ColKind kind, const ColArgs& a, const float2* tw_fwd, hipStream_t s);
 
@@ -140,7 +140,7 @@ int cols_minmax_partials(int logm, int N);
 hipError_t launch_normalize(const float* raw, int N, const float2* mm_part, int n_part, const float* mm, float* out,
                             int rows, int cols, int out_stride, hipStream_t s, const NormBatch* batch = nullptr);
 // the same from a PANEL-major real plane (panel p = columns 4 p .. 4 p + 3, M rows of 4 floats, panels 4 M floats apart)
-hipError_t launch_normalize_panels(const float* raw, int M, int N, const float2* mm_part, int n_part, const float* mm, float* out,
+hipError_t launch_normalize_panels(const float* raw, int M, const float2* mm_part, int n_part, const float* mm, float* out,
                                    int rows, int cols, int out_stride, hipStream_t s);
 hipError_t launch_psf_motion(int size, double angle_deg, float* d_out, hipStream_t s);
 // cv::warpAffine defaults (bilinear, constant 0 border) on a single-channel float image; fwd = the 2 x 3 matrix as cv::warpAffine takes it

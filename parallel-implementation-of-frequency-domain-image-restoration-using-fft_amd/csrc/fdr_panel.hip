@@ -2,9 +2,8 @@
 //
 // Why: a column pass that keeps 4 adjacent columns of a row-major M x N array touches 32 of the
 // 128 bytes of every line; four workgroups share each line, and with >= 128 KB of lines in flight
-// per CU the sharing cannot be served from the 4 MiB XCD L2 -- measured on MI355X: pass B' with
-// the transform compiled out still took 191 us at 4096^2 (2.1 TB/s algorithmic, each line moved
-// ~4x).  The fix is a layout in which every pass moves whole lines:
+// per CU the sharing cannot be served from the 4 MiB XCD L2, and each line moves about four times
+// (LAB_NOTES "panel layout").  The fix is a layout in which every pass moves whole lines:
 //
 //     panel_index(m, n) = (n >> 2) * PS + m * 4 + (n & 3)     (M rows, N columns, float2 elements)
 //
@@ -20,14 +19,12 @@
 //   pass C' : 4 rows gathered from the panels -> row IFFTs -> real plane + min/max partial
 // The layout is private to a plan (never visible through the C ABI); W is stored the same way.
 #include "fdr_fft_core.hpp"
-#include <type_traits>
 #include "fdr_kernels.hpp"
 
 namespace fdr {
 
 // ---------------------------------------------------------------------------------------------
 // rows, 4 at a time
-// ---------------------------------------------------------------------------------------------
 // ---------------------------------------------------------------------------------------------
 // Two-for-one row transforms (fast mode only; rounding differs from the serial path at the 1e-7
 // level, far inside the 1e-4 budget).  The image rows are real, and after the inverse column pass
@@ -37,55 +34,32 @@ namespace fdr {
 //             (Z[N-n] lives in another thread: one natural-order LDS round trip)
 //   inverse : Z = Y_a + i Y_b  ->  z = IFFT(Z);  row a = Re z, row b = Im z   (no fix-up at all)
 // A 4-row group therefore costs 2 complex transforms instead of 4.
+//
+// Cores whose first step is radix 2 (8192 = 2 x 16 x 16 x 16) and that span at least one wave do the first exchange with
+// v_permlane32_swap instead of LDS (FftCore's SWAP0).
 // ---------------------------------------------------------------------------------------------
-#ifndef FDR_SWAP0
-#define FDR_SWAP0 1  // v_permlane32_swap exchange behind a radix-2 first step (8192-point transforms on the 16-value core)
-#endif
-// The one-group row kernels (a workgroup lives for one 4-row group) hold 8 values per thread (radix-8 steps) -- except for
-// rows of FDR_ROWS_ONE_V16_MIN .. FDR_ROWS_ONE_V16_MAX points (log2), which take 16 (radix-16 steps: two LDS exchanges
-// instead of three per 4096-point transform, half the threads).  Measured on MI355X (passbench, 24 x 4096^2, 4 images per
-// launch, us per image): A 25.7 -> 25.2, C1 18.7 -> 17.2, C2 23.9 -> 23.1; at 2048 / 1024 points the 16-value form is slower
-// (fewer waves per transform: 2048^2 C2 6.8 -> 7.3; one 1024^2 image 26.0 -> 30.1 us), so it starts at 4096.
-// The inverse kernels of that form own ONE exchange buffer per thread group (FDR_ROWS_INV_NBUF1_MIN: the two packed pairs
-// hand their mirrored halves over one after the other, the exchanges take a second barrier): 37 KB instead of 74 KB of LDS,
-// four 256-thread workgroups per CU instead of two -- C1 17.2 -> 14.7 us per 4096^2 image (0.45 -> 0.57 of the roofline).
-#ifndef FDR_ROWS_ONE_V16_MIN
-#define FDR_ROWS_ONE_V16_MIN 12
-#endif
-#ifndef FDR_ROWS_ONE_V16_MAX
-#define FDR_ROWS_ONE_V16_MAX 13
-#endif
-#ifndef FDR_ROWS_INV_NBUF1_MIN
-#define FDR_ROWS_INV_NBUF1_MIN 10  // (wherever the inverse kernels hold 16 values per thread)
-#endif
-// (The FORWARD kernel with one buffer -- pairs separated and stored one after the other, a lane pair writing the 64-byte half
-// of a line that its rows 2b, 2b+1 make up, four workgroups per CU -- was measured too: pass A 25.5 -> 28.5 us per 4096^2 image;
-// half-line stores cost more than the occupancy gains.  The same with the lines of both pairs held in registers (2 x 4 items
-// of 32 bytes per lane) so that the stores stay whole lines: 25.5 -> 25.2 us -- pass A is not bound by its occupancy.  Not kept.
-// Non-temporal stores of the spectrum (it is read again by pass B', but four images do not stay in any cache): 24.0 -> 27.0 us.)
-// The inverse kernels have their own lower bound, FDR_ROWS_INV_V16_MIN = 2048 points: with ONE exchange buffer the 16-value form
-// keeps four workgroups per CU there too -- 2048^2 in launches of 4: C2 6.65 -> 5.94, C1 5.27 -> 5.08 us per image, the two-stream
-// batch 20.89 -> 20.47 us per image (config 5's size; the forward kernel with 16 values at 2048 points: 7.9 -> 8.2 us, not
-// taken); at 1024 points the 16-value inverse kernels are slower (C2 1.83 -> 2.05 us per image in launches of 8).
-#ifndef FDR_ROWS_INV_V16_MIN
-#define FDR_ROWS_INV_V16_MIN 11
-#endif
+// One-group row kernels (a workgroup lives for one 4-row group).
 template <int LOGL, bool INV = false>
 struct Rows4PackGeom {
-    static constexpr int LOGV = (LOGL <= FDR_ROWS_ONE_V16_MAX && LOGL >= (INV ? FDR_ROWS_INV_V16_MIN : FDR_ROWS_ONE_V16_MIN)) ? 4 : 3;
+    // values per thread (log2): 16 (radix-16 steps) from 4096 points on, for the inverse kernels from 2048 points on;
+    // 8 below (LAB_NOTES "row kernel width")
+    static constexpr int LOGV = LOGL >= (INV ? 11 : 12) ? 4 : 3;
     using St = Steps<LOGL, LOGV>;
     static constexpr int T = St::T;
     static constexpr int G = T >= 256 ? 1 : 256 / T;
     static constexpr int THREADS = T * G;
-    // inverse kernels with ONE exchange buffer: as many workgroups per CU as the LDS admits, registers capped to match
+    // inverse kernels with 16 values per thread own ONE exchange buffer per thread group: the two packed pairs hand their
+    // mirrored halves over one after the other (rows4_pack_mirror), so that more workgroups fit a CU; as many workgroups
+    // per CU as the LDS admits, registers capped to match
+    static constexpr bool ONE_BUF = INV && LOGV == 4;
     static constexpr int INV_LDS = G * St::BUF * 8;
-    static constexpr int INV_WG_PER_CU = (INV && LOGL >= FDR_ROWS_INV_NBUF1_MIN && LOGV == 4) ? ((160 * 1024) / INV_LDS > 4 ? 4 : (160 * 1024) / INV_LDS) : 1;
+    static constexpr int INV_WG_PER_CU = ONE_BUF ? ((160 * 1024) / INV_LDS > 4 ? 4 : (160 * 1024) / INV_LDS) : 1;
     static constexpr int INV_WAVES_PER_SIMD = INV_WG_PER_CU * THREADS / 256 > 0 ? (INV_WG_PER_CU * THREADS / 256 > 8 ? 8 : INV_WG_PER_CU * THREADS / 256) : 1;
 };
 
 // Reads every register of a prefetched set through an empty asm: the compiler places the wait for those loads HERE (with
 // the exact vmcnt for this point of the program) and treats them as landed afterwards.  Used at the bottom of the
-// persistent loops, right behind the stores of the group just finished: the prefetch is older than those stores, so the
+// persistent loop, right behind the stores of the group just finished: the prefetch is older than those stores, so the
 // wait is vmcnt(#stores) and the stores keep draining; left to the first use (copies at the loop top, where the state
 // of the first iteration merges in) the compiler emits vmcnt(0..1) and the stores drain before the next transform.
 template <int R, int C>
@@ -94,13 +68,6 @@ __device__ __forceinline__ void landed_f(const float (&d)[R][C]) {
     for (int r = 0; r < R; ++r)
 #pragma unroll
         for (int c = 0; c < C; c += 4) asm volatile("" ::"v"(d[r][c]), "v"(d[r][c + 1]), "v"(d[r][c + 2]), "v"(d[r][c + 3]));
-}
-template <int R, int C>
-__device__ __forceinline__ void landed_f2(const float2 (&d)[R][C]) {
-#pragma unroll
-    for (int r = 0; r < R; ++r)
-#pragma unroll
-        for (int c = 0; c < C; c += 2) asm volatile("" ::"v"(d[r][c].x), "v"(d[r][c].y), "v"(d[r][c + 1].x), "v"(d[r][c + 1].y));
 }
 
 
@@ -118,7 +85,7 @@ __global__ __launch_bounds__(Rows4PackGeom<LOGL>::THREADS) void fft_rows4_fwd_pa
     using Geo = Rows4PackGeom<LOGL>;
     using St = typename Geo::St;
     constexpr int G = Geo::G, T = St::T, L = St::L;
-    using Core = FftCore<LOGL, 2, 2, PolicyFast, Geo::LOGV, (St::lr(0) == 1 && T >= 64 && FDR_SWAP0)>;
+    using Core = FftCore<LOGL, 2, 2, PolicyFast, Geo::LOGV, (St::lr(0) == 1 && T >= 64)>;
     __shared__ float2 lds[G * 2 * St::BUF];
     const int g = threadIdx.x >> St::LOGT, tid = Core::thread_index(threadIdx.x & (T - 1));
     float2* grp_lds = lds + g * 2 * St::BUF;
@@ -245,46 +212,29 @@ __global__ __launch_bounds__(Rows4PackGeom<LOGL>::THREADS) void fft_rows4_fwd_pa
 }
 
 // ---------------------------------------------------------------------------------------------
-// Persistent form of pass A (rows of 2048 points and more: one thread group = one workgroup).  A launch of the kernel
-// above runs in lockstep -- every workgroup loads, then every workgroup transforms, then every workgroup stores -- so
-// HBM idles while the CUs compute and the CUs idle while HBM streams (measured: 18 us per round of 512 workgroups at
-// 4096^2 = 10.9 us of memory time + 7 us of transform, nothing overlapped).  Here a workgroup walks over its row groups
-// and requests the NEXT group's four image rows (4 V floats per thread) before it transforms the current one; the
-// stores of the current group drain behind the next group's transform.  The prefetch is unconditional (clamped
-// addresses, collapsed onto one element when there is no next group; zero padding is applied when the values are
-// packed): a conditional load would make the compiler wait for it right away (lesson 1).
-//   LOGV = 3: 8 values per thread, T = L/8 threads, two workgroups per CU at 4096 points (2 x 74 KB of LDS)
-//   LOGV = 4: 16 values per thread, T = L/16 threads: 8192-point rows as ONE 512-thread workgroup per CU with a
-//             256-register budget (the 8-value form needs 1024 threads at 128 registers and cannot hold a prefetch)
+// Persistent form of pass A (8192-point rows: one thread group = one workgroup).  A launch of the kernel above runs in
+// lockstep -- every workgroup loads, then every workgroup transforms, then every workgroup stores -- so HBM idles while
+// the CUs compute and the CUs idle while HBM streams.  Here a workgroup walks over its row groups and requests the NEXT
+// group's four image rows (4 V floats per thread) before it transforms the current one; the stores of the current group
+// drain behind the next group's transform.  The prefetch is unconditional (clamped addresses, collapsed onto one element
+// when there is no next group; zero padding is applied when the values are packed): a conditional load would make the
+// compiler wait for it right away.
+// 16 values per thread, T = L/16 threads: 8192-point rows as ONE 512-thread workgroup per CU with a 256-register budget
+// (the 8-value form needs 1024 threads at 128 registers and cannot hold a prefetch).  Shorter rows gain nothing from
+// the persistent form (LAB_NOTES "persistent row passes").
 // ---------------------------------------------------------------------------------------------
-#ifndef FDR_ROWS12_LOGV
-#define FDR_ROWS12_LOGV 3  // values per thread (log2) of the persistent row passes for rows of 4096 points (A/B builds)
-#endif
-// Shortest rows (log2) that take the persistent form.  Measured on MI355X (passbench, 24 x 4096^2 / 6 x 8192^2 / 32 x
-// 2048^2, us per image, one-group-per-workgroup kernel vs persistent):  8192: A 144.6 -> 121.7, C' 155.2 -> 143.1;
-// 4096: A 34.7 -> 36.2, C' 31.2 -> 34.1;  2048 (4 images per launch): A 8.1 -> 9.0, C' 6.9 -> 8.3.  With the transform
-// compiled out the 4096^2 row passes take 28.5 / 23.8 us: only 6-7 us of transform are exposed there, less than the
-// persistent form's own cost (dummy prefetch, barrier, fewer independent workgroups), so it is used for 8192-point rows
-// only, where the alternative is a 1024-thread workgroup alone on its CU.
-#ifndef FDR_ROWS_PERS_MIN_LOG
-#define FDR_ROWS_PERS_MIN_LOG 13
-#endif
-// The INVERSE passes (C', C1, C2) stopped using it late in round 3: at 8192 points the one-group kernel with 16 values per
-// thread, ONE exchange buffer (two 512-thread workgroups per CU instead of one persistent workgroup) and whole-row loads
-// (FDR_ROWS_LOAD32) beats the persistent kernel -- C1 76.3 -> 65.2, C2 106.3 -> 100.3 us per 8192^2 image, the two-stream batch
-// 426.9 -> 413.7 us per image.  The persistent inverse kernel stays for A/B builds (-DFDR_ROWS_INV_PERS_MIN_LOG=13).
-#ifndef FDR_ROWS_INV_PERS_MIN_LOG
-#define FDR_ROWS_INV_PERS_MIN_LOG 14
-#endif
+constexpr int kRowsFwdPersMinLog = 13;  // shortest rows (log2) whose forward pass is persistent
+constexpr int kRowsFwdPersLogV = 4;     // values per thread (log2) of the persistent forward kernel
 template <int LOGL, int LOGV>
 struct RowsPersGeom {
     using St = Steps<LOGL, LOGV>;
     static constexpr int T = St::T;
     static_assert(T >= 256, "one thread group per workgroup");
+    static_assert(LOGV == 4, "16 values per thread");
     static constexpr int THREADS = T;
     static constexpr int LDS_BYTES = 2 * St::BUF * 8;
     static constexpr int BY_LDS = (160 * 1024) / LDS_BYTES;
-    static constexpr int BY_REGS = (LOGV == 3 ? 4 : 2) * 256 / THREADS;  // 128 registers (V = 8) or 256 (V = 16) per lane
+    static constexpr int BY_REGS = 2 * 256 / THREADS;  // 256 registers per lane
     static constexpr int WG_PER_CU = BY_LDS < BY_REGS ? (BY_LDS < 1 ? 1 : BY_LDS) : (BY_REGS < 1 ? 1 : BY_REGS);
     static constexpr int WAVES_PER_SIMD = WG_PER_CU * THREADS / 256;
 };
@@ -294,7 +244,7 @@ __global__ __launch_bounds__((RowsPersGeom<LOGL, LOGV>::THREADS), (RowsPersGeom<
     const RowArgs a, const float2* __restrict__ tw_fwd, const int ngroups, const int total) {
     using St = Steps<LOGL, LOGV>;
     constexpr int T = St::T, L = St::L, V = St::V;
-    using Core = FftCore<LOGL, 2, 2, PolicyFast, LOGV, (St::lr(0) == 1 && FDR_SWAP0)>;  // 8192 points: wave-local first exchange
+    using Core = FftCore<LOGL, 2, 2, PolicyFast, LOGV, (St::lr(0) == 1)>;  // 8192 points: wave-local first exchange
     __shared__ float2 lds[2 * St::BUF];
     const int tid = Core::thread_index(threadIdx.x);
     const int nimg = a.batch.nimg > 1 ? a.batch.nimg : 1;
@@ -440,7 +390,7 @@ __global__ __launch_bounds__((RowsPersGeom<LOGL, LOGV>::THREADS), (RowsPersGeom<
 // selects; only lane tid = 0 differs (n = 0: DC, n = L/2: Nyquist -- both live in the packed column 0) and is
 // patched separately.  Addresses: one uniform base per slot + two per-lane 32-bit offsets (direct / mirrored).
 template <int LOGL, bool HALF, class Core>
-__device__ __forceinline__ void rows4_load_raw(const RowArgs& a, int rr, int tid, float2 (&y)[4][Core::V], unsigned scale = 1u) {
+__device__ __forceinline__ void rows4_load_raw(const RowArgs& a, int rr, int tid, float2 (&y)[4][Core::V]) {
     constexpr int L = Steps<LOGL>::L;
     if constexpr (!HALF || LOGL < 5) {  // (half-spectrum plans need N >= 32; smaller instantiations are never launched)
 #pragma unroll
@@ -449,13 +399,12 @@ __device__ __forceinline__ void rows4_load_raw(const RowArgs& a, int rr, int tid
             for (int q = 0; q < Core::RHO0; ++q) {
                 const int s = u * Core::RHO0 + q;
                 const int n = Core::in_index(tid, u, q);
-                const float2* p = a.src_c + ((size_t)(n >> 2) * a.pstride + (size_t)rr * 4 + (n & 3)) * scale;
+                const float2* p = a.src_c + ((size_t)(n >> 2) * a.pstride + (size_t)rr * 4 + (n & 3));
                 y[0][s] = p[0]; y[1][s] = p[4]; y[2][s] = p[8]; y[3][s] = p[12];
             }
     } else {
         static_assert(Core::RHO0 >= 2 && Core::LOGR0 >= 2, "n = t + q Q with Q a multiple of 4");
-        const unsigned ps = (unsigned)a.pstride * scale;  // scale = 0: every address collapses onto rows 0..3 of panel 0 (a prefetch with nothing to fetch)
-        rr = (int)((unsigned)rr * scale);
+        const unsigned ps = (unsigned)a.pstride;
         constexpr unsigned PMID = (unsigned)(L / 8);  // panel of column L/2 (one past the stored panels)
         unsigned off_d[Core::NU0], off_m[Core::NU0];
 #pragma unroll
@@ -463,11 +412,11 @@ __device__ __forceinline__ void rows4_load_raw(const RowArgs& a, int rr, int tid
             const unsigned t = (unsigned)(tid + u * Core::T);        // n = t + q Q,  Q = 2^LOGR0 (a multiple of 4)
             const unsigned ta = t >> 2, tb = t & 3u;
             // direct half: stored column t + qQ -> panel qQ/4 + ta, column tb
-            off_d[u] = ta * ps + tb * scale + (unsigned)rr * 4u;
+            off_d[u] = ta * ps + tb + (unsigned)rr * 4u;
             // mirrored half: stored column (RHO0 - q) Q - t -> panel (RHO0-q)Q/4 - ta - (tb != 0), column (4 - tb) & 3,
             // relative to q = RHO0/2 (panel L/8)
             const unsigned pm = PMID - ta - (tb != 0u ? 1u : 0u);     // panel of the mirrored column at q = RHO0/2
-            off_m[u] = pm * ps + ((4u - tb) & 3u) * scale + (unsigned)rr * 4u;
+            off_m[u] = pm * ps + ((4u - tb) & 3u) + (unsigned)rr * 4u;
         }
         auto load_slot = [&](int u, int q) __attribute__((always_inline)) {
             const int s = u * Core::RHO0 + q;
@@ -490,7 +439,7 @@ __device__ __forceinline__ void rows4_load_raw(const RowArgs& a, int rr, int tid
         // Issue order: every stored line is read twice by the workgroup, once for a direct slot and once for the mirrored
         // slot that covers the same block of panels -- direct (u, q) and mirrored (NU0-1-u, RHO0-1-q).  Requested back to
         // back the second touch finds the line in (or on its way into) L1 / L2; in slot order the two are half a tile of
-        // loads apart and the second one goes out to the fabric again (measured at 8192^2: 372 MB read for 268 MB stored).
+        // loads apart and the second one goes out to the fabric again (LAB_NOTES "pass C' reads").
 #pragma unroll
         for (int u = 0; u < Core::NU0; ++u)
 #pragma unroll
@@ -535,48 +484,21 @@ __device__ __forceinline__ void rows4_pack(int tid, const float2 (&y)[4][Core::V
 // the gathers of rows4_load_raw, every stored line requested once), forms Z[n] for itself and Z[N-n] for whichever
 // thread owns index N-n, and hands the latter over through LDS in natural order (the exchange buffers are idle at that
 // point): 4 V / 8 writes + reads per thread and two barriers, against V/2 x 4 eight-byte gathers that went out to the
-// fabric a second time (fabric reads of pass C' measured at 1.10x / 1.45x the stored bytes at 4096^2 / 8192^2).
+// fabric a second time (LAB_NOTES "pass C' reads").
 //   y[row][j], j = u (RHO0/2) + q : stored column in_index(tid, u, q), q < RHO0/2
 // ---------------------------------------------------------------------------------------------
-// How the four rows reach the registers (round 3).  The transform wants lane t to hold COLUMN t & 3 of the four rows of its
-// panel; loaded that way every lane issues four 8-byte loads and a 128-byte line (4 rows x 4 columns of a panel) is requested
-// in sixteen pieces -- `tools/microbench/rmw_bench` (h) / (i): that gather reads a 4096^2 half spectrum at 4.7 TB/s, the same
-// lines requested as ONE 32-byte row of the panel per lane (a quad of lanes = the whole line) at 6.7 TB/s, at any occupancy.
-// So lane t loads ROW t & 3 -- four columns, two 16-byte loads -- and the quad transposes its 4 x 4 block in registers: two
-// rounds of `v_cndmask_b32_dpp` (quad_perm [1,0,3,2], then [2,3,0,1]), 16 VALU instructions per panel and lane, no LDS.
-// Measured (passbench, A/B builds on one box): with the transforms compiled out C1 14.5 -> 11.0 and C2 29.9 -> 24.1 us per
-// 4096^2 image; with them the passes alone do not move (C1 13.3 -> 13.8: four waves per SIMD keep the VALU 60-70 % busy and the
-// transposes are VALU work) but the two-stream batch does, 87.1 -> 86.2 us per image (twice: +1.1 / +1.6 %), because the
-// other stream's passes get the memory system sooner.  Rows of 2048 points and fewer: 1-2 % slower, so FDR_ROWS_LOAD32 applies
-// to 4096- and 8192-point rows (FDR_ROWS_LOAD32_LOG .. _MAX); at 8192 points it is what lets the one-group kernel fit 128
-// registers (the serialised transposes bound the live set; the 8-byte gathers spilled 13-22 registers there).
-#ifndef FDR_ROWS_LOAD32
-#define FDR_ROWS_LOAD32 1
-#endif
-#ifndef FDR_ROWS_LOAD32_LOG
-#define FDR_ROWS_LOAD32_LOG 12
-#endif
-#ifndef FDR_ROWS_LOAD32_LOG_MAX
-#define FDR_ROWS_LOAD32_LOG_MAX 13
-#endif
-template <int CTRL>
-__device__ __forceinline__ float2 quad_swap(float2 v) {  // the value the lane CTRL points at holds (a permutation inside every quad)
-#if defined(__HIP_DEVICE_COMPILE__)
-    const int x = __builtin_amdgcn_mov_dpp(__float_as_int(v.x), CTRL, 0xF, 0xF, false);  // (every lane is written: no `old` value)
-    const int y = __builtin_amdgcn_mov_dpp(__float_as_int(v.y), CTRL, 0xF, 0xF, false);
-    return make_float2(__int_as_float(x), __int_as_float(y));
-#else
-    return v;
-#endif
-}
+// How the four rows reach the registers at 4096 and 8192 points.  The transform wants lane t to hold COLUMN t & 3 of the
+// four rows of its panel; loaded that way every lane issues four 8-byte loads and a 128-byte line (4 rows x 4 columns of a
+// panel) is requested in sixteen pieces.  Instead lane t loads ROW t & 3 -- four columns, two 16-byte loads, a quad of lanes
+// requests the whole line -- and the quad transposes its 4 x 4 block in registers: two rounds of `v_cndmask_b32_dpp`
+// (quad_perm [1,0,3,2], then [2,3,0,1]), 16 VALU instructions per panel and lane, no LDS.  Shorter rows keep the gathers
+// (LAB_NOTES "row loads").
+
 // r[c] = (row l, column c) on lane l of the quad  ->  q[r] = (row r, column l)
-#ifndef FDR_QUAD_ASM
-#define FDR_QUAD_ASM 1
-#endif
 // d = (lane in MASK) ? keep : (value of `from` on the lane quad_perm points at), both halves of two float2: four
-// v_cndmask_b32_dpp (select and cross-lane read in ONE instruction; hipcc emits v_mov_b32_dpp + v_cndmask_b32 for the C form
-// below, twice the VALU work in a pass that is short of VALU issue slots).  s_nop 1: a DPP operand written by the
-// preceding VALU instruction needs two wait states, and the hazard recogniser does not look into inline asm.
+// v_cndmask_b32_dpp (select and cross-lane read in ONE instruction; hipcc emits v_mov_b32_dpp + v_cndmask_b32 for the
+// same thing written in C, twice the VALU work).  s_nop 1: a DPP operand written by the preceding VALU instruction needs
+// two wait states, and the hazard recogniser does not look into inline asm.
 #define FDR_QUAD_SEL(MASK, PERM, d0, d1, from0, from1, keep0, keep1)                                                        \
     asm("s_nop 1\n\ts_mov_b32 vcc_lo, " MASK "\n\ts_mov_b32 vcc_hi, " MASK "\n\t"                                          \
         "v_cndmask_b32_dpp %0, %4, %8, vcc quad_perm:" PERM " row_mask:0xf bank_mask:0xf\n\t"                              \
@@ -586,38 +508,30 @@ __device__ __forceinline__ float2 quad_swap(float2 v) {  // the value the lane C
         : "=&v"(d0.x), "=&v"(d0.y), "=&v"(d1.x), "=&v"(d1.y)                                                               \
         : "v"(from0.x), "v"(from0.y), "v"(from1.x), "v"(from1.y), "v"(keep0.x), "v"(keep0.y), "v"(keep1.x), "v"(keep1.y)   \
         : "vcc")
-__device__ __forceinline__ void quad_transpose(int lane, const float2 (&r)[4], float2& q0, float2& q1, float2& q2, float2& q3) {
-#if FDR_QUAD_ASM && defined(__HIP_DEVICE_COMPILE__)
-    (void)lane;  // (the masks below are the physical lane's low bits, which the logical thread index keeps)
+// (the masks are the physical lane's low bits, which the logical thread index keeps)
+__device__ __forceinline__ void quad_transpose(const float2 (&r)[4], float2& q0, float2& q1, float2& q2, float2& q3) {
+#if defined(__HIP_DEVICE_COMPILE__)
     float2 a00, a01, a10, a11;
     FDR_QUAD_SEL("0x55555555", "[1,0,3,2]", a00, a10, r[1], r[3], r[0], r[2]);  // even lanes keep columns 0 / 2, odd lanes take the
     FDR_QUAD_SEL("0xaaaaaaaa", "[1,0,3,2]", a01, a11, r[0], r[2], r[1], r[3]);  // neighbour's 1 / 3 (and the other way round)
     FDR_QUAD_SEL("0x33333333", "[2,3,0,1]", q0, q1, a10, a11, a00, a01);
     FDR_QUAD_SEL("0xcccccccc", "[2,3,0,1]", q2, q3, a00, a01, a10, a11);
 #else
-    constexpr int X1 = 0xB1, X2 = 0x4E;  // quad_perm [1,0,3,2] (lane ^ 1), [2,3,0,1] (lane ^ 2)
-    const bool odd = (lane & 1) != 0, hi = (lane & 2) != 0;
-    const float2 s0 = quad_swap<X1>(r[0]), s1 = quad_swap<X1>(r[1]), s2 = quad_swap<X1>(r[2]), s3 = quad_swap<X1>(r[3]);
-    const float2 a00 = odd ? s1 : r[0], a01 = odd ? r[1] : s0;  // column (lane & 1) of rows 2 j, 2 j + 1 (j = lane / 2) ...
-    const float2 a10 = odd ? s3 : r[2], a11 = odd ? r[3] : s2;  // ... and column 2 + (lane & 1)
-    const float2 t00 = quad_swap<X2>(a00), t01 = quad_swap<X2>(a01), t10 = quad_swap<X2>(a10), t11 = quad_swap<X2>(a11);
-    q0 = hi ? t10 : a00; q1 = hi ? t11 : a01;
-    q2 = hi ? a10 : t00; q3 = hi ? a11 : t01;
+    (void)r; (void)q0; (void)q1; (void)q2; (void)q3;  // host pass of the translation unit: device code only
 #endif
 }
 
 template <int LOGL, class Core>
-__device__ __forceinline__ void rows4_load_direct(const RowArgs& a, int rr, int tid, float2 (&y)[4][Core::V / 2], unsigned scale = 1u) {
+__device__ __forceinline__ void rows4_load_direct(const RowArgs& a, int rr, int tid, float2 (&y)[4][Core::V / 2]) {
     static_assert(Core::RHO0 >= 2 && Core::LOGR0 >= 2, "n = t + q Q with Q a multiple of 4");
     constexpr int HQ = Core::RHO0 / 2;
-    constexpr bool kRowLoads = FDR_ROWS_LOAD32 && LOGL >= FDR_ROWS_LOAD32_LOG && LOGL <= FDR_ROWS_LOAD32_LOG_MAX;
-    const unsigned ps = (unsigned)a.pstride * scale;  // scale = 0: every address collapses onto rows 0..3 of panel 0
-    rr = (int)((unsigned)rr * scale);
+    constexpr bool kRowLoads = LOGL >= 12;  // whole 32-byte rows of a panel + quad transpose (see above)
+    const unsigned ps = (unsigned)a.pstride;
 #pragma unroll
     for (int u = 0; u < Core::NU0; ++u) {
         const unsigned t = (unsigned)(tid + u * Core::T);  // stored column t + q Q -> panel q Q / 4 + t / 4, column t & 3
         // kRowLoads: row rr + (t & 3) of the panel, its 4 columns; else column t & 3 of rows rr .. rr + 3
-        const unsigned off = kRowLoads ? (t >> 2) * ps + ((unsigned)rr + (t & 3u) * scale) * 4u : (t >> 2) * ps + (t & 3u) * scale + (unsigned)rr * 4u;
+        const unsigned off = kRowLoads ? (t >> 2) * ps + ((unsigned)rr + (t & 3u)) * 4u : (t >> 2) * ps + (t & 3u) + (unsigned)rr * 4u;
 #pragma unroll
         for (int q = 0; q < HQ; ++q) {
             const int j = u * HQ + q;
@@ -646,7 +560,7 @@ __device__ __forceinline__ void rows4_load_direct(const RowArgs& a, int rr, int 
                 asm volatile("" : "+v"(y[0][j].x), "+v"(y[0][j].y), "+v"(y[1][j].x), "+v"(y[1][j].y), "+v"(y[2][j].x), "+v"(y[2][j].y),
                              "+v"(y[3][j].x), "+v"(y[3][j].y), "+v"(y[0][j - 1].x), "+v"(y[1][j - 1].y), "+v"(y[2][j - 1].x), "+v"(y[3][j - 1].y));
             const float2 r[4] = {y[0][j], y[1][j], y[2][j], y[3][j]};
-            quad_transpose(tid, r, y[0][j], y[1][j], y[2][j], y[3][j]);
+            quad_transpose(r, y[0][j], y[1][j], y[2][j], y[3][j]);
         }
     }
 #endif
@@ -828,8 +742,8 @@ __global__ __launch_bounds__((Rows4PackGeom<LOGL, true>::THREADS), (HALF ? Rows4
     using Geo = Rows4PackGeom<LOGL, true>;
     using St = typename Geo::St;
     constexpr int G = Geo::G, T = St::T;
-    constexpr int NBUF = (HALF && LOGL >= FDR_ROWS_INV_NBUF1_MIN && Geo::LOGV == 4) ? 1 : 2;  // 1: one exchange buffer per thread group (more workgroups per CU)
-    using Core = FftCore<LOGL, 2, NBUF, PolicyFast, Geo::LOGV, (St::lr(0) == 1 && T >= 64 && FDR_SWAP0)>;
+    constexpr int NBUF = (HALF && Geo::ONE_BUF) ? 1 : 2;  // 1: one exchange buffer per thread group (more workgroups per CU)
+    using Core = FftCore<LOGL, 2, NBUF, PolicyFast, Geo::LOGV, (St::lr(0) == 1 && T >= 64)>;
     __shared__ float2 lds[G * NBUF * St::BUF];
     const int g = threadIdx.x >> St::LOGT, tid = Core::thread_index(threadIdx.x & (T - 1));
     const int M = a.M;
@@ -845,7 +759,7 @@ __global__ __launch_bounds__((Rows4PackGeom<LOGL, true>::THREADS), (HALF ? Rows4
         float2 y[4][Core::V / 2];
         rows4_load_direct<LOGL, Core>(a, rr, tid, y);
         // pass C2: the partials are folded BEHIND the group's own loads (a workgroup lives for one group here: a fold in
-        // front of them adds its full memory latency to every workgroup -- measured +6 us per 4096^2 image)
+        // front of them adds its full memory latency to every workgroup)
         if constexpr (OUT == 2) block_fold_partials(a.mm_part, a.n_part, fscale, fshift);
         rows4_pack_mirror<LOGL, Core, NBUF == 1>(tid, y, z, lds + g * NBUF * St::BUF);
     } else {
@@ -863,83 +777,6 @@ __global__ __launch_bounds__((Rows4PackGeom<LOGL, true>::THREADS), (HALF ? Rows4
 }
 
 // ---------------------------------------------------------------------------------------------
-// Persistent form of pass C' (see fft_rows4_fwd_pers_kernel): the raw half spectrum of the NEXT 4-row group is
-// requested (rows4_load_raw into y) before the current group is transformed and stored.  grid (workgroups, images):
-// a workgroup stays inside one image, so it writes ONE (min, max) partial for all its groups.
-// ---------------------------------------------------------------------------------------------
-template <int LOGL, int LOGV, bool HALF, int OUT = 0>
-__global__ __launch_bounds__((RowsPersGeom<LOGL, LOGV>::THREADS), (RowsPersGeom<LOGL, LOGV>::WAVES_PER_SIMD)) void fft_rows4_inv_pers_kernel(
-    const RowArgs a0, const float2* __restrict__ tw_fwd, const int ngroups) {
-    RowArgs a = a0;
-    if (a0.batch.nimg > 1) {  // blockIdx.y = image
-        a.src_c = pick_image(a0.batch.spec, blockIdx.y);
-        if constexpr (OUT == 0) a.dst_real = pick_image(a0.batch.raw, blockIdx.y);
-        if constexpr (OUT == 2) a.out = pick_image(a0.batch.out, blockIdx.y);
-        a.mm_part = pick_image(a0.batch.mm_part, blockIdx.y);
-    }
-    float fscale = 0.f, fshift = 0.f;
-    if constexpr (OUT == 2) block_fold_partials(a.mm_part, a.n_part, fscale, fshift);
-    using St = Steps<LOGL, LOGV>;
-    constexpr int V = St::V;
-    using Core = FftCore<LOGL, 2, 2, PolicyFast, LOGV, (St::lr(0) == 1 && FDR_SWAP0)>;  // 8192 points: wave-local first exchange
-    __shared__ float2 lds[2 * St::BUF];
-    const int tid = Core::thread_index(threadIdx.x);
-
-    typename Core::Bases bases;
-    Core::init_bases(bases, tw_fwd, tid);
-
-    float mn = __builtin_inff(), mx = -__builtin_inff();
-    constexpr bool MIRROR = HALF;  // direct half from memory, mirrored half through LDS (rows4_pack_mirror)
-    float2 y[4][MIRROR ? V / 2 : V], z[2][V];
-    auto request = [&](int g, unsigned scale) __attribute__((always_inline)) {
-        int tl = tid;  // opaque copy: the per-lane panel offsets are recomputed per group instead of living in ~16 registers
-        asm volatile("" : "+v"(tl));
-        if constexpr (MIRROR) rows4_load_direct<LOGL, Core>(a, g * 4, tl, y, scale);
-        else rows4_load_raw<LOGL, HALF, Core>(a, g * 4, tl, y, scale);
-    };
-    auto pack = [&]() __attribute__((always_inline)) {
-        if constexpr (MIRROR) rows4_pack_mirror<LOGL, Core>(tid, y, z, lds);
-        else rows4_pack<LOGL, HALF, Core>(tid, y, z);
-    };
-    auto body = [&](int g) __attribute__((always_inline)) {
-        {
-            int tr = tid;  // opaque copy: the exchange addresses are recomputed per group, not carried (and spilled) across the loop
-            asm volatile("" : "+v"(tr));
-            Core::template run<0, true>(z, lds, tw_fwd, bases, tr);
-        }
-        const int r0 = g * 4;
-        int tq = tid;  // opaque copy: keeps the store addresses from being hoisted out of the group loop
-        asm volatile("" : "+v"(tq));
-        rows4_inv_epilogue<Core, OUT, V>(a, r0, tq, z, fscale, fshift, mn, mx);
-    };
-    // loop shape as in fft_rows4_fwd_pers_kernel: the prefetch is waited for at the bottom (pack), behind the stores
-    int grp = blockIdx.x;  // (the grid never exceeds the number of groups)
-    request(grp, 1u);
-    landed_f2(y);
-    pack();
-    while (true) {
-        const int gn = grp + (int)gridDim.x;
-        const bool more = gn < ngroups;
-        if constexpr (LOGV == 3) {
-            // 128-register budget: the three hoisted twiddle bases do not survive the loop in registers; fetched again
-            // here (L1 hits), BEFORE the prefetch is issued -- a reload behind it (a spill slot is vector memory too)
-            // could only be waited for together with the whole prefetch
-            int tb = tid;
-            asm volatile("" : "+v"(tb));
-            Core::init_bases(bases, tw_fwd, tb);
-        }
-        request(more ? gn : 0, more ? 1u : 0u);
-        body(grp);
-        if (!more) break;
-        landed_f2(y);     // wait for the prefetch here, behind this group's stores
-        __syncthreads();  // keeps the two transforms' LDS traffic apart
-        pack();
-        grp = gn;
-    }
-    if constexpr (OUT != 2) block_minmax_store(mn, mx, a.mm_part, (int)blockIdx.x);
-}
-
-// ---------------------------------------------------------------------------------------------
 // Row passes for ONE small image (single-image calls, rows of 256 .. 2048 points, at most 2048 rows; BASELINE config 2).
 // A lone 1024^2 image is 256 four-row groups: the kernels above give each group to ONE thread group that runs its two
 // packed transforms one after the other (128 workgroups of two groups at 1024 points), and with nothing else in flight the
@@ -947,21 +784,18 @@ __global__ __launch_bounds__((RowsPersGeom<LOGL, LOGV>::THREADS), (RowsPersGeom<
 // workgroup (B = 1 transform each, twice the waves on half the chain, one workgroup per group: 256 of them at 1024^2); the
 // step plan, policy and pack / separate formulas are those of the packed kernels, so the bits are the same.
 // ---------------------------------------------------------------------------------------------
-#ifndef FDR_ROWS_SPLIT
-#define FDR_ROWS_SPLIT 1
-#endif
-// (INV: the inverse kernel follows the batched inverse kernels' step plan -- 16 values per thread from FDR_ROWS_INV_V16_MIN points
-// on -- so that ONE image restored alone and the same image inside a batch come out with identical bits.)
+// (INV: the inverse kernel follows the batched inverse kernels' step plan (Rows4PackGeom<LOGL, true>::LOGV), so that ONE
+// image restored alone and the same image inside a batch come out with identical bits.)
 template <int LOGL, bool INV = false>
 struct RowsSplitGeom {
     static constexpr int LOGV = Rows4PackGeom<LOGL, INV>::LOGV;
     using St = Steps<LOGL, LOGV>;
     static constexpr int T = St::T;
     static constexpr int THREADS = 2 * T;
-    static constexpr bool SWAP = St::lr(0) == 1 && T >= 64 && FDR_SWAP0;
+    static constexpr bool SWAP = St::lr(0) == 1 && T >= 64;
 };
 static inline bool rows4_use_split(int logl, int M, int nimg, int half) {
-    return FDR_ROWS_SPLIT && nimg <= 1 && half && logl >= 8 && logl <= 11 && (M & 3) == 0 && M > 0 && M <= 2048;
+    return nimg <= 1 && half && logl >= 8 && logl <= 11 && (M & 3) == 0 && M > 0 && M <= 2048;
 }
 
 template <int LOGL>
@@ -1126,49 +960,8 @@ __global__ __launch_bounds__((RowsSplitGeom<LOGL, true>::THREADS)) void fft_rows
     if constexpr (OUT != 2) block_minmax_store(mn, mx, a.mm_part, (int)blockIdx.x);
 }
 
-// persistent pass C' is used when a workgroup gets more than one group (else there is nothing to overlap); always for
-// 8192-point rows (see launch_rows4_t)
-template <int LOGL>
-static int rows4_inv_pers_grid(int M, int num_cu, int nimg);
-template <int LOGL>
-static bool rows4_inv_use_pers(int M, int num_cu, int nimg) {
-    if constexpr (LOGL >= 11) {
-        if ((M & 3) != 0) return false;
-        return LOGL >= 13 || rows4_inv_pers_grid<LOGL>(M, num_cu, nimg) < (M + 3) / 4;
-    } else {
-        return false;
-    }
-}
-// persistent pass C': workgroups per image (the number of min/max partials the pass writes for one image)
-template <int LOGL>
-static int rows4_inv_pers_grid(int M, int num_cu, int nimg) {
-    if constexpr (LOGL >= 11) {
-        constexpr int LOGV = LOGL >= 13 ? 4 : (LOGL == 12 ? FDR_ROWS12_LOGV : 3);
-        using PG = RowsPersGeom<LOGL, LOGV>;
-        const int groups = (M + 3) / 4;
-        int g = (num_cu > 0 ? num_cu : 256) * PG::WG_PER_CU / (nimg > 1 ? nimg : 1);
-        if (g < 1) g = 1;
-        return g > groups ? groups : g;
-    } else {
-        return 0;
-    }
-}
-
-#ifndef FDR_ROWS_PERSISTENT
-#define FDR_ROWS_PERSISTENT 1
-#endif
 template <int LOGL, int OUT>
-static hipError_t launch_rows4_inv_t(const RowArgs& a, const float2* tw, hipStream_t s, int groups, int nimg, dim3 grid, dim3 block) {
-    if constexpr (LOGL >= FDR_ROWS_INV_PERS_MIN_LOG && FDR_ROWS_PERSISTENT) {
-        constexpr int LOGV = LOGL >= 13 ? 4 : (LOGL == 12 ? FDR_ROWS12_LOGV : 3);
-        using PG = RowsPersGeom<LOGL, LOGV>;
-        if (rows4_inv_use_pers<LOGL>(a.M, a.num_cu, nimg)) {
-            const dim3 pgrid(rows4_inv_pers_grid<LOGL>(a.M, a.num_cu, nimg), nimg), pblock(PG::THREADS);
-            if (a.half) hipLaunchKernelGGL((fft_rows4_inv_pers_kernel<LOGL, LOGV, true, OUT>), pgrid, pblock, 0, s, a, tw, groups);
-            else if constexpr (OUT == 0) hipLaunchKernelGGL((fft_rows4_inv_pers_kernel<LOGL, LOGV, false, 0>), pgrid, pblock, 0, s, a, tw, groups);
-            return hipGetLastError();
-        }
-    }
+static hipError_t launch_rows4_inv_t(const RowArgs& a, const float2* tw, hipStream_t s, dim3 grid, dim3 block) {
     if (a.half) hipLaunchKernelGGL((fft_rows4_inv_packed_kernel<LOGL, true, OUT>), grid, block, 0, s, a, tw);
     else if constexpr (OUT == 0) hipLaunchKernelGGL((fft_rows4_inv_packed_kernel<LOGL, false, 0>), grid, block, 0, s, a, tw);
     return hipGetLastError();
@@ -1202,15 +995,12 @@ static hipError_t launch_rows4_t(RowIn in, RowOut out, const RowArgs& a, const f
         }
     }
     if (in == ROW_IN_REAL && out == ROW_OUT_COMPLEX) {
-        if constexpr (LOGL >= FDR_ROWS_PERS_MIN_LOG && FDR_ROWS_PERSISTENT) {
-            constexpr int LOGV = LOGL >= 13 ? 4 : (LOGL == 12 ? FDR_ROWS12_LOGV : 3);
+        if constexpr (LOGL >= kRowsFwdPersMinLog) {  // persistent, prefetching form (see fft_rows4_fwd_pers_kernel)
+            constexpr int LOGV = kRowsFwdPersLogV;
             using PG = RowsPersGeom<LOGL, LOGV>;
             const int total = groups * nimg;
             int g = (a.num_cu > 0 ? a.num_cu : 256) * PG::WG_PER_CU;
-            // persistent, prefetching form -- when a workgroup gets more than one group (else there is nothing to overlap
-            // and the one-group-per-workgroup kernel has less to do); always for 8192-point rows, which the 8-value
-            // kernel can only run as 1024-thread workgroups
-            if ((a.M & 3) == 0 && a.src_rows > 0 && a.src_cols > 0 && (total > g || LOGL >= 13)) {
+            if ((a.M & 3) == 0 && a.src_rows > 0 && a.src_cols > 0) {
                 if (g > total) g = total;
                 const bool interior = a.src_rows >= a.M && a.src_cols >= (1 << LOGL);
                 const dim3 pgrid(g), pblock(PG::THREADS);
@@ -1227,13 +1017,13 @@ static hipError_t launch_rows4_t(RowIn in, RowOut out, const RowArgs& a, const f
         if (a.half) hipLaunchKernelGGL((fft_rows4_fwd_packed_kernel<LOGL, true>), grid, block, 0, s, a, tw);
         else hipLaunchKernelGGL((fft_rows4_fwd_packed_kernel<LOGL, false>), grid, block, 0, s, a, tw);
     } else if (in == ROW_IN_COMPLEX && out == ROW_OUT_REAL_MINMAX) {
-        return launch_rows4_inv_t<LOGL, 0>(a, tw, s, groups, nimg, igrid, iblock);
+        return launch_rows4_inv_t<LOGL, 0>(a, tw, s, igrid, iblock);
     } else if (in == ROW_IN_COMPLEX && out == ROW_OUT_MINMAX_ONLY) {
         if (!a.half) return hipErrorInvalidValue;  // two-sweep normalisation: half-spectrum path only
-        return launch_rows4_inv_t<LOGL, 1>(a, tw, s, groups, nimg, igrid, iblock);
+        return launch_rows4_inv_t<LOGL, 1>(a, tw, s, igrid, iblock);
     } else if (in == ROW_IN_COMPLEX && out == ROW_OUT_NORMALIZED) {
         if (!a.half) return hipErrorInvalidValue;
-        return launch_rows4_inv_t<LOGL, 2>(a, tw, s, groups, nimg, igrid, iblock);
+        return launch_rows4_inv_t<LOGL, 2>(a, tw, s, igrid, iblock);
     } else {
         return hipErrorInvalidValue;
     }
@@ -1241,11 +1031,8 @@ static hipError_t launch_rows4_t(RowIn in, RowOut out, const RowArgs& a, const f
 }
 
 template <int LOGL>
-static int rows4_partials_t(int M, int num_cu, int nimg, int half) {
+static int rows4_partials_t(int M, int nimg, int half) {
     if (rows4_use_split(LOGL, M, nimg, half)) return M / 4;  // one workgroup, one partial per 4-row group
-    if constexpr (LOGL >= FDR_ROWS_INV_PERS_MIN_LOG && FDR_ROWS_PERSISTENT) {
-        if (rows4_inv_use_pers<LOGL>(M, num_cu, nimg)) return rows4_inv_pers_grid<LOGL>(M, num_cu, nimg);
-    }
     return ((M + 3) / 4 + Rows4PackGeom<LOGL, true>::G - 1) / Rows4PackGeom<LOGL, true>::G;
 }
 
@@ -1270,8 +1057,8 @@ hipError_t launch_rows4(int logl, RowIn in, RowOut out, const RowArgs& a, const 
     return hipErrorInvalidValue;
 }
 
-int rows4_minmax_partials(int logl, int M, int num_cu, int nimg, int half) {
-    FDR_DISPATCH_LOG(logl, rows4_partials_t<LG>(M, num_cu, nimg, half));
+int rows4_minmax_partials(int logl, int M, int nimg, int half) {
+    FDR_DISPATCH_LOG(logl, rows4_partials_t<LG>(M, nimg, half));
     return 0;
 }
 
@@ -1438,8 +1225,6 @@ __device__ __forceinline__ gchar* uniform_gptr(const void* p) {
     return (gchar*)(((unsigned long long)hi << 32) | lo);
 }
 // 32 bytes at (uniform base) + (32-bit lane byte offset): global_load_dwordx4 v, v_off, s[base:base+1] {offset:16}.
-// (Round 3: the tile loads as non-temporal loads -- to keep the shared filter W in L2 longer -- measured 35.4 -> 35.6 us per
-// 4096^2 image, FDR_WPIECE 2 instead of 4: 36.5 us; neither kept.)
 // (HIP's float4, field by field: with native vector types the two halves reach the register arrays as <2 x float>
 // stores, which SROA does not promote -- the arrays then live in scratch memory.)
 #define FDR_GLOAD32(ub, lane_bytes, a, b, c, d)                                                       \
@@ -1477,7 +1262,7 @@ __device__ __forceinline__ void tile_load(const float2* __restrict__ ubase, unsi
             // keep the two 16-byte halves of a row together in the instruction stream: left alone the scheduler issues the
             // 16 first halves of a tile, then the 16 second halves, and with every wave of an XCD doing the same (8 MB of
             // lines requested before the first second half) part of the lines has left the 4 MiB L2 again by then
-            // (measured: +9 % fabric reads in the 4096-point column pass)
+            // (LAB_NOTES "pass B' tile loads")
             asm volatile("" ::: "memory");
 #endif
         }
@@ -1501,7 +1286,7 @@ __device__ __forceinline__ void tile_store(float2* __restrict__ ubase, unsigned 
 // Reads every register of a prefetched set through an empty asm, so the compiler places the wait for those loads HERE
 // and treats them as landed afterwards.  Used right before the tile's stores are issued: vmcnt counts loads and
 // stores in issue order, so a wait for the spectrum prefetch placed after the stores (where the values are first
-// used) would also wait for the stores to drain -- ~5 us per tile that the next forward transform should hide.
+// used) would also wait for the stores to drain, time that the next forward transform should hide.
 __device__ __forceinline__ void landed(const float2 (&d)[4][8]) {
 #pragma unroll
     for (int b = 0; b < 4; ++b)
@@ -1622,19 +1407,6 @@ __global__ __launch_bounds__(PanelGeom<LOGM>::THREADS, PanelGeom<LOGM>::PIPE_WAV
 // 8192-point columns: 512 threads, one workgroup per CU, no spills (the radix-8 kernel needs 1024 threads at 128
 // VGPRs there).  One tile per workgroup; the tile sequence runs over the images of the launch.
 // ---------------------------------------------------------------------------------------------
-#ifndef FDR_WPIECE
-#define FDR_WPIECE 4
-#endif
-#ifndef FDR_SHARE_W
-#define FDR_SHARE_W 1
-#endif
-#ifndef FDR_COLS12_PACKED
-#define FDR_COLS12_PACKED 1
-#endif
-#ifndef FDR_PARK_BASES
-#define FDR_PARK_BASES 1  // 8192-point column pass: twiddle bases parked in LDS across the filter phase (A/B builds: 0)
-#endif
-
 // Phase stamps of pass B' (timing-only debug builds, -DFDR_DEBUG_STAMPS; read back by tools/microbench/passbench): the
 // shader-clock counter of wave 0 of every workgroup at start / tile landed / forward transform done / filter applied /
 // inverse transform done / stores issued / stores retired.  The waits the "landed" and "retired" stamps need are part of
@@ -1660,7 +1432,7 @@ template <int LOGM>
 struct Panel16Geom {
     static constexpr int T = Steps<LOGM, 4>::T;
     // one panel per workgroup at every size: with short columns (64 or 128 threads per transform) grouping several
-    // panels into a 256-thread workgroup was measured slower (2048^2 x 4 images: 45.1 vs 39.7 us) and leaves CUs idle
+    // panels into a 256-thread workgroup is slower and leaves CUs idle (LAB_NOTES "pass B' tile shape")
     static constexpr int G = 1;
     static constexpr int THREADS = T * G;
 };
@@ -1671,8 +1443,7 @@ __global__ __launch_bounds__(Panel16Geom<LOGM>::THREADS, 2) void fft_cols_panel_
     const int npanels, const int ntiles, const int packed0, const int img_shift) {
     using St = Steps<LOGM, 4>;
     constexpr int G = Panel16Geom<LOGM>::G, T = St::T, M = St::L, V = 16;
-    using Core = FftCore<LOGM, 4, 2, typename std::conditional<(LOGM == 12 && !FDR_COLS12_PACKED), PolicyFastScalar, PolicyFast>::type, 4,
-                         (St::lr(0) == 1 && T >= 64 && FDR_SWAP0)>;  // see PolicyFastScalar; 8192 points: wave-local first exchange
+    using Core = FftCore<LOGM, 4, 2, PolicyFast, 4, (St::lr(0) == 1 && T >= 64)>;  // 8192 points: wave-local first exchange
     __shared__ float2 lds[G * 2 * St::BUF];
     const int g = G == 1 ? 0 : (int)(threadIdx.x >> St::LOGT);
     const int tid = Core::thread_index(threadIdx.x & (T - 1));
@@ -1697,36 +1468,17 @@ __global__ __launch_bounds__(Panel16Geom<LOGM>::THREADS, 2) void fft_cols_panel_
     typename Core::Bases bases;
     Core::init_bases(bases, tw_fwd, tid);
     // 8192 points: the tile fills 128 of the 256 registers a lane has and the filter phase needs the rest, so the hoisted
-    // twiddle bases (one float2 per radix-16 step) did not survive it -- hipcc spilled them in the forward transform and
-    // reloaded them from scratch in the inverse (3 x 8 bytes per lane: 28 bytes of scratch, ~50 MB of HBM traffic per
-    // two-image launch, and three exposed memory round trips).  They are parked in the 12 KB of LDS the exchange buffers
+    // twiddle bases (one float2 per radix-16 step) do not survive it in registers -- left to hipcc they are spilled in the
+    // forward transform and reloaded from scratch in the inverse.  They are parked in the 12 KB of LDS the exchange buffers
     // leave instead and picked up again for the inverse: an LDS read where a scratch load was.
-    constexpr bool kParkBases = (LOGM == 13) && FDR_PARK_BASES;
+    constexpr bool kParkBases = LOGM == 13;
     __shared__ float2 parked[kParkBases ? (St::S - 1) * T : 1];
     if constexpr (kParkBases) {
 #pragma unroll
         for (int j = 1; j < St::S; ++j) parked[(j - 1) * T + tid] = bases.b[j][0];  // (the logical index: one slot per thread)
     }
 
-    // (Delaying the workgroup that landed in the odd wave slots by half a load phase, so that the two workgroups of
-    // a CU alternate between memory and LDS phases, was measured: no gain up to 5 us of delay, slower beyond.  Round 3, the
-    // same across CUs: every other TILE's first-round workgroup started 7 .. 40 us late -- 4096^2 35.1 / 34.0 / 34.4 / 36.5 us,
-    // 8192^2 192.7 / 186.3 / 193.9 / 201.5 us per image at 0 / 7 / 14 / 20 us: the CUs are not in lockstep to begin with.)
-    // (Round 3, built, verified against the tests, measured and not kept -- the code is in the history, commit "Experiments on
-    // pass B'", numbers in DESIGN.md section 5:
-    // (1) a PERSISTENT form, one 256-thread workgroup per CU at one wave per SIMD with the whole filter tile and then the next
-    //     tile prefetched into 128 AGPRs by inline-asm `global_load_dwordx4 a[..]` and hand-placed vmcnt waits -- no spills,
-    //     nothing waited for, but 41.3 against 32.7 us per 4096^2 image: alone on its SIMD a wave exposes every LDS round trip and
-    //     barrier of the two transforms, 20 us per tile against the 16.5 us two co-resident workgroups take per tile between them;
-    // (2) column-pipelined transforms (a transform's LDS round trip behind the next transform's butterflies): +13 % VALU
-    //     instructions, 33.9 against 32.7 us;
-    // (3) the first filter piece requested before the forward transform's LAST exchange: the transform's register peak is
-    //     there, 19 spilled registers, 34.2 against 32.7 us (8192 points: 176.9 against 182.4 us with 23 spilled registers);
-    // (4) the second half of the filter tile by `global_load_lds_dwordx4` into the exchange buffers, idle between the
-    //     transforms, so that all of W is in flight at once (one round trip instead of two, two more barriers): 33.4 against
-    //     32.7 us, 8192 points 186.6 against 179.2 us.
-    // Without its filter (-DFDR_DEBUG_SKIP_W) the pass takes 28.6 us, and `tools/microbench/rmw_bench` moves the pass's
-    // traffic alone -- four 64 MiB images in place plus one shared 64 MiB filter -- in 94-106 us, 24-26.5 us per image.)
+    // (Schedules of this kernel that were built and measured slower are listed in LAB_NOTES "pass B' schedules".)
     float2 v[4][V];
     FDR_STAMP(0);
     tile_load<Core, false>(data, loff, 1u, v);
@@ -1784,10 +1536,10 @@ __global__ __launch_bounds__(Panel16Geom<LOGM>::THREADS, 2) void fft_cols_panel_
     }
     {
         const bool col0_done = packed_tile && g == 0;
-        // W in pieces of PC slots, the next piece requested before the current one is used.  (Measured: requesting the
-        // first pieces before the forward transform costs 27 spilled registers and 5 us; the compiler barriers keep
-        // hipcc from hoisting all 32 loads to the top.)
-        constexpr int PC = FDR_WPIECE;  // slots per piece: 8 VGPRs per slot, two pieces in flight
+        // W in pieces of PC slots, the next piece requested before the current one is used; the compiler barriers keep
+        // hipcc from hoisting all the loads to the top, in front of the forward transform, where they spill
+        // (LAB_NOTES "pass B' filter pieces")
+        constexpr int PC = 4;  // slots per piece: 8 VGPRs per slot, two pieces in flight
         auto wload = [&](int h, float2 (&w)[PC][4]) {
 #pragma unroll
             for (int i = 0; i < PC; ++i) {
@@ -1852,8 +1604,8 @@ __global__ __launch_bounds__(Panel16Geom<LOGM>::THREADS, 2) void fft_cols_panel_
 // ---------------------------------------------------------------------------------------------
 // Pass B' for ONE small image (the single-image call of BASELINE config 2: M <= 2048).  The tile kernels above give a
 // 4-column tile to one thread group (64 threads at 1024 points): with a single image in flight that is 128 one-wave
-// workgroups, each running eight 1024-point transforms back to back on one SIMD -- 10 us of dependent VALU and memory
-// latency on a chip that is 95 % idle (measured 14.2 us event-timed at 1024^2, 9.8 with the transforms compiled out).
+// workgroups, each running eight 1024-point transforms back to back on one SIMD -- a long chain of dependent VALU and
+// memory latency on a chip that is nearly idle (LAB_NOTES "single small image").
 // Here the four columns of a panel go to four thread groups of one workgroup (B = 1 transform per group, same FftCore
 // step plan and policy as the tile kernel of that length, so the bits are the same), the filter is requested together with
 // the spectrum (16 or 8 values per lane leave the registers for it), and nothing is staged.  The thread groups are
@@ -1871,9 +1623,6 @@ struct PanelSplitGeom {
     static constexpr int THREADS = 4 * T;
 };
 
-// (Round 3: the same kernel as the BATCHED pass B' at 4096 points -- 1024 threads per tile, one exchange buffer per column
-// (NBUF = 1, 148 KB: one workgroup per CU), W requested up front, grid over (tile, image) as the tile kernel -- measured 43.3
-// against 34.6 us per image: with one tile in flight per CU nothing overlaps its memory phases.  The tile kernel stays.)
 template <int LOGM, int NBUF = 2>
 __global__ __launch_bounds__(PanelSplitGeom<LOGM>::THREADS) void fft_cols_panel_split_kernel(
     const PanelBatch pb, const float2* __restrict__ filt, const float2* __restrict__ tw_fwd, const unsigned pstride, const int packed0,
@@ -1981,10 +1730,6 @@ __global__ __launch_bounds__(PanelSplitGeom<LOGM>::THREADS) void fft_cols_panel_
     }
 }
 
-#ifndef FDR_COLS_SPLIT
-#define FDR_COLS_SPLIT 1  // single images with 256 .. 2048 rows: one thread group per COLUMN (A/B builds: 0)
-#endif
-
 template <int LOGM>
 static hipError_t launch_cols_panel_t(ColKind kind, const ColArgs& a, const float2* tw, hipStream_t s) {
     using Geo = PanelGeom<LOGM>;
@@ -1998,7 +1743,7 @@ static hipError_t launch_cols_panel_t(ColKind kind, const ColArgs& a, const floa
         PanelBatch pb = a.batch;
         if (pb.nimg <= 0) { pb.nimg = 1; pb.data[0] = a.data; }
         for (int k = pb.nimg; k < kMaxGroup; ++k) pb.data[k] = pb.data[0];
-        if constexpr (FDR_COLS_SPLIT && LOGM >= 8 && LOGM <= 11) {
+        if constexpr (LOGM >= 8 && LOGM <= 11) {
             if (pb.nimg == 1) {  // a single small image: latency, not bandwidth (see fft_cols_panel_split_kernel)
                 hipLaunchKernelGGL((fft_cols_panel_split_kernel<LOGM, 2>), dim3(npanels), dim3(PanelSplitGeom<LOGM>::THREADS), 0, s, pb, a.filt, tw,
                                    (unsigned)ps, a.packed0, -1);
@@ -2008,7 +1753,7 @@ static hipError_t launch_cols_panel_t(ColKind kind, const ColArgs& a, const floa
         if constexpr (LOGM >= 10) {  // 16 values per thread: one workgroup per tile, grid (tiles, images)
             using G16 = Panel16Geom<LOGM>;
             const int nt16 = (npanels + G16::G - 1) / G16::G;
-            const int ishift = FDR_SHARE_W && (nt16 % 8 == 0) ? (pb.nimg == 2 ? 1 : pb.nimg == 4 ? 2 : pb.nimg == 8 ? 3 : -1) : -1;
+            const int ishift = (nt16 % 8 == 0) ? (pb.nimg == 2 ? 1 : pb.nimg == 4 ? 2 : pb.nimg == 8 ? 3 : -1) : -1;
             const dim3 grid16 = ishift < 0 ? dim3(nt16, pb.nimg) : dim3(nt16 * pb.nimg);
             hipLaunchKernelGGL((fft_cols_panel_fused16_kernel<LOGM>), grid16, dim3(G16::THREADS), 0, s, pb, a.filt, tw,
                                (unsigned)ps, npanels, nt16, a.packed0, ishift);

@@ -21,17 +21,11 @@ struct RowGeom {
 
 // INV matters only to the fast policy (it conjugates the hoisted forward twiddles); the parity
 // policy receives a direction-specific table and is instantiated with INV = false only.
-// PANEL = 1 (parity operator since round 4): the complex side(s) are panel-major, so that the column passes work on
+// PANEL = 1 (parity operator): the complex side(s) are panel-major, so that the column passes work on
 // contiguous tiles.  A row then touches 32 bytes (its four columns) of a 128-byte line that it shares with three neighbouring
 // rows; the workgroups of such a 4-row group are placed on one XCD back to back (col_tile_of_block) so that the four
-// partial lines meet in that XCD's L2 and HBM sees whole lines.  (A kernel that gives a thread group FOUR rows -- whole lines,
-// one 32-byte row of a panel per lane and a 4 x 4 transpose inside the quad of lanes, as the fast mode's inverse row passes
-// do -- was built, passed the tests and measured SLOWER at every size: A 61 -> 84, C 63 -> 76 us per 4096^2 image; four
-// parity transforms per thread do not fit 128 registers without spills at 4096 points and more.  The same with 16 values per
-// thread and a radix-16 step of the recurrence tables -- 256 threads per 4-row group at 4096 points, no spills once the rows
-// of a stage are pinned one after the other -- passed every test too and was no better: A 66 -> 67, C 66 -> 83 us at 4096^2,
-// 20 -> 25 / 21 -> 29 us at 2048^2, 235 -> 290 / 381 -> 386 us at 8192^2.  The row passes are not bound by the size of their
-// pieces; the one-row kernels stay.)
+// partial lines meet in that XCD's L2 and HBM sees whole lines.  (Four-row parity kernels were slower: LAB_NOTES
+// "parity row kernels".)
 template <int LOGL, class Pol, int IN, int OUT, bool INV, int PANEL>
 __global__ __launch_bounds__(RowGeom<LOGL>::THREADS) void fft_rows_kernel(const RowArgs a, const float2* __restrict__ tw) {
     using St = Steps<LOGL>;
@@ -59,7 +53,7 @@ __global__ __launch_bounds__(RowGeom<LOGL>::THREADS) void fft_rows_kernel(const 
                 if (active && row < a.src_rows && n < a.src_cols) x.x = a.src_real[(size_t)row * a.src_stride + n];
             } else {
                 // (panel-major: unsigned 32-bit element offsets -- (N/4) panels of 4 M + 16 elements stay below 2^32 -- so that an
-                // access is base + one 32-bit register, not a 64-bit multiply-add per element: 10 % of this kernel's VALU work)
+                // access is base + one 32-bit register, not a 64-bit multiply-add per element)
                 if (active) x = PANEL ? a.src_c[(unsigned)(n >> 2) * (unsigned)a.pstride + (unsigned)row * 4u + (unsigned)(n & 3)] : a.src_c[(size_t)row * L + n];
             }
             v[0][u * Core::RHO0 + q] = x;
