@@ -58,6 +58,17 @@ extern "C" {
                                   getOptimalDFTSize (2^a 3^b 5^c, :153-154) instead of to a power of two.  Reference-shaped
                                   passes (rows, transpose, rows, transpose); both modes use the parity arithmetic.        */
 
+#define FDR_FLAG_MIXED_RADIX 2048u /* fast mode: accept plan dimensions 2^a 3^b 5^c up to 8192 -- the sizes getOptimalDFTSize pads to
+                                     (fdr_optimal_dft_size, fft/fft_serial.cpp:153-154) -- and transform them by mixed-radix (2/3/4/5)
+                                     FFTs on a panel-major full spectrum instead of padding to the next power of two.  Any other size
+                                     is refused with FDR_ERR_ARG before device work; FDR_FLAG_ANY_SIZE is not needed and may be set.
+                                     With both dimensions powers of two the flag has no effect (the power-of-two path and its limits
+                                     hold), so a caller may always pass fdr_optimal_dft_size(rows / cols) with it.  Ignored in parity
+                                     mode.  Refused together with FDR_FLAG_TABLES_ONLY or FDR_FLAG_SIMPLE_PATH on such a plan.
+                                     fdr_plan_set_batching: `group` images alternate over the workspaces one by one (no multi-image
+                                     launches); FDR_OPT_BATCH_GRAPH is accepted and ignored (plain launches) -- as on FDR_FLAG_ANY_SIZE
+                                     plans.  fdr_slab_* refuse a non-power-of-two dimension of such a plan.                       */
+
 /* normalisation area selector for fdr_wiener_* */
 #define FDR_NORM_PADDED 1  /* serial semantics: min/max over the padded M x N area, then crop
                               (serial.cpp:36-38 + fft/fft_serial.cpp:243-246)                 */
@@ -86,7 +97,9 @@ int fdr_optimal_dft_size(int n);
  *    Dimensions: powers of two up to 32768 (a dimension above 8192 is transformed in 8192-point
  *    blocks plus radix-2 stages in global memory: the reference's serial path takes any power
  *    of two, fft/fft_serial.cpp:90-108); with FDR_FLAG_ANY_SIZE also non-powers of two up to
- *    4096 (naive DFT).                                                                    */
+ *    4096 (naive DFT).  In fast mode with FDR_FLAG_MIXED_RADIX: 2^a 3^b 5^c up to 8192 in each
+ *    dimension (mixed-radix FFTs, fast-mode arithmetic); FDR_ERR_ARG otherwise, and the plan
+ *    reports FDR_MODE_FAST.                                                               */
 int fdr_plan_create(int device, int M, int N, int mode, unsigned flags, fdr_plan** out);
 int fdr_plan_destroy(fdr_plan* plan);
 int fdr_plan_dims(const fdr_plan* plan, int* M, int* N, int* mode);

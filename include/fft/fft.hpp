@@ -27,6 +27,7 @@ struct Options {
     int mode = FDR_MODE_FAST;         // FDR_MODE_FAST or FDR_MODE_PARITY (bit-identical FFT arithmetic to fft_serial)
     int norm_area = FDR_NORM_PADDED;  // FDR_NORM_PADDED (./serial semantics) or FDR_NORM_CROPPED (reference ./gpu, fft_gpu.cu:379-381)
     int device = 0;
+    bool mixed_radix = false;         // FDR_MODE_FAST: 2^a 3^b 5^c plan sizes by mixed-radix FFTs (FDR_FLAG_MIXED_RADIX) in wienerDeblur_myfft
 };
 // process-wide defaults of the reference-signature overloads (the drivers' --mode / --norm flags); atomics: reading
 // them from several threads is safe, and no entry point ever changes them behind the caller's back
@@ -182,7 +183,8 @@ inline void wienerDeblur_RGB_naive(std::vector<Mat>& channels, const Mat& psf, f
 // the cropped plane (:243-246).  For the pre-padded channels the drivers pass (serial.cpp:36) pad and crop are no-ops.
 inline Mat wienerDeblur_myfft(const Mat& img, const Mat& psf, float K, const Options& o) {
     const int M = fdr_optimal_dft_size(img.rows), N = fdr_optimal_dft_size(img.cols);
-    const unsigned flags = (isPowerOfTwo(M) && isPowerOfTwo(N)) ? 0u : FDR_FLAG_ANY_SIZE;
+    unsigned flags = (isPowerOfTwo(M) && isPowerOfTwo(N)) ? 0u : FDR_FLAG_ANY_SIZE;
+    if (o.mixed_radix && o.mode == FDR_MODE_FAST) flags |= FDR_FLAG_MIXED_RADIX;
     bool created = false;
     PlanCacheSettle settle_;
     fdr_plan* plan = plan_cache().get(o.device, M, N, o.mode, &created, flags);

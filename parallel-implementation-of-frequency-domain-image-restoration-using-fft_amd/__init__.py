@@ -24,6 +24,7 @@ FLAG_SIMPLE_PATH = 1
 FLAG_FULL_SPECTRUM = 32
 FLAG_ANY_SIZE = 512
 FLAG_TABLES_ONLY = 1024
+FLAG_MIXED_RADIX = 2048
 NORM_PADDED = 1
 NORM_CROPPED = 0
 MAX_PASSES = 16
@@ -457,13 +458,16 @@ def wienerDeblur_myfft(img, psf, K, mode=MODE_PARITY, device=0, norm_area=NORM_P
         return p.wiener(img, norm_area)
 
 
-def wienerDeblur_myfft_unpadded(img, psf, K, mode=MODE_PARITY, device=0):
+def wienerDeblur_myfft_unpadded(img, psf, K, mode=MODE_PARITY, device=0, mixed_radix=False):
     """fft_serial::wienerDeblur_myfft called DIRECTLY on a channel of any size (fft/fft_serial.cpp:141-261): pad to
     getOptimalDFTSize (2^a 3^b 5^c; a non-power-of-two dimension is transformed by the naive DFT, :100-101), restore,
-    crop to the input size, normalise over the cropped plane (:243-246)."""
+    crop to the input size, normalise over the cropped plane (:243-246).  mixed_radix=True with MODE_FAST: the
+    mixed-radix FFTs of FLAG_MIXED_RADIX instead of the naive DFT (dimensions up to 8192)."""
     img = np.asarray(img, dtype=np.float32)
     M, N = getOptimalDFTSize(img.shape[0]), getOptimalDFTSize(img.shape[1])
     flags = 0 if (isPowerOfTwo(M) and isPowerOfTwo(N)) else FLAG_ANY_SIZE
+    if mixed_radix and mode == MODE_FAST:
+        flags |= FLAG_MIXED_RADIX
     with Plan(M, N, mode, device, flags=flags) as p:
         p.set_psf(psf, K)
         return p.wiener(img, NORM_CROPPED)

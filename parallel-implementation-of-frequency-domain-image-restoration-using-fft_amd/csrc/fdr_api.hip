@@ -88,6 +88,47 @@ void build_naive_table(int n, std::vector<float2>& out) {
 }
 constexpr int kMaxNaiveLen = 4096;  // 128 MiB of table
 
+bool is_smooth(int n) {  // 2^a 3^b 5^c
+    if (n <= 0) return false;
+    for (int f : {2, 3, 5})
+        while (n % f == 0) n /= f;
+    return n == 1;
+}
+
+// Stockham schedule of a length 2^a 3^b 5^c (radix 4 first, then 2, 3, 5) and the twiddle table exp(-2 pi i m / L) in two
+// levels (w^m = lo[m mod 64] hi[m / 64], each entry evaluated in double and rounded once); per stage {radix, ns, ceil(2^32 / ns) (0 for ns = 1), L / (ns radix)}
+void build_mixed_tables(int L, std::vector<float2>& tw, std::vector<int4>& st) {
+    const double PI = 3.1415926535897932384626433832795;
+    const int nhi = (L + kMixTwLo - 1) / kMixTwLo;
+    tw.resize((size_t)(kMixTwLo + nhi));
+    for (int i = 0; i < kMixTwLo + nhi; ++i) {  // two levels (LDS-sized): lo[i] = w^i, hi[i] = w^(64 i)
+        const double m = i < kMixTwLo ? (double)i : (double)kMixTwLo * (i - kMixTwLo);
+        const double a = -2.0 * PI * m / (double)L;
+        tw[i] = make_float2((float)cos(a), (float)sin(a));
+    }
+    std::vector<int> radix;
+    int r = L;
+    while (r % 4 == 0) { radix.push_back(4); r /= 4; }
+    while (r % 2 == 0) { radix.push_back(2); r /= 2; }
+    while (r % 3 == 0) { radix.push_back(3); r /= 3; }
+    while (r % 5 == 0) { radix.push_back(5); r /= 5; }
+    st.clear();
+    int ns = 1;
+    for (int R : radix) {
+        const unsigned magic = ns == 1 ? 0u : (unsigned)((0x100000000ull + (unsigned long long)ns - 1) / (unsigned long long)ns);
+        st.push_back(make_int4(R, ns, (int)magic, L / (ns * R)));
+        ns *= R;
+    }
+}
+
+// threads per transform of length L: a multiple of 64 with L <= kMixMaxElems * nt
+int mixed_threads(int L) {
+    int nt = (L + kMixMaxElems - 1) / kMixMaxElems;
+    nt = (nt + 63) / 64 * 64;
+    return nt < 64 ? 64 : nt;
+}
+constexpr size_t kMixLdsTarget = 78 * 1024;  // two workgroups per CU (with the static twiddle / reduction arrays)
+
 struct PassTimer {
     static constexpr int kMaxRecords = 8192;
     struct Rec { hipEvent_t a, b; int pass; };
@@ -133,6 +174,11 @@ struct fdr_plan {
     bool generic = false;  // FDR_FLAG_ANY_SIZE with a non-power-of-two dimension: naive DFT along that dimension
     float2 *naive_row = nullptr, *naive_col = nullptr;  // n x n tables of the non-power-of-two dimensions (length N / M)
     bool panel = false;
+    // FDR_FLAG_MIXED_RADIX in fast mode with a dimension that is not a power of two: the mixed-radix passes of fdr_mixed.hip on a
+    // panel-major full spectrum (mix_P columns per panel), row passes with mix_B transforms per workgroup
+    bool mixed = false;
+    MixLen mix_row{}, mix_col{};  // lengths N and M
+    int mix_P = 1, mix_logP = 0, mix_B = 1;
     size_t pstride = 0;  // panel stride (float2 elements)
     bool half = false;   // fast mode: only the non-redundant half of the Hermitian spectrum is kept (N/8 panels, Nyquist packed into column 0)
     int npanels = 0;  // fast mode: panel-major intermediate spectrum and filter
@@ -327,6 +373,10 @@ const char* const kPassRowsNormN[kMaxGroup + 1] = {
     "C2 rows: IFFT+normalize+crop [7 images]",
     "C2 rows: IFFT+normalize+crop [8 images]"};
 const char* const kPassSimple = "simple path (reference-shaped)";
+const char* const kPassMixedRows = "A mixed rows: pad+FFT (real pairs)";
+const char* const kPassMixedCols = "B mixed cols: FFT*W*IFFT";
+const char* const kPassMixedRowsInv = "C mixed rows: IFFT+real+minmax";
+const char* const kPassMixedNorm = "E mixed normalize+crop";
 
 int upload(float2** dst, const std::vector<float2>& v) {
     FDR_HIP(hipMalloc((void**)dst, v.size() * sizeof(float2)));
@@ -357,9 +407,12 @@ hipError_t long_rows_dev(float2* buf, float2* tmp, size_t rows, int L, int logl,
     return hipSuccess;
 }
 
+int mixed_fft2d_dev(fdr_plan* p, float2* d, float2* scratch, bool inverse, hipStream_t s);
+
 int dft2d_dev(fdr_plan* p, float2* d, float2* work2, bool inverse, hipStream_t s) {
     const float2* twr = inverse ? p->tw_row_i : p->tw_row_f;
     const float2* twc = inverse ? p->tw_col_i : p->tw_col_f;
+    if (p->mixed) return mixed_fft2d_dev(p, d, p->work, inverse, s);
     if (p->simple) {  // the reference's own sequence: rows, transpose, rows, transpose (fft/fft_serial.cpp:113-139)
         // one row pass over `rows` rows of length L held in `buf`, `tmp` free: radix-2 for powers of two, else the naive
         // DFT (transform_row_inplace, :100-101), which runs out of place and is copied back
@@ -398,6 +451,28 @@ int dft2d_dev(fdr_plan* p, float2* d, float2* work2, bool inverse, hipStream_t s
     return FDR_OK;
 }
 
+MixRowArgs mixed_row_args(const fdr_plan* p) {
+    MixRowArgs a{};
+    a.len = p->mix_row; a.B = p->mix_B; a.M = p->M; a.logP = p->mix_logP; a.pstride = p->pstride;
+    return a;
+}
+MixColArgs mixed_col_args(const fdr_plan* p) {
+    MixColArgs a{};
+    a.len = p->mix_col; a.N = p->N; a.logP = p->mix_logP; a.pstride = p->pstride;
+    return a;
+}
+
+// unscaled 2-D transform of the row-major M x N array d: rows into the panel-major scratch, columns back into d
+int mixed_fft2d_dev(fdr_plan* p, float2* d, float2* scratch, bool inverse, hipStream_t s) {
+    MixRowArgs ra = mixed_row_args(p);
+    ra.src_c = d; ra.dst_c = scratch; ra.inverse = inverse ? 1 : 0;  // one row per transform
+    FDR_HIP(launch_mixed_rows(MIX_ROWS_C2C, ra, (p->M + ra.B - 1) / ra.B, s));
+    MixColArgs ca = mixed_col_args(p);
+    ca.src = scratch; ca.dst = d; ca.rows_in = p->M; ca.inverse = inverse ? 1 : 0;
+    FDR_HIP(launch_mixed_cols(MIX_COLS_C2C, ca, p->npanels, s));
+    return FDR_OK;
+}
+
 int set_psf_dev_impl(fdr_plan* p, const float* d_psf, int prows, int pcols, int pstride, float K, hipStream_t s) {
     if (p->tables_only) return fail(FDR_ERR_STATE, "fdr_set_psf: plan was created with FDR_FLAG_TABLES_ONLY (slab primitives only)");
     if (prows <= 0 || pcols <= 0 || pstride < pcols) return fail(FDR_ERR_ARG, "fdr_set_psf: bad PSF shape");
@@ -405,7 +480,15 @@ int set_psf_dev_impl(fdr_plan* p, const float* d_psf, int prows, int pcols, int 
         return fail(FDR_ERR_ARG, "fdr_set_psf: PSF larger than the padded image (copyMakeBorder would throw, fft_serial.cpp:168)");
     ScopedPhase phase(p, FDR_PHASE_PRE, s);
     // pad top-left + forward 2-D FFT (fft/fft_serial.cpp:166-171,182)
-    if (p->simple) {
+    if (p->mixed) {
+        // rows of the PSF only (the rows below are zero and not read by the column pass), which turns H into W on its way out
+        MixRowArgs ra = mixed_row_args(p);
+        ra.src_real = d_psf; ra.src_rows = prows; ra.src_cols = pcols; ra.src_stride = pstride; ra.dst_c = p->filt;
+        FDR_HIP(launch_mixed_rows(MIX_ROWS_FWD_REAL, ra, (prows + 2 * p->mix_B - 1) / (2 * p->mix_B), s));
+        MixColArgs ca = mixed_col_args(p);
+        ca.src = p->filt; ca.dst = p->filt; ca.K = K; ca.rows_in = prows;
+        FDR_HIP(launch_mixed_cols(MIX_COLS_FILTER, ca, p->npanels, s));
+    } else if (p->simple) {
         FDR_HIP(launch_pad_real_to_complex(d_psf, prows, pcols, pstride, p->filt, p->M, p->N, s));
         int rc = dft2d_dev(p, p->filt, p->work2, false, s);
         if (rc != FDR_OK) return rc;
@@ -430,7 +513,7 @@ int set_psf_dev_impl(fdr_plan* p, const float* d_psf, int prows, int pcols, int 
         ca.data = p->filt; ca.N = p->N; ca.panel_c = p->ppar ? 1 : 0; ca.pstride = p->pstride;
         FDR_HIP(launch_cols(p->logM, p->mode, COL_FWD, ca, p->tw_col_f, p->tw_col_i, s));
     }
-    if (p->mode == FDR_MODE_FAST && !p->panel)  // (the panel path's column pass has written W already)
+    if (p->mode == FDR_MODE_FAST && !p->panel && !p->mixed)  // (the panel and mixed paths' column passes have written W already)
         FDR_HIP(launch_make_filter_fast(p->filt, p->filt, (size_t)p->M * p->N, K, s));
     p->K = K;
     p->have_psf = true;
@@ -568,6 +651,41 @@ int check_image_args(fdr_plan* p, const float* d_img, int rows, int cols, int st
     return FDR_OK;
 }
 
+// the mixed-radix operator: A (image rows -> spectrum), B (columns . W . inverse columns, only the rows C reads), C (inverse rows,
+// real parts of the cropped rows to the raw plane, min/max over the window), E (normalise + crop)
+int mixed_wiener_dev(fdr_plan* p, fdr_plan::Slot& w, const float* d_img, int rows, int cols, int stride, float* d_out, int out_stride,
+                     int mm_rows, int mm_cols, hipStream_t s) {
+    const int B = p->mix_B, need = rows > mm_rows ? rows : mm_rows;  // spectrum rows pass C transforms
+    {
+        ScopedPass t(p, s, kPassMixedRows);
+        MixRowArgs a = mixed_row_args(p);
+        a.src_real = d_img; a.src_rows = rows; a.src_cols = cols; a.src_stride = stride; a.dst_c = w.work;
+        FDR_HIP(launch_mixed_rows(MIX_ROWS_FWD_REAL, a, (rows + 2 * B - 1) / (2 * B), s));
+    }
+    {
+        ScopedPass t(p, s, kPassMixedCols);
+        MixColArgs c = mixed_col_args(p);
+        c.src = w.work; c.dst = w.work; c.filt = p->filt; c.rows_in = rows; c.rows_out = need;
+        FDR_HIP(launch_mixed_cols(MIX_COLS_FUSED, c, p->npanels, s));
+    }
+    // raw plane of the cropped rows x cols, row stride rs (a multiple of 4 where it fits: vector normalisation)
+    const int rs = ((cols + 3) & ~3) <= p->N ? ((cols + 3) & ~3) : cols;
+    const int n_part = (need + 2 * B - 1) / (2 * B);
+    if (n_part > p->mm_part_cap) return fail(FDR_ERR_STATE, "fdr_wiener: min/max partial count out of range");
+    {
+        ScopedPass t(p, s, kPassMixedRowsInv);
+        MixRowArgs a = mixed_row_args(p);
+        a.src_c = w.work; a.rows_in = need; a.dst_real = w.raw; a.dst_stride = rs; a.out_rows = rows; a.out_cols = cols;
+        a.mm_rows = mm_rows; a.mm_cols = mm_cols; a.mm_part = w.mm_part; a.scale = (float)(1.0 / ((double)p->M * p->N));
+        FDR_HIP(launch_mixed_rows(MIX_ROWS_INV_REAL, a, n_part, s));
+    }
+    {
+        ScopedPass t(p, s, kPassMixedNorm);
+        FDR_HIP(launch_normalize(w.raw, rs, w.mm_part, n_part, nullptr, d_out, rows, cols, out_stride, s));
+    }
+    return FDR_OK;
+}
+
 int wiener_dev_impl(fdr_plan* p, fdr_plan::Slot& w, const float* d_img, int rows, int cols, int stride, float* d_out,
                     int out_stride, int norm_area, hipStream_t s) {
     int vrc = check_image_args(p, d_img, rows, cols, stride, d_out, out_stride);
@@ -577,6 +695,7 @@ int wiener_dev_impl(fdr_plan* p, fdr_plan::Slot& w, const float* d_img, int rows
     const size_t P = (size_t)p->M * p->N;
     int n_part = 0;
 
+    if (p->mixed) return mixed_wiener_dev(p, w, d_img, rows, cols, stride, d_out, out_stride, mm_rows, mm_cols, s);
     if (p->simple) {
         ScopedPass t(p, s, kPassSimple);
         FDR_HIP(launch_pad_real_to_complex(d_img, rows, cols, stride, w.work, p->M, p->N, s));
@@ -673,9 +792,12 @@ int fdr_optimal_dft_size(int n) {
     return -1;
 }
 
+static int plan_create_mixed(fdr_plan* p, int device, int M, int N);
+
 static int plan_create_impl(fdr_plan* p, int device, int M, int N, int mode, unsigned flags) {
     p->device = device; p->M = M; p->N = N; p->mode = mode; p->flags = flags;
     const bool pow2 = fdr_is_pow2(M) && fdr_is_pow2(N);
+    if (!pow2 && mode == FDR_MODE_FAST && (flags & FDR_FLAG_MIXED_RADIX) != 0) return plan_create_mixed(p, device, M, N);
     p->generic = !pow2;  // only reachable with FDR_FLAG_ANY_SIZE: reference-shaped passes, parity arithmetic
     if (p->generic) p->mode = mode = FDR_MODE_PARITY;
     p->logM = fdr_is_pow2(M) ? ilog2(M) : -1;
@@ -736,12 +858,72 @@ static int plan_create_impl(fdr_plan* p, int device, int M, int N, int mode, uns
     return FDR_OK;
 }
 
+// FDR_FLAG_MIXED_RADIX: both lengths' tables (and the power-of-two tables of a power-of-two dimension, for the slab
+// primitives), panel width P (divides N, a panel of M rows within kMixLdsTarget) and row-pass transforms per workgroup B
+static int plan_create_mixed(fdr_plan* p, int device, int M, int N) {
+    p->mixed = true;
+    p->logM = fdr_is_pow2(M) ? ilog2(M) : -1;
+    p->logN = fdr_is_pow2(N) ? ilog2(N) : -1;
+    {
+        int cus = 0;
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) p->num_cu = cus;
+    }
+    int rc = FDR_OK;
+    std::vector<float2> t;
+    std::vector<int4> st;
+    for (int d = 0; d < 2; ++d) {
+        const int L = d == 0 ? N : M;
+        MixLen& ml = d == 0 ? p->mix_row : p->mix_col;
+        if (d == 1 && M == N) { ml = p->mix_row; break; }
+        build_mixed_tables(L, t, st);
+        if ((rc = upload(const_cast<float2**>(&ml.tw), t)) != FDR_OK) return rc;
+        int4* dst = nullptr;
+        FDR_HIP(hipMalloc((void**)&dst, (st.empty() ? 1 : st.size()) * sizeof(int4)));
+        ml.st = dst;
+        if (!st.empty()) FDR_HIP(hipMemcpy(dst, st.data(), st.size() * sizeof(int4), hipMemcpyHostToDevice));
+        ml.L = L; ml.nst = (int)st.size(); ml.nt = mixed_threads(L);
+    }
+    if (fdr_is_pow2(N)) {
+        build_twiddles(N, FDR_MODE_FAST, false, t); if ((rc = upload(&p->tw_row_f, t)) != FDR_OK) return rc;
+        build_twiddles(N, FDR_MODE_FAST, true, t);  if ((rc = upload(&p->tw_row_i, t)) != FDR_OK) return rc;
+    }
+    if (fdr_is_pow2(M)) {
+        build_twiddles(M, FDR_MODE_FAST, false, t); if ((rc = upload(&p->tw_col_f, t)) != FDR_OK) return rc;
+        build_twiddles(M, FDR_MODE_FAST, true, t);  if ((rc = upload(&p->tw_col_i, t)) != FDR_OK) return rc;
+    }
+    p->mix_logP = 0;
+    for (int lp = 2; lp > 0; --lp) {
+        const int P = 1 << lp;
+        if (N % P == 0 && ((size_t)M * P * sizeof(float2) <= kMixLdsTarget) && p->mix_col.nt * P <= 1024) { p->mix_logP = lp; break; }
+    }
+    p->mix_P = 1 << p->mix_logP;
+    p->mix_B = 1;
+    while (p->mix_B < 16 && p->mix_row.nt * p->mix_B * 2 <= 1024 && (size_t)N * p->mix_B * 2 * sizeof(float2) <= kMixLdsTarget) p->mix_B *= 2;
+    p->pstride = (size_t)M * p->mix_P;
+    p->npanels = N / p->mix_P;
+    const size_t P = (size_t)p->npanels * p->pstride;
+    if (hipMalloc((void**)&p->work, P * sizeof(float2)) != hipSuccess || hipMalloc((void**)&p->filt, P * sizeof(float2)) != hipSuccess ||
+        hipMalloc((void**)&p->raw, (size_t)M * N * sizeof(float)) != hipSuccess || hipMalloc((void**)&p->mm, 2 * sizeof(float)) != hipSuccess ||
+        hipMalloc((void**)&p->mm_part, (size_t)(p->mm_part_cap = (int)(((size_t)N + 255) / 256 * M + 8192)) * sizeof(float2)) != hipSuccess)
+        return fail(FDR_ERR_ALLOC, "fdr_plan_create: hipMalloc of the plan workspace failed");
+    p->ws_elems = P;
+    p->slots[0].work = p->work; p->slots[0].raw = p->raw; p->slots[0].mm = p->mm; p->slots[0].mm_part = p->mm_part;
+    return FDR_OK;
+}
+
 int fdr_plan_create(int device, int M, int N, int mode, unsigned flags, fdr_plan** out) {
     if (!out) return fail(FDR_ERR_ARG, "fdr_plan_create: null out");
     *out = nullptr;
     if (M <= 0 || N <= 0) return fail(FDR_ERR_ARG, "fdr_plan_create: non-positive dimension");
     if (mode != FDR_MODE_PARITY && mode != FDR_MODE_FAST) return fail(FDR_ERR_ARG, "fdr_plan_create: unknown mode");
-    if (!fdr_is_pow2(M) || !fdr_is_pow2(N)) {
+    const bool mixed = mode == FDR_MODE_FAST && (flags & FDR_FLAG_MIXED_RADIX) != 0 && !(fdr_is_pow2(M) && fdr_is_pow2(N));
+    if (mixed) {
+        if (!is_smooth(M) || !is_smooth(N) || M > kMixMaxLen || N > kMixMaxLen)
+            return fail(FDR_ERR_ARG, "fdr_plan_create: FDR_FLAG_MIXED_RADIX takes dimensions 2^a 3^b 5^c up to 8192 "
+                                     "(pad each to fdr_optimal_dft_size(n))");
+        if ((flags & (FDR_FLAG_TABLES_ONLY | FDR_FLAG_SIMPLE_PATH)) != 0)
+            return fail(FDR_ERR_ARG, "fdr_plan_create: FDR_FLAG_MIXED_RADIX does not combine with FDR_FLAG_TABLES_ONLY or FDR_FLAG_SIMPLE_PATH");
+    } else if (!fdr_is_pow2(M) || !fdr_is_pow2(N)) {
         if ((flags & FDR_FLAG_ANY_SIZE) == 0)
             return fail(FDR_ERR_NOT_POW2, "fdr_plan_create: M and N must be powers of two (pad first, utils.hpp:40-47) unless FDR_FLAG_ANY_SIZE is set");
         if ((!fdr_is_pow2(M) && M > kMaxNaiveLen) || (!fdr_is_pow2(N) && N > kMaxNaiveLen))
@@ -797,6 +979,8 @@ int fdr_plan_destroy(fdr_plan* p) {
     if (p->fork) (void)hipEventDestroy(p->fork);
     (void)hipFree(p->tw_row_f); (void)hipFree(p->tw_row_i); (void)hipFree(p->tw_col_f); (void)hipFree(p->tw_col_i);
     if (p->naive_col != p->naive_row) (void)hipFree(p->naive_col);
+    if (p->mix_col.tw != p->mix_row.tw) { (void)hipFree(const_cast<float2*>(p->mix_col.tw)); (void)hipFree(const_cast<int4*>(p->mix_col.st)); }
+    (void)hipFree(const_cast<float2*>(p->mix_row.tw)); (void)hipFree(const_cast<int4*>(p->mix_row.st));
     (void)hipFree(p->naive_row);
     for (auto& r : p->phase_pending) { p->timer.pool.push_back(r.a); p->timer.pool.push_back(r.b); }
     p->phase_pending.clear();
@@ -1265,7 +1449,7 @@ int fdr_fft2d_c2c(fdr_plan* p, float* data_host, int inverse) {
     // p->work is free between operator calls and serves as the staging buffer -- unless the plan keeps only the
     // half spectrum there (fast panel mode: about M*N/2 elements), where a full-size buffer is allocated for the call
     float2* buf = p->work;
-    const bool own = p->ws_elems < elems;
+    const bool own = p->ws_elems < elems || p->mixed;  // (a mixed plan's transform uses p->work as its scratch)
     if (own) FDR_HIP(hipMalloc((void**)&buf, bytes));
     hipError_t e = hipMemcpy(buf, data_host, bytes, hipMemcpyHostToDevice);
     int rc = FDR_OK;
@@ -1425,7 +1609,7 @@ int fdr_slab_rows_fft_dev(fdr_plan* p, float* d_complex, int rows, int dim, int 
     const float2* twi = dim == 0 ? p->tw_row_i : p->tw_col_i;
     const float2* naive = dim == 0 ? p->naive_row : p->naive_col;
     hipStream_t s = (hipStream_t)stream;
-    if (naive) return fail(FDR_ERR_ARG, "fdr_slab_rows_fft_dev: power-of-two dimensions only");
+    if (naive || !fdr_is_pow2(L)) return fail(FDR_ERR_ARG, "fdr_slab_rows_fft_dev: power-of-two dimensions only");
     float2* d = reinterpret_cast<float2*>(d_complex);
     if (logl > kMaxLdsLog) {  // more than 8192 points: 8192-point blocks + global radix-2 stages (fdr_aux.hip); stream-ordered scratch
         float2* tmp = nullptr;

@@ -168,4 +168,54 @@ hipError_t launch_dft_naive(const float2* src, float2* dst, int n, int inverse, 
 // table[t * n + k], forward direction, host generated (see fdr_aux.hip); rows transforms of length n, src != dst
 hipError_t launch_dft_naive_rows(const float2* src, float2* dst, int rows, int n, const float2* table, int inverse, hipStream_t s);
 
+// mixed-radix fast mode (fdr_mixed.hip, FDR_FLAG_MIXED_RADIX): transform lengths 2^a 3^b 5^c up to 8192, rows in LDS
+constexpr int kMixMaxElems = 16;              // values one thread holds per stage: threads per transform nt >= L / 16
+constexpr size_t kMixMaxLds = 144 * 1024;     // dynamic LDS of one workgroup (the rest: twiddles, reduction)
+constexpr int kMixMaxLen = 8192;
+constexpr int kMixTwLo = 64;                  // twiddle table = lo[64] then hi[ceil(L / 64)]: w^m = lo[m % 64] hi[m / 64]
+struct MixLen {            // one transform length, device tables built by the plan
+    const float2* tw;      // exp(-2 pi i m / L) as lo[i] = m = i (i < 64), hi[i] = m = 64 i (i < ceil(L / 64)); double-generated
+    const int4* st;        // per Stockham stage {radix, ns (product of the earlier radices), ceil(2^32 / ns) or 0 for ns = 1, L / (ns radix)}
+    int L, nst;            // length, number of stages
+    int nt;                // threads per transform (a multiple of 64, >= L / kMixMaxElems)
+};
+enum MixRowKind {
+    MIX_ROWS_FWD_REAL = 0,  // pass A: real rows (zero padded on load) -> panel-major spectrum, two rows per transform
+    MIX_ROWS_C2C = 1,       // fdr_fft2d_c2c: row-major complex rows -> panel-major, forward or inverse
+    MIX_ROWS_INV_REAL = 2   // pass C: panel-major spectrum -> inverse, real parts of the cropped rows, (min, max) partials
+};
+enum MixColKind {
+    MIX_COLS_FILTER = 0,  // PSF spectrum: forward columns, W = conj(H) / (|H|^2 + K) in place
+    MIX_COLS_FUSED = 1,   // pass B: forward columns, multiply by W, inverse columns
+    MIX_COLS_C2C = 2      // fdr_fft2d_c2c: panel-major -> columns forward or inverse -> row-major M x N
+};
+struct MixRowArgs {
+    MixLen len;          // length N
+    int B;               // transforms per workgroup (FWD_REAL / INV_REAL: two image rows each)
+    int M, logP;         // plan rows, log2 of the panel width
+    size_t pstride;      // panel stride in float2 elements
+    const float* src_real; int src_rows, src_cols, src_stride;  // FWD_REAL
+    const float2* src_c;  // C2C: row-major M x N; INV_REAL: panel-major spectrum
+    int rows_in;          // INV_REAL: spectrum rows read (the others are taken as zero)
+    int inverse;          // C2C
+    float2* dst_c;        // FWD_REAL / C2C: panel-major spectrum
+    float* dst_real; int dst_stride, out_rows, out_cols;  // INV_REAL: raw real plane of the cropped rows x cols
+    int mm_rows, mm_cols; float2* mm_part; float scale;    // INV_REAL: min/max window, one partial per workgroup, 1 / (M N)
+};
+struct MixColArgs {
+    MixLen len;           // length M
+    int N, logP;
+    size_t pstride;
+    const float2* src;    // panel-major input
+    float2* dst;          // FILTER / FUSED: panel-major (may be src); C2C: row-major M x N
+    const float2* filt;   // FUSED: W, panel-major
+    float K;              // FILTER
+    int rows_in;          // rows of src that hold data (the others are taken as zero)
+    int rows_out;         // FUSED: rows written back
+    int inverse;          // C2C
+};
+// blocks = workgroups (rows / (2 B) or rows / B, rounded up); npanels = N / P
+hipError_t launch_mixed_rows(MixRowKind kind, const MixRowArgs& a, int blocks, hipStream_t s);
+hipError_t launch_mixed_cols(MixColKind kind, const MixColArgs& a, int npanels, hipStream_t s);
+
 }  // namespace fdr
