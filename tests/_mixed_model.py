@@ -4,20 +4,25 @@ test_mixed_radix_host.py before it judges the GPU."""
 import numpy as np
 
 
-def wiener_model(img, psf, K, M, N, norm_cropped=True):
-    """Pad image and PSF top-left to M x N, W = conj(H) / (|H|^2 + K), real part of the inverse, crop, min-max normalise
-    over the cropped rows x cols (norm_cropped) or over the padded M x N area."""
+def wiener_raw(img, psf, K, M, N):
+    """The raw M x N plane before normalisation: pad image and PSF top-left to M x N, W = conj(H) / (|H|^2 + K), real part
+    of the inverse transform (taken as the inverse of the Hermitian half spectrum)."""
     img = np.asarray(img, dtype=np.float64)
     psf = np.asarray(psf, dtype=np.float64)
-    rows, cols = img.shape
     f = np.zeros((M, N))
-    f[:rows, :cols] = img
+    f[:img.shape[0], :img.shape[1]] = img
     h = np.zeros((M, N))
     h[:psf.shape[0], :psf.shape[1]] = psf
-    G = np.fft.fft2(f)
-    H = np.fft.fft2(h)
+    G = np.fft.rfft2(f)
+    H = np.fft.rfft2(h)
     W = np.conj(H) / (np.abs(H) ** 2 + K)
-    raw = np.real(np.fft.ifft2(G * W))
+    return np.fft.irfft2(G * W, s=(M, N))
+
+
+def wiener_model(img, psf, K, M, N, norm_cropped=True):
+    """wiener_raw, crop, min-max normalise over the cropped rows x cols (norm_cropped) or over the padded M x N area."""
+    rows, cols = np.shape(img)
+    raw = wiener_raw(img, psf, K, M, N)
     area = raw[:rows, :cols] if norm_cropped else raw
     lo, hi = area.min(), area.max()
     out = raw[:rows, :cols]
