@@ -141,6 +141,26 @@ int fdr_set_psf_dev(fdr_plan* plan, const float* d_psf, int prows, int pcols, in
 /* motionBlurKernel on the device straight into the plan (no host round trip) */
 int fdr_set_psf_motion(fdr_plan* plan, int size, double angle_deg, float K, void* stream);
 
+/* -- constrained least-squares (CLS) filter (Gonzalez & Woods 5.9), the second filter the reference's prototype names
+ *    (others/fft_image_restoration.py:109-112, constrained_least_square_filtering, never defined there).  The same three calls
+ *    with a smoothness weight gamma: for bin (u, v) of the M x N plan
+ *        W = conj(H) / (|H|^2 + K + gamma L^2),   L = 4 sin^2(pi u / M) + 4 sin^2(pi v / N)
+ *    L is the symbol of the periodic 5-point Laplacian [[0,-1,0],[-1,4,-1],[0,-1,0]], so roughness is penalised instead of
+ *    energy.  Evaluated in double, rounded once; a zero denominator gives W = 0.  The filter then serves every fdr_wiener_*
+ *    call (batches, FDR_OPT_BATCH_GRAPH replays) and travels with fdr_plan_export_filter_dev / fdr_plan_import_filter_dev.
+ *    Validation, plan state and the PRE phase as the fdr_set_psf* counterparts; the first call on a plan also uploads a table
+ *    of M + N doubles (kept until fdr_plan_destroy).
+ *      gamma == 0          exactly the Wiener call (same filter bytes)
+ *      gamma < 0, NaN, inf FDR_ERR_ARG before any device work
+ *      gamma > 0           FDR_MODE_FAST plans only: a parity-mode plan (so every FDR_FLAG_ANY_SIZE plan with a non-power-of-two
+ *                          dimension) returns FDR_ERR_ARG before any device work, its previous filter intact -- parity mode is
+ *                          bit-identical to ./serial, which has no CLS
+ *      tables-only plans   FDR_ERR_STATE
+ *    fdr_slab_* and fdr_batch_run have the Wiener filter only.                                                         */
+int fdr_set_psf_cls(fdr_plan* plan, const float* psf_host, int prows, int pcols, int pstride, float K, float gamma);
+int fdr_set_psf_cls_dev(fdr_plan* plan, const float* d_psf, int prows, int pcols, int pstride, float K, float gamma, void* stream);
+int fdr_set_psf_motion_cls(fdr_plan* plan, int size, double angle_deg, float K, float gamma, void* stream);
+
 /* -- the prepared filter of a plan as an opaque block of bytes, for a caller that distributes ONE rank's PSF spectrum to the
  *    others instead of recomputing it everywhere -- the role of the MPI_Bcast / MPI_Scatterv of the padded PSF in the
  *    reference's MPI variant (fft/fft_mpi.cpp:334-378); in the batched mode a broadcast over RCCL (bench.py --bcast-filter).

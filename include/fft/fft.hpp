@@ -28,14 +28,29 @@ struct Options {
     int norm_area = FDR_NORM_PADDED;  // FDR_NORM_PADDED (./serial semantics) or FDR_NORM_CROPPED (reference ./gpu, fft_gpu.cu:379-381)
     int device = 0;
     bool mixed_radix = false;         // FDR_MODE_FAST: 2^a 3^b 5^c plan sizes by mixed-radix FFTs (FDR_FLAG_MIXED_RADIX) in wienerDeblur_myfft
+    float cls_gamma = 0.f;            // > 0: constrained least-squares filter W = conj(H) / (|H|^2 + K + gamma L^2) (fdr_set_psf_cls,
+                                      // FDR_MODE_FAST only: a parity plan refuses it); 0: the Wiener filter
 };
 // process-wide defaults of the reference-signature overloads (the drivers' --mode / --norm flags); atomics: reading
 // them from several threads is safe, and no entry point ever changes them behind the caller's back
 inline std::atomic<int>& default_mode() { static std::atomic<int> m{FDR_MODE_FAST}; return m; }
 inline std::atomic<int>& default_norm() { static std::atomic<int> n{FDR_NORM_PADDED}; return n; }
+inline std::atomic<float>& default_cls_gamma() { static std::atomic<float> g{0.f}; return g; }
 inline void set_mode(int mode) { default_mode().store(mode); }
 inline void set_norm_area(int area) { default_norm().store(area); }
-inline Options defaults() { Options o; o.mode = default_mode().load(); o.norm_area = default_norm().load(); return o; }
+inline void set_cls_gamma(float gamma) { default_cls_gamma().store(gamma); }
+inline Options defaults() {
+    Options o;
+    o.mode = default_mode().load(); o.norm_area = default_norm().load(); o.cls_gamma = default_cls_gamma().load();
+    return o;
+}
+
+// the plan's filter from a host PSF: Wiener, or CLS when o.cls_gamma != 0
+inline void set_psf_opts(fdr_plan* plan, const Mat& psf, float K, const Options& o) {
+    Mat psfc = psf.isContinuous() ? psf : psf.clone();
+    if (o.cls_gamma != 0.f) FDR_CHECK(fdr_set_psf_cls(plan, psfc.ptr<float>(0), psf.rows, psf.cols, psf.cols, K, o.cls_gamma));
+    else FDR_CHECK(fdr_set_psf(plan, psfc.ptr<float>(0), psf.rows, psf.cols, psf.cols, K));
+}
 
 // The reference's Profiler buckets (fft/fft_gpu.cu:17-57).  alloc / h2d / pre / compute / d2h come from
 // fdr_plan_phase_times (hipEvent pairs on the streams the work ran on); post is the host time of wrapping the results.
@@ -130,8 +145,7 @@ inline void wienerDeblur_RGB_optimized(std::vector<Mat>& channels, const Mat& ps
     PlanCacheSettle settle_;
     fdr_plan* plan = plan_cache().get(o.device, nextPowerOfTwo(imgRows), nextPowerOfTwo(imgCols), o.mode, &created);
     if (!created) { float discard[FDR_N_PHASES]; FDR_CHECK(fdr_plan_phase_times(plan, discard, 1)); }  // this call's phases only ([1. Allocation] = 0: reused)
-    Mat psfc = psf.isContinuous() ? psf : psf.clone();
-    FDR_CHECK(fdr_set_psf(plan, psfc.ptr<float>(0), psf.rows, psf.cols, psf.cols, K));
+    set_psf_opts(plan, psf, K, o);
     // all channels through the host batch pipeline: upload, restoration and download of consecutive channels overlap
     // (what the stream + pinned-buffer set-up of fft/fft_gpu.cu:304-350 is after)
     bool same = true;
@@ -165,8 +179,7 @@ inline void wienerDeblur_RGB_naive(std::vector<Mat>& channels, const Mat& psf, f
     for (size_t i = 0; i < channels.size(); ++i) {
         fdr_plan* plan = nullptr;
         FDR_CHECK(fdr_plan_create(o.device, nextPowerOfTwo(channels[i].rows), nextPowerOfTwo(channels[i].cols), o.mode, 0, &plan));
-        Mat psfc = psf.isContinuous() ? psf : psf.clone();
-        FDR_CHECK(fdr_set_psf(plan, psfc.ptr<float>(0), psf.rows, psf.cols, psf.cols, K));
+        set_psf_opts(plan, psf, K, o);
         channels[i] = run_channel(plan, channels[i], o.norm_area);
         p.add(plan);
         fdr_plan_destroy(plan);
@@ -188,8 +201,7 @@ inline Mat wienerDeblur_myfft(const Mat& img, const Mat& psf, float K, const Opt
     bool created = false;
     PlanCacheSettle settle_;
     fdr_plan* plan = plan_cache().get(o.device, M, N, o.mode, &created, flags);
-    Mat psfc = psf.isContinuous() ? psf : psf.clone();
-    FDR_CHECK(fdr_set_psf(plan, psfc.ptr<float>(0), psf.rows, psf.cols, psf.cols, K));
+    set_psf_opts(plan, psf, K, o);
     return run_channel(plan, img, FDR_NORM_CROPPED);
 }
 inline Mat wienerDeblur_myfft(const Mat& img, const Mat& psf, float K) { return wienerDeblur_myfft(img, psf, K, defaults()); }

@@ -117,6 +117,9 @@ def _load():
     L.fdr_set_psf.argtypes = [vp, vp, ci, ci, ci, cf]
     L.fdr_set_psf_dev.argtypes = [vp, vp, ci, ci, ci, cf, vp]
     L.fdr_set_psf_motion.argtypes = [vp, ci, cd, cf, vp]
+    L.fdr_set_psf_cls.argtypes = [vp, vp, ci, ci, ci, cf, cf]
+    L.fdr_set_psf_cls_dev.argtypes = [vp, vp, ci, ci, ci, cf, cf, vp]
+    L.fdr_set_psf_motion_cls.argtypes = [vp, ci, cd, cf, cf, vp]
     L.fdr_wiener_f32.argtypes = [vp, vp, ci, ci, ci, vp, ci, ci]
     L.fdr_wiener_f32_dev.argtypes = [vp, vp, ci, ci, ci, vp, ci, ci, vp]
     L.fdr_wiener_batch_f32_dev.argtypes = [vp, vp, ctypes.c_size_t, ci, ci, ci, ci, vp, ctypes.c_size_t, ci, ci, vp]
@@ -143,7 +146,8 @@ def _load():
                  "fdr_optimal_dft_size", "fdr_plan_set_option", "fdr_plan_phase_times", "fdr_batch_run",
                  "fdr_slab_pad_dev", "fdr_slab_rows_fft_dev", "fdr_slab_pack_dev", "fdr_slab_transpose_dev", "fdr_slab_wiener_dev",
                  "fdr_slab_real_dev", "fdr_slab_minmax_dev", "fdr_slab_normalize_dev", "fdr_warp_affine_f32",
-                 "fdr_plan_filter_bytes", "fdr_plan_export_filter_dev", "fdr_plan_import_filter_dev"):
+                 "fdr_plan_filter_bytes", "fdr_plan_export_filter_dev", "fdr_plan_import_filter_dev",
+                 "fdr_set_psf_cls", "fdr_set_psf_cls_dev", "fdr_set_psf_motion_cls"):
         getattr(L, name).restype = ci
     return L
 
@@ -160,7 +164,8 @@ EXPORTED_SYMBOLS = (
     "fdr_plan_pass_times", "fdr_optimal_dft_size", "fdr_plan_set_option", "fdr_plan_phase_times", "fdr_batch_run",
     "fdr_slab_pad_dev", "fdr_slab_rows_fft_dev", "fdr_slab_pack_dev", "fdr_slab_transpose_dev", "fdr_slab_wiener_dev",
     "fdr_slab_real_dev", "fdr_slab_minmax_dev", "fdr_slab_normalize_dev", "fdr_warp_affine_f32",
-    "fdr_plan_filter_bytes", "fdr_plan_export_filter_dev", "fdr_plan_import_filter_dev")
+    "fdr_plan_filter_bytes", "fdr_plan_export_filter_dev", "fdr_plan_import_filter_dev",
+    "fdr_set_psf_cls", "fdr_set_psf_cls_dev", "fdr_set_psf_motion_cls")
 
 
 def _check(rc):
@@ -294,17 +299,30 @@ class Plan:
     def __exit__(self, *a):
         self.close()
 
-    # PSF
-    def set_psf(self, psf, K=0.01):
+    # PSF.  gamma > 0: the constrained least-squares filter W = conj(H) / (|H|^2 + K + gamma L^2) (fdr_set_psf_cls*, fast mode
+    # only); gamma == 0: the Wiener filter of fdr_set_psf*
+    def set_psf(self, psf, K=0.01, gamma=0.0):
         psf = np.ascontiguousarray(psf, dtype=np.float32)
-        _check(lib.fdr_set_psf(self._h, _ptr(psf), psf.shape[0], psf.shape[1], psf.shape[1], ctypes.c_float(K)))
+        if gamma == 0:
+            _check(lib.fdr_set_psf(self._h, _ptr(psf), psf.shape[0], psf.shape[1], psf.shape[1], ctypes.c_float(K)))
+        else:
+            _check(lib.fdr_set_psf_cls(self._h, _ptr(psf), psf.shape[0], psf.shape[1], psf.shape[1], ctypes.c_float(K),
+                                       ctypes.c_float(gamma)))
 
-    def set_psf_dev(self, d_ptr, prows, pcols, pstride, K=0.01, stream=None):
-        _check(lib.fdr_set_psf_dev(self._h, ctypes.c_void_p(int(d_ptr)), prows, pcols, pstride, ctypes.c_float(K),
-                                   _stream(stream)))
+    def set_psf_dev(self, d_ptr, prows, pcols, pstride, K=0.01, stream=None, gamma=0.0):
+        if gamma == 0:
+            _check(lib.fdr_set_psf_dev(self._h, ctypes.c_void_p(int(d_ptr)), prows, pcols, pstride, ctypes.c_float(K),
+                                       _stream(stream)))
+        else:
+            _check(lib.fdr_set_psf_cls_dev(self._h, ctypes.c_void_p(int(d_ptr)), prows, pcols, pstride, ctypes.c_float(K),
+                                           ctypes.c_float(gamma), _stream(stream)))
 
-    def set_psf_motion(self, size, angle, K=0.01, stream=None):
-        _check(lib.fdr_set_psf_motion(self._h, int(size), float(angle), ctypes.c_float(K), _stream(stream)))
+    def set_psf_motion(self, size, angle, K=0.01, stream=None, gamma=0.0):
+        if gamma == 0:
+            _check(lib.fdr_set_psf_motion(self._h, int(size), float(angle), ctypes.c_float(K), _stream(stream)))
+        else:
+            _check(lib.fdr_set_psf_motion_cls(self._h, int(size), float(angle), ctypes.c_float(K), ctypes.c_float(gamma),
+                                              _stream(stream)))
 
     # the prepared filter as an opaque block (one rank's PSF spectrum handed to the others: fft/fft_mpi.cpp:334-378)
     def filter_bytes(self):
@@ -449,27 +467,29 @@ def host_alloc(shape, dtype=np.float32):
     return np.frombuffer(buf, dtype=dtype).reshape(shape)
 
 
-def wienerDeblur_myfft(img, psf, K, mode=MODE_PARITY, device=0, norm_area=NORM_PADDED):
+def wienerDeblur_myfft(img, psf, K, mode=MODE_PARITY, device=0, norm_area=NORM_PADDED, cls_gamma=0.0):
     """One channel the way the DRIVERS call the operator: pad to powers of two (serial.cpp:36 / fft_gpu.cu:287-288, on the
-    device), restore, normalise (default: over the padded area, serial.cpp:34-39), crop."""
+    device), restore, normalise (default: over the padded area, serial.cpp:34-39), crop.  cls_gamma > 0 (MODE_FAST): the
+    constrained least-squares filter instead of the Wiener filter (Plan.set_psf)."""
     img = np.asarray(img, dtype=np.float32)
     with Plan(nextPowerOfTwo(img.shape[0]), nextPowerOfTwo(img.shape[1]), mode, device) as p:
-        p.set_psf(psf, K)
+        p.set_psf(psf, K, gamma=cls_gamma)
         return p.wiener(img, norm_area)
 
 
-def wienerDeblur_myfft_unpadded(img, psf, K, mode=MODE_PARITY, device=0, mixed_radix=False):
+def wienerDeblur_myfft_unpadded(img, psf, K, mode=MODE_PARITY, device=0, mixed_radix=False, cls_gamma=0.0):
     """fft_serial::wienerDeblur_myfft called DIRECTLY on a channel of any size (fft/fft_serial.cpp:141-261): pad to
     getOptimalDFTSize (2^a 3^b 5^c; a non-power-of-two dimension is transformed by the naive DFT, :100-101), restore,
     crop to the input size, normalise over the cropped plane (:243-246).  mixed_radix=True with MODE_FAST: the
-    mixed-radix FFTs of FLAG_MIXED_RADIX instead of the naive DFT (dimensions up to 8192)."""
+    mixed-radix FFTs of FLAG_MIXED_RADIX instead of the naive DFT (dimensions up to 8192).  cls_gamma > 0: the constrained
+    least-squares filter (fast-mode plans only: a naive-DFT plan is a parity plan and refuses it)."""
     img = np.asarray(img, dtype=np.float32)
     M, N = getOptimalDFTSize(img.shape[0]), getOptimalDFTSize(img.shape[1])
     flags = 0 if (isPowerOfTwo(M) and isPowerOfTwo(N)) else FLAG_ANY_SIZE
     if mixed_radix and mode == MODE_FAST:
         flags |= FLAG_MIXED_RADIX
     with Plan(M, N, mode, device, flags=flags) as p:
-        p.set_psf(psf, K)
+        p.set_psf(psf, K, gamma=cls_gamma)
         return p.wiener(img, NORM_CROPPED)
 
 
@@ -513,21 +533,21 @@ def batch_run(devices, M, N, count, rows=None, cols=None, mode=MODE_FAST, flags=
     return stats, outs
 
 
-def wienerDeblur_RGB_optimized(channels, psf, K, mode=MODE_PARITY, device=0, norm_area=NORM_PADDED):
+def wienerDeblur_RGB_optimized(channels, psf, K, mode=MODE_PARITY, device=0, norm_area=NORM_PADDED, cls_gamma=0.0):
     """fft_gpu::wienerDeblur_RGB_optimized (fft/fft_gpu.cu:279-394): replaces every element of
     `channels` (unpadded float32 planes of one size) in place with its restored [0,1] plane.
-    One plan and one PSF spectrum serve all channels."""
+    One plan and one PSF spectrum serve all channels.  cls_gamma > 0: the constrained least-squares filter."""
     if not channels:
         return
     r, c = np.asarray(channels[0]).shape
     with Plan(nextPowerOfTwo(r), nextPowerOfTwo(c), mode, device) as p:
-        p.set_psf(psf, K)
+        p.set_psf(psf, K, gamma=cls_gamma)
         for i in range(len(channels)):
             channels[i] = p.wiener(channels[i], norm_area)
 
 
-def wienerDeblur_RGB_naive(channels, psf, K, mode=MODE_PARITY, device=0, norm_area=NORM_PADDED):
+def wienerDeblur_RGB_naive(channels, psf, K, mode=MODE_PARITY, device=0, norm_area=NORM_PADDED, cls_gamma=0.0):
     """fft_gpu::wienerDeblur_RGB_naive (fft/fft_gpu.cu:400-512): same results, but every channel
     builds and frees its own plan and PSF spectrum, as the reference's allocation-in-loop variant."""
     for i in range(len(channels)):
-        channels[i] = wienerDeblur_myfft(channels[i], psf, K, mode, device, norm_area)
+        channels[i] = wienerDeblur_myfft(channels[i], psf, K, mode, device, norm_area, cls_gamma)

@@ -196,6 +196,7 @@ struct fdr_plan {
     int mm_part_cap = 0;
     float K = 0.f;
     bool have_psf = false;
+    double* lap = nullptr;  // CLS filters (fdr_set_psf_cls*): a_u = 4 sin^2(pi u / M), u < M, then b_v = 4 sin^2(pi v / N), v < N
     PassTimer timer;
     // the reference Profiler's buckets (fdr_plan_phase_times): resolved sums + event pairs not read back yet
     struct PhaseRec { hipEvent_t a, b; int phase; };
@@ -473,11 +474,34 @@ int mixed_fft2d_dev(fdr_plan* p, float2* d, float2* scratch, bool inverse, hipSt
     return FDR_OK;
 }
 
-int set_psf_dev_impl(fdr_plan* p, const float* d_psf, int prows, int pcols, int pstride, float K, hipStream_t s) {
+// The Laplacian table of the CLS filters, built in double on the host and uploaded on the first fdr_set_psf_cls* call of a plan
+// (synchronous, outside the PRE phase); freed with the plan.  sin^2, not 2 - 2 cos: no cancellation at small frequencies.
+int ensure_lap_table(fdr_plan* p) {
+    if (p->lap) return FDR_OK;
+    std::vector<double> t((size_t)p->M + p->N);
+    const double pi = 3.14159265358979323846;
+    for (int u = 0; u < p->M; ++u) { const double sn = std::sin(pi * u / p->M); t[u] = 4.0 * sn * sn; }
+    for (int v = 0; v < p->N; ++v) { const double sn = std::sin(pi * v / p->N); t[(size_t)p->M + v] = 4.0 * sn * sn; }
+    double* d = nullptr;
+    FDR_HIP(hipMalloc((void**)&d, t.size() * sizeof(double)));
+    const hipError_t e = hipMemcpy(d, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(d); FDR_HIP(e); }
+    p->lap = d;
+    return FDR_OK;
+}
+
+// gamma > 0: the constrained least-squares filter W = conj(H) / (|H|^2 + K + gamma L^2) (fast mode only; the callers have
+// validated gamma and the plan); gamma == 0: the Wiener filter
+int set_psf_dev_impl(fdr_plan* p, const float* d_psf, int prows, int pcols, int pstride, float K, hipStream_t s, double gamma = 0.0) {
     if (p->tables_only) return fail(FDR_ERR_STATE, "fdr_set_psf: plan was created with FDR_FLAG_TABLES_ONLY (slab primitives only)");
     if (prows <= 0 || pcols <= 0 || pstride < pcols) return fail(FDR_ERR_ARG, "fdr_set_psf: bad PSF shape");
     if (prows > p->M || pcols > p->N)
         return fail(FDR_ERR_ARG, "fdr_set_psf: PSF larger than the padded image (copyMakeBorder would throw, fft_serial.cpp:168)");
+    const bool cls = gamma > 0.0;
+    if (cls) {
+        const int rc = ensure_lap_table(p);
+        if (rc != FDR_OK) return rc;
+    }
     ScopedPhase phase(p, FDR_PHASE_PRE, s);
     // pad top-left + forward 2-D FFT (fft/fft_serial.cpp:166-171,182)
     if (p->mixed) {
@@ -487,7 +511,8 @@ int set_psf_dev_impl(fdr_plan* p, const float* d_psf, int prows, int pcols, int 
         FDR_HIP(launch_mixed_rows(MIX_ROWS_FWD_REAL, ra, (prows + 2 * p->mix_B - 1) / (2 * p->mix_B), s));
         MixColArgs ca = mixed_col_args(p);
         ca.src = p->filt; ca.dst = p->filt; ca.K = K; ca.rows_in = prows;
-        FDR_HIP(launch_mixed_cols(MIX_COLS_FILTER, ca, p->npanels, s));
+        ca.lap = p->lap; ca.gamma = gamma;
+        FDR_HIP(launch_mixed_cols(cls ? MIX_COLS_FILTER_CLS : MIX_COLS_FILTER, ca, p->npanels, s));
     } else if (p->simple) {
         FDR_HIP(launch_pad_real_to_complex(d_psf, prows, pcols, pstride, p->filt, p->M, p->N, s));
         int rc = dft2d_dev(p, p->filt, p->work2, false, s);
@@ -503,7 +528,8 @@ int set_psf_dev_impl(fdr_plan* p, const float* d_psf, int prows, int pcols, int 
         ColArgs ca{};
         ca.data = p->filt; ca.N = p->N; ca.num_cu = p->num_cu; ca.pstride = p->pstride; ca.npanels = p->npanels;
         ca.nvalid = nvalid; ca.K = K; ca.packed0 = p->half ? 1 : 0;
-        FDR_HIP(launch_cols_panel(p->logM, COL_FWD_FILTER, ca, p->tw_col_f, s));
+        if (cls) FDR_HIP(launch_cols_panel_cls(p->logM, ca, p->lap, gamma, p->tw_col_f, s));
+        else FDR_HIP(launch_cols_panel(p->logM, COL_FWD_FILTER, ca, p->tw_col_f, s));
     } else {
         RowArgs ra{};
         ra.src_real = d_psf; ra.src_rows = prows; ra.src_cols = pcols; ra.src_stride = pstride;
@@ -513,8 +539,10 @@ int set_psf_dev_impl(fdr_plan* p, const float* d_psf, int prows, int pcols, int 
         ca.data = p->filt; ca.N = p->N; ca.panel_c = p->ppar ? 1 : 0; ca.pstride = p->pstride;
         FDR_HIP(launch_cols(p->logM, p->mode, COL_FWD, ca, p->tw_col_f, p->tw_col_i, s));
     }
-    if (p->mode == FDR_MODE_FAST && !p->panel && !p->mixed)  // (the panel and mixed paths' column passes have written W already)
-        FDR_HIP(launch_make_filter_fast(p->filt, p->filt, (size_t)p->M * p->N, K, s));
+    if (p->mode == FDR_MODE_FAST && !p->panel && !p->mixed) {  // (the panel and mixed paths' column passes have written W already)
+        if (cls) FDR_HIP(launch_make_filter_cls(p->filt, p->filt, p->M, p->N, K, p->lap, gamma, s));
+        else FDR_HIP(launch_make_filter_fast(p->filt, p->filt, (size_t)p->M * p->N, K, s));
+    }
     p->K = K;
     p->have_psf = true;
     return FDR_OK;
@@ -756,6 +784,17 @@ int wiener_dev_impl(fdr_plan* p, fdr_plan::Slot& w, const float* d_img, int rows
     return FDR_OK;
 }
 
+// fdr_set_psf_cls*: gamma finite and >= 0; a tables-only plan FDR_ERR_STATE; gamma > 0 only on a fast-mode plan (parity mode
+// exists to be bit-identical to ./serial, which has no CLS).  All before any device work, the plan's filter untouched.
+int cls_check(const fdr_plan* p, float gamma, const char* fn) {
+    if (!(gamma >= 0.f) || std::isinf(gamma)) return fail(FDR_ERR_ARG, std::string(fn) + ": gamma must be finite and >= 0");
+    if (p->tables_only) return fail(FDR_ERR_STATE, std::string(fn) + ": plan was created with FDR_FLAG_TABLES_ONLY (slab primitives only)");
+    if (gamma > 0.f && p->mode != FDR_MODE_FAST)
+        return fail(FDR_ERR_ARG, std::string(fn) + ": a constrained least-squares filter (gamma > 0) needs a FDR_MODE_FAST plan; "
+                                                   "parity mode (and every FDR_FLAG_ANY_SIZE plan) has the Wiener filter only");
+    return FDR_OK;
+}
+
 int ensure_psf_staging(fdr_plan* p, size_t elems) {
     if (p->psf_cap >= elems) return FDR_OK;
     if (p->psf_dev) { (void)hipFree(p->psf_dev); p->psf_dev = nullptr; p->psf_cap = 0; }
@@ -986,7 +1025,7 @@ int fdr_plan_destroy(fdr_plan* p) {
     p->phase_pending.clear();
     p->timer.destroy();
     (void)hipFree(p->work); (void)hipFree(p->work2); (void)hipFree(p->filt); (void)hipFree(p->raw);
-    (void)hipFree(p->psf_dev); (void)hipFree(p->mm); (void)hipFree(p->mm_part);
+    (void)hipFree(p->psf_dev); (void)hipFree(p->mm); (void)hipFree(p->mm_part); (void)hipFree(p->lap);
     (void)hipFree(p->stage_in); (void)hipFree(p->stage_out);
     delete p;
     return FDR_OK;
@@ -1098,6 +1137,50 @@ int fdr_set_psf_motion(fdr_plan* p, int size, double angle_deg, float K, void* s
     if (rc != FDR_OK) return rc;
     FDR_HIP(launch_psf_motion(size, angle_deg, p->psf_dev, (hipStream_t)stream));
     return set_psf_dev_impl(p, p->psf_dev, size, size, size, K, (hipStream_t)stream);
+}
+
+int fdr_set_psf_cls_dev(fdr_plan* p, const float* d_psf, int prows, int pcols, int pstride, float K, float gamma, void* stream) {
+    if (!p || !d_psf) return fail(FDR_ERR_ARG, "fdr_set_psf_cls_dev: null argument");
+    int rc = cls_check(p, gamma, "fdr_set_psf_cls_dev");
+    if (rc != FDR_OK) return rc;
+    if (gamma == 0.f) return fdr_set_psf_dev(p, d_psf, prows, pcols, pstride, K, stream);
+    FDR_HIP(hipSetDevice(p->device));
+    return set_psf_dev_impl(p, d_psf, prows, pcols, pstride, K, (hipStream_t)stream, gamma);
+}
+
+int fdr_set_psf_cls(fdr_plan* p, const float* psf_host, int prows, int pcols, int pstride, float K, float gamma) {
+    if (!p || !psf_host) return fail(FDR_ERR_ARG, "fdr_set_psf_cls: null argument");
+    int rc = cls_check(p, gamma, "fdr_set_psf_cls");
+    if (rc != FDR_OK) return rc;
+    if (gamma == 0.f) return fdr_set_psf(p, psf_host, prows, pcols, pstride, K);
+    if (prows <= 0 || pcols <= 0 || pstride < pcols) return fail(FDR_ERR_ARG, "fdr_set_psf_cls: bad PSF shape");
+    if (prows > p->M || pcols > p->N) return fail(FDR_ERR_ARG, "fdr_set_psf_cls: PSF larger than the padded image");
+    FDR_HIP(hipSetDevice(p->device));
+    rc = ensure_psf_staging(p, (size_t)prows * pcols);
+    if (rc != FDR_OK) return rc;
+    {
+        ScopedPhase ph(p, FDR_PHASE_H2D, nullptr);
+        FDR_HIP(hipMemcpy2D(p->psf_dev, (size_t)pcols * sizeof(float), psf_host, (size_t)pstride * sizeof(float),
+                            (size_t)pcols * sizeof(float), prows, hipMemcpyHostToDevice));
+    }
+    rc = set_psf_dev_impl(p, p->psf_dev, prows, pcols, pcols, K, nullptr, gamma);
+    if (rc != FDR_OK) return rc;
+    FDR_HIP(hipStreamSynchronize(nullptr));
+    resolve_phases(p);
+    return FDR_OK;
+}
+
+int fdr_set_psf_motion_cls(fdr_plan* p, int size, double angle_deg, float K, float gamma, void* stream) {
+    if (!p || size <= 0) return fail(FDR_ERR_ARG, "fdr_set_psf_motion_cls: bad argument");
+    int rc = cls_check(p, gamma, "fdr_set_psf_motion_cls");
+    if (rc != FDR_OK) return rc;
+    if (gamma == 0.f) return fdr_set_psf_motion(p, size, angle_deg, K, stream);
+    if (size > p->M || size > p->N) return fail(FDR_ERR_ARG, "fdr_set_psf_motion_cls: PSF larger than the padded image");
+    FDR_HIP(hipSetDevice(p->device));
+    rc = ensure_psf_staging(p, (size_t)size * size);
+    if (rc != FDR_OK) return rc;
+    FDR_HIP(launch_psf_motion(size, angle_deg, p->psf_dev, (hipStream_t)stream));
+    return set_psf_dev_impl(p, p->psf_dev, size, size, size, K, (hipStream_t)stream, gamma);
 }
 
 int fdr_plan_filter_bytes(const fdr_plan* p, size_t* bytes) {

@@ -232,6 +232,35 @@ __device__ __forceinline__ float2 wiener_filter_fast(float2 h, float K) {
     return w;
 }
 
+// constrained least squares (fdr_set_psf_cls*): W = conj(H) / (|H|^2 + K + gamma L^2) with L = a_u + b_v the symbol of the
+// periodic 5-point Laplacian, a_u = 4 sin^2(pi u / M), b_v = 4 sin^2(pi v / N).  The double table `lap` holds a_0 .. a_{M-1}
+// then b_0 .. b_{N-1} (built on the host, fdr_api.hip); the quotient is evaluated in double and rounded once, as above.
+__device__ __forceinline__ double cls_reg(const double* __restrict__ lap, int M, int u, int v, double gamma) {
+    const double L = lap[u] + lap[M + v];
+    return gamma * (L * L);
+}
+__device__ __forceinline__ float2 cls_filter_fast(float2 h, float K, double reg) {
+    const double hr = h.x, hi = h.y;
+    const double denom = hr * hr + hi * hi + (double)K + reg;
+    float2 w = make_float2(0.f, 0.f);
+    if (denom != 0.0) { w.x = (float)(hr / denom); w.y = (float)(-hi / denom); }
+    return w;
+}
+// packed_column_filter_slot for the CLS quotient: W0 (column v = 0) and WN (column v = N/2) at row j = min(k, M - k) carry
+// the regularisers reg0 = gamma (a_j + b_0)^2 and regn = gamma (a_j + b_{N/2})^2
+__device__ __forceinline__ float2 packed_column_cls_slot(float2 ck, float2 cmk, int k, int M, float K, double reg0, double regn) {
+    const bool upper = k > M / 2;
+    const float2 c = upper ? cmk : ck, cm = upper ? ck : cmk;  // C[j], C[M - j]
+    const double h0r = 0.5 * ((double)c.x + cm.x), h0i = 0.5 * ((double)c.y - cm.y);
+    const double hnr = 0.5 * ((double)c.y + cm.y), hni = 0.5 * ((double)cm.x - c.x);
+    const double d0 = h0r * h0r + h0i * h0i + (double)K + reg0, dn = hnr * hnr + hni * hni + (double)K + regn;
+    const double w0r = d0 != 0.0 ? h0r / d0 : 0.0, w0i = d0 != 0.0 ? -h0i / d0 : 0.0;
+    const double wnr = dn != 0.0 ? hnr / dn : 0.0, wni = dn != 0.0 ? -hni / dn : 0.0;
+    if (k == 0 || k == M / 2) return make_float2((float)w0r, (float)wnr);
+    if (k < M / 2) return make_float2((float)w0r, (float)w0i);
+    return make_float2((float)wnr, (float)wni);
+}
+
 // One radix-2^LR step on RHO = 2^LR values x[0..RHO) holding Y_s[r + R q][k], q = 0..RHO-1, leaving
 // Y_{s+LR}[r][k + LP q'] in x[q'].
 template <int LR, class Pol>

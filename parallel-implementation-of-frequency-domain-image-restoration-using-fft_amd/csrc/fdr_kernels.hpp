@@ -116,6 +116,9 @@ hipError_t launch_rows4(int logl, RowIn in, RowOut out, const RowArgs& a, const 
 int rows4_minmax_partials(int logl, int M, int nimg, int half);
 // cols_panel: COL_FWD_FILTER (PSF spectrum -> W, in place) or COL_FUSED (FFT . W . IFFT)
 hipError_t launch_cols_panel(int logm, ColKind kind, const ColArgs& a, const float2* tw_fwd, hipStream_t s);
+// (fdr_cls.hip) the COL_FWD_FILTER pass with the constrained least-squares quotient W = conj(H) / (|H|^2 + K + gamma L^2) instead: lap = the
+// Laplacian table of the plan (a_u = 4 sin^2(pi u / M), u < M, then b_v = 4 sin^2(pi v / N), v < N; doubles, device memory)
+hipError_t launch_cols_panel_cls(int logm, const ColArgs& a, const double* lap, double gamma, const float2* tw_fwd, hipStream_t s);
 
 // reference-shaped and auxiliary kernels (fdr_aux.hip)
 hipError_t launch_pad_real_to_complex(const float* src, int rows, int cols, int stride, float2* dst, int M, int N,
@@ -130,6 +133,8 @@ hipError_t launch_long_gather(const float2* src, float2* dst, size_t rows, int L
 hipError_t launch_long_stage(const float2* src, float2* dst, size_t rows, int L, int half, const float2* tw, int mode, hipStream_t s);
 hipError_t launch_wiener_pointwise(float2* g, const float2* filt, size_t count, float K, int mode, hipStream_t s);
 hipError_t launch_make_filter_fast(const float2* H, float2* W, size_t count, float K, hipStream_t s);
+// (fdr_cls.hip) the same with the CLS quotient on a row-major M x N spectrum (simple path); lap as launch_cols_panel_cls
+hipError_t launch_make_filter_cls(const float2* H, float2* W, int M, int N, float K, const double* lap, double gamma, hipStream_t s);
 hipError_t launch_real_minmax(const float2* src, float* dst, int M, int N, int mm_rows, int mm_cols, float2* mm_part,
                               int* n_part, hipStream_t s);
 hipError_t launch_reduce_minmax(const float2* mm_part, int n_part, float* mm, hipStream_t s);
@@ -187,7 +192,8 @@ enum MixRowKind {
 enum MixColKind {
     MIX_COLS_FILTER = 0,  // PSF spectrum: forward columns, W = conj(H) / (|H|^2 + K) in place
     MIX_COLS_FUSED = 1,   // pass B: forward columns, multiply by W, inverse columns
-    MIX_COLS_C2C = 2      // fdr_fft2d_c2c: panel-major -> columns forward or inverse -> row-major M x N
+    MIX_COLS_C2C = 2,     // fdr_fft2d_c2c: panel-major -> columns forward or inverse -> row-major M x N
+    MIX_COLS_FILTER_CLS = 3  // MIX_COLS_FILTER with the CLS quotient W = conj(H) / (|H|^2 + K + gamma L^2) (lap, gamma)
 };
 struct MixRowArgs {
     MixLen len;          // length N
@@ -213,6 +219,8 @@ struct MixColArgs {
     int rows_in;          // rows of src that hold data (the others are taken as zero)
     int rows_out;         // FUSED: rows written back
     int inverse;          // C2C
+    const double* lap;    // FILTER_CLS: the Laplacian table (as launch_cols_panel_cls: M + N doubles)
+    double gamma;         // FILTER_CLS
 };
 // blocks = workgroups (rows / (2 B) or rows / B, rounded up); npanels = N / P
 hipError_t launch_mixed_rows(MixRowKind kind, const MixRowArgs& a, int blocks, hipStream_t s);

@@ -290,6 +290,14 @@ __global__ __launch_bounds__(1024) void mixed_cols_kernel(const MixColArgs a) {
         }
         return;
     }
+    if (KIND == MIX_COLS_FILTER_CLS) {  // the same with the CLS quotient: row m in natural order, column = the panel's first + c
+        const int n0 = blockIdx.x << a.logP;
+        for (int e = threadIdx.x; e < tot; e += T) {
+            const int m = e >> a.logP, c = e & (P - 1);
+            a.dst[base + e] = cls_filter_fast(mx_lds[(size_t)c * M + m], a.K, cls_reg(a.lap, M, m, n0 + c, a.gamma));
+        }
+        return;
+    }
     if (KIND == MIX_COLS_C2C) {  // panel -> row-major M x N
         const int n0 = blockIdx.x << a.logP;
         for (int e = threadIdx.x; e < tot; e += T) {
@@ -351,9 +359,11 @@ hipError_t launch_mixed_cols(MixColKind kind, const MixColArgs& a, int npanels, 
     const int threads = a.len.nt << a.logP;
     const size_t smem = ((size_t)a.len.L << a.logP) * sizeof(float2);
     if (threads > 1024 || smem > kMixMaxLds) return hipErrorInvalidValue;
-    void (*k)(const MixColArgs) = kind == MIX_COLS_FILTER ? mixed_cols_kernel<MIX_COLS_FILTER>
-                                : kind == MIX_COLS_C2C    ? mixed_cols_kernel<MIX_COLS_C2C>
-                                                          : mixed_cols_kernel<MIX_COLS_FUSED>;
+    if (kind == MIX_COLS_FILTER_CLS && a.lap == nullptr) return hipErrorInvalidValue;
+    void (*k)(const MixColArgs) = kind == MIX_COLS_FILTER     ? mixed_cols_kernel<MIX_COLS_FILTER>
+                                : kind == MIX_COLS_FILTER_CLS ? mixed_cols_kernel<MIX_COLS_FILTER_CLS>
+                                : kind == MIX_COLS_C2C        ? mixed_cols_kernel<MIX_COLS_C2C>
+                                                              : mixed_cols_kernel<MIX_COLS_FUSED>;
     hipError_t e = set_lds(k, smem);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k, dim3(npanels), dim3(threads), smem, s, a);

@@ -1,4 +1,5 @@
 // gpu.cpp -- ./gpu <img-path> <psf-length> <psf-angle> [--out file] [--mode fast|parity] [--norm padded|cropped] [--host-epilogue]
+//           [--cls gamma]
 // Drop-in counterpart of the reference's gpu.cpp (argument meaning, printed lines and exit codes as at
 // gpu.cpp:57-138 of the reference): read image, /255, PSF, K = 0.01, split BGR, warm-up call, timed
 // wienerDeblur_RGB_optimized, timed wienerDeblur_RGB_naive, merge, Lab white balance, 8-bit result.
@@ -69,6 +70,9 @@ int main(int argc, char** argv) {
         else if (a == "--verify") verify = true;
         else if (a == "--mode" && i + 1 < argc) fft_gpu::set_mode(string(argv[++i]) == "parity" ? FDR_MODE_PARITY : FDR_MODE_FAST);
         else if (a == "--norm" && i + 1 < argc) fft_gpu::set_norm_area(string(argv[++i]) == "cropped" ? FDR_NORM_CROPPED : FDR_NORM_PADDED);
+        // constrained least-squares filter (fdr_set_psf_cls) in the fft_gpu:: entry points; the serial leg keeps the Wiener filter.
+        // Fast mode only: with --mode parity the library refuses it and the first fft_gpu:: call exits with its message
+        else if (a == "--cls" && i + 1 < argc) fft_gpu::set_cls_gamma(strtof(argv[++i], nullptr));
         else { cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle>\n"; return -1; }
     }
 
