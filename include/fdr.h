@@ -74,6 +74,8 @@ extern "C" {
                               (serial.cpp:36-38 + fft/fft_serial.cpp:243-246)                 */
 #define FDR_NORM_CROPPED 0 /* reference GPU semantics: min/max over the cropped rows x cols
                               area only (fft/fft_gpu.cu:379-381)                              */
+#define FDR_NORM_NONE 2    /* fdr_richardson_lucy_* only: the raw estimate, not normalised (the fdr_wiener_* calls are
+                              unchanged: there any value but FDR_NORM_PADDED means CROPPED)  */
 
 typedef struct fdr_plan fdr_plan;
 
@@ -189,6 +191,43 @@ int fdr_wiener_f32_dev(fdr_plan* plan, const float* d_img, int rows, int cols, i
 int fdr_wiener_batch_f32_dev(fdr_plan* plan, const float* d_imgs, size_t img_pitch, int count,
                              int rows, int cols, int stride,
                              float* d_out, size_t out_pitch, int out_stride, int norm_area, void* stream);
+
+/* -- the forward blur operator and Richardson-Lucy deconvolution (RL; Richardson 1972, Lucy 1974: the iterative maximum-likelihood
+ *    deconvolution for Poisson noise, MATLAB's deconvlucy / scikit-image's richardson_lucy).  The plan is M x N, the image window
+ *    rows x cols at its top-left corner; pad(x) is x on the window and 0 elsewhere; the operator PSF p lies top-left in an M x N
+ *    zero plane exactly as fdr_set_psf places it, and H = DFT2(p), so RL and the Wiener filter invert the same blur model:
+ *        blur(x)   = window( IDFT2( H       . DFT2(pad(x)) ) )      (IDFT2 includes 1/(M N): a delta PSF gives blur(x) = x)
+ *        blur^T(y) = window( IDFT2( conj(H) . DFT2(pad(y)) ) )      (the adjoint: <blur x, y> = <x, blur^T y>)
+ *    Circular convolution on the plan: with rows = M, cols = N and a PSF the caller has rolled to put its centre at (0, 0),
+ *    fft_convolve of the reference's others/gen_blurred_img.ipynb.  RL with n iterations on the input window d:
+ *        d+ = max(d, 0);  u = d+;  n times:  c = blur(u);  r = c > FDR_RL_TAU ? d+ / c : 0;  u = max(u . blur^T(r), 0)
+ *    and the output is u on the window, normalised by norm_area: FDR_NORM_NONE the raw estimate, FDR_NORM_CROPPED min-max to
+ *    [0, 1] over the window, FDR_NORM_PADDED min-max over the M x N plan (u is 0 outside the window); a flat result comes out as
+ *    the fdr_wiener_* calls give a flat plane (all 0).  n = 0 returns d+.  Outside the window u and r stay 0.
+ *    Plans: FDR_MODE_FAST, M and N powers of two, 8 <= M <= 8192, 32 <= N <= 8192, neither FDR_FLAG_SIMPLE_PATH nor
+ *    FDR_FLAG_FULL_SPECTRUM (FDR_FLAG_MIXED_RADIX has no effect on such sizes); every other plan returns FDR_ERR_ARG before any
+ *    device work, a tables-only plan FDR_ERR_STATE, and the plan stays usable.  Batches, fdr_batch_run, fdr_slab_* and filter
+ *    export / import do not cover the operator.
+ *      fdr_set_operator_psf*   the operator PSF (validated as in fdr_set_psf*), held apart from the Wiener / CLS filter: setting
+ *                              either never changes the other.  The first call on a plan allocates the two operator tables
+ *                              (2 x fdr_plan_filter_bytes), kept until fdr_plan_destroy.  PRE phase.
+ *      fdr_blur_f32*           out = blur(img), or blur^T(img) with adjoint != 0.  FDR_ERR_STATE without an operator PSF.
+ *      fdr_richardson_lucy_f32*  n = iterations >= 0; FDR_ERR_ARG for a negative count, an unknown norm_area or an output
+ *                              window that overlaps the input (d is read on every iteration, u is kept in the output).
+ *    Shape errors as fdr_wiener_*.  The _dev forms are asynchronous on `stream` and allocate nothing; the host forms copy in
+ *    and out synchronously and count as COMPUTE (as fdr_wiener_f32).  A 4096^2 iteration moves about 64 bytes per padded
+ *    pixel.                                                                                        */
+#define FDR_RL_TAU 1e-7f /* the guard of the RL ratio: a blurred estimate c <= FDR_RL_TAU gives r = 0 */
+int fdr_set_operator_psf(fdr_plan* plan, const float* psf_host, int prows, int pcols, int pstride);
+int fdr_set_operator_psf_dev(fdr_plan* plan, const float* d_psf, int prows, int pcols, int pstride, void* stream);
+int fdr_set_operator_psf_motion(fdr_plan* plan, int size, double angle_deg, void* stream);
+int fdr_blur_f32(fdr_plan* plan, const float* img_host, int rows, int cols, int stride, float* out_host, int out_stride, int adjoint);
+int fdr_blur_f32_dev(fdr_plan* plan, const float* d_img, int rows, int cols, int stride, float* d_out, int out_stride, int adjoint,
+                     void* stream);
+int fdr_richardson_lucy_f32(fdr_plan* plan, const float* img_host, int rows, int cols, int stride, float* out_host, int out_stride,
+                            int iterations, int norm_area);
+int fdr_richardson_lucy_f32_dev(fdr_plan* plan, const float* d_img, int rows, int cols, int stride, float* d_out, int out_stride,
+                                int iterations, int norm_area, void* stream);
 
 /* Host-pointer batch: `count` images at imgs_host + i*img_pitch, results to out_host + i*out_pitch (elements).
  * H2D copy, restoration and D2H copy of consecutive images overlap on three internal streams with three images in

@@ -14,6 +14,7 @@
 // argument (Options); the argument-free overloads of the reference's signatures use process-wide defaults.
 #pragma once
 #include "../utils.hpp"
+#include <algorithm>
 #include <atomic>
 #include <complex>
 #include <iostream>
@@ -190,6 +191,27 @@ inline void wienerDeblur_RGB_naive(std::vector<Mat>& channels, const Mat& psf, f
     wienerDeblur_RGB_naive(channels, psf, K, defaults());
 }
 
+// Richardson-Lucy deconvolution (fdr_richardson_lucy_f32, include/fdr.h) of every channel, `iterations` steps each, in place: one
+// cached FDR_MODE_FAST plan (each dimension padded to the next power of two, at least 8 rows and 32 columns; the padding stays
+// zero), the operator PSF set once, each channel normalised by o.norm_area.  o.mode and o.cls_gamma do not apply.
+inline void richardsonLucy_RGB(std::vector<Mat>& channels, const Mat& psf, int iterations, const Options& o) {
+    if (channels.empty()) return;
+    const int rows = channels[0].rows, cols = channels[0].cols;
+    bool created = false;
+    PlanCacheSettle settle_;
+    fdr_plan* plan = plan_cache().get(o.device, std::max(8, nextPowerOfTwo(rows)), std::max(32, nextPowerOfTwo(cols)), FDR_MODE_FAST, &created);
+    Mat psfc = psf.isContinuous() ? psf : psf.clone();
+    FDR_CHECK(fdr_set_operator_psf(plan, psfc.ptr<float>(0), psf.rows, psf.cols, psf.cols));
+    for (Mat& c : channels) {
+        Mat src = c.isContinuous() ? c : c.clone();
+        Mat out(c.rows, c.cols, CV_32F);
+        FDR_CHECK(fdr_richardson_lucy_f32(plan, src.ptr<float>(0), c.rows, c.cols, c.cols, out.ptr<float>(0), c.cols, iterations, o.norm_area));
+        c = out;
+    }
+}
+inline void richardsonLucy_RGB(std::vector<Mat>& channels, const Mat& psf, int iterations) {
+    richardsonLucy_RGB(channels, psf, iterations, defaults());
+}
 // The operator exactly as fft_serial::wienerDeblur_myfft defines it (fft/fft_serial.cpp:141-261; the fft_gpu
 // declaration at fft/fft.hpp:44 has no body in the reference): pad to getOptimalDFTSize (2^a 3^b 5^c, :153-154 -- a
 // non-power-of-two dimension is transformed by the naive DFT, :100-101), restore, crop to img's size, normalise over

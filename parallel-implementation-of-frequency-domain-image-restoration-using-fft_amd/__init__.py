@@ -27,6 +27,7 @@ FLAG_TABLES_ONLY = 1024
 FLAG_MIXED_RADIX = 2048
 NORM_PADDED = 1
 NORM_CROPPED = 0
+NORM_NONE = 2  # Richardson-Lucy only: the raw estimate
 MAX_PASSES = 16
 OPT_TWO_SWEEP_NORM = 2
 OPT_BATCH_GRAPH = 3
@@ -137,6 +138,13 @@ def _load():
     L.fdr_dft_naive_c2c.argtypes = [vp, ci, ci]
     L.fdr_synth_image_dev.argtypes = [ci, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_size_t, vp, vp]
     L.fdr_plan_profile.argtypes = [vp, ci]
+    L.fdr_set_operator_psf.argtypes = [vp, vp, ci, ci, ci]
+    L.fdr_set_operator_psf_dev.argtypes = [vp, vp, ci, ci, ci, vp]
+    L.fdr_set_operator_psf_motion.argtypes = [vp, ci, cd, vp]
+    L.fdr_blur_f32.argtypes = [vp, vp, ci, ci, ci, vp, ci, ci]
+    L.fdr_blur_f32_dev.argtypes = [vp, vp, ci, ci, ci, vp, ci, ci, vp]
+    L.fdr_richardson_lucy_f32.argtypes = [vp, vp, ci, ci, ci, vp, ci, ci, ci]
+    L.fdr_richardson_lucy_f32_dev.argtypes = [vp, vp, ci, ci, ci, vp, ci, ci, ci, vp]
     L.fdr_plan_pass_times.argtypes = [vp, ctypes.POINTER(ci), _f32p, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ci)]
     for name in ("fdr_device_count", "fdr_next_pow2", "fdr_is_pow2", "fdr_plan_create", "fdr_plan_destroy", "fdr_plan_dims",
                  "fdr_psf_motion", "fdr_psf_motion_dev", "fdr_set_psf", "fdr_set_psf_dev", "fdr_set_psf_motion",
@@ -147,7 +155,8 @@ def _load():
                  "fdr_slab_pad_dev", "fdr_slab_rows_fft_dev", "fdr_slab_pack_dev", "fdr_slab_transpose_dev", "fdr_slab_wiener_dev",
                  "fdr_slab_real_dev", "fdr_slab_minmax_dev", "fdr_slab_normalize_dev", "fdr_warp_affine_f32",
                  "fdr_plan_filter_bytes", "fdr_plan_export_filter_dev", "fdr_plan_import_filter_dev",
-                 "fdr_set_psf_cls", "fdr_set_psf_cls_dev", "fdr_set_psf_motion_cls"):
+                 "fdr_set_psf_cls", "fdr_set_psf_cls_dev", "fdr_set_psf_motion_cls", "fdr_set_operator_psf", "fdr_set_operator_psf_dev",
+                 "fdr_set_operator_psf_motion", "fdr_blur_f32", "fdr_blur_f32_dev", "fdr_richardson_lucy_f32", "fdr_richardson_lucy_f32_dev"):
         getattr(L, name).restype = ci
     return L
 
@@ -165,7 +174,8 @@ EXPORTED_SYMBOLS = (
     "fdr_slab_pad_dev", "fdr_slab_rows_fft_dev", "fdr_slab_pack_dev", "fdr_slab_transpose_dev", "fdr_slab_wiener_dev",
     "fdr_slab_real_dev", "fdr_slab_minmax_dev", "fdr_slab_normalize_dev", "fdr_warp_affine_f32",
     "fdr_plan_filter_bytes", "fdr_plan_export_filter_dev", "fdr_plan_import_filter_dev",
-    "fdr_set_psf_cls", "fdr_set_psf_cls_dev", "fdr_set_psf_motion_cls")
+    "fdr_set_psf_cls", "fdr_set_psf_cls_dev", "fdr_set_psf_motion_cls", "fdr_set_operator_psf", "fdr_set_operator_psf_dev",
+    "fdr_set_operator_psf_motion", "fdr_blur_f32", "fdr_blur_f32_dev", "fdr_richardson_lucy_f32", "fdr_richardson_lucy_f32_dev")
 
 
 def _check(rc):
@@ -381,6 +391,40 @@ class Plan:
         _check(lib.fdr_wiener_batch_f32(self._h, _ptr(imgs), rows * cols, cnt, rows, cols, cols, _ptr(out), rows * cols, cols, int(norm_area)))
         return out
 
+    # the blur operator and Richardson-Lucy (include/fdr.h): an operator PSF of its own, apart from the Wiener / CLS filter
+    def set_operator_psf(self, psf):
+        psf = np.ascontiguousarray(psf, dtype=np.float32)
+        _check(lib.fdr_set_operator_psf(self._h, _ptr(psf), psf.shape[0], psf.shape[1], psf.shape[1]))
+
+    def set_operator_psf_dev(self, d_ptr, prows, pcols, pstride, stream=None):
+        _check(lib.fdr_set_operator_psf_dev(self._h, ctypes.c_void_p(int(d_ptr)), prows, pcols, pstride, _stream(stream)))
+
+    def set_operator_psf_motion(self, size, angle, stream=None):
+        _check(lib.fdr_set_operator_psf_motion(self._h, int(size), float(angle), _stream(stream)))
+
+    def blur(self, img, adjoint=False):
+        """blur(img) = window(IDFT2(H . DFT2(pad(img)))), or the adjoint with conj(H); host arrays."""
+        img = np.ascontiguousarray(img, dtype=np.float32)
+        out = np.empty_like(img)
+        _check(lib.fdr_blur_f32(self._h, _ptr(img), img.shape[0], img.shape[1], img.shape[1], _ptr(out), img.shape[1], int(bool(adjoint))))
+        return out
+
+    def blur_dev(self, d_img, rows, cols, stride, d_out, out_stride, adjoint=False, stream=None):
+        _check(lib.fdr_blur_f32_dev(self._h, ctypes.c_void_p(int(d_img)), rows, cols, stride, ctypes.c_void_p(int(d_out)), out_stride,
+                                    int(bool(adjoint)), _stream(stream)))
+
+    def richardson_lucy(self, img, iterations, norm_area=NORM_NONE):
+        """`iterations` Richardson-Lucy steps on the window img (host arrays), normalised by norm_area."""
+        img = np.ascontiguousarray(img, dtype=np.float32)
+        out = np.empty_like(img)
+        _check(lib.fdr_richardson_lucy_f32(self._h, _ptr(img), img.shape[0], img.shape[1], img.shape[1], _ptr(out), img.shape[1],
+                                           int(iterations), int(norm_area)))
+        return out
+
+    def richardson_lucy_dev(self, d_img, rows, cols, stride, d_out, out_stride, iterations, norm_area=NORM_NONE, stream=None):
+        _check(lib.fdr_richardson_lucy_f32_dev(self._h, ctypes.c_void_p(int(d_img)), rows, cols, stride, ctypes.c_void_p(int(d_out)),
+                                               out_stride, int(iterations), int(norm_area), _stream(stream)))
+
     def set_concurrency(self, nstreams):
         """Batched mode: alternate images over `nstreams` private workspaces / internal streams."""
         _check(lib.fdr_plan_set_concurrency(self._h, int(nstreams)))
@@ -491,6 +535,22 @@ def wienerDeblur_myfft_unpadded(img, psf, K, mode=MODE_PARITY, device=0, mixed_r
     with Plan(M, N, mode, device, flags=flags) as p:
         p.set_psf(psf, K, gamma=cls_gamma)
         return p.wiener(img, NORM_CROPPED)
+
+
+def _rl_plan_size(rows, cols):
+    """the plan richardsonLucy_myfft pads to: the next power of two, at least 8 rows and 32 columns"""
+    return max(8, nextPowerOfTwo(rows)), max(32, nextPowerOfTwo(cols))
+
+
+def richardsonLucy_myfft(img, psf, iterations, device=0, norm_area=NORM_NONE):
+    """Richardson-Lucy deconvolution of one channel: pad each dimension to the next power of two (at least 8 rows and 32
+    columns; the padding is zero and stays zero), `iterations` steps on the device, crop.  psf lies top-left in the plan, as
+    for the Wiener calls."""
+    img = np.asarray(img, dtype=np.float32)
+    M, N = _rl_plan_size(img.shape[0], img.shape[1])
+    with Plan(M, N, MODE_FAST, device) as p:
+        p.set_operator_psf(psf)
+        return p.richardson_lucy(img, iterations, norm_area)
 
 
 def batch_run(devices, M, N, count, rows=None, cols=None, mode=MODE_FAST, flags=0, psf=None, psf_size=50, psf_angle=30.0, K=0.01,

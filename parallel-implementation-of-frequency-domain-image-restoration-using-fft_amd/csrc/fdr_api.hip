@@ -197,6 +197,11 @@ struct fdr_plan {
     float K = 0.f;
     bool have_psf = false;
     double* lap = nullptr;  // CLS filters (fdr_set_psf_cls*): a_u = 4 sin^2(pi u / M), u < M, then b_v = 4 sin^2(pi v / N), v < N
+    // blur / Richardson-Lucy operator (fdr_set_operator_psf*): H / (M N) and conj(H) / (M N) in the layout of `filt`, one allocation
+    // of 2 ws_elems (op_c = op_h + ws_elems), made by the first fdr_set_operator_psf* call; independent of `filt`
+    float2* op_h = nullptr;
+    float2* op_c = nullptr;
+    bool have_op = false;
     PassTimer timer;
     // the reference Profiler's buckets (fdr_plan_phase_times): resolved sums + event pairs not read back yet
     struct PhaseRec { hipEvent_t a, b; int phase; };
@@ -378,6 +383,16 @@ const char* const kPassMixedRows = "A mixed rows: pad+FFT (real pairs)";
 const char* const kPassMixedCols = "B mixed cols: FFT*W*IFFT";
 const char* const kPassMixedRowsInv = "C mixed rows: IFFT+real+minmax";
 const char* const kPassMixedNorm = "E mixed normalize+crop";
+const char* const kPassOpRowsPsf = "O rows: PSF pad+FFT (operator)";
+const char* const kPassOpCols = "O cols: FFT -> H/MN, conj(H)/MN";
+const char* const kPassOpRowsFwd = "A op rows: pad+FFT (blur / RL)";
+const char* const kPassOpColsH = "B' op cols: FFT*H*IFFT";
+const char* const kPassOpColsConj = "B' op cols: FFT*conj(H)*IFFT";
+const char* const kPassOpRowsBlur = "C op rows: IFFT+crop (blur)";
+const char* const kPassRlInit = "RL init: u = max(d, 0)";
+const char* const kPassRlRatio = "C op rows: IFFT+RL ratio";
+const char* const kPassRlUpdate = "C op rows: IFFT+RL update";
+const char* const kPassRlNorm = "E RL minmax+normalize";
 
 int upload(float2** dst, const std::vector<float2>& v) {
     FDR_HIP(hipMalloc((void**)dst, v.size() * sizeof(float2)));
@@ -795,11 +810,219 @@ int cls_check(const fdr_plan* p, float gamma, const char* fn) {
     return FDR_OK;
 }
 
+// device staging of the host-pointer single-image calls (fdr_wiener_f32, fdr_blur_f32, fdr_richardson_lucy_f32): two M x N
+// float buffers, made on first use and kept
+int ensure_stage(fdr_plan* p, size_t bytes, const char* fn) {
+    if (p->stage_cap >= bytes) return FDR_OK;
+    (void)hipFree(p->stage_in); (void)hipFree(p->stage_out);
+    p->stage_in = p->stage_out = nullptr; p->stage_cap = 0;
+    const size_t cap = (size_t)p->M * p->N * sizeof(float);
+    if (hipMalloc((void**)&p->stage_in, cap) != hipSuccess || hipMalloc((void**)&p->stage_out, cap) != hipSuccess) {
+        (void)hipFree(p->stage_in); p->stage_in = nullptr;
+        return fail(FDR_ERR_ALLOC, std::string(fn) + ": hipMalloc of the staging buffers failed");
+    }
+    p->stage_cap = cap;
+    return FDR_OK;
+}
+
 int ensure_psf_staging(fdr_plan* p, size_t elems) {
     if (p->psf_cap >= elems) return FDR_OK;
     if (p->psf_dev) { (void)hipFree(p->psf_dev); p->psf_dev = nullptr; p->psf_cap = 0; }
     FDR_HIP(hipMalloc((void**)&p->psf_dev, elems * sizeof(float)));
     p->psf_cap = elems;
+    return FDR_OK;
+}
+
+// ---- the blur operator and Richardson-Lucy (fdr_rl.hip): passes A, B' and C of the fast half-spectrum path with the operator
+// tables in place of W and the operator kinds of the inverse row pass ----
+static_assert(kRlTau == FDR_RL_TAU, "the ratio guard of the kernels is FDR_RL_TAU");
+
+// the plans these calls run on; everything else is refused before any device work (a tables-only plan FDR_ERR_STATE)
+int op_plan_check(const fdr_plan* p, const char* fn) {
+    if (p->tables_only) return fail(FDR_ERR_STATE, std::string(fn) + ": plan was created with FDR_FLAG_TABLES_ONLY (slab primitives only)");
+    if (p->mode != FDR_MODE_FAST || !p->panel || !p->half || p->mixed || p->logM < 3 || p->logM > kMaxLdsLog || p->logN < 5 ||
+        p->logN > kMaxLdsLog)
+        return fail(FDR_ERR_ARG, std::string(fn) + ": needs a FDR_MODE_FAST plan on the half-spectrum panel path (M, N powers of two, "
+                                                   "8 <= M <= 8192, 32 <= N <= 8192, neither FDR_FLAG_SIMPLE_PATH nor FDR_FLAG_FULL_SPECTRUM)");
+    return FDR_OK;
+}
+
+// plan, operator PSF and window of a blur / RL call
+int op_image_check(const fdr_plan* p, const char* fn, const float* d_img, int rows, int cols, int stride, const float* d_out, int out_stride) {
+    int rc = op_plan_check(p, fn);
+    if (rc != FDR_OK) return rc;
+    if (!d_img || !d_out) return fail(FDR_ERR_ARG, std::string(fn) + ": null image pointer");
+    if (rows <= 0 || cols <= 0 || rows > p->M || cols > p->N || stride < cols || out_stride < cols)
+        return fail(FDR_ERR_ARG, std::string(fn) + ": image shape does not fit the plan");
+    if (!p->have_op) return fail(FDR_ERR_STATE, std::string(fn) + ": no operator PSF set on this plan (call fdr_set_operator_psf* first)");
+    return FDR_OK;
+}
+
+int rl_arg_check(const char* fn, int iterations, int norm_area) {
+    if (iterations < 0) return fail(FDR_ERR_ARG, std::string(fn) + ": iterations < 0");
+    if (norm_area != FDR_NORM_NONE && norm_area != FDR_NORM_CROPPED && norm_area != FDR_NORM_PADDED)
+        return fail(FDR_ERR_ARG, std::string(fn) + ": unknown norm_area");
+    return FDR_OK;
+}
+
+// the PSF top-left in the M x N plane -> its row spectra (the rows it reaches) -> H / (M N) into op_h, conj(H) / (M N) into op_c
+int set_operator_psf_impl(fdr_plan* p, const float* d_psf, int prows, int pcols, int pstride, hipStream_t s) {
+    if (!p->op_h) {
+        float2* t = nullptr;
+        if (hipMalloc((void**)&t, 2 * p->ws_elems * sizeof(float2)) != hipSuccess)
+            return fail(FDR_ERR_ALLOC, "fdr_set_operator_psf: hipMalloc of the operator tables failed");
+        p->op_h = t;
+        p->op_c = t + p->ws_elems;
+    }
+    ScopedPhase phase(p, FDR_PHASE_PRE, s);
+    const int nvalid = (prows + 3) & ~3;  // <= M (M is a multiple of 8 on this path)
+    {
+        ScopedPass t(p, s, kPassOpRowsPsf);
+        RowArgs ra{};
+        ra.src_real = d_psf; ra.src_rows = prows; ra.src_cols = pcols; ra.src_stride = pstride;
+        ra.dst_c = p->op_h; ra.M = nvalid; ra.pstride = p->pstride; ra.half = 1; ra.num_cu = p->num_cu;
+        FDR_HIP(launch_rows4(p->logN, ROW_IN_REAL, ROW_OUT_COMPLEX, ra, p->tw_row_f, s));
+    }
+    {
+        ScopedPass t(p, s, kPassOpCols);
+        ColArgs ca{};
+        ca.data = p->op_h; ca.N = p->N; ca.num_cu = p->num_cu; ca.pstride = p->pstride; ca.npanels = p->npanels;
+        ca.nvalid = nvalid; ca.packed0 = 1;
+        FDR_HIP(launch_cols_panel_operator(p->logM, ca, p->op_c, p->tw_col_f, s));
+    }
+    p->have_op = true;
+    return FDR_OK;
+}
+
+int op_psf_shape_check(const fdr_plan* p, const char* fn, int prows, int pcols, int pstride) {
+    int rc = op_plan_check(p, fn);
+    if (rc != FDR_OK) return rc;
+    if (prows <= 0 || pcols <= 0 || pstride < pcols) return fail(FDR_ERR_ARG, std::string(fn) + ": bad PSF shape");
+    if (prows > p->M || pcols > p->N) return fail(FDR_ERR_ARG, std::string(fn) + ": PSF larger than the padded image");
+    return FDR_OK;
+}
+
+// pass A: the window of x (zero elsewhere) -> the half spectrum of slot 0
+int op_rows_fwd(fdr_plan* p, const float* x, int rows, int cols, int stride, hipStream_t s) {
+    ScopedPass t(p, s, kPassOpRowsFwd);
+    RowArgs a{};
+    a.src_real = x; a.src_rows = rows; a.src_cols = cols; a.src_stride = stride;
+    a.dst_c = p->work; a.M = p->M; a.pstride = p->pstride; a.half = 1; a.num_cu = p->num_cu;
+    FDR_HIP(launch_rows4(p->logN, ROW_IN_REAL, ROW_OUT_COMPLEX, a, p->tw_row_f, s));
+    return FDR_OK;
+}
+// pass B', unchanged, on one of the operator tables
+int op_cols(fdr_plan* p, bool adjoint, hipStream_t s) {
+    ScopedPass t(p, s, adjoint ? kPassOpColsConj : kPassOpColsH);
+    ColArgs c{};
+    c.data = p->work; c.filt = adjoint ? p->op_c : p->op_h; c.N = p->N; c.num_cu = p->num_cu;
+    c.pstride = p->pstride; c.npanels = p->npanels; c.packed0 = 1;
+    c.batch.nimg = 1; c.batch.data[0] = p->work;
+    FDR_HIP(launch_cols_panel(p->logM, COL_FUSED, c, p->tw_col_f, s));
+    return FDR_OK;
+}
+// pass C with an operator kind: the window rows x cols of the inverse transform through the kind's epilogue into `out`
+int op_rows_inv(fdr_plan* p, RowOut kind, const char* name, const float* src, int src_stride, float* out, int out_stride, int rows,
+                int cols, hipStream_t s) {
+    ScopedPass t(p, s, name);
+    RowArgs a{};
+    a.src_c = p->work; a.M = p->M; a.pstride = p->pstride; a.half = 1; a.num_cu = p->num_cu;
+    a.src_real = src; a.src_stride = src_stride;
+    a.out = out; a.out_rows = rows; a.out_cols = cols; a.out_stride = out_stride;
+    FDR_HIP(launch_rows4(p->logN, ROW_IN_COMPLEX, kind, a, p->tw_row_f, s));
+    return FDR_OK;
+}
+
+int blur_dev_impl(fdr_plan* p, const float* d_img, int rows, int cols, int stride, float* d_out, int out_stride, int adjoint, hipStream_t s) {
+    int rc = op_image_check(p, "fdr_blur_f32", d_img, rows, cols, stride, d_out, out_stride);
+    if (rc == FDR_OK) rc = op_rows_fwd(p, d_img, rows, cols, stride, s);
+    if (rc == FDR_OK) rc = op_cols(p, adjoint != 0, s);
+    if (rc == FDR_OK) rc = op_rows_inv(p, ROW_OUT_BLUR, kPassOpRowsBlur, nullptr, 0, d_out, out_stride, rows, cols, s);
+    return rc;
+}
+
+// [lo, hi) of the elements a rows x cols window with row stride `stride` spans
+bool windows_overlap(const float* a, int a_stride, const float* b, int b_stride, int rows, int cols) {
+    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + ((size_t)(rows - 1) * a_stride + cols) * sizeof(float);
+    const uintptr_t b0 = (uintptr_t)b, b1 = b0 + ((size_t)(rows - 1) * b_stride + cols) * sizeof(float);
+    return a0 < b1 && b0 < a1;
+}
+
+// u (the estimate) lives in d_out; r in the window of the raw plane (row stride cols), the spectrum in slot 0's work.  With a
+// normalisation the last update (or, for no iterations, the initial estimate) goes to the raw plane instead, and the normalise
+// pass writes d_out from there.
+int rl_dev_impl(fdr_plan* p, const float* d_img, int rows, int cols, int stride, float* d_out, int out_stride, int iterations,
+                int norm_area, hipStream_t s) {
+    const char* fn = "fdr_richardson_lucy_f32";
+    int rc = op_image_check(p, fn, d_img, rows, cols, stride, d_out, out_stride);
+    if (rc == FDR_OK) rc = rl_arg_check(fn, iterations, norm_area);
+    if (rc != FDR_OK) return rc;
+    if (windows_overlap(d_img, stride, d_out, out_stride, rows, cols))
+        return fail(FDR_ERR_ARG, std::string(fn) + ": d_out overlaps the input (the input is read on every iteration)");
+    const bool norm = norm_area != FDR_NORM_NONE;
+    float* r = p->raw;
+    const int rs = cols;
+    float* fin = norm ? p->raw : d_out;  // where the final estimate is written
+    const int fs = norm ? rs : out_stride;
+    {
+        ScopedPass t(p, s, kPassRlInit);
+        FDR_HIP(launch_rl_init(d_img, rows, cols, stride, iterations == 0 ? fin : d_out, iterations == 0 ? fs : out_stride, s));
+    }
+    for (int it = 0; it < iterations && rc == FDR_OK; ++it) {
+        const bool last = it == iterations - 1;
+        rc = op_rows_fwd(p, d_out, rows, cols, out_stride, s);                                            // c = blur(u) ...
+        if (rc == FDR_OK) rc = op_cols(p, false, s);
+        if (rc == FDR_OK) rc = op_rows_inv(p, ROW_OUT_RL_RATIO, kPassRlRatio, d_img, stride, r, rs, rows, cols, s);  // ... r = d+ / c
+        if (rc == FDR_OK) rc = op_rows_fwd(p, r, rows, cols, rs, s);                                      // g = blur^T(r) ...
+        if (rc == FDR_OK) rc = op_cols(p, true, s);
+        if (rc == FDR_OK)
+            rc = op_rows_inv(p, ROW_OUT_RL_UPDATE, kPassRlUpdate, d_out, out_stride, last ? fin : d_out, last ? fs : out_stride, rows,
+                             cols, s);                                                                    // ... u = max(u g, 0)
+    }
+    if (rc != FDR_OK || !norm) return rc;
+    // min-max to [0, 1] over the window; FDR_NORM_PADDED also counts the zeros of u outside it (one extra (0, 0) partial)
+    ScopedPass t(p, s, kPassRlNorm);
+    int n_part = 0;
+    FDR_HIP(launch_minmax_real(fin, rows, fs, rows, cols, p->mm_part, &n_part, s));
+    if (norm_area == FDR_NORM_PADDED && (rows < p->M || cols < p->N)) {
+        if (n_part + 1 > p->mm_part_cap) return fail(FDR_ERR_STATE, std::string(fn) + ": min/max partial count out of range");
+        FDR_HIP(hipMemsetAsync(p->mm_part + n_part, 0, sizeof(float2), s));  // (0.f, 0.f)
+        ++n_part;
+    }
+    if (n_part <= 0 || n_part > p->mm_part_cap) return fail(FDR_ERR_STATE, std::string(fn) + ": min/max partial count out of range");
+    FDR_HIP(launch_reduce_minmax(p->mm_part, n_part, p->mm, s));
+    FDR_HIP(launch_normalize(fin, fs, nullptr, 0, p->mm, d_out, rows, cols, out_stride, s));
+    return FDR_OK;
+}
+
+// the host-pointer form of a blur / RL call: image in through the plan's staging, `run(d_in, d_out)` on the null stream (COMPUTE
+// phase), result out; synchronous.  The caller has validated everything that can be refused.
+template <class F>
+int op_host_call(fdr_plan* p, const char* fn, const float* img_host, int rows, int cols, int stride, float* out_host, int out_stride, F run) {
+    const size_t bytes = (size_t)rows * cols * sizeof(float);
+    int rc = ensure_stage(p, bytes, fn);
+    if (rc != FDR_OK) return rc;
+    float *d_in = p->stage_in, *d_out = p->stage_out;
+    hipError_t e;
+    {
+        ScopedPhase ph(p, FDR_PHASE_H2D, nullptr);
+        if (stride == cols) e = hipMemcpy(d_in, img_host, bytes, hipMemcpyHostToDevice);
+        else e = hipMemcpy2D(d_in, (size_t)cols * sizeof(float), img_host, (size_t)stride * sizeof(float), (size_t)cols * sizeof(float), rows,
+                             hipMemcpyHostToDevice);
+    }
+    if (e == hipSuccess) {
+        ScopedPhase ph(p, FDR_PHASE_COMPUTE, nullptr);
+        rc = run(d_in, d_out);
+    }
+    if (e == hipSuccess && rc == FDR_OK) {
+        ScopedPhase ph(p, FDR_PHASE_D2H, nullptr);
+        if (out_stride == cols) e = hipMemcpy(out_host, d_out, bytes, hipMemcpyDeviceToHost);
+        else e = hipMemcpy2D(out_host, (size_t)out_stride * sizeof(float), d_out, (size_t)cols * sizeof(float), (size_t)cols * sizeof(float),
+                             rows, hipMemcpyDeviceToHost);
+    }
+    if (e == hipSuccess) resolve_phases(p);
+    if (rc != FDR_OK) return rc;
+    FDR_HIP(e);
     return FDR_OK;
 }
 
@@ -1025,7 +1248,7 @@ int fdr_plan_destroy(fdr_plan* p) {
     p->phase_pending.clear();
     p->timer.destroy();
     (void)hipFree(p->work); (void)hipFree(p->work2); (void)hipFree(p->filt); (void)hipFree(p->raw);
-    (void)hipFree(p->psf_dev); (void)hipFree(p->mm); (void)hipFree(p->mm_part); (void)hipFree(p->lap);
+    (void)hipFree(p->psf_dev); (void)hipFree(p->mm); (void)hipFree(p->mm_part); (void)hipFree(p->lap); (void)hipFree(p->op_h);
     (void)hipFree(p->stage_in); (void)hipFree(p->stage_out);
     delete p;
     return FDR_OK;
@@ -1219,6 +1442,82 @@ int fdr_wiener_f32_dev(fdr_plan* p, const float* d_img, int rows, int cols, int 
     return wiener_dev_impl(p, p->slots[0], d_img, rows, cols, stride, d_out, out_stride, norm_area, (hipStream_t)stream);
 }
 
+int fdr_set_operator_psf_dev(fdr_plan* p, const float* d_psf, int prows, int pcols, int pstride, void* stream) {
+    if (!p || !d_psf) return fail(FDR_ERR_ARG, "fdr_set_operator_psf_dev: null argument");
+    int rc = op_psf_shape_check(p, "fdr_set_operator_psf_dev", prows, pcols, pstride);
+    if (rc != FDR_OK) return rc;
+    FDR_HIP(hipSetDevice(p->device));
+    return set_operator_psf_impl(p, d_psf, prows, pcols, pstride, (hipStream_t)stream);
+}
+
+int fdr_set_operator_psf(fdr_plan* p, const float* psf_host, int prows, int pcols, int pstride) {
+    if (!p || !psf_host) return fail(FDR_ERR_ARG, "fdr_set_operator_psf: null argument");
+    int rc = op_psf_shape_check(p, "fdr_set_operator_psf", prows, pcols, pstride);
+    if (rc != FDR_OK) return rc;
+    FDR_HIP(hipSetDevice(p->device));
+    rc = ensure_psf_staging(p, (size_t)prows * pcols);
+    if (rc != FDR_OK) return rc;
+    {
+        ScopedPhase ph(p, FDR_PHASE_H2D, nullptr);
+        FDR_HIP(hipMemcpy2D(p->psf_dev, (size_t)pcols * sizeof(float), psf_host, (size_t)pstride * sizeof(float),
+                            (size_t)pcols * sizeof(float), prows, hipMemcpyHostToDevice));
+    }
+    rc = set_operator_psf_impl(p, p->psf_dev, prows, pcols, pcols, nullptr);
+    if (rc != FDR_OK) return rc;
+    FDR_HIP(hipStreamSynchronize(nullptr));
+    resolve_phases(p);
+    return FDR_OK;
+}
+
+int fdr_set_operator_psf_motion(fdr_plan* p, int size, double angle_deg, void* stream) {
+    if (!p || size <= 0) return fail(FDR_ERR_ARG, "fdr_set_operator_psf_motion: bad argument");
+    int rc = op_psf_shape_check(p, "fdr_set_operator_psf_motion", size, size, size);
+    if (rc != FDR_OK) return rc;
+    FDR_HIP(hipSetDevice(p->device));
+    rc = ensure_psf_staging(p, (size_t)size * size);
+    if (rc != FDR_OK) return rc;
+    FDR_HIP(launch_psf_motion(size, angle_deg, p->psf_dev, (hipStream_t)stream));
+    return set_operator_psf_impl(p, p->psf_dev, size, size, size, (hipStream_t)stream);
+}
+
+int fdr_blur_f32_dev(fdr_plan* p, const float* d_img, int rows, int cols, int stride, float* d_out, int out_stride, int adjoint, void* stream) {
+    if (!p) return fail(FDR_ERR_ARG, "fdr_blur_f32_dev: null plan");
+    FDR_HIP(hipSetDevice(p->device));
+    return blur_dev_impl(p, d_img, rows, cols, stride, d_out, out_stride, adjoint, (hipStream_t)stream);
+}
+
+int fdr_blur_f32(fdr_plan* p, const float* img_host, int rows, int cols, int stride, float* out_host, int out_stride, int adjoint) {
+    if (!p || !img_host || !out_host) return fail(FDR_ERR_ARG, "fdr_blur_f32: null argument");
+    int rc = op_image_check(p, "fdr_blur_f32", img_host, rows, cols, stride, out_host, out_stride);
+    if (rc != FDR_OK) return rc;
+    FDR_HIP(hipSetDevice(p->device));
+    return op_host_call(p, "fdr_blur_f32", img_host, rows, cols, stride, out_host, out_stride, [&](const float* d_in, float* d_out) {
+        return blur_dev_impl(p, d_in, rows, cols, cols, d_out, cols, adjoint, nullptr);
+    });
+}
+
+int fdr_richardson_lucy_f32_dev(fdr_plan* p, const float* d_img, int rows, int cols, int stride, float* d_out, int out_stride, int iterations,
+                                int norm_area, void* stream) {
+    if (!p) return fail(FDR_ERR_ARG, "fdr_richardson_lucy_f32_dev: null plan");
+    FDR_HIP(hipSetDevice(p->device));
+    return rl_dev_impl(p, d_img, rows, cols, stride, d_out, out_stride, iterations, norm_area, (hipStream_t)stream);
+}
+
+int fdr_richardson_lucy_f32(fdr_plan* p, const float* img_host, int rows, int cols, int stride, float* out_host, int out_stride,
+                            int iterations, int norm_area) {
+    const char* fn = "fdr_richardson_lucy_f32";
+    if (!p || !img_host || !out_host) return fail(FDR_ERR_ARG, std::string(fn) + ": null argument");
+    int rc = op_image_check(p, fn, img_host, rows, cols, stride, out_host, out_stride);
+    if (rc == FDR_OK) rc = rl_arg_check(fn, iterations, norm_area);
+    if (rc != FDR_OK) return rc;
+    if (windows_overlap(img_host, stride, out_host, out_stride, rows, cols))
+        return fail(FDR_ERR_ARG, std::string(fn) + ": out_host overlaps the input");
+    FDR_HIP(hipSetDevice(p->device));
+    return op_host_call(p, fn, img_host, rows, cols, stride, out_host, out_stride, [&](const float* d_in, float* d_out) {
+        return rl_dev_impl(p, d_in, rows, cols, cols, d_out, cols, iterations, norm_area, nullptr);
+    });
+}
+
 }  // extern "C"
 namespace {
 // fork, every pass of every group, join -- all relative to `us` (the caller's stream, or the capturing stream)
@@ -1373,16 +1672,8 @@ int fdr_wiener_f32(fdr_plan* p, const float* img_host, int rows, int cols, int s
     // of the drivers calls this three times; the reference's _optimized version hoists its buffers the same way,
     // fft/fft_gpu.cu:304-322)
     const size_t bytes = (size_t)rows * cols * sizeof(float);
-    if (p->stage_cap < bytes) {
-        (void)hipFree(p->stage_in); (void)hipFree(p->stage_out);
-        p->stage_in = p->stage_out = nullptr; p->stage_cap = 0;
-        const size_t cap = (size_t)p->M * p->N * sizeof(float);
-        if (hipMalloc((void**)&p->stage_in, cap) != hipSuccess || hipMalloc((void**)&p->stage_out, cap) != hipSuccess) {
-            (void)hipFree(p->stage_in); p->stage_in = nullptr;
-            return fail(FDR_ERR_ALLOC, "fdr_wiener_f32: hipMalloc of the staging buffers failed");
-        }
-        p->stage_cap = cap;
-    }
+    const int sc = ensure_stage(p, bytes, "fdr_wiener_f32");
+    if (sc != FDR_OK) return sc;
     float *d_in = p->stage_in, *d_out = p->stage_out;
     hipError_t e;
     {

@@ -12,8 +12,15 @@ enum RowOut {
     ROW_OUT_COMPLEX = 0,
     ROW_OUT_REAL_MINMAX = 1,  // pass C': real plane + min/max partials
     ROW_OUT_MINMAX_ONLY = 2,  // pass C1 (two-sweep normalisation): min/max partials, nothing stored
-    ROW_OUT_NORMALIZED = 3    // pass C2: the transform again, normalised with the folded partials and cropped on store
+    ROW_OUT_NORMALIZED = 3,   // pass C2: the transform again, normalised with the folded partials and cropped on store
+    // the blur operator and Richardson-Lucy (fdr_rl.hip; half-spectrum rows of 32 points and more, one image): cropped to the
+    // window out_rows x out_cols on store (row stride out_stride), no min/max
+    ROW_OUT_BLUR = 4,         // the value to `out`
+    ROW_OUT_RL_RATIO = 5,     // r = c > kRlTau ? max(d, 0) / c : 0 to `out`; d read from src_real (row stride src_stride)
+    ROW_OUT_RL_UPDATE = 6     // max(u g, 0) to `out`; u read from src_real (row stride src_stride; may be `out` itself)
 };
+// the guard of the Richardson-Lucy ratio (FDR_RL_TAU of fdr.h): a blurred estimate at or below it gives r = 0
+constexpr float kRlTau = 1e-7f;
 enum ColKind {
     COL_FWD = 0,         // forward column FFT, complex in place (PSF spectrum, fft2d)
     COL_INV = 1,         // inverse column FFT, complex in place (fft2d)
@@ -119,6 +126,12 @@ hipError_t launch_cols_panel(int logm, ColKind kind, const ColArgs& a, const flo
 // (fdr_cls.hip) the COL_FWD_FILTER pass with the constrained least-squares quotient W = conj(H) / (|H|^2 + K + gamma L^2) instead: lap = the
 // Laplacian table of the plan (a_u = 4 sin^2(pi u / M), u < M, then b_v = 4 sin^2(pi v / N), v < N; doubles, device memory)
 hipError_t launch_cols_panel_cls(int logm, const ColArgs& a, const double* lap, double gamma, const float2* tw_fwd, hipStream_t s);
+// (fdr_rl.hip) the operator tables of the blur / Richardson-Lucy calls: the PSF column pass of COL_FWD_FILTER (a.data = the row
+// spectra of the PSF, a.nvalid rows, half spectrum) writing H / (M N) in place and conj(H) / (M N) to `conj_out`, both in the
+// layout pass B' reads W from (packed column 0 of panel 0 included)
+hipError_t launch_cols_panel_operator(int logm, const ColArgs& a, float2* conj_out, const float2* tw_fwd, hipStream_t s);
+// (fdr_rl.hip) u = max(d, 0) on a rows x cols window (row strides `stride` / `ustride`)
+hipError_t launch_rl_init(const float* d, int rows, int cols, int stride, float* u, int ustride, hipStream_t s);
 
 // reference-shaped and auxiliary kernels (fdr_aux.hip)
 hipError_t launch_pad_real_to_complex(const float* src, int rows, int cols, int stride, float2* dst, int M, int N,

@@ -726,6 +726,40 @@ __device__ __forceinline__ void rows4_inv_epilogue(const RowArgs& a, const int r
     }
 }
 
+// The operator kinds of the inverse row passes (the blur / Richardson-Lucy calls of fdr_rl.hip, one image at a time), the
+// value v of the inverse transform at (r, n) of the window out_rows x out_cols, src = src_real + r src_stride + n:
+//   OUT 3 (blur)      : v
+//   OUT 4 (RL ratio)  : v > kRlTau ? max(d, 0) / v : 0, d = *src (the input image)
+//   OUT 5 (RL update) : max(u v, 0), u = *src (the estimate; src may be the output itself: read and written by the same lane)
+template <int OUT>
+__device__ __forceinline__ float rows4_rl_value(const float v, const float* src) {
+    if constexpr (OUT == 3) return v;
+    else if constexpr (OUT == 4) return v > kRlTau ? fmaxf(*src, 0.f) / v : 0.f;
+    else return fmaxf(*src * v, 0.f);
+}
+// rows4_inv_epilogue for those kinds: cropped on store as OUT 2, no min/max
+template <class Core, int OUT, int V>
+__device__ __forceinline__ void rows4_rl_epilogue(const RowArgs& a, const int r0, const int tq, const float2 (&z)[2][V]) {
+    constexpr int T = Core::T;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+        const int r = r0 + b;
+        if (r < a.out_rows) {
+            float* o = a.out + (size_t)r * a.out_stride + tq;
+            const float* in = OUT == 3 ? nullptr : a.src_real + (size_t)r * a.src_stride + tq;
+#pragma unroll
+            for (int u = 0; u < Core::NUL; ++u)
+#pragma unroll
+                for (int q = 0; q < Core::RHOL; ++q) {
+                    const int s = u * Core::RHOL + q;
+                    const int c = u * T + (q << Core::LOGOUT);
+                    const float v = b == 0 ? z[0][s].x : b == 1 ? z[0][s].y : b == 2 ? z[1][s].x : z[1][s].y;
+                    if (tq + c < a.out_cols) o[c] = rows4_rl_value<OUT>(v, in + c);
+                }
+        }
+    }
+}
+
 // HALF: the row spectra hold columns 0 .. N/2-1 only, column 0 packed as Y[m,0] + i Y[m,N/2] (see the forward
 // kernel); the upper half is rebuilt as the conjugate of the mirrored column (rows4_pack_mirror).
 template <int LOGL, bool HALF, int OUT = 0>
@@ -772,8 +806,10 @@ __global__ __launch_bounds__((Rows4PackGeom<LOGL, true>::THREADS), (HALF ? Rows4
     Core::template run<0, true>(z, lds + g * NBUF * St::BUF, tw_fwd, bases, tid);
 
     float mn = __builtin_inff(), mx = -__builtin_inff();
-    if (active) rows4_inv_epilogue<Core, OUT, Core::V>(a, r0, tid, z, fscale, fshift, mn, mx);
-    if constexpr (OUT != 2) block_minmax_store(mn, mx, a.mm_part, (int)blockIdx.x);
+    if constexpr (OUT >= 3) {
+        if (active) rows4_rl_epilogue<Core, OUT, Core::V>(a, r0, tid, z);
+    } else if (active) rows4_inv_epilogue<Core, OUT, Core::V>(a, r0, tid, z, fscale, fshift, mn, mx);
+    if constexpr (OUT < 2) block_minmax_store(mn, mx, a.mm_part, (int)blockIdx.x);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -868,7 +904,8 @@ __global__ __launch_bounds__(RowsSplitGeom<LOGL>::THREADS) void fft_rows4_fwd_sp
     }
 }
 
-// OUT as in rows4_inv_epilogue: 0 raw real plane + min/max, 1 min/max only, 2 normalised and cropped
+// OUT as in rows4_inv_epilogue: 0 raw real plane + min/max, 1 min/max only, 2 normalised and cropped; 3..5 the operator
+// kinds of rows4_rl_value
 template <int LOGL, int OUT>
 __global__ __launch_bounds__((RowsSplitGeom<LOGL, true>::THREADS)) void fft_rows4_inv_split_kernel(const RowArgs a, const float2* __restrict__ tw_fwd) {
     using Geo = RowsSplitGeom<LOGL, true>;
@@ -944,7 +981,16 @@ __global__ __launch_bounds__((RowsSplitGeom<LOGL, true>::THREADS)) void fft_rows
                 a.dst_real[(size_t)ra * L + n] = va;
                 a.dst_real[(size_t)rb * L + n] = vb;
             }
-            if constexpr (OUT == 2) {
+            if constexpr (OUT >= 3) {  // the operator kinds (rows4_rl_value)
+                if (n < a.out_cols) {
+                    if (ra < a.out_rows)
+                        a.out[(size_t)ra * a.out_stride + n] =
+                            rows4_rl_value<OUT>(va, OUT == 3 ? nullptr : a.src_real + (size_t)ra * a.src_stride + n);
+                    if (rb < a.out_rows)
+                        a.out[(size_t)rb * a.out_stride + n] =
+                            rows4_rl_value<OUT>(vb, OUT == 3 ? nullptr : a.src_real + (size_t)rb * a.src_stride + n);
+                }
+            } else if constexpr (OUT == 2) {
                 const float pa = va * fscale, pb = vb * fscale;
                 if (n < a.out_cols) {
                     if (ra < a.out_rows) __builtin_nontemporal_store(pa + fshift, a.out + (size_t)ra * a.out_stride + n);
@@ -957,7 +1003,7 @@ __global__ __launch_bounds__((RowsSplitGeom<LOGL, true>::THREADS)) void fft_rows
                 }
             }
         }
-    if constexpr (OUT != 2) block_minmax_store(mn, mx, a.mm_part, (int)blockIdx.x);
+    if constexpr (OUT < 2) block_minmax_store(mn, mx, a.mm_part, (int)blockIdx.x);
 }
 
 template <int LOGL, int OUT>
@@ -988,6 +1034,12 @@ static hipError_t launch_rows4_t(RowIn in, RowOut out, const RowArgs& a, const f
                 hipLaunchKernelGGL((fft_rows4_inv_split_kernel<LOGL, 1>), sgrid, siblock, 0, s, a, tw);
             } else if (in == ROW_IN_COMPLEX && out == ROW_OUT_NORMALIZED) {
                 hipLaunchKernelGGL((fft_rows4_inv_split_kernel<LOGL, 2>), sgrid, siblock, 0, s, a, tw);
+            } else if (in == ROW_IN_COMPLEX && out == ROW_OUT_BLUR) {
+                hipLaunchKernelGGL((fft_rows4_inv_split_kernel<LOGL, 3>), sgrid, siblock, 0, s, a, tw);
+            } else if (in == ROW_IN_COMPLEX && out == ROW_OUT_RL_RATIO) {
+                hipLaunchKernelGGL((fft_rows4_inv_split_kernel<LOGL, 4>), sgrid, siblock, 0, s, a, tw);
+            } else if (in == ROW_IN_COMPLEX && out == ROW_OUT_RL_UPDATE) {
+                hipLaunchKernelGGL((fft_rows4_inv_split_kernel<LOGL, 5>), sgrid, siblock, 0, s, a, tw);
             } else {
                 return hipErrorInvalidValue;
             }
@@ -1024,6 +1076,15 @@ static hipError_t launch_rows4_t(RowIn in, RowOut out, const RowArgs& a, const f
     } else if (in == ROW_IN_COMPLEX && out == ROW_OUT_NORMALIZED) {
         if (!a.half) return hipErrorInvalidValue;
         return launch_rows4_inv_t<LOGL, 2>(a, tw, s, igrid, iblock);
+    } else if (in == ROW_IN_COMPLEX && (out == ROW_OUT_BLUR || out == ROW_OUT_RL_RATIO || out == ROW_OUT_RL_UPDATE)) {
+        // the operator kinds: half spectrum, rows of 32 points and more, one image per launch
+        if constexpr (LOGL >= 5) {
+            if (!a.half || a.batch.nimg > 1) return hipErrorInvalidValue;
+            if (out == ROW_OUT_BLUR) return launch_rows4_inv_t<LOGL, 3>(a, tw, s, igrid, iblock);
+            if (out == ROW_OUT_RL_RATIO) return launch_rows4_inv_t<LOGL, 4>(a, tw, s, igrid, iblock);
+            return launch_rows4_inv_t<LOGL, 5>(a, tw, s, igrid, iblock);
+        }
+        return hipErrorInvalidValue;
     } else {
         return hipErrorInvalidValue;
     }

@@ -1,5 +1,5 @@
 // gpu.cpp -- ./gpu <img-path> <psf-length> <psf-angle> [--out file] [--mode fast|parity] [--norm padded|cropped] [--host-epilogue]
-//           [--cls gamma]
+//           [--cls gamma] [--rl iterations]
 // Drop-in counterpart of the reference's gpu.cpp (argument meaning, printed lines and exit codes as at
 // gpu.cpp:57-138 of the reference): read image, /255, PSF, K = 0.01, split BGR, warm-up call, timed
 // wienerDeblur_RGB_optimized, timed wienerDeblur_RGB_naive, merge, Lab white balance, 8-bit result.
@@ -62,19 +62,28 @@ int main(int argc, char** argv) {
     string out_path, raw_path;
     bool verify = false;         // --verify: areChannelsEqual(parity-mode result, this run's result)
     bool host_epilogue = false;  // Lab white balance on the host (the A/B reference of the device epilogue)
+    int rl_iterations = -1;      // --rl n: a timed Richardson-Lucy leg after the naive one; its planes are the written result
+    bool cls = false, parity = false;
     for (int i = 4; i < argc; ++i) {
         string a = argv[i];
         if (a == "--out" && i + 1 < argc) out_path = argv[++i];
         else if (a == "--raw-out" && i + 1 < argc) raw_path = argv[++i];  // restored float planes B,G,R before white balance
         else if (a == "--host-epilogue") host_epilogue = true;
         else if (a == "--verify") verify = true;
-        else if (a == "--mode" && i + 1 < argc) fft_gpu::set_mode(string(argv[++i]) == "parity" ? FDR_MODE_PARITY : FDR_MODE_FAST);
+        else if (a == "--mode" && i + 1 < argc) {
+            parity = string(argv[++i]) == "parity";
+            fft_gpu::set_mode(parity ? FDR_MODE_PARITY : FDR_MODE_FAST);
+        }
         else if (a == "--norm" && i + 1 < argc) fft_gpu::set_norm_area(string(argv[++i]) == "cropped" ? FDR_NORM_CROPPED : FDR_NORM_PADDED);
         // constrained least-squares filter (fdr_set_psf_cls) in the fft_gpu:: entry points; the serial leg keeps the Wiener filter.
         // Fast mode only: with --mode parity the library refuses it and the first fft_gpu:: call exits with its message
-        else if (a == "--cls" && i + 1 < argc) fft_gpu::set_cls_gamma(strtof(argv[++i], nullptr));
+        else if (a == "--cls" && i + 1 < argc) { cls = true; fft_gpu::set_cls_gamma(strtof(argv[++i], nullptr)); }
+        // Richardson-Lucy (fft_gpu::richardsonLucy_RGB, fast mode): n >= 0 iterations
+        else if (a == "--rl" && i + 1 < argc) rl_iterations = atoi(argv[++i]);
         else { cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle>\n"; return -1; }
     }
+    // the RL leg replaces the result the other options shape (CLS filter, parity check, parity-mode restoration)
+    if (rl_iterations >= 0 && (cls || verify || parity)) { cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle>\n"; return -1; }
 
     Mat img = fdr_io::imread(img_path);
     if (img.empty()) { cout << "Cannot read image\n"; return -1; }
@@ -122,6 +131,15 @@ int main(int argc, char** argv) {
     const double naive_time = getElapsedMs(t_start, t_end);
     cout << "Deblurring 3 channels took(gpu): " << naive_time << " ms\n";
     printf("[Speedup] %.2fx ms\n", serial_time / naive_time);
+
+    if (rl_iterations >= 0) {  // Richardson-Lucy on the same channels: its planes become the written result
+        vector<Mat> rl = input;
+        t_start = high_resolution_clock::now();
+        fft_gpu::richardsonLucy_RGB(rl, psf, rl_iterations);
+        t_end = high_resolution_clock::now();
+        cout << "Deblurring 3 channels took(gpu[richardson-lucy " << rl_iterations << "]): " << getElapsedMs(t_start, t_end) << " ms\n";
+        channels = rl;
+    }
 
     if (verify) {  // the check of gpu.cpp:116-121 between the serial leg's planes and this run's planes
         if (areChannelsEqual(serial_channels, channels))
