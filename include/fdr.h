@@ -229,6 +229,49 @@ int fdr_richardson_lucy_f32(fdr_plan* plan, const float* img_host, int rows, int
 int fdr_richardson_lucy_f32_dev(fdr_plan* plan, const float* d_img, int rows, int cols, int stride, float* d_out, int out_stride,
                                 int iterations, int norm_area, void* stream);
 
+/* -- the motion-blur estimate: the length and angle of a uniform linear motion blur, from the blurred
+ *    picture alone, by the power cepstrum.  The blur puts sinc zeros into |G| in stripes across the motion direction; in the
+ *    cepstrum they show as a negative peak at distance L along it.  The plan is M x N, the image window rows x cols (row stride
+ *    `stride`) at its top-left corner:
+ *        x = w . img on the window, 0 elsewhere;  w[i, j] = h_rows[i] h_cols[j],  h_n[k] = 0.5 - 0.5 cos(2 pi k / (n - 1))
+ *        G = DFT2(x) on M x N;  eps = 1e-6 sum |x|
+ *        c = Re IDFT2(log(|G| + eps))                                    (IDFT2 includes 1/(M N); c is real and even)
+ *        S[a, l] = c bilinearly, periodic, at row -l sin(theta_a), column +l cos(theta_a);  theta_a = a step,
+ *                  a = 0 .. ceil(180 / step) - 1, l = min_length .. max_length
+ *    The row axis points down: theta is the angle of motionBlurKernel / fdr_psf_motion, and the result goes straight into
+ *    fdr_set_psf_motion(plan, length, angle_deg, ...).  (a*, l*) = argmin S (exact ties: the lowest flat index, angle-major);
+ *    length = l*, angle_deg = theta_a*, score = S[a*, l*], confidence = (median S - min S) / (1.4826 MAD S) (0 when MAD is 0),
+ *    computed in double from the float table.  A confidence below about 10 means no clear blur was found.  An all-zero window
+ *    gives length 0, angle 0, score 0, confidence 0 and an all-zero table (and cepstrum).
+ *    Arguments: 0 selects the default -- step 0.5 deg, min_length 3, max_length min(100, min(rows, cols) / 4).
+ *    Plans: FDR_MODE_FAST with M and N powers of two, or 2^a 3^b 5^c with FDR_FLAG_MIXED_RADIX; 32 <= M, N <= 8192.  FDR_ERR_ARG,
+ *    before any device work and with the plan usable afterwards, for any other plan (parity mode, FDR_FLAG_ANY_SIZE sizes),
+ *    rows or cols < 16 or larger than the plan, stride < cols, negative arguments, min_length < 2, min_length > max_length,
+ *    max_length > min(M, N) / 2 - 2, a step that is not finite or not in (0, 90], a table of more than 2^26 entries, or a null
+ *    `est`; FDR_ERR_STATE on a tables-only plan.
+ *    The first call on a plan allocates the workspace (one M x N complex plane, the Hann tables, the partials and the table),
+ *    kept until fdr_plan_destroy; later calls allocate nothing unless a larger table is asked for.  The calls leave the Wiener /
+ *    CLS filter, the operator tables and every result of the other calls as they were.  No float atomics: results are
+ *    bit-identical from call to call.
+ *      fdr_cepstrum_f32*         c into out (M x N floats, row stride N).  The _dev form is asynchronous on `stream`.
+ *      fdr_estimate_motion_f32*  *est; the table S (n_angles x n_lengths floats, angle-major) into scores when it is not NULL.
+ *                                The _dev form is SYNCHRONOUS: it reads the table back, so it returns after its work on
+ *                                `stream` is done.                                                                      */
+typedef struct fdr_motion_estimate {
+    int length;        /* l*, 0 for an all-zero window */
+    double angle_deg;  /* theta_a* in [0, 180) */
+    float score;       /* S[a*, l*] */
+    float confidence;  /* (median S - min S) / (1.4826 MAD S) */
+    int n_angles;      /* table rows: ceil(180 / step) */
+    int n_lengths;     /* table columns: max_length - min_length + 1 */
+} fdr_motion_estimate;
+int fdr_cepstrum_f32(fdr_plan* plan, const float* img_host, int rows, int cols, int stride, float* out_host);
+int fdr_cepstrum_f32_dev(fdr_plan* plan, const float* d_img, int rows, int cols, int stride, float* d_out, void* stream);
+int fdr_estimate_motion_f32(fdr_plan* plan, const float* img_host, int rows, int cols, int stride, int min_length, int max_length,
+                            double angle_step_deg, fdr_motion_estimate* est, float* scores_host);
+int fdr_estimate_motion_f32_dev(fdr_plan* plan, const float* d_img, int rows, int cols, int stride, int min_length, int max_length,
+                                double angle_step_deg, fdr_motion_estimate* est, float* d_scores, void* stream);
+
 /* Host-pointer batch: `count` images at imgs_host + i*img_pitch, results to out_host + i*out_pitch (elements).
  * H2D copy, restoration and D2H copy of consecutive images overlap on three internal streams with three images in
  * flight -- the pinned-buffer / cudaMemcpyAsync pipeline fft/fft_gpu.cu:306-350,372-385 sets out to build.  Buffers

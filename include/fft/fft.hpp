@@ -212,6 +212,26 @@ inline void richardsonLucy_RGB(std::vector<Mat>& channels, const Mat& psf, int i
 inline void richardsonLucy_RGB(std::vector<Mat>& channels, const Mat& psf, int iterations) {
     richardsonLucy_RGB(channels, psf, iterations, defaults());
 }
+// The motion blur of a one-channel picture of unknown blur (fdr_estimate_motion_f32, include/fdr.h): length and angle in the
+// convention of motionBlurKernel, the table minimum and the confidence (below about 10: no clear blur).  Its own FDR_MODE_FAST plan
+// (each dimension padded to fdr_optimal_dft_size, at least 32; FDR_FLAG_MIXED_RADIX), made and freed inside the call.  0 selects an
+// argument's default (min_length 3, max_length min(100, min(rows, cols) / 4), angle_step 0.5 deg).
+inline fdr_motion_estimate estimateMotionBlur(const Mat& gray, int min_length = 0, int max_length = 0, double angle_step = 0) {
+    Mat src = gray.isContinuous() ? gray : gray.clone();
+    fdr_plan* plan = nullptr;
+    FDR_CHECK(fdr_plan_create(defaults().device, std::max(32, fdr_optimal_dft_size(src.rows)), std::max(32, fdr_optimal_dft_size(src.cols)),
+                              FDR_MODE_FAST, FDR_FLAG_MIXED_RADIX, &plan));
+    fdr_motion_estimate est{};
+    const int rc = fdr_estimate_motion_f32(plan, src.ptr<float>(0), src.rows, src.cols, src.cols, min_length, max_length, angle_step, &est,
+                                           nullptr);
+    const std::string err = rc == FDR_OK ? std::string() : std::string(fdr_last_error());
+    fdr_plan_destroy(plan);
+    if (rc != FDR_OK) {
+        std::cerr << "Error: " << __FILE__ << ":" << __LINE__ << ", " << err << "\n";
+        exit(1);
+    }
+    return est;
+}
 // The operator exactly as fft_serial::wienerDeblur_myfft defines it (fft/fft_serial.cpp:141-261; the fft_gpu
 // declaration at fft/fft.hpp:44 has no body in the reference): pad to getOptimalDFTSize (2^a 3^b 5^c, :153-154 -- a
 // non-power-of-two dimension is transformed by the naive DFT, :100-101), restore, crop to img's size, normalise over

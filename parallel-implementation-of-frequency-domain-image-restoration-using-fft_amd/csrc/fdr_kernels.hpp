@@ -133,6 +133,17 @@ hipError_t launch_cols_panel_operator(int logm, const ColArgs& a, float2* conj_o
 // (fdr_rl.hip) u = max(d, 0) on a rows x cols window (row strides `stride` / `ustride`)
 hipError_t launch_rl_init(const float* d, int rows, int cols, int stride, float* u, int ustride, hipStream_t s);
 
+// (fdr_motion.hip) the motion-blur estimate.  window: the Hann tables into hann[rows + cols], w . img on the window and 0 elsewhere
+// into the row-major M x N complex plane, sum |x| partials (motion_pad_partials of them) folded in a fixed order into
+// part[motion_pad_partials(M, N)] (part holds one more double).  log: G -> (log(|G| + 1e-6 sum) / (M N), 0) in place (0 for sum 0).
+// score: table[a * n_lengths + l - min_length] = the real parts bilinearly at (-l sin, l cos), periodic; trig = cos[n_angles], sin[n_angles]
+int motion_pad_partials(int M, int N);
+hipError_t launch_motion_window(const float* img, int rows, int cols, int stride, float* hann, float2* plane, int M, int N, double* part,
+                                hipStream_t s);
+hipError_t launch_motion_log(float2* plane, int M, int N, const double* sum, hipStream_t s);
+hipError_t launch_motion_score(const float2* plane, int M, int N, const double* trig, int n_angles, int min_length, int n_lengths, float* table,
+                               hipStream_t s);
+
 // reference-shaped and auxiliary kernels (fdr_aux.hip)
 hipError_t launch_pad_real_to_complex(const float* src, int rows, int cols, int stride, float2* dst, int M, int N,
                                       hipStream_t s);

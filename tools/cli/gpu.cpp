@@ -1,5 +1,7 @@
 // gpu.cpp -- ./gpu <img-path> <psf-length> <psf-angle> [--out file] [--mode fast|parity] [--norm padded|cropped] [--host-epilogue]
 //           [--cls gamma] [--rl iterations]
+// `auto auto` for length and angle: the blur is estimated first (fft_gpu::estimateMotionBlur on the per-pixel mean of B, G and R),
+// printed as `estimate: length L angle A confidence C`, and the run then goes on exactly as `./gpu <img-path> L A` would.
 // Drop-in counterpart of the reference's gpu.cpp (argument meaning, printed lines and exit codes as at
 // gpu.cpp:57-138 of the reference): read image, /255, PSF, K = 0.01, split BGR, warm-up call, timed
 // wienerDeblur_RGB_optimized, timed wienerDeblur_RGB_naive, merge, Lab white balance, 8-bit result.
@@ -57,8 +59,10 @@ int main(int argc, char** argv) {
         return -1;
     }
     string img_path = argv[1];
-    int psf_length = atoi(argv[2]);
-    double psf_angle = atof(argv[3]);
+    const bool estimate = string(argv[2]) == "auto" && string(argv[3]) == "auto";
+    if (!estimate && (string(argv[2]) == "auto" || string(argv[3]) == "auto")) { cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle>\n"; return -1; }
+    int psf_length = estimate ? 0 : atoi(argv[2]);
+    double psf_angle = estimate ? 0.0 : atof(argv[3]);
     string out_path, raw_path;
     bool verify = false;         // --verify: areChannelsEqual(parity-mode result, this run's result)
     bool host_epilogue = false;  // Lab white balance on the host (the A/B reference of the device epilogue)
@@ -89,6 +93,23 @@ int main(int argc, char** argv) {
     if (img.empty()) { cout << "Cannot read image\n"; return -1; }
     img.convertTo(img, CV_32F);
     img /= 255.0;
+
+    if (estimate) {  // the blur from the picture itself: the per-pixel mean of B, G and R
+        vector<Mat> bgr;
+        split(img, bgr);
+        Mat gray(img.rows, img.cols, CV_32F);
+        for (int r = 0; r < img.rows; ++r)
+            for (int c = 0; c < img.cols; ++c)
+                gray.ptr<float>(r)[c] = (bgr[0].ptr<float>(r)[c] + bgr[1].ptr<float>(r)[c] + bgr[2].ptr<float>(r)[c]) / 3.0f;
+        const fdr_motion_estimate est = fft_gpu::estimateMotionBlur(gray);
+        if (est.length < 1) { cout << "Cannot estimate the blur of an all-zero picture\n"; return -1; }
+        printf("estimate: length %d angle %.17g confidence %.3f\n", est.length, est.angle_deg, (double)est.confidence);
+        fflush(stdout);
+        if (est.confidence < 10.f)
+            cerr << "[Warning] low confidence (" << est.confidence << " < 10): the picture shows no clear motion blur; the estimate may be wrong\n";
+        psf_length = est.length;
+        psf_angle = est.angle_deg;
+    }
 
     Mat psf = motionBlurKernel(psf_length, psf_angle);
     float K = 0.01f;
