@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- Mpixels/s restored (FFT + Wiener + IFFT) on synthetic N x N fp32 images, MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--size 4096] [--batch 4] [--mode fast|parity] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--size 4096] [--batch 4] [--mode fast|parity] [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path (pad -> FFT2 -> Wiener -> IFFT2 -> real -> normalise -> crop)
 over one batch of `--batch` device-resident synthetic images per GPU.  Inputs and outputs stay in
@@ -9,7 +9,14 @@ HBM; the PSF spectrum is prepared once per plan, outside the timed region.  N > 
 GPU (torch.distributed / RCCL), independent images sharded by rank, no data-path collective, weak
 scaling (per-GPU batch fixed).  Rank 0 prints ONE JSON line.
 
-The JSON line also carries
+A plain run does only what the headline `value` needs: set-up, the W warm-up steps, the K timed steps
+(`--repeats` times, median), the `--dump-outputs` files and the line.  Everything else is measured or
+checked only under `--full`: the output checks (`check`), the PSF-recompute and bit-identical-mode legs
+(`config.value_with_psf_recompute`, `config.value_parity_mode`), the per-kernel `roofline` and the
+`cpu_baseline` / `parity` against the CPU oracle; a plain line reports them as null (`parity`: absent).  The `--no-*`
+options below trim a `--full` run.
+
+Under --full the JSON line also carries
   roofline     : algorithmic bytes of the dominant kernel / its mean duration, measured with hipEvent
                  pairs on the launch stream over a repetition of the same K steps (the timed region
                  itself is left un-instrumented), against the 8 TB/s HBM peak.  The formulation is the
@@ -85,6 +92,9 @@ def parse():
     ap.add_argument("--mode", choices=["fast", "parity"], default="fast")
     ap.add_argument("--streams", type=int, default=0, help="internal streams / workspaces the batch alternates over (0 = 2 in fast mode, 3 in parity mode)")
     ap.add_argument("--group", type=int, default=0, help="images per launch of every pass (fast mode; 1..8, streams*group <= 16; 0 = 8 up to 1024^2, 4 up to 4096^2, else 2)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure, run the output and one-by-one checks, the PSF-recompute and parity-mode "
+                         "legs, the per-kernel roofline and (N = 1) the CPU baseline and the parity against the CPU oracle")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo for rehearsals on a one-GPU box)")
     ap.add_argument("--one-device", action="store_true", help="rehearsal: every rank uses cuda:0 (needs --backend gloo)")
@@ -271,9 +281,9 @@ def main():
         dumped = dump_outputs(outs, B, S, args.dump_outputs, "restored" if world == 1 else "restored_rank%d" % rank,
                               DUMP_MAX_BYTES // world)
 
-    # ---- consistency check over RCCL (outside the timed region) ----
+    # ---- consistency check over RCCL (outside the timed region; --full) ----
     images_mine = B * args.steps  # images this rank restored in one repetition of the timed region
-    if B > 0:
+    if B > 0 and args.full:
         chk = float(outs[:B].double().sum().item())
         finite = bool(torch.isfinite(outs[:B]).all().item())
         omin, omax = float(outs[:B].min().item()), float(outs[:B].max().item())
@@ -300,12 +310,12 @@ def main():
     if bcast is not None:  # every rank's filter hash must be rank 0's
         bcast["hash_min"], bcast["hash_max"] = int(comm.allreduce_min(bcast["hash"])), int(comm.allreduce_max(bcast["hash"]))
         bcast["seconds_max"] = comm.allreduce_max(bcast["seconds"])
-    out0 = outs[0].cpu().numpy() if (rank == 0 and B > 0) else None
+    out0 = outs[0].cpu().numpy() if (rank == 0 and B > 0 and args.full) else None
 
     # ---- second figure: the PSF spectrum rebuilt for every image, as the reference's loop does per channel
     #      (fft/fft_gpu.cu:329-343,356): PSF generation + pad + 2-D FFT + filter inside the step, one stream ----
     psf_elapsed = None
-    if not args.no_psf_recompute:  # (every rank takes part in the barriers, also one whose shard is empty)
+    if args.full and not args.no_psf_recompute:  # (every rank takes part in the barriers, also one whose shard is empty)
         nb = min(B, 16)
 
         def step_psf():
@@ -318,7 +328,7 @@ def main():
 
     # ---- third figure: the bit-identical mode (FDR_MODE_PARITY: reference pass order, 72 B/pixel, 5 launches) on a bounded leg ----
     parity_elapsed, parity_images = None, 0
-    if not args.no_parity_leg and args.mode == "fast":
+    if args.full and not args.no_parity_leg and args.mode == "fast":
         nbp = min(B, 12 if S <= 4096 else 4)
         psteps = max(1, min(args.steps, 4))
         pplan = fdr.Plan(S, S, fdr.MODE_PARITY, device=local_rank)
@@ -336,17 +346,19 @@ def main():
         del pouts
 
     # ---- per-kernel durations: hipEvent pairs on the launch stream, same K steps again (one stream: un-overlapped) ----
-    plan.profile(True)
-    for _ in range(args.steps):
-        step()
-    torch.cuda.synchronize()
-    passes = plan.pass_times()
-    plan.profile(False)
+    passes = []
+    if args.full:
+        plan.profile(True)
+        for _ in range(args.steps):
+            step()
+        torch.cuda.synchronize()
+        passes = plan.pass_times()
+        plan.profile(False)
 
     # ---- what a plain streaming kernel reaches on THIS device, for context next to the nominal peak: an out-of-place
     # elementwise pass (read 4 B + write 4 B per element) over the floats of one launch group, torch's own kernel ----
     stream_ref = None
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             n_el = P * max(1, min(args.group, 8))
             src = torch.empty(n_el, dtype=torch.float32, device=dev).fill_(1.0)
@@ -435,7 +447,7 @@ def main():
                   "mode": args.mode, "spectrum": spectrum, "streams": args.streams, "images_per_launch": args.group,
                   "parallelism": "images sharded over %d rank(s), no data-path collective" % world,
                   "collectives": comm.collectives(),  # "rccl", or "gloo (...)" when asked for or when the RCCL group could not be built
-                  "normalize_area": "padded (serial semantics)",
+                  "normalize_area": "padded (serial semantics)", "full": args.full,
                   "repeats": len(reps), "value_min": round(vals[0], 1), "value_max": round(vals[-1], 1),
                   "value_with_psf_recompute": round(psf_images * P / 1e6 / psf_elapsed, 1) if (psf_elapsed and psf_images) else None,
                   "value_parity_mode": round(parity_images * P / 1e6 / parity_elapsed, 1) if (parity_elapsed and parity_images) else None,
@@ -454,7 +466,8 @@ def main():
                       "rank0": {"finite": finite, "out_min": omin, "out_max": omax, "every_image_spans_0_1": spans},
                       "batch_vs_one_by_one": ("skipped (--no-batch-check)" if args.no_batch_check else
                                               "all %d images of a step recomputed one at a time on one stream on every rank: bit-identical required%s"
-                                              % (B, "" if not differing else "; rank 0 DIFFERS at images %s" % differing[:16]))},
+                                              % (B, "" if not differing else "; rank 0 DIFFERS at images %s" % differing[:16]))}
+                     if args.full else None,
         }
         if args.dump_outputs:
             line["dump_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "rank0_files": dumped}
@@ -462,7 +475,7 @@ def main():
             rc = 3
         if bcast is not None and not (bcast["hash_min"] == bcast["hash_max"] == bcast["hash"]):
             rc = 5  # some rank holds a filter that is not rank 0's
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             cs = args.cpu_size or min(S, 4096)
             line["cpu_baseline"], ref0 = cpu_baseline(cs)
             if cs == S and out0 is not None:

@@ -821,14 +821,45 @@ def test_rccl_refusal_falls_back_to_gloo_by_consensus():
     root = _os.path.dirname(_os.path.dirname(_os.path.abspath(__file__)))
     env = dict(_os.environ, MASTER_PORT="29577", FDR_RCCL_PROBE_TIMEOUT_S="60")
     r = subprocess.run([sys.executable, _os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "nccl", "--one-device", "--size", "512",
-                        "--batch", "4", "--steps", "2", "--warmup", "1", "--repeats", "1", "--no-psf-recompute", "--no-parity-leg",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, env=env, cwd=root)
+                        "--batch", "4", "--steps", "2", "--warmup", "1", "--repeats", "1", "--full", "--no-psf-recompute",
+                        "--no-parity-leg", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
     d = json.loads(line)
     assert d["n_gpus"] == 2 and d["check"]["ranks_ok"] == 2 and d["check"]["images_done"] == d["check"]["images_expected"]
     assert d["config"]["collectives"].startswith("gloo (rccl unavailable"), d["config"]["collectives"]
     assert "RCCL group unavailable" in r.stderr
+
+
+def test_plain_bench_run_gives_the_headline_and_the_full_run_the_rest(tmp_path):
+    """bench.py without --full measures only the headline figure: the line carries it, every figure of --full is null,
+    and --dump-outputs writes the last timed step.  A --full run of the same arguments restores the same bits and adds
+    the checks, the two extra legs, the roofline and the CPU baseline with its parity against the oracle."""
+    import json
+    import subprocess
+    import sys
+    root = _os.path.dirname(_os.path.dirname(_os.path.abspath(__file__)))
+    runs = {}
+    for name, extra in (("plain", []), ("full", ["--full"])):
+        out = tmp_path / name
+        r = subprocess.run([sys.executable, _os.path.join(root, "bench.py"), "--gpus", "1", "--size", "512", "--batch", "4",
+                            "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)] + extra,
+                           capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert d["unit"] == "Mpixels/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert d["value"] > 0 and d["ms_per_step"] > 0 and (d["steps"], d["warmup"]) == (3, 1)
+        assert d["config"]["full"] is (name == "full") and d["config"]["repeats"] == 5
+        runs[name] = (d, np.load(str(out / "restored.npy")))
+    plain, full = runs["plain"][0], runs["full"][0]
+    assert plain["check"] is None and plain["roofline"] is None and plain["cpu_baseline"] is None and "parity" not in plain
+    assert plain["config"]["value_with_psf_recompute"] is None and plain["config"]["value_parity_mode"] is None
+    assert full["check"]["images_done"] == full["check"]["images_expected"] == 12 and full["check"]["ranks_ok"] == 1
+    assert "DIFFERS" not in full["check"]["batch_vs_one_by_one"]
+    assert full["roofline"] is not None and full["cpu_baseline"]["value"] > 0 and full["parity"]["max_abs"] <= 1e-4
+    assert full["config"]["value_with_psf_recompute"] > 0 and full["config"]["value_parity_mode"] > 0
+    assert runs["plain"][1].shape == (4, 512, 512)
+    assert np.array_equal(runs["plain"][1], runs["full"][1])
 
 
 def test_cat_picture_through_both_clis(fdr, oracle, tmp_path):
