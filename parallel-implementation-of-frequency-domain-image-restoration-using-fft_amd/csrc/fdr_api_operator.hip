@@ -1,0 +1,221 @@
+// fdr_api_operator.hip -- the blur operator and Richardson-Lucy (fdr_rl.hip): passes A, B' and C of the fast half-spectrum path
+// with the operator tables in place of W and the operator kinds of the inverse row pass; their PSF setters and entry points.
+#include "fdr_host.hpp"
+
+#include <cstdint>
+
+using namespace fdr;
+
+static_assert(kRlTau == FDR_RL_TAU, "the ratio guard of the kernels is FDR_RL_TAU");
+
+namespace {
+
+// names are static strings compared by pointer in PassTimer::pass_id
+const char* const kPassOpRowsPsf = "O rows: PSF pad+FFT (operator)";
+const char* const kPassOpCols = "O cols: FFT -> H/MN, conj(H)/MN";
+const char* const kPassOpRowsFwd = "A op rows: pad+FFT (blur / RL)";
+const char* const kPassOpColsH = "B' op cols: FFT*H*IFFT";
+const char* const kPassOpColsConj = "B' op cols: FFT*conj(H)*IFFT";
+const char* const kPassOpRowsBlur = "C op rows: IFFT+crop (blur)";
+const char* const kPassRlInit = "RL init: u = max(d, 0)";
+const char* const kPassRlRatio = "C op rows: IFFT+RL ratio";
+const char* const kPassRlUpdate = "C op rows: IFFT+RL update";
+const char* const kPassRlNorm = "E RL minmax+normalize";
+
+}  // namespace
+
+namespace fdr {
+
+// the PSF top-left in the M x N plane -> its row spectra (the rows it reaches) -> H / (M N) into op_h, conj(H) / (M N) into op_c
+int set_operator_psf_impl(fdr_plan* p, const float* d_psf, int prows, int pcols, int pstride, hipStream_t s) {
+    if (!p->op_h) {
+        float2* t = nullptr;
+        if (hipMalloc((void**)&t, 2 * p->ws_elems * sizeof(float2)) != hipSuccess)
+            return fail(FDR_ERR_ALLOC, "fdr_set_operator_psf: hipMalloc of the operator tables failed");
+        p->op_h = t;
+        p->op_c = t + p->ws_elems;
+    }
+    ScopedPhase phase(p, FDR_PHASE_PRE, s);
+    const int nvalid = (prows + 3) & ~3;  // <= M (M is a multiple of 8 on this path)
+    {
+        ScopedPass t(p, s, kPassOpRowsPsf);
+        RowArgs ra{};
+        ra.src_real = d_psf; ra.src_rows = prows; ra.src_cols = pcols; ra.src_stride = pstride;
+        ra.dst_c = p->op_h; ra.M = nvalid; ra.pstride = p->pstride; ra.half = 1; ra.num_cu = p->num_cu;
+        FDR_HIP(launch_rows4(p->logN, ROW_IN_REAL, ROW_OUT_COMPLEX, ra, p->tw_row_f, s));
+    }
+    {
+        ScopedPass t(p, s, kPassOpCols);
+        ColArgs ca{};
+        ca.data = p->op_h; ca.N = p->N; ca.num_cu = p->num_cu; ca.pstride = p->pstride; ca.npanels = p->npanels;
+        ca.nvalid = nvalid; ca.packed0 = 1;
+        FDR_HIP(launch_cols_panel_operator(p->logM, ca, p->op_c, p->tw_col_f, s));
+    }
+    p->have_op = true;
+    return FDR_OK;
+}
+
+}  // namespace fdr
+
+namespace {
+
+// pass A: the window of x (zero elsewhere) -> the half spectrum of slot 0
+int op_rows_fwd(fdr_plan* p, const float* x, int rows, int cols, int stride, hipStream_t s) {
+    ScopedPass t(p, s, kPassOpRowsFwd);
+    RowArgs a{};
+    a.src_real = x; a.src_rows = rows; a.src_cols = cols; a.src_stride = stride;
+    a.dst_c = p->work; a.M = p->M; a.pstride = p->pstride; a.half = 1; a.num_cu = p->num_cu;
+    FDR_HIP(launch_rows4(p->logN, ROW_IN_REAL, ROW_OUT_COMPLEX, a, p->tw_row_f, s));
+    return FDR_OK;
+}
+// pass B', unchanged, on one of the operator tables
+int op_cols(fdr_plan* p, bool adjoint, hipStream_t s) {
+    ScopedPass t(p, s, adjoint ? kPassOpColsConj : kPassOpColsH);
+    ColArgs c{};
+    c.data = p->work; c.filt = adjoint ? p->op_c : p->op_h; c.N = p->N; c.num_cu = p->num_cu;
+    c.pstride = p->pstride; c.npanels = p->npanels; c.packed0 = 1;
+    c.batch.nimg = 1; c.batch.data[0] = p->work;
+    FDR_HIP(launch_cols_panel(p->logM, COL_FUSED, c, p->tw_col_f, s));
+    return FDR_OK;
+}
+// pass C with an operator kind: the window rows x cols of the inverse transform through the kind's epilogue into `out`
+int op_rows_inv(fdr_plan* p, RowOut kind, const char* name, const float* src, int src_stride, float* out, int out_stride, int rows,
+                int cols, hipStream_t s) {
+    ScopedPass t(p, s, name);
+    RowArgs a{};
+    a.src_c = p->work; a.M = p->M; a.pstride = p->pstride; a.half = 1; a.num_cu = p->num_cu;
+    a.src_real = src; a.src_stride = src_stride;
+    a.out = out; a.out_rows = rows; a.out_cols = cols; a.out_stride = out_stride;
+    FDR_HIP(launch_rows4(p->logN, ROW_IN_COMPLEX, kind, a, p->tw_row_f, s));
+    return FDR_OK;
+}
+
+int blur_dev_impl(fdr_plan* p, const float* d_img, int rows, int cols, int stride, float* d_out, int out_stride, int adjoint, hipStream_t s) {
+    int rc = op_rows_fwd(p, d_img, rows, cols, stride, s);
+    if (rc == FDR_OK) rc = op_cols(p, adjoint != 0, s);
+    if (rc == FDR_OK) rc = op_rows_inv(p, ROW_OUT_BLUR, kPassOpRowsBlur, nullptr, 0, d_out, out_stride, rows, cols, s);
+    return rc;
+}
+
+// [lo, hi) of the elements a rows x cols window with row stride `stride` spans
+bool windows_overlap(const float* a, int a_stride, const float* b, int b_stride, int rows, int cols) {
+    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + ((size_t)(rows - 1) * a_stride + cols) * sizeof(float);
+    const uintptr_t b0 = (uintptr_t)b, b1 = b0 + ((size_t)(rows - 1) * b_stride + cols) * sizeof(float);
+    return a0 < b1 && b0 < a1;
+}
+
+// everything a Richardson-Lucy call refuses: plan, operator PSF and window, the iteration count, the normalisation, an output
+// that overlaps the input (the input is read on every iteration)
+int rl_check(const fdr_plan* p, const char* fn, const float* img, int rows, int cols, int stride, const float* out, int out_stride,
+             int iterations, int norm_area) {
+    const int rc = check_window(p, fn, NEED_OPERATOR_PSF, rows, cols, stride, out_stride);
+    if (rc != FDR_OK) return rc;
+    if (iterations < 0) return fail(FDR_ERR_ARG, std::string(fn) + ": iterations < 0");
+    if (norm_area != FDR_NORM_NONE && norm_area != FDR_NORM_CROPPED && norm_area != FDR_NORM_PADDED)
+        return fail(FDR_ERR_ARG, std::string(fn) + ": unknown norm_area");
+    if (windows_overlap(img, stride, out, out_stride, rows, cols))
+        return fail(FDR_ERR_ARG, std::string(fn) + ": the output overlaps the input (the input is read on every iteration)");
+    return FDR_OK;
+}
+
+// u (the estimate) lives in d_out; r in the window of the raw plane (row stride cols), the spectrum in slot 0's work.  With a
+// normalisation the last update (or, for no iterations, the initial estimate) goes to the raw plane instead, and the normalise
+// pass writes d_out from there.
+int rl_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, int cols, int stride, float* d_out, int out_stride, int iterations,
+                int norm_area, hipStream_t s) {
+    int rc = FDR_OK;
+    const bool norm = norm_area != FDR_NORM_NONE;
+    float* r = p->raw;
+    const int rs = cols;
+    float* fin = norm ? p->raw : d_out;  // where the final estimate is written
+    const int fs = norm ? rs : out_stride;
+    {
+        ScopedPass t(p, s, kPassRlInit);
+        FDR_HIP(launch_rl_init(d_img, rows, cols, stride, iterations == 0 ? fin : d_out, iterations == 0 ? fs : out_stride, s));
+    }
+    for (int it = 0; it < iterations && rc == FDR_OK; ++it) {
+        const bool last = it == iterations - 1;
+        rc = op_rows_fwd(p, d_out, rows, cols, out_stride, s);                                            // c = blur(u) ...
+        if (rc == FDR_OK) rc = op_cols(p, false, s);
+        if (rc == FDR_OK) rc = op_rows_inv(p, ROW_OUT_RL_RATIO, kPassRlRatio, d_img, stride, r, rs, rows, cols, s);  // ... r = d+ / c
+        if (rc == FDR_OK) rc = op_rows_fwd(p, r, rows, cols, rs, s);                                      // g = blur^T(r) ...
+        if (rc == FDR_OK) rc = op_cols(p, true, s);
+        if (rc == FDR_OK)
+            rc = op_rows_inv(p, ROW_OUT_RL_UPDATE, kPassRlUpdate, d_out, out_stride, last ? fin : d_out, last ? fs : out_stride, rows,
+                             cols, s);                                                                    // ... u = max(u g, 0)
+    }
+    if (rc != FDR_OK || !norm) return rc;
+    // min-max to [0, 1] over the window; FDR_NORM_PADDED also counts the zeros of u outside it (one extra (0, 0) partial)
+    ScopedPass t(p, s, kPassRlNorm);
+    int n_part = 0;
+    FDR_HIP(launch_minmax_real(fin, rows, fs, rows, cols, p->mm_part, &n_part, s));
+    if (norm_area == FDR_NORM_PADDED && (rows < p->M || cols < p->N)) {
+        if (n_part + 1 > p->mm_part_cap) return fail(FDR_ERR_STATE, std::string(fn) + ": min/max partial count out of range");
+        FDR_HIP(hipMemsetAsync(p->mm_part + n_part, 0, sizeof(float2), s));  // (0.f, 0.f)
+        ++n_part;
+    }
+    if (n_part <= 0 || n_part > p->mm_part_cap) return fail(FDR_ERR_STATE, std::string(fn) + ": min/max partial count out of range");
+    FDR_HIP(launch_reduce_minmax(p->mm_part, n_part, p->mm, s));
+    FDR_HIP(launch_normalize(fin, fs, nullptr, 0, p->mm, d_out, rows, cols, out_stride, s));
+    return FDR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fdr_set_operator_psf_dev(fdr_plan* p, const float* d_psf, int prows, int pcols, int pstride, void* stream) {
+    return set_psf(p, "fdr_set_operator_psf_dev", {PSF_DEV, d_psf, prows, pcols, pstride, 0.0}, true, 0.f, 0.f, (hipStream_t)stream);
+}
+
+int fdr_set_operator_psf(fdr_plan* p, const float* psf_host, int prows, int pcols, int pstride) {
+    return set_psf(p, "fdr_set_operator_psf", {PSF_HOST, psf_host, prows, pcols, pstride, 0.0}, true, 0.f, 0.f, nullptr);
+}
+
+int fdr_set_operator_psf_motion(fdr_plan* p, int size, double angle_deg, void* stream) {
+    return set_psf(p, "fdr_set_operator_psf_motion", {PSF_MOTION, nullptr, size, size, size, angle_deg}, true, 0.f, 0.f, (hipStream_t)stream);
+}
+
+int fdr_blur_f32_dev(fdr_plan* p, const float* d_img, int rows, int cols, int stride, float* d_out, int out_stride, int adjoint, void* stream) {
+    const char* fn = "fdr_blur_f32_dev";
+    if (!p || !d_img || !d_out) return null_arg(fn);
+    const int rc = check_window(p, fn, NEED_OPERATOR_PSF, rows, cols, stride, out_stride);
+    if (rc != FDR_OK) return rc;
+    FDR_HIP(hipSetDevice(p->device));
+    return blur_dev_impl(p, d_img, rows, cols, stride, d_out, out_stride, adjoint, (hipStream_t)stream);
+}
+
+int fdr_blur_f32(fdr_plan* p, const float* img_host, int rows, int cols, int stride, float* out_host, int out_stride, int adjoint) {
+    const char* fn = "fdr_blur_f32";
+    if (!p || !img_host || !out_host) return null_arg(fn);
+    const int rc = check_window(p, fn, NEED_OPERATOR_PSF, rows, cols, stride, out_stride);
+    if (rc != FDR_OK) return rc;
+    FDR_HIP(hipSetDevice(p->device));
+    return host_image_call(p, fn, img_host, rows, cols, stride, out_host, rows, cols, out_stride, [&](const float* d_in, float* d_out) {
+        return blur_dev_impl(p, d_in, rows, cols, cols, d_out, cols, adjoint, nullptr);
+    });
+}
+
+int fdr_richardson_lucy_f32_dev(fdr_plan* p, const float* d_img, int rows, int cols, int stride, float* d_out, int out_stride, int iterations,
+                                int norm_area, void* stream) {
+    const char* fn = "fdr_richardson_lucy_f32_dev";
+    if (!p || !d_img || !d_out) return null_arg(fn);
+    const int rc = rl_check(p, fn, d_img, rows, cols, stride, d_out, out_stride, iterations, norm_area);
+    if (rc != FDR_OK) return rc;
+    FDR_HIP(hipSetDevice(p->device));
+    return rl_dev_impl(p, fn, d_img, rows, cols, stride, d_out, out_stride, iterations, norm_area, (hipStream_t)stream);
+}
+
+int fdr_richardson_lucy_f32(fdr_plan* p, const float* img_host, int rows, int cols, int stride, float* out_host, int out_stride,
+                            int iterations, int norm_area) {
+    const char* fn = "fdr_richardson_lucy_f32";
+    if (!p || !img_host || !out_host) return null_arg(fn);
+    const int rc = rl_check(p, fn, img_host, rows, cols, stride, out_host, out_stride, iterations, norm_area);
+    if (rc != FDR_OK) return rc;
+    FDR_HIP(hipSetDevice(p->device));
+    return host_image_call(p, fn, img_host, rows, cols, stride, out_host, rows, cols, out_stride, [&](const float* d_in, float* d_out) {
+        return rl_dev_impl(p, fn, d_in, rows, cols, cols, d_out, cols, iterations, norm_area, nullptr);
+    });
+}
+
+}  // extern "C"

@@ -551,6 +551,23 @@ hipError_t launch_synth(uint64_t seed, uint64_t first, size_t count, float* d_ou
     return hipGetLastError();
 }
 
+// ---- deterministic checksum of `count` floats (fdr_batch_run): per-block partial sums in double, folded on the host ----
+__global__ void checksum_kernel(const float* __restrict__ x, size_t count, double* __restrict__ part) {
+    __shared__ double red[4];
+    double acc = 0.0;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (size_t)gridDim.x * blockDim.x) acc += (double)x[i];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+hipError_t launch_checksum(const float* x, size_t count, double* part, hipStream_t s) {
+    hipLaunchKernelGGL(checksum_kernel, dim3(kChecksumParts), dim3(256), 0, s, x, count, part);
+    return hipGetLastError();
+}
+
 // ---- fft_serial::dft_naive_inplace (fft/fft_serial.cpp:71-87): one thread per output k, terms accumulated in the
 // reference's order t = 0..n-1, every product and sum rounded separately (-ffp-contract=off).
 // Table form (bit parity): table[t * n + k] = (cosf(ang), sinf(ang)) with ang = (float)(2.0f*CV_PI*k*t/n*sign) evaluated

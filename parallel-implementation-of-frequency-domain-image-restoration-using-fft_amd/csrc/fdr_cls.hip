@@ -3,7 +3,7 @@
 //     W(u, v) = conj(H) / (|H|^2 + K + gamma L(u, v)^2),   L(u, v) = 4 sin^2(pi u / M) + 4 sin^2(pi v / N)
 //
 // L is the symbol of the periodic 5-point Laplacian.  The plan keeps a_u = 4 sin^2(pi u / M) (u < M) followed by
-// b_v = 4 sin^2(pi v / N) (v < N) as a double table (fdr_api.hip, ensure_lap_table); cls_filter_fast / cls_reg
+// b_v = 4 sin^2(pi v / N) (v < N) as a double table (fdr_api_wiener.hip, ensure_lap_table); cls_filter_fast / cls_reg
 // (fdr_fft_core.hpp) evaluate the quotient in double and round once, as the Wiener filter does.  Two of the four filter
 // sites live here, in a translation unit of their own so that the Wiener kernels of fdr_panel.hip and fdr_aux.hip keep
 // their code: the PSF column pass of the panel path (half and full spectrum) and the pointwise filter of the simple path.

@@ -234,7 +234,7 @@ __device__ __forceinline__ float2 wiener_filter_fast(float2 h, float K) {
 
 // constrained least squares (fdr_set_psf_cls*): W = conj(H) / (|H|^2 + K + gamma L^2) with L = a_u + b_v the symbol of the
 // periodic 5-point Laplacian, a_u = 4 sin^2(pi u / M), b_v = 4 sin^2(pi v / N).  The double table `lap` holds a_0 .. a_{M-1}
-// then b_0 .. b_{N-1} (built on the host, fdr_api.hip); the quotient is evaluated in double and rounded once, as above.
+// then b_0 .. b_{N-1} (built on the host, fdr_api_wiener.hip); the quotient is evaluated in double and rounded once, as above.
 __device__ __forceinline__ double cls_reg(const double* __restrict__ lap, int M, int u, int v, double gamma) {
     const double L = lap[u] + lap[M + v];
     return gamma * (L * L);

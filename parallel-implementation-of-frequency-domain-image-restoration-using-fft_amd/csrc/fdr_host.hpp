@@ -1,0 +1,245 @@
+// fdr_host.hpp -- private to the host files of libfdr.so (fdr_api_*.hip): the plan, the pass and phase timers, the error
+// helpers and the helpers that more than one entry point uses.  The C ABI is include/fdr.h alone: the shared helpers live in
+// namespace fdr, so none of them is an fdr_* symbol of the library.
+#pragma once
+#include "../../include/fdr.h"
+#include "fdr_kernels.hpp"
+
+#include <hip/hip_runtime.h>
+#include <cstdio>
+#include <functional>
+#include <string>
+#include <vector>
+
+namespace fdr {
+
+extern thread_local std::string g_last_error;  // what fdr_last_error returns
+int fail(int code, const std::string& msg);     // g_last_error = msg, returns code
+int null_arg(const char* fn);                   // FDR_ERR_ARG, "<fn>: null argument"
+
+#define FDR_HIP(call)                                                                              \
+    do {                                                                                           \
+        hipError_t e_ = (call);                                                                    \
+        if (e_ != hipSuccess) {                                                                    \
+            char buf_[512];                                                                        \
+            snprintf(buf_, sizeof buf_, "%s:%d: %s: %s", __FILE__, __LINE__, #call, hipGetErrorString(e_)); \
+            return ::fdr::fail(FDR_ERR_HIP, buf_);                                                 \
+        }                                                                                          \
+    } while (0)
+
+struct PassTimer {
+    static constexpr int kMaxRecords = 8192;
+    struct Rec { hipEvent_t a, b; int pass; };
+    std::vector<Rec> recs;
+    std::vector<hipEvent_t> pool;
+    bool enabled = false;
+    const char* names[FDR_MAX_PASSES] = {nullptr};
+    int n_names = 0;
+
+    int pass_id(const char* name) {
+        for (int i = 0; i < n_names; ++i)
+            if (names[i] == name) return i;
+        if (n_names < FDR_MAX_PASSES) { names[n_names] = name; return n_names++; }
+        return FDR_MAX_PASSES - 1;
+    }
+    hipEvent_t get() {
+        if (!pool.empty()) { hipEvent_t e = pool.back(); pool.pop_back(); return e; }
+        hipEvent_t e = nullptr;
+        (void)hipEventCreate(&e);
+        return e;
+    }
+    void reset() {
+        for (auto& r : recs) { pool.push_back(r.a); pool.push_back(r.b); }
+        recs.clear();
+    }
+    void destroy() {
+        reset();
+        for (auto e : pool) (void)hipEventDestroy(e);
+        pool.clear();
+    }
+};
+
+}  // namespace fdr
+
+struct fdr_plan {
+    int device = 0, M = 0, N = 0, logM = 0, logN = 0, mode = 0;
+    unsigned flags = 0;
+    bool simple = false;
+    bool ppar = false;  // parity operator on a PANEL-major complex intermediate: contiguous column tiles
+    bool big = false;  // a power-of-two dimension above 8192: simple sequence with the long row pass (fdr_aux.hip)
+    int num_cu = 256;
+    bool tables_only = false;  // FDR_FLAG_TABLES_ONLY: no workspaces, slab primitives only
+    bool generic = false;  // FDR_FLAG_ANY_SIZE with a non-power-of-two dimension: naive DFT along that dimension
+    float2 *naive_row = nullptr, *naive_col = nullptr;  // n x n tables of the non-power-of-two dimensions (length N / M)
+    bool panel = false;
+    // FDR_FLAG_MIXED_RADIX in fast mode with a dimension that is not a power of two: the mixed-radix passes of fdr_mixed.hip on a
+    // panel-major full spectrum (mix_P columns per panel), row passes with mix_B transforms per workgroup
+    bool mixed = false;
+    fdr::MixLen mix_row{}, mix_col{};  // lengths N and M
+    int mix_P = 1, mix_logP = 0, mix_B = 1;
+    size_t pstride = 0;  // panel stride (float2 elements)
+    bool half = false;   // fast mode: only the non-redundant half of the Hermitian spectrum is kept (N/8 panels, Nyquist packed into column 0)
+    int npanels = 0;  // fast mode: panel-major intermediate spectrum and filter
+    float2 *tw_row_f = nullptr, *tw_row_i = nullptr, *tw_col_f = nullptr, *tw_col_i = nullptr;
+    float2* work = nullptr;   // M x N complex working spectrum
+    float2* work2 = nullptr;  // simple path: N x M transpose buffer
+    float2* filt = nullptr;   // H (parity) or W (fast)
+    float* raw = nullptr;     // M x N real plane before normalisation
+    float* psf_dev = nullptr; // staging for host-pointer / generated PSFs
+    float *stage_in = nullptr, *stage_out = nullptr;  // device staging of the host-pointer single-image calls: M x N each, kept between calls
+    size_t psf_cap = 0;
+    float* mm = nullptr;       // final {min, max}
+    float2* mm_part = nullptr; // per-workgroup partials
+    int mm_part_cap = 0;
+    float K = 0.f;
+    bool have_psf = false;
+    double* lap = nullptr;  // CLS filters (fdr_set_psf_cls*): a_u = 4 sin^2(pi u / M), u < M, then b_v = 4 sin^2(pi v / N), v < N
+    // blur / Richardson-Lucy operator (fdr_set_operator_psf*): H / (M N) and conj(H) / (M N) in the layout of `filt`, one allocation
+    // of 2 ws_elems (op_c = op_h + ws_elems), made by the first fdr_set_operator_psf* call; independent of `filt`
+    float2* op_h = nullptr;
+    float2* op_c = nullptr;
+    bool have_op = false;
+    // motion-blur estimate (fdr_cepstrum_f32*, fdr_estimate_motion_f32*): made by the first such call, kept until fdr_plan_destroy --
+    // one allocation holding the M x N complex plane, the pad partials + their sum, the Hann tables (M + N); the score table and the
+    // per-angle (cos, sin) table grow on demand.  Host copies of the table and the trig table are kept here too.
+    void* mo_block = nullptr;
+    float2* mo_plane = nullptr;
+    double* mo_part = nullptr;  // motion_pad_partials(M, N) partials, then their sum
+    float* mo_hann = nullptr;
+    float* mo_table = nullptr;
+    double* mo_trig = nullptr;
+    size_t mo_table_cap = 0, mo_trig_cap = 0;  // elements
+    std::vector<float> mo_table_host;
+    std::vector<double> mo_trig_host;
+    fdr::PassTimer timer;
+    // the reference Profiler's buckets (fdr_plan_phase_times): resolved sums + event pairs not read back yet
+    struct PhaseRec { hipEvent_t a, b; int phase; };
+    double phase_ms[FDR_N_PHASES] = {0, 0, 0, 0, 0, 0};
+    std::vector<PhaseRec> phase_pending;
+    // batched mode: images alternate over `nslots` private workspaces, each on its own internal stream,
+    // so the tail of one image's kernels overlaps the head of the next image's (slot 0 = the buffers above)
+    struct Slot {
+        float2* work = nullptr; float2* work2 = nullptr; float* raw = nullptr; float* mm = nullptr; float2* mm_part = nullptr;
+        hipStream_t stream = nullptr; hipEvent_t done = nullptr;
+    };
+    static constexpr int kMaxSlots = 16;
+    Slot slots[kMaxSlots];
+    int nslots = 1;   // = nstreams * group
+    int nstreams = 1;
+    int group = 1;    // images per pass-B' launch (panel path)
+    hipEvent_t fork = nullptr;
+    size_t ws_elems = 0;  // elements of one work / raw buffer
+    bool two_sweep = true;           // FDR_OPT_TWO_SWEEP_NORM: passes C1 + C2 instead of C' + E (fast half-spectrum path)
+    size_t ce_chunk_bytes = (size_t)160 << 20;  // FDR_OPT_CE_CHUNK_MB: spectrum bytes per C1 + C2 launch pair of a multi-stream batch (0 = whole group)
+    // FDR_OPT_BATCH_GRAPH: the launches of one fdr_wiener_batch_f32_dev call (fork, every pass of every group on the
+    // internal streams, join) captured once as a hipGraph and replayed while the call's arguments stay the same
+    struct GraphKey {
+        const float* in; float* out; size_t in_pitch, out_pitch; int count, rows, cols, stride, out_stride, norm_area, nstreams, group;
+        bool two_sweep; float K; size_t ce_cache;
+        bool operator==(const GraphKey& o) const {
+            return in == o.in && out == o.out && in_pitch == o.in_pitch && out_pitch == o.out_pitch && count == o.count && rows == o.rows &&
+                   cols == o.cols && stride == o.stride && out_stride == o.out_stride && norm_area == o.norm_area && nstreams == o.nstreams &&
+                   group == o.group && two_sweep == o.two_sweep && K == o.K && ce_cache == o.ce_cache;
+        }
+    };
+    // host-pointer batch (fdr_wiener_batch_*_f32): three streams, three images in flight; created on first use and kept --
+    // a driver that calls wienerDeblur_RGB_optimized once per picture (3 channels per call) would otherwise pay three
+    // hipStreamCreate, six hipMalloc / hipFree and nine event creations per call, most of such a call's time
+    // (LAB_NOTES "host-pointer calls")
+    struct HostPipe {
+        hipStream_t s_in = nullptr, s_cmp = nullptr, s_out = nullptr;
+        float* d_in[3] = {nullptr, nullptr, nullptr};
+        float* d_out[3] = {nullptr, nullptr, nullptr};
+        hipEvent_t e_in[3] = {nullptr, nullptr, nullptr}, e_cmp[3] = {nullptr, nullptr, nullptr}, e_out[3] = {nullptr, nullptr, nullptr};
+        size_t cap = 0;  // bytes of each d_in / d_out buffer
+        bool ready = false;  // all three streams and nine events exist
+    } pipe;
+    bool batch_graph = false;
+    hipGraphExec_t graph_exec = nullptr;
+    GraphKey graph_key{};
+    hipStream_t cap_stream = nullptr;
+};
+
+namespace fdr {
+
+struct ScopedPass {
+    fdr_plan* p; hipStream_t s; PassTimer::Rec rec; bool on;
+    ScopedPass(fdr_plan* plan, hipStream_t st, const char* name) : p(plan), s(st), on(false) {
+        if (p->timer.enabled && (int)p->timer.recs.size() < PassTimer::kMaxRecords) {
+            rec.a = p->timer.get(); rec.b = p->timer.get(); rec.pass = p->timer.pass_id(name);
+            on = rec.a && rec.b;
+            if (on) (void)hipEventRecord(rec.a, s);
+        }
+    }
+    ~ScopedPass() {
+        if (on) { (void)hipEventRecord(rec.b, s); p->timer.recs.push_back(rec); }
+    }
+};
+
+// folds the pending pairs whose end event has already completed (no waiting) into the sums; keeps the others
+void resolve_finished_phases(fdr_plan* p);
+// waits for every pending pair and folds it into the sums
+void resolve_phases(fdr_plan* p);
+
+// One hipEvent pair on stream s around a phase of the reference's Profiler (fft/fft_gpu.cu:17-57); read back by
+// resolve_phases.  Bounded at 1024 unread pairs; from 768 on, pairs that have completed are folded in first (no waiting), so only
+// a caller with more than 1024 phases IN FLIGHT at once loses records.
+struct ScopedPhase {
+    fdr_plan* p; hipStream_t s; fdr_plan::PhaseRec rec; bool on;
+    ScopedPhase(fdr_plan* plan, int phase, hipStream_t st) : p(plan), s(st), on(false) {
+        if (p->phase_pending.size() >= 768) resolve_finished_phases(p);  // long host batches / many PSF rebuilds: fold what has completed
+        if (p->phase_pending.size() < 1024) {
+            rec.a = p->timer.get(); rec.b = p->timer.get(); rec.phase = phase;
+            on = rec.a && rec.b;
+            if (on) (void)hipEventRecord(rec.a, s);
+        }
+    }
+    ~ScopedPhase() {
+        if (on) { (void)hipEventRecord(rec.b, s); p->phase_pending.push_back(rec); }
+    }
+};
+
+// ---- twiddle tables (fdr_api_plan.hip) ----
+int ilog2(int n);
+void build_twiddles(int n, int mode, bool inverse, std::vector<float2>& out);
+void build_naive_table(int n, std::vector<float2>& out);
+constexpr int kMaxNaiveLen = 4096;  // 128 MiB of table
+
+// ---- the checks of the entry points (fdr_api_plan.hip): a refusal names the entry point `fn` that was called and comes
+// before its first HIP call.  The kind of plan a call needs:
+enum PlanNeed {
+    NEED_PLAN,          // any plan with workspaces (not FDR_FLAG_TABLES_ONLY)
+    NEED_FILTER,        // ... holding a Wiener / CLS filter
+    NEED_OPERATOR,      // ... on the path of the blur operator (fast mode, half-spectrum panel path)
+    NEED_OPERATOR_PSF,  // ... holding the operator tables as well
+    NEED_MOTION         // ... that the motion estimate runs on
+};
+int check_plan(const fdr_plan* p, const char* fn, PlanNeed need);
+// check_plan, then the rows x cols window (row stride `stride`, of the result `out_stride`): at least min x min, within M x N
+int check_window(const fdr_plan* p, const char* fn, PlanNeed need, int rows, int cols, int stride, int out_stride, int min = 1);
+
+// ---- the one path of the nine PSF setters (fdr_api_plan.hip) ----
+// A PSF is a device or a host pointer (rows x cols, row stride `stride`) or a generated motion PSF (size in all three).
+enum PsfKind { PSF_DEV, PSF_HOST, PSF_MOTION };
+struct PsfSource { PsfKind kind; const float* ptr; int rows, cols, stride; double angle_deg; };
+// Checked completely, staged unless it is a device pointer, and built into the Wiener / CLS filter (op false; gamma 0 is the
+// Wiener filter) or into the blur / RL operator tables (op true).  A host PSF is ready when the call returns (fdr_batch_run relies
+// on it); device and generated PSFs stay asynchronous on `s`.
+int set_psf(fdr_plan* p, const char* fn, const PsfSource& src, bool op, float K, float gamma, hipStream_t s);
+// the builders, on a checked device PSF (fdr_api_wiener.hip, fdr_api_operator.hip)
+int set_psf_dev_impl(fdr_plan* p, const float* d_psf, int prows, int pcols, int pstride, float K, hipStream_t s, double gamma);
+int set_operator_psf_impl(fdr_plan* p, const float* d_psf, int prows, int pcols, int pstride, hipStream_t s);
+
+// ---- the host-pointer form of a single-image call (fdr_api_plan.hip) ----
+// The rows x cols image in through the plan's staging, run(d_in, d_out) on the null stream, the out_rows x out_cols result back
+// (none when `out` is null), in the phases H2D, COMPUTE and D2H; synchronous.  The caller has checked everything that can be refused.
+int host_image_call(fdr_plan* p, const char* fn, const float* in, int rows, int cols, int stride, float* out, int out_rows, int out_cols,
+                    int out_stride, const std::function<int(const float* d_in, float* d_out)>& run);
+
+// ---- the plan's transforms (fdr_api_misc.hip) ----
+// unscaled 2-D transform in place on d (M x N), rows then columns as fft/fft_serial.cpp:113-139
+int dft2d_dev(fdr_plan* p, float2* d, float2* work2, bool inverse, hipStream_t s);
+MixRowArgs mixed_row_args(const fdr_plan* p);
+MixColArgs mixed_col_args(const fdr_plan* p);
+
+}  // namespace fdr

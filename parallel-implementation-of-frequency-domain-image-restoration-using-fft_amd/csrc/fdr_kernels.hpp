@@ -193,6 +193,9 @@ struct ColorArgs {
 int color_partials(int rows, int cols);
 hipError_t launch_color_epilogue(const ColorArgs& a, double2* part, hipStream_t s);
 hipError_t launch_synth(uint64_t seed, uint64_t first, size_t count, float* d_out, hipStream_t s);
+// sum of `count` floats as kChecksumParts double partials in `part` (fixed order: the same bits on every run)
+constexpr int kChecksumParts = 1024;
+hipError_t launch_checksum(const float* x, size_t count, double* part, hipStream_t s);
 hipError_t launch_dft_naive(const float2* src, float2* dst, int n, int inverse, hipStream_t s);
 // table[t * n + k], forward direction, host generated (see fdr_aux.hip); rows transforms of length n, src != dst
 hipError_t launch_dft_naive_rows(const float2* src, float2* dst, int rows, int n, const float2* table, int inverse, hipStream_t s);
