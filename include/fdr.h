@@ -229,6 +229,49 @@ int fdr_richardson_lucy_f32(fdr_plan* plan, const float* img_host, int rows, int
 int fdr_richardson_lucy_f32_dev(fdr_plan* plan, const float* d_img, int rows, int cols, int stride, float* d_out, int out_stride,
                                 int iterations, int norm_area, void* stream);
 
+/* -- total-variation (TV) regularised deconvolution by ADMM / split Bregman (Rudin-Osher-Fatemi 1992; Wang-Yang-Yin-Zhang 2008
+ *    "FTVd"; Goldstein-Osher 2009): the edge-preserving restoration beside the linear filters and RL.  It uses the operator PSF of
+ *    fdr_set_operator_psf* (H = DFT2 of the PSF top-left in the plan, blur / blur^T as above) and lives on the whole periodic
+ *    M x N plan: pad(d) is d on the window rows x cols and 0 elsewhere, the result is cropped.  Differences are forward and periodic,
+ *        Dx x[i, j] = x[i, (j+1) % N] - x[i, j],   Dy x[i, j] = x[(i+1) % M, j] - x[i, j],   Dx^T v[i, j] = v[i, (j-1) % N] - v[i, j]
+ *    and |DFT(Dx)|^2 + |DFT(Dy)|^2 = L(u, v) = 4 sin^2(pi u / M) + 4 sin^2(pi v / N), the Laplacian symbol of the CLS filter.
+ *        minimise over x (M x N):  mu / 2 ||blur(x) - pad(d)||^2 + TV(x)
+ *        TV(x) = sum sqrt((Dx x)^2 + (Dy x)^2)  (isotropic)   or   sum |Dx x| + |Dy x|  (anisotropic)
+ *        b = mu blur^T(pad(d)) over the whole plan;  x = pad(d);  wx = wy = 0;  t = 1 / rho;  n = iterations times:
+ *            gx = Dx x + wx;  gy = Dy x + wy
+ *            isotropic:    m = sqrt(gx^2 + gy^2);  s = m > t ? 1 - t / m : 0;  zx = s gx;  zy = s gy
+ *            anisotropic:  zx = sign(gx) max(|gx| - t, 0);  zy likewise
+ *            wx = gx - zx;  wy = gy - zy;  vx = zx - wx;  vy = zy - wy
+ *            x = IDFT2( DFT2(b + rho (Dx^T vx + Dy^T vy)) / (mu |H|^2 + rho L) )        (IDFT2 includes 1 / (M N))
+ *    The output is x on the window -- max(x, 0) with nonneg (the output only, never the iterate) -- normalised by norm_area as
+ *    fdr_richardson_lucy_* defines FDR_NORM_NONE / _CROPPED / _PADDED.  n = 0 returns the window of pad(d).  mu weighs the data
+ *    term (larger: closer to the data, less smoothing; about 1 / noise variance times the step you accept), rho is the ADMM
+ *    penalty (it changes the path, not the minimiser; 1 .. 10 are usual).  The quotient table is evaluated in double and rounded
+ *    once; a zero denominator (a PSF of sum 0) gives 0 there, as in the CLS filter.
+ *    Plans as the operator's: FDR_MODE_FAST, M and N powers of two, 8 <= M <= 8192, 32 <= N <= 8192, neither FDR_FLAG_SIMPLE_PATH
+ *    nor FDR_FLAG_FULL_SPECTRUM; every other plan FDR_ERR_ARG before any device work, a tables-only plan FDR_ERR_STATE, no
+ *    operator PSF FDR_ERR_STATE.  FDR_ERR_ARG for mu or rho not finite or <= 0, iterations < 0, an unknown norm_area, a null
+ *    params pointer or a window that does not fit; the plan stays usable after every refusal.  Unlike RL the output may be the
+ *    input (d is read before anything is written).  Batches, fdr_batch_run and fdr_slab_* do not cover it.
+ *    The first call on a plan allocates the TV workspace, kept until fdr_plan_destroy: the table (fdr_plan_filter_bytes) and six
+ *    M x N float planes -- 24 M N + 8 M N bytes, about 1.8 GB at 8192^2 beside the plan's own; FDR_ERR_ALLOC, plan intact, if it
+ *    cannot be had -- and, if no CLS call has, the M + N doubles of L.  After it the _dev form allocates nothing and is
+ *    asynchronous on `stream`; the table is rebuilt (one pointwise pass, no transform) when mu, rho or the operator PSF changed.
+ *    The host form copies in and out synchronously and counts as COMPUTE.  An iteration moves about 80 bytes per padded pixel
+ *    (DESIGN.md section 14).                                                                                                 */
+typedef struct fdr_tv_params {
+    float mu;        /* weight of the data term, > 0 */
+    float rho;       /* ADMM penalty, > 0 */
+    int iterations;  /* >= 0 */
+    int anisotropic; /* 0: isotropic TV, else anisotropic */
+    int nonneg;      /* != 0: the output is max(x, 0) */
+    int norm_area;   /* FDR_NORM_NONE / FDR_NORM_CROPPED / FDR_NORM_PADDED */
+} fdr_tv_params;
+int fdr_tv_deconv_f32(fdr_plan* plan, const float* img_host, int rows, int cols, int stride, float* out_host, int out_stride,
+                      const fdr_tv_params* params);
+int fdr_tv_deconv_f32_dev(fdr_plan* plan, const float* d_img, int rows, int cols, int stride, float* d_out, int out_stride,
+                          const fdr_tv_params* params, void* stream);
+
 /* -- the motion-blur estimate: the length and angle of a uniform linear motion blur, from the blurred
  *    picture alone, by the power cepstrum.  The blur puts sinc zeros into |G| in stripes across the motion direction; in the
  *    cepstrum they show as a negative peak at distance L along it.  The plan is M x N, the image window rows x cols (row stride

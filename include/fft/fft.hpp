@@ -212,6 +212,28 @@ inline void richardsonLucy_RGB(std::vector<Mat>& channels, const Mat& psf, int i
 inline void richardsonLucy_RGB(std::vector<Mat>& channels, const Mat& psf, int iterations) {
     richardsonLucy_RGB(channels, psf, iterations, defaults());
 }
+// Total-variation deconvolution (fdr_tv_deconv_f32, include/fdr.h) of every channel, in place: the plan and operator PSF of
+// richardsonLucy_RGB, `iterations` ADMM steps of mu / 2 ||blur(x) - d||^2 + TV(x) (isotropic) with penalty rho, the output clamped
+// at 0 and normalised by o.norm_area.  o.mode and o.cls_gamma do not apply.
+inline void tvDeblur_RGB(std::vector<Mat>& channels, const Mat& psf, float mu, int iterations, float rho, const Options& o) {
+    if (channels.empty()) return;
+    const int rows = channels[0].rows, cols = channels[0].cols;
+    bool created = false;
+    PlanCacheSettle settle_;
+    fdr_plan* plan = plan_cache().get(o.device, std::max(8, nextPowerOfTwo(rows)), std::max(32, nextPowerOfTwo(cols)), FDR_MODE_FAST, &created);
+    Mat psfc = psf.isContinuous() ? psf : psf.clone();
+    FDR_CHECK(fdr_set_operator_psf(plan, psfc.ptr<float>(0), psf.rows, psf.cols, psf.cols));
+    const fdr_tv_params prm = {mu, rho, iterations, 0, 1, o.norm_area};
+    for (Mat& c : channels) {
+        Mat src = c.isContinuous() ? c : c.clone();
+        Mat out(c.rows, c.cols, CV_32F);
+        FDR_CHECK(fdr_tv_deconv_f32(plan, src.ptr<float>(0), c.rows, c.cols, c.cols, out.ptr<float>(0), c.cols, &prm));
+        c = out;
+    }
+}
+inline void tvDeblur_RGB(std::vector<Mat>& channels, const Mat& psf, float mu, int iterations = 50, float rho = 2.0f) {
+    tvDeblur_RGB(channels, psf, mu, iterations, rho, defaults());
+}
 // The motion blur of a one-channel picture of unknown blur (fdr_estimate_motion_f32, include/fdr.h): length and angle in the
 // convention of motionBlurKernel, the table minimum and the confidence (below about 10: no clear blur).  Its own FDR_MODE_FAST plan
 // (each dimension padded to fdr_optimal_dft_size, at least 32; FDR_FLAG_MIXED_RADIX), made and freed inside the call.  0 selects an

@@ -59,6 +59,12 @@ class BatchStats(ctypes.Structure):
                 ("wall_ms", ctypes.c_double), ("images_done", ctypes.c_longlong), ("mpixels_per_s", ctypes.c_double), ("filter_path", ctypes.c_int)]
 
 
+class TvParams(ctypes.Structure):
+    """fdr_tv_params of include/fdr.h"""
+    _fields_ = [("mu", ctypes.c_float), ("rho", ctypes.c_float), ("iterations", ctypes.c_int), ("anisotropic", ctypes.c_int),
+                ("nonneg", ctypes.c_int), ("norm_area", ctypes.c_int)]
+
+
 class MotionEstimateC(ctypes.Structure):
     """fdr_motion_estimate of include/fdr.h"""
     _fields_ = [("length", ctypes.c_int), ("angle_deg", ctypes.c_double), ("score", ctypes.c_float), ("confidence", ctypes.c_float),
@@ -168,6 +174,8 @@ def _load():
     L.fdr_blur_f32_dev.argtypes = [vp, vp, ci, ci, ci, vp, ci, ci, vp]
     L.fdr_richardson_lucy_f32.argtypes = [vp, vp, ci, ci, ci, vp, ci, ci, ci]
     L.fdr_richardson_lucy_f32_dev.argtypes = [vp, vp, ci, ci, ci, vp, ci, ci, ci, vp]
+    L.fdr_tv_deconv_f32.argtypes = [vp, vp, ci, ci, ci, vp, ci, ctypes.POINTER(TvParams)]
+    L.fdr_tv_deconv_f32_dev.argtypes = [vp, vp, ci, ci, ci, vp, ci, ctypes.POINTER(TvParams), vp]
     L.fdr_cepstrum_f32.argtypes = [vp, vp, ci, ci, ci, vp]
     L.fdr_cepstrum_f32_dev.argtypes = [vp, vp, ci, ci, ci, vp, vp]
     L.fdr_estimate_motion_f32.argtypes = [vp, vp, ci, ci, ci, ci, ci, cd, ctypes.POINTER(MotionEstimateC), vp]
@@ -184,7 +192,7 @@ def _load():
                  "fdr_plan_filter_bytes", "fdr_plan_export_filter_dev", "fdr_plan_import_filter_dev",
                  "fdr_set_psf_cls", "fdr_set_psf_cls_dev", "fdr_set_psf_motion_cls", "fdr_set_operator_psf", "fdr_set_operator_psf_dev",
                  "fdr_set_operator_psf_motion", "fdr_blur_f32", "fdr_blur_f32_dev", "fdr_richardson_lucy_f32", "fdr_richardson_lucy_f32_dev",
-                 "fdr_cepstrum_f32", "fdr_cepstrum_f32_dev", "fdr_estimate_motion_f32", "fdr_estimate_motion_f32_dev"):
+                 "fdr_tv_deconv_f32", "fdr_tv_deconv_f32_dev", "fdr_cepstrum_f32", "fdr_cepstrum_f32_dev", "fdr_estimate_motion_f32", "fdr_estimate_motion_f32_dev"):
         getattr(L, name).restype = ci
     return L
 
@@ -204,7 +212,7 @@ EXPORTED_SYMBOLS = (
     "fdr_plan_filter_bytes", "fdr_plan_export_filter_dev", "fdr_plan_import_filter_dev",
     "fdr_set_psf_cls", "fdr_set_psf_cls_dev", "fdr_set_psf_motion_cls", "fdr_set_operator_psf", "fdr_set_operator_psf_dev",
     "fdr_set_operator_psf_motion", "fdr_blur_f32", "fdr_blur_f32_dev", "fdr_richardson_lucy_f32", "fdr_richardson_lucy_f32_dev",
-    "fdr_cepstrum_f32", "fdr_cepstrum_f32_dev", "fdr_estimate_motion_f32", "fdr_estimate_motion_f32_dev")
+    "fdr_tv_deconv_f32", "fdr_tv_deconv_f32_dev", "fdr_cepstrum_f32", "fdr_cepstrum_f32_dev", "fdr_estimate_motion_f32", "fdr_estimate_motion_f32_dev")
 
 
 def _check(rc):
@@ -454,6 +462,21 @@ class Plan:
         _check(lib.fdr_richardson_lucy_f32_dev(self._h, ctypes.c_void_p(int(d_img)), rows, cols, stride, ctypes.c_void_p(int(d_out)),
                                                out_stride, int(iterations), int(norm_area), _stream(stream)))
 
+    # total-variation deconvolution by ADMM (include/fdr.h); uses the operator PSF
+    def tv_deconv(self, img, mu, rho=2.0, iterations=50, anisotropic=False, nonneg=False, norm_area=NORM_NONE):
+        """`iterations` ADMM steps of mu / 2 ||blur(x) - img||^2 + TV(x) on the window img (host arrays), normalised by norm_area."""
+        img = np.ascontiguousarray(img, dtype=np.float32)
+        out = np.empty_like(img)
+        prm = TvParams(float(mu), float(rho), int(iterations), int(bool(anisotropic)), int(bool(nonneg)), int(norm_area))
+        _check(lib.fdr_tv_deconv_f32(self._h, _ptr(img), img.shape[0], img.shape[1], img.shape[1], _ptr(out), img.shape[1], ctypes.byref(prm)))
+        return out
+
+    def tv_deconv_dev(self, d_img, rows, cols, stride, d_out, out_stride, mu, rho=2.0, iterations=50, anisotropic=False, nonneg=False,
+                      norm_area=NORM_NONE, stream=None):
+        prm = TvParams(float(mu), float(rho), int(iterations), int(bool(anisotropic)), int(bool(nonneg)), int(norm_area))
+        _check(lib.fdr_tv_deconv_f32_dev(self._h, ctypes.c_void_p(int(d_img)), rows, cols, stride, ctypes.c_void_p(int(d_out)), out_stride,
+                                         ctypes.byref(prm), _stream(stream)))
+
     # the motion-blur estimate (include/fdr.h): the power cepstrum of the windowed picture and the blur it shows
     def cepstrum(self, img):
         """c = Re IDFT2(log(|DFT2(hann . img)| + eps)) on the plan (M x N float32); img is the window at the top-left (host array)"""
@@ -615,6 +638,16 @@ def richardsonLucy_myfft(img, psf, iterations, device=0, norm_area=NORM_NONE):
     with Plan(M, N, MODE_FAST, device) as p:
         p.set_operator_psf(psf)
         return p.richardson_lucy(img, iterations, norm_area)
+
+
+def tvDeblur_myfft(img, psf, mu, rho=2.0, iterations=50, anisotropic=False, nonneg=False, device=0, norm_area=NORM_NONE):
+    """Total-variation deconvolution of one channel: the plan of richardsonLucy_myfft (each dimension padded to the next power of
+    two, at least 8 rows and 32 columns), `iterations` ADMM steps on the device, crop.  psf lies top-left in the plan."""
+    img = np.asarray(img, dtype=np.float32)
+    M, N = _rl_plan_size(img.shape[0], img.shape[1])
+    with Plan(M, N, MODE_FAST, device) as p:
+        p.set_operator_psf(psf)
+        return p.tv_deconv(img, mu, rho, iterations, anisotropic, nonneg, norm_area)
 
 
 def _motion_plan_size(rows, cols):

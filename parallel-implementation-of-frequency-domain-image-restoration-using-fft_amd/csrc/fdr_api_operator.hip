@@ -52,12 +52,9 @@ int set_operator_psf_impl(fdr_plan* p, const float* d_psf, int prows, int pcols,
         FDR_HIP(launch_cols_panel_operator(p->logM, ca, p->op_c, p->tw_col_f, s));
     }
     p->have_op = true;
+    ++p->op_gen;
     return FDR_OK;
 }
-
-}  // namespace fdr
-
-namespace {
 
 // pass A: the window of x (zero elsewhere) -> the half spectrum of slot 0
 int op_rows_fwd(fdr_plan* p, const float* x, int rows, int cols, int stride, hipStream_t s) {
@@ -68,11 +65,11 @@ int op_rows_fwd(fdr_plan* p, const float* x, int rows, int cols, int stride, hip
     FDR_HIP(launch_rows4(p->logN, ROW_IN_REAL, ROW_OUT_COMPLEX, a, p->tw_row_f, s));
     return FDR_OK;
 }
-// pass B', unchanged, on one of the operator tables
-int op_cols(fdr_plan* p, bool adjoint, hipStream_t s) {
-    ScopedPass t(p, s, adjoint ? kPassOpColsConj : kPassOpColsH);
+// pass B', unchanged, with `table` as its filter
+int op_cols_table(fdr_plan* p, const float2* table, const char* name, hipStream_t s) {
+    ScopedPass t(p, s, name);
     ColArgs c{};
-    c.data = p->work; c.filt = adjoint ? p->op_c : p->op_h; c.N = p->N; c.num_cu = p->num_cu;
+    c.data = p->work; c.filt = table; c.N = p->N; c.num_cu = p->num_cu;
     c.pstride = p->pstride; c.npanels = p->npanels; c.packed0 = 1;
     c.batch.nimg = 1; c.batch.data[0] = p->work;
     FDR_HIP(launch_cols_panel(p->logM, COL_FUSED, c, p->tw_col_f, s));
@@ -90,11 +87,44 @@ int op_rows_inv(fdr_plan* p, RowOut kind, const char* name, const float* src, in
     return FDR_OK;
 }
 
-int blur_dev_impl(fdr_plan* p, const float* d_img, int rows, int cols, int stride, float* d_out, int out_stride, int adjoint, hipStream_t s) {
+// min-max to [0, 1] over the window; FDR_NORM_PADDED also counts the zeros outside it (one extra (0, 0) partial)
+int normalize_window(fdr_plan* p, const char* fn, const char* name, const float* fin, int fs, int rows, int cols, int norm_area, float* d_out,
+                     int out_stride, hipStream_t s) {
+    ScopedPass t(p, s, name);
+    int n_part = 0;
+    FDR_HIP(launch_minmax_real(fin, rows, fs, rows, cols, p->mm_part, &n_part, s));
+    if (norm_area == FDR_NORM_PADDED && (rows < p->M || cols < p->N)) {
+        if (n_part + 1 > p->mm_part_cap) return fail(FDR_ERR_STATE, std::string(fn) + ": min/max partial count out of range");
+        FDR_HIP(hipMemsetAsync(p->mm_part + n_part, 0, sizeof(float2), s));  // (0.f, 0.f)
+        ++n_part;
+    }
+    if (n_part <= 0 || n_part > p->mm_part_cap) return fail(FDR_ERR_STATE, std::string(fn) + ": min/max partial count out of range");
+    FDR_HIP(launch_reduce_minmax(p->mm_part, n_part, p->mm, s));
+    FDR_HIP(launch_normalize(fin, fs, nullptr, 0, p->mm, d_out, rows, cols, out_stride, s));
+    return FDR_OK;
+}
+
+// pass B' on one of the operator tables
+static int op_cols(fdr_plan* p, bool adjoint, hipStream_t s) {
+    return op_cols_table(p, adjoint ? p->op_c : p->op_h, adjoint ? kPassOpColsConj : kPassOpColsH, s);
+}
+
+// blur (or blur^T) of the window rows x cols of d_img, the window out_rows x out_cols of the result into d_out
+int blur_window_dev(fdr_plan* p, const float* d_img, int rows, int cols, int stride, float* d_out, int out_stride, int out_rows, int out_cols,
+                    int adjoint, hipStream_t s) {
     int rc = op_rows_fwd(p, d_img, rows, cols, stride, s);
     if (rc == FDR_OK) rc = op_cols(p, adjoint != 0, s);
-    if (rc == FDR_OK) rc = op_rows_inv(p, ROW_OUT_BLUR, kPassOpRowsBlur, nullptr, 0, d_out, out_stride, rows, cols, s);
+    if (rc == FDR_OK) rc = op_rows_inv(p, ROW_OUT_BLUR, kPassOpRowsBlur, nullptr, 0, d_out, out_stride, out_rows, out_cols, s);
     return rc;
+}
+
+}  // namespace fdr
+
+namespace {
+
+
+int blur_dev_impl(fdr_plan* p, const float* d_img, int rows, int cols, int stride, float* d_out, int out_stride, int adjoint, hipStream_t s) {
+    return blur_window_dev(p, d_img, rows, cols, stride, d_out, out_stride, rows, cols, adjoint, s);
 }
 
 // [lo, hi) of the elements a rows x cols window with row stride `stride` spans
@@ -145,19 +175,7 @@ int rl_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, int c
                              cols, s);                                                                    // ... u = max(u g, 0)
     }
     if (rc != FDR_OK || !norm) return rc;
-    // min-max to [0, 1] over the window; FDR_NORM_PADDED also counts the zeros of u outside it (one extra (0, 0) partial)
-    ScopedPass t(p, s, kPassRlNorm);
-    int n_part = 0;
-    FDR_HIP(launch_minmax_real(fin, rows, fs, rows, cols, p->mm_part, &n_part, s));
-    if (norm_area == FDR_NORM_PADDED && (rows < p->M || cols < p->N)) {
-        if (n_part + 1 > p->mm_part_cap) return fail(FDR_ERR_STATE, std::string(fn) + ": min/max partial count out of range");
-        FDR_HIP(hipMemsetAsync(p->mm_part + n_part, 0, sizeof(float2), s));  // (0.f, 0.f)
-        ++n_part;
-    }
-    if (n_part <= 0 || n_part > p->mm_part_cap) return fail(FDR_ERR_STATE, std::string(fn) + ": min/max partial count out of range");
-    FDR_HIP(launch_reduce_minmax(p->mm_part, n_part, p->mm, s));
-    FDR_HIP(launch_normalize(fin, fs, nullptr, 0, p->mm, d_out, rows, cols, out_stride, s));
-    return FDR_OK;
+    return normalize_window(p, fn, kPassRlNorm, fin, fs, rows, cols, norm_area, d_out, out_stride, s);
 }
 
 }  // namespace

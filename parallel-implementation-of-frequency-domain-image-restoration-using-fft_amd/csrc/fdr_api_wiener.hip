@@ -37,8 +37,12 @@ struct GroupedName {
 const GroupedName kPassRowsFwdN(kPassRowsFwd), kPassColsFusedN(kPassColsFused), kPassRowsInvRealN(kPassRowsInvReal),
     kPassNormalizeN(kPassNormalize), kPassRowsMinmaxN(kPassRowsMinmax), kPassRowsNormN(kPassRowsNorm);
 
-// The Laplacian table of the CLS filters, built in double on the host and uploaded on the first fdr_set_psf_cls* call of a plan
-// (synchronous, outside the PRE phase); freed with the plan.  sin^2, not 2 - 2 cos: no cancellation at small frequencies.
+}  // namespace
+
+namespace fdr {
+
+// The Laplacian table of the CLS filters and of the TV solve, built in double on the host and uploaded on the first fdr_set_psf_cls* or
+// fdr_tv_deconv_f32* call of a plan (synchronous, outside the PRE phase); freed with the plan.  sin^2, not 2 - 2 cos: no cancellation at small frequencies.
 int ensure_lap_table(fdr_plan* p) {
     if (p->lap) return FDR_OK;
     std::vector<double> t((size_t)p->M + p->N);
@@ -52,10 +56,6 @@ int ensure_lap_table(fdr_plan* p) {
     p->lap = d;
     return FDR_OK;
 }
-
-}  // namespace
-
-namespace fdr {
 
 // gamma > 0: the constrained least-squares filter W = conj(H) / (|H|^2 + K + gamma L^2) (fast mode only); gamma == 0: the Wiener filter
 int set_psf_dev_impl(fdr_plan* p, const float* d_psf, int prows, int pcols, int pstride, float K, hipStream_t s, double gamma) {

@@ -93,12 +93,21 @@ struct fdr_plan {
     int mm_part_cap = 0;
     float K = 0.f;
     bool have_psf = false;
-    double* lap = nullptr;  // CLS filters (fdr_set_psf_cls*): a_u = 4 sin^2(pi u / M), u < M, then b_v = 4 sin^2(pi v / N), v < N
+    double* lap = nullptr;  // CLS filters (fdr_set_psf_cls*) and the TV solve table: a_u = 4 sin^2(pi u / M), u < M, then b_v = 4 sin^2(pi v / N), v < N
     // blur / Richardson-Lucy operator (fdr_set_operator_psf*): H / (M N) and conj(H) / (M N) in the layout of `filt`, one allocation
     // of 2 ws_elems (op_c = op_h + ws_elems), made by the first fdr_set_operator_psf* call; independent of `filt`
     float2* op_h = nullptr;
     float2* op_c = nullptr;
     bool have_op = false;
+    unsigned op_gen = 0;  // counts the fdr_set_operator_psf* calls that rebuilt the tables
+    // total-variation deconvolution (fdr_tv_deconv_f32*): made by the first such call, kept until fdr_plan_destroy -- one allocation
+    // holding the solve table T (ws_elems, layout of `filt`) and six M x N real planes: x, b and two pairs of duals (rhs lives in `raw`).
+    // T was built for (tv_mu, tv_rho) and the operator tables of generation tv_gen; tv_gen 0 = not built.
+    void* tv_block = nullptr;
+    float2* tv_T = nullptr;
+    float *tv_x = nullptr, *tv_b = nullptr, *tv_w[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};  // tv_w[pair][0 = wx, 1 = wy]
+    float tv_mu = 0.f, tv_rho = 0.f;
+    unsigned tv_gen = 0;
     // motion-blur estimate (fdr_cepstrum_f32*, fdr_estimate_motion_f32*): made by the first such call, kept until fdr_plan_destroy --
     // one allocation holding the M x N complex plane, the pad partials + their sum, the Hann tables (M + N); the score table and the
     // per-angle (cos, sin) table grow on demand.  Host copies of the table and the trig table are kept here too.
@@ -229,6 +238,29 @@ int set_psf(fdr_plan* p, const char* fn, const PsfSource& src, bool op, float K,
 // the builders, on a checked device PSF (fdr_api_wiener.hip, fdr_api_operator.hip)
 int set_psf_dev_impl(fdr_plan* p, const float* d_psf, int prows, int pcols, int pstride, float K, hipStream_t s, double gamma);
 int set_operator_psf_impl(fdr_plan* p, const float* d_psf, int prows, int pcols, int pstride, hipStream_t s);
+
+// the Laplacian table of the CLS filters and of the TV solve (fdr_api_wiener.hip): built in double on the host and uploaded on first
+// use (synchronous), freed with the plan
+int ensure_lap_table(fdr_plan* p);
+
+// ---- the operator passes (fdr_api_operator.hip), shared by the blur, Richardson-Lucy and the TV solve ----
+// pass A: the window of x (zero elsewhere) -> the half spectrum of slot 0
+int op_rows_fwd(fdr_plan* p, const float* x, int rows, int cols, int stride, hipStream_t s);
+// pass B', unchanged, with `table` as its filter; timed as `name`
+int op_cols_table(fdr_plan* p, const float2* table, const char* name, hipStream_t s);
+// pass C with an operator kind: the window rows x cols of the inverse transform through the kind's epilogue into `out`
+int op_rows_inv(fdr_plan* p, RowOut kind, const char* name, const float* src, int src_stride, float* out, int out_stride, int rows, int cols,
+                hipStream_t s);
+// blur (adjoint != 0: blur^T) of the window rows x cols of d_img; the window out_rows x out_cols of the result into d_out
+int blur_window_dev(fdr_plan* p, const float* d_img, int rows, int cols, int stride, float* d_out, int out_stride, int out_rows, int out_cols,
+                    int adjoint, hipStream_t s);
+// min-max of the window `fin` (row stride fs) to [0, 1] into d_out, timed as `name`: FDR_NORM_CROPPED over the window, FDR_NORM_PADDED
+// counting the zeros outside it too
+int normalize_window(fdr_plan* p, const char* fn, const char* name, const float* fin, int fs, int rows, int cols, int norm_area, float* d_out,
+                     int out_stride, hipStream_t s);
+// the entry points of fdr_api_tv.hip
+int tv_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, int cols, int stride, float* d_out, int out_stride,
+                const fdr_tv_params& prm, hipStream_t s);
 
 // ---- the host-pointer form of a single-image call (fdr_api_plan.hip) ----
 // The rows x cols image in through the plan's staging, run(d_in, d_out) on the null stream, the out_rows x out_cols result back

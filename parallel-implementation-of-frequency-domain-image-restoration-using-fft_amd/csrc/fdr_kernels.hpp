@@ -132,6 +132,17 @@ hipError_t launch_cols_panel_cls(int logm, const ColArgs& a, const double* lap, 
 hipError_t launch_cols_panel_operator(int logm, const ColArgs& a, float2* conj_out, const float2* tw_fwd, hipStream_t s);
 // (fdr_rl.hip) u = max(d, 0) on a rows x cols window (row strides `stride` / `ustride`)
 hipError_t launch_rl_init(const float* d, int rows, int cols, int stride, float* u, int ustride, hipStream_t s);
+// (fdr_tv.hip) total-variation deconvolution.  table: T = (1 / (M N)) / (mu |H|^2 + rho L) from op_h = H / (M N) (the operator table
+// of launch_cols_panel_operator) and the Laplacian table `lap` of launch_cols_panel_cls, in the layout pass B' reads its filter
+// from.  init: x = pad(d) over the M x N plan (row stride N), wx = wy = 0.  spatial: one ADMM half-step on full M x N planes --
+// reads x, (wx, wy), b, writes the new duals (nwx, nwy; not the planes read) and rhs = mu b + rho D^T v (not x).  output: the window
+// of x to `out`, clamped at 0 with nonneg.
+hipError_t launch_tv_table(const float2* op_h, float2* T, const double* lap, int M, int N, size_t pstride, int npanels, double mu, double rho,
+                           hipStream_t s);
+hipError_t launch_tv_init(const float* d, int rows, int cols, int stride, float* x, float* wx, float* wy, int M, int N, hipStream_t s);
+hipError_t launch_tv_spatial(const float* x, const float* wx, const float* wy, const float* b, float* nwx, float* nwy, float* rhs, int M, int N,
+                             float mu, float rho, int anisotropic, hipStream_t s);
+hipError_t launch_tv_output(const float* x, int N, float* out, int rows, int cols, int out_stride, int nonneg, hipStream_t s);
 
 // (fdr_motion.hip) the motion-blur estimate.  window: the Hann tables into hann[rows + cols], w . img on the window and 0 elsewhere
 // into the row-major M x N complex plane, sum |x| partials (motion_pad_partials of them) folded in a fixed order into

@@ -1,5 +1,5 @@
 // gpu.cpp -- ./gpu <img-path> <psf-length> <psf-angle> [--out file] [--mode fast|parity] [--norm padded|cropped] [--host-epilogue]
-//           [--cls gamma] [--rl iterations]
+//           [--cls gamma] [--rl iterations] [--tv mu [--tv-iters n] [--tv-rho r]]
 // `auto auto` for length and angle: the blur is estimated first (fft_gpu::estimateMotionBlur on the per-pixel mean of B, G and R),
 // printed as `estimate: length L angle A confidence C`, and the run then goes on exactly as `./gpu <img-path> L A` would.
 // Drop-in counterpart of the reference's gpu.cpp (argument meaning, printed lines and exit codes as at
@@ -67,6 +67,9 @@ int main(int argc, char** argv) {
     bool verify = false;         // --verify: areChannelsEqual(parity-mode result, this run's result)
     bool host_epilogue = false;  // Lab white balance on the host (the A/B reference of the device epilogue)
     int rl_iterations = -1;      // --rl n: a timed Richardson-Lucy leg after the naive one; its planes are the written result
+    float tv_mu = -1.f, tv_rho = 2.0f;  // --tv mu: a timed total-variation leg (fft_gpu::tvDeblur_RGB); its planes are the written result
+    int tv_iterations = 50;
+    bool tv_opts = false;
     bool cls = false, parity = false;
     for (int i = 4; i < argc; ++i) {
         string a = argv[i];
@@ -84,10 +87,20 @@ int main(int argc, char** argv) {
         else if (a == "--cls" && i + 1 < argc) { cls = true; fft_gpu::set_cls_gamma(strtof(argv[++i], nullptr)); }
         // Richardson-Lucy (fft_gpu::richardsonLucy_RGB, fast mode): n >= 0 iterations
         else if (a == "--rl" && i + 1 < argc) rl_iterations = atoi(argv[++i]);
+        // total-variation deconvolution (fft_gpu::tvDeblur_RGB, fast mode): mu > 0, n >= 0 iterations, penalty rho > 0
+        else if (a == "--tv" && i + 1 < argc) tv_mu = strtof(argv[++i], nullptr);
+        else if (a == "--tv-iters" && i + 1 < argc) { tv_opts = true; tv_iterations = atoi(argv[++i]); }
+        else if (a == "--tv-rho" && i + 1 < argc) { tv_opts = true; tv_rho = strtof(argv[++i], nullptr); }
         else { cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle>\n"; return -1; }
     }
     // the RL leg replaces the result the other options shape (CLS filter, parity check, parity-mode restoration)
     if (rl_iterations >= 0 && (cls || verify || parity)) { cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle>\n"; return -1; }
+    // so does the TV leg; --tv-iters / --tv-rho belong to --tv, and one run has one iterative leg
+    const bool tv = tv_mu > 0.f;
+    if ((tv && (cls || verify || parity || rl_iterations >= 0 || tv_iterations < 0 || !(tv_rho > 0.f))) || (!tv && (tv_opts || tv_mu != -1.f))) {
+        cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle>\n";
+        return -1;
+    }
 
     Mat img = fdr_io::imread(img_path);
     if (img.empty()) { cout << "Cannot read image\n"; return -1; }
@@ -160,6 +173,16 @@ int main(int argc, char** argv) {
         t_end = high_resolution_clock::now();
         cout << "Deblurring 3 channels took(gpu[richardson-lucy " << rl_iterations << "]): " << getElapsedMs(t_start, t_end) << " ms\n";
         channels = rl;
+    }
+
+    if (tv) {  // total-variation deconvolution on the same channels: its planes become the written result
+        vector<Mat> tvc = input;
+        t_start = high_resolution_clock::now();
+        fft_gpu::tvDeblur_RGB(tvc, psf, tv_mu, tv_iterations, tv_rho);
+        t_end = high_resolution_clock::now();
+        cout << "Deblurring 3 channels took(gpu[total-variation mu " << tv_mu << " rho " << tv_rho << " n " << tv_iterations
+             << "]): " << getElapsedMs(t_start, t_end) << " ms\n";
+        channels = tvc;
     }
 
     if (verify) {  // the check of gpu.cpp:116-121 between the serial leg's planes and this run's planes
