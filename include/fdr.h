@@ -229,6 +229,50 @@ int fdr_richardson_lucy_f32(fdr_plan* plan, const float* img_host, int rows, int
 int fdr_richardson_lucy_f32_dev(fdr_plan* plan, const float* d_img, int rows, int cols, int stride, float* d_out, int out_stride,
                                 int iterations, int norm_area, void* stream);
 
+/* -- free-boundary, weighted Richardson-Lucy (Bertero & Boccacci 2005, "A simple method for the reduction of boundary effects in the
+ *    Richardson-Lucy approach to image deconvolution"; the WEIGHT argument of MATLAB's deconvlucy): RL for a picture that is a crop
+ *    of a larger scene.  The calls above take the plan for periodic (or the window for surrounded by zeros), so the light that the
+ *    blur carried in from outside the frame is taken for signal and the error grows inward with every iteration.  Here the estimate u
+ *    lives on the whole M x N plan, the data d (rows x cols at the top-left corner) constrain it inside the window only, and per-pixel
+ *    weights m in [0, 1] (rows x cols, row stride wstride; NULL = all ones; 0 = ignore this pixel: dead, saturated, cosmic ray)
+ *    say how much each datum counts.  H is the operator spectrum of fdr_set_operator_psf*, pad(x) is x on the window and 0 elsewhere:
+ *        fullblur(x) = IDFT2( H . DFT2(x) ),  fullblur^T(y) = IDFT2( conj(H) . DFT2(y) )      (whole plan; IDFT2 includes 1/(M N))
+ *        W = pad(m);  dw = pad(m . max(d, 0))
+ *        alpha = fullblur^T(W)                                 (the coverage: how much data sees each plan pixel)
+ *        wgt = alpha > sigma ? 1 / alpha : 0
+ *        u   = alpha > sigma ? sum(dw) / sum(W) : 0            (both sums in double, in a fixed order; 0 when sum(W) = 0)
+ *        n times:  c = window(fullblur(u));  r = c > FDR_RL_TAU ? dw / c : 0  (0 outside the window);  u = max(u . wgt . fullblur^T(pad(r)), 0)
+ *    The output is the top-left out_rows x out_cols of u, rows <= out_rows <= M, cols <= out_cols <= N (with M x N the caller gets
+ *    the extrapolated surround too), normalised over that output window by norm_area exactly as fdr_richardson_lucy_* defines
+ *    FDR_NORM_NONE / _CROPPED / _PADDED (PADDED counts one 0 when the output window is smaller than the plan).  n = 0 returns the
+ *    start.  sigma in (0, 1) cuts plan pixels that almost no datum sees (FDR_RL_SIGMA is the usual choice).  Wherever c > tau,
+ *    sum(alpha . u) = sum(dw) after every iteration: the free-boundary form of flux conservation.
+ *    With M >= rows + prows - 1 and N >= cols + pcols - 1 the two far borders of the window do not couple through the wrap of the
+ *    plan; this is not enforced: a full-plane window is legal, and then alpha = sum(psf) everywhere and an iteration is a plain RL
+ *    step.  A PSF placed top-left works without the c = 0 border rows of the calls above (u is non-zero outside the window); the
+ *    result is then shifted by the PSF's half-size, as for the Wiener calls.  Weights outside [0, 1] are not checked.
+ *    Plans and refusals as fdr_richardson_lucy_f32* (FDR_ERR_STATE without an operator PSF), and FDR_ERR_ARG for a null params
+ *    pointer, sigma outside (0, 1), a weights stride below cols, an output window outside [rows .. M] x [cols .. N] or with
+ *    out_stride < out_cols, or an output that overlaps the input or the weights; always before any device work, the plan usable
+ *    afterwards.  The first call on a plan allocates the workspace, kept until fdr_plan_destroy: three M x N float planes (u, wgt,
+ *    dw) and the partials of the two sums, 12 M N bytes; FDR_ERR_ALLOC, plan intact, if it cannot be had.  After it the _dev form
+ *    allocates nothing and is asynchronous on `stream`; the coverage is recomputed by every call (one adjoint blur: the weights may
+ *    have changed).  The host form copies in and out synchronously and counts as COMPUTE.  The Wiener / CLS filter, the operator
+ *    tables, the TV and motion workspaces and the results of every other call stay as they were.  An iteration moves about 68
+ *    bytes per plan pixel with a full-plane window.                                                    */
+#define FDR_RL_SIGMA 1e-2f /* the usual coverage threshold of the free-boundary calls */
+typedef struct fdr_rlfree_params {
+    int iterations; /* >= 0 */
+    float sigma;    /* coverage threshold, in (0, 1) */
+    int norm_area;  /* FDR_NORM_NONE / FDR_NORM_CROPPED / FDR_NORM_PADDED, over the output window */
+    int out_rows;   /* rows .. M */
+    int out_cols;   /* cols .. N */
+} fdr_rlfree_params;
+int fdr_richardson_lucy_free_f32(fdr_plan* plan, const float* img_host, int rows, int cols, int stride, const float* weights_host,
+                                 int wstride, float* out_host, int out_stride, const fdr_rlfree_params* params);
+int fdr_richardson_lucy_free_f32_dev(fdr_plan* plan, const float* d_img, int rows, int cols, int stride, const float* d_weights,
+                                     int wstride, float* d_out, int out_stride, const fdr_rlfree_params* params, void* stream);
+
 /* -- total-variation (TV) regularised deconvolution by ADMM / split Bregman (Rudin-Osher-Fatemi 1992; Wang-Yang-Yin-Zhang 2008
  *    "FTVd"; Goldstein-Osher 2009): the edge-preserving restoration beside the linear filters and RL.  It uses the operator PSF of
  *    fdr_set_operator_psf* (H = DFT2 of the PSF top-left in the plan, blur / blur^T as above) and lives on the whole periodic

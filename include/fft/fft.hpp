@@ -212,6 +212,37 @@ inline void richardsonLucy_RGB(std::vector<Mat>& channels, const Mat& psf, int i
 inline void richardsonLucy_RGB(std::vector<Mat>& channels, const Mat& psf, int iterations) {
     richardsonLucy_RGB(channels, psf, iterations, defaults());
 }
+// Free-boundary, weighted Richardson-Lucy (fdr_richardson_lucy_free_f32, include/fdr.h) of every channel, in place, for a picture
+// that is a crop of a larger scene: one cached FDR_MODE_FAST plan with room for the PSF's reach beyond the picture (the next powers
+// of two of rows + psf.rows - 1 and cols + psf.cols - 1, at least 8 x 32), the operator PSF set once, `weights` (CV_32F, the
+// picture's size, in [0, 1]; empty = all ones; 0 = ignore the pixel) shared by the channels, each channel normalised by o.norm_area.
+inline void richardsonLucyFree_RGB(std::vector<Mat>& channels, const Mat& psf, int iterations, const Mat& weights, const Options& o,
+                                   float sigma = FDR_RL_SIGMA) {
+    if (channels.empty()) return;
+    const int rows = channels[0].rows, cols = channels[0].cols;
+    if (!weights.empty() && (weights.rows != rows || weights.cols != cols || weights.type() != CV_32F)) {
+        std::cerr << "richardsonLucyFree_RGB: the weights must be CV_32F and have the picture's size\n";
+        exit(1);
+    }
+    bool created = false;
+    PlanCacheSettle settle_;
+    fdr_plan* plan = plan_cache().get(o.device, std::max(8, nextPowerOfTwo(rows + psf.rows - 1)), std::max(32, nextPowerOfTwo(cols + psf.cols - 1)),
+                                      FDR_MODE_FAST, &created);
+    Mat psfc = psf.isContinuous() ? psf : psf.clone();
+    FDR_CHECK(fdr_set_operator_psf(plan, psfc.ptr<float>(0), psf.rows, psf.cols, psf.cols));
+    Mat w = weights.empty() || weights.isContinuous() ? weights : weights.clone();
+    for (Mat& c : channels) {
+        Mat src = c.isContinuous() ? c : c.clone();
+        Mat out(c.rows, c.cols, CV_32F);
+        const fdr_rlfree_params prm = {iterations, sigma, o.norm_area, c.rows, c.cols};
+        FDR_CHECK(fdr_richardson_lucy_free_f32(plan, src.ptr<float>(0), c.rows, c.cols, c.cols, w.empty() ? nullptr : w.ptr<float>(0), cols,
+                                               out.ptr<float>(0), c.cols, &prm));
+        c = out;
+    }
+}
+inline void richardsonLucyFree_RGB(std::vector<Mat>& channels, const Mat& psf, int iterations, const Mat& weights = Mat()) {
+    richardsonLucyFree_RGB(channels, psf, iterations, weights, defaults());
+}
 // Total-variation deconvolution (fdr_tv_deconv_f32, include/fdr.h) of every channel, in place: the plan and operator PSF of
 // richardsonLucy_RGB, `iterations` ADMM steps of mu / 2 ||blur(x) - d||^2 + TV(x) (isotropic) with penalty rho, the output clamped
 // at 0 and normalised by o.norm_area.  o.mode and o.cls_gamma do not apply.

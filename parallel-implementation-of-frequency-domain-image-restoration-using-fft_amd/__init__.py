@@ -30,6 +30,7 @@ FLAG_MIXED_RADIX = 2048
 NORM_PADDED = 1
 NORM_CROPPED = 0
 NORM_NONE = 2  # Richardson-Lucy only: the raw estimate
+RL_SIGMA = 1e-2  # FDR_RL_SIGMA: the usual coverage threshold of free-boundary Richardson-Lucy
 MAX_PASSES = 16
 OPT_TWO_SWEEP_NORM = 2
 OPT_BATCH_GRAPH = 3
@@ -63,6 +64,12 @@ class TvParams(ctypes.Structure):
     """fdr_tv_params of include/fdr.h"""
     _fields_ = [("mu", ctypes.c_float), ("rho", ctypes.c_float), ("iterations", ctypes.c_int), ("anisotropic", ctypes.c_int),
                 ("nonneg", ctypes.c_int), ("norm_area", ctypes.c_int)]
+
+
+class RlFreeParams(ctypes.Structure):
+    """fdr_rlfree_params of include/fdr.h"""
+    _fields_ = [("iterations", ctypes.c_int), ("sigma", ctypes.c_float), ("norm_area", ctypes.c_int), ("out_rows", ctypes.c_int),
+                ("out_cols", ctypes.c_int)]
 
 
 class MotionEstimateC(ctypes.Structure):
@@ -174,6 +181,8 @@ def _load():
     L.fdr_blur_f32_dev.argtypes = [vp, vp, ci, ci, ci, vp, ci, ci, vp]
     L.fdr_richardson_lucy_f32.argtypes = [vp, vp, ci, ci, ci, vp, ci, ci, ci]
     L.fdr_richardson_lucy_f32_dev.argtypes = [vp, vp, ci, ci, ci, vp, ci, ci, ci, vp]
+    L.fdr_richardson_lucy_free_f32.argtypes = [vp, vp, ci, ci, ci, vp, ci, vp, ci, ctypes.POINTER(RlFreeParams)]
+    L.fdr_richardson_lucy_free_f32_dev.argtypes = [vp, vp, ci, ci, ci, vp, ci, vp, ci, ctypes.POINTER(RlFreeParams), vp]
     L.fdr_tv_deconv_f32.argtypes = [vp, vp, ci, ci, ci, vp, ci, ctypes.POINTER(TvParams)]
     L.fdr_tv_deconv_f32_dev.argtypes = [vp, vp, ci, ci, ci, vp, ci, ctypes.POINTER(TvParams), vp]
     L.fdr_cepstrum_f32.argtypes = [vp, vp, ci, ci, ci, vp]
@@ -192,6 +201,7 @@ def _load():
                  "fdr_plan_filter_bytes", "fdr_plan_export_filter_dev", "fdr_plan_import_filter_dev",
                  "fdr_set_psf_cls", "fdr_set_psf_cls_dev", "fdr_set_psf_motion_cls", "fdr_set_operator_psf", "fdr_set_operator_psf_dev",
                  "fdr_set_operator_psf_motion", "fdr_blur_f32", "fdr_blur_f32_dev", "fdr_richardson_lucy_f32", "fdr_richardson_lucy_f32_dev",
+                 "fdr_richardson_lucy_free_f32", "fdr_richardson_lucy_free_f32_dev",
                  "fdr_tv_deconv_f32", "fdr_tv_deconv_f32_dev", "fdr_cepstrum_f32", "fdr_cepstrum_f32_dev", "fdr_estimate_motion_f32", "fdr_estimate_motion_f32_dev"):
         getattr(L, name).restype = ci
     return L
@@ -212,6 +222,7 @@ EXPORTED_SYMBOLS = (
     "fdr_plan_filter_bytes", "fdr_plan_export_filter_dev", "fdr_plan_import_filter_dev",
     "fdr_set_psf_cls", "fdr_set_psf_cls_dev", "fdr_set_psf_motion_cls", "fdr_set_operator_psf", "fdr_set_operator_psf_dev",
     "fdr_set_operator_psf_motion", "fdr_blur_f32", "fdr_blur_f32_dev", "fdr_richardson_lucy_f32", "fdr_richardson_lucy_f32_dev",
+    "fdr_richardson_lucy_free_f32", "fdr_richardson_lucy_free_f32_dev",
     "fdr_tv_deconv_f32", "fdr_tv_deconv_f32_dev", "fdr_cepstrum_f32", "fdr_cepstrum_f32_dev", "fdr_estimate_motion_f32", "fdr_estimate_motion_f32_dev")
 
 
@@ -462,6 +473,34 @@ class Plan:
         _check(lib.fdr_richardson_lucy_f32_dev(self._h, ctypes.c_void_p(int(d_img)), rows, cols, stride, ctypes.c_void_p(int(d_out)),
                                                out_stride, int(iterations), int(norm_area), _stream(stream)))
 
+    # free-boundary, weighted Richardson-Lucy (include/fdr.h); uses the operator PSF
+    def richardson_lucy_free(self, img, iterations, weights=None, sigma=RL_SIGMA, norm_area=NORM_NONE, full_plane=False):
+        """`iterations` free-boundary Richardson-Lucy steps on the window img (host arrays): the estimate lives on the whole plan,
+        the data constrain it inside the window only.  weights (img.shape, in [0, 1]; None = all ones) say how much each pixel
+        counts: 0 excludes it.  Returns the window, or with full_plane the whole M x N estimate; normalised over what is returned."""
+        img = np.ascontiguousarray(img, dtype=np.float32)
+        rows, cols = img.shape
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float32)
+            if w.shape != img.shape:
+                raise ValueError("weights must have the shape of img")
+        orows, ocols = (self.M, self.N) if full_plane else (rows, cols)
+        out = np.empty((orows, ocols), dtype=np.float32)
+        prm = RlFreeParams(int(iterations), float(sigma), int(norm_area), orows, ocols)
+        _check(lib.fdr_richardson_lucy_free_f32(self._h, _ptr(img), rows, cols, cols, _ptr(w) if w is not None else None, cols, _ptr(out),
+                                                ocols, ctypes.byref(prm)))
+        return out
+
+    def richardson_lucy_free_dev(self, d_img, rows, cols, stride, d_out, out_stride, iterations, d_weights=None, wstride=0, sigma=RL_SIGMA,
+                                 norm_area=NORM_NONE, out_rows=None, out_cols=None, stream=None):
+        """the same on device pointers; out_rows x out_cols (default rows x cols, up to M x N) is the output window.  Asynchronous."""
+        prm = RlFreeParams(int(iterations), float(sigma), int(norm_area), int(rows if out_rows is None else out_rows),
+                           int(cols if out_cols is None else out_cols))
+        _check(lib.fdr_richardson_lucy_free_f32_dev(self._h, ctypes.c_void_p(int(d_img)), rows, cols, stride,
+                                                    ctypes.c_void_p(int(d_weights)) if d_weights else None, int(wstride),
+                                                    ctypes.c_void_p(int(d_out)), out_stride, ctypes.byref(prm), _stream(stream)))
+
     # total-variation deconvolution by ADMM (include/fdr.h); uses the operator PSF
     def tv_deconv(self, img, mu, rho=2.0, iterations=50, anisotropic=False, nonneg=False, norm_area=NORM_NONE):
         """`iterations` ADMM steps of mu / 2 ||blur(x) - img||^2 + TV(x) on the window img (host arrays), normalised by norm_area."""
@@ -638,6 +677,24 @@ def richardsonLucy_myfft(img, psf, iterations, device=0, norm_area=NORM_NONE):
     with Plan(M, N, MODE_FAST, device) as p:
         p.set_operator_psf(psf)
         return p.richardson_lucy(img, iterations, norm_area)
+
+
+def _rlfree_plan_size(rows, cols, prows, pcols):
+    """the plan richardsonLucyFree_myfft uses: the next powers of two of rows + prows - 1 and cols + pcols - 1 (the far borders of the
+    window then do not couple through the wrap), at least 8 rows and 32 columns"""
+    return max(8, nextPowerOfTwo(rows + prows - 1)), max(32, nextPowerOfTwo(cols + pcols - 1))
+
+
+def richardsonLucyFree_myfft(img, psf, iterations, weights=None, sigma=RL_SIGMA, device=0, norm_area=NORM_NONE, full_plane=False):
+    """Free-boundary, weighted Richardson-Lucy of one channel that is a crop of a larger scene: a plan with room for the PSF's
+    reach beyond the window, `iterations` steps on the device, the window (or with full_plane the whole plan) back.  psf lies
+    top-left in the plan, as for the Wiener calls; weights as Plan.richardson_lucy_free."""
+    img = np.asarray(img, dtype=np.float32)
+    psf = np.asarray(psf, dtype=np.float32)
+    M, N = _rlfree_plan_size(img.shape[0], img.shape[1], psf.shape[0], psf.shape[1])
+    with Plan(M, N, MODE_FAST, device) as p:
+        p.set_operator_psf(psf)
+        return p.richardson_lucy_free(img, iterations, weights, sigma, norm_area, full_plane)
 
 
 def tvDeblur_myfft(img, psf, mu, rho=2.0, iterations=50, anisotropic=False, nonneg=False, device=0, norm_area=NORM_NONE):

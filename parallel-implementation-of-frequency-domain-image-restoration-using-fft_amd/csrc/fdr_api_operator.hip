@@ -105,7 +105,7 @@ int normalize_window(fdr_plan* p, const char* fn, const char* name, const float*
 }
 
 // pass B' on one of the operator tables
-static int op_cols(fdr_plan* p, bool adjoint, hipStream_t s) {
+int op_cols(fdr_plan* p, bool adjoint, hipStream_t s) {
     return op_cols_table(p, adjoint ? p->op_c : p->op_h, adjoint ? kPassOpColsConj : kPassOpColsH, s);
 }
 

@@ -1,0 +1,143 @@
+// fdr_api_rlfree.hip -- free-boundary, weighted Richardson-Lucy (fdr_richardson_lucy_free_f32*; kernels in fdr_rlfree.hip and the
+// weighted update kind of fdr_panel.hip): the workspace, the checks, the driver and the two entry points.  Every transform is an
+// operator pass of fdr_api_operator.hip: the estimate goes through pass A as a dense M x N plane, the ratio through the window.
+#include "fdr_host.hpp"
+
+#include <cstdint>
+
+using namespace fdr;
+
+namespace {
+
+// names are static strings compared by pointer in PassTimer::pass_id
+const char* const kPassRfSetup = "RLF setup: dw, W, sums";
+const char* const kPassRfStart = "RLF start: wgt = 1/alpha, u";
+const char* const kPassRfRatio = "C op rows: IFFT+RL ratio (free)";
+const char* const kPassRfUpdate = "C op rows: IFFT+RL update (weighted)";
+const char* const kPassRfCrop = "RLF out: crop";
+const char* const kPassRfNorm = "E RLF minmax+normalize";
+
+// the first free-boundary call of a plan: u, wgt and dw (M x N floats each) and the double partials
+int ensure_rlfree_workspace(fdr_plan* p, const char* fn) {
+    if (p->rf_block) return FDR_OK;
+    const size_t P = (size_t)p->M * p->N;
+    const size_t n_part = 2 * (size_t)rlfree_partials(p->M, p->N) + 2;
+    char* blk = nullptr;
+    if (hipMalloc((void**)&blk, 3 * P * sizeof(float) + n_part * sizeof(double)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(FDR_ERR_ALLOC, std::string(fn) + ": hipMalloc of the free-boundary workspace failed");
+    }
+    float* planes = reinterpret_cast<float*>(blk);
+    p->rf_block = blk;
+    p->rf_u = planes;
+    p->rf_wgt = planes + P;
+    p->rf_dw = planes + 2 * P;
+    p->rf_part = reinterpret_cast<double*>(planes + 3 * P);  // 12 P bytes in: a multiple of 8 (P >= 256)
+    return FDR_OK;
+}
+
+bool spans_overlap(const float* a, int a_stride, int a_rows, int a_cols, const float* b, int b_stride, int b_rows, int b_cols) {
+    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + ((size_t)(a_rows - 1) * a_stride + a_cols) * sizeof(float);
+    const uintptr_t b0 = (uintptr_t)b, b1 = b0 + ((size_t)(b_rows - 1) * b_stride + b_cols) * sizeof(float);
+    return a0 < b1 && b0 < a1;
+}
+
+// everything a free-boundary call refuses, before any device work: what the Richardson-Lucy calls refuse, and sigma, the output
+// window and an output that overlaps the weights
+int rlfree_check(const fdr_plan* p, const char* fn, const float* img, int rows, int cols, int stride, const float* weights, int wstride,
+                 const float* out, int out_stride, const fdr_rlfree_params* prm) {
+    if (!prm) return null_arg(fn);
+    const int rc = check_window(p, fn, NEED_OPERATOR_PSF, rows, cols, stride, out_stride);
+    if (rc != FDR_OK) return rc;
+    if (weights && wstride < cols) return fail(FDR_ERR_ARG, std::string(fn) + ": the weights' stride must be >= cols");
+    if (prm->iterations < 0) return fail(FDR_ERR_ARG, std::string(fn) + ": iterations < 0");
+    if (!(prm->sigma > 0.f && prm->sigma < 1.f)) return fail(FDR_ERR_ARG, std::string(fn) + ": sigma must lie in (0, 1)");
+    if (prm->norm_area != FDR_NORM_NONE && prm->norm_area != FDR_NORM_CROPPED && prm->norm_area != FDR_NORM_PADDED)
+        return fail(FDR_ERR_ARG, std::string(fn) + ": unknown norm_area");
+    if (prm->out_rows < rows || prm->out_rows > p->M || prm->out_cols < cols || prm->out_cols > p->N || out_stride < prm->out_cols)
+        return fail(FDR_ERR_ARG, std::string(fn) + ": the output window must lie in [rows .. M] x [cols .. N] and have a stride >= out_cols");
+    if (spans_overlap(img, stride, rows, cols, out, out_stride, prm->out_rows, prm->out_cols))
+        return fail(FDR_ERR_ARG, std::string(fn) + ": the output overlaps the input");
+    if (weights && spans_overlap(weights, wstride, rows, cols, out, out_stride, prm->out_rows, prm->out_cols))
+        return fail(FDR_ERR_ARG, std::string(fn) + ": the output overlaps the weights");
+    return FDR_OK;
+}
+
+// u and wgt are dense M x N planes of the workspace, dw and r (the plan's raw plane) dense rows x cols.  W = pad(m) lies in u's
+// plane until alpha has been transformed out of it; d_w may be that plane itself (the host form stages the weights there).
+int rlfree_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, int cols, int stride, const float* d_w, int wstride,
+                    float* d_out, int out_stride, const fdr_rlfree_params& prm, hipStream_t s) {
+    const int M = p->M, N = p->N;
+    float *u = p->rf_u, *wgt = p->rf_wgt, *dw = p->rf_dw, *r = p->raw;
+    const int n_part = rlfree_partials(rows, cols);
+    {
+        ScopedPass t(p, s, kPassRfSetup);
+        FDR_HIP(launch_rlfree_setup(d_img, stride, d_w, wstride, rows, cols, dw, u, p->rf_part, s));
+    }
+    int rc = blur_window_dev(p, u, rows, cols, cols, wgt, N, M, N, 1, s);  // alpha = fullblur^T(W) over the whole plan
+    if (rc != FDR_OK) return rc;
+    {
+        ScopedPass t(p, s, kPassRfStart);
+        FDR_HIP(launch_rlfree_start(wgt, u, (size_t)M * N, prm.sigma, p->rf_part + 2 * (size_t)n_part, s));
+    }
+    for (int it = 0; it < prm.iterations && rc == FDR_OK; ++it) {
+        rc = op_rows_fwd(p, u, M, N, N, s);                                                             // c = fullblur(u) ...
+        if (rc == FDR_OK) rc = op_cols(p, false, s);
+        if (rc == FDR_OK) rc = op_rows_inv(p, ROW_OUT_RL_RATIO, kPassRfRatio, dw, cols, r, cols, rows, cols, s);  // ... r = dw / c
+        if (rc == FDR_OK) rc = op_rows_fwd(p, r, rows, cols, cols, s);                                  // g = fullblur^T(pad(r)) ...
+        if (rc == FDR_OK) rc = op_cols(p, true, s);
+        if (rc == FDR_OK) {                                                                             // ... u = max(u wgt g, 0)
+            ScopedPass t(p, s, kPassRfUpdate);
+            RowArgs a{};
+            a.src_c = p->work; a.M = M; a.pstride = p->pstride; a.half = 1; a.num_cu = p->num_cu;
+            a.src_real = u; a.src_real2 = wgt; a.src_stride = N;
+            a.out = u; a.out_rows = M; a.out_cols = N; a.out_stride = N;
+            FDR_HIP(launch_rows4(p->logN, ROW_IN_COMPLEX, ROW_OUT_RL_UPDATE_W, a, p->tw_row_f, s));
+        }
+    }
+    if (rc != FDR_OK) return rc;
+    if (prm.norm_area == FDR_NORM_NONE) {
+        ScopedPass t(p, s, kPassRfCrop);
+        FDR_HIP(launch_rlfree_crop(u, N, d_out, prm.out_rows, prm.out_cols, out_stride, s));
+        return FDR_OK;
+    }
+    return normalize_window(p, fn, kPassRfNorm, u, N, prm.out_rows, prm.out_cols, prm.norm_area, d_out, out_stride, s);
+}
+
+}  // namespace
+
+extern "C" {
+
+int fdr_richardson_lucy_free_f32_dev(fdr_plan* p, const float* d_img, int rows, int cols, int stride, const float* d_weights, int wstride,
+                                     float* d_out, int out_stride, const fdr_rlfree_params* params, void* stream) {
+    const char* fn = "fdr_richardson_lucy_free_f32_dev";
+    if (!p || !d_img || !d_out) return null_arg(fn);
+    int rc = rlfree_check(p, fn, d_img, rows, cols, stride, d_weights, wstride, d_out, out_stride, params);
+    if (rc != FDR_OK) return rc;
+    FDR_HIP(hipSetDevice(p->device));
+    rc = ensure_rlfree_workspace(p, fn);
+    if (rc != FDR_OK) return rc;
+    return rlfree_dev_impl(p, fn, d_img, rows, cols, stride, d_weights, wstride, d_out, out_stride, *params, (hipStream_t)stream);
+}
+
+int fdr_richardson_lucy_free_f32(fdr_plan* p, const float* img_host, int rows, int cols, int stride, const float* weights_host, int wstride,
+                                 float* out_host, int out_stride, const fdr_rlfree_params* params) {
+    const char* fn = "fdr_richardson_lucy_free_f32";
+    if (!p || !img_host || !out_host) return null_arg(fn);
+    int rc = rlfree_check(p, fn, img_host, rows, cols, stride, weights_host, wstride, out_host, out_stride, params);
+    if (rc != FDR_OK) return rc;
+    FDR_HIP(hipSetDevice(p->device));
+    rc = ensure_rlfree_workspace(p, fn);
+    if (rc != FDR_OK) return rc;
+    if (weights_host)  // staged dense into u's plane, where the setup pass leaves W anyway
+        FDR_HIP(hipMemcpy2D(p->rf_u, (size_t)cols * sizeof(float), weights_host, (size_t)wstride * sizeof(float), (size_t)cols * sizeof(float),
+                            (size_t)rows, hipMemcpyHostToDevice));
+    const fdr_rlfree_params prm = *params;
+    return host_image_call(p, fn, img_host, rows, cols, stride, out_host, prm.out_rows, prm.out_cols, out_stride,
+                           [&](const float* d_in, float* d_out) {
+                               return rlfree_dev_impl(p, fn, d_in, rows, cols, cols, weights_host ? p->rf_u : nullptr, cols, d_out, prm.out_cols,
+                                                      prm, nullptr);
+                           });
+}
+
+}  // extern "C"

@@ -120,6 +120,12 @@ struct fdr_plan {
     size_t mo_table_cap = 0, mo_trig_cap = 0;  // elements
     std::vector<float> mo_table_host;
     std::vector<double> mo_trig_host;
+    // free-boundary Richardson-Lucy (fdr_richardson_lucy_free_f32*): made by the first such call, kept until fdr_plan_destroy -- one
+    // allocation holding three M x N real planes (the estimate u, wgt = 1 / coverage, dw = weights . max(d, 0) on the window) and the
+    // 2 rlfree_partials(M, N) + 2 double partials of the two sums (r lives in `raw`)
+    void* rf_block = nullptr;
+    float *rf_u = nullptr, *rf_wgt = nullptr, *rf_dw = nullptr;
+    double* rf_part = nullptr;
     fdr::PassTimer timer;
     // the reference Profiler's buckets (fdr_plan_phase_times): resolved sums + event pairs not read back yet
     struct PhaseRec { hipEvent_t a, b; int phase; };
@@ -251,6 +257,8 @@ int op_cols_table(fdr_plan* p, const float2* table, const char* name, hipStream_
 // pass C with an operator kind: the window rows x cols of the inverse transform through the kind's epilogue into `out`
 int op_rows_inv(fdr_plan* p, RowOut kind, const char* name, const float* src, int src_stride, float* out, int out_stride, int rows, int cols,
                 hipStream_t s);
+// pass B' on H / (M N), or with `adjoint` on conj(H) / (M N)
+int op_cols(fdr_plan* p, bool adjoint, hipStream_t s);
 // blur (adjoint != 0: blur^T) of the window rows x cols of d_img; the window out_rows x out_cols of the result into d_out
 int blur_window_dev(fdr_plan* p, const float* d_img, int rows, int cols, int stride, float* d_out, int out_stride, int out_rows, int out_cols,
                     int adjoint, hipStream_t s);

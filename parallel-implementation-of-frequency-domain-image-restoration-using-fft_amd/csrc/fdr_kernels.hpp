@@ -17,7 +17,10 @@ enum RowOut {
     // window out_rows x out_cols on store (row stride out_stride), no min/max
     ROW_OUT_BLUR = 4,         // the value to `out`
     ROW_OUT_RL_RATIO = 5,     // r = c > kRlTau ? max(d, 0) / c : 0 to `out`; d read from src_real (row stride src_stride)
-    ROW_OUT_RL_UPDATE = 6     // max(u g, 0) to `out`; u read from src_real (row stride src_stride; may be `out` itself)
+    ROW_OUT_RL_UPDATE = 6,    // max(u g, 0) to `out`; u read from src_real (row stride src_stride; may be `out` itself)
+    // free-boundary Richardson-Lucy (fdr_rlfree.hip): max(u wgt g, 0) to `out`; u from src_real as ROW_OUT_RL_UPDATE, wgt from
+    // src_real2 (same row stride)
+    ROW_OUT_RL_UPDATE_W = 7
 };
 // the guard of the Richardson-Lucy ratio (FDR_RL_TAU of fdr.h): a blurred estimate at or below it gives r = 0
 constexpr float kRlTau = 1e-7f;
@@ -72,7 +75,11 @@ struct RowArgs {
     const float2* src_c;  // ROW_IN_COMPLEX: M x L
     // output
     float2* dst_c;    // ROW_OUT_COMPLEX: M x L
-    float* dst_real;  // ROW_OUT_REAL_MINMAX: M x L real plane
+    union {
+        float* dst_real;         // ROW_OUT_REAL_MINMAX: M x L real plane
+        const float* src_real2;  // ROW_OUT_RL_UPDATE_W: the second real source (row stride src_stride); shares the slot of dst_real,
+                                 // which that kind does not use, so the argument block of every other kernel keeps its layout
+    };
     float2* mm_part;  // one (min, max) partial per workgroup
     int mm_rows, mm_cols;
     float* out;       // ROW_OUT_NORMALIZED: out_rows x out_cols result, row stride out_stride; mm_part holds n_part partials
@@ -132,6 +139,16 @@ hipError_t launch_cols_panel_cls(int logm, const ColArgs& a, const double* lap, 
 hipError_t launch_cols_panel_operator(int logm, const ColArgs& a, float2* conj_out, const float2* tw_fwd, hipStream_t s);
 // (fdr_rl.hip) u = max(d, 0) on a rows x cols window (row strides `stride` / `ustride`)
 hipError_t launch_rl_init(const float* d, int rows, int cols, int stride, float* u, int ustride, hipStream_t s);
+// (fdr_rlfree.hip) free-boundary, weighted Richardson-Lucy.  setup: dw = m max(d, 0) and W = m on the rows x cols window (m = 1 for a
+// null pointer; both dense, row stride cols; W may be m itself), their sums in double as rlfree_partials(rows, cols) per-workgroup
+// partials each, folded in a fixed order into part[2 n] = sum dw, part[2 n + 1] = sum W (part holds 2 n + 2 doubles).  start: the
+// M x N plane `wgt` holds alpha on entry; wgt = alpha > sigma ? 1 / alpha : 0, u = alpha > sigma ? sum dw / sum W : 0 (0 for sum W = 0).
+// crop: the window rows x cols of u (row stride ustride) to `out`.
+int rlfree_partials(int rows, int cols);
+hipError_t launch_rlfree_setup(const float* d, int stride, const float* m, int mstride, int rows, int cols, float* dw, float* W, double* part,
+                               hipStream_t s);
+hipError_t launch_rlfree_start(float* wgt, float* u, size_t count, float sigma, const double* sums, hipStream_t s);
+hipError_t launch_rlfree_crop(const float* u, int ustride, float* out, int rows, int cols, int out_stride, hipStream_t s);
 // (fdr_tv.hip) total-variation deconvolution.  table: T = (1 / (M N)) / (mu |H|^2 + rho L) from op_h = H / (M N) (the operator table
 // of launch_cols_panel_operator) and the Laplacian table `lap` of launch_cols_panel_cls, in the layout pass B' reads its filter
 // from.  init: x = pad(d) over the M x N plan (row stride N), wx = wy = 0.  spatial: one ADMM half-step on full M x N planes --

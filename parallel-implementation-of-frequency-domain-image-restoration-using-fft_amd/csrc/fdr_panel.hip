@@ -731,11 +731,13 @@ __device__ __forceinline__ void rows4_inv_epilogue(const RowArgs& a, const int r
 //   OUT 3 (blur)      : v
 //   OUT 4 (RL ratio)  : v > kRlTau ? max(d, 0) / v : 0, d = *src (the input image)
 //   OUT 5 (RL update) : max(u v, 0), u = *src (the estimate; src may be the output itself: read and written by the same lane)
+//   OUT 6 (weighted RL update, free boundary) : max(u w v, 0), u = *src as OUT 5, w = *src2 = src_real2 + r src_stride + n
 template <int OUT>
-__device__ __forceinline__ float rows4_rl_value(const float v, const float* src) {
+__device__ __forceinline__ float rows4_rl_value(const float v, const float* src, const float* src2 = nullptr) {
     if constexpr (OUT == 3) return v;
     else if constexpr (OUT == 4) return v > kRlTau ? fmaxf(*src, 0.f) / v : 0.f;
-    else return fmaxf(*src * v, 0.f);
+    else if constexpr (OUT == 5) return fmaxf(*src * v, 0.f);
+    else return fmaxf(*src * *src2 * v, 0.f);
 }
 // rows4_inv_epilogue for those kinds: cropped on store as OUT 2, no min/max
 template <class Core, int OUT, int V>
@@ -747,6 +749,7 @@ __device__ __forceinline__ void rows4_rl_epilogue(const RowArgs& a, const int r0
         if (r < a.out_rows) {
             float* o = a.out + (size_t)r * a.out_stride + tq;
             const float* in = OUT == 3 ? nullptr : a.src_real + (size_t)r * a.src_stride + tq;
+            const float* in2 = OUT == 6 ? a.src_real2 + (size_t)r * a.src_stride + tq : nullptr;
 #pragma unroll
             for (int u = 0; u < Core::NUL; ++u)
 #pragma unroll
@@ -754,7 +757,10 @@ __device__ __forceinline__ void rows4_rl_epilogue(const RowArgs& a, const int r0
                     const int s = u * Core::RHOL + q;
                     const int c = u * T + (q << Core::LOGOUT);
                     const float v = b == 0 ? z[0][s].x : b == 1 ? z[0][s].y : b == 2 ? z[1][s].x : z[1][s].y;
-                    if (tq + c < a.out_cols) o[c] = rows4_rl_value<OUT>(v, in + c);
+                    if (tq + c < a.out_cols) {
+                        if constexpr (OUT == 6) o[c] = rows4_rl_value<OUT>(v, in + c, in2 + c);
+                        else o[c] = rows4_rl_value<OUT>(v, in + c);
+                    }
                 }
         }
     }
@@ -904,7 +910,7 @@ __global__ __launch_bounds__(RowsSplitGeom<LOGL>::THREADS) void fft_rows4_fwd_sp
     }
 }
 
-// OUT as in rows4_inv_epilogue: 0 raw real plane + min/max, 1 min/max only, 2 normalised and cropped; 3..5 the operator
+// OUT as in rows4_inv_epilogue: 0 raw real plane + min/max, 1 min/max only, 2 normalised and cropped; 3..6 the operator
 // kinds of rows4_rl_value
 template <int LOGL, int OUT>
 __global__ __launch_bounds__((RowsSplitGeom<LOGL, true>::THREADS)) void fft_rows4_inv_split_kernel(const RowArgs a, const float2* __restrict__ tw_fwd) {
@@ -985,10 +991,12 @@ __global__ __launch_bounds__((RowsSplitGeom<LOGL, true>::THREADS)) void fft_rows
                 if (n < a.out_cols) {
                     if (ra < a.out_rows)
                         a.out[(size_t)ra * a.out_stride + n] =
-                            rows4_rl_value<OUT>(va, OUT == 3 ? nullptr : a.src_real + (size_t)ra * a.src_stride + n);
+                            rows4_rl_value<OUT>(va, OUT == 3 ? nullptr : a.src_real + (size_t)ra * a.src_stride + n,
+                                                OUT == 6 ? a.src_real2 + (size_t)ra * a.src_stride + n : nullptr);
                     if (rb < a.out_rows)
                         a.out[(size_t)rb * a.out_stride + n] =
-                            rows4_rl_value<OUT>(vb, OUT == 3 ? nullptr : a.src_real + (size_t)rb * a.src_stride + n);
+                            rows4_rl_value<OUT>(vb, OUT == 3 ? nullptr : a.src_real + (size_t)rb * a.src_stride + n,
+                                                OUT == 6 ? a.src_real2 + (size_t)rb * a.src_stride + n : nullptr);
                 }
             } else if constexpr (OUT == 2) {
                 const float pa = va * fscale, pb = vb * fscale;
@@ -1040,6 +1048,8 @@ static hipError_t launch_rows4_t(RowIn in, RowOut out, const RowArgs& a, const f
                 hipLaunchKernelGGL((fft_rows4_inv_split_kernel<LOGL, 4>), sgrid, siblock, 0, s, a, tw);
             } else if (in == ROW_IN_COMPLEX && out == ROW_OUT_RL_UPDATE) {
                 hipLaunchKernelGGL((fft_rows4_inv_split_kernel<LOGL, 5>), sgrid, siblock, 0, s, a, tw);
+            } else if (in == ROW_IN_COMPLEX && out == ROW_OUT_RL_UPDATE_W) {
+                hipLaunchKernelGGL((fft_rows4_inv_split_kernel<LOGL, 6>), sgrid, siblock, 0, s, a, tw);
             } else {
                 return hipErrorInvalidValue;
             }
@@ -1076,13 +1086,15 @@ static hipError_t launch_rows4_t(RowIn in, RowOut out, const RowArgs& a, const f
     } else if (in == ROW_IN_COMPLEX && out == ROW_OUT_NORMALIZED) {
         if (!a.half) return hipErrorInvalidValue;
         return launch_rows4_inv_t<LOGL, 2>(a, tw, s, igrid, iblock);
-    } else if (in == ROW_IN_COMPLEX && (out == ROW_OUT_BLUR || out == ROW_OUT_RL_RATIO || out == ROW_OUT_RL_UPDATE)) {
+    } else if (in == ROW_IN_COMPLEX &&
+               (out == ROW_OUT_BLUR || out == ROW_OUT_RL_RATIO || out == ROW_OUT_RL_UPDATE || out == ROW_OUT_RL_UPDATE_W)) {
         // the operator kinds: half spectrum, rows of 32 points and more, one image per launch
         if constexpr (LOGL >= 5) {
             if (!a.half || a.batch.nimg > 1) return hipErrorInvalidValue;
             if (out == ROW_OUT_BLUR) return launch_rows4_inv_t<LOGL, 3>(a, tw, s, igrid, iblock);
             if (out == ROW_OUT_RL_RATIO) return launch_rows4_inv_t<LOGL, 4>(a, tw, s, igrid, iblock);
-            return launch_rows4_inv_t<LOGL, 5>(a, tw, s, igrid, iblock);
+            if (out == ROW_OUT_RL_UPDATE) return launch_rows4_inv_t<LOGL, 5>(a, tw, s, igrid, iblock);
+            return launch_rows4_inv_t<LOGL, 6>(a, tw, s, igrid, iblock);
         }
         return hipErrorInvalidValue;
     } else {

@@ -1,5 +1,5 @@
 // gpu.cpp -- ./gpu <img-path> <psf-length> <psf-angle> [--out file] [--mode fast|parity] [--norm padded|cropped] [--host-epilogue]
-//           [--cls gamma] [--rl iterations] [--tv mu [--tv-iters n] [--tv-rho r]]
+//           [--cls gamma] [--rl iterations [--free-boundary [--mask mask.png]]] [--tv mu [--tv-iters n] [--tv-rho r]]
 // `auto auto` for length and angle: the blur is estimated first (fft_gpu::estimateMotionBlur on the per-pixel mean of B, G and R),
 // printed as `estimate: length L angle A confidence C`, and the run then goes on exactly as `./gpu <img-path> L A` would.
 // Drop-in counterpart of the reference's gpu.cpp (argument meaning, printed lines and exit codes as at
@@ -67,6 +67,8 @@ int main(int argc, char** argv) {
     bool verify = false;         // --verify: areChannelsEqual(parity-mode result, this run's result)
     bool host_epilogue = false;  // Lab white balance on the host (the A/B reference of the device epilogue)
     int rl_iterations = -1;      // --rl n: a timed Richardson-Lucy leg after the naive one; its planes are the written result
+    bool free_boundary = false;  // --free-boundary: the --rl leg is fft_gpu::richardsonLucyFree_RGB (the picture is a crop of a larger scene)
+    string mask_path;            // --mask file: pixels that are 0 in it (any channel counts) get weight 0, the others weight 1
     float tv_mu = -1.f, tv_rho = 2.0f;  // --tv mu: a timed total-variation leg (fft_gpu::tvDeblur_RGB); its planes are the written result
     int tv_iterations = 50;
     bool tv_opts = false;
@@ -87,6 +89,8 @@ int main(int argc, char** argv) {
         else if (a == "--cls" && i + 1 < argc) { cls = true; fft_gpu::set_cls_gamma(strtof(argv[++i], nullptr)); }
         // Richardson-Lucy (fft_gpu::richardsonLucy_RGB, fast mode): n >= 0 iterations
         else if (a == "--rl" && i + 1 < argc) rl_iterations = atoi(argv[++i]);
+        else if (a == "--free-boundary") free_boundary = true;
+        else if (a == "--mask" && i + 1 < argc) mask_path = argv[++i];
         // total-variation deconvolution (fft_gpu::tvDeblur_RGB, fast mode): mu > 0, n >= 0 iterations, penalty rho > 0
         else if (a == "--tv" && i + 1 < argc) tv_mu = strtof(argv[++i], nullptr);
         else if (a == "--tv-iters" && i + 1 < argc) { tv_opts = true; tv_iterations = atoi(argv[++i]); }
@@ -95,6 +99,11 @@ int main(int argc, char** argv) {
     }
     // the RL leg replaces the result the other options shape (CLS filter, parity check, parity-mode restoration)
     if (rl_iterations >= 0 && (cls || verify || parity)) { cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle>\n"; return -1; }
+    // --free-boundary belongs to --rl, --mask to --free-boundary
+    if ((free_boundary && rl_iterations < 0) || (!mask_path.empty() && !free_boundary)) {
+        cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle>\n";
+        return -1;
+    }
     // so does the TV leg; --tv-iters / --tv-rho belong to --tv, and one run has one iterative leg
     const bool tv = tv_mu > 0.f;
     if ((tv && (cls || verify || parity || rl_iterations >= 0 || tv_iterations < 0 || !(tv_rho > 0.f))) || (!tv && (tv_opts || tv_mu != -1.f))) {
@@ -122,6 +131,20 @@ int main(int argc, char** argv) {
             cerr << "[Warning] low confidence (" << est.confidence << " < 10): the picture shows no clear motion blur; the estimate may be wrong\n";
         psf_length = est.length;
         psf_angle = est.angle_deg;
+    }
+
+    Mat weights;  // --mask: 0 where the mask is 0 in every channel, else 1
+    if (!mask_path.empty()) {
+        const Mat mask = fdr_io::imread(mask_path);
+        if (mask.empty() || mask.rows != img.rows || mask.cols != img.cols) { cout << "Cannot read mask (it must have the image's size)\n"; return -1; }
+        const int cn = mask.channels();  // 8-bit, as read
+        weights = Mat(img.rows, img.cols, CV_32F);
+        for (int r = 0; r < img.rows; ++r)
+            for (int c = 0; c < img.cols; ++c) {
+                bool any = false;
+                for (int k = 0; k < cn; ++k) any = any || mask.ptr<unsigned char>(r)[c * cn + k] != 0;
+                weights.ptr<float>(r)[c] = any ? 1.f : 0.f;
+            }
     }
 
     Mat psf = motionBlurKernel(psf_length, psf_angle);
@@ -169,9 +192,11 @@ int main(int argc, char** argv) {
     if (rl_iterations >= 0) {  // Richardson-Lucy on the same channels: its planes become the written result
         vector<Mat> rl = input;
         t_start = high_resolution_clock::now();
-        fft_gpu::richardsonLucy_RGB(rl, psf, rl_iterations);
+        if (free_boundary) fft_gpu::richardsonLucyFree_RGB(rl, psf, rl_iterations, weights);
+        else fft_gpu::richardsonLucy_RGB(rl, psf, rl_iterations);
         t_end = high_resolution_clock::now();
-        cout << "Deblurring 3 channels took(gpu[richardson-lucy " << rl_iterations << "]): " << getElapsedMs(t_start, t_end) << " ms\n";
+        cout << "Deblurring 3 channels took(gpu[richardson-lucy " << (free_boundary ? "free-boundary " : "") << rl_iterations
+             << "]): " << getElapsedMs(t_start, t_end) << " ms\n";
         channels = rl;
     }
 
