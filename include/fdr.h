@@ -119,6 +119,32 @@ int fdr_plan_dims(const fdr_plan* plan, int* M, int* N, int* mode);
                                       (default 160: pairs at 4096^2, the whole group below) -- because launches of half the size
                                       interleave better with the other stream's memory-bound passes; 0 = always the whole group.
                                       Same bits either way. */
+#define FDR_OPT_PAD_MODE 5         /* what the fdr_wiener_* calls put outside the rows x cols picture in the M x N plan:
+                                      FDR_PAD_ZERO (default; zeros, as the reference pads) or FDR_PAD_SMOOTH, a smooth periodic
+                                      continuation of the picture computed by pass A as it loads (no extra pass, no extra memory).
+                                      A photograph is a crop of a larger scene: zero padding gives the periodic blur model a step at
+                                      the right and bottom borders and at the wrap to the left and top ones, which the inverse filter
+                                      turns into ringing across the whole picture (15 to 19 dB of PSNR).  With
+                                      d the picture, e the padded plane and ramp(n)[j] = 0.5 - 0.5 cos(pi (j + 1) / (n + 1)), j < n:
+                                          r < rows, c >= cols :  t = ramp(N - cols)[c - cols];  e[r, c] = (1 - t) d[r, cols-1] + t d[r, 0]
+                                          r >= rows, all c    :  t = ramp(M - rows)[r - rows];  e[r, c] = (1 - t) e[rows-1, c] + t e[0, c]
+                                          result = window( IDFT2( W . DFT2(e) ) ), normalised as with zeros
+                                      i.e. to the right of its last column the plane fades into column 0, its wrap neighbour, and below
+                                      its last row into row 0.  With rows = M and cols = N there is nothing to fill: same bytes as
+                                      FDR_PAD_ZERO.  FDR_NORM_PADDED takes min and max over the whole restored plan (which now holds a
+                                      restored continuation), FDR_NORM_CROPPED over the window.  The mode serves fdr_wiener_f32, _dev,
+                                      fdr_wiener_batch_f32_dev (part of what an FDR_OPT_BATCH_GRAPH replay is keyed on),
+                                      fdr_wiener_batch_f32 and fdr_wiener_batch_ptrs_f32, with a Wiener or a CLS filter.  Leave a margin
+                                      of at least the PSF's reach (M >= rows + prows - 1, N >= cols + pcols - 1) for the continuation
+                                      to take up the blur that crosses the border.
+                                      Plans: FDR_MODE_FAST on the panel path -- M, N powers of two, 8 .. 8192, with or without
+                                      FDR_FLAG_FULL_SPECTRUM.  Parity mode, FDR_FLAG_SIMPLE_PATH, FDR_FLAG_ANY_SIZE sizes, mixed-radix
+                                      sizes, FDR_FLAG_TABLES_ONLY and dimensions below 8 or above 8192 return FDR_ERR_ARG before any
+                                      device work, as does any other value.  The blur operator, Richardson-Lucy (both forms), the TV
+                                      solve, the motion estimate, fdr_batch_run (its own plans) and fdr_slab_* pad with zeros and
+                                      ignore the option. */
+#define FDR_PAD_ZERO 0
+#define FDR_PAD_SMOOTH 1
 int fdr_plan_set_option(fdr_plan* plan, int option, long long value);
 
 /* -- PSF generation: utils.hpp:15-24 motionBlurKernel(size, angle) ------------------- */

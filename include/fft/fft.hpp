@@ -31,6 +31,10 @@ struct Options {
     bool mixed_radix = false;         // FDR_MODE_FAST: 2^a 3^b 5^c plan sizes by mixed-radix FFTs (FDR_FLAG_MIXED_RADIX) in wienerDeblur_myfft
     float cls_gamma = 0.f;            // > 0: constrained least-squares filter W = conj(H) / (|H|^2 + K + gamma L^2) (fdr_set_psf_cls,
                                       // FDR_MODE_FAST only: a parity plan refuses it); 0: the Wiener filter
+    int pad_mode = FDR_PAD_ZERO;      // FDR_PAD_SMOOTH: wienerDeblur_RGB_optimized / _naive continue the picture smoothly into the padding
+                                      // (FDR_OPT_PAD_MODE, FDR_MODE_FAST only: a parity plan refuses it) on a plan of the next powers of two of
+                                      // rows + psf.rows - 1 and cols + psf.cols - 1 -- up to 4x the plan of FDR_PAD_ZERO for a picture whose
+                                      // sides are powers of two already
 };
 // process-wide defaults of the reference-signature overloads (the drivers' --mode / --norm flags); atomics: reading
 // them from several threads is safe, and no entry point ever changes them behind the caller's back
@@ -40,9 +44,12 @@ inline std::atomic<float>& default_cls_gamma() { static std::atomic<float> g{0.f
 inline void set_mode(int mode) { default_mode().store(mode); }
 inline void set_norm_area(int area) { default_norm().store(area); }
 inline void set_cls_gamma(float gamma) { default_cls_gamma().store(gamma); }
+inline std::atomic<int>& default_pad_mode() { static std::atomic<int> m{FDR_PAD_ZERO}; return m; }
+inline void set_pad_mode(int pad_mode) { default_pad_mode().store(pad_mode); }
 inline Options defaults() {
     Options o;
     o.mode = default_mode().load(); o.norm_area = default_norm().load(); o.cls_gamma = default_cls_gamma().load();
+    o.pad_mode = default_pad_mode().load();
     return o;
 }
 
@@ -52,6 +59,16 @@ inline void set_psf_opts(fdr_plan* plan, const Mat& psf, float K, const Options&
     if (o.cls_gamma != 0.f) FDR_CHECK(fdr_set_psf_cls(plan, psfc.ptr<float>(0), psf.rows, psf.cols, psf.cols, K, o.cls_gamma));
     else FDR_CHECK(fdr_set_psf(plan, psfc.ptr<float>(0), psf.rows, psf.cols, psf.cols, K));
 }
+
+// the plan's padding: plans are cached between calls, so a plan that served FDR_PAD_SMOOTH is set back (a plan that has no
+// smooth padding refuses the option and pads with zeros anyway)
+inline void set_pad_opts(fdr_plan* plan, const Options& o) {
+    if (o.pad_mode != FDR_PAD_ZERO) FDR_CHECK(fdr_plan_set_option(plan, FDR_OPT_PAD_MODE, o.pad_mode));
+    else (void)fdr_plan_set_option(plan, FDR_OPT_PAD_MODE, FDR_PAD_ZERO);
+}
+// the plan of the RGB entry points: the next powers of two of the picture's sides, with FDR_PAD_SMOOTH of the sides plus the PSF's reach
+inline int pad_plan_rows(int rows, const Mat& psf, const Options& o) { return nextPowerOfTwo(o.pad_mode == FDR_PAD_SMOOTH ? rows + psf.rows - 1 : rows); }
+inline int pad_plan_cols(int cols, const Mat& psf, const Options& o) { return nextPowerOfTwo(o.pad_mode == FDR_PAD_SMOOTH ? cols + psf.cols - 1 : cols); }
 
 // The reference's Profiler buckets (fft/fft_gpu.cu:17-57).  alloc / h2d / pre / compute / d2h come from
 // fdr_plan_phase_times (hipEvent pairs on the streams the work ran on); post is the host time of wrapping the results.
@@ -144,8 +161,9 @@ inline void wienerDeblur_RGB_optimized(std::vector<Mat>& channels, const Mat& ps
     const int imgRows = channels[0].rows, imgCols = channels[0].cols;
     bool created = false;
     PlanCacheSettle settle_;
-    fdr_plan* plan = plan_cache().get(o.device, nextPowerOfTwo(imgRows), nextPowerOfTwo(imgCols), o.mode, &created);
+    fdr_plan* plan = plan_cache().get(o.device, pad_plan_rows(imgRows, psf, o), pad_plan_cols(imgCols, psf, o), o.mode, &created);
     if (!created) { float discard[FDR_N_PHASES]; FDR_CHECK(fdr_plan_phase_times(plan, discard, 1)); }  // this call's phases only ([1. Allocation] = 0: reused)
+    set_pad_opts(plan, o);
     set_psf_opts(plan, psf, K, o);
     // all channels through the host batch pipeline: upload, restoration and download of consecutive channels overlap
     // (what the stream + pinned-buffer set-up of fft/fft_gpu.cu:304-350 is after)
@@ -179,7 +197,8 @@ inline void wienerDeblur_RGB_naive(std::vector<Mat>& channels, const Mat& psf, f
     Profiler p;
     for (size_t i = 0; i < channels.size(); ++i) {
         fdr_plan* plan = nullptr;
-        FDR_CHECK(fdr_plan_create(o.device, nextPowerOfTwo(channels[i].rows), nextPowerOfTwo(channels[i].cols), o.mode, 0, &plan));
+        FDR_CHECK(fdr_plan_create(o.device, pad_plan_rows(channels[i].rows, psf, o), pad_plan_cols(channels[i].cols, psf, o), o.mode, 0, &plan));
+        set_pad_opts(plan, o);
         set_psf_opts(plan, psf, K, o);
         channels[i] = run_channel(plan, channels[i], o.norm_area);
         p.add(plan);
@@ -296,6 +315,7 @@ inline Mat wienerDeblur_myfft(const Mat& img, const Mat& psf, float K, const Opt
     bool created = false;
     PlanCacheSettle settle_;
     fdr_plan* plan = plan_cache().get(o.device, M, N, o.mode, &created, flags);
+    (void)fdr_plan_set_option(plan, FDR_OPT_PAD_MODE, FDR_PAD_ZERO);  // (a cached plan may have served FDR_PAD_SMOOTH; o.pad_mode does not apply here)
     set_psf_opts(plan, psf, K, o);
     return run_channel(plan, img, FDR_NORM_CROPPED);
 }

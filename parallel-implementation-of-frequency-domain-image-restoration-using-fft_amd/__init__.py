@@ -35,6 +35,9 @@ MAX_PASSES = 16
 OPT_TWO_SWEEP_NORM = 2
 OPT_BATCH_GRAPH = 3
 OPT_CE_CHUNK_MB = 4
+OPT_PAD_MODE = 5  # Plan.set_option: what the Wiener / CLS calls put outside the picture (fast-mode power-of-two plans)
+PAD_ZERO = 0      # zeros, as the reference pads (default)
+PAD_SMOOTH = 1    # a smooth periodic continuation of the picture (include/fdr.h, FDR_OPT_PAD_MODE)
 PHASES = ("alloc", "h2d", "pre", "compute", "d2h", "post")  # the reference Profiler's buckets, fft/fft_gpu.cu:17-57
 BATCH_MAX_DEVICES = 16
 
@@ -637,12 +640,38 @@ def host_alloc(shape, dtype=np.float32):
     return np.frombuffer(buf, dtype=dtype).reshape(shape)
 
 
-def wienerDeblur_myfft(img, psf, K, mode=MODE_PARITY, device=0, norm_area=NORM_PADDED, cls_gamma=0.0):
+def _pad_plan_size(rows, cols, prows, pcols):
+    """the plan of the Wiener entry points with pad=PAD_SMOOTH: the next powers of two of rows + prows - 1 and cols + pcols - 1, as
+    _rlfree_plan_size -- the margin is then at least the PSF's reach.  A picture whose sides are powers of two already gets a plan of
+    4x the area (and about 4x the time) of its PAD_ZERO plan."""
+    return _rlfree_plan_size(rows, cols, prows, pcols)
+
+
+def _wiener_plan(rows, cols, psf, mode, device, pad):
+    """the plan of wienerDeblur_myfft / _RGB_optimized for one picture size, its padding mode set"""
+    if pad == PAD_ZERO:
+        return Plan(nextPowerOfTwo(rows), nextPowerOfTwo(cols), mode, device)
+    if pad != PAD_SMOOTH:
+        raise ValueError("pad must be PAD_ZERO or PAD_SMOOTH")
+    if mode != MODE_FAST:
+        raise ValueError("pad=PAD_SMOOTH needs mode=MODE_FAST (parity mode is bit-identical to ./serial, which pads with zeros)")
+    prows, pcols = np.shape(psf)
+    p = Plan(*_pad_plan_size(rows, cols, prows, pcols), mode, device)
+    try:
+        p.set_option(OPT_PAD_MODE, PAD_SMOOTH)
+    except Exception:
+        p.close()
+        raise
+    return p
+
+
+def wienerDeblur_myfft(img, psf, K, mode=MODE_PARITY, device=0, norm_area=NORM_PADDED, cls_gamma=0.0, pad=PAD_ZERO):
     """One channel the way the DRIVERS call the operator: pad to powers of two (serial.cpp:36 / fft_gpu.cu:287-288, on the
     device), restore, normalise (default: over the padded area, serial.cpp:34-39), crop.  cls_gamma > 0 (MODE_FAST): the
-    constrained least-squares filter instead of the Wiener filter (Plan.set_psf)."""
+    constrained least-squares filter instead of the Wiener filter (Plan.set_psf).  pad=PAD_SMOOTH (MODE_FAST): the picture is
+    continued smoothly into the padding (OPT_PAD_MODE) of a plan of _pad_plan_size -- for a crop of a larger scene."""
     img = np.asarray(img, dtype=np.float32)
-    with Plan(nextPowerOfTwo(img.shape[0]), nextPowerOfTwo(img.shape[1]), mode, device) as p:
+    with _wiener_plan(img.shape[0], img.shape[1], psf, mode, device, pad) as p:
         p.set_psf(psf, K, gamma=cls_gamma)
         return p.wiener(img, norm_area)
 
@@ -765,21 +794,22 @@ def batch_run(devices, M, N, count, rows=None, cols=None, mode=MODE_FAST, flags=
     return stats, outs
 
 
-def wienerDeblur_RGB_optimized(channels, psf, K, mode=MODE_PARITY, device=0, norm_area=NORM_PADDED, cls_gamma=0.0):
+def wienerDeblur_RGB_optimized(channels, psf, K, mode=MODE_PARITY, device=0, norm_area=NORM_PADDED, cls_gamma=0.0, pad=PAD_ZERO):
     """fft_gpu::wienerDeblur_RGB_optimized (fft/fft_gpu.cu:279-394): replaces every element of
     `channels` (unpadded float32 planes of one size) in place with its restored [0,1] plane.
-    One plan and one PSF spectrum serve all channels.  cls_gamma > 0: the constrained least-squares filter."""
+    One plan and one PSF spectrum serve all channels.  cls_gamma > 0: the constrained least-squares filter.  pad: as
+    wienerDeblur_myfft."""
     if not channels:
         return
     r, c = np.asarray(channels[0]).shape
-    with Plan(nextPowerOfTwo(r), nextPowerOfTwo(c), mode, device) as p:
+    with _wiener_plan(r, c, psf, mode, device, pad) as p:
         p.set_psf(psf, K, gamma=cls_gamma)
         for i in range(len(channels)):
             channels[i] = p.wiener(channels[i], norm_area)
 
 
-def wienerDeblur_RGB_naive(channels, psf, K, mode=MODE_PARITY, device=0, norm_area=NORM_PADDED, cls_gamma=0.0):
+def wienerDeblur_RGB_naive(channels, psf, K, mode=MODE_PARITY, device=0, norm_area=NORM_PADDED, cls_gamma=0.0, pad=PAD_ZERO):
     """fft_gpu::wienerDeblur_RGB_naive (fft/fft_gpu.cu:400-512): same results, but every channel
     builds and frees its own plan and PSF spectrum, as the reference's allocation-in-loop variant."""
     for i in range(len(channels)):
-        channels[i] = wienerDeblur_myfft(channels[i], psf, K, mode, device, norm_area, cls_gamma)
+        channels[i] = wienerDeblur_myfft(channels[i], psf, K, mode, device, norm_area, cls_gamma, pad)

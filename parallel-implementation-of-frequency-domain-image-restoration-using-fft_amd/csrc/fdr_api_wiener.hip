@@ -119,7 +119,7 @@ int panel_stage_A(fdr_plan* p, fdr_plan::Slot& w, const float* d_img, int rows, 
     ScopedPass t(p, s, kPassRowsFwd);   // A: 4 rows per thread group, real -> panel-major (half) spectrum
     RowArgs a{};
     a.src_real = d_img; a.src_rows = rows; a.src_cols = cols; a.src_stride = stride;
-    a.dst_c = w.work; a.M = p->M; a.pstride = p->pstride; a.half = p->half; a.num_cu = p->num_cu;
+    a.dst_c = w.work; a.M = p->M; a.pstride = p->pstride; a.half = p->half; a.num_cu = p->num_cu; a.pad_mode = p->pad_mode;
     FDR_HIP(launch_rows4(p->logN, ROW_IN_REAL, ROW_OUT_COMPLEX, a, p->tw_row_f, s));
     return FDR_OK;
 }
@@ -177,7 +177,7 @@ int panel_stage_A_batch(fdr_plan* p, fdr_plan::Slot* const* ws, int n, const flo
     ScopedPass t(p, s, kPassRowsFwdN[n]);
     RowArgs a{};
     a.src_real = d_imgs[0]; a.src_rows = rows; a.src_cols = cols; a.src_stride = stride;
-    a.dst_c = ws[0]->work; a.M = p->M; a.pstride = p->pstride; a.half = 1; a.num_cu = p->num_cu;
+    a.dst_c = ws[0]->work; a.M = p->M; a.pstride = p->pstride; a.half = 1; a.num_cu = p->num_cu; a.pad_mode = p->pad_mode;
     a.batch.nimg = n;
     for (int k = 0; k < kMaxGroup; ++k) { a.batch.src_real[k] = d_imgs[k < n ? k : 0]; a.batch.spec[k] = ws[k < n ? k : 0]->work; }
     FDR_HIP(launch_rows4(p->logN, ROW_IN_REAL, ROW_OUT_COMPLEX, a, p->tw_row_f, s));
@@ -509,7 +509,7 @@ int fdr_wiener_batch_f32_dev(fdr_plan* p, const float* d_imgs, size_t img_pitch,
     // Not with per-kernel profiling (host-side event pairs).
     if (p->batch_graph && p->panel && !p->timer.enabled) {
         const fdr_plan::GraphKey key{d_imgs, d_out, img_pitch, out_pitch, count, rows, cols, stride, out_stride, norm_area, p->nstreams, p->group,
-                                     p->two_sweep, p->K, p->ce_chunk_bytes};
+                                     p->two_sweep, p->K, p->ce_chunk_bytes, p->pad_mode};
         if (!(p->graph_exec && key == p->graph_key)) {
             if (p->graph_exec) { (void)hipGraphExecDestroy(p->graph_exec); p->graph_exec = nullptr; }
             if (!p->cap_stream) FDR_HIP(hipStreamCreateWithFlags(&p->cap_stream, hipStreamNonBlocking));

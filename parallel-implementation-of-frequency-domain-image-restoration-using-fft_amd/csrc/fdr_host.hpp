@@ -144,17 +144,18 @@ struct fdr_plan {
     int group = 1;    // images per pass-B' launch (panel path)
     hipEvent_t fork = nullptr;
     size_t ws_elems = 0;  // elements of one work / raw buffer
+    int pad_mode = FDR_PAD_ZERO;     // FDR_OPT_PAD_MODE: what pass A of the fdr_wiener_* calls puts outside the picture (panel path)
     bool two_sweep = true;           // FDR_OPT_TWO_SWEEP_NORM: passes C1 + C2 instead of C' + E (fast half-spectrum path)
     size_t ce_chunk_bytes = (size_t)160 << 20;  // FDR_OPT_CE_CHUNK_MB: spectrum bytes per C1 + C2 launch pair of a multi-stream batch (0 = whole group)
     // FDR_OPT_BATCH_GRAPH: the launches of one fdr_wiener_batch_f32_dev call (fork, every pass of every group on the
     // internal streams, join) captured once as a hipGraph and replayed while the call's arguments stay the same
     struct GraphKey {
         const float* in; float* out; size_t in_pitch, out_pitch; int count, rows, cols, stride, out_stride, norm_area, nstreams, group;
-        bool two_sweep; float K; size_t ce_cache;
+        bool two_sweep; float K; size_t ce_cache; int pad_mode;
         bool operator==(const GraphKey& o) const {
             return in == o.in && out == o.out && in_pitch == o.in_pitch && out_pitch == o.out_pitch && count == o.count && rows == o.rows &&
                    cols == o.cols && stride == o.stride && out_stride == o.out_stride && norm_area == o.norm_area && nstreams == o.nstreams &&
-                   group == o.group && two_sweep == o.two_sweep && K == o.K && ce_cache == o.ce_cache;
+                   group == o.group && two_sweep == o.two_sweep && K == o.K && ce_cache == o.ce_cache && pad_mode == o.pad_mode;
         }
     };
     // host-pointer batch (fdr_wiener_batch_*_f32): three streams, three images in flight; created on first use and kept --

@@ -91,7 +91,10 @@ struct RowArgs {
     RowBatch batch;     // rows4 packed kernels: several images per launch
     int panel_c;        // launch_rows (parity operator): the complex side(s) are PANEL-major, full spectrum: element (m, n) at
                         // (n >> 2) * pstride + m * 4 + (n & 3) -- the column passes then work on contiguous tiles
+    int pad_mode;       // rows4 forward kernels (pass A): FDR_PAD_ZERO / FDR_PAD_SMOOTH -- what stands outside the picture.  In the tail
+                        // padding of the block: its size and every other field's offset are unchanged
 };
+static_assert(sizeof(RowArgs) == 448, "pad_mode fits the tail padding of RowArgs: the argument blocks keep their layout");
 
 // up to kMaxGroup images' spectra handled by ONE pass-B' launch (their panels form one tile sequence)
 struct PanelBatch {

@@ -70,11 +70,61 @@ __device__ __forceinline__ void landed_f(const float (&d)[R][C]) {
         for (int c = 0; c < C; c += 4) asm volatile("" ::"v"(d[r][c]), "v"(d[r][c + 1]), "v"(d[r][c + 2]), "v"(d[r][c + 3]));
 }
 
+// ---------------------------------------------------------------------------------------------
+// Smooth padding (RowArgs::pad_mode, FDR_PAD_SMOOTH of fdr.h): outside the rows x cols window the
+// padded plane e continues the picture periodically instead of dropping to zero.  With ramp(n)[j] = 0.5 - 0.5 cos(pi (j + 1) / (n + 1)):
+//     r < rows, c >= cols :  t = ramp(N - cols)[c - cols];  e[r, c] = (1 - t) d[r, cols-1] + t d[r, 0]
+//     r >= rows           :  s = ramp(M - rows)[r - rows];  e[r, c] = (1 - s) e[rows-1, c] + s e[0, c]
+// so an element needs at most four source values (three of them shared along a row or a column: PadRows).  Only the edge branches of the pass A kernels evaluate it (template parameter
+// PAD); their interior branches and every PAD = 0 instantiation are the zero-padding code.  The weights come from cospif in the
+// kernel: no table, nothing to upload, nothing that a stream capture would have to know about.
+// ---------------------------------------------------------------------------------------------
+constexpr int kPadZero = 0, kPadSmooth = 1;  // FDR_PAD_ZERO, FDR_PAD_SMOOTH
+__device__ __forceinline__ float pad_ramp(int j, int n) { return 0.5f - 0.5f * cospif((float)(j + 1) / (float)(n + 1)); }
+// What NR consecutive rows r0 .. r0+NR-1 of the extended plane share (uniform over the thread group, so these are scalar loads): column 0
+// of each row (of row rows-1 below the picture), d[0, 0], the row weights, and whether any of the rows lies below the picture.
+template <int NR>
+struct PadRows {
+    float c0[NR], rs[NR], d00;
+    bool below[NR], any_below;
+};
+template <int NR>
+__device__ __forceinline__ void pad_rows_init(PadRows<NR>& g, const float* __restrict__ src, int stride, int rows, int r0, int M) {
+    g.d00 = src[0];
+    g.any_below = r0 + NR - 1 >= rows;
+#pragma unroll
+    for (int b = 0; b < NR; ++b) {
+        const int r = r0 + b;
+        g.below[b] = r >= rows;
+        g.c0[b] = src[(size_t)(r < rows ? r : rows - 1) * stride];
+        g.rs[b] = r >= rows ? pad_ramp(r - rows, M - rows) : 0.f;
+    }
+}
+// Column n of those rows: v[b] = d[min(r0 + b, rows-1), min(n, cols-1)] on entry (the element itself inside the picture, else the
+// first of its source values), e[r0 + b, n] on return; ncp = N - cols.  One more load (d[0, .]) only below the picture, one cospif only
+// to the right of it; every address lies inside the picture.
+template <int NR>
+__device__ __forceinline__ void pad_smooth_rows(float (&v)[NR], const PadRows<NR>& g, const float* __restrict__ src, int cols, int n, int ncp) {
+    const bool right = n >= cols;
+    float t = 0.f;
+    if (right) {
+        t = pad_ramp(n - cols, ncp);
+#pragma unroll
+        for (int b = 0; b < NR; ++b) v[b] = (1.f - t) * v[b] + t * g.c0[b];
+    }
+    if (g.any_below) {
+        float w = src[right ? cols - 1 : n];
+        if (right) w = (1.f - t) * w + t * g.d00;
+#pragma unroll
+        for (int b = 0; b < NR; ++b) v[b] = g.below[b] ? (1.f - g.rs[b]) * v[b] + g.rs[b] * w : v[b];
+    }
+}
 
 // HALF: keep only the non-redundant half of each Hermitian row spectrum -- columns 0 .. N/2-1 in panels
 // 0 .. N/8-1.  X[m,0] and X[m,N/2] are real for a real row, so the Nyquist column rides in the imaginary
 // part of column 0: stored(m, 0) = X[m,0] + i X[m,N/2]  ("packed column", undone in passes B' and C').
-template <int LOGL, bool HALF>
+// PAD: what the edge branch puts outside the picture (kPadZero / kPadSmooth, see pad_smooth_rows).
+template <int LOGL, bool HALF, int PAD = kPadZero>
 __global__ __launch_bounds__(Rows4PackGeom<LOGL>::THREADS) void fft_rows4_fwd_packed_kernel(const RowArgs a0,
                                                                                           const float2* __restrict__ tw_fwd) {
     RowArgs a = a0;
@@ -115,6 +165,24 @@ __global__ __launch_bounds__(Rows4PackGeom<LOGL>::THREADS) void fft_rows4_fwd_pa
                 // the image is read exactly once: keep it out of the caches that hold the intermediates
                 z[0][s] = make_float2(__builtin_nontemporal_load(row0 + n), __builtin_nontemporal_load(row1 + n));
                 z[1][s] = make_float2(__builtin_nontemporal_load(row2 + n), __builtin_nontemporal_load(row3 + n));
+            }
+    } else if constexpr (PAD == kPadSmooth) {
+        PadRows<4> pr;
+        pad_rows_init(pr, a.src_real, a.src_stride, a.src_rows, rr, M);
+        const float* rowp[4];
+#pragma unroll
+        for (int b = 0; b < 4; ++b) rowp[b] = a.src_real + (size_t)(rr + b < a.src_rows ? rr + b : a.src_rows - 1) * a.src_stride;
+#pragma unroll
+        for (int u = 0; u < Core::NU0; ++u)
+#pragma unroll
+            for (int q = 0; q < Core::RHO0; ++q) {
+                const int s = u * Core::RHO0 + q;
+                const int n = Core::in_index(tid, u, q);
+                const int nc = n < a.src_cols ? n : a.src_cols - 1;
+                float x[4] = {rowp[0][nc], rowp[1][nc], rowp[2][nc], rowp[3][nc]};
+                pad_smooth_rows(x, pr, a.src_real, a.src_cols, n, L - a.src_cols);
+                z[0][s] = make_float2(x[0], x[1]);
+                z[1][s] = make_float2(x[2], x[3]);
             }
     } else {
 #pragma unroll
@@ -239,7 +307,7 @@ struct RowsPersGeom {
     static constexpr int WAVES_PER_SIMD = WG_PER_CU * THREADS / 256;
 };
 
-template <int LOGL, int LOGV, bool HALF, bool INTERIOR>
+template <int LOGL, int LOGV, bool HALF, bool INTERIOR, int PAD = kPadZero>
 __global__ __launch_bounds__((RowsPersGeom<LOGL, LOGV>::THREADS), (RowsPersGeom<LOGL, LOGV>::WAVES_PER_SIMD)) void fft_rows4_fwd_pers_kernel(
     const RowArgs a, const float2* __restrict__ tw_fwd, const int ngroups, const int total) {
     using St = Steps<LOGL, LOGV>;
@@ -282,17 +350,31 @@ __global__ __launch_bounds__((RowsPersGeom<LOGL, LOGV>::THREADS), (RowsPersGeom<
                 }
         }
     };
-    // z[0] = rows 0 + i 1, z[1] = rows 2 + i 3 of group g (zero padding applied here)
+    // z[0] = rows 0 + i 1, z[1] = rows 2 + i 3 of group g of the image at `src` (the padding is applied here).  Smooth padding: the
+    // prefetched value of an element outside the picture is the clamped one, d[min(r, rows-1), min(n, cols-1)] -- the first of the (at
+    // most four) source values; the others are fetched here, by the padded elements only (pad_smooth_rows).
     float2 z[2][V];
-    auto pack = [&](int g) __attribute__((always_inline)) {
+    auto pack = [&](const float* __restrict__ src, int g) __attribute__((always_inline)) {
         const int r0 = g * 4;
+        PadRows<4> pr;
+        // (opaque copy of the thread index: the column weights and offsets below depend on the column alone, and hoisted out of the
+        // group loop they would stay in ~40 registers across the transform, beside the prefetched rows -- more than the budget holds)
+        int tp = tid;
+        if constexpr (!INTERIOR && PAD == kPadSmooth) {
+            asm volatile("" : "+v"(tp));
+            pad_rows_init(pr, src, a.src_stride, a.src_rows, r0, a.M);
+        }
 #pragma unroll
         for (int u = 0; u < Core::NU0; ++u)
 #pragma unroll
             for (int q = 0; q < Core::RHO0; ++q) {
                 const int s = u * Core::RHO0 + q;
                 float v0 = x[0][s], v1 = x[1][s], v2 = x[2][s], v3 = x[3][s];
-                if (!INTERIOR) {
+                if constexpr (!INTERIOR && PAD == kPadSmooth) {
+                    float v[4] = {v0, v1, v2, v3};
+                    pad_smooth_rows(v, pr, src, a.src_cols, Core::in_index(tp, u, q), L - a.src_cols);
+                    v0 = v[0]; v1 = v[1]; v2 = v[2]; v3 = v[3];
+                } else if (!INTERIOR) {
                     const bool cok = Core::in_index(tid, u, q) < a.src_cols;
                     v0 = (cok && r0 + 0 < a.src_rows) ? v0 : 0.f;
                     v1 = (cok && r0 + 1 < a.src_rows) ? v1 : 0.f;
@@ -361,7 +443,7 @@ __global__ __launch_bounds__((RowsPersGeom<LOGL, LOGV>::THREADS), (RowsPersGeom<
     // compiler has to merge it with the first iteration's state (no stores yet) and emits vmcnt(0).
     request(src_of(img), grp, 1u);
     landed_f(x);  // (also here: the loop top must see landed values on both of its entries, or it waits again)
-    pack(grp);
+    pack(src_of(img), grp);
     while (true) {
         const bool more = gi + (int)gridDim.x < total;
         int nimg_i = img, ngrp = grp;
@@ -374,7 +456,7 @@ __global__ __launch_bounds__((RowsPersGeom<LOGL, LOGV>::THREADS), (RowsPersGeom<
         if (!more) break;
         landed_f(x);      // wait for the prefetch here, behind this group's stores
         __syncthreads();  // the separation's reads are done before the next transform's first exchange writes
-        pack(ngrp);
+        pack(src_of(nimg_i), ngrp);
         gi += (int)gridDim.x; img = nimg_i; grp = ngrp;
     }
 }
@@ -840,7 +922,7 @@ static inline bool rows4_use_split(int logl, int M, int nimg, int half) {
     return nimg <= 1 && half && logl >= 8 && logl <= 11 && (M & 3) == 0 && M > 0 && M <= 2048;
 }
 
-template <int LOGL>
+template <int LOGL, int PAD = kPadZero>
 __global__ __launch_bounds__(RowsSplitGeom<LOGL>::THREADS) void fft_rows4_fwd_split_kernel(const RowArgs a, const float2* __restrict__ tw_fwd) {
     using Geo = RowsSplitGeom<LOGL>;
     using St = typename Geo::St;
@@ -857,20 +939,37 @@ __global__ __launch_bounds__(RowsSplitGeom<LOGL>::THREADS) void fft_rows4_fwd_sp
     Core::init_bases(bases, tw_fwd, tid);
 
     float2 z[1][8];
-    const float* __restrict__ rowa = a.src_real + (size_t)(ra < a.src_rows ? ra : 0) * a.src_stride;
-    const float* __restrict__ rowb = a.src_real + (size_t)(rb < a.src_rows ? rb : 0) * a.src_stride;
+    if constexpr (PAD == kPadSmooth) {
+        PadRows<2> pr;
+        pad_rows_init(pr, a.src_real, a.src_stride, a.src_rows, ra, a.M);
+        const float* __restrict__ rowa = a.src_real + (size_t)(ra < a.src_rows ? ra : a.src_rows - 1) * a.src_stride;
+        const float* __restrict__ rowb = a.src_real + (size_t)(rb < a.src_rows ? rb : a.src_rows - 1) * a.src_stride;
 #pragma unroll
-    for (int u = 0; u < Core::NU0; ++u)
+        for (int u = 0; u < Core::NU0; ++u)
 #pragma unroll
-        for (int q = 0; q < Core::RHO0; ++q) {
-            const int n = Core::in_index(tid, u, q);
-            float xa = 0.f, xb = 0.f;
-            if (n < a.src_cols) {
-                if (ra < a.src_rows) xa = __builtin_nontemporal_load(rowa + n);
-                if (rb < a.src_rows) xb = __builtin_nontemporal_load(rowb + n);
+            for (int q = 0; q < Core::RHO0; ++q) {
+                const int n = Core::in_index(tid, u, q);
+                const int nc = n < a.src_cols ? n : a.src_cols - 1;
+                float x[2] = {rowa[nc], rowb[nc]};
+                pad_smooth_rows(x, pr, a.src_real, a.src_cols, n, L - a.src_cols);
+                z[0][u * Core::RHO0 + q] = make_float2(x[0], x[1]);
             }
-            z[0][u * Core::RHO0 + q] = make_float2(xa, xb);
-        }
+    } else {
+        const float* __restrict__ rowa = a.src_real + (size_t)(ra < a.src_rows ? ra : 0) * a.src_stride;
+        const float* __restrict__ rowb = a.src_real + (size_t)(rb < a.src_rows ? rb : 0) * a.src_stride;
+#pragma unroll
+        for (int u = 0; u < Core::NU0; ++u)
+#pragma unroll
+            for (int q = 0; q < Core::RHO0; ++q) {
+                const int n = Core::in_index(tid, u, q);
+                float xa = 0.f, xb = 0.f;
+                if (n < a.src_cols) {
+                    if (ra < a.src_rows) xa = __builtin_nontemporal_load(rowa + n);
+                    if (rb < a.src_rows) xb = __builtin_nontemporal_load(rowb + n);
+                }
+                z[0][u * Core::RHO0 + q] = make_float2(xa, xb);
+            }
+    }
 
     Core::template run<0, false>(z, grp_lds, tw_fwd, bases, tid);
 
@@ -1029,13 +1128,18 @@ static hipError_t launch_rows4_t(RowIn in, RowOut out, const RowArgs& a, const f
     const dim3 grid((groups + Geo::G - 1) / Geo::G, nimg), block(Geo::THREADS);
     using IGeo = Rows4PackGeom<LOGL, true>;  // the inverse kernels' own thread-group shape
     const dim3 igrid((groups + IGeo::G - 1) / IGeo::G, nimg), iblock(IGeo::THREADS);
+    // smooth padding: pass A of a picture smaller than the plan, all M rows (a full window has nothing to fill and runs the
+    // zero-padding kernels: same bits by construction)
+    const bool smooth = in == ROW_IN_REAL && a.pad_mode == kPadSmooth && (a.src_rows < a.M || a.src_cols < (1 << LOGL));
+    if (smooth && (a.src_rows <= 0 || a.src_cols <= 0 || a.src_rows > a.M || a.src_cols > (1 << LOGL))) return hipErrorInvalidValue;
     if constexpr (LOGL >= 8 && LOGL <= 11) {
         if (rows4_use_split(LOGL, a.M, nimg, a.half)) {  // one small image: two thread groups per 4-row group (see above)
             using SG = RowsSplitGeom<LOGL>;
             const dim3 sgrid(a.M / 4), sblock(SG::THREADS), siblock(RowsSplitGeom<LOGL, true>::THREADS);
             if (in == ROW_IN_REAL && out == ROW_OUT_COMPLEX) {
                 if (a.src_rows <= 0 || a.src_cols <= 0) return hipErrorInvalidValue;
-                hipLaunchKernelGGL((fft_rows4_fwd_split_kernel<LOGL>), sgrid, sblock, 0, s, a, tw);
+                if (smooth) hipLaunchKernelGGL((fft_rows4_fwd_split_kernel<LOGL, kPadSmooth>), sgrid, sblock, 0, s, a, tw);
+                else hipLaunchKernelGGL((fft_rows4_fwd_split_kernel<LOGL>), sgrid, sblock, 0, s, a, tw);
             } else if (in == ROW_IN_COMPLEX && out == ROW_OUT_REAL_MINMAX) {
                 hipLaunchKernelGGL((fft_rows4_inv_split_kernel<LOGL, 0>), sgrid, siblock, 0, s, a, tw);
             } else if (in == ROW_IN_COMPLEX && out == ROW_OUT_MINMAX_ONLY) {
@@ -1066,7 +1170,10 @@ static hipError_t launch_rows4_t(RowIn in, RowOut out, const RowArgs& a, const f
                 if (g > total) g = total;
                 const bool interior = a.src_rows >= a.M && a.src_cols >= (1 << LOGL);
                 const dim3 pgrid(g), pblock(PG::THREADS);
-                if (a.half) {
+                if (smooth) {  // (never interior)
+                    if (a.half) hipLaunchKernelGGL((fft_rows4_fwd_pers_kernel<LOGL, LOGV, true, false, kPadSmooth>), pgrid, pblock, 0, s, a, tw, groups, total);
+                    else hipLaunchKernelGGL((fft_rows4_fwd_pers_kernel<LOGL, LOGV, false, false, kPadSmooth>), pgrid, pblock, 0, s, a, tw, groups, total);
+                } else if (a.half) {
                     if (interior) hipLaunchKernelGGL((fft_rows4_fwd_pers_kernel<LOGL, LOGV, true, true>), pgrid, pblock, 0, s, a, tw, groups, total);
                     else hipLaunchKernelGGL((fft_rows4_fwd_pers_kernel<LOGL, LOGV, true, false>), pgrid, pblock, 0, s, a, tw, groups, total);
                 } else {
@@ -1076,7 +1183,10 @@ static hipError_t launch_rows4_t(RowIn in, RowOut out, const RowArgs& a, const f
                 return hipGetLastError();
             }
         }
-        if (a.half) hipLaunchKernelGGL((fft_rows4_fwd_packed_kernel<LOGL, true>), grid, block, 0, s, a, tw);
+        if (smooth) {
+            if (a.half) hipLaunchKernelGGL((fft_rows4_fwd_packed_kernel<LOGL, true, kPadSmooth>), grid, block, 0, s, a, tw);
+            else hipLaunchKernelGGL((fft_rows4_fwd_packed_kernel<LOGL, false, kPadSmooth>), grid, block, 0, s, a, tw);
+        } else if (a.half) hipLaunchKernelGGL((fft_rows4_fwd_packed_kernel<LOGL, true>), grid, block, 0, s, a, tw);
         else hipLaunchKernelGGL((fft_rows4_fwd_packed_kernel<LOGL, false>), grid, block, 0, s, a, tw);
     } else if (in == ROW_IN_COMPLEX && out == ROW_OUT_REAL_MINMAX) {
         return launch_rows4_inv_t<LOGL, 0>(a, tw, s, igrid, iblock);

@@ -1,5 +1,5 @@
 // gpu.cpp -- ./gpu <img-path> <psf-length> <psf-angle> [--out file] [--mode fast|parity] [--norm padded|cropped] [--host-epilogue]
-//           [--cls gamma] [--rl iterations [--free-boundary [--mask mask.png]]] [--tv mu [--tv-iters n] [--tv-rho r]]
+//           [--cls gamma] [--pad zero|smooth] [--rl iterations [--free-boundary [--mask mask.png]]] [--tv mu [--tv-iters n] [--tv-rho r]]
 // `auto auto` for length and angle: the blur is estimated first (fft_gpu::estimateMotionBlur on the per-pixel mean of B, G and R),
 // printed as `estimate: length L angle A confidence C`, and the run then goes on exactly as `./gpu <img-path> L A` would.
 // Drop-in counterpart of the reference's gpu.cpp (argument meaning, printed lines and exit codes as at
@@ -72,7 +72,7 @@ int main(int argc, char** argv) {
     float tv_mu = -1.f, tv_rho = 2.0f;  // --tv mu: a timed total-variation leg (fft_gpu::tvDeblur_RGB); its planes are the written result
     int tv_iterations = 50;
     bool tv_opts = false;
-    bool cls = false, parity = false;
+    bool cls = false, parity = false, pad_smooth = false;
     for (int i = 4; i < argc; ++i) {
         string a = argv[i];
         if (a == "--out" && i + 1 < argc) out_path = argv[++i];
@@ -87,6 +87,14 @@ int main(int argc, char** argv) {
         // constrained least-squares filter (fdr_set_psf_cls) in the fft_gpu:: entry points; the serial leg keeps the Wiener filter.
         // Fast mode only: with --mode parity the library refuses it and the first fft_gpu:: call exits with its message
         else if (a == "--cls" && i + 1 < argc) { cls = true; fft_gpu::set_cls_gamma(strtof(argv[++i], nullptr)); }
+        // smooth padding (FDR_OPT_PAD_MODE) in the fft_gpu:: Wiener / CLS entry points; the serial leg keeps zero padding.  Fast mode only:
+        // with --mode parity the library refuses it and the first fft_gpu:: call exits with its message
+        else if (a == "--pad" && i + 1 < argc) {
+            const string v = argv[++i];
+            if (v != "zero" && v != "smooth") { cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle>\n"; return -1; }
+            pad_smooth = v == "smooth";
+            fft_gpu::set_pad_mode(pad_smooth ? FDR_PAD_SMOOTH : FDR_PAD_ZERO);
+        }
         // Richardson-Lucy (fft_gpu::richardsonLucy_RGB, fast mode): n >= 0 iterations
         else if (a == "--rl" && i + 1 < argc) rl_iterations = atoi(argv[++i]);
         else if (a == "--free-boundary") free_boundary = true;
@@ -98,7 +106,9 @@ int main(int argc, char** argv) {
         else { cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle>\n"; return -1; }
     }
     // the RL leg replaces the result the other options shape (CLS filter, parity check, parity-mode restoration)
-    if (rl_iterations >= 0 && (cls || verify || parity)) { cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle>\n"; return -1; }
+    if (rl_iterations >= 0 && (cls || verify || parity || pad_smooth)) { cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle>\n"; return -1; }
+    // --verify compares against the zero-padded serial leg
+    if (pad_smooth && verify) { cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle>\n"; return -1; }
     // --free-boundary belongs to --rl, --mask to --free-boundary
     if ((free_boundary && rl_iterations < 0) || (!mask_path.empty() && !free_boundary)) {
         cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle>\n";
@@ -106,7 +116,7 @@ int main(int argc, char** argv) {
     }
     // so does the TV leg; --tv-iters / --tv-rho belong to --tv, and one run has one iterative leg
     const bool tv = tv_mu > 0.f;
-    if ((tv && (cls || verify || parity || rl_iterations >= 0 || tv_iterations < 0 || !(tv_rho > 0.f))) || (!tv && (tv_opts || tv_mu != -1.f))) {
+    if ((tv && (cls || verify || parity || pad_smooth || rl_iterations >= 0 || tv_iterations < 0 || !(tv_rho > 0.f))) || (!tv && (tv_opts || tv_mu != -1.f))) {
         cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle>\n";
         return -1;
     }
