@@ -514,7 +514,7 @@ int fdr_plan_set_option(fdr_plan* p, int option, long long value) {
             p->two_sweep = value != 0;
             return FDR_OK;
         case FDR_OPT_PAD_MODE:
-            // the padding is made by pass A of the fast panel path (fdr_panel.hip); no other path has the smooth form
+            // the padding is made by pass A of the fast panel path (fdr_panel_rows.hip); no other path has the smooth form
             if (p->tables_only || p->mode != FDR_MODE_FAST || !p->panel || p->mixed)
                 return fail(FDR_ERR_ARG, "fdr_plan_set_option: FDR_OPT_PAD_MODE needs a FDR_MODE_FAST plan on the panel path (M, N powers of two, "
                                          "8 .. 8192; not FDR_FLAG_SIMPLE_PATH, FDR_FLAG_ANY_SIZE, FDR_FLAG_MIXED_RADIX sizes or FDR_FLAG_TABLES_ONLY)");

@@ -1,5 +1,5 @@
 // fdr_api_rlfree.hip -- free-boundary, weighted Richardson-Lucy (fdr_richardson_lucy_free_f32*; kernels in fdr_rlfree.hip and the
-// weighted update kind of fdr_panel.hip): the workspace, the checks, the driver and the two entry points.  Every transform is an
+// weighted update kind of fdr_panel_rows.hip): the workspace, the checks, the driver and the two entry points.  Every transform is an
 // operator pass of fdr_api_operator.hip: the estimate goes through pass A as a dense M x N plane, the ratio through the window.
 #include "fdr_host.hpp"
 

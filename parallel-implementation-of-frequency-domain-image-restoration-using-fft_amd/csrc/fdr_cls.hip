@@ -5,34 +5,25 @@
 // L is the symbol of the periodic 5-point Laplacian.  The plan keeps a_u = 4 sin^2(pi u / M) (u < M) followed by
 // b_v = 4 sin^2(pi v / N) (v < N) as a double table (fdr_api_wiener.hip, ensure_lap_table); cls_filter_fast / cls_reg
 // (fdr_fft_core.hpp) evaluate the quotient in double and round once, as the Wiener filter does.  Two of the four filter
-// sites live here, in a translation unit of their own so that the Wiener kernels of fdr_panel.hip and fdr_aux.hip keep
+// sites live here, in a translation unit of their own so that the Wiener kernels of fdr_panel_cols.hip and fdr_aux.hip keep
 // their code: the PSF column pass of the panel path (half and full spectrum) and the pointwise filter of the simple path.
 // The mixed-radix site is the MIX_COLS_FILTER_CLS kind of fdr_mixed.hip.
-#include "fdr_fft_core.hpp"
-#include "fdr_kernels.hpp"
+#include "fdr_panel.hpp"
 
 namespace fdr {
 
-// thread groups of the panel column pass (T threads per panel, G panels per workgroup), as the Wiener pass of fdr_panel.hip
-template <int LOGM>
-struct ClsPanelGeom {
-    static constexpr int T = Steps<LOGM>::T;
-    static constexpr int G = T >= 512 ? 1 : (T >= 256 ? 2 : 4);
-    static constexpr int THREADS = T * G;
-};
-
-// The PSF column pass of the panel path (fft_cols_panel_fwd_filter_kernel of fdr_panel.hip) with the CLS quotient: forward
+// The PSF column pass of the panel path (fft_cols_panel_fwd_filter_kernel of fdr_panel_cols.hip) with the CLS quotient: forward
 // column FFT of every panel, in place, rows >= nvalid read as zero.  A value's row frequency is Core::out_index (the transform
 // leaves in last-step order; W is stored at that row), its column 4 p + lane (v < N/2 in the half spectrum, v < N in the full
 // one).  The packed DC / Nyquist column of the half spectrum (column 0 of panel 0) leaves as its filter slots
 // (packed_column_cls_slot) with b_0 for W0 and b_{N/2} for WN.  No minimum occupancy in the launch bounds: the quotient with its
 // table values needs more than 128 registers below LOGM 13, and this pass runs once per PSF.
 template <int LOGM>
-__global__ __launch_bounds__(ClsPanelGeom<LOGM>::THREADS) void fft_cols_panel_fwd_cls_kernel(
+__global__ __launch_bounds__(PanelGeom<LOGM>::THREADS) void fft_cols_panel_fwd_cls_kernel(
     float2* __restrict__ data, const float2* __restrict__ tw_fwd, const size_t pstride, const int npanels, const int nvalid, const float K,
     const int packed0, const double* __restrict__ lap, const int N, const double gamma) {
     using St = Steps<LOGM>;
-    using Geo = ClsPanelGeom<LOGM>;
+    using Geo = PanelGeom<LOGM>;
     constexpr int G = Geo::G, T = St::T;
     using Core = FftCore<LOGM, 4, 2, PolicyFast>;
     __shared__ float2 lds[G * 2 * St::BUF];
@@ -43,15 +34,7 @@ __global__ __launch_bounds__(ClsPanelGeom<LOGM>::THREADS) void fft_cols_panel_fw
     typename Core::Bases bases;
     Core::init_bases(bases, tw_fwd, tid);
     float2 v[4][8];
-#pragma unroll
-    for (int u = 0; u < Core::NU0; ++u)
-#pragma unroll
-        for (int q = 0; q < Core::RHO0; ++q) {
-            const int s = u * Core::RHO0 + q;
-            const int m = Core::in_index(tid, u, q);
-            if (m < nvalid) load4(pbase + (size_t)m * 4, v[0][s], v[1][s], v[2][s], v[3][s]);
-            else v[0][s] = v[1][s] = v[2][s] = v[3][s] = make_float2(0.f, 0.f);
-        }
+    FDR_PANEL_LOAD_VALID(Core, pbase, tid, nvalid, v)
     Core::template run<0, false>(v, lds + g * 2 * St::BUF, tw_fwd, bases, tid);
     // opaque copy of tid: the row indices below are recomputed from it instead of living across the transform (at LOGM 13 the
     // kernel is held to 128 registers by its 1024 threads and would spill them)
@@ -98,7 +81,9 @@ __global__ __launch_bounds__(ClsPanelGeom<LOGM>::THREADS) void fft_cols_panel_fw
             v[2][s] = cls_filter_fast(v[2][s], K, cls_reg(lap, St::L, m, v0 + 2, gamma));
             v[3][s] = cls_filter_fast(v[3][s], K, cls_reg(lap, St::L, m, v0 + 3, gamma));
         }
-    if (active) {  // row m of the panel at m * 4 (natural order), as panel_store_out of fdr_panel.hip
+    // row m of the panel at m * 4 (natural order).  Not panel_store_out (fdr_panel.hpp): its address form gives all eleven kernels
+    // other registers and schedules (tools/kernel_diff.py)
+    if (active) {
 #pragma unroll
         for (int u = 0; u < Core::NUL; ++u)
 #pragma unroll
@@ -111,7 +96,7 @@ __global__ __launch_bounds__(ClsPanelGeom<LOGM>::THREADS) void fft_cols_panel_fw
 
 template <int LOGM>
 static hipError_t launch_cols_panel_cls_t(const ColArgs& a, const double* lap, double gamma, const float2* tw, hipStream_t s) {
-    using Geo = ClsPanelGeom<LOGM>;
+    using Geo = PanelGeom<LOGM>;
     const int npanels = a.npanels > 0 ? a.npanels : a.N / 4;
     const int ntiles = (npanels + Geo::G - 1) / Geo::G;
     hipLaunchKernelGGL((fft_cols_panel_fwd_cls_kernel<LOGM>), dim3(ntiles), dim3(Geo::THREADS), 0, s, a.data, tw, a.pstride, npanels, a.nvalid, a.K,
@@ -121,20 +106,8 @@ static hipError_t launch_cols_panel_cls_t(const ColArgs& a, const double* lap, d
 
 hipError_t launch_cols_panel_cls(int logm, const ColArgs& a, const double* lap, double gamma, const float2* tw_fwd, hipStream_t s) {
     if (lap == nullptr) return hipErrorInvalidValue;
-    switch (logm) {
-        case 3: return launch_cols_panel_cls_t<3>(a, lap, gamma, tw_fwd, s);
-        case 4: return launch_cols_panel_cls_t<4>(a, lap, gamma, tw_fwd, s);
-        case 5: return launch_cols_panel_cls_t<5>(a, lap, gamma, tw_fwd, s);
-        case 6: return launch_cols_panel_cls_t<6>(a, lap, gamma, tw_fwd, s);
-        case 7: return launch_cols_panel_cls_t<7>(a, lap, gamma, tw_fwd, s);
-        case 8: return launch_cols_panel_cls_t<8>(a, lap, gamma, tw_fwd, s);
-        case 9: return launch_cols_panel_cls_t<9>(a, lap, gamma, tw_fwd, s);
-        case 10: return launch_cols_panel_cls_t<10>(a, lap, gamma, tw_fwd, s);
-        case 11: return launch_cols_panel_cls_t<11>(a, lap, gamma, tw_fwd, s);
-        case 12: return launch_cols_panel_cls_t<12>(a, lap, gamma, tw_fwd, s);
-        case 13: return launch_cols_panel_cls_t<13>(a, lap, gamma, tw_fwd, s);
-        default: return hipErrorInvalidValue;
-    }
+    FDR_DISPATCH_LOG(logm, launch_cols_panel_cls_t<LG>(a, lap, gamma, tw_fwd, s));
+    return hipErrorInvalidValue;
 }
 
 // ---- simple path: the CLS quotient on the row-major M x N spectrum (make_filter_fast_kernel of fdr_aux.hip); element i is bin

@@ -8,7 +8,7 @@
 // below places those workgroups on the same XCD (blocks b, b+8, b+16.. share an L2).  This only
 // affects speed, and it is not enough: with >= 128 KB of lines in flight per CU the sharing cannot
 // be served from a 4 MiB L2, which is why the fast mode moved to the panel-major layout of
-// fdr_panel.hip.  These kernels remain the parity-mode column passes (reference pass order) and the
+// fdr_panel.hpp.  These kernels remain the parity-mode column passes (reference pass order) and the
 // column half of fdr_fft2d_c2c in both modes.
 #include "fdr_fft_core.hpp"
 #include "fdr_kernels.hpp"
@@ -199,38 +199,14 @@ template <int LOGM>
 static int cols_partials(int N) { return (N + ColGeom<LOGM>::COLS - 1) / ColGeom<LOGM>::COLS; }
 
 int cols_minmax_partials(int logm, int N) {
-    switch (logm) {
-        case 3: return cols_partials<3>(N);
-        case 4: return cols_partials<4>(N);
-        case 5: return cols_partials<5>(N);
-        case 6: return cols_partials<6>(N);
-        case 7: return cols_partials<7>(N);
-        case 8: return cols_partials<8>(N);
-        case 9: return cols_partials<9>(N);
-        case 10: return cols_partials<10>(N);
-        case 11: return cols_partials<11>(N);
-        case 12: return cols_partials<12>(N);
-        case 13: return cols_partials<13>(N);
-        default: return 0;
-    }
+    FDR_DISPATCH_LOG(logm, cols_partials<LG>(N));
+    return 0;
 }
 
 hipError_t launch_cols(int logm, int mode, ColKind kind, const ColArgs& a, const float2* twf, const float2* twi,
                        hipStream_t s) {
-    switch (logm) {
-        case 3: return launch_cols_kind<3>(mode, kind, a, twf, twi, s);
-        case 4: return launch_cols_kind<4>(mode, kind, a, twf, twi, s);
-        case 5: return launch_cols_kind<5>(mode, kind, a, twf, twi, s);
-        case 6: return launch_cols_kind<6>(mode, kind, a, twf, twi, s);
-        case 7: return launch_cols_kind<7>(mode, kind, a, twf, twi, s);
-        case 8: return launch_cols_kind<8>(mode, kind, a, twf, twi, s);
-        case 9: return launch_cols_kind<9>(mode, kind, a, twf, twi, s);
-        case 10: return launch_cols_kind<10>(mode, kind, a, twf, twi, s);
-        case 11: return launch_cols_kind<11>(mode, kind, a, twf, twi, s);
-        case 12: return launch_cols_kind<12>(mode, kind, a, twf, twi, s);
-        case 13: return launch_cols_kind<13>(mode, kind, a, twf, twi, s);
-        default: return hipErrorInvalidValue;
-    }
+    FDR_DISPATCH_LOG(logm, launch_cols_kind<LG>(mode, kind, a, twf, twi, s));
+    return hipErrorInvalidValue;
 }
 
 }  // namespace fdr

@@ -40,7 +40,7 @@ __device__ __forceinline__ void fdr_jitter(unsigned salt) {
 
 // Stamps inside a transform (timing-only debug builds, -DFDR_DEBUG_STAMPS): shader-clock counter of thread 0 after every
 // butterfly step and every exchange of the column pass's core (16 values x 4 columns per thread), slots 8.. (forward) and
-// 16.. (inverse) of the workgroup's 32-entry record; see fdr_panel.hip.  The values are pinned at each stamp.
+// 16.. (inverse) of the workgroup's 32-entry record; see fdr_panel_cols.hip.  The values are pinned at each stamp.
 #ifdef FDR_DEBUG_STAMPS
 static __device__ unsigned long long fdr_dbg_stamps[8192 * 32];
 #define FDR_CORE_STAMP(cond, slot, v)                                                                                    \

@@ -20,7 +20,8 @@ enum RowOut {
     ROW_OUT_RL_UPDATE = 6,    // max(u g, 0) to `out`; u read from src_real (row stride src_stride; may be `out` itself)
     // free-boundary Richardson-Lucy (fdr_rlfree.hip): max(u wgt g, 0) to `out`; u from src_real as ROW_OUT_RL_UPDATE, wgt from
     // src_real2 (same row stride)
-    ROW_OUT_RL_UPDATE_W = 7
+    ROW_OUT_RL_UPDATE_W = 7,
+    ROW_OUT_LAST = ROW_OUT_RL_UPDATE_W
 };
 // the guard of the Richardson-Lucy ratio (FDR_RL_TAU of fdr.h): a blurred estimate at or below it gives r = 0
 constexpr float kRlTau = 1e-7f;
@@ -119,6 +120,24 @@ struct ColArgs {
     int panel_c;      // launch_cols (parity operator): data / filt panel-major (pstride), dst_real panel-major with stride 4 M floats
 };
 
+// `return expr;` with LG = the value of `var` as a constant, for the transform lengths the kernels are instantiated for
+// (log2 = 3..13); falls through for any other value
+#define FDR_DISPATCH_LOG(var, expr)                                                     \
+    switch (var) {                                                                      \
+        case 3: { constexpr int LG = 3; return expr; }                                  \
+        case 4: { constexpr int LG = 4; return expr; }                                  \
+        case 5: { constexpr int LG = 5; return expr; }                                  \
+        case 6: { constexpr int LG = 6; return expr; }                                  \
+        case 7: { constexpr int LG = 7; return expr; }                                  \
+        case 8: { constexpr int LG = 8; return expr; }                                  \
+        case 9: { constexpr int LG = 9; return expr; }                                  \
+        case 10: { constexpr int LG = 10; return expr; }                                \
+        case 11: { constexpr int LG = 11; return expr; }                                \
+        case 12: { constexpr int LG = 12; return expr; }                                \
+        case 13: { constexpr int LG = 13; return expr; }                                \
+        default: break;                                                                 \
+    }
+
 // launchers (fdr_rows.hip / fdr_cols.hip); logl = log2 of the transform length, 3..13
 // tw: parity mode -> table of the requested direction; fast mode -> the forward table (inverse = conjugate)
 hipError_t launch_rows(int logl, int mode, RowIn in, RowOut out, bool inverse, const RowArgs& a, const float2* tw,
@@ -126,7 +145,8 @@ hipError_t launch_rows(int logl, int mode, RowIn in, RowOut out, bool inverse, c
 hipError_t launch_cols(int logm, int mode, ColKind kind, const ColArgs& a, const float2* tw_fwd, const float2* tw_inv,
                        hipStream_t s);
 
-// fast-mode passes on the panel-major intermediate (fdr_panel.hip); tw_fwd = forward table
+// fast-mode passes on the panel-major intermediate (fdr_panel_rows.hip, fdr_panel_cols.hip; layout in fdr_panel.hpp);
+// tw_fwd = forward table
 // rows4: (ROW_IN_REAL -> ROW_OUT_COMPLEX[panel]) forward, (ROW_IN_COMPLEX[panel] -> ROW_OUT_REAL_MINMAX) inverse
 hipError_t launch_rows4(int logl, RowIn in, RowOut out, const RowArgs& a, const float2* tw_fwd, hipStream_t s);
 // min/max partials pass C' writes per image when `nimg` images share a launch

@@ -5,26 +5,17 @@
 //     blur^T(y) = window( IDFT2( conj(H) . DFT2(pad(y)) ) )
 //     RL:  u = max(d, 0);  n times:  c = blur(u);  r = c > tau ? max(d, 0) / c : 0;  u = max(u . blur^T(r), 0)
 //
-// A blur is passes A, B' and C of the Wiener operator (fdr_panel.hip) with the operator tables in place of W: B' runs unchanged
+// A blur is passes A, B' and C of the Wiener operator (fdr_panel_*.hip) with the operator tables in place of W: B' runs unchanged
 // on H / (M N) or conj(H) / (M N), and the inverse row pass ends in one of the operator kinds of rows4_rl_value (blur, ratio,
 // update), cropped to the window.  Two kernels live here: the PSF column pass that writes both tables in one launch, and the
 // initial estimate.  1 / (M N) is a power of two, so folding it into the tables is exact.
-#include "fdr_fft_core.hpp"
-#include "fdr_kernels.hpp"
+#include "fdr_panel.hpp"
 
 namespace fdr {
 
-// thread groups of the panel column pass (T threads per panel, G panels per workgroup), as the Wiener pass of fdr_panel.hip
-template <int LOGM>
-struct OpPanelGeom {
-    static constexpr int T = Steps<LOGM>::T;
-    static constexpr int G = T >= 512 ? 1 : (T >= 256 ? 2 : 4);
-    static constexpr int THREADS = T * G;
-};
-
 // Filter slot S[k] of the packed DC / Nyquist column (column 0 of panel 0 carries C = H0 + i HN, H0 = H[., 0], HN = H[., N/2],
 // both Hermitian along the column) for the operator H itself, scaled: the layout of packed_column_filter_slot, which pass B'
-// reads (packed_column_filter of fdr_panel.hip):
+// reads (packed_column_filter of fdr_panel_cols.hip):
 //   S[k] = H0[k] (0 < k < M/2),  S[k] = HN[M-k] (M/2 < k < M),  S[0] = (H0[0], HN[0]),  S[M/2] = (H0[M/2], HN[M/2])
 // ck = C[k], cmk = C[M - k]; evaluated at j = min(k, M - k).  The conj(H) slot is its conjugate, except at 0 and M/2 (real parts).
 __device__ __forceinline__ float2 packed_column_operator_slot(float2 ck, float2 cmk, int k, int M, float scale) {
@@ -37,16 +28,16 @@ __device__ __forceinline__ float2 packed_column_operator_slot(float2 ck, float2 
     return make_float2(hnr * scale, hni * scale);
 }
 
-// The PSF column pass of the panel path (fft_cols_panel_fwd_filter_kernel of fdr_panel.hip) for the operator tables: forward
+// The PSF column pass of the panel path (fft_cols_panel_fwd_filter_kernel of fdr_panel_cols.hip) for the operator tables: forward
 // column FFT of every panel of `hdata` (the PSF's row spectra; rows >= nvalid read as zero), then H * scale back into `hdata`
 // and conj(H) * scale into `cdata`, row m of a panel at m * 4 (natural order).  The packed column leaves as its slots
 // (packed_column_operator_slot).  No minimum occupancy in the launch bounds: this pass runs once per PSF.
 template <int LOGM>
-__global__ __launch_bounds__(OpPanelGeom<LOGM>::THREADS) void fft_cols_panel_fwd_operator_kernel(
+__global__ __launch_bounds__(PanelGeom<LOGM>::THREADS) void fft_cols_panel_fwd_operator_kernel(
     float2* __restrict__ hdata, float2* __restrict__ cdata, const float2* __restrict__ tw_fwd, const size_t pstride, const int npanels,
     const int nvalid, const float scale, const int packed0) {
     using St = Steps<LOGM>;
-    using Geo = OpPanelGeom<LOGM>;
+    using Geo = PanelGeom<LOGM>;
     constexpr int G = Geo::G, T = St::T;
     using Core = FftCore<LOGM, 4, 2, PolicyFast>;
     __shared__ float2 lds[G * 2 * St::BUF];
@@ -58,15 +49,7 @@ __global__ __launch_bounds__(OpPanelGeom<LOGM>::THREADS) void fft_cols_panel_fwd
     typename Core::Bases bases;
     Core::init_bases(bases, tw_fwd, tid);
     float2 v[4][8];
-#pragma unroll
-    for (int u = 0; u < Core::NU0; ++u)
-#pragma unroll
-        for (int q = 0; q < Core::RHO0; ++q) {
-            const int s = u * Core::RHO0 + q;
-            const int m = Core::in_index(tid, u, q);
-            if (m < nvalid) load4(hbase + (size_t)m * 4, v[0][s], v[1][s], v[2][s], v[3][s]);
-            else v[0][s] = v[1][s] = v[2][s] = v[3][s] = make_float2(0.f, 0.f);
-        }
+    FDR_PANEL_LOAD_VALID(Core, hbase, tid, nvalid, v)
     Core::template run<0, false>(v, lds + g * 2 * St::BUF, tw_fwd, bases, tid);
     const bool raw0 = packed0 && p == 0;  // uniform per thread group
     if (packed0 && blockIdx.x == 0) {     // uniform per workgroup: the packed column's slots need C[k] and C[M - k]
@@ -110,7 +93,7 @@ __global__ __launch_bounds__(OpPanelGeom<LOGM>::THREADS) void fft_cols_panel_fwd
 
 template <int LOGM>
 static hipError_t launch_cols_panel_operator_t(const ColArgs& a, float2* conj_out, const float2* tw, hipStream_t s) {
-    using Geo = OpPanelGeom<LOGM>;
+    using Geo = PanelGeom<LOGM>;
     const int npanels = a.npanels > 0 ? a.npanels : a.N / 4;
     const int ntiles = (npanels + Geo::G - 1) / Geo::G;
     const float scale = (float)(1.0 / ((double)(1 << LOGM) * a.N));  // a power of two: exact
@@ -121,20 +104,8 @@ static hipError_t launch_cols_panel_operator_t(const ColArgs& a, float2* conj_ou
 
 hipError_t launch_cols_panel_operator(int logm, const ColArgs& a, float2* conj_out, const float2* tw_fwd, hipStream_t s) {
     if (conj_out == nullptr || a.data == nullptr) return hipErrorInvalidValue;
-    switch (logm) {
-        case 3: return launch_cols_panel_operator_t<3>(a, conj_out, tw_fwd, s);
-        case 4: return launch_cols_panel_operator_t<4>(a, conj_out, tw_fwd, s);
-        case 5: return launch_cols_panel_operator_t<5>(a, conj_out, tw_fwd, s);
-        case 6: return launch_cols_panel_operator_t<6>(a, conj_out, tw_fwd, s);
-        case 7: return launch_cols_panel_operator_t<7>(a, conj_out, tw_fwd, s);
-        case 8: return launch_cols_panel_operator_t<8>(a, conj_out, tw_fwd, s);
-        case 9: return launch_cols_panel_operator_t<9>(a, conj_out, tw_fwd, s);
-        case 10: return launch_cols_panel_operator_t<10>(a, conj_out, tw_fwd, s);
-        case 11: return launch_cols_panel_operator_t<11>(a, conj_out, tw_fwd, s);
-        case 12: return launch_cols_panel_operator_t<12>(a, conj_out, tw_fwd, s);
-        case 13: return launch_cols_panel_operator_t<13>(a, conj_out, tw_fwd, s);
-        default: return hipErrorInvalidValue;
-    }
+    FDR_DISPATCH_LOG(logm, launch_cols_panel_operator_t<LG>(a, conj_out, tw_fwd, s));
+    return hipErrorInvalidValue;
 }
 
 // ---- the initial estimate u = max(d, 0) on the window (one row per blockIdx.y) ----

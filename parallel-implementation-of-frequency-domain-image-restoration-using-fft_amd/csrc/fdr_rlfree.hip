@@ -5,7 +5,7 @@
 //     dw = m max(d, 0);  wgt = alpha > sigma ? 1 / alpha : 0;  u = alpha > sigma ? sum(dw) / sum(m) : 0
 //     n times:  c = window(fullblur(u));  r = c > tau ? dw / c : 0;  u = max(u wgt fullblur^T(pad(r)), 0)
 //
-// The transforms are the operator passes of fdr_panel.hip (the weighted update is a kind of the inverse row pass there).  Here:
+// The transforms are the operator passes of fdr_panel_rows.hip (the weighted update is a kind of the inverse row pass there).  Here:
 // the setup pass (dw, W = m dense, and the two sums as per-workgroup double partials), their fixed-order fold, the start (wgt and
 // u from alpha in one pointwise pass) and the crop of the result.  No float atomics: every sum runs in a fixed order.
 #include "fdr_kernels.hpp"

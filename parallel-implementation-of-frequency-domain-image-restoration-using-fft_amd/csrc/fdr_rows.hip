@@ -137,38 +137,14 @@ template <int LOGL>
 static int rows_partials(int M) { return (M + RowGeom<LOGL>::G - 1) / RowGeom<LOGL>::G; }
 
 int rows_minmax_partials(int logl, int M) {
-    switch (logl) {
-        case 3: return rows_partials<3>(M);
-        case 4: return rows_partials<4>(M);
-        case 5: return rows_partials<5>(M);
-        case 6: return rows_partials<6>(M);
-        case 7: return rows_partials<7>(M);
-        case 8: return rows_partials<8>(M);
-        case 9: return rows_partials<9>(M);
-        case 10: return rows_partials<10>(M);
-        case 11: return rows_partials<11>(M);
-        case 12: return rows_partials<12>(M);
-        case 13: return rows_partials<13>(M);
-        default: return 0;
-    }
+    FDR_DISPATCH_LOG(logl, rows_partials<LG>(M));
+    return 0;
 }
 
 hipError_t launch_rows(int logl, int mode, RowIn in, RowOut out, bool inverse, const RowArgs& a, const float2* tw,
                        hipStream_t s) {
-    switch (logl) {
-        case 3: return launch_rows_mode<3>(mode, in, out, inverse, a, tw, s);
-        case 4: return launch_rows_mode<4>(mode, in, out, inverse, a, tw, s);
-        case 5: return launch_rows_mode<5>(mode, in, out, inverse, a, tw, s);
-        case 6: return launch_rows_mode<6>(mode, in, out, inverse, a, tw, s);
-        case 7: return launch_rows_mode<7>(mode, in, out, inverse, a, tw, s);
-        case 8: return launch_rows_mode<8>(mode, in, out, inverse, a, tw, s);
-        case 9: return launch_rows_mode<9>(mode, in, out, inverse, a, tw, s);
-        case 10: return launch_rows_mode<10>(mode, in, out, inverse, a, tw, s);
-        case 11: return launch_rows_mode<11>(mode, in, out, inverse, a, tw, s);
-        case 12: return launch_rows_mode<12>(mode, in, out, inverse, a, tw, s);
-        case 13: return launch_rows_mode<13>(mode, in, out, inverse, a, tw, s);
-        default: return hipErrorInvalidValue;
-    }
+    FDR_DISPATCH_LOG(logl, launch_rows_mode<LG>(mode, in, out, inverse, a, tw, s));
+    return hipErrorInvalidValue;
 }
 
 }  // namespace fdr

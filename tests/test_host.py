@@ -225,7 +225,7 @@ def test_traffic_json_is_tied_to_the_kernel_sources(fdr, tmp_path):
     for n in sorted(os.listdir(d)):
         if n.endswith((".hip", ".hpp", ".h")):
             h.update(n.encode() + b"\0")
-            h.update(open(os.path.join(d, n), "rb").read() + (b" " if n == "fdr_panel.hip" else b""))
+            h.update(open(os.path.join(d, n), "rb").read() + (b" " if n == "fdr_panel_rows.hip" else b""))
     assert h.hexdigest()[:16] != fp
 
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Compiles one .hip file of the package with -Rpass-analysis=kernel-resource-usage and prints one line per kernel:
-registers, spills, scratch, occupancy, LDS.  usage: tools/kernel_resources.py csrc/fdr_panel.hip [filter] [extra flags...]"""
+registers, spills, scratch, occupancy, LDS.  usage: tools/kernel_resources.py csrc/fdr_panel_rows.hip [filter] [extra flags...]"""
 import os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "parallel-implementation-of-frequency-domain-image-restoration-using-fft_amd")

@@ -117,9 +117,11 @@ def main():
         default_images = 4 if size <= 4096 else 2  # images per launch of bench.py's default grouping (what the PMC runs used)
         for kname, vals in fe.items():
             for key, pname in PASS_OF.items():
-                if key.startswith("fft_rows4_inv_"):  # last template argument: 0 raw plane (C'), 1 min/max only (C1), 2 normalised (C2)
-                    if ", 1>(" in kname: pname = "C1 rows: IFFT+minmax"
-                    elif ", 2>(" in kname: pname = "C2 rows: IFFT+normalize+crop"
+                if key.startswith("fft_rows4_inv_"):
+                    # last template argument, the RowOut kind: ROW_OUT_REAL_MINMAX = 1 raw plane (C'), ROW_OUT_MINMAX_ONLY = 2 (C1),
+                    # ROW_OUT_NORMALIZED = 3 (C2); collections before the kind was typed spell them `int` 0, 1, 2
+                    if "(fdr::RowOut)2>(" in kname or ", 1>(" in kname: pname = "C1 rows: IFFT+minmax"
+                    elif "(fdr::RowOut)3>(" in kname or ", 2>(" in kname: pname = "C2 rows: IFFT+normalize+crop"
                 if len(vals) >= 2 and key in kname and ("<%d>" % lg in kname or "<%d," % lg in kname or key == "normalize_kernel"):  # (single dispatches: the PSF's own passes)
                     rd = statistics.median(vals) * round(fetch_factor) * 1024.0
                     wv = [v for k, v in wr.items() if k == kname]
