@@ -53,12 +53,22 @@ MixColArgs mixed_col_args(const fdr_plan* p) {
     a.len = p->mix_col; a.N = p->N; a.logP = p->mix_logP; a.pstride = p->pstride;
     return a;
 }
+RowArgs panel_row_args(const fdr_plan* p) {
+    RowArgs a{};
+    a.M = p->M; a.pstride = p->pstride; a.half = p->path == PATH_FAST_HALF ? 1 : 0; a.num_cu = p->num_cu;
+    return a;
+}
+ColArgs panel_col_args(const fdr_plan* p) {
+    ColArgs a{};
+    a.N = p->N; a.num_cu = p->num_cu; a.pstride = p->pstride; a.npanels = p->npanels; a.packed0 = p->path == PATH_FAST_HALF ? 1 : 0;
+    return a;
+}
 
 int dft2d_dev(fdr_plan* p, float2* d, float2* work2, bool inverse, hipStream_t s) {
     const float2* twr = inverse ? p->tw_row_i : p->tw_row_f;
     const float2* twc = inverse ? p->tw_col_i : p->tw_col_f;
-    if (p->mixed) return mixed_fft2d_dev(p, d, p->work, inverse, s);
-    if (p->simple) {  // the reference's own sequence: rows, transpose, rows, transpose (fft/fft_serial.cpp:113-139)
+    if (p->path == PATH_MIXED) return mixed_fft2d_dev(p, d, p->slots[0].work, inverse, s);
+    if (p->path == PATH_SIMPLE) {  // the reference's own sequence: rows, transpose, rows, transpose (fft/fft_serial.cpp:113-139)
         // one row pass over `rows` rows of length L held in `buf`, `tmp` free: radix-2 for powers of two, else the naive
         // DFT (transform_row_inplace, :100-101), which runs out of place and is copied back
         auto row_pass = [&](float2* buf, float2* tmp, int rows, int L, int logl, const float2* tw, const float2* twf, const float2* twi,
@@ -143,7 +153,7 @@ int fdr_fft2d_c2c_dev(fdr_plan* p, float* d_data, int inverse, void* stream) {
     const int rc = check_plan(p, fn, NEED_PLAN);
     if (rc != FDR_OK) return rc;
     FDR_HIP(hipSetDevice(p->device));
-    return dft2d_dev(p, reinterpret_cast<float2*>(d_data), p->work2, inverse != 0, (hipStream_t)stream);
+    return dft2d_dev(p, reinterpret_cast<float2*>(d_data), p->slots[0].work2, inverse != 0, (hipStream_t)stream);
 }
 
 int fdr_fft2d_c2c(fdr_plan* p, float* data_host, int inverse) {
@@ -153,13 +163,13 @@ int fdr_fft2d_c2c(fdr_plan* p, float* data_host, int inverse) {
     if (rc != FDR_OK) return rc;
     FDR_HIP(hipSetDevice(p->device));
     const size_t elems = (size_t)p->M * p->N, bytes = elems * sizeof(float2);
-    // p->work is free between operator calls and serves as the staging buffer -- unless the plan keeps only the
+    // slot 0's spectrum is free between operator calls and serves as the staging buffer -- unless the plan keeps only the
     // half spectrum there (fast panel mode: about M*N/2 elements), where a full-size buffer is allocated for the call
-    float2* buf = p->work;
-    const bool own = p->ws_elems < elems || p->mixed;  // (a mixed plan's transform uses p->work as its scratch)
+    float2* buf = p->slots[0].work;
+    const bool own = p->ws_elems < elems || p->path == PATH_MIXED;  // (a mixed plan's transform uses that spectrum as its scratch)
     if (own) FDR_HIP(hipMalloc((void**)&buf, bytes));
     hipError_t e = hipMemcpy(buf, data_host, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) rc = dft2d_dev(p, buf, p->work2, inverse != 0, nullptr);
+    if (e == hipSuccess) rc = dft2d_dev(p, buf, p->slots[0].work2, inverse != 0, nullptr);
     if (e == hipSuccess && rc == FDR_OK) e = hipMemcpy(data_host, buf, bytes, hipMemcpyDeviceToHost);
     if (own) (void)hipFree(buf);
     if (rc != FDR_OK) return rc;
@@ -374,8 +384,8 @@ int fdr_slab_minmax_dev(fdr_plan* p, const float* d_real, int rows, int ld, int 
     const long long need = (long long)((ld + 255) / 256) * rows;
     if (need > p->mm_part_cap) return fail(FDR_ERR_ARG, "fdr_slab_minmax_dev: slab larger than the plan's M x N");
     int n_part = 0;
-    FDR_HIP(launch_minmax_real(d_real, rows, ld, mm_rows, mm_cols, p->mm_part, &n_part, (hipStream_t)stream));
-    FDR_HIP(launch_reduce_minmax(p->mm_part, n_part, d_mm, (hipStream_t)stream));
+    FDR_HIP(launch_minmax_real(d_real, rows, ld, mm_rows, mm_cols, p->slots[0].mm_part, &n_part, (hipStream_t)stream));
+    FDR_HIP(launch_reduce_minmax(p->slots[0].mm_part, n_part, d_mm, (hipStream_t)stream));
     return FDR_OK;
 }
 

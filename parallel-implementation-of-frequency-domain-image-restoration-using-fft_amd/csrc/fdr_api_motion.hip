@@ -69,10 +69,10 @@ int ensure_motion_table(fdr_plan* p, const char* fn, const MotionArgs& a) {
 // c (scaled by 1 / (M N) already) in the real parts of mo_plane, and sum |x| in mo_part[motion_pad_partials]
 int motion_cepstrum_plane(fdr_plan* p, const float* d_img, int rows, int cols, int stride, hipStream_t s) {
     FDR_HIP(launch_motion_window(d_img, rows, cols, stride, p->mo_hann, p->mo_plane, p->M, p->N, p->mo_part, s));
-    int rc = dft2d_dev(p, p->mo_plane, p->work2, false, s);
+    int rc = dft2d_dev(p, p->mo_plane, p->slots[0].work2, false, s);
     if (rc != FDR_OK) return rc;
     FDR_HIP(launch_motion_log(p->mo_plane, p->M, p->N, p->mo_part + motion_pad_partials(p->M, p->N), s));
-    return dft2d_dev(p, p->mo_plane, p->work2, true, s);
+    return dft2d_dev(p, p->mo_plane, p->slots[0].work2, true, s);
 }
 
 int cepstrum_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, int cols, int stride, float* d_out, hipStream_t s) {

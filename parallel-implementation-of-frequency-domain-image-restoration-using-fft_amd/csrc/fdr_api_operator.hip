@@ -39,16 +39,15 @@ int set_operator_psf_impl(fdr_plan* p, const float* d_psf, int prows, int pcols,
     const int nvalid = (prows + 3) & ~3;  // <= M (M is a multiple of 8 on this path)
     {
         ScopedPass t(p, s, kPassOpRowsPsf);
-        RowArgs ra{};
+        RowArgs ra = panel_row_args(p);
         ra.src_real = d_psf; ra.src_rows = prows; ra.src_cols = pcols; ra.src_stride = pstride;
-        ra.dst_c = p->op_h; ra.M = nvalid; ra.pstride = p->pstride; ra.half = 1; ra.num_cu = p->num_cu;
+        ra.dst_c = p->op_h; ra.M = nvalid;
         FDR_HIP(launch_rows4(p->logN, ROW_IN_REAL, ROW_OUT_COMPLEX, ra, p->tw_row_f, s));
     }
     {
         ScopedPass t(p, s, kPassOpCols);
-        ColArgs ca{};
-        ca.data = p->op_h; ca.N = p->N; ca.num_cu = p->num_cu; ca.pstride = p->pstride; ca.npanels = p->npanels;
-        ca.nvalid = nvalid; ca.packed0 = 1;
+        ColArgs ca = panel_col_args(p);
+        ca.data = p->op_h; ca.nvalid = nvalid;
         FDR_HIP(launch_cols_panel_operator(p->logM, ca, p->op_c, p->tw_col_f, s));
     }
     p->have_op = true;
@@ -59,19 +58,18 @@ int set_operator_psf_impl(fdr_plan* p, const float* d_psf, int prows, int pcols,
 // pass A: the window of x (zero elsewhere) -> the half spectrum of slot 0
 int op_rows_fwd(fdr_plan* p, const float* x, int rows, int cols, int stride, hipStream_t s) {
     ScopedPass t(p, s, kPassOpRowsFwd);
-    RowArgs a{};
+    RowArgs a = panel_row_args(p);
     a.src_real = x; a.src_rows = rows; a.src_cols = cols; a.src_stride = stride;
-    a.dst_c = p->work; a.M = p->M; a.pstride = p->pstride; a.half = 1; a.num_cu = p->num_cu;
+    a.dst_c = p->slots[0].work;
     FDR_HIP(launch_rows4(p->logN, ROW_IN_REAL, ROW_OUT_COMPLEX, a, p->tw_row_f, s));
     return FDR_OK;
 }
 // pass B', unchanged, with `table` as its filter
 int op_cols_table(fdr_plan* p, const float2* table, const char* name, hipStream_t s) {
     ScopedPass t(p, s, name);
-    ColArgs c{};
-    c.data = p->work; c.filt = table; c.N = p->N; c.num_cu = p->num_cu;
-    c.pstride = p->pstride; c.npanels = p->npanels; c.packed0 = 1;
-    c.batch.nimg = 1; c.batch.data[0] = p->work;
+    ColArgs c = panel_col_args(p);
+    c.data = p->slots[0].work; c.filt = table;
+    c.batch.nimg = 1; c.batch.data[0] = c.data;
     FDR_HIP(launch_cols_panel(p->logM, COL_FUSED, c, p->tw_col_f, s));
     return FDR_OK;
 }
@@ -79,8 +77,8 @@ int op_cols_table(fdr_plan* p, const float2* table, const char* name, hipStream_
 int op_rows_inv(fdr_plan* p, RowOut kind, const char* name, const float* src, int src_stride, float* out, int out_stride, int rows,
                 int cols, hipStream_t s) {
     ScopedPass t(p, s, name);
-    RowArgs a{};
-    a.src_c = p->work; a.M = p->M; a.pstride = p->pstride; a.half = 1; a.num_cu = p->num_cu;
+    RowArgs a = panel_row_args(p);
+    a.src_c = p->slots[0].work;
     a.src_real = src; a.src_stride = src_stride;
     a.out = out; a.out_rows = rows; a.out_cols = cols; a.out_stride = out_stride;
     FDR_HIP(launch_rows4(p->logN, ROW_IN_COMPLEX, kind, a, p->tw_row_f, s));
@@ -91,16 +89,17 @@ int op_rows_inv(fdr_plan* p, RowOut kind, const char* name, const float* src, in
 int normalize_window(fdr_plan* p, const char* fn, const char* name, const float* fin, int fs, int rows, int cols, int norm_area, float* d_out,
                      int out_stride, hipStream_t s) {
     ScopedPass t(p, s, name);
+    const fdr_plan::Slot& w = p->slots[0];
     int n_part = 0;
-    FDR_HIP(launch_minmax_real(fin, rows, fs, rows, cols, p->mm_part, &n_part, s));
+    FDR_HIP(launch_minmax_real(fin, rows, fs, rows, cols, w.mm_part, &n_part, s));
     if (norm_area == FDR_NORM_PADDED && (rows < p->M || cols < p->N)) {
         if (n_part + 1 > p->mm_part_cap) return fail(FDR_ERR_STATE, std::string(fn) + ": min/max partial count out of range");
-        FDR_HIP(hipMemsetAsync(p->mm_part + n_part, 0, sizeof(float2), s));  // (0.f, 0.f)
+        FDR_HIP(hipMemsetAsync(w.mm_part + n_part, 0, sizeof(float2), s));  // (0.f, 0.f)
         ++n_part;
     }
     if (n_part <= 0 || n_part > p->mm_part_cap) return fail(FDR_ERR_STATE, std::string(fn) + ": min/max partial count out of range");
-    FDR_HIP(launch_reduce_minmax(p->mm_part, n_part, p->mm, s));
-    FDR_HIP(launch_normalize(fin, fs, nullptr, 0, p->mm, d_out, rows, cols, out_stride, s));
+    FDR_HIP(launch_reduce_minmax(w.mm_part, n_part, w.mm, s));
+    FDR_HIP(launch_normalize(fin, fs, nullptr, 0, w.mm, d_out, rows, cols, out_stride, s));
     return FDR_OK;
 }
 
@@ -121,11 +120,6 @@ int blur_window_dev(fdr_plan* p, const float* d_img, int rows, int cols, int str
 }  // namespace fdr
 
 namespace {
-
-
-int blur_dev_impl(fdr_plan* p, const float* d_img, int rows, int cols, int stride, float* d_out, int out_stride, int adjoint, hipStream_t s) {
-    return blur_window_dev(p, d_img, rows, cols, stride, d_out, out_stride, rows, cols, adjoint, s);
-}
 
 // [lo, hi) of the elements a rows x cols window with row stride `stride` spans
 bool windows_overlap(const float* a, int a_stride, const float* b, int b_stride, int rows, int cols) {
@@ -155,9 +149,9 @@ int rl_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, int c
                 int norm_area, hipStream_t s) {
     int rc = FDR_OK;
     const bool norm = norm_area != FDR_NORM_NONE;
-    float* r = p->raw;
+    float* r = p->slots[0].raw;
     const int rs = cols;
-    float* fin = norm ? p->raw : d_out;  // where the final estimate is written
+    float* fin = norm ? r : d_out;  // where the final estimate is written
     const int fs = norm ? rs : out_stride;
     {
         ScopedPass t(p, s, kPassRlInit);
@@ -200,7 +194,7 @@ int fdr_blur_f32_dev(fdr_plan* p, const float* d_img, int rows, int cols, int st
     const int rc = check_window(p, fn, NEED_OPERATOR_PSF, rows, cols, stride, out_stride);
     if (rc != FDR_OK) return rc;
     FDR_HIP(hipSetDevice(p->device));
-    return blur_dev_impl(p, d_img, rows, cols, stride, d_out, out_stride, adjoint, (hipStream_t)stream);
+    return blur_window_dev(p, d_img, rows, cols, stride, d_out, out_stride, rows, cols, adjoint, (hipStream_t)stream);
 }
 
 int fdr_blur_f32(fdr_plan* p, const float* img_host, int rows, int cols, int stride, float* out_host, int out_stride, int adjoint) {
@@ -210,7 +204,7 @@ int fdr_blur_f32(fdr_plan* p, const float* img_host, int rows, int cols, int str
     if (rc != FDR_OK) return rc;
     FDR_HIP(hipSetDevice(p->device));
     return host_image_call(p, fn, img_host, rows, cols, stride, out_host, rows, cols, out_stride, [&](const float* d_in, float* d_out) {
-        return blur_dev_impl(p, d_in, rows, cols, cols, d_out, cols, adjoint, nullptr);
+        return blur_window_dev(p, d_in, rows, cols, cols, d_out, cols, rows, cols, adjoint, nullptr);
     });
 }
 

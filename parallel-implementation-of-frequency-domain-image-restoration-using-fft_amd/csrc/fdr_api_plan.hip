@@ -97,15 +97,15 @@ void resolve_phases(fdr_plan* p) {
 int check_plan(const fdr_plan* p, const char* fn, PlanNeed need) {
     if (p->tables_only) return fail(FDR_ERR_STATE, std::string(fn) + ": plan was created with FDR_FLAG_TABLES_ONLY (slab primitives only)");
     if (need == NEED_FILTER && !p->have_psf) return fail(FDR_ERR_STATE, std::string(fn) + ": no PSF set on this plan (call fdr_set_psf* first)");
-    if ((need == NEED_OPERATOR || need == NEED_OPERATOR_PSF) &&
-        (p->mode != FDR_MODE_FAST || !p->panel || !p->half || p->mixed || p->logM < 3 || p->logM > kMaxLdsLog || p->logN < 5 ||
-         p->logN > kMaxLdsLog))
+    // (layout_radix2 gives PATH_FAST_HALF only to fast mode with 8 <= M, N <= 8192, both powers of two, and N >= 32: the
+    // ranges of the message follow from the path)
+    if ((need == NEED_OPERATOR || need == NEED_OPERATOR_PSF) && p->path != PATH_FAST_HALF)
         return fail(FDR_ERR_ARG, std::string(fn) + ": needs a FDR_MODE_FAST plan on the half-spectrum panel path (M, N powers of two, "
                                                    "8 <= M <= 8192, 32 <= N <= 8192, neither FDR_FLAG_SIMPLE_PATH nor FDR_FLAG_FULL_SPECTRUM)");
     if (need == NEED_OPERATOR_PSF && !p->have_op)
         return fail(FDR_ERR_STATE, std::string(fn) + ": no operator PSF set on this plan (call fdr_set_operator_psf* first)");
     if (need == NEED_MOTION && (p->mode != FDR_MODE_FAST || p->generic || p->M < 32 || p->N < 32 || p->M > kMixMaxLen || p->N > kMixMaxLen ||
-                                !(p->mixed || (fdr_is_pow2(p->M) && fdr_is_pow2(p->N)))))
+                                !(p->path == PATH_MIXED || (fdr_is_pow2(p->M) && fdr_is_pow2(p->N)))))
         return fail(FDR_ERR_ARG, std::string(fn) + ": needs a FDR_MODE_FAST plan, M and N powers of two (or 2^a 3^b 5^c with "
                                                    "FDR_FLAG_MIXED_RADIX), 32 <= M, N <= 8192");
     return FDR_OK;
@@ -179,7 +179,7 @@ int alloc_slot(const fdr_plan* p, fdr_plan::Slot& w) {
     const bool ws = !p->tables_only;
     if ((ws && hipMalloc((void**)&w.work, p->ws_elems * sizeof(float2)) != hipSuccess) ||
         (ws && hipMalloc((void**)&w.raw, (size_t)p->M * p->N * sizeof(float)) != hipSuccess) ||
-        (ws && p->simple && hipMalloc((void**)&w.work2, p->ws_elems * sizeof(float2)) != hipSuccess) ||
+        (ws && p->path == PATH_SIMPLE && hipMalloc((void**)&w.work2, p->ws_elems * sizeof(float2)) != hipSuccess) ||
         hipMalloc((void**)&w.mm, 2 * sizeof(float)) != hipSuccess ||
         hipMalloc((void**)&w.mm_part, (size_t)p->mm_part_cap * sizeof(float2)) != hipSuccess)
         return FDR_ERR_ALLOC;
@@ -197,24 +197,21 @@ int layout_radix2(fdr_plan* p, std::vector<float2>& t) {
     const int M = p->M, N = p->N;
     // dimensions above 8192 (one row no longer fits the LDS): the reference-shaped sequence rows / transpose / rows / transpose
     // with the long row pass (fdr_aux.hip, long_gather_kernel) -- as the serial path, correct at any power of two and slower
-    p->simple = p->generic || (p->flags & FDR_FLAG_SIMPLE_PATH) != 0 || M < 8 || N < 8 || M > (1 << kMaxLdsLog) || N > (1 << kMaxLdsLog);
+    const bool simple = p->generic || (p->flags & FDR_FLAG_SIMPLE_PATH) != 0 || M < 8 || N < 8 || M > (1 << kMaxLdsLog) || N > (1 << kMaxLdsLog);
+    const bool half = N >= 32 && (p->flags & FDR_FLAG_FULL_SPECTRUM) == 0;
+    p->path = simple ? PATH_SIMPLE : p->mode == FDR_MODE_PARITY ? PATH_PARITY_PANEL : half ? PATH_FAST_HALF : PATH_FAST_FULL;
     p->big = (fdr_is_pow2(M) && M > (1 << kMaxLdsLog)) || (fdr_is_pow2(N) && N > (1 << kMaxLdsLog));
-    p->panel = p->mode == FDR_MODE_FAST && !p->simple;
-    p->ws_elems = (size_t)M * N;
-    if (p->panel) {  // panel-major buffers: panels of 4 columns, PS elements apart (not a power of two: channel skew)
-        p->pstride = (size_t)M * 4 + 16;
-        p->half = N >= 32 && (p->flags & FDR_FLAG_FULL_SPECTRUM) == 0;
-        p->npanels = p->half ? N / 8 : N / 4;
-        p->ws_elems = (size_t)p->npanels * p->pstride;
-    } else if (p->mode == FDR_MODE_PARITY && !p->simple) {
-        // the bit-identical mode keeps the reference's pass order and full complex spectrum, but its intermediate is panel-major
+    if (simple) {
+        p->ws_elems = (size_t)M * N;
+    } else {
+        // panel-major buffers: panels of 4 columns, PS elements apart (not a power of two: channel skew).
+        // The bit-identical mode keeps the reference's pass order and full complex spectrum, but its intermediate is panel-major
         // too (all N/4 panels): the column passes B and D read and write contiguous M x 32-byte tiles instead of 32 bytes of
         // every row; A and C reach their 32-byte pieces through an XCD-aware workgroup order (fdr_rows.hip); the raw real plane
         // is panel-major as well and normalize_panels_kernel turns it back (LAB_NOTES "parity mode layout").  Same
         // butterflies, same tables, same bits (every parity test compares with ==).
-        p->ppar = true;
         p->pstride = (size_t)M * 4 + 16;
-        p->npanels = N / 4;
+        p->npanels = p->path == PATH_FAST_HALF ? N / 8 : N / 4;
         p->ws_elems = (size_t)p->npanels * p->pstride;
     }
     int rc = FDR_OK;
@@ -235,6 +232,7 @@ int layout_radix2(fdr_plan* p, std::vector<float2>& t) {
 // transforms per workgroup B
 int layout_mixed(fdr_plan* p, std::vector<float2>& t) {
     const int M = p->M, N = p->N;
+    p->path = PATH_MIXED;
     std::vector<int4> st;
     for (int d = 0; d < 2; ++d) {
         const int L = d == 0 ? N : M;
@@ -266,8 +264,8 @@ int layout_mixed(fdr_plan* p, std::vector<float2>& t) {
 int plan_create_impl(fdr_plan* p, int device, int M, int N, int mode, unsigned flags) {
     const bool pow2 = fdr_is_pow2(M) && fdr_is_pow2(N);
     p->device = device; p->M = M; p->N = N; p->flags = flags;
-    p->mixed = !pow2 && mode == FDR_MODE_FAST && (flags & FDR_FLAG_MIXED_RADIX) != 0;
-    p->generic = !pow2 && !p->mixed;  // only reachable with FDR_FLAG_ANY_SIZE: reference-shaped passes, parity arithmetic
+    const bool mixed = !pow2 && mode == FDR_MODE_FAST && (flags & FDR_FLAG_MIXED_RADIX) != 0;
+    p->generic = !pow2 && !mixed;  // only reachable with FDR_FLAG_ANY_SIZE: reference-shaped passes, parity arithmetic
     p->mode = p->generic ? FDR_MODE_PARITY : mode;
     p->tables_only = (flags & FDR_FLAG_TABLES_ONLY) != 0;
     p->logM = fdr_is_pow2(M) ? ilog2(M) : -1;
@@ -286,12 +284,10 @@ int plan_create_impl(fdr_plan* p, int device, int M, int N, int mode, unsigned f
         build_twiddles(M, p->mode, false, t); if ((rc = upload(&p->tw_col_f, t)) != FDR_OK) return rc;
         build_twiddles(M, p->mode, true, t);  if ((rc = upload(&p->tw_col_i, t)) != FDR_OK) return rc;
     }
-    rc = p->mixed ? layout_mixed(p, t) : layout_radix2(p, t);
+    rc = mixed ? layout_mixed(p, t) : layout_radix2(p, t);  // (each sets p->path)
     if (rc != FDR_OK) return rc;
     if ((!p->tables_only && hipMalloc((void**)&p->filt, p->ws_elems * sizeof(float2)) != hipSuccess) || alloc_slot(p, p->slots[0]) != FDR_OK)
         return fail(FDR_ERR_ALLOC, "fdr_plan_create: hipMalloc of the plan workspace failed");
-    const fdr_plan::Slot& w = p->slots[0];
-    p->work = w.work; p->work2 = w.work2; p->raw = w.raw; p->mm = w.mm; p->mm_part = w.mm_part;
     return FDR_OK;
 }
 
@@ -461,7 +457,7 @@ int fdr_plan_destroy(fdr_plan* p) {
         return FDR_OK;
     }
     (void)hipSetDevice(p->device);
-    for (fdr_plan::Slot& w : p->slots) release_slot(w);  // (slot 0 holds p->work, p->work2, p->raw, p->mm and p->mm_part)
+    for (fdr_plan::Slot& w : p->slots) release_slot(w);
     for (int k = 0; k < 3; ++k) {
         (void)hipFree(p->pipe.d_in[k]); (void)hipFree(p->pipe.d_out[k]);
         if (p->pipe.e_in[k]) (void)hipEventDestroy(p->pipe.e_in[k]);
@@ -515,7 +511,7 @@ int fdr_plan_set_option(fdr_plan* p, int option, long long value) {
             return FDR_OK;
         case FDR_OPT_PAD_MODE:
             // the padding is made by pass A of the fast panel path (fdr_panel_rows.hip); no other path has the smooth form
-            if (p->tables_only || p->mode != FDR_MODE_FAST || !p->panel || p->mixed)
+            if (p->tables_only || !on_panel_path(p))
                 return fail(FDR_ERR_ARG, "fdr_plan_set_option: FDR_OPT_PAD_MODE needs a FDR_MODE_FAST plan on the panel path (M, N powers of two, "
                                          "8 .. 8192; not FDR_FLAG_SIMPLE_PATH, FDR_FLAG_ANY_SIZE, FDR_FLAG_MIXED_RADIX sizes or FDR_FLAG_TABLES_ONLY)");
             if (value != FDR_PAD_ZERO && value != FDR_PAD_SMOOTH)

@@ -68,7 +68,7 @@ int rlfree_check(const fdr_plan* p, const char* fn, const float* img, int rows, 
 int rlfree_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, int cols, int stride, const float* d_w, int wstride,
                     float* d_out, int out_stride, const fdr_rlfree_params& prm, hipStream_t s) {
     const int M = p->M, N = p->N;
-    float *u = p->rf_u, *wgt = p->rf_wgt, *dw = p->rf_dw, *r = p->raw;
+    float *u = p->rf_u, *wgt = p->rf_wgt, *dw = p->rf_dw, *r = p->slots[0].raw;
     const int n_part = rlfree_partials(rows, cols);
     {
         ScopedPass t(p, s, kPassRfSetup);
@@ -88,8 +88,8 @@ int rlfree_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, i
         if (rc == FDR_OK) rc = op_cols(p, true, s);
         if (rc == FDR_OK) {                                                                             // ... u = max(u wgt g, 0)
             ScopedPass t(p, s, kPassRfUpdate);
-            RowArgs a{};
-            a.src_c = p->work; a.M = M; a.pstride = p->pstride; a.half = 1; a.num_cu = p->num_cu;
+            RowArgs a = panel_row_args(p);
+            a.src_c = p->slots[0].work;
             a.src_real = u; a.src_real2 = wgt; a.src_stride = N;
             a.out = u; a.out_rows = M; a.out_cols = N; a.out_stride = N;
             FDR_HIP(launch_rows4(p->logN, ROW_IN_COMPLEX, ROW_OUT_RL_UPDATE_W, a, p->tw_row_f, s));

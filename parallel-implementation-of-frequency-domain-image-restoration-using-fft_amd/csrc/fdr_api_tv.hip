@@ -84,7 +84,7 @@ int tv_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, int c
         ScopedPass t(p, s, kPassTvInit);
         FDR_HIP(launch_tv_init(d_img, rows, cols, stride, p->tv_x, p->tv_w[0][0], p->tv_w[0][1], M, N, s));
     }
-    float* rhs = p->raw;
+    float* rhs = p->slots[0].raw;
     for (int it = 0; it < n && rc == FDR_OK; ++it) {
         float* const* w = p->tv_w[it & 1];
         float* const* nw = p->tv_w[(it + 1) & 1];

@@ -66,44 +66,52 @@ int set_psf_dev_impl(fdr_plan* p, const float* d_psf, int prows, int pcols, int 
     }
     ScopedPhase phase(p, FDR_PHASE_PRE, s);
     // pad top-left + forward 2-D FFT (fft/fft_serial.cpp:166-171,182)
-    if (p->mixed) {
-        // rows of the PSF only (the rows below are zero and not read by the column pass), which turns H into W on its way out
-        MixRowArgs ra = mixed_row_args(p);
-        ra.src_real = d_psf; ra.src_rows = prows; ra.src_cols = pcols; ra.src_stride = pstride; ra.dst_c = p->filt;
-        FDR_HIP(launch_mixed_rows(MIX_ROWS_FWD_REAL, ra, (prows + 2 * p->mix_B - 1) / (2 * p->mix_B), s));
-        MixColArgs ca = mixed_col_args(p);
-        ca.src = p->filt; ca.dst = p->filt; ca.K = K; ca.rows_in = prows;
-        ca.lap = p->lap; ca.gamma = gamma;
-        FDR_HIP(launch_mixed_cols(cls ? MIX_COLS_FILTER_CLS : MIX_COLS_FILTER, ca, p->npanels, s));
-    } else if (p->simple) {
-        FDR_HIP(launch_pad_real_to_complex(d_psf, prows, pcols, pstride, p->filt, p->M, p->N, s));
-        int rc = dft2d_dev(p, p->filt, p->work2, false, s);
-        if (rc != FDR_OK) return rc;
-    } else if (p->panel) {
-        // the PSF reaches only the first `prows` rows of the padded field: the row pass transforms just those row groups,
-        // the column pass takes every row below as zero (unread) and turns the spectrum into W on its way out
-        const int nvalid = (prows + 3) & ~3;  // <= M (M is a multiple of 8 on this path)
-        RowArgs ra{};
-        ra.src_real = d_psf; ra.src_rows = prows; ra.src_cols = pcols; ra.src_stride = pstride;
-        ra.dst_c = p->filt; ra.M = nvalid; ra.pstride = p->pstride; ra.half = p->half; ra.num_cu = p->num_cu;
-        FDR_HIP(launch_rows4(p->logN, ROW_IN_REAL, ROW_OUT_COMPLEX, ra, p->tw_row_f, s));
-        ColArgs ca{};
-        ca.data = p->filt; ca.N = p->N; ca.num_cu = p->num_cu; ca.pstride = p->pstride; ca.npanels = p->npanels;
-        ca.nvalid = nvalid; ca.K = K; ca.packed0 = p->half ? 1 : 0;
-        if (cls) FDR_HIP(launch_cols_panel_cls(p->logM, ca, p->lap, gamma, p->tw_col_f, s));
-        else FDR_HIP(launch_cols_panel(p->logM, COL_FWD_FILTER, ca, p->tw_col_f, s));
-    } else {
-        RowArgs ra{};
-        ra.src_real = d_psf; ra.src_rows = prows; ra.src_cols = pcols; ra.src_stride = pstride;
-        ra.dst_c = p->filt; ra.M = p->M; ra.panel_c = p->ppar ? 1 : 0; ra.pstride = p->pstride;
-        FDR_HIP(launch_rows(p->logN, p->mode, ROW_IN_REAL, ROW_OUT_COMPLEX, false, ra, p->tw_row_f, s));
-        ColArgs ca{};
-        ca.data = p->filt; ca.N = p->N; ca.panel_c = p->ppar ? 1 : 0; ca.pstride = p->pstride;
-        FDR_HIP(launch_cols(p->logM, p->mode, COL_FWD, ca, p->tw_col_f, p->tw_col_i, s));
-    }
-    if (p->mode == FDR_MODE_FAST && !p->panel && !p->mixed) {  // (the panel and mixed paths' column passes have written W already)
-        if (cls) FDR_HIP(launch_make_filter_cls(p->filt, p->filt, p->M, p->N, K, p->lap, gamma, s));
-        else FDR_HIP(launch_make_filter_fast(p->filt, p->filt, (size_t)p->M * p->N, K, s));
+    switch (p->path) {
+        case PATH_MIXED: {
+            // rows of the PSF only (the rows below are zero and not read by the column pass), which turns H into W on its way out
+            MixRowArgs ra = mixed_row_args(p);
+            ra.src_real = d_psf; ra.src_rows = prows; ra.src_cols = pcols; ra.src_stride = pstride; ra.dst_c = p->filt;
+            FDR_HIP(launch_mixed_rows(MIX_ROWS_FWD_REAL, ra, (prows + 2 * p->mix_B - 1) / (2 * p->mix_B), s));
+            MixColArgs ca = mixed_col_args(p);
+            ca.src = p->filt; ca.dst = p->filt; ca.K = K; ca.rows_in = prows;
+            ca.lap = p->lap; ca.gamma = gamma;
+            FDR_HIP(launch_mixed_cols(cls ? MIX_COLS_FILTER_CLS : MIX_COLS_FILTER, ca, p->npanels, s));
+            break;
+        }
+        case PATH_SIMPLE: {
+            FDR_HIP(launch_pad_real_to_complex(d_psf, prows, pcols, pstride, p->filt, p->M, p->N, s));
+            const int rc = dft2d_dev(p, p->filt, p->slots[0].work2, false, s);
+            if (rc != FDR_OK) return rc;
+            if (p->mode != FDR_MODE_FAST) break;  // parity keeps H; the column passes of the other fast paths write W themselves
+            if (cls) FDR_HIP(launch_make_filter_cls(p->filt, p->filt, p->M, p->N, K, p->lap, gamma, s));
+            else FDR_HIP(launch_make_filter_fast(p->filt, p->filt, (size_t)p->M * p->N, K, s));
+            break;
+        }
+        case PATH_FAST_FULL:
+        case PATH_FAST_HALF: {
+            // the PSF reaches only the first `prows` rows of the padded field: the row pass transforms just those row groups,
+            // the column pass takes every row below as zero (unread) and turns the spectrum into W on its way out
+            const int nvalid = (prows + 3) & ~3;  // <= M (M is a multiple of 8 on this path)
+            RowArgs ra = panel_row_args(p);
+            ra.src_real = d_psf; ra.src_rows = prows; ra.src_cols = pcols; ra.src_stride = pstride;
+            ra.dst_c = p->filt; ra.M = nvalid;
+            FDR_HIP(launch_rows4(p->logN, ROW_IN_REAL, ROW_OUT_COMPLEX, ra, p->tw_row_f, s));
+            ColArgs ca = panel_col_args(p);
+            ca.data = p->filt; ca.nvalid = nvalid; ca.K = K;
+            if (cls) FDR_HIP(launch_cols_panel_cls(p->logM, ca, p->lap, gamma, p->tw_col_f, s));
+            else FDR_HIP(launch_cols_panel(p->logM, COL_FWD_FILTER, ca, p->tw_col_f, s));
+            break;
+        }
+        case PATH_PARITY_PANEL: {
+            RowArgs ra{};
+            ra.src_real = d_psf; ra.src_rows = prows; ra.src_cols = pcols; ra.src_stride = pstride;
+            ra.dst_c = p->filt; ra.M = p->M; ra.panel_c = 1; ra.pstride = p->pstride;
+            FDR_HIP(launch_rows(p->logN, p->mode, ROW_IN_REAL, ROW_OUT_COMPLEX, false, ra, p->tw_row_f, s));
+            ColArgs ca{};
+            ca.data = p->filt; ca.N = p->N; ca.panel_c = 1; ca.pstride = p->pstride;
+            FDR_HIP(launch_cols(p->logM, p->mode, COL_FWD, ca, p->tw_col_f, p->tw_col_i, s));
+            break;
+        }
     }
     p->K = K;
     p->have_psf = true;
@@ -114,89 +122,51 @@ int set_psf_dev_impl(fdr_plan* p, const float* d_psf, int prows, int pcols, int 
 
 namespace {
 
-// ---- fast panel path in three stages, so that pass B' can be launched once for a group of images ----
-int panel_stage_A(fdr_plan* p, fdr_plan::Slot& w, const float* d_img, int rows, int cols, int stride, hipStream_t s) {
-    ScopedPass t(p, s, kPassRowsFwd);   // A: 4 rows per thread group, real -> panel-major (half) spectrum
-    RowArgs a{};
-    a.src_real = d_img; a.src_rows = rows; a.src_cols = cols; a.src_stride = stride;
-    a.dst_c = w.work; a.M = p->M; a.pstride = p->pstride; a.half = p->half; a.num_cu = p->num_cu; a.pad_mode = p->pad_mode;
+// ---- the fast panel paths in three stages, each for a group of n >= 1 images on the slots ws[0 .. n) ----
+// One image goes by the single-image fields alone (batch.nimg 0: the launchers then pick the split kernels of small images); a
+// group of 2 .. kMaxGroup images adds the batch block (blockIdx.y = image), which the row passes have on the half-spectrum path only.
+int panel_stage_A(fdr_plan* p, fdr_plan::Slot* const* ws, int n, const float* const* d_imgs, int rows, int cols, int stride, hipStream_t s) {
+    ScopedPass t(p, s, kPassRowsFwdN[n]);   // A: 4 rows per thread group, real -> panel-major (half) spectrum
+    RowArgs a = panel_row_args(p);
+    a.src_real = d_imgs[0]; a.src_rows = rows; a.src_cols = cols; a.src_stride = stride;
+    a.dst_c = ws[0]->work; a.pad_mode = p->pad_mode;
+    if (n > 1) {
+        a.batch.nimg = n;
+        for (int k = 0; k < kMaxGroup; ++k) { a.batch.src_real[k] = d_imgs[k < n ? k : 0]; a.batch.spec[k] = ws[k < n ? k : 0]->work; }
+    }
     FDR_HIP(launch_rows4(p->logN, ROW_IN_REAL, ROW_OUT_COMPLEX, a, p->tw_row_f, s));
     return FDR_OK;
 }
 int panel_stage_B(fdr_plan* p, fdr_plan::Slot* const* ws, int n, hipStream_t s) {
     ScopedPass t(p, s, kPassColsFusedN[n]);  // B': per panel, columns forward * W * inverse
-    ColArgs c{};
-    c.data = ws[0]->work; c.filt = p->filt; c.K = p->K; c.N = p->N; c.num_cu = p->num_cu;
-    c.pstride = p->pstride; c.npanels = p->npanels; c.packed0 = p->half ? 1 : 0;
+    ColArgs c = panel_col_args(p);
+    c.data = ws[0]->work; c.filt = p->filt; c.K = p->K;
     c.batch.nimg = n;
     for (int k = 0; k < n; ++k) c.batch.data[k] = ws[k]->work;
     FDR_HIP(launch_cols_panel(p->logM, COL_FUSED, c, p->tw_col_f, s));
     return FDR_OK;
 }
-int panel_stage_CE(fdr_plan* p, fdr_plan::Slot& w, int rows, int cols, float* d_out, int out_stride, int mm_rows,
+int panel_stage_CE(fdr_plan* p, fdr_plan::Slot* const* ws, int n, int rows, int cols, float* const* d_outs, int out_stride, int mm_rows,
                    int mm_cols, hipStream_t s) {
-    if (p->two_sweep && p->half) {
-        // C1 + C2: the inverse row transform runs twice -- once for the min/max alone, once more with the normalisation
-        // applied on store -- so the raw real plane never exists: 4 + 8 bytes per pixel instead of 8 + 8
-        RowArgs a{};
-        a.src_c = w.work; a.mm_part = w.mm_part; a.mm_rows = mm_rows; a.mm_cols = mm_cols; a.M = p->M;
-        a.pstride = p->pstride; a.half = 1; a.num_cu = p->num_cu;
-        a.out = d_out; a.out_rows = rows; a.out_cols = cols; a.out_stride = out_stride;
-        a.n_part = rows4_minmax_partials(p->logN, p->M, 1, p->half ? 1 : 0);
-        if (a.n_part <= 0 || a.n_part > p->mm_part_cap) return fail(FDR_ERR_STATE, "fdr_wiener: min/max partial count out of range");
-        {
-            ScopedPass t(p, s, kPassRowsMinmax);
-            FDR_HIP(launch_rows4(p->logN, ROW_IN_COMPLEX, ROW_OUT_MINMAX_ONLY, a, p->tw_row_f, s));
-        }
-        {
-            ScopedPass t(p, s, kPassRowsNorm);
-            FDR_HIP(launch_rows4(p->logN, ROW_IN_COMPLEX, ROW_OUT_NORMALIZED, a, p->tw_row_f, s));
-        }
-        return FDR_OK;
-    }
-    {   // C': 4 rows rebuilt from the panels, inverse, real plane, min/max partials
-        ScopedPass t(p, s, kPassRowsInvReal);
-        RowArgs a{};
-        a.src_c = w.work; a.dst_real = w.raw; a.mm_part = w.mm_part; a.mm_rows = mm_rows; a.mm_cols = mm_cols; a.M = p->M;
-        a.pstride = p->pstride; a.half = p->half; a.num_cu = p->num_cu;
-        FDR_HIP(launch_rows4(p->logN, ROW_IN_COMPLEX, ROW_OUT_REAL_MINMAX, a, p->tw_row_f, s));
-    }
-    {   // E: normalise to [0,1] and crop
-        ScopedPass t(p, s, kPassNormalize);
-        const int n_part = rows4_minmax_partials(p->logN, p->M, 1, p->half ? 1 : 0);
-        if (n_part <= 0 || n_part > p->mm_part_cap || n_part > 4096) return fail(FDR_ERR_STATE, "fdr_wiener: min/max partial count out of range");
-        FDR_HIP(launch_normalize(w.raw, p->N, w.mm_part, n_part, nullptr, d_out, rows, cols, out_stride, s));
-    }
-    return FDR_OK;
-}
-
-// the same passes for a GROUP of 2..4 images in one launch each (blockIdx.y = image); packed half-spectrum path only
-bool can_batch_rows(const fdr_plan* p) { return p->half; }
-int panel_stage_A_batch(fdr_plan* p, fdr_plan::Slot* const* ws, int n, const float* const* d_imgs, int rows, int cols, int stride,
-                        hipStream_t s) {
-    ScopedPass t(p, s, kPassRowsFwdN[n]);
-    RowArgs a{};
-    a.src_real = d_imgs[0]; a.src_rows = rows; a.src_cols = cols; a.src_stride = stride;
-    a.dst_c = ws[0]->work; a.M = p->M; a.pstride = p->pstride; a.half = 1; a.num_cu = p->num_cu; a.pad_mode = p->pad_mode;
-    a.batch.nimg = n;
-    for (int k = 0; k < kMaxGroup; ++k) { a.batch.src_real[k] = d_imgs[k < n ? k : 0]; a.batch.spec[k] = ws[k < n ? k : 0]->work; }
-    FDR_HIP(launch_rows4(p->logN, ROW_IN_REAL, ROW_OUT_COMPLEX, a, p->tw_row_f, s));
-    return FDR_OK;
-}
-int panel_stage_CE_batch(fdr_plan* p, fdr_plan::Slot* const* ws, int n, int rows, int cols, float* const* d_outs, int out_stride,
-                         int mm_rows, int mm_cols, hipStream_t s) {
-    if (p->two_sweep) {  // C1 + C2 (see panel_stage_CE)
-        RowArgs a{};
-        a.src_c = ws[0]->work; a.mm_part = ws[0]->mm_part; a.mm_rows = mm_rows; a.mm_cols = mm_cols; a.M = p->M;
-        a.pstride = p->pstride; a.half = 1; a.num_cu = p->num_cu;
-        a.out = d_outs[0]; a.out_rows = rows; a.out_cols = cols; a.out_stride = out_stride;
-        a.n_part = rows4_minmax_partials(p->logN, p->M, n, p->half ? 1 : 0);
-        if (a.n_part <= 0 || a.n_part > p->mm_part_cap) return fail(FDR_ERR_STATE, "fdr_wiener: min/max partial count out of range");
+    const bool two_sweep = p->two_sweep && p->path == PATH_FAST_HALF;
+    RowArgs a = panel_row_args(p);
+    a.src_c = ws[0]->work; a.mm_part = ws[0]->mm_part; a.mm_rows = mm_rows; a.mm_cols = mm_cols;
+    const int n_part = rows4_minmax_partials(p->logN, p->M, n, a.half);
+    if (n_part <= 0 || n_part > p->mm_part_cap || (!two_sweep && n_part > 4096))
+        return fail(FDR_ERR_STATE, "fdr_wiener: min/max partial count out of range");
+    if (n > 1) {
         a.batch.nimg = n;
         for (int k = 0; k < kMaxGroup; ++k) {
             const fdr_plan::Slot* w = ws[k < n ? k : 0];
-            a.batch.spec[k] = w->work; a.batch.mm_part[k] = w->mm_part; a.batch.out[k] = d_outs[k < n ? k : 0];
+            a.batch.spec[k] = w->work; a.batch.mm_part[k] = w->mm_part;
+            if (two_sweep) a.batch.out[k] = d_outs[k < n ? k : 0];
+            else a.batch.raw[k] = w->raw;
         }
+    }
+    if (two_sweep) {
+        // C1 + C2: the inverse row transform runs twice -- once for the min/max alone, once more with the normalisation
+        // applied on store -- so the raw real plane never exists: 4 + 8 bytes per pixel instead of 8 + 8
+        a.out = d_outs[0]; a.out_rows = rows; a.out_cols = cols; a.out_stride = out_stride; a.n_part = n_part;
         {
             ScopedPass t(p, s, kPassRowsMinmaxN[n]);
             FDR_HIP(launch_rows4(p->logN, ROW_IN_COMPLEX, ROW_OUT_MINMAX_ONLY, a, p->tw_row_f, s));
@@ -207,31 +177,35 @@ int panel_stage_CE_batch(fdr_plan* p, fdr_plan::Slot* const* ws, int n, int rows
         }
         return FDR_OK;
     }
-    {
+    {   // C': 4 rows rebuilt from the panels, inverse, real plane, min/max partials
         ScopedPass t(p, s, kPassRowsInvRealN[n]);
-        RowArgs a{};
-        a.src_c = ws[0]->work; a.dst_real = ws[0]->raw; a.mm_part = ws[0]->mm_part; a.mm_rows = mm_rows; a.mm_cols = mm_cols; a.M = p->M;
-        a.pstride = p->pstride; a.half = 1; a.num_cu = p->num_cu;
-        a.batch.nimg = n;
-        for (int k = 0; k < kMaxGroup; ++k) {
-            const fdr_plan::Slot* w = ws[k < n ? k : 0];
-            a.batch.spec[k] = w->work; a.batch.raw[k] = w->raw; a.batch.mm_part[k] = w->mm_part;
-        }
+        a.dst_real = ws[0]->raw;
         FDR_HIP(launch_rows4(p->logN, ROW_IN_COMPLEX, ROW_OUT_REAL_MINMAX, a, p->tw_row_f, s));
     }
-    {
+    {   // E: normalise to [0,1] and crop
         ScopedPass t(p, s, kPassNormalizeN[n]);
-        const int n_part = rows4_minmax_partials(p->logN, p->M, n, p->half ? 1 : 0);
-        if (n_part <= 0 || n_part > p->mm_part_cap || n_part > 4096) return fail(FDR_ERR_STATE, "fdr_wiener: min/max partial count out of range");
         NormBatch nb{};
         nb.nimg = n;
         for (int k = 0; k < kMaxGroup; ++k) {
             const fdr_plan::Slot* w = ws[k < n ? k : 0];
             nb.raw[k] = w->raw; nb.part[k] = w->mm_part; nb.out[k] = d_outs[k < n ? k : 0];
         }
-        FDR_HIP(launch_normalize(ws[0]->raw, p->N, ws[0]->mm_part, n_part, nullptr, d_outs[0], rows, cols, out_stride, s, &nb));
+        FDR_HIP(launch_normalize(ws[0]->raw, p->N, ws[0]->mm_part, n_part, nullptr, d_outs[0], rows, cols, out_stride, s, n > 1 ? &nb : nullptr));
     }
     return FDR_OK;
+}
+
+// A, B' and C + E for a group of n images.  Pass B' takes the group in one launch on both panel paths; the row passes do on the
+// half-spectrum path (A once; C + E `chunk` images at a time) and run image by image on the full spectrum.
+int panel_group(fdr_plan* p, fdr_plan::Slot* const* ws, int n, const float* const* d_imgs, int rows, int cols, int stride, float* const* d_outs,
+                int out_stride, int mm_rows, int mm_cols, int chunk, hipStream_t s) {
+    const int na = p->path == PATH_FAST_HALF ? n : 1, nc = na < chunk ? na : chunk;
+    int rc = FDR_OK;
+    for (int k = 0; k < n && rc == FDR_OK; k += na) rc = panel_stage_A(p, ws + k, na, d_imgs + k, rows, cols, stride, s);
+    if (rc == FDR_OK) rc = panel_stage_B(p, ws, n, s);
+    for (int k = 0; k < n && rc == FDR_OK; k += nc)
+        rc = panel_stage_CE(p, ws + k, n - k < nc ? n - k : nc, rows, cols, d_outs + k, out_stride, mm_rows, mm_cols, s);
+    return rc;
 }
 
 // the mixed-radix operator: A (image rows -> spectrum), B (columns . W . inverse columns, only the rows C reads), C (inverse rows,
@@ -274,58 +248,62 @@ int wiener_dev_impl(fdr_plan* p, fdr_plan::Slot& w, const float* d_img, int rows
                     int out_stride, int norm_area, hipStream_t s) {
     const int mm_rows = norm_area == FDR_NORM_PADDED ? p->M : rows;
     const int mm_cols = norm_area == FDR_NORM_PADDED ? p->N : cols;
-    const size_t P = (size_t)p->M * p->N;
     int n_part = 0;
 
-    if (p->mixed) return mixed_wiener_dev(p, w, d_img, rows, cols, stride, d_out, out_stride, mm_rows, mm_cols, s);
-    if (p->simple) {
-        ScopedPass t(p, s, kPassSimple);
-        FDR_HIP(launch_pad_real_to_complex(d_img, rows, cols, stride, w.work, p->M, p->N, s));
-        int rc = dft2d_dev(p, w.work, w.work2, false, s);
-        if (rc != FDR_OK) return rc;
-        FDR_HIP(launch_wiener_pointwise(w.work, p->filt, P, p->K, p->mode, s));
-        rc = dft2d_dev(p, w.work, w.work2, true, s);
-        if (rc != FDR_OK) return rc;
-        FDR_HIP(launch_real_minmax(w.work, w.raw, p->M, p->N, mm_rows, mm_cols, w.mm_part, &n_part, s));
-    } else if (p->mode == FDR_MODE_PARITY) {
-        {   // A: rows, real -> complex (fft/fft_serial.cpp:157-165,176 first half)
-            ScopedPass t(p, s, kPassRowsFwd);
-            RowArgs a{};
-            a.src_real = d_img; a.src_rows = rows; a.src_cols = cols; a.src_stride = stride;
-            a.dst_c = w.work; a.M = p->M; a.panel_c = p->ppar ? 1 : 0; a.pstride = p->pstride;
-            FDR_HIP(launch_rows(p->logN, p->mode, ROW_IN_REAL, ROW_OUT_COMPLEX, false, a, p->tw_row_f, s));
+    switch (p->path) {
+        case PATH_MIXED:
+            return mixed_wiener_dev(p, w, d_img, rows, cols, stride, d_out, out_stride, mm_rows, mm_cols, s);
+        case PATH_FAST_FULL:
+        case PATH_FAST_HALF: {  // a group of one
+            fdr_plan::Slot* one = &w;
+            return panel_group(p, &one, 1, &d_img, rows, cols, stride, &d_out, out_stride, mm_rows, mm_cols, 1, s);
         }
-        {   // B: columns forward + Wiener quotient (:176 second half, :186-224)
-            ScopedPass t(p, s, kPassColsWiener);
-            ColArgs c{};
-            c.data = w.work; c.filt = p->filt; c.K = p->K; c.N = p->N; c.panel_c = p->ppar ? 1 : 0; c.pstride = p->pstride;
-            FDR_HIP(launch_cols(p->logM, p->mode, COL_FWD_WIENER, c, p->tw_col_f, p->tw_col_i, s));
+        case PATH_SIMPLE: {
+            ScopedPass t(p, s, kPassSimple);
+            FDR_HIP(launch_pad_real_to_complex(d_img, rows, cols, stride, w.work, p->M, p->N, s));
+            int rc = dft2d_dev(p, w.work, w.work2, false, s);
+            if (rc != FDR_OK) return rc;
+            FDR_HIP(launch_wiener_pointwise(w.work, p->filt, (size_t)p->M * p->N, p->K, p->mode, s));
+            rc = dft2d_dev(p, w.work, w.work2, true, s);
+            if (rc != FDR_OK) return rc;
+            FDR_HIP(launch_real_minmax(w.work, w.raw, p->M, p->N, mm_rows, mm_cols, w.mm_part, &n_part, s));
+            break;
         }
-        {   // C: rows inverse (:229 first half)
-            ScopedPass t(p, s, kPassRowsInv);
-            RowArgs a{};
-            a.src_c = w.work; a.dst_c = w.work; a.M = p->M; a.panel_c = p->ppar ? 1 : 0; a.pstride = p->pstride;
-            FDR_HIP(launch_rows(p->logN, p->mode, ROW_IN_COMPLEX, ROW_OUT_COMPLEX, true, a, p->tw_row_i, s));
+        case PATH_PARITY_PANEL: {
+            {   // A: rows, real -> complex (fft/fft_serial.cpp:157-165,176 first half)
+                ScopedPass t(p, s, kPassRowsFwd);
+                RowArgs a{};
+                a.src_real = d_img; a.src_rows = rows; a.src_cols = cols; a.src_stride = stride;
+                a.dst_c = w.work; a.M = p->M; a.panel_c = 1; a.pstride = p->pstride;
+                FDR_HIP(launch_rows(p->logN, p->mode, ROW_IN_REAL, ROW_OUT_COMPLEX, false, a, p->tw_row_f, s));
+            }
+            {   // B: columns forward + Wiener quotient (:176 second half, :186-224)
+                ScopedPass t(p, s, kPassColsWiener);
+                ColArgs c{};
+                c.data = w.work; c.filt = p->filt; c.K = p->K; c.N = p->N; c.panel_c = 1; c.pstride = p->pstride;
+                FDR_HIP(launch_cols(p->logM, p->mode, COL_FWD_WIENER, c, p->tw_col_f, p->tw_col_i, s));
+            }
+            {   // C: rows inverse (:229 first half)
+                ScopedPass t(p, s, kPassRowsInv);
+                RowArgs a{};
+                a.src_c = w.work; a.dst_c = w.work; a.M = p->M; a.panel_c = 1; a.pstride = p->pstride;
+                FDR_HIP(launch_rows(p->logN, p->mode, ROW_IN_COMPLEX, ROW_OUT_COMPLEX, true, a, p->tw_row_i, s));
+            }
+            {   // D: columns inverse, real plane, min/max (:229 second half, :236-240, minMaxIdx of :246)
+                ScopedPass t(p, s, kPassColsInvReal);
+                ColArgs c{};
+                c.data = w.work; c.dst_real = w.raw; c.mm_part = w.mm_part; c.mm_rows = mm_rows; c.mm_cols = mm_cols; c.N = p->N;
+                c.panel_c = 1; c.pstride = p->pstride;
+                FDR_HIP(launch_cols(p->logM, p->mode, COL_INV_REAL, c, p->tw_col_f, p->tw_col_i, s));
+                n_part = cols_minmax_partials(p->logM, p->N);
+            }
+            break;
         }
-        {   // D: columns inverse, real plane, min/max (:229 second half, :236-240, minMaxIdx of :246)
-            ScopedPass t(p, s, kPassColsInvReal);
-            ColArgs c{};
-            c.data = w.work; c.dst_real = w.raw; c.mm_part = w.mm_part; c.mm_rows = mm_rows; c.mm_cols = mm_cols; c.N = p->N;
-            c.panel_c = p->ppar ? 1 : 0; c.pstride = p->pstride;
-            FDR_HIP(launch_cols(p->logM, p->mode, COL_INV_REAL, c, p->tw_col_f, p->tw_col_i, s));
-            n_part = cols_minmax_partials(p->logM, p->N);
-        }
-    } else {  // fast mode runs on the panel path (or the simple path for dimensions below 8)
-        fdr_plan::Slot* one[1] = {&w};
-        int rc = panel_stage_A(p, w, d_img, rows, cols, stride, s);
-        if (rc == FDR_OK) rc = panel_stage_B(p, one, 1, s);
-        if (rc == FDR_OK) rc = panel_stage_CE(p, w, rows, cols, d_out, out_stride, mm_rows, mm_cols, s);
-        return rc;
     }
     {   // E: normalise to [0,1] and crop (fft/fft_serial.cpp:246, serial.cpp:38)
         ScopedPass t(p, s, kPassNormalize);
         if (n_part <= 0 || n_part > p->mm_part_cap) return fail(FDR_ERR_STATE, "fdr_wiener: min/max partial count out of range");
-        const bool pp = p->ppar && p->mode == FDR_MODE_PARITY && !p->simple;  // the raw plane is panel-major then
+        const bool pp = p->path == PATH_PARITY_PANEL;  // the raw plane is panel-major then
         if (n_part <= 4096) {
             if (pp) FDR_HIP(launch_normalize_panels(w.raw, p->M, w.mm_part, n_part, nullptr, d_out, rows, cols, out_stride, s));
             else FDR_HIP(launch_normalize(w.raw, p->N, w.mm_part, n_part, nullptr, d_out, rows, cols, out_stride, s));
@@ -344,7 +322,7 @@ int batch_enqueue(fdr_plan* p, const float* d_imgs, size_t img_pitch, int count,
     int rc = FDR_OK;
     const int mm_rows = norm_area == FDR_NORM_PADDED ? p->M : rows;
     const int mm_cols = norm_area == FDR_NORM_PADDED ? p->N : cols;
-    const int group = p->panel ? p->group : 1;
+    const int group = on_panel_path(p) ? p->group : 1;
     // per-kernel profiling wants un-overlapped durations: keep everything on the caller's stream then
     const int ns = (p->timer.enabled || count <= group) ? 1 : p->nstreams;
     if (ns > 1) {  // fork: internal streams wait for everything queued so far on the caller's stream
@@ -358,42 +336,28 @@ int batch_enqueue(fdr_plan* p, const float* d_imgs, size_t img_pitch, int count,
         fdr_plan::Slot* ws[fdr_plan::kMaxSlots];
         for (int k = 0; k < n; ++k) ws[k] = &p->slots[sidx * group + k];
         hipStream_t s = ns > 1 ? p->slots[sidx * group].stream : us;
-        if (!p->panel) {
+        if (!on_panel_path(p)) {
             rc = wiener_dev_impl(p, *ws[0], d_imgs + (size_t)i0 * img_pitch, rows, cols, stride, d_out + (size_t)i0 * out_pitch,
                                  out_stride, norm_area, s);
             continue;
         }
-        if (n > 1 && can_batch_rows(p)) {  // every pass once for the whole group
-            const float* ins[kMaxGroup]; float* outs[kMaxGroup];
-            for (int k = 0; k < n; ++k) { ins[k] = d_imgs + (size_t)(i0 + k) * img_pitch; outs[k] = d_out + (size_t)(i0 + k) * out_pitch; }
-            rc = panel_stage_A_batch(p, ws, n, ins, rows, cols, stride, s);
-            if (rc == FDR_OK) rc = panel_stage_B(p, ws, n, s);
-            // The two inverse row passes (C1: extremes; C2: the same transform again, normalised) go in CHUNKS of the group
-            // when the batch alternates over two or more streams: C1 is the pass with exposed compute, and in launches of half
-            // the size it interleaves better with the memory-bound passes of the other stream's group.  With ONE stream the
-            // chunks only make the launches smaller, and passes A / B' lose in chunks (LAB_NOTES "inverse row chunks").
-            // Hence: >= 2 streams, and a chunk holds at least ce_chunk_bytes of spectrum (FDR_OPT_CE_CHUNK_MB, default
-            // 160 MiB: pairs at 4096^2, the whole group below, no split where one image alone is larger).
-            int chunk = n;
-            if (ns > 1) {
-                const size_t spec_bytes = p->ws_elems * sizeof(float2);
-                if (p->ce_chunk_bytes > 0 && spec_bytes <= p->ce_chunk_bytes) {
-                    const size_t c = p->ce_chunk_bytes / spec_bytes;
-                    if (c < (size_t)n) chunk = (int)c;
-                }
+        const float* ins[kMaxGroup]; float* outs[kMaxGroup];
+        for (int k = 0; k < n; ++k) { ins[k] = d_imgs + (size_t)(i0 + k) * img_pitch; outs[k] = d_out + (size_t)(i0 + k) * out_pitch; }
+        // The two inverse row passes (C1: extremes; C2: the same transform again, normalised) go in CHUNKS of the group
+        // when the batch alternates over two or more streams: C1 is the pass with exposed compute, and in launches of half
+        // the size it interleaves better with the memory-bound passes of the other stream's group.  With ONE stream the
+        // chunks only make the launches smaller, and passes A / B' lose in chunks (LAB_NOTES "inverse row chunks").
+        // Hence: >= 2 streams, and a chunk holds at least ce_chunk_bytes of spectrum (FDR_OPT_CE_CHUNK_MB, default
+        // 160 MiB: pairs at 4096^2, the whole group below, no split where one image alone is larger).
+        int ce_chunk = n;
+        if (ns > 1) {
+            const size_t spec_bytes = p->ws_elems * sizeof(float2);
+            if (p->ce_chunk_bytes > 0 && spec_bytes <= p->ce_chunk_bytes) {
+                const size_t c = p->ce_chunk_bytes / spec_bytes;
+                if (c < (size_t)n) ce_chunk = (int)c;
             }
-            for (int k0 = 0; k0 < n && rc == FDR_OK; k0 += chunk) {
-                const int m = n - k0 < chunk ? n - k0 : chunk;
-                if (m == 1) rc = panel_stage_CE(p, *ws[k0], rows, cols, outs[k0], out_stride, mm_rows, mm_cols, s);
-                else rc = panel_stage_CE_batch(p, ws + k0, m, rows, cols, outs + k0, out_stride, mm_rows, mm_cols, s);
-            }
-            continue;
         }
-        for (int k = 0; k < n && rc == FDR_OK; ++k)
-            rc = panel_stage_A(p, *ws[k], d_imgs + (size_t)(i0 + k) * img_pitch, rows, cols, stride, s);
-        if (rc == FDR_OK) rc = panel_stage_B(p, ws, n, s);
-        for (int k = 0; k < n && rc == FDR_OK; ++k)
-            rc = panel_stage_CE(p, *ws[k], rows, cols, d_out + (size_t)(i0 + k) * out_pitch, out_stride, mm_rows, mm_cols, s);
+        rc = panel_group(p, ws, n, ins, rows, cols, stride, outs, out_stride, mm_rows, mm_cols, ce_chunk, s);
     }
     if (ns > 1) {  // join -- also after an error: the caller's stream continues only after every internal stream has
                    // drained, so work already queued there cannot still be writing d_out when the caller goes on
@@ -507,7 +471,7 @@ int fdr_wiener_batch_f32_dev(fdr_plan* p, const float* d_imgs, size_t img_pitch,
     hipStream_t us = (hipStream_t)stream;
     // graph replay: launch-bound batches (small images) pay one graph launch instead of 4 kernel launches per group.
     // Not with per-kernel profiling (host-side event pairs).
-    if (p->batch_graph && p->panel && !p->timer.enabled) {
+    if (p->batch_graph && on_panel_path(p) && !p->timer.enabled) {
         const fdr_plan::GraphKey key{d_imgs, d_out, img_pitch, out_pitch, count, rows, cols, stride, out_stride, norm_area, p->nstreams, p->group,
                                      p->two_sweep, p->K, p->ce_chunk_bytes, p->pad_mode};
         if (!(p->graph_exec && key == p->graph_key)) {

@@ -1,6 +1,7 @@
-// fdr_host.hpp -- private to the host files of libfdr.so (fdr_api_*.hip): the plan, the pass and phase timers, the error
-// helpers and the helpers that more than one entry point uses.  The C ABI is include/fdr.h alone: the shared helpers live in
-// namespace fdr, so none of them is an fdr_* symbol of the library.
+// fdr_host.hpp -- private to the host files of libfdr.so (fdr_api_*.hip): the plan with its one path, the pass and phase
+// timers, the error helpers and the helpers that more than one entry point uses (the checks, the PSF path, the argument builders
+// of the panel and mixed passes).  The C ABI is include/fdr.h alone: the shared helpers live in namespace fdr, so none of them
+// is an fdr_* symbol of the library.
 #pragma once
 #include "../../include/fdr.h"
 #include "fdr_kernels.hpp"
@@ -11,7 +12,22 @@
 #include <string>
 #include <vector>
 
+#pragma clang diagnostic error "-Wswitch"  // a switch over PlanPath names every path: a new path does not compile until each does
+
 namespace fdr {
+
+// The path of a plan: the passes its Wiener call runs and the layout of its intermediate spectrum and filter ("paths
+// of a plan").  Chosen once, by layout_radix2 / layout_mixed (fdr_api_plan.hip).
+enum PlanPath {
+    PATH_SIMPLE,        // rows, transpose, rows, transpose on a row-major spectrum, in either mode: dimensions below 8 or above 8192,
+                        // FDR_FLAG_ANY_SIZE sizes, FDR_FLAG_SIMPLE_PATH; the only path whose slots have `work2`
+    PATH_PARITY_PANEL,  // parity mode: passes A B C D E on a PANEL-major full spectrum (N / 4 panels): contiguous column tiles
+    PATH_FAST_FULL,     // fast mode: A B' C' E on the panel-major full spectrum (N < 32 or FDR_FLAG_FULL_SPECTRUM)
+    PATH_FAST_HALF,     // fast mode: A B' C1 C2 (or C' E) on the non-redundant half of the Hermitian spectrum (N / 8 panels, Nyquist
+                        // packed into column 0); the path of the blur operator, Richardson-Lucy, TV and FDR_OPT_PAD_MODE
+    PATH_MIXED          // FDR_FLAG_MIXED_RADIX in fast mode with a dimension that is not a power of two: the four passes of
+                        // fdr_mixed.hip on a panel-major full spectrum (mix_P columns per panel)
+};
 
 extern thread_local std::string g_last_error;  // what fdr_last_error returns
 int fail(int code, const std::string& msg);     // g_last_error = msg, returns code
@@ -64,33 +80,23 @@ struct PassTimer {
 struct fdr_plan {
     int device = 0, M = 0, N = 0, logM = 0, logN = 0, mode = 0;
     unsigned flags = 0;
-    bool simple = false;
-    bool ppar = false;  // parity operator on a PANEL-major complex intermediate: contiguous column tiles
-    bool big = false;  // a power-of-two dimension above 8192: simple sequence with the long row pass (fdr_aux.hip)
-    int num_cu = 256;
-    bool tables_only = false;  // FDR_FLAG_TABLES_ONLY: no workspaces, slab primitives only
+    fdr::PlanPath path = fdr::PATH_SIMPLE;
+    // facts next to the path: which row kernel PATH_SIMPLE uses (generic, big), and that there is no workspace (tables_only)
     bool generic = false;  // FDR_FLAG_ANY_SIZE with a non-power-of-two dimension: naive DFT along that dimension
+    bool big = false;  // a power-of-two dimension above 8192: simple sequence with the long row pass (fdr_aux.hip)
+    bool tables_only = false;  // FDR_FLAG_TABLES_ONLY: no workspaces, slab primitives only
+    int num_cu = 256;
     float2 *naive_row = nullptr, *naive_col = nullptr;  // n x n tables of the non-power-of-two dimensions (length N / M)
-    bool panel = false;
-    // FDR_FLAG_MIXED_RADIX in fast mode with a dimension that is not a power of two: the mixed-radix passes of fdr_mixed.hip on a
-    // panel-major full spectrum (mix_P columns per panel), row passes with mix_B transforms per workgroup
-    bool mixed = false;
-    fdr::MixLen mix_row{}, mix_col{};  // lengths N and M
-    int mix_P = 1, mix_logP = 0, mix_B = 1;
+    fdr::MixLen mix_row{}, mix_col{};  // PATH_MIXED: lengths N and M
+    int mix_P = 1, mix_logP = 0, mix_B = 1;  // columns per panel, row-pass transforms per workgroup
     size_t pstride = 0;  // panel stride (float2 elements)
-    bool half = false;   // fast mode: only the non-redundant half of the Hermitian spectrum is kept (N/8 panels, Nyquist packed into column 0)
-    int npanels = 0;  // fast mode: panel-major intermediate spectrum and filter
+    int npanels = 0;  // every path but PATH_SIMPLE: panel-major intermediate spectrum and filter
     float2 *tw_row_f = nullptr, *tw_row_i = nullptr, *tw_col_f = nullptr, *tw_col_i = nullptr;
-    float2* work = nullptr;   // M x N complex working spectrum
-    float2* work2 = nullptr;  // simple path: N x M transpose buffer
     float2* filt = nullptr;   // H (parity) or W (fast)
-    float* raw = nullptr;     // M x N real plane before normalisation
     float* psf_dev = nullptr; // staging for host-pointer / generated PSFs
     float *stage_in = nullptr, *stage_out = nullptr;  // device staging of the host-pointer single-image calls: M x N each, kept between calls
     size_t psf_cap = 0;
-    float* mm = nullptr;       // final {min, max}
-    float2* mm_part = nullptr; // per-workgroup partials
-    int mm_part_cap = 0;
+    int mm_part_cap = 0;  // elements of a slot's mm_part
     float K = 0.f;
     bool have_psf = false;
     double* lap = nullptr;  // CLS filters (fdr_set_psf_cls*) and the TV solve table: a_u = 4 sin^2(pi u / M), u < M, then b_v = 4 sin^2(pi v / N), v < N
@@ -101,7 +107,7 @@ struct fdr_plan {
     bool have_op = false;
     unsigned op_gen = 0;  // counts the fdr_set_operator_psf* calls that rebuilt the tables
     // total-variation deconvolution (fdr_tv_deconv_f32*): made by the first such call, kept until fdr_plan_destroy -- one allocation
-    // holding the solve table T (ws_elems, layout of `filt`) and six M x N real planes: x, b and two pairs of duals (rhs lives in `raw`).
+    // holding the solve table T (ws_elems, layout of `filt`) and six M x N real planes: x, b and two pairs of duals (rhs lives in slot 0's `raw`).
     // T was built for (tv_mu, tv_rho) and the operator tables of generation tv_gen; tv_gen 0 = not built.
     void* tv_block = nullptr;
     float2* tv_T = nullptr;
@@ -122,7 +128,7 @@ struct fdr_plan {
     std::vector<double> mo_trig_host;
     // free-boundary Richardson-Lucy (fdr_richardson_lucy_free_f32*): made by the first such call, kept until fdr_plan_destroy -- one
     // allocation holding three M x N real planes (the estimate u, wgt = 1 / coverage, dw = weights . max(d, 0) on the window) and the
-    // 2 rlfree_partials(M, N) + 2 double partials of the two sums (r lives in `raw`)
+    // 2 rlfree_partials(M, N) + 2 double partials of the two sums (r lives in slot 0's `raw`)
     void* rf_block = nullptr;
     float *rf_u = nullptr, *rf_wgt = nullptr, *rf_dw = nullptr;
     double* rf_part = nullptr;
@@ -131,10 +137,14 @@ struct fdr_plan {
     struct PhaseRec { hipEvent_t a, b; int phase; };
     double phase_ms[FDR_N_PHASES] = {0, 0, 0, 0, 0, 0};
     std::vector<PhaseRec> phase_pending;
-    // batched mode: images alternate over `nslots` private workspaces, each on its own internal stream,
-    // so the tail of one image's kernels overlaps the head of the next image's (slot 0 = the buffers above)
+    // The workspaces.  Slot 0 is the one of every single-image call; in batched mode images alternate over `nslots` private
+    // workspaces, each on its own internal stream, so the tail of one image's kernels overlaps the head of the next image's
     struct Slot {
-        float2* work = nullptr; float2* work2 = nullptr; float* raw = nullptr; float* mm = nullptr; float2* mm_part = nullptr;
+        float2* work = nullptr;     // the working spectrum, ws_elems
+        float2* work2 = nullptr;    // PATH_SIMPLE: N x M transpose buffer
+        float* raw = nullptr;       // M x N real plane before normalisation
+        float* mm = nullptr;        // final {min, max}
+        float2* mm_part = nullptr;  // per-workgroup partials
         hipStream_t stream = nullptr; hipEvent_t done = nullptr;
     };
     static constexpr int kMaxSlots = 16;
@@ -177,6 +187,9 @@ struct fdr_plan {
 };
 
 namespace fdr {
+
+// on one of the two fast panel paths (passes A, B', C of fdr_panel_rows.hip / fdr_panel_cols.hip)
+inline bool on_panel_path(const fdr_plan* p) { return p->path == PATH_FAST_FULL || p->path == PATH_FAST_HALF; }
 
 struct ScopedPass {
     fdr_plan* p; hipStream_t s; PassTimer::Rec rec; bool on;
@@ -280,7 +293,10 @@ int host_image_call(fdr_plan* p, const char* fn, const float* in, int rows, int 
 // ---- the plan's transforms (fdr_api_misc.hip) ----
 // unscaled 2-D transform in place on d (M x N), rows then columns as fft/fft_serial.cpp:113-139
 int dft2d_dev(fdr_plan* p, float2* d, float2* work2, bool inverse, hipStream_t s);
+// what every pass of a path takes from the plan; the caller adds its buffers and windows
 MixRowArgs mixed_row_args(const fdr_plan* p);
 MixColArgs mixed_col_args(const fdr_plan* p);
+RowArgs panel_row_args(const fdr_plan* p);  // M, pstride, half, num_cu (a pass over fewer rows, as the PSF's, overrides M)
+ColArgs panel_col_args(const fdr_plan* p);  // N, num_cu, pstride, npanels, packed0
 
 }  // namespace fdr
