@@ -667,10 +667,15 @@ __device__ __forceinline__ float fdr_max3(float a, float b, float c) {
 
 __device__ __forceinline__ void block_minmax_store(float mn, float mx, float2* __restrict__ part, int index = -1) {
     __shared__ float2 red[16];
+    // A workgroup of fewer than 64 threads (parity pass D on columns of up to 64 points) leaves lanes of its wave switched off, and a
+    // shuffle from such a lane reads 0, not (+inf, -inf): only partners that exist are folded in.
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
-        mn = fminf(mn, __shfl_xor(mn, off));
-        mx = fmaxf(mx, __shfl_xor(mx, off));
+        const float omn = __shfl_xor(mn, off), omx = __shfl_xor(mx, off);
+        if ((threadIdx.x ^ off) < blockDim.x) {
+            mn = fminf(mn, omn);
+            mx = fmaxf(mx, omx);
+        }
     }
     const int wave = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
     FDR_JITTER(1001);

@@ -116,7 +116,8 @@ def failures(what, M, N, e, where, sp, bin_tol, sp_tol):
 
 def max_abs(got, want):
     """max |got - want| in float64; NaN when either holds a NaN (np.max propagates it)"""
-    return float(np.max(np.abs(np.asarray(got, dtype=np.float64) - np.asarray(want, dtype=np.float64))))
+    d = np.atleast_1d(np.subtract(got, want, dtype=np.float64))  # both sides cast to float64 first; one temporary (the windows reach 2^20 pixels)
+    return float(np.max(np.abs(d, out=d)))
 
 
 def check_bins(got, raw, tol, what=""):
