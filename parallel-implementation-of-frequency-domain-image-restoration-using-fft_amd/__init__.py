@@ -112,6 +112,84 @@ def build(force=False):
     return LIB_PATH
 
 
+def _signatures():
+    """Every function of include/fdr.h, once: name -> (restype, argtypes; None = not declared).  _load applies it and
+    EXPORTED_SYMBOLS is its keys, so an entry point cannot have its argument types without its return type."""
+    vp, ci, cf, cd, cu, sz, u64, P = (ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_double, ctypes.c_uint, ctypes.c_size_t,
+                                      ctypes.c_uint64, ctypes.POINTER)
+    return {
+        "fdr_version": (ci, None),
+        "fdr_last_error": (ctypes.c_char_p, None),
+        "fdr_device_count": (ci, [P(ci)]),
+        "fdr_next_pow2": (ci, [ci]),
+        "fdr_is_pow2": (ci, [ci]),
+        "fdr_optimal_dft_size": (ci, [ci]),
+        "fdr_plan_set_option": (ci, [vp, ci, ctypes.c_longlong]),
+        "fdr_plan_phase_times": (ci, [vp, _f32p, ci]),
+        "fdr_batch_run": (ci, [P(BatchDesc), P(BatchStats)]),
+        "fdr_slab_pad_dev": (ci, [vp, ci, ci, ci, vp, ci, ci, vp]),
+        "fdr_slab_rows_fft_dev": (ci, [vp, vp, ci, ci, ci, vp]),
+        "fdr_slab_pack_dev": (ci, [vp, ci, ci, ci, P(ci), ci, vp, vp]),
+        "fdr_slab_transpose_dev": (ci, [vp, vp, ci, ci, ci, vp]),
+        "fdr_slab_wiener_dev": (ci, [vp, vp, vp, sz, cf, vp]),
+        "fdr_slab_real_dev": (ci, [vp, vp, sz, vp]),
+        "fdr_slab_minmax_dev": (ci, [vp, vp, ci, ci, ci, ci, vp, vp]),
+        "fdr_slab_normalize_dev": (ci, [vp, ci, vp, vp, ci, ci, ci, vp]),
+        "fdr_plan_create": (ci, [ci, ci, ci, ci, cu, P(vp)]),
+        "fdr_plan_destroy": (ci, [vp]),
+        "fdr_plan_dims": (ci, [vp, P(ci), P(ci), P(ci)]),
+        "fdr_psf_motion": (ci, [ci, cd, vp]),
+        "fdr_psf_motion_dev": (ci, [ci, ci, cd, vp, vp]),
+        "fdr_warp_affine_f32": (ci, [vp, ci, ci, ci, P(cd), vp, ci, ci, ci]),
+        "fdr_plan_filter_bytes": (ci, [vp, P(sz)]),
+        "fdr_plan_export_filter_dev": (ci, [vp, vp, sz, vp]),
+        "fdr_plan_import_filter_dev": (ci, [vp, vp, sz, cf, vp]),
+        "fdr_set_psf": (ci, [vp, vp, ci, ci, ci, cf]),
+        "fdr_set_psf_dev": (ci, [vp, vp, ci, ci, ci, cf, vp]),
+        "fdr_set_psf_motion": (ci, [vp, ci, cd, cf, vp]),
+        "fdr_set_psf_cls": (ci, [vp, vp, ci, ci, ci, cf, cf]),
+        "fdr_set_psf_cls_dev": (ci, [vp, vp, ci, ci, ci, cf, cf, vp]),
+        "fdr_set_psf_motion_cls": (ci, [vp, ci, cd, cf, cf, vp]),
+        "fdr_wiener_f32": (ci, [vp, vp, ci, ci, ci, vp, ci, ci]),
+        "fdr_wiener_f32_dev": (ci, [vp, vp, ci, ci, ci, vp, ci, ci, vp]),
+        "fdr_wiener_batch_f32_dev": (ci, [vp, vp, sz, ci, ci, ci, ci, vp, sz, ci, ci, vp]),
+        "fdr_wiener_batch_f32": (ci, [vp, vp, sz, ci, ci, ci, ci, vp, sz, ci, ci]),
+        "fdr_wiener_batch_ptrs_f32": (ci, [vp, P(vp), P(vp), ci, ci, ci, ci, ci, ci]),
+        "fdr_host_alloc": (ci, [sz, P(vp)]),
+        "fdr_host_free": (ci, [vp]),
+        "fdr_white_balance_u8": (ci, [ci, P(vp), P(vp), ci, ci, ci, vp, ci]),
+        "fdr_white_balance_u8_dev": (ci, [ci, P(vp), P(vp), ci, ci, ci, vp, ci, vp]),
+        "fdr_plan_set_concurrency": (ci, [vp, ci]),
+        "fdr_plan_set_batching": (ci, [vp, ci, ci]),
+        "fdr_fft2d_c2c": (ci, [vp, vp, ci]),
+        "fdr_fft2d_c2c_dev": (ci, [vp, vp, ci, vp]),
+        "fdr_fft1d_c2c": (ci, [vp, ci, ci, ci]),
+        "fdr_dft_naive_c2c": (ci, [vp, ci, ci]),
+        "fdr_synth_image_dev": (ci, [ci, u64, u64, sz, vp, vp]),
+        "fdr_plan_profile": (ci, [vp, ci]),
+        "fdr_set_operator_psf": (ci, [vp, vp, ci, ci, ci]),
+        "fdr_set_operator_psf_dev": (ci, [vp, vp, ci, ci, ci, vp]),
+        "fdr_set_operator_psf_motion": (ci, [vp, ci, cd, vp]),
+        "fdr_blur_f32": (ci, [vp, vp, ci, ci, ci, vp, ci, ci]),
+        "fdr_blur_f32_dev": (ci, [vp, vp, ci, ci, ci, vp, ci, ci, vp]),
+        "fdr_richardson_lucy_f32": (ci, [vp, vp, ci, ci, ci, vp, ci, ci, ci]),
+        "fdr_richardson_lucy_f32_dev": (ci, [vp, vp, ci, ci, ci, vp, ci, ci, ci, vp]),
+        "fdr_richardson_lucy_free_f32": (ci, [vp, vp, ci, ci, ci, vp, ci, vp, ci, P(RlFreeParams)]),
+        "fdr_richardson_lucy_free_f32_dev": (ci, [vp, vp, ci, ci, ci, vp, ci, vp, ci, P(RlFreeParams), vp]),
+        "fdr_tv_deconv_f32": (ci, [vp, vp, ci, ci, ci, vp, ci, P(TvParams)]),
+        "fdr_tv_deconv_f32_dev": (ci, [vp, vp, ci, ci, ci, vp, ci, P(TvParams), vp]),
+        "fdr_cepstrum_f32": (ci, [vp, vp, ci, ci, ci, vp]),
+        "fdr_cepstrum_f32_dev": (ci, [vp, vp, ci, ci, ci, vp, vp]),
+        "fdr_estimate_motion_f32": (ci, [vp, vp, ci, ci, ci, ci, ci, cd, P(MotionEstimateC), vp]),
+        "fdr_estimate_motion_f32_dev": (ci, [vp, vp, ci, ci, ci, ci, ci, cd, P(MotionEstimateC), vp, vp]),
+        "fdr_plan_pass_times": (ci, [vp, P(ci), _f32p, P(ctypes.c_char_p), P(ci)]),
+    }
+
+
+_SIGNATURES = _signatures()
+EXPORTED_SYMBOLS = tuple(_SIGNATURES)
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -127,106 +205,15 @@ def _load():
     except Exception:  # pragma: no cover - torch is optional for this binding
         pass
     L = ctypes.CDLL(LIB_PATH)
-    vp, ci, cf, cd, cu = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_double, ctypes.c_uint
-    L.fdr_version.restype = ci
-    L.fdr_last_error.restype = ctypes.c_char_p
-    L.fdr_device_count.argtypes = [ctypes.POINTER(ci)]
-    L.fdr_next_pow2.argtypes = [ci]
-    L.fdr_is_pow2.argtypes = [ci]
-    L.fdr_optimal_dft_size.argtypes = [ci]
-    L.fdr_plan_set_option.argtypes = [vp, ci, ctypes.c_longlong]
-    L.fdr_plan_phase_times.argtypes = [vp, _f32p, ci]
-    L.fdr_batch_run.argtypes = [ctypes.POINTER(BatchDesc), ctypes.POINTER(BatchStats)]
-    L.fdr_slab_pad_dev.argtypes = [vp, ci, ci, ci, vp, ci, ci, vp]
-    L.fdr_slab_rows_fft_dev.argtypes = [vp, vp, ci, ci, ci, vp]
-    L.fdr_slab_pack_dev.argtypes = [vp, ci, ci, ci, ctypes.POINTER(ci), ci, vp, vp]
-    L.fdr_slab_transpose_dev.argtypes = [vp, vp, ci, ci, ci, vp]
-    L.fdr_slab_wiener_dev.argtypes = [vp, vp, vp, ctypes.c_size_t, cf, vp]
-    L.fdr_slab_real_dev.argtypes = [vp, vp, ctypes.c_size_t, vp]
-    L.fdr_slab_minmax_dev.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp]
-    L.fdr_slab_normalize_dev.argtypes = [vp, ci, vp, vp, ci, ci, ci, vp]
-    L.fdr_plan_create.argtypes = [ci, ci, ci, ci, cu, ctypes.POINTER(vp)]
-    L.fdr_plan_destroy.argtypes = [vp]
-    L.fdr_plan_dims.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ci)]
-    L.fdr_psf_motion.argtypes = [ci, cd, vp]
-    L.fdr_psf_motion_dev.argtypes = [ci, ci, cd, vp, vp]
-    L.fdr_warp_affine_f32.argtypes = [vp, ci, ci, ci, ctypes.POINTER(cd), vp, ci, ci, ci]
-    L.fdr_plan_filter_bytes.argtypes = [vp, ctypes.POINTER(ctypes.c_size_t)]
-    L.fdr_plan_export_filter_dev.argtypes = [vp, vp, ctypes.c_size_t, vp]
-    L.fdr_plan_import_filter_dev.argtypes = [vp, vp, ctypes.c_size_t, cf, vp]
-    L.fdr_set_psf.argtypes = [vp, vp, ci, ci, ci, cf]
-    L.fdr_set_psf_dev.argtypes = [vp, vp, ci, ci, ci, cf, vp]
-    L.fdr_set_psf_motion.argtypes = [vp, ci, cd, cf, vp]
-    L.fdr_set_psf_cls.argtypes = [vp, vp, ci, ci, ci, cf, cf]
-    L.fdr_set_psf_cls_dev.argtypes = [vp, vp, ci, ci, ci, cf, cf, vp]
-    L.fdr_set_psf_motion_cls.argtypes = [vp, ci, cd, cf, cf, vp]
-    L.fdr_wiener_f32.argtypes = [vp, vp, ci, ci, ci, vp, ci, ci]
-    L.fdr_wiener_f32_dev.argtypes = [vp, vp, ci, ci, ci, vp, ci, ci, vp]
-    L.fdr_wiener_batch_f32_dev.argtypes = [vp, vp, ctypes.c_size_t, ci, ci, ci, ci, vp, ctypes.c_size_t, ci, ci, vp]
-    L.fdr_wiener_batch_f32.argtypes = [vp, vp, ctypes.c_size_t, ci, ci, ci, ci, vp, ctypes.c_size_t, ci, ci]
-    L.fdr_wiener_batch_ptrs_f32.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ci, ci, ci, ci, ci, ci]
-    L.fdr_host_alloc.argtypes = [ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p)]
-    L.fdr_host_free.argtypes = [vp]
-    L.fdr_white_balance_u8.argtypes = [ci, ctypes.POINTER(vp), ctypes.POINTER(vp), ci, ci, ci, vp, ci]
-    L.fdr_white_balance_u8_dev.argtypes = [ci, ctypes.POINTER(vp), ctypes.POINTER(vp), ci, ci, ci, vp, ci, vp]
-    L.fdr_plan_set_concurrency.argtypes = [vp, ci]
-    L.fdr_plan_set_batching.argtypes = [vp, ci, ci]
-    L.fdr_fft2d_c2c.argtypes = [vp, vp, ci]
-    L.fdr_fft2d_c2c_dev.argtypes = [vp, vp, ci, vp]
-    L.fdr_fft1d_c2c.argtypes = [vp, ci, ci, ci]
-    L.fdr_dft_naive_c2c.argtypes = [vp, ci, ci]
-    L.fdr_synth_image_dev.argtypes = [ci, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_size_t, vp, vp]
-    L.fdr_plan_profile.argtypes = [vp, ci]
-    L.fdr_set_operator_psf.argtypes = [vp, vp, ci, ci, ci]
-    L.fdr_set_operator_psf_dev.argtypes = [vp, vp, ci, ci, ci, vp]
-    L.fdr_set_operator_psf_motion.argtypes = [vp, ci, cd, vp]
-    L.fdr_blur_f32.argtypes = [vp, vp, ci, ci, ci, vp, ci, ci]
-    L.fdr_blur_f32_dev.argtypes = [vp, vp, ci, ci, ci, vp, ci, ci, vp]
-    L.fdr_richardson_lucy_f32.argtypes = [vp, vp, ci, ci, ci, vp, ci, ci, ci]
-    L.fdr_richardson_lucy_f32_dev.argtypes = [vp, vp, ci, ci, ci, vp, ci, ci, ci, vp]
-    L.fdr_richardson_lucy_free_f32.argtypes = [vp, vp, ci, ci, ci, vp, ci, vp, ci, ctypes.POINTER(RlFreeParams)]
-    L.fdr_richardson_lucy_free_f32_dev.argtypes = [vp, vp, ci, ci, ci, vp, ci, vp, ci, ctypes.POINTER(RlFreeParams), vp]
-    L.fdr_tv_deconv_f32.argtypes = [vp, vp, ci, ci, ci, vp, ci, ctypes.POINTER(TvParams)]
-    L.fdr_tv_deconv_f32_dev.argtypes = [vp, vp, ci, ci, ci, vp, ci, ctypes.POINTER(TvParams), vp]
-    L.fdr_cepstrum_f32.argtypes = [vp, vp, ci, ci, ci, vp]
-    L.fdr_cepstrum_f32_dev.argtypes = [vp, vp, ci, ci, ci, vp, vp]
-    L.fdr_estimate_motion_f32.argtypes = [vp, vp, ci, ci, ci, ci, ci, cd, ctypes.POINTER(MotionEstimateC), vp]
-    L.fdr_estimate_motion_f32_dev.argtypes = [vp, vp, ci, ci, ci, ci, ci, cd, ctypes.POINTER(MotionEstimateC), vp, vp]
-    L.fdr_plan_pass_times.argtypes = [vp, ctypes.POINTER(ci), _f32p, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ci)]
-    for name in ("fdr_device_count", "fdr_next_pow2", "fdr_is_pow2", "fdr_plan_create", "fdr_plan_destroy", "fdr_plan_dims",
-                 "fdr_psf_motion", "fdr_psf_motion_dev", "fdr_set_psf", "fdr_set_psf_dev", "fdr_set_psf_motion",
-                 "fdr_wiener_f32", "fdr_wiener_f32_dev", "fdr_wiener_batch_f32_dev", "fdr_wiener_batch_f32", "fdr_wiener_batch_ptrs_f32", "fdr_host_alloc", "fdr_host_free",
-                 "fdr_white_balance_u8", "fdr_white_balance_u8_dev", "fdr_plan_set_concurrency", "fdr_plan_set_batching",
-                 "fdr_fft2d_c2c", "fdr_fft2d_c2c_dev", "fdr_fft1d_c2c", "fdr_dft_naive_c2c", "fdr_synth_image_dev", "fdr_plan_profile", "fdr_plan_pass_times",
-                 "fdr_optimal_dft_size", "fdr_plan_set_option", "fdr_plan_phase_times", "fdr_batch_run",
-                 "fdr_slab_pad_dev", "fdr_slab_rows_fft_dev", "fdr_slab_pack_dev", "fdr_slab_transpose_dev", "fdr_slab_wiener_dev",
-                 "fdr_slab_real_dev", "fdr_slab_minmax_dev", "fdr_slab_normalize_dev", "fdr_warp_affine_f32",
-                 "fdr_plan_filter_bytes", "fdr_plan_export_filter_dev", "fdr_plan_import_filter_dev",
-                 "fdr_set_psf_cls", "fdr_set_psf_cls_dev", "fdr_set_psf_motion_cls", "fdr_set_operator_psf", "fdr_set_operator_psf_dev",
-                 "fdr_set_operator_psf_motion", "fdr_blur_f32", "fdr_blur_f32_dev", "fdr_richardson_lucy_f32", "fdr_richardson_lucy_f32_dev",
-                 "fdr_richardson_lucy_free_f32", "fdr_richardson_lucy_free_f32_dev",
-                 "fdr_tv_deconv_f32", "fdr_tv_deconv_f32_dev", "fdr_cepstrum_f32", "fdr_cepstrum_f32_dev", "fdr_estimate_motion_f32", "fdr_estimate_motion_f32_dev"):
-        getattr(L, name).restype = ci
+    for name, (restype, argtypes) in _SIGNATURES.items():
+        fn = getattr(L, name)
+        fn.restype = restype
+        if argtypes is not None:
+            fn.argtypes = argtypes
     return L
 
 
 lib = _load()
-
-EXPORTED_SYMBOLS = (
-    "fdr_version", "fdr_last_error", "fdr_device_count", "fdr_next_pow2", "fdr_is_pow2", "fdr_plan_create",
-    "fdr_plan_destroy", "fdr_plan_dims", "fdr_psf_motion", "fdr_psf_motion_dev", "fdr_set_psf", "fdr_set_psf_dev",
-    "fdr_set_psf_motion", "fdr_wiener_f32", "fdr_wiener_f32_dev", "fdr_wiener_batch_f32_dev", "fdr_wiener_batch_f32", "fdr_wiener_batch_ptrs_f32",
-    "fdr_host_alloc", "fdr_host_free", "fdr_white_balance_u8", "fdr_white_balance_u8_dev", "fdr_plan_set_concurrency",
-    "fdr_plan_set_batching", "fdr_fft2d_c2c",
-    "fdr_fft2d_c2c_dev", "fdr_fft1d_c2c", "fdr_dft_naive_c2c", "fdr_synth_image_dev", "fdr_plan_profile",
-    "fdr_plan_pass_times", "fdr_optimal_dft_size", "fdr_plan_set_option", "fdr_plan_phase_times", "fdr_batch_run",
-    "fdr_slab_pad_dev", "fdr_slab_rows_fft_dev", "fdr_slab_pack_dev", "fdr_slab_transpose_dev", "fdr_slab_wiener_dev",
-    "fdr_slab_real_dev", "fdr_slab_minmax_dev", "fdr_slab_normalize_dev", "fdr_warp_affine_f32",
-    "fdr_plan_filter_bytes", "fdr_plan_export_filter_dev", "fdr_plan_import_filter_dev",
-    "fdr_set_psf_cls", "fdr_set_psf_cls_dev", "fdr_set_psf_motion_cls", "fdr_set_operator_psf", "fdr_set_operator_psf_dev",
-    "fdr_set_operator_psf_motion", "fdr_blur_f32", "fdr_blur_f32_dev", "fdr_richardson_lucy_f32", "fdr_richardson_lucy_f32_dev",
-    "fdr_richardson_lucy_free_f32", "fdr_richardson_lucy_free_f32_dev",
-    "fdr_tv_deconv_f32", "fdr_tv_deconv_f32_dev", "fdr_cepstrum_f32", "fdr_cepstrum_f32_dev", "fdr_estimate_motion_f32", "fdr_estimate_motion_f32_dev")
 
 
 def _check(rc):

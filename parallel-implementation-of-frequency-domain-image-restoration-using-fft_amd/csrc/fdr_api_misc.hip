@@ -6,7 +6,14 @@ using namespace fdr;
 
 namespace {
 
-// `rows` transforms of L = 2^logl > 8192 points held contiguously in `buf`, `tmp` of the same size free: see fdr_aux.hip
+// The table a power-of-two row kernel reads, of the two of its length and mode.  The register kernels (launch_rows) take the forward
+// table in fast mode and conjugate it themselves; in parity mode they take the table of the direction, as simple_rows_kernel and
+// the long stages do in either mode.
+const float2* row_table(bool register_kernels, int mode, bool inverse, const float2* twf, const float2* twi) {
+    return (register_kernels && mode == FDR_MODE_FAST) || !inverse ? twf : twi;
+}
+
+// `rows` transforms of L = 2^logl > 8192 points held contiguously in `buf`, `tmp` of the same size free: see fdr_simple.hip
 // (long_gather_kernel).  twf / twi: the forward / inverse tables of the plan's mode for length L (their first 8191 entries
 // are the tables of the 8192-point transform: build_twiddles stores stage `len` at offset len/2 - 1).  Result in `buf`.
 hipError_t long_rows_dev(float2* buf, float2* tmp, size_t rows, int L, int logl, int mode, bool inverse, const float2* twf, const float2* twi,
@@ -17,15 +24,29 @@ hipError_t long_rows_dev(float2* buf, float2* tmp, size_t rows, int L, int logl,
     if (e != hipSuccess) return e;
     RowArgs ra{};
     ra.src_c = tmp; ra.dst_c = tmp; ra.M = (int)(rows << logs);
-    // the register kernels: parity -> the table of the direction; fast -> the forward table (they conjugate it)
-    e = launch_rows(kMaxLdsLog, mode, ROW_IN_COMPLEX, ROW_OUT_COMPLEX, inverse, ra, mode == FDR_MODE_FAST ? twf : (inverse ? twi : twf), s);
+    e = launch_rows(kMaxLdsLog, mode, ROW_IN_COMPLEX, ROW_OUT_COMPLEX, inverse, ra, row_table(true, mode, inverse, twf, twi), s);
     if (e != hipSuccess) return e;
     for (int half = L0; half < L; half <<= 1) {  // in place in `tmp` (a butterfly reads and writes its own pair), the last one into `buf`
         const bool last = (half << 1) == L;
-        e = launch_long_stage(tmp, last ? buf : tmp, rows, L, half, inverse ? twi : twf, mode, s);
+        e = launch_long_stage(tmp, last ? buf : tmp, rows, L, half, row_table(false, mode, inverse, twf, twi), mode, s);
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+// The one power-of-two row pass: `rows` transforms of length L = 2^logl that lie contiguously in `buf`, in place.  twf / twi: both
+// tables of the mode for length L.  More than 8192 points: 8192-point blocks + global radix-2 stages through `tmp` (rows x L, needed
+// only there); 8 points and more: the register kernels; fewer: simple_rows_kernel.  `simple_kernel` keeps simple_rows_kernel for
+// every length up to 8192: the reference-shaped plans (FDR_FLAG_SIMPLE_PATH, the on-device cross-check).
+hipError_t pow2_rows_dev(float2* buf, float2* tmp, int rows, int L, int logl, int mode, bool inverse, const float2* twf, const float2* twi,
+                         bool simple_kernel, hipStream_t s) {
+    if (logl > kMaxLdsLog) return long_rows_dev(buf, tmp, (size_t)rows, L, logl, mode, inverse, twf, twi, s);
+    if (L >= 8 && !simple_kernel) {
+        RowArgs ra{};
+        ra.src_c = buf; ra.dst_c = buf; ra.M = rows;
+        return launch_rows(logl, mode, ROW_IN_COMPLEX, ROW_OUT_COMPLEX, inverse, ra, row_table(true, mode, inverse, twf, twi), s);
+    }
+    return launch_simple_rows(buf, rows, L, logl, row_table(false, mode, inverse, twf, twi), mode, s);
 }
 
 // unscaled 2-D transform of the row-major M x N array d: rows into the panel-major scratch, columns back into d
@@ -65,41 +86,30 @@ ColArgs panel_col_args(const fdr_plan* p) {
 }
 
 int dft2d_dev(fdr_plan* p, float2* d, float2* work2, bool inverse, hipStream_t s) {
-    const float2* twr = inverse ? p->tw_row_i : p->tw_row_f;
-    const float2* twc = inverse ? p->tw_col_i : p->tw_col_f;
     if (p->path == PATH_MIXED) return mixed_fft2d_dev(p, d, p->slots[0].work, inverse, s);
     if (p->path == PATH_SIMPLE) {  // the reference's own sequence: rows, transpose, rows, transpose (fft/fft_serial.cpp:113-139)
         // one row pass over `rows` rows of length L held in `buf`, `tmp` free: radix-2 for powers of two, else the naive
         // DFT (transform_row_inplace, :100-101), which runs out of place and is copied back
-        auto row_pass = [&](float2* buf, float2* tmp, int rows, int L, int logl, const float2* tw, const float2* twf, const float2* twi,
-                            const float2* naive) -> int {
+        const bool simple_kernel = !(p->generic || p->big);  // FDR_FLAG_SIMPLE_PATH plans and plans with a dimension below 8
+        auto row_pass = [&](float2* buf, float2* tmp, int rows, int L, int logl, const float2* twf, const float2* twi, const float2* naive) -> int {
             if (naive) {
                 FDR_HIP(launch_dft_naive_rows(buf, tmp, rows, L, naive, inverse ? 1 : 0, s));
                 FDR_HIP(hipMemcpyAsync(buf, tmp, (size_t)rows * L * sizeof(float2), hipMemcpyDeviceToDevice, s));
-            } else if (logl > kMaxLdsLog) {  // more than 8192 points: 8192-point blocks + global radix-2 stages
-                FDR_HIP(long_rows_dev(buf, tmp, (size_t)rows, L, logl, p->mode, inverse, twf, twi, s));
-            } else if ((p->generic || p->big) && L >= 8) {
-                // register kernels, in place (parity: the table of the direction; fast: the forward table, they conjugate it)
-                RowArgs ra{};
-                ra.src_c = buf; ra.dst_c = buf; ra.M = rows;
-                FDR_HIP(launch_rows(logl, p->mode, ROW_IN_COMPLEX, ROW_OUT_COMPLEX, inverse, ra, p->mode == FDR_MODE_FAST ? twf : tw, s));
             } else {
-                FDR_HIP(launch_simple_rows(buf, rows, L, logl, tw, p->mode, s));
+                FDR_HIP(pow2_rows_dev(buf, tmp, rows, L, logl, p->mode, inverse, twf, twi, simple_kernel, s));
             }
             return FDR_OK;
         };
-        int rc = row_pass(d, work2, p->M, p->N, p->logN, twr, p->tw_row_f, p->tw_row_i, p->naive_row);
+        int rc = row_pass(d, work2, p->M, p->N, p->logN, p->tw_row_f, p->tw_row_i, p->naive_row);
         if (rc != FDR_OK) return rc;
         FDR_HIP(launch_transpose(d, work2, p->M, p->N, s));
-        rc = row_pass(work2, d, p->N, p->M, p->logM, twc, p->tw_col_f, p->tw_col_i, p->naive_col);
+        rc = row_pass(work2, d, p->N, p->M, p->logM, p->tw_col_f, p->tw_col_i, p->naive_col);
         if (rc != FDR_OK) return rc;
         FDR_HIP(launch_transpose(work2, d, p->N, p->M, s));
         return FDR_OK;
     }
-    RowArgs ra{};
-    ra.src_c = d; ra.dst_c = d; ra.M = p->M;
-    FDR_HIP(launch_rows(p->logN, p->mode, ROW_IN_COMPLEX, ROW_OUT_COMPLEX, inverse, ra,
-                        p->mode == FDR_MODE_FAST ? p->tw_row_f : twr, s));
+    // the panel paths: N from 8 to 8192, the register kernels in place, then the column kernels
+    FDR_HIP(pow2_rows_dev(d, nullptr, p->M, p->N, p->logN, p->mode, inverse, p->tw_row_f, p->tw_row_i, false, s));
     ColArgs ca{};
     ca.data = d; ca.N = p->N;
     FDR_HIP(launch_cols(p->logM, p->mode, inverse ? COL_INV : COL_FWD, ca, p->tw_col_f, p->tw_col_i, s));
@@ -119,13 +129,11 @@ int fdr_psf_motion_dev(int device, int size, double angle_deg, float* d_out, voi
 
 int fdr_psf_motion(int size, double angle_deg, float* out_host) {
     if (size <= 0 || !out_host) return fail(FDR_ERR_ARG, "fdr_psf_motion: bad argument");
-    float* d = nullptr;
     const size_t bytes = (size_t)size * size * sizeof(float);
-    FDR_HIP(hipMalloc((void**)&d, bytes));
-    hipError_t e = launch_psf_motion(size, angle_deg, d, nullptr);
-    if (e == hipSuccess) e = hipMemcpy(out_host, d, bytes, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    FDR_HIP(e);
+    DeviceBuffer d;
+    FDR_ALLOC(d, bytes, "fdr_psf_motion");
+    FDR_HIP(launch_psf_motion(size, angle_deg, d.as<float>(), nullptr));
+    FDR_HIP(hipMemcpy(out_host, d.ptr, bytes, hipMemcpyDeviceToHost));
     return FDR_OK;
 }
 
@@ -135,15 +143,13 @@ int fdr_warp_affine_f32(const float* src_host, int srows, int scols, int sstride
         return fail(FDR_ERR_ARG, "fdr_warp_affine_f32: bad argument");
     if (srows > 32767 || scols > 32767 || drows > 32767 || dcols > 32767)
         return fail(FDR_ERR_ARG, "fdr_warp_affine_f32: image dimension above 32767 (cv::warpAffine's short coordinates)");
-    float *d_src = nullptr, *d_dst = nullptr;
     const size_t sb = (size_t)scols * sizeof(float), db = (size_t)dcols * sizeof(float);
-    FDR_HIP(hipMalloc((void**)&d_src, sb * srows));
-    if (hipMalloc((void**)&d_dst, db * drows) != hipSuccess) { (void)hipFree(d_src); return fail(FDR_ERR_ALLOC, "fdr_warp_affine_f32: hipMalloc"); }
-    hipError_t e = hipMemcpy2D(d_src, sb, src_host, (size_t)sstride * sizeof(float), sb, srows, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = launch_warp_affine(d_src, srows, scols, scols, M, d_dst, drows, dcols, dcols, nullptr);
-    if (e == hipSuccess) e = hipMemcpy2D(dst_host, (size_t)dstride * sizeof(float), d_dst, db, db, drows, hipMemcpyDeviceToHost);
-    (void)hipFree(d_src); (void)hipFree(d_dst);
-    FDR_HIP(e);
+    DeviceBuffer d_src, d_dst;
+    FDR_ALLOC(d_src, sb * srows, "fdr_warp_affine_f32");
+    FDR_ALLOC(d_dst, db * drows, "fdr_warp_affine_f32");
+    FDR_HIP(hipMemcpy2D(d_src.ptr, sb, src_host, (size_t)sstride * sizeof(float), sb, srows, hipMemcpyHostToDevice));
+    FDR_HIP(launch_warp_affine(d_src.as<float>(), srows, scols, scols, M, d_dst.as<float>(), drows, dcols, dcols, nullptr));
+    FDR_HIP(hipMemcpy2D(dst_host, (size_t)dstride * sizeof(float), d_dst.ptr, db, db, drows, hipMemcpyDeviceToHost));
     return FDR_OK;
 }
 
@@ -159,95 +165,69 @@ int fdr_fft2d_c2c_dev(fdr_plan* p, float* d_data, int inverse, void* stream) {
 int fdr_fft2d_c2c(fdr_plan* p, float* data_host, int inverse) {
     const char* fn = "fdr_fft2d_c2c";
     if (!p || !data_host) return null_arg(fn);
-    int rc = check_plan(p, fn, NEED_PLAN);
+    const int rc = check_plan(p, fn, NEED_PLAN);
     if (rc != FDR_OK) return rc;
     FDR_HIP(hipSetDevice(p->device));
     const size_t elems = (size_t)p->M * p->N, bytes = elems * sizeof(float2);
     // slot 0's spectrum is free between operator calls and serves as the staging buffer -- unless the plan keeps only the
     // half spectrum there (fast panel mode: about M*N/2 elements), where a full-size buffer is allocated for the call
     float2* buf = p->slots[0].work;
-    const bool own = p->ws_elems < elems || p->path == PATH_MIXED;  // (a mixed plan's transform uses that spectrum as its scratch)
-    if (own) FDR_HIP(hipMalloc((void**)&buf, bytes));
-    hipError_t e = hipMemcpy(buf, data_host, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) rc = dft2d_dev(p, buf, p->slots[0].work2, inverse != 0, nullptr);
-    if (e == hipSuccess && rc == FDR_OK) e = hipMemcpy(data_host, buf, bytes, hipMemcpyDeviceToHost);
-    if (own) (void)hipFree(buf);
-    if (rc != FDR_OK) return rc;
-    FDR_HIP(e);
+    DeviceBuffer own;
+    if (p->ws_elems < elems || p->path == PATH_MIXED) {  // (a mixed plan's transform uses that spectrum as its scratch)
+        FDR_ALLOC(own, bytes, fn);
+        buf = own.as<float2>();
+    }
+    FDR_HIP(hipMemcpy(buf, data_host, bytes, hipMemcpyHostToDevice));
+    const int rd = dft2d_dev(p, buf, p->slots[0].work2, inverse != 0, nullptr);
+    if (rd != FDR_OK) return rd;
+    FDR_HIP(hipMemcpy(data_host, buf, bytes, hipMemcpyDeviceToHost));
     return FDR_OK;
 }
 
 int fdr_dft_naive_c2c(float* data_host, int n, int inverse) {
+    const char* fn = "fdr_dft_naive_c2c";
     if (!data_host || n < 0) return fail(FDR_ERR_ARG, "fdr_dft_naive_c2c: bad argument");
     if (n <= 1) return FDR_OK;  // fft/fft_serial.cpp:74
-    float2 *a = nullptr, *b = nullptr, *tab = nullptr;
     const size_t bytes = (size_t)n * sizeof(float2);
-    FDR_HIP(hipMalloc((void**)&a, bytes));
-    if (hipMalloc((void**)&b, bytes) != hipSuccess) { (void)hipFree(a); return fail(FDR_ERR_ALLOC, "fdr_dft_naive_c2c: hipMalloc"); }
-    hipError_t e = hipMemcpy(a, data_host, bytes, hipMemcpyHostToDevice);
+    DeviceBuffer a, b, tab;
+    FDR_ALLOC(a, bytes, fn);
+    FDR_ALLOC(b, bytes, fn);
+    FDR_HIP(hipMemcpy(a.ptr, data_host, bytes, hipMemcpyHostToDevice));
     if (n <= kMaxNaiveLen) {  // host-generated twiddles: the bits of the serial path's cosf / sinf
         std::vector<float2> t;
         build_naive_table(n, t);
-        if (e == hipSuccess) e = hipMalloc((void**)&tab, t.size() * sizeof(float2));
-        if (e == hipSuccess) e = hipMemcpy(tab, t.data(), t.size() * sizeof(float2), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = launch_dft_naive_rows(a, b, 1, n, tab, inverse, nullptr);
-    } else if (e == hipSuccess) {
-        e = launch_dft_naive(a, b, n, inverse, nullptr);
+        FDR_ALLOC(tab, t.size() * sizeof(float2), fn);
+        FDR_HIP(hipMemcpy(tab.ptr, t.data(), t.size() * sizeof(float2), hipMemcpyHostToDevice));
+        FDR_HIP(launch_dft_naive_rows(a.as<float2>(), b.as<float2>(), 1, n, tab.as<float2>(), inverse, nullptr));
+    } else {
+        FDR_HIP(launch_dft_naive(a.as<float2>(), b.as<float2>(), n, inverse, nullptr));
     }
-    if (e == hipSuccess) e = hipMemcpy(data_host, b, bytes, hipMemcpyDeviceToHost);
-    (void)hipFree(a); (void)hipFree(b); (void)hipFree(tab);
-    FDR_HIP(e);
+    FDR_HIP(hipMemcpy(data_host, b.ptr, bytes, hipMemcpyDeviceToHost));
     return FDR_OK;
 }
 
 int fdr_fft1d_c2c(float* data_host, int n, int inverse, int mode) {
+    const char* fn = "fdr_fft1d_c2c";
     if (!data_host || n < 0) return fail(FDR_ERR_ARG, "fdr_fft1d_c2c: bad argument");
     if (mode != FDR_MODE_PARITY && mode != FDR_MODE_FAST) return fail(FDR_ERR_ARG, "fdr_fft1d_c2c: unknown mode");
     if (n <= 1) return FDR_OK;                                        // fft/fft_serial.cpp:43
     if (!fdr_is_pow2(n)) return fdr_dft_naive_c2c(data_host, n, inverse);  // fft/fft_serial.cpp:100-101
     if (n > (1 << kMaxLongLog)) return fail(FDR_ERR_ARG, "fdr_fft1d_c2c: power-of-two length above 32768");
-    std::vector<float2> t;
-    if (n > (1 << kMaxLdsLog)) {  // 8192-point blocks + global stages (fdr_aux.hip): both tables of the mode
-        std::vector<float2> ti;
-        build_twiddles(n, mode, false, t);
-        build_twiddles(n, mode, true, ti);
-        float2 *twf = nullptr, *twi = nullptr, *d = nullptr, *tmp = nullptr;
-        const size_t bytes = (size_t)n * sizeof(float2), tb = t.size() * sizeof(float2);
-        hipError_t e = hipMalloc((void**)&twf, tb);
-        if (e == hipSuccess) e = hipMalloc((void**)&twi, tb);
-        if (e == hipSuccess) e = hipMalloc((void**)&d, bytes);
-        if (e == hipSuccess) e = hipMalloc((void**)&tmp, bytes);
-        if (e == hipSuccess) e = hipMemcpy(twf, t.data(), tb, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(twi, ti.data(), tb, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(d, data_host, bytes, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = long_rows_dev(d, tmp, 1, n, ilog2(n), mode, inverse != 0, twf, twi, nullptr);
-        if (e == hipSuccess) e = hipMemcpy(data_host, d, bytes, hipMemcpyDeviceToHost);
-        (void)hipFree(twf); (void)hipFree(twi); (void)hipFree(d); (void)hipFree(tmp);
-        FDR_HIP(e);
-        return FDR_OK;
-    }
-    // the register kernels take the forward table in fast mode (they conjugate it); the simple kernel
-    // (n < 8) and parity mode take the table of the requested direction
-    build_twiddles(n, mode, (mode == FDR_MODE_FAST && n >= 8) ? false : (inverse != 0), t);
-    float2 *tw = nullptr, *d = nullptr;
-    const size_t bytes = (size_t)n * sizeof(float2);
-    FDR_HIP(hipMalloc((void**)&tw, t.size() * sizeof(float2)));
-    if (hipMalloc((void**)&d, bytes) != hipSuccess) { (void)hipFree(tw); return fail(FDR_ERR_ALLOC, "fdr_fft1d_c2c: hipMalloc"); }
-    hipError_t e = hipMemcpy(tw, t.data(), t.size() * sizeof(float2), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d, data_host, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        const int logn = ilog2(n);
-        if (n >= 8) {
-            RowArgs ra{};
-            ra.src_c = d; ra.dst_c = d; ra.M = 1;
-            e = launch_rows(logn, mode, ROW_IN_COMPLEX, ROW_OUT_COMPLEX, inverse != 0, ra, tw, nullptr);
-        } else {
-            e = launch_simple_rows(d, 1, n, logn, tw, mode, nullptr);
-        }
-    }
-    if (e == hipSuccess) e = hipMemcpy(data_host, d, bytes, hipMemcpyDeviceToHost);
-    (void)hipFree(tw); (void)hipFree(d);
-    FDR_HIP(e);
+    std::vector<float2> tf, ti;  // both tables of the mode: pow2_rows_dev picks the one its kernel reads
+    build_twiddles(n, mode, false, tf);
+    build_twiddles(n, mode, true, ti);
+    const bool is_long = n > (1 << kMaxLdsLog);
+    const size_t bytes = (size_t)n * sizeof(float2), tb = tf.size() * sizeof(float2);
+    DeviceBuffer twf, twi, d, tmp;
+    FDR_ALLOC(twf, tb, fn);
+    FDR_ALLOC(twi, tb, fn);
+    FDR_ALLOC(d, bytes, fn);
+    if (is_long) FDR_ALLOC(tmp, bytes, fn);
+    FDR_HIP(hipMemcpy(twf.ptr, tf.data(), tb, hipMemcpyHostToDevice));
+    FDR_HIP(hipMemcpy(twi.ptr, ti.data(), tb, hipMemcpyHostToDevice));
+    FDR_HIP(hipMemcpy(d.ptr, data_host, bytes, hipMemcpyHostToDevice));
+    FDR_HIP(pow2_rows_dev(d.as<float2>(), tmp.as<float2>(), 1, n, ilog2(n), mode, inverse != 0, twf.as<float2>(), twi.as<float2>(), false, nullptr));
+    FDR_HIP(hipMemcpy(data_host, d.ptr, bytes, hipMemcpyDeviceToHost));
     return FDR_OK;
 }
 
@@ -273,29 +253,25 @@ int fdr_white_balance_u8_dev(int device, const float* const d_orig_bgr[3], const
 
 int fdr_white_balance_u8(int device, const float* const orig_bgr[3], const float* const restored_bgr[3], int rows, int cols,
                          int stride, unsigned char* out_bgr8, int out_stride_bytes) {
+    const char* fn = "fdr_white_balance_u8";
     if (!orig_bgr || !restored_bgr || !out_bgr8) return fail(FDR_ERR_ARG, "fdr_white_balance_u8: null argument");
     if (rows <= 0 || cols <= 0 || stride < cols || out_stride_bytes < 3 * cols) return fail(FDR_ERR_ARG, "fdr_white_balance_u8: bad shape");
+    for (int c = 0; c < 3; ++c)
+        if (!orig_bgr[c] || !restored_bgr[c]) return fail(FDR_ERR_ARG, "fdr_white_balance_u8: null plane");
     FDR_HIP(hipSetDevice(device));
     const size_t plane = (size_t)rows * cols * sizeof(float), rowb = (size_t)cols * sizeof(float);
-    float* d = nullptr; unsigned char* d_out = nullptr;
-    FDR_HIP(hipMalloc((void**)&d, 6 * plane));
-    if (hipMalloc((void**)&d_out, (size_t)rows * cols * 3) != hipSuccess) { (void)hipFree(d); return fail(FDR_ERR_ALLOC, "fdr_white_balance_u8: hipMalloc"); }
+    DeviceBuffer d, d_out;
+    FDR_ALLOC(d, 6 * plane, fn);
+    FDR_ALLOC(d_out, (size_t)rows * cols * 3, fn);
     const float* dp[6];
-    hipError_t e = hipSuccess;
-    for (int c = 0; c < 6 && e == hipSuccess; ++c) {
-        const float* src = c < 3 ? orig_bgr[c] : restored_bgr[c - 3];
-        if (!src) { (void)hipFree(d); (void)hipFree(d_out); return fail(FDR_ERR_ARG, "fdr_white_balance_u8: null plane"); }
-        float* dst = d + (size_t)c * rows * cols;
+    for (int c = 0; c < 6; ++c) {
+        float* dst = d.as<float>() + (size_t)c * rows * cols;
         dp[c] = dst;
-        e = hipMemcpy2D(dst, rowb, src, (size_t)stride * sizeof(float), rowb, rows, hipMemcpyHostToDevice);
+        FDR_HIP(hipMemcpy2D(dst, rowb, c < 3 ? orig_bgr[c] : restored_bgr[c - 3], (size_t)stride * sizeof(float), rowb, rows, hipMemcpyHostToDevice));
     }
-    int rc = FDR_OK;
-    if (e == hipSuccess) rc = fdr_white_balance_u8_dev(device, dp, dp + 3, rows, cols, cols, d_out, 3 * cols, nullptr);
-    if (e == hipSuccess && rc == FDR_OK)
-        e = hipMemcpy2D(out_bgr8, (size_t)out_stride_bytes, d_out, (size_t)cols * 3, (size_t)cols * 3, rows, hipMemcpyDeviceToHost);
-    (void)hipFree(d); (void)hipFree(d_out);
+    const int rc = fdr_white_balance_u8_dev(device, dp, dp + 3, rows, cols, cols, d_out.as<unsigned char>(), 3 * cols, nullptr);
     if (rc != FDR_OK) return rc;
-    FDR_HIP(e);
+    FDR_HIP(hipMemcpy2D(out_bgr8, (size_t)out_stride_bytes, d_out.ptr, (size_t)cols * 3, (size_t)cols * 3, rows, hipMemcpyDeviceToHost));
     return FDR_OK;
 }
 
@@ -327,22 +303,12 @@ int fdr_slab_rows_fft_dev(fdr_plan* p, float* d_complex, int rows, int dim, int 
     hipStream_t s = (hipStream_t)stream;
     if (naive || !fdr_is_pow2(L)) return fail(FDR_ERR_ARG, "fdr_slab_rows_fft_dev: power-of-two dimensions only");
     float2* d = reinterpret_cast<float2*>(d_complex);
-    if (logl > kMaxLdsLog) {  // more than 8192 points: 8192-point blocks + global radix-2 stages (fdr_aux.hip); stream-ordered scratch
-        float2* tmp = nullptr;
-        FDR_HIP(hipMallocAsync((void**)&tmp, (size_t)rows * L * sizeof(float2), s));
-        const hipError_t e = long_rows_dev(d, tmp, (size_t)rows, L, logl, p->mode, inverse != 0, twf, twi, s);
-        (void)hipFreeAsync(tmp, s);
-        FDR_HIP(e);
-        return FDR_OK;
-    }
-    if (L >= 8) {
-        RowArgs ra{};
-        ra.src_c = d; ra.dst_c = d; ra.M = rows;
-        // fast mode: the register kernels take the forward table and conjugate it; parity: the table of the direction
-        FDR_HIP(launch_rows(logl, p->mode, ROW_IN_COMPLEX, ROW_OUT_COMPLEX, inverse != 0, ra, p->mode == FDR_MODE_FAST ? twf : (inverse ? twi : twf), s));
-    } else {
-        FDR_HIP(launch_simple_rows(d, rows, L, logl, inverse ? twi : twf, p->mode, s));
-    }
+    float2* tmp = nullptr;
+    const bool is_long = logl > kMaxLdsLog;  // 8192-point blocks + global radix-2 stages: stream-ordered scratch
+    if (is_long) FDR_HIP(hipMallocAsync((void**)&tmp, (size_t)rows * L * sizeof(float2), s));
+    const hipError_t e = pow2_rows_dev(d, tmp, rows, L, logl, p->mode, inverse != 0, twf, twi, false, s);
+    if (is_long) (void)hipFreeAsync(tmp, s);
+    FDR_HIP(e);
     return FDR_OK;
 }
 

@@ -196,7 +196,7 @@ void release_slot(fdr_plan::Slot& w) {
 int layout_radix2(fdr_plan* p, std::vector<float2>& t) {
     const int M = p->M, N = p->N;
     // dimensions above 8192 (one row no longer fits the LDS): the reference-shaped sequence rows / transpose / rows / transpose
-    // with the long row pass (fdr_aux.hip, long_gather_kernel) -- as the serial path, correct at any power of two and slower
+    // with the long row pass (fdr_simple.hip, long_gather_kernel) -- as the serial path, correct at any power of two and slower
     const bool simple = p->generic || (p->flags & FDR_FLAG_SIMPLE_PATH) != 0 || M < 8 || N < 8 || M > (1 << kMaxLdsLog) || N > (1 << kMaxLdsLog);
     const bool half = N >= 32 && (p->flags & FDR_FLAG_FULL_SPECTRUM) == 0;
     p->path = simple ? PATH_SIMPLE : p->mode == FDR_MODE_PARITY ? PATH_PARITY_PANEL : half ? PATH_FAST_HALF : PATH_FAST_FULL;

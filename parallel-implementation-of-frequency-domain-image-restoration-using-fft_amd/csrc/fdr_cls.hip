@@ -5,7 +5,7 @@
 // L is the symbol of the periodic 5-point Laplacian.  The plan keeps a_u = 4 sin^2(pi u / M) (u < M) followed by
 // b_v = 4 sin^2(pi v / N) (v < N) as a double table (fdr_api_wiener.hip, ensure_lap_table); cls_filter_fast / cls_reg
 // (fdr_fft_core.hpp) evaluate the quotient in double and round once, as the Wiener filter does.  Two of the four filter
-// sites live here, in a translation unit of their own so that the Wiener kernels of fdr_panel_cols.hip and fdr_aux.hip keep
+// sites live here, in a translation unit of their own so that the Wiener kernels of fdr_panel_cols.hip and fdr_simple.hip keep
 // their code: the PSF column pass of the panel path (half and full spectrum) and the pointwise filter of the simple path.
 // The mixed-radix site is the MIX_COLS_FILTER_CLS kind of fdr_mixed.hip.
 #include "fdr_panel.hpp"
@@ -110,7 +110,7 @@ hipError_t launch_cols_panel_cls(int logm, const ColArgs& a, const double* lap, 
     return hipErrorInvalidValue;
 }
 
-// ---- simple path: the CLS quotient on the row-major M x N spectrum (make_filter_fast_kernel of fdr_aux.hip); element i is bin
+// ---- simple path: the CLS quotient on the row-major M x N spectrum (make_filter_fast_kernel of fdr_simple.hip); element i is bin
 // (i / N, i % N) ----
 __global__ void make_filter_cls_kernel(const float2* __restrict__ H, float2* __restrict__ W, int M, int N, float K,
                                        const double* __restrict__ lap, double gamma) {

@@ -43,6 +43,21 @@ int null_arg(const char* fn);                   // FDR_ERR_ARG, "<fn>: null argu
         }                                                                                          \
     } while (0)
 
+// Device scratch of a one-shot host-pointer call: hipMalloc in alloc, hipFree when the scope ends, so every return is safe.
+struct DeviceBuffer {
+    void* ptr = nullptr;
+    DeviceBuffer() = default;
+    DeviceBuffer(DeviceBuffer&& o) noexcept : ptr(o.ptr) { o.ptr = nullptr; }  // move-only: no copy, no assignment
+    ~DeviceBuffer() { if (ptr) (void)hipFree(ptr); }
+    hipError_t alloc(size_t bytes) { return ptr ? hipErrorInvalidValue : hipMalloc(&ptr, bytes); }  // once: a second call would leak
+    template <class T> T* as() const { return static_cast<T*>(ptr); }
+};
+// buf.alloc(bytes) or return FDR_ERR_ALLOC, "<fn>: hipMalloc"
+#define FDR_ALLOC(buf, bytes, fn)                                                                           \
+    do {                                                                                                    \
+        if ((buf).alloc(bytes) != hipSuccess) return ::fdr::fail(FDR_ERR_ALLOC, std::string(fn) + ": hipMalloc"); \
+    } while (0)
+
 struct PassTimer {
     static constexpr int kMaxRecords = 8192;
     struct Rec { hipEvent_t a, b; int pass; };
@@ -83,7 +98,7 @@ struct fdr_plan {
     fdr::PlanPath path = fdr::PATH_SIMPLE;
     // facts next to the path: which row kernel PATH_SIMPLE uses (generic, big), and that there is no workspace (tables_only)
     bool generic = false;  // FDR_FLAG_ANY_SIZE with a non-power-of-two dimension: naive DFT along that dimension
-    bool big = false;  // a power-of-two dimension above 8192: simple sequence with the long row pass (fdr_aux.hip)
+    bool big = false;  // a power-of-two dimension above 8192: simple sequence with the long row pass (fdr_simple.hip)
     bool tables_only = false;  // FDR_FLAG_TABLES_ONLY: no workspaces, slab primitives only
     int num_cu = 256;
     float2 *naive_row = nullptr, *naive_col = nullptr;  // n x n tables of the non-power-of-two dimensions (length N / M)

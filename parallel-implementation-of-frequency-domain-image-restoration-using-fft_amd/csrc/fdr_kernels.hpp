@@ -195,12 +195,12 @@ hipError_t launch_motion_log(float2* plane, int M, int N, const double* sum, hip
 hipError_t launch_motion_score(const float2* plane, int M, int N, const double* trig, int n_angles, int min_length, int n_lengths, float* table,
                                hipStream_t s);
 
-// reference-shaped and auxiliary kernels (fdr_aux.hip)
+// the reference-shaped simple path and the free-standing transforms (fdr_simple.hip)
 hipError_t launch_pad_real_to_complex(const float* src, int rows, int cols, int stride, float2* dst, int M, int N,
                                       hipStream_t s);
 hipError_t launch_simple_rows(float2* data, int rows, int L, int logl, const float2* tw, int mode, hipStream_t s);
 hipError_t launch_transpose(const float2* src, float2* dst, int rows, int cols, hipStream_t s);
-// transforms of more than 8192 points (fdr_aux.hip): subsequences gathered into 8192-point blocks, and one radix-2 stage
+// transforms of more than 8192 points (fdr_simple.hip): subsequences gathered into 8192-point blocks, and one radix-2 stage
 // (butterfly distance `half`) over rows of length L in global memory; tw = table of the requested direction (both modes)
 constexpr int kMaxLdsLog = 13;    // longest transform the row / column kernels hold on chip
 constexpr int kMaxLongLog = 15;   // longest transform at all (32768 points)
@@ -212,6 +212,7 @@ hipError_t launch_make_filter_fast(const float2* H, float2* W, size_t count, flo
 hipError_t launch_make_filter_cls(const float2* H, float2* W, int M, int N, float K, const double* lap, double gamma, hipStream_t s);
 hipError_t launch_real_minmax(const float2* src, float* dst, int M, int N, int mm_rows, int mm_cols, float2* mm_part,
                               int* n_part, hipStream_t s);
+// min/max and normalisation (fdr_norm.hip)
 hipError_t launch_reduce_minmax(const float2* mm_part, int n_part, float* mm, hipStream_t s);
 // number of (min,max) partials the row / column real-output passes write for an M x N plan
 int rows_minmax_partials(int logl, int M);
@@ -222,12 +223,13 @@ hipError_t launch_normalize(const float* raw, int N, const float2* mm_part, int 
 // the same from a PANEL-major real plane (panel p = columns 4 p .. 4 p + 3, M rows of 4 floats, panels 4 M floats apart)
 hipError_t launch_normalize_panels(const float* raw, int M, const float2* mm_part, int n_part, const float* mm, float* out,
                                    int rows, int cols, int out_stride, hipStream_t s);
+// image utilities (fdr_image.hip: the motion PSF, the affine warp, launch_synth and launch_checksum below)
 hipError_t launch_psf_motion(int size, double angle_deg, float* d_out, hipStream_t s);
 // cv::warpAffine defaults (bilinear, constant 0 border) on a single-channel float image; fwd = the 2 x 3 matrix as cv::warpAffine takes it
 hipError_t launch_warp_affine(const float* src, int srows, int scols, int sstride, const double fwd[6], float* dst, int drows, int dcols,
                               int dstride, hipStream_t s);
 // slab mode (single image over several GPUs): column blocks of a row slab packed for the all-to-all, dense transposes
-// of 4- or 8-byte elements, real part, min/max partials of a real plane
+// of 4- or 8-byte elements (fdr_simple.hip), real part, min/max partials of a real plane (fdr_norm.hip)
 hipError_t launch_slab_pack(const void* src, int rows, int ld, int parts, const int* counts, int elem_size, void* dst, hipStream_t s);
 hipError_t launch_transpose_any(const void* src, void* dst, int rows, int cols, int elem_size, hipStream_t s);
 hipError_t launch_real_part(const float2* src, float* dst, size_t count, hipStream_t s);
@@ -248,7 +250,7 @@ hipError_t launch_synth(uint64_t seed, uint64_t first, size_t count, float* d_ou
 constexpr int kChecksumParts = 1024;
 hipError_t launch_checksum(const float* x, size_t count, double* part, hipStream_t s);
 hipError_t launch_dft_naive(const float2* src, float2* dst, int n, int inverse, hipStream_t s);
-// table[t * n + k], forward direction, host generated (see fdr_aux.hip); rows transforms of length n, src != dst
+// table[t * n + k], forward direction, host generated (see fdr_simple.hip); rows transforms of length n, src != dst
 hipError_t launch_dft_naive_rows(const float2* src, float2* dst, int rows, int n, const float2* table, int inverse, hipStream_t s);
 
 // mixed-radix fast mode (fdr_mixed.hip, FDR_FLAG_MIXED_RADIX): transform lengths 2^a 3^b 5^c up to 8192, rows in LDS

@@ -697,7 +697,7 @@ def test_one_gpu_shard_of_config5_every_image(fdr, oracle):
 def test_lengths_above_8192_follow_the_serial_path(fdr, oracle, shape):
     """fft_serial::transform_row_inplace takes ANY length (fft/fft_serial.cpp:90-108: radix-2 for every power of two), so a
     9000-pixel-wide picture pads to 16384 and works through ./serial; here the same through the library: 8192-point blocks
-    on chip plus radix-2 stages in global memory (csrc/fdr_aux.hip, long_gather_kernel), the reference's sequence rows /
+    on chip plus radix-2 stages in global memory (csrc/fdr_simple.hip, long_gather_kernel), the reference's sequence rows /
     transpose / rows / transpose.  Parity mode: bit-identical to the oracle, 2-D transform and whole operator; fast mode:
     within 1e-4."""
     rows, cols = shape

@@ -129,6 +129,49 @@ def test_new_entry_points_validate_arguments_before_device_work(fdr):
     assert L.fdr_plan_create(0, 5000, 64, 0, fdr.FLAG_ANY_SIZE, ctypes.byref(h)) == -1     # ... and too long for the naive-DFT table
 
 
+def test_one_shot_host_calls_refuse_before_device_work(fdr):
+    """The host-pointer calls that allocate their own device scratch (fdr_psf_motion, fdr_warp_affine_f32, fdr_fft2d_c2c,
+    fdr_dft_naive_c2c, fdr_fft1d_c2c, fdr_white_balance_u8): every refusal comes before the first HIP call (so this runs
+    without a GPU), with its code and its text; lengths 0 and 1 are transforms that do nothing."""
+    L = fdr.lib
+    err = L.fdr_last_error
+    buf = (ctypes.c_float * 16)()
+    p = ctypes.cast(buf, ctypes.c_void_p)
+    m = (ctypes.c_double * 6)(1, 0, 0, 0, 1, 0)
+    assert L.fdr_psf_motion(5, 30.0, None) == -1 and err() == b"fdr_psf_motion: bad argument"
+    assert L.fdr_psf_motion(-1, 30.0, p) == -1 and err() == b"fdr_psf_motion: bad argument"
+    assert L.fdr_warp_affine_f32(p, 2, 2, 1, m, p, 2, 2, 2) == -1 and err() == b"fdr_warp_affine_f32: bad argument"  # stride < cols
+    assert L.fdr_warp_affine_f32(p, 2, 2, 2, None, p, 2, 2, 2) == -1 and err() == b"fdr_warp_affine_f32: bad argument"
+    assert L.fdr_warp_affine_f32(p, 2, 2, 2, m, p, 0, 2, 2) == -1 and err() == b"fdr_warp_affine_f32: bad argument"
+    for shape in ((32768, 2, 2, 2), (2, 32768, 2, 2), (2, 2, 32768, 2), (2, 2, 2, 32768)):
+        sr, sc, dr, dc = shape
+        assert L.fdr_warp_affine_f32(p, sr, sc, sc, m, p, dr, dc, dc) == -1
+        assert err() == b"fdr_warp_affine_f32: image dimension above 32767 (cv::warpAffine's short coordinates)"
+    assert L.fdr_fft2d_c2c(None, p, 0) == -1 and err() == b"fdr_fft2d_c2c: null argument"
+    assert L.fdr_dft_naive_c2c(None, 4, 0) == -1 and err() == b"fdr_dft_naive_c2c: bad argument"
+    assert L.fdr_dft_naive_c2c(p, -1, 0) == -1 and err() == b"fdr_dft_naive_c2c: bad argument"
+    assert L.fdr_dft_naive_c2c(p, 0, 0) == 0 and L.fdr_dft_naive_c2c(p, 1, 1) == 0
+    assert L.fdr_fft1d_c2c(None, 8, 0, 0) == -1 and err() == b"fdr_fft1d_c2c: bad argument"
+    assert L.fdr_fft1d_c2c(p, -8, 0, 0) == -1 and err() == b"fdr_fft1d_c2c: bad argument"
+    assert L.fdr_fft1d_c2c(p, 8, 0, 2) == -1 and err() == b"fdr_fft1d_c2c: unknown mode"
+    assert L.fdr_fft1d_c2c(p, 65536, 0, 1) == -1 and err() == b"fdr_fft1d_c2c: power-of-two length above 32768"
+    assert L.fdr_fft1d_c2c(p, 0, 0, 0) == 0 and L.fdr_fft1d_c2c(p, 1, 1, 1) == 0
+    assert list(buf) == [0.0] * 16
+    # the colour epilogue: null arrays, a bad shape, and a null plane -- refused before anything is allocated
+    out = (ctypes.c_ubyte * 48)()
+    po = ctypes.cast(out, ctypes.c_void_p)
+    planes = (ctypes.c_void_p * 3)(p.value, p.value, p.value)
+    assert L.fdr_white_balance_u8(0, None, planes, 2, 2, 2, po, 6) == -1 and err() == b"fdr_white_balance_u8: null argument"
+    assert L.fdr_white_balance_u8(0, planes, planes, 2, 2, 2, None, 6) == -1 and err() == b"fdr_white_balance_u8: null argument"
+    assert L.fdr_white_balance_u8(0, planes, planes, 2, 2, 1, po, 6) == -1 and err() == b"fdr_white_balance_u8: bad shape"
+    assert L.fdr_white_balance_u8(0, planes, planes, 2, 2, 2, po, 5) == -1 and err() == b"fdr_white_balance_u8: bad shape"
+    for hole in range(3):
+        holed = (ctypes.c_void_p * 3)(*[None if c == hole else p.value for c in range(3)])
+        assert L.fdr_white_balance_u8(0, holed, planes, 2, 2, 2, po, 6) == -1 and err() == b"fdr_white_balance_u8: null plane"
+        assert L.fdr_white_balance_u8(0, planes, holed, 2, 2, 2, po, 6) == -1 and err() == b"fdr_white_balance_u8: null plane"
+    assert bytes(out) == bytes(48)
+
+
 def test_no_cpu_fallback_in_product_package():
     """The product path must not reach into oracle/ (or any numpy FFT) -- checked textually."""
     pkg_dir = os.path.join(ROOT, PKG)
