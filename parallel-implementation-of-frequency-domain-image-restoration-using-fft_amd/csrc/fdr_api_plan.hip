@@ -8,6 +8,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
+#include <cstring>
 #include <mutex>
 #include <new>
 
@@ -126,46 +127,7 @@ namespace {
 
 std::atomic<bool> g_process_exiting{false};  // set by an atexit handler that runs before the HIP runtime's own (fdr_plan_destroy)
 
-bool is_smooth(int n) {  // 2^a 3^b 5^c
-    if (n <= 0) return false;
-    for (int f : {2, 3, 5})
-        while (n % f == 0) n /= f;
-    return n == 1;
-}
-
-// Stockham schedule of a length 2^a 3^b 5^c (radix 4 first, then 2, 3, 5) and the twiddle table exp(-2 pi i m / L) in two
-// levels (w^m = lo[m mod 64] hi[m / 64], each entry evaluated in double and rounded once); per stage {radix, ns, ceil(2^32 / ns) (0 for ns = 1), L / (ns radix)}
-void build_mixed_tables(int L, std::vector<float2>& tw, std::vector<int4>& st) {
-    const double PI = 3.1415926535897932384626433832795;
-    const int nhi = (L + kMixTwLo - 1) / kMixTwLo;
-    tw.resize((size_t)(kMixTwLo + nhi));
-    for (int i = 0; i < kMixTwLo + nhi; ++i) {  // two levels (LDS-sized): lo[i] = w^i, hi[i] = w^(64 i)
-        const double m = i < kMixTwLo ? (double)i : (double)kMixTwLo * (i - kMixTwLo);
-        const double a = -2.0 * PI * m / (double)L;
-        tw[i] = make_float2((float)cos(a), (float)sin(a));
-    }
-    std::vector<int> radix;
-    int r = L;
-    while (r % 4 == 0) { radix.push_back(4); r /= 4; }
-    while (r % 2 == 0) { radix.push_back(2); r /= 2; }
-    while (r % 3 == 0) { radix.push_back(3); r /= 3; }
-    while (r % 5 == 0) { radix.push_back(5); r /= 5; }
-    st.clear();
-    int ns = 1;
-    for (int R : radix) {
-        const unsigned magic = ns == 1 ? 0u : (unsigned)((0x100000000ull + (unsigned long long)ns - 1) / (unsigned long long)ns);
-        st.push_back(make_int4(R, ns, (int)magic, L / (ns * R)));
-        ns *= R;
-    }
-}
-
-// threads per transform of length L: a multiple of 64 with L <= kMixMaxElems * nt
-int mixed_threads(int L) {
-    int nt = (L + kMixMaxElems - 1) / kMixMaxElems;
-    nt = (nt + 63) / 64 * 64;
-    return nt < 64 ? 64 : nt;
-}
-constexpr size_t kMixLdsTarget = 78 * 1024;  // two workgroups per CU (with the static twiddle / reduction arrays)
+static_assert(sizeof(MixTwiddle) == sizeof(float2) && sizeof(MixStage) == sizeof(int4), "fdr_mixed_plan.hpp: the kernels read float2 / int4");
 
 int upload(float2** dst, const std::vector<float2>& v) {
     FDR_HIP(hipMalloc((void**)dst, v.size() * sizeof(float2)));
@@ -228,17 +190,19 @@ int layout_radix2(fdr_plan* p, std::vector<float2>& t) {
     return upload(&p->naive_col, t);
 }
 
-// FDR_FLAG_MIXED_RADIX: both lengths' tables, panel width P (divides N, a panel of M rows within kMixLdsTarget) and row-pass
-// transforms per workgroup B
+// FDR_FLAG_MIXED_RADIX: both lengths' tables, panel width P and row-pass transforms per workgroup B (fdr_mixed_plan.hpp)
 int layout_mixed(fdr_plan* p, std::vector<float2>& t) {
     const int M = p->M, N = p->N;
     p->path = PATH_MIXED;
-    std::vector<int4> st;
+    std::vector<MixTwiddle> tw;
+    std::vector<MixStage> st;
     for (int d = 0; d < 2; ++d) {
         const int L = d == 0 ? N : M;
         MixLen& ml = d == 0 ? p->mix_row : p->mix_col;
         if (d == 1 && M == N) { ml = p->mix_row; break; }
-        build_mixed_tables(L, t, st);
+        build_mixed_tables(L, tw, st);
+        t.resize(tw.size());
+        std::memcpy(t.data(), tw.data(), tw.size() * sizeof(float2));
         const int rc = upload(const_cast<float2**>(&ml.tw), t);
         if (rc != FDR_OK) return rc;
         int4* dst = nullptr;
@@ -247,14 +211,10 @@ int layout_mixed(fdr_plan* p, std::vector<float2>& t) {
         if (!st.empty()) FDR_HIP(hipMemcpy(dst, st.data(), st.size() * sizeof(int4), hipMemcpyHostToDevice));
         ml.L = L; ml.nst = (int)st.size(); ml.nt = mixed_threads(L);
     }
-    p->mix_logP = 0;
-    for (int lp = 2; lp > 0; --lp) {
-        const int P = 1 << lp;
-        if (N % P == 0 && ((size_t)M * P * sizeof(float2) <= kMixLdsTarget) && p->mix_col.nt * P <= 1024) { p->mix_logP = lp; break; }
-    }
-    p->mix_P = 1 << p->mix_logP;
-    p->mix_B = 1;
-    while (p->mix_B < 16 && p->mix_row.nt * p->mix_B * 2 <= 1024 && (size_t)N * p->mix_B * 2 * sizeof(float2) <= kMixLdsTarget) p->mix_B *= 2;
+    const MixLayout lay = mixed_layout(M, N);
+    p->mix_logP = lay.logP;
+    p->mix_P = 1 << lay.logP;
+    p->mix_B = lay.B;
     p->pstride = (size_t)M * p->mix_P;
     p->npanels = N / p->mix_P;
     p->ws_elems = (size_t)p->npanels * p->pstride;

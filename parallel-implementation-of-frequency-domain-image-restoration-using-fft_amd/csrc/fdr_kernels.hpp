@@ -5,6 +5,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "fdr_mixed_plan.hpp"
+
 namespace fdr {
 
 enum RowIn { ROW_IN_REAL = 0, ROW_IN_COMPLEX = 1 };
@@ -254,10 +256,7 @@ hipError_t launch_dft_naive(const float2* src, float2* dst, int n, int inverse, 
 hipError_t launch_dft_naive_rows(const float2* src, float2* dst, int rows, int n, const float2* table, int inverse, hipStream_t s);
 
 // mixed-radix fast mode (fdr_mixed.hip, FDR_FLAG_MIXED_RADIX): transform lengths 2^a 3^b 5^c up to 8192, rows in LDS
-constexpr int kMixMaxElems = 16;              // values one thread holds per stage: threads per transform nt >= L / 16
-constexpr size_t kMixMaxLds = 144 * 1024;     // dynamic LDS of one workgroup (the rest: twiddles, reduction)
-constexpr int kMixMaxLen = 8192;
-constexpr int kMixTwLo = 64;                  // twiddle table = lo[64] then hi[ceil(L / 64)]: w^m = lo[m % 64] hi[m / 64]
+// (kMixMaxElems, kMixMaxLds, kMixMaxLen, kMixTwLo and the host-built tables: fdr_mixed_plan.hpp)
 struct MixLen {            // one transform length, device tables built by the plan
     const float2* tw;      // exp(-2 pi i m / L) as lo[i] = m = i (i < 64), hi[i] = m = 64 i (i < ceil(L / 64)); double-generated
     const int4* st;        // per Stockham stage {radix, ns (product of the earlier radices), ceil(2^32 / ns) or 0 for ns = 1, L / (ns radix)}

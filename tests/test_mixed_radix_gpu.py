@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
-from _mixed_model import optimal_size, wiener_model
+from _mixed_model import LINE_TOL, PEAK_TOL, line_errors, optimal_size, wiener_model
 
 pytestmark = pytest.mark.gpu
 
@@ -49,6 +49,11 @@ def test_fft2d_against_numpy(fdr, shape):
     want_i = np.fft.ifft2(x128) * (M * N)
     assert np.linalg.norm(inv - want_i) / np.linalg.norm(want_i) <= 1e-5
     assert np.linalg.norm(back - x128) / np.linalg.norm(x128) <= 1e-5
+    # ... and line by line: every single row and column of the forward and inverse transforms, and the largest error of the
+    # plane (the thresholds of test_mixed_lengths_gpu.py)
+    for name, got, ref in (("forward", fwd, want), ("inverse", inv, want_i)):
+        line, peak, where = line_errors(got, ref)
+        assert line <= LINE_TOL and peak <= PEAK_TOL, (name, line, where, peak)
 
 
 @pytest.mark.parametrize("shape", [(30, 50), (45, 100), (97, 33), (6, 10), (200, 300), (250, 180)])
