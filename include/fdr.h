@@ -385,6 +385,84 @@ int fdr_estimate_motion_f32(fdr_plan* plan, const float* img_host, int rows, int
 int fdr_estimate_motion_f32_dev(fdr_plan* plan, const float* d_img, int rows, int cols, int stride, int min_length, int max_length,
                                 double angle_step_deg, fdr_motion_estimate* est, float* d_scores, void* stream);
 
+/* -- choosing the regularisation weight from the picture (Gonzalez & Woods section 5.9, Golub, Heath & Wahba
+ *    1979, Immerkaer 1996).  The plan is M x N, the image window rows x cols (row stride `stride`) at its top-left corner, pad(d) is
+ *    d on the window and 0 elsewhere, H the DFT2 of the operator PSF (fdr_set_operator_psf*), L(u, v) = 4 sin^2(pi u / M) +
+ *    4 sin^2(pi v / N).  For a pair (K, gamma) -- the arguments of fdr_set_psf_cls*, whose filter is W = conj(H) / (|H|^2 + K +
+ *    gamma L^2):
+ *        G = DFT2(pad(d));  P = |G|^2 / (M N)                            (sum over the full spectrum of P = sum of d^2)
+ *        t = K + gamma L^2;  den = |H|^2 + t;  q = den > 0 ? t / den : 0       (q = 1 - H W: what the filter leaves of the data)
+ *        rho(K, gamma)   = sum over all M N bins of P q^2                (= || pad(d) - blur(restored) ||^2, the residual energy)
+ *        trace(K, gamma) = sum over all M N bins of q
+ *        gcv(K, gamma)   = M N rho / trace^2                             (+inf when trace = 0)
+ *    P is a float per bin, computed from the fast-mode spectrum; q and every sum are double, taken in a fixed order.
+ *    The noise estimate: with the mask n = [[1,-2,1],[-2,4,-2],[1,-2,1]] and S = the sum over the (rows - 2)(cols - 2) interior
+ *    pixels of |(d * n)[i, j]| (the stencil and the sum in double, in a fixed order),
+ *        sigma = sqrt(pi / 2) S / (6 (rows - 2)(cols - 2))
+ *    Texture passes the mask: on finely textured pictures at low noise sigma comes out too large (2.4 times on this project's
+ *    textured test scene).
+ *    The search: one weight (`param`) runs over v_i = lo (hi / lo)^(i / (n_grid - 1)), i = 0 .. n_grid - 1, the other stays at
+ *    `fixed`.  `refine` times a new grid of n_grid log-spaced candidates is laid over a bracket [a, b], ends included.
+ *      FDR_REG_DISCREPANCY  the target is T = tau rows cols sigma^2.  rho(hi) = 0 (an all-zero window): value = hi, FDR_REG_AT_HIGH.
+ *                           rho(lo) >= T: value = lo, FDR_REG_AT_LOW.  rho(hi) < T: value = hi, FDR_REG_AT_HIGH.  (These three
+ *                           return after the first grid.)  Otherwise the bracket is [v_(i-1), v_i] for the first i with
+ *                           rho(v_i) >= T, in every round, and value = the point where the straight line through
+ *                           (log a, log rho(a)) and (log b, log rho(b)) of the last bracket meets log T (b when rho(a) = 0).
+ *      FDR_REG_GCV          i = argmin gcv(v_i), the lowest index on ties; the bracket is [v_max(i-1, 0), v_min(i+1, n_grid-1)];
+ *                           value = the argmin of the last round; FDR_REG_AT_LOW when it is lo, FDR_REG_AT_HIGH when it is hi.
+ *                           With the flat penalty (param K) GCV under-regularises by several dB: prefer the discrepancy
+ *                           principle there.
+ *    residual, trace and gcv of the choice are those of the candidate of the last round nearest to `value` (in log).
+ *    Plans: as for the operator -- FDR_MODE_FAST, M and N powers of two, 8 <= M <= 8192, 32 <= N <= 8192, neither
+ *    FDR_FLAG_SIMPLE_PATH nor FDR_FLAG_FULL_SPECTRUM; FDR_ERR_ARG before any device work for any other plan, FDR_ERR_STATE on a
+ *    tables-only plan or without an operator PSF.  FDR_ERR_ARG also for: null pointers; a window that does not fit or stride <
+ *    cols; rows or cols < 3 where the noise is estimated; negative or non-finite weights; lo >= hi or lo <= 0; n_grid outside
+ *    4 .. 64, refine outside 0 .. 8, n outside 1 .. 4096; an unknown method or param; negative (or non-finite) sigma or tau.  Every
+ *    refusal leaves the plan usable.  The first call on a plan allocates the workspace (the power plane: one float per
+ *    half-spectrum bin, partial sums, candidates), FDR_ERR_ALLOC with the plan intact when that fails; it is kept until
+ *    fdr_plan_destroy and later calls allocate nothing.  The Wiener / CLS filter, the operator tables and the workspaces of the other
+ *    calls stay as they were.  Padding is zeros: FDR_OPT_PAD_MODE is ignored.  Results are bit-identical from call to call.
+ *      fdr_noise_sigma_f32*  sigma of a picture; needs no plan.
+ *      fdr_reg_curve_f32*    residual[i] = rho(K[i], gamma[i]), trace[i] likewise, i < n; K, gamma, residual, trace are HOST arrays.
+ *      fdr_choose_reg_f32*   the search.  Zero fields of fdr_reg_params select the defaults (refine: -1).
+ *    Every _dev form takes the picture from device memory and is SYNCHRONOUS: it reads its results back, so it returns after its
+ *    work on `stream` is done.                                                                                                 */
+#define FDR_REG_DISCREPANCY 0
+#define FDR_REG_GCV 1
+#define FDR_REG_PARAM_K 0
+#define FDR_REG_PARAM_GAMMA 1
+#define FDR_REG_AT_LOW 1
+#define FDR_REG_AT_HIGH 2
+typedef struct fdr_reg_params {
+    int method;      /* FDR_REG_DISCREPANCY / FDR_REG_GCV */
+    int param;       /* which weight is searched: FDR_REG_PARAM_K / FDR_REG_PARAM_GAMMA */
+    float fixed;     /* the other weight, >= 0 */
+    float sigma;     /* discrepancy: noise standard deviation; 0 = estimate it (fdr_noise_sigma) */
+    float tau;       /* discrepancy: safety factor on the target; 0 = 1 */
+    double lo, hi;   /* search range, 0 < lo < hi; 0, 0 = 1e-8, 1e2 */
+    int n_grid;      /* candidates per round, 4 .. 64; 0 = 32 */
+    int refine;      /* refinement rounds, 0 .. 8; -1 = default 2 */
+} fdr_reg_params;
+typedef struct fdr_reg_choice {
+    double value;    /* the chosen weight: goes into fdr_set_psf_cls*(K, gamma) with `fixed` as the other */
+    double sigma;    /* the noise level used (estimated or given); 0 for GCV unless given */
+    double residual; /* rho at the candidate nearest to value in the last round */
+    double trace;
+    double gcv;
+    int flags;       /* FDR_REG_AT_LOW / _AT_HIGH: the range's end was taken */
+    int evaluations; /* candidates evaluated */
+} fdr_reg_choice;
+int fdr_noise_sigma_f32(int device, const float* img_host, int rows, int cols, int stride, double* sigma);
+int fdr_noise_sigma_f32_dev(int device, const float* d_img, int rows, int cols, int stride, double* sigma, void* stream);
+int fdr_reg_curve_f32(fdr_plan* plan, const float* img_host, int rows, int cols, int stride, const double* K, const double* gamma, int n,
+                      double* residual, double* trace);
+int fdr_reg_curve_f32_dev(fdr_plan* plan, const float* d_img, int rows, int cols, int stride, const double* K, const double* gamma, int n,
+                          double* residual, double* trace, void* stream);
+int fdr_choose_reg_f32(fdr_plan* plan, const float* img_host, int rows, int cols, int stride, const fdr_reg_params* params,
+                       fdr_reg_choice* choice);
+int fdr_choose_reg_f32_dev(fdr_plan* plan, const float* d_img, int rows, int cols, int stride, const fdr_reg_params* params,
+                           fdr_reg_choice* choice, void* stream);
+
 /* Host-pointer batch: `count` images at imgs_host + i*img_pitch, results to out_host + i*out_pitch (elements).
  * H2D copy, restoration and D2H copy of consecutive images overlap on three internal streams with three images in
  * flight -- the pinned-buffer / cudaMemcpyAsync pipeline fft/fft_gpu.cu:306-350,372-385 sets out to build.  Buffers

@@ -304,6 +304,38 @@ inline fdr_motion_estimate estimateMotionBlur(const Mat& gray, int min_length = 
     }
     return est;
 }
+// K or gamma of the Wiener / CLS filter for one blurred channel and its PSF (fdr_choose_reg_f32, include/fdr.h): by generalised
+// cross-validation or the discrepancy principle (method), searching K or gamma (param) with the other weight at `fixed`; sigma 0 =
+// estimated from the picture (discrepancy principle only).  Its own FDR_MODE_FAST plan (the one of richardsonLucy_RGB: each dimension
+// padded to the next power of two, at least 8 rows and 32 columns), made and freed inside the call.  The value goes into
+// set_cls_gamma / the K argument of the Wiener entry points.
+inline fdr_reg_choice chooseRegularisation(const Mat& channel, const Mat& psf, int method = FDR_REG_GCV, int param = FDR_REG_PARAM_GAMMA,
+                                           float fixed = 0.f, float sigma = 0.f) {
+    Mat src = channel.isContinuous() ? channel : channel.clone();
+    Mat psfc = psf.isContinuous() ? psf : psf.clone();
+    fdr_plan* plan = nullptr;
+    FDR_CHECK(fdr_plan_create(defaults().device, std::max(8, nextPowerOfTwo(src.rows)), std::max(32, nextPowerOfTwo(src.cols)), FDR_MODE_FAST, 0,
+                              &plan));
+    fdr_reg_params prm{};
+    prm.method = method; prm.param = param; prm.fixed = fixed; prm.sigma = sigma; prm.refine = -1;
+    fdr_reg_choice choice{};
+    int rc = fdr_set_operator_psf(plan, psfc.ptr<float>(0), psf.rows, psf.cols, psf.cols);
+    if (rc == FDR_OK) rc = fdr_choose_reg_f32(plan, src.ptr<float>(0), src.rows, src.cols, src.cols, &prm, &choice);
+    const std::string err = rc == FDR_OK ? std::string() : std::string(fdr_last_error());
+    fdr_plan_destroy(plan);
+    if (rc != FDR_OK) {
+        std::cerr << "Error: " << __FILE__ << ":" << __LINE__ << ", " << err << "\n";
+        exit(1);
+    }
+    return choice;
+}
+// Immerkaer's estimate of the noise standard deviation of a one-channel picture, at least 3 x 3 (fdr_noise_sigma_f32)
+inline double estimateNoiseSigma(const Mat& gray) {
+    Mat src = gray.isContinuous() ? gray : gray.clone();
+    double sigma = 0.0;
+    FDR_CHECK(fdr_noise_sigma_f32(defaults().device, src.ptr<float>(0), src.rows, src.cols, src.cols, &sigma));
+    return sigma;
+}
 // The operator exactly as fft_serial::wienerDeblur_myfft defines it (fft/fft_serial.cpp:141-261; the fft_gpu
 // declaration at fft/fft.hpp:44 has no body in the reference): pad to getOptimalDFTSize (2^a 3^b 5^c, :153-154 -- a
 // non-power-of-two dimension is transformed by the naive DFT, :100-101), restore, crop to img's size, normalise over

@@ -40,6 +40,12 @@ PAD_ZERO = 0      # zeros, as the reference pads (default)
 PAD_SMOOTH = 1    # a smooth periodic continuation of the picture (include/fdr.h, FDR_OPT_PAD_MODE)
 PHASES = ("alloc", "h2d", "pre", "compute", "d2h", "post")  # the reference Profiler's buckets, fft/fft_gpu.cu:17-57
 BATCH_MAX_DEVICES = 16
+REG_DISCREPANCY = 0  # Plan.choose_regularisation: residual energy = tau rows cols sigma^2 (Morozov; Gonzalez & Woods 5.9)
+REG_GCV = 1          # ... or the minimum of M N rho / trace^2 (generalised cross-validation): needs no noise level
+REG_PARAM_K = 0      # the weight that is searched: K ...
+REG_PARAM_GAMMA = 1  # ... or the CLS gamma
+REG_AT_LOW = 1       # RegChoice.flags: the search range's lower / upper end was taken
+REG_AT_HIGH = 2
 
 _f32p = ctypes.POINTER(ctypes.c_float)
 
@@ -79,6 +85,23 @@ class MotionEstimateC(ctypes.Structure):
     """fdr_motion_estimate of include/fdr.h"""
     _fields_ = [("length", ctypes.c_int), ("angle_deg", ctypes.c_double), ("score", ctypes.c_float), ("confidence", ctypes.c_float),
                 ("n_angles", ctypes.c_int), ("n_lengths", ctypes.c_int)]
+
+
+class RegParams(ctypes.Structure):
+    """fdr_reg_params of include/fdr.h"""
+    _fields_ = [("method", ctypes.c_int), ("param", ctypes.c_int), ("fixed", ctypes.c_float), ("sigma", ctypes.c_float),
+                ("tau", ctypes.c_float), ("lo", ctypes.c_double), ("hi", ctypes.c_double), ("n_grid", ctypes.c_int), ("refine", ctypes.c_int)]
+
+
+class RegChoiceC(ctypes.Structure):
+    """fdr_reg_choice of include/fdr.h"""
+    _fields_ = [("value", ctypes.c_double), ("sigma", ctypes.c_double), ("residual", ctypes.c_double), ("trace", ctypes.c_double),
+                ("gcv", ctypes.c_double), ("flags", ctypes.c_int), ("evaluations", ctypes.c_int)]
+
+
+# the result of Plan.choose_regularisation* / chooseRegularisation: the chosen weight (K or gamma, whichever was searched), the noise
+# level used, residual energy, trace and GCV score at the candidate nearest to it, REG_AT_* flags, candidates evaluated
+RegChoice = collections.namedtuple("RegChoice", "value sigma residual trace gcv flags evaluations")
 
 
 # the result of Plan.estimate_motion* / estimateMotionBlur: blur length (px) and angle (deg, motionBlurKernel convention), the
@@ -182,6 +205,12 @@ def _signatures():
         "fdr_cepstrum_f32_dev": (ci, [vp, vp, ci, ci, ci, vp, vp]),
         "fdr_estimate_motion_f32": (ci, [vp, vp, ci, ci, ci, ci, ci, cd, P(MotionEstimateC), vp]),
         "fdr_estimate_motion_f32_dev": (ci, [vp, vp, ci, ci, ci, ci, ci, cd, P(MotionEstimateC), vp, vp]),
+        "fdr_noise_sigma_f32": (ci, [ci, vp, ci, ci, ci, P(cd)]),
+        "fdr_noise_sigma_f32_dev": (ci, [ci, vp, ci, ci, ci, P(cd), vp]),
+        "fdr_reg_curve_f32": (ci, [vp, vp, ci, ci, ci, vp, vp, ci, vp, vp]),
+        "fdr_reg_curve_f32_dev": (ci, [vp, vp, ci, ci, ci, vp, vp, ci, vp, vp, vp]),
+        "fdr_choose_reg_f32": (ci, [vp, vp, ci, ci, ci, P(RegParams), P(RegChoiceC)]),
+        "fdr_choose_reg_f32_dev": (ci, [vp, vp, ci, ci, ci, P(RegParams), P(RegChoiceC), vp]),
         "fdr_plan_pass_times": (ci, [vp, P(ci), _f32p, P(ctypes.c_char_p), P(ci)]),
     }
 
@@ -541,6 +570,64 @@ class Plan:
                                                _stream(stream)))
         return MotionEstimate(est.length, est.angle_deg, est.score, est.confidence, est.n_angles, est.n_lengths)
 
+    # choosing the regularisation weight (include/fdr.h): noise estimate, residual / trace curve, discrepancy principle and GCV
+    def noise_sigma(self, img):
+        """Immerkaer's estimate of the noise standard deviation of img (host array, at least 3 x 3), on the plan's device"""
+        img = np.ascontiguousarray(img, dtype=np.float32)
+        sigma = ctypes.c_double()
+        _check(lib.fdr_noise_sigma_f32(self.device, _ptr(img), img.shape[0], img.shape[1], img.shape[1], ctypes.byref(sigma)))
+        return sigma.value
+
+    def noise_sigma_dev(self, d_img, rows, cols, stride, stream=None):
+        """the same on a device window.  Returns after the work on `stream`."""
+        sigma = ctypes.c_double()
+        _check(lib.fdr_noise_sigma_f32_dev(self.device, ctypes.c_void_p(int(d_img)), rows, cols, stride, ctypes.byref(sigma), _stream(stream)))
+        return sigma.value
+
+    def reg_curve(self, img, K, gamma):
+        """(residual, trace) as float64 arrays: rho and trace of the CLS filter with each pair (K[i], gamma[i]) on the window img
+        (host array), with the operator PSF of set_operator_psf*; K and gamma broadcast against each other"""
+        img = np.ascontiguousarray(img, dtype=np.float32)
+        K, gamma = np.broadcast_arrays(np.asarray(K, dtype=np.float64), np.asarray(gamma, dtype=np.float64))
+        shape = K.shape
+        K, gamma = np.ascontiguousarray(K).ravel(), np.ascontiguousarray(gamma).ravel()
+        rho, tr = np.empty(K.size, dtype=np.float64), np.empty(K.size, dtype=np.float64)
+        _check(lib.fdr_reg_curve_f32(self._h, _ptr(img), img.shape[0], img.shape[1], img.shape[1], _ptr(K), _ptr(gamma), K.size, _ptr(rho),
+                                     _ptr(tr)))
+        return rho.reshape(shape), tr.reshape(shape)
+
+    def reg_curve_dev(self, d_img, rows, cols, stride, K, gamma, stream=None):
+        """the same on a device window (K, gamma: equally long host sequences).  Returns after the work on `stream`."""
+        K, gamma = np.ascontiguousarray(K, dtype=np.float64).ravel(), np.ascontiguousarray(gamma, dtype=np.float64).ravel()
+        rho, tr = np.empty(K.size, dtype=np.float64), np.empty(K.size, dtype=np.float64)
+        _check(lib.fdr_reg_curve_f32_dev(self._h, ctypes.c_void_p(int(d_img)), rows, cols, stride, _ptr(K), _ptr(gamma), min(K.size, gamma.size),
+                                         _ptr(rho), _ptr(tr), _stream(stream)))
+        return rho, tr
+
+    @staticmethod
+    def _reg_params(method, param, fixed, sigma, tau, lo, hi, n_grid, refine):
+        return RegParams(int(method), int(param), float(fixed), float(sigma), float(tau), float(lo), float(hi), int(n_grid), int(refine))
+
+    def choose_regularisation(self, img, method=REG_GCV, param=REG_PARAM_GAMMA, fixed=0.0, sigma=0.0, tau=0.0, lo=0.0, hi=0.0, n_grid=0,
+                              refine=-1):
+        """K or gamma (param) of the CLS filter for the window img (host array), by the discrepancy principle or GCV (method), with
+        the other weight at `fixed`: a RegChoice.  0 selects an argument's default (sigma: estimated, tau 1, range 1e-8 .. 1e2, 32
+        candidates per round; refine -1: 2 rounds).  The value goes into set_psf(psf, K, gamma)."""
+        img = np.ascontiguousarray(img, dtype=np.float32)
+        prm = self._reg_params(method, param, fixed, sigma, tau, lo, hi, n_grid, refine)
+        c = RegChoiceC()
+        _check(lib.fdr_choose_reg_f32(self._h, _ptr(img), img.shape[0], img.shape[1], img.shape[1], ctypes.byref(prm), ctypes.byref(c)))
+        return RegChoice(c.value, c.sigma, c.residual, c.trace, c.gcv, c.flags, c.evaluations)
+
+    def choose_regularisation_dev(self, d_img, rows, cols, stride, method=REG_GCV, param=REG_PARAM_GAMMA, fixed=0.0, sigma=0.0, tau=0.0,
+                                  lo=0.0, hi=0.0, n_grid=0, refine=-1, stream=None):
+        """the same on a device window.  Returns after the work on `stream`."""
+        prm = self._reg_params(method, param, fixed, sigma, tau, lo, hi, n_grid, refine)
+        c = RegChoiceC()
+        _check(lib.fdr_choose_reg_f32_dev(self._h, ctypes.c_void_p(int(d_img)), rows, cols, stride, ctypes.byref(prm), ctypes.byref(c),
+                                          _stream(stream)))
+        return RegChoice(c.value, c.sigma, c.residual, c.trace, c.gcv, c.flags, c.evaluations)
+
     def set_concurrency(self, nstreams):
         """Batched mode: alternate images over `nstreams` private workspaces / internal streams."""
         _check(lib.fdr_plan_set_concurrency(self._h, int(nstreams)))
@@ -739,6 +826,21 @@ def estimateMotionBlur(img, device=0, min_length=0, max_length=0, angle_step=0.0
     M, N = _motion_plan_size(img.shape[0], img.shape[1])
     with Plan(M, N, MODE_FAST, device, flags=FLAG_MIXED_RADIX) as p:
         return p.estimate_motion(img, min_length, max_length, angle_step, scores)
+
+
+def chooseRegularisation(img, psf, method=REG_GCV, param=REG_PARAM_GAMMA, fixed=0.0, sigma=0.0, tau=0.0, lo=0.0, hi=0.0, n_grid=0, refine=-1,
+                         device=0):
+    """K or gamma of the Wiener / CLS filter for a blurred picture and its PSF, chosen on the device (fdr_choose_reg_f32).
+    img: one channel, or rows x cols x channels (their per-pixel mean is used).  The plan is that of richardsonLucy_myfft (each
+    dimension padded to the next power of two, at least 8 rows and 32 columns); psf lies top-left in it.  Returns a RegChoice;
+    arguments as Plan.choose_regularisation."""
+    img = np.asarray(img, dtype=np.float32)
+    if img.ndim == 3:
+        img = img.mean(axis=2, dtype=np.float32)
+    M, N = _rl_plan_size(img.shape[0], img.shape[1])
+    with Plan(M, N, MODE_FAST, device) as p:
+        p.set_operator_psf(psf)
+        return p.choose_regularisation(img, method, param, fixed, sigma, tau, lo, hi, n_grid, refine)
 
 
 def batch_run(devices, M, N, count, rows=None, cols=None, mode=MODE_FAST, flags=0, psf=None, psf_size=50, psf_angle=30.0, K=0.01,

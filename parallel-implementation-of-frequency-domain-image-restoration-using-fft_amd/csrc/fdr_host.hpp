@@ -147,6 +147,17 @@ struct fdr_plan {
     void* rf_block = nullptr;
     float *rf_u = nullptr, *rf_wgt = nullptr, *rf_dw = nullptr;
     double* rf_part = nullptr;
+    // choosing the regularisation weight (fdr_reg_curve_f32*, fdr_choose_reg_f32*): made by the first such call, kept until
+    // fdr_plan_destroy -- one allocation holding the power plane (ws_elems floats in the layout of `filt`, one float per bin, then the
+    // two extra floats of the packed column), the partials of the sweep and of the noise sum, and the candidate and result arrays
+    // (kRegMaxCurve pairs each); host copies of the last two are kept here too
+    void* rg_block = nullptr;
+    float* rg_power = nullptr;  // ws_elems + 2 floats
+    double* rg_part = nullptr;  // reg_curve_partials(M, npanels) * 2 kRegCandidates doubles
+    double* rg_noise = nullptr; // kRegMaxPartials + 1 doubles
+    double* rg_cand = nullptr;  // kRegMaxCurve (K, gamma) pairs
+    double* rg_res = nullptr;   // kRegMaxCurve (rho, trace) pairs
+    std::vector<double> rg_cand_host, rg_res_host;
     fdr::PassTimer timer;
     // the reference Profiler's buckets (fdr_plan_phase_times): resolved sums + event pairs not read back yet
     struct PhaseRec { hipEvent_t a, b; int phase; };
@@ -295,6 +306,9 @@ int blur_window_dev(fdr_plan* p, const float* d_img, int rows, int cols, int str
 // counting the zeros outside it too
 int normalize_window(fdr_plan* p, const char* fn, const char* name, const float* fin, int fs, int rows, int cols, int norm_area, float* d_out,
                      int out_stride, hipStream_t s);
+// pairs of one fdr_reg_curve_f32* call (fdr_api_reg.hip): what the candidate and result arrays of the plan hold
+constexpr int kRegMaxCurve = 4096;
+static_assert(kRegMaxCurve % kRegCandidates == 0, "the last sweep reads kRegCandidates pairs");
 // the entry points of fdr_api_tv.hip
 int tv_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, int cols, int stride, float* d_out, int out_stride,
                 const fdr_tv_params& prm, hipStream_t s);

@@ -197,6 +197,23 @@ hipError_t launch_motion_log(float2* plane, int M, int N, const double* sum, hip
 hipError_t launch_motion_score(const float2* plane, int M, int N, const double* trig, int n_angles, int min_length, int n_lengths, float* table,
                                hipStream_t s);
 
+// (fdr_reg.hip) choosing the regularisation weight.  noise: the Immerkaer sum S of |d * [[1,-2,1],[-2,4,-2],[1,-2,1]]| over the interior
+// of the rows x cols window (rows, cols >= 3) as reg_noise_partials(rows, cols) double partials, folded in a fixed order into
+// part[reg_noise_partials(rows, cols)] (part holds one more double; at most kRegMaxPartials + 1).  power: the forward column FFT of
+// a.data (the row spectra of pass A, a.nvalid rows, half spectrum, only read) and |G|^2 / (M N) as one float per bin into `power`
+// (row m of panel p at p * pstride + m * 4 floats); the packed column's slots hold |G0[k]|^2 for k <= M/2 and |GN[M - k]|^2 above,
+// extras[0 .. 1] = |GN[0]|^2, |GN[M/2]|^2 (all scaled).  curve: rho and trace of `ncand` <= kRegCandidates pairs (cand holds
+// kRegCandidates (K, gamma) pairs of doubles; the pairs past ncand are evaluated and dropped) into out[2 c], out[2 c + 1], through
+// reg_curve_partials(M, npanels) * 2 kRegCandidates double partials in `part`.
+constexpr int kRegCandidates = 16;    // candidate pairs per sweep of the spectrum
+constexpr int kRegMaxPartials = 1024;  // workgroups of the noise and curve kernels
+int reg_noise_partials(int rows, int cols);
+hipError_t launch_reg_noise(const float* d, int rows, int cols, int stride, double* part, hipStream_t s);
+hipError_t launch_cols_panel_power(int logm, const ColArgs& a, float* power, float* extras, const float2* tw_fwd, hipStream_t s);
+int reg_curve_partials(int M, int npanels);
+hipError_t launch_reg_curve(const float2* op_h, const float* power, const float* extras, const double* lap, const double* cand, int ncand, int M,
+                            int N, size_t pstride, int npanels, double* part, double* out, hipStream_t s);
+
 // the reference-shaped simple path and the free-standing transforms (fdr_simple.hip)
 hipError_t launch_pad_real_to_complex(const float* src, int rows, int cols, int stride, float2* dst, int M, int N,
                                       hipStream_t s);

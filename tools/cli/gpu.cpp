@@ -1,7 +1,11 @@
 // gpu.cpp -- ./gpu <img-path> <psf-length> <psf-angle> [--out file] [--mode fast|parity] [--norm padded|cropped] [--host-epilogue]
-//           [--cls gamma] [--pad zero|smooth] [--rl iterations [--free-boundary [--mask mask.png]]] [--tv mu [--tv-iters n] [--tv-rho r]]
+//           [--cls gamma|auto] [--k K|auto] [--reg gcv|discrepancy] [--sigma s] [--pad zero|smooth] [--rl iterations [--free-boundary [--mask mask.png]]] [--tv mu [--tv-iters n] [--tv-rho r]]
 // `auto auto` for length and angle: the blur is estimated first (fft_gpu::estimateMotionBlur on the per-pixel mean of B, G and R),
 // printed as `estimate: length L angle A confidence C`, and the run then goes on exactly as `./gpu <img-path> L A` would.
+// `--cls auto` (gamma, with K = 0) or `--k auto` (K, with gamma = 0): the weight is chosen first (fft_gpu::chooseRegularisation on the same
+// mean, with the PSF of the run; --reg names the method -- default gcv for gamma, discrepancy for K -- and --sigma the noise level of the
+// discrepancy principle, else estimated), printed as `regularisation: K k gamma g sigma s method m flags f`, and the run then goes on
+// exactly as `--k k --cls g` would (`--cls 0` is the Wiener filter).  It combines with `auto auto`.
 // Drop-in counterpart of the reference's gpu.cpp (argument meaning, printed lines and exit codes as at
 // gpu.cpp:57-138 of the reference): read image, /255, PSF, K = 0.01, split BGR, warm-up call, timed
 // wienerDeblur_RGB_optimized, timed wienerDeblur_RGB_naive, merge, Lab white balance, 8-bit result.
@@ -73,6 +77,9 @@ int main(int argc, char** argv) {
     int tv_iterations = 50;
     bool tv_opts = false;
     bool cls = false, parity = false, pad_smooth = false;
+    bool cls_auto = false, k_auto = false;  // --cls auto / --k auto: the weight is chosen from the picture
+    string reg_method;                      // --reg gcv|discrepancy
+    float reg_sigma = 0.f, K = 0.01f;       // --sigma s; --k K
     for (int i = 4; i < argc; ++i) {
         string a = argv[i];
         if (a == "--out" && i + 1 < argc) out_path = argv[++i];
@@ -86,7 +93,18 @@ int main(int argc, char** argv) {
         else if (a == "--norm" && i + 1 < argc) fft_gpu::set_norm_area(string(argv[++i]) == "cropped" ? FDR_NORM_CROPPED : FDR_NORM_PADDED);
         // constrained least-squares filter (fdr_set_psf_cls) in the fft_gpu:: entry points; the serial leg keeps the Wiener filter.
         // Fast mode only: with --mode parity the library refuses it and the first fft_gpu:: call exits with its message
-        else if (a == "--cls" && i + 1 < argc) { cls = true; fft_gpu::set_cls_gamma(strtof(argv[++i], nullptr)); }
+        else if (a == "--cls" && i + 1 < argc) {
+            cls = true;
+            if (string(argv[++i]) == "auto") cls_auto = true;
+            else fft_gpu::set_cls_gamma(strtof(argv[i], nullptr));
+        }
+        // the Wiener constant of every leg (default 0.01), or `auto`
+        else if (a == "--k" && i + 1 < argc) {
+            if (string(argv[++i]) == "auto") k_auto = true;
+            else K = strtof(argv[i], nullptr);
+        }
+        else if (a == "--reg" && i + 1 < argc) reg_method = argv[++i];
+        else if (a == "--sigma" && i + 1 < argc) reg_sigma = strtof(argv[++i], nullptr);
         // smooth padding (FDR_OPT_PAD_MODE) in the fft_gpu:: Wiener / CLS entry points; the serial leg keeps zero padding.  Fast mode only:
         // with --mode parity the library refuses it and the first fft_gpu:: call exits with its message
         else if (a == "--pad" && i + 1 < argc) {
@@ -104,6 +122,12 @@ int main(int argc, char** argv) {
         else if (a == "--tv-iters" && i + 1 < argc) { tv_opts = true; tv_iterations = atoi(argv[++i]); }
         else if (a == "--tv-rho" && i + 1 < argc) { tv_opts = true; tv_rho = strtof(argv[++i], nullptr); }
         else { cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle>\n"; return -1; }
+    }
+    // one weight is searched at a time; --reg and --sigma belong to a search
+    if ((cls_auto && k_auto) || (!(cls_auto || k_auto) && (!reg_method.empty() || reg_sigma != 0.f)) ||
+        (!reg_method.empty() && reg_method != "gcv" && reg_method != "discrepancy") || !(K >= 0.f) || !(reg_sigma >= 0.f)) {
+        cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle>\n";
+        return -1;
     }
     // the RL leg replaces the result the other options shape (CLS filter, parity check, parity-mode restoration)
     if (rl_iterations >= 0 && (cls || verify || parity || pad_smooth)) { cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle>\n"; return -1; }
@@ -126,13 +150,16 @@ int main(int argc, char** argv) {
     img.convertTo(img, CV_32F);
     img /= 255.0;
 
-    if (estimate) {  // the blur from the picture itself: the per-pixel mean of B, G and R
+    Mat gray;  // the per-pixel mean of B, G and R: what the blur and the regularisation weight are found on
+    if (estimate || cls_auto || k_auto) {
         vector<Mat> bgr;
         split(img, bgr);
-        Mat gray(img.rows, img.cols, CV_32F);
+        gray = Mat(img.rows, img.cols, CV_32F);
         for (int r = 0; r < img.rows; ++r)
             for (int c = 0; c < img.cols; ++c)
                 gray.ptr<float>(r)[c] = (bgr[0].ptr<float>(r)[c] + bgr[1].ptr<float>(r)[c] + bgr[2].ptr<float>(r)[c]) / 3.0f;
+    }
+    if (estimate) {  // the blur from the picture itself
         const fdr_motion_estimate est = fft_gpu::estimateMotionBlur(gray);
         if (est.length < 1) { cout << "Cannot estimate the blur of an all-zero picture\n"; return -1; }
         printf("estimate: length %d angle %.17g confidence %.3f\n", est.length, est.angle_deg, (double)est.confidence);
@@ -158,7 +185,18 @@ int main(int argc, char** argv) {
     }
 
     Mat psf = motionBlurKernel(psf_length, psf_angle);
-    float K = 0.01f;
+    if (cls_auto || k_auto) {  // the weight from the picture and the PSF: gamma with K = 0, or K with gamma = 0
+        const bool gcv = reg_method.empty() ? cls_auto : reg_method == "gcv";
+        const fdr_reg_choice c = fft_gpu::chooseRegularisation(gray, psf, gcv ? FDR_REG_GCV : FDR_REG_DISCREPANCY,
+                                                               cls_auto ? FDR_REG_PARAM_GAMMA : FDR_REG_PARAM_K, 0.f, reg_sigma);
+        K = cls_auto ? 0.f : (float)c.value;
+        const float gamma = cls_auto ? (float)c.value : 0.f;
+        printf("regularisation: K %.9g gamma %.9g sigma %.9g method %s flags %d\n", (double)K, (double)gamma, c.sigma, gcv ? "gcv" : "discrepancy",
+               c.flags);
+        fflush(stdout);
+        if (c.flags) cerr << "[Warning] the search ended at the " << (c.flags & FDR_REG_AT_LOW ? "lower" : "upper") << " end of its range\n";
+        fft_gpu::set_cls_gamma(gamma);
+    }
 
     vector<Mat> channels;
     split(img, channels);
