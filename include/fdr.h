@@ -299,6 +299,42 @@ int fdr_richardson_lucy_free_f32(fdr_plan* plan, const float* img_host, int rows
 int fdr_richardson_lucy_free_f32_dev(fdr_plan* plan, const float* d_img, int rows, int cols, int stride, const float* d_weights,
                                      int wstride, float* d_out, int out_stride, const fdr_rlfree_params* params, void* stream);
 
+/* -- accelerated Richardson-Lucy: Biggs & Andrews' vector extrapolation ("Acceleration of iterative image restoration algorithms",
+ *    Applied Optics 36, 1997; the default of MATLAB's deconvlucy) around the unchanged iteration of either form above.  With
+ *    step(y) one iteration applied to y (plain form: c = blur(y), r = c > FDR_RL_TAU ? d+ / c : 0, step(y) = max(y . blur^T(r), 0) on
+ *    the window; free-boundary form: c = window(fullblur(y)), r likewise from dw, step(y) = max(y . wgt . fullblur^T(pad(r)), 0) on the
+ *    whole plan, with setup, coverage, wgt and the start exactly as above) and u_0 the start of the plain call:
+ *        k = 0, 1 :  alpha_k = 0;  y_k = u_k
+ *        k >= 2   :  alpha_k = clamp( sum(g_(k-1) . g_(k-2)) / sum(g_(k-2) . g_(k-2)), 0, FDR_RL_ACCEL_MAX )
+ *                    (0 when the denominator is 0 or the quotient is not finite)
+ *                    y_k = max(u_k + alpha_k (u_k - u_(k-1)), 0)
+ *        every k  :  u_(k+1) = step(y_k);   g_k = u_(k+1) - y_k
+ *    The output is u_n, normalised or cropped exactly as the plain calls do it.  The sums run over the window (plain form) or the
+ *    whole M x N plan (free-boundary form), in double and in a fixed order (per-workgroup partials, then one workgroup; no float
+ *    atomics), so results are bit-identical from call to call; alpha is rounded to float once and stays on the device: the _dev
+ *    forms make no host read-back and stay asynchronous on `stream`.  alpha_0 = alpha_1 = 0, so n <= 2 gives the bits of the plain
+ *    calls (and launches nothing else).  Every u_k is the output of a step, so the flux identities of the plain calls hold.  Per
+ *    iteration the extrapolation adds one inner-product pass and one pointwise pass, about 28 bytes per pixel of the estimate, and
+ *    no transform; it typically reaches in 10 iterations what the plain calls need 20 to 30 for, and fits noise sooner as well
+ *    (DESIGN.md section 21).
+ *    alphas may be NULL; otherwise it receives `iterations` floats, alpha_0 .. alpha_(n-1).  Plans, refusals, overlap rules, phases
+ *    and norm_area as the plain counterparts; the _dev forms also return FDR_ERR_ARG for a d_alphas range that overlaps the output,
+ *    the input or the weights.  The first accelerated call on a plan (either form) allocates the workspace both forms share, kept
+ *    until fdr_plan_destroy: three M x N float planes (y, the second plane of the estimate, g), the double partials and alpha,
+ *    12 M N + 16 ceil(M / 8) ceil(N / 1024) + 8 bytes; FDR_ERR_ALLOC, plan intact, if it cannot be had.  After it the _dev forms
+ *    allocate nothing (the free-boundary form needs its own workspace as before).  The plain form's estimate alternates between
+ *    d_out and the workspace; the input is still read on every iteration.                                                       */
+#define FDR_RL_ACCEL_MAX 0.9990234375f /* 1 - 2^-10: the upper bound of the extrapolation factor */
+int fdr_richardson_lucy_accel_f32(fdr_plan* plan, const float* img_host, int rows, int cols, int stride, float* out_host, int out_stride,
+                                  int iterations, int norm_area, float* alphas_host);
+int fdr_richardson_lucy_accel_f32_dev(fdr_plan* plan, const float* d_img, int rows, int cols, int stride, float* d_out, int out_stride,
+                                      int iterations, int norm_area, float* d_alphas, void* stream);
+int fdr_richardson_lucy_free_accel_f32(fdr_plan* plan, const float* img_host, int rows, int cols, int stride, const float* weights_host,
+                                       int wstride, float* out_host, int out_stride, const fdr_rlfree_params* params, float* alphas_host);
+int fdr_richardson_lucy_free_accel_f32_dev(fdr_plan* plan, const float* d_img, int rows, int cols, int stride, const float* d_weights,
+                                           int wstride, float* d_out, int out_stride, const fdr_rlfree_params* params, float* d_alphas,
+                                           void* stream);
+
 /* -- total-variation (TV) regularised deconvolution by ADMM / split Bregman (Rudin-Osher-Fatemi 1992; Wang-Yang-Yin-Zhang 2008
  *    "FTVd"; Goldstein-Osher 2009): the edge-preserving restoration beside the linear filters and RL.  It uses the operator PSF of
  *    fdr_set_operator_psf* (H = DFT2 of the PSF top-left in the plan, blur / blur^T as above) and lives on the whole periodic

@@ -212,8 +212,9 @@ inline void wienerDeblur_RGB_naive(std::vector<Mat>& channels, const Mat& psf, f
 
 // Richardson-Lucy deconvolution (fdr_richardson_lucy_f32, include/fdr.h) of every channel, `iterations` steps each, in place: one
 // cached FDR_MODE_FAST plan (each dimension padded to the next power of two, at least 8 rows and 32 columns; the padding stays
-// zero), the operator PSF set once, each channel normalised by o.norm_area.  o.mode and o.cls_gamma do not apply.
-inline void richardsonLucy_RGB(std::vector<Mat>& channels, const Mat& psf, int iterations, const Options& o) {
+// zero), the operator PSF set once, each channel normalised by o.norm_area.  o.mode and o.cls_gamma do not apply.  accelerate: the
+// iteration with Biggs & Andrews' vector extrapolation (fdr_richardson_lucy_accel_f32).
+inline void richardsonLucy_RGB(std::vector<Mat>& channels, const Mat& psf, int iterations, const Options& o, bool accelerate = false) {
     if (channels.empty()) return;
     const int rows = channels[0].rows, cols = channels[0].cols;
     bool created = false;
@@ -224,19 +225,24 @@ inline void richardsonLucy_RGB(std::vector<Mat>& channels, const Mat& psf, int i
     for (Mat& c : channels) {
         Mat src = c.isContinuous() ? c : c.clone();
         Mat out(c.rows, c.cols, CV_32F);
-        FDR_CHECK(fdr_richardson_lucy_f32(plan, src.ptr<float>(0), c.rows, c.cols, c.cols, out.ptr<float>(0), c.cols, iterations, o.norm_area));
+        if (accelerate)
+            FDR_CHECK(fdr_richardson_lucy_accel_f32(plan, src.ptr<float>(0), c.rows, c.cols, c.cols, out.ptr<float>(0), c.cols, iterations,
+                                                    o.norm_area, nullptr));
+        else
+            FDR_CHECK(fdr_richardson_lucy_f32(plan, src.ptr<float>(0), c.rows, c.cols, c.cols, out.ptr<float>(0), c.cols, iterations, o.norm_area));
         c = out;
     }
 }
-inline void richardsonLucy_RGB(std::vector<Mat>& channels, const Mat& psf, int iterations) {
-    richardsonLucy_RGB(channels, psf, iterations, defaults());
+inline void richardsonLucy_RGB(std::vector<Mat>& channels, const Mat& psf, int iterations, bool accelerate = false) {
+    richardsonLucy_RGB(channels, psf, iterations, defaults(), accelerate);
 }
 // Free-boundary, weighted Richardson-Lucy (fdr_richardson_lucy_free_f32, include/fdr.h) of every channel, in place, for a picture
 // that is a crop of a larger scene: one cached FDR_MODE_FAST plan with room for the PSF's reach beyond the picture (the next powers
 // of two of rows + psf.rows - 1 and cols + psf.cols - 1, at least 8 x 32), the operator PSF set once, `weights` (CV_32F, the
 // picture's size, in [0, 1]; empty = all ones; 0 = ignore the pixel) shared by the channels, each channel normalised by o.norm_area.
+// accelerate as richardsonLucy_RGB (fdr_richardson_lucy_free_accel_f32).
 inline void richardsonLucyFree_RGB(std::vector<Mat>& channels, const Mat& psf, int iterations, const Mat& weights, const Options& o,
-                                   float sigma = FDR_RL_SIGMA) {
+                                   float sigma = FDR_RL_SIGMA, bool accelerate = false) {
     if (channels.empty()) return;
     const int rows = channels[0].rows, cols = channels[0].cols;
     if (!weights.empty() && (weights.rows != rows || weights.cols != cols || weights.type() != CV_32F)) {
@@ -254,13 +260,18 @@ inline void richardsonLucyFree_RGB(std::vector<Mat>& channels, const Mat& psf, i
         Mat src = c.isContinuous() ? c : c.clone();
         Mat out(c.rows, c.cols, CV_32F);
         const fdr_rlfree_params prm = {iterations, sigma, o.norm_area, c.rows, c.cols};
-        FDR_CHECK(fdr_richardson_lucy_free_f32(plan, src.ptr<float>(0), c.rows, c.cols, c.cols, w.empty() ? nullptr : w.ptr<float>(0), cols,
-                                               out.ptr<float>(0), c.cols, &prm));
+        if (accelerate)
+            FDR_CHECK(fdr_richardson_lucy_free_accel_f32(plan, src.ptr<float>(0), c.rows, c.cols, c.cols, w.empty() ? nullptr : w.ptr<float>(0),
+                                                         cols, out.ptr<float>(0), c.cols, &prm, nullptr));
+        else
+            FDR_CHECK(fdr_richardson_lucy_free_f32(plan, src.ptr<float>(0), c.rows, c.cols, c.cols, w.empty() ? nullptr : w.ptr<float>(0), cols,
+                                                   out.ptr<float>(0), c.cols, &prm));
         c = out;
     }
 }
-inline void richardsonLucyFree_RGB(std::vector<Mat>& channels, const Mat& psf, int iterations, const Mat& weights = Mat()) {
-    richardsonLucyFree_RGB(channels, psf, iterations, weights, defaults());
+inline void richardsonLucyFree_RGB(std::vector<Mat>& channels, const Mat& psf, int iterations, const Mat& weights = Mat(),
+                                   bool accelerate = false) {
+    richardsonLucyFree_RGB(channels, psf, iterations, weights, defaults(), FDR_RL_SIGMA, accelerate);
 }
 // Total-variation deconvolution (fdr_tv_deconv_f32, include/fdr.h) of every channel, in place: the plan and operator PSF of
 // richardsonLucy_RGB, `iterations` ADMM steps of mu / 2 ||blur(x) - d||^2 + TV(x) (isotropic) with penalty rho, the output clamped

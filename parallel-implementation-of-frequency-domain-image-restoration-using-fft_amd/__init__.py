@@ -31,6 +31,7 @@ NORM_PADDED = 1
 NORM_CROPPED = 0
 NORM_NONE = 2  # Richardson-Lucy only: the raw estimate
 RL_SIGMA = 1e-2  # FDR_RL_SIGMA: the usual coverage threshold of free-boundary Richardson-Lucy
+RL_ACCEL_MAX = 0.9990234375  # FDR_RL_ACCEL_MAX = 1 - 2^-10: the upper bound of accelerated Richardson-Lucy's extrapolation factor
 MAX_PASSES = 16
 OPT_TWO_SWEEP_NORM = 2
 OPT_BATCH_GRAPH = 3
@@ -199,6 +200,10 @@ def _signatures():
         "fdr_richardson_lucy_f32_dev": (ci, [vp, vp, ci, ci, ci, vp, ci, ci, ci, vp]),
         "fdr_richardson_lucy_free_f32": (ci, [vp, vp, ci, ci, ci, vp, ci, vp, ci, P(RlFreeParams)]),
         "fdr_richardson_lucy_free_f32_dev": (ci, [vp, vp, ci, ci, ci, vp, ci, vp, ci, P(RlFreeParams), vp]),
+        "fdr_richardson_lucy_accel_f32": (ci, [vp, vp, ci, ci, ci, vp, ci, ci, ci, vp]),
+        "fdr_richardson_lucy_accel_f32_dev": (ci, [vp, vp, ci, ci, ci, vp, ci, ci, ci, vp, vp]),
+        "fdr_richardson_lucy_free_accel_f32": (ci, [vp, vp, ci, ci, ci, vp, ci, vp, ci, P(RlFreeParams), vp]),
+        "fdr_richardson_lucy_free_accel_f32_dev": (ci, [vp, vp, ci, ci, ci, vp, ci, vp, ci, P(RlFreeParams), vp, vp]),
         "fdr_tv_deconv_f32": (ci, [vp, vp, ci, ci, ci, vp, ci, P(TvParams)]),
         "fdr_tv_deconv_f32_dev": (ci, [vp, vp, ci, ci, ci, vp, ci, P(TvParams), vp]),
         "fdr_cepstrum_f32": (ci, [vp, vp, ci, ci, ci, vp]),
@@ -243,6 +248,15 @@ def _load():
 
 
 lib = _load()
+
+
+def _alphas_array(iterations, accelerate, return_alphas):
+    """room for the extrapolation factors of an accelerated Richardson-Lucy call (None when they are not asked for)"""
+    if not return_alphas:
+        return None
+    if not accelerate:
+        raise ValueError("return_alphas needs accelerate=True")
+    return np.zeros(max(int(iterations), 0), dtype=np.float32)
 
 
 def _check(rc):
@@ -480,23 +494,41 @@ class Plan:
         _check(lib.fdr_blur_f32_dev(self._h, ctypes.c_void_p(int(d_img)), rows, cols, stride, ctypes.c_void_p(int(d_out)), out_stride,
                                     int(bool(adjoint)), _stream(stream)))
 
-    def richardson_lucy(self, img, iterations, norm_area=NORM_NONE):
-        """`iterations` Richardson-Lucy steps on the window img (host arrays), normalised by norm_area."""
+    def richardson_lucy(self, img, iterations, norm_area=NORM_NONE, accelerate=False, return_alphas=False):
+        """`iterations` Richardson-Lucy steps on the window img (host arrays), normalised by norm_area.  accelerate: with Biggs &
+        Andrews' vector extrapolation (fdr_richardson_lucy_accel_f32); return_alphas (accelerated only): (result, the
+        `iterations` extrapolation factors)."""
         img = np.ascontiguousarray(img, dtype=np.float32)
         out = np.empty_like(img)
-        _check(lib.fdr_richardson_lucy_f32(self._h, _ptr(img), img.shape[0], img.shape[1], img.shape[1], _ptr(out), img.shape[1],
-                                           int(iterations), int(norm_area)))
-        return out
+        alphas = _alphas_array(iterations, accelerate, return_alphas)
+        if accelerate:
+            _check(lib.fdr_richardson_lucy_accel_f32(self._h, _ptr(img), img.shape[0], img.shape[1], img.shape[1], _ptr(out), img.shape[1],
+                                                     int(iterations), int(norm_area), _ptr(alphas) if return_alphas else None))
+        else:
+            _check(lib.fdr_richardson_lucy_f32(self._h, _ptr(img), img.shape[0], img.shape[1], img.shape[1], _ptr(out), img.shape[1],
+                                               int(iterations), int(norm_area)))
+        return (out, alphas) if return_alphas else out
 
-    def richardson_lucy_dev(self, d_img, rows, cols, stride, d_out, out_stride, iterations, norm_area=NORM_NONE, stream=None):
+    def richardson_lucy_dev(self, d_img, rows, cols, stride, d_out, out_stride, iterations, norm_area=NORM_NONE, stream=None,
+                            accelerate=False, d_alphas=None):
+        """the same on device pointers, asynchronous; d_alphas (accelerated only): device room for `iterations` floats"""
+        if accelerate:
+            _check(lib.fdr_richardson_lucy_accel_f32_dev(self._h, ctypes.c_void_p(int(d_img)), rows, cols, stride,
+                                                         ctypes.c_void_p(int(d_out)), out_stride, int(iterations), int(norm_area),
+                                                         ctypes.c_void_p(int(d_alphas)) if d_alphas else None, _stream(stream)))
+            return
+        if d_alphas:
+            raise ValueError("d_alphas needs accelerate=True")
         _check(lib.fdr_richardson_lucy_f32_dev(self._h, ctypes.c_void_p(int(d_img)), rows, cols, stride, ctypes.c_void_p(int(d_out)),
                                                out_stride, int(iterations), int(norm_area), _stream(stream)))
 
     # free-boundary, weighted Richardson-Lucy (include/fdr.h); uses the operator PSF
-    def richardson_lucy_free(self, img, iterations, weights=None, sigma=RL_SIGMA, norm_area=NORM_NONE, full_plane=False):
+    def richardson_lucy_free(self, img, iterations, weights=None, sigma=RL_SIGMA, norm_area=NORM_NONE, full_plane=False, accelerate=False,
+                             return_alphas=False):
         """`iterations` free-boundary Richardson-Lucy steps on the window img (host arrays): the estimate lives on the whole plan,
         the data constrain it inside the window only.  weights (img.shape, in [0, 1]; None = all ones) say how much each pixel
-        counts: 0 excludes it.  Returns the window, or with full_plane the whole M x N estimate; normalised over what is returned."""
+        counts: 0 excludes it.  Returns the window, or with full_plane the whole M x N estimate; normalised over what is returned.
+        accelerate and return_alphas as Plan.richardson_lucy (fdr_richardson_lucy_free_accel_f32)."""
         img = np.ascontiguousarray(img, dtype=np.float32)
         rows, cols = img.shape
         w = None
@@ -507,15 +539,29 @@ class Plan:
         orows, ocols = (self.M, self.N) if full_plane else (rows, cols)
         out = np.empty((orows, ocols), dtype=np.float32)
         prm = RlFreeParams(int(iterations), float(sigma), int(norm_area), orows, ocols)
-        _check(lib.fdr_richardson_lucy_free_f32(self._h, _ptr(img), rows, cols, cols, _ptr(w) if w is not None else None, cols, _ptr(out),
-                                                ocols, ctypes.byref(prm)))
-        return out
+        alphas = _alphas_array(iterations, accelerate, return_alphas)
+        if accelerate:
+            _check(lib.fdr_richardson_lucy_free_accel_f32(self._h, _ptr(img), rows, cols, cols, _ptr(w) if w is not None else None, cols,
+                                                          _ptr(out), ocols, ctypes.byref(prm), _ptr(alphas) if return_alphas else None))
+        else:
+            _check(lib.fdr_richardson_lucy_free_f32(self._h, _ptr(img), rows, cols, cols, _ptr(w) if w is not None else None, cols, _ptr(out),
+                                                    ocols, ctypes.byref(prm)))
+        return (out, alphas) if return_alphas else out
 
     def richardson_lucy_free_dev(self, d_img, rows, cols, stride, d_out, out_stride, iterations, d_weights=None, wstride=0, sigma=RL_SIGMA,
-                                 norm_area=NORM_NONE, out_rows=None, out_cols=None, stream=None):
-        """the same on device pointers; out_rows x out_cols (default rows x cols, up to M x N) is the output window.  Asynchronous."""
+                                 norm_area=NORM_NONE, out_rows=None, out_cols=None, stream=None, accelerate=False, d_alphas=None):
+        """the same on device pointers; out_rows x out_cols (default rows x cols, up to M x N) is the output window.  Asynchronous.
+        d_alphas (accelerated only): device room for `iterations` floats."""
         prm = RlFreeParams(int(iterations), float(sigma), int(norm_area), int(rows if out_rows is None else out_rows),
                            int(cols if out_cols is None else out_cols))
+        if accelerate:
+            _check(lib.fdr_richardson_lucy_free_accel_f32_dev(self._h, ctypes.c_void_p(int(d_img)), rows, cols, stride,
+                                                              ctypes.c_void_p(int(d_weights)) if d_weights else None, int(wstride),
+                                                              ctypes.c_void_p(int(d_out)), out_stride, ctypes.byref(prm),
+                                                              ctypes.c_void_p(int(d_alphas)) if d_alphas else None, _stream(stream)))
+            return
+        if d_alphas:
+            raise ValueError("d_alphas needs accelerate=True")
         _check(lib.fdr_richardson_lucy_free_f32_dev(self._h, ctypes.c_void_p(int(d_img)), rows, cols, stride,
                                                     ctypes.c_void_p(int(d_weights)) if d_weights else None, int(wstride),
                                                     ctypes.c_void_p(int(d_out)), out_stride, ctypes.byref(prm), _stream(stream)))
@@ -771,15 +817,15 @@ def _rl_plan_size(rows, cols):
     return max(8, nextPowerOfTwo(rows)), max(32, nextPowerOfTwo(cols))
 
 
-def richardsonLucy_myfft(img, psf, iterations, device=0, norm_area=NORM_NONE):
+def richardsonLucy_myfft(img, psf, iterations, device=0, norm_area=NORM_NONE, accelerate=False):
     """Richardson-Lucy deconvolution of one channel: pad each dimension to the next power of two (at least 8 rows and 32
     columns; the padding is zero and stays zero), `iterations` steps on the device, crop.  psf lies top-left in the plan, as
-    for the Wiener calls."""
+    for the Wiener calls.  accelerate: the accelerated iteration of Plan.richardson_lucy."""
     img = np.asarray(img, dtype=np.float32)
     M, N = _rl_plan_size(img.shape[0], img.shape[1])
     with Plan(M, N, MODE_FAST, device) as p:
         p.set_operator_psf(psf)
-        return p.richardson_lucy(img, iterations, norm_area)
+        return p.richardson_lucy(img, iterations, norm_area, accelerate=accelerate)
 
 
 def _rlfree_plan_size(rows, cols, prows, pcols):
@@ -788,16 +834,17 @@ def _rlfree_plan_size(rows, cols, prows, pcols):
     return max(8, nextPowerOfTwo(rows + prows - 1)), max(32, nextPowerOfTwo(cols + pcols - 1))
 
 
-def richardsonLucyFree_myfft(img, psf, iterations, weights=None, sigma=RL_SIGMA, device=0, norm_area=NORM_NONE, full_plane=False):
+def richardsonLucyFree_myfft(img, psf, iterations, weights=None, sigma=RL_SIGMA, device=0, norm_area=NORM_NONE, full_plane=False,
+                             accelerate=False):
     """Free-boundary, weighted Richardson-Lucy of one channel that is a crop of a larger scene: a plan with room for the PSF's
     reach beyond the window, `iterations` steps on the device, the window (or with full_plane the whole plan) back.  psf lies
-    top-left in the plan, as for the Wiener calls; weights as Plan.richardson_lucy_free."""
+    top-left in the plan, as for the Wiener calls; weights and accelerate as Plan.richardson_lucy_free."""
     img = np.asarray(img, dtype=np.float32)
     psf = np.asarray(psf, dtype=np.float32)
     M, N = _rlfree_plan_size(img.shape[0], img.shape[1], psf.shape[0], psf.shape[1])
     with Plan(M, N, MODE_FAST, device) as p:
         p.set_operator_psf(psf)
-        return p.richardson_lucy_free(img, iterations, weights, sigma, norm_area, full_plane)
+        return p.richardson_lucy_free(img, iterations, weights, sigma, norm_area, full_plane, accelerate=accelerate)
 
 
 def tvDeblur_myfft(img, psf, mu, rho=2.0, iterations=50, anisotropic=False, nonneg=False, device=0, norm_area=NORM_NONE):

@@ -1,5 +1,6 @@
-// fdr_api_operator.hip -- the blur operator and Richardson-Lucy (fdr_rl.hip): passes A, B' and C of the fast half-spectrum path
-// with the operator tables in place of W and the operator kinds of the inverse row pass; their PSF setters and entry points.
+// fdr_api_operator.hip -- the blur operator and Richardson-Lucy, plain and accelerated (fdr_rl.hip, fdr_rlaccel.hip): passes A, B'
+// and C of the fast half-spectrum path with the operator tables in place of W and the operator kinds of the inverse row pass;
+// their PSF setters and entry points.
 #include "fdr_host.hpp"
 
 #include <cstdint>
@@ -142,34 +143,81 @@ int rl_check(const fdr_plan* p, const char* fn, const float* img, int rows, int 
     return FDR_OK;
 }
 
-// u (the estimate) lives in d_out; r in the window of the raw plane (row stride cols), the spectrum in slot 0's work.  With a
-// normalisation the last update (or, for no iterations, the initial estimate) goes to the raw plane instead, and the normalise
-// pass writes d_out from there.
-int rl_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, int cols, int stride, float* d_out, int out_stride, int iterations,
-                int norm_area, hipStream_t s) {
-    int rc = FDR_OK;
-    const bool norm = norm_area != FDR_NORM_NONE;
+// one iteration: c = blur(y), r = d+ / c into the window of the raw plane (row stride cols), out = max(y . blur^T(r), 0); `out` may
+// be y itself
+int rl_step(fdr_plan* p, const float* d_img, int stride, const float* y, int ys, float* out, int os, int rows, int cols, hipStream_t s) {
     float* r = p->slots[0].raw;
     const int rs = cols;
-    float* fin = norm ? r : d_out;  // where the final estimate is written
-    const int fs = norm ? rs : out_stride;
+    int rc = op_rows_fwd(p, y, rows, cols, ys, s);                                                    // c = blur(y) ...
+    if (rc == FDR_OK) rc = op_cols(p, false, s);
+    if (rc == FDR_OK) rc = op_rows_inv(p, ROW_OUT_RL_RATIO, kPassRlRatio, d_img, stride, r, rs, rows, cols, s);  // ... r = d+ / c
+    if (rc == FDR_OK) rc = op_rows_fwd(p, r, rows, cols, rs, s);                                      // g = blur^T(r) ...
+    if (rc == FDR_OK) rc = op_cols(p, true, s);
+    if (rc == FDR_OK) rc = op_rows_inv(p, ROW_OUT_RL_UPDATE, kPassRlUpdate, y, ys, out, os, rows, cols, s);  // ... out = max(y g, 0)
+    return rc;
+}
+
+// u (the estimate) lives in d_out; r in the window of the raw plane (row stride cols), the spectrum in slot 0's work.  With a
+// normalisation the last update (or, for no iterations, the initial estimate) goes to the raw plane instead, and the normalise
+// pass writes d_out from there.  Accelerated (rl_accel_loop), the estimate alternates between d_out and a plane of the acceleration
+// workspace, starting where u_n comes to lie in d_out.
+int rl_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, int cols, int stride, float* d_out, int out_stride, int iterations,
+                int norm_area, bool accel, float* d_alphas, hipStream_t s) {
+    int rc = FDR_OK;
+    const bool norm = norm_area != FDR_NORM_NONE;
+    float* fin = norm ? p->slots[0].raw : d_out;  // where the final estimate is written
+    const int fs = norm ? cols : out_stride;
+    float* const U[2] = {d_out, accel ? p->ra_u : d_out};
+    const int us[2] = {out_stride, accel ? cols : out_stride};
+    const int first = accel ? iterations & 1 : 0;
     {
         ScopedPass t(p, s, kPassRlInit);
-        FDR_HIP(launch_rl_init(d_img, rows, cols, stride, iterations == 0 ? fin : d_out, iterations == 0 ? fs : out_stride, s));
+        FDR_HIP(launch_rl_init(d_img, rows, cols, stride, iterations == 0 ? fin : U[first], iterations == 0 ? fs : us[first], s));
     }
-    for (int it = 0; it < iterations && rc == FDR_OK; ++it) {
-        const bool last = it == iterations - 1;
-        rc = op_rows_fwd(p, d_out, rows, cols, out_stride, s);                                            // c = blur(u) ...
-        if (rc == FDR_OK) rc = op_cols(p, false, s);
-        if (rc == FDR_OK) rc = op_rows_inv(p, ROW_OUT_RL_RATIO, kPassRlRatio, d_img, stride, r, rs, rows, cols, s);  // ... r = d+ / c
-        if (rc == FDR_OK) rc = op_rows_fwd(p, r, rows, cols, rs, s);                                      // g = blur^T(r) ...
-        if (rc == FDR_OK) rc = op_cols(p, true, s);
-        if (rc == FDR_OK)
-            rc = op_rows_inv(p, ROW_OUT_RL_UPDATE, kPassRlUpdate, d_out, out_stride, last ? fin : d_out, last ? fs : out_stride, rows,
-                             cols, s);                                                                    // ... u = max(u g, 0)
+    if (accel) {
+        rc = rl_accel_loop(p, iterations, rows, cols, U, us, first, fin, fs, d_alphas, s,
+                           [&](const float* y, int ys, float* out, int os) { return rl_step(p, d_img, stride, y, ys, out, os, rows, cols, s); },
+                           nullptr);
+    } else {
+        for (int it = 0; it < iterations && rc == FDR_OK; ++it) {
+            const bool last = it == iterations - 1;
+            rc = rl_step(p, d_img, stride, d_out, out_stride, last ? fin : d_out, last ? fs : out_stride, rows, cols, s);
+        }
     }
     if (rc != FDR_OK || !norm) return rc;
     return normalize_window(p, fn, kPassRlNorm, fin, fs, rows, cols, norm_area, d_out, out_stride, s);
+}
+
+// the checks, the device and the driver of the four entry points; the accelerated ones also refuse alphas that overlap a window and
+// make sure of their workspace
+int rl_dev_entry(fdr_plan* p, const char* fn, const float* d_img, int rows, int cols, int stride, float* d_out, int out_stride, int iterations,
+                 int norm_area, bool accel, float* d_alphas, hipStream_t s) {
+    if (!p || !d_img || !d_out) return null_arg(fn);
+    int rc = rl_check(p, fn, d_img, rows, cols, stride, d_out, out_stride, iterations, norm_area);
+    if (rc == FDR_OK && accel) rc = check_alphas(fn, d_alphas, iterations, d_out, out_stride, rows, cols, "output");
+    if (rc == FDR_OK && accel) rc = check_alphas(fn, d_alphas, iterations, d_img, stride, rows, cols, "input");
+    if (rc != FDR_OK) return rc;
+    FDR_HIP(hipSetDevice(p->device));
+    if (accel) rc = ensure_rlaccel_workspace(p, fn);
+    if (rc != FDR_OK) return rc;
+    return rl_dev_impl(p, fn, d_img, rows, cols, stride, d_out, out_stride, iterations, norm_area, accel, d_alphas, s);
+}
+
+int rl_host_entry(fdr_plan* p, const char* fn, const float* img_host, int rows, int cols, int stride, float* out_host, int out_stride,
+                  int iterations, int norm_area, bool accel, float* alphas_host) {
+    if (!p || !img_host || !out_host) return null_arg(fn);
+    int rc = rl_check(p, fn, img_host, rows, cols, stride, out_host, out_stride, iterations, norm_area);
+    if (rc != FDR_OK) return rc;
+    FDR_HIP(hipSetDevice(p->device));
+    if (accel) rc = ensure_rlaccel_workspace(p, fn);
+    if (rc != FDR_OK) return rc;
+    DeviceBuffer d_alphas;
+    if (accel && alphas_host && iterations > 0) FDR_ALLOC(d_alphas, (size_t)iterations * sizeof(float), fn);
+    rc = host_image_call(p, fn, img_host, rows, cols, stride, out_host, rows, cols, out_stride, [&](const float* d_in, float* d_out) {
+        return rl_dev_impl(p, fn, d_in, rows, cols, cols, d_out, cols, iterations, norm_area, accel, d_alphas.as<float>(), nullptr);
+    });
+    if (rc == FDR_OK && d_alphas.ptr) FDR_HIP(hipMemcpy(alphas_host, d_alphas.ptr, (size_t)iterations * sizeof(float), hipMemcpyDeviceToHost));
+    return rc;
 }
 
 }  // namespace
@@ -210,24 +258,26 @@ int fdr_blur_f32(fdr_plan* p, const float* img_host, int rows, int cols, int str
 
 int fdr_richardson_lucy_f32_dev(fdr_plan* p, const float* d_img, int rows, int cols, int stride, float* d_out, int out_stride, int iterations,
                                 int norm_area, void* stream) {
-    const char* fn = "fdr_richardson_lucy_f32_dev";
-    if (!p || !d_img || !d_out) return null_arg(fn);
-    const int rc = rl_check(p, fn, d_img, rows, cols, stride, d_out, out_stride, iterations, norm_area);
-    if (rc != FDR_OK) return rc;
-    FDR_HIP(hipSetDevice(p->device));
-    return rl_dev_impl(p, fn, d_img, rows, cols, stride, d_out, out_stride, iterations, norm_area, (hipStream_t)stream);
+    return rl_dev_entry(p, "fdr_richardson_lucy_f32_dev", d_img, rows, cols, stride, d_out, out_stride, iterations, norm_area, false, nullptr,
+                        (hipStream_t)stream);
 }
 
 int fdr_richardson_lucy_f32(fdr_plan* p, const float* img_host, int rows, int cols, int stride, float* out_host, int out_stride,
                             int iterations, int norm_area) {
-    const char* fn = "fdr_richardson_lucy_f32";
-    if (!p || !img_host || !out_host) return null_arg(fn);
-    const int rc = rl_check(p, fn, img_host, rows, cols, stride, out_host, out_stride, iterations, norm_area);
-    if (rc != FDR_OK) return rc;
-    FDR_HIP(hipSetDevice(p->device));
-    return host_image_call(p, fn, img_host, rows, cols, stride, out_host, rows, cols, out_stride, [&](const float* d_in, float* d_out) {
-        return rl_dev_impl(p, fn, d_in, rows, cols, cols, d_out, cols, iterations, norm_area, nullptr);
-    });
+    return rl_host_entry(p, "fdr_richardson_lucy_f32", img_host, rows, cols, stride, out_host, out_stride, iterations, norm_area, false,
+                         nullptr);
+}
+
+int fdr_richardson_lucy_accel_f32_dev(fdr_plan* p, const float* d_img, int rows, int cols, int stride, float* d_out, int out_stride,
+                                      int iterations, int norm_area, float* d_alphas, void* stream) {
+    return rl_dev_entry(p, "fdr_richardson_lucy_accel_f32_dev", d_img, rows, cols, stride, d_out, out_stride, iterations, norm_area, true,
+                        d_alphas, (hipStream_t)stream);
+}
+
+int fdr_richardson_lucy_accel_f32(fdr_plan* p, const float* img_host, int rows, int cols, int stride, float* out_host, int out_stride,
+                                  int iterations, int norm_area, float* alphas_host) {
+    return rl_host_entry(p, "fdr_richardson_lucy_accel_f32", img_host, rows, cols, stride, out_host, out_stride, iterations, norm_area, true,
+                         alphas_host);
 }
 
 }  // extern "C"

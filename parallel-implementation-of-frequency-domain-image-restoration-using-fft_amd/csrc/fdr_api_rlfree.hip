@@ -1,4 +1,4 @@
-// fdr_api_rlfree.hip -- free-boundary, weighted Richardson-Lucy (fdr_richardson_lucy_free_f32*; kernels in fdr_rlfree.hip and the
+// fdr_api_rlfree.hip -- free-boundary, weighted Richardson-Lucy, plain and accelerated (fdr_richardson_lucy_free_f32*, _free_accel_f32*; kernels in fdr_rlfree.hip and the
 // weighted update kind of fdr_panel_rows.hip): the workspace, the checks, the driver and the two entry points.  Every transform is an
 // operator pass of fdr_api_operator.hip: the estimate goes through pass A as a dense M x N plane, the ratio through the window.
 #include "fdr_host.hpp"
@@ -63,12 +63,33 @@ int rlfree_check(const fdr_plan* p, const char* fn, const float* img, int rows, 
     return FDR_OK;
 }
 
+// one iteration on the whole plan: c = window(fullblur(y)), r = dw / c into the plan's raw plane, out = max(y wgt fullblur^T(pad(r)), 0);
+// y and out are dense M x N planes, and `out` may be y itself
+int rlfree_step(fdr_plan* p, const float* y, float* out, int rows, int cols, hipStream_t s) {
+    const int M = p->M, N = p->N;
+    float* r = p->slots[0].raw;
+    int rc = op_rows_fwd(p, y, M, N, N, s);                                                         // c = fullblur(y) ...
+    if (rc == FDR_OK) rc = op_cols(p, false, s);
+    if (rc == FDR_OK) rc = op_rows_inv(p, ROW_OUT_RL_RATIO, kPassRfRatio, p->rf_dw, cols, r, cols, rows, cols, s);  // ... r = dw / c
+    if (rc == FDR_OK) rc = op_rows_fwd(p, r, rows, cols, cols, s);                                  // g = fullblur^T(pad(r)) ...
+    if (rc == FDR_OK) rc = op_cols(p, true, s);
+    if (rc != FDR_OK) return rc;
+    ScopedPass t(p, s, kPassRfUpdate);                                                              // ... out = max(y wgt g, 0)
+    RowArgs a = panel_row_args(p);
+    a.src_c = p->slots[0].work;
+    a.src_real = y; a.src_real2 = p->rf_wgt; a.src_stride = N;
+    a.out = out; a.out_rows = M; a.out_cols = N; a.out_stride = N;
+    FDR_HIP(launch_rows4(p->logN, ROW_IN_COMPLEX, ROW_OUT_RL_UPDATE_W, a, p->tw_row_f, s));
+    return FDR_OK;
+}
+
 // u and wgt are dense M x N planes of the workspace, dw and r (the plan's raw plane) dense rows x cols.  W = pad(m) lies in u's
 // plane until alpha has been transformed out of it; d_w may be that plane itself (the host form stages the weights there).
+// Accelerated (rl_accel_loop), the estimate alternates between u's plane and one of the acceleration workspace.
 int rlfree_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, int cols, int stride, const float* d_w, int wstride,
-                    float* d_out, int out_stride, const fdr_rlfree_params& prm, hipStream_t s) {
+                    float* d_out, int out_stride, const fdr_rlfree_params& prm, bool accel, float* d_alphas, hipStream_t s) {
     const int M = p->M, N = p->N;
-    float *u = p->rf_u, *wgt = p->rf_wgt, *dw = p->rf_dw, *r = p->slots[0].raw;
+    float *u = p->rf_u, *wgt = p->rf_wgt, *dw = p->rf_dw;
     const int n_part = rlfree_partials(rows, cols);
     {
         ScopedPass t(p, s, kPassRfSetup);
@@ -80,20 +101,13 @@ int rlfree_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, i
         ScopedPass t(p, s, kPassRfStart);
         FDR_HIP(launch_rlfree_start(wgt, u, (size_t)M * N, prm.sigma, p->rf_part + 2 * (size_t)n_part, s));
     }
-    for (int it = 0; it < prm.iterations && rc == FDR_OK; ++it) {
-        rc = op_rows_fwd(p, u, M, N, N, s);                                                             // c = fullblur(u) ...
-        if (rc == FDR_OK) rc = op_cols(p, false, s);
-        if (rc == FDR_OK) rc = op_rows_inv(p, ROW_OUT_RL_RATIO, kPassRfRatio, dw, cols, r, cols, rows, cols, s);  // ... r = dw / c
-        if (rc == FDR_OK) rc = op_rows_fwd(p, r, rows, cols, cols, s);                                  // g = fullblur^T(pad(r)) ...
-        if (rc == FDR_OK) rc = op_cols(p, true, s);
-        if (rc == FDR_OK) {                                                                             // ... u = max(u wgt g, 0)
-            ScopedPass t(p, s, kPassRfUpdate);
-            RowArgs a = panel_row_args(p);
-            a.src_c = p->slots[0].work;
-            a.src_real = u; a.src_real2 = wgt; a.src_stride = N;
-            a.out = u; a.out_rows = M; a.out_cols = N; a.out_stride = N;
-            FDR_HIP(launch_rows4(p->logN, ROW_IN_COMPLEX, ROW_OUT_RL_UPDATE_W, a, p->tw_row_f, s));
-        }
+    if (accel) {
+        float* const U[2] = {u, p->ra_u};
+        const int us[2] = {N, N};
+        rc = rl_accel_loop(p, prm.iterations, M, N, U, us, 0, nullptr, 0, d_alphas, s,
+                           [&](const float* y, int, float* out, int) { return rlfree_step(p, y, out, rows, cols, s); }, &u);
+    } else {
+        for (int it = 0; it < prm.iterations && rc == FDR_OK; ++it) rc = rlfree_step(p, u, u, rows, cols, s);
     }
     if (rc != FDR_OK) return rc;
     if (prm.norm_area == FDR_NORM_NONE) {
@@ -104,40 +118,76 @@ int rlfree_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, i
     return normalize_window(p, fn, kPassRfNorm, u, N, prm.out_rows, prm.out_cols, prm.norm_area, d_out, out_stride, s);
 }
 
+// the checks, the device, the workspaces and the driver of the four entry points; the accelerated ones also refuse alphas that
+// overlap a window
+int rlfree_dev_entry(fdr_plan* p, const char* fn, const float* d_img, int rows, int cols, int stride, const float* d_weights, int wstride,
+                     float* d_out, int out_stride, const fdr_rlfree_params* params, bool accel, float* d_alphas, hipStream_t s) {
+    if (!p || !d_img || !d_out) return null_arg(fn);
+    int rc = rlfree_check(p, fn, d_img, rows, cols, stride, d_weights, wstride, d_out, out_stride, params);
+    if (rc == FDR_OK && accel)
+        rc = check_alphas(fn, d_alphas, params->iterations, d_out, out_stride, params->out_rows, params->out_cols, "output");
+    if (rc == FDR_OK && accel) rc = check_alphas(fn, d_alphas, params->iterations, d_img, stride, rows, cols, "input");
+    if (rc == FDR_OK && accel && d_weights) rc = check_alphas(fn, d_alphas, params->iterations, d_weights, wstride, rows, cols, "weights");
+    if (rc != FDR_OK) return rc;
+    FDR_HIP(hipSetDevice(p->device));
+    rc = ensure_rlfree_workspace(p, fn);
+    if (rc == FDR_OK && accel) rc = ensure_rlaccel_workspace(p, fn);
+    if (rc != FDR_OK) return rc;
+    return rlfree_dev_impl(p, fn, d_img, rows, cols, stride, d_weights, wstride, d_out, out_stride, *params, accel, d_alphas, s);
+}
+
+int rlfree_host_entry(fdr_plan* p, const char* fn, const float* img_host, int rows, int cols, int stride, const float* weights_host,
+                      int wstride, float* out_host, int out_stride, const fdr_rlfree_params* params, bool accel, float* alphas_host) {
+    if (!p || !img_host || !out_host) return null_arg(fn);
+    int rc = rlfree_check(p, fn, img_host, rows, cols, stride, weights_host, wstride, out_host, out_stride, params);
+    if (rc != FDR_OK) return rc;
+    FDR_HIP(hipSetDevice(p->device));
+    rc = ensure_rlfree_workspace(p, fn);
+    if (rc == FDR_OK && accel) rc = ensure_rlaccel_workspace(p, fn);
+    if (rc != FDR_OK) return rc;
+    const fdr_rlfree_params prm = *params;
+    DeviceBuffer d_alphas;
+    if (accel && alphas_host && prm.iterations > 0) FDR_ALLOC(d_alphas, (size_t)prm.iterations * sizeof(float), fn);
+    if (weights_host)  // staged dense into u's plane, where the setup pass leaves W anyway
+        FDR_HIP(hipMemcpy2D(p->rf_u, (size_t)cols * sizeof(float), weights_host, (size_t)wstride * sizeof(float), (size_t)cols * sizeof(float),
+                            (size_t)rows, hipMemcpyHostToDevice));
+    rc = host_image_call(p, fn, img_host, rows, cols, stride, out_host, prm.out_rows, prm.out_cols, out_stride,
+                         [&](const float* d_in, float* d_out) {
+                             return rlfree_dev_impl(p, fn, d_in, rows, cols, cols, weights_host ? p->rf_u : nullptr, cols, d_out, prm.out_cols,
+                                                    prm, accel, d_alphas.as<float>(), nullptr);
+                         });
+    if (rc == FDR_OK && d_alphas.ptr)
+        FDR_HIP(hipMemcpy(alphas_host, d_alphas.ptr, (size_t)prm.iterations * sizeof(float), hipMemcpyDeviceToHost));
+    return rc;
+}
+
 }  // namespace
 
 extern "C" {
 
 int fdr_richardson_lucy_free_f32_dev(fdr_plan* p, const float* d_img, int rows, int cols, int stride, const float* d_weights, int wstride,
                                      float* d_out, int out_stride, const fdr_rlfree_params* params, void* stream) {
-    const char* fn = "fdr_richardson_lucy_free_f32_dev";
-    if (!p || !d_img || !d_out) return null_arg(fn);
-    int rc = rlfree_check(p, fn, d_img, rows, cols, stride, d_weights, wstride, d_out, out_stride, params);
-    if (rc != FDR_OK) return rc;
-    FDR_HIP(hipSetDevice(p->device));
-    rc = ensure_rlfree_workspace(p, fn);
-    if (rc != FDR_OK) return rc;
-    return rlfree_dev_impl(p, fn, d_img, rows, cols, stride, d_weights, wstride, d_out, out_stride, *params, (hipStream_t)stream);
+    return rlfree_dev_entry(p, "fdr_richardson_lucy_free_f32_dev", d_img, rows, cols, stride, d_weights, wstride, d_out, out_stride, params,
+                            false, nullptr, (hipStream_t)stream);
 }
 
 int fdr_richardson_lucy_free_f32(fdr_plan* p, const float* img_host, int rows, int cols, int stride, const float* weights_host, int wstride,
                                  float* out_host, int out_stride, const fdr_rlfree_params* params) {
-    const char* fn = "fdr_richardson_lucy_free_f32";
-    if (!p || !img_host || !out_host) return null_arg(fn);
-    int rc = rlfree_check(p, fn, img_host, rows, cols, stride, weights_host, wstride, out_host, out_stride, params);
-    if (rc != FDR_OK) return rc;
-    FDR_HIP(hipSetDevice(p->device));
-    rc = ensure_rlfree_workspace(p, fn);
-    if (rc != FDR_OK) return rc;
-    if (weights_host)  // staged dense into u's plane, where the setup pass leaves W anyway
-        FDR_HIP(hipMemcpy2D(p->rf_u, (size_t)cols * sizeof(float), weights_host, (size_t)wstride * sizeof(float), (size_t)cols * sizeof(float),
-                            (size_t)rows, hipMemcpyHostToDevice));
-    const fdr_rlfree_params prm = *params;
-    return host_image_call(p, fn, img_host, rows, cols, stride, out_host, prm.out_rows, prm.out_cols, out_stride,
-                           [&](const float* d_in, float* d_out) {
-                               return rlfree_dev_impl(p, fn, d_in, rows, cols, cols, weights_host ? p->rf_u : nullptr, cols, d_out, prm.out_cols,
-                                                      prm, nullptr);
-                           });
+    return rlfree_host_entry(p, "fdr_richardson_lucy_free_f32", img_host, rows, cols, stride, weights_host, wstride, out_host, out_stride,
+                             params, false, nullptr);
+}
+
+int fdr_richardson_lucy_free_accel_f32_dev(fdr_plan* p, const float* d_img, int rows, int cols, int stride, const float* d_weights,
+                                           int wstride, float* d_out, int out_stride, const fdr_rlfree_params* params, float* d_alphas,
+                                           void* stream) {
+    return rlfree_dev_entry(p, "fdr_richardson_lucy_free_accel_f32_dev", d_img, rows, cols, stride, d_weights, wstride, d_out, out_stride,
+                            params, true, d_alphas, (hipStream_t)stream);
+}
+
+int fdr_richardson_lucy_free_accel_f32(fdr_plan* p, const float* img_host, int rows, int cols, int stride, const float* weights_host,
+                                       int wstride, float* out_host, int out_stride, const fdr_rlfree_params* params, float* alphas_host) {
+    return rlfree_host_entry(p, "fdr_richardson_lucy_free_accel_f32", img_host, rows, cols, stride, weights_host, wstride, out_host,
+                             out_stride, params, true, alphas_host);
 }
 
 }  // extern "C"

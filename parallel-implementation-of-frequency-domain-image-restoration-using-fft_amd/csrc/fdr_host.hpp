@@ -147,6 +147,13 @@ struct fdr_plan {
     void* rf_block = nullptr;
     float *rf_u = nullptr, *rf_wgt = nullptr, *rf_dw = nullptr;
     double* rf_part = nullptr;
+    // accelerated Richardson-Lucy, both forms (fdr_richardson_lucy_accel_f32*, fdr_richardson_lucy_free_accel_f32*): made by the
+    // first such call, kept until fdr_plan_destroy -- one allocation holding three M x N real planes (the extrapolated point y, the
+    // second plane of the estimate, the direction g), the 2 rlaccel_partials(M, N) double partials and alpha
+    void* ra_block = nullptr;
+    float *ra_y = nullptr, *ra_u = nullptr, *ra_g = nullptr;
+    double* ra_part = nullptr;
+    float* ra_alpha = nullptr;
     // choosing the regularisation weight (fdr_reg_curve_f32*, fdr_choose_reg_f32*): made by the first such call, kept until
     // fdr_plan_destroy -- one allocation holding the power plane (ws_elems floats in the layout of `filt`, one float per bin, then the
     // two extra floats of the packed column), the partials of the sweep and of the noise sum, and the candidate and result arrays
@@ -306,6 +313,18 @@ int blur_window_dev(fdr_plan* p, const float* d_img, int rows, int cols, int str
 // counting the zeros outside it too
 int normalize_window(fdr_plan* p, const char* fn, const char* name, const float* fin, int fs, int rows, int cols, int norm_area, float* d_out,
                      int out_stride, hipStream_t s);
+// ---- accelerated Richardson-Lucy (fdr_api_rlaccel.hip), shared by the plain and the free-boundary form ----
+// the workspace of the accelerated calls; FDR_ERR_ALLOC, sticky HIP error cleared and plan intact, if it cannot be had
+int ensure_rlaccel_workspace(fdr_plan* p, const char* fn);
+// FDR_ERR_ARG when the n floats at d_alphas overlap the rows x cols window at `w` (row stride ws); a null d_alphas is fine
+int check_alphas(const char* fn, const float* d_alphas, int n, const float* w, int ws, int rows, int cols, const char* what);
+// One iteration of either form: u_next = step(y), y a rows x cols window with row stride ys, `out` another plane
+using RlStep = std::function<int(const float* y, int ys, float* out, int os)>;
+// n accelerated iterations on a rows x cols window.  u_k lives in U[(first + k) & 1] (row strides us[]), u_0 there on entry; the
+// last step writes to `fin` (row stride fs) when it is not null.  *result, when not null, receives the plane of u_n.  alpha_0 ..
+// alpha_(n-1) go to d_alphas when it is not null.  For n <= 2 this is n steps and nothing else.
+int rl_accel_loop(fdr_plan* p, int n, int rows, int cols, float* const U[2], const int us[2], int first, float* fin, int fs, float* d_alphas,
+                  hipStream_t s, const RlStep& step, float** result);
 // pairs of one fdr_reg_curve_f32* call (fdr_api_reg.hip): what the candidate and result arrays of the plan hold
 constexpr int kRegMaxCurve = 4096;
 static_assert(kRegMaxCurve % kRegCandidates == 0, "the last sweep reads kRegCandidates pairs");

@@ -174,6 +174,17 @@ hipError_t launch_rlfree_setup(const float* d, int stride, const float* m, int m
                                hipStream_t s);
 hipError_t launch_rlfree_start(float* wgt, float* u, size_t count, float sigma, const double* sums, hipStream_t s);
 hipError_t launch_rlfree_crop(const float* u, int ustride, float* out, int rows, int cols, int out_stride, hipStream_t s);
+// (fdr_rlaccel.hip) accelerated Richardson-Lucy, on rows x cols windows with their own row strides.  direction: g = u1 - y over the
+// previous g; with `part` not null also sum(g_new g_old) and sum(g_old g_old) in double as rlaccel_partials(rows, cols)
+// per-workgroup partials each (part holds 2 n doubles); with a null `part` the old g is not read.  alpha: one workgroup folds the
+// partials in index order, alpha = clamp(num / den, 0, amax) (0 for den = 0 or a quotient that is not finite) to *alpha and, when
+// not null, *record.  extrapolate: y = max(u1 + alpha (u1 - u0), 0), alpha read from the device.
+int rlaccel_partials(int rows, int cols);
+hipError_t launch_rlaccel_direction(const float* u1, int u1s, const float* y, int ys, float* g, int gs, int rows, int cols, double* part,
+                                    hipStream_t s);
+hipError_t launch_rlaccel_alpha(const double* part, int n, float amax, float* alpha, float* record, hipStream_t s);
+hipError_t launch_rlaccel_extrapolate(const float* u1, int u1s, const float* u0, int u0s, const float* alpha, float* y, int ys, int rows,
+                                      int cols, hipStream_t s);
 // (fdr_tv.hip) total-variation deconvolution.  table: T = (1 / (M N)) / (mu |H|^2 + rho L) from op_h = H / (M N) (the operator table
 // of launch_cols_panel_operator) and the Laplacian table `lap` of launch_cols_panel_cls, in the layout pass B' reads its filter
 // from.  init: x = pad(d) over the M x N plan (row stride N), wx = wy = 0.  spatial: one ADMM half-step on full M x N planes --

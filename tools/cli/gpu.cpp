@@ -1,5 +1,5 @@
 // gpu.cpp -- ./gpu <img-path> <psf-length> <psf-angle> [--out file] [--mode fast|parity] [--norm padded|cropped] [--host-epilogue]
-//           [--cls gamma|auto] [--k K|auto] [--reg gcv|discrepancy] [--sigma s] [--pad zero|smooth] [--rl iterations [--free-boundary [--mask mask.png]]] [--tv mu [--tv-iters n] [--tv-rho r]]
+//           [--cls gamma|auto] [--k K|auto] [--reg gcv|discrepancy] [--sigma s] [--pad zero|smooth] [--rl iterations [--accel] [--free-boundary [--mask mask.png]]] [--tv mu [--tv-iters n] [--tv-rho r]]
 // `auto auto` for length and angle: the blur is estimated first (fft_gpu::estimateMotionBlur on the per-pixel mean of B, G and R),
 // printed as `estimate: length L angle A confidence C`, and the run then goes on exactly as `./gpu <img-path> L A` would.
 // `--cls auto` (gamma, with K = 0) or `--k auto` (K, with gamma = 0): the weight is chosen first (fft_gpu::chooseRegularisation on the same
@@ -71,6 +71,7 @@ int main(int argc, char** argv) {
     bool verify = false;         // --verify: areChannelsEqual(parity-mode result, this run's result)
     bool host_epilogue = false;  // Lab white balance on the host (the A/B reference of the device epilogue)
     int rl_iterations = -1;      // --rl n: a timed Richardson-Lucy leg after the naive one; its planes are the written result
+    bool accel = false;          // --accel: the --rl leg runs the accelerated iteration (vector extrapolation)
     bool free_boundary = false;  // --free-boundary: the --rl leg is fft_gpu::richardsonLucyFree_RGB (the picture is a crop of a larger scene)
     string mask_path;            // --mask file: pixels that are 0 in it (any channel counts) get weight 0, the others weight 1
     float tv_mu = -1.f, tv_rho = 2.0f;  // --tv mu: a timed total-variation leg (fft_gpu::tvDeblur_RGB); its planes are the written result
@@ -115,6 +116,7 @@ int main(int argc, char** argv) {
         }
         // Richardson-Lucy (fft_gpu::richardsonLucy_RGB, fast mode): n >= 0 iterations
         else if (a == "--rl" && i + 1 < argc) rl_iterations = atoi(argv[++i]);
+        else if (a == "--accel") accel = true;
         else if (a == "--free-boundary") free_boundary = true;
         else if (a == "--mask" && i + 1 < argc) mask_path = argv[++i];
         // total-variation deconvolution (fft_gpu::tvDeblur_RGB, fast mode): mu > 0, n >= 0 iterations, penalty rho > 0
@@ -133,8 +135,8 @@ int main(int argc, char** argv) {
     if (rl_iterations >= 0 && (cls || verify || parity || pad_smooth)) { cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle>\n"; return -1; }
     // --verify compares against the zero-padded serial leg
     if (pad_smooth && verify) { cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle>\n"; return -1; }
-    // --free-boundary belongs to --rl, --mask to --free-boundary
-    if ((free_boundary && rl_iterations < 0) || (!mask_path.empty() && !free_boundary)) {
+    // --free-boundary and --accel belong to --rl, --mask to --free-boundary
+    if ((free_boundary && rl_iterations < 0) || (accel && rl_iterations < 0) || (!mask_path.empty() && !free_boundary)) {
         cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle>\n";
         return -1;
     }
@@ -240,11 +242,11 @@ int main(int argc, char** argv) {
     if (rl_iterations >= 0) {  // Richardson-Lucy on the same channels: its planes become the written result
         vector<Mat> rl = input;
         t_start = high_resolution_clock::now();
-        if (free_boundary) fft_gpu::richardsonLucyFree_RGB(rl, psf, rl_iterations, weights);
-        else fft_gpu::richardsonLucy_RGB(rl, psf, rl_iterations);
+        if (free_boundary) fft_gpu::richardsonLucyFree_RGB(rl, psf, rl_iterations, weights, accel);
+        else fft_gpu::richardsonLucy_RGB(rl, psf, rl_iterations, accel);
         t_end = high_resolution_clock::now();
         cout << "Deblurring 3 channels took(gpu[richardson-lucy " << (free_boundary ? "free-boundary " : "") << rl_iterations
-             << "]): " << getElapsedMs(t_start, t_end) << " ms\n";
+             << (accel ? " accelerated" : "") << "]): " << getElapsedMs(t_start, t_end) << " ms\n";
         channels = rl;
     }
 
