@@ -335,6 +335,74 @@ int fdr_richardson_lucy_free_accel_f32_dev(fdr_plan* plan, const float* d_img, i
                                            int wstride, float* d_out, int out_stride, const fdr_rlfree_params* params, float* d_alphas,
                                            void* stream);
 
+/* -- Richardson-Lucy that stops from the data: the fit trace and the discrepancy rules.  The iteration count is RL's only
+ *    regularisation: on noisy data the estimate first sharpens, then fits the noise.  These calls run any of the four forms above
+ *    (free_boundary, accelerate) and measure, inside the ratio pass of every step and at no extra pass, how well the reblurred
+ *    point fits the data.  With c = blur(y_k) on the window (y_k = u_k in the plain forms, the extrapolated point in the
+ *    accelerated ones: the input of step k), d+ = max(d, 0) and w the pixel's weight (1 in the plain form; m, or 1 for NULL weights,
+ *    in the free-boundary form):
+ *        res_k = sum w (d+ - c)^2
+ *        kl_k  = sum w ( c - d+ + (d+ > 0 && c > FDR_RL_TAU ? d+ ln(d+ / c) : 0) )          (the generalised Kullback-Leibler distance)
+ *    both over the window, in double and in a fixed order (each thread adds its terms in order, a fixed tree per workgroup, one
+ *    workgroup folds the partials in index order; no atomics), so a trace is bit-identical from call to call.  trace[2 k] = res_k,
+ *    trace[2 k + 1] = kl_k.  With S = rows cols (plain form) or S = sum(W), the double sum of the setup (free-boundary form):
+ *        FDR_RL_STOP_NONE      `iterations` steps, the trace only.
+ *        FDR_RL_STOP_RESIDUAL  Gaussian noise (Morozov's discrepancy principle): stat_k = res_k, target = tau sigma^2 S; sigma = 0
+ *                              estimates it from the window (fdr_noise_sigma; the weights are not looked at).
+ *        FDR_RL_STOP_KL        Poisson noise, d in units of 1 / gain photons (Bertero, Boccacci, Talenti, Zanella, Zanni 2010, "A
+ *                              discrepancy principle for Poisson data"): stat_k = 2 gain kl_k / S, target = tau.
+ *    k* is the first k with stat_k <= target.  The step in flight is always finished and the host looks only after every
+ *    check_every steps: iterations_done = min(n, c ceil((k* + 1) / c)), c = check_every; without such a k, iterations_done = n and
+ *    stopped = 0.  The output is u_(iterations_done): bit for bit what the call of the same form returns for iterations =
+ *    iterations_done with the same norm_area and output window.  result->sigma is the sigma used (RESIDUAL; else the one passed),
+ *    result->target the target, result->statistic the last stat_k the decision looked at (stat_k* when it stopped, else that of
+ *    the last step); target and statistic are 0 with FDR_RL_STOP_NONE.  trace may be NULL; otherwise it receives
+ *    2 iterations_done doubles (room for 2 n is needed).
+ *    With FDR_RL_STOP_NONE the _dev form makes no read-back, stays asynchronous on `stream` and allocates nothing after the first
+ *    call.  With a rule it is synchronous, as fdr_choose_reg_f32_dev is: it reads 2 check_every doubles back every check_every
+ *    steps (and sum(W), and the noise sum for sigma = 0, once).  The rule errs on the early side: it stops at the first iterate
+ *    that fits to within the noise, which on the scenes tried lay at or up to 0.2 dB below the best iterate and always above the
+ *    blurred input; in the accelerated forms the trace speaks of y_k, not of u_k; a textured picture
+ *    inflates the estimated sigma and so stops earlier still.
+ *    Plans, refusals, overlap rules and phases are those of the underlying form (cov_sigma, out_rows and out_cols are the sigma,
+ *    out_rows and out_cols of fdr_rlfree_params; the plain form takes out_rows = out_cols = 0 or rows, cols).  FDR_ERR_ARG also for
+ *    a null params or result, an unknown rule, KL with a gain that is not finite and > 0, a sigma or tau that is negative or not
+ *    finite, check_every < 0, a weights pointer in the plain form, a window below 3 x 3 when sigma is to be estimated, and a
+ *    d_trace range (2 n doubles) that overlaps a window; always before any device work, the plan usable afterwards.  The first
+ *    call on a plan allocates the workspace, kept until fdr_plan_destroy: 16 bytes per workgroup of the inverse row pass, the
+ *    partials of the noise estimate, an internal trace of 1024 steps (it grows only for a call with a rule, without the caller's
+ *    trace and with more steps than that) and, for the free-boundary form with weights, two M x N float planes (the dense weights
+ *    and the dense copy of d: the ratio pass forms dw = w d+ itself, the float product of the setup); FDR_ERR_ALLOC, plan intact, if
+ *    it cannot be had.  The workspaces of the underlying form are needed as before.                                                      */
+#define FDR_RL_STOP_NONE 0     /* run `iterations` steps, record the trace only */
+#define FDR_RL_STOP_RESIDUAL 1 /* Gaussian noise: res_k <= tau sigma^2 S */
+#define FDR_RL_STOP_KL 2       /* Poisson noise (Bertero et al. 2010): 2 gain kl_k / S <= tau */
+typedef struct fdr_rl_auto_params {
+    int iterations;    /* the most steps taken, >= 0 */
+    int free_boundary; /* 0: the plain form; else the free-boundary, weighted form */
+    int accelerate;    /* 0: the plain iteration; else Biggs & Andrews' extrapolation */
+    int rule;          /* FDR_RL_STOP_* */
+    float sigma;       /* RESIDUAL: noise standard deviation; 0 = fdr_noise_sigma of the window */
+    float gain;        /* KL: photons per unit of d, > 0 */
+    float tau;         /* 0 = 1 */
+    int check_every;   /* 0 = 1 */
+    int norm_area;     /* FDR_NORM_NONE / FDR_NORM_CROPPED / FDR_NORM_PADDED */
+    float cov_sigma;   /* free form: as fdr_rlfree_params.sigma */
+    int out_rows;      /* free form: as fdr_rlfree_params; plain form: 0 or rows */
+    int out_cols;      /* free form: as fdr_rlfree_params; plain form: 0 or cols */
+} fdr_rl_auto_params;
+typedef struct fdr_rl_auto_result {
+    int iterations_done;
+    int stopped; /* 1: the rule fired; 0: `iterations` steps were taken */
+    double sigma, target, statistic;
+} fdr_rl_auto_result;
+int fdr_richardson_lucy_auto_f32(fdr_plan* plan, const float* img_host, int rows, int cols, int stride, const float* weights_host,
+                                 int wstride, float* out_host, int out_stride, const fdr_rl_auto_params* params,
+                                 fdr_rl_auto_result* result, double* trace_host);
+int fdr_richardson_lucy_auto_f32_dev(fdr_plan* plan, const float* d_img, int rows, int cols, int stride, const float* d_weights,
+                                     int wstride, float* d_out, int out_stride, const fdr_rl_auto_params* params,
+                                     fdr_rl_auto_result* result, double* d_trace, void* stream);
+
 /* -- total-variation (TV) regularised deconvolution by ADMM / split Bregman (Rudin-Osher-Fatemi 1992; Wang-Yang-Yin-Zhang 2008
  *    "FTVd"; Goldstein-Osher 2009): the edge-preserving restoration beside the linear filters and RL.  It uses the operator PSF of
  *    fdr_set_operator_psf* (H = DFT2 of the PSF top-left in the plan, blur / blur^T as above) and lives on the whole periodic

@@ -273,6 +273,52 @@ inline void richardsonLucyFree_RGB(std::vector<Mat>& channels, const Mat& psf, i
                                    bool accelerate = false) {
     richardsonLucyFree_RGB(channels, psf, iterations, weights, defaults(), FDR_RL_SIGMA, accelerate);
 }
+// What richardsonLucyAuto_RGB takes beside the picture: the rule (FDR_RL_STOP_*) and its arguments as fdr_rl_auto_params has them
+// (sigma 0 = estimated per channel; tau and check_every 0 = 1), the form, and the weights and coverage threshold of the free form.
+struct RlAutoOptions {
+    float sigma = 0.f, gain = 0.f, tau = 0.f;
+    int check_every = 0;
+    bool free_boundary = false, accelerate = false;
+    Mat weights;
+    float cov_sigma = FDR_RL_SIGMA;
+};
+// Richardson-Lucy that chooses its own iteration count (fdr_richardson_lucy_auto_f32, include/fdr.h) of every channel, in place: at
+// most max_iterations steps of the form a.free_boundary / a.accelerate asks for, on the plan and operator PSF of richardsonLucy_RGB
+// (free form: of richardsonLucyFree_RGB), stopped per channel by `rule`.  Returns the channels' results (iterations_done, stopped,
+// sigma, target, statistic), in order.
+inline std::vector<fdr_rl_auto_result> richardsonLucyAuto_RGB(std::vector<Mat>& channels, const Mat& psf, int max_iterations, int rule,
+                                                              const RlAutoOptions& a, const Options& o) {
+    std::vector<fdr_rl_auto_result> results;
+    if (channels.empty()) return results;
+    const int rows = channels[0].rows, cols = channels[0].cols;
+    if (!a.weights.empty() && (!a.free_boundary || a.weights.rows != rows || a.weights.cols != cols || a.weights.type() != CV_32F)) {
+        std::cerr << "richardsonLucyAuto_RGB: the weights belong to the free-boundary form, must be CV_32F and have the picture's size\n";
+        exit(1);
+    }
+    bool created = false;
+    PlanCacheSettle settle_;
+    const int pr = a.free_boundary ? rows + psf.rows - 1 : rows, pc = a.free_boundary ? cols + psf.cols - 1 : cols;
+    fdr_plan* plan = plan_cache().get(o.device, std::max(8, nextPowerOfTwo(pr)), std::max(32, nextPowerOfTwo(pc)), FDR_MODE_FAST, &created);
+    Mat psfc = psf.isContinuous() ? psf : psf.clone();
+    FDR_CHECK(fdr_set_operator_psf(plan, psfc.ptr<float>(0), psf.rows, psf.cols, psf.cols));
+    Mat w = a.weights.empty() || a.weights.isContinuous() ? a.weights : a.weights.clone();
+    for (Mat& c : channels) {
+        Mat src = c.isContinuous() ? c : c.clone();
+        Mat out(c.rows, c.cols, CV_32F);
+        const fdr_rl_auto_params prm = {max_iterations, a.free_boundary ? 1 : 0, a.accelerate ? 1 : 0, rule, a.sigma, a.gain, a.tau, a.check_every,
+                                        o.norm_area, a.cov_sigma, c.rows, c.cols};
+        fdr_rl_auto_result res = {};
+        FDR_CHECK(fdr_richardson_lucy_auto_f32(plan, src.ptr<float>(0), c.rows, c.cols, c.cols, w.empty() ? nullptr : w.ptr<float>(0), cols,
+                                               out.ptr<float>(0), c.cols, &prm, &res, nullptr));
+        results.push_back(res);
+        c = out;
+    }
+    return results;
+}
+inline std::vector<fdr_rl_auto_result> richardsonLucyAuto_RGB(std::vector<Mat>& channels, const Mat& psf, int max_iterations, int rule,
+                                                              const RlAutoOptions& a = RlAutoOptions()) {
+    return richardsonLucyAuto_RGB(channels, psf, max_iterations, rule, a, defaults());
+}
 // Total-variation deconvolution (fdr_tv_deconv_f32, include/fdr.h) of every channel, in place: the plan and operator PSF of
 // richardsonLucy_RGB, `iterations` ADMM steps of mu / 2 ||blur(x) - d||^2 + TV(x) (isotropic) with penalty rho, the output clamped
 // at 0 and normalised by o.norm_area.  o.mode and o.cls_gamma do not apply.

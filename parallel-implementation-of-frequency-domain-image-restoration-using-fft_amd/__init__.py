@@ -31,6 +31,7 @@ NORM_PADDED = 1
 NORM_CROPPED = 0
 NORM_NONE = 2  # Richardson-Lucy only: the raw estimate
 RL_SIGMA = 1e-2  # FDR_RL_SIGMA: the usual coverage threshold of free-boundary Richardson-Lucy
+RL_STOP_NONE, RL_STOP_RESIDUAL, RL_STOP_KL = 0, 1, 2  # FDR_RL_STOP_*: the stopping rules of Plan.richardson_lucy_auto
 RL_ACCEL_MAX = 0.9990234375  # FDR_RL_ACCEL_MAX = 1 - 2^-10: the upper bound of accelerated Richardson-Lucy's extrapolation factor
 MAX_PASSES = 16
 OPT_TWO_SWEEP_NORM = 2
@@ -80,6 +81,24 @@ class RlFreeParams(ctypes.Structure):
     """fdr_rlfree_params of include/fdr.h"""
     _fields_ = [("iterations", ctypes.c_int), ("sigma", ctypes.c_float), ("norm_area", ctypes.c_int), ("out_rows", ctypes.c_int),
                 ("out_cols", ctypes.c_int)]
+
+
+class RlAutoParams(ctypes.Structure):
+    """fdr_rl_auto_params of include/fdr.h"""
+    _fields_ = [("iterations", ctypes.c_int), ("free_boundary", ctypes.c_int), ("accelerate", ctypes.c_int), ("rule", ctypes.c_int),
+                ("sigma", ctypes.c_float), ("gain", ctypes.c_float), ("tau", ctypes.c_float), ("check_every", ctypes.c_int),
+                ("norm_area", ctypes.c_int), ("cov_sigma", ctypes.c_float), ("out_rows", ctypes.c_int), ("out_cols", ctypes.c_int)]
+
+
+class RlAutoResultC(ctypes.Structure):
+    """fdr_rl_auto_result of include/fdr.h"""
+    _fields_ = [("iterations_done", ctypes.c_int), ("stopped", ctypes.c_int), ("sigma", ctypes.c_double), ("target", ctypes.c_double),
+                ("statistic", ctypes.c_double)]
+
+
+# the result of Plan.richardson_lucy_auto* / richardsonLucyAuto_myfft beside the image: the steps taken, whether the rule fired, the
+# noise level used, the target and the last statistic the decision saw (in the rule's units)
+RlAutoResult = collections.namedtuple("RlAutoResult", "iterations_done stopped sigma target statistic")
 
 
 class MotionEstimateC(ctypes.Structure):
@@ -210,6 +229,8 @@ def _signatures():
         "fdr_cepstrum_f32_dev": (ci, [vp, vp, ci, ci, ci, vp, vp]),
         "fdr_estimate_motion_f32": (ci, [vp, vp, ci, ci, ci, ci, ci, cd, P(MotionEstimateC), vp]),
         "fdr_estimate_motion_f32_dev": (ci, [vp, vp, ci, ci, ci, ci, ci, cd, P(MotionEstimateC), vp, vp]),
+        "fdr_richardson_lucy_auto_f32": (ci, [vp, vp, ci, ci, ci, vp, ci, vp, ci, P(RlAutoParams), P(RlAutoResultC), vp]),
+        "fdr_richardson_lucy_auto_f32_dev": (ci, [vp, vp, ci, ci, ci, vp, ci, vp, ci, P(RlAutoParams), P(RlAutoResultC), vp, vp]),
         "fdr_noise_sigma_f32": (ci, [ci, vp, ci, ci, ci, P(cd)]),
         "fdr_noise_sigma_f32_dev": (ci, [ci, vp, ci, ci, ci, P(cd), vp]),
         "fdr_reg_curve_f32": (ci, [vp, vp, ci, ci, ci, vp, vp, ci, vp, vp]),
@@ -566,6 +587,46 @@ class Plan:
                                                     ctypes.c_void_p(int(d_weights)) if d_weights else None, int(wstride),
                                                     ctypes.c_void_p(int(d_out)), out_stride, ctypes.byref(prm), _stream(stream)))
 
+    # Richardson-Lucy that stops from the data (include/fdr.h); uses the operator PSF
+    def richardson_lucy_auto(self, img, max_iterations, rule=RL_STOP_RESIDUAL, sigma=0.0, gain=0.0, tau=0.0, check_every=0,
+                             free_boundary=False, accelerate=False, weights=None, cov_sigma=RL_SIGMA, norm_area=NORM_NONE, full_plane=False):
+        """At most max_iterations Richardson-Lucy steps of the chosen form (free_boundary, accelerate) on the window img (host
+        arrays), stopped by `rule` (RL_STOP_NONE: never; RL_STOP_RESIDUAL: Gaussian noise of standard deviation sigma, 0 = estimated;
+        RL_STOP_KL: Poisson noise with `gain` photons per unit) looked at every check_every steps.  weights, cov_sigma and full_plane
+        as Plan.richardson_lucy_free.  Returns (image, RlAutoResult, trace): trace[k] = (res_k, kl_k) of the point step k started
+        from, iterations_done rows."""
+        img = np.ascontiguousarray(img, dtype=np.float32)
+        rows, cols = img.shape
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float32)
+            if w.shape != img.shape:
+                raise ValueError("weights must have the shape of img")
+        orows, ocols = (self.M, self.N) if full_plane and free_boundary else (rows, cols)
+        out = np.empty((orows, ocols), dtype=np.float32)
+        prm = RlAutoParams(int(max_iterations), int(bool(free_boundary)), int(bool(accelerate)), int(rule), float(sigma), float(gain),
+                           float(tau), int(check_every), int(norm_area), float(cov_sigma), orows, ocols)
+        res = RlAutoResultC()
+        trace = np.zeros((max(int(max_iterations), 0), 2), dtype=np.float64)
+        _check(lib.fdr_richardson_lucy_auto_f32(self._h, _ptr(img), rows, cols, cols, _ptr(w) if w is not None else None, cols, _ptr(out),
+                                                ocols, ctypes.byref(prm), ctypes.byref(res), _ptr(trace) if trace.size else None))
+        return out, RlAutoResult(res.iterations_done, res.stopped, res.sigma, res.target, res.statistic), trace[:res.iterations_done]
+
+    def richardson_lucy_auto_dev(self, d_img, rows, cols, stride, d_out, out_stride, max_iterations, rule=RL_STOP_RESIDUAL, sigma=0.0,
+                                 gain=0.0, tau=0.0, check_every=0, free_boundary=False, accelerate=False, d_weights=None, wstride=0,
+                                 cov_sigma=RL_SIGMA, norm_area=NORM_NONE, out_rows=None, out_cols=None, d_trace=None, stream=None):
+        """the same on device pointers; d_trace: device room for 2 max_iterations doubles (or None).  Asynchronous with RL_STOP_NONE,
+        synchronous with a rule.  Returns the RlAutoResult."""
+        prm = RlAutoParams(int(max_iterations), int(bool(free_boundary)), int(bool(accelerate)), int(rule), float(sigma), float(gain),
+                           float(tau), int(check_every), int(norm_area), float(cov_sigma), int(rows if out_rows is None else out_rows),
+                           int(cols if out_cols is None else out_cols))
+        res = RlAutoResultC()
+        _check(lib.fdr_richardson_lucy_auto_f32_dev(self._h, ctypes.c_void_p(int(d_img)), rows, cols, stride,
+                                                    ctypes.c_void_p(int(d_weights)) if d_weights else None, int(wstride),
+                                                    ctypes.c_void_p(int(d_out)), out_stride, ctypes.byref(prm), ctypes.byref(res),
+                                                    ctypes.c_void_p(int(d_trace)) if d_trace else None, _stream(stream)))
+        return RlAutoResult(res.iterations_done, res.stopped, res.sigma, res.target, res.statistic)
+
     # total-variation deconvolution by ADMM (include/fdr.h); uses the operator PSF
     def tv_deconv(self, img, mu, rho=2.0, iterations=50, anisotropic=False, nonneg=False, norm_area=NORM_NONE):
         """`iterations` ADMM steps of mu / 2 ||blur(x) - img||^2 + TV(x) on the window img (host arrays), normalised by norm_area."""
@@ -845,6 +906,23 @@ def richardsonLucyFree_myfft(img, psf, iterations, weights=None, sigma=RL_SIGMA,
     with Plan(M, N, MODE_FAST, device) as p:
         p.set_operator_psf(psf)
         return p.richardson_lucy_free(img, iterations, weights, sigma, norm_area, full_plane, accelerate=accelerate)
+
+
+def richardsonLucyAuto_myfft(img, psf, max_iterations, rule=RL_STOP_RESIDUAL, sigma=0.0, gain=0.0, tau=0.0, check_every=0, free_boundary=False,
+                             accelerate=False, weights=None, cov_sigma=RL_SIGMA, device=0, norm_area=NORM_NONE):
+    """Richardson-Lucy of one channel that chooses its own iteration count: the plan of richardsonLucy_myfft (free_boundary: of
+    richardsonLucyFree_myfft), at most max_iterations steps stopped by `rule` as Plan.richardson_lucy_auto describes, crop.  Returns
+    (image, RlAutoResult, trace)."""
+    img = np.asarray(img, dtype=np.float32)
+    psf = np.asarray(psf, dtype=np.float32)
+    if free_boundary:
+        M, N = _rlfree_plan_size(img.shape[0], img.shape[1], psf.shape[0], psf.shape[1])
+    else:
+        M, N = _rl_plan_size(img.shape[0], img.shape[1])
+    with Plan(M, N, MODE_FAST, device) as p:
+        p.set_operator_psf(psf)
+        return p.richardson_lucy_auto(img, max_iterations, rule, sigma, gain, tau, check_every, free_boundary, accelerate, weights, cov_sigma,
+                                      norm_area)
 
 
 def tvDeblur_myfft(img, psf, mu, rho=2.0, iterations=50, anisotropic=False, nonneg=False, device=0, norm_area=NORM_NONE):

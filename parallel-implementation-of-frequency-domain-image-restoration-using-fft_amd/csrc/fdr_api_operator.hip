@@ -20,6 +20,7 @@ const char* const kPassOpColsConj = "B' op cols: FFT*conj(H)*IFFT";
 const char* const kPassOpRowsBlur = "C op rows: IFFT+crop (blur)";
 const char* const kPassRlInit = "RL init: u = max(d, 0)";
 const char* const kPassRlRatio = "C op rows: IFFT+RL ratio";
+const char* const kPassRlRatioFit = "C op rows: IFFT+RL ratio+fit";
 const char* const kPassRlUpdate = "C op rows: IFFT+RL update";
 const char* const kPassRlNorm = "E RL minmax+normalize";
 
@@ -76,11 +77,15 @@ int op_cols_table(fdr_plan* p, const float2* table, const char* name, hipStream_
 }
 // pass C with an operator kind: the window rows x cols of the inverse transform through the kind's epilogue into `out`
 int op_rows_inv(fdr_plan* p, RowOut kind, const char* name, const float* src, int src_stride, float* out, int out_stride, int rows,
-                int cols, hipStream_t s) {
+                int cols, hipStream_t s, const RlFit* fit) {
     ScopedPass t(p, s, name);
     RowArgs a = panel_row_args(p);
     a.src_c = p->slots[0].work;
     a.src_real = src; a.src_stride = src_stride;
+    if (fit) {  // ROW_OUT_RL_RATIO_STAT: the weights beside the datum, the (res, kl) partials in the slot of the min/max ones
+        a.src_real2 = fit->weights;
+        a.mm_part = reinterpret_cast<float2*>(fit->part);
+    }
     a.out = out; a.out_rows = rows; a.out_cols = cols; a.out_stride = out_stride;
     FDR_HIP(launch_rows4(p->logN, ROW_IN_COMPLEX, kind, a, p->tw_row_f, s));
     return FDR_OK;
@@ -118,8 +123,6 @@ int blur_window_dev(fdr_plan* p, const float* d_img, int rows, int cols, int str
     return rc;
 }
 
-}  // namespace fdr
-
 namespace {
 
 // [lo, hi) of the elements a rows x cols window with row stride `stride` spans
@@ -128,6 +131,8 @@ bool windows_overlap(const float* a, int a_stride, const float* b, int b_stride,
     const uintptr_t b0 = (uintptr_t)b, b1 = b0 + ((size_t)(rows - 1) * b_stride + cols) * sizeof(float);
     return a0 < b1 && b0 < a1;
 }
+
+}  // namespace
 
 // everything a Richardson-Lucy call refuses: plan, operator PSF and window, the iteration count, the normalisation, an output
 // that overlaps the input (the input is read on every iteration)
@@ -144,18 +149,25 @@ int rl_check(const fdr_plan* p, const char* fn, const float* img, int rows, int 
 }
 
 // one iteration: c = blur(y), r = d+ / c into the window of the raw plane (row stride cols), out = max(y . blur^T(r), 0); `out` may
-// be y itself
-int rl_step(fdr_plan* p, const float* d_img, int stride, const float* y, int ys, float* out, int os, int rows, int cols, hipStream_t s) {
+// be y itself.  With `fit` the ratio pass is the kind that also leaves the fit partials of c (the same r).
+int rl_step(fdr_plan* p, const float* d_img, int stride, const float* y, int ys, float* out, int os, int rows, int cols, hipStream_t s,
+            const RlFit* fit) {
     float* r = p->slots[0].raw;
     const int rs = cols;
     int rc = op_rows_fwd(p, y, rows, cols, ys, s);                                                    // c = blur(y) ...
     if (rc == FDR_OK) rc = op_cols(p, false, s);
-    if (rc == FDR_OK) rc = op_rows_inv(p, ROW_OUT_RL_RATIO, kPassRlRatio, d_img, stride, r, rs, rows, cols, s);  // ... r = d+ / c
+    if (rc == FDR_OK)                                                                                 // ... r = d+ / c
+        rc = op_rows_inv(p, fit ? ROW_OUT_RL_RATIO_STAT : ROW_OUT_RL_RATIO, fit ? kPassRlRatioFit : kPassRlRatio, d_img, stride, r, rs, rows,
+                         cols, s, fit);
     if (rc == FDR_OK) rc = op_rows_fwd(p, r, rows, cols, rs, s);                                      // g = blur^T(r) ...
     if (rc == FDR_OK) rc = op_cols(p, true, s);
     if (rc == FDR_OK) rc = op_rows_inv(p, ROW_OUT_RL_UPDATE, kPassRlUpdate, y, ys, out, os, rows, cols, s);  // ... out = max(y g, 0)
     return rc;
 }
+
+}  // namespace fdr
+
+namespace {
 
 // u (the estimate) lives in d_out; r in the window of the raw plane (row stride cols), the spectrum in slot 0's work.  With a
 // normalisation the last update (or, for no iterations, the initial estimate) goes to the raw plane instead, and the normalise

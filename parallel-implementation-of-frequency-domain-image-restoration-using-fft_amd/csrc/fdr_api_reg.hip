@@ -54,6 +54,10 @@ int reg_prepare(fdr_plan* p, const char* fn) {
     return rc;
 }
 
+}  // namespace
+
+namespace fdr {
+
 double sigma_of_sum(double S, int rows, int cols) {
     const double pi = 3.14159265358979323846;
     return std::sqrt(pi / 2.0) * S / (6.0 * (double)(rows - 2) * (double)(cols - 2));
@@ -74,6 +78,10 @@ int noise_window_check(const char* fn, int rows, int cols, int stride) {
         return fail(FDR_ERR_ARG, std::string(fn) + ": the noise estimate needs a window of at least 3 x 3 and stride >= cols");
     return FDR_OK;
 }
+
+}  // namespace fdr
+
+namespace {
 
 // pass A and the power pass: P of the window into rg_power
 int reg_power_dev(fdr_plan* p, const float* d_img, int rows, int cols, int stride, hipStream_t s) {

@@ -51,11 +51,16 @@ int check_alphas(const char* fn, const float* d_alphas, int n, const float* w, i
 // iteration still extrapolates, so never for n <= 2 and never after the last step.
 int rl_accel_loop(fdr_plan* p, int n, int rows, int cols, float* const U[2], const int us[2], int first, float* fin, int fs, float* d_alphas,
                   hipStream_t s, const RlStep& step, float** result) {
+    if (d_alphas && n > 0) FDR_HIP(hipMemsetAsync(d_alphas, 0, (size_t)(n < 2 ? n : 2) * sizeof(float), s));  // alpha_0 = alpha_1 = 0
+    if (result) *result = U[first & 1];
+    return rl_accel_steps(p, 0, n, n, rows, cols, U, us, first, fin, fs, d_alphas, s, step, result);
+}
+
+int rl_accel_steps(fdr_plan* p, int k0, int k1, int n, int rows, int cols, float* const U[2], const int us[2], int first, float* fin, int fs,
+                   float* d_alphas, hipStream_t s, const RlStep& step, float** result) {
     float *Y = p->ra_y, *G = p->ra_g;
     const int n_part = rlaccel_partials(rows, cols);
-    float* un = U[first & 1];
-    if (d_alphas && n > 0) FDR_HIP(hipMemsetAsync(d_alphas, 0, (size_t)(n < 2 ? n : 2) * sizeof(float), s));  // alpha_0 = alpha_1 = 0
-    for (int k = 0; k < n; ++k) {
+    for (int k = k0; k < k1; ++k) {
         const int ic = (first + k) & 1, ip = ic ^ 1;
         const bool last = k == n - 1;
         const float* y = U[ic];
@@ -70,14 +75,13 @@ int rl_accel_loop(fdr_plan* p, int n, int rows, int cols, float* const U[2], con
         const int os = last && fin ? fs : us[ip];
         const int rc = step(y, ys, out, os);
         if (rc != FDR_OK) return rc;
-        un = out;
+        if (result) *result = out;
         if (last || n <= 2) continue;
         ScopedPass t(p, s, kPassRaDirection);
         FDR_HIP(launch_rlaccel_direction(out, os, y, ys, G, cols, rows, cols, k >= 1 ? p->ra_part : nullptr, s));
         if (k >= 1)
             FDR_HIP(launch_rlaccel_alpha(p->ra_part, n_part, FDR_RL_ACCEL_MAX, p->ra_alpha, d_alphas ? d_alphas + k + 1 : nullptr, s));
     }
-    if (result) *result = un;
     return FDR_OK;
 }
 

@@ -13,9 +13,14 @@ namespace {
 const char* const kPassRfSetup = "RLF setup: dw, W, sums";
 const char* const kPassRfStart = "RLF start: wgt = 1/alpha, u";
 const char* const kPassRfRatio = "C op rows: IFFT+RL ratio (free)";
+const char* const kPassRfRatioFit = "C op rows: IFFT+RL ratio+fit (free)";
 const char* const kPassRfUpdate = "C op rows: IFFT+RL update (weighted)";
 const char* const kPassRfCrop = "RLF out: crop";
 const char* const kPassRfNorm = "E RLF minmax+normalize";
+
+}  // namespace
+
+namespace fdr {
 
 // the first free-boundary call of a plan: u, wgt and dw (M x N floats each) and the double partials
 int ensure_rlfree_workspace(fdr_plan* p, const char* fn) {
@@ -64,13 +69,15 @@ int rlfree_check(const fdr_plan* p, const char* fn, const float* img, int rows, 
 }
 
 // one iteration on the whole plan: c = window(fullblur(y)), r = dw / c into the plan's raw plane, out = max(y wgt fullblur^T(pad(r)), 0);
-// y and out are dense M x N planes, and `out` may be y itself
-int rlfree_step(fdr_plan* p, const float* y, float* out, int rows, int cols, hipStream_t s) {
+// y and out are dense M x N planes, and `out` may be y itself.  With `fit` (weights and d dense, row stride cols) the ratio pass forms
+// dw = w d+ itself, the product of the setup pass, and leaves the fit partials of c beside the same r.
+int rlfree_step(fdr_plan* p, const float* y, float* out, int rows, int cols, hipStream_t s, const RlFit* fit, const float* d_dense) {
     const int M = p->M, N = p->N;
     float* r = p->slots[0].raw;
     int rc = op_rows_fwd(p, y, M, N, N, s);                                                         // c = fullblur(y) ...
     if (rc == FDR_OK) rc = op_cols(p, false, s);
-    if (rc == FDR_OK) rc = op_rows_inv(p, ROW_OUT_RL_RATIO, kPassRfRatio, p->rf_dw, cols, r, cols, rows, cols, s);  // ... r = dw / c
+    if (rc == FDR_OK && fit) rc = op_rows_inv(p, ROW_OUT_RL_RATIO_STAT, kPassRfRatioFit, d_dense, cols, r, cols, rows, cols, s, fit);
+    else if (rc == FDR_OK) rc = op_rows_inv(p, ROW_OUT_RL_RATIO, kPassRfRatio, p->rf_dw, cols, r, cols, rows, cols, s);  // ... r = dw / c
     if (rc == FDR_OK) rc = op_rows_fwd(p, r, rows, cols, cols, s);                                  // g = fullblur^T(pad(r)) ...
     if (rc == FDR_OK) rc = op_cols(p, true, s);
     if (rc != FDR_OK) return rc;
@@ -85,22 +92,47 @@ int rlfree_step(fdr_plan* p, const float* y, float* out, int rows, int cols, hip
 
 // u and wgt are dense M x N planes of the workspace, dw and r (the plan's raw plane) dense rows x cols.  W = pad(m) lies in u's
 // plane until alpha has been transformed out of it; d_w may be that plane itself (the host form stages the weights there).
-// Accelerated (rl_accel_loop), the estimate alternates between u's plane and one of the acceleration workspace.
-int rlfree_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, int cols, int stride, const float* d_w, int wstride,
-                    float* d_out, int out_stride, const fdr_rlfree_params& prm, bool accel, float* d_alphas, hipStream_t s) {
+// begin: the setup, the coverage and the start; the dense W (rows x cols) is copied to keep_w first when that is not null, and
+// *sums is where the device holds (sum dw, sum W).
+int rlfree_begin(fdr_plan* p, const float* d_img, int rows, int cols, int stride, const float* d_w, int wstride, float sigma, float* keep_w,
+                 const double** sums, hipStream_t s) {
     const int M = p->M, N = p->N;
     float *u = p->rf_u, *wgt = p->rf_wgt, *dw = p->rf_dw;
     const int n_part = rlfree_partials(rows, cols);
     {
         ScopedPass t(p, s, kPassRfSetup);
         FDR_HIP(launch_rlfree_setup(d_img, stride, d_w, wstride, rows, cols, dw, u, p->rf_part, s));
+        if (keep_w) FDR_HIP(hipMemcpyAsync(keep_w, u, (size_t)rows * cols * sizeof(float), hipMemcpyDeviceToDevice, s));
     }
-    int rc = blur_window_dev(p, u, rows, cols, cols, wgt, N, M, N, 1, s);  // alpha = fullblur^T(W) over the whole plan
+    const int rc = blur_window_dev(p, u, rows, cols, cols, wgt, N, M, N, 1, s);  // alpha = fullblur^T(W) over the whole plan
     if (rc != FDR_OK) return rc;
-    {
-        ScopedPass t(p, s, kPassRfStart);
-        FDR_HIP(launch_rlfree_start(wgt, u, (size_t)M * N, prm.sigma, p->rf_part + 2 * (size_t)n_part, s));
+    ScopedPass t(p, s, kPassRfStart);
+    FDR_HIP(launch_rlfree_start(wgt, u, (size_t)M * N, sigma, p->rf_part + 2 * (size_t)n_part, s));
+    if (sums) *sums = p->rf_part + 2 * (size_t)n_part;
+    return FDR_OK;
+}
+
+// finish: the output window of the dense M x N estimate u, cropped or normalised, into d_out
+int rlfree_finish(fdr_plan* p, const char* fn, const float* u, float* d_out, int out_stride, const fdr_rlfree_params& prm, hipStream_t s) {
+    if (prm.norm_area == FDR_NORM_NONE) {
+        ScopedPass t(p, s, kPassRfCrop);
+        FDR_HIP(launch_rlfree_crop(u, p->N, d_out, prm.out_rows, prm.out_cols, out_stride, s));
+        return FDR_OK;
     }
+    return normalize_window(p, fn, kPassRfNorm, u, p->N, prm.out_rows, prm.out_cols, prm.norm_area, d_out, out_stride, s);
+}
+
+}  // namespace fdr
+
+namespace {
+
+// Accelerated (rl_accel_loop), the estimate alternates between u's plane and one of the acceleration workspace.
+int rlfree_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, int cols, int stride, const float* d_w, int wstride,
+                    float* d_out, int out_stride, const fdr_rlfree_params& prm, bool accel, float* d_alphas, hipStream_t s) {
+    const int M = p->M, N = p->N;
+    float* u = p->rf_u;
+    int rc = rlfree_begin(p, d_img, rows, cols, stride, d_w, wstride, prm.sigma, nullptr, nullptr, s);
+    if (rc != FDR_OK) return rc;
     if (accel) {
         float* const U[2] = {u, p->ra_u};
         const int us[2] = {N, N};
@@ -110,12 +142,7 @@ int rlfree_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, i
         for (int it = 0; it < prm.iterations && rc == FDR_OK; ++it) rc = rlfree_step(p, u, u, rows, cols, s);
     }
     if (rc != FDR_OK) return rc;
-    if (prm.norm_area == FDR_NORM_NONE) {
-        ScopedPass t(p, s, kPassRfCrop);
-        FDR_HIP(launch_rlfree_crop(u, N, d_out, prm.out_rows, prm.out_cols, out_stride, s));
-        return FDR_OK;
-    }
-    return normalize_window(p, fn, kPassRfNorm, u, N, prm.out_rows, prm.out_cols, prm.norm_area, d_out, out_stride, s);
+    return rlfree_finish(p, fn, u, d_out, out_stride, prm, s);
 }
 
 // the checks, the device, the workspaces and the driver of the four entry points; the accelerated ones also refuse alphas that

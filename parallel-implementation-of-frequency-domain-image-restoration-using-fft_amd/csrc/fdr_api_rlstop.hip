@@ -1,0 +1,273 @@
+// fdr_api_rlstop.hip -- Richardson-Lucy that stops from the data (fdr_richardson_lucy_auto_f32*; kernels: the ratio kind
+// ROW_OUT_RL_RATIO_STAT of fdr_panel_rows.hip and the fold of fdr_rlstop.hip): the workspace, the checks, the driver around the
+// unchanged steps of the four forms (fdr_api_operator.hip, fdr_api_rlfree.hip, fdr_api_rlaccel.hip) and the two entry points.
+//
+// The final count is not known in advance, so nothing is routed by it: the estimate stays in its own plane(s) for every step, the
+// accelerated forms start at parity 0, and what the stop leaves is brought to the output (or to the normalise pass) afterwards.
+// The values of u_k do not depend on the plane they lie in, so the output has the bits of the call with that count.
+#include "fdr_host.hpp"
+
+#include <cmath>
+#include <cstdint>
+
+using namespace fdr;
+
+namespace {
+
+// names are static strings compared by pointer in PassTimer::pass_id
+const char* const kPassRsInit = "RL init: u = max(d, 0)";
+const char* const kPassRsFold = "RLS fold: res, kl";
+const char* const kPassRsNoise = "RLS noise: sum |d * n|";
+const char* const kPassRsMove = "RLS out: move";
+const char* const kPassRsNorm = "E RL minmax+normalize";
+
+constexpr int kRsTraceSteps = 1024;  // steps of the internal trace the first call makes room for
+
+// the checked arguments with their defaults
+struct AutoArgs {
+    int n, rule, every, norm_area;
+    bool free_form, accel, estimate;
+    double sigma, gain, tau;
+    fdr_rlfree_params fp;  // free form
+};
+
+bool finite_nonneg(float v) { return std::isfinite(v) && v >= 0.f; }
+
+bool bytes_overlap(const void* a, size_t a_bytes, const float* w, int ws, int rows, int cols) {
+    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + a_bytes;
+    const uintptr_t b0 = (uintptr_t)w, b1 = b0 + ((size_t)(rows - 1) * ws + cols) * sizeof(float);
+    return a0 < b1 && b0 < a1;
+}
+
+// everything an auto call refuses, before any device work: what the underlying form refuses, then the rule's own arguments
+int auto_check(const fdr_plan* p, const char* fn, const float* img, int rows, int cols, int stride, const float* weights, int wstride,
+               const float* out, int out_stride, const fdr_rl_auto_params* prm, const double* d_trace, AutoArgs* a) {
+    a->n = prm->iterations; a->rule = prm->rule; a->norm_area = prm->norm_area;
+    a->free_form = prm->free_boundary != 0; a->accel = prm->accelerate != 0;
+    a->fp = fdr_rlfree_params{prm->iterations, prm->cov_sigma, prm->norm_area, prm->out_rows, prm->out_cols};
+    int rc;
+    if (a->free_form) {
+        rc = rlfree_check(p, fn, img, rows, cols, stride, weights, wstride, out, out_stride, &a->fp);
+    } else {
+        rc = rl_check(p, fn, img, rows, cols, stride, out, out_stride, prm->iterations, prm->norm_area);
+        if (rc == FDR_OK && weights) return fail(FDR_ERR_ARG, std::string(fn) + ": the plain form takes no weights");
+        if (rc == FDR_OK && !((prm->out_rows == 0 || prm->out_rows == rows) && (prm->out_cols == 0 || prm->out_cols == cols)))
+            return fail(FDR_ERR_ARG, std::string(fn) + ": the plain form's output window is the input's (out_rows, out_cols = 0 or rows, cols)");
+        a->fp.out_rows = rows; a->fp.out_cols = cols;
+    }
+    if (rc != FDR_OK) return rc;
+    if (prm->rule != FDR_RL_STOP_NONE && prm->rule != FDR_RL_STOP_RESIDUAL && prm->rule != FDR_RL_STOP_KL)
+        return fail(FDR_ERR_ARG, std::string(fn) + ": unknown rule");
+    if (prm->rule == FDR_RL_STOP_KL && !(std::isfinite(prm->gain) && prm->gain > 0.f))
+        return fail(FDR_ERR_ARG, std::string(fn) + ": the KL rule needs a finite gain > 0");
+    if (!finite_nonneg(prm->sigma) || !finite_nonneg(prm->tau)) return fail(FDR_ERR_ARG, std::string(fn) + ": sigma and tau must be finite and >= 0");
+    if (prm->check_every < 0) return fail(FDR_ERR_ARG, std::string(fn) + ": check_every < 0");
+    a->sigma = prm->sigma; a->gain = prm->gain;
+    a->tau = prm->tau != 0.f ? (double)prm->tau : 1.0;
+    a->every = prm->check_every ? prm->check_every : 1;
+    a->estimate = prm->rule == FDR_RL_STOP_RESIDUAL && prm->sigma == 0.f;
+    if (a->estimate) {
+        rc = noise_window_check(fn, rows, cols, stride);
+        if (rc != FDR_OK) return rc;
+    }
+    if (d_trace && a->n > 0) {
+        const size_t bytes = (size_t)a->n * 2 * sizeof(double);
+        if (bytes_overlap(d_trace, bytes, img, stride, rows, cols)) return fail(FDR_ERR_ARG, std::string(fn) + ": the trace overlaps the input");
+        if (bytes_overlap(d_trace, bytes, out, out_stride, a->fp.out_rows, a->fp.out_cols))
+            return fail(FDR_ERR_ARG, std::string(fn) + ": the trace overlaps the output");
+        if (weights && bytes_overlap(d_trace, bytes, weights, wstride, rows, cols))
+            return fail(FDR_ERR_ARG, std::string(fn) + ": the trace overlaps the weights");
+    }
+    return FDR_OK;
+}
+
+// the partials (first call), the two planes of the weighted free form (its first call) and room for `steps` steps in the internal trace
+int ensure_rlstop_workspace(fdr_plan* p, const char* fn, bool free_form, int steps) {
+    if (!p->rs_block) {
+        const int n_part = rows4_minmax_partials(p->logN, p->M, 1, 1);
+        if (n_part <= 0) return fail(FDR_ERR_STATE, std::string(fn) + ": no inverse row pass for this plan");
+        char* b = nullptr;
+        if (hipMalloc((void**)&b, ((size_t)n_part * 2 + kRegMaxPartials + 1) * sizeof(double)) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(FDR_ERR_ALLOC, std::string(fn) + ": hipMalloc of the workspace failed");
+        }
+        p->rs_block = b;
+        p->rs_part = reinterpret_cast<double*>(b);
+        p->rs_noise = p->rs_part + (size_t)n_part * 2;
+        p->rs_n_part = n_part;
+    }
+    const int want = steps > kRsTraceSteps ? steps : kRsTraceSteps;
+    if (want > p->rs_trace_cap) {  // a grown trace: only calls that wait for their own end use it, so nothing in flight reads the old one
+        double* t = nullptr;
+        if (hipMalloc((void**)&t, (size_t)want * 2 * sizeof(double)) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(FDR_ERR_ALLOC, std::string(fn) + ": hipMalloc of the trace failed");
+        }
+        (void)hipFree(p->rs_trace);
+        p->rs_trace = t;
+        p->rs_trace_cap = want;
+    }
+    if (free_form && !p->rs_planes) {
+        float* t = nullptr;
+        if (hipMalloc((void**)&t, 2 * (size_t)p->M * p->N * sizeof(float)) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(FDR_ERR_ALLOC, std::string(fn) + ": hipMalloc of the weight planes failed");
+        }
+        p->rs_planes = t;
+    }
+    return FDR_OK;
+}
+
+// The whole call on `s`.  tr: where the device writes the trace (the caller's, the internal one, or null for none).  With a rule
+// the stream is waited for after every a.every steps and those entries are read back.
+int auto_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, int cols, int stride, const float* d_w, int wstride, float* d_out,
+                  int out_stride, const AutoArgs& a, double* tr, fdr_rl_auto_result* res, hipStream_t s) {
+    const int M = p->M, N = p->N, n = a.n;
+    *res = fdr_rl_auto_result{n, 0, a.sigma, 0.0, 0.0};
+    double sigma = a.sigma;
+    int rc = FDR_OK;
+    if (a.estimate) {
+        ScopedPass t(p, s, kPassRsNoise);
+        rc = noise_sigma_dev(d_img, rows, cols, stride, p->rs_noise, &sigma, s);
+        if (rc != FDR_OK) return rc;
+    }
+    // the start of the form; cur = the plane of u_k (row stride cs), U / us = the two planes of the accelerated estimate
+    // free-boundary form with weights: the ratio pass reads d and W (dense copies) and forms dw itself.  Without weights W = 1 and
+    // dw = d+: the pass reads the stored dw as its datum and nothing else (max(dw, 0) = dw, the same bits).
+    const bool weighted = a.free_form && d_w != nullptr;
+    float* W = weighted ? p->rs_planes : nullptr;
+    const float* D = weighted ? p->rs_planes + (size_t)M * N : p->rf_dw;
+    double S = (double)rows * (double)cols;
+    float* cur;
+    if (a.free_form) {
+        const double* sums = nullptr;
+        if (weighted)
+            FDR_HIP(hipMemcpy2DAsync(p->rs_planes + (size_t)M * N, (size_t)cols * sizeof(float), d_img, (size_t)stride * sizeof(float),
+                                     (size_t)cols * sizeof(float), (size_t)rows, hipMemcpyDeviceToDevice, s));
+        rc = rlfree_begin(p, d_img, rows, cols, stride, d_w, wstride, a.fp.sigma, W, &sums, s);
+        if (rc != FDR_OK) return rc;
+        if (a.rule != FDR_RL_STOP_NONE) {
+            FDR_HIP(hipMemcpyAsync(&S, sums + 1, sizeof(double), hipMemcpyDeviceToHost, s));
+            FDR_HIP(hipStreamSynchronize(s));
+        }
+        cur = p->rf_u;
+    } else {
+        ScopedPass t(p, s, kPassRsInit);
+        FDR_HIP(launch_rl_init(d_img, rows, cols, stride, d_out, out_stride, s));
+        cur = d_out;
+    }
+    float* const U[2] = {cur, a.accel ? p->ra_u : cur};
+    const int us[2] = {a.free_form ? N : out_stride, a.free_form ? N : (a.accel ? cols : out_stride)};
+    const int R = a.free_form ? M : rows, C = a.free_form ? N : cols;  // the window the estimate lives on
+
+    const RlFit fit{W, p->rs_part};
+    int k = 0;  // the step about to run
+    auto step = [&](const float* y, int ys, float* out, int os) {
+        int rc2 = a.free_form ? rlfree_step(p, y, out, rows, cols, s, &fit, D) : rl_step(p, d_img, stride, y, ys, out, os, rows, cols, s, &fit);
+        if (rc2 == FDR_OK && tr) {
+            ScopedPass t(p, s, kPassRsFold);
+            FDR_HIP(launch_rlstop_fold(p->rs_part, p->rs_n_part, tr + 2 * (size_t)k, s));
+        }
+        ++k;
+        return rc2;
+    };
+    const double target = a.rule == FDR_RL_STOP_RESIDUAL ? a.tau * sigma * sigma * S : (a.rule == FDR_RL_STOP_KL ? a.tau : 0.0);
+    std::vector<double> seen;
+    int done = 0, stopped = 0;
+    double statistic = 0.0;
+    while (done < n && !stopped) {
+        const int k1 = a.rule == FDR_RL_STOP_NONE ? n : (n - done < a.every ? n : done + a.every);
+        if (a.accel) {
+            rc = rl_accel_steps(p, done, k1, n, R, C, U, us, 0, nullptr, 0, nullptr, s, step, &cur);
+        } else {
+            for (int i = done; i < k1 && rc == FDR_OK; ++i) rc = step(cur, us[0], cur, us[0]);
+        }
+        if (rc != FDR_OK) return rc;
+        if (a.rule != FDR_RL_STOP_NONE) {
+            seen.resize((size_t)(k1 - done) * 2);
+            FDR_HIP(hipMemcpyAsync(seen.data(), tr + 2 * (size_t)done, seen.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+            FDR_HIP(hipStreamSynchronize(s));
+            for (int i = 0; i < k1 - done && !stopped; ++i) {
+                statistic = a.rule == FDR_RL_STOP_RESIDUAL ? seen[2 * i] : 2.0 * a.gain * seen[2 * i + 1] / S;
+                stopped = statistic <= target;
+            }
+        }
+        done = k1;
+    }
+    *res = fdr_rl_auto_result{done, stopped, sigma, target, statistic};
+
+    // u_done lies in `cur`: to the output
+    if (a.free_form) return rlfree_finish(p, fn, cur, d_out, out_stride, a.fp, s);
+    const int cs = cur == d_out ? out_stride : cols;
+    if (a.norm_area == FDR_NORM_NONE) {
+        if (cur == d_out) return FDR_OK;
+        ScopedPass t(p, s, kPassRsMove);
+        FDR_HIP(hipMemcpy2DAsync(d_out, (size_t)out_stride * sizeof(float), cur, (size_t)cs * sizeof(float), (size_t)cols * sizeof(float),
+                                 (size_t)rows, hipMemcpyDeviceToDevice, s));
+        return FDR_OK;
+    }
+    if (cur == d_out) {  // the normalise pass reads one plane and writes another: through the raw plane, free once the last step is done
+        ScopedPass t(p, s, kPassRsMove);
+        float* raw = p->slots[0].raw;
+        FDR_HIP(hipMemcpy2DAsync(raw, (size_t)cols * sizeof(float), d_out, (size_t)out_stride * sizeof(float), (size_t)cols * sizeof(float),
+                                 (size_t)rows, hipMemcpyDeviceToDevice, s));
+        cur = raw;
+    }
+    return normalize_window(p, fn, kPassRsNorm, cur, cols, rows, cols, a.norm_area, d_out, out_stride, s);
+}
+
+// the workspaces of the form and of the trace
+int auto_prepare(fdr_plan* p, const char* fn, const AutoArgs& a, bool weighted, bool internal_trace) {
+    int rc = FDR_OK;
+    if (a.free_form) rc = ensure_rlfree_workspace(p, fn);
+    if (rc == FDR_OK && a.accel) rc = ensure_rlaccel_workspace(p, fn);
+    if (rc == FDR_OK) rc = ensure_rlstop_workspace(p, fn, a.free_form && weighted, internal_trace ? a.n : 0);
+    return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fdr_richardson_lucy_auto_f32_dev(fdr_plan* p, const float* d_img, int rows, int cols, int stride, const float* d_weights, int wstride,
+                                     float* d_out, int out_stride, const fdr_rl_auto_params* params, fdr_rl_auto_result* result,
+                                     double* d_trace, void* stream) {
+    const char* fn = "fdr_richardson_lucy_auto_f32_dev";
+    if (!p || !d_img || !d_out || !params || !result) return null_arg(fn);
+    AutoArgs a{};
+    int rc = auto_check(p, fn, d_img, rows, cols, stride, d_weights, wstride, d_out, out_stride, params, d_trace, &a);
+    if (rc != FDR_OK) return rc;
+    FDR_HIP(hipSetDevice(p->device));
+    const bool internal = !d_trace && a.rule != FDR_RL_STOP_NONE;
+    rc = auto_prepare(p, fn, a, d_weights != nullptr, internal);
+    if (rc != FDR_OK) return rc;
+    return auto_dev_impl(p, fn, d_img, rows, cols, stride, d_weights, wstride, d_out, out_stride, a, d_trace ? d_trace : (internal ? p->rs_trace : nullptr),
+                         result, (hipStream_t)stream);
+}
+
+int fdr_richardson_lucy_auto_f32(fdr_plan* p, const float* img_host, int rows, int cols, int stride, const float* weights_host, int wstride,
+                                 float* out_host, int out_stride, const fdr_rl_auto_params* params, fdr_rl_auto_result* result,
+                                 double* trace_host) {
+    const char* fn = "fdr_richardson_lucy_auto_f32";
+    if (!p || !img_host || !out_host || !params || !result) return null_arg(fn);
+    AutoArgs a{};
+    int rc = auto_check(p, fn, img_host, rows, cols, stride, weights_host, wstride, out_host, out_stride, params, nullptr, &a);
+    if (rc != FDR_OK) return rc;
+    FDR_HIP(hipSetDevice(p->device));
+    const bool internal = trace_host || a.rule != FDR_RL_STOP_NONE;
+    rc = auto_prepare(p, fn, a, weights_host != nullptr, internal);
+    if (rc != FDR_OK) return rc;
+    if (a.free_form && weights_host)  // staged dense into u's plane, where the setup pass leaves W anyway
+        FDR_HIP(hipMemcpy2D(p->rf_u, (size_t)cols * sizeof(float), weights_host, (size_t)wstride * sizeof(float), (size_t)cols * sizeof(float),
+                            (size_t)rows, hipMemcpyHostToDevice));
+    rc = host_image_call(p, fn, img_host, rows, cols, stride, out_host, a.fp.out_rows, a.fp.out_cols, out_stride,
+                         [&](const float* d_in, float* d_out) {
+                             return auto_dev_impl(p, fn, d_in, rows, cols, cols, a.free_form && weights_host ? p->rf_u : nullptr, cols, d_out,
+                                                  a.fp.out_cols, a, internal ? p->rs_trace : nullptr, result, nullptr);
+                         });
+    if (rc == FDR_OK && trace_host && result->iterations_done > 0)
+        FDR_HIP(hipMemcpy(trace_host, p->rs_trace, (size_t)result->iterations_done * 2 * sizeof(double), hipMemcpyDeviceToHost));
+    return rc;
+}
+
+}  // extern "C"

@@ -154,6 +154,18 @@ struct fdr_plan {
     float *ra_y = nullptr, *ra_u = nullptr, *ra_g = nullptr;
     double* ra_part = nullptr;
     float* ra_alpha = nullptr;
+    // stopping Richardson-Lucy from the data (fdr_richardson_lucy_auto_f32*): made by the first such call, kept until fdr_plan_destroy
+    // -- rs_block holds the (res, kl) partials of the ratio pass (one double2 per workgroup of the plan's inverse row grid) and the
+    // partials of the noise estimate; rs_trace the internal trace (2 rs_trace_cap doubles; it grows only when a call with a rule and
+    // without the caller's trace asks for more steps); rs_planes, free-boundary form with weights only, two M x N planes: the dense weights W
+    // and the dense copy of d that the ratio pass reads beside them
+    void* rs_block = nullptr;
+    double* rs_part = nullptr;
+    double* rs_noise = nullptr;  // kRegMaxPartials + 1 doubles
+    int rs_n_part = 0;
+    double* rs_trace = nullptr;
+    int rs_trace_cap = 0;
+    float* rs_planes = nullptr;
     // choosing the regularisation weight (fdr_reg_curve_f32*, fdr_choose_reg_f32*): made by the first such call, kept until
     // fdr_plan_destroy -- one allocation holding the power plane (ws_elems floats in the layout of `filt`, one float per bin, then the
     // two extra floats of the packed column), the partials of the sweep and of the noise sum, and the candidate and result arrays
@@ -301,9 +313,12 @@ int ensure_lap_table(fdr_plan* p);
 int op_rows_fwd(fdr_plan* p, const float* x, int rows, int cols, int stride, hipStream_t s);
 // pass B', unchanged, with `table` as its filter; timed as `name`
 int op_cols_table(fdr_plan* p, const float2* table, const char* name, hipStream_t s);
+// what ROW_OUT_RL_RATIO_STAT takes beside the datum: the weights (dense, the row stride of the datum; null = 1) and the room for the
+// (res, kl) partials, one double2 per workgroup of the pass
+struct RlFit { const float* weights; double* part; };
 // pass C with an operator kind: the window rows x cols of the inverse transform through the kind's epilogue into `out`
 int op_rows_inv(fdr_plan* p, RowOut kind, const char* name, const float* src, int src_stride, float* out, int out_stride, int rows, int cols,
-                hipStream_t s);
+                hipStream_t s, const RlFit* fit = nullptr);
 // pass B' on H / (M N), or with `adjoint` on conj(H) / (M N)
 int op_cols(fdr_plan* p, bool adjoint, hipStream_t s);
 // blur (adjoint != 0: blur^T) of the window rows x cols of d_img; the window out_rows x out_cols of the result into d_out
@@ -313,6 +328,25 @@ int blur_window_dev(fdr_plan* p, const float* d_img, int rows, int cols, int str
 // counting the zeros outside it too
 int normalize_window(fdr_plan* p, const char* fn, const char* name, const float* fin, int fs, int rows, int cols, int norm_area, float* d_out,
                      int out_stride, hipStream_t s);
+// ---- Richardson-Lucy, both forms (fdr_api_operator.hip, fdr_api_rlfree.hip): the checks and the step, shared with the calls that
+// stop from the data (fdr_api_rlstop.hip).  `fit`: the ratio pass also leaves the fit partials of c (same r, same update).
+int rl_check(const fdr_plan* p, const char* fn, const float* img, int rows, int cols, int stride, const float* out, int out_stride,
+             int iterations, int norm_area);
+int rl_step(fdr_plan* p, const float* d_img, int stride, const float* y, int ys, float* out, int os, int rows, int cols, hipStream_t s,
+            const RlFit* fit = nullptr);
+int ensure_rlfree_workspace(fdr_plan* p, const char* fn);
+bool spans_overlap(const float* a, int a_stride, int a_rows, int a_cols, const float* b, int b_stride, int b_rows, int b_cols);
+int rlfree_check(const fdr_plan* p, const char* fn, const float* img, int rows, int cols, int stride, const float* weights, int wstride,
+                 const float* out, int out_stride, const fdr_rlfree_params* prm);
+int rlfree_step(fdr_plan* p, const float* y, float* out, int rows, int cols, hipStream_t s, const RlFit* fit = nullptr,
+                const float* d_dense = nullptr);
+int rlfree_begin(fdr_plan* p, const float* d_img, int rows, int cols, int stride, const float* d_w, int wstride, float sigma, float* keep_w,
+                 const double** sums, hipStream_t s);
+int rlfree_finish(fdr_plan* p, const char* fn, const float* u, float* d_out, int out_stride, const fdr_rlfree_params& prm, hipStream_t s);
+// ---- the noise estimate (fdr_api_reg.hip): the Immerkaer sum of a device window through `part` (reg_noise_partials + 1 doubles), read
+// back: synchronous; and the refusal of a window it cannot work on
+int noise_sigma_dev(const float* d_img, int rows, int cols, int stride, double* part, double* sigma, hipStream_t s);
+int noise_window_check(const char* fn, int rows, int cols, int stride);
 // ---- accelerated Richardson-Lucy (fdr_api_rlaccel.hip), shared by the plain and the free-boundary form ----
 // the workspace of the accelerated calls; FDR_ERR_ALLOC, sticky HIP error cleared and plan intact, if it cannot be had
 int ensure_rlaccel_workspace(fdr_plan* p, const char* fn);
@@ -325,6 +359,10 @@ using RlStep = std::function<int(const float* y, int ys, float* out, int os)>;
 // alpha_(n-1) go to d_alphas when it is not null.  For n <= 2 this is n steps and nothing else.
 int rl_accel_loop(fdr_plan* p, int n, int rows, int cols, float* const U[2], const int us[2], int first, float* fin, int fs, float* d_alphas,
                   hipStream_t s, const RlStep& step, float** result);
+// iterations k0 .. k1 - 1 of a run of at most n (what rl_accel_loop is made of): u_k0 lies in U[(first + k0) & 1] and the state of the
+// earlier iterations (g, alpha) in the workspace; *result, when not null, receives the plane of u_k1 (untouched for k0 = k1)
+int rl_accel_steps(fdr_plan* p, int k0, int k1, int n, int rows, int cols, float* const U[2], const int us[2], int first, float* fin, int fs,
+                   float* d_alphas, hipStream_t s, const RlStep& step, float** result);
 // pairs of one fdr_reg_curve_f32* call (fdr_api_reg.hip): what the candidate and result arrays of the plan hold
 constexpr int kRegMaxCurve = 4096;
 static_assert(kRegMaxCurve % kRegCandidates == 0, "the last sweep reads kRegCandidates pairs");

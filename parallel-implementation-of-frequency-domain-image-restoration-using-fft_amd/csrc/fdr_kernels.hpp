@@ -23,7 +23,12 @@ enum RowOut {
     // free-boundary Richardson-Lucy (fdr_rlfree.hip): max(u wgt g, 0) to `out`; u from src_real as ROW_OUT_RL_UPDATE, wgt from
     // src_real2 (same row stride)
     ROW_OUT_RL_UPDATE_W = 7,
-    ROW_OUT_LAST = ROW_OUT_RL_UPDATE_W
+    // the ratio that also measures the fit (fdr_rlstop.hip): d from src_real, the pixel's weight w from src_real2 (same row stride;
+    // null: w = 1); r = c > kRlTau ? (w max(d, 0)) / c : 0 to `out` -- the bits of ROW_OUT_RL_RATIO on d (w = 1) or on dw = w max(d, 0)
+    // -- and the workgroup's sums over the window of w (d+ - c)^2 and w (c - d+ + d+ ln(d+ / c)) as ONE pair of doubles at
+    // mm_part (read as double2*), index blockIdx.x; rows4_minmax_partials(logl, M, 1, 1) of them
+    ROW_OUT_RL_RATIO_STAT = 8,
+    ROW_OUT_LAST = ROW_OUT_RL_RATIO_STAT
 };
 // the guard of the Richardson-Lucy ratio (FDR_RL_TAU of fdr.h): a blurred estimate at or below it gives r = 0
 constexpr float kRlTau = 1e-7f;
@@ -80,10 +85,10 @@ struct RowArgs {
     float2* dst_c;    // ROW_OUT_COMPLEX: M x L
     union {
         float* dst_real;         // ROW_OUT_REAL_MINMAX: M x L real plane
-        const float* src_real2;  // ROW_OUT_RL_UPDATE_W: the second real source (row stride src_stride); shares the slot of dst_real,
+        const float* src_real2;  // ROW_OUT_RL_UPDATE_W, ROW_OUT_RL_RATIO_STAT: the second real source (row stride src_stride); shares the slot of dst_real,
                                  // which that kind does not use, so the argument block of every other kernel keeps its layout
     };
-    float2* mm_part;  // one (min, max) partial per workgroup
+    float2* mm_part;  // one (min, max) partial per workgroup (ROW_OUT_RL_RATIO_STAT: one double2 (res, kl) per workgroup)
     int mm_rows, mm_cols;
     float* out;       // ROW_OUT_NORMALIZED: out_rows x out_cols result, row stride out_stride; mm_part holds n_part partials
     int out_rows, out_cols, out_stride, n_part;
@@ -185,6 +190,9 @@ hipError_t launch_rlaccel_direction(const float* u1, int u1s, const float* y, in
 hipError_t launch_rlaccel_alpha(const double* part, int n, float amax, float* alpha, float* record, hipStream_t s);
 hipError_t launch_rlaccel_extrapolate(const float* u1, int u1s, const float* u0, int u0s, const float* alpha, float* y, int ys, int rows,
                                       int cols, hipStream_t s);
+// (fdr_rlstop.hip) the fit trace of Richardson-Lucy: one workgroup folds the n (res, kl) pairs ROW_OUT_RL_RATIO_STAT left in `part`
+// in index order (thread t adds t, t + 256, ... in order, then a fixed tree) into out[0] = res, out[1] = kl
+hipError_t launch_rlstop_fold(const double* part, int n, double* out, hipStream_t s);
 // (fdr_tv.hip) total-variation deconvolution.  table: T = (1 / (M N)) / (mu |H|^2 + rho L) from op_h = H / (M N) (the operator table
 // of launch_cols_panel_operator) and the Laplacian table `lap` of launch_cols_panel_cls, in the layout pass B' reads its filter
 // from.  init: x = pad(d) over the M x N plan (row stride N), wx = wy = 0.  spatial: one ADMM half-step on full M x N planes --

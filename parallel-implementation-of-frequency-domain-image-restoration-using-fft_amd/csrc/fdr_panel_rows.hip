@@ -73,6 +73,7 @@ constexpr bool row_out_normalizes(RowOut o) { return o == ROW_OUT_NORMALIZED; } 
 constexpr bool row_out_operator(RowOut o) { return o >= ROW_OUT_BLUR; }          // half spectrum, >= 32 points, one image, cropped
 constexpr bool row_out_reads_src(RowOut o) { return row_out_operator(o) && o != ROW_OUT_BLUR; }               // src_real
 constexpr bool row_out_reads_src2(RowOut o) { return o == ROW_OUT_RL_UPDATE_W; }                              // src_real2 as well
+constexpr bool row_out_fit_sums(RowOut o) { return o == ROW_OUT_RL_RATIO_STAT; }  // src_real2 when not null, (res, kl) partials
 
 // ---------------------------------------------------------------------------------------------
 // pass A
@@ -987,9 +988,56 @@ __device__ __forceinline__ float rows4_rl_value(const float v, const float* src,
     else if constexpr (OUT == ROW_OUT_RL_UPDATE_W) return fmaxf(*src * *src2 * v, 0.f);
     else static_assert(OUT != OUT, "an operator kind without its value");
 }
-// rows4_inv_epilogue for those kinds: cropped on store as ROW_OUT_NORMALIZED, no min/max
+// ROW_OUT_RL_RATIO_STAT: the ratio of ROW_OUT_RL_RATIO on d = *src (src2 null) or, free boundary, on dw = w max(d, 0), w = *src2 (the
+// float product of rlfree_setup_kernel, so the same bits as the ratio on the stored dw), and the pixel's terms of the two fit
+// sums, added in double: res += w (d+ - c)^2, kl += w (c - d+ + (d+ > 0 && c > kRlTau ? d+ ln(d+ / c) : 0)).
+// The logarithm without double transcendentals: q = d+ / c rounded to float leaves the residual d+ - q c exactly in one FMA, so
+// ln(d+ / c) = ln(q) + ln(1 + delta), delta = (d+ - q c) / (q c) <= 2^-24, ln(1 + delta) = delta to 2^-48; logf (not the
+// hardware's log2: it keeps its RELATIVE accuracy near q = 1, where the three terms cancel to d+ e^2 / 2, e = d+ / c - 1)
+// gives ln(q) to an ulp, i.e. the term to about 1.2e-7 / |e| -- below what the float32 c itself leaves of it (2e-6 / |e|).
+__device__ __forceinline__ float rows4_rl_ratio_stat(const float v, const float* src, const float* src2, double& res, double& kl) {
+    const float dp = fmaxf(*src, 0.f);
+    const bool ok = v > kRlTau;
+    float num = dp, q = ok ? dp / v : 0.f, r = q;
+    double w = 1.0;
+    if (src2) {
+        const float wf = *src2;
+        num = wf * dp;
+        r = ok ? num / v : 0.f;
+        w = (double)wf;
+    }
+    const double c = (double)v, d = (double)dp, e = d - c;
+    double t = c - d;
+    if (dp > 0.f && ok) t += d * ((double)logf(q) + (double)__fdividef(fmaf(-q, v, dp), dp));
+    res += w * (e * e);
+    kl += w * t;
+    return r;
+}
+// The workgroup's two sums (every wave is whole): an xor tree within each wave -- both partners form the same sum, so every lane
+// ends with the same bits -- then thread 0 adds the waves in index order and writes the pair to part[index].
+__device__ __forceinline__ void block_sum2_store(double s0, double s1, double2* __restrict__ part, int index) {
+    __shared__ double2 sum_red[16];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        s0 += __shfl_xor(s0, off);
+        s1 += __shfl_xor(s1, off);
+    }
+    const int wave = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
+    if ((threadIdx.x & 63) == 0) sum_red[wave] = make_double2(s0, s1);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < nw; ++w) {
+            s0 += sum_red[w].x;
+            s1 += sum_red[w].y;
+        }
+        part[index] = make_double2(s0, s1);
+    }
+}
+// rows4_inv_epilogue for those kinds: cropped on store as ROW_OUT_NORMALIZED, no min/max; res and kl: the thread's fit sums
+// (ROW_OUT_RL_RATIO_STAT only), rows in order and the columns of a row in order
 template <class Core, RowOut OUT, int V>
-__device__ __forceinline__ void rows4_rl_epilogue(const RowArgs& a, const int r0, const int tq, const float2 (&z)[2][V]) {
+__device__ __forceinline__ void rows4_rl_epilogue(const RowArgs& a, const int r0, const int tq, const float2 (&z)[2][V], double& res,
+                                                  double& kl) {
     constexpr int T = Core::T;
 #pragma unroll
     for (int b = 0; b < 4; ++b) {
@@ -997,7 +1045,7 @@ __device__ __forceinline__ void rows4_rl_epilogue(const RowArgs& a, const int r0
         if (r < a.out_rows) {
             float* o = a.out + (size_t)r * a.out_stride + tq;
             const float* in = row_out_reads_src(OUT) ? a.src_real + (size_t)r * a.src_stride + tq : nullptr;
-            const float* in2 = row_out_reads_src2(OUT) ? a.src_real2 + (size_t)r * a.src_stride + tq : nullptr;
+            const float* in2 = (row_out_reads_src2(OUT) || (row_out_fit_sums(OUT) && a.src_real2)) ? a.src_real2 + (size_t)r * a.src_stride + tq : nullptr;
 #pragma unroll
             for (int u = 0; u < Core::NUL; ++u)
 #pragma unroll
@@ -1006,7 +1054,8 @@ __device__ __forceinline__ void rows4_rl_epilogue(const RowArgs& a, const int r0
                     const int c = u * T + (q << Core::LOGOUT);
                     const float v = b == 0 ? z[0][s].x : b == 1 ? z[0][s].y : b == 2 ? z[1][s].x : z[1][s].y;
                     if (tq + c < a.out_cols) {
-                        if constexpr (row_out_reads_src2(OUT)) o[c] = rows4_rl_value<OUT>(v, in + c, in2 + c);
+                        if constexpr (row_out_fit_sums(OUT)) o[c] = rows4_rl_ratio_stat(v, in + c, in2 ? in2 + c : nullptr, res, kl);
+                        else if constexpr (row_out_reads_src2(OUT)) o[c] = rows4_rl_value<OUT>(v, in + c, in2 + c);
                         else o[c] = rows4_rl_value<OUT>(v, in + c);
                     }
                 }
@@ -1060,10 +1109,15 @@ __global__ __launch_bounds__((Rows4PackGeom<LOGL, true>::THREADS), (HALF ? Rows4
     Core::template run<0, true>(z, lds + g * NBUF * St::BUF, tw_fwd, bases, tid);
 
     float mn = __builtin_inff(), mx = -__builtin_inff();
+    double res = 0.0, kl = 0.0;  // row_out_fit_sums: an inactive thread group adds nothing
     if constexpr (row_out_operator(OUT)) {
-        if (active) rows4_rl_epilogue<Core, OUT, Core::V>(a, r0, tid, z);
+        if (active) rows4_rl_epilogue<Core, OUT, Core::V>(a, r0, tid, z, res, kl);
     } else if (active) rows4_inv_epilogue<Core, OUT, Core::V>(a, r0, tid, z, fscale, fshift, mn, mx);
     if constexpr (row_out_minmax(OUT)) block_minmax_store(mn, mx, a.mm_part, (int)blockIdx.x);
+    if constexpr (row_out_fit_sums(OUT)) {
+        static_assert(Geo::THREADS % 64 == 0, "block_sum2_store: whole waves");
+        block_sum2_store(res, kl, reinterpret_cast<double2*>(a.mm_part), (int)blockIdx.x);
+    }
 }
 
 // The inverse row pass for ONE small image: the two packed pairs of a 4-row group on two thread groups (RowsSplitGeom).  OUT as in rows4_inv_epilogue and rows4_rl_value.
@@ -1132,6 +1186,7 @@ __global__ __launch_bounds__((RowsSplitGeom<LOGL, true>::THREADS)) void fft_rows
     Core::template run<0, true>(z, grp_lds, tw_fwd, bases, tid);
 
     float mn = __builtin_inff(), mx = -__builtin_inff();
+    double res = 0.0, kl = 0.0;  // row_out_fit_sums: the thread's terms, columns in order, row ra before rb
 #pragma unroll
     for (int u = 0; u < Core::NUL; ++u)
 #pragma unroll
@@ -1142,7 +1197,16 @@ __global__ __launch_bounds__((RowsSplitGeom<LOGL, true>::THREADS)) void fft_rows
                 a.dst_real[(size_t)ra * L + n] = va;
                 a.dst_real[(size_t)rb * L + n] = vb;
             }
-            if constexpr (row_out_operator(OUT)) {  // (rows4_rl_value)
+            if constexpr (row_out_fit_sums(OUT)) {  // (rows4_rl_ratio_stat)
+                if (n < a.out_cols) {
+                    if (ra < a.out_rows)
+                        a.out[(size_t)ra * a.out_stride + n] = rows4_rl_ratio_stat(
+                            va, a.src_real + (size_t)ra * a.src_stride + n, a.src_real2 ? a.src_real2 + (size_t)ra * a.src_stride + n : nullptr, res, kl);
+                    if (rb < a.out_rows)
+                        a.out[(size_t)rb * a.out_stride + n] = rows4_rl_ratio_stat(
+                            vb, a.src_real + (size_t)rb * a.src_stride + n, a.src_real2 ? a.src_real2 + (size_t)rb * a.src_stride + n : nullptr, res, kl);
+                }
+            } else if constexpr (row_out_operator(OUT)) {  // (rows4_rl_value)
                 if (n < a.out_cols) {
                     if (ra < a.out_rows)
                         a.out[(size_t)ra * a.out_stride + n] =
@@ -1167,6 +1231,10 @@ __global__ __launch_bounds__((RowsSplitGeom<LOGL, true>::THREADS)) void fft_rows
             }
         }
     if constexpr (row_out_minmax(OUT)) block_minmax_store(mn, mx, a.mm_part, (int)blockIdx.x);
+    if constexpr (row_out_fit_sums(OUT)) {
+        static_assert(Geo::THREADS % 64 == 0, "block_sum2_store: whole waves");
+        block_sum2_store(res, kl, reinterpret_cast<double2*>(a.mm_part), (int)blockIdx.x);
+    }
 }
 
 // One inverse row pass of kind OUT.  The guards: ROW_OUT_REAL_MINMAX alone has a full-spectrum form; the operator kinds take rows of

@@ -1,11 +1,15 @@
 // gpu.cpp -- ./gpu <img-path> <psf-length> <psf-angle> [--out file] [--mode fast|parity] [--norm padded|cropped] [--host-epilogue]
-//           [--cls gamma|auto] [--k K|auto] [--reg gcv|discrepancy] [--sigma s] [--pad zero|smooth] [--rl iterations [--accel] [--free-boundary [--mask mask.png]]] [--tv mu [--tv-iters n] [--tv-rho r]]
+//           [--cls gamma|auto] [--k K|auto] [--reg gcv|discrepancy] [--sigma s] [--pad zero|smooth] [--rl iterations|auto [--accel] [--free-boundary [--mask mask.png]] [--rl-max n] [--rl-stop residual|kl] [--gain g] [--rl-check c]] [--tv mu [--tv-iters n] [--tv-rho r]]
 // `auto auto` for length and angle: the blur is estimated first (fft_gpu::estimateMotionBlur on the per-pixel mean of B, G and R),
 // printed as `estimate: length L angle A confidence C`, and the run then goes on exactly as `./gpu <img-path> L A` would.
 // `--cls auto` (gamma, with K = 0) or `--k auto` (K, with gamma = 0): the weight is chosen first (fft_gpu::chooseRegularisation on the same
 // mean, with the PSF of the run; --reg names the method -- default gcv for gamma, discrepancy for K -- and --sigma the noise level of the
 // discrepancy principle, else estimated), printed as `regularisation: K k gamma g sigma s method m flags f`, and the run then goes on
 // exactly as `--k k --cls g` would (`--cls 0` is the Wiener filter).  It combines with `auto auto`.
+// `--rl auto`: the iteration count is found first (fft_gpu::richardsonLucyAuto_RGB on the same mean, with the PSF, form and mask of the run: at most
+// --rl-max steps (default 100), stopped by --rl-stop residual (default; --sigma = the noise level of the mean, else estimated) or kl (--gain = photons
+// per unit, required), looked at every --rl-check steps), printed as `rl: iterations k of n rule r sigma s statistic v target t stopped 0|1`,
+// and the run then goes on exactly as `--rl k` would.  It combines with --accel, --free-boundary, --mask and `auto auto`.
 // Drop-in counterpart of the reference's gpu.cpp (argument meaning, printed lines and exit codes as at
 // gpu.cpp:57-138 of the reference): read image, /255, PSF, K = 0.01, split BGR, warm-up call, timed
 // wienerDeblur_RGB_optimized, timed wienerDeblur_RGB_naive, merge, Lab white balance, 8-bit result.
@@ -71,6 +75,11 @@ int main(int argc, char** argv) {
     bool verify = false;         // --verify: areChannelsEqual(parity-mode result, this run's result)
     bool host_epilogue = false;  // Lab white balance on the host (the A/B reference of the device epilogue)
     int rl_iterations = -1;      // --rl n: a timed Richardson-Lucy leg after the naive one; its planes are the written result
+    bool rl_auto = false;        // --rl auto: the count is found from the picture first
+    int rl_max = 100, rl_check = 0;  // --rl-max n, --rl-check c
+    string rl_stop;              // --rl-stop residual|kl
+    float rl_gain = 0.f;         // --gain g
+    bool rl_auto_opts = false;   // one of the four above was given
     bool accel = false;          // --accel: the --rl leg runs the accelerated iteration (vector extrapolation)
     bool free_boundary = false;  // --free-boundary: the --rl leg is fft_gpu::richardsonLucyFree_RGB (the picture is a crop of a larger scene)
     string mask_path;            // --mask file: pixels that are 0 in it (any channel counts) get weight 0, the others weight 1
@@ -115,7 +124,14 @@ int main(int argc, char** argv) {
             fft_gpu::set_pad_mode(pad_smooth ? FDR_PAD_SMOOTH : FDR_PAD_ZERO);
         }
         // Richardson-Lucy (fft_gpu::richardsonLucy_RGB, fast mode): n >= 0 iterations
-        else if (a == "--rl" && i + 1 < argc) rl_iterations = atoi(argv[++i]);
+        else if (a == "--rl" && i + 1 < argc) {
+            if (string(argv[++i]) == "auto") { rl_auto = true; rl_iterations = 0; }
+            else rl_iterations = atoi(argv[i]);
+        }
+        else if (a == "--rl-max" && i + 1 < argc) { rl_auto_opts = true; rl_max = atoi(argv[++i]); }
+        else if (a == "--rl-stop" && i + 1 < argc) { rl_auto_opts = true; rl_stop = argv[++i]; }
+        else if (a == "--gain" && i + 1 < argc) { rl_auto_opts = true; rl_gain = strtof(argv[++i], nullptr); }
+        else if (a == "--rl-check" && i + 1 < argc) { rl_auto_opts = true; rl_check = atoi(argv[++i]); }
         else if (a == "--accel") accel = true;
         else if (a == "--free-boundary") free_boundary = true;
         else if (a == "--mask" && i + 1 < argc) mask_path = argv[++i];
@@ -126,7 +142,7 @@ int main(int argc, char** argv) {
         else { cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle>\n"; return -1; }
     }
     // one weight is searched at a time; --reg and --sigma belong to a search
-    if ((cls_auto && k_auto) || (!(cls_auto || k_auto) && (!reg_method.empty() || reg_sigma != 0.f)) ||
+    if ((cls_auto && k_auto) || (!(cls_auto || k_auto) && (!reg_method.empty() || (reg_sigma != 0.f && !rl_auto))) ||
         (!reg_method.empty() && reg_method != "gcv" && reg_method != "discrepancy") || !(K >= 0.f) || !(reg_sigma >= 0.f)) {
         cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle>\n";
         return -1;
@@ -137,6 +153,13 @@ int main(int argc, char** argv) {
     if (pad_smooth && verify) { cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle>\n"; return -1; }
     // --free-boundary and --accel belong to --rl, --mask to --free-boundary
     if ((free_boundary && rl_iterations < 0) || (accel && rl_iterations < 0) || (!mask_path.empty() && !free_boundary)) {
+        cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle>\n";
+        return -1;
+    }
+    // --rl-max, --rl-stop, --gain and --rl-check belong to --rl auto; the kl rule needs its gain, the residual rule takes none
+    const bool rl_kl = rl_stop == "kl";
+    if ((rl_auto_opts && !rl_auto) || (!rl_stop.empty() && rl_stop != "residual" && !rl_kl) || rl_max < 0 || rl_check < 0 ||
+        (rl_auto && (rl_kl ? !(rl_gain > 0.f) || reg_sigma != 0.f : rl_gain != 0.f))) {
         cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle>\n";
         return -1;
     }
@@ -153,7 +176,7 @@ int main(int argc, char** argv) {
     img /= 255.0;
 
     Mat gray;  // the per-pixel mean of B, G and R: what the blur and the regularisation weight are found on
-    if (estimate || cls_auto || k_auto) {
+    if (estimate || cls_auto || k_auto || rl_auto) {
         vector<Mat> bgr;
         split(img, bgr);
         gray = Mat(img.rows, img.cols, CV_32F);
@@ -198,6 +221,19 @@ int main(int argc, char** argv) {
         fflush(stdout);
         if (c.flags) cerr << "[Warning] the search ended at the " << (c.flags & FDR_REG_AT_LOW ? "lower" : "upper") << " end of its range\n";
         fft_gpu::set_cls_gamma(gamma);
+    }
+
+    if (rl_auto) {  // the iteration count from the picture, the PSF and the noise
+        vector<Mat> one(1, gray.clone());
+        fft_gpu::RlAutoOptions ao;
+        ao.sigma = reg_sigma; ao.gain = rl_gain; ao.check_every = rl_check;
+        ao.free_boundary = free_boundary; ao.accelerate = accel; ao.weights = weights;
+        const fdr_rl_auto_result r = fft_gpu::richardsonLucyAuto_RGB(one, psf, rl_max, rl_kl ? FDR_RL_STOP_KL : FDR_RL_STOP_RESIDUAL, ao)[0];
+        printf("rl: iterations %d of %d rule %s sigma %.9g statistic %.9g target %.9g stopped %d\n", r.iterations_done, rl_max,
+               rl_kl ? "kl" : "residual", r.sigma, r.statistic, r.target, r.stopped);
+        fflush(stdout);
+        if (!r.stopped) cerr << "[Warning] the rule did not fire within " << rl_max << " iterations\n";
+        rl_iterations = r.iterations_done;
     }
 
     vector<Mat> channels;
