@@ -403,6 +403,65 @@ int fdr_richardson_lucy_auto_f32_dev(fdr_plan* plan, const float* d_img, int row
                                      int wstride, float* d_out, int out_stride, const fdr_rl_auto_params* params,
                                      fdr_rl_auto_result* result, double* d_trace, void* stream);
 
+/* -- blind Richardson-Lucy (Fish, Brinicombe, Pike & Walker 1995, "Blind deconvolution by means of the Richardson-Lucy algorithm";
+ *    Holmes 1992; MATLAB's deconvblind): the PSF takes the same multiplicative maximum-likelihood step as the image, from the same
+ *    ratio.  The call REFINES a PSF: it does not find one from nothing.  A flat start does not move (the symmetric saddle), a zero
+ *    of the start stays zero for good (that is how a caller masks the support), and the PSF is determined only up to a shift inside
+ *    its support, with the image shifted the other way.  The usual start is fdr_psf_gaussian.
+ *    The plan is M x N, the window rows x cols at its top-left corner, p_k the prows x pcols PSF top-left in the plan as
+ *    fdr_set_operator_psf places it, H_k = DFT2(pad(p_k)), and
+ *        corr_u(y) = IDFT2( conj(DFT2(u)) . DFT2(y) ), cropped to the top-left prows x pcols
+ *    Plain form (blur, d+ and u_0 = d+ as in fdr_richardson_lucy_f32, blur_k with p_k):
+ *        every k:        c = blur_k(u_k);  r = c > FDR_RL_TAU ? d+ / c : 0
+ *                        u_(k+1) = max(u_k . blur_k^T(r), 0)                          (exactly the step of fdr_richardson_lucy_f32 with p_k)
+ *        k >= psf_hold:  q = max(p_k . corr_(u_k)(pad(r)), 0);  s = sum(q)            (s in double, in a fixed order)
+ *                        p_(k+1) = s > 0 and finite ? q / s : p_k
+ *        k <  psf_hold:  p_(k+1) = p_k
+ *    Both updates use the same r and the iterates of step k (the joint, Jacobi form).
+ *    Free-boundary, weighted form (W, dw, fullblur and sigma as in fdr_richardson_lucy_free_f32): the coverage alpha_k =
+ *    fullblur_k^T(W) and wgt_k are recomputed from every new p_k, u_0 is that form's start under p_0, the image step is that form's
+ *    step with p_k, and the PSF step is the exact EM step
+ *        num = corr_(u_k)(pad(r));  den = corr_(u_k)(W);  q = den > 0 ? max(p_k . num / den, 0) : 0;  then s and p_(k+1) as above
+ *    So p_k >= 0 and sum(p_k) = 1 for every k >= 1 that followed an update, psf_hold >= iterations is the non-blind call (the bits of
+ *    fdr_richardson_lucy_f32 / _free_f32 with p_0, the PSF untouched), and a 1 x 1 PSF stays {1}.  On a CROPPED window use the
+ *    free-boundary form: the plain form's periodic model is wrong at the rim and its PSF does not converge there.
+ *    Output: u_n on the output window, normalised as in the underlying form, and p_n in place of the start PSF.  On return the
+ *    plan's operator tables are those of p_n (every PSF update rebuilds them, as fdr_set_operator_psf_dev does): fdr_blur_*, the RL
+ *    calls, fdr_tv_deconv_* and fdr_choose_reg_* follow directly.  An operator PSF need not have been set before.
+ *    Plans, refusals, overlap rules and phases are those of the underlying form.  FDR_ERR_ARG, before any device work and with the
+ *    plan usable afterwards, also for: a null params or PSF pointer, psf_hold < 0, a PSF that is empty, larger than the plan or of
+ *    more than FDR_BLIND_MAX_PSF entries, pstride < pcols, weights in the plain form, a plain-form output window other than 0, 0 or
+ *    rows, cols, a PSF range that overlaps the input, the weights or the output, and -- host form -- a start PSF with a negative
+ *    entry or a sum that is not finite and > 0.  The _dev form checks the start PSF in its first kernel instead: a bad one sets the
+ *    plan's status word to 1, the PSF is then never updated or written, and the image of that call is meaningless;
+ *    fdr_richardson_lucy_blind_status synchronises the device and reads the word of the last call (0 = the start was good).
+ *    The _dev form makes no host read-back and stays asynchronous on `stream`.  The first call on a plan allocates the workspace,
+ *    kept until fdr_plan_destroy: one table of fdr_plan_filter_bytes, four PSF planes of FDR_BLIND_MAX_PSF floats, the status word and,
+ *    at the first free-boundary call, one M x N float plane (the dense weights); FDR_ERR_ALLOC, plan intact, if it cannot be had.
+ *    Later calls allocate nothing.  The workspace of the free-boundary form is needed as before.  The Wiener / CLS filter and the
+ *    other calls' workspaces stay as they were.  No float atomics: results are bit-identical from call to call.
+ *    fdr_psf_gaussian: out[i, j] = exp(-((i - c)^2 + (j - c)^2) / (2 sigma^2)) / sum, c = size / 2 (integer division: the centre of
+ *    motionBlurKernel), evaluated in double, divided by its double sum, rounded once; sigma = 0 selects size / 4; 1 <= size <= 256.  */
+#define FDR_BLIND_MAX_PSF 65536
+typedef struct fdr_blind_params {
+    int iterations;    /* >= 0 */
+    int free_boundary; /* 0: the plain form; else the free-boundary, weighted form */
+    int psf_hold;      /* the PSF is kept for the first psf_hold steps, >= 0 */
+    int norm_area;     /* FDR_NORM_NONE / FDR_NORM_CROPPED / FDR_NORM_PADDED */
+    float cov_sigma;   /* free form: as fdr_rlfree_params.sigma */
+    int out_rows;      /* free form: as fdr_rlfree_params; plain form: 0 or rows */
+    int out_cols;      /* free form: as fdr_rlfree_params; plain form: 0 or cols */
+} fdr_blind_params;
+int fdr_richardson_lucy_blind_f32(fdr_plan* plan, const float* img_host, int rows, int cols, int stride, const float* weights_host,
+                                  int wstride, float* psf_host, int prows, int pcols, int pstride, float* out_host, int out_stride,
+                                  const fdr_blind_params* params);
+int fdr_richardson_lucy_blind_f32_dev(fdr_plan* plan, const float* d_img, int rows, int cols, int stride, const float* d_weights,
+                                      int wstride, float* d_psf, int prows, int pcols, int pstride, float* d_out, int out_stride,
+                                      const fdr_blind_params* params, void* stream);
+int fdr_richardson_lucy_blind_status(fdr_plan* plan, int* status);
+int fdr_psf_gaussian(int size, double sigma, float* out_host);
+int fdr_psf_gaussian_dev(int device, int size, double sigma, float* d_out, void* stream);
+
 /* -- total-variation (TV) regularised deconvolution by ADMM / split Bregman (Rudin-Osher-Fatemi 1992; Wang-Yang-Yin-Zhang 2008
  *    "FTVd"; Goldstein-Osher 2009): the edge-preserving restoration beside the linear filters and RL.  It uses the operator PSF of
  *    fdr_set_operator_psf* (H = DFT2 of the PSF top-left in the plan, blur / blur^T as above) and lives on the whole periodic

@@ -273,6 +273,60 @@ inline void richardsonLucyFree_RGB(std::vector<Mat>& channels, const Mat& psf, i
                                    bool accelerate = false) {
     richardsonLucyFree_RGB(channels, psf, iterations, weights, defaults(), FDR_RL_SIGMA, accelerate);
 }
+// What richardsonLucyBlind_RGB takes beside the picture and the start PSF: the form, the steps the PSF is held for, and the weights and
+// coverage threshold of the free form.
+struct BlindOptions {
+    bool free_boundary = false;
+    int psf_hold = 0;
+    Mat weights;  // free form: CV_32F, the picture's size; empty = all ones
+    float cov_sigma = FDR_RL_SIGMA;
+};
+// Blind Richardson-Lucy (fdr_richardson_lucy_blind_f32, include/fdr.h) of a picture, in place: the PSF is refined from psf_start
+// (usually fdr_psf_gaussian) on the per-pixel mean of the channels with FDR_NORM_NONE, on the plan of richardsonLucy_RGB (free form: of
+// richardsonLucyFree_RGB); then each channel goes through the non-blind call of the same form with that PSF -- the plan's operator
+// tables are already its -- and the same iteration count, normalised by o.norm_area.  Returns the refined PSF.  It refines a PSF: a
+// flat start does not move, zeros of the start stay zeros.
+inline Mat richardsonLucyBlind_RGB(std::vector<Mat>& channels, const Mat& psf_start, int iterations, const BlindOptions& b, const Options& o) {
+    if (channels.empty()) return Mat();
+    const int rows = channels[0].rows, cols = channels[0].cols;
+    if (!b.weights.empty() && (!b.free_boundary || b.weights.rows != rows || b.weights.cols != cols || b.weights.type() != CV_32F)) {
+        std::cerr << "richardsonLucyBlind_RGB: the weights belong to the free-boundary form, must be CV_32F and have the picture's size\n";
+        exit(1);
+    }
+    bool created = false;
+    PlanCacheSettle settle_;
+    const int M = b.free_boundary ? nextPowerOfTwo(rows + psf_start.rows - 1) : nextPowerOfTwo(rows);
+    const int N = b.free_boundary ? nextPowerOfTwo(cols + psf_start.cols - 1) : nextPowerOfTwo(cols);
+    fdr_plan* plan = plan_cache().get(o.device, std::max(8, M), std::max(32, N), FDR_MODE_FAST, &created);
+    Mat psf = psf_start.clone();  // continuous; receives p_n
+    Mat w = b.weights.empty() || b.weights.isContinuous() ? b.weights : b.weights.clone();
+    const float* wp = w.empty() ? nullptr : w.ptr<float>(0);
+    Mat mean(rows, cols, CV_32F), out(rows, cols, CV_32F);
+    const float inv = (float)channels.size();
+    for (int r = 0; r < rows; ++r)
+        for (int c = 0; c < cols; ++c) {
+            float sum = channels[0].ptr<float>(r)[c];
+            for (size_t k = 1; k < channels.size(); ++k) sum += channels[k].ptr<float>(r)[c];
+            mean.ptr<float>(r)[c] = sum / inv;
+        }
+    const fdr_blind_params bp = {iterations, b.free_boundary ? 1 : 0, b.psf_hold, FDR_NORM_NONE, b.cov_sigma, rows, cols};
+    FDR_CHECK(fdr_richardson_lucy_blind_f32(plan, mean.ptr<float>(0), rows, cols, cols, wp, cols, psf.ptr<float>(0), psf.rows, psf.cols, psf.cols,
+                                            out.ptr<float>(0), cols, &bp));
+    for (Mat& c : channels) {
+        Mat src = c.isContinuous() ? c : c.clone();
+        Mat res(rows, cols, CV_32F);
+        const fdr_rlfree_params prm = {iterations, b.cov_sigma, o.norm_area, rows, cols};
+        if (b.free_boundary)
+            FDR_CHECK(fdr_richardson_lucy_free_f32(plan, src.ptr<float>(0), rows, cols, cols, wp, cols, res.ptr<float>(0), cols, &prm));
+        else
+            FDR_CHECK(fdr_richardson_lucy_f32(plan, src.ptr<float>(0), rows, cols, cols, res.ptr<float>(0), cols, iterations, o.norm_area));
+        c = res;
+    }
+    return psf;
+}
+inline Mat richardsonLucyBlind_RGB(std::vector<Mat>& channels, const Mat& psf_start, int iterations, const BlindOptions& b = BlindOptions()) {
+    return richardsonLucyBlind_RGB(channels, psf_start, iterations, b, defaults());
+}
 // What richardsonLucyAuto_RGB takes beside the picture: the rule (FDR_RL_STOP_*) and its arguments as fdr_rl_auto_params has them
 // (sigma 0 = estimated per channel; tau and check_every 0 = 1), the form, and the weights and coverage threshold of the free form.
 struct RlAutoOptions {

@@ -83,6 +83,12 @@ class RlFreeParams(ctypes.Structure):
                 ("out_cols", ctypes.c_int)]
 
 
+class BlindParams(ctypes.Structure):
+    """fdr_blind_params of include/fdr.h"""
+    _fields_ = [("iterations", ctypes.c_int), ("free_boundary", ctypes.c_int), ("psf_hold", ctypes.c_int), ("norm_area", ctypes.c_int),
+                ("cov_sigma", ctypes.c_float), ("out_rows", ctypes.c_int), ("out_cols", ctypes.c_int)]
+
+
 class RlAutoParams(ctypes.Structure):
     """fdr_rl_auto_params of include/fdr.h"""
     _fields_ = [("iterations", ctypes.c_int), ("free_boundary", ctypes.c_int), ("accelerate", ctypes.c_int), ("rule", ctypes.c_int),
@@ -223,6 +229,11 @@ def _signatures():
         "fdr_richardson_lucy_accel_f32_dev": (ci, [vp, vp, ci, ci, ci, vp, ci, ci, ci, vp, vp]),
         "fdr_richardson_lucy_free_accel_f32": (ci, [vp, vp, ci, ci, ci, vp, ci, vp, ci, P(RlFreeParams), vp]),
         "fdr_richardson_lucy_free_accel_f32_dev": (ci, [vp, vp, ci, ci, ci, vp, ci, vp, ci, P(RlFreeParams), vp, vp]),
+        "fdr_richardson_lucy_blind_f32": (ci, [vp, vp, ci, ci, ci, vp, ci, vp, ci, ci, ci, vp, ci, P(BlindParams)]),
+        "fdr_richardson_lucy_blind_f32_dev": (ci, [vp, vp, ci, ci, ci, vp, ci, vp, ci, ci, ci, vp, ci, P(BlindParams), vp]),
+        "fdr_richardson_lucy_blind_status": (ci, [vp, P(ci)]),
+        "fdr_psf_gaussian": (ci, [ci, cd, vp]),
+        "fdr_psf_gaussian_dev": (ci, [ci, ci, cd, vp, vp]),
         "fdr_tv_deconv_f32": (ci, [vp, vp, ci, ci, ci, vp, ci, P(TvParams)]),
         "fdr_tv_deconv_f32_dev": (ci, [vp, vp, ci, ci, ci, vp, ci, P(TvParams), vp]),
         "fdr_cepstrum_f32": (ci, [vp, vp, ci, ci, ci, vp]),
@@ -587,6 +598,47 @@ class Plan:
                                                     ctypes.c_void_p(int(d_weights)) if d_weights else None, int(wstride),
                                                     ctypes.c_void_p(int(d_out)), out_stride, ctypes.byref(prm), _stream(stream)))
 
+    # blind Richardson-Lucy (include/fdr.h): refines the PSF with the picture and leaves the operator tables of the refined PSF
+    def richardson_lucy_blind(self, img, psf_start, iterations, free_boundary=False, weights=None, psf_hold=0, cov_sigma=RL_SIGMA,
+                              norm_area=NORM_NONE, full_plane=False):
+        """`iterations` blind Richardson-Lucy steps on the window img (host arrays) from the start PSF psf_start: the plain form, or
+        with free_boundary the free-boundary, weighted one (weights, cov_sigma and full_plane as Plan.richardson_lucy_free).  The
+        PSF is kept for the first psf_hold steps.  Returns (image, psf); the plan's operator PSF is then the returned one.  The call
+        refines a PSF: a flat start does not move and zeros of the start stay zeros."""
+        img = np.ascontiguousarray(img, dtype=np.float32)
+        psf = np.array(psf_start, dtype=np.float32, order="C", ndmin=2)
+        rows, cols = img.shape
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float32)
+            if w.shape != img.shape:
+                raise ValueError("weights must have the shape of img")
+        orows, ocols = (self.M, self.N) if (full_plane and free_boundary) else (rows, cols)
+        out = np.empty((orows, ocols), dtype=np.float32)
+        prm = BlindParams(int(iterations), int(bool(free_boundary)), int(psf_hold), int(norm_area), float(cov_sigma), orows, ocols)
+        _check(lib.fdr_richardson_lucy_blind_f32(self._h, _ptr(img), rows, cols, cols, _ptr(w) if w is not None else None, cols, _ptr(psf),
+                                                 psf.shape[0], psf.shape[1], psf.shape[1], _ptr(out), ocols, ctypes.byref(prm)))
+        return out, psf
+
+    def richardson_lucy_blind_dev(self, d_img, rows, cols, stride, d_psf, prows, pcols, pstride, d_out, out_stride, iterations,
+                                  free_boundary=False, d_weights=None, wstride=0, psf_hold=0, cov_sigma=RL_SIGMA, norm_area=NORM_NONE,
+                                  out_rows=None, out_cols=None, stream=None):
+        """the same on device pointers, asynchronous: d_psf holds the start PSF and receives the refined one; out_rows x out_cols
+        (free form; default rows x cols, up to M x N) is the output window.  A bad start PSF shows in blind_status()."""
+        prm = BlindParams(int(iterations), int(bool(free_boundary)), int(psf_hold), int(norm_area), float(cov_sigma),
+                          int(rows if out_rows is None else out_rows), int(cols if out_cols is None else out_cols))
+        _check(lib.fdr_richardson_lucy_blind_f32_dev(self._h, ctypes.c_void_p(int(d_img)), rows, cols, stride,
+                                                     ctypes.c_void_p(int(d_weights)) if d_weights else None, int(wstride),
+                                                     ctypes.c_void_p(int(d_psf)) if d_psf else None, int(prows), int(pcols), int(pstride),
+                                                     ctypes.c_void_p(int(d_out)), out_stride, ctypes.byref(prm), _stream(stream)))
+
+    def blind_status(self):
+        """the status word of the last blind call on this plan (synchronises the device): 0 = its start PSF was good, 1 = it had a
+        negative entry or a sum that is not finite and > 0 (the PSF was then left alone)"""
+        st = ctypes.c_int(-1)
+        _check(lib.fdr_richardson_lucy_blind_status(self._h, ctypes.byref(st)))
+        return st.value
+
     # Richardson-Lucy that stops from the data (include/fdr.h); uses the operator PSF
     def richardson_lucy_auto(self, img, max_iterations, rule=RL_STOP_RESIDUAL, sigma=0.0, gain=0.0, tau=0.0, check_every=0,
                              free_boundary=False, accelerate=False, weights=None, cov_sigma=RL_SIGMA, norm_area=NORM_NONE, full_plane=False):
@@ -906,6 +958,32 @@ def richardsonLucyFree_myfft(img, psf, iterations, weights=None, sigma=RL_SIGMA,
     with Plan(M, N, MODE_FAST, device) as p:
         p.set_operator_psf(psf)
         return p.richardson_lucy_free(img, iterations, weights, sigma, norm_area, full_plane, accelerate=accelerate)
+
+
+def psf_gaussian(size, sigma=0.0):
+    """fdr_psf_gaussian: the size x size Gaussian PSF centred at size // 2 (the centre of motionBlurKernel), sum 1; sigma = 0 selects
+    size / 4.  The usual start of richardsonLucyBlind_myfft.  Computed on the host: needs no device."""
+    out = np.empty((int(size), int(size)), dtype=np.float32) if size > 0 else np.empty((1, 1), dtype=np.float32)
+    _check(lib.fdr_psf_gaussian(int(size), float(sigma), _ptr(out)))
+    return out
+
+
+def richardsonLucyBlind_myfft(img, psf_start=None, psf_size=9, iterations=30, free_boundary=False, mask=None, psf_hold=0, psf_sigma=0.0,
+                              cov_sigma=RL_SIGMA, device=0, norm_area=NORM_NONE):
+    """Blind Richardson-Lucy of one channel: refines the PSF together with the picture and returns (image, psf).  psf_start: the
+    start PSF (None: psf_gaussian(psf_size, psf_sigma)); zeros in it stay zeros, so it also masks the support.  The plan is that of
+    richardsonLucy_myfft, or with free_boundary (the form for a crop of a larger scene) of richardsonLucyFree_myfft; mask (img.shape,
+    in [0, 1]; free_boundary only) are the pixel weights.  This refines a PSF, it does not find one from nothing."""
+    img = np.asarray(img, dtype=np.float32)
+    psf = psf_gaussian(psf_size, psf_sigma) if psf_start is None else np.asarray(psf_start, dtype=np.float32)
+    if mask is not None and not free_boundary:
+        raise ValueError("mask needs free_boundary=True")
+    if free_boundary:
+        M, N = _rlfree_plan_size(img.shape[0], img.shape[1], psf.shape[0], psf.shape[1])
+    else:
+        M, N = _rl_plan_size(img.shape[0], img.shape[1])
+    with Plan(M, N, MODE_FAST, device) as p:
+        return p.richardson_lucy_blind(img, psf, iterations, free_boundary, mask, psf_hold, cov_sigma, norm_area)
 
 
 def richardsonLucyAuto_myfft(img, psf, max_iterations, rule=RL_STOP_RESIDUAL, sigma=0.0, gain=0.0, tau=0.0, check_every=0, free_boundary=False,

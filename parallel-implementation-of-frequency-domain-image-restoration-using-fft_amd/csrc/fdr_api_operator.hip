@@ -109,6 +109,18 @@ int normalize_window(fdr_plan* p, const char* fn, const char* name, const float*
     return FDR_OK;
 }
 
+// the start of the plain form: u = max(d, 0) on the window
+int rl_init_estimate(fdr_plan* p, const float* d_img, int rows, int cols, int stride, float* u, int us, hipStream_t s) {
+    ScopedPass t(p, s, kPassRlInit);
+    FDR_HIP(launch_rl_init(d_img, rows, cols, stride, u, us, s));
+    return FDR_OK;
+}
+// the normalisation that ends a plain-form call
+int rl_normalize(fdr_plan* p, const char* fn, const float* fin, int fs, int rows, int cols, int norm_area, float* d_out, int out_stride,
+                 hipStream_t s) {
+    return normalize_window(p, fn, kPassRlNorm, fin, fs, rows, cols, norm_area, d_out, out_stride, s);
+}
+
 // pass B' on one of the operator tables
 int op_cols(fdr_plan* p, bool adjoint, hipStream_t s) {
     return op_cols_table(p, adjoint ? p->op_c : p->op_h, adjoint ? kPassOpColsConj : kPassOpColsH, s);
@@ -137,8 +149,8 @@ bool windows_overlap(const float* a, int a_stride, const float* b, int b_stride,
 // everything a Richardson-Lucy call refuses: plan, operator PSF and window, the iteration count, the normalisation, an output
 // that overlaps the input (the input is read on every iteration)
 int rl_check(const fdr_plan* p, const char* fn, const float* img, int rows, int cols, int stride, const float* out, int out_stride,
-             int iterations, int norm_area) {
-    const int rc = check_window(p, fn, NEED_OPERATOR_PSF, rows, cols, stride, out_stride);
+             int iterations, int norm_area, PlanNeed need) {
+    const int rc = check_window(p, fn, need, rows, cols, stride, out_stride);
     if (rc != FDR_OK) return rc;
     if (iterations < 0) return fail(FDR_ERR_ARG, std::string(fn) + ": iterations < 0");
     if (norm_area != FDR_NORM_NONE && norm_area != FDR_NORM_CROPPED && norm_area != FDR_NORM_PADDED)
@@ -151,14 +163,16 @@ int rl_check(const fdr_plan* p, const char* fn, const float* img, int rows, int 
 // one iteration: c = blur(y), r = d+ / c into the window of the raw plane (row stride cols), out = max(y . blur^T(r), 0); `out` may
 // be y itself.  With `fit` the ratio pass is the kind that also leaves the fit partials of c (the same r).
 int rl_step(fdr_plan* p, const float* d_img, int stride, const float* y, int ys, float* out, int os, int rows, int cols, hipStream_t s,
-            const RlFit* fit) {
+            const RlFit* fit, const RlHooks* hooks) {
     float* r = p->slots[0].raw;
     const int rs = cols;
     int rc = op_rows_fwd(p, y, rows, cols, ys, s);                                                    // c = blur(y) ...
+    if (rc == FDR_OK && hooks) rc = hooks->after_fwd();
     if (rc == FDR_OK) rc = op_cols(p, false, s);
     if (rc == FDR_OK)                                                                                 // ... r = d+ / c
         rc = op_rows_inv(p, fit ? ROW_OUT_RL_RATIO_STAT : ROW_OUT_RL_RATIO, fit ? kPassRlRatioFit : kPassRlRatio, d_img, stride, r, rs, rows,
                          cols, s, fit);
+    if (rc == FDR_OK && hooks) rc = hooks->after_ratio();
     if (rc == FDR_OK) rc = op_rows_fwd(p, r, rows, cols, rs, s);                                      // g = blur^T(r) ...
     if (rc == FDR_OK) rc = op_cols(p, true, s);
     if (rc == FDR_OK) rc = op_rows_inv(p, ROW_OUT_RL_UPDATE, kPassRlUpdate, y, ys, out, os, rows, cols, s);  // ... out = max(y g, 0)
@@ -182,10 +196,8 @@ int rl_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, int c
     float* const U[2] = {d_out, accel ? p->ra_u : d_out};
     const int us[2] = {out_stride, accel ? cols : out_stride};
     const int first = accel ? iterations & 1 : 0;
-    {
-        ScopedPass t(p, s, kPassRlInit);
-        FDR_HIP(launch_rl_init(d_img, rows, cols, stride, iterations == 0 ? fin : U[first], iterations == 0 ? fs : us[first], s));
-    }
+    rc = rl_init_estimate(p, d_img, rows, cols, stride, iterations == 0 ? fin : U[first], iterations == 0 ? fs : us[first], s);
+    if (rc != FDR_OK) return rc;
     if (accel) {
         rc = rl_accel_loop(p, iterations, rows, cols, U, us, first, fin, fs, d_alphas, s,
                            [&](const float* y, int ys, float* out, int os) { return rl_step(p, d_img, stride, y, ys, out, os, rows, cols, s); },
@@ -197,7 +209,7 @@ int rl_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, int c
         }
     }
     if (rc != FDR_OK || !norm) return rc;
-    return normalize_window(p, fn, kPassRlNorm, fin, fs, rows, cols, norm_area, d_out, out_stride, s);
+    return rl_normalize(p, fn, fin, fs, rows, cols, norm_area, d_out, out_stride, s);
 }
 
 // the checks, the device and the driver of the four entry points; the accelerated ones also refuse alphas that overlap a window and

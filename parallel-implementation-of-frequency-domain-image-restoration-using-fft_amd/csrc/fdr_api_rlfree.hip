@@ -50,9 +50,9 @@ bool spans_overlap(const float* a, int a_stride, int a_rows, int a_cols, const f
 // everything a free-boundary call refuses, before any device work: what the Richardson-Lucy calls refuse, and sigma, the output
 // window and an output that overlaps the weights
 int rlfree_check(const fdr_plan* p, const char* fn, const float* img, int rows, int cols, int stride, const float* weights, int wstride,
-                 const float* out, int out_stride, const fdr_rlfree_params* prm) {
+                 const float* out, int out_stride, const fdr_rlfree_params* prm, PlanNeed need) {
     if (!prm) return null_arg(fn);
-    const int rc = check_window(p, fn, NEED_OPERATOR_PSF, rows, cols, stride, out_stride);
+    const int rc = check_window(p, fn, need, rows, cols, stride, out_stride);
     if (rc != FDR_OK) return rc;
     if (weights && wstride < cols) return fail(FDR_ERR_ARG, std::string(fn) + ": the weights' stride must be >= cols");
     if (prm->iterations < 0) return fail(FDR_ERR_ARG, std::string(fn) + ": iterations < 0");
@@ -71,13 +71,16 @@ int rlfree_check(const fdr_plan* p, const char* fn, const float* img, int rows, 
 // one iteration on the whole plan: c = window(fullblur(y)), r = dw / c into the plan's raw plane, out = max(y wgt fullblur^T(pad(r)), 0);
 // y and out are dense M x N planes, and `out` may be y itself.  With `fit` (weights and d dense, row stride cols) the ratio pass forms
 // dw = w d+ itself, the product of the setup pass, and leaves the fit partials of c beside the same r.
-int rlfree_step(fdr_plan* p, const float* y, float* out, int rows, int cols, hipStream_t s, const RlFit* fit, const float* d_dense) {
+int rlfree_step(fdr_plan* p, const float* y, float* out, int rows, int cols, hipStream_t s, const RlFit* fit, const float* d_dense,
+                const RlHooks* hooks) {
     const int M = p->M, N = p->N;
     float* r = p->slots[0].raw;
     int rc = op_rows_fwd(p, y, M, N, N, s);                                                         // c = fullblur(y) ...
+    if (rc == FDR_OK && hooks) rc = hooks->after_fwd();
     if (rc == FDR_OK) rc = op_cols(p, false, s);
     if (rc == FDR_OK && fit) rc = op_rows_inv(p, ROW_OUT_RL_RATIO_STAT, kPassRfRatioFit, d_dense, cols, r, cols, rows, cols, s, fit);
     else if (rc == FDR_OK) rc = op_rows_inv(p, ROW_OUT_RL_RATIO, kPassRfRatio, p->rf_dw, cols, r, cols, rows, cols, s);  // ... r = dw / c
+    if (rc == FDR_OK && hooks) rc = hooks->after_ratio();
     if (rc == FDR_OK) rc = op_rows_fwd(p, r, rows, cols, cols, s);                                  // g = fullblur^T(pad(r)) ...
     if (rc == FDR_OK) rc = op_cols(p, true, s);
     if (rc != FDR_OK) return rc;

@@ -166,6 +166,15 @@ struct fdr_plan {
     double* rs_trace = nullptr;
     int rs_trace_cap = 0;
     float* rs_planes = nullptr;
+    // blind Richardson-Lucy (fdr_richardson_lucy_blind_f32*): made by the first such call, kept until fdr_plan_destroy -- bl_block holds
+    // the table conj(U) / (M N) of the image (ws_elems, layout of `filt`), four PSF planes of kBlindMaxPsf floats (the PSF p_k, num, den
+    // and the staging of the host form's PSF) and the status word; bl_w, made by the first free-boundary blind call, the dense weights
+    // W (M x N floats), which the coverage of every new PSF and the PSF step's denominator are computed from
+    void* bl_block = nullptr;
+    float2* bl_table = nullptr;
+    float *bl_p = nullptr, *bl_num = nullptr, *bl_den = nullptr, *bl_stage = nullptr;
+    int* bl_status = nullptr;
+    float* bl_w = nullptr;
     // choosing the regularisation weight (fdr_reg_curve_f32*, fdr_choose_reg_f32*): made by the first such call, kept until
     // fdr_plan_destroy -- one allocation holding the power plane (ws_elems floats in the layout of `filt`, one float per bin, then the
     // two extra floats of the packed column), the partials of the sweep and of the noise sum, and the candidate and result arrays
@@ -316,6 +325,10 @@ int op_cols_table(fdr_plan* p, const float2* table, const char* name, hipStream_
 // what ROW_OUT_RL_RATIO_STAT takes beside the datum: the weights (dense, the row stride of the datum; null = 1) and the room for the
 // (res, kl) partials, one double2 per workgroup of the pass
 struct RlFit { const float* weights; double* part; };
+// what a step of either form runs between its own passes for the blind call (fdr_api_blind.hip): after_fwd when pass A of the
+// estimate has left its row spectra in slot 0 (which it may read, not write), after_ratio when r lies in the window of the raw
+// plane (slot 0's spectrum is free then).  Neither changes an operand of the step's own passes: the step keeps its bits.
+struct RlHooks { std::function<int()> after_fwd, after_ratio; };
 // pass C with an operator kind: the window rows x cols of the inverse transform through the kind's epilogue into `out`
 int op_rows_inv(fdr_plan* p, RowOut kind, const char* name, const float* src, int src_stride, float* out, int out_stride, int rows, int cols,
                 hipStream_t s, const RlFit* fit = nullptr);
@@ -331,15 +344,19 @@ int normalize_window(fdr_plan* p, const char* fn, const char* name, const float*
 // ---- Richardson-Lucy, both forms (fdr_api_operator.hip, fdr_api_rlfree.hip): the checks and the step, shared with the calls that
 // stop from the data (fdr_api_rlstop.hip).  `fit`: the ratio pass also leaves the fit partials of c (same r, same update).
 int rl_check(const fdr_plan* p, const char* fn, const float* img, int rows, int cols, int stride, const float* out, int out_stride,
-             int iterations, int norm_area);
+             int iterations, int norm_area, PlanNeed need = NEED_OPERATOR_PSF);
 int rl_step(fdr_plan* p, const float* d_img, int stride, const float* y, int ys, float* out, int os, int rows, int cols, hipStream_t s,
-            const RlFit* fit = nullptr);
+            const RlFit* fit = nullptr, const RlHooks* hooks = nullptr);
+// the start u = max(d, 0) and the closing normalisation of a plain-form call, timed under the plain call's names
+int rl_init_estimate(fdr_plan* p, const float* d_img, int rows, int cols, int stride, float* u, int us, hipStream_t s);
+int rl_normalize(fdr_plan* p, const char* fn, const float* fin, int fs, int rows, int cols, int norm_area, float* d_out, int out_stride,
+                 hipStream_t s);
 int ensure_rlfree_workspace(fdr_plan* p, const char* fn);
 bool spans_overlap(const float* a, int a_stride, int a_rows, int a_cols, const float* b, int b_stride, int b_rows, int b_cols);
 int rlfree_check(const fdr_plan* p, const char* fn, const float* img, int rows, int cols, int stride, const float* weights, int wstride,
-                 const float* out, int out_stride, const fdr_rlfree_params* prm);
+                 const float* out, int out_stride, const fdr_rlfree_params* prm, PlanNeed need = NEED_OPERATOR_PSF);
 int rlfree_step(fdr_plan* p, const float* y, float* out, int rows, int cols, hipStream_t s, const RlFit* fit = nullptr,
-                const float* d_dense = nullptr);
+                const float* d_dense = nullptr, const RlHooks* hooks = nullptr);
 int rlfree_begin(fdr_plan* p, const float* d_img, int rows, int cols, int stride, const float* d_w, int wstride, float sigma, float* keep_w,
                  const double** sums, hipStream_t s);
 int rlfree_finish(fdr_plan* p, const char* fn, const float* u, float* d_out, int out_stride, const fdr_rlfree_params& prm, hipStream_t s);

@@ -193,6 +193,19 @@ hipError_t launch_rlaccel_extrapolate(const float* u1, int u1s, const float* u0,
 // (fdr_rlstop.hip) the fit trace of Richardson-Lucy: one workgroup folds the n (res, kl) pairs ROW_OUT_RL_RATIO_STAT left in `part`
 // in index order (thread t adds t, t + 256, ... in order, then a fixed tree) into out[0] = res, out[1] = kl
 hipError_t launch_rlstop_fold(const double* part, int n, double* out, hipStream_t s);
+// (fdr_blind.hip) blind Richardson-Lucy.  conj: the column pass of launch_cols_panel_operator on the row spectra a.data (a.nvalid rows,
+// half spectrum; only read), storing conj(U) / (M N) alone, to `conj_out` (not a.data), in the layout pass B' reads its filter from.
+// start: the caller's prows x pcols PSF (row stride pstride) dense into p, *status = 0 when no entry is negative and the double sum is
+// finite and > 0, else 1.  project: q = max(p . num, 0) (den null) or den > 0 ? max(p . num / den, 0) : 0, s = sum(q) in double in a
+// fixed order, p = q / s when s is finite and > 0 and *status is 0 (else p stays); the PSF also to `out` (row stride ostride) when
+// that is not null.  wgt: alpha in `wgt` (count floats, a multiple of 4) -> alpha > sigma ? 1 / alpha : 0.  gaussian: fdr_psf_gaussian.
+constexpr int kBlindMaxPsf = 65536;  // entries of a PSF the one-workgroup kernels take
+hipError_t launch_cols_panel_conj(int logm, const ColArgs& a, float2* conj_out, const float2* tw_fwd, hipStream_t s);
+hipError_t launch_blind_psf_start(const float* psf, int prows, int pcols, int pstride, float* p, int* status, hipStream_t s);
+hipError_t launch_blind_psf_project(float* p, const float* num, const float* den, int prows, int pcols, const int* status, float* out,
+                                    int ostride, hipStream_t s);
+hipError_t launch_blind_wgt(float* wgt, size_t count, float sigma, hipStream_t s);
+hipError_t launch_psf_gaussian(int size, double sigma, float* d_out, hipStream_t s);
 // (fdr_tv.hip) total-variation deconvolution.  table: T = (1 / (M N)) / (mu |H|^2 + rho L) from op_h = H / (M N) (the operator table
 // of launch_cols_panel_operator) and the Laplacian table `lap` of launch_cols_panel_cls, in the layout pass B' reads its filter
 // from.  init: x = pad(d) over the M x N plan (row stride N), wx = wy = 0.  spatial: one ADMM half-step on full M x N planes --

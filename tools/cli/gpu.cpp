@@ -6,6 +6,10 @@
 // mean, with the PSF of the run; --reg names the method -- default gcv for gamma, discrepancy for K -- and --sigma the noise level of the
 // discrepancy principle, else estimated), printed as `regularisation: K k gamma g sigma s method m flags f`, and the run then goes on
 // exactly as `--k k --cls g` would (`--cls 0` is the Wiener filter).  It combines with `auto auto`.
+// `blind <size>` in place of length and angle, with --rl n: the PSF is not stated but refined from a size x size Gaussian start
+// (--psf-sigma s, default size / 4) by blind Richardson-Lucy on the per-pixel mean of B, G and R (fft_gpu::richardsonLucyBlind_RGB; --free-boundary,
+// --mask and --psf-hold h apply), printed as `blind: size S iterations n psf-sum 1 psf-peak P at (i, j)`; --psf-out file writes the
+// PSF min-max scaled.  The Wiener legs of the run then use the refined PSF, and the written result is the blind call's.
 // `--rl auto`: the iteration count is found first (fft_gpu::richardsonLucyAuto_RGB on the same mean, with the PSF, form and mask of the run: at most
 // --rl-max steps (default 100), stopped by --rl-stop residual (default; --sigma = the noise level of the mean, else estimated) or kl (--gain = photons
 // per unit, required), looked at every --rl-check steps), printed as `rl: iterations k of n rule r sigma s statistic v target t stopped 0|1`,
@@ -68,10 +72,14 @@ int main(int argc, char** argv) {
     }
     string img_path = argv[1];
     const bool estimate = string(argv[2]) == "auto" && string(argv[3]) == "auto";
+    const bool blind = string(argv[2]) == "blind";  // argv[3] is the PSF's size
     if (!estimate && (string(argv[2]) == "auto" || string(argv[3]) == "auto")) { cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle>\n"; return -1; }
-    int psf_length = estimate ? 0 : atoi(argv[2]);
-    double psf_angle = estimate ? 0.0 : atof(argv[3]);
-    string out_path, raw_path;
+    int psf_length = estimate ? 0 : atoi(argv[blind ? 3 : 2]);
+    double psf_angle = estimate || blind ? 0.0 : atof(argv[3]);
+    string out_path, raw_path, psf_out_path;  // --psf-out file (blind)
+    int psf_hold = 0;                          // --psf-hold h (blind)
+    double psf_sigma = 0.0;                    // --psf-sigma s (blind)
+    bool blind_opts = false;
     bool verify = false;         // --verify: areChannelsEqual(parity-mode result, this run's result)
     bool host_epilogue = false;  // Lab white balance on the host (the A/B reference of the device epilogue)
     int rl_iterations = -1;      // --rl n: a timed Richardson-Lucy leg after the naive one; its planes are the written result
@@ -135,6 +143,9 @@ int main(int argc, char** argv) {
         else if (a == "--accel") accel = true;
         else if (a == "--free-boundary") free_boundary = true;
         else if (a == "--mask" && i + 1 < argc) mask_path = argv[++i];
+        else if (a == "--psf-hold" && i + 1 < argc) { blind_opts = true; psf_hold = atoi(argv[++i]); }
+        else if (a == "--psf-sigma" && i + 1 < argc) { blind_opts = true; psf_sigma = atof(argv[++i]); }
+        else if (a == "--psf-out" && i + 1 < argc) { blind_opts = true; psf_out_path = argv[++i]; }
         // total-variation deconvolution (fft_gpu::tvDeblur_RGB, fast mode): mu > 0, n >= 0 iterations, penalty rho > 0
         else if (a == "--tv" && i + 1 < argc) tv_mu = strtof(argv[++i], nullptr);
         else if (a == "--tv-iters" && i + 1 < argc) { tv_opts = true; tv_iterations = atoi(argv[++i]); }
@@ -160,6 +171,12 @@ int main(int argc, char** argv) {
     const bool rl_kl = rl_stop == "kl";
     if ((rl_auto_opts && !rl_auto) || (!rl_stop.empty() && rl_stop != "residual" && !rl_kl) || rl_max < 0 || rl_check < 0 ||
         (rl_auto && (rl_kl ? !(rl_gain > 0.f) || reg_sigma != 0.f : rl_gain != 0.f))) {
+        cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle>\n";
+        return -1;
+    }
+    // blind needs --rl n (a count, plain iteration) and a size; its options belong to it
+    if ((blind && (rl_iterations < 0 || rl_auto || accel || psf_length < 1 || psf_length > 256 || psf_hold < 0 || !(psf_sigma >= 0.0) || cls_auto || k_auto)) ||
+        (!blind && blind_opts)) {
         cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle>\n";
         return -1;
     }
@@ -209,7 +226,41 @@ int main(int argc, char** argv) {
             }
     }
 
-    Mat psf = motionBlurKernel(psf_length, psf_angle);
+    vector<Mat> blind_planes;  // blind: the restored B, G, R of the blind leg
+    Mat psf;
+    if (blind) {  // the PSF from the picture, refined from a Gaussian start
+        Mat start(psf_length, psf_length, CV_32F);
+        if (fdr_psf_gaussian(psf_length, psf_sigma, start.ptr<float>(0)) != FDR_OK) { cerr << "Error: " << fdr_last_error() << "\n"; return -1; }
+        split(img, blind_planes);
+        fft_gpu::BlindOptions bo;
+        bo.free_boundary = free_boundary; bo.psf_hold = psf_hold; bo.weights = weights;
+        psf = fft_gpu::richardsonLucyBlind_RGB(blind_planes, start, rl_iterations, bo);
+        double sum = 0.0;
+        float peak = -1.f, lo = psf.ptr<float>(0)[0];
+        int pi = 0, pj = 0;
+        for (int r = 0; r < psf.rows; ++r)
+            for (int c = 0; c < psf.cols; ++c) {
+                const float v = psf.ptr<float>(r)[c];
+                sum += v;
+                lo = std::min(lo, v);
+                if (v > peak) { peak = v; pi = r; pj = c; }
+            }
+        printf("blind: size %d iterations %d psf-sum %.6g psf-peak %.9g at (%d, %d)\n", psf_length, rl_iterations, sum, (double)peak, pi, pj);
+        fflush(stdout);
+        if (!psf_out_path.empty()) {  // min-max scaled, grey
+            Mat k8(psf.rows, psf.cols, CV_8UC3);
+            for (int r = 0; r < psf.rows; ++r)
+                for (int c = 0; c < psf.cols; ++c) {
+                    const float t = peak > lo ? (psf.ptr<float>(r)[c] - lo) / (peak - lo) : 0.f;
+                    const unsigned char g = (unsigned char)std::lround(255.0f * t);
+                    for (int k = 0; k < 3; ++k) k8.ptr<unsigned char>(r)[3 * c + k] = g;
+                }
+            if (!fdr_io::imwrite(psf_out_path, k8)) { cout << "Cannot write " << psf_out_path << "\n"; return -1; }
+            cout << "Wrote " << psf_out_path << "\n";
+        }
+    } else {
+        psf = motionBlurKernel(psf_length, psf_angle);
+    }
     if (cls_auto || k_auto) {  // the weight from the picture and the PSF: gamma with K = 0, or K with gamma = 0
         const bool gcv = reg_method.empty() ? cls_auto : reg_method == "gcv";
         const fdr_reg_choice c = fft_gpu::chooseRegularisation(gray, psf, gcv ? FDR_REG_GCV : FDR_REG_DISCREPANCY,
@@ -275,7 +326,9 @@ int main(int argc, char** argv) {
     cout << "Deblurring 3 channels took(gpu): " << naive_time << " ms\n";
     printf("[Speedup] %.2fx ms\n", serial_time / naive_time);
 
-    if (rl_iterations >= 0) {  // Richardson-Lucy on the same channels: its planes become the written result
+    if (blind) {  // the blind leg's planes are the written result
+        channels = blind_planes;
+    } else if (rl_iterations >= 0) {  // Richardson-Lucy on the same channels: its planes become the written result
         vector<Mat> rl = input;
         t_start = high_resolution_clock::now();
         if (free_boundary) fft_gpu::richardsonLucyFree_RGB(rl, psf, rl_iterations, weights, accel);
