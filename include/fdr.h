@@ -232,8 +232,9 @@ int fdr_wiener_batch_f32_dev(fdr_plan* plan, const float* d_imgs, size_t img_pit
  *    the fdr_wiener_* calls give a flat plane (all 0).  n = 0 returns d+.  Outside the window u and r stay 0.
  *    Plans: FDR_MODE_FAST, M and N powers of two, 8 <= M <= 8192, 32 <= N <= 8192, neither FDR_FLAG_SIMPLE_PATH nor
  *    FDR_FLAG_FULL_SPECTRUM (FDR_FLAG_MIXED_RADIX has no effect on such sizes); every other plan returns FDR_ERR_ARG before any
- *    device work, a tables-only plan FDR_ERR_STATE, and the plan stays usable.  Batches, fdr_batch_run, fdr_slab_* and filter
- *    export / import do not cover the operator.
+ *    device work, a tables-only plan FDR_ERR_STATE, and the plan stays usable.  fdr_wiener_batch_*, fdr_batch_run, fdr_slab_* and
+ *    filter export / import do not cover the operator; several images per launch are fdr_blur_batch_f32_dev and
+ *    fdr_richardson_lucy_batch_f32* below.
  *      fdr_set_operator_psf*   the operator PSF (validated as in fdr_set_psf*), held apart from the Wiener / CLS filter: setting
  *                              either never changes the other.  The first call on a plan allocates the two operator tables
  *                              (2 x fdr_plan_filter_bytes), kept until fdr_plan_destroy.  PRE phase.
@@ -298,6 +299,50 @@ int fdr_richardson_lucy_free_f32(fdr_plan* plan, const float* img_host, int rows
                                  int wstride, float* out_host, int out_stride, const fdr_rlfree_params* params);
 int fdr_richardson_lucy_free_f32_dev(fdr_plan* plan, const float* d_img, int rows, int cols, int stride, const float* d_weights,
                                      int wstride, float* d_out, int out_stride, const fdr_rlfree_params* params, void* stream);
+
+/* -- batched blur and Richardson-Lucy: `count` images with one operator PSF, several per launch.  Image i is read at d_imgs + i img_pitch
+ *    and written at d_out + i out_pitch (elements), as in fdr_wiener_batch_f32_dev; a colour picture is three such planes.  The call
+ *    cuts the batch into launch groups of `group` images (fdr_plan_set_batching; the last group may be smaller) and every pass of a
+ *    group -- the forward rows, the column pass, the inverse rows with the ratio or the update -- is ONE launch over its images, so
+ *    the operator table is read once per group and a small image no longer leaves the chip idle.  A group runs to completion (start,
+ *    every iteration, normalisation) on the caller's stream, on the workspaces 0 .. group - 1 that fdr_plan_set_batching made, before
+ *    the next begins; nstreams above 1 and FDR_OPT_BATCH_GRAPH are accepted and change nothing here, and group = 1 (the default) is
+ *    literally the loop of the single-image _dev calls.  The maths is that of the single-image calls and so are the bits: every image
+ *    of a batch comes out bit for bit as the single-image _dev call of the same form gives it on the same plan, for every group size,
+ *    tail and layout.
+ *      fdr_blur_batch_f32_dev             fdr_blur_f32_dev per image.
+ *      fdr_richardson_lucy_batch_f32_dev  params->free_boundary == 0: fdr_richardson_lucy_f32_dev per image (u in each output window,
+ *                              r in each workspace: no allocation); out_rows = out_cols = 0 or rows, cols; weights must be NULL.
+ *                              free_boundary != 0: fdr_richardson_lucy_free_f32_dev per image with ONE weights plane (rows x cols, row
+ *                              stride wstride; NULL = all ones) for the whole batch: the setup of image 0, the coverage alpha and wgt
+ *                              are computed once per call, every image has its own dw, its own sums and its own M x N estimate, and
+ *                              the output window is out_rows x out_cols per image.  The first such call with a group g > 1 grows the
+ *                              free-boundary workspace from three to 1 + 2 g planes (4 (1 + 2 g) M N bytes and g sets of partials);
+ *                              FDR_ERR_ALLOC leaves the plan and the three-plane workspace as they were.  (The start of images after
+ *                              the first thresholds wgt > 0 in place of alpha > sigma: the same for every finite alpha.)
+ *      fdr_richardson_lucy_batch_f32      host pointers, synchronous: every image in, the batch, every result back.
+ *    Refusals, always before any device work and with the plan usable afterwards: a negative count (count = 0 returns FDR_OK at
+ *    once), a null pointer, whatever the single-image call of the form refuses for one image (plan, operator PSF, window, strides,
+ *    iterations, norm_area, sigma, the output window), weights in the plain form, and an output that overlaps the input or the
+ *    weights anywhere within the span of the batch (first element of image 0 to last element of image count - 1).  Neither _dev
+ *    form allocates after its first call, and both stay asynchronous on `stream`.  The accelerated, data-stopped and blind
+ *    iterations, TV, per-image weights, mixed-radix and full-spectrum plans and fdr_batch_run have no batched form (DESIGN.md
+ *    section 24).  Per image and iteration a group of g moves 64 - 8 (1 - 1/g) bytes per padded pixel.                        */
+int fdr_blur_batch_f32_dev(fdr_plan* plan, const float* d_imgs, size_t img_pitch, int count, int rows, int cols, int stride,
+                           float* d_out, size_t out_pitch, int out_stride, int adjoint, void* stream);
+typedef struct fdr_rl_batch_params {
+    int iterations;     /* >= 0 */
+    int norm_area;      /* FDR_NORM_NONE / _CROPPED / _PADDED, per image */
+    int free_boundary;  /* 0: fdr_richardson_lucy_f32's iteration; 1: fdr_richardson_lucy_free_f32's */
+    float sigma;        /* free form: coverage threshold in (0, 1) */
+    int out_rows, out_cols; /* free form: rows..M, cols..N; plain form: rows, cols (0, 0 means the same) */
+} fdr_rl_batch_params;
+int fdr_richardson_lucy_batch_f32_dev(fdr_plan* plan, const float* d_imgs, size_t img_pitch, int count, int rows, int cols, int stride,
+                                      const float* d_weights, int wstride, float* d_out, size_t out_pitch, int out_stride,
+                                      const fdr_rl_batch_params* params, void* stream);
+int fdr_richardson_lucy_batch_f32(fdr_plan* plan, const float* imgs_host, size_t img_pitch, int count, int rows, int cols, int stride,
+                                  const float* weights_host, int wstride, float* out_host, size_t out_pitch, int out_stride,
+                                  const fdr_rl_batch_params* params);
 
 /* -- accelerated Richardson-Lucy: Biggs & Andrews' vector extrapolation ("Acceleration of iterative image restoration algorithms",
  *    Applied Optics 36, 1997; the default of MATLAB's deconvlucy) around the unchanged iteration of either form above.  With

@@ -83,6 +83,12 @@ class RlFreeParams(ctypes.Structure):
                 ("out_cols", ctypes.c_int)]
 
 
+class RlBatchParams(ctypes.Structure):
+    """fdr_rl_batch_params of include/fdr.h"""
+    _fields_ = [("iterations", ctypes.c_int), ("norm_area", ctypes.c_int), ("free_boundary", ctypes.c_int), ("sigma", ctypes.c_float),
+                ("out_rows", ctypes.c_int), ("out_cols", ctypes.c_int)]
+
+
 class BlindParams(ctypes.Structure):
     """fdr_blind_params of include/fdr.h"""
     _fields_ = [("iterations", ctypes.c_int), ("free_boundary", ctypes.c_int), ("psf_hold", ctypes.c_int), ("norm_area", ctypes.c_int),
@@ -225,6 +231,9 @@ def _signatures():
         "fdr_richardson_lucy_f32_dev": (ci, [vp, vp, ci, ci, ci, vp, ci, ci, ci, vp]),
         "fdr_richardson_lucy_free_f32": (ci, [vp, vp, ci, ci, ci, vp, ci, vp, ci, P(RlFreeParams)]),
         "fdr_richardson_lucy_free_f32_dev": (ci, [vp, vp, ci, ci, ci, vp, ci, vp, ci, P(RlFreeParams), vp]),
+        "fdr_blur_batch_f32_dev": (ci, [vp, vp, sz, ci, ci, ci, ci, vp, sz, ci, ci, vp]),
+        "fdr_richardson_lucy_batch_f32": (ci, [vp, vp, sz, ci, ci, ci, ci, vp, ci, vp, sz, ci, P(RlBatchParams)]),
+        "fdr_richardson_lucy_batch_f32_dev": (ci, [vp, vp, sz, ci, ci, ci, ci, vp, ci, vp, sz, ci, P(RlBatchParams), vp]),
         "fdr_richardson_lucy_accel_f32": (ci, [vp, vp, ci, ci, ci, vp, ci, ci, ci, vp]),
         "fdr_richardson_lucy_accel_f32_dev": (ci, [vp, vp, ci, ci, ci, vp, ci, ci, ci, vp, vp]),
         "fdr_richardson_lucy_free_accel_f32": (ci, [vp, vp, ci, ci, ci, vp, ci, vp, ci, P(RlFreeParams), vp]),
@@ -597,6 +606,45 @@ class Plan:
         _check(lib.fdr_richardson_lucy_free_f32_dev(self._h, ctypes.c_void_p(int(d_img)), rows, cols, stride,
                                                     ctypes.c_void_p(int(d_weights)) if d_weights else None, int(wstride),
                                                     ctypes.c_void_p(int(d_out)), out_stride, ctypes.byref(prm), _stream(stream)))
+
+    # several images per launch (include/fdr.h, "batched blur and Richardson-Lucy"): groups of set_batching's `group` images, every
+    # image with the bits of its single-image call
+    def blur_batch_dev(self, d_imgs, img_pitch, count, rows, cols, stride, d_out, out_pitch, out_stride, adjoint=False, stream=None):
+        """blur (or blur^T) of `count` windows, image i at d_imgs + i img_pitch / d_out + i out_pitch (elements); asynchronous"""
+        _check(lib.fdr_blur_batch_f32_dev(self._h, ctypes.c_void_p(int(d_imgs)), img_pitch, count, rows, cols, stride,
+                                          ctypes.c_void_p(int(d_out)), out_pitch, out_stride, int(bool(adjoint)), _stream(stream)))
+
+    def richardson_lucy_batch_dev(self, d_imgs, img_pitch, count, rows, cols, stride, d_out, out_pitch, out_stride, iterations,
+                                  norm_area=NORM_NONE, free_boundary=False, d_weights=None, wstride=0, sigma=RL_SIGMA, out_rows=None,
+                                  out_cols=None, stream=None):
+        """`iterations` Richardson-Lucy steps on `count` windows with the plan's operator PSF: the iteration of richardson_lucy_dev,
+        or with free_boundary that of richardson_lucy_free_dev (one weights plane, or None, for all images; out_rows x out_cols the
+        output window).  Asynchronous."""
+        prm = RlBatchParams(int(iterations), int(norm_area), int(bool(free_boundary)), float(sigma),
+                            int((rows if free_boundary else 0) if out_rows is None else out_rows),
+                            int((cols if free_boundary else 0) if out_cols is None else out_cols))
+        _check(lib.fdr_richardson_lucy_batch_f32_dev(self._h, ctypes.c_void_p(int(d_imgs)), img_pitch, count, rows, cols, stride,
+                                                     ctypes.c_void_p(int(d_weights)) if d_weights else None, int(wstride),
+                                                     ctypes.c_void_p(int(d_out)), out_pitch, out_stride, ctypes.byref(prm), _stream(stream)))
+
+    def richardson_lucy_batch(self, imgs, iterations, free_boundary=False, weights=None, sigma=RL_SIGMA, norm_area=NORM_NONE,
+                              full_plane=False):
+        """Host arrays [count, rows, cols] in, [count, rows, cols] out (free_boundary with full_plane: [count, M, N]); weights
+        ([rows, cols], free_boundary only) serve every image."""
+        imgs = np.ascontiguousarray(imgs, dtype=np.float32)
+        cnt, rows, cols = imgs.shape
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float32)
+            if w.shape != (rows, cols):
+                raise ValueError("weights must have the shape of one image")
+        orows, ocols = (self.M, self.N) if (free_boundary and full_plane) else (rows, cols)
+        out = np.empty((cnt, orows, ocols), dtype=np.float32)
+        prm = RlBatchParams(int(iterations), int(norm_area), int(bool(free_boundary)), float(sigma), orows if free_boundary else 0,
+                            ocols if free_boundary else 0)
+        _check(lib.fdr_richardson_lucy_batch_f32(self._h, _ptr(imgs), rows * cols, cnt, rows, cols, cols, _ptr(w) if w is not None else None,
+                                                 cols, _ptr(out), orows * ocols, ocols, ctypes.byref(prm)))
+        return out
 
     # blind Richardson-Lucy (include/fdr.h): refines the PSF with the picture and leaves the operator tables of the refined PSF
     def richardson_lucy_blind(self, img, psf_start, iterations, free_boundary=False, weights=None, psf_hold=0, cov_sigma=RL_SIGMA,
@@ -1098,6 +1146,37 @@ def wienerDeblur_RGB_optimized(channels, psf, K, mode=MODE_PARITY, device=0, nor
         p.set_psf(psf, K, gamma=cls_gamma)
         for i in range(len(channels)):
             channels[i] = p.wiener(channels[i], norm_area)
+
+
+def _rl_rgb(channels, M, N, psf, iterations, device, **kw):
+    """the channels of one picture as ONE batched call on a group of len(channels) (at most 8) images"""
+    with Plan(M, N, MODE_FAST, device) as p:
+        p.set_operator_psf(psf)
+        p.set_batching(1, min(len(channels), 8))
+        out = p.richardson_lucy_batch(np.stack([np.asarray(c, dtype=np.float32) for c in channels]), iterations, **kw)
+    for i in range(len(channels)):
+        channels[i] = out[i]
+
+
+def richardsonLucy_RGB(channels, psf, iterations, device=0, norm_area=NORM_NONE):
+    """fft_gpu::richardsonLucy_RGB: replaces every element of `channels` (float32 planes of one size) in place with its
+    Richardson-Lucy estimate -- the bits of richardsonLucy_myfft per channel, from one plan and one launch per pass."""
+    if not channels:
+        return
+    r, c = np.asarray(channels[0]).shape
+    M, N = _rl_plan_size(r, c)
+    _rl_rgb(channels, M, N, psf, iterations, device, norm_area=norm_area)
+
+
+def richardsonLucyFree_RGB(channels, psf, iterations, weights=None, sigma=RL_SIGMA, device=0, norm_area=NORM_NONE):
+    """fft_gpu::richardsonLucyFree_RGB: the free-boundary form of richardsonLucy_RGB (richardsonLucyFree_myfft per channel); one
+    weights plane (or None) serves every channel, and its coverage is computed once."""
+    if not channels:
+        return
+    r, c = np.asarray(channels[0]).shape
+    psf = np.asarray(psf, dtype=np.float32)
+    M, N = _rlfree_plan_size(r, c, psf.shape[0], psf.shape[1])
+    _rl_rgb(channels, M, N, psf, iterations, device, free_boundary=True, weights=weights, sigma=sigma, norm_area=norm_area)
 
 
 def wienerDeblur_RGB_naive(channels, psf, K, mode=MODE_PARITY, device=0, norm_area=NORM_PADDED, cls_gamma=0.0, pad=PAD_ZERO):

@@ -15,6 +15,7 @@ namespace {
 const char* const kPassOpRowsPsf = "O rows: PSF pad+FFT (operator)";
 const char* const kPassOpCols = "O cols: FFT -> H/MN, conj(H)/MN";
 const char* const kPassOpRowsFwd = "A op rows: pad+FFT (blur / RL)";
+const char* const kPassOpRowsFwdN = "A op rows: pad+FFT (blur / RL), group";
 const char* const kPassOpColsH = "B' op cols: FFT*H*IFFT";
 const char* const kPassOpColsConj = "B' op cols: FFT*conj(H)*IFFT";
 const char* const kPassOpRowsBlur = "C op rows: IFFT+crop (blur)";
@@ -57,38 +58,71 @@ int set_operator_psf_impl(fdr_plan* p, const float* d_psf, int prows, int pcols,
     return FDR_OK;
 }
 
-// pass A: the window of x (zero elsewhere) -> the half spectrum of slot 0
-int op_rows_fwd(fdr_plan* p, const float* x, int rows, int cols, int stride, hipStream_t s) {
-    ScopedPass t(p, s, kPassOpRowsFwd);
-    RowArgs a = panel_row_args(p);
-    a.src_real = x; a.src_rows = rows; a.src_cols = cols; a.src_stride = stride;
-    a.dst_c = p->slots[0].work;
+// The three operator passes for a group of n >= 1 images on the slots ws[0 .. n), shaped as the panel stages of fdr_api_wiener.hip:
+// one image goes by the single-image fields alone (batch.nimg 0: the launchers then pick the split kernels of small images), a
+// group of 2 .. kMaxGroup images adds the batch block (blockIdx.y = image).
+// pass A: the window of xs[k] (zero elsewhere, whatever the plan's pad mode) -> the half spectrum of slot k
+int op_rows_fwd_n(fdr_plan* p, fdr_plan::Slot* const* ws, int n, const float* const* xs, int rows, int cols, int stride, hipStream_t s) {
+    ScopedPass t(p, s, n > 1 ? kPassOpRowsFwdN : kPassOpRowsFwd);
+    RowArgs a = panel_row_args(p);  // (pad_mode stays FDR_PAD_ZERO)
+    a.src_real = xs[0]; a.src_rows = rows; a.src_cols = cols; a.src_stride = stride;
+    a.dst_c = ws[0]->work;
+    if (n > 1) {
+        a.batch.nimg = n;
+        for (int k = 0; k < kMaxGroup; ++k) { a.batch.src_real[k] = xs[k < n ? k : 0]; a.batch.spec[k] = ws[k < n ? k : 0]->work; }
+    }
     FDR_HIP(launch_rows4(p->logN, ROW_IN_REAL, ROW_OUT_COMPLEX, a, p->tw_row_f, s));
     return FDR_OK;
 }
-// pass B', unchanged, with `table` as its filter
-int op_cols_table(fdr_plan* p, const float2* table, const char* name, hipStream_t s) {
+// pass B', unchanged, with `table` as its filter: read once for the group
+int op_cols_table_n(fdr_plan* p, fdr_plan::Slot* const* ws, int n, const float2* table, const char* name, hipStream_t s) {
     ScopedPass t(p, s, name);
     ColArgs c = panel_col_args(p);
-    c.data = p->slots[0].work; c.filt = table;
-    c.batch.nimg = 1; c.batch.data[0] = c.data;
+    c.data = ws[0]->work; c.filt = table;
+    c.batch.nimg = n;
+    for (int k = 0; k < n; ++k) c.batch.data[k] = ws[k]->work;
     FDR_HIP(launch_cols_panel(p->logM, COL_FUSED, c, p->tw_col_f, s));
     return FDR_OK;
 }
-// pass C with an operator kind: the window rows x cols of the inverse transform through the kind's epilogue into `out`
-int op_rows_inv(fdr_plan* p, RowOut kind, const char* name, const float* src, int src_stride, float* out, int out_stride, int rows,
-                int cols, hipStream_t s, const RlFit* fit) {
+// pass C with an operator kind: the window rows x cols of the inverse transform of slot k through the kind's epilogue into outs[k];
+// srcs[k] the kind's real source (null for ROW_OUT_BLUR), src2 the second source of ROW_OUT_RL_UPDATE_W, one plane for the group
+int op_rows_inv_n(fdr_plan* p, fdr_plan::Slot* const* ws, int n, RowOut kind, const char* name, const float* const* srcs, int src_stride,
+                  const float* src2, float* const* outs, int out_stride, int rows, int cols, hipStream_t s, const RlFit* fit) {
+    if (fit && n > 1) return fail(FDR_ERR_STATE, "op_rows_inv: the fit sums take one image per launch");
     ScopedPass t(p, s, name);
     RowArgs a = panel_row_args(p);
-    a.src_c = p->slots[0].work;
-    a.src_real = src; a.src_stride = src_stride;
+    a.src_c = ws[0]->work;
+    a.src_real = srcs ? srcs[0] : nullptr; a.src_stride = src_stride;
+    a.src_real2 = src2;
     if (fit) {  // ROW_OUT_RL_RATIO_STAT: the weights beside the datum, the (res, kl) partials in the slot of the min/max ones
         a.src_real2 = fit->weights;
         a.mm_part = reinterpret_cast<float2*>(fit->part);
     }
-    a.out = out; a.out_rows = rows; a.out_cols = cols; a.out_stride = out_stride;
+    a.out = outs[0]; a.out_rows = rows; a.out_cols = cols; a.out_stride = out_stride;
+    if (n > 1) {
+        a.batch.nimg = n;
+        for (int k = 0; k < kMaxGroup; ++k) {
+            const int j = k < n ? k : 0;
+            a.batch.spec[k] = ws[j]->work; a.batch.src_real[k] = srcs ? srcs[j] : nullptr; a.batch.out[k] = outs[j];
+        }
+    }
     FDR_HIP(launch_rows4(p->logN, ROW_IN_COMPLEX, kind, a, p->tw_row_f, s));
     return FDR_OK;
+}
+
+// the single-image forms: a group of one on slot 0
+int op_rows_fwd(fdr_plan* p, const float* x, int rows, int cols, int stride, hipStream_t s) {
+    fdr_plan::Slot* w = &p->slots[0];
+    return op_rows_fwd_n(p, &w, 1, &x, rows, cols, stride, s);
+}
+int op_cols_table(fdr_plan* p, const float2* table, const char* name, hipStream_t s) {
+    fdr_plan::Slot* w = &p->slots[0];
+    return op_cols_table_n(p, &w, 1, table, name, s);
+}
+int op_rows_inv(fdr_plan* p, RowOut kind, const char* name, const float* src, int src_stride, float* out, int out_stride, int rows,
+                int cols, hipStream_t s, const RlFit* fit) {
+    fdr_plan::Slot* w = &p->slots[0];
+    return op_rows_inv_n(p, &w, 1, kind, name, &src, src_stride, nullptr, &out, out_stride, rows, cols, s, fit);
 }
 
 // min-max to [0, 1] over the window; FDR_NORM_PADDED also counts the zeros outside it (one extra (0, 0) partial)
@@ -126,12 +160,25 @@ int op_cols(fdr_plan* p, bool adjoint, hipStream_t s) {
     return op_cols_table(p, adjoint ? p->op_c : p->op_h, adjoint ? kPassOpColsConj : kPassOpColsH, s);
 }
 
+int op_cols_n(fdr_plan* p, fdr_plan::Slot* const* ws, int n, bool adjoint, hipStream_t s) {
+    return op_cols_table_n(p, ws, n, adjoint ? p->op_c : p->op_h, adjoint ? kPassOpColsConj : kPassOpColsH, s);
+}
+
 // blur (or blur^T) of the window rows x cols of d_img, the window out_rows x out_cols of the result into d_out
 int blur_window_dev(fdr_plan* p, const float* d_img, int rows, int cols, int stride, float* d_out, int out_stride, int out_rows, int out_cols,
                     int adjoint, hipStream_t s) {
     int rc = op_rows_fwd(p, d_img, rows, cols, stride, s);
     if (rc == FDR_OK) rc = op_cols(p, adjoint != 0, s);
     if (rc == FDR_OK) rc = op_rows_inv(p, ROW_OUT_BLUR, kPassOpRowsBlur, nullptr, 0, d_out, out_stride, out_rows, out_cols, s);
+    return rc;
+}
+
+// the same for a group of n images on the slots ws[0 .. n): six launches whatever n
+int blur_window_dev_n(fdr_plan* p, fdr_plan::Slot* const* ws, int n, const float* const* d_imgs, int rows, int cols, int stride,
+                      float* const* d_outs, int out_stride, int adjoint, hipStream_t s) {
+    int rc = op_rows_fwd_n(p, ws, n, d_imgs, rows, cols, stride, s);
+    if (rc == FDR_OK) rc = op_cols_n(p, ws, n, adjoint != 0, s);
+    if (rc == FDR_OK) rc = op_rows_inv_n(p, ws, n, ROW_OUT_BLUR, kPassOpRowsBlur, nullptr, 0, nullptr, d_outs, out_stride, rows, cols, s);
     return rc;
 }
 
@@ -179,6 +226,21 @@ int rl_step(fdr_plan* p, const float* d_img, int stride, const float* y, int ys,
     return rc;
 }
 
+// rl_step for a group of n images on the slots ws[0 .. n): image k's r in the window of slot k's raw plane, outs[k] may be ys[k]
+int rl_step_n(fdr_plan* p, fdr_plan::Slot* const* ws, int n, const float* const* d_imgs, int stride, const float* const* ys, int ystride,
+              float* const* outs, int os, int rows, int cols, hipStream_t s) {
+    float* r[kMaxGroup];
+    for (int k = 0; k < n; ++k) r[k] = ws[k]->raw;
+    const int rs = cols;
+    int rc = op_rows_fwd_n(p, ws, n, ys, rows, cols, ystride, s);
+    if (rc == FDR_OK) rc = op_cols_n(p, ws, n, false, s);
+    if (rc == FDR_OK) rc = op_rows_inv_n(p, ws, n, ROW_OUT_RL_RATIO, kPassRlRatio, d_imgs, stride, nullptr, r, rs, rows, cols, s);
+    if (rc == FDR_OK) rc = op_rows_fwd_n(p, ws, n, r, rows, cols, rs, s);
+    if (rc == FDR_OK) rc = op_cols_n(p, ws, n, true, s);
+    if (rc == FDR_OK) rc = op_rows_inv_n(p, ws, n, ROW_OUT_RL_UPDATE, kPassRlUpdate, ys, ystride, nullptr, outs, os, rows, cols, s);
+    return rc;
+}
+
 }  // namespace fdr
 
 namespace {
@@ -211,6 +273,20 @@ int rl_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, int c
     if (rc != FDR_OK || !norm) return rc;
     return rl_normalize(p, fn, fin, fs, rows, cols, norm_area, d_out, out_stride, s);
 }
+
+}  // namespace
+
+namespace fdr {
+
+// the driver of fdr_richardson_lucy_f32_dev on a checked call (a batch with groups of one is the loop of these)
+int rl_plain_dev(fdr_plan* p, const char* fn, const float* d_img, int rows, int cols, int stride, float* d_out, int out_stride, int iterations,
+                 int norm_area, hipStream_t s) {
+    return rl_dev_impl(p, fn, d_img, rows, cols, stride, d_out, out_stride, iterations, norm_area, false, nullptr, s);
+}
+
+}  // namespace fdr
+
+namespace {
 
 // the checks, the device and the driver of the four entry points; the accelerated ones also refuse alphas that overlap a window and
 // make sure of their workspace

@@ -22,24 +22,33 @@ const char* const kPassRfNorm = "E RLF minmax+normalize";
 
 namespace fdr {
 
-// the first free-boundary call of a plan: u, wgt and dw (M x N floats each) and the double partials
-int ensure_rlfree_workspace(fdr_plan* p, const char* fn) {
-    if (p->rf_block) return FDR_OK;
+// The workspace of the free-boundary calls: 1 + 2 g planes of M x N floats (wgt; u and dw of g images) and the double partials of
+// the two sums, once per image.  The first call of a plan makes the three planes of one image; a batched call on groups of g images
+// grows it to 1 + 2 g planes on its first use.  The new block is had before the old one is let go: on FDR_ERR_ALLOC the plan and the
+// workspace it had stay as they were.  Plane order: u_0, wgt, dw_0, then u_k, dw_k for k = 1 .. g - 1.
+int ensure_rlfree_workspace(fdr_plan* p, const char* fn, int group) {
+    if (p->rf_block && p->rf_group >= group) return FDR_OK;
     const size_t P = (size_t)p->M * p->N;
     const size_t n_part = 2 * (size_t)rlfree_partials(p->M, p->N) + 2;
+    const size_t planes = 1 + 2 * (size_t)group;
     char* blk = nullptr;
-    if (hipMalloc((void**)&blk, 3 * P * sizeof(float) + n_part * sizeof(double)) != hipSuccess) {
+    if (hipMalloc((void**)&blk, planes * P * sizeof(float) + (size_t)group * n_part * sizeof(double)) != hipSuccess) {
         (void)hipGetLastError();
         return fail(FDR_ERR_ALLOC, std::string(fn) + ": hipMalloc of the free-boundary workspace failed");
     }
-    float* planes = reinterpret_cast<float*>(blk);
+    if (p->rf_block) (void)hipFree(p->rf_block);  // (waits for the device: nothing queued still uses it)
+    float* base = reinterpret_cast<float*>(blk);
     p->rf_block = blk;
-    p->rf_u = planes;
-    p->rf_wgt = planes + P;
-    p->rf_dw = planes + 2 * P;
-    p->rf_part = reinterpret_cast<double*>(planes + 3 * P);  // 12 P bytes in: a multiple of 8 (P >= 256)
+    p->rf_group = group;
+    p->rf_u = base;
+    p->rf_wgt = base + P;
+    p->rf_dw = base + 2 * P;
+    p->rf_part = reinterpret_cast<double*>(base + planes * P);  // a multiple of 8 bytes in (P >= 256)
     return FDR_OK;
 }
+float* rlfree_u_plane(const fdr_plan* p, int k) { return k == 0 ? p->rf_u : p->rf_u + (size_t)(1 + 2 * k) * p->M * p->N; }
+float* rlfree_dw_plane(const fdr_plan* p, int k) { return k == 0 ? p->rf_dw : p->rf_u + (size_t)(2 + 2 * k) * p->M * p->N; }
+double* rlfree_part(const fdr_plan* p, int k) { return p->rf_part + (size_t)k * (2 * (size_t)rlfree_partials(p->M, p->N) + 2); }
 
 bool spans_overlap(const float* a, int a_stride, int a_rows, int a_cols, const float* b, int b_stride, int b_rows, int b_cols) {
     const uintptr_t a0 = (uintptr_t)a, a1 = a0 + ((size_t)(a_rows - 1) * a_stride + a_cols) * sizeof(float);
@@ -115,6 +124,37 @@ int rlfree_begin(fdr_plan* p, const float* d_img, int rows, int cols, int stride
     return FDR_OK;
 }
 
+// The pieces of rlfree_begin for a batch, which computes the coverage once and starts every image from it.  setup: dw and W = pad(m)
+// dense into `dw` and `W`, the two sums behind the partials at `part`; returns where the device holds (sum dw, sum W).
+int rlfree_setup_image(fdr_plan* p, const float* d_img, int rows, int cols, int stride, const float* d_w, int wstride, float* dw, float* W,
+                       double* part, const double** sums, hipStream_t s) {
+    ScopedPass t(p, s, kPassRfSetup);
+    FDR_HIP(launch_rlfree_setup(d_img, stride, d_w, wstride, rows, cols, dw, W, part, s));
+    *sums = part + 2 * (size_t)rlfree_partials(rows, cols);
+    return FDR_OK;
+}
+// start: the M x N plane `alpha` becomes alpha > sigma ? 1 / alpha : 0 and u = alpha > sigma ? sum dw / sum W : 0
+int rlfree_start_image(fdr_plan* p, float* alpha, float* u, float sigma, const double* sums, hipStream_t s) {
+    ScopedPass t(p, s, kPassRfStart);
+    FDR_HIP(launch_rlfree_start(alpha, u, (size_t)p->M * p->N, sigma, sums, s));
+    return FDR_OK;
+}
+
+// rlfree_step for a group of n images on the slots ws[0 .. n), in place on the dense M x N estimates us[k]; dws[k] dense rows x cols;
+// wgt is the one plane of the call
+int rlfree_step_n(fdr_plan* p, fdr_plan::Slot* const* ws, int n, float* const* us, const float* const* dws, int rows, int cols, hipStream_t s) {
+    const int M = p->M, N = p->N;
+    float* r[kMaxGroup];
+    for (int k = 0; k < n; ++k) r[k] = ws[k]->raw;
+    int rc = op_rows_fwd_n(p, ws, n, us, M, N, N, s);
+    if (rc == FDR_OK) rc = op_cols_n(p, ws, n, false, s);
+    if (rc == FDR_OK) rc = op_rows_inv_n(p, ws, n, ROW_OUT_RL_RATIO, kPassRfRatio, dws, cols, nullptr, r, cols, rows, cols, s);
+    if (rc == FDR_OK) rc = op_rows_fwd_n(p, ws, n, r, rows, cols, cols, s);
+    if (rc == FDR_OK) rc = op_cols_n(p, ws, n, true, s);
+    if (rc == FDR_OK) rc = op_rows_inv_n(p, ws, n, ROW_OUT_RL_UPDATE_W, kPassRfUpdate, us, N, p->rf_wgt, us, N, M, N, s);
+    return rc;
+}
+
 // finish: the output window of the dense M x N estimate u, cropped or normalised, into d_out
 int rlfree_finish(fdr_plan* p, const char* fn, const float* u, float* d_out, int out_stride, const fdr_rlfree_params& prm, hipStream_t s) {
     if (prm.norm_area == FDR_NORM_NONE) {
@@ -147,6 +187,20 @@ int rlfree_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, i
     if (rc != FDR_OK) return rc;
     return rlfree_finish(p, fn, u, d_out, out_stride, prm, s);
 }
+
+}  // namespace
+
+namespace fdr {
+
+// the driver of fdr_richardson_lucy_free_f32_dev on a checked call with its workspace (a batch with groups of one is the loop of these)
+int rlfree_plain_dev(fdr_plan* p, const char* fn, const float* d_img, int rows, int cols, int stride, const float* d_w, int wstride, float* d_out,
+                     int out_stride, const fdr_rlfree_params& prm, hipStream_t s) {
+    return rlfree_dev_impl(p, fn, d_img, rows, cols, stride, d_w, wstride, d_out, out_stride, prm, false, nullptr, s);
+}
+
+}  // namespace fdr
+
+namespace {
 
 // the checks, the device, the workspaces and the driver of the four entry points; the accelerated ones also refuse alphas that
 // overlap a window

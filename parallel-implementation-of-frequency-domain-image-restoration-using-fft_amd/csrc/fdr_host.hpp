@@ -143,8 +143,11 @@ struct fdr_plan {
     std::vector<double> mo_trig_host;
     // free-boundary Richardson-Lucy (fdr_richardson_lucy_free_f32*): made by the first such call, kept until fdr_plan_destroy -- one
     // allocation holding three M x N real planes (the estimate u, wgt = 1 / coverage, dw = weights . max(d, 0) on the window) and the
-    // 2 rlfree_partials(M, N) + 2 double partials of the two sums (r lives in slot 0's `raw`)
+    // 2 rlfree_partials(M, N) + 2 double partials of the two sums (r lives in slot 0's `raw`).  A batched call on groups of g images
+    // (fdr_richardson_lucy_batch_f32*) grows it to 1 + 2 g planes and g sets of partials: rf_group = the images it holds
+    // (ensure_rlfree_workspace; rlfree_u_plane, rlfree_dw_plane, rlfree_part for image k > 0)
     void* rf_block = nullptr;
+    int rf_group = 0;
     float *rf_u = nullptr, *rf_wgt = nullptr, *rf_dw = nullptr;
     double* rf_part = nullptr;
     // accelerated Richardson-Lucy, both forms (fdr_richardson_lucy_accel_f32*, fdr_richardson_lucy_free_accel_f32*): made by the
@@ -334,6 +337,17 @@ int op_rows_inv(fdr_plan* p, RowOut kind, const char* name, const float* src, in
                 hipStream_t s, const RlFit* fit = nullptr);
 // pass B' on H / (M N), or with `adjoint` on conj(H) / (M N)
 int op_cols(fdr_plan* p, bool adjoint, hipStream_t s);
+// The same passes for a group of n >= 1 images on the slots ws[0 .. n) with per-image pointers (blockIdx.y = image; n = 1 is the
+// single-image launch): pass A keeps FDR_PAD_ZERO, pass B' reads the table once for the group, pass C takes the four kinds
+// ROW_OUT_BLUR, _RL_RATIO, _RL_UPDATE and _RL_UPDATE_W (src2: the one wgt plane of the group).  An image comes out with the bits
+// it gets alone.
+int op_rows_fwd_n(fdr_plan* p, fdr_plan::Slot* const* ws, int n, const float* const* xs, int rows, int cols, int stride, hipStream_t s);
+int op_cols_table_n(fdr_plan* p, fdr_plan::Slot* const* ws, int n, const float2* table, const char* name, hipStream_t s);
+int op_rows_inv_n(fdr_plan* p, fdr_plan::Slot* const* ws, int n, RowOut kind, const char* name, const float* const* srcs, int src_stride,
+                  const float* src2, float* const* outs, int out_stride, int rows, int cols, hipStream_t s, const RlFit* fit = nullptr);
+int op_cols_n(fdr_plan* p, fdr_plan::Slot* const* ws, int n, bool adjoint, hipStream_t s);
+int blur_window_dev_n(fdr_plan* p, fdr_plan::Slot* const* ws, int n, const float* const* d_imgs, int rows, int cols, int stride,
+                      float* const* d_outs, int out_stride, int adjoint, hipStream_t s);
 // blur (adjoint != 0: blur^T) of the window rows x cols of d_img; the window out_rows x out_cols of the result into d_out
 int blur_window_dev(fdr_plan* p, const float* d_img, int rows, int cols, int stride, float* d_out, int out_stride, int out_rows, int out_cols,
                     int adjoint, hipStream_t s);
@@ -351,7 +365,24 @@ int rl_step(fdr_plan* p, const float* d_img, int stride, const float* y, int ys,
 int rl_init_estimate(fdr_plan* p, const float* d_img, int rows, int cols, int stride, float* u, int us, hipStream_t s);
 int rl_normalize(fdr_plan* p, const char* fn, const float* fin, int fs, int rows, int cols, int norm_area, float* d_out, int out_stride,
                  hipStream_t s);
-int ensure_rlfree_workspace(fdr_plan* p, const char* fn);
+// one step of either form for a group of n images on the slots ws[0 .. n) (fdr_api_rlbatch.hip): the six launches of rl_step /
+// rlfree_step, each over the group
+int rl_step_n(fdr_plan* p, fdr_plan::Slot* const* ws, int n, const float* const* d_imgs, int stride, const float* const* ys, int ystride,
+              float* const* outs, int os, int rows, int cols, hipStream_t s);
+int rlfree_step_n(fdr_plan* p, fdr_plan::Slot* const* ws, int n, float* const* us, const float* const* dws, int rows, int cols, hipStream_t s);
+// the drivers of fdr_richardson_lucy_f32_dev and fdr_richardson_lucy_free_f32_dev on a checked call
+int rl_plain_dev(fdr_plan* p, const char* fn, const float* d_img, int rows, int cols, int stride, float* d_out, int out_stride, int iterations,
+                 int norm_area, hipStream_t s);
+int rlfree_plain_dev(fdr_plan* p, const char* fn, const float* d_img, int rows, int cols, int stride, const float* d_w, int wstride, float* d_out,
+                     int out_stride, const fdr_rlfree_params& prm, hipStream_t s);
+// the free-boundary workspace for `group` images (1 + 2 group planes); FDR_ERR_ALLOC leaves the plan and the workspace it had intact
+int ensure_rlfree_workspace(fdr_plan* p, const char* fn, int group = 1);
+float* rlfree_u_plane(const fdr_plan* p, int k);    // image k of a group: its dense M x N estimate,
+float* rlfree_dw_plane(const fdr_plan* p, int k);   // its dw
+double* rlfree_part(const fdr_plan* p, int k);      // and the partials of its sums
+int rlfree_setup_image(fdr_plan* p, const float* d_img, int rows, int cols, int stride, const float* d_w, int wstride, float* dw, float* W,
+                       double* part, const double** sums, hipStream_t s);
+int rlfree_start_image(fdr_plan* p, float* alpha, float* u, float sigma, const double* sums, hipStream_t s);
 bool spans_overlap(const float* a, int a_stride, int a_rows, int a_cols, const float* b, int b_stride, int b_rows, int b_cols);
 int rlfree_check(const fdr_plan* p, const char* fn, const float* img, int rows, int cols, int stride, const float* weights, int wstride,
                  const float* out, int out_stride, const fdr_rlfree_params* prm, PlanNeed need = NEED_OPERATOR_PSF);

@@ -15,13 +15,14 @@ enum RowOut {
     ROW_OUT_REAL_MINMAX = 1,  // pass C': real plane + min/max partials
     ROW_OUT_MINMAX_ONLY = 2,  // pass C1 (two-sweep normalisation): min/max partials, nothing stored
     ROW_OUT_NORMALIZED = 3,   // pass C2: the transform again, normalised with the folded partials and cropped on store
-    // the blur operator and Richardson-Lucy (fdr_rl.hip; half-spectrum rows of 32 points and more, one image): cropped to the
-    // window out_rows x out_cols on store (row stride out_stride), no min/max
+    // the blur operator and Richardson-Lucy (fdr_rl.hip; half-spectrum rows of 32 points and more): cropped to the
+    // window out_rows x out_cols on store (row stride out_stride), no min/max.  A group of images (batch.nimg > 1) takes spec[], out[]
+    // and, for the kinds that read it, src_real[] from the batch block; ROW_OUT_RL_RATIO_STAT is one image per launch
     ROW_OUT_BLUR = 4,         // the value to `out`
     ROW_OUT_RL_RATIO = 5,     // r = c > kRlTau ? max(d, 0) / c : 0 to `out`; d read from src_real (row stride src_stride)
     ROW_OUT_RL_UPDATE = 6,    // max(u g, 0) to `out`; u read from src_real (row stride src_stride; may be `out` itself)
     // free-boundary Richardson-Lucy (fdr_rlfree.hip): max(u wgt g, 0) to `out`; u from src_real as ROW_OUT_RL_UPDATE, wgt from
-    // src_real2 (same row stride)
+    // src_real2 (same row stride; one plane for every image of a group)
     ROW_OUT_RL_UPDATE_W = 7,
     // the ratio that also measures the fit (fdr_rlstop.hip): d from src_real, the pixel's weight w from src_real2 (same row stride;
     // null: w = 1); r = c > kRlTau ? (w max(d, 0)) / c : 0 to `out` -- the bits of ROW_OUT_RL_RATIO on d (w = 1) or on dw = w max(d, 0)
@@ -54,11 +55,11 @@ __host__ __device__ __forceinline__ P pick_image(P const (&p)[kMaxGroup], int i)
     return i < 4 ? lo : hi;
 }
 struct RowBatch {
-    const float* src_real[kMaxGroup];  // pass A input
+    const float* src_real[kMaxGroup];  // pass A input; operator kinds of the inverse pass: the real source (d, dw or u)
     float2* spec[kMaxGroup];           // pass A output / pass C' input (panel-major spectrum)
     float* raw[kMaxGroup];             // pass C' output
     float2* mm_part[kMaxGroup];        // pass C' min/max partials
-    float* out[kMaxGroup];             // pass C2 output (normalised, cropped)
+    float* out[kMaxGroup];             // pass C2 output (normalised, cropped); operator kinds: the cropped result
     int nimg;
 };
 struct NormBatch {

@@ -70,7 +70,8 @@ static inline bool rows4_use_split(int logl, int M, int nimg, int half) {
 constexpr bool row_out_stores_raw(RowOut o) { return o == ROW_OUT_REAL_MINMAX; }                              // the raw real plane
 constexpr bool row_out_minmax(RowOut o) { return o == ROW_OUT_REAL_MINMAX || o == ROW_OUT_MINMAX_ONLY; }      // min/max partials
 constexpr bool row_out_normalizes(RowOut o) { return o == ROW_OUT_NORMALIZED; }  // folds the partials, scales and shifts on store
-constexpr bool row_out_operator(RowOut o) { return o >= ROW_OUT_BLUR; }          // half spectrum, >= 32 points, one image, cropped
+constexpr bool row_out_operator(RowOut o) { return o >= ROW_OUT_BLUR; }          // half spectrum, >= 32 points, cropped
+constexpr bool row_out_operator_group(RowOut o) { return row_out_operator(o) && o != ROW_OUT_RL_RATIO_STAT; }  // ... takes a group of images
 constexpr bool row_out_reads_src(RowOut o) { return row_out_operator(o) && o != ROW_OUT_BLUR; }               // src_real
 constexpr bool row_out_reads_src2(RowOut o) { return o == ROW_OUT_RL_UPDATE_W; }                              // src_real2 as well
 constexpr bool row_out_fit_sums(RowOut o) { return o == ROW_OUT_RL_RATIO_STAT; }  // src_real2 when not null, (res, kl) partials
@@ -974,7 +975,8 @@ __device__ __forceinline__ void rows4_inv_epilogue(const RowArgs& a, const int r
     }
 }
 
-// The operator kinds of the inverse row passes (the blur / Richardson-Lucy calls of fdr_rl.hip, one image at a time), the
+// The operator kinds of the inverse row passes (the blur / Richardson-Lucy calls of fdr_rl.hip; a group of images per launch for all
+// but ROW_OUT_RL_RATIO_STAT, each image with its own src_real and out and the bits it gets alone), the
 // value v of the inverse transform at (r, n) of the window out_rows x out_cols, src = src_real + r src_stride + n:
 //   ROW_OUT_BLUR        : v
 //   ROW_OUT_RL_RATIO    : v > kRlTau ? max(d, 0) / v : 0, d = *src (the input image)
@@ -1074,6 +1076,10 @@ __global__ __launch_bounds__((Rows4PackGeom<LOGL, true>::THREADS), (HALF ? Rows4
         if constexpr (row_out_stores_raw(OUT)) a.dst_real = pick_image(a0.batch.raw, blockIdx.y);
         if constexpr (row_out_normalizes(OUT)) a.out = pick_image(a0.batch.out, blockIdx.y);
         a.mm_part = pick_image(a0.batch.mm_part, blockIdx.y);
+        if constexpr (row_out_operator_group(OUT)) {  // its own real source (d, dw or u) and destination; src_real2 (wgt) is the group's
+            a.out = pick_image(a0.batch.out, blockIdx.y);
+            if constexpr (row_out_reads_src(OUT)) a.src_real = pick_image(a0.batch.src_real, blockIdx.y);
+        }
     }
     float fscale = 0.f, fshift = 0.f;
     using Geo = Rows4PackGeom<LOGL, true>;
@@ -1238,7 +1244,7 @@ __global__ __launch_bounds__((RowsSplitGeom<LOGL, true>::THREADS)) void fft_rows
 }
 
 // One inverse row pass of kind OUT.  The guards: ROW_OUT_REAL_MINMAX alone has a full-spectrum form; the operator kinds take rows of
-// 32 points and more and one image per launch.
+// 32 points and more, and ROW_OUT_RL_RATIO_STAT (one pair of fit sums per launch) one image per launch.
 template <int LOGL, RowOut OUT>
 static hipError_t launch_rows4_inv_kind(const RowArgs& a, const float2* tw, hipStream_t s) {
     using Geo = Rows4PackGeom<LOGL, true>;
@@ -1254,7 +1260,7 @@ static hipError_t launch_rows4_inv_kind(const RowArgs& a, const float2* tw, hipS
     if constexpr (row_out_operator(OUT) && LOGL < 5) {
         return hipErrorInvalidValue;
     } else {
-        if (row_out_operator(OUT) && nimg > 1) return hipErrorInvalidValue;
+        if (row_out_operator(OUT) && !row_out_operator_group(OUT) && nimg > 1) return hipErrorInvalidValue;
         if (a.half) hipLaunchKernelGGL((fft_rows4_inv_packed_kernel<LOGL, true, OUT>), grid, block, 0, s, a, tw);
         else if constexpr (row_out_stores_raw(OUT)) hipLaunchKernelGGL((fft_rows4_inv_packed_kernel<LOGL, false, OUT>), grid, block, 0, s, a, tw);
         else return hipErrorInvalidValue;  // half-spectrum path only
