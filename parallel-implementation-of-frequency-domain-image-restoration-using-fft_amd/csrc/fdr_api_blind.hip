@@ -1,8 +1,8 @@
 // fdr_api_blind.hip -- blind Richardson-Lucy, both forms (fdr_richardson_lucy_blind_f32*; kernels in fdr_blind.hip), and the
-// Gaussian PSF: the workspace, the checks, the driver and the entry points.  The image step is rl_step / rlfree_step unchanged; the
-// PSF step hangs on the two hooks of a step (RlHooks): the table conj(U_k) / (M N) from the row spectra of u_k, then, from the
-// same r, corr_(u_k) through pass A, pass B' on that table and pass C cropped to the PSF; after the step the projection and the
-// operator tables of p_(k+1).
+// Gaussian PSF: the workspace, the checks, the hooks and the entry points.  The image iterations are the form's own driver
+// (rl_group_dev, rlfree_batch_dev, one image); the PSF step hangs on its three hooks (RlHooks), from iteration psf_hold on: the
+// table conj(U_k) / (M N) from the row spectra of u_k, then, from the same r, corr_(u_k) through pass A, pass B' on that table and
+// pass C cropped to the PSF; after the step the projection, the operator tables of p_(k+1) and (free form) its coverage.
 #include "fdr_host.hpp"
 
 #include <cmath>
@@ -66,25 +66,25 @@ int blind_check(const fdr_plan* p, const char* fn, const float* img, int rows, i
         orows = prm->out_rows; ocols = prm->out_cols;
     } else {
         rc = rl_check(p, fn, img, rows, cols, stride, out, out_stride, prm->iterations, prm->norm_area, NEED_OPERATOR);
-        if (rc == FDR_OK && weights) return fail(FDR_ERR_ARG, std::string(fn) + ": the plain form takes no weights");
-        if (rc == FDR_OK && !((prm->out_rows == 0 && prm->out_cols == 0) || (prm->out_rows == rows && prm->out_cols == cols)))
-            return fail(FDR_ERR_ARG, std::string(fn) + ": the plain form's output window is the input's (out_rows, out_cols = 0 or rows, cols)");
+        if (rc == FDR_OK)
+            rc = plain_form_check(fn, weights, rows, cols, prm->out_rows, prm->out_cols, false,
+                                  ": the plain form's output window is the input's (out_rows, out_cols = 0 or rows, cols)");
     }
     if (rc != FDR_OK) return rc;
     if (prm->psf_hold < 0) return fail(FDR_ERR_ARG, std::string(fn) + ": psf_hold < 0");
     if (prows <= 0 || pcols <= 0 || pstride < pcols) return fail(FDR_ERR_ARG, std::string(fn) + ": bad PSF shape");
     if (prows > p->M || pcols > p->N) return fail(FDR_ERR_ARG, std::string(fn) + ": PSF larger than the padded image");
     if ((size_t)prows * pcols > (size_t)kBlindMaxPsf) return fail(FDR_ERR_ARG, std::string(fn) + ": a PSF of more than 65536 entries");
-    if (spans_overlap(psf, pstride, prows, pcols, img, stride, rows, cols)) return fail(FDR_ERR_ARG, std::string(fn) + ": the PSF overlaps the input");
-    if (weights && spans_overlap(psf, pstride, prows, pcols, weights, wstride, rows, cols))
-        return fail(FDR_ERR_ARG, std::string(fn) + ": the PSF overlaps the weights");
-    if (spans_overlap(psf, pstride, prows, pcols, out, out_stride, orows, ocols)) return fail(FDR_ERR_ARG, std::string(fn) + ": the PSF overlaps the output");
+    const ByteRange f = window_range(psf, prows, pcols, pstride);
+    if (ranges_overlap(f, window_range(img, rows, cols, stride))) return fail(FDR_ERR_ARG, std::string(fn) + ": the PSF overlaps the input");
+    if (weights && ranges_overlap(f, window_range(weights, rows, cols, wstride))) return fail(FDR_ERR_ARG, std::string(fn) + ": the PSF overlaps the weights");
+    if (ranges_overlap(f, window_range(out, orows, ocols, out_stride))) return fail(FDR_ERR_ARG, std::string(fn) + ": the PSF overlaps the output");
     return FDR_OK;
 }
 
-// the PSF step's share of a step, and what follows the step
+// the PSF step's share of an iteration: what the three hooks run
 struct BlindStep {
-    fdr_plan* p; int rows, cols, prows, pcols; bool free_form; hipStream_t s;
+    fdr_plan* p; int rows, cols, prows, pcols; bool free_form; float sigma; hipStream_t s;
     // the table of the image: slot 0 holds the row spectra of u_k (`nrows` of them are not zero); they are only read
     int table(int nrows) const {
         ScopedPass t(p, s, kPassBlTable);
@@ -105,60 +105,44 @@ struct BlindStep {
         if (rc == FDR_OK && free_form) rc = corr(p->bl_w, p->bl_den);
         return rc;
     }
-    // p_(k+1) and its operator tables; the PSF also to `out` (row stride ostride) when that is not null
-    int project(float* out, int ostride) const {
+    // p_(k+1) and its operator tables; after the last step the PSF also to `out` (row stride ostride), before it (free form) the
+    // coverage of p_(k+1)
+    int after_step(bool last, float* out, int ostride) const {
         {
             ScopedPass t(p, s, kPassBlPsf);
-            FDR_HIP(launch_blind_psf_project(p->bl_p, p->bl_num, free_form ? p->bl_den : nullptr, prows, pcols, p->bl_status, out, ostride, s));
+            FDR_HIP(launch_blind_psf_project(p->bl_p, p->bl_num, free_form ? p->bl_den : nullptr, prows, pcols, p->bl_status, last ? out : nullptr,
+                                             ostride, s));
         }
-        return set_operator_psf_impl(p, p->bl_p, prows, pcols, pcols, s);
+        int rc = set_operator_psf_impl(p, p->bl_p, prows, pcols, pcols, s);
+        if (rc != FDR_OK || last || !free_form) return rc;
+        rc = blur_window_dev(p, p->bl_w, rows, cols, cols, p->rf_wgt, p->N, p->M, p->N, 1, s);
+        if (rc != FDR_OK) return rc;
+        ScopedPass t(p, s, kPassBlPsf);
+        FDR_HIP(launch_blind_wgt(p->rf_wgt, (size_t)p->M * p->N, sigma, s));
+        return FDR_OK;
     }
 };
 
+// the start PSF and its operator tables, the hooks, the form's driver on one image
 int blind_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, int cols, int stride, const float* d_w, int wstride, float* d_psf,
                    int prows, int pcols, int pstride, float* d_out, int out_stride, const fdr_blind_params& prm, hipStream_t s) {
-    const int M = p->M, N = p->N, n = prm.iterations;
+    const int n = prm.iterations, hold = prm.psf_hold;
     const bool free_form = prm.free_boundary != 0;
-    const BlindStep bs{p, rows, cols, prows, pcols, free_form, s};
+    const BlindStep bs{p, rows, cols, prows, pcols, free_form, prm.cov_sigma, s};
     {
         ScopedPass t(p, s, kPassBlPsf);
         FDR_HIP(launch_blind_psf_start(d_psf, prows, pcols, pstride, p->bl_p, p->bl_status, s));
     }
-    int rc = set_operator_psf_impl(p, p->bl_p, prows, pcols, pcols, s);
+    const int rc = set_operator_psf_impl(p, p->bl_p, prows, pcols, pcols, s);
     if (rc != FDR_OK) return rc;
     RlHooks hooks;
-    hooks.after_fwd = [&] { return bs.table(free_form ? M : rows); };
-    hooks.after_ratio = [&] { return bs.after_ratio(); };
-    if (free_form) {
-        const fdr_rlfree_params f = free_params(prm);
-        float* u = p->rf_u;
-        rc = rlfree_begin(p, d_img, rows, cols, stride, d_w, wstride, f.sigma, p->bl_w, nullptr, s);
-        for (int it = 0; it < n && rc == FDR_OK; ++it) {
-            const bool blind = it >= prm.psf_hold, last = it == n - 1;
-            rc = rlfree_step(p, u, u, rows, cols, s, nullptr, nullptr, blind ? &hooks : nullptr);
-            if (rc != FDR_OK || !blind) continue;
-            rc = bs.project(last ? d_psf : nullptr, pstride);
-            if (rc != FDR_OK || last) continue;
-            rc = blur_window_dev(p, p->bl_w, rows, cols, cols, p->rf_wgt, N, M, N, 1, s);  // the coverage of p_(k+1)
-            if (rc != FDR_OK) continue;
-            ScopedPass t(p, s, kPassBlPsf);
-            FDR_HIP(launch_blind_wgt(p->rf_wgt, (size_t)M * N, f.sigma, s));
-        }
-        if (rc != FDR_OK) return rc;
-        return rlfree_finish(p, fn, u, d_out, out_stride, f, s);
-    }
-    // plain form: u in d_out, the last update (or, for no iterations, the start) to the raw plane when a normalisation follows
-    const bool norm = prm.norm_area != FDR_NORM_NONE;
-    float* fin = norm ? p->slots[0].raw : d_out;
-    const int fs = norm ? cols : out_stride;
-    rc = rl_init_estimate(p, d_img, rows, cols, stride, n == 0 ? fin : d_out, n == 0 ? fs : out_stride, s);
-    for (int it = 0; it < n && rc == FDR_OK; ++it) {
-        const bool blind = it >= prm.psf_hold, last = it == n - 1;
-        rc = rl_step(p, d_img, stride, d_out, out_stride, last ? fin : d_out, last ? fs : out_stride, rows, cols, s, nullptr, blind ? &hooks : nullptr);
-        if (rc == FDR_OK && blind) rc = bs.project(last ? d_psf : nullptr, pstride);
-    }
-    if (rc != FDR_OK || !norm) return rc;
-    return rl_normalize(p, fn, fin, fs, rows, cols, prm.norm_area, d_out, out_stride, s);
+    hooks.after_fwd = [&](int it) { return it < hold ? FDR_OK : bs.table(free_form ? p->M : rows); };
+    hooks.after_ratio = [&](int it) { return it < hold ? FDR_OK : bs.after_ratio(); };
+    hooks.after_step = [&](int it) { return it < hold ? FDR_OK : bs.after_step(it == n - 1, d_psf, pstride); };
+    if (free_form)
+        return rlfree_batch_dev(p, fn, d_img, 0, 1, rows, cols, stride, d_w, wstride, d_out, 0, out_stride, free_params(prm), s, &hooks, p->bl_w);
+    fdr_plan::Slot* w = &p->slots[0];
+    return rl_group_dev(p, fn, &w, 1, &d_img, rows, cols, stride, &d_out, out_stride, n, prm.norm_area, s, &hooks);
 }
 
 // the start PSF of the host form, as fdr.h states it: no negative entry, a finite sum > 0
@@ -213,9 +197,8 @@ int fdr_richardson_lucy_blind_f32(fdr_plan* p, const float* img_host, int rows, 
     if (rc != FDR_OK) return rc;
     const size_t pw = (size_t)pcols * sizeof(float);
     FDR_HIP(hipMemcpy2D(p->bl_stage, pw, psf_host, (size_t)pstride * sizeof(float), pw, (size_t)prows, hipMemcpyHostToDevice));
-    if (free_form && weights_host)  // staged dense into u's plane, where the setup pass leaves W anyway
-        FDR_HIP(hipMemcpy2D(p->rf_u, (size_t)cols * sizeof(float), weights_host, (size_t)wstride * sizeof(float), (size_t)cols * sizeof(float),
-                            (size_t)rows, hipMemcpyHostToDevice));
+    if (free_form && weights_host) rc = stage_weights(p, weights_host, rows, cols, wstride);
+    if (rc != FDR_OK) return rc;
     const int orows = free_form ? prm.out_rows : rows, ocols = free_form ? prm.out_cols : cols;
     rc = host_image_call(p, fn, img_host, rows, cols, stride, out_host, orows, ocols, out_stride, [&](const float* d_in, float* d_out) {
         return blind_dev_impl(p, fn, d_in, rows, cols, cols, free_form && weights_host ? p->rf_u : nullptr, cols, p->bl_stage, prows, pcols,

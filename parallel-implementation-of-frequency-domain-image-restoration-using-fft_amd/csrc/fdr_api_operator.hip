@@ -1,13 +1,9 @@
-// fdr_api_operator.hip -- the blur operator and Richardson-Lucy, plain and accelerated (fdr_rl.hip, fdr_rlaccel.hip): passes A, B'
-// and C of the fast half-spectrum path with the operator tables in place of W and the operator kinds of the inverse row pass;
-// their PSF setters and entry points.
+// fdr_api_operator.hip -- the blur operator: passes A, B' and C of the fast half-spectrum path with the operator tables in place of
+// W and the operator kinds of the inverse row pass, for a group of images; the PSF setters, the min-max normalisation of a window
+// and the entry points of the blur.  Richardson-Lucy on these passes: fdr_api_rl.hip (plain form), fdr_api_rlfree.hip.
 #include "fdr_host.hpp"
 
-#include <cstdint>
-
 using namespace fdr;
-
-static_assert(kRlTau == FDR_RL_TAU, "the ratio guard of the kernels is FDR_RL_TAU");
 
 namespace {
 
@@ -19,11 +15,6 @@ const char* const kPassOpRowsFwdN = "A op rows: pad+FFT (blur / RL), group";
 const char* const kPassOpColsH = "B' op cols: FFT*H*IFFT";
 const char* const kPassOpColsConj = "B' op cols: FFT*conj(H)*IFFT";
 const char* const kPassOpRowsBlur = "C op rows: IFFT+crop (blur)";
-const char* const kPassRlInit = "RL init: u = max(d, 0)";
-const char* const kPassRlRatio = "C op rows: IFFT+RL ratio";
-const char* const kPassRlRatioFit = "C op rows: IFFT+RL ratio+fit";
-const char* const kPassRlUpdate = "C op rows: IFFT+RL update";
-const char* const kPassRlNorm = "E RL minmax+normalize";
 
 }  // namespace
 
@@ -120,9 +111,9 @@ int op_cols_table(fdr_plan* p, const float2* table, const char* name, hipStream_
     return op_cols_table_n(p, &w, 1, table, name, s);
 }
 int op_rows_inv(fdr_plan* p, RowOut kind, const char* name, const float* src, int src_stride, float* out, int out_stride, int rows,
-                int cols, hipStream_t s, const RlFit* fit) {
+                int cols, hipStream_t s) {
     fdr_plan::Slot* w = &p->slots[0];
-    return op_rows_inv_n(p, &w, 1, kind, name, &src, src_stride, nullptr, &out, out_stride, rows, cols, s, fit);
+    return op_rows_inv_n(p, &w, 1, kind, name, &src, src_stride, nullptr, &out, out_stride, rows, cols, s);
 }
 
 // min-max to [0, 1] over the window; FDR_NORM_PADDED also counts the zeros outside it (one extra (0, 0) partial)
@@ -143,23 +134,7 @@ int normalize_window(fdr_plan* p, const char* fn, const char* name, const float*
     return FDR_OK;
 }
 
-// the start of the plain form: u = max(d, 0) on the window
-int rl_init_estimate(fdr_plan* p, const float* d_img, int rows, int cols, int stride, float* u, int us, hipStream_t s) {
-    ScopedPass t(p, s, kPassRlInit);
-    FDR_HIP(launch_rl_init(d_img, rows, cols, stride, u, us, s));
-    return FDR_OK;
-}
-// the normalisation that ends a plain-form call
-int rl_normalize(fdr_plan* p, const char* fn, const float* fin, int fs, int rows, int cols, int norm_area, float* d_out, int out_stride,
-                 hipStream_t s) {
-    return normalize_window(p, fn, kPassRlNorm, fin, fs, rows, cols, norm_area, d_out, out_stride, s);
-}
-
 // pass B' on one of the operator tables
-int op_cols(fdr_plan* p, bool adjoint, hipStream_t s) {
-    return op_cols_table(p, adjoint ? p->op_c : p->op_h, adjoint ? kPassOpColsConj : kPassOpColsH, s);
-}
-
 int op_cols_n(fdr_plan* p, fdr_plan::Slot* const* ws, int n, bool adjoint, hipStream_t s) {
     return op_cols_table_n(p, ws, n, adjoint ? p->op_c : p->op_h, adjoint ? kPassOpColsConj : kPassOpColsH, s);
 }
@@ -168,7 +143,8 @@ int op_cols_n(fdr_plan* p, fdr_plan::Slot* const* ws, int n, bool adjoint, hipSt
 int blur_window_dev(fdr_plan* p, const float* d_img, int rows, int cols, int stride, float* d_out, int out_stride, int out_rows, int out_cols,
                     int adjoint, hipStream_t s) {
     int rc = op_rows_fwd(p, d_img, rows, cols, stride, s);
-    if (rc == FDR_OK) rc = op_cols(p, adjoint != 0, s);
+    fdr_plan::Slot* w = &p->slots[0];
+    if (rc == FDR_OK) rc = op_cols_n(p, &w, 1, adjoint != 0, s);
     if (rc == FDR_OK) rc = op_rows_inv(p, ROW_OUT_BLUR, kPassOpRowsBlur, nullptr, 0, d_out, out_stride, out_rows, out_cols, s);
     return rc;
 }
@@ -182,145 +158,7 @@ int blur_window_dev_n(fdr_plan* p, fdr_plan::Slot* const* ws, int n, const float
     return rc;
 }
 
-namespace {
-
-// [lo, hi) of the elements a rows x cols window with row stride `stride` spans
-bool windows_overlap(const float* a, int a_stride, const float* b, int b_stride, int rows, int cols) {
-    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + ((size_t)(rows - 1) * a_stride + cols) * sizeof(float);
-    const uintptr_t b0 = (uintptr_t)b, b1 = b0 + ((size_t)(rows - 1) * b_stride + cols) * sizeof(float);
-    return a0 < b1 && b0 < a1;
-}
-
-}  // namespace
-
-// everything a Richardson-Lucy call refuses: plan, operator PSF and window, the iteration count, the normalisation, an output
-// that overlaps the input (the input is read on every iteration)
-int rl_check(const fdr_plan* p, const char* fn, const float* img, int rows, int cols, int stride, const float* out, int out_stride,
-             int iterations, int norm_area, PlanNeed need) {
-    const int rc = check_window(p, fn, need, rows, cols, stride, out_stride);
-    if (rc != FDR_OK) return rc;
-    if (iterations < 0) return fail(FDR_ERR_ARG, std::string(fn) + ": iterations < 0");
-    if (norm_area != FDR_NORM_NONE && norm_area != FDR_NORM_CROPPED && norm_area != FDR_NORM_PADDED)
-        return fail(FDR_ERR_ARG, std::string(fn) + ": unknown norm_area");
-    if (windows_overlap(img, stride, out, out_stride, rows, cols))
-        return fail(FDR_ERR_ARG, std::string(fn) + ": the output overlaps the input (the input is read on every iteration)");
-    return FDR_OK;
-}
-
-// one iteration: c = blur(y), r = d+ / c into the window of the raw plane (row stride cols), out = max(y . blur^T(r), 0); `out` may
-// be y itself.  With `fit` the ratio pass is the kind that also leaves the fit partials of c (the same r).
-int rl_step(fdr_plan* p, const float* d_img, int stride, const float* y, int ys, float* out, int os, int rows, int cols, hipStream_t s,
-            const RlFit* fit, const RlHooks* hooks) {
-    float* r = p->slots[0].raw;
-    const int rs = cols;
-    int rc = op_rows_fwd(p, y, rows, cols, ys, s);                                                    // c = blur(y) ...
-    if (rc == FDR_OK && hooks) rc = hooks->after_fwd();
-    if (rc == FDR_OK) rc = op_cols(p, false, s);
-    if (rc == FDR_OK)                                                                                 // ... r = d+ / c
-        rc = op_rows_inv(p, fit ? ROW_OUT_RL_RATIO_STAT : ROW_OUT_RL_RATIO, fit ? kPassRlRatioFit : kPassRlRatio, d_img, stride, r, rs, rows,
-                         cols, s, fit);
-    if (rc == FDR_OK && hooks) rc = hooks->after_ratio();
-    if (rc == FDR_OK) rc = op_rows_fwd(p, r, rows, cols, rs, s);                                      // g = blur^T(r) ...
-    if (rc == FDR_OK) rc = op_cols(p, true, s);
-    if (rc == FDR_OK) rc = op_rows_inv(p, ROW_OUT_RL_UPDATE, kPassRlUpdate, y, ys, out, os, rows, cols, s);  // ... out = max(y g, 0)
-    return rc;
-}
-
-// rl_step for a group of n images on the slots ws[0 .. n): image k's r in the window of slot k's raw plane, outs[k] may be ys[k]
-int rl_step_n(fdr_plan* p, fdr_plan::Slot* const* ws, int n, const float* const* d_imgs, int stride, const float* const* ys, int ystride,
-              float* const* outs, int os, int rows, int cols, hipStream_t s) {
-    float* r[kMaxGroup];
-    for (int k = 0; k < n; ++k) r[k] = ws[k]->raw;
-    const int rs = cols;
-    int rc = op_rows_fwd_n(p, ws, n, ys, rows, cols, ystride, s);
-    if (rc == FDR_OK) rc = op_cols_n(p, ws, n, false, s);
-    if (rc == FDR_OK) rc = op_rows_inv_n(p, ws, n, ROW_OUT_RL_RATIO, kPassRlRatio, d_imgs, stride, nullptr, r, rs, rows, cols, s);
-    if (rc == FDR_OK) rc = op_rows_fwd_n(p, ws, n, r, rows, cols, rs, s);
-    if (rc == FDR_OK) rc = op_cols_n(p, ws, n, true, s);
-    if (rc == FDR_OK) rc = op_rows_inv_n(p, ws, n, ROW_OUT_RL_UPDATE, kPassRlUpdate, ys, ystride, nullptr, outs, os, rows, cols, s);
-    return rc;
-}
-
 }  // namespace fdr
-
-namespace {
-
-// u (the estimate) lives in d_out; r in the window of the raw plane (row stride cols), the spectrum in slot 0's work.  With a
-// normalisation the last update (or, for no iterations, the initial estimate) goes to the raw plane instead, and the normalise
-// pass writes d_out from there.  Accelerated (rl_accel_loop), the estimate alternates between d_out and a plane of the acceleration
-// workspace, starting where u_n comes to lie in d_out.
-int rl_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, int cols, int stride, float* d_out, int out_stride, int iterations,
-                int norm_area, bool accel, float* d_alphas, hipStream_t s) {
-    int rc = FDR_OK;
-    const bool norm = norm_area != FDR_NORM_NONE;
-    float* fin = norm ? p->slots[0].raw : d_out;  // where the final estimate is written
-    const int fs = norm ? cols : out_stride;
-    float* const U[2] = {d_out, accel ? p->ra_u : d_out};
-    const int us[2] = {out_stride, accel ? cols : out_stride};
-    const int first = accel ? iterations & 1 : 0;
-    rc = rl_init_estimate(p, d_img, rows, cols, stride, iterations == 0 ? fin : U[first], iterations == 0 ? fs : us[first], s);
-    if (rc != FDR_OK) return rc;
-    if (accel) {
-        rc = rl_accel_loop(p, iterations, rows, cols, U, us, first, fin, fs, d_alphas, s,
-                           [&](const float* y, int ys, float* out, int os) { return rl_step(p, d_img, stride, y, ys, out, os, rows, cols, s); },
-                           nullptr);
-    } else {
-        for (int it = 0; it < iterations && rc == FDR_OK; ++it) {
-            const bool last = it == iterations - 1;
-            rc = rl_step(p, d_img, stride, d_out, out_stride, last ? fin : d_out, last ? fs : out_stride, rows, cols, s);
-        }
-    }
-    if (rc != FDR_OK || !norm) return rc;
-    return rl_normalize(p, fn, fin, fs, rows, cols, norm_area, d_out, out_stride, s);
-}
-
-}  // namespace
-
-namespace fdr {
-
-// the driver of fdr_richardson_lucy_f32_dev on a checked call (a batch with groups of one is the loop of these)
-int rl_plain_dev(fdr_plan* p, const char* fn, const float* d_img, int rows, int cols, int stride, float* d_out, int out_stride, int iterations,
-                 int norm_area, hipStream_t s) {
-    return rl_dev_impl(p, fn, d_img, rows, cols, stride, d_out, out_stride, iterations, norm_area, false, nullptr, s);
-}
-
-}  // namespace fdr
-
-namespace {
-
-// the checks, the device and the driver of the four entry points; the accelerated ones also refuse alphas that overlap a window and
-// make sure of their workspace
-int rl_dev_entry(fdr_plan* p, const char* fn, const float* d_img, int rows, int cols, int stride, float* d_out, int out_stride, int iterations,
-                 int norm_area, bool accel, float* d_alphas, hipStream_t s) {
-    if (!p || !d_img || !d_out) return null_arg(fn);
-    int rc = rl_check(p, fn, d_img, rows, cols, stride, d_out, out_stride, iterations, norm_area);
-    if (rc == FDR_OK && accel) rc = check_alphas(fn, d_alphas, iterations, d_out, out_stride, rows, cols, "output");
-    if (rc == FDR_OK && accel) rc = check_alphas(fn, d_alphas, iterations, d_img, stride, rows, cols, "input");
-    if (rc != FDR_OK) return rc;
-    FDR_HIP(hipSetDevice(p->device));
-    if (accel) rc = ensure_rlaccel_workspace(p, fn);
-    if (rc != FDR_OK) return rc;
-    return rl_dev_impl(p, fn, d_img, rows, cols, stride, d_out, out_stride, iterations, norm_area, accel, d_alphas, s);
-}
-
-int rl_host_entry(fdr_plan* p, const char* fn, const float* img_host, int rows, int cols, int stride, float* out_host, int out_stride,
-                  int iterations, int norm_area, bool accel, float* alphas_host) {
-    if (!p || !img_host || !out_host) return null_arg(fn);
-    int rc = rl_check(p, fn, img_host, rows, cols, stride, out_host, out_stride, iterations, norm_area);
-    if (rc != FDR_OK) return rc;
-    FDR_HIP(hipSetDevice(p->device));
-    if (accel) rc = ensure_rlaccel_workspace(p, fn);
-    if (rc != FDR_OK) return rc;
-    DeviceBuffer d_alphas;
-    if (accel && alphas_host && iterations > 0) FDR_ALLOC(d_alphas, (size_t)iterations * sizeof(float), fn);
-    rc = host_image_call(p, fn, img_host, rows, cols, stride, out_host, rows, cols, out_stride, [&](const float* d_in, float* d_out) {
-        return rl_dev_impl(p, fn, d_in, rows, cols, cols, d_out, cols, iterations, norm_area, accel, d_alphas.as<float>(), nullptr);
-    });
-    if (rc == FDR_OK && d_alphas.ptr) FDR_HIP(hipMemcpy(alphas_host, d_alphas.ptr, (size_t)iterations * sizeof(float), hipMemcpyDeviceToHost));
-    return rc;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -354,30 +192,6 @@ int fdr_blur_f32(fdr_plan* p, const float* img_host, int rows, int cols, int str
     return host_image_call(p, fn, img_host, rows, cols, stride, out_host, rows, cols, out_stride, [&](const float* d_in, float* d_out) {
         return blur_window_dev(p, d_in, rows, cols, cols, d_out, cols, rows, cols, adjoint, nullptr);
     });
-}
-
-int fdr_richardson_lucy_f32_dev(fdr_plan* p, const float* d_img, int rows, int cols, int stride, float* d_out, int out_stride, int iterations,
-                                int norm_area, void* stream) {
-    return rl_dev_entry(p, "fdr_richardson_lucy_f32_dev", d_img, rows, cols, stride, d_out, out_stride, iterations, norm_area, false, nullptr,
-                        (hipStream_t)stream);
-}
-
-int fdr_richardson_lucy_f32(fdr_plan* p, const float* img_host, int rows, int cols, int stride, float* out_host, int out_stride,
-                            int iterations, int norm_area) {
-    return rl_host_entry(p, "fdr_richardson_lucy_f32", img_host, rows, cols, stride, out_host, out_stride, iterations, norm_area, false,
-                         nullptr);
-}
-
-int fdr_richardson_lucy_accel_f32_dev(fdr_plan* p, const float* d_img, int rows, int cols, int stride, float* d_out, int out_stride,
-                                      int iterations, int norm_area, float* d_alphas, void* stream) {
-    return rl_dev_entry(p, "fdr_richardson_lucy_accel_f32_dev", d_img, rows, cols, stride, d_out, out_stride, iterations, norm_area, true,
-                        d_alphas, (hipStream_t)stream);
-}
-
-int fdr_richardson_lucy_accel_f32(fdr_plan* p, const float* img_host, int rows, int cols, int stride, float* out_host, int out_stride,
-                                  int iterations, int norm_area, float* alphas_host) {
-    return rl_host_entry(p, "fdr_richardson_lucy_accel_f32", img_host, rows, cols, stride, out_host, out_stride, iterations, norm_area, true,
-                         alphas_host);
 }
 
 }  // extern "C"

@@ -1,9 +1,7 @@
 // fdr_api_rlaccel.hip -- what the two accelerated Richardson-Lucy forms share (kernels in fdr_rlaccel.hip): the workspace, the
-// check of the alphas' range and the recursion around a step.  The entry points live beside their plain counterparts
-// (fdr_api_operator.hip, fdr_api_rlfree.hip), whose checks and step they use.
+// check and the host staging of the alphas and the recursion around a step.  The entry points live beside their plain counterparts
+// (fdr_api_rl.hip, fdr_api_rlfree.hip), whose checks and step they use.
 #include "fdr_host.hpp"
-
-#include <cstdint>
 
 using namespace fdr;
 
@@ -41,10 +39,18 @@ int ensure_rlaccel_workspace(fdr_plan* p, const char* fn) {
 
 int check_alphas(const char* fn, const float* d_alphas, int n, const float* w, int ws, int rows, int cols, const char* what) {
     if (!d_alphas || n <= 0) return FDR_OK;
-    const uintptr_t a0 = (uintptr_t)d_alphas, a1 = a0 + (size_t)n * sizeof(float);
-    const uintptr_t b0 = (uintptr_t)w, b1 = b0 + ((size_t)(rows - 1) * ws + cols) * sizeof(float);
-    if (a0 < b1 && b0 < a1) return fail(FDR_ERR_ARG, std::string(fn) + ": the alphas overlap the " + what);
+    if (ranges_overlap(byte_range(d_alphas, (size_t)n * sizeof(float)), window_range(w, rows, cols, ws)))
+        return fail(FDR_ERR_ARG, std::string(fn) + ": the alphas overlap the " + what);
     return FDR_OK;
+}
+
+int with_host_alphas(const char* fn, float* alphas_host, int n, const std::function<int(float* d_alphas)>& run) {
+    DeviceBuffer d;
+    const size_t bytes = alphas_host && n > 0 ? (size_t)n * sizeof(float) : 0;
+    if (bytes) FDR_ALLOC(d, bytes, fn);
+    const int rc = run(d.as<float>());
+    if (rc == FDR_OK && bytes) FDR_HIP(hipMemcpy(alphas_host, d.ptr, bytes, hipMemcpyDeviceToHost));
+    return rc;
 }
 
 // y and g are dense (row stride cols) in the workspace.  The direction of iteration k yields alpha_(k+1); it runs while a later

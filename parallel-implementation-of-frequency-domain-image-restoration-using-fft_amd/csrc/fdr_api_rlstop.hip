@@ -1,6 +1,6 @@
 // fdr_api_rlstop.hip -- Richardson-Lucy that stops from the data (fdr_richardson_lucy_auto_f32*; kernels: the ratio kind
 // ROW_OUT_RL_RATIO_STAT of fdr_panel_rows.hip and the fold of fdr_rlstop.hip): the workspace, the checks, the driver around the
-// unchanged steps of the four forms (fdr_api_operator.hip, fdr_api_rlfree.hip, fdr_api_rlaccel.hip) and the two entry points.
+// unchanged steps of the four forms (fdr_api_rl.hip, fdr_api_rlfree.hip, fdr_api_rlaccel.hip) and the two entry points.
 //
 // The final count is not known in advance, so nothing is routed by it: the estimate stays in its own plane(s) for every step, the
 // accelerated forms start at parity 0, and what the stop leaves is brought to the output (or to the normalise pass) afterwards.
@@ -8,18 +8,15 @@
 #include "fdr_host.hpp"
 
 #include <cmath>
-#include <cstdint>
 
 using namespace fdr;
 
 namespace {
 
 // names are static strings compared by pointer in PassTimer::pass_id
-const char* const kPassRsInit = "RL init: u = max(d, 0)";
 const char* const kPassRsFold = "RLS fold: res, kl";
 const char* const kPassRsNoise = "RLS noise: sum |d * n|";
 const char* const kPassRsMove = "RLS out: move";
-const char* const kPassRsNorm = "E RL minmax+normalize";
 
 constexpr int kRsTraceSteps = 1024;  // steps of the internal trace the first call makes room for
 
@@ -33,12 +30,6 @@ struct AutoArgs {
 
 bool finite_nonneg(float v) { return std::isfinite(v) && v >= 0.f; }
 
-bool bytes_overlap(const void* a, size_t a_bytes, const float* w, int ws, int rows, int cols) {
-    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + a_bytes;
-    const uintptr_t b0 = (uintptr_t)w, b1 = b0 + ((size_t)(rows - 1) * ws + cols) * sizeof(float);
-    return a0 < b1 && b0 < a1;
-}
-
 // everything an auto call refuses, before any device work: what the underlying form refuses, then the rule's own arguments
 int auto_check(const fdr_plan* p, const char* fn, const float* img, int rows, int cols, int stride, const float* weights, int wstride,
                const float* out, int out_stride, const fdr_rl_auto_params* prm, const double* d_trace, AutoArgs* a) {
@@ -50,9 +41,9 @@ int auto_check(const fdr_plan* p, const char* fn, const float* img, int rows, in
         rc = rlfree_check(p, fn, img, rows, cols, stride, weights, wstride, out, out_stride, &a->fp);
     } else {
         rc = rl_check(p, fn, img, rows, cols, stride, out, out_stride, prm->iterations, prm->norm_area);
-        if (rc == FDR_OK && weights) return fail(FDR_ERR_ARG, std::string(fn) + ": the plain form takes no weights");
-        if (rc == FDR_OK && !((prm->out_rows == 0 || prm->out_rows == rows) && (prm->out_cols == 0 || prm->out_cols == cols)))
-            return fail(FDR_ERR_ARG, std::string(fn) + ": the plain form's output window is the input's (out_rows, out_cols = 0 or rows, cols)");
+        if (rc == FDR_OK)
+            rc = plain_form_check(fn, weights, rows, cols, prm->out_rows, prm->out_cols, true,
+                                  ": the plain form's output window is the input's (out_rows, out_cols = 0 or rows, cols)");
         a->fp.out_rows = rows; a->fp.out_cols = cols;
     }
     if (rc != FDR_OK) return rc;
@@ -71,11 +62,11 @@ int auto_check(const fdr_plan* p, const char* fn, const float* img, int rows, in
         if (rc != FDR_OK) return rc;
     }
     if (d_trace && a->n > 0) {
-        const size_t bytes = (size_t)a->n * 2 * sizeof(double);
-        if (bytes_overlap(d_trace, bytes, img, stride, rows, cols)) return fail(FDR_ERR_ARG, std::string(fn) + ": the trace overlaps the input");
-        if (bytes_overlap(d_trace, bytes, out, out_stride, a->fp.out_rows, a->fp.out_cols))
+        const ByteRange t = byte_range(d_trace, (size_t)a->n * 2 * sizeof(double));
+        if (ranges_overlap(t, window_range(img, rows, cols, stride))) return fail(FDR_ERR_ARG, std::string(fn) + ": the trace overlaps the input");
+        if (ranges_overlap(t, window_range(out, a->fp.out_rows, a->fp.out_cols, out_stride)))
             return fail(FDR_ERR_ARG, std::string(fn) + ": the trace overlaps the output");
-        if (weights && bytes_overlap(d_trace, bytes, weights, wstride, rows, cols))
+        if (weights && ranges_overlap(t, window_range(weights, rows, cols, wstride)))
             return fail(FDR_ERR_ARG, std::string(fn) + ": the trace overlaps the weights");
     }
     return FDR_OK;
@@ -152,8 +143,8 @@ int auto_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, int
         }
         cur = p->rf_u;
     } else {
-        ScopedPass t(p, s, kPassRsInit);
-        FDR_HIP(launch_rl_init(d_img, rows, cols, stride, d_out, out_stride, s));
+        rc = rl_init_estimate(p, d_img, rows, cols, stride, d_out, out_stride, s);
+        if (rc != FDR_OK) return rc;
         cur = d_out;
     }
     float* const U[2] = {cur, a.accel ? p->ra_u : cur};
@@ -161,9 +152,11 @@ int auto_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, int
     const int R = a.free_form ? M : rows, C = a.free_form ? N : cols;  // the window the estimate lives on
 
     const RlFit fit{W, p->rs_part};
+    fdr_plan::Slot* w0 = &p->slots[0];
     int k = 0;  // the step about to run
     auto step = [&](const float* y, int ys, float* out, int os) {
-        int rc2 = a.free_form ? rlfree_step(p, y, out, rows, cols, s, &fit, D) : rl_step(p, d_img, stride, y, ys, out, os, rows, cols, s, &fit);
+        int rc2 = a.free_form ? rlfree_step(p, &w0, 1, &y, &out, &D, p->rf_wgt, rows, cols, s, &fit)
+                              : rl_step(p, &w0, 1, &d_img, stride, &y, ys, &out, os, rows, cols, s, &fit);
         if (rc2 == FDR_OK && tr) {
             ScopedPass t(p, s, kPassRsFold);
             FDR_HIP(launch_rlstop_fold(p->rs_part, p->rs_n_part, tr + 2 * (size_t)k, s));
@@ -213,7 +206,7 @@ int auto_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, int
                                  (size_t)rows, hipMemcpyDeviceToDevice, s));
         cur = raw;
     }
-    return normalize_window(p, fn, kPassRsNorm, cur, cols, rows, cols, a.norm_area, d_out, out_stride, s);
+    return rl_normalize(p, fn, cur, cols, rows, cols, a.norm_area, d_out, out_stride, s);
 }
 
 // the workspaces of the form and of the trace
@@ -257,9 +250,8 @@ int fdr_richardson_lucy_auto_f32(fdr_plan* p, const float* img_host, int rows, i
     const bool internal = trace_host || a.rule != FDR_RL_STOP_NONE;
     rc = auto_prepare(p, fn, a, weights_host != nullptr, internal);
     if (rc != FDR_OK) return rc;
-    if (a.free_form && weights_host)  // staged dense into u's plane, where the setup pass leaves W anyway
-        FDR_HIP(hipMemcpy2D(p->rf_u, (size_t)cols * sizeof(float), weights_host, (size_t)wstride * sizeof(float), (size_t)cols * sizeof(float),
-                            (size_t)rows, hipMemcpyHostToDevice));
+    if (a.free_form && weights_host) rc = stage_weights(p, weights_host, rows, cols, wstride);
+    if (rc != FDR_OK) return rc;
     rc = host_image_call(p, fn, img_host, rows, cols, stride, out_host, a.fp.out_rows, a.fp.out_cols, out_stride,
                          [&](const float* d_in, float* d_out) {
                              return auto_dev_impl(p, fn, d_in, rows, cols, cols, a.free_form && weights_host ? p->rf_u : nullptr, cols, d_out,

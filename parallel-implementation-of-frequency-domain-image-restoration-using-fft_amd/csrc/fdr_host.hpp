@@ -7,6 +7,7 @@
 #include "fdr_kernels.hpp"
 
 #include <hip/hip_runtime.h>
+#include <cstdint>
 #include <cstdio>
 #include <functional>
 #include <string>
@@ -320,77 +321,105 @@ int set_operator_psf_impl(fdr_plan* p, const float* d_psf, int prows, int pcols,
 // use (synchronous), freed with the plan
 int ensure_lap_table(fdr_plan* p);
 
+// ---- byte ranges: the one overlap test of the checks ----
+struct ByteRange { uintptr_t lo, hi; };  // [lo, hi)
+inline ByteRange byte_range(const void* ptr, size_t bytes) { return {(uintptr_t)ptr, (uintptr_t)ptr + bytes}; }
+// `count` windows rows x cols (row stride `stride`) that lie `pitch` elements apart
+inline ByteRange window_range(const float* base, int rows, int cols, int stride, int count = 1, size_t pitch = 0) {
+    return byte_range(base, ((size_t)(count - 1) * pitch + (size_t)(rows - 1) * stride + cols) * sizeof(float));
+}
+inline bool ranges_overlap(const ByteRange& a, const ByteRange& b) { return a.lo < b.hi && b.lo < a.hi; }
+
 // ---- the operator passes (fdr_api_operator.hip), shared by the blur, Richardson-Lucy and the TV solve ----
-// pass A: the window of x (zero elsewhere) -> the half spectrum of slot 0
-int op_rows_fwd(fdr_plan* p, const float* x, int rows, int cols, int stride, hipStream_t s);
-// pass B', unchanged, with `table` as its filter; timed as `name`
-int op_cols_table(fdr_plan* p, const float2* table, const char* name, hipStream_t s);
 // what ROW_OUT_RL_RATIO_STAT takes beside the datum: the weights (dense, the row stride of the datum; null = 1) and the room for the
 // (res, kl) partials, one double2 per workgroup of the pass
 struct RlFit { const float* weights; double* part; };
-// what a step of either form runs between its own passes for the blind call (fdr_api_blind.hip): after_fwd when pass A of the
-// estimate has left its row spectra in slot 0 (which it may read, not write), after_ratio when r lies in the window of the raw
-// plane (slot 0's spectrum is free then).  Neither changes an operand of the step's own passes: the step keeps its bits.
-struct RlHooks { std::function<int()> after_fwd, after_ratio; };
-// pass C with an operator kind: the window rows x cols of the inverse transform through the kind's epilogue into `out`
-int op_rows_inv(fdr_plan* p, RowOut kind, const char* name, const float* src, int src_stride, float* out, int out_stride, int rows, int cols,
-                hipStream_t s, const RlFit* fit = nullptr);
-// pass B' on H / (M N), or with `adjoint` on conj(H) / (M N)
-int op_cols(fdr_plan* p, bool adjoint, hipStream_t s);
-// The same passes for a group of n >= 1 images on the slots ws[0 .. n) with per-image pointers (blockIdx.y = image; n = 1 is the
-// single-image launch): pass A keeps FDR_PAD_ZERO, pass B' reads the table once for the group, pass C takes the four kinds
-// ROW_OUT_BLUR, _RL_RATIO, _RL_UPDATE and _RL_UPDATE_W (src2: the one wgt plane of the group).  An image comes out with the bits
-// it gets alone.
+// The passes for a group of n >= 1 images on the slots ws[0 .. n) with per-image pointers (blockIdx.y = image; n = 1 is the
+// single-image launch): pass A (the window of xs[k], zero elsewhere -> the half spectrum of slot k) keeps FDR_PAD_ZERO, pass B'
+// reads `table` once for the group and is timed as `name`, pass C takes the four kinds ROW_OUT_BLUR, _RL_RATIO, _RL_UPDATE and
+// _RL_UPDATE_W (src2: the one wgt plane of the group) and, for one image, _RL_RATIO_STAT with `fit`.  An image comes out with the
+// bits it gets alone.
 int op_rows_fwd_n(fdr_plan* p, fdr_plan::Slot* const* ws, int n, const float* const* xs, int rows, int cols, int stride, hipStream_t s);
 int op_cols_table_n(fdr_plan* p, fdr_plan::Slot* const* ws, int n, const float2* table, const char* name, hipStream_t s);
 int op_rows_inv_n(fdr_plan* p, fdr_plan::Slot* const* ws, int n, RowOut kind, const char* name, const float* const* srcs, int src_stride,
                   const float* src2, float* const* outs, int out_stride, int rows, int cols, hipStream_t s, const RlFit* fit = nullptr);
-int op_cols_n(fdr_plan* p, fdr_plan::Slot* const* ws, int n, bool adjoint, hipStream_t s);
-int blur_window_dev_n(fdr_plan* p, fdr_plan::Slot* const* ws, int n, const float* const* d_imgs, int rows, int cols, int stride,
-                      float* const* d_outs, int out_stride, int adjoint, hipStream_t s);
+int op_cols_n(fdr_plan* p, fdr_plan::Slot* const* ws, int n, bool adjoint, hipStream_t s);  // pass B' on H / (M N), `adjoint`: on conj(H) / (M N)
+// the single-image forms: a group of one on slot 0
+int op_rows_fwd(fdr_plan* p, const float* x, int rows, int cols, int stride, hipStream_t s);
+int op_cols_table(fdr_plan* p, const float2* table, const char* name, hipStream_t s);
+int op_rows_inv(fdr_plan* p, RowOut kind, const char* name, const float* src, int src_stride, float* out, int out_stride, int rows, int cols,
+                hipStream_t s);
 // blur (adjoint != 0: blur^T) of the window rows x cols of d_img; the window out_rows x out_cols of the result into d_out
 int blur_window_dev(fdr_plan* p, const float* d_img, int rows, int cols, int stride, float* d_out, int out_stride, int out_rows, int out_cols,
                     int adjoint, hipStream_t s);
+int blur_window_dev_n(fdr_plan* p, fdr_plan::Slot* const* ws, int n, const float* const* d_imgs, int rows, int cols, int stride,
+                      float* const* d_outs, int out_stride, int adjoint, hipStream_t s);
 // min-max of the window `fin` (row stride fs) to [0, 1] into d_out, timed as `name`: FDR_NORM_CROPPED over the window, FDR_NORM_PADDED
 // counting the zeros outside it too
 int normalize_window(fdr_plan* p, const char* fn, const char* name, const float* fin, int fs, int rows, int cols, int norm_area, float* d_out,
                      int out_stride, hipStream_t s);
-// ---- Richardson-Lucy, both forms (fdr_api_operator.hip, fdr_api_rlfree.hip): the checks and the step, shared with the calls that
-// stop from the data (fdr_api_rlstop.hip).  `fit`: the ratio pass also leaves the fit partials of c (same r, same update).
+// images of one launch group: the plan's group on the path of the operator, never more than the batch holds
+inline int launch_group(const fdr_plan* p, int count) { return p->group < count ? p->group : count; }
+// the launch group that starts at image i0 of a batch of `count` (`pitch` elements apart): its n images on the slots 0 .. n - 1
+struct LaunchGroup {
+    int n;
+    fdr_plan::Slot* ws[kMaxGroup];
+    const float* ins[kMaxGroup];
+    float* outs[kMaxGroup];
+    LaunchGroup(fdr_plan* p, int i0, int count, const float* d_imgs, size_t img_pitch, float* d_out, size_t out_pitch)
+        : n(launch_group(p, count) < count - i0 ? launch_group(p, count) : count - i0) {
+        for (int k = 0; k < n; ++k) { ws[k] = &p->slots[k]; ins[k] = d_imgs + (size_t)(i0 + k) * img_pitch; outs[k] = d_out + (size_t)(i0 + k) * out_pitch; }
+    }
+};
+
+// ---- Richardson-Lucy, both forms (fdr_api_rl.hip, fdr_api_rlfree.hip): the checks, the step and the driver of each form, on a
+// group of n >= 1 images on the slots ws[0 .. n).  The calls that stop from the data (fdr_api_rlstop.hip), the blind call
+// (fdr_api_blind.hip) and the batches (fdr_api_rlbatch.hip) are built from them.
+// What a driver runs around and inside a step for the blind call, each with the index of the iteration: after_fwd when pass A of
+// the estimate has left its row spectra in slot 0 (which it may read, not write), after_ratio when r lies in the window of the raw
+// plane (slot 0's spectrum is free then), after_step when the update is written.  No hook changes an operand of the step's own
+// passes: the step keeps its bits.  An empty hook is skipped; hooks take one image per step (FDR_ERR_STATE otherwise).
+struct RlHooks { std::function<int(int it)> after_fwd, after_ratio, after_step; };
 int rl_check(const fdr_plan* p, const char* fn, const float* img, int rows, int cols, int stride, const float* out, int out_stride,
              int iterations, int norm_area, PlanNeed need = NEED_OPERATOR_PSF);
-int rl_step(fdr_plan* p, const float* d_img, int stride, const float* y, int ys, float* out, int os, int rows, int cols, hipStream_t s,
-            const RlFit* fit = nullptr, const RlHooks* hooks = nullptr);
-// the start u = max(d, 0) and the closing normalisation of a plain-form call, timed under the plain call's names
+// what the calls that take both forms' arguments refuse in the plain form: weights, and an output window other than the input's.
+// `each_alone`: out_rows and out_cols may be 0 or the input's independently (the auto call); otherwise both 0 or both the input's.
+// `window_msg` is the call's own wording of the second refusal.
+int plain_form_check(const char* fn, const float* weights, int rows, int cols, int out_rows, int out_cols, bool each_alone, const char* window_msg);
+// One iteration of the plain form: c = blur(y), r = d+ / c into the window of slot k's raw plane (row stride cols), out = max(y .
+// blur^T(r), 0); outs[k] may be ys[k].  With `fit` (one image) the ratio pass also leaves the fit partials of c: same r, same update.
+int rl_step(fdr_plan* p, fdr_plan::Slot* const* ws, int n, const float* const* d_imgs, int stride, const float* const* ys, int ystride,
+            float* const* outs, int os, int rows, int cols, hipStream_t s, const RlFit* fit = nullptr, const RlHooks* hooks = nullptr, int it = 0);
+// the start u = max(d, 0) and the closing normalisation of a plain-form call
 int rl_init_estimate(fdr_plan* p, const float* d_img, int rows, int cols, int stride, float* u, int us, hipStream_t s);
 int rl_normalize(fdr_plan* p, const char* fn, const float* fin, int fs, int rows, int cols, int norm_area, float* d_out, int out_stride,
                  hipStream_t s);
-// one step of either form for a group of n images on the slots ws[0 .. n) (fdr_api_rlbatch.hip): the six launches of rl_step /
-// rlfree_step, each over the group
-int rl_step_n(fdr_plan* p, fdr_plan::Slot* const* ws, int n, const float* const* d_imgs, int stride, const float* const* ys, int ystride,
-              float* const* outs, int os, int rows, int cols, hipStream_t s);
-int rlfree_step_n(fdr_plan* p, fdr_plan::Slot* const* ws, int n, float* const* us, const float* const* dws, int rows, int cols, hipStream_t s);
-// the drivers of fdr_richardson_lucy_f32_dev and fdr_richardson_lucy_free_f32_dev on a checked call
-int rl_plain_dev(fdr_plan* p, const char* fn, const float* d_img, int rows, int cols, int stride, float* d_out, int out_stride, int iterations,
-                 int norm_area, hipStream_t s);
-int rlfree_plain_dev(fdr_plan* p, const char* fn, const float* d_img, int rows, int cols, int stride, const float* d_w, int wstride, float* d_out,
-                     int out_stride, const fdr_rlfree_params& prm, hipStream_t s);
+// the plain form on a checked group: start per image, `iterations` steps, normalisation per image
+int rl_group_dev(fdr_plan* p, const char* fn, fdr_plan::Slot* const* ws, int n, const float* const* d_imgs, int rows, int cols, int stride,
+                 float* const* d_outs, int out_stride, int iterations, int norm_area, hipStream_t s, const RlHooks* hooks = nullptr);
 // the free-boundary workspace for `group` images (1 + 2 group planes); FDR_ERR_ALLOC leaves the plan and the workspace it had intact
 int ensure_rlfree_workspace(fdr_plan* p, const char* fn, int group = 1);
-float* rlfree_u_plane(const fdr_plan* p, int k);    // image k of a group: its dense M x N estimate,
-float* rlfree_dw_plane(const fdr_plan* p, int k);   // its dw
-double* rlfree_part(const fdr_plan* p, int k);      // and the partials of its sums
-int rlfree_setup_image(fdr_plan* p, const float* d_img, int rows, int cols, int stride, const float* d_w, int wstride, float* dw, float* W,
-                       double* part, const double** sums, hipStream_t s);
-int rlfree_start_image(fdr_plan* p, float* alpha, float* u, float sigma, const double* sums, hipStream_t s);
-bool spans_overlap(const float* a, int a_stride, int a_rows, int a_cols, const float* b, int b_stride, int b_rows, int b_cols);
 int rlfree_check(const fdr_plan* p, const char* fn, const float* img, int rows, int cols, int stride, const float* weights, int wstride,
                  const float* out, int out_stride, const fdr_rlfree_params* prm, PlanNeed need = NEED_OPERATOR_PSF);
-int rlfree_step(fdr_plan* p, const float* y, float* out, int rows, int cols, hipStream_t s, const RlFit* fit = nullptr,
-                const float* d_dense = nullptr, const RlHooks* hooks = nullptr);
+// host weights (rows x cols) dense into u's plane, where the setup pass leaves W anyway: the d_w of the host forms (synchronous)
+int stage_weights(fdr_plan* p, const float* weights_host, int rows, int cols, int wstride);
+// One iteration of the free-boundary form on the whole plan: c = window(fullblur(y)), r = datum / c into slot k's raw plane, out =
+// max(y wgt fullblur^T(pad(r)), 0).  ys[k] and outs[k] are dense M x N planes and may be the same; datums[k] is dense rows x cols:
+// dw, or with `fit` (one image; weights dense too) d, from which the ratio pass forms dw = w d+ itself; wgt is the one plane of the call.
+int rlfree_step(fdr_plan* p, fdr_plan::Slot* const* ws, int n, const float* const* ys, float* const* outs, const float* const* datums,
+                const float* wgt, int rows, int cols, hipStream_t s, const RlFit* fit = nullptr, const RlHooks* hooks = nullptr, int it = 0);
+// begin, image 0 of a call: the setup (dw into rf_dw, W = pad(m) into rf_u, copied dense to keep_w when that is not null), the
+// coverage alpha = fullblur^T(W) and the start (rf_wgt = 1 / alpha, u_0 in rf_u); *sums, when not null, is where the device holds
+// (sum dw, sum W).  d_w may be rf_u itself (stage_weights).
 int rlfree_begin(fdr_plan* p, const float* d_img, int rows, int cols, int stride, const float* d_w, int wstride, float sigma, float* keep_w,
                  const double** sums, hipStream_t s);
+// finish: the output window of the dense M x N estimate u, cropped or normalised, into d_out
 int rlfree_finish(fdr_plan* p, const char* fn, const float* u, float* d_out, int out_stride, const fdr_rlfree_params& prm, hipStream_t s);
+// the free-boundary form on a checked batch of `count` images with its workspace (for launch_group(p, count) images): begin, steps in
+// place, finish, in launch groups; one image with its hooks and keep_w is the blind call's
+int rlfree_batch_dev(fdr_plan* p, const char* fn, const float* d_imgs, size_t img_pitch, int count, int rows, int cols, int stride, const float* d_w,
+                     int wstride, float* d_out, size_t out_pitch, int out_stride, const fdr_rlfree_params& prm, hipStream_t s,
+                     const RlHooks* hooks = nullptr, float* keep_w = nullptr);
 // ---- the noise estimate (fdr_api_reg.hip): the Immerkaer sum of a device window through `part` (reg_noise_partials + 1 doubles), read
 // back: synchronous; and the refusal of a window it cannot work on
 int noise_sigma_dev(const float* d_img, int rows, int cols, int stride, double* part, double* sigma, hipStream_t s);
@@ -400,6 +429,8 @@ int noise_window_check(const char* fn, int rows, int cols, int stride);
 int ensure_rlaccel_workspace(fdr_plan* p, const char* fn);
 // FDR_ERR_ARG when the n floats at d_alphas overlap the rows x cols window at `w` (row stride ws); a null d_alphas is fine
 int check_alphas(const char* fn, const float* d_alphas, int n, const float* w, int ws, int rows, int cols, const char* what);
+// run(d_alphas) of a host-pointer call: a one-shot device buffer for the n alphas (null for a null host pointer or n <= 0), read back after it
+int with_host_alphas(const char* fn, float* alphas_host, int n, const std::function<int(float* d_alphas)>& run);
 // One iteration of either form: u_next = step(y), y a rows x cols window with row stride ys, `out` another plane
 using RlStep = std::function<int(const float* y, int ys, float* out, int os)>;
 // n accelerated iterations on a rows x cols window.  u_k lives in U[(first + k) & 1] (row strides us[]), u_0 there on entry; the
