@@ -303,6 +303,39 @@ inline void richardsonLucyFree_RGB(std::vector<Mat>& channels, const Mat& psf, i
                                    bool accelerate = false) {
     richardsonLucyFree_RGB(channels, psf, iterations, weights, defaults(), FDR_RL_SIGMA, accelerate);
 }
+// Richardson-Lucy with a total-variation prior (fdr_richardson_lucy_tv_f32, include/fdr.h) of every channel, in place, channel by
+// channel: lambda in 0 .. FDR_RLTV_MAX_LAMBDA weighs the prior (0 is the unregularised form), eps (the units of the picture; 0 =
+// FDR_RLTV_EPS) smooths |grad u|.  free_boundary: on the plan and with the weights and sigma of richardsonLucyFree_RGB, for a picture
+// that is a crop; otherwise on the plan of richardsonLucy_RGB, and `weights` must be empty.  Each channel normalised by o.norm_area.
+inline void richardsonLucyTV_RGB(std::vector<Mat>& channels, const Mat& psf, int iterations, float lambda, float eps, bool free_boundary,
+                                 const Mat& weights, const Options& o, float sigma = FDR_RL_SIGMA) {
+    if (channels.empty()) return;
+    const int rows = channels[0].rows, cols = channels[0].cols;
+    if (!weights.empty() && (!free_boundary || weights.rows != rows || weights.cols != cols || weights.type() != CV_32F)) {
+        std::cerr << "richardsonLucyTV_RGB: weights belong to the free-boundary form, must be CV_32F and have the picture's size\n";
+        exit(1);
+    }
+    bool created = false;
+    PlanCacheSettle settle_;
+    const int M = free_boundary ? nextPowerOfTwo(rows + psf.rows - 1) : nextPowerOfTwo(rows);
+    const int N = free_boundary ? nextPowerOfTwo(cols + psf.cols - 1) : nextPowerOfTwo(cols);
+    fdr_plan* plan = plan_cache().get(o.device, std::max(8, M), std::max(32, N), FDR_MODE_FAST, &created);
+    Mat psfc = psf.isContinuous() ? psf : psf.clone();
+    FDR_CHECK(fdr_set_operator_psf(plan, psfc.ptr<float>(0), psf.rows, psf.cols, psf.cols));
+    Mat w = weights.empty() || weights.isContinuous() ? weights : weights.clone();
+    for (Mat& c : channels) {
+        Mat src = c.isContinuous() ? c : c.clone();
+        Mat out(c.rows, c.cols, CV_32F);
+        const fdr_rl_tv_params prm = {iterations, free_boundary ? 1 : 0, lambda, eps, o.norm_area, sigma, c.rows, c.cols};
+        FDR_CHECK(fdr_richardson_lucy_tv_f32(plan, src.ptr<float>(0), c.rows, c.cols, c.cols, w.empty() ? nullptr : w.ptr<float>(0), cols,
+                                             out.ptr<float>(0), c.cols, &prm));
+        c = out;
+    }
+}
+inline void richardsonLucyTV_RGB(std::vector<Mat>& channels, const Mat& psf, int iterations, float lambda, float eps = 0.f,
+                                 bool free_boundary = false, const Mat& weights = Mat()) {
+    richardsonLucyTV_RGB(channels, psf, iterations, lambda, eps, free_boundary, weights, defaults(), FDR_RL_SIGMA);
+}
 // What richardsonLucyBlind_RGB takes beside the picture and the start PSF: the form, the steps the PSF is held for, and the weights and
 // coverage threshold of the free form.
 struct BlindOptions {

@@ -31,6 +31,8 @@ NORM_PADDED = 1
 NORM_CROPPED = 0
 NORM_NONE = 2  # Richardson-Lucy only: the raw estimate
 RL_SIGMA = 1e-2  # FDR_RL_SIGMA: the usual coverage threshold of free-boundary Richardson-Lucy
+RLTV_MAX_LAMBDA = 0.125  # FDR_RLTV_MAX_LAMBDA: the largest weight of Richardson-Lucy's total-variation prior
+RLTV_EPS = 1e-3  # FDR_RLTV_EPS: the smoothing of |grad u| that eps = 0 selects
 RL_STOP_NONE, RL_STOP_RESIDUAL, RL_STOP_KL = 0, 1, 2  # FDR_RL_STOP_*: the stopping rules of Plan.richardson_lucy_auto
 RL_ACCEL_MAX = 0.9990234375  # FDR_RL_ACCEL_MAX = 1 - 2^-10: the upper bound of accelerated Richardson-Lucy's extrapolation factor
 MAX_PASSES = 16
@@ -81,6 +83,12 @@ class RlFreeParams(ctypes.Structure):
     """fdr_rlfree_params of include/fdr.h"""
     _fields_ = [("iterations", ctypes.c_int), ("sigma", ctypes.c_float), ("norm_area", ctypes.c_int), ("out_rows", ctypes.c_int),
                 ("out_cols", ctypes.c_int)]
+
+
+class RlTvParams(ctypes.Structure):
+    """fdr_rl_tv_params of include/fdr.h"""
+    _fields_ = [("iterations", ctypes.c_int), ("free_boundary", ctypes.c_int), ("lambda", ctypes.c_float), ("eps", ctypes.c_float),
+                ("norm_area", ctypes.c_int), ("cov_sigma", ctypes.c_float), ("out_rows", ctypes.c_int), ("out_cols", ctypes.c_int)]
 
 
 class RlBatchParams(ctypes.Structure):
@@ -231,6 +239,9 @@ def _signatures():
         "fdr_richardson_lucy_f32_dev": (ci, [vp, vp, ci, ci, ci, vp, ci, ci, ci, vp]),
         "fdr_richardson_lucy_free_f32": (ci, [vp, vp, ci, ci, ci, vp, ci, vp, ci, P(RlFreeParams)]),
         "fdr_richardson_lucy_free_f32_dev": (ci, [vp, vp, ci, ci, ci, vp, ci, vp, ci, P(RlFreeParams), vp]),
+        "fdr_richardson_lucy_tv_f32": (ci, [vp, vp, ci, ci, ci, vp, ci, vp, ci, P(RlTvParams)]),
+        "fdr_richardson_lucy_tv_f32_dev": (ci, [vp, vp, ci, ci, ci, vp, ci, vp, ci, P(RlTvParams), vp]),
+        "fdr_rl_tv_factor_f32_dev": (ci, [ci, vp, ci, ci, ci, vp, cf, cf, vp, ci, vp]),
         "fdr_blur_batch_f32_dev": (ci, [vp, vp, sz, ci, ci, ci, ci, vp, sz, ci, ci, vp]),
         "fdr_richardson_lucy_batch_f32": (ci, [vp, vp, sz, ci, ci, ci, ci, vp, ci, vp, sz, ci, P(RlBatchParams)]),
         "fdr_richardson_lucy_batch_f32_dev": (ci, [vp, vp, sz, ci, ci, ci, ci, vp, ci, vp, sz, ci, P(RlBatchParams), vp]),
@@ -606,6 +617,42 @@ class Plan:
         _check(lib.fdr_richardson_lucy_free_f32_dev(self._h, ctypes.c_void_p(int(d_img)), rows, cols, stride,
                                                     ctypes.c_void_p(int(d_weights)) if d_weights else None, int(wstride),
                                                     ctypes.c_void_p(int(d_out)), out_stride, ctypes.byref(prm), _stream(stream)))
+
+    # Richardson-Lucy with a total-variation prior, both forms (include/fdr.h); uses the operator PSF
+    def richardson_lucy_tv(self, img, iterations, lam, eps=0.0, free_boundary=False, weights=None, cov_sigma=RL_SIGMA, norm_area=NORM_NONE,
+                           full_plane=False):
+        """`iterations` Richardson-Lucy steps with a total-variation prior of weight lam (0 .. RLTV_MAX_LAMBDA; 0 is the call of the
+        form) on the window img (host arrays); eps (in the units of img; 0 = RLTV_EPS) smooths |grad u|.  free_boundary: the
+        free-boundary, weighted form with weights, cov_sigma and full_plane as Plan.richardson_lucy_free; the plain form takes none."""
+        img = np.ascontiguousarray(img, dtype=np.float32)
+        rows, cols = img.shape
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float32)
+            if w.shape != img.shape:
+                raise ValueError("weights must have the shape of img")
+        if full_plane and not free_boundary:
+            raise ValueError("full_plane needs free_boundary=True")
+        orows, ocols = (self.M, self.N) if full_plane else (rows, cols)
+        out = np.empty((orows, ocols), dtype=np.float32)
+        prm = RlTvParams(int(iterations), int(bool(free_boundary)), float(lam), float(eps), int(norm_area), float(cov_sigma), orows, ocols)
+        _check(lib.fdr_richardson_lucy_tv_f32(self._h, _ptr(img), rows, cols, cols, _ptr(w) if w is not None else None, cols, _ptr(out), ocols,
+                                              ctypes.byref(prm)))
+        return out
+
+    def richardson_lucy_tv_dev(self, d_img, rows, cols, stride, d_out, out_stride, iterations, lam, eps=0.0, free_boundary=False, d_weights=None,
+                               wstride=0, cov_sigma=RL_SIGMA, norm_area=NORM_NONE, out_rows=None, out_cols=None, stream=None):
+        """the same on device pointers; out_rows x out_cols (default rows x cols; free_boundary: up to M x N) is the output window.
+        Asynchronous."""
+        prm = RlTvParams(int(iterations), int(bool(free_boundary)), float(lam), float(eps), int(norm_area), float(cov_sigma),
+                         int(rows if out_rows is None else out_rows), int(cols if out_cols is None else out_cols))
+        _check(lib.fdr_richardson_lucy_tv_f32_dev(self._h, ctypes.c_void_p(int(d_img)), rows, cols, stride,
+                                                  ctypes.c_void_p(int(d_weights)) if d_weights else None, int(wstride),
+                                                  ctypes.c_void_p(int(d_out)), out_stride, ctypes.byref(prm), _stream(stream)))
+
+    def rl_tv_factor_dev(self, d_u, rows, cols, stride, d_out, out_stride, lam, eps=0.0, d_w=None, stream=None):
+        """the factor w / (1 - lam div(grad u / |grad u|)) of one such step on a device window, on the plan's device (rl_tv_factor_dev)"""
+        rl_tv_factor_dev(d_u, rows, cols, stride, d_out, out_stride, lam, eps, d_w, self.device, stream)
 
     # several images per launch (include/fdr.h, "batched blur and Richardson-Lucy"): groups of set_batching's `group` images, every
     # image with the bits of its single-image call
@@ -1006,6 +1053,30 @@ def richardsonLucyFree_myfft(img, psf, iterations, weights=None, sigma=RL_SIGMA,
     with Plan(M, N, MODE_FAST, device) as p:
         p.set_operator_psf(psf)
         return p.richardson_lucy_free(img, iterations, weights, sigma, norm_area, full_plane, accelerate=accelerate)
+
+
+def rl_tv_factor_dev(d_u, rows, cols, stride, d_out, out_stride, lam, eps=0.0, d_w=None, device=0, stream=None):
+    """fdr_rl_tv_factor_f32_dev: d_out = w / (1 - lam div(grad u / sqrt(|grad u|^2 + eps^2))) on the rows x cols device window d_u (row
+    stride `stride`; d_w, same stride, None = 1), forward differences replicated at the far edges.  Any size, stride and alignment;
+    needs no plan.  Asynchronous."""
+    _check(lib.fdr_rl_tv_factor_f32_dev(int(device), ctypes.c_void_p(int(d_u)), rows, cols, stride, ctypes.c_void_p(int(d_w)) if d_w else None,
+                                        float(lam), float(eps), ctypes.c_void_p(int(d_out)), out_stride, _stream(stream)))
+
+
+def richardsonLucyTV_myfft(img, psf, iterations, lam, eps=0.0, free_boundary=False, weights=None, cov_sigma=RL_SIGMA, device=0,
+                           norm_area=NORM_NONE, full_plane=False):
+    """Richardson-Lucy with a total-variation prior of one channel: the plan of richardsonLucy_myfft, or with free_boundary (the form
+    for a crop of a larger scene; weights as richardsonLucyFree_myfft) that of richardsonLucyFree_myfft, `iterations` steps, crop.
+    lam in 0 .. RLTV_MAX_LAMBDA (0.01 is a usual value for a picture scaled to 1); eps in the units of img, 0 = RLTV_EPS."""
+    img = np.asarray(img, dtype=np.float32)
+    psf = np.asarray(psf, dtype=np.float32)
+    if free_boundary:
+        M, N = _rlfree_plan_size(img.shape[0], img.shape[1], psf.shape[0], psf.shape[1])
+    else:
+        M, N = _rl_plan_size(img.shape[0], img.shape[1])
+    with Plan(M, N, MODE_FAST, device) as p:
+        p.set_operator_psf(psf)
+        return p.richardson_lucy_tv(img, iterations, lam, eps, free_boundary, weights, cov_sigma, norm_area, full_plane)
 
 
 def psf_gaussian(size, sigma=0.0):

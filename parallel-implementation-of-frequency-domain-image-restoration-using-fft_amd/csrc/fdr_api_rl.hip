@@ -16,6 +16,7 @@ const char* const kPassRlInit = "RL init: u = max(d, 0)";
 const char* const kPassRlRatio = "C op rows: IFFT+RL ratio";
 const char* const kPassRlRatioFit = "C op rows: IFFT+RL ratio+fit";
 const char* const kPassRlUpdate = "C op rows: IFFT+RL update";
+const char* const kPassRlUpdateF = "C op rows: IFFT+RL update (factor)";
 const char* const kPassRlNorm = "E RL minmax+normalize";
 
 }  // namespace
@@ -44,7 +45,7 @@ int plain_form_check(const char* fn, const float* weights, int rows, int cols, i
 }
 
 int rl_step(fdr_plan* p, fdr_plan::Slot* const* ws, int n, const float* const* d_imgs, int stride, const float* const* ys, int ystride,
-            float* const* outs, int os, int rows, int cols, hipStream_t s, const RlFit* fit, const RlHooks* hooks, int it) {
+            float* const* outs, int os, int rows, int cols, hipStream_t s, const RlFit* fit, const RlHooks* hooks, int it, const float* factor) {
     if (hooks && n > 1) return fail(FDR_ERR_STATE, "rl_step: the hooks take one image per step");
     float* r[kMaxGroup];
     for (int k = 0; k < n; ++k) r[k] = ws[k]->raw;
@@ -58,6 +59,8 @@ int rl_step(fdr_plan* p, fdr_plan::Slot* const* ws, int n, const float* const* d
     if (rc == FDR_OK && hooks && hooks->after_ratio) rc = hooks->after_ratio(it);
     if (rc == FDR_OK) rc = op_rows_fwd_n(p, ws, n, r, rows, cols, rs, s);                                // g = blur^T(r) ...
     if (rc == FDR_OK) rc = op_cols_n(p, ws, n, true, s);
+    if (rc == FDR_OK && factor)                                                                          // ... out = max(y factor g, 0)
+        return op_rows_inv_n(p, ws, n, ROW_OUT_RL_UPDATE_W, kPassRlUpdateF, ys, ystride, factor, outs, os, rows, cols, s);
     if (rc == FDR_OK) rc = op_rows_inv_n(p, ws, n, ROW_OUT_RL_UPDATE, kPassRlUpdate, ys, ystride, nullptr, outs, os, rows, cols, s);  // ... out = max(y g, 0)
     return rc;
 }

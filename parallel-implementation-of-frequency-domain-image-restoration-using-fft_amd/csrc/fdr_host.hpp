@@ -158,6 +158,11 @@ struct fdr_plan {
     float *ra_y = nullptr, *ra_u = nullptr, *ra_g = nullptr;
     double* ra_part = nullptr;
     float* ra_alpha = nullptr;
+    // Richardson-Lucy with a total-variation prior (fdr_richardson_lucy_tv_f32*): made by the first such call with lambda > 0, kept until
+    // fdr_plan_destroy -- one allocation of two M x N float planes: the factor w / g of the step and the plain form's estimate (dense
+    // rows x cols; the free-boundary form keeps its estimate in rf_u)
+    void* rt_block = nullptr;
+    float *rt_f = nullptr, *rt_u = nullptr;
     // stopping Richardson-Lucy from the data (fdr_richardson_lucy_auto_f32*): made by the first such call, kept until fdr_plan_destroy
     // -- rs_block holds the (res, kl) partials of the ratio pass (one double2 per workgroup of the plan's inverse row grid) and the
     // partials of the noise estimate; rs_trace the internal trace (2 rs_trace_cap doubles; it grows only when a call with a rule and
@@ -388,8 +393,10 @@ int rl_check(const fdr_plan* p, const char* fn, const float* img, int rows, int 
 int plain_form_check(const char* fn, const float* weights, int rows, int cols, int out_rows, int out_cols, bool each_alone, const char* window_msg);
 // One iteration of the plain form: c = blur(y), r = d+ / c into the window of slot k's raw plane (row stride cols), out = max(y .
 // blur^T(r), 0); outs[k] may be ys[k].  With `fit` (one image) the ratio pass also leaves the fit partials of c: same r, same update.
+// With `factor` (one plane for the group, row stride ystride) the update is the weighted one: out = max(y . factor . blur^T(r), 0).
 int rl_step(fdr_plan* p, fdr_plan::Slot* const* ws, int n, const float* const* d_imgs, int stride, const float* const* ys, int ystride,
-            float* const* outs, int os, int rows, int cols, hipStream_t s, const RlFit* fit = nullptr, const RlHooks* hooks = nullptr, int it = 0);
+            float* const* outs, int os, int rows, int cols, hipStream_t s, const RlFit* fit = nullptr, const RlHooks* hooks = nullptr, int it = 0,
+            const float* factor = nullptr);
 // the start u = max(d, 0) and the closing normalisation of a plain-form call
 int rl_init_estimate(fdr_plan* p, const float* d_img, int rows, int cols, int stride, float* u, int us, hipStream_t s);
 int rl_normalize(fdr_plan* p, const char* fn, const float* fin, int fs, int rows, int cols, int norm_area, float* d_out, int out_stride,

@@ -180,6 +180,11 @@ hipError_t launch_rlfree_setup(const float* d, int stride, const float* m, int m
                                hipStream_t s);
 hipError_t launch_rlfree_start(float* wgt, float* u, size_t count, float sigma, const double* sums, hipStream_t s);
 hipError_t launch_rlfree_crop(const float* u, int ustride, float* out, int rows, int cols, int out_stride, hipStream_t s);
+// (fdr_rltv.hip) Richardson-Lucy with a total-variation prior: out = w / (1 - lambda div(grad u / sqrt(|grad u|^2 + eps^2))) on the
+// rows x cols domain of u (forward differences, replicated at the far edges; u and w with row stride `stride`, w = 1 for a null
+// pointer; out is neither).  Any size, stride and alignment.
+hipError_t launch_rltv_factor(const float* u, int rows, int cols, int stride, const float* w, float lambda, float eps, float* out,
+                              int out_stride, hipStream_t s);
 // (fdr_rlaccel.hip) accelerated Richardson-Lucy, on rows x cols windows with their own row strides.  direction: g = u1 - y over the
 // previous g; with `part` not null also sum(g_new g_old) and sum(g_old g_old) in double as rlaccel_partials(rows, cols)
 // per-workgroup partials each (part holds 2 n doubles); with a null `part` the old g is not read.  alpha: one workgroup folds the

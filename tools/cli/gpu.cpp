@@ -1,5 +1,5 @@
 // gpu.cpp -- ./gpu <img-path> <psf-length> <psf-angle> [--out file] [--mode fast|parity] [--norm padded|cropped] [--host-epilogue]
-//           [--cls gamma|auto] [--k K|auto] [--reg gcv|discrepancy] [--sigma s] [--pad zero|smooth] [--rl iterations|auto [--accel] [--free-boundary [--mask mask.png]] [--rl-max n] [--rl-stop residual|kl] [--gain g] [--rl-check c]] [--tv mu [--tv-iters n] [--tv-rho r]]
+//           [--cls gamma|auto] [--k K|auto] [--reg gcv|discrepancy] [--sigma s] [--pad zero|smooth] [--rl iterations|auto [--accel] [--rl-tv lambda [--rl-tv-eps e]] [--free-boundary [--mask mask.png]] [--rl-max n] [--rl-stop residual|kl] [--gain g] [--rl-check c]] [--tv mu [--tv-iters n] [--tv-rho r]]
 // `auto auto` for length and angle: the blur is estimated first (fft_gpu::estimateMotionBlur on the per-pixel mean of B, G and R),
 // printed as `estimate: length L angle A confidence C`, and the run then goes on exactly as `./gpu <img-path> L A` would.
 // `--cls auto` (gamma, with K = 0) or `--k auto` (K, with gamma = 0): the weight is chosen first (fft_gpu::chooseRegularisation on the same
@@ -14,6 +14,9 @@
 // --rl-max steps (default 100), stopped by --rl-stop residual (default; --sigma = the noise level of the mean, else estimated) or kl (--gain = photons
 // per unit, required), looked at every --rl-check steps), printed as `rl: iterations k of n rule r sigma s statistic v target t stopped 0|1`,
 // and the run then goes on exactly as `--rl k` would.  It combines with --accel, --free-boundary, --mask and `auto auto`.
+// `--rl n --rl-tv lambda [--rl-tv-eps e]`: the --rl leg runs Richardson-Lucy with a total-variation prior of weight lambda (fft_gpu::richardsonLucyTV_RGB;
+// eps smooths |grad u|, default FDR_RLTV_EPS); --free-boundary and --mask apply, `auto auto` works as before; --accel, `--rl auto` and `blind` have no
+// regularised form and are refused with a message.
 // Drop-in counterpart of the reference's gpu.cpp (argument meaning, printed lines and exit codes as at
 // gpu.cpp:57-138 of the reference): read image, /255, PSF, K = 0.01, split BGR, warm-up call, timed
 // wienerDeblur_RGB_optimized, timed wienerDeblur_RGB_naive, merge, Lab white balance, 8-bit result.
@@ -89,6 +92,8 @@ int main(int argc, char** argv) {
     float rl_gain = 0.f;         // --gain g
     bool rl_auto_opts = false;   // one of the four above was given
     bool accel = false;          // --accel: the --rl leg runs the accelerated iteration (vector extrapolation)
+    float rl_tv = -1.f, rl_tv_eps = 0.f;  // --rl-tv lambda: the --rl leg is fft_gpu::richardsonLucyTV_RGB; --rl-tv-eps e
+    bool rl_tv_opts = false;
     bool free_boundary = false;  // --free-boundary: the --rl leg is fft_gpu::richardsonLucyFree_RGB (the picture is a crop of a larger scene)
     string mask_path;            // --mask file: pixels that are 0 in it (any channel counts) get weight 0, the others weight 1
     float tv_mu = -1.f, tv_rho = 2.0f;  // --tv mu: a timed total-variation leg (fft_gpu::tvDeblur_RGB); its planes are the written result
@@ -141,6 +146,8 @@ int main(int argc, char** argv) {
         else if (a == "--gain" && i + 1 < argc) { rl_auto_opts = true; rl_gain = strtof(argv[++i], nullptr); }
         else if (a == "--rl-check" && i + 1 < argc) { rl_auto_opts = true; rl_check = atoi(argv[++i]); }
         else if (a == "--accel") accel = true;
+        else if (a == "--rl-tv" && i + 1 < argc) { rl_tv_opts = true; rl_tv = strtof(argv[++i], nullptr); }
+        else if (a == "--rl-tv-eps" && i + 1 < argc) { rl_tv_opts = true; rl_tv_eps = strtof(argv[++i], nullptr); }
         else if (a == "--free-boundary") free_boundary = true;
         else if (a == "--mask" && i + 1 < argc) mask_path = argv[++i];
         else if (a == "--psf-hold" && i + 1 < argc) { blind_opts = true; psf_hold = atoi(argv[++i]); }
@@ -166,6 +173,17 @@ int main(int argc, char** argv) {
     if ((free_boundary && rl_iterations < 0) || (accel && rl_iterations < 0) || (!mask_path.empty() && !free_boundary)) {
         cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle>\n";
         return -1;
+    }
+    // --rl-tv belongs to --rl n; lambda in [0, FDR_RLTV_MAX_LAMBDA], eps finite and >= 0; the prior has no accelerated, data-stopped or blind form
+    if (rl_tv_opts) {
+        if (accel || rl_auto || blind) {
+            cout << "--rl-tv has no accelerated, data-stopped or blind form: it cannot be combined with --accel, --rl auto or blind\n";
+            return -1;
+        }
+        if (rl_iterations < 0 || !(rl_tv >= 0.f && rl_tv <= FDR_RLTV_MAX_LAMBDA) || !(rl_tv_eps >= 0.f) || !std::isfinite(rl_tv_eps)) {
+            cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle>\n";
+            return -1;
+        }
     }
     // --rl-max, --rl-stop, --gain and --rl-check belong to --rl auto; the kl rule needs its gain, the residual rule takes none
     const bool rl_kl = rl_stop == "kl";
@@ -331,11 +349,14 @@ int main(int argc, char** argv) {
     } else if (rl_iterations >= 0) {  // Richardson-Lucy on the same channels: its planes become the written result
         vector<Mat> rl = input;
         t_start = high_resolution_clock::now();
-        if (free_boundary) fft_gpu::richardsonLucyFree_RGB(rl, psf, rl_iterations, weights, accel);
+        if (rl_tv_opts) fft_gpu::richardsonLucyTV_RGB(rl, psf, rl_iterations, rl_tv, rl_tv_eps, free_boundary, weights);
+        else if (free_boundary) fft_gpu::richardsonLucyFree_RGB(rl, psf, rl_iterations, weights, accel);
         else fft_gpu::richardsonLucy_RGB(rl, psf, rl_iterations, accel);
         t_end = high_resolution_clock::now();
         cout << "Deblurring 3 channels took(gpu[richardson-lucy " << (free_boundary ? "free-boundary " : "") << rl_iterations
-             << (accel ? " accelerated" : "") << "]): " << getElapsedMs(t_start, t_end) << " ms\n";
+             << (accel ? " accelerated" : "");
+        if (rl_tv_opts) cout << " tv " << rl_tv;
+        cout << "]): " << getElapsedMs(t_start, t_end) << " ms\n";
         channels = rl;
     }
 
