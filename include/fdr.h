@@ -650,6 +650,73 @@ int fdr_estimate_motion_f32(fdr_plan* plan, const float* img_host, int rows, int
 int fdr_estimate_motion_f32_dev(fdr_plan* plan, const float* d_img, int rows, int cols, int stride, int min_length, int max_length,
                                 double angle_step_deg, fdr_motion_estimate* est, float* d_scores, void* stream);
 
+/* -- the defocus estimate: the radius of a uniform disk blur (an out-of-focus picture), from the blurred
+ *    picture alone, and the disk PSF itself.
+ *    fdr_psf_disk: out[i, j] = the share of pixel (i, j)'s unit square that lies inside the disk of radius `radius` about
+ *    c = size / 2 (integer division, the centre of fdr_psf_gaussian), over the sum of the shares.  A share is counted on a fixed
+ *    16 x 16 grid of sub-samples, in integers: sub-sample k of pixel i lies at X = (2 k + 1) + 32 (i - c) - 16 in units of 1 / 32 px
+ *    (Y likewise), and is inside when (double)(X^2 + Y^2) <= (32 radius)^2.  out = count / total count, divided in double and
+ *    rounded once.  FDR_ERR_ARG unless 1 <= size <= 256, radius is finite and 0 < radius <= min(c, size - 1 - c) + 0.5 (the disk
+ *    lies inside the size x size square).
+ *    fdr_set_psf_disk, fdr_set_psf_disk_cls, fdr_set_operator_psf_disk: fdr_set_psf_dev, fdr_set_psf_cls_dev and
+ *    fdr_set_operator_psf_dev on the disk of size 2 ceil(radius) + 1, generated on the device; they refuse what those refuse, and a
+ *    radius that is not finite, not above 0 or above 127.
+ *    The estimate.  The transfer function of the disk, J1(2 pi R rho) / (pi R rho), has rings of zeros; in the power cepstrum c of
+ *    the motion estimate above (same window, same eps, same plans) they show as a negative ring of radius about 2 R.  With S the
+ *    score table of the motion estimate for l = min_diameter .. max_diameter:
+ *        T[d] = median over a of S[a, d]       (the mean of the two middle values for an even number of angles)
+ *        k* = argmin T (exact ties: the lowest index);  diameter = min_diameter + k*;  score = T[k*]
+ *        confidence = (median T - T[k*]) / (1.4826 MAD T)                (0 when the MAD is 0)
+ *        ring = diameter + 0.5 (T[k* - 1] - T[k* + 1]) / (T[k* - 1] - 2 T[k*] + T[k* + 1]), the offset clamped to +-0.5; the
+ *               diameter itself at either end of T or when the denominator is 0
+ *        radius = FDR_DEFOCUS_A ring + FDR_DEFOCUS_B
+ *    T is a float per diameter, computed on the device; the pick runs in double on the host.  The median over the directions leaves
+ *    the single peak of a motion blur out: a confidence below FDR_DEFOCUS_CONF_MIN means no ring was found.  The two constants are
+ *    the least-squares line through the rings of 13 radii from 2 to 13 px on three synthetic scenes (tests/_defocus_model.py).  A
+ *    radius below about 1.6 px lies under the smallest diameter.  An all-zero window gives diameter 0, ring 0, radius 0, score 0,
+ *    confidence 0 and an all-zero profile.
+ *    Arguments, plans, refusals and the workspace are those of fdr_estimate_motion_f32* (min_diameter and max_diameter in the place of
+ *    min_length and max_length), and FDR_ERR_ARG for a step that gives more than 4096 angles.  The cepstrum workspace is the motion
+ *    estimate's own (one per plan); the first defocus call adds 80 KB for its trig table and profile, later calls allocate nothing.
+ *      fdr_estimate_defocus_f32*  *est; T (n_diameters floats) into profile when it is not NULL.  The _dev form is SYNCHRONOUS.
+ *      fdr_estimate_blur_f32*     both estimates from one cepstrum: *motion is what fdr_estimate_motion_f32* returns for (min_length,
+ *                                 max_length, motion_step_deg), *defocus what fdr_estimate_defocus_f32* returns for (min_diameter,
+ *                                 max_diameter, defocus_step_deg), bit for bit; *kind = fdr_blur_kind of the two confidences.
+ *      fdr_blur_kind              m = motion_conf / FDR_MOTION_CONF_MIN, f = defocus_conf / FDR_DEFOCUS_CONF_MIN: FDR_BLUR_NONE when
+ *                                 both are below 1, else FDR_BLUR_MOTION when m >= f, else FDR_BLUR_DEFOCUS.                   */
+#define FDR_DEFOCUS_A 0.52304
+#define FDR_DEFOCUS_B (-0.01685)
+#define FDR_MOTION_CONF_MIN 10.0
+#define FDR_DEFOCUS_CONF_MIN 6.0
+#define FDR_BLUR_NONE 0
+#define FDR_BLUR_MOTION 1
+#define FDR_BLUR_DEFOCUS 2
+typedef struct fdr_defocus_estimate {
+    int diameter;        /* d*, 0 for an all-zero window */
+    double ring;         /* d_sub */
+    double radius;       /* FDR_DEFOCUS_A * ring + FDR_DEFOCUS_B */
+    float score;         /* T[d*] */
+    float confidence;    /* (median T - T[d*]) / (1.4826 MAD T) */
+    int n_angles;        /* ceil(180 / step) */
+    int n_diameters;     /* entries of T: max_diameter - min_diameter + 1 */
+} fdr_defocus_estimate;
+int fdr_psf_disk(int size, double radius, float* out_host);
+int fdr_psf_disk_dev(int device, int size, double radius, float* d_out, void* stream);
+int fdr_set_psf_disk(fdr_plan* plan, double radius, float K, void* stream);
+int fdr_set_psf_disk_cls(fdr_plan* plan, double radius, float K, float gamma, void* stream);
+int fdr_set_operator_psf_disk(fdr_plan* plan, double radius, void* stream);
+int fdr_estimate_defocus_f32(fdr_plan* plan, const float* img_host, int rows, int cols, int stride, int min_diameter, int max_diameter,
+                             double angle_step_deg, fdr_defocus_estimate* est, float* profile_host);
+int fdr_estimate_defocus_f32_dev(fdr_plan* plan, const float* d_img, int rows, int cols, int stride, int min_diameter, int max_diameter,
+                                 double angle_step_deg, fdr_defocus_estimate* est, float* d_profile, void* stream);
+int fdr_estimate_blur_f32(fdr_plan* plan, const float* img_host, int rows, int cols, int stride, int min_length, int max_length,
+                          double motion_step_deg, int min_diameter, int max_diameter, double defocus_step_deg,
+                          fdr_motion_estimate* motion, fdr_defocus_estimate* defocus, int* kind);
+int fdr_estimate_blur_f32_dev(fdr_plan* plan, const float* d_img, int rows, int cols, int stride, int min_length, int max_length,
+                              double motion_step_deg, int min_diameter, int max_diameter, double defocus_step_deg,
+                              fdr_motion_estimate* motion, fdr_defocus_estimate* defocus, int* kind, void* stream);
+int fdr_blur_kind(double motion_confidence, double defocus_confidence);
+
 /* -- choosing the regularisation weight from the picture (Gonzalez & Woods section 5.9, Golub, Heath & Wahba
  *    1979, Immerkaer 1996).  The plan is M x N, the image window rows x cols (row stride `stride`) at its top-left corner, pad(d) is
  *    d on the window and 0 elsewhere, H the DFT2 of the operator PSF (fdr_set_operator_psf*), L(u, v) = 4 sin^2(pi u / M) +

@@ -478,6 +478,43 @@ inline fdr_motion_estimate estimateMotionBlur(const Mat& gray, int min_length = 
     }
     return est;
 }
+// The defocus blur of a one-channel picture (fdr_estimate_defocus_f32, include/fdr.h): the radius of the uniform disk, which goes
+// straight into diskBlurKernel, the ring it was read from and the confidence (below FDR_DEFOCUS_CONF_MIN: no ring).  Plan and
+// defaults as estimateMotionBlur.
+inline fdr_defocus_estimate estimateDefocusBlur(const Mat& gray, int min_diameter = 0, int max_diameter = 0, double angle_step = 0) {
+    Mat src = gray.isContinuous() ? gray : gray.clone();
+    fdr_plan* plan = nullptr;
+    FDR_CHECK(fdr_plan_create(defaults().device, std::max(32, fdr_optimal_dft_size(src.rows)), std::max(32, fdr_optimal_dft_size(src.cols)),
+                              FDR_MODE_FAST, FDR_FLAG_MIXED_RADIX, &plan));
+    fdr_defocus_estimate est{};
+    const int rc = fdr_estimate_defocus_f32(plan, src.ptr<float>(0), src.rows, src.cols, src.cols, min_diameter, max_diameter, angle_step, &est,
+                                            nullptr);
+    const std::string err = rc == FDR_OK ? std::string() : std::string(fdr_last_error());
+    fdr_plan_destroy(plan);
+    if (rc != FDR_OK) {
+        std::cerr << "Error: " << __FILE__ << ":" << __LINE__ << ", " << err << "\n";
+        exit(1);
+    }
+    return est;
+}
+// Both estimates of a one-channel picture from one cepstrum and the kind of blur they point to (fdr_estimate_blur_f32): each
+// estimate is what estimateMotionBlur / estimateDefocusBlur return with their defaults, kind one of FDR_BLUR_NONE / _MOTION / _DEFOCUS.
+struct BlurEstimate { int kind; fdr_motion_estimate motion; fdr_defocus_estimate defocus; };
+inline BlurEstimate estimateBlur(const Mat& gray) {
+    Mat src = gray.isContinuous() ? gray : gray.clone();
+    fdr_plan* plan = nullptr;
+    FDR_CHECK(fdr_plan_create(defaults().device, std::max(32, fdr_optimal_dft_size(src.rows)), std::max(32, fdr_optimal_dft_size(src.cols)),
+                              FDR_MODE_FAST, FDR_FLAG_MIXED_RADIX, &plan));
+    BlurEstimate b{};
+    const int rc = fdr_estimate_blur_f32(plan, src.ptr<float>(0), src.rows, src.cols, src.cols, 0, 0, 0.0, 0, 0, 0.0, &b.motion, &b.defocus, &b.kind);
+    const std::string err = rc == FDR_OK ? std::string() : std::string(fdr_last_error());
+    fdr_plan_destroy(plan);
+    if (rc != FDR_OK) {
+        std::cerr << "Error: " << __FILE__ << ":" << __LINE__ << ", " << err << "\n";
+        exit(1);
+    }
+    return b;
+}
 // K or gamma of the Wiener / CLS filter for one blurred channel and its PSF (fdr_choose_reg_f32, include/fdr.h): by generalised
 // cross-validation or the discrepancy principle (method), searching K or gamma (param) with the other weight at `fixed`; sigma 0 =
 // estimated from the picture (discrepancy principle only).  Its own FDR_MODE_FAST plan (the one of richardsonLucy_RGB: each dimension

@@ -1,6 +1,7 @@
 // utils.hpp -- drop-in counterpart of the reference's utils.hpp (same names, same argument meaning):
 //   getElapsedMs            reference utils.hpp:9-12
 //   motionBlurKernel        reference utils.hpp:15-24   -> PSF kernel on the GPU (fdr_psf_motion)
+//   diskBlurKernel          (no counterpart)            -> the defocus PSF on the GPU (fdr_psf_disk)
 //   nextPowerOfTwo / getNextPowerOf2   :27-37           -> fdr_next_pow2
 //   autoPadToPowerOfTwo     :40-47
 //   isPowerOfTwo            :50-52                      -> fdr_is_pow2
@@ -10,6 +11,7 @@
 #include "fdr.h"
 #include "fdr_mat.hpp"
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -35,6 +37,14 @@ inline Mat motionBlurKernel(int size, double angle) {
     Mat rotated(size, size, CV_32F);
     FDR_CHECK(fdr_psf_motion(size, angle, rotated.ptr<float>(0)));
     return rotated;
+}
+
+// the uniform disk of `radius` px (an out-of-focus blur), 2 ceil(radius) + 1 pixels square, centred, sum 1
+inline Mat diskBlurKernel(double radius) {
+    const int size = radius > 0.0 && radius <= 127.0 ? 2 * (int)std::ceil(radius) + 1 : 1;  // (a bad radius: the library's message)
+    Mat disk(size, size, CV_32F);
+    FDR_CHECK(fdr_psf_disk(size, radius, disk.ptr<float>(0)));
+    return disk;
 }
 
 inline int nextPowerOfTwo(int n) { return fdr_next_pow2(n); }

@@ -127,6 +127,12 @@ class MotionEstimateC(ctypes.Structure):
                 ("n_angles", ctypes.c_int), ("n_lengths", ctypes.c_int)]
 
 
+class DefocusEstimateC(ctypes.Structure):
+    """fdr_defocus_estimate of include/fdr.h"""
+    _fields_ = [("diameter", ctypes.c_int), ("ring", ctypes.c_double), ("radius", ctypes.c_double), ("score", ctypes.c_float),
+                ("confidence", ctypes.c_float), ("n_angles", ctypes.c_int), ("n_diameters", ctypes.c_int)]
+
+
 class RegParams(ctypes.Structure):
     """fdr_reg_params of include/fdr.h"""
     _fields_ = [("method", ctypes.c_int), ("param", ctypes.c_int), ("fixed", ctypes.c_float), ("sigma", ctypes.c_float),
@@ -149,6 +155,14 @@ RegChoice = collections.namedtuple("RegChoice", "value sigma residual trace gcv 
 MotionEstimate = collections.namedtuple("MotionEstimate", "length angle score confidence n_angles n_lengths")
 
 
+# the result of Plan.estimate_defocus* / estimateDefocusBlur: the ring's diameter (px, whole and sub-pixel), the disk radius it stands
+# for (goes straight into psf_disk / Plan.set_psf_disk), the profile minimum, its confidence and the shape of the search
+DefocusEstimate = collections.namedtuple("DefocusEstimate", "diameter ring radius score confidence n_angles n_diameters")
+# the result of Plan.estimate_blur* / estimateBlur: both estimates of one cepstrum and the blur kind they point to (BLUR_*)
+BlurEstimate = collections.namedtuple("BlurEstimate", "kind motion defocus")
+BLUR_NONE, BLUR_MOTION, BLUR_DEFOCUS = 0, 1, 2
+
+
 def _motion_table_shape(rows, cols, min_length, max_length, angle_step):
     """(n_angles, n_lengths) of the estimate's table, with fdr.h's defaults for arguments of 0"""
     lo = int(min_length) or 3
@@ -157,6 +171,10 @@ def _motion_table_shape(rows, cols, min_length, max_length, angle_step):
     if not (0 < step <= 90) or hi < lo or math.ceil(180.0 / step) * (hi - lo + 1) > 1 << 26:
         return 1, 1  # refused by the library before it writes anything
     return int(math.ceil(180.0 / step)), hi - lo + 1
+
+
+def _defocus_estimate(est):
+    return DefocusEstimate(est.diameter, est.ring, est.radius, est.score, est.confidence, est.n_angles, est.n_diameters)
 
 
 class FdrError(RuntimeError):
@@ -260,6 +278,16 @@ def _signatures():
         "fdr_cepstrum_f32_dev": (ci, [vp, vp, ci, ci, ci, vp, vp]),
         "fdr_estimate_motion_f32": (ci, [vp, vp, ci, ci, ci, ci, ci, cd, P(MotionEstimateC), vp]),
         "fdr_estimate_motion_f32_dev": (ci, [vp, vp, ci, ci, ci, ci, ci, cd, P(MotionEstimateC), vp, vp]),
+        "fdr_psf_disk": (ci, [ci, cd, vp]),
+        "fdr_psf_disk_dev": (ci, [ci, ci, cd, vp, vp]),
+        "fdr_set_psf_disk": (ci, [vp, cd, cf, vp]),
+        "fdr_set_psf_disk_cls": (ci, [vp, cd, cf, cf, vp]),
+        "fdr_set_operator_psf_disk": (ci, [vp, cd, vp]),
+        "fdr_estimate_defocus_f32": (ci, [vp, vp, ci, ci, ci, ci, ci, cd, P(DefocusEstimateC), vp]),
+        "fdr_estimate_defocus_f32_dev": (ci, [vp, vp, ci, ci, ci, ci, ci, cd, P(DefocusEstimateC), vp, vp]),
+        "fdr_estimate_blur_f32": (ci, [vp, vp, ci, ci, ci, ci, ci, cd, ci, ci, cd, P(MotionEstimateC), P(DefocusEstimateC), P(ci)]),
+        "fdr_estimate_blur_f32_dev": (ci, [vp, vp, ci, ci, ci, ci, ci, cd, ci, ci, cd, P(MotionEstimateC), P(DefocusEstimateC), P(ci), vp]),
+        "fdr_blur_kind": (ci, [cd, cd]),
         "fdr_richardson_lucy_auto_f32": (ci, [vp, vp, ci, ci, ci, vp, ci, vp, ci, P(RlAutoParams), P(RlAutoResultC), vp]),
         "fdr_richardson_lucy_auto_f32_dev": (ci, [vp, vp, ci, ci, ci, vp, ci, vp, ci, P(RlAutoParams), P(RlAutoResultC), vp, vp]),
         "fdr_noise_sigma_f32": (ci, [ci, vp, ci, ci, ci, P(cd)]),
@@ -467,6 +495,13 @@ class Plan:
             _check(lib.fdr_set_psf_motion_cls(self._h, int(size), float(angle), ctypes.c_float(K), ctypes.c_float(gamma),
                                               _stream(stream)))
 
+    def set_psf_disk(self, radius, K=0.01, gamma=0.0, stream=None):
+        """the Wiener (gamma = 0) or CLS filter of the disk of `radius` px, size 2 ceil(radius) + 1, generated on the device"""
+        if gamma == 0:
+            _check(lib.fdr_set_psf_disk(self._h, float(radius), ctypes.c_float(K), _stream(stream)))
+        else:
+            _check(lib.fdr_set_psf_disk_cls(self._h, float(radius), ctypes.c_float(K), ctypes.c_float(gamma), _stream(stream)))
+
     # the prepared filter as an opaque block (one rank's PSF spectrum handed to the others: fft/fft_mpi.cpp:334-378)
     def filter_bytes(self):
         n = ctypes.c_size_t(0)
@@ -534,6 +569,9 @@ class Plan:
 
     def set_operator_psf_motion(self, size, angle, stream=None):
         _check(lib.fdr_set_operator_psf_motion(self._h, int(size), float(angle), _stream(stream)))
+
+    def set_operator_psf_disk(self, radius, stream=None):
+        _check(lib.fdr_set_operator_psf_disk(self._h, float(radius), _stream(stream)))
 
     def blur(self, img, adjoint=False):
         """blur(img) = window(IDFT2(H . DFT2(pad(img)))), or the adjoint with conj(H); host arrays."""
@@ -823,6 +861,51 @@ class Plan:
                                                float(angle_step), ctypes.byref(est), ctypes.c_void_p(int(d_scores)) if d_scores else None,
                                                _stream(stream)))
         return MotionEstimate(est.length, est.angle_deg, est.score, est.confidence, est.n_angles, est.n_lengths)
+
+    # the defocus estimate (include/fdr.h): the ring of a disk blur in the same cepstrum, and both estimates from one cepstrum
+    def estimate_defocus(self, img, min_diameter=0, max_diameter=0, angle_step=0.0, return_profile=False):
+        """the disk radius of the window img (host array): a DefocusEstimate, and with return_profile=True also the profile T
+        (n_diameters float32).  0 selects an argument's default, as in estimate_motion."""
+        img = np.ascontiguousarray(img, dtype=np.float32)
+        rows, cols = img.shape
+        est = DefocusEstimateC()
+        prof = np.empty(_motion_table_shape(rows, cols, min_diameter, max_diameter, angle_step)[1], dtype=np.float32) if return_profile else None
+        _check(lib.fdr_estimate_defocus_f32(self._h, _ptr(img), rows, cols, cols, int(min_diameter), int(max_diameter), float(angle_step),
+                                            ctypes.byref(est), _ptr(prof) if return_profile else None))
+        res = _defocus_estimate(est)
+        if return_profile:
+            assert prof.shape == (est.n_diameters,)
+            return res, prof
+        return res
+
+    def estimate_defocus_dev(self, d_img, rows, cols, stride, min_diameter=0, max_diameter=0, angle_step=0.0, d_profile=None, stream=None):
+        """the same on a device window; d_profile (n_diameters floats) may be None.  Returns after the work on `stream`."""
+        est = DefocusEstimateC()
+        _check(lib.fdr_estimate_defocus_f32_dev(self._h, ctypes.c_void_p(int(d_img)), rows, cols, stride, int(min_diameter), int(max_diameter),
+                                                float(angle_step), ctypes.byref(est), ctypes.c_void_p(int(d_profile)) if d_profile else None,
+                                                _stream(stream)))
+        return _defocus_estimate(est)
+
+    def estimate_blur(self, img, min_length=0, max_length=0, motion_step=0.0, min_diameter=0, max_diameter=0, defocus_step=0.0):
+        """both estimates of the window img (host array) from one cepstrum: BlurEstimate(kind, MotionEstimate, DefocusEstimate), each
+        part what estimate_motion / estimate_defocus return, kind one of BLUR_NONE, BLUR_MOTION, BLUR_DEFOCUS"""
+        img = np.ascontiguousarray(img, dtype=np.float32)
+        mo, de, kind = MotionEstimateC(), DefocusEstimateC(), ctypes.c_int(0)
+        _check(lib.fdr_estimate_blur_f32(self._h, _ptr(img), img.shape[0], img.shape[1], img.shape[1], int(min_length), int(max_length),
+                                         float(motion_step), int(min_diameter), int(max_diameter), float(defocus_step), ctypes.byref(mo),
+                                         ctypes.byref(de), ctypes.byref(kind)))
+        return BlurEstimate(kind.value, MotionEstimate(mo.length, mo.angle_deg, mo.score, mo.confidence, mo.n_angles, mo.n_lengths),
+                            _defocus_estimate(de))
+
+    def estimate_blur_dev(self, d_img, rows, cols, stride, min_length=0, max_length=0, motion_step=0.0, min_diameter=0, max_diameter=0,
+                          defocus_step=0.0, stream=None):
+        """the same on a device window.  Returns after the work on `stream`."""
+        mo, de, kind = MotionEstimateC(), DefocusEstimateC(), ctypes.c_int(0)
+        _check(lib.fdr_estimate_blur_f32_dev(self._h, ctypes.c_void_p(int(d_img)), rows, cols, stride, int(min_length), int(max_length),
+                                             float(motion_step), int(min_diameter), int(max_diameter), float(defocus_step), ctypes.byref(mo),
+                                             ctypes.byref(de), ctypes.byref(kind), _stream(stream)))
+        return BlurEstimate(kind.value, MotionEstimate(mo.length, mo.angle_deg, mo.score, mo.confidence, mo.n_angles, mo.n_lengths),
+                            _defocus_estimate(de))
 
     # choosing the regularisation weight (include/fdr.h): noise estimate, residual / trace curve, discrepancy principle and GCV
     def noise_sigma(self, img):
@@ -1148,6 +1231,37 @@ def estimateMotionBlur(img, device=0, min_length=0, max_length=0, angle_step=0.0
     M, N = _motion_plan_size(img.shape[0], img.shape[1])
     with Plan(M, N, MODE_FAST, device, flags=FLAG_MIXED_RADIX) as p:
         return p.estimate_motion(img, min_length, max_length, angle_step, scores)
+
+
+def psf_disk(size, radius):
+    """fdr_psf_disk: the size x size uniform disk of `radius` px centred at size // 2, each pixel the share of its square inside the
+    disk (16 x 16 sub-samples), sum 1; generated by the device PSF kernel"""
+    out = np.empty((int(size), int(size)), dtype=np.float32) if size > 0 else np.empty((1, 1), dtype=np.float32)
+    _check(lib.fdr_psf_disk(int(size), float(radius), _ptr(out)))
+    return out
+
+
+def estimateDefocusBlur(img, device=0, min_diameter=0, max_diameter=0, angle_step=0.0, return_profile=False):
+    """the disk radius of an out-of-focus picture, by the ring in its power cepstrum on the device (fdr_estimate_defocus_f32).  img
+    and plan as estimateMotionBlur.  Returns a DefocusEstimate (and the profile with return_profile=True); the radius goes
+    straight into psf_disk / Plan.set_psf_disk."""
+    img = np.asarray(img, dtype=np.float32)
+    if img.ndim == 3:
+        img = img.mean(axis=2, dtype=np.float32)
+    M, N = _motion_plan_size(img.shape[0], img.shape[1])
+    with Plan(M, N, MODE_FAST, device, flags=FLAG_MIXED_RADIX) as p:
+        return p.estimate_defocus(img, min_diameter, max_diameter, angle_step, return_profile)
+
+
+def estimateBlur(img, device=0):
+    """the kind of blur of a picture and both estimates, from one cepstrum (fdr_estimate_blur_f32): a BlurEstimate.  img and plan as
+    estimateMotionBlur."""
+    img = np.asarray(img, dtype=np.float32)
+    if img.ndim == 3:
+        img = img.mean(axis=2, dtype=np.float32)
+    M, N = _motion_plan_size(img.shape[0], img.shape[1])
+    with Plan(M, N, MODE_FAST, device, flags=FLAG_MIXED_RADIX) as p:
+        return p.estimate_blur(img)
 
 
 def chooseRegularisation(img, psf, method=REG_GCV, param=REG_PARAM_GAMMA, fixed=0.0, sigma=0.0, tau=0.0, lo=0.0, hi=0.0, n_grid=0, refine=-1,

@@ -1,5 +1,6 @@
 // fdr_api_motion.hip -- the motion-blur estimate (fdr_motion.hip): window / pad, the plan's complex 2-D transform forward, log |G|,
-// the transform inverse, then the score gather (fdr_estimate_motion_f32*) or the real part (fdr_cepstrum_f32*).
+// the transform inverse, then the score gather (fdr_estimate_motion_f32*) or the real part (fdr_cepstrum_f32*).  The arguments, the
+// workspace, the cepstrum and the search are shared with the defocus and the combined estimate (fdr_api_defocus.hip; fdr_host.hpp).
 #include "fdr_host.hpp"
 
 #include <algorithm>
@@ -12,42 +13,6 @@ namespace {
 
 constexpr int kMotionMinWindow = 16;
 constexpr size_t kMotionMaxTable = (size_t)1 << 26;
-
-// the search arguments with their defaults (0 selects one), after the plan and window checks; FDR_ERR_ARG for anything outside
-// the documented ranges
-struct MotionArgs { int min_length, max_length, n_angles, n_lengths; double step; };
-int motion_args(const fdr_plan* p, const char* fn, int rows, int cols, int stride, int min_length, int max_length, double step, MotionArgs* a) {
-    const int rc = check_window(p, fn, NEED_MOTION, rows, cols, stride, cols, kMotionMinWindow);
-    if (rc != FDR_OK) return rc;
-    if (min_length < 0 || max_length < 0) return fail(FDR_ERR_ARG, std::string(fn) + ": negative length");
-    if (!std::isfinite(step) || step < 0.0 || step > 90.0) return fail(FDR_ERR_ARG, std::string(fn) + ": the angle step must be finite and in (0, 90]");
-    a->min_length = min_length ? min_length : 3;
-    a->max_length = max_length ? max_length : std::min(100, std::min(rows, cols) / 4);
-    a->step = step != 0.0 ? step : 0.5;
-    if (a->min_length < 2) return fail(FDR_ERR_ARG, std::string(fn) + ": min_length < 2");
-    if (a->min_length > a->max_length) return fail(FDR_ERR_ARG, std::string(fn) + ": min_length > max_length");
-    if (a->max_length > std::min(p->M, p->N) / 2 - 2) return fail(FDR_ERR_ARG, std::string(fn) + ": max_length > min(M, N) / 2 - 2");
-    const double na = std::ceil(180.0 / a->step);
-    a->n_lengths = a->max_length - a->min_length + 1;
-    if (na * a->n_lengths > (double)kMotionMaxTable) return fail(FDR_ERR_ARG, std::string(fn) + ": score table above 2^26 entries");
-    a->n_angles = (int)na;
-    return FDR_OK;
-}
-
-// the fixed part of the workspace (first call on the plan)
-int ensure_motion_workspace(fdr_plan* p, const char* fn) {
-    if (p->mo_block) return FDR_OK;
-    const size_t plane = (size_t)p->M * p->N * sizeof(float2);
-    const size_t part = ((size_t)motion_pad_partials(p->M, p->N) + 1) * sizeof(double);
-    const size_t hann = ((size_t)p->M + p->N) * sizeof(float);
-    char* b = nullptr;
-    if (hipMalloc((void**)&b, plane + part + hann) != hipSuccess) return fail(FDR_ERR_ALLOC, std::string(fn) + ": hipMalloc of the workspace failed");
-    p->mo_block = b;
-    p->mo_plane = reinterpret_cast<float2*>(b);
-    p->mo_part = reinterpret_cast<double*>(b + plane);
-    p->mo_hann = reinterpret_cast<float*>(b + plane + part);
-    return FDR_OK;
-}
 
 // the table (device and host) and the trig table for `a`, grown when a larger one is asked for
 int ensure_motion_table(fdr_plan* p, const char* fn, const MotionArgs& a) {
@@ -66,8 +31,46 @@ int ensure_motion_table(fdr_plan* p, const char* fn, const MotionArgs& a) {
     return FDR_OK;
 }
 
-// c (scaled by 1 / (M N) already) in the real parts of mo_plane, and sum |x| in mo_part[motion_pad_partials]
+}  // namespace
+
+namespace fdr {
+
+int motion_args(const fdr_plan* p, const char* fn, int rows, int cols, int stride, int min_length, int max_length, double step, MotionArgs* a,
+                const char* what) {
+    const std::string f(fn), w(what);
+    const int rc = check_window(p, fn, NEED_MOTION, rows, cols, stride, cols, kMotionMinWindow);
+    if (rc != FDR_OK) return rc;
+    if (min_length < 0 || max_length < 0) return fail(FDR_ERR_ARG, f + ": negative " + w);
+    if (!std::isfinite(step) || step < 0.0 || step > 90.0) return fail(FDR_ERR_ARG, std::string(fn) + ": the angle step must be finite and in (0, 90]");
+    a->min_length = min_length ? min_length : 3;
+    a->max_length = max_length ? max_length : std::min(100, std::min(rows, cols) / 4);
+    a->step = step != 0.0 ? step : 0.5;
+    if (a->min_length < 2) return fail(FDR_ERR_ARG, f + ": min_" + w + " < 2");
+    if (a->min_length > a->max_length) return fail(FDR_ERR_ARG, f + ": min_" + w + " > max_" + w);
+    if (a->max_length > std::min(p->M, p->N) / 2 - 2) return fail(FDR_ERR_ARG, f + ": max_" + w + " > min(M, N) / 2 - 2");
+    const double na = std::ceil(180.0 / a->step);
+    a->n_lengths = a->max_length - a->min_length + 1;
+    if (na * a->n_lengths > (double)kMotionMaxTable) return fail(FDR_ERR_ARG, std::string(fn) + ": score table above 2^26 entries");
+    a->n_angles = (int)na;
+    return FDR_OK;
+}
+
+int ensure_motion_workspace(fdr_plan* p, const char* fn) {
+    if (p->mo_block) return FDR_OK;
+    const size_t plane = (size_t)p->M * p->N * sizeof(float2);
+    const size_t part = ((size_t)motion_pad_partials(p->M, p->N) + 1) * sizeof(double);
+    const size_t hann = ((size_t)p->M + p->N) * sizeof(float);
+    char* b = nullptr;
+    if (hipMalloc((void**)&b, plane + part + hann) != hipSuccess) return fail(FDR_ERR_ALLOC, std::string(fn) + ": hipMalloc of the workspace failed");
+    p->mo_block = b;
+    p->mo_plane = reinterpret_cast<float2*>(b);
+    p->mo_part = reinterpret_cast<double*>(b + plane);
+    p->mo_hann = reinterpret_cast<float*>(b + plane + part);
+    return FDR_OK;
+}
+
 int motion_cepstrum_plane(fdr_plan* p, const float* d_img, int rows, int cols, int stride, hipStream_t s) {
+    ScopedPass t(p, s, "cepstrum");
     FDR_HIP(launch_motion_window(d_img, rows, cols, stride, p->mo_hann, p->mo_plane, p->M, p->N, p->mo_part, s));
     int rc = dft2d_dev(p, p->mo_plane, p->slots[0].work2, false, s);
     if (rc != FDR_OK) return rc;
@@ -75,15 +78,6 @@ int motion_cepstrum_plane(fdr_plan* p, const float* d_img, int rows, int cols, i
     return dft2d_dev(p, p->mo_plane, p->slots[0].work2, true, s);
 }
 
-int cepstrum_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, int cols, int stride, float* d_out, hipStream_t s) {
-    int rc = ensure_motion_workspace(p, fn);
-    if (rc == FDR_OK) rc = motion_cepstrum_plane(p, d_img, rows, cols, stride, s);
-    if (rc != FDR_OK) return rc;
-    FDR_HIP(launch_real_part(p->mo_plane, d_out, (size_t)p->M * p->N, s));
-    return FDR_OK;
-}
-
-// median of v (destroys its order), as numpy.median: the mean of the two middle values for an even count
 double median_of(std::vector<double>& v) {
     const size_t n = v.size(), h = n / 2;
     std::nth_element(v.begin(), v.begin() + h, v.end());
@@ -93,11 +87,8 @@ double median_of(std::vector<double>& v) {
     return 0.5 * (lo + hi);
 }
 
-// the whole estimate on `s`, synchronous: d_scores (may be null) gets a copy of the table
-int estimate_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, int cols, int stride, const MotionArgs& a,
-                      fdr_motion_estimate* est, float* d_scores, hipStream_t s) {
-    int rc = ensure_motion_workspace(p, fn);
-    if (rc == FDR_OK) rc = ensure_motion_table(p, fn, a);
+int motion_search_prepare(fdr_plan* p, const char* fn, const MotionArgs& a, hipStream_t s) {
+    const int rc = ensure_motion_table(p, fn, a);
     if (rc != FDR_OK) return rc;
     const double pi = 3.14159265358979323846;
     p->mo_trig_host.resize(2 * (size_t)a.n_angles);
@@ -106,18 +97,23 @@ int estimate_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows,
         p->mo_trig_host[k] = std::cos(th);
         p->mo_trig_host[(size_t)a.n_angles + k] = std::sin(th);
     }
-    const size_t nt = (size_t)a.n_angles * a.n_lengths;
     FDR_HIP(hipMemcpyAsync(p->mo_trig, p->mo_trig_host.data(), p->mo_trig_host.size() * sizeof(double), hipMemcpyHostToDevice, s));
-    rc = motion_cepstrum_plane(p, d_img, rows, cols, stride, s);
-    if (rc != FDR_OK) return rc;
+    return FDR_OK;
+}
+
+int motion_search_launch(fdr_plan* p, const MotionArgs& a, float* d_scores, hipStream_t s) {
+    const size_t nt = (size_t)a.n_angles * a.n_lengths;
+    ScopedPass t(p, s, "motion score");
     FDR_HIP(launch_motion_score(p->mo_plane, p->M, p->N, p->mo_trig, a.n_angles, a.min_length, a.n_lengths, p->mo_table, s));
     if (d_scores) FDR_HIP(hipMemcpyAsync(d_scores, p->mo_table, nt * sizeof(float), hipMemcpyDeviceToDevice, s));
-    double sum = 0.0;
     FDR_HIP(hipMemcpyAsync(p->mo_table_host.data(), p->mo_table, nt * sizeof(float), hipMemcpyDeviceToHost, s));
-    FDR_HIP(hipMemcpyAsync(&sum, p->mo_part + motion_pad_partials(p->M, p->N), sizeof(double), hipMemcpyDeviceToHost, s));
-    FDR_HIP(hipStreamSynchronize(s));
+    return FDR_OK;
+}
+
+void motion_search_pick(const fdr_plan* p, const MotionArgs& a, double sum, fdr_motion_estimate* est) {
+    const size_t nt = (size_t)a.n_angles * a.n_lengths;
     *est = fdr_motion_estimate{0, 0.0, 0.f, 0.f, a.n_angles, a.n_lengths};
-    if (!(sum > 0.0)) return FDR_OK;  // an all-zero window: the defined zero result (the table is all zeros)
+    if (!(sum > 0.0)) return;  // an all-zero window: the defined zero result (the table is all zeros)
     const float* S = p->mo_table_host.data();
     size_t kmin = 0;
     for (size_t k = 1; k < nt; ++k)
@@ -131,6 +127,32 @@ int estimate_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows,
     est->angle_deg = (double)(kmin / a.n_lengths) * a.step;
     est->score = S[kmin];
     est->confidence = mad > 0.0 ? (float)((med - smin) / (1.4826 * mad)) : 0.f;
+}
+
+}  // namespace fdr
+
+namespace {
+
+int cepstrum_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, int cols, int stride, float* d_out, hipStream_t s) {
+    int rc = ensure_motion_workspace(p, fn);
+    if (rc == FDR_OK) rc = motion_cepstrum_plane(p, d_img, rows, cols, stride, s);
+    if (rc != FDR_OK) return rc;
+    FDR_HIP(launch_real_part(p->mo_plane, d_out, (size_t)p->M * p->N, s));
+    return FDR_OK;
+}
+
+// the whole estimate on `s`, synchronous: d_scores (may be null) gets a copy of the table
+int estimate_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, int cols, int stride, const MotionArgs& a,
+                      fdr_motion_estimate* est, float* d_scores, hipStream_t s) {
+    int rc = ensure_motion_workspace(p, fn);
+    if (rc == FDR_OK) rc = motion_search_prepare(p, fn, a, s);
+    if (rc == FDR_OK) rc = motion_cepstrum_plane(p, d_img, rows, cols, stride, s);
+    if (rc == FDR_OK) rc = motion_search_launch(p, a, d_scores, s);
+    if (rc != FDR_OK) return rc;
+    double sum = 0.0;
+    FDR_HIP(hipMemcpyAsync(&sum, p->mo_part + motion_pad_partials(p->M, p->N), sizeof(double), hipMemcpyDeviceToHost, s));
+    FDR_HIP(hipStreamSynchronize(s));
+    motion_search_pick(p, a, sum, est);
     return FDR_OK;
 }
 

@@ -284,7 +284,7 @@ hipError_t copy_window(float* dst, int dst_stride, const float* src, int src_str
 namespace fdr {
 
 int set_psf(fdr_plan* p, const char* fn, const PsfSource& src, bool op, float K, float gamma, hipStream_t s) {
-    if (!p || (src.kind != PSF_MOTION && !src.ptr)) return null_arg(fn);
+    if (!p || ((src.kind == PSF_DEV || src.kind == PSF_HOST) && !src.ptr)) return null_arg(fn);
     int rc = op ? check_plan(p, fn, NEED_OPERATOR) : filter_check(p, fn, gamma);
     if (rc != FDR_OK) return rc;
     if (src.rows <= 0 || src.cols <= 0 || src.stride < src.cols) return fail(FDR_ERR_ARG, std::string(fn) + ": bad PSF shape");
@@ -300,6 +300,8 @@ int set_psf(fdr_plan* p, const char* fn, const PsfSource& src, bool op, float K,
         stride = src.cols;
         if (src.kind == PSF_MOTION) {
             FDR_HIP(launch_psf_motion(src.rows, src.angle_deg, p->psf_dev, s));
+        } else if (src.kind == PSF_DISK) {
+            FDR_HIP(launch_psf_disk(src.rows, src.angle_deg, p->psf_dev, s));
         } else {
             ScopedPhase ph(p, FDR_PHASE_H2D, nullptr);
             FDR_HIP(hipMemcpy2D(p->psf_dev, (size_t)src.cols * sizeof(float), src.ptr, (size_t)src.stride * sizeof(float),
@@ -440,7 +442,7 @@ int fdr_plan_destroy(fdr_plan* p) {
     p->timer.destroy();
     (void)hipFree(p->filt); (void)hipFree(p->psf_dev); (void)hipFree(p->lap); (void)hipFree(p->op_h);
     (void)hipFree(p->stage_in); (void)hipFree(p->stage_out);
-    (void)hipFree(p->mo_block); (void)hipFree(p->mo_table); (void)hipFree(p->mo_trig); (void)hipFree(p->tv_block);
+    (void)hipFree(p->mo_block); (void)hipFree(p->mo_table); (void)hipFree(p->mo_trig); (void)hipFree(p->df_block); (void)hipFree(p->tv_block);
     (void)hipFree(p->rf_block); (void)hipFree(p->rt_block); (void)hipFree(p->ra_block); (void)hipFree(p->rg_block);
     (void)hipFree(p->bl_block); (void)hipFree(p->bl_w);
     (void)hipFree(p->rs_block); (void)hipFree(p->rs_trace); (void)hipFree(p->rs_planes);

@@ -142,6 +142,13 @@ struct fdr_plan {
     size_t mo_table_cap = 0, mo_trig_cap = 0;  // elements
     std::vector<float> mo_table_host;
     std::vector<double> mo_trig_host;
+    // defocus estimate (fdr_estimate_defocus_f32*, fdr_estimate_blur_f32*): beside the motion workspace, which it shares, one allocation
+    // of fixed size made by the first such call: the trig table (2 kDefocusMaxAngles doubles), then the profile T (kDefocusMaxDiameters floats)
+    void* df_block = nullptr;
+    double* df_trig = nullptr;
+    float* df_profile = nullptr;
+    std::vector<double> df_trig_host;
+    std::vector<float> df_profile_host;
     // free-boundary Richardson-Lucy (fdr_richardson_lucy_free_f32*): made by the first such call, kept until fdr_plan_destroy -- one
     // allocation holding three M x N real planes (the estimate u, wgt = 1 / coverage, dw = weights . max(d, 0) on the window) and the
     // 2 rlfree_partials(M, N) + 2 double partials of the two sums (r lives in slot 0's `raw`).  A batched call on groups of g images
@@ -310,9 +317,10 @@ int check_plan(const fdr_plan* p, const char* fn, PlanNeed need);
 // check_plan, then the rows x cols window (row stride `stride`, of the result `out_stride`): at least min x min, within M x N
 int check_window(const fdr_plan* p, const char* fn, PlanNeed need, int rows, int cols, int stride, int out_stride, int min = 1);
 
-// ---- the one path of the nine PSF setters (fdr_api_plan.hip) ----
-// A PSF is a device or a host pointer (rows x cols, row stride `stride`) or a generated motion PSF (size in all three).
-enum PsfKind { PSF_DEV, PSF_HOST, PSF_MOTION };
+// ---- the one path of the twelve PSF setters (fdr_api_plan.hip) ----
+// A PSF is a device or a host pointer (rows x cols, row stride `stride`) or a generated motion or disk PSF (size in all three;
+// angle_deg holds the disk's radius).
+enum PsfKind { PSF_DEV, PSF_HOST, PSF_MOTION, PSF_DISK };
 struct PsfSource { PsfKind kind; const float* ptr; int rows, cols, stride; double angle_deg; };
 // Checked completely, staged unless it is a device pointer, and built into the Wiener / CLS filter (op false; gamma 0 is the
 // Wiener filter) or into the blur / RL operator tables (op true).  A host PSF is ready when the call returns (fdr_batch_run relies
@@ -455,6 +463,25 @@ static_assert(kRegMaxCurve % kRegCandidates == 0, "the last sweep reads kRegCand
 // the entry points of fdr_api_tv.hip
 int tv_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, int cols, int stride, float* d_out, int out_stride,
                 const fdr_tv_params& prm, hipStream_t s);
+
+// ---- the motion-blur estimate (fdr_api_motion.hip), shared with the defocus and the combined estimate (fdr_api_defocus.hip) ----
+// the search arguments with their defaults (0 selects one), after the plan and window checks; FDR_ERR_ARG for anything outside
+// the documented ranges (`what` names the searched quantity in the message: "length", or "diameter" for the defocus search)
+struct MotionArgs { int min_length, max_length, n_angles, n_lengths; double step; };
+int motion_args(const fdr_plan* p, const char* fn, int rows, int cols, int stride, int min_length, int max_length, double step, MotionArgs* a,
+                const char* what = "length");
+// the fixed part of the workspace (first call on the plan)
+int ensure_motion_workspace(fdr_plan* p, const char* fn);
+// c (scaled by 1 / (M N) already) in the real parts of mo_plane, and sum |x| in mo_part[motion_pad_partials]
+int motion_cepstrum_plane(fdr_plan* p, const float* d_img, int rows, int cols, int stride, hipStream_t s);
+// the search on the plane, in three steps around the cepstrum: prepare (before it: the table grown to `a`, the trig table uploaded),
+// launch (after it: the score gather, the table to d_scores when that is not null and to the host copy, asynchronous on `s`) and,
+// once `s` is synchronised and `sum` (sum |x|) read back, the pick from the host copy
+int motion_search_prepare(fdr_plan* p, const char* fn, const MotionArgs& a, hipStream_t s);
+int motion_search_launch(fdr_plan* p, const MotionArgs& a, float* d_scores, hipStream_t s);
+void motion_search_pick(const fdr_plan* p, const MotionArgs& a, double sum, fdr_motion_estimate* est);
+// median of v (destroys its order), as numpy.median: the mean of the two middle values for an even count
+double median_of(std::vector<double>& v);
 
 // ---- the host-pointer form of a single-image call (fdr_api_plan.hip) ----
 // The rows x cols image in through the plan's staging, run(d_in, d_out) on the null stream, the out_rows x out_cols result back

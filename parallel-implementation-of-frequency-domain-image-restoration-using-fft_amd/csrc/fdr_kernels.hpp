@@ -234,6 +234,14 @@ hipError_t launch_motion_window(const float* img, int rows, int cols, int stride
 hipError_t launch_motion_log(float2* plane, int M, int N, const double* sum, hipStream_t s);
 hipError_t launch_motion_score(const float2* plane, int M, int N, const double* trig, int n_angles, int min_length, int n_lengths, float* table,
                                hipStream_t s);
+// (fdr_defocus.hip) the defocus estimate.  disk: fdr_psf_disk (size <= kDiskMaxSize, radius > 0; one workgroup).  profile: T[d -
+// min_diameter] = the median over a of the score launch_motion_score would put at table[a * n_diameters + d - min_diameter], from the
+// same plane and trig table; one workgroup per diameter, n_angles <= kDefocusMaxAngles
+constexpr int kDiskMaxSize = 256;
+constexpr int kDefocusMaxAngles = 4096;  // one column of scores in LDS: 16 KB
+hipError_t launch_psf_disk(int size, double radius, float* d_out, hipStream_t s);
+hipError_t launch_defocus_profile(const float2* plane, int M, int N, const double* trig, int n_angles, int min_diameter, int n_diameters,
+                                  float* T, hipStream_t s);
 
 // (fdr_reg.hip) choosing the regularisation weight.  noise: the Immerkaer sum S of |d * [[1,-2,1],[-2,4,-2],[1,-2,1]]| over the interior
 // of the rows x cols window (rows, cols >= 3) as reg_noise_partials(rows, cols) double partials, folded in a fixed order into

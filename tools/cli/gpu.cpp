@@ -1,4 +1,4 @@
-// gpu.cpp -- ./gpu <img-path> <psf-length> <psf-angle> [--out file] [--mode fast|parity] [--norm padded|cropped] [--host-epilogue]
+// gpu.cpp -- ./gpu <img-path> <psf-length> <psf-angle> | auto auto [--any-blur] | defocus <radius|auto> | blind <size>  [--out file] [--mode fast|parity] [--norm padded|cropped] [--host-epilogue]
 //           [--cls gamma|auto] [--k K|auto] [--reg gcv|discrepancy] [--sigma s] [--pad zero|smooth] [--rl iterations|auto [--accel] [--rl-tv lambda [--rl-tv-eps e]] [--free-boundary [--mask mask.png]] [--rl-max n] [--rl-stop residual|kl] [--gain g] [--rl-check c]] [--tv mu [--tv-iters n] [--tv-rho r]]
 // `auto auto` for length and angle: the blur is estimated first (fft_gpu::estimateMotionBlur on the per-pixel mean of B, G and R),
 // printed as `estimate: length L angle A confidence C`, and the run then goes on exactly as `./gpu <img-path> L A` would.
@@ -6,6 +6,12 @@
 // mean, with the PSF of the run; --reg names the method -- default gcv for gamma, discrepancy for K -- and --sigma the noise level of the
 // discrepancy principle, else estimated), printed as `regularisation: K k gamma g sigma s method m flags f`, and the run then goes on
 // exactly as `--k k --cls g` would (`--cls 0` is the Wiener filter).  It combines with `auto auto`.
+// `defocus <radius>` in place of length and angle: the PSF is the uniform disk of that radius (diskBlurKernel), and every leg and option
+// works as with a motion PSF.  `defocus auto`: the radius is estimated first (fft_gpu::estimateDefocusBlur on the same mean), printed as
+// `estimate: defocus radius R diameter D confidence C`, and the run then goes on exactly as `./gpu <img-path> defocus R` would.
+// `auto auto --any-blur`: both blurs are looked for in one cepstrum (fft_gpu::estimateBlur), printed as `estimate: kind motion length L
+// angle A confidence C` or `estimate: kind defocus radius R diameter D confidence C`, and the run goes on as `L A` or `defocus R` would;
+// `estimate: kind none ...` ends the run with a message and a non-zero exit code.  `defocus` beside `blind` is refused with a message.
 // `blind <size>` in place of length and angle, with --rl n: the PSF is not stated but refined from a size x size Gaussian start
 // (--psf-sigma s, default size / 4) by blind Richardson-Lucy on the per-pixel mean of B, G and R (fft_gpu::richardsonLucyBlind_RGB; --free-boundary,
 // --mask and --psf-hold h apply), printed as `blind: size S iterations n psf-sum 1 psf-peak P at (i, j)`; --psf-out file writes the
@@ -76,9 +82,18 @@ int main(int argc, char** argv) {
     string img_path = argv[1];
     const bool estimate = string(argv[2]) == "auto" && string(argv[3]) == "auto";
     const bool blind = string(argv[2]) == "blind";  // argv[3] is the PSF's size
-    if (!estimate && (string(argv[2]) == "auto" || string(argv[3]) == "auto")) { cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle>\n"; return -1; }
-    int psf_length = estimate ? 0 : atoi(argv[blind ? 3 : 2]);
-    double psf_angle = estimate || blind ? 0.0 : atof(argv[3]);
+    bool defocus = string(argv[2]) == "defocus";    // argv[3] is the disk's radius, or `auto`
+    const bool defocus_auto = defocus && string(argv[3]) == "auto";
+    if (!estimate && !defocus && (string(argv[2]) == "auto" || string(argv[3]) == "auto")) { cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle>\n"; return -1; }
+    int psf_length = estimate || defocus ? 0 : atoi(argv[blind ? 3 : 2]);
+    double psf_angle = estimate || blind || defocus ? 0.0 : atof(argv[3]);
+    double psf_radius = defocus && !defocus_auto ? atof(argv[3]) : 0.0;
+    bool any_blur = false;  // --any-blur, with `auto auto`: motion or defocus, whichever the picture shows
+    for (int i = 3; i < argc; ++i)
+        if ((defocus && string(argv[i]) == "blind") || (blind && string(argv[i]) == "defocus")) {
+            cout << "defocus states the PSF, blind refines one from a Gaussian start: they cannot be combined\n";
+            return -1;
+        }
     string out_path, raw_path, psf_out_path;  // --psf-out file (blind)
     int psf_hold = 0;                          // --psf-hold h (blind)
     double psf_sigma = 0.0;                    // --psf-sigma s (blind)
@@ -109,6 +124,7 @@ int main(int argc, char** argv) {
         else if (a == "--raw-out" && i + 1 < argc) raw_path = argv[++i];  // restored float planes B,G,R before white balance
         else if (a == "--host-epilogue") host_epilogue = true;
         else if (a == "--verify") verify = true;
+        else if (a == "--any-blur") any_blur = true;
         else if (a == "--mode" && i + 1 < argc) {
             parity = string(argv[++i]) == "parity";
             fft_gpu::set_mode(parity ? FDR_MODE_PARITY : FDR_MODE_FAST);
@@ -159,6 +175,8 @@ int main(int argc, char** argv) {
         else if (a == "--tv-rho" && i + 1 < argc) { tv_opts = true; tv_rho = strtof(argv[++i], nullptr); }
         else { cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle>\n"; return -1; }
     }
+    if (defocus && !defocus_auto && !(psf_radius > 0.0 && psf_radius <= 127.0)) { cout << "Usage: ./gpu <img-path> defocus <radius in (0, 127]|auto>\n"; return -1; }
+    if (any_blur && !estimate) { cout << "Usage: ./gpu <img-path> auto auto --any-blur\n"; return -1; }
     // one weight is searched at a time; --reg and --sigma belong to a search
     if ((cls_auto && k_auto) || (!(cls_auto || k_auto) && (!reg_method.empty() || (reg_sigma != 0.f && !rl_auto))) ||
         (!reg_method.empty() && reg_method != "gcv" && reg_method != "discrepancy") || !(K >= 0.f) || !(reg_sigma >= 0.f)) {
@@ -211,7 +229,7 @@ int main(int argc, char** argv) {
     img /= 255.0;
 
     Mat gray;  // the per-pixel mean of B, G and R: what the blur and the regularisation weight are found on
-    if (estimate || cls_auto || k_auto || rl_auto) {
+    if (estimate || defocus_auto || cls_auto || k_auto || rl_auto) {
         vector<Mat> bgr;
         split(img, bgr);
         gray = Mat(img.rows, img.cols, CV_32F);
@@ -219,8 +237,34 @@ int main(int argc, char** argv) {
             for (int c = 0; c < img.cols; ++c)
                 gray.ptr<float>(r)[c] = (bgr[0].ptr<float>(r)[c] + bgr[1].ptr<float>(r)[c] + bgr[2].ptr<float>(r)[c]) / 3.0f;
     }
-    if (estimate) {  // the blur from the picture itself
-        const fdr_motion_estimate est = fft_gpu::estimateMotionBlur(gray);
+    fdr_motion_estimate est{};
+    fdr_defocus_estimate dest{};
+    if (any_blur) {  // the kind of blur and its parameters from one cepstrum
+        const fft_gpu::BlurEstimate b = fft_gpu::estimateBlur(gray);
+        est = b.motion;
+        dest = b.defocus;
+        if (b.kind == FDR_BLUR_NONE) {
+            printf("estimate: kind none motion-confidence %.3f defocus-confidence %.3f\n", (double)est.confidence, (double)dest.confidence);
+            cout << "The picture shows neither a motion blur nor a defocus blur: nothing to restore\n";
+            return -1;
+        }
+        defocus = b.kind == FDR_BLUR_DEFOCUS;
+        if (defocus) printf("estimate: kind defocus radius %.17g diameter %d confidence %.3f\n", dest.radius, dest.diameter, (double)dest.confidence);
+        else printf("estimate: kind motion length %d angle %.17g confidence %.3f\n", est.length, est.angle_deg, (double)est.confidence);
+        fflush(stdout);
+        if (defocus) psf_radius = dest.radius;
+        else { psf_length = est.length; psf_angle = est.angle_deg; }
+    } else if (defocus_auto) {  // the disk's radius from the picture itself
+        dest = fft_gpu::estimateDefocusBlur(gray);
+        if (dest.diameter < 1) { cout << "Cannot estimate the blur of an all-zero picture\n"; return -1; }
+        printf("estimate: defocus radius %.17g diameter %d confidence %.3f\n", dest.radius, dest.diameter, (double)dest.confidence);
+        fflush(stdout);
+        if (dest.confidence < (float)FDR_DEFOCUS_CONF_MIN)
+            cerr << "[Warning] low confidence (" << dest.confidence << " < " << FDR_DEFOCUS_CONF_MIN
+                 << "): the picture shows no clear defocus ring; the estimate may be wrong\n";
+        psf_radius = dest.radius;
+    } else if (estimate) {  // the blur from the picture itself
+        est = fft_gpu::estimateMotionBlur(gray);
         if (est.length < 1) { cout << "Cannot estimate the blur of an all-zero picture\n"; return -1; }
         printf("estimate: length %d angle %.17g confidence %.3f\n", est.length, est.angle_deg, (double)est.confidence);
         fflush(stdout);
@@ -276,6 +320,8 @@ int main(int argc, char** argv) {
             if (!fdr_io::imwrite(psf_out_path, k8)) { cout << "Cannot write " << psf_out_path << "\n"; return -1; }
             cout << "Wrote " << psf_out_path << "\n";
         }
+    } else if (defocus) {
+        psf = diskBlurKernel(psf_radius);
     } else {
         psf = motionBlurKernel(psf_length, psf_angle);
     }
