@@ -325,9 +325,10 @@ int fdr_richardson_lucy_free_f32_dev(fdr_plan* plan, const float* d_img, int row
  *    once), a null pointer, whatever the single-image call of the form refuses for one image (plan, operator PSF, window, strides,
  *    iterations, norm_area, sigma, the output window), weights in the plain form, and an output that overlaps the input or the
  *    weights anywhere within the span of the batch (first element of image 0 to last element of image count - 1).  Neither _dev
- *    form allocates after its first call, and both stay asynchronous on `stream`.  The accelerated, data-stopped and blind
- *    iterations, TV, per-image weights, mixed-radix and full-spectrum plans and fdr_batch_run have no batched form (DESIGN.md
- *    section 24).  Per image and iteration a group of g moves 64 - 8 (1 - 1/g) bytes per padded pixel.                        */
+ *    form allocates after its first call, and both stay asynchronous on `stream`.  The accelerated iteration has the batched form
+ *    fdr_richardson_lucy_batch_accel_f32* below; the data-stopped and blind iterations, TV, per-image weights, mixed-radix and
+ *    full-spectrum plans and fdr_batch_run have no batched form (DESIGN.md sections 24 and 29).  Per image and iteration a group of
+ *    g moves 64 - 8 (1 - 1/g) bytes per padded pixel.                                                                           */
 int fdr_blur_batch_f32_dev(fdr_plan* plan, const float* d_imgs, size_t img_pitch, int count, int rows, int cols, int stride,
                            float* d_out, size_t out_pitch, int out_stride, int adjoint, void* stream);
 typedef struct fdr_rl_batch_params {
@@ -379,6 +380,28 @@ int fdr_richardson_lucy_free_accel_f32(fdr_plan* plan, const float* img_host, in
 int fdr_richardson_lucy_free_accel_f32_dev(fdr_plan* plan, const float* d_img, int rows, int cols, int stride, const float* d_weights,
                                            int wstride, float* d_out, int out_stride, const fdr_rlfree_params* params, float* d_alphas,
                                            void* stream);
+
+/* -- batched accelerated Richardson-Lucy: fdr_richardson_lucy_batch_f32* with the accelerated iteration above, several images per
+ *    launch.  Arguments, launch groups, forms, workspaces and refusals are those of fdr_richardson_lucy_batch_f32*, and params is the
+ *    same struct.  Per iteration a group makes the launches of one image: one extrapolation, one direction and one alpha launch over
+ *    the group (the image is the third grid dimension), every image with its own inner products, its own partials and its own alpha,
+ *    folded in the single-image order.  Every image and every alpha comes out bit for bit as fdr_richardson_lucy_accel_f32_dev or
+ *    fdr_richardson_lucy_free_accel_f32_dev gives it for that image alone on the same plan, for every group size, tail and layout;
+ *    iterations <= 2 gives the bits of fdr_richardson_lucy_batch_f32*.  group = 1 is literally the loop of the single accelerated
+ *    calls.  d_alphas may be NULL; otherwise image i receives `iterations` floats at d_alphas + i alpha_pitch (elements), and
+ *    alpha_pitch >= iterations is required.  Refused as well, before any device work: alpha_pitch < iterations with alphas given,
+ *    and an alphas range (first float of image 0 to last float of image count - 1) that overlaps the inputs, the outputs or the
+ *    weights of the batch.  The first call with a group g > 1 grows the acceleration workspace to g images (g (12 M N + 16 ceil(M / 8)
+ *    ceil(N / 1024)) + 32 bytes; the new block is had before the old one is freed, FDR_ERR_ALLOC leaves the plan and the old
+ *    workspace usable); after it the _dev form allocates nothing and stays asynchronous on `stream`, with no host read-back.  Per
+ *    image and iteration the extrapolation adds its 28 bytes per pixel of the estimate, which a group does not share (DESIGN.md
+ *    section 29).  The host form stages as fdr_richardson_lucy_batch_f32 and is synchronous.                                    */
+int fdr_richardson_lucy_batch_accel_f32_dev(fdr_plan* plan, const float* d_imgs, size_t img_pitch, int count, int rows, int cols, int stride,
+                                            const float* d_weights, int wstride, float* d_out, size_t out_pitch, int out_stride,
+                                            const fdr_rl_batch_params* params, float* d_alphas, size_t alpha_pitch, void* stream);
+int fdr_richardson_lucy_batch_accel_f32(fdr_plan* plan, const float* imgs_host, size_t img_pitch, int count, int rows, int cols, int stride,
+                                        const float* weights_host, int wstride, float* out_host, size_t out_pitch, int out_stride,
+                                        const fdr_rl_batch_params* params, float* alphas_host, size_t alpha_pitch);
 
 /* -- Richardson-Lucy that stops from the data: the fit trace and the discrepancy rules.  The iteration count is RL's only
  *    regularisation: on noisy data the estimate first sharpens, then fits the noise.  These calls run any of the four forms above

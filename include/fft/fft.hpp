@@ -210,11 +210,12 @@ inline void wienerDeblur_RGB_naive(std::vector<Mat>& channels, const Mat& psf, f
     wienerDeblur_RGB_naive(channels, psf, K, defaults());
 }
 
-// The non-accelerated Richardson-Lucy of every channel as ONE batched call (fdr_richardson_lucy_batch_f32, include/fdr.h): the channels
+// The Richardson-Lucy of every channel as ONE batched call (fdr_richardson_lucy_batch_f32, accelerated:
+// fdr_richardson_lucy_batch_accel_f32, include/fdr.h): the channels
 // of a picture share the PSF (and the weights), so a launch group of channels.size() images (at most 8) runs every pass of the
 // iteration once for all of them -- with the bits of the per-channel calls.  False (nothing done) when the channels differ in size
 // or type: the caller then loops.
-inline bool rl_channels_batched(fdr_plan* plan, std::vector<Mat>& channels, const float* weights, fdr_rl_batch_params prm) {
+inline bool rl_channels_batched(fdr_plan* plan, std::vector<Mat>& channels, const float* weights, fdr_rl_batch_params prm, bool accelerate = false) {
     const int rows = channels[0].rows, cols = channels[0].cols, count = (int)channels.size();
     for (const Mat& c : channels)
         if (c.rows != rows || c.cols != cols || c.type() != CV_32F) return false;
@@ -225,7 +226,10 @@ inline bool rl_channels_batched(fdr_plan* plan, std::vector<Mat>& channels, cons
         for (int r = 0; r < rows; ++r) std::copy(channels[i].ptr<float>(r), channels[i].ptr<float>(r) + cols, in.begin() + i * px + (size_t)r * cols);
     if (prm.free_boundary) { prm.out_rows = out_rows; prm.out_cols = out_cols; }
     FDR_CHECK(fdr_plan_set_batching(plan, 1, std::min(count, 8)));
-    FDR_CHECK(fdr_richardson_lucy_batch_f32(plan, in.data(), px, count, rows, cols, cols, weights, cols, out.data(), px, cols, &prm));
+    if (accelerate)
+        FDR_CHECK(fdr_richardson_lucy_batch_accel_f32(plan, in.data(), px, count, rows, cols, cols, weights, cols, out.data(), px, cols, &prm, nullptr, 0));
+    else
+        FDR_CHECK(fdr_richardson_lucy_batch_f32(plan, in.data(), px, count, rows, cols, cols, weights, cols, out.data(), px, cols, &prm));
     FDR_CHECK(fdr_plan_set_batching(plan, 1, 1));  // the cached plan goes back as it came
     for (int i = 0; i < count; ++i) {
         Mat o(rows, cols, CV_32F);
@@ -238,8 +242,8 @@ inline bool rl_channels_batched(fdr_plan* plan, std::vector<Mat>& channels, cons
 // Richardson-Lucy deconvolution (fdr_richardson_lucy_f32, include/fdr.h) of every channel, `iterations` steps each, in place: one
 // cached FDR_MODE_FAST plan (each dimension padded to the next power of two, at least 8 rows and 32 columns; the padding stays
 // zero), the operator PSF set once, each channel normalised by o.norm_area.  o.mode and o.cls_gamma do not apply.  accelerate: the
-// iteration with Biggs & Andrews' vector extrapolation (fdr_richardson_lucy_accel_f32), channel by channel; without it the channels go
-// through one batched call (rl_channels_batched).
+// iteration with Biggs & Andrews' vector extrapolation (fdr_richardson_lucy_accel_f32).  Either way the channels go through one
+// batched call (rl_channels_batched); channels of different sizes or types run one by one.
 inline void richardsonLucy_RGB(std::vector<Mat>& channels, const Mat& psf, int iterations, const Options& o, bool accelerate = false) {
     if (channels.empty()) return;
     const int rows = channels[0].rows, cols = channels[0].cols;
@@ -248,7 +252,7 @@ inline void richardsonLucy_RGB(std::vector<Mat>& channels, const Mat& psf, int i
     fdr_plan* plan = plan_cache().get(o.device, std::max(8, nextPowerOfTwo(rows)), std::max(32, nextPowerOfTwo(cols)), FDR_MODE_FAST, &created);
     Mat psfc = psf.isContinuous() ? psf : psf.clone();
     FDR_CHECK(fdr_set_operator_psf(plan, psfc.ptr<float>(0), psf.rows, psf.cols, psf.cols));
-    if (!accelerate && rl_channels_batched(plan, channels, nullptr, fdr_rl_batch_params{iterations, o.norm_area, 0, 0.f, 0, 0})) return;
+    if (rl_channels_batched(plan, channels, nullptr, fdr_rl_batch_params{iterations, o.norm_area, 0, 0.f, 0, 0}, accelerate)) return;
     for (Mat& c : channels) {
         Mat src = c.isContinuous() ? c : c.clone();
         Mat out(c.rows, c.cols, CV_32F);
@@ -267,7 +271,7 @@ inline void richardsonLucy_RGB(std::vector<Mat>& channels, const Mat& psf, int i
 // that is a crop of a larger scene: one cached FDR_MODE_FAST plan with room for the PSF's reach beyond the picture (the next powers
 // of two of rows + psf.rows - 1 and cols + psf.cols - 1, at least 8 x 32), the operator PSF set once, `weights` (CV_32F, the
 // picture's size, in [0, 1]; empty = all ones; 0 = ignore the pixel) shared by the channels, each channel normalised by o.norm_area.
-// accelerate as richardsonLucy_RGB (fdr_richardson_lucy_free_accel_f32); without it one batched call, the coverage computed once.
+// accelerate as richardsonLucy_RGB (fdr_richardson_lucy_free_accel_f32); one batched call either way, the coverage computed once.
 inline void richardsonLucyFree_RGB(std::vector<Mat>& channels, const Mat& psf, int iterations, const Mat& weights, const Options& o,
                                    float sigma = FDR_RL_SIGMA, bool accelerate = false) {
     if (channels.empty()) return;
@@ -283,8 +287,8 @@ inline void richardsonLucyFree_RGB(std::vector<Mat>& channels, const Mat& psf, i
     Mat psfc = psf.isContinuous() ? psf : psf.clone();
     FDR_CHECK(fdr_set_operator_psf(plan, psfc.ptr<float>(0), psf.rows, psf.cols, psf.cols));
     Mat w = weights.empty() || weights.isContinuous() ? weights : weights.clone();
-    if (!accelerate &&
-        rl_channels_batched(plan, channels, w.empty() ? nullptr : w.ptr<float>(0), fdr_rl_batch_params{iterations, o.norm_area, 1, sigma, rows, cols}))
+    if (rl_channels_batched(plan, channels, w.empty() ? nullptr : w.ptr<float>(0), fdr_rl_batch_params{iterations, o.norm_area, 1, sigma, rows, cols},
+                            accelerate))
         return;
     for (Mat& c : channels) {
         Mat src = c.isContinuous() ? c : c.clone();

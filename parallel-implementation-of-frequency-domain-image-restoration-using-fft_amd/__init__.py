@@ -263,6 +263,8 @@ def _signatures():
         "fdr_blur_batch_f32_dev": (ci, [vp, vp, sz, ci, ci, ci, ci, vp, sz, ci, ci, vp]),
         "fdr_richardson_lucy_batch_f32": (ci, [vp, vp, sz, ci, ci, ci, ci, vp, ci, vp, sz, ci, P(RlBatchParams)]),
         "fdr_richardson_lucy_batch_f32_dev": (ci, [vp, vp, sz, ci, ci, ci, ci, vp, ci, vp, sz, ci, P(RlBatchParams), vp]),
+        "fdr_richardson_lucy_batch_accel_f32": (ci, [vp, vp, sz, ci, ci, ci, ci, vp, ci, vp, sz, ci, P(RlBatchParams), vp, sz]),
+        "fdr_richardson_lucy_batch_accel_f32_dev": (ci, [vp, vp, sz, ci, ci, ci, ci, vp, ci, vp, sz, ci, P(RlBatchParams), vp, sz, vp]),
         "fdr_richardson_lucy_accel_f32": (ci, [vp, vp, ci, ci, ci, vp, ci, ci, ci, vp]),
         "fdr_richardson_lucy_accel_f32_dev": (ci, [vp, vp, ci, ci, ci, vp, ci, ci, ci, vp, vp]),
         "fdr_richardson_lucy_free_accel_f32": (ci, [vp, vp, ci, ci, ci, vp, ci, vp, ci, P(RlFreeParams), vp]),
@@ -701,21 +703,30 @@ class Plan:
 
     def richardson_lucy_batch_dev(self, d_imgs, img_pitch, count, rows, cols, stride, d_out, out_pitch, out_stride, iterations,
                                   norm_area=NORM_NONE, free_boundary=False, d_weights=None, wstride=0, sigma=RL_SIGMA, out_rows=None,
-                                  out_cols=None, stream=None):
+                                  out_cols=None, stream=None, accelerate=False, d_alphas=None, alpha_pitch=None):
         """`iterations` Richardson-Lucy steps on `count` windows with the plan's operator PSF: the iteration of richardson_lucy_dev,
         or with free_boundary that of richardson_lucy_free_dev (one weights plane, or None, for all images; out_rows x out_cols the
-        output window).  Asynchronous."""
+        output window).  accelerate: the accelerated iteration on the group (fdr_richardson_lucy_batch_accel_f32_dev); d_alphas
+        (accelerated only): device room for image i's `iterations` floats at d_alphas + i alpha_pitch (default pitch: iterations).
+        Asynchronous."""
         prm = RlBatchParams(int(iterations), int(norm_area), int(bool(free_boundary)), float(sigma),
                             int((rows if free_boundary else 0) if out_rows is None else out_rows),
                             int((cols if free_boundary else 0) if out_cols is None else out_cols))
-        _check(lib.fdr_richardson_lucy_batch_f32_dev(self._h, ctypes.c_void_p(int(d_imgs)), img_pitch, count, rows, cols, stride,
-                                                     ctypes.c_void_p(int(d_weights)) if d_weights else None, int(wstride),
-                                                     ctypes.c_void_p(int(d_out)), out_pitch, out_stride, ctypes.byref(prm), _stream(stream)))
+        args = (self._h, ctypes.c_void_p(int(d_imgs)), img_pitch, count, rows, cols, stride, ctypes.c_void_p(int(d_weights)) if d_weights else None,
+                int(wstride), ctypes.c_void_p(int(d_out)), out_pitch, out_stride, ctypes.byref(prm))
+        if accelerate:
+            _check(lib.fdr_richardson_lucy_batch_accel_f32_dev(*args, ctypes.c_void_p(int(d_alphas)) if d_alphas else None,
+                                                               int(max(int(iterations), 0) if alpha_pitch is None else alpha_pitch), _stream(stream)))
+            return
+        if d_alphas:
+            raise ValueError("d_alphas needs accelerate=True")
+        _check(lib.fdr_richardson_lucy_batch_f32_dev(*args, _stream(stream)))
 
     def richardson_lucy_batch(self, imgs, iterations, free_boundary=False, weights=None, sigma=RL_SIGMA, norm_area=NORM_NONE,
-                              full_plane=False):
+                              full_plane=False, accelerate=False, return_alphas=False):
         """Host arrays [count, rows, cols] in, [count, rows, cols] out (free_boundary with full_plane: [count, M, N]); weights
-        ([rows, cols], free_boundary only) serve every image."""
+        ([rows, cols], free_boundary only) serve every image.  accelerate: the accelerated iteration
+        (fdr_richardson_lucy_batch_accel_f32); return_alphas (accelerated only): (results, alphas [count, iterations])."""
         imgs = np.ascontiguousarray(imgs, dtype=np.float32)
         cnt, rows, cols = imgs.shape
         w = None
@@ -727,9 +738,17 @@ class Plan:
         out = np.empty((cnt, orows, ocols), dtype=np.float32)
         prm = RlBatchParams(int(iterations), int(norm_area), int(bool(free_boundary)), float(sigma), orows if free_boundary else 0,
                             ocols if free_boundary else 0)
-        _check(lib.fdr_richardson_lucy_batch_f32(self._h, _ptr(imgs), rows * cols, cnt, rows, cols, cols, _ptr(w) if w is not None else None,
-                                                 cols, _ptr(out), orows * ocols, ocols, ctypes.byref(prm)))
-        return out
+        args = (self._h, _ptr(imgs), rows * cols, cnt, rows, cols, cols, _ptr(w) if w is not None else None, cols, _ptr(out), orows * ocols, ocols,
+                ctypes.byref(prm))
+        if return_alphas and not accelerate:
+            raise ValueError("return_alphas needs accelerate=True")
+        if not accelerate:
+            _check(lib.fdr_richardson_lucy_batch_f32(*args))
+            return out
+        n = max(int(iterations), 0)
+        alphas = np.zeros((cnt, n), dtype=np.float32) if return_alphas else None
+        _check(lib.fdr_richardson_lucy_batch_accel_f32(*args, _ptr(alphas) if return_alphas and alphas.size else None, n))
+        return (out, alphas) if return_alphas else out
 
     # blind Richardson-Lucy (include/fdr.h): refines the PSF with the picture and leaves the operator tables of the refined PSF
     def richardson_lucy_blind(self, img, psf_start, iterations, free_boundary=False, weights=None, psf_hold=0, cov_sigma=RL_SIGMA,
@@ -1343,25 +1362,27 @@ def _rl_rgb(channels, M, N, psf, iterations, device, **kw):
         channels[i] = out[i]
 
 
-def richardsonLucy_RGB(channels, psf, iterations, device=0, norm_area=NORM_NONE):
+def richardsonLucy_RGB(channels, psf, iterations, device=0, norm_area=NORM_NONE, accelerate=False):
     """fft_gpu::richardsonLucy_RGB: replaces every element of `channels` (float32 planes of one size) in place with its
-    Richardson-Lucy estimate -- the bits of richardsonLucy_myfft per channel, from one plan and one launch per pass."""
+    Richardson-Lucy estimate -- the bits of richardsonLucy_myfft per channel, from one plan and one launch per pass.  accelerate:
+    the accelerated iteration, batched as well (the bits of richardsonLucy_myfft(..., accelerate=True) per channel)."""
     if not channels:
         return
     r, c = np.asarray(channels[0]).shape
     M, N = _rl_plan_size(r, c)
-    _rl_rgb(channels, M, N, psf, iterations, device, norm_area=norm_area)
+    _rl_rgb(channels, M, N, psf, iterations, device, norm_area=norm_area, accelerate=accelerate)
 
 
-def richardsonLucyFree_RGB(channels, psf, iterations, weights=None, sigma=RL_SIGMA, device=0, norm_area=NORM_NONE):
+def richardsonLucyFree_RGB(channels, psf, iterations, weights=None, sigma=RL_SIGMA, device=0, norm_area=NORM_NONE, accelerate=False):
     """fft_gpu::richardsonLucyFree_RGB: the free-boundary form of richardsonLucy_RGB (richardsonLucyFree_myfft per channel); one
-    weights plane (or None) serves every channel, and its coverage is computed once."""
+    weights plane (or None) serves every channel, and its coverage is computed once.  accelerate as richardsonLucy_RGB."""
     if not channels:
         return
     r, c = np.asarray(channels[0]).shape
     psf = np.asarray(psf, dtype=np.float32)
     M, N = _rlfree_plan_size(r, c, psf.shape[0], psf.shape[1])
-    _rl_rgb(channels, M, N, psf, iterations, device, free_boundary=True, weights=weights, sigma=sigma, norm_area=norm_area)
+    _rl_rgb(channels, M, N, psf, iterations, device, free_boundary=True, weights=weights, sigma=sigma, norm_area=norm_area,
+            accelerate=accelerate)
 
 
 def wienerDeblur_RGB_naive(channels, psf, K, mode=MODE_PARITY, device=0, norm_area=NORM_PADDED, cls_gamma=0.0, pad=PAD_ZERO):

@@ -1,8 +1,8 @@
 // fdr_api_rl.hip -- Richardson-Lucy, the plain form (fdr_richardson_lucy_f32*, fdr_richardson_lucy_accel_f32*; kernels in fdr_rl.hip
 // and the RL kinds of fdr_panel_rows.hip): the checks, the one step and the one driver of the form, both on a group of n >= 1 images,
 // and the four entry points.  Every transform is an operator pass of fdr_api_operator.hip.  The batch (fdr_api_rlbatch.hip) and the
-// blind call (fdr_api_blind.hip) run the driver; the accelerated path here and the auto call (fdr_api_rlstop.hip) route their planes
-// themselves, around the same step.
+// blind call (fdr_api_blind.hip) run the drivers (rl_group_dev, accelerated: rl_group_accel_dev); the auto call (fdr_api_rlstop.hip)
+// routes its planes itself, around the same step.
 #include "fdr_host.hpp"
 
 using namespace fdr;
@@ -95,29 +95,44 @@ int rl_group_dev(fdr_plan* p, const char* fn, fdr_plan::Slot* const* ws, int n, 
     return rc;
 }
 
+// Accelerated (rl_accel_loop): image k's estimate alternates between its output window and its plane of the acceleration workspace,
+// starting where u_n comes to lie in the output window (`first`, common to the group), and the last update goes to slot k's raw plane
+// under a normalisation.
+int rl_group_accel_dev(fdr_plan* p, const char* fn, fdr_plan::Slot* const* ws, int n, const float* const* d_imgs, int rows, int cols, int stride,
+                       float* const* d_outs, int out_stride, int iterations, int norm_area, float* d_alphas, size_t alpha_pitch, hipStream_t s) {
+    const bool norm = norm_area != FDR_NORM_NONE;
+    float* fin[kMaxGroup];
+    float* U[kMaxGroup][2];
+    for (int k = 0; k < n; ++k) {
+        fin[k] = norm ? ws[k]->raw : d_outs[k];
+        U[k][0] = d_outs[k];
+        U[k][1] = rlaccel_u_plane(p, k);
+    }
+    const int fs = norm ? cols : out_stride;
+    const int us[2] = {out_stride, cols};
+    const int first = iterations & 1;
+    int rc = FDR_OK;
+    for (int k = 0; k < n && rc == FDR_OK; ++k)
+        rc = rl_init_estimate(p, d_imgs[k], rows, cols, stride, iterations == 0 ? fin[k] : U[k][first], iterations == 0 ? fs : us[first], s);
+    if (rc != FDR_OK) return rc;
+    rc = rl_accel_loop(p, n, iterations, rows, cols, U, us, first, fin, fs, d_alphas, alpha_pitch, s,
+                       [&](const float* const* ys, int ystride, float* const* outs, int os) {
+                           return rl_step(p, ws, n, d_imgs, stride, ys, ystride, outs, os, rows, cols, s);
+                       }, nullptr);
+    for (int k = 0; k < n && rc == FDR_OK && norm; ++k) rc = rl_normalize(p, fn, fin[k], fs, rows, cols, norm_area, d_outs[k], out_stride, s);
+    return rc;
+}
+
 }  // namespace fdr
 
 namespace {
 
-// One image on slot 0: the driver; accelerated (rl_accel_loop), the estimate alternates between d_out and a plane of the
-// acceleration workspace, starting where u_n comes to lie in d_out, and the last update goes to the raw plane under a normalisation.
+// One image on slot 0: the driver of the form, plain or accelerated, on a group of one
 int rl_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, int cols, int stride, float* d_out, int out_stride, int iterations,
                 int norm_area, bool accel, float* d_alphas, hipStream_t s) {
     fdr_plan::Slot* w = &p->slots[0];
     if (!accel) return rl_group_dev(p, fn, &w, 1, &d_img, rows, cols, stride, &d_out, out_stride, iterations, norm_area, s);
-    const bool norm = norm_area != FDR_NORM_NONE;
-    float* fin = norm ? w->raw : d_out;
-    const int fs = norm ? cols : out_stride;
-    float* const U[2] = {d_out, p->ra_u};
-    const int us[2] = {out_stride, cols};
-    const int first = iterations & 1;
-    int rc = rl_init_estimate(p, d_img, rows, cols, stride, iterations == 0 ? fin : U[first], iterations == 0 ? fs : us[first], s);
-    if (rc != FDR_OK) return rc;
-    rc = rl_accel_loop(p, iterations, rows, cols, U, us, first, fin, fs, d_alphas, s, [&](const float* y, int ys, float* out, int os) {
-        return rl_step(p, &w, 1, &d_img, stride, &y, ys, &out, os, rows, cols, s);
-    }, nullptr);
-    if (rc != FDR_OK || !norm) return rc;
-    return rl_normalize(p, fn, fin, fs, rows, cols, norm_area, d_out, out_stride, s);
+    return rl_group_accel_dev(p, fn, &w, 1, &d_img, rows, cols, stride, &d_out, out_stride, iterations, norm_area, d_alphas, 0, s);
 }
 
 // the checks, the device and the driver of the four entry points; the accelerated ones also refuse alphas that overlap a window and

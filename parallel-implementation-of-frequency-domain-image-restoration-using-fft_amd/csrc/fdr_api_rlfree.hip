@@ -1,8 +1,8 @@
 // fdr_api_rlfree.hip -- free-boundary, weighted Richardson-Lucy, plain and accelerated (fdr_richardson_lucy_free_f32*, _free_accel_f32*;
 // kernels in fdr_rlfree.hip and the weighted update kind of fdr_panel_rows.hip): the workspace, the checks, the one step and the one
 // driver of the form, both on a group of n >= 1 images, and the four entry points.  The single call is a batch of one image; the
-// batch (fdr_api_rlbatch.hip) and the blind call (fdr_api_blind.hip) run the same driver, the accelerated path here and the auto call
-// (fdr_api_rlstop.hip) rl_accel_loop and their own loop around the same step.  Every transform is an operator pass of
+// batch (fdr_api_rlbatch.hip) and the blind call (fdr_api_blind.hip) run the same driver, which also runs the accelerated recursion
+// (rl_accel_loop) on a launch group; the auto call (fdr_api_rlstop.hip) has its own loop around the same step.  Every transform is an operator pass of
 // fdr_api_operator.hip: the estimate goes through pass A as a dense M x N plane, the ratio through the window.
 #include "fdr_host.hpp"
 
@@ -152,13 +152,14 @@ int rlfree_finish(fdr_plan* p, const char* fn, const float* u, float* d_out, int
 // image that copy would replace the coverage passes of the single calls, so several images are the loop of batches of one.
 int rlfree_batch_dev(fdr_plan* p, const char* fn, const float* d_imgs, size_t img_pitch, int count, int rows, int cols, int stride, const float* d_w,
                      int wstride, float* d_out, size_t out_pitch, int out_stride, const fdr_rlfree_params& prm, hipStream_t s, const RlHooks* hooks,
-                     float* keep_w) {
+                     float* keep_w, bool accel, float* d_alphas, size_t alpha_pitch) {
+    if (accel && hooks) return fail(FDR_ERR_STATE, "rlfree_batch_dev: the accelerated recursion takes no hooks");
     const int group = launch_group(p, count);
     int rc = FDR_OK;
     if (group == 1 && count > 1) {  // the loop of the single-image calls, each with its own coverage
         for (int i = 0; i < count && rc == FDR_OK; ++i)
             rc = rlfree_batch_dev(p, fn, d_imgs + (size_t)i * img_pitch, 0, 1, rows, cols, stride, d_w, wstride, d_out + (size_t)i * out_pitch, 0,
-                                  out_stride, prm, s, hooks, keep_w);
+                                  out_stride, prm, s, hooks, keep_w, accel, d_alphas ? d_alphas + (size_t)i * alpha_pitch : nullptr, 0);
         return rc;
     }
     rc = rlfree_begin(p, d_imgs, rows, cols, stride, d_w, wstride, prm.sigma, keep_w, nullptr, s);
@@ -175,11 +176,22 @@ int rlfree_batch_dev(fdr_plan* p, const char* fn, const float* d_imgs, size_t im
             FDR_HIP(hipMemcpyAsync(g.ws[k]->raw, p->rf_wgt, (size_t)p->M * p->N * sizeof(float), hipMemcpyDeviceToDevice, s));
             rc = rlfree_start_image(p, g.ws[k]->raw, us[k], 0.f, sums, s);
         }
-        for (int it = 0; it < prm.iterations && rc == FDR_OK; ++it) {
+        float* fin[kMaxGroup];  // where u_n lies
+        for (int k = 0; k < g.n; ++k) fin[k] = us[k];
+        if (accel && rc == FDR_OK) {  // the estimate alternates between image k's u plane and its plane of the acceleration workspace
+            float* U[kMaxGroup][2];
+            for (int k = 0; k < g.n; ++k) { U[k][0] = us[k]; U[k][1] = rlaccel_u_plane(p, k); }
+            const int strides[2] = {p->N, p->N};
+            rc = rl_accel_loop(p, g.n, prm.iterations, p->M, p->N, U, strides, 0, nullptr, 0, d_alphas ? d_alphas + (size_t)i0 * alpha_pitch : nullptr,
+                               alpha_pitch, s, [&](const float* const* ys, int, float* const* outs, int) {
+                                   return rlfree_step(p, g.ws, g.n, ys, outs, dws, p->rf_wgt, rows, cols, s);
+                               }, fin);
+        }
+        for (int it = 0; it < prm.iterations && rc == FDR_OK && !accel; ++it) {
             rc = rlfree_step(p, g.ws, g.n, us, us, dws, p->rf_wgt, rows, cols, s, nullptr, hooks, it);
             if (rc == FDR_OK && hooks && hooks->after_step) rc = hooks->after_step(it);
         }
-        for (int k = 0; k < g.n && rc == FDR_OK; ++k) rc = rlfree_finish(p, fn, us[k], g.outs[k], out_stride, prm, s);
+        for (int k = 0; k < g.n && rc == FDR_OK; ++k) rc = rlfree_finish(p, fn, fin[k], g.outs[k], out_stride, prm, s);
     }
     return rc;
 }
@@ -188,22 +200,10 @@ int rlfree_batch_dev(fdr_plan* p, const char* fn, const float* d_imgs, size_t im
 
 namespace {
 
-// One image: the driver; accelerated (rl_accel_loop), the estimate alternates between u's plane and one of the acceleration workspace.
+// One image: the driver on a batch of one, plain or accelerated
 int rlfree_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, int cols, int stride, const float* d_w, int wstride,
                     float* d_out, int out_stride, const fdr_rlfree_params& prm, bool accel, float* d_alphas, hipStream_t s) {
-    if (!accel) return rlfree_batch_dev(p, fn, d_img, 0, 1, rows, cols, stride, d_w, wstride, d_out, 0, out_stride, prm, s);
-    float* u = p->rf_u;
-    int rc = rlfree_begin(p, d_img, rows, cols, stride, d_w, wstride, prm.sigma, nullptr, nullptr, s);
-    if (rc != FDR_OK) return rc;
-    fdr_plan::Slot* w = &p->slots[0];
-    const float* dw = p->rf_dw;
-    float* const U[2] = {u, p->ra_u};
-    const int us[2] = {p->N, p->N};
-    rc = rl_accel_loop(p, prm.iterations, p->M, p->N, U, us, 0, nullptr, 0, d_alphas, s, [&](const float* y, int, float* out, int) {
-        return rlfree_step(p, &w, 1, &y, &out, &dw, p->rf_wgt, rows, cols, s);
-    }, &u);
-    if (rc != FDR_OK) return rc;
-    return rlfree_finish(p, fn, u, d_out, out_stride, prm, s);
+    return rlfree_batch_dev(p, fn, d_img, 0, 1, rows, cols, stride, d_w, wstride, d_out, 0, out_stride, prm, s, nullptr, nullptr, accel, d_alphas, 0);
 }
 
 // the checks, the device, the workspaces and the driver of the four entry points; the accelerated ones also refuse alphas that

@@ -147,7 +147,7 @@ int auto_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, int
         if (rc != FDR_OK) return rc;
         cur = d_out;
     }
-    float* const U[2] = {cur, a.accel ? p->ra_u : cur};
+    float* const U[1][2] = {{cur, a.accel ? p->ra_u : cur}};  // a group of one image for rl_accel_steps
     const int us[2] = {a.free_form ? N : out_stride, a.free_form ? N : (a.accel ? cols : out_stride)};
     const int R = a.free_form ? M : rows, C = a.free_form ? N : cols;  // the window the estimate lives on
 
@@ -171,7 +171,8 @@ int auto_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, int
     while (done < n && !stopped) {
         const int k1 = a.rule == FDR_RL_STOP_NONE ? n : (n - done < a.every ? n : done + a.every);
         if (a.accel) {
-            rc = rl_accel_steps(p, done, k1, n, R, C, U, us, 0, nullptr, 0, nullptr, s, step, &cur);
+            rc = rl_accel_steps(p, 1, done, k1, n, R, C, U, us, 0, nullptr, 0, nullptr, 0, s,
+                                [&](const float* const* ys, int ystride, float* const* outs, int os) { return step(ys[0], ystride, outs[0], os); }, &cur);
         } else {
             for (int i = done; i < k1 && rc == FDR_OK; ++i) rc = step(cur, us[0], cur, us[0]);
         }

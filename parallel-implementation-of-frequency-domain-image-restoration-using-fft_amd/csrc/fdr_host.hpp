@@ -160,8 +160,12 @@ struct fdr_plan {
     double* rf_part = nullptr;
     // accelerated Richardson-Lucy, both forms (fdr_richardson_lucy_accel_f32*, fdr_richardson_lucy_free_accel_f32*): made by the
     // first such call, kept until fdr_plan_destroy -- one allocation holding three M x N real planes (the extrapolated point y, the
-    // second plane of the estimate, the direction g), the 2 rlaccel_partials(M, N) double partials and alpha
+    // second plane of the estimate, the direction g), the 2 rlaccel_partials(M, N) double partials and alpha.  A batched call on groups
+    // of g images (fdr_richardson_lucy_batch_accel_f32*) grows it to g of each: ra_group = the images it holds; the partials and the
+    // alphas of the group follow ra_part and ra_alpha, the planes of image k > 0 lie at ra_more (rlaccel_y_plane, _u_plane, _g_plane)
     void* ra_block = nullptr;
+    int ra_group = 0;
+    float* ra_more = nullptr;
     float *ra_y = nullptr, *ra_u = nullptr, *ra_g = nullptr;
     double* ra_part = nullptr;
     float* ra_alpha = nullptr;
@@ -412,6 +416,12 @@ int rl_normalize(fdr_plan* p, const char* fn, const float* fin, int fs, int rows
 // the plain form on a checked group: start per image, `iterations` steps, normalisation per image
 int rl_group_dev(fdr_plan* p, const char* fn, fdr_plan::Slot* const* ws, int n, const float* const* d_imgs, int rows, int cols, int stride,
                  float* const* d_outs, int out_stride, int iterations, int norm_area, hipStream_t s, const RlHooks* hooks = nullptr);
+// the accelerated plain form on a checked group with the acceleration workspace for n images: start per image, the recursion of
+// rl_accel_loop around rl_step on the group (the estimate alternates between each image's output window and its workspace plane,
+// the last update goes to the slot's raw plane under a normalisation), normalisation per image.  Image k's alphas go to
+// d_alphas + k alpha_pitch when d_alphas is not null.
+int rl_group_accel_dev(fdr_plan* p, const char* fn, fdr_plan::Slot* const* ws, int n, const float* const* d_imgs, int rows, int cols, int stride,
+                       float* const* d_outs, int out_stride, int iterations, int norm_area, float* d_alphas, size_t alpha_pitch, hipStream_t s);
 // the free-boundary workspace for `group` images (1 + 2 group planes); FDR_ERR_ALLOC leaves the plan and the workspace it had intact
 int ensure_rlfree_workspace(fdr_plan* p, const char* fn, int group = 1);
 int rlfree_check(const fdr_plan* p, const char* fn, const float* img, int rows, int cols, int stride, const float* weights, int wstride,
@@ -431,32 +441,44 @@ int rlfree_begin(fdr_plan* p, const float* d_img, int rows, int cols, int stride
 // finish: the output window of the dense M x N estimate u, cropped or normalised, into d_out
 int rlfree_finish(fdr_plan* p, const char* fn, const float* u, float* d_out, int out_stride, const fdr_rlfree_params& prm, hipStream_t s);
 // the free-boundary form on a checked batch of `count` images with its workspace (for launch_group(p, count) images): begin, steps in
-// place, finish, in launch groups; one image with its hooks and keep_w is the blind call's
+// place, finish, in launch groups; one image with its hooks and keep_w is the blind call's.  `accel` (no hooks; needs the acceleration
+// workspace for the group as well): the recursion of rl_accel_loop around the step, the estimate alternating between image k's u
+// plane and its acceleration plane, image i's alphas to d_alphas + i alpha_pitch when d_alphas is not null.
 int rlfree_batch_dev(fdr_plan* p, const char* fn, const float* d_imgs, size_t img_pitch, int count, int rows, int cols, int stride, const float* d_w,
                      int wstride, float* d_out, size_t out_pitch, int out_stride, const fdr_rlfree_params& prm, hipStream_t s,
-                     const RlHooks* hooks = nullptr, float* keep_w = nullptr);
+                     const RlHooks* hooks = nullptr, float* keep_w = nullptr, bool accel = false, float* d_alphas = nullptr,
+                     size_t alpha_pitch = 0);
 // ---- the noise estimate (fdr_api_reg.hip): the Immerkaer sum of a device window through `part` (reg_noise_partials + 1 doubles), read
 // back: synchronous; and the refusal of a window it cannot work on
 int noise_sigma_dev(const float* d_img, int rows, int cols, int stride, double* part, double* sigma, hipStream_t s);
 int noise_window_check(const char* fn, int rows, int cols, int stride);
 // ---- accelerated Richardson-Lucy (fdr_api_rlaccel.hip), shared by the plain and the free-boundary form ----
-// the workspace of the accelerated calls; FDR_ERR_ALLOC, sticky HIP error cleared and plan intact, if it cannot be had
-int ensure_rlaccel_workspace(fdr_plan* p, const char* fn);
+// the workspace of the accelerated calls for `group` images: per image three M x N planes, 2 rlaccel_partials(M, N) doubles and one
+// alpha.  It grows on the first use with a larger group; FDR_ERR_ALLOC, sticky HIP error cleared, leaves the plan and the workspace
+// it had intact.  Image 0's planes, partials and alpha are ra_y, ra_u, ra_g, ra_part and ra_alpha.
+int ensure_rlaccel_workspace(fdr_plan* p, const char* fn, int group = 1);
+// image k of a group: the extrapolated point y, the second plane of its estimate, its direction g
+float* rlaccel_y_plane(const fdr_plan* p, int k);
+float* rlaccel_u_plane(const fdr_plan* p, int k);
+float* rlaccel_g_plane(const fdr_plan* p, int k);
 // FDR_ERR_ARG when the n floats at d_alphas overlap the rows x cols window at `w` (row stride ws); a null d_alphas is fine
 int check_alphas(const char* fn, const float* d_alphas, int n, const float* w, int ws, int rows, int cols, const char* what);
 // run(d_alphas) of a host-pointer call: a one-shot device buffer for the n alphas (null for a null host pointer or n <= 0), read back after it
 int with_host_alphas(const char* fn, float* alphas_host, int n, const std::function<int(float* d_alphas)>& run);
-// One iteration of either form: u_next = step(y), y a rows x cols window with row stride ys, `out` another plane
-using RlStep = std::function<int(const float* y, int ys, float* out, int os)>;
-// n accelerated iterations on a rows x cols window.  u_k lives in U[(first + k) & 1] (row strides us[]), u_0 there on entry; the
-// last step writes to `fin` (row stride fs) when it is not null.  *result, when not null, receives the plane of u_n.  alpha_0 ..
-// alpha_(n-1) go to d_alphas when it is not null.  For n <= 2 this is n steps and nothing else.
-int rl_accel_loop(fdr_plan* p, int n, int rows, int cols, float* const U[2], const int us[2], int first, float* fin, int fs, float* d_alphas,
-                  hipStream_t s, const RlStep& step, float** result);
-// iterations k0 .. k1 - 1 of a run of at most n (what rl_accel_loop is made of): u_k0 lies in U[(first + k0) & 1] and the state of the
-// earlier iterations (g, alpha) in the workspace; *result, when not null, receives the plane of u_k1 (untouched for k0 = k1)
-int rl_accel_steps(fdr_plan* p, int k0, int k1, int n, int rows, int cols, float* const U[2], const int us[2], int first, float* fin, int fs,
-                   float* d_alphas, hipStream_t s, const RlStep& step, float** result);
+// One iteration of either form on a group: image i's u_next = step(y) from ys[i], a rows x cols window with row stride ystride, to
+// outs[i] (row stride os), another plane
+using RlStep = std::function<int(const float* const* ys, int ystride, float* const* outs, int os)>;
+// n accelerated iterations on the rows x cols windows of a group of nimg images (1 .. kMaxGroup; one image launches the single-image
+// kernels).  Image i's u_k lives in U[i][(first + k) & 1] (row strides us[], common to the group), u_0 there on entry; the last step
+// writes to fin[i] (row stride fs) when fin is not null.  result[i], when result is not null, receives the plane of image i's u_n.
+// Image i's alpha_0 .. alpha_(n-1) go to d_alphas + i alpha_pitch when d_alphas is not null.  For n <= 2 this is n steps and nothing
+// else.  A group makes the launches of one image: one extrapolation, one direction and one alpha launch per iteration.
+int rl_accel_loop(fdr_plan* p, int nimg, int n, int rows, int cols, float* const (*U)[2], const int us[2], int first, float* const* fin, int fs,
+                  float* d_alphas, size_t alpha_pitch, hipStream_t s, const RlStep& step, float** result);
+// iterations k0 .. k1 - 1 of a run of at most n (what rl_accel_loop is made of): u_k0 lies in U[i][(first + k0) & 1] and the state of
+// the earlier iterations (g, alpha) in the workspace; result[i] receives the plane of u_k1 (untouched for k0 = k1)
+int rl_accel_steps(fdr_plan* p, int nimg, int k0, int k1, int n, int rows, int cols, float* const (*U)[2], const int us[2], int first,
+                   float* const* fin, int fs, float* d_alphas, size_t alpha_pitch, hipStream_t s, const RlStep& step, float** result);
 // pairs of one fdr_reg_curve_f32* call (fdr_api_reg.hip): what the candidate and result arrays of the plan hold
 constexpr int kRegMaxCurve = 4096;
 static_assert(kRegMaxCurve % kRegCandidates == 0, "the last sweep reads kRegCandidates pairs");

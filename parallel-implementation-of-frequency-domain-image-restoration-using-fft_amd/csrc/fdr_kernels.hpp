@@ -196,6 +196,14 @@ hipError_t launch_rlaccel_direction(const float* u1, int u1s, const float* y, in
 hipError_t launch_rlaccel_alpha(const double* part, int n, float amax, float* alpha, float* record, hipStream_t s);
 hipError_t launch_rlaccel_extrapolate(const float* u1, int u1s, const float* u0, int u0s, const float* alpha, float* y, int ys, int rows,
                                       int cols, hipStream_t s);
+// the same on a group of 1 <= nimg <= kMaxGroup images in one launch each (blockIdx.z = image; one image is the single-image launch):
+// per-image planes with one row stride per operand, image z's partials at part + z 2 n (n = rlaccel_partials(rows, cols)), its alpha
+// at alpha[z] and, when `record` is not null, at record[z alpha_pitch].  Every image gets the bits of the single-image kernels.
+hipError_t launch_rlaccel_direction_n(int nimg, const float* const* u1, int u1s, const float* const* y, int ys, float* const* g, int gs, int rows,
+                                      int cols, double* part, hipStream_t s);
+hipError_t launch_rlaccel_alpha_n(int nimg, const double* part, int n, float amax, float* alpha, float* record, size_t alpha_pitch, hipStream_t s);
+hipError_t launch_rlaccel_extrapolate_n(int nimg, const float* const* u1, int u1s, const float* const* u0, int u0s, const float* alpha,
+                                        float* const* y, int ys, int rows, int cols, hipStream_t s);
 // (fdr_rlstop.hip) the fit trace of Richardson-Lucy: one workgroup folds the n (res, kl) pairs ROW_OUT_RL_RATIO_STAT left in `part`
 // in index order (thread t adds t, t + 256, ... in order, then a fixed tree) into out[0] = res, out[1] = kl
 hipError_t launch_rlstop_fold(const double* part, int n, double* out, hipStream_t s);

@@ -11,6 +11,11 @@
 // planes are windows with arbitrary row strides.  A thread owns four consecutive columns of kRaRows rows and adds its products
 // in that order whether it loads them as one 16-byte request or as four scalars, so the sums do not depend on the alignment of
 // the caller's planes.  No float atomics: every sum runs in a fixed order.
+//
+// Each kernel has a group form for 2 .. kMaxGroup images per launch (fdr_richardson_lucy_batch_accel_f32*): blockIdx.z is the image,
+// the per-image planes travel by value in the argument block and are picked by a select chain on scalars, image z has its own 2 n
+// partials at part + z 2 n and its own alpha[z].  Both forms expand the same per-tile code on the same tiling, so an image of a
+// group comes out with the bits it gets alone.
 #include "fdr_kernels.hpp"
 
 #include <cstdint>
@@ -43,106 +48,168 @@ __device__ __forceinline__ void ra_store4(float* row, int x, int cols, float4 v)
     if (x + 3 < cols) row[x + 3] = v.w;
 }
 
+// the planes of a group, by value in the argument block.  direction: u1, y (read), g; extrapolation: u1, u0 (read), yw (written).
+struct RaPlanes {
+    const float* u1[kMaxGroup];
+    const float* y[kMaxGroup];
+    const float* u0[kMaxGroup];
+    float* g[kMaxGroup];
+    float* yw[kMaxGroup];
+};
+// entry i (uniform over the workgroup) as a select chain on scalars, on the member itself: a dynamic index, or pick_image's array
+// reference to a by-value kernel argument, sends the argument block to scratch memory
+#define FDR_RA_PICK(arr, i) \
+    ((i) < 4 ? ((i) == 0 ? arr[0] : (i) == 1 ? arr[1] : (i) == 2 ? arr[2] : arr[3]) : ((i) == 4 ? arr[4] : (i) == 5 ? arr[5] : (i) == 6 ? arr[6] : arr[7]))
+static_assert(kMaxGroup == 8, "select chain written for 8 entries");
+
+// The per-tile code of each kernel is a macro, expanded in the single-image kernel and in its group form: as an inlined function it
+// changed the register allocation of the single-image kernels, whose code must stay what it was (tools/kernel_diff.py).  A macro
+// takes the operands by the names the kernel gives them and may return from the kernel.
+
 // kRaRows rows (blockIdx.y) of kRaCols columns (blockIdx.x) of the window: g = u1 - y over the previous g (same index), and with
 // PARTIALS the workgroup's sum(g_new g_old) to part[b] and sum(g_old g_old) to part[n + b] (double, fixed-order tree),
 // b = blockIdx.y * gridDim.x + blockIdx.x.  Without PARTIALS (the first direction of a call) g is written only, not read.
 // Columns past `cols` load as zeros and add nothing.
+#define FDR_RA_DIRECTION_TILE(u1, u1s, y, ys, g, gs, rows, cols, part, n) \
+    do {                                                                                        \
+        __shared__ double red[2][kRaThreads];                                                   \
+        const int x = blockIdx.x * kRaCols + 4 * (int)threadIdx.x;                              \
+        const int r0 = blockIdx.y * kRaRows;                                                    \
+        double s_no = 0.0, s_oo = 0.0;                                                          \
+        if (x < cols) {                                                                         \
+            for (int i = 0; i < kRaRows; ++i) {                                                 \
+                const size_t r = (size_t)(r0 + i);                                              \
+                if (r0 + i >= rows) break;                                                      \
+                const float4 a = ra_load4<VEC>(u1 + r * u1s, x, cols);                          \
+                const float4 b = ra_load4<VEC>(y + r * ys, x, cols);                            \
+                const float4 gn = make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w);      \
+                if (PARTIALS) {                                                                 \
+                    const float4 go = ra_load4<VEC>(g + r * gs, x, cols);                       \
+                    s_no += (double)gn.x * (double)go.x;  s_oo += (double)go.x * (double)go.x;  \
+                    s_no += (double)gn.y * (double)go.y;  s_oo += (double)go.y * (double)go.y;  \
+                    s_no += (double)gn.z * (double)go.z;  s_oo += (double)go.z * (double)go.z;  \
+                    s_no += (double)gn.w * (double)go.w;  s_oo += (double)go.w * (double)go.w;  \
+                }                                                                               \
+                ra_store4<VEC>(g + r * gs, x, cols, gn);                                        \
+            }                                                                                   \
+        }                                                                                       \
+        if (!PARTIALS) return;                                                                  \
+        red[0][threadIdx.x] = s_no;                                                             \
+        red[1][threadIdx.x] = s_oo;                                                             \
+        __syncthreads();                                                                        \
+        for (int h = kRaThreads / 2; h > 0; h >>= 1) {                                          \
+            if ((int)threadIdx.x < h) {                                                         \
+                red[0][threadIdx.x] += red[0][threadIdx.x + h];                                 \
+                red[1][threadIdx.x] += red[1][threadIdx.x + h];                                 \
+            }                                                                                   \
+            __syncthreads();                                                                    \
+        }                                                                                       \
+        if (threadIdx.x == 0) {                                                                 \
+            const size_t b = (size_t)blockIdx.y * gridDim.x + blockIdx.x;                       \
+            part[b] = red[0][0];                                                                \
+            part[(size_t)n + b] = red[1][0];                                                    \
+        }                                                                                       \
+    } while (0)
 template <bool VEC, bool PARTIALS>
 __global__ __launch_bounds__(kRaThreads) void rlaccel_direction_kernel(const float* __restrict__ u1, int u1s, const float* __restrict__ y, int ys,
                                                                        float* __restrict__ g, int gs, int rows, int cols,
                                                                        double* __restrict__ part, int n) {
-    __shared__ double red[2][kRaThreads];
-    const int x = blockIdx.x * kRaCols + 4 * (int)threadIdx.x;
-    const int r0 = blockIdx.y * kRaRows;
-    double s_no = 0.0, s_oo = 0.0;
-    if (x < cols) {
-        for (int i = 0; i < kRaRows; ++i) {
-            const size_t r = (size_t)(r0 + i);
-            if (r0 + i >= rows) break;
-            const float4 a = ra_load4<VEC>(u1 + r * u1s, x, cols);
-            const float4 b = ra_load4<VEC>(y + r * ys, x, cols);
-            const float4 gn = make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w);
-            if (PARTIALS) {
-                const float4 go = ra_load4<VEC>(g + r * gs, x, cols);
-                s_no += (double)gn.x * (double)go.x;  s_oo += (double)go.x * (double)go.x;
-                s_no += (double)gn.y * (double)go.y;  s_oo += (double)go.y * (double)go.y;
-                s_no += (double)gn.z * (double)go.z;  s_oo += (double)go.z * (double)go.z;
-                s_no += (double)gn.w * (double)go.w;  s_oo += (double)go.w * (double)go.w;
-            }
-            ra_store4<VEC>(g + r * gs, x, cols, gn);
-        }
-    }
-    if (!PARTIALS) return;
-    red[0][threadIdx.x] = s_no;
-    red[1][threadIdx.x] = s_oo;
-    __syncthreads();
-    for (int h = kRaThreads / 2; h > 0; h >>= 1) {
-        if ((int)threadIdx.x < h) {
-            red[0][threadIdx.x] += red[0][threadIdx.x + h];
-            red[1][threadIdx.x] += red[1][threadIdx.x + h];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        const size_t b = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
-        part[b] = red[0][0];
-        part[(size_t)n + b] = red[1][0];
-    }
+    FDR_RA_DIRECTION_TILE(u1, u1s, y, ys, g, gs, rows, cols, part, n);
+}
+// the group form: image blockIdx.z on its planes, its partials at part + z 2 n
+template <bool VEC, bool PARTIALS>
+__global__ __launch_bounds__(kRaThreads) void rlaccel_direction_group_kernel(const RaPlanes pl, int u1s, int ys, int gs, int rows, int cols,
+                                                                             double* __restrict__ part0, int n) {
+    const int z = blockIdx.z;
+    const float* __restrict__ u1 = FDR_RA_PICK(pl.u1, z);
+    const float* __restrict__ y = FDR_RA_PICK(pl.y, z);
+    float* __restrict__ g = FDR_RA_PICK(pl.g, z);
+    double* __restrict__ part = PARTIALS ? part0 + (size_t)z * 2 * (size_t)n : part0;
+    FDR_RA_DIRECTION_TILE(u1, u1s, y, ys, g, gs, rows, cols, part, n);
 }
 
 // one workgroup: num = sum of part[0 .. n), den = sum of part[n .. 2 n) (thread t adds t, t + 256, ... in order, then a fixed
 // tree); alpha = clamp(num / den, 0, max) rounded to float once, 0 for den = 0 or a quotient that is not finite; to *alpha and,
 // when `record` is not null, to *record
+#define FDR_RA_ALPHA_FOLD(part, n, amax, alpha, record) \
+    do {                                                                                                             \
+        __shared__ double red[2][kRaThreads];                                                                        \
+        double a = 0.0, b = 0.0;                                                                                     \
+        for (int k = threadIdx.x; k < n; k += kRaThreads) {                                                          \
+            a += part[k];                                                                                            \
+            b += part[(size_t)n + k];                                                                                \
+        }                                                                                                            \
+        red[0][threadIdx.x] = a;                                                                                     \
+        red[1][threadIdx.x] = b;                                                                                     \
+        __syncthreads();                                                                                             \
+        for (int h = kRaThreads / 2; h > 0; h >>= 1) {                                                               \
+            if ((int)threadIdx.x < h) {                                                                              \
+                red[0][threadIdx.x] += red[0][threadIdx.x + h];                                                      \
+                red[1][threadIdx.x] += red[1][threadIdx.x + h];                                                      \
+            }                                                                                                        \
+            __syncthreads();                                                                                         \
+        }                                                                                                            \
+        if (threadIdx.x == 0) {                                                                                      \
+            const double num = red[0][0], den = red[1][0];                                                           \
+            double q = den != 0.0 ? num / den : 0.0;                                                                 \
+            if (!(q >= 0.0) || q > 1.7976931348623157e308) q = 0.0;  /* negative, NaN or infinite: no extrapolation */\
+            if (q > (double)amax) q = (double)amax;                                                                  \
+            const float v = (float)q;                                                                                \
+            *alpha = v;                                                                                              \
+            if (record) *record = v;                                                                                 \
+        }                                                                                                            \
+    } while (0)
 __global__ __launch_bounds__(kRaThreads) void rlaccel_alpha_kernel(const double* __restrict__ part, int n, float amax, float* __restrict__ alpha,
                                                                    float* __restrict__ record) {
-    __shared__ double red[2][kRaThreads];
-    double a = 0.0, b = 0.0;
-    for (int k = threadIdx.x; k < n; k += kRaThreads) {
-        a += part[k];
-        b += part[(size_t)n + k];
-    }
-    red[0][threadIdx.x] = a;
-    red[1][threadIdx.x] = b;
-    __syncthreads();
-    for (int h = kRaThreads / 2; h > 0; h >>= 1) {
-        if ((int)threadIdx.x < h) {
-            red[0][threadIdx.x] += red[0][threadIdx.x + h];
-            red[1][threadIdx.x] += red[1][threadIdx.x + h];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        const double num = red[0][0], den = red[1][0];
-        double q = den != 0.0 ? num / den : 0.0;
-        if (!(q >= 0.0) || q > 1.7976931348623157e308) q = 0.0;  // negative, NaN or infinite: no extrapolation
-        if (q > (double)amax) q = (double)amax;
-        const float v = (float)q;
-        *alpha = v;
-        if (record) *record = v;
-    }
+    FDR_RA_ALPHA_FOLD(part, n, amax, alpha, record);
+}
+// the group form, one workgroup per image (blockIdx.z): its partials at part + z 2 n, to alpha[z] and record[z alpha_pitch]
+__global__ __launch_bounds__(kRaThreads) void rlaccel_alpha_group_kernel(const double* __restrict__ part0, int n, float amax,
+                                                                         float* __restrict__ alpha0, float* __restrict__ record0,
+                                                                         size_t alpha_pitch) {
+    const size_t z = blockIdx.z;
+    const double* __restrict__ part = part0 + z * 2 * (size_t)n;
+    float* __restrict__ alpha = alpha0 + z;
+    float* __restrict__ record = record0 ? record0 + z * alpha_pitch : nullptr;
+    FDR_RA_ALPHA_FOLD(part, n, amax, alpha, record);
 }
 
 // y = max(u1 + alpha (u1 - u0), 0) on the window, alpha from the device scalar; the tiling of the direction kernel
+#define FDR_RA_EXTRAPOLATE_TILE(u1, u1s, u0, u0s, alpha, y, ys, rows, cols) \
+    do {                                                            \
+        const int x = blockIdx.x * kRaCols + 4 * (int)threadIdx.x;  \
+        if (x >= cols) return;                                      \
+        const float al = *alpha;                                    \
+        const int r0 = blockIdx.y * kRaRows;                        \
+        for (int i = 0; i < kRaRows; ++i) {                         \
+            const size_t r = (size_t)(r0 + i);                      \
+            if (r0 + i >= rows) break;                              \
+            const float4 a = ra_load4<VEC>(u1 + r * u1s, x, cols);  \
+            const float4 b = ra_load4<VEC>(u0 + r * u0s, x, cols);  \
+            float4 v;                                               \
+            v.x = fmaxf(fmaf(al, a.x - b.x, a.x), 0.f);             \
+            v.y = fmaxf(fmaf(al, a.y - b.y, a.y), 0.f);             \
+            v.z = fmaxf(fmaf(al, a.z - b.z, a.z), 0.f);             \
+            v.w = fmaxf(fmaf(al, a.w - b.w, a.w), 0.f);             \
+            ra_store4<VEC>(y + r * ys, x, cols, v);                 \
+        }                                                           \
+    } while (0)
 template <bool VEC>
 __global__ __launch_bounds__(kRaThreads) void rlaccel_extrapolate_kernel(const float* __restrict__ u1, int u1s, const float* __restrict__ u0,
                                                                          int u0s, const float* __restrict__ alpha, float* __restrict__ y, int ys,
                                                                          int rows, int cols) {
-    const int x = blockIdx.x * kRaCols + 4 * (int)threadIdx.x;
-    if (x >= cols) return;
-    const float al = *alpha;
-    const int r0 = blockIdx.y * kRaRows;
-    for (int i = 0; i < kRaRows; ++i) {
-        const size_t r = (size_t)(r0 + i);
-        if (r0 + i >= rows) break;
-        const float4 a = ra_load4<VEC>(u1 + r * u1s, x, cols);
-        const float4 b = ra_load4<VEC>(u0 + r * u0s, x, cols);
-        float4 v;
-        v.x = fmaxf(fmaf(al, a.x - b.x, a.x), 0.f);
-        v.y = fmaxf(fmaf(al, a.y - b.y, a.y), 0.f);
-        v.z = fmaxf(fmaf(al, a.z - b.z, a.z), 0.f);
-        v.w = fmaxf(fmaf(al, a.w - b.w, a.w), 0.f);
-        ra_store4<VEC>(y + r * ys, x, cols, v);
-    }
+    FDR_RA_EXTRAPOLATE_TILE(u1, u1s, u0, u0s, alpha, y, ys, rows, cols);
+}
+// the group form: image blockIdx.z on its planes, with alpha[z]
+template <bool VEC>
+__global__ __launch_bounds__(kRaThreads) void rlaccel_extrapolate_group_kernel(const RaPlanes pl, int u1s, int u0s, const float* __restrict__ alpha0,
+                                                                               int ys, int rows, int cols) {
+    const int z = blockIdx.z;
+    const float* __restrict__ u1 = FDR_RA_PICK(pl.u1, z);
+    const float* __restrict__ u0 = FDR_RA_PICK(pl.u0, z);
+    float* __restrict__ y = FDR_RA_PICK(pl.yw, z);
+    const float* __restrict__ alpha = alpha0 + z;
+    FDR_RA_EXTRAPOLATE_TILE(u1, u1s, u0, u0s, alpha, y, ys, rows, cols);
 }
 
 int rlaccel_partials(int rows, int cols) { return ((rows + kRaRows - 1) / kRaRows) * ((cols + kRaCols - 1) / kRaCols); }
@@ -185,6 +252,62 @@ hipError_t launch_rlaccel_extrapolate(const float* u1, int u1s, const float* u0,
         hipLaunchKernelGGL((rlaccel_extrapolate_kernel<true>), grid, block, 0, s, u1, u1s, u0, u0s, alpha, y, ys, rows, cols);
     else
         hipLaunchKernelGGL((rlaccel_extrapolate_kernel<false>), grid, block, 0, s, u1, u1s, u0, u0s, alpha, y, ys, rows, cols);
+    return hipGetLastError();
+}
+
+// ---- the group forms: nimg images per launch; one image is the single-image launch ----
+namespace {
+bool ra_vec_ok_n(int nimg, const float* const* a, int as, const float* const* b, int bs, const float* const* c, int cs) {
+    for (int k = 0; k < nimg; ++k)
+        if (!ra_vec_ok(a[k], as, b[k], bs, c[k], cs)) return false;
+    return true;
+}
+}  // namespace
+
+hipError_t launch_rlaccel_direction_n(int nimg, const float* const* u1, int u1s, const float* const* y, int ys, float* const* g, int gs, int rows,
+                                      int cols, double* part, hipStream_t s) {
+    if (nimg < 1 || nimg > kMaxGroup) return hipErrorInvalidValue;
+    if (nimg == 1) return launch_rlaccel_direction(u1[0], u1s, y[0], ys, g[0], gs, rows, cols, part, s);
+    if (rows <= 0 || cols <= 0 || u1s < cols || ys < cols || gs < cols) return hipErrorInvalidValue;
+    RaPlanes pl{};
+    for (int k = 0; k < nimg; ++k) { pl.u1[k] = u1[k]; pl.y[k] = y[k]; pl.g[k] = g[k]; }
+    const bool vec = ra_vec_ok_n(nimg, u1, u1s, y, ys, g, gs);
+    const int n = rlaccel_partials(rows, cols);
+    dim3 grid = ra_grid(rows, cols);
+    grid.z = (unsigned)nimg;
+    const dim3 block(kRaThreads);
+    if (part) {
+        if (vec) hipLaunchKernelGGL((rlaccel_direction_group_kernel<true, true>), grid, block, 0, s, pl, u1s, ys, gs, rows, cols, part, n);
+        else hipLaunchKernelGGL((rlaccel_direction_group_kernel<false, true>), grid, block, 0, s, pl, u1s, ys, gs, rows, cols, part, n);
+    } else {
+        if (vec) hipLaunchKernelGGL((rlaccel_direction_group_kernel<true, false>), grid, block, 0, s, pl, u1s, ys, gs, rows, cols, part, n);
+        else hipLaunchKernelGGL((rlaccel_direction_group_kernel<false, false>), grid, block, 0, s, pl, u1s, ys, gs, rows, cols, part, n);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_rlaccel_alpha_n(int nimg, const double* part, int n, float amax, float* alpha, float* record, size_t alpha_pitch, hipStream_t s) {
+    if (nimg < 1 || nimg > kMaxGroup) return hipErrorInvalidValue;
+    if (nimg == 1) return launch_rlaccel_alpha(part, n, amax, alpha, record, s);
+    if (n <= 0 || !part || !alpha) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rlaccel_alpha_group_kernel, dim3(1, 1, (unsigned)nimg), dim3(kRaThreads), 0, s, part, n, amax, alpha, record, alpha_pitch);
+    return hipGetLastError();
+}
+
+hipError_t launch_rlaccel_extrapolate_n(int nimg, const float* const* u1, int u1s, const float* const* u0, int u0s, const float* alpha,
+                                        float* const* y, int ys, int rows, int cols, hipStream_t s) {
+    if (nimg < 1 || nimg > kMaxGroup) return hipErrorInvalidValue;
+    if (nimg == 1) return launch_rlaccel_extrapolate(u1[0], u1s, u0[0], u0s, alpha, y[0], ys, rows, cols, s);
+    if (rows <= 0 || cols <= 0 || u1s < cols || u0s < cols || ys < cols || !alpha) return hipErrorInvalidValue;
+    RaPlanes pl{};
+    for (int k = 0; k < nimg; ++k) { pl.u1[k] = u1[k]; pl.u0[k] = u0[k]; pl.yw[k] = y[k]; }
+    dim3 grid = ra_grid(rows, cols);
+    grid.z = (unsigned)nimg;
+    const dim3 block(kRaThreads);
+    if (ra_vec_ok_n(nimg, u1, u1s, u0, u0s, y, ys))
+        hipLaunchKernelGGL((rlaccel_extrapolate_group_kernel<true>), grid, block, 0, s, pl, u1s, u0s, alpha, ys, rows, cols);
+    else
+        hipLaunchKernelGGL((rlaccel_extrapolate_group_kernel<false>), grid, block, 0, s, pl, u1s, u0s, alpha, ys, rows, cols);
     return hipGetLastError();
 }
 
