@@ -326,9 +326,9 @@ int fdr_richardson_lucy_free_f32_dev(fdr_plan* plan, const float* d_img, int row
  *    iterations, norm_area, sigma, the output window), weights in the plain form, and an output that overlaps the input or the
  *    weights anywhere within the span of the batch (first element of image 0 to last element of image count - 1).  Neither _dev
  *    form allocates after its first call, and both stay asynchronous on `stream`.  The accelerated iteration has the batched form
- *    fdr_richardson_lucy_batch_accel_f32* below; the data-stopped and blind iterations, TV, per-image weights, mixed-radix and
- *    full-spectrum plans and fdr_batch_run have no batched form (DESIGN.md sections 24 and 29).  Per image and iteration a group of
- *    g moves 64 - 8 (1 - 1/g) bytes per padded pixel.                                                                           */
+ *    fdr_richardson_lucy_batch_accel_f32* below and TV the batched form fdr_tv_deconv_batch_f32*; the data-stopped and blind
+ *    iterations, per-image weights, mixed-radix and full-spectrum plans and fdr_batch_run have none (DESIGN.md sections 24, 29 and 30).
+ *    Per image and iteration a group of g moves 64 - 8 (1 - 1/g) bytes per padded pixel.                                        */
 int fdr_blur_batch_f32_dev(fdr_plan* plan, const float* d_imgs, size_t img_pitch, int count, int rows, int cols, int stride,
                            float* d_out, size_t out_pitch, int out_stride, int adjoint, void* stream);
 typedef struct fdr_rl_batch_params {
@@ -610,7 +610,8 @@ int fdr_rl_tv_factor_f32_dev(int device, const float* d_u, int rows, int cols, i
  *    nor FDR_FLAG_FULL_SPECTRUM; every other plan FDR_ERR_ARG before any device work, a tables-only plan FDR_ERR_STATE, no
  *    operator PSF FDR_ERR_STATE.  FDR_ERR_ARG for mu or rho not finite or <= 0, iterations < 0, an unknown norm_area, a null
  *    params pointer or a window that does not fit; the plan stays usable after every refusal.  Unlike RL the output may be the
- *    input (d is read before anything is written).  Batches, fdr_batch_run and fdr_slab_* do not cover it.
+ *    input (d is read before anything is written).  Several images per launch, and the channels of a colour picture under one
+ *    shrinkage: fdr_tv_deconv_batch_f32* below; fdr_batch_run and fdr_slab_* do not cover it.
  *    The first call on a plan allocates the TV workspace, kept until fdr_plan_destroy: the table (fdr_plan_filter_bytes) and six
  *    M x N float planes -- 24 M N + 8 M N bytes, about 1.8 GB at 8192^2 beside the plan's own; FDR_ERR_ALLOC, plan intact, if it
  *    cannot be had -- and, if no CLS call has, the M + N doubles of L.  After it the _dev form allocates nothing and is
@@ -629,6 +630,47 @@ int fdr_tv_deconv_f32(fdr_plan* plan, const float* img_host, int rows, int cols,
                       const fdr_tv_params* params);
 int fdr_tv_deconv_f32_dev(fdr_plan* plan, const float* d_img, int rows, int cols, int stride, float* d_out, int out_stride,
                           const fdr_tv_params* params, void* stream);
+
+/* -- batched and colour TV deconvolution: `count` images with one operator PSF, several per launch.  Image i
+ *    is read at d_imgs + i img_pitch and written at d_out + i out_pitch (elements).  The batch is cut into launch groups of `group`
+ *    images (fdr_plan_set_batching; the last group may be smaller) and every pass of a group -- b, the start, per iteration the
+ *    spatial kernel, the forward rows, the solve columns and the x rows, the output -- is ONE launch over its images, so the solve
+ *    table is read once per group and a small picture no longer leaves the chip idle.  A group runs to completion on the caller's
+ *    stream, on the workspaces 0 .. group - 1, before the next begins, exactly as in fdr_richardson_lucy_batch_f32_dev.
+ *      FDR_TV_COUPLE_NONE      every image on its own: it comes out bit for bit as fdr_tv_deconv_f32_dev gives it on the same plan,
+ *                              for every group size, tail, window and layout, isotropic or anisotropic; group = 1 is literally the
+ *                              loop of the single calls.
+ *      FDR_TV_COUPLE_CHANNELS  vectorial TV (Blomgren & Chan 1998; Bresson & Chan 2008): the images are the channels of one picture,
+ *                              TV(x) = sum over pixels of sqrt(sum over c of |grad x_c|^2).  The iteration is the one above with
+ *                              one change: z_c = s g_c with s = m > t ? 1 - t / m : 0 and m = sqrt(sum over c of gx_c^2 + gy_c^2),
+ *                              summed over c = 0 .. count - 1 in that order, in float -- one shrinkage for all channels of a pixel,
+ *                              so an edge lies in the same place in every channel.  b, the duals, v, the divergence, the solve
+ *                              (with the one table T), the clamp and the normalisation stay per channel.  All channels sit in one
+ *                              launch: FDR_ERR_ARG if count exceeds the plan's `group` (at most 8).  Isotropic only: FDR_ERR_ARG with
+ *                              anisotropic != 0.  count = 1 gives the bits of fdr_tv_deconv_f32_dev.  The minimiser differs from
+ *                              the channel-wise one; its best mu is about 0.7 of the channel-wise best.
+ *    Refusals, always before any device work and with the plan usable afterwards: a null pointer or null params, a negative count
+ *    (count = 0 returns FDR_OK at once), whatever fdr_tv_deconv_f32_dev refuses for one image, an unknown coupling, and -- unlike
+ *    the single call -- an output that overlaps the input anywhere within the span of the batch.  The first call with a group g
+ *    larger than any before grows the TV workspace to the table and 6 g planes (8 M N + 24 g M N bytes; the table is then built
+ *    again); FDR_ERR_ALLOC leaves the plan and the workspace it had intact.  After that the _dev form allocates nothing, reads
+ *    nothing back and stays asynchronous on `stream`; the host form copies in and out synchronously.  Results repeat bit for bit
+ *    from call to call (no atomics).                                                                                          */
+#define FDR_TV_COUPLE_NONE 0     /* every image on its own: fdr_tv_deconv_f32_dev per image, bit for bit */
+#define FDR_TV_COUPLE_CHANNELS 1 /* vectorial TV: one shrinkage by the joint gradient norm of all `count` images */
+typedef struct fdr_tv_batch_params {
+    float mu;        /* weight of the data term, > 0 */
+    float rho;       /* ADMM penalty, > 0 */
+    int iterations;  /* >= 0 */
+    int anisotropic; /* 0: isotropic TV, else anisotropic (FDR_TV_COUPLE_NONE only) */
+    int nonneg;      /* != 0: the output is max(x, 0) */
+    int norm_area;   /* FDR_NORM_NONE / FDR_NORM_CROPPED / FDR_NORM_PADDED, per image */
+    int coupling;    /* FDR_TV_COUPLE_NONE / FDR_TV_COUPLE_CHANNELS */
+} fdr_tv_batch_params;
+int fdr_tv_deconv_batch_f32_dev(fdr_plan* plan, const float* d_imgs, size_t img_pitch, int count, int rows, int cols, int stride,
+                                float* d_out, size_t out_pitch, int out_stride, const fdr_tv_batch_params* params, void* stream);
+int fdr_tv_deconv_batch_f32(fdr_plan* plan, const float* imgs_host, size_t img_pitch, int count, int rows, int cols, int stride,
+                            float* out_host, size_t out_pitch, int out_stride, const fdr_tv_batch_params* params);
 
 /* -- the motion-blur estimate: the length and angle of a uniform linear motion blur, from the blurred
  *    picture alone, by the power cepstrum.  The blur puts sinc zeros into |G| in stripes across the motion direction; in the

@@ -442,15 +442,41 @@ inline std::vector<fdr_rl_auto_result> richardsonLucyAuto_RGB(std::vector<Mat>& 
 }
 // Total-variation deconvolution (fdr_tv_deconv_f32, include/fdr.h) of every channel, in place: the plan and operator PSF of
 // richardsonLucy_RGB, `iterations` ADMM steps of mu / 2 ||blur(x) - d||^2 + TV(x) (isotropic) with penalty rho, the output clamped
-// at 0 and normalised by o.norm_area.  o.mode and o.cls_gamma do not apply.
-inline void tvDeblur_RGB(std::vector<Mat>& channels, const Mat& psf, float mu, int iterations, float rho, const Options& o) {
+// at 0 and normalised by o.norm_area.  o.mode and o.cls_gamma do not apply.  The channels go through ONE batched call
+// (fdr_tv_deconv_batch_f32) on a launch group of channels.size() images (at most 8), with the bits of the per-channel calls;
+// channels of different sizes or types run one by one.  coupled: vectorial TV -- the channels share one shrinkage by their joint
+// gradient norm (FDR_TV_COUPLE_CHANNELS; at most 8 channels of one size), so edges fall in the same place in every channel.
+inline void tvDeblur_RGB(std::vector<Mat>& channels, const Mat& psf, float mu, int iterations, float rho, const Options& o, bool coupled = false) {
     if (channels.empty()) return;
-    const int rows = channels[0].rows, cols = channels[0].cols;
+    const int rows = channels[0].rows, cols = channels[0].cols, count = (int)channels.size();
     bool created = false;
     PlanCacheSettle settle_;
     fdr_plan* plan = plan_cache().get(o.device, std::max(8, nextPowerOfTwo(rows)), std::max(32, nextPowerOfTwo(cols)), FDR_MODE_FAST, &created);
     Mat psfc = psf.isContinuous() ? psf : psf.clone();
     FDR_CHECK(fdr_set_operator_psf(plan, psfc.ptr<float>(0), psf.rows, psf.cols, psf.cols));
+    bool same = true;
+    for (const Mat& c : channels) same = same && c.rows == rows && c.cols == cols && c.type() == CV_32F;
+    if (same || coupled) {
+        if (!same) {
+            std::cerr << "tvDeblur_RGB: the coupled form needs CV_32F channels of one size\n";
+            exit(1);
+        }
+        const size_t px = (size_t)rows * cols;
+        std::vector<float> in(px * count), out(px * count);
+        for (int i = 0; i < count; ++i)
+            for (int r = 0; r < rows; ++r) std::copy(channels[i].ptr<float>(r), channels[i].ptr<float>(r) + cols, in.begin() + i * px + (size_t)r * cols);
+        const fdr_tv_batch_params bp = {mu, rho, iterations, 0, 1, o.norm_area, coupled ? FDR_TV_COUPLE_CHANNELS : FDR_TV_COUPLE_NONE};
+        FDR_CHECK(fdr_plan_set_batching(plan, 1, std::min(count, 8)));
+        const int rc = fdr_tv_deconv_batch_f32(plan, in.data(), px, count, rows, cols, cols, out.data(), px, cols, &bp);
+        FDR_CHECK(fdr_plan_set_batching(plan, 1, 1));  // the cached plan goes back as it came
+        FDR_CHECK(rc);
+        for (int i = 0; i < count; ++i) {
+            Mat m(rows, cols, CV_32F);
+            std::copy(out.begin() + i * px, out.begin() + (i + 1) * px, m.ptr<float>(0));
+            channels[i] = m;
+        }
+        return;
+    }
     const fdr_tv_params prm = {mu, rho, iterations, 0, 1, o.norm_area};
     for (Mat& c : channels) {
         Mat src = c.isContinuous() ? c : c.clone();
@@ -459,8 +485,8 @@ inline void tvDeblur_RGB(std::vector<Mat>& channels, const Mat& psf, float mu, i
         c = out;
     }
 }
-inline void tvDeblur_RGB(std::vector<Mat>& channels, const Mat& psf, float mu, int iterations = 50, float rho = 2.0f) {
-    tvDeblur_RGB(channels, psf, mu, iterations, rho, defaults());
+inline void tvDeblur_RGB(std::vector<Mat>& channels, const Mat& psf, float mu, int iterations = 50, float rho = 2.0f, bool coupled = false) {
+    tvDeblur_RGB(channels, psf, mu, iterations, rho, defaults(), coupled);
 }
 // The motion blur of a one-channel picture of unknown blur (fdr_estimate_motion_f32, include/fdr.h): length and angle in the
 // convention of motionBlurKernel, the table minimum and the confidence (below about 10: no clear blur).  Its own FDR_MODE_FAST plan

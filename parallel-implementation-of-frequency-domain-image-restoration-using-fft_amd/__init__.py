@@ -34,6 +34,8 @@ RL_SIGMA = 1e-2  # FDR_RL_SIGMA: the usual coverage threshold of free-boundary R
 RLTV_MAX_LAMBDA = 0.125  # FDR_RLTV_MAX_LAMBDA: the largest weight of Richardson-Lucy's total-variation prior
 RLTV_EPS = 1e-3  # FDR_RLTV_EPS: the smoothing of |grad u| that eps = 0 selects
 RL_STOP_NONE, RL_STOP_RESIDUAL, RL_STOP_KL = 0, 1, 2  # FDR_RL_STOP_*: the stopping rules of Plan.richardson_lucy_auto
+TV_COUPLE_NONE = 0      # FDR_TV_COUPLE_NONE: every image of a TV batch on its own
+TV_COUPLE_CHANNELS = 1  # FDR_TV_COUPLE_CHANNELS: vectorial TV, one shrinkage by the joint gradient norm of the channels
 RL_ACCEL_MAX = 0.9990234375  # FDR_RL_ACCEL_MAX = 1 - 2^-10: the upper bound of accelerated Richardson-Lucy's extrapolation factor
 MAX_PASSES = 16
 OPT_TWO_SWEEP_NORM = 2
@@ -77,6 +79,12 @@ class TvParams(ctypes.Structure):
     """fdr_tv_params of include/fdr.h"""
     _fields_ = [("mu", ctypes.c_float), ("rho", ctypes.c_float), ("iterations", ctypes.c_int), ("anisotropic", ctypes.c_int),
                 ("nonneg", ctypes.c_int), ("norm_area", ctypes.c_int)]
+
+
+class TvBatchParams(ctypes.Structure):
+    """fdr_tv_batch_params of include/fdr.h"""
+    _fields_ = [("mu", ctypes.c_float), ("rho", ctypes.c_float), ("iterations", ctypes.c_int), ("anisotropic", ctypes.c_int),
+                ("nonneg", ctypes.c_int), ("norm_area", ctypes.c_int), ("coupling", ctypes.c_int)]
 
 
 class RlFreeParams(ctypes.Structure):
@@ -276,6 +284,8 @@ def _signatures():
         "fdr_psf_gaussian_dev": (ci, [ci, ci, cd, vp, vp]),
         "fdr_tv_deconv_f32": (ci, [vp, vp, ci, ci, ci, vp, ci, P(TvParams)]),
         "fdr_tv_deconv_f32_dev": (ci, [vp, vp, ci, ci, ci, vp, ci, P(TvParams), vp]),
+        "fdr_tv_deconv_batch_f32": (ci, [vp, vp, sz, ci, ci, ci, ci, vp, sz, ci, P(TvBatchParams)]),
+        "fdr_tv_deconv_batch_f32_dev": (ci, [vp, vp, sz, ci, ci, ci, ci, vp, sz, ci, P(TvBatchParams), vp]),
         "fdr_cepstrum_f32": (ci, [vp, vp, ci, ci, ci, vp]),
         "fdr_cepstrum_f32_dev": (ci, [vp, vp, ci, ci, ci, vp, vp]),
         "fdr_estimate_motion_f32": (ci, [vp, vp, ci, ci, ci, ci, ci, cd, P(MotionEstimateC), vp]),
@@ -846,6 +856,28 @@ class Plan:
         _check(lib.fdr_tv_deconv_f32_dev(self._h, ctypes.c_void_p(int(d_img)), rows, cols, stride, ctypes.c_void_p(int(d_out)), out_stride,
                                          ctypes.byref(prm), _stream(stream)))
 
+
+    def tv_deconv_batch_dev(self, d_imgs, img_pitch, count, rows, cols, stride, d_out, out_pitch, out_stride, mu, rho=2.0, iterations=50,
+                            anisotropic=False, nonneg=False, norm_area=NORM_NONE, coupled=False, stream=None):
+        """fdr_tv_deconv_batch_f32_dev: tv_deconv_dev on `count` windows, image i at d_imgs + i img_pitch / d_out + i out_pitch
+        (elements), in launch groups of the plan's `group` (set_batching).  coupled: the images are the channels of one picture
+        and share one shrinkage by their joint gradient norm (vectorial TV; count <= group, isotropic).  Asynchronous."""
+        prm = TvBatchParams(float(mu), float(rho), int(iterations), int(bool(anisotropic)), int(bool(nonneg)), int(norm_area),
+                            TV_COUPLE_CHANNELS if coupled else TV_COUPLE_NONE)
+        _check(lib.fdr_tv_deconv_batch_f32_dev(self._h, ctypes.c_void_p(int(d_imgs)), img_pitch, count, rows, cols, stride,
+                                               ctypes.c_void_p(int(d_out)), out_pitch, out_stride, ctypes.byref(prm), _stream(stream)))
+
+    def tv_deconv_batch(self, imgs, mu, rho=2.0, iterations=50, anisotropic=False, nonneg=False, norm_area=NORM_NONE, coupled=False):
+        """Host arrays [count, rows, cols] in, [count, rows, cols] out: tv_deconv per image, several per launch; coupled: vectorial
+        TV on the images as the channels of one picture (fdr_tv_deconv_batch_f32)."""
+        imgs = np.ascontiguousarray(imgs, dtype=np.float32)
+        cnt, rows, cols = imgs.shape
+        out = np.empty((cnt, rows, cols), dtype=np.float32)
+        prm = TvBatchParams(float(mu), float(rho), int(iterations), int(bool(anisotropic)), int(bool(nonneg)), int(norm_area),
+                            TV_COUPLE_CHANNELS if coupled else TV_COUPLE_NONE)
+        _check(lib.fdr_tv_deconv_batch_f32(self._h, _ptr(imgs), rows * cols, cnt, rows, cols, cols, _ptr(out), rows * cols, cols, ctypes.byref(prm)))
+        return out
+
     # the motion-blur estimate (include/fdr.h): the power cepstrum of the windowed picture and the blur it shows
     def cepstrum(self, img):
         """c = Re IDFT2(log(|DFT2(hann . img)| + eps)) on the plan (M x N float32); img is the window at the top-left (host array)"""
@@ -1232,6 +1264,22 @@ def tvDeblur_myfft(img, psf, mu, rho=2.0, iterations=50, anisotropic=False, nonn
     with Plan(M, N, MODE_FAST, device) as p:
         p.set_operator_psf(psf)
         return p.tv_deconv(img, mu, rho, iterations, anisotropic, nonneg, norm_area)
+
+
+def tvDeblur_RGB(channels, psf, mu, rho=2.0, iterations=50, nonneg=False, device=0, norm_area=NORM_NONE, coupled=False):
+    """fft_gpu::tvDeblur_RGB: replaces every element of `channels` (float32 planes of one size, at most 8 when coupled) in place with
+    its total-variation estimate, from one plan (that of richardsonLucy_RGB) and one launch per pass -- the bits of tvDeblur_myfft per
+    channel, or with coupled the vectorial TV of the picture: one shrinkage by the joint gradient norm of the channels."""
+    if not channels:
+        return
+    r, c = np.asarray(channels[0]).shape
+    M, N = _rl_plan_size(r, c)
+    with Plan(M, N, MODE_FAST, device) as p:
+        p.set_operator_psf(psf)
+        p.set_batching(1, min(len(channels), 8))
+        out = p.tv_deconv_batch(np.stack([np.asarray(c, dtype=np.float32) for c in channels]), mu, rho, iterations, False, nonneg, norm_area, coupled)
+    for i in range(len(channels)):
+        channels[i] = out[i]
 
 
 def _motion_plan_size(rows, cols):

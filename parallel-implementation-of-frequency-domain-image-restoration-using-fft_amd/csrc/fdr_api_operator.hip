@@ -149,12 +149,14 @@ int blur_window_dev(fdr_plan* p, const float* d_img, int rows, int cols, int str
     return rc;
 }
 
-// the same for a group of n images on the slots ws[0 .. n): six launches whatever n
+// the same for a group of n images on the slots ws[0 .. n): six launches whatever n (out_rows = out_cols = 0: the window of the input)
 int blur_window_dev_n(fdr_plan* p, fdr_plan::Slot* const* ws, int n, const float* const* d_imgs, int rows, int cols, int stride,
-                      float* const* d_outs, int out_stride, int adjoint, hipStream_t s) {
+                      float* const* d_outs, int out_stride, int adjoint, hipStream_t s, int out_rows, int out_cols) {
     int rc = op_rows_fwd_n(p, ws, n, d_imgs, rows, cols, stride, s);
     if (rc == FDR_OK) rc = op_cols_n(p, ws, n, adjoint != 0, s);
-    if (rc == FDR_OK) rc = op_rows_inv_n(p, ws, n, ROW_OUT_BLUR, kPassOpRowsBlur, nullptr, 0, nullptr, d_outs, out_stride, rows, cols, s);
+    if (rc == FDR_OK)
+        rc = op_rows_inv_n(p, ws, n, ROW_OUT_BLUR, kPassOpRowsBlur, nullptr, 0, nullptr, d_outs, out_stride, out_rows ? out_rows : rows,
+                           out_cols ? out_cols : cols, s);
     return rc;
 }
 

@@ -124,8 +124,11 @@ struct fdr_plan {
     unsigned op_gen = 0;  // counts the fdr_set_operator_psf* calls that rebuilt the tables
     // total-variation deconvolution (fdr_tv_deconv_f32*): made by the first such call, kept until fdr_plan_destroy -- one allocation
     // holding the solve table T (ws_elems, layout of `filt`) and six M x N real planes: x, b and two pairs of duals (rhs lives in slot 0's `raw`).
-    // T was built for (tv_mu, tv_rho) and the operator tables of generation tv_gen; tv_gen 0 = not built.
+    // T was built for (tv_mu, tv_rho) and the operator tables of generation tv_gen; tv_gen 0 = not built.  A batched call on groups of
+    // g images (fdr_tv_deconv_batch_f32*) grows it to one T and 6 g planes: tv_group = the images it holds, the six planes of image k
+    // lie 6 k M N floats behind those of image 0 (ensure_tv_workspace, tv_image_stride), its rhs in slot k's `raw`.
     void* tv_block = nullptr;
+    int tv_group = 0;
     float2* tv_T = nullptr;
     float *tv_x = nullptr, *tv_b = nullptr, *tv_w[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};  // tv_w[pair][0 = wx, 1 = wy]
     float tv_mu = 0.f, tv_rho = 0.f;
@@ -369,8 +372,9 @@ int op_rows_inv(fdr_plan* p, RowOut kind, const char* name, const float* src, in
 // blur (adjoint != 0: blur^T) of the window rows x cols of d_img; the window out_rows x out_cols of the result into d_out
 int blur_window_dev(fdr_plan* p, const float* d_img, int rows, int cols, int stride, float* d_out, int out_stride, int out_rows, int out_cols,
                     int adjoint, hipStream_t s);
+// (the group form writes the window of the input unless out_rows x out_cols names another)
 int blur_window_dev_n(fdr_plan* p, fdr_plan::Slot* const* ws, int n, const float* const* d_imgs, int rows, int cols, int stride,
-                      float* const* d_outs, int out_stride, int adjoint, hipStream_t s);
+                      float* const* d_outs, int out_stride, int adjoint, hipStream_t s, int out_rows = 0, int out_cols = 0);
 // min-max of the window `fin` (row stride fs) to [0, 1] into d_out, timed as `name`: FDR_NORM_CROPPED over the window, FDR_NORM_PADDED
 // counting the zeros outside it too
 int normalize_window(fdr_plan* p, const char* fn, const char* name, const float* fin, int fs, int rows, int cols, int norm_area, float* d_out,
@@ -482,7 +486,22 @@ int rl_accel_steps(fdr_plan* p, int nimg, int k0, int k1, int n, int rows, int c
 // pairs of one fdr_reg_curve_f32* call (fdr_api_reg.hip): what the candidate and result arrays of the plan hold
 constexpr int kRegMaxCurve = 4096;
 static_assert(kRegMaxCurve % kRegCandidates == 0, "the last sweep reads kRegCandidates pairs");
-// the entry points of fdr_api_tv.hip
+// ---- total-variation deconvolution (fdr_api_tv.hip), shared with its batch (fdr_api_tvbatch.hip) ----
+// everything a TV call refuses for one image, before any device work
+int tv_check(const fdr_plan* p, const char* fn, int rows, int cols, int stride, int out_stride, const fdr_tv_params* prm);
+// the TV workspace for `group` images (T and 6 group planes) and the Laplacian table, both synchronous and on first use only.  The
+// workspace grows on the first use with a larger group (T is then built again by the next call); FDR_ERR_ALLOC, sticky HIP error
+// cleared, leaves the plan and the workspace it had intact.
+int ensure_tv_workspace(fdr_plan* p, const char* fn, int group = 1);
+int tv_prepare(fdr_plan* p, const char* fn, int group = 1);
+inline size_t tv_image_stride(const fdr_plan* p) { return (size_t)6 * p->M * p->N; }
+// The iteration on a checked group of n >= 1 images on the slots ws[0 .. n) and the planes 0 .. n - 1 of the workspace: b and the
+// start per group, per iteration one spatial, one forward-row, one solve-column and one x-row launch for the group, the output (and
+// its normalisation, per image) at the end.  `coupled`: the images are the channels of one picture and share the shrinkage
+// (isotropic).  Uncoupled, every image gets the bits it gets alone; one image makes the launches of the single-image call.
+int tv_group_dev(fdr_plan* p, const char* fn, fdr_plan::Slot* const* ws, int n, const float* const* d_imgs, int rows, int cols, int stride,
+                 float* const* d_outs, int out_stride, const fdr_tv_params& prm, bool coupled, hipStream_t s);
+// one image on slot 0: the group of one
 int tv_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, int cols, int stride, float* d_out, int out_stride,
                 const fdr_tv_params& prm, hipStream_t s);
 

@@ -231,6 +231,17 @@ hipError_t launch_tv_init(const float* d, int rows, int cols, int stride, float*
 hipError_t launch_tv_spatial(const float* x, const float* wx, const float* wy, const float* b, float* nwx, float* nwy, float* rhs, int M, int N,
                              float mu, float rho, int anisotropic, hipStream_t s);
 hipError_t launch_tv_output(const float* x, int N, float* out, int rows, int cols, int out_stride, int nonneg, hipStream_t s);
+// the same on a group of 1 <= nimg <= kMaxGroup images in one launch each (blockIdx.z = image; one image is the single-image launch):
+// per-image planes (spatial: those of image k lie k * stride floats behind those of image 0, its rhs is rhs[k]), every image with the
+// bits of the single-image kernels.  spatial with `coupled` (isotropic only; any nimg >= 1):
+// the images are the channels of one picture and share the shrinkage, z_c = s g_c, s = max(1 - t / m, 0), m^2 = the sum over the
+// channels, in their order, of gx_c^2 + gy_c^2 (vectorial TV); one channel gives the bits of the single-image kernel.
+hipError_t launch_tv_init_n(int nimg, const float* const* d, int rows, int cols, int stride, float* const* x, float* const* wx, float* const* wy,
+                            int M, int N, hipStream_t s);
+hipError_t launch_tv_spatial_n(int nimg, const float* x, const float* wx, const float* wy, const float* b, float* nwx, float* nwy, size_t stride,
+                               float* const* rhs, int M, int N, float mu, float rho, int anisotropic, int coupled, hipStream_t s);
+hipError_t launch_tv_output_n(int nimg, const float* const* x, int N, float* const* out, int rows, int cols, int out_stride, int nonneg,
+                              hipStream_t s);
 
 // (fdr_motion.hip) the motion-blur estimate.  window: the Hann tables into hann[rows + cols], w . img on the window and 0 elsewhere
 // into the row-major M x N complex plane, sum |x| partials (motion_pad_partials of them) folded in a fixed order into

@@ -1,5 +1,5 @@
 // gpu.cpp -- ./gpu <img-path> <psf-length> <psf-angle> | auto auto [--any-blur] | defocus <radius|auto> | blind <size>  [--out file] [--mode fast|parity] [--norm padded|cropped] [--host-epilogue]
-//           [--cls gamma|auto] [--k K|auto] [--reg gcv|discrepancy] [--sigma s] [--pad zero|smooth] [--rl iterations|auto [--accel] [--rl-tv lambda [--rl-tv-eps e]] [--free-boundary [--mask mask.png]] [--rl-max n] [--rl-stop residual|kl] [--gain g] [--rl-check c]] [--tv mu [--tv-iters n] [--tv-rho r]]
+//           [--cls gamma|auto] [--k K|auto] [--reg gcv|discrepancy] [--sigma s] [--pad zero|smooth] [--rl iterations|auto [--accel] [--rl-tv lambda [--rl-tv-eps e]] [--free-boundary [--mask mask.png]] [--rl-max n] [--rl-stop residual|kl] [--gain g] [--rl-check c]] [--tv mu [--tv-iters n] [--tv-rho r] [--tv-color]]
 // `auto auto` for length and angle: the blur is estimated first (fft_gpu::estimateMotionBlur on the per-pixel mean of B, G and R),
 // printed as `estimate: length L angle A confidence C`, and the run then goes on exactly as `./gpu <img-path> L A` would.
 // `--cls auto` (gamma, with K = 0) or `--k auto` (K, with gamma = 0): the weight is chosen first (fft_gpu::chooseRegularisation on the same
@@ -114,6 +114,7 @@ int main(int argc, char** argv) {
     float tv_mu = -1.f, tv_rho = 2.0f;  // --tv mu: a timed total-variation leg (fft_gpu::tvDeblur_RGB); its planes are the written result
     int tv_iterations = 50;
     bool tv_opts = false;
+    bool tv_color = false;  // --tv-color: vectorial TV, the three channels under one shrinkage (tvDeblur_RGB's coupled form)
     bool cls = false, parity = false, pad_smooth = false;
     bool cls_auto = false, k_auto = false;  // --cls auto / --k auto: the weight is chosen from the picture
     string reg_method;                      // --reg gcv|discrepancy
@@ -173,6 +174,7 @@ int main(int argc, char** argv) {
         else if (a == "--tv" && i + 1 < argc) tv_mu = strtof(argv[++i], nullptr);
         else if (a == "--tv-iters" && i + 1 < argc) { tv_opts = true; tv_iterations = atoi(argv[++i]); }
         else if (a == "--tv-rho" && i + 1 < argc) { tv_opts = true; tv_rho = strtof(argv[++i], nullptr); }
+        else if (a == "--tv-color") { tv_opts = true; tv_color = true; }
         else { cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle>\n"; return -1; }
     }
     if (defocus && !defocus_auto && !(psf_radius > 0.0 && psf_radius <= 127.0)) { cout << "Usage: ./gpu <img-path> defocus <radius in (0, 127]|auto>\n"; return -1; }
@@ -216,7 +218,7 @@ int main(int argc, char** argv) {
         cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle>\n";
         return -1;
     }
-    // so does the TV leg; --tv-iters / --tv-rho belong to --tv, and one run has one iterative leg
+    // so does the TV leg; --tv-iters / --tv-rho / --tv-color belong to --tv, and one run has one iterative leg
     const bool tv = tv_mu > 0.f;
     if ((tv && (cls || verify || parity || pad_smooth || rl_iterations >= 0 || tv_iterations < 0 || !(tv_rho > 0.f))) || (!tv && (tv_opts || tv_mu != -1.f))) {
         cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle>\n";
@@ -409,10 +411,10 @@ int main(int argc, char** argv) {
     if (tv) {  // total-variation deconvolution on the same channels: its planes become the written result
         vector<Mat> tvc = input;
         t_start = high_resolution_clock::now();
-        fft_gpu::tvDeblur_RGB(tvc, psf, tv_mu, tv_iterations, tv_rho);
+        fft_gpu::tvDeblur_RGB(tvc, psf, tv_mu, tv_iterations, tv_rho, tv_color);
         t_end = high_resolution_clock::now();
         cout << "Deblurring 3 channels took(gpu[total-variation mu " << tv_mu << " rho " << tv_rho << " n " << tv_iterations
-             << "]): " << getElapsedMs(t_start, t_end) << " ms\n";
+             << (tv_color ? " colour" : "") << "]): " << getElapsedMs(t_start, t_end) << " ms\n";
         channels = tvc;
     }
 
