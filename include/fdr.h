@@ -672,6 +672,50 @@ int fdr_tv_deconv_batch_f32_dev(fdr_plan* plan, const float* d_imgs, size_t img_
 int fdr_tv_deconv_batch_f32(fdr_plan* plan, const float* imgs_host, size_t img_pitch, int count, int rows, int cols, int stride,
                             float* out_host, size_t out_pitch, int out_stride, const fdr_tv_batch_params* params);
 
+/* -- free-boundary, weighted TV deconvolution: fdr_tv_deconv_f32 for a picture that is a crop of a larger scene (DESIGN.md section
+ *    31).  The periodic call's data term counts the zero padding of the plan as data; here the data constrain x inside the window
+ *    only, each pixel by its weight, and x is free elsewhere on the plan, as in fdr_richardson_lucy_free_f32:
+ *        minimise over x (M x N):  mu / 2 sum m (blur(x) - pad(d))^2 + TV(x),   m = the weights on the window, 0 elsewhere
+ *    (weights null: 1 on the window; 0 excludes a pixel, as a dead or saturated one).  ADMM with two splittings (Almeida &
+ *    Figueiredo 2013; Matakos, Ramani & Fessler 2013): z = D x with the scaled dual w and the penalty rho as above, and s = blur(x)
+ *    with the scaled dual q and the penalty nu, which keeps the linear solve diagonal in the Fourier domain:
+ *        x = pad(d);  w = 0;  q = 0;  t = 1 / rho;  n = iterations times:
+ *            c = blur(x)                                                             whole plan
+ *            e = c + q;  s = (mu m pad(d) + nu e) / (mu m + nu);  q = e - s;  r = s - q     (outside the window: q = 0, r = c)
+ *            b = blur^T(r)                                                           whole plan
+ *            g = D x + w;  z = shrink(g, t);  w = g - z;  v = z - w                  as fdr_tv_deconv_f32
+ *            x = IDFT2( DFT2(nu b + rho (Dx^T vx + Dy^T vy)) / (nu |H|^2 + rho L) )
+ *    The output is the top-left out_rows x out_cols of x (rows <= out_rows <= M, cols <= out_cols <= N: the window, the whole plan
+ *    or anything between), max(x, 0) with nonneg, normalised by norm_area over what is returned as fdr_richardson_lucy_free_f32
+ *    does.  n = 0 returns pad(d) there.  nu = 0 selects nu = rho; like rho it changes the path, not the minimiser.  With the
+ *    window equal to the plan and no weights the minimiser is that of fdr_tv_deconv_f32.  The solve divides by nu |H|^2 + rho L with
+ *    nu of the order of rho, so a large mu does not amplify rounding as it does in the periodic call.
+ *    Plans and refusals as fdr_tv_deconv_f32*, and FDR_ERR_ARG for nu not finite or < 0, wstride < cols with weights, an output
+ *    window outside [rows .. M] x [cols .. N], out_stride < out_cols, and an output that overlaps the input or the weights (both
+ *    are read in every iteration, in place, from the caller's windows).  Weights outside [0, 1] are not checked.  The plan stays
+ *    usable after every refusal.
+ *    The first call on a plan allocates, beside the TV workspace of fdr_tv_deconv_f32, two more M x N float planes (q and c / r) in
+ *    a block of their own, kept until fdr_plan_destroy; FDR_ERR_ALLOC, plan intact, if it cannot be had.  After it the _dev form
+ *    allocates nothing, reads nothing back and is asynchronous on `stream`; the solve table is shared with fdr_tv_deconv_f32 and
+ *    rebuilt when nu, rho or the operator PSF differ from what it was built for.  The host form copies in and out synchronously.
+ *    An iteration is three blur chains, the spatial kernel and one streaming pass over the window (20 bytes per pixel, 24 with
+ *    weights).  Results repeat bit for bit from call to call (no atomics).                                                     */
+typedef struct fdr_tv_free_params {
+    float mu;        /* weight of the data term, > 0 */
+    float rho;       /* ADMM penalty of z = D x, > 0 */
+    float nu;        /* ADMM penalty of s = blur(x), >= 0; 0 selects rho */
+    int iterations;  /* >= 0 */
+    int anisotropic; /* 0: isotropic TV, else anisotropic */
+    int nonneg;      /* != 0: the output is max(x, 0) */
+    int norm_area;   /* FDR_NORM_NONE / FDR_NORM_CROPPED / FDR_NORM_PADDED, over the output window */
+    int out_rows;    /* rows .. M */
+    int out_cols;    /* cols .. N */
+} fdr_tv_free_params;
+int fdr_tv_deconv_free_f32(fdr_plan* plan, const float* img_host, int rows, int cols, int stride, const float* weights_host, int wstride,
+                           float* out_host, int out_stride, const fdr_tv_free_params* params);
+int fdr_tv_deconv_free_f32_dev(fdr_plan* plan, const float* d_img, int rows, int cols, int stride, const float* d_weights, int wstride,
+                               float* d_out, int out_stride, const fdr_tv_free_params* params, void* stream);
+
 /* -- the motion-blur estimate: the length and angle of a uniform linear motion blur, from the blurred
  *    picture alone, by the power cepstrum.  The blur puts sinc zeros into |G| in stripes across the motion direction; in the
  *    cepstrum they show as a negative peak at distance L along it.  The plan is M x N, the image window rows x cols (row stride

@@ -87,6 +87,13 @@ class TvBatchParams(ctypes.Structure):
                 ("nonneg", ctypes.c_int), ("norm_area", ctypes.c_int), ("coupling", ctypes.c_int)]
 
 
+class TvFreeParams(ctypes.Structure):
+    """fdr_tv_free_params of include/fdr.h"""
+    _fields_ = [("mu", ctypes.c_float), ("rho", ctypes.c_float), ("nu", ctypes.c_float), ("iterations", ctypes.c_int),
+                ("anisotropic", ctypes.c_int), ("nonneg", ctypes.c_int), ("norm_area", ctypes.c_int), ("out_rows", ctypes.c_int),
+                ("out_cols", ctypes.c_int)]
+
+
 class RlFreeParams(ctypes.Structure):
     """fdr_rlfree_params of include/fdr.h"""
     _fields_ = [("iterations", ctypes.c_int), ("sigma", ctypes.c_float), ("norm_area", ctypes.c_int), ("out_rows", ctypes.c_int),
@@ -286,6 +293,8 @@ def _signatures():
         "fdr_tv_deconv_f32_dev": (ci, [vp, vp, ci, ci, ci, vp, ci, P(TvParams), vp]),
         "fdr_tv_deconv_batch_f32": (ci, [vp, vp, sz, ci, ci, ci, ci, vp, sz, ci, P(TvBatchParams)]),
         "fdr_tv_deconv_batch_f32_dev": (ci, [vp, vp, sz, ci, ci, ci, ci, vp, sz, ci, P(TvBatchParams), vp]),
+        "fdr_tv_deconv_free_f32": (ci, [vp, vp, ci, ci, ci, vp, ci, vp, ci, P(TvFreeParams)]),
+        "fdr_tv_deconv_free_f32_dev": (ci, [vp, vp, ci, ci, ci, vp, ci, vp, ci, P(TvFreeParams), vp]),
         "fdr_cepstrum_f32": (ci, [vp, vp, ci, ci, ci, vp]),
         "fdr_cepstrum_f32_dev": (ci, [vp, vp, ci, ci, ci, vp, vp]),
         "fdr_estimate_motion_f32": (ci, [vp, vp, ci, ci, ci, ci, ci, cd, P(MotionEstimateC), vp]),
@@ -856,6 +865,35 @@ class Plan:
         _check(lib.fdr_tv_deconv_f32_dev(self._h, ctypes.c_void_p(int(d_img)), rows, cols, stride, ctypes.c_void_p(int(d_out)), out_stride,
                                          ctypes.byref(prm), _stream(stream)))
 
+    # free-boundary, weighted TV deconvolution (include/fdr.h); uses the operator PSF
+    def tv_deconv_free(self, img, mu, rho=2.0, iterations=50, weights=None, nu=0.0, anisotropic=False, nonneg=False, norm_area=NORM_NONE,
+                       full_plane=False):
+        """`iterations` ADMM steps of mu / 2 sum m (blur(x) - img)^2 + TV(x) on the window img (host arrays) that is a crop of a larger
+        scene: x lives on the whole plan, the data constrain it inside the window only.  weights (img.shape, in [0, 1]; None = all
+        ones) say how much each pixel counts: 0 excludes it.  nu is the penalty of the splitting s = blur(x) (0 = rho).  Returns the
+        window, or with full_plane the whole M x N estimate; normalised over what is returned (fdr_tv_deconv_free_f32)."""
+        img = np.ascontiguousarray(img, dtype=np.float32)
+        rows, cols = img.shape
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float32)
+            if w.shape != img.shape:
+                raise ValueError("weights must have the shape of img")
+        orows, ocols = (self.M, self.N) if full_plane else (rows, cols)
+        out = np.empty((orows, ocols), dtype=np.float32)
+        prm = TvFreeParams(float(mu), float(rho), float(nu), int(iterations), int(bool(anisotropic)), int(bool(nonneg)), int(norm_area), orows, ocols)
+        _check(lib.fdr_tv_deconv_free_f32(self._h, _ptr(img), rows, cols, cols, _ptr(w) if w is not None else None, cols, _ptr(out), ocols,
+                                          ctypes.byref(prm)))
+        return out
+
+    def tv_deconv_free_dev(self, d_img, rows, cols, stride, d_out, out_stride, mu, rho=2.0, iterations=50, d_weights=None, wstride=0, nu=0.0,
+                           anisotropic=False, nonneg=False, norm_area=NORM_NONE, out_rows=None, out_cols=None, stream=None):
+        """the same on device pointers; out_rows x out_cols (default rows x cols, up to M x N) is the output window.  Asynchronous."""
+        prm = TvFreeParams(float(mu), float(rho), float(nu), int(iterations), int(bool(anisotropic)), int(bool(nonneg)), int(norm_area),
+                           int(rows if out_rows is None else out_rows), int(cols if out_cols is None else out_cols))
+        _check(lib.fdr_tv_deconv_free_f32_dev(self._h, ctypes.c_void_p(int(d_img)), rows, cols, stride,
+                                              ctypes.c_void_p(int(d_weights)) if d_weights else None, int(wstride),
+                                              ctypes.c_void_p(int(d_out)), out_stride, ctypes.byref(prm), _stream(stream)))
 
     def tv_deconv_batch_dev(self, d_imgs, img_pitch, count, rows, cols, stride, d_out, out_pitch, out_stride, mu, rho=2.0, iterations=50,
                             anisotropic=False, nonneg=False, norm_area=NORM_NONE, coupled=False, stream=None):
@@ -1280,6 +1318,34 @@ def tvDeblur_RGB(channels, psf, mu, rho=2.0, iterations=50, nonneg=False, device
         out = p.tv_deconv_batch(np.stack([np.asarray(c, dtype=np.float32) for c in channels]), mu, rho, iterations, False, nonneg, norm_area, coupled)
     for i in range(len(channels)):
         channels[i] = out[i]
+
+
+def tvDeblurFree_myfft(img, psf, mu, rho=2.0, iterations=50, weights=None, nu=0.0, anisotropic=False, nonneg=False, device=0,
+                       norm_area=NORM_NONE, full_plane=False):
+    """Free-boundary, weighted total-variation deconvolution of one channel that is a crop of a larger scene: the plan of
+    richardsonLucyFree_myfft (room for the PSF's reach beyond the window), `iterations` ADMM steps on the device, the window (or with
+    full_plane the whole plan) back.  psf lies top-left in the plan; weights as Plan.tv_deconv_free."""
+    img = np.asarray(img, dtype=np.float32)
+    psf = np.asarray(psf, dtype=np.float32)
+    M, N = _rlfree_plan_size(img.shape[0], img.shape[1], psf.shape[0], psf.shape[1])
+    with Plan(M, N, MODE_FAST, device) as p:
+        p.set_operator_psf(psf)
+        return p.tv_deconv_free(img, mu, rho, iterations, weights, nu, anisotropic, nonneg, norm_area, full_plane)
+
+
+def tvDeblurFree_RGB(channels, psf, mu, rho=2.0, iterations=50, nonneg=False, device=0, norm_area=NORM_NONE, weights=None, nu=0.0):
+    """fft_gpu::tvDeblurFree_RGB: replaces every element of `channels` (float32 planes of one size) in place with its free-boundary
+    total-variation estimate, from one plan (that of tvDeblurFree_myfft) and one weights plane for all channels, one channel after
+    the other -- the bits of tvDeblurFree_myfft per channel."""
+    if not channels:
+        return
+    psf = np.asarray(psf, dtype=np.float32)
+    r, c = np.asarray(channels[0]).shape
+    M, N = _rlfree_plan_size(r, c, psf.shape[0], psf.shape[1])
+    with Plan(M, N, MODE_FAST, device) as p:
+        p.set_operator_psf(psf)
+        for i in range(len(channels)):
+            channels[i] = p.tv_deconv_free(channels[i], mu, rho, iterations, weights, nu, False, nonneg, norm_area)
 
 
 def _motion_plan_size(rows, cols):

@@ -1,0 +1,163 @@
+// fdr_api_tvfree.hip -- free-boundary, weighted TV deconvolution by ADMM with two splittings (fdr_tv_deconv_free_f32*; the data step
+// in fdr_tvfree.hip): the two planes it adds to the TV workspace, the checks, the driver and the two entry points.  Everything but
+// the data step is the periodic call's: the table kernel, the start and the spatial kernel of fdr_tv.hip with nu in the place of
+// mu, and the blur and solve chains of fdr_api_operator.hip on full planes.
+#include "fdr_host.hpp"
+
+#include <cmath>
+
+using namespace fdr;
+
+namespace {
+
+// names are static strings compared by pointer in PassTimer::pass_id
+const char* const kPassTfTable = "TV table: 1/(nu|H|^2+rho L)/MN (free)";
+const char* const kPassTfInit = "TVF init: x = pad(d), w = q = 0";
+const char* const kPassTfData = "TVF data: s, q, r = 2s-e (window)";
+const char* const kPassTfSpatial = "TV spatial: shrink+dual+div (free)";
+const char* const kPassTfSolve = "B' op cols: FFT*T*IFFT (TVF solve)";
+const char* const kPassTfX = "C op rows: IFFT (TVF x)";
+const char* const kPassTfOut = "TVF out: crop+clamp";
+const char* const kPassTfNorm = "E TVF minmax+normalize";
+
+// everything a free-boundary TV call refuses, before any device work: what the periodic call refuses, and nu, the weights' stride,
+// the output window and an output that overlaps the input or the weights (both are read in every iteration)
+int tvfree_check(const fdr_plan* p, const char* fn, const float* img, int rows, int cols, int stride, const float* weights, int wstride,
+                 const float* out, int out_stride, const fdr_tv_free_params* prm) {
+    if (!prm) return null_arg(fn);
+    const fdr_tv_params periodic = {prm->mu, prm->rho, prm->iterations, prm->anisotropic, prm->nonneg, prm->norm_area};
+    const int rc = tv_check(p, fn, rows, cols, stride, out_stride, &periodic);
+    if (rc != FDR_OK) return rc;
+    if (!std::isfinite(prm->nu) || prm->nu < 0.f) return fail(FDR_ERR_ARG, std::string(fn) + ": nu must be finite and >= 0");
+    if (weights && wstride < cols) return fail(FDR_ERR_ARG, std::string(fn) + ": the weights' stride must be >= cols");
+    if (prm->out_rows < rows || prm->out_rows > p->M || prm->out_cols < cols || prm->out_cols > p->N || out_stride < prm->out_cols)
+        return fail(FDR_ERR_ARG, std::string(fn) + ": the output window must lie in [rows .. M] x [cols .. N] and have a stride >= out_cols");
+    const ByteRange o = window_range(out, prm->out_rows, prm->out_cols, out_stride);
+    if (ranges_overlap(window_range(img, rows, cols, stride), o)) return fail(FDR_ERR_ARG, std::string(fn) + ": the output overlaps the input");
+    if (weights && ranges_overlap(window_range(weights, rows, cols, wstride), o))
+        return fail(FDR_ERR_ARG, std::string(fn) + ": the output overlaps the weights");
+    return FDR_OK;
+}
+
+// the new block first (nothing old is let go for it), then the periodic call's workspace for one image and the Laplacian table
+int tvfree_prepare(fdr_plan* p, const char* fn) {
+    int rc = ensure_tvfree_workspace(p, fn);
+    if (rc == FDR_OK) rc = tv_prepare(p, fn);
+    return rc;
+}
+
+// x, b, the duals, q, c / r and rhs (slot 0's raw plane) are full M x N planes; d and the weights are read from the caller's
+// windows by every data step
+int tvfree_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, int cols, int stride, const float* d_w, int wstride, float* d_out,
+                    int out_stride, const fdr_tv_free_params& prm, hipStream_t s) {
+    const int M = p->M, N = p->N, iters = prm.iterations;
+    const float nu = prm.nu > 0.f ? prm.nu : prm.rho;
+    fdr_plan::Slot* ws = &p->slots[0];
+    float *x = p->tv_x, *b = p->tv_b, *c = p->tf_c, *rhs = ws->raw;
+    const float *xc = x, *cc = c, *rhsc = rhs;
+    // T is the periodic call's table for mu = nu: the cache says so, and a periodic call with another mu builds its own again
+    if (iters > 0 && (p->tv_gen != p->op_gen || p->tv_mu != nu || p->tv_rho != prm.rho)) {
+        ScopedPass t(p, s, kPassTfTable);
+        FDR_HIP(launch_tv_table(p->op_h, p->tv_T, p->lap, M, N, p->pstride, p->npanels, (double)nu, (double)prm.rho, s));
+        p->tv_gen = p->op_gen; p->tv_mu = nu; p->tv_rho = prm.rho;
+    }
+    {
+        ScopedPass t(p, s, kPassTfInit);
+        FDR_HIP(launch_tv_init_n(1, &d_img, rows, cols, stride, &x, &p->tv_w[0][0], &p->tv_w[0][1], M, N, s));
+        if (iters > 0) FDR_HIP(hipMemsetAsync(p->tf_q, 0, (size_t)M * N * sizeof(float), s));
+    }
+    int rc = FDR_OK;
+    for (int it = 0; it < iters && rc == FDR_OK; ++it) {
+        float* const* w = p->tv_w[it & 1];
+        float* const* nw = p->tv_w[(it + 1) & 1];
+        rc = blur_window_dev_n(p, &ws, 1, &xc, M, N, N, &c, N, 0, s, M, N);  // c = blur(x)
+        if (rc != FDR_OK) break;
+        {
+            ScopedPass t(p, s, kPassTfData);
+            FDR_HIP(launch_tvfree_data(c, p->tf_q, d_img, stride, d_w, wstride, rows, cols, M, N, prm.mu, nu, s));  // c becomes r
+        }
+        rc = blur_window_dev_n(p, &ws, 1, &cc, M, N, N, &b, N, 1, s, M, N);  // b = blur^T(r)
+        if (rc != FDR_OK) break;
+        {
+            ScopedPass t(p, s, kPassTfSpatial);
+            FDR_HIP(launch_tv_spatial_n(1, x, w[0], w[1], b, nw[0], nw[1], 0, &rhs, M, N, nu, prm.rho, prm.anisotropic, 0, s));
+        }
+        rc = op_rows_fwd_n(p, &ws, 1, &rhsc, M, N, N, s);
+        if (rc == FDR_OK) rc = op_cols_table_n(p, &ws, 1, p->tv_T, kPassTfSolve, s);
+        if (rc == FDR_OK) rc = op_rows_inv_n(p, &ws, 1, ROW_OUT_BLUR, kPassTfX, nullptr, 0, nullptr, &x, N, M, N, s);
+    }
+    if (rc != FDR_OK) return rc;
+    if (prm.norm_area == FDR_NORM_NONE) {
+        ScopedPass t(p, s, kPassTfOut);
+        FDR_HIP(launch_tv_output_n(1, &xc, N, &d_out, prm.out_rows, prm.out_cols, out_stride, prm.nonneg, s));
+        return FDR_OK;
+    }
+    const float* fin = x;
+    if (prm.nonneg) {  // the clamped plane goes to rhs, free by now
+        ScopedPass t(p, s, kPassTfOut);
+        FDR_HIP(launch_tv_output_n(1, &xc, N, &rhs, prm.out_rows, prm.out_cols, N, 1, s));
+        fin = rhs;
+    }
+    return normalize_window(p, fn, kPassTfNorm, fin, N, prm.out_rows, prm.out_cols, prm.norm_area, d_out, out_stride, s);
+}
+
+}  // namespace
+
+namespace fdr {
+
+// The first free-boundary TV call of a plan: q and c / r, two M x N planes in a block of their own.  Nothing is let go for it, so
+// on FDR_ERR_ALLOC the plan is what it was.
+int ensure_tvfree_workspace(fdr_plan* p, const char* fn) {
+    if (p->tf_block) return FDR_OK;
+    const size_t P = (size_t)p->M * p->N;
+    float* blk = nullptr;
+    if (hipMalloc((void**)&blk, 2 * P * sizeof(float)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(FDR_ERR_ALLOC, std::string(fn) + ": hipMalloc of the free-boundary TV workspace failed");
+    }
+    p->tf_block = blk;
+    p->tf_q = blk;
+    p->tf_c = blk + P;
+    return FDR_OK;
+}
+
+}  // namespace fdr
+
+extern "C" {
+
+int fdr_tv_deconv_free_f32_dev(fdr_plan* p, const float* d_img, int rows, int cols, int stride, const float* d_weights, int wstride,
+                               float* d_out, int out_stride, const fdr_tv_free_params* params, void* stream) {
+    const char* fn = "fdr_tv_deconv_free_f32_dev";
+    if (!p || !d_img || !d_out) return null_arg(fn);
+    int rc = tvfree_check(p, fn, d_img, rows, cols, stride, d_weights, wstride, d_out, out_stride, params);
+    if (rc != FDR_OK) return rc;
+    FDR_HIP(hipSetDevice(p->device));
+    rc = tvfree_prepare(p, fn);
+    if (rc != FDR_OK) return rc;
+    return tvfree_dev_impl(p, fn, d_img, rows, cols, stride, d_weights, wstride, d_out, out_stride, *params, (hipStream_t)stream);
+}
+
+int fdr_tv_deconv_free_f32(fdr_plan* p, const float* img_host, int rows, int cols, int stride, const float* weights_host, int wstride,
+                           float* out_host, int out_stride, const fdr_tv_free_params* params) {
+    const char* fn = "fdr_tv_deconv_free_f32";
+    if (!p || !img_host || !out_host) return null_arg(fn);
+    int rc = tvfree_check(p, fn, img_host, rows, cols, stride, weights_host, wstride, out_host, out_stride, params);
+    if (rc != FDR_OK) return rc;
+    FDR_HIP(hipSetDevice(p->device));
+    rc = tvfree_prepare(p, fn);
+    if (rc != FDR_OK) return rc;
+    const fdr_tv_free_params prm = *params;
+    DeviceBuffer d_w;  // the weights, dense, for this call alone: no plane of the workspace is free over the whole iteration
+    if (weights_host) {
+        FDR_ALLOC(d_w, (size_t)rows * cols * sizeof(float), fn);
+        FDR_HIP(hipMemcpy2D(d_w.ptr, (size_t)cols * sizeof(float), weights_host, (size_t)wstride * sizeof(float), (size_t)cols * sizeof(float),
+                            (size_t)rows, hipMemcpyHostToDevice));
+    }
+    return host_image_call(p, fn, img_host, rows, cols, stride, out_host, prm.out_rows, prm.out_cols, out_stride,
+                           [&](const float* d_in, float* d_out) {
+                               return tvfree_dev_impl(p, fn, d_in, rows, cols, cols, weights_host ? d_w.as<float>() : nullptr, cols, d_out,
+                                                      prm.out_cols, prm, nullptr);
+                           });
+}
+
+}  // extern "C"

@@ -133,6 +133,11 @@ struct fdr_plan {
     float *tv_x = nullptr, *tv_b = nullptr, *tv_w[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};  // tv_w[pair][0 = wx, 1 = wy]
     float tv_mu = 0.f, tv_rho = 0.f;
     unsigned tv_gen = 0;
+    // free-boundary TV deconvolution (fdr_tv_deconv_free_f32*): beside the TV workspace for one image, which it shares, one allocation
+    // of two M x N real planes made by the first such call, kept until fdr_plan_destroy: the dual q of the splitting s = blur(x) and
+    // c = blur(x), which the data step turns into r in place.  Its solve table is tv_T with tv_mu = nu.
+    void* tf_block = nullptr;
+    float *tf_q = nullptr, *tf_c = nullptr;
     // motion-blur estimate (fdr_cepstrum_f32*, fdr_estimate_motion_f32*): made by the first such call, kept until fdr_plan_destroy --
     // one allocation holding the M x N complex plane, the pad partials + their sum, the Hann tables (M + N); the score table and the
     // per-angle (cos, sin) table grow on demand.  Host copies of the table and the trig table are kept here too.
@@ -504,6 +509,9 @@ int tv_group_dev(fdr_plan* p, const char* fn, fdr_plan::Slot* const* ws, int n, 
 // one image on slot 0: the group of one
 int tv_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, int cols, int stride, float* d_out, int out_stride,
                 const fdr_tv_params& prm, hipStream_t s);
+// ---- free-boundary TV deconvolution (fdr_api_tvfree.hip) ----
+// the two planes of the free form; FDR_ERR_ALLOC, sticky HIP error cleared, leaves the plan as it was
+int ensure_tvfree_workspace(fdr_plan* p, const char* fn);
 
 // ---- the motion-blur estimate (fdr_api_motion.hip), shared with the defocus and the combined estimate (fdr_api_defocus.hip) ----
 // the search arguments with their defaults (0 selects one), after the plan and window checks; FDR_ERR_ARG for anything outside

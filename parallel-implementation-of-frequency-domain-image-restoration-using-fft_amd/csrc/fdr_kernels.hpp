@@ -242,6 +242,11 @@ hipError_t launch_tv_spatial_n(int nimg, const float* x, const float* wx, const 
                                float* const* rhs, int M, int N, float mu, float rho, int anisotropic, int coupled, hipStream_t s);
 hipError_t launch_tv_output_n(int nimg, const float* const* x, int N, float* const* out, int rows, int cols, int out_stride, int nonneg,
                               hipStream_t s);
+// (fdr_tvfree.hip) the data step of free-boundary TV deconvolution on the rows x cols window of the dense M x N planes c and q (row
+// stride N): e = c + q; s = (mu w d + nu e) / (mu w + nu); q = e - s; c = s - q.  d and w (null: 1) are the caller's windows, read in
+// place with their own strides; nothing outside the window is read or written.
+hipError_t launch_tvfree_data(float* c, float* q, const float* d, int stride, const float* w, int wstride, int rows, int cols, int M, int N, float mu,
+                              float nu, hipStream_t s);
 
 // (fdr_motion.hip) the motion-blur estimate.  window: the Hann tables into hann[rows + cols], w . img on the window and 0 elsewhere
 // into the row-major M x N complex plane, sum |x| partials (motion_pad_partials of them) folded in a fixed order into

@@ -1,0 +1,80 @@
+// fdr_tvfree.hip -- free-boundary, weighted TV deconvolution (fdr_tv_deconv_free_f32*; driver in fdr_api_tvfree.hip), the one
+// kernel the periodic iteration of fdr_tv.hip does not have: the data step of the second splitting s = blur(x),
+//
+//     e = c + q;  s = (mu m pad(d) + nu e) / (mu m + nu);  q = e - s;  r = s - q
+//
+// with c = blur(x) on entry and r in its place on exit.  m is the weights on the window and 0 outside it, where the step is
+// s = e, q = 0, r = c: nothing to compute and nothing to store, so the launch covers the window alone and q, zero outside the
+// window since the start, is never touched there.  d and the weights are read in place from the caller's strided windows.
+#include "fdr_kernels.hpp"
+
+namespace fdr {
+
+// A thread owns four consecutive pixels j .. j + 3 of window row i.  c and q are dense M x N planes (N a multiple of 4, the base
+// 256-byte aligned): 16-byte loads and stores.  d (and w) take one 16-byte load when the group lies inside the window and the
+// window's base and stride keep every row 16-byte aligned (dvec / wvec, decided on the host), scalar loads otherwise.  In the
+// group that straddles column `cols` the pixels beyond it keep the c and q they were loaded with.
+template <bool WEIGHTS>
+__global__ __launch_bounds__(256) void tvfree_data_kernel(float* __restrict__ c, float* __restrict__ q, const float* __restrict__ d, const int stride,
+                                                          const float* __restrict__ w, const int wstride, const int rows, const int cols,
+                                                          const int N, const float mu, const float nu, const int dvec, const int wvec) {
+    const int j = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    const int i = blockIdx.y * blockDim.y + threadIdx.y;
+    if (i >= rows || j >= cols) return;
+    const size_t at = (size_t)i * N + j;
+    const float4 c4 = *reinterpret_cast<const float4*>(c + at), q4 = *reinterpret_cast<const float4*>(q + at);
+    float cc[4] = {c4.x, c4.y, c4.z, c4.w}, qq[4] = {q4.x, q4.y, q4.z, q4.w};
+    float dd[4] = {0.f, 0.f, 0.f, 0.f}, mm[4] = {1.f, 1.f, 1.f, 1.f};
+    const bool whole = j + 3 < cols;
+    const float* dr = d + (size_t)i * stride + j;
+    if (whole && dvec) {
+        const float4 v = *reinterpret_cast<const float4*>(dr);
+        dd[0] = v.x; dd[1] = v.y; dd[2] = v.z; dd[3] = v.w;
+    } else {
+#pragma unroll
+        for (int l = 0; l < 4; ++l)
+            if (j + l < cols) dd[l] = dr[l];
+    }
+    if (WEIGHTS) {
+        const float* wr = w + (size_t)i * wstride + j;
+        if (whole && wvec) {
+            const float4 v = *reinterpret_cast<const float4*>(wr);
+            mm[0] = v.x; mm[1] = v.y; mm[2] = v.z; mm[3] = v.w;
+        } else {
+#pragma unroll
+            for (int l = 0; l < 4; ++l)
+                if (j + l < cols) mm[l] = wr[l];
+        }
+    }
+#pragma unroll
+    for (int l = 0; l < 4; ++l) {
+        if (j + l < cols) {
+            const float e = cc[l] + qq[l];
+            const float a = mu * mm[l];
+            const float s = (a * dd[l] + nu * e) / (a + nu);
+            qq[l] = e - s;
+            cc[l] = s - qq[l];
+        }
+    }
+    *reinterpret_cast<float4*>(q + at) = make_float4(qq[0], qq[1], qq[2], qq[3]);
+    *reinterpret_cast<float4*>(c + at) = make_float4(cc[0], cc[1], cc[2], cc[3]);
+}
+
+// rows x cols must lie within the M x N planes c and q (N a multiple of 4); d and w (null: weights of 1) are rows x cols windows
+// with their own strides, of any alignment
+hipError_t launch_tvfree_data(float* c, float* q, const float* d, int stride, const float* w, int wstride, int rows, int cols, int M, int N, float mu,
+                              float nu, hipStream_t s) {
+    if (!c || !q || !d || rows < 1 || cols < 1 || rows > M || cols > N || (N & 3) || stride < cols || (w && wstride < cols)) return hipErrorInvalidValue;
+    const int groups = (cols + 3) / 4;
+    const int tx = groups <= 64 ? 64 : groups <= 128 ? 128 : 256, ty = 256 / tx;
+    const dim3 grid((unsigned)((groups + tx - 1) / tx), (unsigned)((rows + ty - 1) / ty));
+    const int dvec = ((uintptr_t)d & 15) == 0 && (stride & 3) == 0;
+    const int wvec = w && ((uintptr_t)w & 15) == 0 && (wstride & 3) == 0;
+    if (w)
+        hipLaunchKernelGGL((tvfree_data_kernel<true>), grid, dim3(tx, ty), 0, s, c, q, d, stride, w, wstride, rows, cols, N, mu, nu, dvec, wvec);
+    else
+        hipLaunchKernelGGL((tvfree_data_kernel<false>), grid, dim3(tx, ty), 0, s, c, q, d, stride, w, wstride, rows, cols, N, mu, nu, dvec, wvec);
+    return hipGetLastError();
+}
+
+}  // namespace fdr

@@ -1,5 +1,6 @@
 // gpu.cpp -- ./gpu <img-path> <psf-length> <psf-angle> | auto auto [--any-blur] | defocus <radius|auto> | blind <size>  [--out file] [--mode fast|parity] [--norm padded|cropped] [--host-epilogue]
-//           [--cls gamma|auto] [--k K|auto] [--reg gcv|discrepancy] [--sigma s] [--pad zero|smooth] [--rl iterations|auto [--accel] [--rl-tv lambda [--rl-tv-eps e]] [--free-boundary [--mask mask.png]] [--rl-max n] [--rl-stop residual|kl] [--gain g] [--rl-check c]] [--tv mu [--tv-iters n] [--tv-rho r] [--tv-color]]
+//           [--cls gamma|auto] [--k K|auto] [--reg gcv|discrepancy] [--sigma s] [--pad zero|smooth] [--rl iterations|auto [--accel] [--rl-tv lambda [--rl-tv-eps e]] [--free-boundary [--mask mask.png]] [--rl-max n] [--rl-stop residual|kl] [--gain g] [--rl-check c]] [--tv mu [--tv-iters n] [--tv-rho r] [--tv-color | --free-boundary [--mask mask.png]]]
+// `--tv mu --free-boundary`: the TV leg is fft_gpu::tvDeblurFree_RGB (the picture is a crop of a larger scene; --mask as for --rl); --tv-color has no such form.
 // `auto auto` for length and angle: the blur is estimated first (fft_gpu::estimateMotionBlur on the per-pixel mean of B, G and R),
 // printed as `estimate: length L angle A confidence C`, and the run then goes on exactly as `./gpu <img-path> L A` would.
 // `--cls auto` (gamma, with K = 0) or `--k auto` (K, with gamma = 0): the weight is chosen first (fft_gpu::chooseRegularisation on the same
@@ -189,8 +190,8 @@ int main(int argc, char** argv) {
     if (rl_iterations >= 0 && (cls || verify || parity || pad_smooth)) { cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle>\n"; return -1; }
     // --verify compares against the zero-padded serial leg
     if (pad_smooth && verify) { cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle>\n"; return -1; }
-    // --free-boundary and --accel belong to --rl, --mask to --free-boundary
-    if ((free_boundary && rl_iterations < 0) || (accel && rl_iterations < 0) || (!mask_path.empty() && !free_boundary)) {
+    // --free-boundary belongs to --rl or --tv, --accel to --rl, --mask to --free-boundary
+    if ((free_boundary && rl_iterations < 0 && !(tv_mu > 0.f)) || (accel && rl_iterations < 0) || (!mask_path.empty() && !free_boundary)) {
         cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle>\n";
         return -1;
     }
@@ -222,6 +223,11 @@ int main(int argc, char** argv) {
     const bool tv = tv_mu > 0.f;
     if ((tv && (cls || verify || parity || pad_smooth || rl_iterations >= 0 || tv_iterations < 0 || !(tv_rho > 0.f))) || (!tv && (tv_opts || tv_mu != -1.f))) {
         cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle>\n";
+        return -1;
+    }
+    // the free-boundary TV leg runs the channels one after the other: it has no vectorial form
+    if (tv && free_boundary && tv_color) {
+        cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle> --tv <mu> --free-boundary [--mask m.png] [--tv-iters n] [--tv-rho r] (no --tv-color)\n";
         return -1;
     }
 
@@ -411,9 +417,10 @@ int main(int argc, char** argv) {
     if (tv) {  // total-variation deconvolution on the same channels: its planes become the written result
         vector<Mat> tvc = input;
         t_start = high_resolution_clock::now();
-        fft_gpu::tvDeblur_RGB(tvc, psf, tv_mu, tv_iterations, tv_rho, tv_color);
+        if (free_boundary) fft_gpu::tvDeblurFree_RGB(tvc, psf, tv_mu, tv_iterations, tv_rho, weights);
+        else fft_gpu::tvDeblur_RGB(tvc, psf, tv_mu, tv_iterations, tv_rho, tv_color);
         t_end = high_resolution_clock::now();
-        cout << "Deblurring 3 channels took(gpu[total-variation mu " << tv_mu << " rho " << tv_rho << " n " << tv_iterations
+        cout << "Deblurring 3 channels took(gpu[total-variation " << (free_boundary ? "free-boundary " : "") << "mu " << tv_mu << " rho " << tv_rho << " n " << tv_iterations
              << (tv_color ? " colour" : "") << "]): " << getElapsedMs(t_start, t_end) << " ms\n";
         channels = tvc;
     }
