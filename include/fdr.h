@@ -716,6 +716,63 @@ int fdr_tv_deconv_free_f32(fdr_plan* plan, const float* img_host, int rows, int 
 int fdr_tv_deconv_free_f32_dev(fdr_plan* plan, const float* d_img, int rows, int cols, int stride, const float* d_weights, int wstride,
                                float* d_out, int out_stride, const fdr_tv_free_params* params, void* stream);
 
+/* -- noise-constrained TV deconvolution: fdr_tv_deconv_free_f32 with mu chosen from the noise level.  The
+ *    caller states the noise standard deviation sigma of the picture instead of the weight mu (sigma = 0: it is estimated from the
+ *    window as fdr_noise_sigma_f32 does; the weights are not looked at), and the call solves the constrained problem
+ *        minimise over x (M x N):  TV(x)   subject to   sum m (blur(x) - pad(d))^2 <= c2 = tau sigma^2 S,   S = sum m
+ *    (m as above: the weights on the window, 0 elsewhere; tau = 0 selects 1) by ADMM on the splittings of the free call, the
+ *    weighted data step replaced by a projection of s onto the discrepancy ball (Afonso, Bioucas-Dias & Figueiredo 2011, C-SALSA;
+ *    Wen & Chan 2012).  Every iteration k is that of fdr_tv_deconv_free_f32 with its own weight mu_k:
+ *            c = blur(x)
+ *            res_e = sum m (c + q - pad(d))^2;  res_c = sum m (c - pad(d))^2;  S = sum m         over the window, in double
+ *            g = 0 for res_e <= c2;  FDR_TV_AUTO_MAX_RATIO for c2 = 0 or a quotient that is not finite;
+ *                else min(sqrt(res_e / c2) - 1, FDR_TV_AUTO_MAX_RATIO);   mu_k = float(nu g)
+ *            e = c + q;  s = (mu_k m pad(d) + nu e) / (mu_k m + nu);  q = e - s;  r = s - q;  ... the rest unchanged
+ *    For weights of 0 and 1 this s is the exact projection of e onto the ball, the iteration is ADMM for the constrained problem
+ *    and mu_k converges to its Lagrange multiplier: the mu of the fdr_tv_deconv_free_f32 call with the same minimiser.  For
+ *    fractional weights it is an approximation of the projection and the discrepancy settles above the target (1.35 times after 300
+ *    steps on the quality scene of the tests).  nu = 0 selects FDR_TV_AUTO_NU_RATIO rho: the projection needs nu well above rho
+ *    to converge in about a hundred steps; out_rows x out_cols, nonneg and norm_area as in the free call;
+ *    n = 0 returns pad(d).
+ *    trace (3 n doubles, optional): trace[3 k .. 3 k + 2] = (res_c, res_e, mu_k) of iteration k.  The host form fills `result`
+ *    (optional) from the last iteration; with n = 0 nothing is measured or estimated: sigma is the one given and target, mu,
+ *    discrepancy and S are 0.
+ *    Plans and refusals as fdr_tv_deconv_free_f32*, and FDR_ERR_ARG for sigma or tau negative or not finite, a window below 3 x 3
+ *    when sigma is to be estimated, and (_dev) a d_trace range of 3 n doubles that overlaps the input, the weights or the output.
+ *    Every refusal comes before any device work and leaves the plan usable.
+ *    The first call on a plan allocates, beside the workspaces of fdr_tv_deconv_free_f32, one small block (the partials of the
+ *    sums, mu_k, the last sums), kept until fdr_plan_destroy; FDR_ERR_ALLOC, plan intact, if it cannot be had.  After it the _dev
+ *    form allocates nothing and, with sigma > 0, reads nothing back and is asynchronous on `stream`; with sigma = 0 it waits
+ *    for `stream` once, before the first iteration, to read the noise sum back (as fdr_richardson_lucy_auto_f32_dev does for its
+ *    residual rule).  The solve table is the shared one, built for nu.  An iteration adds one more streaming pass over the window
+ *    (12 bytes per pixel, 16 with weights) and a single-workgroup fold to the free call's.  Results and traces repeat bit for bit from
+ *    call to call (no atomics; every sum runs in a fixed order that does not depend on the alignment of the windows).            */
+#define FDR_TV_AUTO_MAX_RATIO 1e6 /* the clamp of sqrt(res_e / c2) - 1 */
+#define FDR_TV_AUTO_NU_RATIO 25.f /* nu = 0 selects this times rho */
+typedef struct fdr_tv_auto_params {
+    float sigma;     /* noise standard deviation of the picture, >= 0; 0 = fdr_noise_sigma of the window */
+    float tau;       /* the ball is tau sigma^2 S, >= 0; 0 selects 1 */
+    float rho;       /* ADMM penalty of z = D x, > 0 */
+    float nu;        /* ADMM penalty of s = blur(x), >= 0; 0 selects FDR_TV_AUTO_NU_RATIO rho */
+    int iterations;  /* >= 0 */
+    int anisotropic; /* 0: isotropic TV, else anisotropic */
+    int nonneg;      /* != 0: the output is max(x, 0) */
+    int norm_area;   /* FDR_NORM_NONE / FDR_NORM_CROPPED / FDR_NORM_PADDED, over the output window */
+    int out_rows;    /* rows .. M */
+    int out_cols;    /* cols .. N */
+} fdr_tv_auto_params;
+typedef struct fdr_tv_auto_result {
+    double sigma;       /* the noise level used: given or estimated */
+    double target;      /* c2 = tau sigma^2 S */
+    double mu;          /* mu_k of the last iteration: the mu of the equivalent fdr_tv_deconv_free_f32 call */
+    double discrepancy; /* res_c of the last iteration, to compare with target */
+    double S;           /* sum m: rows cols without weights */
+} fdr_tv_auto_result;
+int fdr_tv_deconv_auto_f32(fdr_plan* plan, const float* img_host, int rows, int cols, int stride, const float* weights_host, int wstride,
+                           float* out_host, int out_stride, const fdr_tv_auto_params* params, fdr_tv_auto_result* result, double* trace_host);
+int fdr_tv_deconv_auto_f32_dev(fdr_plan* plan, const float* d_img, int rows, int cols, int stride, const float* d_weights, int wstride,
+                               float* d_out, int out_stride, const fdr_tv_auto_params* params, double* d_trace, void* stream);
+
 /* -- the motion-blur estimate: the length and angle of a uniform linear motion blur, from the blurred
  *    picture alone, by the power cepstrum.  The blur puts sinc zeros into |G| in stripes across the motion direction; in the
  *    cepstrum they show as a negative peak at distance L along it.  The plan is M x N, the image window rows x cols (row stride

@@ -518,6 +518,44 @@ inline void tvDeblurFree_RGB(std::vector<Mat>& channels, const Mat& psf, float m
 inline void tvDeblurFree_RGB(std::vector<Mat>& channels, const Mat& psf, float mu, int iterations = 50, float rho = 2.0f, const Mat& weights = Mat()) {
     tvDeblurFree_RGB(channels, psf, mu, iterations, rho, weights, defaults());
 }
+// Noise-constrained total-variation deconvolution (fdr_tv_deconv_auto_f32, include/fdr.h) of every channel, in place: tvDeblurFree_RGB
+// without mu.  The caller states the noise standard deviation sigma of the channels (0: estimated per channel, fdr_noise_sigma_f32)
+// and tau (0: 1); every step takes its weight from the discrepancy ball tau sigma^2 sum(weights).  The plan, operator PSF and
+// `weights` of tvDeblurFree_RGB, `iterations` ADMM steps (isotropic, penalties rho and nu = FDR_TV_AUTO_NU_RATIO rho), the output
+// clamped at 0 and normalised by o.norm_area, one channel after the other.  Returns the channels' results (sigma, target, mu,
+// discrepancy, S), in order.
+inline std::vector<fdr_tv_auto_result> tvDeblurAuto_RGB(std::vector<Mat>& channels, const Mat& psf, float sigma, int iterations, float rho, float tau,
+                                                        const Mat& weights, const Options& o) {
+    std::vector<fdr_tv_auto_result> results;
+    if (channels.empty()) return results;
+    const int rows = channels[0].rows, cols = channels[0].cols;
+    if (!weights.empty() && (weights.rows != rows || weights.cols != cols || weights.type() != CV_32F)) {
+        std::cerr << "tvDeblurAuto_RGB: the weights must be CV_32F and have the picture's size\n";
+        exit(1);
+    }
+    bool created = false;
+    PlanCacheSettle settle_;
+    fdr_plan* plan = plan_cache().get(o.device, std::max(8, nextPowerOfTwo(rows + psf.rows - 1)), std::max(32, nextPowerOfTwo(cols + psf.cols - 1)),
+                                      FDR_MODE_FAST, &created);
+    Mat psfc = psf.isContinuous() ? psf : psf.clone();
+    FDR_CHECK(fdr_set_operator_psf(plan, psfc.ptr<float>(0), psf.rows, psf.cols, psf.cols));
+    Mat w = weights.empty() || weights.isContinuous() ? weights : weights.clone();
+    for (Mat& c : channels) {
+        Mat src = c.isContinuous() ? c : c.clone();
+        Mat out(c.rows, c.cols, CV_32F);
+        const fdr_tv_auto_params prm = {sigma, tau, rho, 0.f, iterations, 0, 1, o.norm_area, c.rows, c.cols};
+        fdr_tv_auto_result res = {};
+        FDR_CHECK(fdr_tv_deconv_auto_f32(plan, src.ptr<float>(0), c.rows, c.cols, c.cols, w.empty() ? nullptr : w.ptr<float>(0), cols,
+                                         out.ptr<float>(0), c.cols, &prm, &res, nullptr));
+        results.push_back(res);
+        c = out;
+    }
+    return results;
+}
+inline std::vector<fdr_tv_auto_result> tvDeblurAuto_RGB(std::vector<Mat>& channels, const Mat& psf, float sigma = 0.f, int iterations = 100,
+                                                        float rho = 2.0f, float tau = 0.f, const Mat& weights = Mat()) {
+    return tvDeblurAuto_RGB(channels, psf, sigma, iterations, rho, tau, weights, defaults());
+}
 // The motion blur of a one-channel picture of unknown blur (fdr_estimate_motion_f32, include/fdr.h): length and angle in the
 // convention of motionBlurKernel, the table minimum and the confidence (below about 10: no clear blur).  Its own FDR_MODE_FAST plan
 // (each dimension padded to fdr_optimal_dft_size, at least 32; FDR_FLAG_MIXED_RADIX), made and freed inside the call.  0 selects an

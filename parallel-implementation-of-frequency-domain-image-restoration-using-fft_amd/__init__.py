@@ -94,6 +94,26 @@ class TvFreeParams(ctypes.Structure):
                 ("out_cols", ctypes.c_int)]
 
 
+class TvAutoParams(ctypes.Structure):
+    """fdr_tv_auto_params of include/fdr.h"""
+    _fields_ = [("sigma", ctypes.c_float), ("tau", ctypes.c_float), ("rho", ctypes.c_float), ("nu", ctypes.c_float),
+                ("iterations", ctypes.c_int), ("anisotropic", ctypes.c_int), ("nonneg", ctypes.c_int), ("norm_area", ctypes.c_int),
+                ("out_rows", ctypes.c_int), ("out_cols", ctypes.c_int)]
+
+
+class TvAutoResultC(ctypes.Structure):
+    """fdr_tv_auto_result of include/fdr.h"""
+    _fields_ = [("sigma", ctypes.c_double), ("target", ctypes.c_double), ("mu", ctypes.c_double), ("discrepancy", ctypes.c_double),
+                ("S", ctypes.c_double)]
+
+
+# the result of Plan.tv_deconv_auto / tvDeblurAuto_myfft beside the image: the noise level used, the target tau sigma^2 S, the last
+# mu_k (the mu of the equivalent tv_deconv_free call), the last discrepancy sum m (blur(x) - d)^2 and S = sum m
+TvAutoResult = collections.namedtuple("TvAutoResult", "sigma target mu discrepancy S")
+TV_AUTO_MAX_RATIO = 1e6
+TV_AUTO_NU_RATIO = 25.0
+
+
 class RlFreeParams(ctypes.Structure):
     """fdr_rlfree_params of include/fdr.h"""
     _fields_ = [("iterations", ctypes.c_int), ("sigma", ctypes.c_float), ("norm_area", ctypes.c_int), ("out_rows", ctypes.c_int),
@@ -295,6 +315,8 @@ def _signatures():
         "fdr_tv_deconv_batch_f32_dev": (ci, [vp, vp, sz, ci, ci, ci, ci, vp, sz, ci, P(TvBatchParams), vp]),
         "fdr_tv_deconv_free_f32": (ci, [vp, vp, ci, ci, ci, vp, ci, vp, ci, P(TvFreeParams)]),
         "fdr_tv_deconv_free_f32_dev": (ci, [vp, vp, ci, ci, ci, vp, ci, vp, ci, P(TvFreeParams), vp]),
+        "fdr_tv_deconv_auto_f32": (ci, [vp, vp, ci, ci, ci, vp, ci, vp, ci, P(TvAutoParams), P(TvAutoResultC), vp]),
+        "fdr_tv_deconv_auto_f32_dev": (ci, [vp, vp, ci, ci, ci, vp, ci, vp, ci, P(TvAutoParams), vp, vp]),
         "fdr_cepstrum_f32": (ci, [vp, vp, ci, ci, ci, vp]),
         "fdr_cepstrum_f32_dev": (ci, [vp, vp, ci, ci, ci, vp, vp]),
         "fdr_estimate_motion_f32": (ci, [vp, vp, ci, ci, ci, ci, ci, cd, P(MotionEstimateC), vp]),
@@ -895,6 +917,42 @@ class Plan:
                                               ctypes.c_void_p(int(d_weights)) if d_weights else None, int(wstride),
                                               ctypes.c_void_p(int(d_out)), out_stride, ctypes.byref(prm), _stream(stream)))
 
+    # noise-constrained TV deconvolution (include/fdr.h): the free-boundary call with mu chosen from the noise level
+    def tv_deconv_auto(self, img, sigma=0.0, rho=2.0, iterations=100, weights=None, tau=0.0, nu=0.0, anisotropic=False, nonneg=False,
+                       norm_area=NORM_NONE, full_plane=False):
+        """tv_deconv_free without mu: minimises TV(x) subject to sum m (blur(x) - img)^2 <= tau sigma^2 sum m, sigma the noise standard
+        deviation of img (0: estimated from img as noise_sigma does), tau = 0 selecting 1 and nu = 0 selecting TV_AUTO_NU_RATIO rho.
+        Returns (image, TvAutoResult, trace): trace[k] = (res_c, res_e, mu_k) of iteration k (fdr_tv_deconv_auto_f32)."""
+        img = np.ascontiguousarray(img, dtype=np.float32)
+        rows, cols = img.shape
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float32)
+            if w.shape != img.shape:
+                raise ValueError("weights must have the shape of img")
+        orows, ocols = (self.M, self.N) if full_plane else (rows, cols)
+        out = np.empty((orows, ocols), dtype=np.float32)
+        trace = np.zeros((max(int(iterations), 0), 3), dtype=np.float64)
+        prm = TvAutoParams(float(sigma), float(tau), float(rho), float(nu), int(iterations), int(bool(anisotropic)), int(bool(nonneg)),
+                           int(norm_area), orows, ocols)
+        res = TvAutoResultC()
+        _check(lib.fdr_tv_deconv_auto_f32(self._h, _ptr(img), rows, cols, cols, _ptr(w) if w is not None else None, cols, _ptr(out), ocols,
+                                          ctypes.byref(prm), ctypes.byref(res), _ptr(trace) if trace.size else None))
+        return out, TvAutoResult(res.sigma, res.target, res.mu, res.discrepancy, res.S), trace
+
+    def tv_deconv_auto_dev(self, d_img, rows, cols, stride, d_out, out_stride, sigma=0.0, rho=2.0, iterations=100, d_weights=None, wstride=0,
+                           tau=0.0, nu=0.0, anisotropic=False, nonneg=False, norm_area=NORM_NONE, out_rows=None, out_cols=None, d_trace=None,
+                           stream=None):
+        """the same on device pointers; out_rows x out_cols (default rows x cols, up to M x N) is the output window, d_trace room for
+        3 * iterations doubles or None.  Asynchronous with sigma > 0; with sigma = 0 the stream is waited for once, before the first
+        iteration, for the noise estimate."""
+        prm = TvAutoParams(float(sigma), float(tau), float(rho), float(nu), int(iterations), int(bool(anisotropic)), int(bool(nonneg)),
+                           int(norm_area), int(rows if out_rows is None else out_rows), int(cols if out_cols is None else out_cols))
+        _check(lib.fdr_tv_deconv_auto_f32_dev(self._h, ctypes.c_void_p(int(d_img)), rows, cols, stride,
+                                              ctypes.c_void_p(int(d_weights)) if d_weights else None, int(wstride),
+                                              ctypes.c_void_p(int(d_out)), out_stride, ctypes.byref(prm),
+                                              ctypes.c_void_p(int(d_trace)) if d_trace else None, _stream(stream)))
+
     def tv_deconv_batch_dev(self, d_imgs, img_pitch, count, rows, cols, stride, d_out, out_pitch, out_stride, mu, rho=2.0, iterations=50,
                             anisotropic=False, nonneg=False, norm_area=NORM_NONE, coupled=False, stream=None):
         """fdr_tv_deconv_batch_f32_dev: tv_deconv_dev on `count` windows, image i at d_imgs + i img_pitch / d_out + i out_pitch
@@ -1346,6 +1404,39 @@ def tvDeblurFree_RGB(channels, psf, mu, rho=2.0, iterations=50, nonneg=False, de
         p.set_operator_psf(psf)
         for i in range(len(channels)):
             channels[i] = p.tv_deconv_free(channels[i], mu, rho, iterations, weights, nu, False, nonneg, norm_area)
+
+
+def tvDeblurAuto_myfft(img, psf, sigma=0.0, rho=2.0, iterations=100, weights=None, tau=0.0, nu=0.0, anisotropic=False, nonneg=False, device=0,
+                       norm_area=NORM_NONE, full_plane=False):
+    """Noise-constrained total-variation deconvolution of one channel that is a crop of a larger scene: tvDeblurFree_myfft with the
+    noise level sigma (0: estimated from img) in the place of mu, on the same plan.  Returns (image, TvAutoResult, trace) as
+    Plan.tv_deconv_auto."""
+    img = np.asarray(img, dtype=np.float32)
+    psf = np.asarray(psf, dtype=np.float32)
+    M, N = _rlfree_plan_size(img.shape[0], img.shape[1], psf.shape[0], psf.shape[1])
+    with Plan(M, N, MODE_FAST, device) as p:
+        p.set_operator_psf(psf)
+        return p.tv_deconv_auto(img, sigma, rho, iterations, weights, tau, nu, anisotropic, nonneg, norm_area, full_plane)
+
+
+def tvDeblurAuto_RGB(channels, psf, sigma=0.0, rho=2.0, iterations=100, nonneg=False, device=0, norm_area=NORM_NONE, weights=None, tau=0.0,
+                     nu=0.0):
+    """fft_gpu::tvDeblurAuto_RGB: replaces every element of `channels` (float32 planes of one size) in place with its noise-constrained
+    total-variation estimate, from one plan (that of tvDeblurAuto_myfft) and one weights plane for all channels, one channel after the
+    other, sigma given or (0) estimated per channel -- the bits of tvDeblurAuto_myfft per channel.  Returns the TvAutoResult of
+    every channel."""
+    results = []
+    if not channels:
+        return results
+    psf = np.asarray(psf, dtype=np.float32)
+    r, c = np.asarray(channels[0]).shape
+    M, N = _rlfree_plan_size(r, c, psf.shape[0], psf.shape[1])
+    with Plan(M, N, MODE_FAST, device) as p:
+        p.set_operator_psf(psf)
+        for i in range(len(channels)):
+            channels[i], res, _ = p.tv_deconv_auto(channels[i], sigma, rho, iterations, weights, tau, nu, False, nonneg, norm_area)
+            results.append(res)
+    return results
 
 
 def _motion_plan_size(rows, cols):

@@ -14,11 +14,17 @@ namespace {
 const char* const kPassTfTable = "TV table: 1/(nu|H|^2+rho L)/MN (free)";
 const char* const kPassTfInit = "TVF init: x = pad(d), w = q = 0";
 const char* const kPassTfData = "TVF data: s, q, r = 2s-e (window)";
+const char* const kPassTaNorm = "TVA norm+mu: res_e, res_c, S -> mu_k";
+const char* const kPassTaData = "TVA data: s, q, r = 2s-e (mu_k)";
 const char* const kPassTfSpatial = "TV spatial: shrink+dual+div (free)";
 const char* const kPassTfSolve = "B' op cols: FFT*T*IFFT (TVF solve)";
 const char* const kPassTfX = "C op rows: IFFT (TVF x)";
 const char* const kPassTfOut = "TVF out: crop+clamp";
 const char* const kPassTfNorm = "E TVF minmax+normalize";
+
+}  // namespace
+
+namespace fdr {
 
 // everything a free-boundary TV call refuses, before any device work: what the periodic call refuses, and nu, the weights' stride,
 // the output window and an output that overlaps the input or the weights (both are read in every iteration)
@@ -49,7 +55,7 @@ int tvfree_prepare(fdr_plan* p, const char* fn) {
 // x, b, the duals, q, c / r and rhs (slot 0's raw plane) are full M x N planes; d and the weights are read from the caller's
 // windows by every data step
 int tvfree_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, int cols, int stride, const float* d_w, int wstride, float* d_out,
-                    int out_stride, const fdr_tv_free_params& prm, hipStream_t s) {
+                    int out_stride, const fdr_tv_free_params& prm, hipStream_t s, const TvAuto* au) {
     const int M = p->M, N = p->N, iters = prm.iterations;
     const float nu = prm.nu > 0.f ? prm.nu : prm.rho;
     fdr_plan::Slot* ws = &p->slots[0];
@@ -72,7 +78,16 @@ int tvfree_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, i
         float* const* nw = p->tv_w[(it + 1) & 1];
         rc = blur_window_dev_n(p, &ws, 1, &xc, M, N, N, &c, N, 0, s, M, N);  // c = blur(x)
         if (rc != FDR_OK) break;
-        {
+        if (au) {  // the weight of this step from the discrepancy of e = c + q, then the step with it
+            {
+                ScopedPass t(p, s, kPassTaNorm);
+                FDR_HIP(launch_tvauto_norm(c, p->tf_q, d_img, stride, d_w, wstride, rows, cols, M, N, p->ta_part, s));
+                FDR_HIP(launch_tvauto_mu(p->ta_part, tvauto_partials(rows, cols), au->sigma, au->tau, nu, p->ta_mu, p->ta_stat,
+                                         au->trace ? au->trace + 3 * (size_t)it : nullptr, s));
+            }
+            ScopedPass t(p, s, kPassTaData);
+            FDR_HIP(launch_tvauto_data(c, p->tf_q, d_img, stride, d_w, wstride, rows, cols, M, N, p->ta_mu, nu, s));  // c becomes r
+        } else {
             ScopedPass t(p, s, kPassTfData);
             FDR_HIP(launch_tvfree_data(c, p->tf_q, d_img, stride, d_w, wstride, rows, cols, M, N, prm.mu, nu, s));  // c becomes r
         }
@@ -100,10 +115,6 @@ int tvfree_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, i
     }
     return normalize_window(p, fn, kPassTfNorm, fin, N, prm.out_rows, prm.out_cols, prm.norm_area, d_out, out_stride, s);
 }
-
-}  // namespace
-
-namespace fdr {
 
 // The first free-boundary TV call of a plan: q and c / r, two M x N planes in a block of their own.  Nothing is let go for it, so
 // on FDR_ERR_ALLOC the plan is what it was.

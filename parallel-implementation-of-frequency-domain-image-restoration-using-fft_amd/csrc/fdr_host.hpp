@@ -138,6 +138,14 @@ struct fdr_plan {
     // c = blur(x), which the data step turns into r in place.  Its solve table is tv_T with tv_mu = nu.
     void* tf_block = nullptr;
     float *tf_q = nullptr, *tf_c = nullptr;
+    // noise-constrained TV deconvolution (fdr_tv_deconv_auto_f32*): beside the workspaces of the free form, which it shares, one small
+    // allocation made by the first such call, kept until fdr_plan_destroy: the 3 tvauto_max_partials(M, N) double partials of the
+    // norm kernel, the (res_c, res_e, mu_k, S) of the last step, the partials of the noise estimate and the device scalar mu_k
+    void* ta_block = nullptr;
+    double* ta_part = nullptr;
+    double* ta_stat = nullptr;   // 4 doubles
+    double* ta_noise = nullptr;  // kRegMaxPartials + 1 doubles
+    float* ta_mu = nullptr;
     // motion-blur estimate (fdr_cepstrum_f32*, fdr_estimate_motion_f32*): made by the first such call, kept until fdr_plan_destroy --
     // one allocation holding the M x N complex plane, the pad partials + their sum, the Hann tables (M + N); the score table and the
     // per-angle (cos, sin) table grow on demand.  Host copies of the table and the trig table are kept here too.
@@ -512,6 +520,19 @@ int tv_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, int c
 // ---- free-boundary TV deconvolution (fdr_api_tvfree.hip) ----
 // the two planes of the free form; FDR_ERR_ALLOC, sticky HIP error cleared, leaves the plan as it was
 int ensure_tvfree_workspace(fdr_plan* p, const char* fn);
+// everything a free-boundary TV call refuses, before any device work; the workspaces of a call (the two planes first, then the
+// periodic call's for one image and the Laplacian table)
+int tvfree_check(const fdr_plan* p, const char* fn, const float* img, int rows, int cols, int stride, const float* weights, int wstride,
+                 const float* out, int out_stride, const fdr_tv_free_params* prm);
+int tvfree_prepare(fdr_plan* p, const char* fn);
+// what the noise-constrained call (fdr_api_tvauto.hip) adds to an iteration: the noise level and tau of the discrepancy ball, and
+// where the device writes the trace (3 doubles per iteration; null: none).  The partials, mu_k and the last step's sums are the plan's.
+struct TvAuto { double sigma, tau; double* trace; };
+// the iteration on checked arguments with the workspaces made: x, b, the duals, q, c / r and rhs (slot 0's raw plane) are full M x N
+// planes; d and the weights are read from the caller's windows by every data step.  With `au` the data step takes its weight from
+// the norm and mu launches before it (prm.mu is not used) and the ta_ block must exist.
+int tvfree_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, int cols, int stride, const float* d_w, int wstride, float* d_out,
+                    int out_stride, const fdr_tv_free_params& prm, hipStream_t s, const TvAuto* au = nullptr);
 
 // ---- the motion-blur estimate (fdr_api_motion.hip), shared with the defocus and the combined estimate (fdr_api_defocus.hip) ----
 // the search arguments with their defaults (0 selects one), after the plan and window checks; FDR_ERR_ARG for anything outside

@@ -247,6 +247,19 @@ hipError_t launch_tv_output_n(int nimg, const float* const* x, int N, float* con
 // place with their own strides; nothing outside the window is read or written.
 hipError_t launch_tvfree_data(float* c, float* q, const float* d, int stride, const float* w, int wstride, int rows, int cols, int M, int N, float mu,
                               float nu, hipStream_t s);
+// (fdr_tvauto.hip) noise-constrained TV deconvolution, on the same window, planes and caller's windows.  norm: res_e = sum w (c + q -
+// d)^2, res_c = sum w (c - d)^2 and S = sum w in double as tvauto_partials(rows, cols) per-workgroup partials each (part holds 3 n
+// doubles; no window of an M x N plan needs more than tvauto_max_partials(M, N)).  mu: one workgroup folds the partials in index
+// order; with c2 = tau sigma^2 S, g = 0 for res_e <= c2, 1e6 for c2 = 0 or a quotient that is not finite, else min(sqrt(res_e / c2)
+// - 1, 1e6); *mu = float(nu g), stat[0 .. 3] = (res_c, res_e, mu, S) and, when not null, trace[0 .. 2] = (res_c, res_e, mu).
+// data: launch_tvfree_data's step with mu read from the device.
+int tvauto_partials(int rows, int cols);
+int tvauto_max_partials(int M, int N);
+hipError_t launch_tvauto_norm(const float* c, const float* q, const float* d, int stride, const float* w, int wstride, int rows, int cols, int M, int N,
+                              double* part, hipStream_t s);
+hipError_t launch_tvauto_mu(const double* part, int n, double sigma, double tau, float nu, float* mu, double* stat, double* trace, hipStream_t s);
+hipError_t launch_tvauto_data(float* c, float* q, const float* d, int stride, const float* w, int wstride, int rows, int cols, int M, int N,
+                              const float* mu, float nu, hipStream_t s);
 
 // (fdr_motion.hip) the motion-blur estimate.  window: the Hann tables into hann[rows + cols], w . img on the window and 0 elsewhere
 // into the row-major M x N complex plane, sum |x| partials (motion_pad_partials of them) folded in a fixed order into

@@ -1,6 +1,10 @@
 // gpu.cpp -- ./gpu <img-path> <psf-length> <psf-angle> | auto auto [--any-blur] | defocus <radius|auto> | blind <size>  [--out file] [--mode fast|parity] [--norm padded|cropped] [--host-epilogue]
 //           [--cls gamma|auto] [--k K|auto] [--reg gcv|discrepancy] [--sigma s] [--pad zero|smooth] [--rl iterations|auto [--accel] [--rl-tv lambda [--rl-tv-eps e]] [--free-boundary [--mask mask.png]] [--rl-max n] [--rl-stop residual|kl] [--gain g] [--rl-check c]] [--tv mu [--tv-iters n] [--tv-rho r] [--tv-color | --free-boundary [--mask mask.png]]]
 // `--tv mu --free-boundary`: the TV leg is fft_gpu::tvDeblurFree_RGB (the picture is a crop of a larger scene; --mask as for --rl); --tv-color has no such form.
+// `--tv auto [--sigma s] [--tv-tau t] [--tv-iters n] [--tv-rho r] [--mask mask.png]`: the TV leg is fft_gpu::tvDeblurAuto_RGB -- the free-boundary
+// iteration with mu chosen in every step from the noise level (--sigma, else estimated per channel; the ball is t sigma^2 S, t default 1; n default
+// 100), printed per channel as `total-variation: sigma S target T mu M discrepancy D`.  It works with `auto auto`; --tv-color, --rl, --cls and
+// --mode parity beside it are refused.
 // `auto auto` for length and angle: the blur is estimated first (fft_gpu::estimateMotionBlur on the per-pixel mean of B, G and R),
 // printed as `estimate: length L angle A confidence C`, and the run then goes on exactly as `./gpu <img-path> L A` would.
 // `--cls auto` (gamma, with K = 0) or `--k auto` (K, with gamma = 0): the weight is chosen first (fft_gpu::chooseRegularisation on the same
@@ -116,6 +120,9 @@ int main(int argc, char** argv) {
     int tv_iterations = 50;
     bool tv_opts = false;
     bool tv_color = false;  // --tv-color: vectorial TV, the three channels under one shrinkage (tvDeblur_RGB's coupled form)
+    bool tv_auto = false;   // --tv auto: the TV leg is fft_gpu::tvDeblurAuto_RGB, mu chosen from the noise level (--sigma, else estimated)
+    float tv_tau = 0.f;     // --tv-tau t: the discrepancy ball is t sigma^2 S (default 1)
+    bool tv_tau_given = false, tv_iters_given = false;
     bool cls = false, parity = false, pad_smooth = false;
     bool cls_auto = false, k_auto = false;  // --cls auto / --k auto: the weight is chosen from the picture
     string reg_method;                      // --reg gcv|discrepancy
@@ -172,8 +179,12 @@ int main(int argc, char** argv) {
         else if (a == "--psf-sigma" && i + 1 < argc) { blind_opts = true; psf_sigma = atof(argv[++i]); }
         else if (a == "--psf-out" && i + 1 < argc) { blind_opts = true; psf_out_path = argv[++i]; }
         // total-variation deconvolution (fft_gpu::tvDeblur_RGB, fast mode): mu > 0, n >= 0 iterations, penalty rho > 0
-        else if (a == "--tv" && i + 1 < argc) tv_mu = strtof(argv[++i], nullptr);
-        else if (a == "--tv-iters" && i + 1 < argc) { tv_opts = true; tv_iterations = atoi(argv[++i]); }
+        else if (a == "--tv" && i + 1 < argc) {
+            if (string(argv[++i]) == "auto") tv_auto = true;
+            else tv_mu = strtof(argv[i], nullptr);
+        }
+        else if (a == "--tv-tau" && i + 1 < argc) { tv_tau_given = true; tv_tau = strtof(argv[++i], nullptr); }
+        else if (a == "--tv-iters" && i + 1 < argc) { tv_opts = true; tv_iters_given = true; tv_iterations = atoi(argv[++i]); }
         else if (a == "--tv-rho" && i + 1 < argc) { tv_opts = true; tv_rho = strtof(argv[++i], nullptr); }
         else if (a == "--tv-color") { tv_opts = true; tv_color = true; }
         else { cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle>\n"; return -1; }
@@ -181,7 +192,7 @@ int main(int argc, char** argv) {
     if (defocus && !defocus_auto && !(psf_radius > 0.0 && psf_radius <= 127.0)) { cout << "Usage: ./gpu <img-path> defocus <radius in (0, 127]|auto>\n"; return -1; }
     if (any_blur && !estimate) { cout << "Usage: ./gpu <img-path> auto auto --any-blur\n"; return -1; }
     // one weight is searched at a time; --reg and --sigma belong to a search
-    if ((cls_auto && k_auto) || (!(cls_auto || k_auto) && (!reg_method.empty() || (reg_sigma != 0.f && !rl_auto))) ||
+    if ((cls_auto && k_auto) || (!(cls_auto || k_auto) && (!reg_method.empty() || (reg_sigma != 0.f && !rl_auto && !tv_auto))) ||
         (!reg_method.empty() && reg_method != "gcv" && reg_method != "discrepancy") || !(K >= 0.f) || !(reg_sigma >= 0.f)) {
         cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle>\n";
         return -1;
@@ -190,8 +201,9 @@ int main(int argc, char** argv) {
     if (rl_iterations >= 0 && (cls || verify || parity || pad_smooth)) { cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle>\n"; return -1; }
     // --verify compares against the zero-padded serial leg
     if (pad_smooth && verify) { cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle>\n"; return -1; }
-    // --free-boundary belongs to --rl or --tv, --accel to --rl, --mask to --free-boundary
-    if ((free_boundary && rl_iterations < 0 && !(tv_mu > 0.f)) || (accel && rl_iterations < 0) || (!mask_path.empty() && !free_boundary)) {
+    // --free-boundary belongs to --rl or --tv, --accel to --rl, --mask to --free-boundary (--tv auto is a free-boundary leg with or without the word)
+    if ((free_boundary && rl_iterations < 0 && !(tv_mu > 0.f) && !tv_auto) || (accel && rl_iterations < 0) ||
+        (!mask_path.empty() && !free_boundary && !tv_auto)) {
         cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle>\n";
         return -1;
     }
@@ -220,11 +232,17 @@ int main(int argc, char** argv) {
         return -1;
     }
     // so does the TV leg; --tv-iters / --tv-rho / --tv-color belong to --tv, and one run has one iterative leg
-    const bool tv = tv_mu > 0.f;
+    const bool tv = tv_mu > 0.f || tv_auto;
     if ((tv && (cls || verify || parity || pad_smooth || rl_iterations >= 0 || tv_iterations < 0 || !(tv_rho > 0.f))) || (!tv && (tv_opts || tv_mu != -1.f))) {
         cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle>\n";
         return -1;
     }
+    // --tv auto states no mu and runs the channels one after the other; --tv-tau belongs to it and is >= 0
+    if ((tv_auto && (tv_mu != -1.f || tv_color || !(tv_tau >= 0.f) || !std::isfinite(tv_tau))) || (!tv_auto && tv_tau_given)) {
+        cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle> --tv auto [--sigma s] [--tv-tau t] [--tv-iters n] [--tv-rho r] [--mask m.png] (no --tv-color)\n";
+        return -1;
+    }
+    if (tv_auto && !tv_iters_given) tv_iterations = 100;  // the constrained iteration needs about a hundred steps
     // the free-boundary TV leg runs the channels one after the other: it has no vectorial form
     if (tv && free_boundary && tv_color) {
         cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle> --tv <mu> --free-boundary [--mask m.png] [--tv-iters n] [--tv-rho r] (no --tv-color)\n";
@@ -416,12 +434,19 @@ int main(int argc, char** argv) {
 
     if (tv) {  // total-variation deconvolution on the same channels: its planes become the written result
         vector<Mat> tvc = input;
+        vector<fdr_tv_auto_result> chosen;
         t_start = high_resolution_clock::now();
-        if (free_boundary) fft_gpu::tvDeblurFree_RGB(tvc, psf, tv_mu, tv_iterations, tv_rho, weights);
+        if (tv_auto) chosen = fft_gpu::tvDeblurAuto_RGB(tvc, psf, reg_sigma, tv_iterations, tv_rho, tv_tau, weights);
+        else if (free_boundary) fft_gpu::tvDeblurFree_RGB(tvc, psf, tv_mu, tv_iterations, tv_rho, weights);
         else fft_gpu::tvDeblur_RGB(tvc, psf, tv_mu, tv_iterations, tv_rho, tv_color);
         t_end = high_resolution_clock::now();
-        cout << "Deblurring 3 channels took(gpu[total-variation " << (free_boundary ? "free-boundary " : "") << "mu " << tv_mu << " rho " << tv_rho << " n " << tv_iterations
-             << (tv_color ? " colour" : "") << "]): " << getElapsedMs(t_start, t_end) << " ms\n";
+        for (const fdr_tv_auto_result& r : chosen)
+            printf("total-variation: sigma %.9g target %.9g mu %.9g discrepancy %.9g\n", r.sigma, r.target, r.mu, r.discrepancy);
+        fflush(stdout);
+        cout << "Deblurring 3 channels took(gpu[total-variation " << (free_boundary && !tv_auto ? "free-boundary " : "");
+        if (tv_auto) cout << "auto";
+        else cout << "mu " << tv_mu;
+        cout << " rho " << tv_rho << " n " << tv_iterations << (tv_color ? " colour" : "") << "]): " << getElapsedMs(t_start, t_end) << " ms\n";
         channels = tvc;
     }
 
