@@ -773,6 +773,77 @@ int fdr_tv_deconv_auto_f32(fdr_plan* plan, const float* img_host, int rows, int 
 int fdr_tv_deconv_auto_f32_dev(fdr_plan* plan, const float* d_img, int rows, int cols, int stride, const float* d_weights, int wstride,
                                float* d_out, int out_stride, const fdr_tv_auto_params* params, double* d_trace, void* stream);
 
+/* -- free-boundary and noise-constrained TV deconvolution in groups: `count` crops with one operator PSF and one weights plane (or
+ *    none), several per launch, and the vectorial coupling for them.  Image i is read at d_imgs + i img_pitch
+ *    and written at d_out + i out_pitch (elements), its output window out_rows x out_cols as in the single calls; the one weights
+ *    window serves every image, as in fdr_richardson_lucy_batch_f32*.  The batch is cut into launch groups of `group` images
+ *    (fdr_plan_set_batching; the last group may be smaller) and every pass of a group -- the start, per iteration the blur, the data
+ *    step on the windows (for the auto form the sums and the fold before it), the adjoint blur, the spatial kernel and the three
+ *    solve passes, the output -- is ONE launch over its images.  A group runs to completion on the caller's stream, on the
+ *    workspaces 0 .. group - 1, before the next begins.
+ *      FDR_TV_COUPLE_NONE      every image on its own: it comes out bit for bit as fdr_tv_deconv_free_f32_dev / _auto_f32_dev gives it
+ *                              on the same plan (for the auto form every trace entry as well), for every group size, tail, window,
+ *                              output window, pitch and stride, weights none, mask or fractional, isotropic or anisotropic;
+ *                              group = 1 is literally the loop of the single calls.
+ *      FDR_TV_COUPLE_CHANNELS  the images are the channels of one picture under vectorial TV.  The iteration of the single call
+ *                              changes in one place: z_c = s g_c with the joint gradient norm over the channels, exactly as in
+ *                              fdr_tv_deconv_batch_f32* (summed over c in order, in float; isotropic only).  The data step, the
+ *                              duals q_c, w_c, b_c, the solve and -- auto form -- the ball, the three sums and mu_k stay per channel:
+ *                              noise levels differ between channels, so there is no joint ball.  count = 1 gives the single call's
+ *                              bits.  FDR_ERR_ARG if count exceeds the plan's `group` (at most 8) or with anisotropic != 0.
+ *    Auto form: `sigmas` (host, count entries) gives a noise level per image, null: params->sigma serves all; an entry of 0 is
+ *    estimated from that image as the single call does (one wait on the stream before its group's first iteration).  Each image
+ *    has its own ball tau sigma_i^2 S, its own sums and its own mu_k.  Image i's trace (3 n doubles) goes to d_trace + i
+ *    trace_pitch (elements; d_trace may be null); the host form fills results[i] (may be null) as the single call fills `result`.
+ *    Refusals, always before any device work and with the plan usable afterwards: a null plan or null params, a negative count
+ *    (count = 0 returns FDR_OK at once), whatever the single call refuses for one image, an unknown coupling, any output of the
+ *    batch that overlaps any input or the weights; auto form: a sigmas entry negative or not finite, trace_pitch < 3 n when a trace
+ *    is asked for and count > 1, a trace range that overlaps an input, an output or the weights.
+ *    The first call with a group g larger than any before grows the free call's block to 2 g planes, the auto block to g sets of
+ *    partials, sums and mu_k, and the TV workspace to 6 g planes, each new block had before the old one is let go; FDR_ERR_ALLOC
+ *    leaves the plan and its workspaces intact.  After that the _dev forms allocate nothing and, with every sigma given, read
+ *    nothing back and stay asynchronous on `stream`; the host forms copy in and out synchronously.  Results and traces repeat bit
+ *    for bit from call to call (no atomics).                                                                                  */
+typedef struct fdr_tv_free_batch_params {
+    float mu;        /* weight of the data term, > 0 */
+    float rho;       /* ADMM penalty of z = D x, > 0 */
+    float nu;        /* ADMM penalty of s = blur(x), >= 0; 0 selects rho */
+    int iterations;  /* >= 0 */
+    int anisotropic; /* 0: isotropic TV, else anisotropic (FDR_TV_COUPLE_NONE only) */
+    int nonneg;      /* != 0: the output is max(x, 0) */
+    int norm_area;   /* FDR_NORM_NONE / FDR_NORM_CROPPED / FDR_NORM_PADDED, per image over its output window */
+    int out_rows;    /* rows .. M */
+    int out_cols;    /* cols .. N */
+    int coupling;    /* FDR_TV_COUPLE_NONE / FDR_TV_COUPLE_CHANNELS */
+} fdr_tv_free_batch_params;
+int fdr_tv_deconv_free_batch_f32_dev(fdr_plan* plan, const float* d_imgs, size_t img_pitch, int count, int rows, int cols, int stride,
+                                     const float* d_weights, int wstride, float* d_out, size_t out_pitch, int out_stride,
+                                     const fdr_tv_free_batch_params* params, void* stream);
+int fdr_tv_deconv_free_batch_f32(fdr_plan* plan, const float* imgs_host, size_t img_pitch, int count, int rows, int cols, int stride,
+                                 const float* weights_host, int wstride, float* out_host, size_t out_pitch, int out_stride,
+                                 const fdr_tv_free_batch_params* params);
+typedef struct fdr_tv_auto_batch_params {
+    float sigma;     /* noise standard deviation of every picture when `sigmas` is null, >= 0; 0 = estimated per image */
+    float tau;       /* the balls are tau sigma_i^2 S, >= 0; 0 selects 1 */
+    float rho;       /* ADMM penalty of z = D x, > 0 */
+    float nu;        /* ADMM penalty of s = blur(x), >= 0; 0 selects FDR_TV_AUTO_NU_RATIO rho */
+    int iterations;  /* >= 0 */
+    int anisotropic; /* 0: isotropic TV, else anisotropic (FDR_TV_COUPLE_NONE only) */
+    int nonneg;      /* != 0: the output is max(x, 0) */
+    int norm_area;   /* FDR_NORM_NONE / FDR_NORM_CROPPED / FDR_NORM_PADDED, per image over its output window */
+    int out_rows;    /* rows .. M */
+    int out_cols;    /* cols .. N */
+    int coupling;    /* FDR_TV_COUPLE_NONE / FDR_TV_COUPLE_CHANNELS */
+} fdr_tv_auto_batch_params;
+int fdr_tv_deconv_auto_batch_f32_dev(fdr_plan* plan, const float* d_imgs, size_t img_pitch, int count, int rows, int cols, int stride,
+                                     const float* d_weights, int wstride, float* d_out, size_t out_pitch, int out_stride,
+                                     const fdr_tv_auto_batch_params* params, const double* sigmas, double* d_trace, size_t trace_pitch,
+                                     void* stream);
+int fdr_tv_deconv_auto_batch_f32(fdr_plan* plan, const float* imgs_host, size_t img_pitch, int count, int rows, int cols, int stride,
+                                 const float* weights_host, int wstride, float* out_host, size_t out_pitch, int out_stride,
+                                 const fdr_tv_auto_batch_params* params, const double* sigmas, fdr_tv_auto_result* results,
+                                 double* trace_host, size_t trace_pitch);
+
 /* -- the motion-blur estimate: the length and angle of a uniform linear motion blur, from the blurred
  *    picture alone, by the power cepstrum.  The blur puts sinc zeros into |G| in stripes across the motion direction; in the
  *    cepstrum they show as a negative peak at distance L along it.  The plan is M x N, the image window rows x cols (row stride

@@ -490,11 +490,14 @@ inline void tvDeblur_RGB(std::vector<Mat>& channels, const Mat& psf, float mu, i
 }
 // Free-boundary, weighted total-variation deconvolution (fdr_tv_deconv_free_f32, include/fdr.h) of every channel, in place, for a
 // picture that is a crop of a larger scene: the plan, operator PSF and `weights` of richardsonLucyFree_RGB, `iterations` ADMM steps
-// (isotropic, penalties rho and nu = rho), the output clamped at 0 and normalised by o.norm_area.  The channels run one after the
-// other on the one plan.
-inline void tvDeblurFree_RGB(std::vector<Mat>& channels, const Mat& psf, float mu, int iterations, float rho, const Mat& weights, const Options& o) {
+// (isotropic, penalties rho and nu = rho), the output clamped at 0 and normalised by o.norm_area.  The channels go through ONE
+// batched call (fdr_tv_deconv_free_batch_f32) on a launch group of channels.size() images (at most 8), with the bits of the
+// per-channel calls; channels of different sizes or types run one by one.  coupled: vectorial TV -- the channels share one
+// shrinkage by their joint gradient norm (FDR_TV_COUPLE_CHANNELS; at most 8 channels of one size); the data step stays per channel.
+inline void tvDeblurFree_RGB(std::vector<Mat>& channels, const Mat& psf, float mu, int iterations, float rho, const Mat& weights, const Options& o,
+                             bool coupled = false) {
     if (channels.empty()) return;
-    const int rows = channels[0].rows, cols = channels[0].cols;
+    const int rows = channels[0].rows, cols = channels[0].cols, count = (int)channels.size();
     if (!weights.empty() && (weights.rows != rows || weights.cols != cols || weights.type() != CV_32F)) {
         std::cerr << "tvDeblurFree_RGB: the weights must be CV_32F and have the picture's size\n";
         exit(1);
@@ -506,6 +509,30 @@ inline void tvDeblurFree_RGB(std::vector<Mat>& channels, const Mat& psf, float m
     Mat psfc = psf.isContinuous() ? psf : psf.clone();
     FDR_CHECK(fdr_set_operator_psf(plan, psfc.ptr<float>(0), psf.rows, psf.cols, psf.cols));
     Mat w = weights.empty() || weights.isContinuous() ? weights : weights.clone();
+    bool same = true;
+    for (const Mat& c : channels) same = same && c.rows == rows && c.cols == cols && c.type() == CV_32F;
+    if (same || coupled) {
+        if (!same) {
+            std::cerr << "tvDeblurFree_RGB: the coupled form needs CV_32F channels of one size\n";
+            exit(1);
+        }
+        const size_t px = (size_t)rows * cols;
+        std::vector<float> in(px * count), out(px * count);
+        for (int i = 0; i < count; ++i)
+            for (int r = 0; r < rows; ++r) std::copy(channels[i].ptr<float>(r), channels[i].ptr<float>(r) + cols, in.begin() + i * px + (size_t)r * cols);
+        const fdr_tv_free_batch_params bp = {mu, rho, 0.f, iterations, 0, 1, o.norm_area, rows, cols, coupled ? FDR_TV_COUPLE_CHANNELS : FDR_TV_COUPLE_NONE};
+        FDR_CHECK(fdr_plan_set_batching(plan, 1, std::min(count, 8)));
+        const int rc = fdr_tv_deconv_free_batch_f32(plan, in.data(), px, count, rows, cols, cols, w.empty() ? nullptr : w.ptr<float>(0), cols, out.data(), px,
+                                                    cols, &bp);
+        FDR_CHECK(fdr_plan_set_batching(plan, 1, 1));  // the cached plan goes back as it came
+        FDR_CHECK(rc);
+        for (int i = 0; i < count; ++i) {
+            Mat m(rows, cols, CV_32F);
+            std::copy(out.begin() + i * px, out.begin() + (i + 1) * px, m.ptr<float>(0));
+            channels[i] = m;
+        }
+        return;
+    }
     for (Mat& c : channels) {
         Mat src = c.isContinuous() ? c : c.clone();
         Mat out(c.rows, c.cols, CV_32F);
@@ -515,20 +542,23 @@ inline void tvDeblurFree_RGB(std::vector<Mat>& channels, const Mat& psf, float m
         c = out;
     }
 }
-inline void tvDeblurFree_RGB(std::vector<Mat>& channels, const Mat& psf, float mu, int iterations = 50, float rho = 2.0f, const Mat& weights = Mat()) {
-    tvDeblurFree_RGB(channels, psf, mu, iterations, rho, weights, defaults());
+inline void tvDeblurFree_RGB(std::vector<Mat>& channels, const Mat& psf, float mu, int iterations = 50, float rho = 2.0f, const Mat& weights = Mat(),
+                             bool coupled = false) {
+    tvDeblurFree_RGB(channels, psf, mu, iterations, rho, weights, defaults(), coupled);
 }
 // Noise-constrained total-variation deconvolution (fdr_tv_deconv_auto_f32, include/fdr.h) of every channel, in place: tvDeblurFree_RGB
 // without mu.  The caller states the noise standard deviation sigma of the channels (0: estimated per channel, fdr_noise_sigma_f32)
 // and tau (0: 1); every step takes its weight from the discrepancy ball tau sigma^2 sum(weights).  The plan, operator PSF and
 // `weights` of tvDeblurFree_RGB, `iterations` ADMM steps (isotropic, penalties rho and nu = FDR_TV_AUTO_NU_RATIO rho), the output
-// clamped at 0 and normalised by o.norm_area, one channel after the other.  Returns the channels' results (sigma, target, mu,
-// discrepancy, S), in order.
+// clamped at 0 and normalised by o.norm_area.  The channels go through ONE batched call (fdr_tv_deconv_auto_batch_f32) on a launch
+// group of channels.size() images (at most 8), with the bits of the per-channel calls; channels of different sizes or types run
+// one by one.  coupled: vectorial TV -- one shrinkage by the joint gradient norm of the channels (at most 8 of one size), every
+// channel with its own ball and its own mu_k.  Returns the channels' results (sigma, target, mu, discrepancy, S), in order.
 inline std::vector<fdr_tv_auto_result> tvDeblurAuto_RGB(std::vector<Mat>& channels, const Mat& psf, float sigma, int iterations, float rho, float tau,
-                                                        const Mat& weights, const Options& o) {
+                                                        const Mat& weights, const Options& o, bool coupled = false) {
     std::vector<fdr_tv_auto_result> results;
     if (channels.empty()) return results;
-    const int rows = channels[0].rows, cols = channels[0].cols;
+    const int rows = channels[0].rows, cols = channels[0].cols, count = (int)channels.size();
     if (!weights.empty() && (weights.rows != rows || weights.cols != cols || weights.type() != CV_32F)) {
         std::cerr << "tvDeblurAuto_RGB: the weights must be CV_32F and have the picture's size\n";
         exit(1);
@@ -540,6 +570,32 @@ inline std::vector<fdr_tv_auto_result> tvDeblurAuto_RGB(std::vector<Mat>& channe
     Mat psfc = psf.isContinuous() ? psf : psf.clone();
     FDR_CHECK(fdr_set_operator_psf(plan, psfc.ptr<float>(0), psf.rows, psf.cols, psf.cols));
     Mat w = weights.empty() || weights.isContinuous() ? weights : weights.clone();
+    bool same = true;
+    for (const Mat& c : channels) same = same && c.rows == rows && c.cols == cols && c.type() == CV_32F;
+    if (same || coupled) {
+        if (!same) {
+            std::cerr << "tvDeblurAuto_RGB: the coupled form needs CV_32F channels of one size\n";
+            exit(1);
+        }
+        const size_t px = (size_t)rows * cols;
+        std::vector<float> in(px * count), out(px * count);
+        for (int i = 0; i < count; ++i)
+            for (int r = 0; r < rows; ++r) std::copy(channels[i].ptr<float>(r), channels[i].ptr<float>(r) + cols, in.begin() + i * px + (size_t)r * cols);
+        const fdr_tv_auto_batch_params bp = {sigma, tau, rho, 0.f, iterations, 0, 1, o.norm_area, rows, cols,
+                                             coupled ? FDR_TV_COUPLE_CHANNELS : FDR_TV_COUPLE_NONE};
+        results.resize(count);
+        FDR_CHECK(fdr_plan_set_batching(plan, 1, std::min(count, 8)));
+        const int rc = fdr_tv_deconv_auto_batch_f32(plan, in.data(), px, count, rows, cols, cols, w.empty() ? nullptr : w.ptr<float>(0), cols, out.data(), px,
+                                                    cols, &bp, nullptr, results.data(), nullptr, 0);
+        FDR_CHECK(fdr_plan_set_batching(plan, 1, 1));  // the cached plan goes back as it came
+        FDR_CHECK(rc);
+        for (int i = 0; i < count; ++i) {
+            Mat m(rows, cols, CV_32F);
+            std::copy(out.begin() + i * px, out.begin() + (i + 1) * px, m.ptr<float>(0));
+            channels[i] = m;
+        }
+        return results;
+    }
     for (Mat& c : channels) {
         Mat src = c.isContinuous() ? c : c.clone();
         Mat out(c.rows, c.cols, CV_32F);
@@ -553,8 +609,8 @@ inline std::vector<fdr_tv_auto_result> tvDeblurAuto_RGB(std::vector<Mat>& channe
     return results;
 }
 inline std::vector<fdr_tv_auto_result> tvDeblurAuto_RGB(std::vector<Mat>& channels, const Mat& psf, float sigma = 0.f, int iterations = 100,
-                                                        float rho = 2.0f, float tau = 0.f, const Mat& weights = Mat()) {
-    return tvDeblurAuto_RGB(channels, psf, sigma, iterations, rho, tau, weights, defaults());
+                                                        float rho = 2.0f, float tau = 0.f, const Mat& weights = Mat(), bool coupled = false) {
+    return tvDeblurAuto_RGB(channels, psf, sigma, iterations, rho, tau, weights, defaults(), coupled);
 }
 // The motion blur of a one-channel picture of unknown blur (fdr_estimate_motion_f32, include/fdr.h): length and angle in the
 // convention of motionBlurKernel, the table minimum and the confidence (below about 10: no clear blur).  Its own FDR_MODE_FAST plan

@@ -101,6 +101,20 @@ class TvAutoParams(ctypes.Structure):
                 ("out_rows", ctypes.c_int), ("out_cols", ctypes.c_int)]
 
 
+class TvFreeBatchParams(ctypes.Structure):
+    """fdr_tv_free_batch_params of include/fdr.h"""
+    _fields_ = [("mu", ctypes.c_float), ("rho", ctypes.c_float), ("nu", ctypes.c_float), ("iterations", ctypes.c_int),
+                ("anisotropic", ctypes.c_int), ("nonneg", ctypes.c_int), ("norm_area", ctypes.c_int), ("out_rows", ctypes.c_int),
+                ("out_cols", ctypes.c_int), ("coupling", ctypes.c_int)]
+
+
+class TvAutoBatchParams(ctypes.Structure):
+    """fdr_tv_auto_batch_params of include/fdr.h"""
+    _fields_ = [("sigma", ctypes.c_float), ("tau", ctypes.c_float), ("rho", ctypes.c_float), ("nu", ctypes.c_float),
+                ("iterations", ctypes.c_int), ("anisotropic", ctypes.c_int), ("nonneg", ctypes.c_int), ("norm_area", ctypes.c_int),
+                ("out_rows", ctypes.c_int), ("out_cols", ctypes.c_int), ("coupling", ctypes.c_int)]
+
+
 class TvAutoResultC(ctypes.Structure):
     """fdr_tv_auto_result of include/fdr.h"""
     _fields_ = [("sigma", ctypes.c_double), ("target", ctypes.c_double), ("mu", ctypes.c_double), ("discrepancy", ctypes.c_double),
@@ -317,6 +331,10 @@ def _signatures():
         "fdr_tv_deconv_free_f32_dev": (ci, [vp, vp, ci, ci, ci, vp, ci, vp, ci, P(TvFreeParams), vp]),
         "fdr_tv_deconv_auto_f32": (ci, [vp, vp, ci, ci, ci, vp, ci, vp, ci, P(TvAutoParams), P(TvAutoResultC), vp]),
         "fdr_tv_deconv_auto_f32_dev": (ci, [vp, vp, ci, ci, ci, vp, ci, vp, ci, P(TvAutoParams), vp, vp]),
+        "fdr_tv_deconv_free_batch_f32": (ci, [vp, vp, sz, ci, ci, ci, ci, vp, ci, vp, sz, ci, P(TvFreeBatchParams)]),
+        "fdr_tv_deconv_free_batch_f32_dev": (ci, [vp, vp, sz, ci, ci, ci, ci, vp, ci, vp, sz, ci, P(TvFreeBatchParams), vp]),
+        "fdr_tv_deconv_auto_batch_f32": (ci, [vp, vp, sz, ci, ci, ci, ci, vp, ci, vp, sz, ci, P(TvAutoBatchParams), vp, vp, vp, sz]),
+        "fdr_tv_deconv_auto_batch_f32_dev": (ci, [vp, vp, sz, ci, ci, ci, ci, vp, ci, vp, sz, ci, P(TvAutoBatchParams), vp, vp, sz, vp]),
         "fdr_cepstrum_f32": (ci, [vp, vp, ci, ci, ci, vp]),
         "fdr_cepstrum_f32_dev": (ci, [vp, vp, ci, ci, ci, vp, vp]),
         "fdr_estimate_motion_f32": (ci, [vp, vp, ci, ci, ci, ci, ci, cd, P(MotionEstimateC), vp]),
@@ -974,6 +992,86 @@ class Plan:
         _check(lib.fdr_tv_deconv_batch_f32(self._h, _ptr(imgs), rows * cols, cnt, rows, cols, cols, _ptr(out), rows * cols, cols, ctypes.byref(prm)))
         return out
 
+    # free-boundary and noise-constrained TV deconvolution in groups (include/fdr.h): several crops per launch, or the channels of
+    # one picture under vectorial TV
+    def _crop_batch_args(self, imgs, weights, full_plane):
+        imgs = np.ascontiguousarray(imgs, dtype=np.float32)
+        cnt, rows, cols = imgs.shape
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float32)
+            if w.shape != (rows, cols):
+                raise ValueError("weights must have the shape of one image")
+        orows, ocols = (self.M, self.N) if full_plane else (rows, cols)
+        return imgs, cnt, rows, cols, w, orows, ocols, np.empty((cnt, orows, ocols), dtype=np.float32)
+
+    def tv_deconv_free_batch(self, imgs, mu, rho=2.0, iterations=50, weights=None, nu=0.0, anisotropic=False, nonneg=False,
+                             norm_area=NORM_NONE, full_plane=False, coupled=False):
+        """Host arrays [count, rows, cols] in, [count, rows, cols] (full_plane: [count, M, N]) out: tv_deconv_free per image with one
+        weights plane for all, several per launch (set_batching); coupled: vectorial TV on the images as the channels of one picture
+        (fdr_tv_deconv_free_batch_f32)."""
+        imgs, cnt, rows, cols, w, orows, ocols, out = self._crop_batch_args(imgs, weights, full_plane)
+        prm = TvFreeBatchParams(float(mu), float(rho), float(nu), int(iterations), int(bool(anisotropic)), int(bool(nonneg)), int(norm_area),
+                                orows, ocols, TV_COUPLE_CHANNELS if coupled else TV_COUPLE_NONE)
+        _check(lib.fdr_tv_deconv_free_batch_f32(self._h, _ptr(imgs), rows * cols, cnt, rows, cols, cols, _ptr(w) if w is not None else None, cols,
+                                                _ptr(out), orows * ocols, ocols, ctypes.byref(prm)))
+        return out
+
+    def tv_deconv_free_batch_dev(self, d_imgs, img_pitch, count, rows, cols, stride, d_out, out_pitch, out_stride, mu, rho=2.0, iterations=50,
+                                 d_weights=None, wstride=0, nu=0.0, anisotropic=False, nonneg=False, norm_area=NORM_NONE, out_rows=None,
+                                 out_cols=None, coupled=False, stream=None):
+        """fdr_tv_deconv_free_batch_f32_dev: tv_deconv_free_dev on `count` windows, image i at d_imgs + i img_pitch / d_out + i
+        out_pitch (elements), one weights window for all, in launch groups of the plan's `group` (set_batching).  coupled: the images
+        are the channels of one picture and share one shrinkage (count <= group, isotropic).  Asynchronous."""
+        prm = TvFreeBatchParams(float(mu), float(rho), float(nu), int(iterations), int(bool(anisotropic)), int(bool(nonneg)), int(norm_area),
+                                int(rows if out_rows is None else out_rows), int(cols if out_cols is None else out_cols),
+                                TV_COUPLE_CHANNELS if coupled else TV_COUPLE_NONE)
+        _check(lib.fdr_tv_deconv_free_batch_f32_dev(self._h, ctypes.c_void_p(int(d_imgs)), img_pitch, count, rows, cols, stride,
+                                                    ctypes.c_void_p(int(d_weights)) if d_weights else None, int(wstride),
+                                                    ctypes.c_void_p(int(d_out)), out_pitch, out_stride, ctypes.byref(prm), _stream(stream)))
+
+    def tv_deconv_auto_batch(self, imgs, sigma=0.0, rho=2.0, iterations=100, weights=None, tau=0.0, nu=0.0, anisotropic=False, nonneg=False,
+                             norm_area=NORM_NONE, full_plane=False, sigmas=None, coupled=False):
+        """tv_deconv_auto on host arrays [count, rows, cols], several per launch: sigmas (count entries; None: sigma for all) gives a
+        noise level per image, 0 = estimated from that image; every image has its own ball and its own mu_k, also with coupled
+        (vectorial TV on the images as the channels of one picture).  Returns (images, [TvAutoResult], traces [count, iterations, 3])
+        (fdr_tv_deconv_auto_batch_f32)."""
+        imgs, cnt, rows, cols, w, orows, ocols, out = self._crop_batch_args(imgs, weights, full_plane)
+        n = max(int(iterations), 0)
+        traces = np.zeros((cnt, n, 3), dtype=np.float64)
+        sg = None
+        if sigmas is not None:
+            sg = np.ascontiguousarray(sigmas, dtype=np.float64)
+            if sg.shape != (cnt,):
+                raise ValueError("sigmas must have one entry per image")
+        prm = TvAutoBatchParams(float(sigma), float(tau), float(rho), float(nu), int(iterations), int(bool(anisotropic)), int(bool(nonneg)),
+                                int(norm_area), orows, ocols, TV_COUPLE_CHANNELS if coupled else TV_COUPLE_NONE)
+        res = (TvAutoResultC * max(cnt, 1))()
+        _check(lib.fdr_tv_deconv_auto_batch_f32(self._h, _ptr(imgs), rows * cols, cnt, rows, cols, cols, _ptr(w) if w is not None else None, cols,
+                                                _ptr(out), orows * ocols, ocols, ctypes.byref(prm), _ptr(sg) if sg is not None else None, res,
+                                                _ptr(traces) if traces.size else None, 3 * n))
+        return out, [TvAutoResult(r.sigma, r.target, r.mu, r.discrepancy, r.S) for r in res[:cnt]], traces
+
+    def tv_deconv_auto_batch_dev(self, d_imgs, img_pitch, count, rows, cols, stride, d_out, out_pitch, out_stride, sigma=0.0, rho=2.0,
+                                 iterations=100, d_weights=None, wstride=0, tau=0.0, nu=0.0, anisotropic=False, nonneg=False, norm_area=NORM_NONE,
+                                 out_rows=None, out_cols=None, sigmas=None, d_trace=None, trace_pitch=0, coupled=False, stream=None):
+        """fdr_tv_deconv_auto_batch_f32_dev: tv_deconv_auto_dev on `count` windows laid out as in tv_deconv_free_batch_dev; sigmas is a
+        host sequence of count noise levels or None, image i's trace (3 * iterations doubles) goes to d_trace + i trace_pitch
+        (elements) when d_trace is given.  Asynchronous when every noise level is given; an estimated one waits for the stream once."""
+        prm = TvAutoBatchParams(float(sigma), float(tau), float(rho), float(nu), int(iterations), int(bool(anisotropic)), int(bool(nonneg)),
+                                int(norm_area), int(rows if out_rows is None else out_rows), int(cols if out_cols is None else out_cols),
+                                TV_COUPLE_CHANNELS if coupled else TV_COUPLE_NONE)
+        sg = None
+        if sigmas is not None:
+            sg = np.ascontiguousarray(sigmas, dtype=np.float64)
+            if sg.shape != (count,):
+                raise ValueError("sigmas must have one entry per image")
+        _check(lib.fdr_tv_deconv_auto_batch_f32_dev(self._h, ctypes.c_void_p(int(d_imgs)), img_pitch, count, rows, cols, stride,
+                                                    ctypes.c_void_p(int(d_weights)) if d_weights else None, int(wstride),
+                                                    ctypes.c_void_p(int(d_out)), out_pitch, out_stride, ctypes.byref(prm),
+                                                    _ptr(sg) if sg is not None else None, ctypes.c_void_p(int(d_trace)) if d_trace else None,
+                                                    int(trace_pitch), _stream(stream)))
+
     # the motion-blur estimate (include/fdr.h): the power cepstrum of the windowed picture and the blur it shows
     def cepstrum(self, img):
         """c = Re IDFT2(log(|DFT2(hann . img)| + eps)) on the plan (M x N float32); img is the window at the top-left (host array)"""
@@ -1391,10 +1489,12 @@ def tvDeblurFree_myfft(img, psf, mu, rho=2.0, iterations=50, weights=None, nu=0.
         return p.tv_deconv_free(img, mu, rho, iterations, weights, nu, anisotropic, nonneg, norm_area, full_plane)
 
 
-def tvDeblurFree_RGB(channels, psf, mu, rho=2.0, iterations=50, nonneg=False, device=0, norm_area=NORM_NONE, weights=None, nu=0.0):
-    """fft_gpu::tvDeblurFree_RGB: replaces every element of `channels` (float32 planes of one size) in place with its free-boundary
-    total-variation estimate, from one plan (that of tvDeblurFree_myfft) and one weights plane for all channels, one channel after
-    the other -- the bits of tvDeblurFree_myfft per channel."""
+def tvDeblurFree_RGB(channels, psf, mu, rho=2.0, iterations=50, nonneg=False, device=0, norm_area=NORM_NONE, weights=None, nu=0.0,
+                     coupled=False):
+    """fft_gpu::tvDeblurFree_RGB: replaces every element of `channels` (float32 planes of one size, at most 8 when coupled) in place
+    with its free-boundary total-variation estimate, from one plan (that of tvDeblurFree_myfft), one weights plane for all channels
+    and one launch per pass -- the bits of tvDeblurFree_myfft per channel, or with coupled the vectorial TV of the picture: one
+    shrinkage by the joint gradient norm of the channels."""
     if not channels:
         return
     psf = np.asarray(psf, dtype=np.float32)
@@ -1402,8 +1502,11 @@ def tvDeblurFree_RGB(channels, psf, mu, rho=2.0, iterations=50, nonneg=False, de
     M, N = _rlfree_plan_size(r, c, psf.shape[0], psf.shape[1])
     with Plan(M, N, MODE_FAST, device) as p:
         p.set_operator_psf(psf)
-        for i in range(len(channels)):
-            channels[i] = p.tv_deconv_free(channels[i], mu, rho, iterations, weights, nu, False, nonneg, norm_area)
+        p.set_batching(1, min(len(channels), 8))
+        out = p.tv_deconv_free_batch(np.stack([np.asarray(c, dtype=np.float32) for c in channels]), mu, rho, iterations, weights, nu, False,
+                                     nonneg, norm_area, False, coupled)
+    for i in range(len(channels)):
+        channels[i] = out[i]
 
 
 def tvDeblurAuto_myfft(img, psf, sigma=0.0, rho=2.0, iterations=100, weights=None, tau=0.0, nu=0.0, anisotropic=False, nonneg=False, device=0,
@@ -1420,11 +1523,11 @@ def tvDeblurAuto_myfft(img, psf, sigma=0.0, rho=2.0, iterations=100, weights=Non
 
 
 def tvDeblurAuto_RGB(channels, psf, sigma=0.0, rho=2.0, iterations=100, nonneg=False, device=0, norm_area=NORM_NONE, weights=None, tau=0.0,
-                     nu=0.0):
-    """fft_gpu::tvDeblurAuto_RGB: replaces every element of `channels` (float32 planes of one size) in place with its noise-constrained
-    total-variation estimate, from one plan (that of tvDeblurAuto_myfft) and one weights plane for all channels, one channel after the
-    other, sigma given or (0) estimated per channel -- the bits of tvDeblurAuto_myfft per channel.  Returns the TvAutoResult of
-    every channel."""
+                     nu=0.0, coupled=False):
+    """fft_gpu::tvDeblurAuto_RGB: replaces every element of `channels` (float32 planes of one size, at most 8 when coupled) in place
+    with its noise-constrained total-variation estimate, from one plan (that of tvDeblurAuto_myfft), one weights plane for all
+    channels and one launch per pass, sigma given or (0) estimated per channel -- the bits of tvDeblurAuto_myfft per channel, or with
+    coupled the vectorial TV of the picture with a ball and a mu_k per channel.  Returns the TvAutoResult of every channel."""
     results = []
     if not channels:
         return results
@@ -1433,9 +1536,11 @@ def tvDeblurAuto_RGB(channels, psf, sigma=0.0, rho=2.0, iterations=100, nonneg=F
     M, N = _rlfree_plan_size(r, c, psf.shape[0], psf.shape[1])
     with Plan(M, N, MODE_FAST, device) as p:
         p.set_operator_psf(psf)
-        for i in range(len(channels)):
-            channels[i], res, _ = p.tv_deconv_auto(channels[i], sigma, rho, iterations, weights, tau, nu, False, nonneg, norm_area)
-            results.append(res)
+        p.set_batching(1, min(len(channels), 8))
+        out, results, _ = p.tv_deconv_auto_batch(np.stack([np.asarray(c, dtype=np.float32) for c in channels]), sigma, rho, iterations, weights,
+                                                 tau, nu, False, nonneg, norm_area, False, None, coupled)
+    for i in range(len(channels)):
+        channels[i] = out[i]
     return results
 
 

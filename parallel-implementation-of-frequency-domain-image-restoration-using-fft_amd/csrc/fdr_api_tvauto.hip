@@ -1,7 +1,8 @@
 // fdr_api_tvauto.hip -- noise-constrained TV deconvolution (fdr_tv_deconv_auto_f32*; kernels in fdr_tvauto.hip): the free-boundary
 // iteration of fdr_api_tvfree.hip with the weight of every data step taken from the discrepancy of that step.  Here: the small block
-// it adds to the workspaces of the free call, the checks and the two entry points.  The driver is the free call's (tvfree_dev_impl
-// with a TvAuto), on the shared solve table built for nu.
+// it adds to the workspaces of the free call (per image of a launch group), the checks and the two entry points.  The driver is the
+// free call's (tvfree_group_dev with a TvAuto), on the shared solve table built for nu; the batched entry points are in
+// fdr_api_tvfreebatch.hip.
 #include "fdr_host.hpp"
 
 #include <cmath>
@@ -13,14 +14,11 @@ namespace {
 // names are static strings compared by pointer in PassTimer::pass_id
 const char* const kPassTaNoise = "TVA noise: sum |d * n|";
 
-// the checked arguments with their defaults
-struct TvAutoArgs {
-    fdr_tv_free_params fp;  // the free call's, with nu resolved; mu is a placeholder
-    double sigma, tau;
-    bool estimate;
-};
-
 bool finite_nonneg(float v) { return std::isfinite(v) && v >= 0.f; }
+
+}  // namespace
+
+namespace fdr {
 
 // everything an auto call refuses, before any device work: what the free call refuses, then its own arguments
 int tvauto_check(const fdr_plan* p, const char* fn, const float* img, int rows, int cols, int stride, const float* weights, int wstride,
@@ -51,31 +49,44 @@ int tvauto_check(const fdr_plan* p, const char* fn, const float* img, int rows, 
     return FDR_OK;
 }
 
-// The first auto call of a plan: the partials of the three sums, the last step's sums, the partials of the noise estimate and mu_k
-// in a block of its own.  Nothing is let go for it, so on FDR_ERR_ALLOC the plan is what it was.
-int ensure_tvauto_workspace(fdr_plan* p, const char* fn) {
-    if (p->ta_block) return FDR_OK;
-    const size_t n_part = 3 * (size_t)tvauto_max_partials(p->M, p->N);
-    const size_t doubles = n_part + 4 + (size_t)kRegMaxPartials + 1;
+// The first auto call of a plan, or the first on a larger group: per image of the group the partials of the three sums, the last
+// step's sums and mu_k, and the partials of the noise estimate once, in a block of its own.  The new block is had before the old one
+// is let go (nothing it holds outlives a call), so on FDR_ERR_ALLOC the plan is what it was.
+int ensure_tvauto_workspace(fdr_plan* p, const char* fn, int group) {
+    if (p->ta_block && p->ta_group >= group) return FDR_OK;
+    const size_t n_part = (size_t)group * 3 * (size_t)tvauto_max_partials(p->M, p->N);
+    const size_t doubles = n_part + 4 * (size_t)group + (size_t)kRegMaxPartials + 1;
     char* blk = nullptr;
-    if (hipMalloc((void**)&blk, doubles * sizeof(double) + sizeof(float)) != hipSuccess) {
+    if (hipMalloc((void**)&blk, doubles * sizeof(double) + (size_t)group * sizeof(float)) != hipSuccess) {
         (void)hipGetLastError();
         return fail(FDR_ERR_ALLOC, std::string(fn) + ": hipMalloc of the noise-constrained TV workspace failed");
     }
+    if (p->ta_block) (void)hipFree(p->ta_block);  // (waits for the device: nothing queued still uses it)
     p->ta_block = blk;
+    p->ta_group = group;
     p->ta_part = reinterpret_cast<double*>(blk);
     p->ta_stat = p->ta_part + n_part;
-    p->ta_noise = p->ta_stat + 4;
+    p->ta_noise = p->ta_stat + 4 * (size_t)group;
     p->ta_mu = reinterpret_cast<float*>(p->ta_noise + kRegMaxPartials + 1);
     return FDR_OK;
 }
 
 // the free call's workspaces first, then the block of this call
-int tvauto_prepare(fdr_plan* p, const char* fn) {
-    int rc = tvfree_prepare(p, fn);
-    if (rc == FDR_OK) rc = ensure_tvauto_workspace(p, fn);
+int tvauto_prepare(fdr_plan* p, const char* fn, int group) {
+    int rc = tvfree_prepare(p, fn, group);
+    if (rc == FDR_OK) rc = ensure_tvauto_workspace(p, fn, group);
     return rc;
 }
+
+// the noise level of one window, as fdr_noise_sigma_f32 estimates it: one launch and one read-back (waits for `s`)
+int tvauto_noise_dev(fdr_plan* p, const float* d_img, int rows, int cols, int stride, double* sigma, hipStream_t s) {
+    ScopedPass t(p, s, kPassTaNoise);
+    return noise_sigma_dev(d_img, rows, cols, stride, p->ta_noise, sigma, s);
+}
+
+}  // namespace fdr
+
+namespace {
 
 // The whole call on `s`: the noise estimate when sigma is not given (one read-back), then the iteration.  *sigma_used, when not
 // null, receives the noise level of the ball.
@@ -83,12 +94,11 @@ int tvauto_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, i
                     int out_stride, const TvAutoArgs& a, double* d_trace, double* sigma_used, hipStream_t s) {
     double sigma = a.sigma;
     if (a.estimate && a.fp.iterations > 0) {
-        ScopedPass t(p, s, kPassTaNoise);
-        const int rc = noise_sigma_dev(d_img, rows, cols, stride, p->ta_noise, &sigma, s);
+        const int rc = tvauto_noise_dev(p, d_img, rows, cols, stride, &sigma, s);
         if (rc != FDR_OK) return rc;
     }
     if (sigma_used) *sigma_used = sigma;
-    const TvAuto au{sigma, a.tau, d_trace};
+    const TvAuto au{a.tau, {sigma}, {d_trace}};
     return tvfree_dev_impl(p, fn, d_img, rows, cols, stride, d_w, wstride, d_out, out_stride, a.fp, s, &au);
 }
 

@@ -1,5 +1,6 @@
 // fdr_api_tvfree.hip -- free-boundary, weighted TV deconvolution by ADMM with two splittings (fdr_tv_deconv_free_f32*; the data step
-// in fdr_tvfree.hip): the two planes it adds to the TV workspace, the checks, the driver and the two entry points.  Everything but
+// in fdr_tvfree.hip): the two planes per image it adds to the TV workspace, the checks, the driver (on a group of n >= 1 images: the
+// batches of fdr_api_tvfreebatch.hip run it too) and the two entry points.  Everything but
 // the data step is the periodic call's: the table kernel, the start and the spatial kernel of fdr_tv.hip with nu in the place of
 // mu, and the blur and solve chains of fdr_api_operator.hip on full planes.
 #include "fdr_host.hpp"
@@ -17,6 +18,7 @@ const char* const kPassTfData = "TVF data: s, q, r = 2s-e (window)";
 const char* const kPassTaNorm = "TVA norm+mu: res_e, res_c, S -> mu_k";
 const char* const kPassTaData = "TVA data: s, q, r = 2s-e (mu_k)";
 const char* const kPassTfSpatial = "TV spatial: shrink+dual+div (free)";
+const char* const kPassTfSpatialJoint = "TV spatial: joint shrink+dual+div (free)";  // the coupled kernel, all channels of a tile
 const char* const kPassTfSolve = "B' op cols: FFT*T*IFFT (TVF solve)";
 const char* const kPassTfX = "C op rows: IFFT (TVF x)";
 const char* const kPassTfOut = "TVF out: crop+clamp";
@@ -45,22 +47,30 @@ int tvfree_check(const fdr_plan* p, const char* fn, const float* img, int rows, 
     return FDR_OK;
 }
 
-// the new block first (nothing old is let go for it), then the periodic call's workspace for one image and the Laplacian table
-int tvfree_prepare(fdr_plan* p, const char* fn) {
-    int rc = ensure_tvfree_workspace(p, fn);
-    if (rc == FDR_OK) rc = tv_prepare(p, fn);
+// the new block first (nothing old is let go before it is had), then the periodic call's workspace for the group and the Laplacian table
+int tvfree_prepare(fdr_plan* p, const char* fn, int group) {
+    int rc = ensure_tvfree_workspace(p, fn, group);
+    if (rc == FDR_OK) rc = tv_prepare(p, fn, group);
     return rc;
 }
 
-// x, b, the duals, q, c / r and rhs (slot 0's raw plane) are full M x N planes; d and the weights are read from the caller's
+// x, b, the duals, q, c / r and rhs (slot k's raw plane) are full M x N planes; d and the weights are read from the caller's
 // windows by every data step
-int tvfree_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, int cols, int stride, const float* d_w, int wstride, float* d_out,
-                    int out_stride, const fdr_tv_free_params& prm, hipStream_t s, const TvAuto* au) {
+int tvfree_group_dev(fdr_plan* p, const char* fn, fdr_plan::Slot* const* ws, int n, const float* const* d_imgs, int rows, int cols, int stride,
+                     const float* d_w, int wstride, float* const* d_outs, int out_stride, const fdr_tv_free_params& prm, bool coupled, hipStream_t s,
+                     const TvAuto* au) {
+    if (n < 1 || n > kMaxGroup || n > p->tv_group || n > p->tf_group || (au && n > p->ta_group))
+        return fail(FDR_ERR_STATE, std::string(fn) + ": the free-boundary TV workspaces do not hold the group");
     const int M = p->M, N = p->N, iters = prm.iterations;
+    const size_t P = (size_t)M * N, step = tv_image_stride(p);
     const float nu = prm.nu > 0.f ? prm.nu : prm.rho;
-    fdr_plan::Slot* ws = &p->slots[0];
-    float *x = p->tv_x, *b = p->tv_b, *c = p->tf_c, *rhs = ws->raw;
-    const float *xc = x, *cc = c, *rhsc = rhs;
+    float *x[kMaxGroup], *b[kMaxGroup], *w0x[kMaxGroup], *w0y[kMaxGroup], *q[kMaxGroup], *c[kMaxGroup], *rhs[kMaxGroup];
+    const float *xc[kMaxGroup], *cc[kMaxGroup], *qc[kMaxGroup], *rhsc[kMaxGroup];
+    for (int k = 0; k < n; ++k) {
+        x[k] = p->tv_x + k * step; b[k] = p->tv_b + k * step; w0x[k] = p->tv_w[0][0] + k * step; w0y[k] = p->tv_w[0][1] + k * step;
+        q[k] = p->tf_q + k * P; c[k] = p->tf_c + k * P; rhs[k] = ws[k]->raw;
+        xc[k] = x[k]; cc[k] = c[k]; qc[k] = q[k]; rhsc[k] = rhs[k];
+    }
     // T is the periodic call's table for mu = nu: the cache says so, and a periodic call with another mu builds its own again
     if (iters > 0 && (p->tv_gen != p->op_gen || p->tv_mu != nu || p->tv_rho != prm.rho)) {
         ScopedPass t(p, s, kPassTfTable);
@@ -69,66 +79,78 @@ int tvfree_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, i
     }
     {
         ScopedPass t(p, s, kPassTfInit);
-        FDR_HIP(launch_tv_init_n(1, &d_img, rows, cols, stride, &x, &p->tv_w[0][0], &p->tv_w[0][1], M, N, s));
-        if (iters > 0) FDR_HIP(hipMemsetAsync(p->tf_q, 0, (size_t)M * N * sizeof(float), s));
+        FDR_HIP(launch_tv_init_n(n, d_imgs, rows, cols, stride, x, w0x, w0y, M, N, s));
+        if (iters > 0) FDR_HIP(hipMemsetAsync(p->tf_q, 0, (size_t)n * P * sizeof(float), s));  // the group's q planes lie together
     }
     int rc = FDR_OK;
     for (int it = 0; it < iters && rc == FDR_OK; ++it) {
         float* const* w = p->tv_w[it & 1];
         float* const* nw = p->tv_w[(it + 1) & 1];
-        rc = blur_window_dev_n(p, &ws, 1, &xc, M, N, N, &c, N, 0, s, M, N);  // c = blur(x)
+        rc = blur_window_dev_n(p, ws, n, xc, M, N, N, c, N, 0, s, M, N);  // c = blur(x)
         if (rc != FDR_OK) break;
-        if (au) {  // the weight of this step from the discrepancy of e = c + q, then the step with it
+        if (au) {  // the weight of this step from the discrepancy of e = c + q, image by image, then the step with it
             {
                 ScopedPass t(p, s, kPassTaNorm);
-                FDR_HIP(launch_tvauto_norm(c, p->tf_q, d_img, stride, d_w, wstride, rows, cols, M, N, p->ta_part, s));
-                FDR_HIP(launch_tvauto_mu(p->ta_part, tvauto_partials(rows, cols), au->sigma, au->tau, nu, p->ta_mu, p->ta_stat,
-                                         au->trace ? au->trace + 3 * (size_t)it : nullptr, s));
+                double* tr[kMaxGroup];
+                for (int k = 0; k < n; ++k) tr[k] = au->trace[k] ? au->trace[k] + 3 * (size_t)it : nullptr;
+                FDR_HIP(launch_tvauto_norm_n(n, cc, qc, d_imgs, stride, d_w, wstride, rows, cols, M, N, p->ta_part, s));
+                FDR_HIP(launch_tvauto_mu_n(n, p->ta_part, tvauto_partials(rows, cols), au->sigma, au->tau, nu, p->ta_mu, p->ta_stat, tr, s));
             }
             ScopedPass t(p, s, kPassTaData);
-            FDR_HIP(launch_tvauto_data(c, p->tf_q, d_img, stride, d_w, wstride, rows, cols, M, N, p->ta_mu, nu, s));  // c becomes r
+            FDR_HIP(launch_tvauto_data_n(n, c, q, d_imgs, stride, d_w, wstride, rows, cols, M, N, p->ta_mu, nu, s));  // c becomes r
         } else {
             ScopedPass t(p, s, kPassTfData);
-            FDR_HIP(launch_tvfree_data(c, p->tf_q, d_img, stride, d_w, wstride, rows, cols, M, N, prm.mu, nu, s));  // c becomes r
+            FDR_HIP(launch_tvfree_data_n(n, c, q, d_imgs, stride, d_w, wstride, rows, cols, M, N, prm.mu, nu, s));  // c becomes r
         }
-        rc = blur_window_dev_n(p, &ws, 1, &cc, M, N, N, &b, N, 1, s, M, N);  // b = blur^T(r)
+        rc = blur_window_dev_n(p, ws, n, cc, M, N, N, b, N, 1, s, M, N);  // b = blur^T(r)
         if (rc != FDR_OK) break;
         {
-            ScopedPass t(p, s, kPassTfSpatial);
-            FDR_HIP(launch_tv_spatial_n(1, x, w[0], w[1], b, nw[0], nw[1], 0, &rhs, M, N, nu, prm.rho, prm.anisotropic, 0, s));
+            ScopedPass t(p, s, coupled ? kPassTfSpatialJoint : kPassTfSpatial);
+            FDR_HIP(launch_tv_spatial_n(n, p->tv_x, w[0], w[1], p->tv_b, nw[0], nw[1], step, rhs, M, N, nu, prm.rho, prm.anisotropic, coupled, s));
         }
-        rc = op_rows_fwd_n(p, &ws, 1, &rhsc, M, N, N, s);
-        if (rc == FDR_OK) rc = op_cols_table_n(p, &ws, 1, p->tv_T, kPassTfSolve, s);
-        if (rc == FDR_OK) rc = op_rows_inv_n(p, &ws, 1, ROW_OUT_BLUR, kPassTfX, nullptr, 0, nullptr, &x, N, M, N, s);
+        rc = op_rows_fwd_n(p, ws, n, rhsc, M, N, N, s);
+        if (rc == FDR_OK) rc = op_cols_table_n(p, ws, n, p->tv_T, kPassTfSolve, s);
+        if (rc == FDR_OK) rc = op_rows_inv_n(p, ws, n, ROW_OUT_BLUR, kPassTfX, nullptr, 0, nullptr, x, N, M, N, s);
     }
     if (rc != FDR_OK) return rc;
     if (prm.norm_area == FDR_NORM_NONE) {
         ScopedPass t(p, s, kPassTfOut);
-        FDR_HIP(launch_tv_output_n(1, &xc, N, &d_out, prm.out_rows, prm.out_cols, out_stride, prm.nonneg, s));
+        FDR_HIP(launch_tv_output_n(n, xc, N, d_outs, prm.out_rows, prm.out_cols, out_stride, prm.nonneg, s));
         return FDR_OK;
     }
-    const float* fin = x;
-    if (prm.nonneg) {  // the clamped plane goes to rhs, free by now
+    const float* const* fin = xc;
+    if (prm.nonneg) {  // the clamped planes go to rhs, free by now
         ScopedPass t(p, s, kPassTfOut);
-        FDR_HIP(launch_tv_output_n(1, &xc, N, &rhs, prm.out_rows, prm.out_cols, N, 1, s));
-        fin = rhs;
+        FDR_HIP(launch_tv_output_n(n, xc, N, rhs, prm.out_rows, prm.out_cols, N, 1, s));
+        fin = rhsc;
     }
-    return normalize_window(p, fn, kPassTfNorm, fin, N, prm.out_rows, prm.out_cols, prm.norm_area, d_out, out_stride, s);
+    for (int k = 0; k < n && rc == FDR_OK; ++k)
+        rc = normalize_window(p, fn, kPassTfNorm, fin[k], N, prm.out_rows, prm.out_cols, prm.norm_area, d_outs[k], out_stride, s);
+    return rc;
 }
 
-// The first free-boundary TV call of a plan: q and c / r, two M x N planes in a block of their own.  Nothing is let go for it, so
-// on FDR_ERR_ALLOC the plan is what it was.
-int ensure_tvfree_workspace(fdr_plan* p, const char* fn) {
-    if (p->tf_block) return FDR_OK;
+int tvfree_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, int cols, int stride, const float* d_w, int wstride, float* d_out,
+                    int out_stride, const fdr_tv_free_params& prm, hipStream_t s, const TvAuto* au) {
+    fdr_plan::Slot* w = &p->slots[0];
+    return tvfree_group_dev(p, fn, &w, 1, &d_img, rows, cols, stride, d_w, wstride, &d_out, out_stride, prm, false, s, au);
+}
+
+// The first free-boundary TV call of a plan, or the first on a larger group: q and c / r, two M x N planes per image of the group
+// in a block of their own, the q planes first.  The new block is had before the old one is let go (nothing it holds outlives a
+// call), so on FDR_ERR_ALLOC the plan is what it was.
+int ensure_tvfree_workspace(fdr_plan* p, const char* fn, int group) {
+    if (p->tf_block && p->tf_group >= group) return FDR_OK;
     const size_t P = (size_t)p->M * p->N;
     float* blk = nullptr;
-    if (hipMalloc((void**)&blk, 2 * P * sizeof(float)) != hipSuccess) {
+    if (hipMalloc((void**)&blk, (size_t)group * 2 * P * sizeof(float)) != hipSuccess) {
         (void)hipGetLastError();
         return fail(FDR_ERR_ALLOC, std::string(fn) + ": hipMalloc of the free-boundary TV workspace failed");
     }
+    if (p->tf_block) (void)hipFree(p->tf_block);  // (waits for the device: nothing queued still uses it)
     p->tf_block = blk;
+    p->tf_group = group;
     p->tf_q = blk;
-    p->tf_c = blk + P;
+    p->tf_c = blk + (size_t)group * P;
     return FDR_OK;
 }
 

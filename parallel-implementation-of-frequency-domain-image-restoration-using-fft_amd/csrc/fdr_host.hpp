@@ -135,13 +135,20 @@ struct fdr_plan {
     unsigned tv_gen = 0;
     // free-boundary TV deconvolution (fdr_tv_deconv_free_f32*): beside the TV workspace for one image, which it shares, one allocation
     // of two M x N real planes made by the first such call, kept until fdr_plan_destroy: the dual q of the splitting s = blur(x) and
-    // c = blur(x), which the data step turns into r in place.  Its solve table is tv_T with tv_mu = nu.
+    // c = blur(x), which the data step turns into r in place.  Its solve table is tv_T with tv_mu = nu.  A batched call on groups of g
+    // images (fdr_tv_deconv_free_batch_f32*) grows it to 2 g planes: tf_group = the images it holds, the g planes q first (image k's
+    // at tf_q + k M N, so that one memset clears a group's), then the g planes c / r (image k's at tf_c + k M N).
     void* tf_block = nullptr;
+    int tf_group = 0;
     float *tf_q = nullptr, *tf_c = nullptr;
     // noise-constrained TV deconvolution (fdr_tv_deconv_auto_f32*): beside the workspaces of the free form, which it shares, one small
     // allocation made by the first such call, kept until fdr_plan_destroy: the 3 tvauto_max_partials(M, N) double partials of the
-    // norm kernel, the (res_c, res_e, mu_k, S) of the last step, the partials of the noise estimate and the device scalar mu_k
+    // norm kernel, the (res_c, res_e, mu_k, S) of the last step, the partials of the noise estimate and the device scalar mu_k.  A
+    // batched call on groups of g images (fdr_tv_deconv_auto_batch_f32*) grows it to g sets: ta_group = the images it holds, image k's
+    // partials at ta_part + k 3 n (n = tvauto_partials of the window), its sums at ta_stat + 4 k, its mu_k at ta_mu + k; the noise
+    // estimate runs one image at a time on the one ta_noise.
     void* ta_block = nullptr;
+    int ta_group = 0;
     double* ta_part = nullptr;
     double* ta_stat = nullptr;   // 4 doubles
     double* ta_noise = nullptr;  // kRegMaxPartials + 1 doubles
@@ -518,19 +525,42 @@ int tv_group_dev(fdr_plan* p, const char* fn, fdr_plan::Slot* const* ws, int n, 
 int tv_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, int cols, int stride, float* d_out, int out_stride,
                 const fdr_tv_params& prm, hipStream_t s);
 // ---- free-boundary TV deconvolution (fdr_api_tvfree.hip) ----
-// the two planes of the free form; FDR_ERR_ALLOC, sticky HIP error cleared, leaves the plan as it was
-int ensure_tvfree_workspace(fdr_plan* p, const char* fn);
+// the 2 group planes of the free form (grows on the first use with a larger group, the new block had before the old one is let
+// go); FDR_ERR_ALLOC, sticky HIP error cleared, leaves the plan as it was
+int ensure_tvfree_workspace(fdr_plan* p, const char* fn, int group = 1);
 // everything a free-boundary TV call refuses, before any device work; the workspaces of a call (the two planes first, then the
 // periodic call's for one image and the Laplacian table)
 int tvfree_check(const fdr_plan* p, const char* fn, const float* img, int rows, int cols, int stride, const float* weights, int wstride,
                  const float* out, int out_stride, const fdr_tv_free_params* prm);
-int tvfree_prepare(fdr_plan* p, const char* fn);
-// what the noise-constrained call (fdr_api_tvauto.hip) adds to an iteration: the noise level and tau of the discrepancy ball, and
-// where the device writes the trace (3 doubles per iteration; null: none).  The partials, mu_k and the last step's sums are the plan's.
-struct TvAuto { double sigma, tau; double* trace; };
-// the iteration on checked arguments with the workspaces made: x, b, the duals, q, c / r and rhs (slot 0's raw plane) are full M x N
-// planes; d and the weights are read from the caller's windows by every data step.  With `au` the data step takes its weight from
-// the norm and mu launches before it (prm.mu is not used) and the ta_ block must exist.
+int tvfree_prepare(fdr_plan* p, const char* fn, int group = 1);
+// what the noise-constrained calls (fdr_api_tvauto.hip, fdr_api_tvfreebatch.hip) add to an iteration: tau and, for every image of the
+// group, the noise level of its discrepancy ball and where the device writes its trace (3 doubles per iteration; null: none).  The
+// partials, mu_k and the last step's sums are the plan's.
+struct TvAuto { double tau; double sigma[kMaxGroup]; double* trace[kMaxGroup]; };
+// the workspaces of an auto call for `group` images: the free call's, then the ta_ block (ensure_tvauto_workspace: it grows as the
+// free call's does); the auto call's own arguments (sigma, tau, nu) checked and nu resolved into *fp, the free call's parameters
+struct TvAutoArgs {
+    fdr_tv_free_params fp;  // the free call's, with nu resolved; mu is a placeholder
+    double sigma, tau;
+    bool estimate;
+};
+int tvauto_check(const fdr_plan* p, const char* fn, const float* img, int rows, int cols, int stride, const float* weights, int wstride,
+                 const float* out, int out_stride, const fdr_tv_auto_params* prm, const double* d_trace, TvAutoArgs* a);
+int ensure_tvauto_workspace(fdr_plan* p, const char* fn, int group = 1);
+int tvauto_prepare(fdr_plan* p, const char* fn, int group = 1);
+// the noise level of one window as fdr_noise_sigma_f32 estimates it, on the auto block's partials: one launch, one read-back
+int tvauto_noise_dev(fdr_plan* p, const float* d_img, int rows, int cols, int stride, double* sigma, hipStream_t s);
+// The iteration on a checked group of n >= 1 images on the slots ws[0 .. n) and the planes 0 .. n - 1 of the workspaces: x, b, the
+// duals, q, c / r and rhs (slot k's raw plane) are full M x N planes; every d and the one weights window are read from the caller's
+// windows by every data step.  Per iteration one blur, the window launches, one adjoint blur, one spatial launch and the three solve
+// passes, each over the n images; then the output (and the per-image normalisation).  With `au` the data step takes image k's
+// weight from the norm and mu launches before it (prm.mu is not used) and the ta_ block must hold the group.  `coupled`: the images
+// are the channels of one picture and share the shrinkage (isotropic only); everything else stays per image.  One image, uncoupled,
+// makes the launches and the bits the single-image calls have always made.
+int tvfree_group_dev(fdr_plan* p, const char* fn, fdr_plan::Slot* const* ws, int n, const float* const* d_imgs, int rows, int cols, int stride,
+                     const float* d_w, int wstride, float* const* d_outs, int out_stride, const fdr_tv_free_params& prm, bool coupled, hipStream_t s,
+                     const TvAuto* au = nullptr);
+// one image on slot 0: the group of one
 int tvfree_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, int cols, int stride, const float* d_w, int wstride, float* d_out,
                     int out_stride, const fdr_tv_free_params& prm, hipStream_t s, const TvAuto* au = nullptr);
 

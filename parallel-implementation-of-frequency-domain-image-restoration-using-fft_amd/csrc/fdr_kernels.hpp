@@ -247,6 +247,19 @@ hipError_t launch_tv_output_n(int nimg, const float* const* x, int N, float* con
 // place with their own strides; nothing outside the window is read or written.
 hipError_t launch_tvfree_data(float* c, float* q, const float* d, int stride, const float* w, int wstride, int rows, int cols, int M, int N, float mu,
                               float nu, hipStream_t s);
+// the arithmetic of that step on one pixel, shared by every data kernel (single and group, fixed and device mu) so that all of them
+// round alike: c = blur(x) and q on entry, r = s - q and the new q on exit; m is the pixel's weight
+__device__ __forceinline__ void tvfree_data_pixel(const float mu, const float nu, const float m, const float d, float& c, float& q) {
+    const float e = c + q;
+    const float a = mu * m;
+    const float s = (a * d + nu * e) / (a + nu);
+    q = e - s;
+    c = s - q;
+}
+// the same on a group of 1 <= nimg <= kMaxGroup images in one launch (blockIdx.z = image; one image is the single-image launch): per-
+// image planes c, q and windows d (one stride, any alignment each), ONE weights window for all.  Every image gets the single kernel's bits.
+hipError_t launch_tvfree_data_n(int nimg, float* const* c, float* const* q, const float* const* d, int stride, const float* w, int wstride, int rows,
+                                int cols, int M, int N, float mu, float nu, hipStream_t s);
 // (fdr_tvauto.hip) noise-constrained TV deconvolution, on the same window, planes and caller's windows.  norm: res_e = sum w (c + q -
 // d)^2, res_c = sum w (c - d)^2 and S = sum w in double as tvauto_partials(rows, cols) per-workgroup partials each (part holds 3 n
 // doubles; no window of an M x N plan needs more than tvauto_max_partials(M, N)).  mu: one workgroup folds the partials in index
@@ -260,6 +273,16 @@ hipError_t launch_tvauto_norm(const float* c, const float* q, const float* d, in
 hipError_t launch_tvauto_mu(const double* part, int n, double sigma, double tau, float nu, float* mu, double* stat, double* trace, hipStream_t s);
 hipError_t launch_tvauto_data(float* c, float* q, const float* d, int stride, const float* w, int wstride, int rows, int cols, int M, int N,
                               const float* mu, float nu, hipStream_t s);
+// the same on a group of 1 <= nimg <= kMaxGroup images in one launch each (one image is the single-image launch), every image with
+// the bits of the single kernels: image z's partials at part + z 3 n (n = tvauto_partials(rows, cols)), its noise level sigma[z], its
+// weight at mu[z], its sums at stat + 4 z and, where trace[z] is not null, there (trace itself may be null).  The mu launch runs one
+// workgroup per image.
+hipError_t launch_tvauto_norm_n(int nimg, const float* const* c, const float* const* q, const float* const* d, int stride, const float* w, int wstride,
+                                int rows, int cols, int M, int N, double* part, hipStream_t s);
+hipError_t launch_tvauto_mu_n(int nimg, const double* part, int n, const double* sigma, double tau, float nu, float* mu, double* stat,
+                              double* const* trace, hipStream_t s);
+hipError_t launch_tvauto_data_n(int nimg, float* const* c, float* const* q, const float* const* d, int stride, const float* w, int wstride, int rows,
+                                int cols, int M, int N, const float* mu, float nu, hipStream_t s);
 
 // (fdr_motion.hip) the motion-blur estimate.  window: the Hann tables into hann[rows + cols], w . img on the window and 0 elsewhere
 // into the row-major M x N complex plane, sum |x| partials (motion_pad_partials of them) folded in a fixed order into

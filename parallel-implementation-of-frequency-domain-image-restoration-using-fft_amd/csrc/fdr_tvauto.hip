@@ -10,7 +10,10 @@
 // forms mu_k, writes the device scalar and the trace) and the data step (reads that scalar).  d and the weights are read in place
 // from the caller's strided windows, as tvfree_data_kernel reads them.  A thread adds its terms in one order whether it loads them
 // as one 16-byte request or as four scalars, so the sums do not depend on the alignment of the caller's windows.  No atomics: every
-// sum runs in a fixed order.
+// sum runs in a fixed order.  Each kernel has a group form (fdr_tv_deconv_auto_batch_f32*) for up to kMaxGroup images in one launch:
+// the window kernels with blockIdx.z as the image, the fold with one workgroup per image; image z has its own partials, noise
+// level, mu, sums and trace slot, and the single and the group kernel instantiate one device function, so an image has the same
+// sums and bits in a group as alone.
 #include "fdr_kernels.hpp"
 
 #include <cstdint>
@@ -57,10 +60,9 @@ __device__ __forceinline__ void ta_load_sum4(const float* row, int j, int cols, 
 // workgroup's sums go to part[b], part[n + b], part[2 n + b] (res_e, res_c, S), b = blockIdx.y gridDim.x + blockIdx.x,
 // n = gridDim.x gridDim.y.
 template <bool WEIGHTS>
-__global__ __launch_bounds__(kTaThreads) void tvauto_norm_kernel(const float* __restrict__ c, const float* __restrict__ q, const float* __restrict__ d,
-                                                                 const int stride, const float* __restrict__ w, const int wstride, const int rows,
-                                                                 const int cols, const int N, const int dvec, const int wvec,
-                                                                 double* __restrict__ part) {
+__device__ __forceinline__ void tvauto_norm_block(const float* __restrict__ c, const float* __restrict__ q, const float* __restrict__ d,
+                                                  const int stride, const float* __restrict__ w, const int wstride, const int rows, const int cols,
+                                                  const int N, const int dvec, const int wvec, double* __restrict__ part) {
     __shared__ double red[3][kTaThreads / 64];
     const int j = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
     const int r0 = blockIdx.y * (blockDim.y * kTaRows) + threadIdx.y;
@@ -115,12 +117,42 @@ __global__ __launch_bounds__(kTaThreads) void tvauto_norm_kernel(const float* __
         part[2 * n + b] = ((red[2][0] + red[2][1]) + red[2][2]) + red[2][3];
     }
 }
+template <bool WEIGHTS>
+__global__ __launch_bounds__(kTaThreads) void tvauto_norm_kernel(const float* __restrict__ c, const float* __restrict__ q, const float* __restrict__ d,
+                                                                 const int stride, const float* __restrict__ w, const int wstride, const int rows,
+                                                                 const int cols, const int N, const int dvec, const int wvec,
+                                                                 double* __restrict__ part) {
+    tvauto_norm_block<WEIGHTS>(c, q, d, stride, w, wstride, rows, cols, N, dvec, wvec, part);
+}
+
+// entry i (uniform over the workgroup) of a per-image array of a by-value kernel argument: pick_image's select chain on scalars,
+// written on the member itself (a dynamic index, or pick_image's array reference, sends the argument block to scratch memory)
+#define FDR_TA_PICK(arr, i) \
+    ((i) < 4 ? ((i) == 0 ? arr[0] : (i) == 1 ? arr[1] : (i) == 2 ? arr[2] : arr[3]) : ((i) == 4 ? arr[4] : (i) == 5 ? arr[5] : (i) == 6 ? arr[6] : arr[7]))
+static_assert(kMaxGroup == 8, "select chain written for 8 entries");
+
+// the group forms of the window kernels: image blockIdx.z on its planes and its window, the weights window shared; bit z of dvec
+// says whether image z's window takes 16-byte loads.  The workgroup's place in the image is (blockIdx.x, blockIdx.y), as in the
+// single kernels, so image z's partials, written to part + z 3 n, are those of its single launch.
+struct TvAutoPlanes {
+    float* c[kMaxGroup];
+    float* q[kMaxGroup];
+    const float* d[kMaxGroup];
+};
+template <bool WEIGHTS>
+__global__ __launch_bounds__(kTaThreads) void tvauto_norm_group_kernel(const TvAutoPlanes pl, const int stride, const float* __restrict__ w,
+                                                                       const int wstride, const int rows, const int cols, const int N, const int dvec,
+                                                                       const int wvec, double* __restrict__ part) {
+    const int z = blockIdx.z;
+    const size_t n = (size_t)gridDim.x * gridDim.y;
+    tvauto_norm_block<WEIGHTS>(FDR_TA_PICK(pl.c, z), FDR_TA_PICK(pl.q, z), FDR_TA_PICK(pl.d, z), stride, w, wstride, rows, cols, N, (dvec >> z) & 1,
+                               wvec, part + (size_t)z * 3 * n);
+}
 
 // one workgroup: res_e, res_c and S from the 3 n partials (thread t adds t, t + 256, ... in order, then a fixed tree), c2 and mu_k in
 // double, mu_k rounded to float once into *mu; stat = (res_c, res_e, mu_k, S), and the first three to `trace` when that is not null
-__global__ __launch_bounds__(kTaThreads) void tvauto_mu_kernel(const double* __restrict__ part, const int n, const double sigma, const double tau,
-                                                               const float nu, float* __restrict__ mu, double* __restrict__ stat,
-                                                               double* __restrict__ trace) {
+__device__ __forceinline__ void tvauto_mu_fold(const double* __restrict__ part, const int n, const double sigma, const double tau, const float nu,
+                                               float* __restrict__ mu, double* __restrict__ stat, double* __restrict__ trace) {
     __shared__ double red[3][kTaThreads];
     double a = 0.0, b = 0.0, m = 0.0;
     // kTaFold partials of each sum per round, loaded together and added in index order: one workgroup is bound by the latency of
@@ -173,14 +205,28 @@ __global__ __launch_bounds__(kTaThreads) void tvauto_mu_kernel(const double* __r
         if (trace) { trace[0] = res_c; trace[1] = res_e; trace[2] = (double)v; }
     }
 }
+__global__ __launch_bounds__(kTaThreads) void tvauto_mu_kernel(const double* __restrict__ part, const int n, const double sigma, const double tau,
+                                                               const float nu, float* __restrict__ mu, double* __restrict__ stat,
+                                                               double* __restrict__ trace) {
+    tvauto_mu_fold(part, n, sigma, tau, nu, mu, stat, trace);
+}
+// the group form: workgroup z folds image z's partials with image z's noise level into mu[z], stat + 4 z and image z's trace slot
+struct TvAutoLevels {
+    double sigma[kMaxGroup];
+    double* trace[kMaxGroup];  // null: no trace
+};
+__global__ __launch_bounds__(kTaThreads) void tvauto_mu_group_kernel(const double* __restrict__ part, const int n, const TvAutoLevels lv, const double tau,
+                                                                     const float nu, float* __restrict__ mu, double* __restrict__ stat) {
+    const int z = blockIdx.x;
+    tvauto_mu_fold(part + (size_t)z * 3 * n, n, FDR_TA_PICK(lv.sigma, z), tau, nu, mu + z, stat + 4 * z, FDR_TA_PICK(lv.trace, z));
+}
 
 // tvfree_data_kernel's step with mu read from the device scalar: a thread owns four consecutive pixels of one window row; in the
 // group that straddles column `cols` the pixels beyond it keep the c and q they were loaded with
 template <bool WEIGHTS>
-__global__ __launch_bounds__(kTaThreads) void tvauto_data_kernel(float* __restrict__ c, float* __restrict__ q, const float* __restrict__ d, const int stride,
-                                                                 const float* __restrict__ w, const int wstride, const int rows, const int cols,
-                                                                 const int N, const float* __restrict__ mu_dev, const float nu, const int dvec,
-                                                                 const int wvec) {
+__device__ __forceinline__ void tvauto_data_group4(float* __restrict__ c, float* __restrict__ q, const float* __restrict__ d, const int stride,
+                                                   const float* __restrict__ w, const int wstride, const int rows, const int cols, const int N,
+                                                   const float* __restrict__ mu_dev, const float nu, const int dvec, const int wvec) {
     const int j = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
     const int i = blockIdx.y * blockDim.y + threadIdx.y;
     if (i >= rows || j >= cols) return;
@@ -193,16 +239,26 @@ __global__ __launch_bounds__(kTaThreads) void tvauto_data_kernel(float* __restri
     if (WEIGHTS) ta_load_window4(w + (size_t)i * wstride + j, j, cols, wvec != 0, 1.f, mm);
 #pragma unroll
     for (int l = 0; l < 4; ++l) {
-        if (j + l < cols) {
-            const float e = cc[l] + qq[l];
-            const float a = mu * mm[l];
-            const float s = (a * dd[l] + nu * e) / (a + nu);
-            qq[l] = e - s;
-            cc[l] = s - qq[l];
-        }
+        if (j + l < cols) tvfree_data_pixel(mu, nu, mm[l], dd[l], cc[l], qq[l]);
     }
     *reinterpret_cast<float4*>(q + at) = make_float4(qq[0], qq[1], qq[2], qq[3]);
     *reinterpret_cast<float4*>(c + at) = make_float4(cc[0], cc[1], cc[2], cc[3]);
+}
+template <bool WEIGHTS>
+__global__ __launch_bounds__(kTaThreads) void tvauto_data_kernel(float* __restrict__ c, float* __restrict__ q, const float* __restrict__ d, const int stride,
+                                                                 const float* __restrict__ w, const int wstride, const int rows, const int cols,
+                                                                 const int N, const float* __restrict__ mu_dev, const float nu, const int dvec,
+                                                                 const int wvec) {
+    tvauto_data_group4<WEIGHTS>(c, q, d, stride, w, wstride, rows, cols, N, mu_dev, nu, dvec, wvec);
+}
+// the group form: image blockIdx.z with its own weight mu_dev[z]
+template <bool WEIGHTS>
+__global__ __launch_bounds__(kTaThreads) void tvauto_data_group_kernel(const TvAutoPlanes pl, const int stride, const float* __restrict__ w,
+                                                                       const int wstride, const int rows, const int cols, const int N,
+                                                                       const float* __restrict__ mu_dev, const float nu, const int dvec, const int wvec) {
+    const int z = blockIdx.z;
+    tvauto_data_group4<WEIGHTS>(FDR_TA_PICK(pl.c, z), FDR_TA_PICK(pl.q, z), FDR_TA_PICK(pl.d, z), stride, w, wstride, rows, cols, N, mu_dev + z, nu,
+                                (dvec >> z) & 1, wvec);
 }
 
 namespace {
@@ -258,6 +314,71 @@ hipError_t launch_tvauto_data(float* c, float* q, const float* d, int stride, co
     const int wvec = w && ((uintptr_t)w & 15) == 0 && (wstride & 3) == 0;
     if (w) hipLaunchKernelGGL((tvauto_data_kernel<true>), grid, dim3(tx, ty), 0, s, c, q, d, stride, w, wstride, rows, cols, N, mu, nu, dvec, wvec);
     else hipLaunchKernelGGL((tvauto_data_kernel<false>), grid, dim3(tx, ty), 0, s, c, q, d, stride, w, wstride, rows, cols, N, mu, nu, dvec, wvec);
+    return hipGetLastError();
+}
+
+namespace {
+// the planes of a group for a kernel argument (entries past nimg repeat image 0) and the alignment bits of its windows
+bool ta_group_planes(int nimg, float* const* c, float* const* q, const float* const* d, int stride, TvAutoPlanes* pl, int* dvec) {
+    *dvec = 0;
+    for (int k = 0; k < kMaxGroup; ++k) {
+        const int i = k < nimg ? k : 0;
+        if (!c[i] || !q[i] || !d[i]) return false;
+        pl->c[k] = c[i]; pl->q[k] = q[i]; pl->d[k] = d[i];
+        if (((uintptr_t)d[i] & 15) == 0 && (stride & 3) == 0) *dvec |= 1 << k;
+    }
+    return true;
+}
+}  // namespace
+
+hipError_t launch_tvauto_norm_n(int nimg, const float* const* c, const float* const* q, const float* const* d, int stride, const float* w, int wstride,
+                                int rows, int cols, int M, int N, double* part, hipStream_t s) {
+    if (nimg < 1 || nimg > kMaxGroup) return hipErrorInvalidValue;
+    if (nimg == 1) return launch_tvauto_norm(c[0], q[0], d[0], stride, w, wstride, rows, cols, M, N, part, s);
+    if (!ta_window_ok(c[0], q[0], d[0], stride, w, wstride, rows, cols, M, N) || !part) return hipErrorInvalidValue;
+    TvAutoPlanes pl;
+    int dvec;
+    if (!ta_group_planes(nimg, const_cast<float* const*>(c), const_cast<float* const*>(q), d, stride, &pl, &dvec)) return hipErrorInvalidValue;
+    int tx, ty;
+    ta_block(cols, &tx, &ty);
+    const int groups = (cols + 3) / 4;
+    const dim3 grid((unsigned)((groups + tx - 1) / tx), (unsigned)((rows + ty * kTaRows - 1) / (ty * kTaRows)), (unsigned)nimg);
+    const int wvec = w && ((uintptr_t)w & 15) == 0 && (wstride & 3) == 0;
+    if (w) hipLaunchKernelGGL((tvauto_norm_group_kernel<true>), grid, dim3(tx, ty), 0, s, pl, stride, w, wstride, rows, cols, N, dvec, wvec, part);
+    else hipLaunchKernelGGL((tvauto_norm_group_kernel<false>), grid, dim3(tx, ty), 0, s, pl, stride, w, wstride, rows, cols, N, dvec, wvec, part);
+    return hipGetLastError();
+}
+
+hipError_t launch_tvauto_mu_n(int nimg, const double* part, int n, const double* sigma, double tau, float nu, float* mu, double* stat,
+                              double* const* trace, hipStream_t s) {
+    if (nimg < 1 || nimg > kMaxGroup || !sigma) return hipErrorInvalidValue;
+    if (nimg == 1) return launch_tvauto_mu(part, n, sigma[0], tau, nu, mu, stat, trace ? trace[0] : nullptr, s);
+    if (n <= 0 || !part || !mu || !stat) return hipErrorInvalidValue;
+    TvAutoLevels lv;
+    for (int k = 0; k < kMaxGroup; ++k) {
+        const int i = k < nimg ? k : 0;
+        lv.sigma[k] = sigma[i];
+        lv.trace[k] = trace ? trace[i] : nullptr;
+    }
+    hipLaunchKernelGGL(tvauto_mu_group_kernel, dim3((unsigned)nimg), dim3(kTaThreads), 0, s, part, n, lv, tau, nu, mu, stat);
+    return hipGetLastError();
+}
+
+hipError_t launch_tvauto_data_n(int nimg, float* const* c, float* const* q, const float* const* d, int stride, const float* w, int wstride, int rows,
+                                int cols, int M, int N, const float* mu, float nu, hipStream_t s) {
+    if (nimg < 1 || nimg > kMaxGroup) return hipErrorInvalidValue;
+    if (nimg == 1) return launch_tvauto_data(c[0], q[0], d[0], stride, w, wstride, rows, cols, M, N, mu, nu, s);
+    if (!ta_window_ok(c[0], q[0], d[0], stride, w, wstride, rows, cols, M, N) || !mu) return hipErrorInvalidValue;
+    TvAutoPlanes pl;
+    int dvec;
+    if (!ta_group_planes(nimg, c, q, d, stride, &pl, &dvec)) return hipErrorInvalidValue;
+    int tx, ty;
+    ta_block(cols, &tx, &ty);
+    const int groups = (cols + 3) / 4;
+    const dim3 grid((unsigned)((groups + tx - 1) / tx), (unsigned)((rows + ty - 1) / ty), (unsigned)nimg);
+    const int wvec = w && ((uintptr_t)w & 15) == 0 && (wstride & 3) == 0;
+    if (w) hipLaunchKernelGGL((tvauto_data_group_kernel<true>), grid, dim3(tx, ty), 0, s, pl, stride, w, wstride, rows, cols, N, mu, nu, dvec, wvec);
+    else hipLaunchKernelGGL((tvauto_data_group_kernel<false>), grid, dim3(tx, ty), 0, s, pl, stride, w, wstride, rows, cols, N, mu, nu, dvec, wvec);
     return hipGetLastError();
 }
 

@@ -6,6 +6,9 @@
 // with c = blur(x) on entry and r in its place on exit.  m is the weights on the window and 0 outside it, where the step is
 // s = e, q = 0, r = c: nothing to compute and nothing to store, so the launch covers the window alone and q, zero outside the
 // window since the start, is never touched there.  d and the weights are read in place from the caller's strided windows.
+// The group form (fdr_tv_deconv_free_batch_f32*) makes the step of up to kMaxGroup images in one launch, blockIdx.z the image, with
+// one weights window for all; the single kernel and the group kernel instantiate one device function, and every data kernel of the
+// library computes a pixel by tvfree_data_pixel (fdr_kernels.hpp), so an image has the same bits in a group as alone.
 #include "fdr_kernels.hpp"
 
 namespace fdr {
@@ -15,9 +18,9 @@ namespace fdr {
 // window's base and stride keep every row 16-byte aligned (dvec / wvec, decided on the host), scalar loads otherwise.  In the
 // group that straddles column `cols` the pixels beyond it keep the c and q they were loaded with.
 template <bool WEIGHTS>
-__global__ __launch_bounds__(256) void tvfree_data_kernel(float* __restrict__ c, float* __restrict__ q, const float* __restrict__ d, const int stride,
-                                                          const float* __restrict__ w, const int wstride, const int rows, const int cols,
-                                                          const int N, const float mu, const float nu, const int dvec, const int wvec) {
+__device__ __forceinline__ void tvfree_data_group4(float* __restrict__ c, float* __restrict__ q, const float* __restrict__ d, const int stride,
+                                                   const float* __restrict__ w, const int wstride, const int rows, const int cols, const int N,
+                                                   const float mu, const float nu, const int dvec, const int wvec) {
     const int j = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
     const int i = blockIdx.y * blockDim.y + threadIdx.y;
     if (i >= rows || j >= cols) return;
@@ -48,16 +51,38 @@ __global__ __launch_bounds__(256) void tvfree_data_kernel(float* __restrict__ c,
     }
 #pragma unroll
     for (int l = 0; l < 4; ++l) {
-        if (j + l < cols) {
-            const float e = cc[l] + qq[l];
-            const float a = mu * mm[l];
-            const float s = (a * dd[l] + nu * e) / (a + nu);
-            qq[l] = e - s;
-            cc[l] = s - qq[l];
-        }
+        if (j + l < cols) tvfree_data_pixel(mu, nu, mm[l], dd[l], cc[l], qq[l]);
     }
     *reinterpret_cast<float4*>(q + at) = make_float4(qq[0], qq[1], qq[2], qq[3]);
     *reinterpret_cast<float4*>(c + at) = make_float4(cc[0], cc[1], cc[2], cc[3]);
+}
+template <bool WEIGHTS>
+__global__ __launch_bounds__(256) void tvfree_data_kernel(float* __restrict__ c, float* __restrict__ q, const float* __restrict__ d, const int stride,
+                                                          const float* __restrict__ w, const int wstride, const int rows, const int cols,
+                                                          const int N, const float mu, const float nu, const int dvec, const int wvec) {
+    tvfree_data_group4<WEIGHTS>(c, q, d, stride, w, wstride, rows, cols, N, mu, nu, dvec, wvec);
+}
+
+// entry i (uniform over the workgroup) of a per-image pointer array of a by-value kernel argument: pick_image's select chain on
+// scalars, written on the member itself (a dynamic index, or pick_image's array reference, sends the argument block to scratch memory)
+#define FDR_TF_PICK(arr, i) \
+    ((i) < 4 ? ((i) == 0 ? arr[0] : (i) == 1 ? arr[1] : (i) == 2 ? arr[2] : arr[3]) : ((i) == 4 ? arr[4] : (i) == 5 ? arr[5] : (i) == 6 ? arr[6] : arr[7]))
+static_assert(kMaxGroup == 8, "select chain written for 8 entries");
+
+// the group form: image blockIdx.z on its planes and its window, the weights window shared.  Bit z of dvec says whether image z's
+// window takes 16-byte loads: the images of a batch with an odd pitch differ in alignment.
+struct TvFreePlanes {
+    float* c[kMaxGroup];
+    float* q[kMaxGroup];
+    const float* d[kMaxGroup];
+};
+template <bool WEIGHTS>
+__global__ __launch_bounds__(256) void tvfree_data_group_kernel(const TvFreePlanes pl, const int stride, const float* __restrict__ w, const int wstride,
+                                                                const int rows, const int cols, const int N, const float mu, const float nu,
+                                                                const int dvec, const int wvec) {
+    const int z = blockIdx.z;
+    tvfree_data_group4<WEIGHTS>(FDR_TF_PICK(pl.c, z), FDR_TF_PICK(pl.q, z), FDR_TF_PICK(pl.d, z), stride, w, wstride, rows, cols, N, mu, nu,
+                                (dvec >> z) & 1, wvec);
 }
 
 // rows x cols must lie within the M x N planes c and q (N a multiple of 4); d and w (null: weights of 1) are rows x cols windows
@@ -74,6 +99,30 @@ hipError_t launch_tvfree_data(float* c, float* q, const float* d, int stride, co
         hipLaunchKernelGGL((tvfree_data_kernel<true>), grid, dim3(tx, ty), 0, s, c, q, d, stride, w, wstride, rows, cols, N, mu, nu, dvec, wvec);
     else
         hipLaunchKernelGGL((tvfree_data_kernel<false>), grid, dim3(tx, ty), 0, s, c, q, d, stride, w, wstride, rows, cols, N, mu, nu, dvec, wvec);
+    return hipGetLastError();
+}
+
+hipError_t launch_tvfree_data_n(int nimg, float* const* c, float* const* q, const float* const* d, int stride, const float* w, int wstride, int rows,
+                                int cols, int M, int N, float mu, float nu, hipStream_t s) {
+    if (nimg < 1 || nimg > kMaxGroup) return hipErrorInvalidValue;
+    if (nimg == 1) return launch_tvfree_data(c[0], q[0], d[0], stride, w, wstride, rows, cols, M, N, mu, nu, s);
+    if (rows < 1 || cols < 1 || rows > M || cols > N || (N & 3) || stride < cols || (w && wstride < cols)) return hipErrorInvalidValue;
+    TvFreePlanes pl;
+    int dvec = 0;
+    for (int k = 0; k < kMaxGroup; ++k) {
+        const int i = k < nimg ? k : 0;
+        if (!c[i] || !q[i] || !d[i]) return hipErrorInvalidValue;
+        pl.c[k] = c[i]; pl.q[k] = q[i]; pl.d[k] = d[i];
+        if (((uintptr_t)d[i] & 15) == 0 && (stride & 3) == 0) dvec |= 1 << k;
+    }
+    const int groups = (cols + 3) / 4;
+    const int tx = groups <= 64 ? 64 : groups <= 128 ? 128 : 256, ty = 256 / tx;
+    const dim3 grid((unsigned)((groups + tx - 1) / tx), (unsigned)((rows + ty - 1) / ty), (unsigned)nimg);
+    const int wvec = w && ((uintptr_t)w & 15) == 0 && (wstride & 3) == 0;
+    if (w)
+        hipLaunchKernelGGL((tvfree_data_group_kernel<true>), grid, dim3(tx, ty), 0, s, pl, stride, w, wstride, rows, cols, N, mu, nu, dvec, wvec);
+    else
+        hipLaunchKernelGGL((tvfree_data_group_kernel<false>), grid, dim3(tx, ty), 0, s, pl, stride, w, wstride, rows, cols, N, mu, nu, dvec, wvec);
     return hipGetLastError();
 }
 
