@@ -554,8 +554,8 @@ int fdr_psf_gaussian_dev(int device, int size, double sigma, float* d_out, void*
  *    4 lambda max(u) the explicit step oscillates at the scale of eps in flat areas: a call still repeats bit for bit, but results
  *    then depend on the arithmetic -- a float32 and a float64 run of the same formulas, lambda = 0.01 and eps = 1e-3 on a 256^2 picture
  *    scaled to 1, agree to 9e-6 after 3 steps, 1e-3 after 10 and 2.8e-2 in max-norm after 30 (rms 6.4e-4, under 0.01 dB of PSNR), while
- *    with eps = 0.05 they agree to 8e-7 through 100 steps.  And there is no accelerated, data-stopped, blind or batched form, no anisotropic prior and no
- *    automatic lambda.
+ *    with eps = 0.05 they agree to 8e-7 through 100 steps.  And there is no accelerated, data-stopped or blind form, no anisotropic prior and no
+ *    automatic lambda; the batched form is fdr_richardson_lucy_tv_batch_f32* below.
  *    Plans, refusals, overlap rules and phases are those of the underlying form (cov_sigma, out_rows and out_cols are the sigma,
  *    out_rows and out_cols of fdr_rlfree_params; the plain form takes no weights and out_rows = out_cols = 0 or rows, cols).
  *    FDR_ERR_ARG also for a null params pointer, a lambda that is negative, not finite or above FDR_RLTV_MAX_LAMBDA and an eps that is
@@ -586,6 +586,52 @@ int fdr_richardson_lucy_tv_f32_dev(fdr_plan* plan, const float* d_img, int rows,
                                    float* d_out, int out_stride, const fdr_rl_tv_params* params, void* stream);
 int fdr_rl_tv_factor_f32_dev(int device, const float* d_u, int rows, int cols, int stride, const float* d_w, float lambda, float eps,
                              float* d_out, int out_stride, void* stream);
+
+/* -- Richardson-Lucy with the TV prior on several images per launch, and with the channels of a colour picture coupled.  Arguments,
+ *    launch groups, forms and refusals are those of fdr_richardson_lucy_batch_f32* (image i at d_imgs + i img_pitch, written at
+ *    d_out + i out_pitch; groups of `group` images of fdr_plan_set_batching, each run to completion on the caller's stream; in the
+ *    free form ONE weights plane and one coverage per call), the prior's two numbers those of fdr_richardson_lucy_tv_f32*.  Per
+ *    group and iteration the call makes ONE factor launch and the six passes of the form; image k's factor plane is the second
+ *    source of its weighted update.
+ *      couple = FDR_TV_COUPLE_NONE      every image on its own: it comes out bit for bit as fdr_richardson_lucy_tv_f32_dev gives it
+ *                              on the same plan, for every group size, tail and layout; group = 1 is the loop of those calls.
+ *      couple = FDR_TV_COUPLE_CHANNELS  vectorial TV: the images are the channels of one picture and share the norm of the prior,
+ *                                  m^2 = eps^2 + sum_c (gx_c^2 + gy_c^2)  (c = 0, 1, .. in this order),  p_c = grad u_c / m,
+ *                                  g_c = 1 - lambda div p_c,  factor_c = w / g_c,
+ *                              so an edge falls in the same place in every channel.  m is no smaller than a channel's own, so
+ *                              |div p_c| <= 2 + sqrt(2) and g >= 0.57 hold as before.  The whole batch has to be one launch group:
+ *                              FDR_ERR_ARG for count > group.  One channel gives the bits of the uncoupled call.
+ *    lambda = 0 IS fdr_richardson_lucy_batch_f32_dev (same bits, nothing else launched or allocated; couple is still checked).
+ *    FDR_ERR_ARG also for an unknown `couple`; every refusal comes before any device work and leaves the plan usable.  The first
+ *    call with lambda > 0 and a group g > 1 grows the prior's workspace from 2 to 2 g planes of M x N floats (plain form: image k's
+ *    dense estimate beside its factor); the new block is had before the old one is let go, so FDR_ERR_ALLOC leaves the plan and the
+ *    old workspace usable.  After it the _dev form allocates nothing and stays asynchronous on `stream`.  The coupled factor launch
+ *    reads u twice: 12 bytes per pixel of the domain against 8 (16 against 12 with w).
+ *      fdr_rl_tv_factor_group_f32_dev  the factor alone for `count` (1 .. 8) planes, plane k at d_u + k u_pitch -> d_out + k out_pitch,
+ *                              one d_w (NULL = 1) for all, coupled or not: the checks of fdr_rl_tv_factor_f32_dev, and FDR_ERR_ARG for
+ *                              a count outside 1 .. 8, an unknown `couple` and an output that overlaps an input anywhere in the span
+ *                              of the planes.  Uncoupled, plane k has the bits of fdr_rl_tv_factor_f32_dev on it.
+ *    The accelerated, data-stopped and blind forms with the prior, per-image weights, mixed-radix and full-spectrum plans have no
+ *    batched form.                                                                                        */
+typedef struct fdr_rl_tv_batch_params {
+    int iterations;    /* >= 0 */
+    int free_boundary; /* 0: the plain form; else the free-boundary, weighted form */
+    float lambda;      /* weight of the prior, 0 .. FDR_RLTV_MAX_LAMBDA */
+    float eps;         /* smoothing of |grad u|, > 0; 0 = FDR_RLTV_EPS */
+    int norm_area;     /* FDR_NORM_NONE / FDR_NORM_CROPPED / FDR_NORM_PADDED, per image */
+    float cov_sigma;   /* free form: as fdr_rlfree_params.sigma */
+    int out_rows;      /* free form: as fdr_rlfree_params; plain form: 0 or rows */
+    int out_cols;      /* free form: as fdr_rlfree_params; plain form: 0 or cols */
+    int couple;        /* FDR_TV_COUPLE_NONE / FDR_TV_COUPLE_CHANNELS */
+} fdr_rl_tv_batch_params;
+int fdr_richardson_lucy_tv_batch_f32_dev(fdr_plan* plan, const float* d_imgs, size_t img_pitch, int count, int rows, int cols, int stride,
+                                         const float* d_weights, int wstride, float* d_out, size_t out_pitch, int out_stride,
+                                         const fdr_rl_tv_batch_params* params, void* stream);
+int fdr_richardson_lucy_tv_batch_f32(fdr_plan* plan, const float* imgs_host, size_t img_pitch, int count, int rows, int cols, int stride,
+                                     const float* weights_host, int wstride, float* out_host, size_t out_pitch, int out_stride,
+                                     const fdr_rl_tv_batch_params* params);
+int fdr_rl_tv_factor_group_f32_dev(int device, const float* d_u, size_t u_pitch, int count, int rows, int cols, int stride, const float* d_w,
+                                   float lambda, float eps, int couple, float* d_out, size_t out_pitch, int out_stride, void* stream);
 
 /* -- total-variation (TV) regularised deconvolution by ADMM / split Bregman (Rudin-Osher-Fatemi 1992; Wang-Yang-Yin-Zhang 2008
  *    "FTVd"; Goldstein-Osher 2009): the edge-preserving restoration beside the linear filters and RL.  It uses the operator PSF of

@@ -307,12 +307,38 @@ inline void richardsonLucyFree_RGB(std::vector<Mat>& channels, const Mat& psf, i
                                    bool accelerate = false) {
     richardsonLucyFree_RGB(channels, psf, iterations, weights, defaults(), FDR_RL_SIGMA, accelerate);
 }
-// Richardson-Lucy with a total-variation prior (fdr_richardson_lucy_tv_f32, include/fdr.h) of every channel, in place, channel by
-// channel: lambda in 0 .. FDR_RLTV_MAX_LAMBDA weighs the prior (0 is the unregularised form), eps (the units of the picture; 0 =
+// The channels of richardsonLucyTV_RGB as ONE batched call (fdr_richardson_lucy_tv_batch_f32, include/fdr.h): a launch group of
+// channels.size() images (at most 8) runs the factor launch and every pass of the iteration once for all of them.  False (nothing
+// done) when the channels differ in size or type or are more than 8: the caller then loops.
+inline bool rltv_channels_batched(fdr_plan* plan, std::vector<Mat>& channels, const float* weights, fdr_rl_tv_batch_params prm) {
+    const int rows = channels[0].rows, cols = channels[0].cols, count = (int)channels.size();
+    if (count > 8) return false;
+    for (const Mat& c : channels)
+        if (c.rows != rows || c.cols != cols || c.type() != CV_32F) return false;
+    const size_t px = (size_t)rows * cols;
+    std::vector<float> in(px * count), out(px * count);
+    for (int i = 0; i < count; ++i)
+        for (int r = 0; r < rows; ++r) std::copy(channels[i].ptr<float>(r), channels[i].ptr<float>(r) + cols, in.begin() + i * px + (size_t)r * cols);
+    prm.out_rows = rows; prm.out_cols = cols;
+    FDR_CHECK(fdr_plan_set_batching(plan, 1, count));
+    FDR_CHECK(fdr_richardson_lucy_tv_batch_f32(plan, in.data(), px, count, rows, cols, cols, weights, cols, out.data(), px, cols, &prm));
+    FDR_CHECK(fdr_plan_set_batching(plan, 1, 1));  // the cached plan goes back as it came
+    for (int i = 0; i < count; ++i) {
+        Mat o(rows, cols, CV_32F);
+        std::copy(out.begin() + i * px, out.begin() + (i + 1) * px, o.ptr<float>(0));
+        channels[i] = o;
+    }
+    return true;
+}
+// Richardson-Lucy with a total-variation prior (fdr_richardson_lucy_tv_f32, include/fdr.h) of every channel, in place:
+// lambda in 0 .. FDR_RLTV_MAX_LAMBDA weighs the prior (0 is the unregularised form), eps (the units of the picture; 0 =
 // FDR_RLTV_EPS) smooths |grad u|.  free_boundary: on the plan and with the weights and sigma of richardsonLucyFree_RGB, for a picture
 // that is a crop; otherwise on the plan of richardsonLucy_RGB, and `weights` must be empty.  Each channel normalised by o.norm_area.
+// The channels go through one batched call (rltv_channels_batched) with the bits of the per-channel calls; channels of different
+// sizes or types run one by one.  coupled: the channels share one vectorial TV prior (FDR_TV_COUPLE_CHANNELS: an edge falls in the
+// same place in every channel); it needs channels of one size and type, at most 8.
 inline void richardsonLucyTV_RGB(std::vector<Mat>& channels, const Mat& psf, int iterations, float lambda, float eps, bool free_boundary,
-                                 const Mat& weights, const Options& o, float sigma = FDR_RL_SIGMA) {
+                                 const Mat& weights, const Options& o, float sigma = FDR_RL_SIGMA, bool coupled = false) {
     if (channels.empty()) return;
     const int rows = channels[0].rows, cols = channels[0].cols;
     if (!weights.empty() && (!free_boundary || weights.rows != rows || weights.cols != cols || weights.type() != CV_32F)) {
@@ -327,6 +353,14 @@ inline void richardsonLucyTV_RGB(std::vector<Mat>& channels, const Mat& psf, int
     Mat psfc = psf.isContinuous() ? psf : psf.clone();
     FDR_CHECK(fdr_set_operator_psf(plan, psfc.ptr<float>(0), psf.rows, psf.cols, psf.cols));
     Mat w = weights.empty() || weights.isContinuous() ? weights : weights.clone();
+    if (rltv_channels_batched(plan, channels, w.empty() ? nullptr : w.ptr<float>(0),
+                              fdr_rl_tv_batch_params{iterations, free_boundary ? 1 : 0, lambda, eps, o.norm_area, sigma, rows, cols,
+                                                     coupled ? FDR_TV_COUPLE_CHANNELS : FDR_TV_COUPLE_NONE}))
+        return;
+    if (coupled) {
+        std::cerr << "richardsonLucyTV_RGB: coupled channels must have one size, be CV_32F and be at most 8\n";
+        exit(1);
+    }
     for (Mat& c : channels) {
         Mat src = c.isContinuous() ? c : c.clone();
         Mat out(c.rows, c.cols, CV_32F);
@@ -337,8 +371,8 @@ inline void richardsonLucyTV_RGB(std::vector<Mat>& channels, const Mat& psf, int
     }
 }
 inline void richardsonLucyTV_RGB(std::vector<Mat>& channels, const Mat& psf, int iterations, float lambda, float eps = 0.f,
-                                 bool free_boundary = false, const Mat& weights = Mat()) {
-    richardsonLucyTV_RGB(channels, psf, iterations, lambda, eps, free_boundary, weights, defaults(), FDR_RL_SIGMA);
+                                 bool free_boundary = false, const Mat& weights = Mat(), bool coupled = false) {
+    richardsonLucyTV_RGB(channels, psf, iterations, lambda, eps, free_boundary, weights, defaults(), FDR_RL_SIGMA, coupled);
 }
 // What richardsonLucyBlind_RGB takes beside the picture and the start PSF: the form, the steps the PSF is held for, and the weights and
 // coverage threshold of the free form.

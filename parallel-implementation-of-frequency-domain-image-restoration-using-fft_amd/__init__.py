@@ -140,6 +140,11 @@ class RlTvParams(ctypes.Structure):
                 ("norm_area", ctypes.c_int), ("cov_sigma", ctypes.c_float), ("out_rows", ctypes.c_int), ("out_cols", ctypes.c_int)]
 
 
+class RlTvBatchParams(ctypes.Structure):
+    """fdr_rl_tv_batch_params of include/fdr.h"""
+    _fields_ = RlTvParams._fields_ + [("couple", ctypes.c_int)]
+
+
 class RlBatchParams(ctypes.Structure):
     """fdr_rl_batch_params of include/fdr.h"""
     _fields_ = [("iterations", ctypes.c_int), ("norm_area", ctypes.c_int), ("free_boundary", ctypes.c_int), ("sigma", ctypes.c_float),
@@ -309,6 +314,9 @@ def _signatures():
         "fdr_richardson_lucy_tv_f32": (ci, [vp, vp, ci, ci, ci, vp, ci, vp, ci, P(RlTvParams)]),
         "fdr_richardson_lucy_tv_f32_dev": (ci, [vp, vp, ci, ci, ci, vp, ci, vp, ci, P(RlTvParams), vp]),
         "fdr_rl_tv_factor_f32_dev": (ci, [ci, vp, ci, ci, ci, vp, cf, cf, vp, ci, vp]),
+        "fdr_richardson_lucy_tv_batch_f32": (ci, [vp, vp, sz, ci, ci, ci, ci, vp, ci, vp, sz, ci, P(RlTvBatchParams)]),
+        "fdr_richardson_lucy_tv_batch_f32_dev": (ci, [vp, vp, sz, ci, ci, ci, ci, vp, ci, vp, sz, ci, P(RlTvBatchParams), vp]),
+        "fdr_rl_tv_factor_group_f32_dev": (ci, [ci, vp, sz, ci, ci, ci, ci, vp, cf, cf, ci, vp, sz, ci, vp]),
         "fdr_blur_batch_f32_dev": (ci, [vp, vp, sz, ci, ci, ci, ci, vp, sz, ci, ci, vp]),
         "fdr_richardson_lucy_batch_f32": (ci, [vp, vp, sz, ci, ci, ci, ci, vp, ci, vp, sz, ci, P(RlBatchParams)]),
         "fdr_richardson_lucy_batch_f32_dev": (ci, [vp, vp, sz, ci, ci, ci, ci, vp, ci, vp, sz, ci, P(RlBatchParams), vp]),
@@ -752,6 +760,52 @@ class Plan:
     def rl_tv_factor_dev(self, d_u, rows, cols, stride, d_out, out_stride, lam, eps=0.0, d_w=None, stream=None):
         """the factor w / (1 - lam div(grad u / |grad u|)) of one such step on a device window, on the plan's device (rl_tv_factor_dev)"""
         rl_tv_factor_dev(d_u, rows, cols, stride, d_out, out_stride, lam, eps, d_w, self.device, stream)
+
+    def rl_tv_factor_group_dev(self, d_u, u_pitch, count, rows, cols, stride, d_out, out_pitch, out_stride, lam, eps=0.0, d_w=None,
+                               couple=TV_COUPLE_NONE, stream=None):
+        """the factors of `count` (1 .. 8) device windows in one launch, window k at d_u + k u_pitch -> d_out + k out_pitch (elements),
+        one d_w (or None) for all, on the plan's device.  couple=TV_COUPLE_NONE: window k gets the bits of rl_tv_factor_dev on it;
+        TV_COUPLE_CHANNELS: the windows are the channels of one picture and share the norm sqrt(eps^2 + sum_c |grad u_c|^2).
+        Asynchronous."""
+        _check(lib.fdr_rl_tv_factor_group_f32_dev(int(self.device), ctypes.c_void_p(int(d_u)), int(u_pitch), int(count), rows, cols, stride,
+                                                  ctypes.c_void_p(int(d_w)) if d_w else None, float(lam), float(eps), int(couple),
+                                                  ctypes.c_void_p(int(d_out)), int(out_pitch), out_stride, _stream(stream)))
+
+    def richardson_lucy_tv_batch_dev(self, d_imgs, img_pitch, count, rows, cols, stride, d_out, out_pitch, out_stride, iterations, lam, eps=0.0,
+                                     free_boundary=False, d_weights=None, wstride=0, cov_sigma=RL_SIGMA, norm_area=NORM_NONE, out_rows=None,
+                                     out_cols=None, couple=TV_COUPLE_NONE, stream=None):
+        """richardson_lucy_tv_dev on `count` windows, image i at d_imgs + i img_pitch / d_out + i out_pitch (elements), in launch
+        groups of set_batching's `group` images: one factor launch and one launch per pass for a group.  couple=TV_COUPLE_NONE: every
+        image has the bits of richardson_lucy_tv_dev; TV_COUPLE_CHANNELS: the images are the channels of one picture under one
+        vectorial TV prior (count <= group).  free_boundary: one weights plane (or None) for all images.  Asynchronous."""
+        prm = RlTvBatchParams(int(iterations), int(bool(free_boundary)), float(lam), float(eps), int(norm_area), float(cov_sigma),
+                              int((rows if free_boundary else 0) if out_rows is None else out_rows),
+                              int((cols if free_boundary else 0) if out_cols is None else out_cols), int(couple))
+        _check(lib.fdr_richardson_lucy_tv_batch_f32_dev(self._h, ctypes.c_void_p(int(d_imgs)), int(img_pitch), int(count), rows, cols, stride,
+                                                        ctypes.c_void_p(int(d_weights)) if d_weights else None, int(wstride),
+                                                        ctypes.c_void_p(int(d_out)), int(out_pitch), out_stride, ctypes.byref(prm),
+                                                        _stream(stream)))
+
+    def richardson_lucy_tv_batch(self, imgs, iterations, lam, eps=0.0, free_boundary=False, weights=None, cov_sigma=RL_SIGMA,
+                                 norm_area=NORM_NONE, full_plane=False, couple=TV_COUPLE_NONE):
+        """Host arrays [count, rows, cols] in, [count, rows, cols] out (free_boundary with full_plane: [count, M, N]); weights
+        ([rows, cols], free_boundary only) serve every image.  couple as richardson_lucy_tv_batch_dev."""
+        imgs = np.ascontiguousarray(imgs, dtype=np.float32)
+        cnt, rows, cols = imgs.shape
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float32)
+            if w.shape != (rows, cols):
+                raise ValueError("weights must have the shape of one image")
+        if full_plane and not free_boundary:
+            raise ValueError("full_plane needs free_boundary=True")
+        orows, ocols = (self.M, self.N) if full_plane else (rows, cols)
+        out = np.empty((cnt, orows, ocols), dtype=np.float32)
+        prm = RlTvBatchParams(int(iterations), int(bool(free_boundary)), float(lam), float(eps), int(norm_area), float(cov_sigma),
+                              orows if free_boundary else 0, ocols if free_boundary else 0, int(couple))
+        _check(lib.fdr_richardson_lucy_tv_batch_f32(self._h, _ptr(imgs), rows * cols, cnt, rows, cols, cols, _ptr(w) if w is not None else None,
+                                                    cols, _ptr(out), orows * ocols, ocols, ctypes.byref(prm)))
+        return out
 
     # several images per launch (include/fdr.h, "batched blur and Richardson-Lucy"): groups of set_batching's `group` images, every
     # image with the bits of its single-image call
@@ -1405,6 +1459,29 @@ def richardsonLucyTV_myfft(img, psf, iterations, lam, eps=0.0, free_boundary=Fal
     with Plan(M, N, MODE_FAST, device) as p:
         p.set_operator_psf(psf)
         return p.richardson_lucy_tv(img, iterations, lam, eps, free_boundary, weights, cov_sigma, norm_area, full_plane)
+
+
+def richardsonLucyTV_RGB(channels, psf, iterations, lam, eps=0.0, free_boundary=False, weights=None, coupled=False, cov_sigma=RL_SIGMA,
+                         device=0, norm_area=NORM_NONE):
+    """fft_gpu::richardsonLucyTV_RGB: replaces every element of `channels` (float32 planes of one size, at most 8) in place with its
+    Richardson-Lucy estimate under the TV prior, from one plan and one batched call: the bits of richardsonLucyTV_myfft per channel,
+    or with coupled=True the channels under one vectorial TV prior (one norm for all, so an edge falls in the same place in every
+    channel).  free_boundary and weights as richardsonLucyTV_myfft; one weights plane serves every channel."""
+    if not channels:
+        return
+    psf = np.asarray(psf, dtype=np.float32)
+    r, c = np.asarray(channels[0]).shape
+    if free_boundary:
+        M, N = _rlfree_plan_size(r, c, psf.shape[0], psf.shape[1])
+    else:
+        M, N = _rl_plan_size(r, c)
+    with Plan(M, N, MODE_FAST, device) as p:
+        p.set_operator_psf(psf)
+        p.set_batching(1, min(len(channels), 8))
+        out = p.richardson_lucy_tv_batch(np.stack([np.asarray(ch, dtype=np.float32) for ch in channels]), iterations, lam, eps, free_boundary,
+                                         weights, cov_sigma, norm_area, couple=TV_COUPLE_CHANNELS if coupled else TV_COUPLE_NONE)
+    for i in range(len(channels)):
+        channels[i] = out[i]
 
 
 def psf_gaussian(size, sigma=0.0):

@@ -76,15 +76,17 @@ int op_cols_table_n(fdr_plan* p, fdr_plan::Slot* const* ws, int n, const float2*
     return FDR_OK;
 }
 // pass C with an operator kind: the window rows x cols of the inverse transform of slot k through the kind's epilogue into outs[k];
-// srcs[k] the kind's real source (null for ROW_OUT_BLUR), src2 the second source of ROW_OUT_RL_UPDATE_W, one plane for the group
+// srcs[k] the kind's real source (null for ROW_OUT_BLUR), src2 the second source of ROW_OUT_RL_UPDATE_W: one plane for the group, or
+// with src2_pitch image k's own at src2 + k src2_pitch
 int op_rows_inv_n(fdr_plan* p, fdr_plan::Slot* const* ws, int n, RowOut kind, const char* name, const float* const* srcs, int src_stride,
-                  const float* src2, float* const* outs, int out_stride, int rows, int cols, hipStream_t s, const RlFit* fit) {
+                  const float* src2, float* const* outs, int out_stride, int rows, int cols, hipStream_t s, const RlFit* fit, size_t src2_pitch) {
     if (fit && n > 1) return fail(FDR_ERR_STATE, "op_rows_inv: the fit sums take one image per launch");
     ScopedPass t(p, s, name);
     RowArgs a = panel_row_args(p);
     a.src_c = ws[0]->work;
     a.src_real = srcs ? srcs[0] : nullptr; a.src_stride = src_stride;
     a.src_real2 = src2;
+    a.src2_pitch = n > 1 ? (int)src2_pitch : 0;
     if (fit) {  // ROW_OUT_RL_RATIO_STAT: the weights beside the datum, the (res, kl) partials in the slot of the min/max ones
         a.src_real2 = fit->weights;
         a.mm_part = reinterpret_cast<float2*>(fit->part);

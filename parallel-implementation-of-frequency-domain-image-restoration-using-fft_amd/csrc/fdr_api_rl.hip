@@ -45,7 +45,8 @@ int plain_form_check(const char* fn, const float* weights, int rows, int cols, i
 }
 
 int rl_step(fdr_plan* p, fdr_plan::Slot* const* ws, int n, const float* const* d_imgs, int stride, const float* const* ys, int ystride,
-            float* const* outs, int os, int rows, int cols, hipStream_t s, const RlFit* fit, const RlHooks* hooks, int it, const float* factor) {
+            float* const* outs, int os, int rows, int cols, hipStream_t s, const RlFit* fit, const RlHooks* hooks, int it, const float* factor,
+            size_t factor_pitch) {
     if (hooks && n > 1) return fail(FDR_ERR_STATE, "rl_step: the hooks take one image per step");
     float* r[kMaxGroup];
     for (int k = 0; k < n; ++k) r[k] = ws[k]->raw;
@@ -60,7 +61,7 @@ int rl_step(fdr_plan* p, fdr_plan::Slot* const* ws, int n, const float* const* d
     if (rc == FDR_OK) rc = op_rows_fwd_n(p, ws, n, r, rows, cols, rs, s);                                // g = blur^T(r) ...
     if (rc == FDR_OK) rc = op_cols_n(p, ws, n, true, s);
     if (rc == FDR_OK && factor)                                                                          // ... out = max(y factor g, 0)
-        return op_rows_inv_n(p, ws, n, ROW_OUT_RL_UPDATE_W, kPassRlUpdateF, ys, ystride, factor, outs, os, rows, cols, s);
+        return op_rows_inv_n(p, ws, n, ROW_OUT_RL_UPDATE_W, kPassRlUpdateF, ys, ystride, factor, outs, os, rows, cols, s, nullptr, factor_pitch);
     if (rc == FDR_OK) rc = op_rows_inv_n(p, ws, n, ROW_OUT_RL_UPDATE, kPassRlUpdate, ys, ystride, nullptr, outs, os, rows, cols, s);  // ... out = max(y g, 0)
     return rc;
 }

@@ -11,7 +11,7 @@
 
 using namespace fdr;
 
-namespace {
+namespace fdr {
 
 // what the two batched Richardson-Lucy calls refuse, before any device work: the single-image call of the form on image 0 (plan,
 // operator PSF, window, strides, iteration count, normalisation, sigma, output window), weights in the plain form, and an output
@@ -44,7 +44,7 @@ int rl_batch_check(const fdr_plan* p, const char* fn, const float* imgs, size_t 
 // workspace grows to the group before anything runs.  Groups of one are the loop of the single accelerated calls in either form.)
 int rl_batch_run(fdr_plan* p, const char* fn, const float* d_imgs, size_t img_pitch, int count, int rows, int cols, int stride,
                  const float* d_w, int wstride, float* d_out, size_t out_pitch, int out_stride, const fdr_rl_batch_params& b,
-                 const fdr_rlfree_params& free_prm, hipStream_t s, bool accel = false, float* d_alphas = nullptr, size_t alpha_pitch = 0) {
+                 const fdr_rlfree_params& free_prm, hipStream_t s, bool accel, float* d_alphas, size_t alpha_pitch) {
     const int group = launch_group(p, count);
     int rc = FDR_OK;
     if (b.free_boundary) rc = ensure_rlfree_workspace(p, fn, group);
@@ -63,6 +63,10 @@ int rl_batch_run(fdr_plan* p, const char* fn, const float* d_imgs, size_t img_pi
     }
     return rc;
 }
+
+}  // namespace fdr
+
+namespace {
 
 // what the accelerated batch refuses on top of rl_batch_check: an alpha pitch below the iteration count, and alphas that overlap,
 // anywhere in the span of the batch, the inputs, the outputs or the weights.  Null alphas or no iterations: nothing to check.

@@ -106,7 +106,7 @@ int stage_weights(fdr_plan* p, const float* weights_host, int rows, int cols, in
 }
 
 int rlfree_step(fdr_plan* p, fdr_plan::Slot* const* ws, int n, const float* const* ys, float* const* outs, const float* const* datums,
-                const float* wgt, int rows, int cols, hipStream_t s, const RlFit* fit, const RlHooks* hooks, int it) {
+                const float* wgt, int rows, int cols, hipStream_t s, const RlFit* fit, const RlHooks* hooks, int it, size_t wgt_pitch) {
     if (hooks && n > 1) return fail(FDR_ERR_STATE, "rlfree_step: the hooks take one image per step");
     const int M = p->M, N = p->N;
     float* r[kMaxGroup];
@@ -120,7 +120,7 @@ int rlfree_step(fdr_plan* p, fdr_plan::Slot* const* ws, int n, const float* cons
     if (rc == FDR_OK && hooks && hooks->after_ratio) rc = hooks->after_ratio(it);
     if (rc == FDR_OK) rc = op_rows_fwd_n(p, ws, n, r, rows, cols, cols, s);                          // g = fullblur^T(pad(r)) ...
     if (rc == FDR_OK) rc = op_cols_n(p, ws, n, true, s);
-    if (rc == FDR_OK) rc = op_rows_inv_n(p, ws, n, ROW_OUT_RL_UPDATE_W, kPassRfUpdate, ys, N, wgt, outs, N, M, N, s);  // ... out = max(y wgt g, 0)
+    if (rc == FDR_OK) rc = op_rows_inv_n(p, ws, n, ROW_OUT_RL_UPDATE_W, kPassRfUpdate, ys, N, wgt, outs, N, M, N, s, nullptr, wgt_pitch);  // ... out = max(y wgt g, 0)
     return rc;
 }
 
@@ -152,9 +152,12 @@ int rlfree_finish(fdr_plan* p, const char* fn, const float* u, float* d_out, int
 // image that copy would replace the coverage passes of the single calls, so several images are the loop of batches of one.
 int rlfree_batch_dev(fdr_plan* p, const char* fn, const float* d_imgs, size_t img_pitch, int count, int rows, int cols, int stride, const float* d_w,
                      int wstride, float* d_out, size_t out_pitch, int out_stride, const fdr_rlfree_params& prm, hipStream_t s, const RlHooks* hooks,
-                     float* keep_w, bool accel, float* d_alphas, size_t alpha_pitch) {
+                     float* keep_w, bool accel, float* d_alphas, size_t alpha_pitch, const RlTvPrior* tv) {
     if (accel && hooks) return fail(FDR_ERR_STATE, "rlfree_batch_dev: the accelerated recursion takes no hooks");
     const int group = launch_group(p, count);
+    if (tv && (accel || hooks || group == 1 || p->rt_group < group))
+        return fail(FDR_ERR_STATE, "rlfree_batch_dev: the prior takes launch groups of several images, plain steps and its workspace");
+    const size_t P = (size_t)p->M * p->N;
     int rc = FDR_OK;
     if (group == 1 && count > 1) {  // the loop of the single-image calls, each with its own coverage
         for (int i = 0; i < count && rc == FDR_OK; ++i)
@@ -163,12 +166,14 @@ int rlfree_batch_dev(fdr_plan* p, const char* fn, const float* d_imgs, size_t im
         return rc;
     }
     rc = rlfree_begin(p, d_imgs, rows, cols, stride, d_w, wstride, prm.sigma, keep_w, nullptr, s);
+    if (rc == FDR_OK && tv)  // the prior's estimates lie one pitch apart, in its own workspace: image 0's start goes there
+        FDR_HIP(hipMemcpyAsync(p->rt_u, p->rf_u, P * sizeof(float), hipMemcpyDeviceToDevice, s));
     for (int i0 = 0; i0 < count && rc == FDR_OK; i0 += group) {
         const LaunchGroup g(p, i0, count, d_imgs, img_pitch, d_out, out_pitch);
         float* us[kMaxGroup];
         const float* dws[kMaxGroup];
         for (int k = 0; k < g.n && rc == FDR_OK; ++k) {
-            us[k] = rlfree_u_plane(p, k); dws[k] = rlfree_dw_plane(p, k);
+            us[k] = tv ? p->rt_u + (size_t)k * P : rlfree_u_plane(p, k); dws[k] = rlfree_dw_plane(p, k);
             if (i0 + k == 0) continue;  // begun above
             const double* sums = nullptr;
             rc = rlfree_setup_image(p, g.ins[k], rows, cols, stride, d_w, wstride, rlfree_dw_plane(p, k), us[k], rlfree_part(p, k), nullptr, &sums, s);
@@ -188,7 +193,8 @@ int rlfree_batch_dev(fdr_plan* p, const char* fn, const float* d_imgs, size_t im
                                }, fin);
         }
         for (int it = 0; it < prm.iterations && rc == FDR_OK && !accel; ++it) {
-            rc = rlfree_step(p, g.ws, g.n, us, us, dws, p->rf_wgt, rows, cols, s, nullptr, hooks, it);
+            if (tv) rc = rltv_factor_group(p, g.n, p->M, p->N, p->N, p->rf_wgt, *tv, s);  // factor_k = wgt / g_k from the u_k that enter the step
+            if (rc == FDR_OK) rc = rlfree_step(p, g.ws, g.n, us, us, dws, tv ? p->rt_f : p->rf_wgt, rows, cols, s, nullptr, hooks, it, tv ? P : 0);
             if (rc == FDR_OK && hooks && hooks->after_step) rc = hooks->after_step(it);
         }
         for (int k = 0; k < g.n && rc == FDR_OK; ++k) rc = rlfree_finish(p, fn, fin[k], g.outs[k], out_stride, prm, s);

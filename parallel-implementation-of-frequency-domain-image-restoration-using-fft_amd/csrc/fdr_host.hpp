@@ -194,8 +194,11 @@ struct fdr_plan {
     float* ra_alpha = nullptr;
     // Richardson-Lucy with a total-variation prior (fdr_richardson_lucy_tv_f32*): made by the first such call with lambda > 0, kept until
     // fdr_plan_destroy -- one allocation of two M x N float planes: the factor w / g of the step and the plain form's estimate (dense
-    // rows x cols; the free-boundary form keeps its estimate in rf_u)
+    // rows x cols; the free-boundary form keeps its estimate in rf_u).  A batched call on groups of g images
+    // (fdr_richardson_lucy_tv_batch_f32*) grows it to 2 g planes: rt_group = the images it holds, the g factor planes first (image k's
+    // at rt_f + k M N), then the g estimates (image k's at rt_u + k M N, in both forms: a group's estimates lie one pitch apart)
     void* rt_block = nullptr;
+    int rt_group = 0;
     float *rt_f = nullptr, *rt_u = nullptr;
     // stopping Richardson-Lucy from the data (fdr_richardson_lucy_auto_f32*): made by the first such call, kept until fdr_plan_destroy
     // -- rs_block holds the (res, kl) partials of the ratio pass (one double2 per workgroup of the plan's inverse row grid) and the
@@ -377,12 +380,14 @@ struct RlFit { const float* weights; double* part; };
 // The passes for a group of n >= 1 images on the slots ws[0 .. n) with per-image pointers (blockIdx.y = image; n = 1 is the
 // single-image launch): pass A (the window of xs[k], zero elsewhere -> the half spectrum of slot k) keeps FDR_PAD_ZERO, pass B'
 // reads `table` once for the group and is timed as `name`, pass C takes the four kinds ROW_OUT_BLUR, _RL_RATIO, _RL_UPDATE and
-// _RL_UPDATE_W (src2: the one wgt plane of the group) and, for one image, _RL_RATIO_STAT with `fit`.  An image comes out with the
+// _RL_UPDATE_W (src2: the one wgt plane of the group, or with src2_pitch image k's own plane at src2 + k src2_pitch floats, at most
+// an M x N plane apart) and, for one image, _RL_RATIO_STAT with `fit`.  An image comes out with the
 // bits it gets alone.
 int op_rows_fwd_n(fdr_plan* p, fdr_plan::Slot* const* ws, int n, const float* const* xs, int rows, int cols, int stride, hipStream_t s);
 int op_cols_table_n(fdr_plan* p, fdr_plan::Slot* const* ws, int n, const float2* table, const char* name, hipStream_t s);
 int op_rows_inv_n(fdr_plan* p, fdr_plan::Slot* const* ws, int n, RowOut kind, const char* name, const float* const* srcs, int src_stride,
-                  const float* src2, float* const* outs, int out_stride, int rows, int cols, hipStream_t s, const RlFit* fit = nullptr);
+                  const float* src2, float* const* outs, int out_stride, int rows, int cols, hipStream_t s, const RlFit* fit = nullptr,
+                  size_t src2_pitch = 0);
 int op_cols_n(fdr_plan* p, fdr_plan::Slot* const* ws, int n, bool adjoint, hipStream_t s);  // pass B' on H / (M N), `adjoint`: on conj(H) / (M N)
 // the single-image forms: a group of one on slot 0
 int op_rows_fwd(fdr_plan* p, const float* x, int rows, int cols, int stride, hipStream_t s);
@@ -429,10 +434,11 @@ int rl_check(const fdr_plan* p, const char* fn, const float* img, int rows, int 
 int plain_form_check(const char* fn, const float* weights, int rows, int cols, int out_rows, int out_cols, bool each_alone, const char* window_msg);
 // One iteration of the plain form: c = blur(y), r = d+ / c into the window of slot k's raw plane (row stride cols), out = max(y .
 // blur^T(r), 0); outs[k] may be ys[k].  With `fit` (one image) the ratio pass also leaves the fit partials of c: same r, same update.
-// With `factor` (one plane for the group, row stride ystride) the update is the weighted one: out = max(y . factor . blur^T(r), 0).
+// With `factor` (row stride ystride; image k's plane at factor + k factor_pitch) the update is the weighted one: out = max(y . factor .
+// blur^T(r), 0).
 int rl_step(fdr_plan* p, fdr_plan::Slot* const* ws, int n, const float* const* d_imgs, int stride, const float* const* ys, int ystride,
             float* const* outs, int os, int rows, int cols, hipStream_t s, const RlFit* fit = nullptr, const RlHooks* hooks = nullptr, int it = 0,
-            const float* factor = nullptr);
+            const float* factor = nullptr, size_t factor_pitch = 0);
 // the start u = max(d, 0) and the closing normalisation of a plain-form call
 int rl_init_estimate(fdr_plan* p, const float* d_img, int rows, int cols, int stride, float* u, int us, hipStream_t s);
 int rl_normalize(fdr_plan* p, const char* fn, const float* fin, int fs, int rows, int cols, int norm_area, float* d_out, int out_stride,
@@ -454,9 +460,11 @@ int rlfree_check(const fdr_plan* p, const char* fn, const float* img, int rows, 
 int stage_weights(fdr_plan* p, const float* weights_host, int rows, int cols, int wstride);
 // One iteration of the free-boundary form on the whole plan: c = window(fullblur(y)), r = datum / c into slot k's raw plane, out =
 // max(y wgt fullblur^T(pad(r)), 0).  ys[k] and outs[k] are dense M x N planes and may be the same; datums[k] is dense rows x cols:
-// dw, or with `fit` (one image; weights dense too) d, from which the ratio pass forms dw = w d+ itself; wgt is the one plane of the call.
+// dw, or with `fit` (one image; weights dense too) d, from which the ratio pass forms dw = w d+ itself; wgt is the one plane of the call,
+// or with wgt_pitch image k's own plane at wgt + k wgt_pitch (the prior's factor wgt / g_k).
 int rlfree_step(fdr_plan* p, fdr_plan::Slot* const* ws, int n, const float* const* ys, float* const* outs, const float* const* datums,
-                const float* wgt, int rows, int cols, hipStream_t s, const RlFit* fit = nullptr, const RlHooks* hooks = nullptr, int it = 0);
+                const float* wgt, int rows, int cols, hipStream_t s, const RlFit* fit = nullptr, const RlHooks* hooks = nullptr, int it = 0,
+                size_t wgt_pitch = 0);
 // begin, image 0 of a call: the setup (dw into rf_dw, W = pad(m) into rf_u, copied dense to keep_w when that is not null), the
 // coverage alpha = fullblur^T(W) and the start (rf_wgt = 1 / alpha, u_0 in rf_u); *sums, when not null, is where the device holds
 // (sum dw, sum W).  d_w may be rf_u itself (stage_weights).
@@ -464,6 +472,11 @@ int rlfree_begin(fdr_plan* p, const float* d_img, int rows, int cols, int stride
                  const double** sums, hipStream_t s);
 // finish: the output window of the dense M x N estimate u, cropped or normalised, into d_out
 int rlfree_finish(fdr_plan* p, const char* fn, const float* u, float* d_out, int out_stride, const fdr_rlfree_params& prm, hipStream_t s);
+// `tv` of rlfree_batch_dev, the TV prior of fdr_api_rltv.hip (launch groups of more than one image, no hooks, not accelerated; needs
+// the prior's workspace for the group): image k's estimate lives in rt_u + k M N, and every step is preceded by one factor launch for
+// the group and takes factor_k = wgt / g_k, at rt_f + k M N, in the place of wgt.  `coupled`: the images are the channels of one
+// picture and share the prior's norm.
+struct RlTvPrior { float lambda, eps; bool coupled; };
 // the free-boundary form on a checked batch of `count` images with its workspace (for launch_group(p, count) images): begin, steps in
 // place, finish, in launch groups; one image with its hooks and keep_w is the blind call's.  `accel` (no hooks; needs the acceleration
 // workspace for the group as well): the recursion of rl_accel_loop around the step, the estimate alternating between image k's u
@@ -471,7 +484,17 @@ int rlfree_finish(fdr_plan* p, const char* fn, const float* u, float* d_out, int
 int rlfree_batch_dev(fdr_plan* p, const char* fn, const float* d_imgs, size_t img_pitch, int count, int rows, int cols, int stride, const float* d_w,
                      int wstride, float* d_out, size_t out_pitch, int out_stride, const fdr_rlfree_params& prm, hipStream_t s,
                      const RlHooks* hooks = nullptr, float* keep_w = nullptr, bool accel = false, float* d_alphas = nullptr,
-                     size_t alpha_pitch = 0);
+                     size_t alpha_pitch = 0, const RlTvPrior* tv = nullptr);
+// ---- the TV prior of Richardson-Lucy (fdr_api_rltv.hip) ----
+// the factor launch of a group: the n planes rows x cols (row stride `stride`) at rt_u + k M N to rt_f + k M N (same stride), w the group's
+int rltv_factor_group(fdr_plan* p, int n, int rows, int cols, int stride, const float* w, const RlTvPrior& tv, hipStream_t s);
+// the checks and the driver of fdr_richardson_lucy_batch_f32* (fdr_api_rlbatch.hip), which the batch with the prior shares
+int rl_batch_check(const fdr_plan* p, const char* fn, const float* imgs, size_t img_pitch, int count, int rows, int cols, int stride,
+                   const float* weights, int wstride, const float* out, size_t out_pitch, int out_stride, const fdr_rl_batch_params& b,
+                   fdr_rlfree_params* free_prm);
+int rl_batch_run(fdr_plan* p, const char* fn, const float* d_imgs, size_t img_pitch, int count, int rows, int cols, int stride,
+                 const float* d_w, int wstride, float* d_out, size_t out_pitch, int out_stride, const fdr_rl_batch_params& b,
+                 const fdr_rlfree_params& free_prm, hipStream_t s, bool accel = false, float* d_alphas = nullptr, size_t alpha_pitch = 0);
 // ---- the noise estimate (fdr_api_reg.hip): the Immerkaer sum of a device window through `part` (reg_noise_partials + 1 doubles), read
 // back: synchronous; and the refusal of a window it cannot work on
 int noise_sigma_dev(const float* d_img, int rows, int cols, int stride, double* part, double* sigma, hipStream_t s);

@@ -22,7 +22,7 @@ enum RowOut {
     ROW_OUT_RL_RATIO = 5,     // r = c > kRlTau ? max(d, 0) / c : 0 to `out`; d read from src_real (row stride src_stride)
     ROW_OUT_RL_UPDATE = 6,    // max(u g, 0) to `out`; u read from src_real (row stride src_stride; may be `out` itself)
     // free-boundary Richardson-Lucy (fdr_rlfree.hip): max(u wgt g, 0) to `out`; u from src_real as ROW_OUT_RL_UPDATE, wgt from
-    // src_real2 (same row stride; one plane for every image of a group)
+    // src_real2 (same row stride; one plane for every image of a group, or with src2_pitch image k's own plane, the TV prior's factor)
     ROW_OUT_RL_UPDATE_W = 7,
     // the ratio that also measures the fit (fdr_rlstop.hip): d from src_real, the pixel's weight w from src_real2 (same row stride;
     // null: w = 1); r = c > kRlTau ? (w max(d, 0)) / c : 0 to `out` -- the bits of ROW_OUT_RL_RATIO on d (w = 1) or on dw = w max(d, 0)
@@ -94,6 +94,9 @@ struct RowArgs {
     float* out;       // ROW_OUT_NORMALIZED: out_rows x out_cols result, row stride out_stride; mm_part holds n_part partials
     int out_rows, out_cols, out_stride, n_part;
     int M;              // number of rows to transform
+    int src2_pitch;     // rows4 packed kernels, ROW_OUT_RL_UPDATE_W on a group: image k reads src_real2 + k src2_pitch floats (0: one
+                        // plane for the group).  In the four bytes of padding between M and pstride: the block's size and every
+                        // other field's offset are unchanged
     size_t pstride;     // rows4 kernels: panel stride of the panel-major spectrum, in float2 elements
     int half;           // rows4 packed kernels: half (Hermitian) spectrum, N/8 panels
     int num_cu;         // rows4 persistent kernels: CUs of the device
@@ -103,7 +106,11 @@ struct RowArgs {
     int pad_mode;       // rows4 forward kernels (pass A): FDR_PAD_ZERO / FDR_PAD_SMOOTH -- what stands outside the picture.  In the tail
                         // padding of the block: its size and every other field's offset are unchanged
 };
-static_assert(sizeof(RowArgs) == 448, "pad_mode fits the tail padding of RowArgs: the argument blocks keep their layout");
+// Every rows4 kernel takes the block by value with the twiddle table behind it: a block that grew would move that pointer in the
+// argument segment of all of them, so pad_mode sits in the tail padding and src2_pitch in the padding behind M.
+static_assert(sizeof(RowArgs) == 448 && offsetof(RowArgs, src2_pitch) == offsetof(RowArgs, M) + sizeof(int) &&
+                  offsetof(RowArgs, pstride) == offsetof(RowArgs, M) + 2 * sizeof(int),
+              "pad_mode and src2_pitch fit the padding of RowArgs: the argument blocks keep their size and layout");
 
 // up to kMaxGroup images' spectra handled by ONE pass-B' launch (their panels form one tile sequence)
 struct PanelBatch {
@@ -185,6 +192,11 @@ hipError_t launch_rlfree_crop(const float* u, int ustride, float* out, int rows,
 // pointer; out is neither).  Any size, stride and alignment.
 hipError_t launch_rltv_factor(const float* u, int rows, int cols, int stride, const float* w, float lambda, float eps, float* out,
                               int out_stride, hipStream_t s);
+// the same on a group of 1 <= count <= kMaxGroup planes in one launch: plane k's u and out lie k u_pitch and k out_pitch floats
+// behind those given, w is the group's.  Uncoupled every plane gets the bits of launch_rltv_factor on it (one plane is that launch);
+// `coupled`: the planes are the channels of one picture and share m = sqrt(eps^2 + sum_c |grad u_c|^2), added in channel order.
+hipError_t launch_rltv_factor_group(const float* u, size_t u_pitch, int count, int rows, int cols, int stride, const float* w, float lambda,
+                                    float eps, float* out, size_t out_pitch, int out_stride, bool coupled, hipStream_t s);
 // (fdr_rlaccel.hip) accelerated Richardson-Lucy, on rows x cols windows with their own row strides.  direction: g = u1 - y over the
 // previous g; with `part` not null also sum(g_new g_old) and sum(g_old g_old) in double as rlaccel_partials(rows, cols)
 // per-workgroup partials each (part holds 2 n doubles); with a null `part` the old g is not read.  alpha: one workgroup folds the

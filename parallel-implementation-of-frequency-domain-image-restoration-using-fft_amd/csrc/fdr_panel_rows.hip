@@ -1076,9 +1076,10 @@ __global__ __launch_bounds__((Rows4PackGeom<LOGL, true>::THREADS), (HALF ? Rows4
         if constexpr (row_out_stores_raw(OUT)) a.dst_real = pick_image(a0.batch.raw, blockIdx.y);
         if constexpr (row_out_normalizes(OUT)) a.out = pick_image(a0.batch.out, blockIdx.y);
         a.mm_part = pick_image(a0.batch.mm_part, blockIdx.y);
-        if constexpr (row_out_operator_group(OUT)) {  // its own real source (d, dw or u) and destination; src_real2 (wgt) is the group's
-            a.out = pick_image(a0.batch.out, blockIdx.y);
+        if constexpr (row_out_operator_group(OUT)) {  // its own real source (d, dw or u) and destination; src_real2 is the group's
+            a.out = pick_image(a0.batch.out, blockIdx.y);  // (wgt: src2_pitch = 0) or the image's own (its factor plane)
             if constexpr (row_out_reads_src(OUT)) a.src_real = pick_image(a0.batch.src_real, blockIdx.y);
+            if constexpr (row_out_reads_src2(OUT)) a.src_real2 = a0.src_real2 + (size_t)blockIdx.y * (size_t)a0.src2_pitch;
         }
     }
     float fscale = 0.f, fshift = 0.f;

@@ -1,5 +1,5 @@
 // gpu.cpp -- ./gpu <img-path> <psf-length> <psf-angle> | auto auto [--any-blur] | defocus <radius|auto> | blind <size>  [--out file] [--mode fast|parity] [--norm padded|cropped] [--host-epilogue]
-//           [--cls gamma|auto] [--k K|auto] [--reg gcv|discrepancy] [--sigma s] [--pad zero|smooth] [--rl iterations|auto [--accel] [--rl-tv lambda [--rl-tv-eps e]] [--free-boundary [--mask mask.png]] [--rl-max n] [--rl-stop residual|kl] [--gain g] [--rl-check c]] [--tv mu [--tv-iters n] [--tv-rho r] [--tv-color | --free-boundary [--mask mask.png]]]
+//           [--cls gamma|auto] [--k K|auto] [--reg gcv|discrepancy] [--sigma s] [--pad zero|smooth] [--rl iterations|auto [--accel] [--rl-tv lambda [--rl-tv-eps e] [--rl-tv-color]] [--free-boundary [--mask mask.png]] [--rl-max n] [--rl-stop residual|kl] [--gain g] [--rl-check c]] [--tv mu [--tv-iters n] [--tv-rho r] [--tv-color | --free-boundary [--mask mask.png]]]
 // `--tv mu --free-boundary`: the TV leg is fft_gpu::tvDeblurFree_RGB (the picture is a crop of a larger scene; --mask as for --rl); --tv-color has no such form.
 // `--tv auto [--sigma s] [--tv-tau t] [--tv-iters n] [--tv-rho r] [--mask mask.png]`: the TV leg is fft_gpu::tvDeblurAuto_RGB -- the free-boundary
 // iteration with mu chosen in every step from the noise level (--sigma, else estimated per channel; the ball is t sigma^2 S, t default 1; n default
@@ -27,7 +27,8 @@
 // and the run then goes on exactly as `--rl k` would.  It combines with --accel, --free-boundary, --mask and `auto auto`.
 // `--rl n --rl-tv lambda [--rl-tv-eps e]`: the --rl leg runs Richardson-Lucy with a total-variation prior of weight lambda (fft_gpu::richardsonLucyTV_RGB;
 // eps smooths |grad u|, default FDR_RLTV_EPS); --free-boundary and --mask apply, `auto auto` works as before; --accel, `--rl auto` and `blind` have no
-// regularised form and are refused with a message.
+// regularised form and are refused with a message.  The three channels go through one batched call; --rl-tv-color beside --rl-tv couples them
+// under one vectorial TV prior (an edge falls in the same place in every channel); without --rl-tv it is a usage error.
 // Drop-in counterpart of the reference's gpu.cpp (argument meaning, printed lines and exit codes as at
 // gpu.cpp:57-138 of the reference): read image, /255, PSF, K = 0.01, split BGR, warm-up call, timed
 // wienerDeblur_RGB_optimized, timed wienerDeblur_RGB_naive, merge, Lab white balance, 8-bit result.
@@ -113,7 +114,7 @@ int main(int argc, char** argv) {
     bool rl_auto_opts = false;   // one of the four above was given
     bool accel = false;          // --accel: the --rl leg runs the accelerated iteration (vector extrapolation)
     float rl_tv = -1.f, rl_tv_eps = 0.f;  // --rl-tv lambda: the --rl leg is fft_gpu::richardsonLucyTV_RGB; --rl-tv-eps e
-    bool rl_tv_opts = false;
+    bool rl_tv_opts = false, rl_tv_color = false;  // --rl-tv-color: the channels under one vectorial TV prior (coupled)
     bool free_boundary = false;  // --free-boundary: the --rl leg is fft_gpu::richardsonLucyFree_RGB (the picture is a crop of a larger scene)
     string mask_path;            // --mask file: pixels that are 0 in it (any channel counts) get weight 0, the others weight 1
     float tv_mu = -1.f, tv_rho = 2.0f;  // --tv mu: a timed total-variation leg (fft_gpu::tvDeblur_RGB); its planes are the written result
@@ -173,6 +174,7 @@ int main(int argc, char** argv) {
         else if (a == "--accel") accel = true;
         else if (a == "--rl-tv" && i + 1 < argc) { rl_tv_opts = true; rl_tv = strtof(argv[++i], nullptr); }
         else if (a == "--rl-tv-eps" && i + 1 < argc) { rl_tv_opts = true; rl_tv_eps = strtof(argv[++i], nullptr); }
+        else if (a == "--rl-tv-color") { rl_tv_opts = true; rl_tv_color = true; }
         else if (a == "--free-boundary") free_boundary = true;
         else if (a == "--mask" && i + 1 < argc) mask_path = argv[++i];
         else if (a == "--psf-hold" && i + 1 < argc) { blind_opts = true; psf_hold = atoi(argv[++i]); }
@@ -421,7 +423,7 @@ int main(int argc, char** argv) {
     } else if (rl_iterations >= 0) {  // Richardson-Lucy on the same channels: its planes become the written result
         vector<Mat> rl = input;
         t_start = high_resolution_clock::now();
-        if (rl_tv_opts) fft_gpu::richardsonLucyTV_RGB(rl, psf, rl_iterations, rl_tv, rl_tv_eps, free_boundary, weights);
+        if (rl_tv_opts) fft_gpu::richardsonLucyTV_RGB(rl, psf, rl_iterations, rl_tv, rl_tv_eps, free_boundary, weights, rl_tv_color);
         else if (free_boundary) fft_gpu::richardsonLucyFree_RGB(rl, psf, rl_iterations, weights, accel);
         else fft_gpu::richardsonLucy_RGB(rl, psf, rl_iterations, accel);
         t_end = high_resolution_clock::now();
