@@ -890,6 +890,71 @@ int fdr_tv_deconv_auto_batch_f32(fdr_plan* plan, const float* imgs_host, size_t 
                                  const fdr_tv_auto_batch_params* params, const double* sigmas, fdr_tv_auto_result* results,
                                  double* trace_host, size_t trace_pitch);
 
+/* -- sectioned restoration (Trussell & Hunt 1978; Nagy & O'Leary 1998): a picture of any size, larger than a
+ *    plan can be, is cut into overlapping tiles, every tile is restored as a crop of a larger scene by the free-boundary iteration
+ *    of the chosen method on ONE tile plan, with one PSF for all tiles or one per tile (a blur that changes across the frame), and
+ *    the tiles are blended with a partition of unity.  Geometry, per axis (rows; columns alike), in integers and doubles on the host:
+ *        n = 1 and the window win = rows when rows <= T; otherwise win = T, n = ceil((rows - O) / (T - O)) and tile a starts at
+ *        y_a = min(a (T - O), rows - T): all tiles have one size, the last ends at the picture's edge (its overlap may exceed O)
+ *        h(s) = 0.5 - 0.5 cos(pi s) for s < 1, else 1;  w_a(t) = rise . fall,  rise = h((t + 0.5) / O_a) with O_a the real overlap
+ *        with tile a - 1 (1 for a = 0 or O_a = 0), fall the same from the far end against tile a + 1
+ *        W_a(y) = w_a(y - y_a) / sum over the covering a' of w_a'(y - y_a'), formed in double and rounded to float once
+ *    With 0 <= O <= T / 2 at most three tiles cover a pixel along an axis.  With o_ab the restored window of tile (a, b),
+ *        out[y, x] = sum over covering a (outer, ascending), covering b (inner, ascending) of (Wy_a(y) . Wx_b(x)) . o_ab[y - y_a, x - x_b]
+ *    in float, every product and sum rounded to nearest on its own, starting from +0: a float32 model repeats it bit for bit.
+ *    Tile (a, b) is the single call fdr_richardson_lucy_free_f32_dev (FDR_TILED_RL_FREE: iterations, sigma) or
+ *    fdr_tv_deconv_free_f32_dev (FDR_TILED_TV_FREE: mu, rho, nu, iterations, anisotropic, nonneg) on its win_rows x win_cols window
+ *    of the picture (and of the weights, rows x cols for the whole picture, null = ones) with FDR_NORM_NONE and the output window
+ *    equal to the input's, bit for bit, on the tile plan holding that tile's PSF CENTRED: the prows x pcols PSF written into an
+ *    M x N plane rolled by (-(prows / 2), -(pcols / 2)) -- the centre of fdr_psf_motion -- and set as fdr_set_operator_psf_dev sets
+ *    an M x N PSF, so the result is registered with the data.  psf_count = 1: the PSF at d_psfs for all tiles; psf_count =
+ *    tiles_r tiles_c: PSF a tiles_c + b, at d_psfs + k psf_pitch floats, for tile (a, b).  With one PSF and no weights the tiles of
+ *    a tile row that lie at the uniform pitch T - O run in launch groups of fdr_plan_set_batching (the bits are those of the single
+ *    calls); otherwise tile by tile.  norm_area: FDR_NORM_NONE, or FDR_NORM_CROPPED = min-max over the whole blended picture.
+ *      fdr_tiled_layout_get   pure host: tiles and window of a picture, the smallest tile plan (min_M, min_N: the next powers of two
+ *                             of win + p - 1, within [8, 8192] x [32, 8192]) and the bytes of workspace of the _dev call on a tile
+ *                             plan of min_M x min_N: the staging of every tile's window, the PSF plane and the weight tables.  A larger
+ *                             tile plan M x N needs 4 (M N - min_M min_N) bytes more.
+ *      fdr_tiled_tile_origin  pure host: (y_a, x_b) of tile (a, b).
+ *      fdr_restore_tiled_f32_dev  device pointers; allocates nothing after the tile plan's own first-use workspaces (those of the
+ *                             method's single and batched calls), reads nothing back, asynchronous on `stream`.  d_work needs 256-byte
+ *                             alignment.  On return the plan's operator tables are those of the LAST tile's PSF (an operator PSF set
+ *                             before the call is replaced).
+ *      fdr_restore_tiled_f32  host pointers, synchronous; allocates and frees its own device buffers.
+ *    FDR_ERR_ARG, before any device work and with the plan usable afterwards: whatever the tile's single call refuses (with any
+ *    operator-path plan: the call sets the PSF itself), tile_rows or tile_cols < 1, an overlap negative or above T / 2, a tile plan
+ *    below win + p - 1 in either dimension, psf_count neither 1 nor tiles_r tiles_c, psf_pitch below the PSF's span when there are
+ *    several, work_bytes too small or d_work misaligned, FDR_NORM_PADDED (there is no single plan), and an output that overlaps the
+ *    input, the weights, the PSFs or the workspace.  The blend is one launch over the picture, a gather without atomics (4 bytes
+ *    read per covering tile and 4 written per pixel); fdr_plan_pass_times records it and the normalisation; the PSF roll is not recorded (a tile's
+ *    own passes, the blend and the normalisation already take up to FDR_MAX_PASSES names).  Results repeat bit for bit, whatever the launch group.          */
+#define FDR_TILED_RL_FREE 0
+#define FDR_TILED_TV_FREE 1
+typedef struct fdr_tiled_params {
+    int method;                       /* FDR_TILED_RL_FREE / FDR_TILED_TV_FREE */
+    int tile_rows, tile_cols;         /* T: the tile window, >= 1 (a picture no larger is one tile of its own extent) */
+    int overlap_rows, overlap_cols;   /* O: 0 .. T / 2 */
+    int iterations;                   /* >= 0 */
+    float sigma;                      /* RL: coverage threshold in (0, 1) */
+    float mu, rho, nu;                /* TV: as fdr_tv_free_params */
+    int anisotropic, nonneg;          /* TV */
+    int norm_area;                    /* FDR_NORM_NONE / FDR_NORM_CROPPED, over the blended picture */
+} fdr_tiled_params;
+typedef struct fdr_tiled_layout {
+    int tiles_r, tiles_c;  /* tiles per axis */
+    int win_rows, win_cols; /* the window of every tile: min(T, extent) */
+    int min_M, min_N;      /* the smallest tile plan */
+    size_t work_bytes;     /* of the _dev call on that plan */
+} fdr_tiled_layout;
+int fdr_tiled_layout_get(int rows, int cols, int prows, int pcols, const fdr_tiled_params* params, fdr_tiled_layout* layout);
+int fdr_tiled_tile_origin(int rows, int cols, const fdr_tiled_params* params, int a, int b, int* y, int* x);
+int fdr_restore_tiled_f32_dev(fdr_plan* tile_plan, const float* d_img, int rows, int cols, int stride, const float* d_weights, int wstride,
+                              const float* d_psfs, size_t psf_pitch, int psf_count, int prows, int pcols, int pstride, float* d_out,
+                              int out_stride, const fdr_tiled_params* params, void* d_work, size_t work_bytes, void* stream);
+int fdr_restore_tiled_f32(fdr_plan* tile_plan, const float* img_host, int rows, int cols, int stride, const float* weights_host, int wstride,
+                          const float* psfs_host, size_t psf_pitch, int psf_count, int prows, int pcols, int pstride, float* out_host,
+                          int out_stride, const fdr_tiled_params* params);
+
 /* -- the motion-blur estimate: the length and angle of a uniform linear motion blur, from the blurred
  *    picture alone, by the power cepstrum.  The blur puts sinc zeros into |G| in stripes across the motion direction; in the
  *    cepstrum they show as a negative peak at distance L along it.  The plan is M x N, the image window rows x cols (row stride

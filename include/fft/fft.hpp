@@ -580,6 +580,48 @@ inline void tvDeblurFree_RGB(std::vector<Mat>& channels, const Mat& psf, float m
                              bool coupled = false) {
     tvDeblurFree_RGB(channels, psf, mu, iterations, rho, weights, defaults(), coupled);
 }
+// Sectioned restoration (fdr_restore_tiled_f32, include/fdr.h) of every channel, in place, for a picture of any size: overlapping
+// tiles of `tile` pixels (a picture no larger is one tile), `overlap` of them shared with the neighbour, every tile restored as a
+// crop of a larger scene by the free-boundary iteration of `method` with the PSF taken as CENTRED (the result is registered with the
+// picture), the tiles blended with a partition of unity.  One tiled call per channel on one tile plan, the smallest of
+// fdr_tiled_layout_get.  norm_area: FDR_NORM_NONE or FDR_NORM_CROPPED (there is no padded area).
+struct TiledOptions {
+    int method = FDR_TILED_RL_FREE;   // FDR_TILED_RL_FREE / FDR_TILED_TV_FREE
+    int tile = 1024, overlap = 64;    // both axes
+    int iterations = 30;
+    float sigma = FDR_RL_SIGMA;       // RL: coverage threshold
+    float mu = 200.f, rho = 2.f;      // TV (nu = rho, isotropic, clamped at 0)
+    int norm_area = FDR_NORM_NONE;
+    int device = 0;
+};
+inline void restoreTiled_RGB(std::vector<Mat>& channels, const Mat& psf, const TiledOptions& t, const Mat& weights = Mat()) {
+    if (channels.empty()) return;
+    const int rows = channels[0].rows, cols = channels[0].cols;
+    if (!weights.empty() && (weights.rows != rows || weights.cols != cols || weights.type() != CV_32F)) {
+        std::cerr << "restoreTiled_RGB: the weights must be CV_32F and have the picture's size\n";
+        exit(1);
+    }
+    for (const Mat& c : channels)
+        if (c.rows != rows || c.cols != cols || c.type() != CV_32F) {
+            std::cerr << "restoreTiled_RGB: needs CV_32F channels of one size\n";
+            exit(1);
+        }
+    const fdr_tiled_params prm = {t.method, t.tile, t.tile, t.overlap, t.overlap, t.iterations, t.sigma, t.mu, t.rho, 0.f, 0, 1, t.norm_area};
+    fdr_tiled_layout lay;
+    FDR_CHECK(fdr_tiled_layout_get(rows, cols, psf.rows, psf.cols, &prm, &lay));
+    bool created = false;
+    PlanCacheSettle settle_;
+    fdr_plan* plan = plan_cache().get(t.device, lay.min_M, lay.min_N, FDR_MODE_FAST, &created);
+    Mat psfc = psf.isContinuous() ? psf : psf.clone();
+    Mat w = weights.empty() || weights.isContinuous() ? weights : weights.clone();
+    for (Mat& c : channels) {
+        Mat src = c.isContinuous() ? c : c.clone();
+        Mat out(rows, cols, CV_32F);
+        FDR_CHECK(fdr_restore_tiled_f32(plan, src.ptr<float>(0), rows, cols, cols, w.empty() ? nullptr : w.ptr<float>(0), cols, psfc.ptr<float>(0),
+                                        (size_t)psf.rows * psf.cols, 1, psf.rows, psf.cols, psf.cols, out.ptr<float>(0), cols, &prm));
+        c = out;
+    }
+}
 // Noise-constrained total-variation deconvolution (fdr_tv_deconv_auto_f32, include/fdr.h) of every channel, in place: tvDeblurFree_RGB
 // without mu.  The caller states the noise standard deviation sigma of the channels (0: estimated per channel, fdr_noise_sigma_f32)
 // and tau (0: 1); every step takes its weight from the discrepancy ball tau sigma^2 sum(weights).  The plan, operator PSF and

@@ -134,6 +134,37 @@ class RlFreeParams(ctypes.Structure):
                 ("out_cols", ctypes.c_int)]
 
 
+TILED_RL_FREE = 0  # FDR_TILED_RL_FREE: the tiles by free-boundary Richardson-Lucy
+TILED_TV_FREE = 1  # FDR_TILED_TV_FREE: the tiles by free-boundary TV deconvolution
+
+
+class TiledParams(ctypes.Structure):
+    """fdr_tiled_params of include/fdr.h"""
+    _fields_ = [("method", ctypes.c_int), ("tile_rows", ctypes.c_int), ("tile_cols", ctypes.c_int), ("overlap_rows", ctypes.c_int),
+                ("overlap_cols", ctypes.c_int), ("iterations", ctypes.c_int), ("sigma", ctypes.c_float), ("mu", ctypes.c_float),
+                ("rho", ctypes.c_float), ("nu", ctypes.c_float), ("anisotropic", ctypes.c_int), ("nonneg", ctypes.c_int),
+                ("norm_area", ctypes.c_int)]
+
+    @classmethod
+    def make(cls, method, tile, overlap=0, iterations=30, sigma=RL_SIGMA, mu=1.0, rho=2.0, nu=0.0, anisotropic=False, nonneg=False,
+             norm_area=NORM_NONE):
+        """tile and overlap: one number for both axes or (rows, cols)"""
+        tr, tc = (tile, tile) if np.isscalar(tile) else tile
+        orr, oc = (overlap, overlap) if np.isscalar(overlap) else overlap
+        return cls(int(method), int(tr), int(tc), int(orr), int(oc), int(iterations), float(sigma), float(mu), float(rho), float(nu),
+                   int(bool(anisotropic)), int(bool(nonneg)), int(norm_area))
+
+
+class TiledLayoutC(ctypes.Structure):
+    """fdr_tiled_layout of include/fdr.h"""
+    _fields_ = [("tiles_r", ctypes.c_int), ("tiles_c", ctypes.c_int), ("win_rows", ctypes.c_int), ("win_cols", ctypes.c_int),
+                ("min_M", ctypes.c_int), ("min_N", ctypes.c_int), ("work_bytes", ctypes.c_size_t)]
+
+
+# what tiled_layout returns: tiles per axis, the window of every tile, the smallest tile plan and the workspace of the _dev call on it
+TiledLayout = collections.namedtuple("TiledLayout", "tiles_r tiles_c win_rows win_cols min_M min_N work_bytes")
+
+
 class RlTvParams(ctypes.Structure):
     """fdr_rl_tv_params of include/fdr.h"""
     _fields_ = [("iterations", ctypes.c_int), ("free_boundary", ctypes.c_int), ("lambda", ctypes.c_float), ("eps", ctypes.c_float),
@@ -343,6 +374,10 @@ def _signatures():
         "fdr_tv_deconv_free_batch_f32_dev": (ci, [vp, vp, sz, ci, ci, ci, ci, vp, ci, vp, sz, ci, P(TvFreeBatchParams), vp]),
         "fdr_tv_deconv_auto_batch_f32": (ci, [vp, vp, sz, ci, ci, ci, ci, vp, ci, vp, sz, ci, P(TvAutoBatchParams), vp, vp, vp, sz]),
         "fdr_tv_deconv_auto_batch_f32_dev": (ci, [vp, vp, sz, ci, ci, ci, ci, vp, ci, vp, sz, ci, P(TvAutoBatchParams), vp, vp, sz, vp]),
+        "fdr_tiled_layout_get": (ci, [ci, ci, ci, ci, P(TiledParams), P(TiledLayoutC)]),
+        "fdr_tiled_tile_origin": (ci, [ci, ci, P(TiledParams), ci, ci, P(ci), P(ci)]),
+        "fdr_restore_tiled_f32_dev": (ci, [vp, vp, ci, ci, ci, vp, ci, vp, sz, ci, ci, ci, ci, vp, ci, P(TiledParams), vp, sz, vp]),
+        "fdr_restore_tiled_f32": (ci, [vp, vp, ci, ci, ci, vp, ci, vp, sz, ci, ci, ci, ci, vp, ci, P(TiledParams)]),
         "fdr_cepstrum_f32": (ci, [vp, vp, ci, ci, ci, vp]),
         "fdr_cepstrum_f32_dev": (ci, [vp, vp, ci, ci, ci, vp, vp]),
         "fdr_estimate_motion_f32": (ci, [vp, vp, ci, ci, ci, ci, ci, cd, P(MotionEstimateC), vp]),
@@ -989,6 +1024,40 @@ class Plan:
                                               ctypes.c_void_p(int(d_weights)) if d_weights else None, int(wstride),
                                               ctypes.c_void_p(int(d_out)), out_stride, ctypes.byref(prm), _stream(stream)))
 
+    # sectioned restoration (include/fdr.h): overlapping tiles on this plan, blended; one PSF for all tiles or one per tile
+    def restore_tiled(self, img, psfs, params, weights=None):
+        """The picture img (host array, any size) restored in overlapping tiles on this tile plan by the free-boundary iteration of
+        params.method (a TiledParams) and blended.  psfs: one PSF (2-D) for all tiles, or tiles_r x tiles_c PSFs of one shape (3-D, tile
+        (a, b) at a tiles_c + b); a PSF is taken as centred, so the result is registered with img.  weights (img.shape; None = ones)
+        as Plan.richardson_lucy_free.  The plan's operator tables are those of the last tile's PSF afterwards (fdr_restore_tiled_f32)."""
+        img = np.ascontiguousarray(img, dtype=np.float32)
+        rows, cols = img.shape
+        psfs = np.ascontiguousarray(psfs, dtype=np.float32)
+        if psfs.ndim == 2:
+            psfs = psfs[None]
+        if psfs.ndim != 3:
+            raise ValueError("psfs must be one PSF (2-D) or a stack of PSFs (3-D)")
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float32)
+            if w.shape != img.shape:
+                raise ValueError("weights must have the shape of img")
+        count, prows, pcols = psfs.shape
+        out = np.empty((rows, cols), dtype=np.float32)
+        _check(lib.fdr_restore_tiled_f32(self._h, _ptr(img), rows, cols, cols, _ptr(w) if w is not None else None, cols, _ptr(psfs),
+                                         prows * pcols, count, prows, pcols, pcols, _ptr(out), cols, ctypes.byref(params)))
+        return out
+
+    def restore_tiled_dev(self, d_img, rows, cols, stride, d_psfs, psf_pitch, psf_count, prows, pcols, pstride, d_out, out_stride, params,
+                          d_work, work_bytes, d_weights=None, wstride=0, stream=None):
+        """the same on device pointers, with the caller's workspace (tiled_layout(...).work_bytes for the smallest tile plan).
+        Allocates nothing after the plan's first-use workspaces; asynchronous."""
+        _check(lib.fdr_restore_tiled_f32_dev(self._h, ctypes.c_void_p(int(d_img)), rows, cols, stride,
+                                             ctypes.c_void_p(int(d_weights)) if d_weights else None, int(wstride),
+                                             ctypes.c_void_p(int(d_psfs)), int(psf_pitch), int(psf_count), prows, pcols, pstride,
+                                             ctypes.c_void_p(int(d_out)), out_stride, ctypes.byref(params), ctypes.c_void_p(int(d_work)),
+                                             int(work_bytes), _stream(stream)))
+
     # noise-constrained TV deconvolution (include/fdr.h): the free-boundary call with mu chosen from the noise level
     def tv_deconv_auto(self, img, sigma=0.0, rho=2.0, iterations=100, weights=None, tau=0.0, nu=0.0, anisotropic=False, nonneg=False,
                        norm_area=NORM_NONE, full_plane=False):
@@ -1584,6 +1653,50 @@ def tvDeblurFree_RGB(channels, psf, mu, rho=2.0, iterations=50, nonneg=False, de
                                      nonneg, norm_area, False, coupled)
     for i in range(len(channels)):
         channels[i] = out[i]
+
+
+def tiled_layout(rows, cols, prows, pcols, params):
+    """fdr_tiled_layout_get: how a rows x cols picture is tiled by params (a TiledParams) for a prows x pcols PSF.  Pure host."""
+    lay = TiledLayoutC()
+    _check(lib.fdr_tiled_layout_get(int(rows), int(cols), int(prows), int(pcols), ctypes.byref(params), ctypes.byref(lay)))
+    return TiledLayout(lay.tiles_r, lay.tiles_c, lay.win_rows, lay.win_cols, lay.min_M, lay.min_N, lay.work_bytes)
+
+
+def tiled_tile_origin(rows, cols, params, a, b):
+    """fdr_tiled_tile_origin: (y, x) of tile (a, b).  Pure host."""
+    y, x = ctypes.c_int(0), ctypes.c_int(0)
+    _check(lib.fdr_tiled_tile_origin(int(rows), int(cols), ctypes.byref(params), int(a), int(b), ctypes.byref(y), ctypes.byref(x)))
+    return y.value, x.value
+
+
+def _tiled_psf_shape(psf_or_psfs):
+    psfs = np.asarray(psf_or_psfs, dtype=np.float32)
+    if psfs.ndim not in (2, 3):
+        raise ValueError("psfs must be one PSF (2-D) or a stack of PSFs (3-D)")
+    return psfs, psfs.shape[-2], psfs.shape[-1]
+
+
+def restoreTiled_myfft(img, psf_or_psfs, params, weights=None, device=0):
+    """Sectioned restoration of one channel of any size: the smallest tile plan of tiled_layout, the tiles by params.method on the
+    device, the blended picture back.  psf_or_psfs and weights as Plan.restore_tiled."""
+    img = np.asarray(img, dtype=np.float32)
+    psfs, prows, pcols = _tiled_psf_shape(psf_or_psfs)
+    lay = tiled_layout(img.shape[0], img.shape[1], prows, pcols, params)
+    with Plan(lay.min_M, lay.min_N, MODE_FAST, device) as p:
+        return p.restore_tiled(img, psfs, params, weights)
+
+
+def restoreTiled_RGB(channels, psf_or_psfs, params, weights=None, device=0):
+    """fft_gpu::restoreTiled_RGB: replaces every element of `channels` (float32 planes of one size) in place with its sectioned
+    restoration, one tiled call per channel on one tile plan -- the bits of restoreTiled_myfft per channel."""
+    if not channels:
+        return
+    psfs, prows, pcols = _tiled_psf_shape(psf_or_psfs)
+    r, c = np.asarray(channels[0]).shape
+    lay = tiled_layout(r, c, prows, pcols, params)
+    with Plan(lay.min_M, lay.min_N, MODE_FAST, device) as p:
+        for i in range(len(channels)):
+            channels[i] = p.restore_tiled(channels[i], psfs, params, weights)
 
 
 def tvDeblurAuto_myfft(img, psf, sigma=0.0, rho=2.0, iterations=100, weights=None, tau=0.0, nu=0.0, anisotropic=False, nonneg=False, device=0,

@@ -232,6 +232,9 @@ struct fdr_plan {
     double* rg_cand = nullptr;  // kRegMaxCurve (K, gamma) pairs
     double* rg_res = nullptr;   // kRegMaxCurve (rho, trace) pairs
     std::vector<double> rg_cand_host, rg_res_host;
+    // sectioned restoration (fdr_restore_tiled_f32*): the host copy of the last call's weight tables (one entry per picture row, then one
+    // per picture column), kept here while the upload may still read it; everything else of such a call lies in the caller's workspace
+    std::vector<fdr::TiledCover> tl_tab_host;
     fdr::PassTimer timer;
     // the reference Profiler's buckets (fdr_plan_phase_times): resolved sums + event pairs not read back yet
     struct PhaseRec { hipEvent_t a, b; int phase; };

@@ -440,4 +440,29 @@ struct MixColArgs {
 hipError_t launch_mixed_rows(MixRowKind kind, const MixRowArgs& a, int blocks, hipStream_t s);
 hipError_t launch_mixed_cols(MixColKind kind, const MixColArgs& a, int npanels, hipStream_t s);
 
+// (fdr_tiled.hip) sectioned restoration (fdr_restore_tiled_f32*): the blend of the staged tile windows into the picture and the roll
+// that centres a PSF in a plane.
+// What covers one picture row (or column): the first covering tile, how many follow it (0 .. 3; 0 only in the padding of the column
+// table) and their normalised weights, in tile order.  Built on the host (fdr_api_tiled.hip), 32 bytes so that an entry is two 16-byte loads.
+constexpr int kTiledMaxCover = 3;
+struct alignas(16) TiledCover {
+    int first, count;
+    float w[kTiledMaxCover];
+    int pad[3];
+};
+static_assert(sizeof(TiledCover) == 32, "an entry is two 16-byte loads");
+// One axis of the tiling: n tiles of `win` pixels, tile a at min(a step, last)
+struct TiledAxis { int n, win, step, last; };
+__host__ __device__ __forceinline__ int tiled_origin(const TiledAxis& ax, int a) {
+    const long long o = (long long)a * ax.step;
+    return o < ax.last ? (int)o : ax.last;
+}
+// out[y, x] = sum over the covering tile rows a (outer) and tile columns b (inner), ascending, of (Wy_a(y) Wx_b(x)) o_ab[y - y_a, x - x_b],
+// every product and sum rounded on its own, from +0.  `stage` holds the windows dense, tile (a, b) at (a ac.n + b) ar.win ac.win;
+// rtab has `rows` entries, ctab `cols` rounded up to a multiple of four (count 0 in the padding).  Any out pointer and stride.
+hipError_t launch_tiled_blend(const float* stage, const TiledCover* rtab, const TiledCover* ctab, TiledAxis ar, TiledAxis ac, float* out, int rows,
+                              int cols, int out_stride, hipStream_t s);
+// plane (M x N, dense) = the prows x pcols PSF (row stride pstride) rolled by (-(prows / 2), -(pcols / 2)), zero elsewhere; prows <= M, pcols <= N
+hipError_t launch_tiled_psf_centre(const float* psf, int prows, int pcols, int pstride, float* plane, int M, int N, hipStream_t s);
+
 }  // namespace fdr

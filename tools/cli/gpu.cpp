@@ -1,5 +1,7 @@
 // gpu.cpp -- ./gpu <img-path> <psf-length> <psf-angle> | auto auto [--any-blur] | defocus <radius|auto> | blind <size>  [--out file] [--mode fast|parity] [--norm padded|cropped] [--host-epilogue]
 //           [--cls gamma|auto] [--k K|auto] [--reg gcv|discrepancy] [--sigma s] [--pad zero|smooth] [--rl iterations|auto [--accel] [--rl-tv lambda [--rl-tv-eps e] [--rl-tv-color]] [--free-boundary [--mask mask.png]] [--rl-max n] [--rl-stop residual|kl] [--gain g] [--rl-check c]] [--tv mu [--tv-iters n] [--tv-rho r] [--tv-color | --free-boundary [--mask mask.png]]]
+// `--rl n|--tv mu --free-boundary --tile T [--overlap O]`: the leg is fft_gpu::restoreTiled_RGB -- overlapping T x T tiles (O pixels shared, default T / 8),
+// each restored as a crop of a larger scene with the PSF centred, blended and normalised over the picture; one PSF, --mask as before.
 // `--tv mu --free-boundary`: the TV leg is fft_gpu::tvDeblurFree_RGB (the picture is a crop of a larger scene; --mask as for --rl); --tv-color has no such form.
 // `--tv auto [--sigma s] [--tv-tau t] [--tv-iters n] [--tv-rho r] [--mask mask.png]`: the TV leg is fft_gpu::tvDeblurAuto_RGB -- the free-boundary
 // iteration with mu chosen in every step from the noise level (--sigma, else estimated per channel; the ball is t sigma^2 S, t default 1; n default
@@ -117,6 +119,7 @@ int main(int argc, char** argv) {
     bool rl_tv_opts = false, rl_tv_color = false;  // --rl-tv-color: the channels under one vectorial TV prior (coupled)
     bool free_boundary = false;  // --free-boundary: the --rl leg is fft_gpu::richardsonLucyFree_RGB (the picture is a crop of a larger scene)
     string mask_path;            // --mask file: pixels that are 0 in it (any channel counts) get weight 0, the others weight 1
+    int tile = 0, tile_overlap = -1;  // --tile T [--overlap O]: the free-boundary --rl n / --tv mu leg is fft_gpu::restoreTiled_RGB (default O = T / 8)
     float tv_mu = -1.f, tv_rho = 2.0f;  // --tv mu: a timed total-variation leg (fft_gpu::tvDeblur_RGB); its planes are the written result
     int tv_iterations = 50;
     bool tv_opts = false;
@@ -177,6 +180,8 @@ int main(int argc, char** argv) {
         else if (a == "--rl-tv-color") { rl_tv_opts = true; rl_tv_color = true; }
         else if (a == "--free-boundary") free_boundary = true;
         else if (a == "--mask" && i + 1 < argc) mask_path = argv[++i];
+        else if (a == "--tile" && i + 1 < argc) tile = atoi(argv[++i]);
+        else if (a == "--overlap" && i + 1 < argc) tile_overlap = atoi(argv[++i]);
         else if (a == "--psf-hold" && i + 1 < argc) { blind_opts = true; psf_hold = atoi(argv[++i]); }
         else if (a == "--psf-sigma" && i + 1 < argc) { blind_opts = true; psf_sigma = atof(argv[++i]); }
         else if (a == "--psf-out" && i + 1 < argc) { blind_opts = true; psf_out_path = argv[++i]; }
@@ -208,6 +213,14 @@ int main(int argc, char** argv) {
         (!mask_path.empty() && !free_boundary && !tv_auto)) {
         cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle>\n";
         return -1;
+    }
+    // --tile belongs to the free-boundary form of --rl n or --tv mu, plain: sectioning has no accelerated, TV-prior, data-stopped or blind form
+    if (tile != 0 || tile_overlap != -1) {
+        if (tile < 1 || !free_boundary || accel || rl_tv_opts || rl_auto || tv_auto || tv_color || blind || (tile_overlap != -1 && (tile_overlap < 0 || tile_overlap > tile / 2))) {
+            cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle> --rl <n>|--tv <mu> --free-boundary --tile <T> [--overlap <O in 0 .. T/2>] [--mask m.png]\n";
+            return -1;
+        }
+        if (tile_overlap == -1) tile_overlap = tile / 8;
     }
     // --rl-tv belongs to --rl n; lambda in [0, FDR_RLTV_MAX_LAMBDA], eps finite and >= 0; the prior has no accelerated, data-stopped or blind form
     if (rl_tv_opts) {
@@ -423,12 +436,18 @@ int main(int argc, char** argv) {
     } else if (rl_iterations >= 0) {  // Richardson-Lucy on the same channels: its planes become the written result
         vector<Mat> rl = input;
         t_start = high_resolution_clock::now();
-        if (rl_tv_opts) fft_gpu::richardsonLucyTV_RGB(rl, psf, rl_iterations, rl_tv, rl_tv_eps, free_boundary, weights, rl_tv_color);
+        if (tile > 0) {
+            fft_gpu::TiledOptions to;
+            to.method = FDR_TILED_RL_FREE; to.tile = tile; to.overlap = tile_overlap; to.iterations = rl_iterations; to.norm_area = FDR_NORM_CROPPED;
+            fft_gpu::restoreTiled_RGB(rl, psf, to, weights);
+        }
+        else if (rl_tv_opts) fft_gpu::richardsonLucyTV_RGB(rl, psf, rl_iterations, rl_tv, rl_tv_eps, free_boundary, weights, rl_tv_color);
         else if (free_boundary) fft_gpu::richardsonLucyFree_RGB(rl, psf, rl_iterations, weights, accel);
         else fft_gpu::richardsonLucy_RGB(rl, psf, rl_iterations, accel);
         t_end = high_resolution_clock::now();
         cout << "Deblurring 3 channels took(gpu[richardson-lucy " << (free_boundary ? "free-boundary " : "") << rl_iterations
              << (accel ? " accelerated" : "");
+        if (tile > 0) cout << " tile " << tile << " overlap " << tile_overlap;
         if (rl_tv_opts) cout << " tv " << rl_tv;
         cout << "]): " << getElapsedMs(t_start, t_end) << " ms\n";
         channels = rl;
@@ -439,6 +458,12 @@ int main(int argc, char** argv) {
         vector<fdr_tv_auto_result> chosen;
         t_start = high_resolution_clock::now();
         if (tv_auto) chosen = fft_gpu::tvDeblurAuto_RGB(tvc, psf, reg_sigma, tv_iterations, tv_rho, tv_tau, weights);
+        else if (tile > 0) {
+            fft_gpu::TiledOptions to;
+            to.method = FDR_TILED_TV_FREE; to.tile = tile; to.overlap = tile_overlap; to.iterations = tv_iterations; to.mu = tv_mu; to.rho = tv_rho;
+            to.norm_area = FDR_NORM_CROPPED;
+            fft_gpu::restoreTiled_RGB(tvc, psf, to, weights);
+        }
         else if (free_boundary) fft_gpu::tvDeblurFree_RGB(tvc, psf, tv_mu, tv_iterations, tv_rho, weights);
         else fft_gpu::tvDeblur_RGB(tvc, psf, tv_mu, tv_iterations, tv_rho, tv_color);
         t_end = high_resolution_clock::now();
@@ -448,7 +473,9 @@ int main(int argc, char** argv) {
         cout << "Deblurring 3 channels took(gpu[total-variation " << (free_boundary && !tv_auto ? "free-boundary " : "");
         if (tv_auto) cout << "auto";
         else cout << "mu " << tv_mu;
-        cout << " rho " << tv_rho << " n " << tv_iterations << (tv_color ? " colour" : "") << "]): " << getElapsedMs(t_start, t_end) << " ms\n";
+        cout << " rho " << tv_rho << " n " << tv_iterations << (tv_color ? " colour" : "");
+        if (tile > 0) cout << " tile " << tile << " overlap " << tile_overlap;
+        cout << "]): " << getElapsedMs(t_start, t_end) << " ms\n";
         channels = tvc;
     }
 
