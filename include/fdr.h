@@ -890,6 +890,77 @@ int fdr_tv_deconv_auto_batch_f32(fdr_plan* plan, const float* imgs_host, size_t 
                                  const fdr_tv_auto_batch_params* params, const double* sigmas, fdr_tv_auto_result* results,
                                  double* trace_host, size_t trace_pitch);
 
+/* -- Poisson-likelihood TV deconvolution: fdr_tv_deconv_free_f32 for photon-limited pictures.  The data
+ *    term is the negative Poisson log-likelihood of the counts instead of least squares (PIDAL, Figueiredo & Bioucas-Dias 2010;
+ *    Setzer, Steidl & Teuber 2010), convex like the free call's, so the iteration settles where fdr_richardson_lucy_tv_f32 cycles:
+ *        minimise over x (M x N):  mu sum m [ (blur(x) + b) - d+ log(blur(x) + b) ] + TV(x)
+ *    d+ = max(d, 0); m = the weights on the window, 0 elsewhere; b = background >= 0, a known level in the units of the data (sky,
+ *    dark current); the detector's gain is part of mu: mu = photons per unit times the weight wanted on the likelihood.  The
+ *    iteration is that of fdr_tv_deconv_free_f32, every line of it, with the data step replaced: for a window pixel with m > 0
+ *            e = c + q;  k = mu m / nu;  a = e + b - k;  y = the root >= 0 of y^2 - a y - k d+ = 0;  s = y - b;  q = e - s;  r = s - q
+ *    with the root formed without cancellation, rt = sqrt(a a + 4 k d+), y = a >= 0 ? (a + rt) / 2 : 2 k d+ / (rt - a); for m = 0,
+ *    as outside the window, s = e.  s + b >= 0 always.  Every operation is a correctly rounded float operation in the order
+ *    tvpoisson_data_pixel (csrc/fdr_kernels.hpp) states, so a float32 model repeats the step bit for bit.  The start is x = pad(d);
+ *    nu = 0 selects rho; the output window, nonneg and norm_area as in the free call; n = 0 returns pad(d).  Negative data are
+ *    clamped, not refused; a NaN in the data stays a NaN in the output.
+ *      fdr_tv_deconv_poisson_f32*        one image: arguments, plans, workspaces (none beyond the free call's) and passes as
+ *                                        fdr_tv_deconv_free_f32*; the data step has its own pass name.
+ *      fdr_tv_deconv_poisson_batch_f32*  `count` crops as fdr_tv_deconv_free_batch_f32*: FDR_TV_COUPLE_NONE gives every image the
+ *                                        bits of the single _dev call, for every group, tail, pitch and alignment (group = 1 is the
+ *                                        loop of single calls); FDR_TV_COUPLE_CHANNELS shares the shrinkage by the joint gradient
+ *                                        norm, the data step stays per channel (count <= group, isotropic; count = 1: the single
+ *                                        call's bits).
+ *      fdr_tv_poisson_step_f32_dev       the data step alone on the window rows x cols of two dense M x N planes of the caller's
+ *                                        (row stride N, 16-byte aligned): c = blur(x) and q in, r and the new q out; nothing outside
+ *                                        the window is read or written.  d_img and d_weights (NULL = 1) are rows x cols windows
+ *                                        of any alignment.  nu must be > 0 here.  Needs no PSF; asynchronous on `stream`.
+ *      fdr_tv_poisson_step_group_f32_dev the same for `count` (1 .. 8) images in one launch: image k's planes at d_c + k c_pitch and
+ *                                        d_q + k q_pitch (pitches >= M N, multiples of 4), its data at d_imgs + k img_pitch, one
+ *                                        weights window for all; image k gets the bits of the single step.
+ *    FDR_ERR_ARG, before any device work and with the plan usable afterwards: whatever fdr_tv_deconv_free_f32* (the batch:
+ *    fdr_tv_deconv_free_batch_f32*) refuses, and a background that is negative or not finite; the steps: a window outside the plan,
+ *    a stride below cols, mu or nu not finite or <= 0, planes that are misaligned or overlap each other, the data or the weights. */
+typedef struct fdr_tv_poisson_params {
+    float mu;         /* weight of the likelihood, > 0: photons per unit of the data times the weight wanted */
+    float rho;        /* ADMM penalty of z = D x, > 0 */
+    float nu;         /* ADMM penalty of s = blur(x), >= 0; 0 selects rho */
+    float background; /* b >= 0, in the units of the data */
+    int iterations;   /* >= 0 */
+    int anisotropic;  /* 0: isotropic TV, else anisotropic */
+    int nonneg;       /* != 0: the output is max(x, 0) */
+    int norm_area;    /* FDR_NORM_NONE / FDR_NORM_CROPPED / FDR_NORM_PADDED, over the output window */
+    int out_rows;     /* rows .. M */
+    int out_cols;     /* cols .. N */
+} fdr_tv_poisson_params;
+typedef struct fdr_tv_poisson_batch_params {
+    float mu;         /* weight of the likelihood, > 0 */
+    float rho;        /* ADMM penalty of z = D x, > 0 */
+    float nu;         /* ADMM penalty of s = blur(x), >= 0; 0 selects rho */
+    float background; /* b >= 0, one for all images */
+    int iterations;   /* >= 0 */
+    int anisotropic;  /* 0: isotropic TV, else anisotropic (FDR_TV_COUPLE_NONE only) */
+    int nonneg;       /* != 0: the output is max(x, 0) */
+    int norm_area;    /* FDR_NORM_NONE / FDR_NORM_CROPPED / FDR_NORM_PADDED, per image over its output window */
+    int out_rows;     /* rows .. M */
+    int out_cols;     /* cols .. N */
+    int coupling;     /* FDR_TV_COUPLE_NONE / FDR_TV_COUPLE_CHANNELS */
+} fdr_tv_poisson_batch_params;
+int fdr_tv_deconv_poisson_f32(fdr_plan* plan, const float* img_host, int rows, int cols, int stride, const float* weights_host, int wstride,
+                              float* out_host, int out_stride, const fdr_tv_poisson_params* params);
+int fdr_tv_deconv_poisson_f32_dev(fdr_plan* plan, const float* d_img, int rows, int cols, int stride, const float* d_weights, int wstride,
+                                  float* d_out, int out_stride, const fdr_tv_poisson_params* params, void* stream);
+int fdr_tv_deconv_poisson_batch_f32_dev(fdr_plan* plan, const float* d_imgs, size_t img_pitch, int count, int rows, int cols, int stride,
+                                        const float* d_weights, int wstride, float* d_out, size_t out_pitch, int out_stride,
+                                        const fdr_tv_poisson_batch_params* params, void* stream);
+int fdr_tv_deconv_poisson_batch_f32(fdr_plan* plan, const float* imgs_host, size_t img_pitch, int count, int rows, int cols, int stride,
+                                    const float* weights_host, int wstride, float* out_host, size_t out_pitch, int out_stride,
+                                    const fdr_tv_poisson_batch_params* params);
+int fdr_tv_poisson_step_f32_dev(fdr_plan* plan, float* d_c, float* d_q, const float* d_img, int rows, int cols, int stride,
+                                const float* d_weights, int wstride, float mu, float nu, float background, void* stream);
+int fdr_tv_poisson_step_group_f32_dev(fdr_plan* plan, float* d_c, size_t c_pitch, float* d_q, size_t q_pitch, const float* d_imgs,
+                                      size_t img_pitch, int count, int rows, int cols, int stride, const float* d_weights, int wstride,
+                                      float mu, float nu, float background, void* stream);
+
 /* -- sectioned restoration (Trussell & Hunt 1978; Nagy & O'Leary 1998): a picture of any size, larger than a
  *    plan can be, is cut into overlapping tiles, every tile is restored as a crop of a larger scene by the free-boundary iteration
  *    of the chosen method on ONE tile plan, with one PSF for all tiles or one per tile (a blur that changes across the frame), and

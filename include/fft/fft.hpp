@@ -580,6 +580,65 @@ inline void tvDeblurFree_RGB(std::vector<Mat>& channels, const Mat& psf, float m
                              bool coupled = false) {
     tvDeblurFree_RGB(channels, psf, mu, iterations, rho, weights, defaults(), coupled);
 }
+// Poisson-likelihood total-variation deconvolution (fdr_tv_deconv_poisson_f32, include/fdr.h) of every channel, in place, for a
+// photon-limited picture that is a crop of a larger scene: tvDeblurFree_RGB with the data term mu sum m [(blur(x) + b) - d+ log(blur(x)
+// + b)], b = background >= 0 in the units of the channels, mu = photons per unit times the weight wanted on the likelihood.  The
+// plan, operator PSF, `weights`, penalties, clamp and normalisation of tvDeblurFree_RGB; the channels go through ONE batched call
+// (fdr_tv_deconv_poisson_batch_f32) with the bits of the per-channel calls, channels of different sizes or types one by one.
+// coupled: vectorial TV, the data step per channel (at most 8 channels of one size).
+inline void tvDeblurPoisson_RGB(std::vector<Mat>& channels, const Mat& psf, float mu, int iterations, float rho, const Mat& weights, float background,
+                                const Options& o, bool coupled = false) {
+    if (channels.empty()) return;
+    const int rows = channels[0].rows, cols = channels[0].cols, count = (int)channels.size();
+    if (!weights.empty() && (weights.rows != rows || weights.cols != cols || weights.type() != CV_32F)) {
+        std::cerr << "tvDeblurPoisson_RGB: the weights must be CV_32F and have the picture's size\n";
+        exit(1);
+    }
+    bool created = false;
+    PlanCacheSettle settle_;
+    fdr_plan* plan = plan_cache().get(o.device, std::max(8, nextPowerOfTwo(rows + psf.rows - 1)), std::max(32, nextPowerOfTwo(cols + psf.cols - 1)),
+                                      FDR_MODE_FAST, &created);
+    Mat psfc = psf.isContinuous() ? psf : psf.clone();
+    FDR_CHECK(fdr_set_operator_psf(plan, psfc.ptr<float>(0), psf.rows, psf.cols, psf.cols));
+    Mat w = weights.empty() || weights.isContinuous() ? weights : weights.clone();
+    bool same = true;
+    for (const Mat& c : channels) same = same && c.rows == rows && c.cols == cols && c.type() == CV_32F;
+    if (same || coupled) {
+        if (!same) {
+            std::cerr << "tvDeblurPoisson_RGB: the coupled form needs CV_32F channels of one size\n";
+            exit(1);
+        }
+        const size_t px = (size_t)rows * cols;
+        std::vector<float> in(px * count), out(px * count);
+        for (int i = 0; i < count; ++i)
+            for (int r = 0; r < rows; ++r) std::copy(channels[i].ptr<float>(r), channels[i].ptr<float>(r) + cols, in.begin() + i * px + (size_t)r * cols);
+        const fdr_tv_poisson_batch_params bp = {mu, rho, 0.f, background, iterations, 0, 1, o.norm_area, rows, cols,
+                                                coupled ? FDR_TV_COUPLE_CHANNELS : FDR_TV_COUPLE_NONE};
+        FDR_CHECK(fdr_plan_set_batching(plan, 1, std::min(count, 8)));
+        const int rc = fdr_tv_deconv_poisson_batch_f32(plan, in.data(), px, count, rows, cols, cols, w.empty() ? nullptr : w.ptr<float>(0), cols,
+                                                       out.data(), px, cols, &bp);
+        FDR_CHECK(fdr_plan_set_batching(plan, 1, 1));  // the cached plan goes back as it came
+        FDR_CHECK(rc);
+        for (int i = 0; i < count; ++i) {
+            Mat m(rows, cols, CV_32F);
+            std::copy(out.begin() + i * px, out.begin() + (i + 1) * px, m.ptr<float>(0));
+            channels[i] = m;
+        }
+        return;
+    }
+    for (Mat& c : channels) {
+        Mat src = c.isContinuous() ? c : c.clone();
+        Mat out(c.rows, c.cols, CV_32F);
+        const fdr_tv_poisson_params prm = {mu, rho, 0.f, background, iterations, 0, 1, o.norm_area, c.rows, c.cols};
+        FDR_CHECK(fdr_tv_deconv_poisson_f32(plan, src.ptr<float>(0), c.rows, c.cols, c.cols, w.empty() ? nullptr : w.ptr<float>(0), cols,
+                                            out.ptr<float>(0), c.cols, &prm));
+        c = out;
+    }
+}
+inline void tvDeblurPoisson_RGB(std::vector<Mat>& channels, const Mat& psf, float mu, int iterations = 50, float rho = 2.0f, const Mat& weights = Mat(),
+                                float background = 0.f, bool coupled = false) {
+    tvDeblurPoisson_RGB(channels, psf, mu, iterations, rho, weights, background, defaults(), coupled);
+}
 // Sectioned restoration (fdr_restore_tiled_f32, include/fdr.h) of every channel, in place, for a picture of any size: overlapping
 // tiles of `tile` pixels (a picture no larger is one tile), `overlap` of them shared with the neighbour, every tile restored as a
 // crop of a larger scene by the free-boundary iteration of `method` with the PSF taken as CENTRED (the result is registered with the

@@ -108,6 +108,20 @@ class TvFreeBatchParams(ctypes.Structure):
                 ("out_cols", ctypes.c_int), ("coupling", ctypes.c_int)]
 
 
+class TvPoissonParams(ctypes.Structure):
+    """fdr_tv_poisson_params of include/fdr.h"""
+    _fields_ = [("mu", ctypes.c_float), ("rho", ctypes.c_float), ("nu", ctypes.c_float), ("background", ctypes.c_float),
+                ("iterations", ctypes.c_int), ("anisotropic", ctypes.c_int), ("nonneg", ctypes.c_int), ("norm_area", ctypes.c_int),
+                ("out_rows", ctypes.c_int), ("out_cols", ctypes.c_int)]
+
+
+class TvPoissonBatchParams(ctypes.Structure):
+    """fdr_tv_poisson_batch_params of include/fdr.h"""
+    _fields_ = [("mu", ctypes.c_float), ("rho", ctypes.c_float), ("nu", ctypes.c_float), ("background", ctypes.c_float),
+                ("iterations", ctypes.c_int), ("anisotropic", ctypes.c_int), ("nonneg", ctypes.c_int), ("norm_area", ctypes.c_int),
+                ("out_rows", ctypes.c_int), ("out_cols", ctypes.c_int), ("coupling", ctypes.c_int)]
+
+
 class TvAutoBatchParams(ctypes.Structure):
     """fdr_tv_auto_batch_params of include/fdr.h"""
     _fields_ = [("sigma", ctypes.c_float), ("tau", ctypes.c_float), ("rho", ctypes.c_float), ("nu", ctypes.c_float),
@@ -374,6 +388,12 @@ def _signatures():
         "fdr_tv_deconv_free_batch_f32_dev": (ci, [vp, vp, sz, ci, ci, ci, ci, vp, ci, vp, sz, ci, P(TvFreeBatchParams), vp]),
         "fdr_tv_deconv_auto_batch_f32": (ci, [vp, vp, sz, ci, ci, ci, ci, vp, ci, vp, sz, ci, P(TvAutoBatchParams), vp, vp, vp, sz]),
         "fdr_tv_deconv_auto_batch_f32_dev": (ci, [vp, vp, sz, ci, ci, ci, ci, vp, ci, vp, sz, ci, P(TvAutoBatchParams), vp, vp, sz, vp]),
+        "fdr_tv_deconv_poisson_f32": (ci, [vp, vp, ci, ci, ci, vp, ci, vp, ci, P(TvPoissonParams)]),
+        "fdr_tv_deconv_poisson_f32_dev": (ci, [vp, vp, ci, ci, ci, vp, ci, vp, ci, P(TvPoissonParams), vp]),
+        "fdr_tv_deconv_poisson_batch_f32": (ci, [vp, vp, sz, ci, ci, ci, ci, vp, ci, vp, sz, ci, P(TvPoissonBatchParams)]),
+        "fdr_tv_deconv_poisson_batch_f32_dev": (ci, [vp, vp, sz, ci, ci, ci, ci, vp, ci, vp, sz, ci, P(TvPoissonBatchParams), vp]),
+        "fdr_tv_poisson_step_f32_dev": (ci, [vp, vp, vp, vp, ci, ci, ci, vp, ci, cf, cf, cf, vp]),
+        "fdr_tv_poisson_step_group_f32_dev": (ci, [vp, vp, sz, vp, sz, vp, sz, ci, ci, ci, ci, vp, ci, cf, cf, cf, vp]),
         "fdr_tiled_layout_get": (ci, [ci, ci, ci, ci, P(TiledParams), P(TiledLayoutC)]),
         "fdr_tiled_tile_origin": (ci, [ci, ci, P(TiledParams), ci, ci, P(ci), P(ci)]),
         "fdr_restore_tiled_f32_dev": (ci, [vp, vp, ci, ci, ci, vp, ci, vp, sz, ci, ci, ci, ci, vp, ci, P(TiledParams), vp, sz, vp]),
@@ -1024,6 +1044,52 @@ class Plan:
                                               ctypes.c_void_p(int(d_weights)) if d_weights else None, int(wstride),
                                               ctypes.c_void_p(int(d_out)), out_stride, ctypes.byref(prm), _stream(stream)))
 
+    # Poisson-likelihood TV deconvolution (include/fdr.h): the free-boundary call with the data step of the Poisson term
+    def tv_deconv_poisson(self, img, mu, rho=2.0, iterations=50, weights=None, nu=0.0, background=0.0, anisotropic=False, nonneg=False,
+                          norm_area=NORM_NONE, full_plane=False):
+        """tv_deconv_free for photon-limited pictures: `iterations` ADMM steps of mu sum m [(blur(x) + b) - img+ log(blur(x) + b)] +
+        TV(x), b = background >= 0 in the units of img, mu = photons per unit times the weight wanted on the likelihood.  weights, nu,
+        nonneg, norm_area and full_plane as tv_deconv_free (fdr_tv_deconv_poisson_f32)."""
+        img = np.ascontiguousarray(img, dtype=np.float32)
+        rows, cols = img.shape
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float32)
+            if w.shape != img.shape:
+                raise ValueError("weights must have the shape of img")
+        orows, ocols = (self.M, self.N) if full_plane else (rows, cols)
+        out = np.empty((orows, ocols), dtype=np.float32)
+        prm = TvPoissonParams(float(mu), float(rho), float(nu), float(background), int(iterations), int(bool(anisotropic)), int(bool(nonneg)),
+                              int(norm_area), orows, ocols)
+        _check(lib.fdr_tv_deconv_poisson_f32(self._h, _ptr(img), rows, cols, cols, _ptr(w) if w is not None else None, cols, _ptr(out), ocols,
+                                             ctypes.byref(prm)))
+        return out
+
+    def tv_deconv_poisson_dev(self, d_img, rows, cols, stride, d_out, out_stride, mu, rho=2.0, iterations=50, d_weights=None, wstride=0, nu=0.0,
+                              background=0.0, anisotropic=False, nonneg=False, norm_area=NORM_NONE, out_rows=None, out_cols=None, stream=None):
+        """the same on device pointers; out_rows x out_cols (default rows x cols, up to M x N) is the output window.  Asynchronous."""
+        prm = TvPoissonParams(float(mu), float(rho), float(nu), float(background), int(iterations), int(bool(anisotropic)), int(bool(nonneg)),
+                              int(norm_area), int(rows if out_rows is None else out_rows), int(cols if out_cols is None else out_cols))
+        _check(lib.fdr_tv_deconv_poisson_f32_dev(self._h, ctypes.c_void_p(int(d_img)), rows, cols, stride,
+                                                 ctypes.c_void_p(int(d_weights)) if d_weights else None, int(wstride),
+                                                 ctypes.c_void_p(int(d_out)), out_stride, ctypes.byref(prm), _stream(stream)))
+
+    def tv_poisson_step_dev(self, d_c, d_q, d_img, rows, cols, stride, mu, nu, background=0.0, d_weights=None, wstride=0, stream=None):
+        """fdr_tv_poisson_step_f32_dev: the data step of tv_deconv_poisson alone, in place on the rows x cols window of the dense M x N
+        device planes d_c (blur(x) in, r out) and d_q; d_img and d_weights (None = 1) are device windows.  Asynchronous."""
+        _check(lib.fdr_tv_poisson_step_f32_dev(self._h, ctypes.c_void_p(int(d_c)), ctypes.c_void_p(int(d_q)), ctypes.c_void_p(int(d_img)), rows,
+                                               cols, stride, ctypes.c_void_p(int(d_weights)) if d_weights else None, int(wstride), float(mu),
+                                               float(nu), float(background), _stream(stream)))
+
+    def tv_poisson_step_group_dev(self, d_c, c_pitch, d_q, q_pitch, d_imgs, img_pitch, count, rows, cols, stride, mu, nu, background=0.0,
+                                  d_weights=None, wstride=0, stream=None):
+        """fdr_tv_poisson_step_group_f32_dev: tv_poisson_step_dev on `count` (1 .. 8) images in one launch, image k's planes at d_c + k
+        c_pitch and d_q + k q_pitch, its data at d_imgs + k img_pitch (elements), one weights window for all.  Asynchronous."""
+        _check(lib.fdr_tv_poisson_step_group_f32_dev(self._h, ctypes.c_void_p(int(d_c)), int(c_pitch), ctypes.c_void_p(int(d_q)), int(q_pitch),
+                                                     ctypes.c_void_p(int(d_imgs)), int(img_pitch), int(count), rows, cols, stride,
+                                                     ctypes.c_void_p(int(d_weights)) if d_weights else None, int(wstride), float(mu), float(nu),
+                                                     float(background), _stream(stream)))
+
     # sectioned restoration (include/fdr.h): overlapping tiles on this plan, blended; one PSF for all tiles or one per tile
     def restore_tiled(self, img, psfs, params, weights=None):
         """The picture img (host array, any size) restored in overlapping tiles on this tile plan by the free-boundary iteration of
@@ -1152,6 +1218,31 @@ class Plan:
         _check(lib.fdr_tv_deconv_free_batch_f32_dev(self._h, ctypes.c_void_p(int(d_imgs)), img_pitch, count, rows, cols, stride,
                                                     ctypes.c_void_p(int(d_weights)) if d_weights else None, int(wstride),
                                                     ctypes.c_void_p(int(d_out)), out_pitch, out_stride, ctypes.byref(prm), _stream(stream)))
+
+    def tv_deconv_poisson_batch(self, imgs, mu, rho=2.0, iterations=50, weights=None, nu=0.0, background=0.0, anisotropic=False, nonneg=False,
+                                norm_area=NORM_NONE, full_plane=False, coupled=False):
+        """Host arrays [count, rows, cols] in, [count, rows, cols] (full_plane: [count, M, N]) out: tv_deconv_poisson per image with one
+        weights plane and one background for all, several per launch (set_batching); coupled: vectorial TV on the images as the
+        channels of one picture, the data step per channel (fdr_tv_deconv_poisson_batch_f32)."""
+        imgs, cnt, rows, cols, w, orows, ocols, out = self._crop_batch_args(imgs, weights, full_plane)
+        prm = TvPoissonBatchParams(float(mu), float(rho), float(nu), float(background), int(iterations), int(bool(anisotropic)),
+                                   int(bool(nonneg)), int(norm_area), orows, ocols, TV_COUPLE_CHANNELS if coupled else TV_COUPLE_NONE)
+        _check(lib.fdr_tv_deconv_poisson_batch_f32(self._h, _ptr(imgs), rows * cols, cnt, rows, cols, cols, _ptr(w) if w is not None else None,
+                                                   cols, _ptr(out), orows * ocols, ocols, ctypes.byref(prm)))
+        return out
+
+    def tv_deconv_poisson_batch_dev(self, d_imgs, img_pitch, count, rows, cols, stride, d_out, out_pitch, out_stride, mu, rho=2.0,
+                                    iterations=50, d_weights=None, wstride=0, nu=0.0, background=0.0, anisotropic=False, nonneg=False,
+                                    norm_area=NORM_NONE, out_rows=None, out_cols=None, coupled=False, stream=None):
+        """fdr_tv_deconv_poisson_batch_f32_dev: tv_deconv_poisson_dev on `count` windows laid out as in tv_deconv_free_batch_dev, in
+        launch groups of the plan's `group`; coupled: one shrinkage for the channels of one picture (count <= group, isotropic).
+        Asynchronous."""
+        prm = TvPoissonBatchParams(float(mu), float(rho), float(nu), float(background), int(iterations), int(bool(anisotropic)),
+                                   int(bool(nonneg)), int(norm_area), int(rows if out_rows is None else out_rows),
+                                   int(cols if out_cols is None else out_cols), TV_COUPLE_CHANNELS if coupled else TV_COUPLE_NONE)
+        _check(lib.fdr_tv_deconv_poisson_batch_f32_dev(self._h, ctypes.c_void_p(int(d_imgs)), img_pitch, count, rows, cols, stride,
+                                                       ctypes.c_void_p(int(d_weights)) if d_weights else None, int(wstride),
+                                                       ctypes.c_void_p(int(d_out)), out_pitch, out_stride, ctypes.byref(prm), _stream(stream)))
 
     def tv_deconv_auto_batch(self, imgs, sigma=0.0, rho=2.0, iterations=100, weights=None, tau=0.0, nu=0.0, anisotropic=False, nonneg=False,
                              norm_area=NORM_NONE, full_plane=False, sigmas=None, coupled=False):
@@ -1651,6 +1742,39 @@ def tvDeblurFree_RGB(channels, psf, mu, rho=2.0, iterations=50, nonneg=False, de
         p.set_batching(1, min(len(channels), 8))
         out = p.tv_deconv_free_batch(np.stack([np.asarray(c, dtype=np.float32) for c in channels]), mu, rho, iterations, weights, nu, False,
                                      nonneg, norm_area, False, coupled)
+    for i in range(len(channels)):
+        channels[i] = out[i]
+
+
+def tvDeblurPoisson_myfft(img, psf, mu, rho=2.0, iterations=50, weights=None, nu=0.0, background=0.0, anisotropic=False, nonneg=False,
+                          device=0, norm_area=NORM_NONE, full_plane=False):
+    """Poisson-likelihood total-variation deconvolution of one photon-limited channel that is a crop of a larger scene: the plan of
+    tvDeblurFree_myfft, `iterations` ADMM steps on the device, the window (or with full_plane the whole plan) back.  psf lies top-left
+    in the plan; mu, background and weights as Plan.tv_deconv_poisson."""
+    img = np.asarray(img, dtype=np.float32)
+    psf = np.asarray(psf, dtype=np.float32)
+    M, N = _rlfree_plan_size(img.shape[0], img.shape[1], psf.shape[0], psf.shape[1])
+    with Plan(M, N, MODE_FAST, device) as p:
+        p.set_operator_psf(psf)
+        return p.tv_deconv_poisson(img, mu, rho, iterations, weights, nu, background, anisotropic, nonneg, norm_area, full_plane)
+
+
+def tvDeblurPoisson_RGB(channels, psf, mu, rho=2.0, iterations=50, nonneg=False, device=0, norm_area=NORM_NONE, weights=None, nu=0.0,
+                        background=0.0, coupled=False):
+    """fft_gpu::tvDeblurPoisson_RGB: replaces every element of `channels` (float32 planes of one size, at most 8 when coupled) in place
+    with its Poisson-likelihood total-variation estimate, from one plan (that of tvDeblurPoisson_myfft), one weights plane and one
+    background for all channels and one launch per pass -- the bits of tvDeblurPoisson_myfft per channel, or with coupled the
+    vectorial TV of the picture."""
+    if not channels:
+        return
+    psf = np.asarray(psf, dtype=np.float32)
+    r, c = np.asarray(channels[0]).shape
+    M, N = _rlfree_plan_size(r, c, psf.shape[0], psf.shape[1])
+    with Plan(M, N, MODE_FAST, device) as p:
+        p.set_operator_psf(psf)
+        p.set_batching(1, min(len(channels), 8))
+        out = p.tv_deconv_poisson_batch(np.stack([np.asarray(c, dtype=np.float32) for c in channels]), mu, rho, iterations, weights, nu,
+                                        background, False, nonneg, norm_area, False, coupled)
     for i in range(len(channels)):
         channels[i] = out[i]
 

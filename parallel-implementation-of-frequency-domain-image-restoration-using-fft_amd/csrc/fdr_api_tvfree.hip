@@ -17,6 +17,7 @@ const char* const kPassTfInit = "TVF init: x = pad(d), w = q = 0";
 const char* const kPassTfData = "TVF data: s, q, r = 2s-e (window)";
 const char* const kPassTaNorm = "TVA norm+mu: res_e, res_c, S -> mu_k";
 const char* const kPassTaData = "TVA data: s, q, r = 2s-e (mu_k)";
+const char* const kPassTpData = "TVP data: Poisson s, q, r = 2s-e (window)";
 const char* const kPassTfSpatial = "TV spatial: shrink+dual+div (free)";
 const char* const kPassTfSpatialJoint = "TV spatial: joint shrink+dual+div (free)";  // the coupled kernel, all channels of a tile
 const char* const kPassTfSolve = "B' op cols: FFT*T*IFFT (TVF solve)";
@@ -58,8 +59,8 @@ int tvfree_prepare(fdr_plan* p, const char* fn, int group) {
 // windows by every data step
 int tvfree_group_dev(fdr_plan* p, const char* fn, fdr_plan::Slot* const* ws, int n, const float* const* d_imgs, int rows, int cols, int stride,
                      const float* d_w, int wstride, float* const* d_outs, int out_stride, const fdr_tv_free_params& prm, bool coupled, hipStream_t s,
-                     const TvAuto* au) {
-    if (n < 1 || n > kMaxGroup || n > p->tv_group || n > p->tf_group || (au && n > p->ta_group))
+                     const TvAuto* au, const TvPoisson* po) {
+    if (n < 1 || n > kMaxGroup || n > p->tv_group || n > p->tf_group || (au && n > p->ta_group) || (au && po))
         return fail(FDR_ERR_STATE, std::string(fn) + ": the free-boundary TV workspaces do not hold the group");
     const int M = p->M, N = p->N, iters = prm.iterations;
     const size_t P = (size_t)M * N, step = tv_image_stride(p);
@@ -98,6 +99,9 @@ int tvfree_group_dev(fdr_plan* p, const char* fn, fdr_plan::Slot* const* ws, int
             }
             ScopedPass t(p, s, kPassTaData);
             FDR_HIP(launch_tvauto_data_n(n, c, q, d_imgs, stride, d_w, wstride, rows, cols, M, N, p->ta_mu, nu, s));  // c becomes r
+        } else if (po) {  // the Poisson likelihood: another step on the same window, planes and bytes
+            ScopedPass t(p, s, kPassTpData);
+            FDR_HIP(launch_tvpoisson_data_n(n, c, q, d_imgs, stride, d_w, wstride, rows, cols, M, N, prm.mu, nu, po->background, s));  // c becomes r
         } else {
             ScopedPass t(p, s, kPassTfData);
             FDR_HIP(launch_tvfree_data_n(n, c, q, d_imgs, stride, d_w, wstride, rows, cols, M, N, prm.mu, nu, s));  // c becomes r
@@ -130,9 +134,9 @@ int tvfree_group_dev(fdr_plan* p, const char* fn, fdr_plan::Slot* const* ws, int
 }
 
 int tvfree_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, int cols, int stride, const float* d_w, int wstride, float* d_out,
-                    int out_stride, const fdr_tv_free_params& prm, hipStream_t s, const TvAuto* au) {
+                    int out_stride, const fdr_tv_free_params& prm, hipStream_t s, const TvAuto* au, const TvPoisson* po) {
     fdr_plan::Slot* w = &p->slots[0];
-    return tvfree_group_dev(p, fn, &w, 1, &d_img, rows, cols, stride, d_w, wstride, &d_out, out_stride, prm, false, s, au);
+    return tvfree_group_dev(p, fn, &w, 1, &d_img, rows, cols, stride, d_w, wstride, &d_out, out_stride, prm, false, s, au, po);
 }
 
 // The first free-boundary TV call of a plan, or the first on a larger group: q and c / r, two M x N planes per image of the group

@@ -14,10 +14,10 @@
 
 using namespace fdr;
 
-namespace {
+namespace fdr {
 
-// what both batched forms refuse beyond the single call on image 0 (checked by the caller), before any device work: an unknown
-// coupling, the coupled form with the anisotropic shrinkage or with more channels than the plan's launch group holds, and any output
+// what the batched forms (these and the Poisson one of fdr_api_tvpoisson.hip) refuse beyond the single call on image 0 (checked
+// by the caller), before any device work: an unknown coupling, the coupled form with the anisotropic shrinkage or with more channels than the plan's launch group holds, and any output
 // of the batch that overlaps any input or the weights (a later group still reads them after an earlier one has written its output)
 int crop_batch_check(const fdr_plan* p, const char* fn, const float* imgs, size_t img_pitch, int count, int rows, int cols, int stride,
                      const float* weights, int wstride, const float* out, size_t out_pitch, int out_stride, const fdr_tv_free_params& one,
@@ -35,6 +35,10 @@ int crop_batch_check(const fdr_plan* p, const char* fn, const float* imgs, size_
         return fail(FDR_ERR_ARG, std::string(fn) + ": the outputs of the batch overlap the weights");
     return FDR_OK;
 }
+
+}  // namespace fdr
+
+namespace {
 
 int free_batch_check(const fdr_plan* p, const char* fn, const float* imgs, size_t img_pitch, int count, int rows, int cols, int stride,
                      const float* weights, int wstride, const float* out, size_t out_pitch, int out_stride, const fdr_tv_free_batch_params& b,
@@ -127,8 +131,12 @@ int auto_batch_run(fdr_plan* p, const char* fn, const float* d_imgs, size_t img_
     return rc;
 }
 
+}  // namespace
+
+namespace fdr {
+
 // the dense copy of the host weights for one call (no plane of the workspace is free over the whole iteration)
-int stage_weights(const char* fn, const float* weights_host, int rows, int cols, int wstride, DeviceBuffer* d_w) {
+int stage_crop_weights(const char* fn, const float* weights_host, int rows, int cols, int wstride, DeviceBuffer* d_w) {
     if (!weights_host) return FDR_OK;
     FDR_ALLOC(*d_w, (size_t)rows * cols * sizeof(float), fn);
     FDR_HIP(hipMemcpy2D(d_w->ptr, (size_t)cols * sizeof(float), weights_host, (size_t)wstride * sizeof(float), (size_t)cols * sizeof(float),
@@ -138,9 +146,8 @@ int stage_weights(const char* fn, const float* weights_host, int rows, int cols,
 
 // host pointers: every image in (dense), `run` on the dense device batch on the null stream, every output window back; one-shot
 // device buffers, as fdr_tv_deconv_batch_f32
-template <class Run>
 int host_batch_call(fdr_plan* p, const char* fn, const float* imgs_host, size_t img_pitch, int count, int rows, int cols, int stride, float* out_host,
-                    size_t out_pitch, int out_stride, int out_rows, int out_cols, const Run& run) {
+                    size_t out_pitch, int out_stride, int out_rows, int out_cols, const HostBatchRun& run) {
     const size_t px = (size_t)rows * cols, opx = (size_t)out_rows * out_cols;
     DeviceBuffer d_in, d_out;
     FDR_ALLOC(d_in, (size_t)count * px * sizeof(float), fn);
@@ -167,7 +174,7 @@ int host_batch_call(fdr_plan* p, const char* fn, const float* imgs_host, size_t 
     return rc;
 }
 
-}  // namespace
+}  // namespace fdr
 
 extern "C" {
 
@@ -202,7 +209,7 @@ int fdr_tv_deconv_free_batch_f32(fdr_plan* p, const float* imgs_host, size_t img
     FDR_HIP(hipSetDevice(p->device));
     const bool coupled = params->coupling == FDR_TV_COUPLE_CHANNELS;
     DeviceBuffer d_w;
-    rc = stage_weights(fn, weights_host, rows, cols, wstride, &d_w);
+    rc = stage_crop_weights(fn, weights_host, rows, cols, wstride, &d_w);
     if (rc != FDR_OK) return rc;
     return host_batch_call(p, fn, imgs_host, img_pitch, count, rows, cols, stride, out_host, out_pitch, out_stride, one.out_rows, one.out_cols,
                            [&](const float* d_in, size_t px, float* d_out, size_t opx) {
@@ -246,7 +253,7 @@ int fdr_tv_deconv_auto_batch_f32(fdr_plan* p, const float* imgs_host, size_t img
     const bool coupled = params->coupling == FDR_TV_COUPLE_CHANNELS;
     const size_t n3 = (size_t)a.fp.iterations * 3;
     DeviceBuffer d_w, d_tr;  // the dense weights and the traces (3 n doubles per image, dense), for this call alone
-    rc = stage_weights(fn, weights_host, rows, cols, wstride, &d_w);
+    rc = stage_crop_weights(fn, weights_host, rows, cols, wstride, &d_w);
     if (rc != FDR_OK) return rc;
     if (trace_host && n3 > 0) FDR_ALLOC(d_tr, (size_t)count * n3 * sizeof(double), fn);
     std::vector<double> sigma_used((size_t)count, 0.0), stats(4 * (size_t)count, 0.0);

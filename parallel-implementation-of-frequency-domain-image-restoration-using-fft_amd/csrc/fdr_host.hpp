@@ -563,6 +563,9 @@ int tvfree_prepare(fdr_plan* p, const char* fn, int group = 1);
 // group, the noise level of its discrepancy ball and where the device writes its trace (3 doubles per iteration; null: none).  The
 // partials, mu_k and the last step's sums are the plan's.
 struct TvAuto { double tau; double sigma[kMaxGroup]; double* trace[kMaxGroup]; };
+// what the Poisson-likelihood calls (fdr_api_tvpoisson.hip) change in an iteration: the data step is that of the term
+// mu m [(s + b) - d+ log(s + b)], b = background, on prm.mu and nu; nothing else
+struct TvPoisson { float background; };
 // the workspaces of an auto call for `group` images: the free call's, then the ta_ block (ensure_tvauto_workspace: it grows as the
 // free call's does); the auto call's own arguments (sigma, tau, nu) checked and nu resolved into *fp, the free call's parameters
 struct TvAutoArgs {
@@ -582,13 +585,25 @@ int tvauto_noise_dev(fdr_plan* p, const float* d_img, int rows, int cols, int st
 // passes, each over the n images; then the output (and the per-image normalisation).  With `au` the data step takes image k's
 // weight from the norm and mu launches before it (prm.mu is not used) and the ta_ block must hold the group.  `coupled`: the images
 // are the channels of one picture and share the shrinkage (isotropic only); everything else stays per image.  One image, uncoupled,
-// makes the launches and the bits the single-image calls have always made.
+// makes the launches and the bits the single-image calls have always made.  With `po` (not beside `au`) the data step is the Poisson
+// one, under its own pass name; every other pass, workspace and table is the free call's.
 int tvfree_group_dev(fdr_plan* p, const char* fn, fdr_plan::Slot* const* ws, int n, const float* const* d_imgs, int rows, int cols, int stride,
                      const float* d_w, int wstride, float* const* d_outs, int out_stride, const fdr_tv_free_params& prm, bool coupled, hipStream_t s,
-                     const TvAuto* au = nullptr);
+                     const TvAuto* au = nullptr, const TvPoisson* po = nullptr);
 // one image on slot 0: the group of one
 int tvfree_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, int cols, int stride, const float* d_w, int wstride, float* d_out,
-                    int out_stride, const fdr_tv_free_params& prm, hipStream_t s, const TvAuto* au = nullptr);
+                    int out_stride, const fdr_tv_free_params& prm, hipStream_t s, const TvAuto* au = nullptr, const TvPoisson* po = nullptr);
+// what the crop batches (fdr_api_tvfreebatch.hip, fdr_api_tvpoisson.hip) share beyond the single call's checks on image 0: the
+// refusals of a batch (an unknown coupling, the coupled form with anisotropic != 0 or count > group, outputs that overlap any input
+// or the weights), the dense one-shot device copy of host weights (none for null), and the host-pointer form: every image in
+// (dense), run(d_in, in_pitch, d_out, out_pitch) on the null stream, every output window back, synchronous
+int crop_batch_check(const fdr_plan* p, const char* fn, const float* imgs, size_t img_pitch, int count, int rows, int cols, int stride,
+                     const float* weights, int wstride, const float* out, size_t out_pitch, int out_stride, const fdr_tv_free_params& one,
+                     int coupling);
+int stage_crop_weights(const char* fn, const float* weights_host, int rows, int cols, int wstride, DeviceBuffer* d_w);
+using HostBatchRun = std::function<int(const float* d_in, size_t in_pitch, float* d_out, size_t out_pitch)>;
+int host_batch_call(fdr_plan* p, const char* fn, const float* imgs_host, size_t img_pitch, int count, int rows, int cols, int stride, float* out_host,
+                    size_t out_pitch, int out_stride, int out_rows, int out_cols, const HostBatchRun& run);
 
 // ---- the motion-blur estimate (fdr_api_motion.hip), shared with the defocus and the combined estimate (fdr_api_defocus.hip) ----
 // the search arguments with their defaults (0 selects one), after the plan and window checks; FDR_ERR_ARG for anything outside

@@ -272,6 +272,45 @@ __device__ __forceinline__ void tvfree_data_pixel(const float mu, const float nu
 // image planes c, q and windows d (one stride, any alignment each), ONE weights window for all.  Every image gets the single kernel's bits.
 hipError_t launch_tvfree_data_n(int nimg, float* const* c, float* const* q, const float* const* d, int stride, const float* w, int wstride, int rows,
                                 int cols, int M, int N, float mu, float nu, hipStream_t s);
+// (fdr_tvpoisson.hip) the data step of Poisson-likelihood TV deconvolution, on the same window, planes and caller's windows as
+// launch_tvfree_data (c and q 16-byte aligned as well): the minimiser over s of mu m [(s + b) - d+ log(s + b)] + nu / 2 (s - e)^2,
+// b = background >= 0, then q = e - s; c = s - q.
+hipError_t launch_tvpoisson_data(float* c, float* q, const float* d, int stride, const float* w, int wstride, int rows, int cols, int M, int N,
+                                 float mu, float nu, float background, hipStream_t s);
+// The arithmetic of that step on one pixel, shared by every kernel that makes it.  Every operation is one correctly rounded
+// float operation (no contraction), in this order:
+//     e  = c + q
+//     m > 0 (a pixel that counts):
+//         k  = (mu * m) / nu
+//         dp = d < 0 ? 0 : d                      (a NaN stays)
+//         a  = (e + b) - k
+//         t  = k * dp
+//         rt = sqrtf(a * a + 4 * t)
+//         y  = a >= 0 ? 0.5 * (a + rt) : (2 * t) / (rt - a)      (the root of y^2 - a y - t = 0 that is >= 0, without cancellation)
+//         s  = y - b
+//     otherwise s = e
+//     q  = e - s
+//     c  = s - q
+__device__ __forceinline__ void tvpoisson_data_pixel(const float mu, const float nu, const float b, const float m, const float d, float& c,
+                                                     float& q) {
+    const float e = c + q;
+    float s = e;
+    if (m > 0.f) {
+        const float k = (mu * m) / nu;
+        const float dp = d < 0.f ? 0.f : d;
+        const float a = (e + b) - k;
+        const float t = k * dp;
+        const float rt = sqrtf(a * a + 4.f * t);
+        const float y = a >= 0.f ? 0.5f * (a + rt) : (2.f * t) / (rt - a);
+        s = y - b;
+    }
+    q = e - s;
+    c = s - q;
+}
+// the same on a group of 1 <= nimg <= kMaxGroup images in one launch (blockIdx.z = image; one image is the single-image launch), one
+// weights window for all; every image gets the single kernel's bits
+hipError_t launch_tvpoisson_data_n(int nimg, float* const* c, float* const* q, const float* const* d, int stride, const float* w, int wstride,
+                                   int rows, int cols, int M, int N, float mu, float nu, float background, hipStream_t s);
 // (fdr_tvauto.hip) noise-constrained TV deconvolution, on the same window, planes and caller's windows.  norm: res_e = sum w (c + q -
 // d)^2, res_c = sum w (c - d)^2 and S = sum w in double as tvauto_partials(rows, cols) per-workgroup partials each (part holds 3 n
 // doubles; no window of an M x N plan needs more than tvauto_max_partials(M, N)).  mu: one workgroup folds the partials in index

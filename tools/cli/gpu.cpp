@@ -7,6 +7,10 @@
 // iteration with mu chosen in every step from the noise level (--sigma, else estimated per channel; the ball is t sigma^2 S, t default 1; n default
 // 100), printed per channel as `total-variation: sigma S target T mu M discrepancy D`.  It works with `auto auto`; --tv-color, --rl, --cls and
 // --mode parity beside it are refused.
+// `--tv mu --poisson [--background b] [--tv-iters n] [--tv-rho r] [--mask mask.png] [--tv-color]`: the TV leg is fft_gpu::tvDeblurPoisson_RGB -- the
+// free-boundary iteration with the Poisson likelihood as its data term (photon-limited pictures; b is the known level under the counts, default
+// 0; mu = photons per unit times the weight wanted).  --poisson implies --free-boundary; --tv-color couples the channels.  It works with `auto
+// auto`; --tv auto, --rl, --cls, --tile and --mode parity beside it are refused with the usage text, before the picture is read.
 // `auto auto` for length and angle: the blur is estimated first (fft_gpu::estimateMotionBlur on the per-pixel mean of B, G and R),
 // printed as `estimate: length L angle A confidence C`, and the run then goes on exactly as `./gpu <img-path> L A` would.
 // `--cls auto` (gamma, with K = 0) or `--k auto` (K, with gamma = 0): the weight is chosen first (fft_gpu::chooseRegularisation on the same
@@ -127,6 +131,9 @@ int main(int argc, char** argv) {
     bool tv_auto = false;   // --tv auto: the TV leg is fft_gpu::tvDeblurAuto_RGB, mu chosen from the noise level (--sigma, else estimated)
     float tv_tau = 0.f;     // --tv-tau t: the discrepancy ball is t sigma^2 S (default 1)
     bool tv_tau_given = false, tv_iters_given = false;
+    bool poisson = false;       // --poisson: the --tv mu leg is fft_gpu::tvDeblurPoisson_RGB (Poisson likelihood; implies --free-boundary)
+    float background = 0.f;     // --background b: the known level under the counts, in the units of the picture (default 0)
+    bool background_given = false;
     bool cls = false, parity = false, pad_smooth = false;
     bool cls_auto = false, k_auto = false;  // --cls auto / --k auto: the weight is chosen from the picture
     string reg_method;                      // --reg gcv|discrepancy
@@ -194,10 +201,23 @@ int main(int argc, char** argv) {
         else if (a == "--tv-iters" && i + 1 < argc) { tv_opts = true; tv_iters_given = true; tv_iterations = atoi(argv[++i]); }
         else if (a == "--tv-rho" && i + 1 < argc) { tv_opts = true; tv_rho = strtof(argv[++i], nullptr); }
         else if (a == "--tv-color") { tv_opts = true; tv_color = true; }
+        else if (a == "--poisson") poisson = true;
+        else if (a == "--background" && i + 1 < argc) { background_given = true; background = strtof(argv[++i], nullptr); }
         else { cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle>\n"; return -1; }
     }
     if (defocus && !defocus_auto && !(psf_radius > 0.0 && psf_radius <= 127.0)) { cout << "Usage: ./gpu <img-path> defocus <radius in (0, 127]|auto>\n"; return -1; }
     if (any_blur && !estimate) { cout << "Usage: ./gpu <img-path> auto auto --any-blur\n"; return -1; }
+    // --poisson belongs to --tv mu and is a free-boundary leg of its own: no --tv auto, --rl, --cls, --tile or parity mode beside it;
+    // --background belongs to it and is finite and >= 0
+    if (poisson || background_given) {
+        if (!poisson || !(tv_mu > 0.f) || tv_auto || rl_iterations >= 0 || cls || tile != 0 || tile_overlap != -1 || parity || !(background >= 0.f) ||
+            !std::isfinite(background)) {
+            cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle> --tv <mu> --poisson [--background b] [--tv-iters n] [--tv-rho r] [--mask m.png] "
+                    "[--tv-color] (no --tv auto, --rl, --cls, --tile or --mode parity)\n";
+            return -1;
+        }
+        free_boundary = true;
+    }
     // one weight is searched at a time; --reg and --sigma belong to a search
     if ((cls_auto && k_auto) || (!(cls_auto || k_auto) && (!reg_method.empty() || (reg_sigma != 0.f && !rl_auto && !tv_auto))) ||
         (!reg_method.empty() && reg_method != "gcv" && reg_method != "discrepancy") || !(K >= 0.f) || !(reg_sigma >= 0.f)) {
@@ -259,7 +279,7 @@ int main(int argc, char** argv) {
     }
     if (tv_auto && !tv_iters_given) tv_iterations = 100;  // the constrained iteration needs about a hundred steps
     // the free-boundary TV leg runs the channels one after the other: it has no vectorial form
-    if (tv && free_boundary && tv_color) {
+    if (tv && free_boundary && tv_color && !poisson) {
         cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle> --tv <mu> --free-boundary [--mask m.png] [--tv-iters n] [--tv-rho r] (no --tv-color)\n";
         return -1;
     }
@@ -464,15 +484,17 @@ int main(int argc, char** argv) {
             to.norm_area = FDR_NORM_CROPPED;
             fft_gpu::restoreTiled_RGB(tvc, psf, to, weights);
         }
+        else if (poisson) fft_gpu::tvDeblurPoisson_RGB(tvc, psf, tv_mu, tv_iterations, tv_rho, weights, background, tv_color);
         else if (free_boundary) fft_gpu::tvDeblurFree_RGB(tvc, psf, tv_mu, tv_iterations, tv_rho, weights);
         else fft_gpu::tvDeblur_RGB(tvc, psf, tv_mu, tv_iterations, tv_rho, tv_color);
         t_end = high_resolution_clock::now();
         for (const fdr_tv_auto_result& r : chosen)
             printf("total-variation: sigma %.9g target %.9g mu %.9g discrepancy %.9g\n", r.sigma, r.target, r.mu, r.discrepancy);
         fflush(stdout);
-        cout << "Deblurring 3 channels took(gpu[total-variation " << (free_boundary && !tv_auto ? "free-boundary " : "");
+        cout << "Deblurring 3 channels took(gpu[total-variation " << (poisson ? "poisson " : free_boundary && !tv_auto ? "free-boundary " : "");
         if (tv_auto) cout << "auto";
         else cout << "mu " << tv_mu;
+        if (poisson) cout << " background " << background;
         cout << " rho " << tv_rho << " n " << tv_iterations << (tv_color ? " colour" : "");
         if (tile > 0) cout << " tile " << tile << " overlap " << tile_overlap;
         cout << "]): " << getElapsedMs(t_start, t_end) << " ms\n";
