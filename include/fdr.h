@@ -633,6 +633,65 @@ int fdr_richardson_lucy_tv_batch_f32(fdr_plan* plan, const float* imgs_host, siz
 int fdr_rl_tv_factor_group_f32_dev(int device, const float* d_u, size_t u_pitch, int count, int rows, int cols, int stride, const float* d_w,
                                    float lambda, float eps, int couple, float* d_out, size_t out_pitch, int out_stride, void* stream);
 
+/* -- multi-frame Richardson-Lucy: `count` (1 .. FDR_MAX_FRAMES) exposures of ONE scene, each with its own PSF, restored jointly on
+ *    the free-boundary, weighted form (Bertero & Boccacci 2000),
+ *        u <- u / alpha . sum_k H_k^T( w_k d_k / (H_k u) ),   alpha = sum_k H_k^T w_k,
+ *    so that what one PSF's transfer function lost another frame's supplies.
+ *      fdr_set_frame_psfs*     the frame tables: PSF k (prows x pcols, row stride pstride) lies at psfs + k psf_pitch, top-left in the
+ *                              plan as fdr_set_operator_psf* takes it, and becomes the pair H_k / (M N), conj(H_k) / (M N) by the passes
+ *                              of that setter (same bits).  The tables live in a block of their own (2 count spectra), made or regrown
+ *                              here, the new block before the old one is freed (FDR_ERR_ALLOC leaves the plan as it was); they never
+ *                              touch the operator tables, the filter or any other call's state, and no other call reads them.  PSF
+ *                              sums are NOT normalised: a frame's PSF sum is its relative exposure, which alpha accounts for, and a
+ *                              registration shift goes into the PSF.  The checks of the operator setter, and FDR_ERR_ARG for a count
+ *                              outside 1 .. FDR_MAX_FRAMES and, for count > 1, a psf_pitch below the span of one PSF.
+ *      fdr_frame_count         the frames of the last successful set (0 before the first)
+ *      fdr_spectrum_sum_f32_dev  the one new kernel alone: dst[i] = (accumulate ? dst[i] : src_0[i]) + src_k[i] for the remaining k in
+ *                              ascending order, plain float adds, i < n_floats: the bits of that loop in float32, however the sources
+ *                              are cut into launches.  d_srcs is a HOST array of n (1 .. 8) device pointers.  FDR_ERR_ARG for an n
+ *                              outside 1 .. 8, an n_floats that is odd or < 2, a pointer that is null or not 16-byte aligned, and a dst
+ *                              that overlaps a source other than exactly itself.
+ *      fdr_blur_frames_f32_dev  adjoint = 0: the ONE window d_in gives `count` windows blur_k(x), window k at d_out + k out_pitch, with
+ *                              the bits of fdr_blur_f32_dev under PSF k.  adjoint != 0: `count` windows y_k at d_in + k in_pitch give
+ *                              the ONE window sum_k blur_k^T(y_k) at d_out: the K column-pass results are added in the spectrum
+ *                              (fixed order, the same bits for every launch group) and go through one inverse row pass.
+ *                              FDR_ERR_ARG for a count that is not fdr_frame_count, windows of the K-fold side that overlap each other
+ *                              (pitch) and an output that overlaps the input anywhere in the span of the windows.
+ *      fdr_richardson_lucy_frames_f32*  the restoration: frame k at imgs + k img_pitch, weights NULL (all ones), one plane for all
+ *                              frames (weight_pitch = 0) or one per frame (at weights + k weight_pitch; saturation and cosmic rays
+ *                              differ per exposure).  Semantics are fdr_richardson_lucy_free_f32*'s with the sums over k: wgt = alpha >
+ *                              sigma count ? 1 / alpha : 0, u_0 = (sum_k sum dw_k) / (sum_k sum W_k) where seen; with tv_lambda > 0 the
+ *                              prior of fdr_richardson_lucy_tv_f32* (tv_eps 0 = FDR_RLTV_EPS).  One frame has the bits of those calls.
+ *                              No float atomics: two calls give the same bytes, whatever the plan's launch group.  FDR_ERR_ARG for what
+ *                              fdr_richardson_lucy_free_f32* refuses, a count that is not fdr_frame_count (FDR_ERR_STATE with no
+ *                              tables), an img_pitch below a window's span for count > 1, a weight_pitch that is neither 0 nor at least
+ *                              the span, an output that overlaps any frame or weights plane, a bad tv_lambda or tv_eps; every refusal
+ *                              comes before any device work.  The workspace (u, wgt, count dw planes, one spectrum, the sums) is made
+ *                              on first use and grown for a larger count; the _dev form allocates nothing afterwards and stays
+ *                              asynchronous on `stream`.                                                                           */
+#define FDR_MAX_FRAMES 8
+typedef struct fdr_rl_frames_params {
+    int iterations;  /* >= 0 */
+    float sigma;     /* coverage threshold per frame, in (0, 1): wgt = 0 where alpha <= sigma count */
+    int norm_area;   /* FDR_NORM_NONE / FDR_NORM_CROPPED / FDR_NORM_PADDED */
+    int out_rows;    /* the output window, rows .. M */
+    int out_cols;    /* cols .. N */
+    float tv_lambda; /* weight of the TV prior, 0 .. FDR_RLTV_MAX_LAMBDA; 0 = none */
+    float tv_eps;    /* smoothing of |grad u|; 0 = FDR_RLTV_EPS */
+} fdr_rl_frames_params;
+int fdr_set_frame_psfs(fdr_plan* plan, const float* psfs_host, size_t psf_pitch, int count, int prows, int pcols, int pstride);
+int fdr_set_frame_psfs_dev(fdr_plan* plan, const float* d_psfs, size_t psf_pitch, int count, int prows, int pcols, int pstride, void* stream);
+int fdr_frame_count(fdr_plan* plan, int* count);
+int fdr_spectrum_sum_f32_dev(int device, float* d_dst, const float* const* d_srcs, int n, size_t n_floats, int accumulate, void* stream);
+int fdr_blur_frames_f32_dev(fdr_plan* plan, const float* d_in, size_t in_pitch, int rows, int cols, int stride, float* d_out, size_t out_pitch,
+                            int out_stride, int count, int adjoint, void* stream);
+int fdr_richardson_lucy_frames_f32_dev(fdr_plan* plan, const float* d_imgs, size_t img_pitch, int count, int rows, int cols, int stride,
+                                       const float* d_weights, size_t weight_pitch, int wstride, float* d_out, int out_stride,
+                                       const fdr_rl_frames_params* params, void* stream);
+int fdr_richardson_lucy_frames_f32(fdr_plan* plan, const float* imgs_host, size_t img_pitch, int count, int rows, int cols, int stride,
+                                   const float* weights_host, size_t weight_pitch, int wstride, float* out_host, int out_stride,
+                                   const fdr_rl_frames_params* params);
+
 /* -- total-variation (TV) regularised deconvolution by ADMM / split Bregman (Rudin-Osher-Fatemi 1992; Wang-Yang-Yin-Zhang 2008
  *    "FTVd"; Goldstein-Osher 2009): the edge-preserving restoration beside the linear filters and RL.  It uses the operator PSF of
  *    fdr_set_operator_psf* (H = DFT2 of the PSF top-left in the plan, blur / blur^T as above) and lives on the whole periodic

@@ -374,6 +374,55 @@ inline void richardsonLucyTV_RGB(std::vector<Mat>& channels, const Mat& psf, int
                                  bool free_boundary = false, const Mat& weights = Mat(), bool coupled = false) {
     richardsonLucyTV_RGB(channels, psf, iterations, lambda, eps, free_boundary, weights, defaults(), FDR_RL_SIGMA, coupled);
 }
+// Multi-frame Richardson-Lucy (fdr_richardson_lucy_frames_f32, include/fdr.h): frames[k] holds the channels of exposure k of ONE
+// scene, psfs[k] its PSF (CV_32F; top-left in the plan as for richardsonLucyFree_RGB; sums are not normalised: a PSF's sum is its
+// frame's relative exposure, a registration shift goes into the PSF).  Every channel of frames[0] is replaced by the joint
+// free-boundary estimate from that channel of all K <= FDR_MAX_FRAMES exposures: one cached FDR_MODE_FAST plan with room for the
+// largest PSF's reach, the frame tables set ONCE, then one call per channel on launch groups of K frames, normalised by o.norm_area.
+// `weights` (CV_32F, the picture's size; empty = all ones) serves every frame; lambda > 0 adds the TV prior of richardsonLucyTV_RGB.
+inline void richardsonLucyFrames_RGB(std::vector<std::vector<Mat>>& frames, const std::vector<Mat>& psfs, int iterations, float lambda,
+                                     float eps, const Mat& weights, const Options& o, float sigma = FDR_RL_SIGMA) {
+    const int K = (int)frames.size();
+    if (K == 0 || frames[0].empty()) return;
+    const int rows = frames[0][0].rows, cols = frames[0][0].cols;
+    const size_t nch = frames[0].size();
+    bool ok = K <= FDR_MAX_FRAMES && (int)psfs.size() == K && (weights.empty() || (weights.rows == rows && weights.cols == cols && weights.type() == CV_32F));
+    int pr = 0, pc = 0;
+    for (int k = 0; k < K && ok; ++k) {
+        ok = frames[k].size() == nch && psfs[k].type() == CV_32F && psfs[k].rows > 0 && psfs[k].cols > 0;
+        for (size_t c = 0; c < nch && ok; ++c) ok = frames[k][c].rows == rows && frames[k][c].cols == cols && frames[k][c].type() == CV_32F;
+        if (ok) { pr = std::max(pr, psfs[k].rows); pc = std::max(pc, psfs[k].cols); }
+    }
+    if (!ok) {
+        std::cerr << "richardsonLucyFrames_RGB: 1 .. 8 frames of the same CV_32F channels and size, one CV_32F PSF each, CV_32F weights of the picture's size\n";
+        exit(1);
+    }
+    bool created = false;
+    PlanCacheSettle settle_;
+    fdr_plan* plan = plan_cache().get(o.device, std::max(8, nextPowerOfTwo(rows + pr - 1)), std::max(32, nextPowerOfTwo(cols + pc - 1)), FDR_MODE_FAST,
+                                      &created);
+    const size_t ppx = (size_t)pr * pc, px = (size_t)rows * cols;
+    std::vector<float> tabs(ppx * K, 0.f), in(px * K);  // the PSFs padded with zeros (bottom, right) to one shape: top-left, nothing changes
+    for (int k = 0; k < K; ++k)
+        for (int r = 0; r < psfs[k].rows; ++r) std::copy(psfs[k].ptr<float>(r), psfs[k].ptr<float>(r) + psfs[k].cols, tabs.begin() + k * ppx + (size_t)r * pc);
+    FDR_CHECK(fdr_set_frame_psfs(plan, tabs.data(), ppx, K, pr, pc, pc));
+    Mat w = weights.empty() || weights.isContinuous() ? weights : weights.clone();
+    const fdr_rl_frames_params prm = {iterations, sigma, o.norm_area, rows, cols, lambda, eps};
+    FDR_CHECK(fdr_plan_set_batching(plan, 1, K));
+    for (size_t c = 0; c < nch; ++c) {
+        for (int k = 0; k < K; ++k)
+            for (int r = 0; r < rows; ++r) std::copy(frames[k][c].ptr<float>(r), frames[k][c].ptr<float>(r) + cols, in.begin() + k * px + (size_t)r * cols);
+        Mat out(rows, cols, CV_32F);
+        FDR_CHECK(fdr_richardson_lucy_frames_f32(plan, in.data(), px, K, rows, cols, cols, w.empty() ? nullptr : w.ptr<float>(0), 0, cols,
+                                                 out.ptr<float>(0), cols, &prm));
+        frames[0][c] = out;
+    }
+    FDR_CHECK(fdr_plan_set_batching(plan, 1, 1));  // the cached plan goes back as it came
+}
+inline void richardsonLucyFrames_RGB(std::vector<std::vector<Mat>>& frames, const std::vector<Mat>& psfs, int iterations, float lambda = 0.f,
+                                     float eps = 0.f, const Mat& weights = Mat()) {
+    richardsonLucyFrames_RGB(frames, psfs, iterations, lambda, eps, weights, defaults());
+}
 // What richardsonLucyBlind_RGB takes beside the picture and the start PSF: the form, the steps the PSF is held for, and the weights and
 // coverage threshold of the free form.
 struct BlindOptions {

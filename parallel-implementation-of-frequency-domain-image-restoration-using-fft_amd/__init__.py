@@ -185,6 +185,15 @@ class RlTvParams(ctypes.Structure):
                 ("norm_area", ctypes.c_int), ("cov_sigma", ctypes.c_float), ("out_rows", ctypes.c_int), ("out_cols", ctypes.c_int)]
 
 
+MAX_FRAMES = 8  # FDR_MAX_FRAMES
+
+
+class RlFramesParams(ctypes.Structure):
+    """fdr_rl_frames_params of include/fdr.h"""
+    _fields_ = [("iterations", ctypes.c_int), ("sigma", ctypes.c_float), ("norm_area", ctypes.c_int), ("out_rows", ctypes.c_int),
+                ("out_cols", ctypes.c_int), ("tv_lambda", ctypes.c_float), ("tv_eps", ctypes.c_float)]
+
+
 class RlTvBatchParams(ctypes.Structure):
     """fdr_rl_tv_batch_params of include/fdr.h"""
     _fields_ = RlTvParams._fields_ + [("couple", ctypes.c_int)]
@@ -362,6 +371,13 @@ def _signatures():
         "fdr_richardson_lucy_tv_batch_f32": (ci, [vp, vp, sz, ci, ci, ci, ci, vp, ci, vp, sz, ci, P(RlTvBatchParams)]),
         "fdr_richardson_lucy_tv_batch_f32_dev": (ci, [vp, vp, sz, ci, ci, ci, ci, vp, ci, vp, sz, ci, P(RlTvBatchParams), vp]),
         "fdr_rl_tv_factor_group_f32_dev": (ci, [ci, vp, sz, ci, ci, ci, ci, vp, cf, cf, ci, vp, sz, ci, vp]),
+        "fdr_set_frame_psfs": (ci, [vp, vp, sz, ci, ci, ci, ci]),
+        "fdr_set_frame_psfs_dev": (ci, [vp, vp, sz, ci, ci, ci, ci, vp]),
+        "fdr_frame_count": (ci, [vp, P(ci)]),
+        "fdr_spectrum_sum_f32_dev": (ci, [ci, vp, P(vp), ci, sz, ci, vp]),
+        "fdr_blur_frames_f32_dev": (ci, [vp, vp, sz, ci, ci, ci, vp, sz, ci, ci, ci, vp]),
+        "fdr_richardson_lucy_frames_f32": (ci, [vp, vp, sz, ci, ci, ci, ci, vp, sz, ci, vp, ci, P(RlFramesParams)]),
+        "fdr_richardson_lucy_frames_f32_dev": (ci, [vp, vp, sz, ci, ci, ci, ci, vp, sz, ci, vp, ci, P(RlFramesParams), vp]),
         "fdr_blur_batch_f32_dev": (ci, [vp, vp, sz, ci, ci, ci, ci, vp, sz, ci, ci, vp]),
         "fdr_richardson_lucy_batch_f32": (ci, [vp, vp, sz, ci, ci, ci, ci, vp, ci, vp, sz, ci, P(RlBatchParams)]),
         "fdr_richardson_lucy_batch_f32_dev": (ci, [vp, vp, sz, ci, ci, ci, ci, vp, ci, vp, sz, ci, P(RlBatchParams), vp]),
@@ -779,6 +795,67 @@ class Plan:
         _check(lib.fdr_richardson_lucy_free_f32_dev(self._h, ctypes.c_void_p(int(d_img)), rows, cols, stride,
                                                     ctypes.c_void_p(int(d_weights)) if d_weights else None, int(wstride),
                                                     ctypes.c_void_p(int(d_out)), out_stride, ctypes.byref(prm), _stream(stream)))
+
+    # multi-frame Richardson-Lucy (include/fdr.h): several exposures of one scene, one PSF each, in frame tables of their own
+    def set_frame_psfs(self, psfs):
+        """the frame tables from K (1 .. MAX_FRAMES) host PSFs of one shape, each top-left in the plan as set_operator_psf takes it;
+        sums are not normalised (a frame's PSF sum is its relative exposure).  Apart from every other table of the plan."""
+        psfs = np.ascontiguousarray(np.stack([np.asarray(q, dtype=np.float32) for q in psfs]), dtype=np.float32)
+        k, pr, pc = psfs.shape
+        _check(lib.fdr_set_frame_psfs(self._h, _ptr(psfs), pr * pc, k, pr, pc, pc))
+
+    def set_frame_psfs_dev(self, d_psfs, psf_pitch, count, prows, pcols, pstride, stream=None):
+        """the same from device memory: PSF k at d_psfs + k psf_pitch (elements).  Asynchronous."""
+        _check(lib.fdr_set_frame_psfs_dev(self._h, ctypes.c_void_p(int(d_psfs)), int(psf_pitch), int(count), prows, pcols, pstride,
+                                          _stream(stream)))
+
+    def frame_count(self):
+        """frames of the last set_frame_psfs (0 before the first)"""
+        n = ctypes.c_int(0)
+        _check(lib.fdr_frame_count(self._h, ctypes.byref(n)))
+        return n.value
+
+    def blur_frames_dev(self, d_in, in_pitch, rows, cols, stride, d_out, out_pitch, out_stride, count, adjoint=False, stream=None):
+        """adjoint=False: the one window d_in through every frame's PSF, window k to d_out + k out_pitch (the bits of blur_dev under
+        PSF k).  adjoint=True: the `count` windows at d_in + k in_pitch to the ONE window sum_k blur_k^T(y_k) at d_out, added in the
+        spectrum in a fixed order.  Pitches in elements.  Asynchronous."""
+        _check(lib.fdr_blur_frames_f32_dev(self._h, ctypes.c_void_p(int(d_in)), int(in_pitch), rows, cols, stride, ctypes.c_void_p(int(d_out)),
+                                           int(out_pitch), out_stride, int(count), int(bool(adjoint)), _stream(stream)))
+
+    def richardson_lucy_frames(self, frames, iterations, weights=None, tv_lambda=0.0, tv_eps=0.0, sigma=RL_SIGMA, norm_area=NORM_NONE,
+                               full_plane=False):
+        """`iterations` joint free-boundary Richardson-Lucy steps on the K frames (host arrays of one shape, K = frame_count()):
+        u <- u / alpha . sum_k H_k^T(w_k d_k / (H_k u)).  weights: None, one plane for all frames, or K planes (one per frame).
+        tv_lambda > 0 adds the TV prior of richardson_lucy_tv (tv_eps 0 = RLTV_EPS).  Returns the window, or with full_plane the
+        whole M x N estimate; normalised over what is returned."""
+        frames = np.ascontiguousarray(np.stack([np.asarray(f, dtype=np.float32) for f in frames]), dtype=np.float32)
+        k, rows, cols = frames.shape
+        w, wpitch = None, 0
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float32)
+            if w.shape == (rows, cols):
+                wpitch = 0
+            elif w.shape == (k, rows, cols):
+                wpitch = rows * cols
+            else:
+                raise ValueError("weights must have the shape of one frame or of all frames")
+        orows, ocols = (self.M, self.N) if full_plane else (rows, cols)
+        out = np.empty((orows, ocols), dtype=np.float32)
+        prm = RlFramesParams(int(iterations), float(sigma), int(norm_area), orows, ocols, float(tv_lambda), float(tv_eps))
+        _check(lib.fdr_richardson_lucy_frames_f32(self._h, _ptr(frames), rows * cols, k, rows, cols, cols, _ptr(w) if w is not None else None,
+                                                  wpitch, cols, _ptr(out), ocols, ctypes.byref(prm)))
+        return out
+
+    def richardson_lucy_frames_dev(self, d_imgs, img_pitch, count, rows, cols, stride, d_out, out_stride, iterations, d_weights=None,
+                                   weight_pitch=0, wstride=0, tv_lambda=0.0, tv_eps=0.0, sigma=RL_SIGMA, norm_area=NORM_NONE, out_rows=None,
+                                   out_cols=None, stream=None):
+        """the same on device pointers: frame k at d_imgs + k img_pitch, weights None, one plane (weight_pitch 0) or one per frame;
+        out_rows x out_cols (default rows x cols, up to M x N) is the output window.  Asynchronous."""
+        prm = RlFramesParams(int(iterations), float(sigma), int(norm_area), int(rows if out_rows is None else out_rows),
+                             int(cols if out_cols is None else out_cols), float(tv_lambda), float(tv_eps))
+        _check(lib.fdr_richardson_lucy_frames_f32_dev(self._h, ctypes.c_void_p(int(d_imgs)), int(img_pitch), int(count), rows, cols, stride,
+                                                      ctypes.c_void_p(int(d_weights)) if d_weights else None, int(weight_pitch), int(wstride),
+                                                      ctypes.c_void_p(int(d_out)), out_stride, ctypes.byref(prm), _stream(stream)))
 
     # Richardson-Lucy with a total-variation prior, both forms (include/fdr.h); uses the operator PSF
     def richardson_lucy_tv(self, img, iterations, lam, eps=0.0, free_boundary=False, weights=None, cov_sigma=RL_SIGMA, norm_area=NORM_NONE,
@@ -1595,6 +1672,60 @@ def richardsonLucyFree_myfft(img, psf, iterations, weights=None, sigma=RL_SIGMA,
     with Plan(M, N, MODE_FAST, device) as p:
         p.set_operator_psf(psf)
         return p.richardson_lucy_free(img, iterations, weights, sigma, norm_area, full_plane, accelerate=accelerate)
+
+
+def spectrum_sum_dev(d_dst, d_srcs, n_floats, accumulate=False, device=0, stream=None):
+    """fdr_spectrum_sum_f32_dev: dst[i] = (accumulate ? dst[i] : src_0[i]) + the remaining sources in ascending order, plain float32
+    adds, i < n_floats (even).  d_srcs: 1 .. 8 device pointers, 16-byte aligned as d_dst; d_dst may be one of them.  Asynchronous."""
+    arr = (ctypes.c_void_p * len(d_srcs))(*[int(q) for q in d_srcs])
+    _check(lib.fdr_spectrum_sum_f32_dev(int(device), ctypes.c_void_p(int(d_dst)), arr, len(d_srcs), int(n_floats), int(bool(accumulate)),
+                                        _stream(stream)))
+
+
+def _frames_plan_size(rows, cols, psfs):
+    """the plan of richardsonLucyFree_myfft for the largest of the PSFs"""
+    return _rlfree_plan_size(rows, cols, max(q.shape[0] for q in psfs), max(q.shape[1] for q in psfs))
+
+
+def _frame_psfs(psfs):
+    """K PSFs padded with zeros (bottom, right) to one shape: a PSF lies top-left in the plan, so the padding changes nothing"""
+    psfs = [np.asarray(q, dtype=np.float32) for q in psfs]
+    pr, pc = max(q.shape[0] for q in psfs), max(q.shape[1] for q in psfs)
+    out = np.zeros((len(psfs), pr, pc), dtype=np.float32)
+    for k, q in enumerate(psfs):
+        out[k, :q.shape[0], :q.shape[1]] = q
+    return out
+
+
+def richardsonLucyFrames_myfft(frames, psfs, iterations, weights=None, tv_lambda=0.0, tv_eps=0.0, sigma=RL_SIGMA, device=0,
+                               norm_area=NORM_NONE, full_plane=False):
+    """Joint free-boundary Richardson-Lucy of K (1 .. MAX_FRAMES) exposures of one scene, frame k blurred by psfs[k] (top-left in
+    the plan, as for richardsonLucyFree_myfft; sums not normalised: a PSF's sum is its frame's relative exposure): the plan of
+    richardsonLucyFree_myfft, the frame tables, `iterations` steps, the window back.  weights: None, one plane, or one per frame;
+    tv_lambda > 0 adds the TV prior (without it the joint iteration fits the noise within a few steps, as plain RL does)."""
+    frames = [np.asarray(f, dtype=np.float32) for f in frames]
+    psfs = _frame_psfs(psfs)
+    M, N = _frames_plan_size(frames[0].shape[0], frames[0].shape[1], psfs)
+    with Plan(M, N, MODE_FAST, device) as p:
+        p.set_frame_psfs(psfs)
+        p.set_batching(1, min(len(frames), 8))
+        return p.richardson_lucy_frames(frames, iterations, weights, tv_lambda, tv_eps, sigma, norm_area, full_plane)
+
+
+def richardsonLucyFrames_RGB(frames, psfs, iterations, weights=None, tv_lambda=0.0, tv_eps=0.0, sigma=RL_SIGMA, device=0, norm_area=NORM_NONE):
+    """fft_gpu::richardsonLucyFrames_RGB: frames[k] is the list of channel planes of exposure k (every exposure the same channels
+    and size).  Returns the list of restored channels: the frame tables are set once, then one joint call per channel (the bits of
+    richardsonLucyFrames_myfft on that channel)."""
+    if not frames or not frames[0]:
+        return []
+    psfs = _frame_psfs(psfs)
+    r, c = np.asarray(frames[0][0]).shape
+    M, N = _frames_plan_size(r, c, psfs)
+    with Plan(M, N, MODE_FAST, device) as p:
+        p.set_frame_psfs(psfs)
+        p.set_batching(1, min(len(frames), 8))
+        return [p.richardson_lucy_frames([f[ch] for f in frames], iterations, weights, tv_lambda, tv_eps, sigma, norm_area)
+                for ch in range(len(frames[0]))]
 
 
 def rl_tv_factor_dev(d_u, rows, cols, stride, d_out, out_stride, lam, eps=0.0, d_w=None, device=0, stream=None):

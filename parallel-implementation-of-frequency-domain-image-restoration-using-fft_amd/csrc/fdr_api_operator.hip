@@ -20,7 +20,27 @@ const char* const kPassOpRowsBlur = "C op rows: IFFT+crop (blur)";
 
 namespace fdr {
 
-// the PSF top-left in the M x N plane -> its row spectra (the rows it reaches) -> H / (M N) into op_h, conj(H) / (M N) into op_c
+// the PSF top-left in the M x N plane -> its row spectra (the rows it reaches) -> H / (M N) into h, conj(H) / (M N) into c
+int build_operator_tables(fdr_plan* p, const float* d_psf, int prows, int pcols, int pstride, float2* h, float2* c, hipStream_t s) {
+    ScopedPhase phase(p, FDR_PHASE_PRE, s);
+    const int nvalid = (prows + 3) & ~3;  // <= M (M is a multiple of 8 on this path)
+    {
+        ScopedPass t(p, s, kPassOpRowsPsf);
+        RowArgs ra = panel_row_args(p);
+        ra.src_real = d_psf; ra.src_rows = prows; ra.src_cols = pcols; ra.src_stride = pstride;
+        ra.dst_c = h; ra.M = nvalid;
+        FDR_HIP(launch_rows4(p->logN, ROW_IN_REAL, ROW_OUT_COMPLEX, ra, p->tw_row_f, s));
+    }
+    {
+        ScopedPass t(p, s, kPassOpCols);
+        ColArgs ca = panel_col_args(p);
+        ca.data = h; ca.nvalid = nvalid;
+        FDR_HIP(launch_cols_panel_operator(p->logM, ca, c, p->tw_col_f, s));
+    }
+    return FDR_OK;
+}
+
+// the operator setter: the tables on op_h / op_c, made by the first call
 int set_operator_psf_impl(fdr_plan* p, const float* d_psf, int prows, int pcols, int pstride, hipStream_t s) {
     if (!p->op_h) {
         float2* t = nullptr;
@@ -29,21 +49,8 @@ int set_operator_psf_impl(fdr_plan* p, const float* d_psf, int prows, int pcols,
         p->op_h = t;
         p->op_c = t + p->ws_elems;
     }
-    ScopedPhase phase(p, FDR_PHASE_PRE, s);
-    const int nvalid = (prows + 3) & ~3;  // <= M (M is a multiple of 8 on this path)
-    {
-        ScopedPass t(p, s, kPassOpRowsPsf);
-        RowArgs ra = panel_row_args(p);
-        ra.src_real = d_psf; ra.src_rows = prows; ra.src_cols = pcols; ra.src_stride = pstride;
-        ra.dst_c = p->op_h; ra.M = nvalid;
-        FDR_HIP(launch_rows4(p->logN, ROW_IN_REAL, ROW_OUT_COMPLEX, ra, p->tw_row_f, s));
-    }
-    {
-        ScopedPass t(p, s, kPassOpCols);
-        ColArgs ca = panel_col_args(p);
-        ca.data = p->op_h; ca.nvalid = nvalid;
-        FDR_HIP(launch_cols_panel_operator(p->logM, ca, p->op_c, p->tw_col_f, s));
-    }
+    const int rc = build_operator_tables(p, d_psf, prows, pcols, pstride, p->op_h, p->op_c, s);
+    if (rc != FDR_OK) return rc;
     p->have_op = true;
     ++p->op_gen;
     return FDR_OK;

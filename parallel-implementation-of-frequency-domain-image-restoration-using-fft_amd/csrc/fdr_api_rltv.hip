@@ -19,10 +19,14 @@ const char* const kPassRtFactor = "RLTV factor: w / (1 - lambda div)";
 const char* const kPassRtFactorGroup = "RLTV factor (group): w / (1 - lambda div)";
 const char* const kPassRtFactorCoupled = "RLTV factor (coupled): w / (1 - lambda div p_c)";
 
+}  // namespace
+
+namespace fdr {
+
 // 2 g M x N planes (g factors, then g estimates), made by the first call with lambda > 0 for one image and grown by the first batched
 // call on groups of g.  The new block is had before the old one is let go: when it cannot be had the sticky HIP error is cleared and
 // the plan and the workspace it had stay as they were.
-int ensure_rltv_workspace(fdr_plan* p, const char* fn, int group = 1) {
+int ensure_rltv_workspace(fdr_plan* p, const char* fn, int group) {
     if (p->rt_block && p->rt_group >= group) return FDR_OK;
     const size_t P = (size_t)p->M * p->N;
     void* blk = nullptr;
@@ -50,6 +54,10 @@ int prior_check(const char* fn, float lambda, float eps) {
     if (!(eps >= 0.f) || !std::isfinite(eps)) return fail(FDR_ERR_ARG, std::string(fn) + ": eps must be finite and >= 0");
     return FDR_OK;
 }
+
+}  // namespace fdr
+
+namespace {
 
 fdr_rlfree_params free_params(const fdr_rl_tv_params& prm) {
     return fdr_rlfree_params{prm.iterations, prm.cov_sigma, prm.norm_area, prm.out_rows, prm.out_cols};

@@ -200,6 +200,21 @@ struct fdr_plan {
     void* rt_block = nullptr;
     int rt_group = 0;
     float *rt_f = nullptr, *rt_u = nullptr;
+    // multi-frame Richardson-Lucy (fdr_set_frame_psfs*, fdr_blur_frames_f32_dev, fdr_richardson_lucy_frames_f32*).  fr_tables: one
+    // allocation of 2 fr_cap ws_elems float2, made or regrown by the setter alone: frame k's H_k / (M N) at fr_tables + 2 k ws_elems,
+    // its conj(H_k) / (M N) ws_elems behind (layout of `filt`); fr_count = the frames of the last set.  Nothing else reads or writes
+    // them, and they touch neither op_h / op_c, filt, op_gen nor the TV table.  fr_block: the workspace of the calls, made on first
+    // use and grown for a larger count (fr_ws_count = the frames it holds): the accumulator spectrum fr_acc (ws_elems), the planes
+    // fr_u, fr_wgt (M x N) and fr_ws_count planes dw (frame k's at fr_dw + k M N), then per frame the 2 rlfree_partials(M, N) + 2
+    // doubles of its sums (frames_part) and the folded pair fr_sums.  fdr_blur_frames_f32_dev needs fr_acc only and makes the block
+    // for one frame.
+    float2* fr_tables = nullptr;
+    int fr_cap = 0, fr_count = 0;
+    void* fr_block = nullptr;
+    int fr_ws_count = 0;
+    float2* fr_acc = nullptr;
+    float *fr_u = nullptr, *fr_wgt = nullptr, *fr_dw = nullptr;
+    double *fr_part = nullptr, *fr_sums = nullptr;
     // stopping Richardson-Lucy from the data (fdr_richardson_lucy_auto_f32*): made by the first such call, kept until fdr_plan_destroy
     // -- rs_block holds the (res, kl) partials of the ratio pass (one double2 per workgroup of the plan's inverse row grid) and the
     // partials of the noise estimate; rs_trace the internal trace (2 rs_trace_cap doubles; it grows only when a call with a rule and
@@ -362,6 +377,9 @@ int set_psf(fdr_plan* p, const char* fn, const PsfSource& src, bool op, float K,
 // the builders, on a checked device PSF (fdr_api_wiener.hip, fdr_api_operator.hip)
 int set_psf_dev_impl(fdr_plan* p, const float* d_psf, int prows, int pcols, int pstride, float K, hipStream_t s, double gamma);
 int set_operator_psf_impl(fdr_plan* p, const float* d_psf, int prows, int pcols, int pstride, hipStream_t s);
+// the two launches of the operator setter on any pair of tables (ws_elems each, layout of `filt`): the PSF's row spectra into `h`,
+// then H / (M N) in place and conj(H) / (M N) into `c`.  Touches nothing else of the plan.
+int build_operator_tables(fdr_plan* p, const float* d_psf, int prows, int pcols, int pstride, float2* h, float2* c, hipStream_t s);
 
 // the Laplacian table of the CLS filters and of the TV solve (fdr_api_wiener.hip): built in double on the host and uploaded on first
 // use (synchronous), freed with the plan
@@ -491,6 +509,11 @@ int rlfree_batch_dev(fdr_plan* p, const char* fn, const float* d_imgs, size_t im
 // ---- the TV prior of Richardson-Lucy (fdr_api_rltv.hip) ----
 // the factor launch of a group: the n planes rows x cols (row stride `stride`) at rt_u + k M N to rt_f + k M N (same stride), w the group's
 int rltv_factor_group(fdr_plan* p, int n, int rows, int cols, int stride, const float* w, const RlTvPrior& tv, hipStream_t s);
+// what the multi-frame call (fdr_api_frames.hip) shares with the single one: the prior's workspace (2 group planes; it grows as the
+// others do), the refusal of a bad lambda or eps, and the factor launch of one image: u (rows x cols, row stride `stride`) and w to rt_f
+int ensure_rltv_workspace(fdr_plan* p, const char* fn, int group = 1);
+int prior_check(const char* fn, float lambda, float eps);
+int rltv_factor(fdr_plan* p, const float* u, int rows, int cols, int stride, const float* w, float lambda, float eps, hipStream_t s);
 // the checks and the driver of fdr_richardson_lucy_batch_f32* (fdr_api_rlbatch.hip), which the batch with the prior shares
 int rl_batch_check(const fdr_plan* p, const char* fn, const float* imgs, size_t img_pitch, int count, int rows, int cols, int stride,
                    const float* weights, int wstride, const float* out, size_t out_pitch, int out_stride, const fdr_rl_batch_params& b,

@@ -197,6 +197,13 @@ hipError_t launch_rltv_factor(const float* u, int rows, int cols, int stride, co
 // `coupled`: the planes are the channels of one picture and share m = sqrt(eps^2 + sum_c |grad u_c|^2), added in channel order.
 hipError_t launch_rltv_factor_group(const float* u, size_t u_pitch, int count, int rows, int cols, int stride, const float* w, float lambda,
                                     float eps, float* out, size_t out_pitch, int out_stride, bool coupled, hipStream_t s);
+// (fdr_frames.hip) multi-frame Richardson-Lucy.  sum: dst[i] = (accumulate ? dst[i] : src_0[i]) + src_k[i] for the remaining k < n in
+// ascending order, plain float adds, i < n_floats (even, >= 2; every pointer 16-byte aligned; dst may be a source exactly): the
+// spectra pass B' left for the frames of a launch group, added in the domain where the inverse row pass is still to come.  fold:
+// out[j] = sum_k sums[k pitch + j], j = 0, 1, in ascending k (the (sum dw, sum W) pairs of the frames; out may not be one of them).
+struct FrameSrcs { const float* p[kMaxGroup]; };
+hipError_t launch_frames_sum(float* dst, const FrameSrcs& srcs, int n, size_t n_floats, bool accumulate, hipStream_t s);
+hipError_t launch_frames_fold(const double* sums, size_t pitch, int n, double* out, hipStream_t s);
 // (fdr_rlaccel.hip) accelerated Richardson-Lucy, on rows x cols windows with their own row strides.  direction: g = u1 - y over the
 // previous g; with `part` not null also sum(g_new g_old) and sum(g_old g_old) in double as rlaccel_partials(rows, cols)
 // per-workgroup partials each (part holds 2 n doubles); with a null `part` the old g is not read.  alpha: one workgroup folds the

@@ -1,5 +1,5 @@
 // gpu.cpp -- ./gpu <img-path> <psf-length> <psf-angle> | auto auto [--any-blur] | defocus <radius|auto> | blind <size>  [--out file] [--mode fast|parity] [--norm padded|cropped] [--host-epilogue]
-//           [--cls gamma|auto] [--k K|auto] [--reg gcv|discrepancy] [--sigma s] [--pad zero|smooth] [--rl iterations|auto [--accel] [--rl-tv lambda [--rl-tv-eps e] [--rl-tv-color]] [--free-boundary [--mask mask.png]] [--rl-max n] [--rl-stop residual|kl] [--gain g] [--rl-check c]] [--tv mu [--tv-iters n] [--tv-rho r] [--tv-color | --free-boundary [--mask mask.png]]]
+//           [--cls gamma|auto] [--k K|auto] [--reg gcv|discrepancy] [--sigma s] [--pad zero|smooth] [--rl iterations|auto [--accel] [--rl-tv lambda [--rl-tv-eps e] [--rl-tv-color]] [--free-boundary [--mask mask.png] [--frame img2 L2 A2 ...]] [--rl-max n] [--rl-stop residual|kl] [--gain g] [--rl-check c]] [--tv mu [--tv-iters n] [--tv-rho r] [--tv-color | --free-boundary [--mask mask.png]]]
 // `--rl n|--tv mu --free-boundary --tile T [--overlap O]`: the leg is fft_gpu::restoreTiled_RGB -- overlapping T x T tiles (O pixels shared, default T / 8),
 // each restored as a crop of a larger scene with the PSF centred, blended and normalised over the picture; one PSF, --mask as before.
 // `--tv mu --free-boundary`: the TV leg is fft_gpu::tvDeblurFree_RGB (the picture is a crop of a larger scene; --mask as for --rl); --tv-color has no such form.
@@ -31,6 +31,11 @@
 // --rl-max steps (default 100), stopped by --rl-stop residual (default; --sigma = the noise level of the mean, else estimated) or kl (--gain = photons
 // per unit, required), looked at every --rl-check steps), printed as `rl: iterations k of n rule r sigma s statistic v target t stopped 0|1`,
 // and the run then goes on exactly as `--rl k` would.  It combines with --accel, --free-boundary, --mask and `auto auto`.
+// `--rl n --free-boundary --frame <img2> <L2> <A2> [--frame ...] [--rl-tv lambda [--rl-tv-eps e]] [--mask mask.png]`: the --rl leg is
+// fft_gpu::richardsonLucyFrames_RGB -- the picture and every --frame picture (at most 7, all of the picture's size) are exposures of ONE
+// scene, each with its own motion PSF (length, angle), restored jointly; --mask serves every frame.  Beside --frame only --rl n, --free-boundary,
+// --rl-tv, --rl-tv-eps, --mask, --out and --raw-out may stand: anything else (--accel, `--rl auto`, blind, defocus, `auto auto`, --tile, --rl-tv-color,
+// --tv, --cls, --k, --sigma, --reg, --norm, --pad, --mode, --host-epilogue, ...) is refused with the usage text, before a picture is read.
 // `--rl n --rl-tv lambda [--rl-tv-eps e]`: the --rl leg runs Richardson-Lucy with a total-variation prior of weight lambda (fft_gpu::richardsonLucyTV_RGB;
 // eps smooths |grad u|, default FDR_RLTV_EPS); --free-boundary and --mask apply, `auto auto` works as before; --accel, `--rl auto` and `blind` have no
 // regularised form and are refused with a message.  The three channels go through one batched call; --rl-tv-color beside --rl-tv couples them
@@ -123,6 +128,8 @@ int main(int argc, char** argv) {
     bool rl_tv_opts = false, rl_tv_color = false;  // --rl-tv-color: the channels under one vectorial TV prior (coupled)
     bool free_boundary = false;  // --free-boundary: the --rl leg is fft_gpu::richardsonLucyFree_RGB (the picture is a crop of a larger scene)
     string mask_path;            // --mask file: pixels that are 0 in it (any channel counts) get weight 0, the others weight 1
+    struct FrameArg { string path; int length; double angle; };
+    vector<FrameArg> frame_args;  // --frame img L A: a further exposure of the same scene with its own motion PSF (fft_gpu::richardsonLucyFrames_RGB)
     int tile = 0, tile_overlap = -1;  // --tile T [--overlap O]: the free-boundary --rl n / --tv mu leg is fft_gpu::restoreTiled_RGB (default O = T / 8)
     float tv_mu = -1.f, tv_rho = 2.0f;  // --tv mu: a timed total-variation leg (fft_gpu::tvDeblur_RGB); its planes are the written result
     int tv_iterations = 50;
@@ -187,6 +194,7 @@ int main(int argc, char** argv) {
         else if (a == "--rl-tv-color") { rl_tv_opts = true; rl_tv_color = true; }
         else if (a == "--free-boundary") free_boundary = true;
         else if (a == "--mask" && i + 1 < argc) mask_path = argv[++i];
+        else if (a == "--frame" && i + 3 < argc) { frame_args.push_back({argv[i + 1], atoi(argv[i + 2]), atof(argv[i + 3])}); i += 3; }
         else if (a == "--tile" && i + 1 < argc) tile = atoi(argv[++i]);
         else if (a == "--overlap" && i + 1 < argc) tile_overlap = atoi(argv[++i]);
         else if (a == "--psf-hold" && i + 1 < argc) { blind_opts = true; psf_hold = atoi(argv[++i]); }
@@ -233,6 +241,25 @@ int main(int argc, char** argv) {
         (!mask_path.empty() && !free_boundary && !tv_auto)) {
         cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle>\n";
         return -1;
+    }
+    // --frame belongs to --rl n --free-boundary with stated motion PSFs, and takes only --rl-tv, --rl-tv-eps and --mask beside them
+    if (!frame_args.empty()) {
+        bool ok = rl_iterations >= 0 && free_boundary && !rl_auto && !accel && !blind && !defocus && !estimate && tile == 0 && tile_overlap == -1 &&
+                  !rl_tv_color && tv_mu == -1.f && !tv_auto && !poisson && !cls && !cls_auto && !k_auto && !pad_smooth && !parity && !verify &&
+                  (int)frame_args.size() < FDR_MAX_FRAMES && psf_length >= 1;
+        for (const FrameArg& f : frame_args) ok = ok && f.length >= 1;
+        // nothing else beside them: only the words below (with their values) and the two output paths may stand on the command line
+        for (int i = 4; i < argc && ok; ++i) {
+            const string a = argv[i];
+            if (a == "--frame") i += 3;
+            else if (a == "--rl" || a == "--rl-tv" || a == "--rl-tv-eps" || a == "--mask" || a == "--out" || a == "--raw-out") i += 1;
+            else ok = a == "--free-boundary";
+        }
+        if (!ok) {
+            cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle> --rl <n> --free-boundary --frame <img2> <L2> <A2> [--frame ...] [--rl-tv lambda] "
+                    "[--mask m.png] (at most 7 --frame; no other leg or option beside them)\n";
+            return -1;
+        }
     }
     // --tile belongs to the free-boundary form of --rl n or --tv mu, plain: sectioning has no accelerated, TV-prior, data-stopped or blind form
     if (tile != 0 || tile_overlap != -1) {
@@ -461,6 +488,22 @@ int main(int argc, char** argv) {
             to.method = FDR_TILED_RL_FREE; to.tile = tile; to.overlap = tile_overlap; to.iterations = rl_iterations; to.norm_area = FDR_NORM_CROPPED;
             fft_gpu::restoreTiled_RGB(rl, psf, to, weights);
         }
+        else if (!frame_args.empty()) {  // the picture and the --frame pictures jointly: the planes of the joint estimate
+            vector<vector<Mat>> frames(1, rl);
+            vector<Mat> psfs(1, psf);
+            for (const FrameArg& f : frame_args) {
+                Mat fi = fdr_io::imread(f.path);
+                if (fi.empty() || fi.rows != img.rows || fi.cols != img.cols) { cout << "Cannot read frame " << f.path << " (it must have the image's size)\n"; return -1; }
+                fi.convertTo(fi, CV_32F);
+                fi /= 255.0;
+                vector<Mat> ch;
+                split(fi, ch);
+                frames.push_back(ch);
+                psfs.push_back(motionBlurKernel(f.length, f.angle));
+            }
+            fft_gpu::richardsonLucyFrames_RGB(frames, psfs, rl_iterations, rl_tv_opts ? rl_tv : 0.f, rl_tv_eps, weights);
+            rl = frames[0];
+        }
         else if (rl_tv_opts) fft_gpu::richardsonLucyTV_RGB(rl, psf, rl_iterations, rl_tv, rl_tv_eps, free_boundary, weights, rl_tv_color);
         else if (free_boundary) fft_gpu::richardsonLucyFree_RGB(rl, psf, rl_iterations, weights, accel);
         else fft_gpu::richardsonLucy_RGB(rl, psf, rl_iterations, accel);
@@ -468,6 +511,7 @@ int main(int argc, char** argv) {
         cout << "Deblurring 3 channels took(gpu[richardson-lucy " << (free_boundary ? "free-boundary " : "") << rl_iterations
              << (accel ? " accelerated" : "");
         if (tile > 0) cout << " tile " << tile << " overlap " << tile_overlap;
+        if (!frame_args.empty()) cout << " frames " << frame_args.size() + 1;
         if (rl_tv_opts) cout << " tv " << rl_tv;
         cout << "]): " << getElapsedMs(t_start, t_end) << " ms\n";
         channels = rl;
