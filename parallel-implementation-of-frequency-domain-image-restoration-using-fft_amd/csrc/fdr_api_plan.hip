@@ -1,5 +1,6 @@
 // fdr_api_plan.hip -- plans of libfdr.so: twiddle tables, create / destroy / dims / options / batching, profiling and phase
-// times, and what the entry points share: the checks, the PSF path and the host-pointer single-image call.  The host files
+// times, and what the entry points share: the checks, the PSF path and the host-pointer forms of a single-image call and of a TV
+// batch (with its first refusals and the staging of a crop call's weights).  The host files
 // (fdr_api_*.hip) use only the HIP runtime -- no torch, no OpenCV -- and there is deliberately NO CPU fallback in them: every
 // entry point either launches HIP kernels or fails.
 #include "fdr_host.hpp"
@@ -343,6 +344,54 @@ int host_image_call(fdr_plan* p, const char* fn, const float* in, int rows, int 
     if (rc != FDR_OK) return rc;
     FDR_HIP(e);
     return FDR_OK;
+}
+
+// the dense copy of the host weights for one call (no plane of the workspace is free over the whole iteration)
+int stage_crop_weights(const char* fn, const float* weights_host, int rows, int cols, int wstride, DeviceBuffer* d_w) {
+    if (!weights_host) return FDR_OK;
+    FDR_ALLOC(*d_w, (size_t)rows * cols * sizeof(float), fn);
+    FDR_HIP(hipMemcpy2D(d_w->ptr, (size_t)cols * sizeof(float), weights_host, (size_t)wstride * sizeof(float), (size_t)cols * sizeof(float),
+                        (size_t)rows, hipMemcpyHostToDevice));
+    return FDR_OK;
+}
+
+bool tv_batch_begin(const char* fn, const void* p, const void* params, int count, const void* imgs, const void* out, int* rc) {
+    if (!p || !params) *rc = null_arg(fn);
+    else if (count < 0) *rc = fail(FDR_ERR_ARG, std::string(fn) + ": negative count");
+    else if (count == 0) *rc = FDR_OK;
+    else if (!imgs || !out) *rc = null_arg(fn);
+    else return true;
+    return false;
+}
+
+// host pointers: every image in (dense), `run` on the dense device batch on the null stream, every output window back; one-shot
+// device buffers
+int host_batch_call(fdr_plan* p, const char* fn, const float* imgs_host, size_t img_pitch, int count, int rows, int cols, int stride, float* out_host,
+                    size_t out_pitch, int out_stride, int out_rows, int out_cols, const HostBatchRun& run) {
+    const size_t px = (size_t)rows * cols, opx = (size_t)out_rows * out_cols;
+    DeviceBuffer d_in, d_out;
+    FDR_ALLOC(d_in, (size_t)count * px * sizeof(float), fn);
+    FDR_ALLOC(d_out, (size_t)count * opx * sizeof(float), fn);
+    int rc = FDR_OK;
+    {
+        ScopedPhase phase(p, FDR_PHASE_H2D, nullptr);
+        for (int i = 0; i < count; ++i)
+            FDR_HIP(hipMemcpy2D(d_in.as<float>() + (size_t)i * px, (size_t)cols * sizeof(float), imgs_host + (size_t)i * img_pitch,
+                                (size_t)stride * sizeof(float), (size_t)cols * sizeof(float), (size_t)rows, hipMemcpyHostToDevice));
+    }
+    {
+        ScopedPhase phase(p, FDR_PHASE_COMPUTE, nullptr);
+        rc = run(d_in.as<float>(), px, d_out.as<float>(), opx);
+    }
+    if (rc == FDR_OK) {
+        ScopedPhase phase(p, FDR_PHASE_D2H, nullptr);
+        for (int i = 0; i < count; ++i)
+            FDR_HIP(hipMemcpy2D(out_host + (size_t)i * out_pitch, (size_t)out_stride * sizeof(float), d_out.as<float>() + (size_t)i * opx,
+                                (size_t)out_cols * sizeof(float), (size_t)out_cols * sizeof(float), (size_t)out_rows, hipMemcpyDeviceToHost));
+    }
+    (void)hipStreamSynchronize(nullptr);  // (also on an error: the one-shot buffers are freed on return)
+    resolve_phases(p);
+    return rc;
 }
 
 }  // namespace fdr

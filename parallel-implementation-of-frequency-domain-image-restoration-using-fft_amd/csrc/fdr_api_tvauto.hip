@@ -1,7 +1,7 @@
 // fdr_api_tvauto.hip -- noise-constrained TV deconvolution (fdr_tv_deconv_auto_f32*; kernels in fdr_tvauto.hip): the free-boundary
 // iteration of fdr_api_tvfree.hip with the weight of every data step taken from the discrepancy of that step.  Here: the small block
 // it adds to the workspaces of the free call (per image of a launch group), the checks and the two entry points.  The driver is the
-// free call's (tvfree_group_dev with a TvAuto), on the shared solve table built for nu; the batched entry points are in
+// free call's (tvfree_group_dev with the AUTO data step), on the shared solve table built for nu; the batched entry points are in
 // fdr_api_tvfreebatch.hip.
 #include "fdr_host.hpp"
 
@@ -98,8 +98,10 @@ int tvauto_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, i
         if (rc != FDR_OK) return rc;
     }
     if (sigma_used) *sigma_used = sigma;
-    const TvAuto au{a.tau, {sigma}, {d_trace}};
-    return tvfree_dev_impl(p, fn, d_img, rows, cols, stride, d_w, wstride, d_out, out_stride, a.fp, s, &au);
+    TvDataStep au = tv_data_auto(a.tau);
+    au.sigma[0] = sigma;
+    au.trace[0] = d_trace;
+    return tvfree_dev_impl(p, fn, d_img, rows, cols, stride, d_w, wstride, d_out, out_stride, a.fp, s, au);
 }
 
 }  // namespace
@@ -131,17 +133,14 @@ int fdr_tv_deconv_auto_f32(fdr_plan* p, const float* img_host, int rows, int col
     if (rc != FDR_OK) return rc;
     const int n = a.fp.iterations;
     DeviceBuffer d_w, d_tr;  // the dense weights and the trace, for this call alone
-    if (weights_host) {
-        FDR_ALLOC(d_w, (size_t)rows * cols * sizeof(float), fn);
-        FDR_HIP(hipMemcpy2D(d_w.ptr, (size_t)cols * sizeof(float), weights_host, (size_t)wstride * sizeof(float), (size_t)cols * sizeof(float),
-                            (size_t)rows, hipMemcpyHostToDevice));
-    }
+    rc = stage_crop_weights(fn, weights_host, rows, cols, wstride, &d_w);
+    if (rc != FDR_OK) return rc;
     if (trace_host && n > 0) FDR_ALLOC(d_tr, (size_t)n * 3 * sizeof(double), fn);
     double sigma = a.sigma;
     rc = host_image_call(p, fn, img_host, rows, cols, stride, out_host, a.fp.out_rows, a.fp.out_cols, out_stride,
                          [&](const float* d_in, float* d_out) {
-                             return tvauto_dev_impl(p, fn, d_in, rows, cols, cols, weights_host ? d_w.as<float>() : nullptr, cols, d_out,
-                                                    a.fp.out_cols, a, d_tr.as<double>(), &sigma, nullptr);
+                             return tvauto_dev_impl(p, fn, d_in, rows, cols, cols, d_w.as<float>(), cols, d_out, a.fp.out_cols, a,
+                                                    d_tr.as<double>(), &sigma, nullptr);
                          });
     if (rc != FDR_OK) return rc;
     if (trace_host && n > 0) FDR_HIP(hipMemcpy(trace_host, d_tr.ptr, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost));

@@ -50,54 +50,30 @@ extern "C" {
 int fdr_tv_deconv_batch_f32_dev(fdr_plan* p, const float* d_imgs, size_t img_pitch, int count, int rows, int cols, int stride, float* d_out,
                                 size_t out_pitch, int out_stride, const fdr_tv_batch_params* params, void* stream) {
     const char* fn = "fdr_tv_deconv_batch_f32_dev";
-    if (!p || !params) return null_arg(fn);
-    if (count < 0) return fail(FDR_ERR_ARG, std::string(fn) + ": negative count");
-    if (count == 0) return FDR_OK;
-    if (!d_imgs || !d_out) return null_arg(fn);
+    int rc;
+    if (!tv_batch_begin(fn, p, params, count, d_imgs, d_out, &rc)) return rc;
     fdr_tv_params one{};
-    const int rc = tv_batch_check(p, fn, d_imgs, img_pitch, count, rows, cols, stride, d_out, out_pitch, out_stride, *params, &one);
+    rc = tv_batch_check(p, fn, d_imgs, img_pitch, count, rows, cols, stride, d_out, out_pitch, out_stride, *params, &one);
     if (rc != FDR_OK) return rc;
     FDR_HIP(hipSetDevice(p->device));
     return tv_batch_run(p, fn, d_imgs, img_pitch, count, rows, cols, stride, d_out, out_pitch, out_stride, one,
                         params->coupling == FDR_TV_COUPLE_CHANNELS, (hipStream_t)stream);
 }
 
-// host pointers: every image in (dense), the batch on the null stream, every result back; one-shot device buffers
 int fdr_tv_deconv_batch_f32(fdr_plan* p, const float* imgs_host, size_t img_pitch, int count, int rows, int cols, int stride, float* out_host,
                             size_t out_pitch, int out_stride, const fdr_tv_batch_params* params) {
     const char* fn = "fdr_tv_deconv_batch_f32";
-    if (!p || !params) return null_arg(fn);
-    if (count < 0) return fail(FDR_ERR_ARG, std::string(fn) + ": negative count");
-    if (count == 0) return FDR_OK;
-    if (!imgs_host || !out_host) return null_arg(fn);
+    int rc;
+    if (!tv_batch_begin(fn, p, params, count, imgs_host, out_host, &rc)) return rc;
     fdr_tv_params one{};
-    int rc = tv_batch_check(p, fn, imgs_host, img_pitch, count, rows, cols, stride, out_host, out_pitch, out_stride, *params, &one);
+    rc = tv_batch_check(p, fn, imgs_host, img_pitch, count, rows, cols, stride, out_host, out_pitch, out_stride, *params, &one);
     if (rc != FDR_OK) return rc;
     FDR_HIP(hipSetDevice(p->device));
-    const size_t px = (size_t)rows * cols;
-    DeviceBuffer d_in, d_out;
-    FDR_ALLOC(d_in, (size_t)count * px * sizeof(float), fn);
-    FDR_ALLOC(d_out, (size_t)count * px * sizeof(float), fn);
-    {
-        ScopedPhase phase(p, FDR_PHASE_H2D, nullptr);
-        for (int i = 0; i < count; ++i)
-            FDR_HIP(hipMemcpy2D(d_in.as<float>() + (size_t)i * px, (size_t)cols * sizeof(float), imgs_host + (size_t)i * img_pitch,
-                                (size_t)stride * sizeof(float), (size_t)cols * sizeof(float), (size_t)rows, hipMemcpyHostToDevice));
-    }
-    {
-        ScopedPhase phase(p, FDR_PHASE_COMPUTE, nullptr);
-        rc = tv_batch_run(p, fn, d_in.as<float>(), px, count, rows, cols, cols, d_out.as<float>(), px, cols, one,
-                          params->coupling == FDR_TV_COUPLE_CHANNELS, nullptr);
-    }
-    if (rc == FDR_OK) {
-        ScopedPhase phase(p, FDR_PHASE_D2H, nullptr);
-        for (int i = 0; i < count; ++i)
-            FDR_HIP(hipMemcpy2D(out_host + (size_t)i * out_pitch, (size_t)out_stride * sizeof(float), d_out.as<float>() + (size_t)i * px,
-                                (size_t)cols * sizeof(float), (size_t)cols * sizeof(float), (size_t)rows, hipMemcpyDeviceToHost));
-    }
-    (void)hipStreamSynchronize(nullptr);  // (also on an error: the one-shot buffers are freed on return)
-    resolve_phases(p);
-    return rc;
+    const bool coupled = params->coupling == FDR_TV_COUPLE_CHANNELS;
+    return host_batch_call(p, fn, imgs_host, img_pitch, count, rows, cols, stride, out_host, out_pitch, out_stride, rows, cols,
+                           [&](const float* d_in, size_t px, float* d_out, size_t opx) {
+                               return tv_batch_run(p, fn, d_in, px, count, rows, cols, cols, d_out, opx, cols, one, coupled, nullptr);
+                           });
 }
 
 }  // extern "C"

@@ -1,8 +1,9 @@
 // fdr_api_tvfree.hip -- free-boundary, weighted TV deconvolution by ADMM with two splittings (fdr_tv_deconv_free_f32*; the data step
 // in fdr_tvfree.hip): the two planes per image it adds to the TV workspace, the checks, the driver (on a group of n >= 1 images: the
-// batches of fdr_api_tvfreebatch.hip run it too) and the two entry points.  Everything but
-// the data step is the periodic call's: the table kernel, the start and the spatial kernel of fdr_tv.hip with nu in the place of
-// mu, and the blur and solve chains of fdr_api_operator.hip on full planes.
+// batches of fdr_api_tvfreebatch.hip run it too, and the noise-constrained and Poisson forms with their own data step, chosen by a
+// TvDataStep) and the two entry points.  Everything but the data step is the periodic call's: the start of fdr_tv.hip, the table,
+// the prior half-step and the output tail of fdr_api_tv.hip with nu in the place of mu, and the blur chain of fdr_api_operator.hip
+// on full planes.
 #include "fdr_host.hpp"
 
 #include <cmath>
@@ -12,18 +13,20 @@ using namespace fdr;
 namespace {
 
 // names are static strings compared by pointer in PassTimer::pass_id
-const char* const kPassTfTable = "TV table: 1/(nu|H|^2+rho L)/MN (free)";
 const char* const kPassTfInit = "TVF init: x = pad(d), w = q = 0";
 const char* const kPassTfData = "TVF data: s, q, r = 2s-e (window)";
 const char* const kPassTaNorm = "TVA norm+mu: res_e, res_c, S -> mu_k";
 const char* const kPassTaData = "TVA data: s, q, r = 2s-e (mu_k)";
 const char* const kPassTpData = "TVP data: Poisson s, q, r = 2s-e (window)";
-const char* const kPassTfSpatial = "TV spatial: shrink+dual+div (free)";
-const char* const kPassTfSpatialJoint = "TV spatial: joint shrink+dual+div (free)";  // the coupled kernel, all channels of a tile
-const char* const kPassTfSolve = "B' op cols: FFT*T*IFFT (TVF solve)";
-const char* const kPassTfX = "C op rows: IFFT (TVF x)";
-const char* const kPassTfOut = "TVF out: crop+clamp";
-const char* const kPassTfNorm = "E TVF minmax+normalize";
+const TvPassNames kTfPasses = {
+    "TV table: 1/(nu|H|^2+rho L)/MN (free)",
+    "TV spatial: shrink+dual+div (free)",
+    "TV spatial: joint shrink+dual+div (free)",  // the coupled kernel, all channels of a tile
+    "B' op cols: FFT*T*IFFT (TVF solve)",
+    "C op rows: IFFT (TVF x)",
+    "TVF out: crop+clamp",
+    "E TVF minmax+normalize",
+};
 
 }  // namespace
 
@@ -59,84 +62,66 @@ int tvfree_prepare(fdr_plan* p, const char* fn, int group) {
 // windows by every data step
 int tvfree_group_dev(fdr_plan* p, const char* fn, fdr_plan::Slot* const* ws, int n, const float* const* d_imgs, int rows, int cols, int stride,
                      const float* d_w, int wstride, float* const* d_outs, int out_stride, const fdr_tv_free_params& prm, bool coupled, hipStream_t s,
-                     const TvAuto* au, const TvPoisson* po) {
-    if (n < 1 || n > kMaxGroup || n > p->tv_group || n > p->tf_group || (au && n > p->ta_group) || (au && po))
+                     const TvDataStep& data) {
+    if (n < 1 || n > kMaxGroup || n > p->tv_group || n > p->tf_group || (data.kind == TvDataStep::AUTO && n > p->ta_group))
         return fail(FDR_ERR_STATE, std::string(fn) + ": the free-boundary TV workspaces do not hold the group");
     const int M = p->M, N = p->N, iters = prm.iterations;
     const size_t P = (size_t)M * N, step = tv_image_stride(p);
     const float nu = prm.nu > 0.f ? prm.nu : prm.rho;
-    float *x[kMaxGroup], *b[kMaxGroup], *w0x[kMaxGroup], *w0y[kMaxGroup], *q[kMaxGroup], *c[kMaxGroup], *rhs[kMaxGroup];
-    const float *xc[kMaxGroup], *cc[kMaxGroup], *qc[kMaxGroup], *rhsc[kMaxGroup];
+    float *x[kMaxGroup], *b[kMaxGroup], *w0x[kMaxGroup], *w0y[kMaxGroup], *q[kMaxGroup], *c[kMaxGroup];
+    const float *xc[kMaxGroup], *cc[kMaxGroup], *qc[kMaxGroup];
     for (int k = 0; k < n; ++k) {
         x[k] = p->tv_x + k * step; b[k] = p->tv_b + k * step; w0x[k] = p->tv_w[0][0] + k * step; w0y[k] = p->tv_w[0][1] + k * step;
-        q[k] = p->tf_q + k * P; c[k] = p->tf_c + k * P; rhs[k] = ws[k]->raw;
-        xc[k] = x[k]; cc[k] = c[k]; qc[k] = q[k]; rhsc[k] = rhs[k];
+        q[k] = p->tf_q + k * P; c[k] = p->tf_c + k * P;
+        xc[k] = x[k]; cc[k] = c[k]; qc[k] = q[k];
     }
+    int rc = FDR_OK;
     // T is the periodic call's table for mu = nu: the cache says so, and a periodic call with another mu builds its own again
-    if (iters > 0 && (p->tv_gen != p->op_gen || p->tv_mu != nu || p->tv_rho != prm.rho)) {
-        ScopedPass t(p, s, kPassTfTable);
-        FDR_HIP(launch_tv_table(p->op_h, p->tv_T, p->lap, M, N, p->pstride, p->npanels, (double)nu, (double)prm.rho, s));
-        p->tv_gen = p->op_gen; p->tv_mu = nu; p->tv_rho = prm.rho;
-    }
+    if (iters > 0) rc = tv_solve_table(p, kTfPasses, nu, prm.rho, s);
+    if (rc != FDR_OK) return rc;
     {
         ScopedPass t(p, s, kPassTfInit);
         FDR_HIP(launch_tv_init_n(n, d_imgs, rows, cols, stride, x, w0x, w0y, M, N, s));
         if (iters > 0) FDR_HIP(hipMemsetAsync(p->tf_q, 0, (size_t)n * P * sizeof(float), s));  // the group's q planes lie together
     }
-    int rc = FDR_OK;
     for (int it = 0; it < iters && rc == FDR_OK; ++it) {
-        float* const* w = p->tv_w[it & 1];
-        float* const* nw = p->tv_w[(it + 1) & 1];
         rc = blur_window_dev_n(p, ws, n, xc, M, N, N, c, N, 0, s, M, N);  // c = blur(x)
         if (rc != FDR_OK) break;
-        if (au) {  // the weight of this step from the discrepancy of e = c + q, image by image, then the step with it
+        switch (data.kind) {  // the data step: c becomes r
+        case TvDataStep::AUTO: {  // the weight of this step from the discrepancy of e = c + q, image by image, then the step with it
             {
                 ScopedPass t(p, s, kPassTaNorm);
                 double* tr[kMaxGroup];
-                for (int k = 0; k < n; ++k) tr[k] = au->trace[k] ? au->trace[k] + 3 * (size_t)it : nullptr;
+                for (int k = 0; k < n; ++k) tr[k] = data.trace[k] ? data.trace[k] + 3 * (size_t)it : nullptr;
                 FDR_HIP(launch_tvauto_norm_n(n, cc, qc, d_imgs, stride, d_w, wstride, rows, cols, M, N, p->ta_part, s));
-                FDR_HIP(launch_tvauto_mu_n(n, p->ta_part, tvauto_partials(rows, cols), au->sigma, au->tau, nu, p->ta_mu, p->ta_stat, tr, s));
+                FDR_HIP(launch_tvauto_mu_n(n, p->ta_part, tvauto_partials(rows, cols), data.sigma, data.tau, nu, p->ta_mu, p->ta_stat, tr, s));
             }
             ScopedPass t(p, s, kPassTaData);
-            FDR_HIP(launch_tvauto_data_n(n, c, q, d_imgs, stride, d_w, wstride, rows, cols, M, N, p->ta_mu, nu, s));  // c becomes r
-        } else if (po) {  // the Poisson likelihood: another step on the same window, planes and bytes
+            FDR_HIP(launch_tvauto_data_n(n, c, q, d_imgs, stride, d_w, wstride, rows, cols, M, N, p->ta_mu, nu, s));
+            break;
+        }
+        case TvDataStep::POISSON: {  // the Poisson likelihood: another step on the same window, planes and bytes
             ScopedPass t(p, s, kPassTpData);
-            FDR_HIP(launch_tvpoisson_data_n(n, c, q, d_imgs, stride, d_w, wstride, rows, cols, M, N, prm.mu, nu, po->background, s));  // c becomes r
-        } else {
+            FDR_HIP(launch_tvpoisson_data_n(n, c, q, d_imgs, stride, d_w, wstride, rows, cols, M, N, prm.mu, nu, data.background, s));
+            break;
+        }
+        case TvDataStep::LEAST_SQUARES: {
             ScopedPass t(p, s, kPassTfData);
-            FDR_HIP(launch_tvfree_data_n(n, c, q, d_imgs, stride, d_w, wstride, rows, cols, M, N, prm.mu, nu, s));  // c becomes r
+            FDR_HIP(launch_tvfree_data_n(n, c, q, d_imgs, stride, d_w, wstride, rows, cols, M, N, prm.mu, nu, s));
+            break;
+        }
         }
         rc = blur_window_dev_n(p, ws, n, cc, M, N, N, b, N, 1, s, M, N);  // b = blur^T(r)
-        if (rc != FDR_OK) break;
-        {
-            ScopedPass t(p, s, coupled ? kPassTfSpatialJoint : kPassTfSpatial);
-            FDR_HIP(launch_tv_spatial_n(n, p->tv_x, w[0], w[1], p->tv_b, nw[0], nw[1], step, rhs, M, N, nu, prm.rho, prm.anisotropic, coupled, s));
-        }
-        rc = op_rows_fwd_n(p, ws, n, rhsc, M, N, N, s);
-        if (rc == FDR_OK) rc = op_cols_table_n(p, ws, n, p->tv_T, kPassTfSolve, s);
-        if (rc == FDR_OK) rc = op_rows_inv_n(p, ws, n, ROW_OUT_BLUR, kPassTfX, nullptr, 0, nullptr, x, N, M, N, s);
+        if (rc == FDR_OK) rc = tv_prior_half_step(p, kTfPasses, ws, n, it, nu, prm.rho, prm.anisotropic, coupled, s);
     }
     if (rc != FDR_OK) return rc;
-    if (prm.norm_area == FDR_NORM_NONE) {
-        ScopedPass t(p, s, kPassTfOut);
-        FDR_HIP(launch_tv_output_n(n, xc, N, d_outs, prm.out_rows, prm.out_cols, out_stride, prm.nonneg, s));
-        return FDR_OK;
-    }
-    const float* const* fin = xc;
-    if (prm.nonneg) {  // the clamped planes go to rhs, free by now
-        ScopedPass t(p, s, kPassTfOut);
-        FDR_HIP(launch_tv_output_n(n, xc, N, rhs, prm.out_rows, prm.out_cols, N, 1, s));
-        fin = rhsc;
-    }
-    for (int k = 0; k < n && rc == FDR_OK; ++k)
-        rc = normalize_window(p, fn, kPassTfNorm, fin[k], N, prm.out_rows, prm.out_cols, prm.norm_area, d_outs[k], out_stride, s);
-    return rc;
+    return tv_output_tail(p, fn, kTfPasses, ws, n, d_outs, prm.out_rows, prm.out_cols, out_stride, prm.nonneg, prm.norm_area, s);
 }
 
 int tvfree_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, int cols, int stride, const float* d_w, int wstride, float* d_out,
-                    int out_stride, const fdr_tv_free_params& prm, hipStream_t s, const TvAuto* au, const TvPoisson* po) {
+                    int out_stride, const fdr_tv_free_params& prm, hipStream_t s, const TvDataStep& data) {
     fdr_plan::Slot* w = &p->slots[0];
-    return tvfree_group_dev(p, fn, &w, 1, &d_img, rows, cols, stride, d_w, wstride, &d_out, out_stride, prm, false, s, au, po);
+    return tvfree_group_dev(p, fn, &w, 1, &d_img, rows, cols, stride, d_w, wstride, &d_out, out_stride, prm, false, s, data);
 }
 
 // The first free-boundary TV call of a plan, or the first on a larger group: q and c / r, two M x N planes per image of the group
@@ -184,16 +169,12 @@ int fdr_tv_deconv_free_f32(fdr_plan* p, const float* img_host, int rows, int col
     rc = tvfree_prepare(p, fn);
     if (rc != FDR_OK) return rc;
     const fdr_tv_free_params prm = *params;
-    DeviceBuffer d_w;  // the weights, dense, for this call alone: no plane of the workspace is free over the whole iteration
-    if (weights_host) {
-        FDR_ALLOC(d_w, (size_t)rows * cols * sizeof(float), fn);
-        FDR_HIP(hipMemcpy2D(d_w.ptr, (size_t)cols * sizeof(float), weights_host, (size_t)wstride * sizeof(float), (size_t)cols * sizeof(float),
-                            (size_t)rows, hipMemcpyHostToDevice));
-    }
+    DeviceBuffer d_w;  // the weights, dense, for this call alone
+    rc = stage_crop_weights(fn, weights_host, rows, cols, wstride, &d_w);
+    if (rc != FDR_OK) return rc;
     return host_image_call(p, fn, img_host, rows, cols, stride, out_host, prm.out_rows, prm.out_cols, out_stride,
                            [&](const float* d_in, float* d_out) {
-                               return tvfree_dev_impl(p, fn, d_in, rows, cols, cols, weights_host ? d_w.as<float>() : nullptr, cols, d_out,
-                                                      prm.out_cols, prm, nullptr);
+                               return tvfree_dev_impl(p, fn, d_in, rows, cols, cols, d_w.as<float>(), cols, d_out, prm.out_cols, prm, nullptr);
                            });
 }
 

@@ -113,7 +113,7 @@ int auto_batch_run(fdr_plan* p, const char* fn, const float* d_imgs, size_t img_
     int rc = tvauto_prepare(p, fn, group);
     for (int i0 = 0; i0 < count && rc == FDR_OK; i0 += group) {
         const LaunchGroup g(p, i0, count, d_imgs, img_pitch, d_out, out_pitch);
-        TvAuto au{a.tau, {}, {}};
+        TvDataStep au = tv_data_auto(a.tau);
         for (int k = 0; k < g.n && rc == FDR_OK; ++k) {
             double sigma = sigmas ? sigmas[i0 + k] : a.sigma;
             if (sigma == 0.0 && iters > 0) rc = tvauto_noise_dev(p, g.ins[k], rows, cols, stride, &sigma, s);
@@ -122,7 +122,7 @@ int auto_batch_run(fdr_plan* p, const char* fn, const float* d_imgs, size_t img_
             if (sigma_used) sigma_used[i0 + k] = sigma;
         }
         if (rc != FDR_OK) break;
-        rc = tvfree_group_dev(p, fn, g.ws, g.n, g.ins, rows, cols, stride, d_w, wstride, g.outs, out_stride, a.fp, coupled, s, &au);
+        rc = tvfree_group_dev(p, fn, g.ws, g.n, g.ins, rows, cols, stride, d_w, wstride, g.outs, out_stride, a.fp, coupled, s, au);
         if (rc == FDR_OK && stats && iters > 0) {
             FDR_HIP(hipMemcpyAsync(stats + 4 * (size_t)i0, p->ta_stat, 4 * (size_t)g.n * sizeof(double), hipMemcpyDeviceToHost, s));
             FDR_HIP(hipStreamSynchronize(s));
@@ -133,61 +133,16 @@ int auto_batch_run(fdr_plan* p, const char* fn, const float* d_imgs, size_t img_
 
 }  // namespace
 
-namespace fdr {
-
-// the dense copy of the host weights for one call (no plane of the workspace is free over the whole iteration)
-int stage_crop_weights(const char* fn, const float* weights_host, int rows, int cols, int wstride, DeviceBuffer* d_w) {
-    if (!weights_host) return FDR_OK;
-    FDR_ALLOC(*d_w, (size_t)rows * cols * sizeof(float), fn);
-    FDR_HIP(hipMemcpy2D(d_w->ptr, (size_t)cols * sizeof(float), weights_host, (size_t)wstride * sizeof(float), (size_t)cols * sizeof(float),
-                        (size_t)rows, hipMemcpyHostToDevice));
-    return FDR_OK;
-}
-
-// host pointers: every image in (dense), `run` on the dense device batch on the null stream, every output window back; one-shot
-// device buffers, as fdr_tv_deconv_batch_f32
-int host_batch_call(fdr_plan* p, const char* fn, const float* imgs_host, size_t img_pitch, int count, int rows, int cols, int stride, float* out_host,
-                    size_t out_pitch, int out_stride, int out_rows, int out_cols, const HostBatchRun& run) {
-    const size_t px = (size_t)rows * cols, opx = (size_t)out_rows * out_cols;
-    DeviceBuffer d_in, d_out;
-    FDR_ALLOC(d_in, (size_t)count * px * sizeof(float), fn);
-    FDR_ALLOC(d_out, (size_t)count * opx * sizeof(float), fn);
-    int rc = FDR_OK;
-    {
-        ScopedPhase phase(p, FDR_PHASE_H2D, nullptr);
-        for (int i = 0; i < count; ++i)
-            FDR_HIP(hipMemcpy2D(d_in.as<float>() + (size_t)i * px, (size_t)cols * sizeof(float), imgs_host + (size_t)i * img_pitch,
-                                (size_t)stride * sizeof(float), (size_t)cols * sizeof(float), (size_t)rows, hipMemcpyHostToDevice));
-    }
-    {
-        ScopedPhase phase(p, FDR_PHASE_COMPUTE, nullptr);
-        rc = run(d_in.as<float>(), px, d_out.as<float>(), opx);
-    }
-    if (rc == FDR_OK) {
-        ScopedPhase phase(p, FDR_PHASE_D2H, nullptr);
-        for (int i = 0; i < count; ++i)
-            FDR_HIP(hipMemcpy2D(out_host + (size_t)i * out_pitch, (size_t)out_stride * sizeof(float), d_out.as<float>() + (size_t)i * opx,
-                                (size_t)out_cols * sizeof(float), (size_t)out_cols * sizeof(float), (size_t)out_rows, hipMemcpyDeviceToHost));
-    }
-    (void)hipStreamSynchronize(nullptr);  // (also on an error: the one-shot buffers are freed on return)
-    resolve_phases(p);
-    return rc;
-}
-
-}  // namespace fdr
-
 extern "C" {
 
 int fdr_tv_deconv_free_batch_f32_dev(fdr_plan* p, const float* d_imgs, size_t img_pitch, int count, int rows, int cols, int stride,
                                      const float* d_weights, int wstride, float* d_out, size_t out_pitch, int out_stride,
                                      const fdr_tv_free_batch_params* params, void* stream) {
     const char* fn = "fdr_tv_deconv_free_batch_f32_dev";
-    if (!p || !params) return null_arg(fn);
-    if (count < 0) return fail(FDR_ERR_ARG, std::string(fn) + ": negative count");
-    if (count == 0) return FDR_OK;
-    if (!d_imgs || !d_out) return null_arg(fn);
+    int rc;
+    if (!tv_batch_begin(fn, p, params, count, d_imgs, d_out, &rc)) return rc;
     fdr_tv_free_params one{};
-    const int rc = free_batch_check(p, fn, d_imgs, img_pitch, count, rows, cols, stride, d_weights, wstride, d_out, out_pitch, out_stride, *params, &one);
+    rc = free_batch_check(p, fn, d_imgs, img_pitch, count, rows, cols, stride, d_weights, wstride, d_out, out_pitch, out_stride, *params, &one);
     if (rc != FDR_OK) return rc;
     FDR_HIP(hipSetDevice(p->device));
     return free_batch_run(p, fn, d_imgs, img_pitch, count, rows, cols, stride, d_weights, wstride, d_out, out_pitch, out_stride, one,
@@ -198,12 +153,10 @@ int fdr_tv_deconv_free_batch_f32(fdr_plan* p, const float* imgs_host, size_t img
                                  const float* weights_host, int wstride, float* out_host, size_t out_pitch, int out_stride,
                                  const fdr_tv_free_batch_params* params) {
     const char* fn = "fdr_tv_deconv_free_batch_f32";
-    if (!p || !params) return null_arg(fn);
-    if (count < 0) return fail(FDR_ERR_ARG, std::string(fn) + ": negative count");
-    if (count == 0) return FDR_OK;
-    if (!imgs_host || !out_host) return null_arg(fn);
+    int rc;
+    if (!tv_batch_begin(fn, p, params, count, imgs_host, out_host, &rc)) return rc;
     fdr_tv_free_params one{};
-    int rc = free_batch_check(p, fn, imgs_host, img_pitch, count, rows, cols, stride, weights_host, wstride, out_host, out_pitch, out_stride, *params,
+    rc = free_batch_check(p, fn, imgs_host, img_pitch, count, rows, cols, stride, weights_host, wstride, out_host, out_pitch, out_stride, *params,
                               &one);
     if (rc != FDR_OK) return rc;
     FDR_HIP(hipSetDevice(p->device));
@@ -223,12 +176,10 @@ int fdr_tv_deconv_auto_batch_f32_dev(fdr_plan* p, const float* d_imgs, size_t im
                                      const fdr_tv_auto_batch_params* params, const double* sigmas, double* d_trace, size_t trace_pitch,
                                      void* stream) {
     const char* fn = "fdr_tv_deconv_auto_batch_f32_dev";
-    if (!p || !params) return null_arg(fn);
-    if (count < 0) return fail(FDR_ERR_ARG, std::string(fn) + ": negative count");
-    if (count == 0) return FDR_OK;
-    if (!d_imgs || !d_out) return null_arg(fn);
+    int rc;
+    if (!tv_batch_begin(fn, p, params, count, d_imgs, d_out, &rc)) return rc;
     TvAutoArgs a{};
-    const int rc = auto_batch_check(p, fn, d_imgs, img_pitch, count, rows, cols, stride, d_weights, wstride, d_out, out_pitch, out_stride, *params,
+    rc = auto_batch_check(p, fn, d_imgs, img_pitch, count, rows, cols, stride, d_weights, wstride, d_out, out_pitch, out_stride, *params,
                                     sigmas, d_trace, d_trace != nullptr, trace_pitch, &a);
     if (rc != FDR_OK) return rc;
     FDR_HIP(hipSetDevice(p->device));
@@ -241,12 +192,10 @@ int fdr_tv_deconv_auto_batch_f32(fdr_plan* p, const float* imgs_host, size_t img
                                  const fdr_tv_auto_batch_params* params, const double* sigmas, fdr_tv_auto_result* results, double* trace_host,
                                  size_t trace_pitch) {
     const char* fn = "fdr_tv_deconv_auto_batch_f32";
-    if (!p || !params) return null_arg(fn);
-    if (count < 0) return fail(FDR_ERR_ARG, std::string(fn) + ": negative count");
-    if (count == 0) return FDR_OK;
-    if (!imgs_host || !out_host) return null_arg(fn);
+    int rc;
+    if (!tv_batch_begin(fn, p, params, count, imgs_host, out_host, &rc)) return rc;
     TvAutoArgs a{};
-    int rc = auto_batch_check(p, fn, imgs_host, img_pitch, count, rows, cols, stride, weights_host, wstride, out_host, out_pitch, out_stride, *params,
+    rc = auto_batch_check(p, fn, imgs_host, img_pitch, count, rows, cols, stride, weights_host, wstride, out_host, out_pitch, out_stride, *params,
                               sigmas, nullptr, trace_host != nullptr, trace_pitch, &a);
     if (rc != FDR_OK) return rc;
     FDR_HIP(hipSetDevice(p->device));

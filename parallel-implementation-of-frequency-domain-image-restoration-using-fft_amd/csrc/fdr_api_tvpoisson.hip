@@ -1,7 +1,7 @@
 // fdr_api_tvpoisson.hip -- Poisson-likelihood TV deconvolution (fdr_tv_deconv_poisson_f32*, its batches and the data step alone;
-// kernel in fdr_tvpoisson.hip): the free-boundary iteration of fdr_api_tvfree.hip with the least-squares data step replaced by that
+// kernel in fdr_tvfree.hip): the free-boundary iteration of fdr_api_tvfree.hip with the least-squares data step replaced by that
 // of the Poisson term mu m [(blur(x) + b) - d+ log(blur(x) + b)].  Here: the checks and the entry points.  The driver is the free
-// call's (tvfree_group_dev with a TvPoisson), on its workspaces and on the shared solve table built for nu; nothing is allocated
+// call's (tvfree_group_dev with the POISSON data step), on its workspaces and on the shared solve table built for nu; nothing is allocated
 // that the free call does not allocate.
 #include "fdr_host.hpp"
 
@@ -44,11 +44,11 @@ int poisson_batch_run(fdr_plan* p, const char* fn, const float* d_imgs, size_t i
                       const float* d_w, int wstride, float* d_out, size_t out_pitch, int out_stride, const fdr_tv_free_params& fp,
                       float background, bool coupled, hipStream_t s) {
     const int group = launch_group(p, count);
-    const TvPoisson po{background};
+    const TvDataStep po = tv_data_poisson(background);
     int rc = tvfree_prepare(p, fn, group);
     for (int i0 = 0; i0 < count && rc == FDR_OK; i0 += group) {
         const LaunchGroup g(p, i0, count, d_imgs, img_pitch, d_out, out_pitch);
-        rc = tvfree_group_dev(p, fn, g.ws, g.n, g.ins, rows, cols, stride, d_w, wstride, g.outs, out_stride, fp, coupled, s, nullptr, &po);
+        rc = tvfree_group_dev(p, fn, g.ws, g.n, g.ins, rows, cols, stride, d_w, wstride, g.outs, out_stride, fp, coupled, s, po);
     }
     return rc;
 }
@@ -80,8 +80,8 @@ int fdr_tv_deconv_poisson_f32_dev(fdr_plan* p, const float* d_img, int rows, int
     FDR_HIP(hipSetDevice(p->device));
     rc = tvfree_prepare(p, fn);
     if (rc != FDR_OK) return rc;
-    const TvPoisson po{params->background};
-    return tvfree_dev_impl(p, fn, d_img, rows, cols, stride, d_weights, wstride, d_out, out_stride, fp, (hipStream_t)stream, nullptr, &po);
+    return tvfree_dev_impl(p, fn, d_img, rows, cols, stride, d_weights, wstride, d_out, out_stride, fp, (hipStream_t)stream,
+                           tv_data_poisson(params->background));
 }
 
 int fdr_tv_deconv_poisson_f32(fdr_plan* p, const float* img_host, int rows, int cols, int stride, const float* weights_host, int wstride,
@@ -94,14 +94,13 @@ int fdr_tv_deconv_poisson_f32(fdr_plan* p, const float* img_host, int rows, int 
     FDR_HIP(hipSetDevice(p->device));
     rc = tvfree_prepare(p, fn);
     if (rc != FDR_OK) return rc;
-    const TvPoisson po{params->background};
+    const TvDataStep po = tv_data_poisson(params->background);
     DeviceBuffer d_w;  // the weights, dense, for this call alone
     rc = stage_crop_weights(fn, weights_host, rows, cols, wstride, &d_w);
     if (rc != FDR_OK) return rc;
     return host_image_call(p, fn, img_host, rows, cols, stride, out_host, fp.out_rows, fp.out_cols, out_stride,
                            [&](const float* d_in, float* d_out) {
-                               return tvfree_dev_impl(p, fn, d_in, rows, cols, cols, d_w.as<float>(), cols, d_out, fp.out_cols, fp, nullptr, nullptr,
-                                                      &po);
+                               return tvfree_dev_impl(p, fn, d_in, rows, cols, cols, d_w.as<float>(), cols, d_out, fp.out_cols, fp, nullptr, po);
                            });
 }
 
@@ -109,12 +108,10 @@ int fdr_tv_deconv_poisson_batch_f32_dev(fdr_plan* p, const float* d_imgs, size_t
                                         const float* d_weights, int wstride, float* d_out, size_t out_pitch, int out_stride,
                                         const fdr_tv_poisson_batch_params* params, void* stream) {
     const char* fn = "fdr_tv_deconv_poisson_batch_f32_dev";
-    if (!p || !params) return null_arg(fn);
-    if (count < 0) return fail(FDR_ERR_ARG, std::string(fn) + ": negative count");
-    if (count == 0) return FDR_OK;
-    if (!d_imgs || !d_out) return null_arg(fn);
+    int rc;
+    if (!tv_batch_begin(fn, p, params, count, d_imgs, d_out, &rc)) return rc;
     fdr_tv_free_params fp{};
-    const int rc = poisson_batch_check(p, fn, d_imgs, img_pitch, count, rows, cols, stride, d_weights, wstride, d_out, out_pitch, out_stride, *params, &fp);
+    rc = poisson_batch_check(p, fn, d_imgs, img_pitch, count, rows, cols, stride, d_weights, wstride, d_out, out_pitch, out_stride, *params, &fp);
     if (rc != FDR_OK) return rc;
     FDR_HIP(hipSetDevice(p->device));
     return poisson_batch_run(p, fn, d_imgs, img_pitch, count, rows, cols, stride, d_weights, wstride, d_out, out_pitch, out_stride, fp,
@@ -125,12 +122,10 @@ int fdr_tv_deconv_poisson_batch_f32(fdr_plan* p, const float* imgs_host, size_t 
                                     const float* weights_host, int wstride, float* out_host, size_t out_pitch, int out_stride,
                                     const fdr_tv_poisson_batch_params* params) {
     const char* fn = "fdr_tv_deconv_poisson_batch_f32";
-    if (!p || !params) return null_arg(fn);
-    if (count < 0) return fail(FDR_ERR_ARG, std::string(fn) + ": negative count");
-    if (count == 0) return FDR_OK;
-    if (!imgs_host || !out_host) return null_arg(fn);
+    int rc;
+    if (!tv_batch_begin(fn, p, params, count, imgs_host, out_host, &rc)) return rc;
     fdr_tv_free_params fp{};
-    int rc = poisson_batch_check(p, fn, imgs_host, img_pitch, count, rows, cols, stride, weights_host, wstride, out_host, out_pitch, out_stride, *params,
+    rc = poisson_batch_check(p, fn, imgs_host, img_pitch, count, rows, cols, stride, weights_host, wstride, out_host, out_pitch, out_stride, *params,
                                  &fp);
     if (rc != FDR_OK) return rc;
     FDR_HIP(hipSetDevice(p->device));
@@ -159,7 +154,7 @@ int fdr_tv_poisson_step_f32_dev(fdr_plan* p, float* d_c, float* d_q, const float
         (d_weights && (ranges_overlap(c, window_range(d_weights, rows, cols, wstride)) || ranges_overlap(q, window_range(d_weights, rows, cols, wstride)))))
         return fail(FDR_ERR_ARG, std::string(fn) + ": the planes c and q overlap each other, the data or the weights");
     FDR_HIP(hipSetDevice(p->device));
-    FDR_HIP(launch_tvpoisson_data(d_c, d_q, d_img, stride, d_weights, wstride, rows, cols, p->M, p->N, mu, nu, background, (hipStream_t)stream));
+    FDR_HIP(launch_tvpoisson_data_n(1, &d_c, &d_q, &d_img, stride, d_weights, wstride, rows, cols, p->M, p->N, mu, nu, background, (hipStream_t)stream));
     return FDR_OK;
 }
 

@@ -564,6 +564,18 @@ int tv_check(const fdr_plan* p, const char* fn, int rows, int cols, int stride, 
 int ensure_tv_workspace(fdr_plan* p, const char* fn, int group = 1);
 int tv_prepare(fdr_plan* p, const char* fn, int group = 1);
 inline size_t tv_image_stride(const fdr_plan* p) { return (size_t)6 * p->M * p->N; }
+// The stages the periodic driver and the free-boundary driver (fdr_api_tvfree.hip) share, on the planes 0 .. n - 1 of the TV
+// workspace and the slots ws[0 .. n), each timed under the form's pass names (static strings: PassTimer compares them by pointer).
+// table: T for the data weight (mu; nu in the free forms) and rho, unless the plan holds it already.  prior half-step of iteration
+// `it`: one spatial launch (the duals alternate with `it`; rhs is slot k's raw plane), then the solve into x as forward rows, table
+// columns and inverse rows.  output tail: the rows x cols window of every x cropped and clamped into d_outs, or, with a norm_area,
+// normalised per image (clamped into rhs first with nonneg).
+struct TvPassNames { const char *table, *spatial, *spatial_joint, *solve, *x, *out, *norm; };
+int tv_solve_table(fdr_plan* p, const TvPassNames& names, float weight, float rho, hipStream_t s);
+int tv_prior_half_step(fdr_plan* p, const TvPassNames& names, fdr_plan::Slot* const* ws, int n, int it, float weight, float rho, int anisotropic,
+                       bool coupled, hipStream_t s);
+int tv_output_tail(fdr_plan* p, const char* fn, const TvPassNames& names, fdr_plan::Slot* const* ws, int n, float* const* d_outs, int rows, int cols,
+                   int out_stride, int nonneg, int norm_area, hipStream_t s);
 // The iteration on a checked group of n >= 1 images on the slots ws[0 .. n) and the planes 0 .. n - 1 of the workspace: b and the
 // start per group, per iteration one spatial, one forward-row, one solve-column and one x-row launch for the group, the output (and
 // its normalisation, per image) at the end.  `coupled`: the images are the channels of one picture and share the shrinkage
@@ -582,13 +594,19 @@ int ensure_tvfree_workspace(fdr_plan* p, const char* fn, int group = 1);
 int tvfree_check(const fdr_plan* p, const char* fn, const float* img, int rows, int cols, int stride, const float* weights, int wstride,
                  const float* out, int out_stride, const fdr_tv_free_params* prm);
 int tvfree_prepare(fdr_plan* p, const char* fn, int group = 1);
-// what the noise-constrained calls (fdr_api_tvauto.hip, fdr_api_tvfreebatch.hip) add to an iteration: tau and, for every image of the
-// group, the noise level of its discrepancy ball and where the device writes its trace (3 doubles per iteration; null: none).  The
-// partials, mu_k and the last step's sums are the plan's.
-struct TvAuto { double tau; double sigma[kMaxGroup]; double* trace[kMaxGroup]; };
-// what the Poisson-likelihood calls (fdr_api_tvpoisson.hip) change in an iteration: the data step is that of the term
-// mu m [(s + b) - d+ log(s + b)], b = background, on prm.mu and nu; nothing else
-struct TvPoisson { float background; };
+// The data step of a free-boundary iteration, the one thing its forms differ in.  LEAST_SQUARES (fdr_api_tvfree.hip): the term
+// mu / 2 m (s - d)^2 on prm.mu.  AUTO (fdr_api_tvauto.hip, fdr_api_tvfreebatch.hip): the same with every image's weight chosen in
+// every iteration (prm.mu is not used) from tau and, for every image of the group, the noise level of its discrepancy ball; the
+// device writes image k's trace to trace[k] (3 doubles per iteration; null: none); the partials, mu_k and the last step's sums are
+// the plan's.  POISSON (fdr_api_tvpoisson.hip): the term mu m [(s + b) - d+ log(s + b)], b = background, on prm.mu.
+struct TvDataStep {
+    enum Kind { LEAST_SQUARES, AUTO, POISSON } kind;
+    double tau, sigma[kMaxGroup];  // AUTO
+    double* trace[kMaxGroup];      // AUTO
+    float background;              // POISSON
+};
+inline TvDataStep tv_data_auto(double tau) { TvDataStep d{}; d.kind = TvDataStep::AUTO; d.tau = tau; return d; }
+inline TvDataStep tv_data_poisson(float background) { TvDataStep d{}; d.kind = TvDataStep::POISSON; d.background = background; return d; }
 // the workspaces of an auto call for `group` images: the free call's, then the ta_ block (ensure_tvauto_workspace: it grows as the
 // free call's does); the auto call's own arguments (sigma, tau, nu) checked and nu resolved into *fp, the free call's parameters
 struct TvAutoArgs {
@@ -605,28 +623,23 @@ int tvauto_noise_dev(fdr_plan* p, const float* d_img, int rows, int cols, int st
 // The iteration on a checked group of n >= 1 images on the slots ws[0 .. n) and the planes 0 .. n - 1 of the workspaces: x, b, the
 // duals, q, c / r and rhs (slot k's raw plane) are full M x N planes; every d and the one weights window are read from the caller's
 // windows by every data step.  Per iteration one blur, the window launches, one adjoint blur, one spatial launch and the three solve
-// passes, each over the n images; then the output (and the per-image normalisation).  With `au` the data step takes image k's
-// weight from the norm and mu launches before it (prm.mu is not used) and the ta_ block must hold the group.  `coupled`: the images
-// are the channels of one picture and share the shrinkage (isotropic only); everything else stays per image.  One image, uncoupled,
-// makes the launches and the bits the single-image calls have always made.  With `po` (not beside `au`) the data step is the Poisson
-// one, under its own pass name; every other pass, workspace and table is the free call's.
+// passes, each over the n images; then the output (and the per-image normalisation).  `data` selects the data step, each kind
+// under its own pass name; every other pass, workspace and table is the same for all.  The AUTO step takes image k's weight from the
+// norm and mu launches before it, and the ta_ block must hold the group.  `coupled`: the images are the channels of one picture and
+// share the shrinkage (isotropic only); everything else stays per image.  One image, uncoupled, makes the launches and the bits the
+// single-image calls have always made.
 int tvfree_group_dev(fdr_plan* p, const char* fn, fdr_plan::Slot* const* ws, int n, const float* const* d_imgs, int rows, int cols, int stride,
                      const float* d_w, int wstride, float* const* d_outs, int out_stride, const fdr_tv_free_params& prm, bool coupled, hipStream_t s,
-                     const TvAuto* au = nullptr, const TvPoisson* po = nullptr);
+                     const TvDataStep& data = TvDataStep());
 // one image on slot 0: the group of one
 int tvfree_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, int cols, int stride, const float* d_w, int wstride, float* d_out,
-                    int out_stride, const fdr_tv_free_params& prm, hipStream_t s, const TvAuto* au = nullptr, const TvPoisson* po = nullptr);
+                    int out_stride, const fdr_tv_free_params& prm, hipStream_t s, const TvDataStep& data = TvDataStep());
 // what the crop batches (fdr_api_tvfreebatch.hip, fdr_api_tvpoisson.hip) share beyond the single call's checks on image 0: the
 // refusals of a batch (an unknown coupling, the coupled form with anisotropic != 0 or count > group, outputs that overlap any input
-// or the weights), the dense one-shot device copy of host weights (none for null), and the host-pointer form: every image in
-// (dense), run(d_in, in_pitch, d_out, out_pitch) on the null stream, every output window back, synchronous
+// or the weights)
 int crop_batch_check(const fdr_plan* p, const char* fn, const float* imgs, size_t img_pitch, int count, int rows, int cols, int stride,
                      const float* weights, int wstride, const float* out, size_t out_pitch, int out_stride, const fdr_tv_free_params& one,
                      int coupling);
-int stage_crop_weights(const char* fn, const float* weights_host, int rows, int cols, int wstride, DeviceBuffer* d_w);
-using HostBatchRun = std::function<int(const float* d_in, size_t in_pitch, float* d_out, size_t out_pitch)>;
-int host_batch_call(fdr_plan* p, const char* fn, const float* imgs_host, size_t img_pitch, int count, int rows, int cols, int stride, float* out_host,
-                    size_t out_pitch, int out_stride, int out_rows, int out_cols, const HostBatchRun& run);
 
 // ---- the motion-blur estimate (fdr_api_motion.hip), shared with the defocus and the combined estimate (fdr_api_defocus.hip) ----
 // the search arguments with their defaults (0 selects one), after the plan and window checks; FDR_ERR_ARG for anything outside
@@ -647,11 +660,21 @@ void motion_search_pick(const fdr_plan* p, const MotionArgs& a, double sum, fdr_
 // median of v (destroys its order), as numpy.median: the mean of the two middle values for an even count
 double median_of(std::vector<double>& v);
 
-// ---- the host-pointer form of a single-image call (fdr_api_plan.hip) ----
+// ---- the host-pointer forms of a single-image call and of a TV batch (fdr_api_plan.hip) ----
 // The rows x cols image in through the plan's staging, run(d_in, d_out) on the null stream, the out_rows x out_cols result back
 // (none when `out` is null), in the phases H2D, COMPUTE and D2H; synchronous.  The caller has checked everything that can be refused.
 int host_image_call(fdr_plan* p, const char* fn, const float* in, int rows, int cols, int stride, float* out, int out_rows, int out_cols,
                     int out_stride, const std::function<int(const float* d_in, float* d_out)>& run);
+// the dense one-shot device copy of the host weights of a crop call (none for null: d_w stays empty)
+int stage_crop_weights(const char* fn, const float* weights_host, int rows, int cols, int wstride, DeviceBuffer* d_w);
+// What every TV batch entry refuses first, in this order: a null plan or params, a negative count, then (count == 0 is FDR_OK with
+// nothing done) null images or output.  False: the entry returns *rc now; true: there is a batch to check.
+bool tv_batch_begin(const char* fn, const void* p, const void* params, int count, const void* imgs, const void* out, int* rc);
+// the host-pointer form of a TV batch: every image in (dense, one-shot device buffers), run(d_in, in_pitch, d_out, out_pitch) on the
+// null stream, every out_rows x out_cols window back, in the phases H2D, COMPUTE and D2H; synchronous
+using HostBatchRun = std::function<int(const float* d_in, size_t in_pitch, float* d_out, size_t out_pitch)>;
+int host_batch_call(fdr_plan* p, const char* fn, const float* imgs_host, size_t img_pitch, int count, int rows, int cols, int stride, float* out_host,
+                    size_t out_pitch, int out_stride, int out_rows, int out_cols, const HostBatchRun& run);
 
 // ---- the plan's transforms (fdr_api_misc.hip) ----
 // unscaled 2-D transform in place on d (M x N), rows then columns as fft/fft_serial.cpp:113-139

@@ -54,6 +54,12 @@ __host__ __device__ __forceinline__ P pick_image(P const (&p)[kMaxGroup], int i)
     const P hi = i == 4 ? p[4] : i == 5 ? p[5] : i == 6 ? p[6] : p[7];
     return i < 4 ? lo : hi;
 }
+// The same chain written on the member itself, for the per-image arrays of a struct that is a by-value kernel argument
+// (FDR_PICK_IMAGE(pl.c, z)): a macro and not pick_image, because pick_image's array reference, like a dynamic index, sends the whole
+// argument block to scratch memory.
+#define FDR_PICK_IMAGE(arr, i) \
+    ((i) < 4 ? ((i) == 0 ? arr[0] : (i) == 1 ? arr[1] : (i) == 2 ? arr[2] : arr[3]) : ((i) == 4 ? arr[4] : (i) == 5 ? arr[5] : (i) == 6 ? arr[6] : arr[7]))
+static_assert(kMaxGroup == 8, "FDR_PICK_IMAGE's select chain is written for 8 entries");
 struct RowBatch {
     const float* src_real[kMaxGroup];  // pass A input; operator kinds of the inverse pass: the real source (d, dw or u)
     float2* spec[kMaxGroup];           // pass A output / pass C' input (panel-major spectrum)
@@ -261,13 +267,55 @@ hipError_t launch_tv_spatial_n(int nimg, const float* x, const float* wx, const 
                                float* const* rhs, int M, int N, float mu, float rho, int anisotropic, int coupled, hipStream_t s);
 hipError_t launch_tv_output_n(int nimg, const float* const* x, int N, float* const* out, int rows, int cols, int out_stride, int nonneg,
                               hipStream_t s);
-// (fdr_tvfree.hip) the data step of free-boundary TV deconvolution on the rows x cols window of the dense M x N planes c and q (row
-// stride N): e = c + q; s = (mu w d + nu e) / (mu w + nu); q = e - s; c = s - q.  d and w (null: 1) are the caller's windows, read in
-// place with their own strides; nothing outside the window is read or written.
-hipError_t launch_tvfree_data(float* c, float* q, const float* d, int stride, const float* w, int wstride, int rows, int cols, int M, int N, float mu,
-                              float nu, hipStream_t s);
-// the arithmetic of that step on one pixel, shared by every data kernel (single and group, fixed and device mu) so that all of them
-// round alike: c = blur(x) and q on entry, r = s - q and the new q on exit; m is the pixel's weight
+// (fdr_tvfree.hip) the window launches of the free-boundary TV forms: the data step, and the norm of fdr_tvauto.hip on the same
+// window.  The planes of a launch group as a kernel argument, and what the host decides for a launch: the planes (entries past nimg
+// repeat image 0), the alignment bits (bit z of dvec: image z's window d takes 16-byte loads; wvec: the one weights window does),
+// the workgroup of tx x ty = 256 threads, four pixels of a row each, and gx, the workgroups across the window (tv_window_block; the
+// workgroups down the window are the kernel's own: the norm kernel gives a thread several rows).  tv_window_launch fills it, or returns false for what no window kernel takes: nimg outside 1 .. kMaxGroup, a null plane or window, planes c and q
+// that are not 16-byte aligned, a window outside the M x N planes, N no multiple of 4, a stride below cols.
+struct TvWindowPlanes {
+    float* c[kMaxGroup];
+    float* q[kMaxGroup];
+    const float* d[kMaxGroup];
+};
+struct TvWindowLaunch {
+    TvWindowPlanes pl;
+    int dvec, wvec;
+    int tx, ty, gx;
+};
+inline void tv_window_block(int cols, int* tx, int* ty, int* gx) {
+    const int groups = (cols + 3) / 4;
+    *tx = groups <= 64 ? 64 : groups <= 128 ? 128 : 256;
+    *ty = 256 / *tx;
+    *gx = (groups + *tx - 1) / *tx;
+}
+bool tv_window_launch(int nimg, float* const* c, float* const* q, const float* const* d, int stride, const float* w, int wstride, int rows, int cols,
+                      int M, int N, TvWindowLaunch* L);
+// four consecutive pixels of a caller's window row (wr = the row's base + j): one 16-byte load when the group lies inside the
+// window (`whole`: j + 3 < cols) and the host found every row aligned (`vec`), scalar loads otherwise; pixels beyond column `cols`
+// keep what v held
+__device__ __forceinline__ void tv_load_window4(const float* wr, int j, int cols, bool whole, int vec, float v[4]) {
+    if (whole && vec) {
+        const float4 t = *reinterpret_cast<const float4*>(wr);
+        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+    } else {
+#pragma unroll
+        for (int l = 0; l < 4; ++l)
+            if (j + l < cols) v[l] = wr[l];
+    }
+}
+// The data step on the rows x cols window of the dense M x N planes c and q (row stride N, 16-byte aligned) of 1 <= nimg <= kMaxGroup
+// images in one launch (blockIdx.z = image; one image makes the single kernel's launch): per-image planes c, q and windows d (one
+// stride, any alignment each), ONE weights window w (null: 1) for all, read in place with their own strides; nothing outside the
+// window is read or written, and every image gets the bits it gets alone.  Least squares: e = c + q; s = (mu w d + nu e) / (mu w +
+// nu); q = e - s; c = s - q.
+hipError_t launch_tvfree_data_n(int nimg, float* const* c, float* const* q, const float* const* d, int stride, const float* w, int wstride, int rows,
+                                int cols, int M, int N, float mu, float nu, hipStream_t s);
+// the same with image z's weight read from the device, mu[z] (where launch_tvauto_mu_n left it)
+hipError_t launch_tvauto_data_n(int nimg, float* const* c, float* const* q, const float* const* d, int stride, const float* w, int wstride, int rows,
+                                int cols, int M, int N, const float* mu, float nu, hipStream_t s);
+// the arithmetic of the least-squares step on one pixel, shared by every launch of it (single and group, fixed and device mu) so
+// that all of them round alike: c = blur(x) and q on entry, r = s - q and the new q on exit; m is the pixel's weight
 __device__ __forceinline__ void tvfree_data_pixel(const float mu, const float nu, const float m, const float d, float& c, float& q) {
     const float e = c + q;
     const float a = mu * m;
@@ -275,16 +323,11 @@ __device__ __forceinline__ void tvfree_data_pixel(const float mu, const float nu
     q = e - s;
     c = s - q;
 }
-// the same on a group of 1 <= nimg <= kMaxGroup images in one launch (blockIdx.z = image; one image is the single-image launch): per-
-// image planes c, q and windows d (one stride, any alignment each), ONE weights window for all.  Every image gets the single kernel's bits.
-hipError_t launch_tvfree_data_n(int nimg, float* const* c, float* const* q, const float* const* d, int stride, const float* w, int wstride, int rows,
-                                int cols, int M, int N, float mu, float nu, hipStream_t s);
-// (fdr_tvpoisson.hip) the data step of Poisson-likelihood TV deconvolution, on the same window, planes and caller's windows as
-// launch_tvfree_data (c and q 16-byte aligned as well): the minimiser over s of mu m [(s + b) - d+ log(s + b)] + nu / 2 (s - e)^2,
-// b = background >= 0, then q = e - s; c = s - q.
-hipError_t launch_tvpoisson_data(float* c, float* q, const float* d, int stride, const float* w, int wstride, int rows, int cols, int M, int N,
-                                 float mu, float nu, float background, hipStream_t s);
-// The arithmetic of that step on one pixel, shared by every kernel that makes it.  Every operation is one correctly rounded
+// the data step of Poisson-likelihood TV deconvolution, on the same window, planes and caller's windows: the minimiser over s of
+// mu m [(s + b) - d+ log(s + b)] + nu / 2 (s - e)^2, b = background >= 0, then q = e - s; c = s - q
+hipError_t launch_tvpoisson_data_n(int nimg, float* const* c, float* const* q, const float* const* d, int stride, const float* w, int wstride,
+                                   int rows, int cols, int M, int N, float mu, float nu, float background, hipStream_t s);
+// The arithmetic of that step on one pixel, shared by every launch of it.  Every operation is one correctly rounded
 // float operation (no contraction), in this order:
 //     e  = c + q
 //     m > 0 (a pixel that counts):
@@ -314,33 +357,23 @@ __device__ __forceinline__ void tvpoisson_data_pixel(const float mu, const float
     q = e - s;
     c = s - q;
 }
-// the same on a group of 1 <= nimg <= kMaxGroup images in one launch (blockIdx.z = image; one image is the single-image launch), one
-// weights window for all; every image gets the single kernel's bits
-hipError_t launch_tvpoisson_data_n(int nimg, float* const* c, float* const* q, const float* const* d, int stride, const float* w, int wstride,
-                                   int rows, int cols, int M, int N, float mu, float nu, float background, hipStream_t s);
 // (fdr_tvauto.hip) noise-constrained TV deconvolution, on the same window, planes and caller's windows.  norm: res_e = sum w (c + q -
 // d)^2, res_c = sum w (c - d)^2 and S = sum w in double as tvauto_partials(rows, cols) per-workgroup partials each (part holds 3 n
 // doubles; no window of an M x N plan needs more than tvauto_max_partials(M, N)).  mu: one workgroup folds the partials in index
 // order; with c2 = tau sigma^2 S, g = 0 for res_e <= c2, 1e6 for c2 = 0 or a quotient that is not finite, else min(sqrt(res_e / c2)
-// - 1, 1e6); *mu = float(nu g), stat[0 .. 3] = (res_c, res_e, mu, S) and, when not null, trace[0 .. 2] = (res_c, res_e, mu).
-// data: launch_tvfree_data's step with mu read from the device.
+// - 1, 1e6); *mu = float(nu g), stat[0 .. 3] = (res_c, res_e, mu, S) and, when not null, trace[0 .. 2] = (res_c, res_e, mu).  The
+// data step that reads that mu is launch_tvauto_data_n above.
 int tvauto_partials(int rows, int cols);
 int tvauto_max_partials(int M, int N);
-hipError_t launch_tvauto_norm(const float* c, const float* q, const float* d, int stride, const float* w, int wstride, int rows, int cols, int M, int N,
-                              double* part, hipStream_t s);
 hipError_t launch_tvauto_mu(const double* part, int n, double sigma, double tau, float nu, float* mu, double* stat, double* trace, hipStream_t s);
-hipError_t launch_tvauto_data(float* c, float* q, const float* d, int stride, const float* w, int wstride, int rows, int cols, int M, int N,
-                              const float* mu, float nu, hipStream_t s);
-// the same on a group of 1 <= nimg <= kMaxGroup images in one launch each (one image is the single-image launch), every image with
-// the bits of the single kernels: image z's partials at part + z 3 n (n = tvauto_partials(rows, cols)), its noise level sigma[z], its
+// on a group of 1 <= nimg <= kMaxGroup images in one launch each (one image makes the single kernel's launch), every image with the
+// bits of the single kernels: image z's partials at part + z 3 n (n = tvauto_partials(rows, cols)), its noise level sigma[z], its
 // weight at mu[z], its sums at stat + 4 z and, where trace[z] is not null, there (trace itself may be null).  The mu launch runs one
 // workgroup per image.
 hipError_t launch_tvauto_norm_n(int nimg, const float* const* c, const float* const* q, const float* const* d, int stride, const float* w, int wstride,
                                 int rows, int cols, int M, int N, double* part, hipStream_t s);
 hipError_t launch_tvauto_mu_n(int nimg, const double* part, int n, const double* sigma, double tau, float nu, float* mu, double* stat,
                               double* const* trace, hipStream_t s);
-hipError_t launch_tvauto_data_n(int nimg, float* const* c, float* const* q, const float* const* d, int stride, const float* w, int wstride, int rows,
-                                int cols, int M, int N, const float* mu, float nu, hipStream_t s);
 
 // (fdr_motion.hip) the motion-blur estimate.  window: the Hann tables into hann[rows + cols], w . img on the window and 0 elsewhere
 // into the row-major M x N complex plane, sum |x| partials (motion_pad_partials of them) folded in a fixed order into

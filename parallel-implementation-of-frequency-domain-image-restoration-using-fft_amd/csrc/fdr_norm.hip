@@ -68,14 +68,9 @@ __global__ __launch_bounds__(256) void normalize_kernel(const float* __restrict_
                                                         int rows, int cols, int out_stride, const NormBatch nb) {
     if (nb.nimg > 1) {  // blockIdx.y = image
         const int i = blockIdx.y;
-        // (direct member accesses: through pick_image's array reference this by-value kernel argument went to scratch
-        // memory; LAB_NOTES "kernel arguments in scratch")
-#define FDR_PICK8(arr) (i < 4 ? (i == 0 ? arr[0] : i == 1 ? arr[1] : i == 2 ? arr[2] : arr[3]) : (i == 4 ? arr[4] : i == 5 ? arr[5] : i == 6 ? arr[6] : arr[7]))
-        static_assert(kMaxGroup == 8, "select chain written for 8 entries");
-        raw = FDR_PICK8(nb.raw);
-        part = FDR_PICK8(nb.part);
-        out = FDR_PICK8(nb.out);
-#undef FDR_PICK8
+        raw = FDR_PICK_IMAGE(nb.raw, i);
+        part = FDR_PICK_IMAGE(nb.part, i);
+        out = FDR_PICK_IMAGE(nb.out, i);
     }
     __shared__ float2 red[4];
     float mn, mx;

@@ -56,11 +56,6 @@ struct RaPlanes {
     float* g[kMaxGroup];
     float* yw[kMaxGroup];
 };
-// entry i (uniform over the workgroup) as a select chain on scalars, on the member itself: a dynamic index, or pick_image's array
-// reference to a by-value kernel argument, sends the argument block to scratch memory
-#define FDR_RA_PICK(arr, i) \
-    ((i) < 4 ? ((i) == 0 ? arr[0] : (i) == 1 ? arr[1] : (i) == 2 ? arr[2] : arr[3]) : ((i) == 4 ? arr[4] : (i) == 5 ? arr[5] : (i) == 6 ? arr[6] : arr[7]))
-static_assert(kMaxGroup == 8, "select chain written for 8 entries");
 
 // The per-tile code of each kernel is a macro, expanded in the single-image kernel and in its group form: as an inlined function it
 // changed the register allocation of the single-image kernels, whose code must stay what it was (tools/kernel_diff.py).  A macro
@@ -121,9 +116,9 @@ template <bool VEC, bool PARTIALS>
 __global__ __launch_bounds__(kRaThreads) void rlaccel_direction_group_kernel(const RaPlanes pl, int u1s, int ys, int gs, int rows, int cols,
                                                                              double* __restrict__ part0, int n) {
     const int z = blockIdx.z;
-    const float* __restrict__ u1 = FDR_RA_PICK(pl.u1, z);
-    const float* __restrict__ y = FDR_RA_PICK(pl.y, z);
-    float* __restrict__ g = FDR_RA_PICK(pl.g, z);
+    const float* __restrict__ u1 = FDR_PICK_IMAGE(pl.u1, z);
+    const float* __restrict__ y = FDR_PICK_IMAGE(pl.y, z);
+    float* __restrict__ g = FDR_PICK_IMAGE(pl.g, z);
     double* __restrict__ part = PARTIALS ? part0 + (size_t)z * 2 * (size_t)n : part0;
     FDR_RA_DIRECTION_TILE(u1, u1s, y, ys, g, gs, rows, cols, part, n);
 }
@@ -205,9 +200,9 @@ template <bool VEC>
 __global__ __launch_bounds__(kRaThreads) void rlaccel_extrapolate_group_kernel(const RaPlanes pl, int u1s, int u0s, const float* __restrict__ alpha0,
                                                                                int ys, int rows, int cols) {
     const int z = blockIdx.z;
-    const float* __restrict__ u1 = FDR_RA_PICK(pl.u1, z);
-    const float* __restrict__ u0 = FDR_RA_PICK(pl.u0, z);
-    float* __restrict__ y = FDR_RA_PICK(pl.yw, z);
+    const float* __restrict__ u1 = FDR_PICK_IMAGE(pl.u1, z);
+    const float* __restrict__ u0 = FDR_PICK_IMAGE(pl.u0, z);
+    float* __restrict__ y = FDR_PICK_IMAGE(pl.yw, z);
     const float* __restrict__ alpha = alpha0 + z;
     FDR_RA_EXTRAPOLATE_TILE(u1, u1s, u0, u0s, alpha, y, ys, rows, cols);
 }

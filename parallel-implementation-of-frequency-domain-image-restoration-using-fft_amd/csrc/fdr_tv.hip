@@ -65,12 +65,6 @@ hipError_t launch_tv_table(const float2* op_h, float2* T, const double* lap, int
     return hipGetLastError();
 }
 
-// entry i (uniform over the workgroup) of a per-image pointer array of a by-value kernel argument, as a select chain on scalars on
-// the member itself (a dynamic index, or pick_image's array reference, sends the argument block to scratch memory)
-#define FDR_TV_PICK(arr, i) \
-    ((i) < 4 ? ((i) == 0 ? arr[0] : (i) == 1 ? arr[1] : (i) == 2 ? arr[2] : arr[3]) : ((i) == 4 ? arr[4] : (i) == 5 ? arr[5] : (i) == 6 ? arr[6] : arr[7]))
-static_assert(kMaxGroup == 8, "select chain written for 8 entries");
-
 // ---- the start: x = pad(d) over the whole plan, wx = wy = 0 (four pixels of a row per thread) ----
 __device__ __forceinline__ void tv_init_row(const float* __restrict__ d, const int rows, const int cols, const int stride, float* __restrict__ x,
                                             float* __restrict__ wx, float* __restrict__ wy, const int N) {
@@ -103,7 +97,7 @@ struct TvInitPlanes {
 };
 __global__ __launch_bounds__(256) void tv_init_group_kernel(const TvInitPlanes pl, const int rows, const int cols, const int stride, const int N) {
     const int z = blockIdx.z;
-    tv_init_row(FDR_TV_PICK(pl.d, z), rows, cols, stride, FDR_TV_PICK(pl.x, z), FDR_TV_PICK(pl.wx, z), FDR_TV_PICK(pl.wy, z), N);
+    tv_init_row(FDR_PICK_IMAGE(pl.d, z), rows, cols, stride, FDR_PICK_IMAGE(pl.x, z), FDR_PICK_IMAGE(pl.wx, z), FDR_PICK_IMAGE(pl.wy, z), N);
 }
 
 hipError_t launch_tv_init(const float* d, int rows, int cols, int stride, float* x, float* wx, float* wy, int M, int N, hipStream_t s) {
@@ -146,7 +140,7 @@ struct TvOutPlanes {
 };
 __global__ __launch_bounds__(256) void tv_output_group_kernel(const TvOutPlanes pl, const int N, const int cols, const int out_stride, const int nonneg) {
     const int z = blockIdx.z;
-    tv_output_pixel(FDR_TV_PICK(pl.x, z), N, FDR_TV_PICK(pl.out, z), cols, out_stride, nonneg);
+    tv_output_pixel(FDR_PICK_IMAGE(pl.x, z), N, FDR_PICK_IMAGE(pl.out, z), cols, out_stride, nonneg);
 }
 
 hipError_t launch_tv_output(const float* x, int N, float* out, int rows, int cols, int out_stride, int nonneg, hipStream_t s) {
@@ -397,7 +391,7 @@ __global__ __launch_bounds__(kTvThreads) void tv_spatial_group_kernel(const TvPl
     const float no44[4][4] = {}, no4[4] = {};
     const size_t at = (size_t)z * pl.stride;
     tv_spatial_tile<ANISO ? TV_ANISO : TV_ISO>(tv_tile(M, N, logtx), xs, vxr, vyb, pl.x + at, pl.wx + at, pl.wy + at, pl.b + at, pl.nwx + at,
-                                               pl.nwy + at, FDR_TV_PICK(pl.rhs, z), N, mu, rho, t, no44, no4, no4);
+                                               pl.nwy + at, FDR_PICK_IMAGE(pl.rhs, z), N, mu, rho, t, no44, no4, no4);
 }
 
 // Vectorial TV: the nimg images are the channels of one picture and share one shrinkage, z_c = s g_c with s = max(1 - t / m, 0) and
@@ -461,7 +455,7 @@ __global__ __launch_bounds__(kTvThreads) void tv_spatial_coupled_kernel(const Tv
     }
     for (int c = 0; c < nimg; ++c) {  // sweep 2: shrink, duals, divergence, rhs per channel
         const size_t at = (size_t)c * pl.stride;
-        tv_spatial_tile<TV_JOINT>(g, xs, vxr, vyb, pl.x + at, pl.wx + at, pl.wy + at, pl.b + at, pl.nwx + at, pl.nwy + at, FDR_TV_PICK(pl.rhs, c), N,
+        tv_spatial_tile<TV_JOINT>(g, xs, vxr, vyb, pl.x + at, pl.wx + at, pl.wy + at, pl.b + at, pl.nwx + at, pl.nwy + at, FDR_PICK_IMAGE(pl.rhs, c), N,
                                   mu, rho, t, js, jl, ju);
         __syncthreads();  // vxr and vyb are read no more
     }

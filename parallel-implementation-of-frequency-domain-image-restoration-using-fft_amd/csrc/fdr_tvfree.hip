@@ -1,129 +1,136 @@
-// fdr_tvfree.hip -- free-boundary, weighted TV deconvolution (fdr_tv_deconv_free_f32*; driver in fdr_api_tvfree.hip), the one
-// kernel the periodic iteration of fdr_tv.hip does not have: the data step of the second splitting s = blur(x),
+// fdr_tvfree.hip -- the window data step of the free-boundary ADMM iteration (driver in fdr_api_tvfree.hip), the one kernel the
+// periodic iteration of fdr_tv.hip does not have: the step of the second splitting s = blur(x),
 //
-//     e = c + q;  s = (mu m pad(d) + nu e) / (mu m + nu);  q = e - s;  r = s - q
+//     e = c + q;  s = the minimiser of the data term + nu / 2 (s - e)^2;  q = e - s;  r = s - q
 //
-// with c = blur(x) on entry and r in its place on exit.  m is the weights on the window and 0 outside it, where the step is
-// s = e, q = 0, r = c: nothing to compute and nothing to store, so the launch covers the window alone and q, zero outside the
-// window since the start, is never touched there.  d and the weights are read in place from the caller's strided windows.
-// The group form (fdr_tv_deconv_free_batch_f32*) makes the step of up to kMaxGroup images in one launch, blockIdx.z the image, with
-// one weights window for all; the single kernel and the group kernel instantiate one device function, and every data kernel of the
-// library computes a pixel by tvfree_data_pixel (fdr_kernels.hpp), so an image has the same bits in a group as alone.
+// with c = blur(x) on entry and r in its place on exit.  One kernel makes it for the three data terms of the library, which differ in
+// the arithmetic of a pixel alone (a step object, below): least squares with the weight mu an argument (fdr_tv_deconv_free_f32*),
+// least squares with every image's mu read from the device, where the mu kernel of fdr_tvauto.hip left it (fdr_tv_deconv_auto_f32*),
+// and the Poisson likelihood with a background (fdr_tv_deconv_poisson_f32*, fdr_tv_poisson_step*_f32_dev).  Outside the window, where
+// the weights are 0, the step is s = e, q = 0, r = c: nothing to compute and nothing to store, so the launch covers the window alone
+// and q, zero outside the window since the start, is never touched there; it moves 20 bytes per pixel, 24 with weights.  d and the
+// weights are read in place from the caller's strided windows.  The group form makes the step of up to kMaxGroup images in one
+// launch, blockIdx.z the image, with one weights window for all; the single kernel and the group kernel instantiate one device
+// function, and a pixel is computed by tvfree_data_pixel or tvpoisson_data_pixel (fdr_kernels.hpp), so an image has the same bits in
+// a group as alone.
 #include "fdr_kernels.hpp"
 
 namespace fdr {
 
+// The data term of a step, a by-value kernel argument: image(z) runs once per thread that has pixels, before its loads, with the
+// image of the launch group (0 in the single kernel); pixel() is the arithmetic on one pixel of weight m.
+struct TvStepLeastSquares {
+    float mu;
+    __device__ __forceinline__ void image(int) {}
+    __device__ __forceinline__ void pixel(float nu, float m, float d, float& c, float& q) const { tvfree_data_pixel(mu, nu, m, d, c, q); }
+};
+struct TvStepLeastSquaresDeviceMu {
+    const float* mu_dev;  // one weight per image of the group
+    float mu;             // this image's, loaded by image()
+    __device__ __forceinline__ void image(int z) { mu = mu_dev[z]; }
+    __device__ __forceinline__ void pixel(float nu, float m, float d, float& c, float& q) const { tvfree_data_pixel(mu, nu, m, d, c, q); }
+};
+struct TvStepPoisson {
+    float mu, background;
+    __device__ __forceinline__ void image(int) {}
+    __device__ __forceinline__ void pixel(float nu, float m, float d, float& c, float& q) const {
+        tvpoisson_data_pixel(mu, nu, background, m, d, c, q);
+    }
+};
+
 // A thread owns four consecutive pixels j .. j + 3 of window row i.  c and q are dense M x N planes (N a multiple of 4, the base
-// 256-byte aligned): 16-byte loads and stores.  d (and w) take one 16-byte load when the group lies inside the window and the
-// window's base and stride keep every row 16-byte aligned (dvec / wvec, decided on the host), scalar loads otherwise.  In the
-// group that straddles column `cols` the pixels beyond it keep the c and q they were loaded with.
-template <bool WEIGHTS>
-__device__ __forceinline__ void tvfree_data_group4(float* __restrict__ c, float* __restrict__ q, const float* __restrict__ d, const int stride,
-                                                   const float* __restrict__ w, const int wstride, const int rows, const int cols, const int N,
-                                                   const float mu, const float nu, const int dvec, const int wvec) {
+// 16-byte aligned): 16-byte loads and stores.  d (and w) are loaded by tv_load_window4 under dvec (wvec), decided on the host.  In
+// the group that straddles column `cols` the pixels beyond it keep the c and q they were loaded with.
+template <bool WEIGHTS, class Step>
+__device__ __forceinline__ void tv_data_group4(float* __restrict__ c, float* __restrict__ q, const float* __restrict__ d, const int stride,
+                                               const float* __restrict__ w, const int wstride, const int rows, const int cols, const int N,
+                                               const float nu, Step step, const int z, const int dvec, const int wvec) {
     const int j = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
     const int i = blockIdx.y * blockDim.y + threadIdx.y;
     if (i >= rows || j >= cols) return;
+    step.image(z);
     const size_t at = (size_t)i * N + j;
     const float4 c4 = *reinterpret_cast<const float4*>(c + at), q4 = *reinterpret_cast<const float4*>(q + at);
     float cc[4] = {c4.x, c4.y, c4.z, c4.w}, qq[4] = {q4.x, q4.y, q4.z, q4.w};
     float dd[4] = {0.f, 0.f, 0.f, 0.f}, mm[4] = {1.f, 1.f, 1.f, 1.f};
     const bool whole = j + 3 < cols;
-    const float* dr = d + (size_t)i * stride + j;
-    if (whole && dvec) {
-        const float4 v = *reinterpret_cast<const float4*>(dr);
-        dd[0] = v.x; dd[1] = v.y; dd[2] = v.z; dd[3] = v.w;
-    } else {
-#pragma unroll
-        for (int l = 0; l < 4; ++l)
-            if (j + l < cols) dd[l] = dr[l];
-    }
-    if (WEIGHTS) {
-        const float* wr = w + (size_t)i * wstride + j;
-        if (whole && wvec) {
-            const float4 v = *reinterpret_cast<const float4*>(wr);
-            mm[0] = v.x; mm[1] = v.y; mm[2] = v.z; mm[3] = v.w;
-        } else {
-#pragma unroll
-            for (int l = 0; l < 4; ++l)
-                if (j + l < cols) mm[l] = wr[l];
-        }
-    }
+    tv_load_window4(d + (size_t)i * stride + j, j, cols, whole, dvec, dd);
+    if (WEIGHTS) tv_load_window4(w + (size_t)i * wstride + j, j, cols, whole, wvec, mm);
 #pragma unroll
     for (int l = 0; l < 4; ++l) {
-        if (j + l < cols) tvfree_data_pixel(mu, nu, mm[l], dd[l], cc[l], qq[l]);
+        if (j + l < cols) step.pixel(nu, mm[l], dd[l], cc[l], qq[l]);
     }
     *reinterpret_cast<float4*>(q + at) = make_float4(qq[0], qq[1], qq[2], qq[3]);
     *reinterpret_cast<float4*>(c + at) = make_float4(cc[0], cc[1], cc[2], cc[3]);
 }
-template <bool WEIGHTS>
-__global__ __launch_bounds__(256) void tvfree_data_kernel(float* __restrict__ c, float* __restrict__ q, const float* __restrict__ d, const int stride,
-                                                          const float* __restrict__ w, const int wstride, const int rows, const int cols,
-                                                          const int N, const float mu, const float nu, const int dvec, const int wvec) {
-    tvfree_data_group4<WEIGHTS>(c, q, d, stride, w, wstride, rows, cols, N, mu, nu, dvec, wvec);
+template <bool WEIGHTS, class Step>
+__global__ __launch_bounds__(256) void tv_data_kernel(float* __restrict__ c, float* __restrict__ q, const float* __restrict__ d, const int stride,
+                                                      const float* __restrict__ w, const int wstride, const int rows, const int cols, const int N,
+                                                      const float nu, const Step step, const int dvec, const int wvec) {
+    tv_data_group4<WEIGHTS>(c, q, d, stride, w, wstride, rows, cols, N, nu, step, 0, dvec, wvec);
 }
-
-// entry i (uniform over the workgroup) of a per-image pointer array of a by-value kernel argument: pick_image's select chain on
-// scalars, written on the member itself (a dynamic index, or pick_image's array reference, sends the argument block to scratch memory)
-#define FDR_TF_PICK(arr, i) \
-    ((i) < 4 ? ((i) == 0 ? arr[0] : (i) == 1 ? arr[1] : (i) == 2 ? arr[2] : arr[3]) : ((i) == 4 ? arr[4] : (i) == 5 ? arr[5] : (i) == 6 ? arr[6] : arr[7]))
-static_assert(kMaxGroup == 8, "select chain written for 8 entries");
-
 // the group form: image blockIdx.z on its planes and its window, the weights window shared.  Bit z of dvec says whether image z's
 // window takes 16-byte loads: the images of a batch with an odd pitch differ in alignment.
-struct TvFreePlanes {
-    float* c[kMaxGroup];
-    float* q[kMaxGroup];
-    const float* d[kMaxGroup];
-};
-template <bool WEIGHTS>
-__global__ __launch_bounds__(256) void tvfree_data_group_kernel(const TvFreePlanes pl, const int stride, const float* __restrict__ w, const int wstride,
-                                                                const int rows, const int cols, const int N, const float mu, const float nu,
-                                                                const int dvec, const int wvec) {
+template <bool WEIGHTS, class Step>
+__global__ __launch_bounds__(256) void tv_data_group_kernel(const TvWindowPlanes pl, const int stride, const float* __restrict__ w, const int wstride,
+                                                            const int rows, const int cols, const int N, const float nu, const Step step,
+                                                            const int dvec, const int wvec) {
     const int z = blockIdx.z;
-    tvfree_data_group4<WEIGHTS>(FDR_TF_PICK(pl.c, z), FDR_TF_PICK(pl.q, z), FDR_TF_PICK(pl.d, z), stride, w, wstride, rows, cols, N, mu, nu,
-                                (dvec >> z) & 1, wvec);
+    tv_data_group4<WEIGHTS>(FDR_PICK_IMAGE(pl.c, z), FDR_PICK_IMAGE(pl.q, z), FDR_PICK_IMAGE(pl.d, z), stride, w, wstride, rows, cols, N, nu, step, z,
+                            (dvec >> z) & 1, wvec);
 }
 
-// rows x cols must lie within the M x N planes c and q (N a multiple of 4); d and w (null: weights of 1) are rows x cols windows
-// with their own strides, of any alignment
-hipError_t launch_tvfree_data(float* c, float* q, const float* d, int stride, const float* w, int wstride, int rows, int cols, int M, int N, float mu,
-                              float nu, hipStream_t s) {
-    if (!c || !q || !d || rows < 1 || cols < 1 || rows > M || cols > N || (N & 3) || stride < cols || (w && wstride < cols)) return hipErrorInvalidValue;
-    const int groups = (cols + 3) / 4;
-    const int tx = groups <= 64 ? 64 : groups <= 128 ? 128 : 256, ty = 256 / tx;
-    const dim3 grid((unsigned)((groups + tx - 1) / tx), (unsigned)((rows + ty - 1) / ty));
-    const int dvec = ((uintptr_t)d & 15) == 0 && (stride & 3) == 0;
-    const int wvec = w && ((uintptr_t)w & 15) == 0 && (wstride & 3) == 0;
-    if (w)
-        hipLaunchKernelGGL((tvfree_data_kernel<true>), grid, dim3(tx, ty), 0, s, c, q, d, stride, w, wstride, rows, cols, N, mu, nu, dvec, wvec);
-    else
-        hipLaunchKernelGGL((tvfree_data_kernel<false>), grid, dim3(tx, ty), 0, s, c, q, d, stride, w, wstride, rows, cols, N, mu, nu, dvec, wvec);
+bool tv_window_launch(int nimg, float* const* c, float* const* q, const float* const* d, int stride, const float* w, int wstride, int rows, int cols,
+                      int M, int N, TvWindowLaunch* L) {
+    if (nimg < 1 || nimg > kMaxGroup || !c || !q || !d) return false;
+    if (rows < 1 || cols < 1 || rows > M || cols > N || (N & 3) || stride < cols || (w && wstride < cols)) return false;
+    L->dvec = 0;
+    for (int k = 0; k < kMaxGroup; ++k) {
+        const int i = k < nimg ? k : 0;
+        if (!c[i] || !q[i] || !d[i] || ((uintptr_t)c[i] & 15) || ((uintptr_t)q[i] & 15)) return false;
+        L->pl.c[k] = c[i]; L->pl.q[k] = q[i]; L->pl.d[k] = d[i];
+        if (((uintptr_t)d[i] & 15) == 0 && (stride & 3) == 0) L->dvec |= 1 << k;
+    }
+    L->wvec = w && ((uintptr_t)w & 15) == 0 && (wstride & 3) == 0;
+    tv_window_block(cols, &L->tx, &L->ty, &L->gx);
+    return true;
+}
+
+namespace {
+
+// one image makes the single kernel's launch, more make the group kernel's
+template <class Step>
+hipError_t launch_tv_data(int nimg, float* const* c, float* const* q, const float* const* d, int stride, const float* w, int wstride, int rows, int cols,
+                          int M, int N, float nu, const Step step, hipStream_t s) {
+    TvWindowLaunch L;
+    if (!tv_window_launch(nimg, c, q, d, stride, w, wstride, rows, cols, M, N, &L)) return hipErrorInvalidValue;
+    const dim3 block((unsigned)L.tx, (unsigned)L.ty), grid((unsigned)L.gx, (unsigned)((rows + L.ty - 1) / L.ty), (unsigned)nimg);
+    if (nimg == 1) {
+        if (w) hipLaunchKernelGGL((tv_data_kernel<true, Step>), grid, block, 0, s, c[0], q[0], d[0], stride, w, wstride, rows, cols, N, nu, step, L.dvec & 1, L.wvec);
+        else hipLaunchKernelGGL((tv_data_kernel<false, Step>), grid, block, 0, s, c[0], q[0], d[0], stride, w, wstride, rows, cols, N, nu, step, L.dvec & 1, L.wvec);
+    } else {
+        if (w) hipLaunchKernelGGL((tv_data_group_kernel<true, Step>), grid, block, 0, s, L.pl, stride, w, wstride, rows, cols, N, nu, step, L.dvec, L.wvec);
+        else hipLaunchKernelGGL((tv_data_group_kernel<false, Step>), grid, block, 0, s, L.pl, stride, w, wstride, rows, cols, N, nu, step, L.dvec, L.wvec);
+    }
     return hipGetLastError();
 }
+
+}  // namespace
 
 hipError_t launch_tvfree_data_n(int nimg, float* const* c, float* const* q, const float* const* d, int stride, const float* w, int wstride, int rows,
                                 int cols, int M, int N, float mu, float nu, hipStream_t s) {
-    if (nimg < 1 || nimg > kMaxGroup) return hipErrorInvalidValue;
-    if (nimg == 1) return launch_tvfree_data(c[0], q[0], d[0], stride, w, wstride, rows, cols, M, N, mu, nu, s);
-    if (rows < 1 || cols < 1 || rows > M || cols > N || (N & 3) || stride < cols || (w && wstride < cols)) return hipErrorInvalidValue;
-    TvFreePlanes pl;
-    int dvec = 0;
-    for (int k = 0; k < kMaxGroup; ++k) {
-        const int i = k < nimg ? k : 0;
-        if (!c[i] || !q[i] || !d[i]) return hipErrorInvalidValue;
-        pl.c[k] = c[i]; pl.q[k] = q[i]; pl.d[k] = d[i];
-        if (((uintptr_t)d[i] & 15) == 0 && (stride & 3) == 0) dvec |= 1 << k;
-    }
-    const int groups = (cols + 3) / 4;
-    const int tx = groups <= 64 ? 64 : groups <= 128 ? 128 : 256, ty = 256 / tx;
-    const dim3 grid((unsigned)((groups + tx - 1) / tx), (unsigned)((rows + ty - 1) / ty), (unsigned)nimg);
-    const int wvec = w && ((uintptr_t)w & 15) == 0 && (wstride & 3) == 0;
-    if (w)
-        hipLaunchKernelGGL((tvfree_data_group_kernel<true>), grid, dim3(tx, ty), 0, s, pl, stride, w, wstride, rows, cols, N, mu, nu, dvec, wvec);
-    else
-        hipLaunchKernelGGL((tvfree_data_group_kernel<false>), grid, dim3(tx, ty), 0, s, pl, stride, w, wstride, rows, cols, N, mu, nu, dvec, wvec);
-    return hipGetLastError();
+    return launch_tv_data(nimg, c, q, d, stride, w, wstride, rows, cols, M, N, nu, TvStepLeastSquares{mu}, s);
+}
+
+hipError_t launch_tvauto_data_n(int nimg, float* const* c, float* const* q, const float* const* d, int stride, const float* w, int wstride, int rows,
+                                int cols, int M, int N, const float* mu, float nu, hipStream_t s) {
+    if (!mu) return hipErrorInvalidValue;
+    return launch_tv_data(nimg, c, q, d, stride, w, wstride, rows, cols, M, N, nu, TvStepLeastSquaresDeviceMu{mu, 0.f}, s);
+}
+
+hipError_t launch_tvpoisson_data_n(int nimg, float* const* c, float* const* q, const float* const* d, int stride, const float* w, int wstride,
+                                   int rows, int cols, int M, int N, float mu, float nu, float background, hipStream_t s) {
+    return launch_tv_data(nimg, c, q, d, stride, w, wstride, rows, cols, M, N, nu, TvStepPoisson{mu, background}, s);
 }
 
 }  // namespace fdr
