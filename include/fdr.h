@@ -1047,7 +1047,11 @@ int fdr_tv_poisson_step_group_f32_dev(fdr_plan* plan, float* d_c, size_t c_pitch
  *                             tile plan M x N needs 4 (M N - min_M min_N) bytes more.
  *      fdr_tiled_tile_origin  pure host: (y_a, x_b) of tile (a, b).
  *      fdr_restore_tiled_f32_dev  device pointers; allocates nothing after the tile plan's own first-use workspaces (those of the
- *                             method's single and batched calls), reads nothing back, asynchronous on `stream`.  d_work needs 256-byte
+ *                             method's single and batched calls), reads nothing back, asynchronous on `stream`.  A limit for very
+ *                             large pictures: the weight tables (32 bytes per picture row and column) are made on the host and
+ *                             uploaded from pageable memory, which the HIP runtime takes at the call without waiting up to 1 MiB
+ *                             and for which it waits for `stream` from 4 MiB on (measured): with rows + cols
+ *                             above 32768 the call may wait.  d_work needs 256-byte
  *                             alignment.  On return the plan's operator tables are those of the LAST tile's PSF (an operator PSF set
  *                             before the call is replaced).
  *      fdr_restore_tiled_f32  host pointers, synchronous; allocates and frees its own device buffers.
@@ -1160,6 +1164,7 @@ int fdr_estimate_motion_f32_dev(fdr_plan* plan, const float* d_img, int rows, in
  *      fdr_estimate_blur_f32*     both estimates from one cepstrum: *motion is what fdr_estimate_motion_f32* returns for (min_length,
  *                                 max_length, motion_step_deg), *defocus what fdr_estimate_defocus_f32* returns for (min_diameter,
  *                                 max_diameter, defocus_step_deg), bit for bit; *kind = fdr_blur_kind of the two confidences.
+ *                                 The _dev form is SYNCHRONOUS as well: it returns both estimates to the host.
  *      fdr_blur_kind              m = motion_conf / FDR_MOTION_CONF_MIN, f = defocus_conf / FDR_DEFOCUS_CONF_MIN: FDR_BLUR_NONE when
  *                                 both are below 1, else FDR_BLUR_MOTION when m >= f, else FDR_BLUR_DEFOCUS.                   */
 #define FDR_DEFOCUS_A 0.52304
