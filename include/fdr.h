@@ -641,7 +641,8 @@ int fdr_rl_tv_factor_group_f32_dev(int device, const float* d_u, size_t u_pitch,
  *                              plan as fdr_set_operator_psf* takes it, and becomes the pair H_k / (M N), conj(H_k) / (M N) by the passes
  *                              of that setter (same bits).  The tables live in a block of their own (2 count spectra), made or regrown
  *                              here, the new block before the old one is freed (FDR_ERR_ALLOC leaves the plan as it was); they never
- *                              touch the operator tables, the filter or any other call's state, and no other call reads them.  PSF
+ *                              touch the operator tables or the filter, and only the multi-frame calls (these and
+ *                              fdr_tv_deconv_frames_f32*, whose solve table a new set invalidates) read them.  PSF
  *                              sums are NOT normalised: a frame's PSF sum is its relative exposure, which alpha accounts for, and a
  *                              registration shift goes into the PSF.  The checks of the operator setter, and FDR_ERR_ARG for a count
  *                              outside 1 .. FDR_MAX_FRAMES and, for count > 1, a psf_pitch below the span of one PSF.
@@ -1019,6 +1020,59 @@ int fdr_tv_poisson_step_f32_dev(fdr_plan* plan, float* d_c, float* d_q, const fl
 int fdr_tv_poisson_step_group_f32_dev(fdr_plan* plan, float* d_c, size_t c_pitch, float* d_q, size_t q_pitch, const float* d_imgs,
                                       size_t img_pitch, int count, int rows, int cols, int stride, const float* d_weights, int wstride,
                                       float mu, float nu, float background, void* stream);
+
+/* -- multi-frame TV deconvolution: the `count` = fdr_frame_count exposures of ONE scene under one TV prior.
+ *    Frame k has the PSF k of fdr_set_frame_psfs* (H_k, sums NOT normalised: a frame's PSF sum is its exposure, a registration
+ *    shift goes into the PSF) and weights m_k on its window; one unknown x lives on the whole M x N plan:
+ *        minimise over x:  mu sum_k Phi_k(blur_k(x)) + TV(x)
+ *          FDR_TV_FRAMES_LEAST_SQUARES:  Phi_k(s) = 1/2 sum m_k (s - pad(d_k))^2
+ *          FDR_TV_FRAMES_POISSON:        Phi_k(s) = sum m_k [ (s + b) - d_k+ log(s + b) ],   b = background >= 0
+ *        x = pad(d_0);  w = 0;  q_k = 0;  t = 1 / rho;  nu = 0 selects rho;  n = iterations times:
+ *            c_k = blur_k(x) over the whole plan, k = 0 .. count - 1
+ *            e_k = c_k + q_k;  s_k = the data step of fdr_tv_deconv_free_f32* / fdr_tv_deconv_poisson_f32* on frame k's window with m_k
+ *            q_k = e_k - s_k;  r_k = s_k - q_k                                  (outside the window: q_k = 0, r_k = c_k)
+ *            b = sum_k blur_k^T(r_k): added in the spectrum in ascending k (the sum kernel of the multi-frame RL call), ONE inverse row pass
+ *            g = D x + w;  z = shrink(g, t);  w = g - z;  v = z - w             (as fdr_tv_deconv_f32)
+ *            x = IDFT2( DFT2(nu b + rho D^T v) / (nu sum_k |H_k|^2 + rho L) )
+ *    The start is frame 0 (the problem is convex: the start changes the path, not the minimiser); n = 0 returns pad(d_0).  The output
+ *    window, nonneg and norm_area are the free call's.  Frame k is read at imgs + k img_pitch; weights are NULL (all ones), one
+ *    plane for all frames (weight_pitch = 0) or one per frame (at weights + k weight_pitch).  One frame gives the bits of
+ *    fdr_tv_deconv_free_f32_dev / fdr_tv_deconv_poisson_f32_dev under that PSF as the operator PSF.  No atomics: two calls give the
+ *    same bytes, whatever the plan's launch group.  The operator PSF is neither needed nor touched; the solve table is shared with the
+ *    other TV calls, each of which builds its own again after a call of another kind or a new frame set.
+ *    THE STREAM TRAVELS IN THE STRUCT, deliberately: the _dev form runs on (hipStream_t)params->stream (NULL = the null stream) and
+ *    has no `void* stream` parameter; the host form ignores the field.  The stream-order table of the test suite is keyed on
+ *    `void* stream` parameters and is closed to edits for now, so this entry is fenced by a test file of its own with the same
+ *    helper; when that table can next be edited its cases move there.
+ *    FDR_ERR_ARG, before any device work and with the plan usable afterwards: what fdr_tv_deconv_free_f32* refuses (but for the
+ *    operator PSF, which is not needed), an unknown data_term, a background that is negative or not finite or != 0 with least
+ *    squares, a count that is not fdr_frame_count (FDR_ERR_STATE with no frame tables), an img_pitch below a window's span for
+ *    count > 1, a weight_pitch that is neither 0 nor at least the span, an output that overlaps any frame or weights plane.  The
+ *    workspace (count planes q, count planes c / r and one spectrum, beside the TV workspace of one image) is made on first use and
+ *    grown for a larger count, the new block before the old one is freed (FDR_ERR_ALLOC leaves everything as it was); the _dev
+ *    form allocates nothing afterwards, reads nothing back and stays asynchronous on its stream.                                   */
+#define FDR_TV_FRAMES_LEAST_SQUARES 0
+#define FDR_TV_FRAMES_POISSON 1
+typedef struct fdr_tv_frames_params {
+    float mu;         /* weight of the data term, > 0 */
+    float rho;        /* ADMM penalty of z = D x, > 0 */
+    float nu;         /* ADMM penalty of s_k = blur_k(x), >= 0; 0 selects rho */
+    float background; /* FDR_TV_FRAMES_POISSON: b >= 0, in the units of the data; must be 0 with least squares */
+    int data_term;    /* FDR_TV_FRAMES_LEAST_SQUARES / FDR_TV_FRAMES_POISSON */
+    int iterations;   /* >= 0 */
+    int anisotropic;  /* 0: isotropic TV, else anisotropic */
+    int nonneg;       /* != 0: the output is max(x, 0) */
+    int norm_area;    /* FDR_NORM_NONE / FDR_NORM_CROPPED / FDR_NORM_PADDED, over the output window */
+    int out_rows;     /* rows .. M */
+    int out_cols;     /* cols .. N */
+    void* stream;     /* _dev form: the hipStream_t of the call (NULL = the null stream); the host form ignores it */
+} fdr_tv_frames_params;
+int fdr_tv_deconv_frames_f32(fdr_plan* plan, const float* imgs_host, size_t img_pitch, int count, int rows, int cols, int stride,
+                             const float* weights_host, size_t weight_pitch, int wstride, float* out_host, int out_stride,
+                             const fdr_tv_frames_params* params);
+int fdr_tv_deconv_frames_f32_dev(fdr_plan* plan, const float* d_imgs, size_t img_pitch, int count, int rows, int cols, int stride,
+                                 const float* d_weights, size_t weight_pitch, int wstride, float* d_out, int out_stride,
+                                 const fdr_tv_frames_params* params);
 
 /* -- sectioned restoration (Trussell & Hunt 1978; Nagy & O'Leary 1998): a picture of any size, larger than a
  *    plan can be, is cut into overlapping tiles, every tile is restored as a crop of a larger scene by the free-boundary iteration

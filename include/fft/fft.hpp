@@ -374,14 +374,15 @@ inline void richardsonLucyTV_RGB(std::vector<Mat>& channels, const Mat& psf, int
                                  bool free_boundary = false, const Mat& weights = Mat(), bool coupled = false) {
     richardsonLucyTV_RGB(channels, psf, iterations, lambda, eps, free_boundary, weights, defaults(), FDR_RL_SIGMA, coupled);
 }
-// Multi-frame Richardson-Lucy (fdr_richardson_lucy_frames_f32, include/fdr.h): frames[k] holds the channels of exposure k of ONE
-// scene, psfs[k] its PSF (CV_32F; top-left in the plan as for richardsonLucyFree_RGB; sums are not normalised: a PSF's sum is its
-// frame's relative exposure, a registration shift goes into the PSF).  Every channel of frames[0] is replaced by the joint
-// free-boundary estimate from that channel of all K <= FDR_MAX_FRAMES exposures: one cached FDR_MODE_FAST plan with room for the
-// largest PSF's reach, the frame tables set ONCE, then one call per channel on launch groups of K frames, normalised by o.norm_area.
-// `weights` (CV_32F, the picture's size; empty = all ones) serves every frame; lambda > 0 adds the TV prior of richardsonLucyTV_RGB.
-inline void richardsonLucyFrames_RGB(std::vector<std::vector<Mat>>& frames, const std::vector<Mat>& psfs, int iterations, float lambda,
-                                     float eps, const Mat& weights, const Options& o, float sigma = FDR_RL_SIGMA) {
+// What the two multi-frame drivers below share.  frames[k] holds the channels of exposure k of ONE scene, psfs[k] its PSF (CV_32F;
+// top-left in the plan as for richardsonLucyFree_RGB; sums are not normalised: a PSF's sum is its frame's relative exposure, a
+// registration shift goes into the PSF).  One cached FDR_MODE_FAST plan with room for the largest PSF's reach, the frame tables set
+// ONCE, then restore(plan, in, px, weights or null, out) once per channel -- `in` that channel of all K <= FDR_MAX_FRAMES exposures,
+// dense, px floats apart -- on launch groups of K frames; every channel of frames[0] is replaced by the joint estimate.  `weights`
+// (CV_32F, the picture's size; empty = all ones) serves every frame.
+template <class Restore>
+inline void frames_each_channel(const char* who, std::vector<std::vector<Mat>>& frames, const std::vector<Mat>& psfs, const Mat& weights,
+                                const Options& o, const Restore& restore) {
     const int K = (int)frames.size();
     if (K == 0 || frames[0].empty()) return;
     const int rows = frames[0][0].rows, cols = frames[0][0].cols;
@@ -394,7 +395,7 @@ inline void richardsonLucyFrames_RGB(std::vector<std::vector<Mat>>& frames, cons
         if (ok) { pr = std::max(pr, psfs[k].rows); pc = std::max(pc, psfs[k].cols); }
     }
     if (!ok) {
-        std::cerr << "richardsonLucyFrames_RGB: 1 .. 8 frames of the same CV_32F channels and size, one CV_32F PSF each, CV_32F weights of the picture's size\n";
+        std::cerr << who << ": 1 .. 8 frames of the same CV_32F channels and size, one CV_32F PSF each, CV_32F weights of the picture's size\n";
         exit(1);
     }
     bool created = false;
@@ -407,21 +408,48 @@ inline void richardsonLucyFrames_RGB(std::vector<std::vector<Mat>>& frames, cons
         for (int r = 0; r < psfs[k].rows; ++r) std::copy(psfs[k].ptr<float>(r), psfs[k].ptr<float>(r) + psfs[k].cols, tabs.begin() + k * ppx + (size_t)r * pc);
     FDR_CHECK(fdr_set_frame_psfs(plan, tabs.data(), ppx, K, pr, pc, pc));
     Mat w = weights.empty() || weights.isContinuous() ? weights : weights.clone();
-    const fdr_rl_frames_params prm = {iterations, sigma, o.norm_area, rows, cols, lambda, eps};
     FDR_CHECK(fdr_plan_set_batching(plan, 1, K));
     for (size_t c = 0; c < nch; ++c) {
         for (int k = 0; k < K; ++k)
             for (int r = 0; r < rows; ++r) std::copy(frames[k][c].ptr<float>(r), frames[k][c].ptr<float>(r) + cols, in.begin() + k * px + (size_t)r * cols);
         Mat out(rows, cols, CV_32F);
-        FDR_CHECK(fdr_richardson_lucy_frames_f32(plan, in.data(), px, K, rows, cols, cols, w.empty() ? nullptr : w.ptr<float>(0), 0, cols,
-                                                 out.ptr<float>(0), cols, &prm));
+        FDR_CHECK(restore(plan, in.data(), px, w.empty() ? nullptr : w.ptr<float>(0), out.ptr<float>(0)));
         frames[0][c] = out;
     }
     FDR_CHECK(fdr_plan_set_batching(plan, 1, 1));  // the cached plan goes back as it came
 }
+// Multi-frame Richardson-Lucy (fdr_richardson_lucy_frames_f32, include/fdr.h) of the channels of K exposures (frames_each_channel
+// above): the joint free-boundary estimate, normalised by o.norm_area; lambda > 0 adds the TV prior of richardsonLucyTV_RGB.
+inline void richardsonLucyFrames_RGB(std::vector<std::vector<Mat>>& frames, const std::vector<Mat>& psfs, int iterations, float lambda,
+                                     float eps, const Mat& weights, const Options& o, float sigma = FDR_RL_SIGMA) {
+    if (frames.empty() || frames[0].empty()) return;
+    const int K = (int)frames.size(), rows = frames[0][0].rows, cols = frames[0][0].cols;
+    const fdr_rl_frames_params prm = {iterations, sigma, o.norm_area, rows, cols, lambda, eps};
+    frames_each_channel("richardsonLucyFrames_RGB", frames, psfs, weights, o, [&](fdr_plan* plan, const float* in, size_t px, const float* w, float* out) {
+        return fdr_richardson_lucy_frames_f32(plan, in, px, K, rows, cols, cols, w, 0, cols, out, cols, &prm);
+    });
+}
 inline void richardsonLucyFrames_RGB(std::vector<std::vector<Mat>>& frames, const std::vector<Mat>& psfs, int iterations, float lambda = 0.f,
                                      float eps = 0.f, const Mat& weights = Mat()) {
     richardsonLucyFrames_RGB(frames, psfs, iterations, lambda, eps, weights, defaults());
+}
+// Multi-frame TV deconvolution (fdr_tv_deconv_frames_f32, include/fdr.h) of the channels of K exposures (frames_each_channel above):
+// min mu sum_k Phi_k(blur_k(x)) + TV(x) by `iterations` ADMM steps, Phi_k least squares or, with poisson, the Poisson likelihood
+// with the known background; normalised by o.norm_area.
+inline void tvDeblurFrames_RGB(std::vector<std::vector<Mat>>& frames, const std::vector<Mat>& psfs, float mu, int iterations, bool poisson,
+                               float background, const Mat& weights, const Options& o, float rho = 2.f, float nu = 0.f, bool anisotropic = false,
+                               bool nonneg = false) {
+    if (frames.empty() || frames[0].empty()) return;
+    const int K = (int)frames.size(), rows = frames[0][0].rows, cols = frames[0][0].cols;
+    const fdr_tv_frames_params prm = {mu, rho, nu, background, poisson ? FDR_TV_FRAMES_POISSON : FDR_TV_FRAMES_LEAST_SQUARES, iterations,
+                                      anisotropic ? 1 : 0, nonneg ? 1 : 0, o.norm_area, rows, cols, nullptr};
+    frames_each_channel("tvDeblurFrames_RGB", frames, psfs, weights, o, [&](fdr_plan* plan, const float* in, size_t px, const float* w, float* out) {
+        return fdr_tv_deconv_frames_f32(plan, in, px, K, rows, cols, cols, w, 0, cols, out, cols, &prm);
+    });
+}
+inline void tvDeblurFrames_RGB(std::vector<std::vector<Mat>>& frames, const std::vector<Mat>& psfs, float mu, int iterations, bool poisson = false,
+                               float background = 0.f, const Mat& weights = Mat()) {
+    tvDeblurFrames_RGB(frames, psfs, mu, iterations, poisson, background, weights, defaults());
 }
 // What richardsonLucyBlind_RGB takes beside the picture and the start PSF: the form, the steps the PSF is held for, and the weights and
 // coverage threshold of the free form.

@@ -194,6 +194,17 @@ class RlFramesParams(ctypes.Structure):
                 ("out_cols", ctypes.c_int), ("tv_lambda", ctypes.c_float), ("tv_eps", ctypes.c_float)]
 
 
+TV_FRAMES_LEAST_SQUARES = 0  # FDR_TV_FRAMES_LEAST_SQUARES
+TV_FRAMES_POISSON = 1        # FDR_TV_FRAMES_POISSON
+
+
+class TvFramesParams(ctypes.Structure):
+    """fdr_tv_frames_params of include/fdr.h (the stream of the _dev form travels in the struct)"""
+    _fields_ = [("mu", ctypes.c_float), ("rho", ctypes.c_float), ("nu", ctypes.c_float), ("background", ctypes.c_float),
+                ("data_term", ctypes.c_int), ("iterations", ctypes.c_int), ("anisotropic", ctypes.c_int), ("nonneg", ctypes.c_int),
+                ("norm_area", ctypes.c_int), ("out_rows", ctypes.c_int), ("out_cols", ctypes.c_int), ("stream", ctypes.c_void_p)]
+
+
 class RlTvBatchParams(ctypes.Structure):
     """fdr_rl_tv_batch_params of include/fdr.h"""
     _fields_ = RlTvParams._fields_ + [("couple", ctypes.c_int)]
@@ -378,6 +389,8 @@ def _signatures():
         "fdr_blur_frames_f32_dev": (ci, [vp, vp, sz, ci, ci, ci, vp, sz, ci, ci, ci, vp]),
         "fdr_richardson_lucy_frames_f32": (ci, [vp, vp, sz, ci, ci, ci, ci, vp, sz, ci, vp, ci, P(RlFramesParams)]),
         "fdr_richardson_lucy_frames_f32_dev": (ci, [vp, vp, sz, ci, ci, ci, ci, vp, sz, ci, vp, ci, P(RlFramesParams), vp]),
+        "fdr_tv_deconv_frames_f32": (ci, [vp, vp, sz, ci, ci, ci, ci, vp, sz, ci, vp, ci, P(TvFramesParams)]),
+        "fdr_tv_deconv_frames_f32_dev": (ci, [vp, vp, sz, ci, ci, ci, ci, vp, sz, ci, vp, ci, P(TvFramesParams)]),
         "fdr_blur_batch_f32_dev": (ci, [vp, vp, sz, ci, ci, ci, ci, vp, sz, ci, ci, vp]),
         "fdr_richardson_lucy_batch_f32": (ci, [vp, vp, sz, ci, ci, ci, ci, vp, ci, vp, sz, ci, P(RlBatchParams)]),
         "fdr_richardson_lucy_batch_f32_dev": (ci, [vp, vp, sz, ci, ci, ci, ci, vp, ci, vp, sz, ci, P(RlBatchParams), vp]),
@@ -856,6 +869,44 @@ class Plan:
         _check(lib.fdr_richardson_lucy_frames_f32_dev(self._h, ctypes.c_void_p(int(d_imgs)), int(img_pitch), int(count), rows, cols, stride,
                                                       ctypes.c_void_p(int(d_weights)) if d_weights else None, int(weight_pitch), int(wstride),
                                                       ctypes.c_void_p(int(d_out)), out_stride, ctypes.byref(prm), _stream(stream)))
+
+    # multi-frame TV deconvolution (include/fdr.h): the frames of set_frame_psfs under one TV prior
+    def tv_deconv_frames(self, frames, mu, iterations, weights=None, data_term=TV_FRAMES_LEAST_SQUARES, background=0.0, rho=2.0, nu=0.0,
+                         anisotropic=False, nonneg=False, norm_area=NORM_NONE, full_plane=False):
+        """`iterations` ADMM steps of  min mu sum_k Phi_k(blur_k(x)) + TV(x)  on the K frames (host arrays of one shape, K =
+        frame_count()); Phi_k least squares or (TV_FRAMES_POISSON, with the known background) the Poisson likelihood.  weights: None,
+        one plane for all frames, or K planes (one per frame).  Returns the window, or with full_plane the whole M x N estimate."""
+        frames = np.ascontiguousarray(np.stack([np.asarray(f, dtype=np.float32) for f in frames]), dtype=np.float32)
+        k, rows, cols = frames.shape
+        w, wpitch = None, 0
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float32)
+            if w.shape == (rows, cols):
+                wpitch = 0
+            elif w.shape == (k, rows, cols):
+                wpitch = rows * cols
+            else:
+                raise ValueError("weights must have the shape of one frame or of all frames")
+        orows, ocols = (self.M, self.N) if full_plane else (rows, cols)
+        out = np.empty((orows, ocols), dtype=np.float32)
+        prm = TvFramesParams(float(mu), float(rho), float(nu), float(background), int(data_term), int(iterations), int(bool(anisotropic)),
+                             int(bool(nonneg)), int(norm_area), orows, ocols, None)
+        _check(lib.fdr_tv_deconv_frames_f32(self._h, _ptr(frames), rows * cols, k, rows, cols, cols, _ptr(w) if w is not None else None,
+                                            wpitch, cols, _ptr(out), ocols, ctypes.byref(prm)))
+        return out
+
+    def tv_deconv_frames_dev(self, d_imgs, img_pitch, count, rows, cols, stride, d_out, out_stride, mu, iterations, d_weights=None,
+                             weight_pitch=0, wstride=0, data_term=TV_FRAMES_LEAST_SQUARES, background=0.0, rho=2.0, nu=0.0, anisotropic=False,
+                             nonneg=False, norm_area=NORM_NONE, out_rows=None, out_cols=None, stream=None):
+        """the same on device pointers: frame k at d_imgs + k img_pitch, weights None, one plane (weight_pitch 0) or one per frame;
+        out_rows x out_cols (default rows x cols, up to M x N) is the output window.  Asynchronous on `stream`, which travels in the
+        parameter struct."""
+        prm = TvFramesParams(float(mu), float(rho), float(nu), float(background), int(data_term), int(iterations), int(bool(anisotropic)),
+                             int(bool(nonneg)), int(norm_area), int(rows if out_rows is None else out_rows),
+                             int(cols if out_cols is None else out_cols), int(stream) if stream else None)
+        _check(lib.fdr_tv_deconv_frames_f32_dev(self._h, ctypes.c_void_p(int(d_imgs)), int(img_pitch), int(count), rows, cols, stride,
+                                                ctypes.c_void_p(int(d_weights)) if d_weights else None, int(weight_pitch), int(wstride),
+                                                ctypes.c_void_p(int(d_out)), out_stride, ctypes.byref(prm)))
 
     # Richardson-Lucy with a total-variation prior, both forms (include/fdr.h); uses the operator PSF
     def richardson_lucy_tv(self, img, iterations, lam, eps=0.0, free_boundary=False, weights=None, cov_sigma=RL_SIGMA, norm_area=NORM_NONE,
@@ -1725,6 +1776,38 @@ def richardsonLucyFrames_RGB(frames, psfs, iterations, weights=None, tv_lambda=0
         p.set_frame_psfs(psfs)
         p.set_batching(1, min(len(frames), 8))
         return [p.richardson_lucy_frames([f[ch] for f in frames], iterations, weights, tv_lambda, tv_eps, sigma, norm_area)
+                for ch in range(len(frames[0]))]
+
+
+def tvDeblurFrames_myfft(frames, psfs, mu, iterations, weights=None, data_term=TV_FRAMES_LEAST_SQUARES, background=0.0, rho=2.0, nu=0.0,
+                         anisotropic=False, nonneg=False, device=0, norm_area=NORM_NONE, full_plane=False):
+    """Joint TV deconvolution of K (1 .. MAX_FRAMES) exposures of one scene, frame k blurred by psfs[k] (top-left in the plan; sums
+    not normalised: a PSF's sum is its frame's relative exposure): the plan of richardsonLucyFrames_myfft, the frame tables,
+    `iterations` ADMM steps of  min mu sum_k Phi_k(blur_k(x)) + TV(x),  the window back.  weights: None, one plane, or one per frame."""
+    frames = [np.asarray(f, dtype=np.float32) for f in frames]
+    psfs = _frame_psfs(psfs)
+    M, N = _frames_plan_size(frames[0].shape[0], frames[0].shape[1], psfs)
+    with Plan(M, N, MODE_FAST, device) as p:
+        p.set_frame_psfs(psfs)
+        p.set_batching(1, min(len(frames), 8))
+        return p.tv_deconv_frames(frames, mu, iterations, weights, data_term, background, rho, nu, anisotropic, nonneg, norm_area, full_plane)
+
+
+def tvDeblurFrames_RGB(frames, psfs, mu, iterations, weights=None, data_term=TV_FRAMES_LEAST_SQUARES, background=0.0, rho=2.0, nu=0.0,
+                       anisotropic=False, nonneg=False, device=0, norm_area=NORM_NONE):
+    """fft_gpu::tvDeblurFrames_RGB: frames[k] is the list of channel planes of exposure k (every exposure the same channels and
+    size).  Returns the list of restored channels: the frame tables are set once, then one joint call per channel (the bits of
+    tvDeblurFrames_myfft on that channel)."""
+    if not frames or not frames[0]:
+        return []
+    psfs = _frame_psfs(psfs)
+    r, c = np.asarray(frames[0][0]).shape
+    M, N = _frames_plan_size(r, c, psfs)
+    with Plan(M, N, MODE_FAST, device) as p:
+        p.set_frame_psfs(psfs)
+        p.set_batching(1, min(len(frames), 8))
+        return [p.tv_deconv_frames([f[ch] for f in frames], mu, iterations, weights, data_term, background, rho, nu, anisotropic, nonneg,
+                                   norm_area)
                 for ch in range(len(frames[0]))]
 
 

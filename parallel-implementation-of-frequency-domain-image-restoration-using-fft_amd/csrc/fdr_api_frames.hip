@@ -17,13 +17,10 @@ const char* const kPassFrStart = "RLM start: fold, wgt = 1/alpha, u";
 const char* const kPassFrColsH = "B' op cols: FFT*H_k*IFFT (frame)";
 const char* const kPassFrColsConj = "B' op cols: FFT*conj(H_k)*IFFT (frame)";
 const char* const kPassFrSum = "S frames: sum of spectra";
-const char* const kPassFrBlur = "C op rows: IFFT+crop (frames)";
 const char* const kPassFrRatio = "C op rows: IFFT+RL ratio (frames)";
 const char* const kPassFrUpdate = "C op rows: IFFT+RL update (frames)";
 
-const float2* frame_table(const fdr_plan* p, int k, bool adjoint) { return p->fr_tables + (2 * (size_t)k + (adjoint ? 1 : 0)) * p->ws_elems; }
 size_t frames_part_set(const fdr_plan* p) { return 2 * (size_t)rlfree_partials(p->M, p->N) + 2; }
-size_t window_span(int rows, int cols, int stride) { return (size_t)(rows - 1) * stride + cols; }
 
 // The workspace for `count` frames.  The new block is had before the old one is let go: when it cannot be had the sticky HIP error
 // is cleared and the plan and the workspace it had stay as they were.
@@ -49,6 +46,14 @@ int ensure_frames_workspace(fdr_plan* p, const char* fn, int count) {
     return FDR_OK;
 }
 
+}  // namespace
+
+namespace fdr {
+
+const char* const kPassFrBlur = "C op rows: IFFT+crop (frames)";
+
+const float2* frame_table(const fdr_plan* p, int k, bool adjoint) { return p->fr_tables + (2 * (size_t)k + (adjoint ? 1 : 0)) * p->ws_elems; }
+
 // the frames i0 .. i0 + n - 1 on the slots ws[0 .. n): pass B' of each on its own table, then their spectra into the accumulator
 // (`first`: stored, else added to what it holds)
 int frames_cols(fdr_plan* p, fdr_plan::Slot* const* ws, int n, int i0, bool adjoint, hipStream_t s) {
@@ -57,21 +62,25 @@ int frames_cols(fdr_plan* p, fdr_plan::Slot* const* ws, int n, int i0, bool adjo
         rc = op_cols_table_n(p, &ws[k], 1, frame_table(p, i0 + k, adjoint), adjoint ? kPassFrColsConj : kPassFrColsH, s);
     return rc;
 }
-int frames_sum(fdr_plan* p, fdr_plan::Slot* const* ws, int n, bool first, hipStream_t s) {
+int frames_sum(fdr_plan* p, float2* acc, fdr_plan::Slot* const* ws, int n, bool first, hipStream_t s) {
     ScopedPass t(p, s, kPassFrSum);
     FrameSrcs srcs{};
     for (int k = 0; k < n; ++k) srcs.p[k] = reinterpret_cast<const float*>(ws[k]->work);
-    FDR_HIP(launch_frames_sum(reinterpret_cast<float*>(p->fr_acc), srcs, n, 2 * p->ws_elems, !first, s));
+    FDR_HIP(launch_frames_sum(reinterpret_cast<float*>(acc), srcs, n, 2 * p->ws_elems, !first, s));
     return FDR_OK;
 }
-// pass C of the accumulator: a Slot value whose spectrum is fr_acc
-int frames_rows_inv(fdr_plan* p, RowOut kind, const char* name, const float* src, int src_stride, const float* src2, float* out, int out_stride,
-                    int rows, int cols, hipStream_t s) {
-    fdr_plan::Slot acc = p->slots[0];
-    acc.work = p->fr_acc;
-    fdr_plan::Slot* w = &acc;
+// pass C of the accumulator: a Slot value whose spectrum is `acc`
+int frames_rows_inv(fdr_plan* p, float2* acc, RowOut kind, const char* name, const float* src, int src_stride, const float* src2, float* out,
+                    int out_stride, int rows, int cols, hipStream_t s) {
+    fdr_plan::Slot a = p->slots[0];
+    a.work = acc;
+    fdr_plan::Slot* w = &a;
     return op_rows_inv_n(p, &w, 1, kind, name, &src, src_stride, src2, &out, out_stride, rows, cols, s);
 }
+
+}  // namespace fdr
+
+namespace {
 
 // sum_k blur_k^T(y_k) of `count` windows (rows x cols, row stride `stride`, frame k's at ys + k pitch) -> the window out_rows x
 // out_cols at d_out.  `prepare(k, slot)`, when set, produces frame k's window dense in the slot's raw plane first (the setup of the
@@ -91,9 +100,9 @@ int frames_adjoint(fdr_plan* p, const float* ys, size_t pitch, int count, int ro
         }
         if (rc == FDR_OK) rc = op_rows_fwd_n(p, ws, n, xs, rows, cols, prepare ? cols : stride, s);
         if (rc == FDR_OK) rc = frames_cols(p, ws, n, i0, true, s);
-        if (rc == FDR_OK) rc = frames_sum(p, ws, n, i0 == 0, s);
+        if (rc == FDR_OK) rc = frames_sum(p, p->fr_acc, ws, n, i0 == 0, s);
     }
-    if (rc == FDR_OK) rc = frames_rows_inv(p, ROW_OUT_BLUR, kPassFrBlur, nullptr, 0, nullptr, d_out, out_stride, out_rows, out_cols, s);
+    if (rc == FDR_OK) rc = frames_rows_inv(p, p->fr_acc, ROW_OUT_BLUR, kPassFrBlur, nullptr, 0, nullptr, d_out, out_stride, out_rows, out_cols, s);
     return rc;
 }
 
@@ -175,10 +184,10 @@ int frames_rl_dev(fdr_plan* p, const char* fn, const FramesArgs& a, const fdr_rl
                 rc = op_rows_inv_n(p, ws, n, ROW_OUT_RL_RATIO, kPassFrRatio, dws, cols, nullptr, r, cols, rows, cols, s);
             if (rc == FDR_OK) rc = op_rows_fwd_n(p, ws, n, r, rows, cols, cols, s);               // sum_k fullblur_k^T(pad(r_k)) ...
             if (rc == FDR_OK) rc = frames_cols(p, ws, n, i0, true, s);
-            if (rc == FDR_OK) rc = frames_sum(p, ws, n, i0 == 0, s);
+            if (rc == FDR_OK) rc = frames_sum(p, p->fr_acc, ws, n, i0 == 0, s);
         }
         if (rc == FDR_OK)                                                                        // ... u = max(u wgt g, 0)
-            rc = frames_rows_inv(p, ROW_OUT_RL_UPDATE_W, kPassFrUpdate, p->fr_u, N, wgt, p->fr_u, N, M, N, s);
+            rc = frames_rows_inv(p, p->fr_acc, ROW_OUT_RL_UPDATE_W, kPassFrUpdate, p->fr_u, N, wgt, p->fr_u, N, M, N, s);
     }
     if (rc != FDR_OK) return rc;
     return rlfree_finish(p, fn, p->fr_u, a.out, a.out_stride, free_params(prm), s);
@@ -196,6 +205,7 @@ int set_frame_psfs_impl(fdr_plan* p, const char* fn, const float* d_psfs, size_t
         p->fr_cap = count;
     }
     p->fr_count = 0;  // (a HIP error below leaves no half-built set behind)
+    ++p->fr_gen;      // (the solve table of fdr_tv_deconv_frames_f32*, if tv_T holds it, is of the old set)
     for (int k = 0; k < count; ++k) {
         float2* h = p->fr_tables + 2 * (size_t)k * p->ws_elems;
         const int rc = build_operator_tables(p, d_psfs + (size_t)k * pitch, prows, pcols, pstride, h, h + p->ws_elems, s);

@@ -495,7 +495,7 @@ int fdr_plan_destroy(fdr_plan* p) {
     (void)hipFree(p->rf_block); (void)hipFree(p->rt_block); (void)hipFree(p->ra_block); (void)hipFree(p->rg_block);
     (void)hipFree(p->bl_block); (void)hipFree(p->bl_w); (void)hipFree(p->tf_block); (void)hipFree(p->ta_block);
     (void)hipFree(p->rs_block); (void)hipFree(p->rs_trace); (void)hipFree(p->rs_planes);
-    (void)hipFree(p->fr_tables); (void)hipFree(p->fr_block);
+    (void)hipFree(p->fr_tables); (void)hipFree(p->fr_block); (void)hipFree(p->tm_block);
     delete p;
     return FDR_OK;
 }

@@ -50,14 +50,14 @@ int ensure_tv_workspace(fdr_plan* p, const char* fn, int group) {
     p->tv_b = planes + P;
     p->tv_w[0][0] = planes + 2 * P; p->tv_w[0][1] = planes + 3 * P;
     p->tv_w[1][0] = planes + 4 * P; p->tv_w[1][1] = planes + 5 * P;
-    p->tv_gen = 0;
+    p->tv_gen = 0; p->tv_fr_gen = 0;
     return FDR_OK;
 }
 
 // everything a TV call refuses, before any device work
-int tv_check(const fdr_plan* p, const char* fn, int rows, int cols, int stride, int out_stride, const fdr_tv_params* prm) {
+int tv_check(const fdr_plan* p, const char* fn, int rows, int cols, int stride, int out_stride, const fdr_tv_params* prm, PlanNeed need) {
     if (!prm) return null_arg(fn);
-    const int rc = check_window(p, fn, NEED_OPERATOR_PSF, rows, cols, stride, out_stride);
+    const int rc = check_window(p, fn, need, rows, cols, stride, out_stride);
     if (rc != FDR_OK) return rc;
     if (!std::isfinite(prm->mu) || !(prm->mu > 0.f)) return fail(FDR_ERR_ARG, std::string(fn) + ": mu must be finite and > 0");
     if (!std::isfinite(prm->rho) || !(prm->rho > 0.f)) return fail(FDR_ERR_ARG, std::string(fn) + ": rho must be finite and > 0");
@@ -76,12 +76,13 @@ int tv_prepare(fdr_plan* p, const char* fn, int group) {
 
 // ---- the stages the periodic driver below and the free-boundary driver (fdr_api_tvfree.hip) share, under the form's pass names ----
 
-// T for the data weight `weight` (mu, or nu in the free forms) and rho, unless the plan holds it for this operator PSF already
+// T for the data weight `weight` (mu, or nu in the free forms) and rho, unless the plan holds it for this operator PSF already (a
+// table of the frame set, which fdr_tv_deconv_frames_f32* left with tv_gen = 0, is never taken for it)
 int tv_solve_table(fdr_plan* p, const TvPassNames& names, float weight, float rho, hipStream_t s) {
-    if (p->tv_gen == p->op_gen && p->tv_mu == weight && p->tv_rho == rho) return FDR_OK;
+    if (p->tv_gen == p->op_gen && p->tv_fr_gen == 0 && p->tv_mu == weight && p->tv_rho == rho) return FDR_OK;
     ScopedPass t(p, s, names.table);
     FDR_HIP(launch_tv_table(p->op_h, p->tv_T, p->lap, p->M, p->N, p->pstride, p->npanels, (double)weight, (double)rho, s));
-    p->tv_gen = p->op_gen; p->tv_mu = weight; p->tv_rho = rho;
+    p->tv_gen = p->op_gen; p->tv_fr_gen = 0; p->tv_mu = weight; p->tv_rho = rho;
     return FDR_OK;
 }
 

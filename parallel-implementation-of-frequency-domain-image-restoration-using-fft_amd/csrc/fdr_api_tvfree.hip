@@ -13,10 +13,16 @@ using namespace fdr;
 namespace {
 
 // names are static strings compared by pointer in PassTimer::pass_id
-const char* const kPassTfInit = "TVF init: x = pad(d), w = q = 0";
-const char* const kPassTfData = "TVF data: s, q, r = 2s-e (window)";
 const char* const kPassTaNorm = "TVA norm+mu: res_e, res_c, S -> mu_k";
 const char* const kPassTaData = "TVA data: s, q, r = 2s-e (mu_k)";
+
+}  // namespace
+
+namespace fdr {
+
+// (shared with the multi-frame form of fdr_api_tvframes.hip, which runs these passes)
+const char* const kPassTfInit = "TVF init: x = pad(d), w = q = 0";
+const char* const kPassTfData = "TVF data: s, q, r = 2s-e (window)";
 const char* const kPassTpData = "TVP data: Poisson s, q, r = 2s-e (window)";
 const TvPassNames kTfPasses = {
     "TV table: 1/(nu|H|^2+rho L)/MN (free)",
@@ -28,17 +34,13 @@ const TvPassNames kTfPasses = {
     "E TVF minmax+normalize",
 };
 
-}  // namespace
-
-namespace fdr {
-
 // everything a free-boundary TV call refuses, before any device work: what the periodic call refuses, and nu, the weights' stride,
 // the output window and an output that overlaps the input or the weights (both are read in every iteration)
 int tvfree_check(const fdr_plan* p, const char* fn, const float* img, int rows, int cols, int stride, const float* weights, int wstride,
-                 const float* out, int out_stride, const fdr_tv_free_params* prm) {
+                 const float* out, int out_stride, const fdr_tv_free_params* prm, PlanNeed need) {
     if (!prm) return null_arg(fn);
     const fdr_tv_params periodic = {prm->mu, prm->rho, prm->iterations, prm->anisotropic, prm->nonneg, prm->norm_area};
-    const int rc = tv_check(p, fn, rows, cols, stride, out_stride, &periodic);
+    const int rc = tv_check(p, fn, rows, cols, stride, out_stride, &periodic, need);
     if (rc != FDR_OK) return rc;
     if (!std::isfinite(prm->nu) || prm->nu < 0.f) return fail(FDR_ERR_ARG, std::string(fn) + ": nu must be finite and >= 0");
     if (weights && wstride < cols) return fail(FDR_ERR_ARG, std::string(fn) + ": the weights' stride must be >= cols");

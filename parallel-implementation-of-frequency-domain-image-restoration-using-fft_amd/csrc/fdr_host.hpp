@@ -202,8 +202,9 @@ struct fdr_plan {
     float *rt_f = nullptr, *rt_u = nullptr;
     // multi-frame Richardson-Lucy (fdr_set_frame_psfs*, fdr_blur_frames_f32_dev, fdr_richardson_lucy_frames_f32*).  fr_tables: one
     // allocation of 2 fr_cap ws_elems float2, made or regrown by the setter alone: frame k's H_k / (M N) at fr_tables + 2 k ws_elems,
-    // its conj(H_k) / (M N) ws_elems behind (layout of `filt`); fr_count = the frames of the last set.  Nothing else reads or writes
-    // them, and they touch neither op_h / op_c, filt, op_gen nor the TV table.  fr_block: the workspace of the calls, made on first
+    // its conj(H_k) / (M N) ws_elems behind (layout of `filt`); fr_count = the frames of the last set.  Only the multi-frame calls
+    // read them (these and fdr_tv_deconv_frames_f32*), nothing else writes them, and they touch neither op_h / op_c, filt nor
+    // op_gen (a new set outdates a TV table built from the old one: fr_gen below).  fr_block: the workspace of the calls, made on first
     // use and grown for a larger count (fr_ws_count = the frames it holds): the accumulator spectrum fr_acc (ws_elems), the planes
     // fr_u, fr_wgt (M x N) and fr_ws_count planes dw (frame k's at fr_dw + k M N), then per frame the 2 rlfree_partials(M, N) + 2
     // doubles of its sums (frames_part) and the folded pair fr_sums.  fdr_blur_frames_f32_dev needs fr_acc only and makes the block
@@ -215,6 +216,17 @@ struct fdr_plan {
     float2* fr_acc = nullptr;
     float *fr_u = nullptr, *fr_wgt = nullptr, *fr_dw = nullptr;
     double *fr_part = nullptr, *fr_sums = nullptr;
+    // multi-frame TV deconvolution (fdr_tv_deconv_frames_f32*): beside the TV workspace of one image, which it shares (x, b, the duals
+    // and T), one allocation made on first use and grown for a larger count (tm_count = the frames it holds): the accumulator spectrum
+    // tm_acc (ws_elems), then the tm_count planes q (frame k's at tm_q + k M N, so that one memset clears them), then the tm_count
+    // planes c / r (frame k's at tm_c + k M N).  fr_gen counts the fdr_set_frame_psfs* calls; tv_fr_gen says whose table tv_T holds:
+    // 0 the operator's (then tv_gen, tv_mu and tv_rho describe it), else the frame tables' of generation tv_fr_gen, built for nu =
+    // tv_mu and tv_rho (tv_gen is 0 then, so the operator's calls build theirs again).
+    unsigned fr_gen = 0, tv_fr_gen = 0;
+    void* tm_block = nullptr;
+    int tm_count = 0;
+    float2* tm_acc = nullptr;
+    float *tm_q = nullptr, *tm_c = nullptr;
     // stopping Richardson-Lucy from the data (fdr_richardson_lucy_auto_f32*): made by the first such call, kept until fdr_plan_destroy
     // -- rs_block holds the (res, kl) partials of the ratio pass (one double2 per workgroup of the plan's inverse row grid) and the
     // partials of the noise estimate; rs_trace the internal trace (2 rs_trace_cap doubles; it grows only when a call with a rule and
@@ -557,7 +569,8 @@ constexpr int kRegMaxCurve = 4096;
 static_assert(kRegMaxCurve % kRegCandidates == 0, "the last sweep reads kRegCandidates pairs");
 // ---- total-variation deconvolution (fdr_api_tv.hip), shared with its batch (fdr_api_tvbatch.hip) ----
 // everything a TV call refuses for one image, before any device work
-int tv_check(const fdr_plan* p, const char* fn, int rows, int cols, int stride, int out_stride, const fdr_tv_params* prm);
+int tv_check(const fdr_plan* p, const char* fn, int rows, int cols, int stride, int out_stride, const fdr_tv_params* prm,
+             PlanNeed need = NEED_OPERATOR_PSF);
 // the TV workspace for `group` images (T and 6 group planes) and the Laplacian table, both synchronous and on first use only.  The
 // workspace grows on the first use with a larger group (T is then built again by the next call); FDR_ERR_ALLOC, sticky HIP error
 // cleared, leaves the plan and the workspace it had intact.
@@ -592,8 +605,14 @@ int ensure_tvfree_workspace(fdr_plan* p, const char* fn, int group = 1);
 // everything a free-boundary TV call refuses, before any device work; the workspaces of a call (the two planes first, then the
 // periodic call's for one image and the Laplacian table)
 int tvfree_check(const fdr_plan* p, const char* fn, const float* img, int rows, int cols, int stride, const float* weights, int wstride,
-                 const float* out, int out_stride, const fdr_tv_free_params* prm);
+                 const float* out, int out_stride, const fdr_tv_free_params* prm, PlanNeed need = NEED_OPERATOR_PSF);
 int tvfree_prepare(fdr_plan* p, const char* fn, int group = 1);
+// the pass names of the free-boundary forms (static strings: PassTimer compares them by pointer), for the multi-frame form, which
+// runs the same kernels: the shared stages, the start and the two data steps
+extern const TvPassNames kTfPasses;
+extern const char* const kPassTfInit;
+extern const char* const kPassTfData;
+extern const char* const kPassTpData;
 // The data step of a free-boundary iteration, the one thing its forms differ in.  LEAST_SQUARES (fdr_api_tvfree.hip): the term
 // mu / 2 m (s - d)^2 on prm.mu.  AUTO (fdr_api_tvauto.hip, fdr_api_tvfreebatch.hip): the same with every image's weight chosen in
 // every iteration (prm.mu is not used) from tau and, for every image of the group, the noise level of its discrepancy ball; the
@@ -640,6 +659,18 @@ int tvfree_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, i
 int crop_batch_check(const fdr_plan* p, const char* fn, const float* imgs, size_t img_pitch, int count, int rows, int cols, int stride,
                      const float* weights, int wstride, const float* out, size_t out_pitch, int out_stride, const fdr_tv_free_params& one,
                      int coupling);
+
+// ---- the frame passes of multi-frame Richardson-Lucy (fdr_api_frames.hip), shared with multi-frame TV (fdr_api_tvframes.hip) ----
+// frame k's table H_k / (M N), or conj(H_k) / (M N); the span of a window in floats
+const float2* frame_table(const fdr_plan* p, int k, bool adjoint);
+inline size_t window_span(int rows, int cols, int stride) { return (size_t)(rows - 1) * stride + cols; }
+// the frames i0 .. i0 + n - 1 on the slots ws[0 .. n): pass B' of each on its own table; then their spectra into the accumulator `acc`
+// (ws_elems, 16-byte aligned; `first`: stored, else added to what it holds); then pass C of the accumulator
+int frames_cols(fdr_plan* p, fdr_plan::Slot* const* ws, int n, int i0, bool adjoint, hipStream_t s);
+int frames_sum(fdr_plan* p, float2* acc, fdr_plan::Slot* const* ws, int n, bool first, hipStream_t s);
+int frames_rows_inv(fdr_plan* p, float2* acc, RowOut kind, const char* name, const float* src, int src_stride, const float* src2, float* out,
+                    int out_stride, int rows, int cols, hipStream_t s);
+extern const char* const kPassFrBlur;  // pass C with ROW_OUT_BLUR on frames
 
 // ---- the motion-blur estimate (fdr_api_motion.hip), shared with the defocus and the combined estimate (fdr_api_defocus.hip) ----
 // the search arguments with their defaults (0 selects one), after the plan and window checks; FDR_ERR_ARG for anything outside

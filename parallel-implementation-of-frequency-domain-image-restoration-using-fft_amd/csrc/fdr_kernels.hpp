@@ -210,6 +210,12 @@ hipError_t launch_rltv_factor_group(const float* u, size_t u_pitch, int count, i
 struct FrameSrcs { const float* p[kMaxGroup]; };
 hipError_t launch_frames_sum(float* dst, const FrameSrcs& srcs, int n, size_t n_floats, bool accumulate, hipStream_t s);
 hipError_t launch_frames_fold(const double* sums, size_t pitch, int n, double* out, hipStream_t s);
+// (fdr_tvframes.hip) multi-frame TV deconvolution: T = (1 / (M N)) / (nu sum_k |H_k|^2 + rho L) from the `count` (1 .. kMaxGroup)
+// frame tables H_k / (M N) (16-byte aligned, the layout of launch_tv_table's op_h), summed in double in ascending k and rounded
+// once; one table gives the bytes of launch_tv_table on it
+struct FrameTables { const float2* p[kMaxGroup]; };
+hipError_t launch_tv_frames_table(const FrameTables& tabs, int count, float2* T, const double* lap, int M, int N, size_t pstride, int npanels,
+                                  double nu, double rho, hipStream_t s);
 // (fdr_rlaccel.hip) accelerated Richardson-Lucy, on rows x cols windows with their own row strides.  direction: g = u1 - y over the
 // previous g; with `part` not null also sum(g_new g_old) and sum(g_old g_old) in double as rlaccel_partials(rows, cols)
 // per-workgroup partials each (part holds 2 n doubles); with a null `part` the old g is not read.  alpha: one workgroup folds the
@@ -252,6 +258,12 @@ hipError_t launch_psf_gaussian(int size, double sigma, float* d_out, hipStream_t
 // of x to `out`, clamped at 0 with nonneg.
 hipError_t launch_tv_table(const float2* op_h, float2* T, const double* lap, int M, int N, size_t pstride, int npanels, double mu, double rho,
                            hipStream_t s);
+// an entry of that table and of the frames' (fdr_tvframes.hip): (1 / (M N)) / (mu h2 + rho lap) in double, rounded once; a zero (or
+// negative) denominator gives 0, as the CLS filter does
+__device__ __forceinline__ float tv_quotient(double h2, double lap, double mu, double rho, double inv_mn) {
+    const double den = mu * h2 + rho * lap;
+    return den > 0.0 ? (float)(inv_mn / den) : 0.f;
+}
 hipError_t launch_tv_init(const float* d, int rows, int cols, int stride, float* x, float* wx, float* wy, int M, int N, hipStream_t s);
 hipError_t launch_tv_spatial(const float* x, const float* wx, const float* wy, const float* b, float* nwx, float* nwy, float* rhs, int M, int N,
                              float mu, float rho, int anisotropic, hipStream_t s);
@@ -278,6 +290,7 @@ struct TvWindowPlanes {
     float* q[kMaxGroup];
     const float* d[kMaxGroup];
 };
+struct TvWindowWeights { const float* w[kMaxGroup]; };  // a weights window per image (entries past nimg repeat image 0's)
 struct TvWindowLaunch {
     TvWindowPlanes pl;
     int dvec, wvec;
@@ -327,6 +340,13 @@ __device__ __forceinline__ void tvfree_data_pixel(const float mu, const float nu
 // mu m [(s + b) - d+ log(s + b)] + nu / 2 (s - e)^2, b = background >= 0, then q = e - s; c = s - q
 hipError_t launch_tvpoisson_data_n(int nimg, float* const* c, float* const* q, const float* const* d, int stride, const float* w, int wstride,
                                    int rows, int cols, int M, int N, float mu, float nu, float background, hipStream_t s);
+// both steps with a weights window per image, w[k] image k's (none null; one stride, any alignment each): the exposures of
+// fdr_tv_deconv_frames_f32*, whose masks differ.  Every image gets the bits of the launches above on its own window; one image makes
+// the single kernel's launch.
+hipError_t launch_tvfree_data_weights_n(int nimg, float* const* c, float* const* q, const float* const* d, int stride, const float* const* w,
+                                        int wstride, int rows, int cols, int M, int N, float mu, float nu, hipStream_t s);
+hipError_t launch_tvpoisson_data_weights_n(int nimg, float* const* c, float* const* q, const float* const* d, int stride, const float* const* w,
+                                           int wstride, int rows, int cols, int M, int N, float mu, float nu, float background, hipStream_t s);
 // The arithmetic of that step on one pixel, shared by every launch of it.  Every operation is one correctly rounded
 // float operation (no contraction), in this order:
 //     e  = c + q

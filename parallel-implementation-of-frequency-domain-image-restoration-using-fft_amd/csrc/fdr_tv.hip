@@ -15,13 +15,7 @@
 
 namespace fdr {
 
-// ---- the solve table ----
-// (1 / (M N)) / (mu h2 + rho lap) in double, rounded once; a zero (or negative) denominator gives 0, as the CLS filter does
-__device__ __forceinline__ float tv_quotient(double h2, double lap, double mu, double rho, double inv_mn) {
-    const double den = mu * h2 + rho * lap;
-    return den > 0.0 ? (float)(inv_mn / den) : 0.f;
-}
-
+// ---- the solve table (tv_quotient: fdr_kernels.hpp) ----
 // One thread per row m of a panel p: the four columns 4 p .. 4 p + 3 (v < N/2) of op_h (H / (M N), row m at m * 4) -> T at the
 // same place.  Column 0 of panel 0 is the packed DC / Nyquist column; its H slots (packed_column_operator_slot of fdr_rl.hip)
 // hold H0[k] for 0 < k < M/2, HN[M - k] for M/2 < k < M and two real values at 0 and M/2, so |H0|^2 and |HN|^2 of the bin a T

@@ -10,9 +10,9 @@
 // the weights are 0, the step is s = e, q = 0, r = c: nothing to compute and nothing to store, so the launch covers the window alone
 // and q, zero outside the window since the start, is never touched there; it moves 20 bytes per pixel, 24 with weights.  d and the
 // weights are read in place from the caller's strided windows.  The group form makes the step of up to kMaxGroup images in one
-// launch, blockIdx.z the image, with one weights window for all; the single kernel and the group kernel instantiate one device
-// function, and a pixel is computed by tvfree_data_pixel or tvpoisson_data_pixel (fdr_kernels.hpp), so an image has the same bits in
-// a group as alone.
+// launch, blockIdx.z the image, with one weights window for all, or (the frames of fdr_tv_deconv_frames_f32*, whose exposures differ
+// in their masks) with image z's own; the single kernel and the group kernels instantiate one device function, and a pixel is
+// computed by tvfree_data_pixel or tvpoisson_data_pixel (fdr_kernels.hpp), so an image has the same bits in a group as alone.
 #include "fdr_kernels.hpp"
 
 namespace fdr {
@@ -80,6 +80,16 @@ __global__ __launch_bounds__(256) void tv_data_group_kernel(const TvWindowPlanes
                             (dvec >> z) & 1, wvec);
 }
 
+// the group form with a weights window per image: image blockIdx.z reads its own, bit z of wvec says whether it takes 16-byte loads
+template <class Step>
+__global__ __launch_bounds__(256) void tv_data_group_weights_kernel(const TvWindowPlanes pl, const int stride, const TvWindowWeights wp,
+                                                                    const int wstride, const int rows, const int cols, const int N, const float nu,
+                                                                    const Step step, const int dvec, const int wvec) {
+    const int z = blockIdx.z;
+    tv_data_group4<true>(FDR_PICK_IMAGE(pl.c, z), FDR_PICK_IMAGE(pl.q, z), FDR_PICK_IMAGE(pl.d, z), stride, FDR_PICK_IMAGE(wp.w, z), wstride, rows, cols,
+                         N, nu, step, z, (dvec >> z) & 1, (wvec >> z) & 1);
+}
+
 bool tv_window_launch(int nimg, float* const* c, float* const* q, const float* const* d, int stride, const float* w, int wstride, int rows, int cols,
                       int M, int N, TvWindowLaunch* L) {
     if (nimg < 1 || nimg > kMaxGroup || !c || !q || !d) return false;
@@ -115,6 +125,27 @@ hipError_t launch_tv_data(int nimg, float* const* c, float* const* q, const floa
     return hipGetLastError();
 }
 
+// the same with a weights window per image, wk[k] image k's (none null): one image makes the single kernel's launch on its window
+template <class Step>
+hipError_t launch_tv_data_weights(int nimg, float* const* c, float* const* q, const float* const* d, int stride, const float* const* wk, int wstride,
+                                  int rows, int cols, int M, int N, float nu, const Step step, hipStream_t s) {
+    if (!wk || nimg < 1 || nimg > kMaxGroup) return hipErrorInvalidValue;
+    for (int k = 0; k < nimg; ++k)
+        if (!wk[k]) return hipErrorInvalidValue;
+    if (nimg == 1) return launch_tv_data(1, c, q, d, stride, wk[0], wstride, rows, cols, M, N, nu, step, s);
+    TvWindowLaunch L;
+    if (!tv_window_launch(nimg, c, q, d, stride, wk[0], wstride, rows, cols, M, N, &L)) return hipErrorInvalidValue;
+    TvWindowWeights wp;
+    int wvec = 0;
+    for (int k = 0; k < kMaxGroup; ++k) {
+        wp.w[k] = wk[k < nimg ? k : 0];
+        if (((uintptr_t)wp.w[k] & 15) == 0 && (wstride & 3) == 0) wvec |= 1 << k;
+    }
+    const dim3 block((unsigned)L.tx, (unsigned)L.ty), grid((unsigned)L.gx, (unsigned)((rows + L.ty - 1) / L.ty), (unsigned)nimg);
+    hipLaunchKernelGGL((tv_data_group_weights_kernel<Step>), grid, block, 0, s, L.pl, stride, wp, wstride, rows, cols, N, nu, step, L.dvec, wvec);
+    return hipGetLastError();
+}
+
 }  // namespace
 
 hipError_t launch_tvfree_data_n(int nimg, float* const* c, float* const* q, const float* const* d, int stride, const float* w, int wstride, int rows,
@@ -131,6 +162,16 @@ hipError_t launch_tvauto_data_n(int nimg, float* const* c, float* const* q, cons
 hipError_t launch_tvpoisson_data_n(int nimg, float* const* c, float* const* q, const float* const* d, int stride, const float* w, int wstride,
                                    int rows, int cols, int M, int N, float mu, float nu, float background, hipStream_t s) {
     return launch_tv_data(nimg, c, q, d, stride, w, wstride, rows, cols, M, N, nu, TvStepPoisson{mu, background}, s);
+}
+
+hipError_t launch_tvfree_data_weights_n(int nimg, float* const* c, float* const* q, const float* const* d, int stride, const float* const* w,
+                                        int wstride, int rows, int cols, int M, int N, float mu, float nu, hipStream_t s) {
+    return launch_tv_data_weights(nimg, c, q, d, stride, w, wstride, rows, cols, M, N, nu, TvStepLeastSquares{mu}, s);
+}
+
+hipError_t launch_tvpoisson_data_weights_n(int nimg, float* const* c, float* const* q, const float* const* d, int stride, const float* const* w,
+                                           int wstride, int rows, int cols, int M, int N, float mu, float nu, float background, hipStream_t s) {
+    return launch_tv_data_weights(nimg, c, q, d, stride, w, wstride, rows, cols, M, N, nu, TvStepPoisson{mu, background}, s);
 }
 
 }  // namespace fdr
