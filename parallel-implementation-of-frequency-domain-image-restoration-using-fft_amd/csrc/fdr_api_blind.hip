@@ -22,29 +22,10 @@ const char* const kPassBlPsf = "BL PSF: start / project / wgt";
 static_assert(FDR_BLIND_MAX_PSF == kBlindMaxPsf, "the PSF limit of the header is the one-workgroup kernels'");
 
 int ensure_blind_workspace(fdr_plan* p, const char* fn, bool free_form) {
-    if (!p->bl_block) {
-        char* blk = nullptr;
-        const size_t table = p->ws_elems * sizeof(float2), planes = 4 * (size_t)kBlindMaxPsf * sizeof(float);
-        if (hipMalloc((void**)&blk, table + planes + sizeof(int)) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(FDR_ERR_ALLOC, std::string(fn) + ": hipMalloc of the blind workspace failed");
-        }
-        p->bl_block = blk;
-        p->bl_table = reinterpret_cast<float2*>(blk);
-        p->bl_p = reinterpret_cast<float*>(blk + table);
-        p->bl_num = p->bl_p + kBlindMaxPsf;
-        p->bl_den = p->bl_num + kBlindMaxPsf;
-        p->bl_stage = p->bl_den + kBlindMaxPsf;
-        p->bl_status = reinterpret_cast<int*>(blk + table + planes);
-    }
-    if (free_form && !p->bl_w) {
-        if (hipMalloc((void**)&p->bl_w, (size_t)p->M * p->N * sizeof(float)) != hipSuccess) {
-            (void)hipGetLastError();
-            p->bl_w = nullptr;
-            return fail(FDR_ERR_ALLOC, std::string(fn) + ": hipMalloc of the blind workspace failed");
-        }
-    }
-    return FDR_OK;
+    int rc = ensure_workspace(p->blind.ws, fn, "blind workspace", 1, [p](auto& c, int) { layout(c, p->blind, p->ws_elems, (size_t)kBlindMaxPsf); });
+    if (rc == FDR_OK && free_form)
+        rc = ensure_workspace(p->blind.w_ws, fn, "blind workspace", 1, [p](auto& c, int) { layout(c, p->blind.w, (size_t)p->M * p->N, 16); });
+    return rc;
 }
 
 fdr_rlfree_params free_params(const fdr_blind_params& b) {
@@ -90,19 +71,19 @@ struct BlindStep {
         ScopedPass t(p, s, kPassBlTable);
         ColArgs ca = panel_col_args(p);
         ca.data = p->slots[0].work; ca.nvalid = (nrows + 3) & ~3;  // <= M (M is a multiple of 8 on this path)
-        FDR_HIP(launch_cols_panel_conj(p->logM, ca, p->bl_table, p->tw_col_f, s));
+        FDR_HIP(launch_cols_panel_conj(p->logM, ca, p->blind.table, p->tw_col_f, s));
         return FDR_OK;
     }
     // corr_(u_k) of the window rows x cols of x (dense) into the PSF plane dst
     int corr(const float* x, float* dst) const {
         int rc = op_rows_fwd(p, x, rows, cols, cols, s);
-        if (rc == FDR_OK) rc = op_cols_table(p, p->bl_table, kPassBlCorr, s);
+        if (rc == FDR_OK) rc = op_cols_table(p, p->blind.table, kPassBlCorr, s);
         if (rc == FDR_OK) rc = op_rows_inv(p, ROW_OUT_BLUR, kPassBlCrop, nullptr, 0, dst, pcols, prows, pcols, s);
         return rc;
     }
     int after_ratio() const {
-        int rc = corr(p->slots[0].raw, p->bl_num);
-        if (rc == FDR_OK && free_form) rc = corr(p->bl_w, p->bl_den);
+        int rc = corr(p->slots[0].raw, p->blind.num);
+        if (rc == FDR_OK && free_form) rc = corr(p->blind.w, p->blind.den);
         return rc;
     }
     // p_(k+1) and its operator tables; after the last step the PSF also to `out` (row stride ostride), before it (free form) the
@@ -110,15 +91,15 @@ struct BlindStep {
     int after_step(bool last, float* out, int ostride) const {
         {
             ScopedPass t(p, s, kPassBlPsf);
-            FDR_HIP(launch_blind_psf_project(p->bl_p, p->bl_num, free_form ? p->bl_den : nullptr, prows, pcols, p->bl_status, last ? out : nullptr,
+            FDR_HIP(launch_blind_psf_project(p->blind.p, p->blind.num, free_form ? p->blind.den : nullptr, prows, pcols, p->blind.status, last ? out : nullptr,
                                              ostride, s));
         }
-        int rc = set_operator_psf_impl(p, p->bl_p, prows, pcols, pcols, s);
+        int rc = set_operator_psf_impl(p, p->blind.p, prows, pcols, pcols, s);
         if (rc != FDR_OK || last || !free_form) return rc;
-        rc = blur_window_dev(p, p->bl_w, rows, cols, cols, p->rf_wgt, p->N, p->M, p->N, 1, s);
+        rc = blur_window_dev(p, p->blind.w, rows, cols, cols, p->rlfree.wgt, p->N, p->M, p->N, 1, s);
         if (rc != FDR_OK) return rc;
         ScopedPass t(p, s, kPassBlPsf);
-        FDR_HIP(launch_blind_wgt(p->rf_wgt, (size_t)p->M * p->N, sigma, s));
+        FDR_HIP(launch_blind_wgt(p->rlfree.wgt, (size_t)p->M * p->N, sigma, s));
         return FDR_OK;
     }
 };
@@ -131,16 +112,16 @@ int blind_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, in
     const BlindStep bs{p, rows, cols, prows, pcols, free_form, prm.cov_sigma, s};
     {
         ScopedPass t(p, s, kPassBlPsf);
-        FDR_HIP(launch_blind_psf_start(d_psf, prows, pcols, pstride, p->bl_p, p->bl_status, s));
+        FDR_HIP(launch_blind_psf_start(d_psf, prows, pcols, pstride, p->blind.p, p->blind.status, s));
     }
-    const int rc = set_operator_psf_impl(p, p->bl_p, prows, pcols, pcols, s);
+    const int rc = set_operator_psf_impl(p, p->blind.p, prows, pcols, pcols, s);
     if (rc != FDR_OK) return rc;
     RlHooks hooks;
     hooks.after_fwd = [&](int it) { return it < hold ? FDR_OK : bs.table(free_form ? p->M : rows); };
     hooks.after_ratio = [&](int it) { return it < hold ? FDR_OK : bs.after_ratio(); };
     hooks.after_step = [&](int it) { return it < hold ? FDR_OK : bs.after_step(it == n - 1, d_psf, pstride); };
     if (free_form)
-        return rlfree_batch_dev(p, fn, d_img, 0, 1, rows, cols, stride, d_w, wstride, d_out, 0, out_stride, free_params(prm), s, &hooks, p->bl_w);
+        return rlfree_batch_dev(p, fn, d_img, 0, 1, rows, cols, stride, d_w, wstride, d_out, 0, out_stride, free_params(prm), s, &hooks, p->blind.w);
     fdr_plan::Slot* w = &p->slots[0];
     return rl_group_dev(p, fn, &w, 1, &d_img, rows, cols, stride, &d_out, out_stride, n, prm.norm_area, s, &hooks);
 }
@@ -196,26 +177,26 @@ int fdr_richardson_lucy_blind_f32(fdr_plan* p, const float* img_host, int rows, 
     rc = ensure_form_workspaces(p, fn, free_form);
     if (rc != FDR_OK) return rc;
     const size_t pw = (size_t)pcols * sizeof(float);
-    FDR_HIP(hipMemcpy2D(p->bl_stage, pw, psf_host, (size_t)pstride * sizeof(float), pw, (size_t)prows, hipMemcpyHostToDevice));
+    FDR_HIP(hipMemcpy2D(p->blind.stage, pw, psf_host, (size_t)pstride * sizeof(float), pw, (size_t)prows, hipMemcpyHostToDevice));
     if (free_form && weights_host) rc = stage_weights(p, weights_host, rows, cols, wstride);
     if (rc != FDR_OK) return rc;
     const int orows = free_form ? prm.out_rows : rows, ocols = free_form ? prm.out_cols : cols;
     rc = host_image_call(p, fn, img_host, rows, cols, stride, out_host, orows, ocols, out_stride, [&](const float* d_in, float* d_out) {
-        return blind_dev_impl(p, fn, d_in, rows, cols, cols, free_form && weights_host ? p->rf_u : nullptr, cols, p->bl_stage, prows, pcols,
+        return blind_dev_impl(p, fn, d_in, rows, cols, cols, free_form && weights_host ? p->rlfree.u : nullptr, cols, p->blind.stage, prows, pcols,
                               pcols, d_out, ocols, prm, nullptr);
     });
     if (rc != FDR_OK) return rc;
-    FDR_HIP(hipMemcpy2D(psf_host, (size_t)pstride * sizeof(float), p->bl_stage, pw, pw, (size_t)prows, hipMemcpyDeviceToHost));
+    FDR_HIP(hipMemcpy2D(psf_host, (size_t)pstride * sizeof(float), p->blind.stage, pw, pw, (size_t)prows, hipMemcpyDeviceToHost));
     return FDR_OK;
 }
 
 int fdr_richardson_lucy_blind_status(fdr_plan* p, int* status) {
     const char* fn = "fdr_richardson_lucy_blind_status";
     if (!p || !status) return null_arg(fn);
-    if (!p->bl_block) return fail(FDR_ERR_STATE, std::string(fn) + ": no blind call has run on this plan");
+    if (!p->blind.ws.block) return fail(FDR_ERR_STATE, std::string(fn) + ": no blind call has run on this plan");
     FDR_HIP(hipSetDevice(p->device));
     FDR_HIP(hipDeviceSynchronize());
-    FDR_HIP(hipMemcpy(status, p->bl_status, sizeof(int), hipMemcpyDeviceToHost));
+    FDR_HIP(hipMemcpy(status, p->blind.status, sizeof(int), hipMemcpyDeviceToHost));
     return FDR_OK;
 }
 

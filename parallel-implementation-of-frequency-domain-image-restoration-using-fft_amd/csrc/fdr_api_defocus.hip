@@ -41,16 +41,12 @@ int defocus_args(const fdr_plan* p, const char* fn, int rows, int cols, int stri
 }
 
 int ensure_defocus_workspace(fdr_plan* p, const char* fn) {
-    if (p->df_block) return FDR_OK;
-    const size_t trig = 2 * (size_t)kDefocusMaxAngles * sizeof(double);
-    char* b = nullptr;
-    if (hipMalloc((void**)&b, trig + (size_t)kDefocusMaxDiameters * sizeof(float)) != hipSuccess)
-        return fail(FDR_ERR_ALLOC, std::string(fn) + ": hipMalloc of the workspace failed");
-    p->df_block = b;
-    p->df_trig = reinterpret_cast<double*>(b);
-    p->df_profile = reinterpret_cast<float*>(b + trig);
-    p->df_trig_host.resize(2 * (size_t)kDefocusMaxAngles);
-    p->df_profile_host.resize(kDefocusMaxDiameters);
+    bool made = false;
+    const int rc = ensure_workspace(p->defocus.ws, fn, "workspace", 1,
+                                    [p](auto& c, int) { layout(c, p->defocus, (size_t)kDefocusMaxAngles, (size_t)kDefocusMaxDiameters); }, &made);
+    if (rc != FDR_OK || !made) return rc;
+    p->defocus.trig_host.resize(2 * (size_t)kDefocusMaxAngles);
+    p->defocus.profile_host.resize(kDefocusMaxDiameters);
     return FDR_OK;
 }
 
@@ -61,10 +57,10 @@ int defocus_search_prepare(fdr_plan* p, const char* fn, const MotionArgs& a, hip
     const double pi = 3.14159265358979323846;
     for (int k = 0; k < a.n_angles; ++k) {
         const double th = (double)k * a.step * (pi / 180.0);
-        p->df_trig_host[k] = std::cos(th);
-        p->df_trig_host[(size_t)a.n_angles + k] = std::sin(th);
+        p->defocus.trig_host[k] = std::cos(th);
+        p->defocus.trig_host[(size_t)a.n_angles + k] = std::sin(th);
     }
-    FDR_HIP(hipMemcpyAsync(p->df_trig, p->df_trig_host.data(), 2 * (size_t)a.n_angles * sizeof(double), hipMemcpyHostToDevice, s));
+    FDR_HIP(hipMemcpyAsync(p->defocus.trig, p->defocus.trig_host.data(), 2 * (size_t)a.n_angles * sizeof(double), hipMemcpyHostToDevice, s));
     return FDR_OK;
 }
 
@@ -72,9 +68,9 @@ int defocus_search_prepare(fdr_plan* p, const char* fn, const MotionArgs& a, hip
 int defocus_search_launch(fdr_plan* p, const MotionArgs& a, float* d_profile, hipStream_t s) {
     const size_t bytes = (size_t)a.n_lengths * sizeof(float);
     ScopedPass t(p, s, "defocus profile");
-    FDR_HIP(launch_defocus_profile(p->mo_plane, p->M, p->N, p->df_trig, a.n_angles, a.min_length, a.n_lengths, p->df_profile, s));
-    if (d_profile) FDR_HIP(hipMemcpyAsync(d_profile, p->df_profile, bytes, hipMemcpyDeviceToDevice, s));
-    FDR_HIP(hipMemcpyAsync(p->df_profile_host.data(), p->df_profile, bytes, hipMemcpyDeviceToHost, s));
+    FDR_HIP(launch_defocus_profile(p->motion.plane, p->M, p->N, p->defocus.trig, a.n_angles, a.min_length, a.n_lengths, p->defocus.profile, s));
+    if (d_profile) FDR_HIP(hipMemcpyAsync(d_profile, p->defocus.profile, bytes, hipMemcpyDeviceToDevice, s));
+    FDR_HIP(hipMemcpyAsync(p->defocus.profile_host.data(), p->defocus.profile, bytes, hipMemcpyDeviceToHost, s));
     return FDR_OK;
 }
 
@@ -82,7 +78,7 @@ int defocus_search_launch(fdr_plan* p, const MotionArgs& a, float* d_profile, hi
 void defocus_search_pick(const fdr_plan* p, const MotionArgs& a, double sum, fdr_defocus_estimate* est) {
     *est = fdr_defocus_estimate{0, 0.0, 0.0, 0.f, 0.f, a.n_angles, a.n_lengths};
     if (!(sum > 0.0)) return;  // an all-zero window: the defined zero result (the profile is all zeros)
-    const float* T = p->df_profile_host.data();
+    const float* T = p->defocus.profile_host.data();
     const int n = a.n_lengths;
     int k = 0;
     for (int i = 1; i < n; ++i)
@@ -105,7 +101,7 @@ void defocus_search_pick(const fdr_plan* p, const MotionArgs& a, double sum, fdr
 }
 
 int read_sum_and_wait(fdr_plan* p, double* sum, hipStream_t s) {
-    FDR_HIP(hipMemcpyAsync(sum, p->mo_part + motion_pad_partials(p->M, p->N), sizeof(double), hipMemcpyDeviceToHost, s));
+    FDR_HIP(hipMemcpyAsync(sum, p->motion.part + motion_pad_partials(p->M, p->N), sizeof(double), hipMemcpyDeviceToHost, s));
     FDR_HIP(hipStreamSynchronize(s));
     return FDR_OK;
 }
@@ -207,7 +203,7 @@ int fdr_estimate_defocus_f32(fdr_plan* p, const float* img_host, int rows, int c
         return defocus_dev_impl(p, fn, d_in, rows, cols, cols, a, est, nullptr, nullptr);
     });
     if (rc != FDR_OK) return rc;
-    if (profile_host) std::memcpy(profile_host, p->df_profile_host.data(), (size_t)a.n_lengths * sizeof(float));
+    if (profile_host) std::memcpy(profile_host, p->defocus.profile_host.data(), (size_t)a.n_lengths * sizeof(float));
     return FDR_OK;
 }
 

@@ -22,28 +22,10 @@ const char* const kPassFrUpdate = "C op rows: IFFT+RL update (frames)";
 
 size_t frames_part_set(const fdr_plan* p) { return 2 * (size_t)rlfree_partials(p->M, p->N) + 2; }
 
-// The workspace for `count` frames.  The new block is had before the old one is let go: when it cannot be had the sticky HIP error
-// is cleared and the plan and the workspace it had stay as they were.
+// the workspace for `count` frames
 int ensure_frames_workspace(fdr_plan* p, const char* fn, int count) {
-    if (p->fr_block && p->fr_ws_count >= count) return FDR_OK;
-    const size_t P = (size_t)p->M * p->N;
-    const size_t bytes = p->ws_elems * sizeof(float2) + (2 + (size_t)count) * P * sizeof(float) +
-                         ((size_t)count * frames_part_set(p) + 2) * sizeof(double);
-    char* blk = nullptr;
-    if (hipMalloc((void**)&blk, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(FDR_ERR_ALLOC, std::string(fn) + ": hipMalloc of the frames workspace failed");
-    }
-    if (p->fr_block) (void)hipFree(p->fr_block);  // (waits for the device: nothing queued still uses it)
-    p->fr_block = blk;
-    p->fr_ws_count = count;
-    p->fr_acc = reinterpret_cast<float2*>(blk);  // 16-byte aligned for the sum kernel: first in the block
-    p->fr_u = reinterpret_cast<float*>(p->fr_acc + p->ws_elems);
-    p->fr_wgt = p->fr_u + P;
-    p->fr_dw = p->fr_wgt + P;
-    p->fr_part = reinterpret_cast<double*>(p->fr_dw + (size_t)count * P);  // a multiple of 8 bytes in (P >= 256)
-    p->fr_sums = p->fr_part + (size_t)count * frames_part_set(p);
-    return FDR_OK;
+    return ensure_workspace(p->frames.ws, fn, "frames workspace", count,
+                            [p](auto& c, int n) { layout(c, p->frames, (size_t)p->M * p->N, p->ws_elems, frames_part_set(p), n); });
 }
 
 }  // namespace
@@ -52,7 +34,7 @@ namespace fdr {
 
 const char* const kPassFrBlur = "C op rows: IFFT+crop (frames)";
 
-const float2* frame_table(const fdr_plan* p, int k, bool adjoint) { return p->fr_tables + (2 * (size_t)k + (adjoint ? 1 : 0)) * p->ws_elems; }
+const float2* frame_table(const fdr_plan* p, int k, bool adjoint) { return p->frames.tables + (2 * (size_t)k + (adjoint ? 1 : 0)) * p->ws_elems; }
 
 // the frames i0 .. i0 + n - 1 on the slots ws[0 .. n): pass B' of each on its own table, then their spectra into the accumulator
 // (`first`: stored, else added to what it holds)
@@ -100,9 +82,9 @@ int frames_adjoint(fdr_plan* p, const float* ys, size_t pitch, int count, int ro
         }
         if (rc == FDR_OK) rc = op_rows_fwd_n(p, ws, n, xs, rows, cols, prepare ? cols : stride, s);
         if (rc == FDR_OK) rc = frames_cols(p, ws, n, i0, true, s);
-        if (rc == FDR_OK) rc = frames_sum(p, p->fr_acc, ws, n, i0 == 0, s);
+        if (rc == FDR_OK) rc = frames_sum(p, p->frames.acc, ws, n, i0 == 0, s);
     }
-    if (rc == FDR_OK) rc = frames_rows_inv(p, p->fr_acc, ROW_OUT_BLUR, kPassFrBlur, nullptr, 0, nullptr, d_out, out_stride, out_rows, out_cols, s);
+    if (rc == FDR_OK) rc = frames_rows_inv(p, p->frames.acc, ROW_OUT_BLUR, kPassFrBlur, nullptr, 0, nullptr, d_out, out_stride, out_rows, out_cols, s);
     return rc;
 }
 
@@ -123,8 +105,8 @@ int frames_check(const fdr_plan* p, const char* fn, const FramesArgs& a, const f
     const fdr_rlfree_params f = free_params(*prm);
     int rc = rlfree_check(p, fn, a.imgs, a.rows, a.cols, a.stride, a.weights, a.wstride, a.out, a.out_stride, &f, NEED_OPERATOR);
     if (rc != FDR_OK) return rc;
-    if (p->fr_count == 0) return fail(FDR_ERR_STATE, std::string(fn) + ": no frame PSFs set on this plan (call fdr_set_frame_psfs* first)");
-    if (a.count != p->fr_count) return fail(FDR_ERR_ARG, std::string(fn) + ": count is not the number of frame PSFs set (fdr_frame_count)");
+    if (p->frames.count == 0) return fail(FDR_ERR_STATE, std::string(fn) + ": no frame PSFs set on this plan (call fdr_set_frame_psfs* first)");
+    if (a.count != p->frames.count) return fail(FDR_ERR_ARG, std::string(fn) + ": count is not the number of frame PSFs set (fdr_frame_count)");
     rc = prior_check(fn, prm->tv_lambda, prm->tv_eps);
     if (rc != FDR_OK) return rc;
     if (a.count > 1 && a.img_pitch < window_span(a.rows, a.cols, a.stride)) return fail(FDR_ERR_ARG, std::string(fn) + ": the frames overlap each other (img_pitch)");
@@ -151,67 +133,60 @@ int frames_rl_dev(fdr_plan* p, const char* fn, const FramesArgs& a, const fdr_rl
     const size_t P = (size_t)M * N;
     const size_t set = frames_part_set(p);
     // dw_k, W_k and their sums per frame, alpha = sum_k fullblur_k^T(W_k) over the whole plan
-    int rc = frames_adjoint(p, nullptr, 0, count, rows, cols, cols, p->fr_wgt, N, M, N, s, [&](int k, fdr_plan::Slot* w) {
+    int rc = frames_adjoint(p, nullptr, 0, count, rows, cols, cols, p->frames.wgt, N, M, N, s, [&](int k, fdr_plan::Slot* w) {
         ScopedPass t(p, s, kPassFrSetup);
         const float* m = a.weights ? a.weights + (size_t)k * a.weight_pitch : nullptr;
-        FDR_HIP(launch_rlfree_setup(a.imgs + (size_t)k * a.img_pitch, a.stride, m, a.wstride, rows, cols, p->fr_dw + (size_t)k * P, w->raw,
-                                    p->fr_part + (size_t)k * set, s));
+        FDR_HIP(launch_rlfree_setup(a.imgs + (size_t)k * a.img_pitch, a.stride, m, a.wstride, rows, cols, p->frames.dw + (size_t)k * P, w->raw,
+                                    p->frames.part + (size_t)k * set, s));
         return FDR_OK;
     });
     if (rc != FDR_OK) return rc;
     {   // the K pairs (sum dw_k, sum W_k) folded in ascending k on the device, then the start of the free form on the folded pair
         ScopedPass t(p, s, kPassFrStart);
-        FDR_HIP(launch_frames_fold(p->fr_part + 2 * (size_t)rlfree_partials(rows, cols), set, count, p->fr_sums, s));
-        FDR_HIP(launch_rlfree_start(p->fr_wgt, p->fr_u, P, prm.sigma * (float)count, p->fr_sums, s));
+        FDR_HIP(launch_frames_fold(p->frames.part + 2 * (size_t)rlfree_partials(rows, cols), set, count, p->frames.sums, s));
+        FDR_HIP(launch_rlfree_start(p->frames.wgt, p->frames.u, P, prm.sigma * (float)count, p->frames.sums, s));
     }
     const float eps = prm.tv_eps == 0.f ? FDR_RLTV_EPS : prm.tv_eps;
     const int group = launch_group(p, count);
     for (int it = 0; it < prm.iterations && rc == FDR_OK; ++it) {
-        const float* wgt = p->fr_wgt;
+        const float* wgt = p->frames.wgt;
         if (prm.tv_lambda != 0.f) {  // factor = wgt / g from the u that enters the step, in wgt's place
-            rc = rltv_factor(p, p->fr_u, M, N, N, p->fr_wgt, prm.tv_lambda, eps, s);
-            wgt = p->rt_f;
+            rc = rltv_factor(p, p->frames.u, M, N, N, p->frames.wgt, prm.tv_lambda, eps, s);
+            wgt = p->rltv.f;
         }
         for (int i0 = 0; i0 < count && rc == FDR_OK; i0 += group) {
             const int n = group < count - i0 ? group : count - i0;
             fdr_plan::Slot* ws[kMaxGroup];
             const float *us[kMaxGroup], *dws[kMaxGroup];
             float* r[kMaxGroup];
-            for (int k = 0; k < n; ++k) { ws[k] = &p->slots[k]; us[k] = p->fr_u; dws[k] = p->fr_dw + (size_t)(i0 + k) * P; r[k] = ws[k]->raw; }
+            for (int k = 0; k < n; ++k) { ws[k] = &p->slots[k]; us[k] = p->frames.u; dws[k] = p->frames.dw + (size_t)(i0 + k) * P; r[k] = ws[k]->raw; }
             rc = op_rows_fwd_n(p, ws, n, us, M, N, N, s);                                        // c_k = window(fullblur_k(u)) ...
             if (rc == FDR_OK) rc = frames_cols(p, ws, n, i0, false, s);
             if (rc == FDR_OK)                                                                    // ... r_k = dw_k / c_k
                 rc = op_rows_inv_n(p, ws, n, ROW_OUT_RL_RATIO, kPassFrRatio, dws, cols, nullptr, r, cols, rows, cols, s);
             if (rc == FDR_OK) rc = op_rows_fwd_n(p, ws, n, r, rows, cols, cols, s);               // sum_k fullblur_k^T(pad(r_k)) ...
             if (rc == FDR_OK) rc = frames_cols(p, ws, n, i0, true, s);
-            if (rc == FDR_OK) rc = frames_sum(p, p->fr_acc, ws, n, i0 == 0, s);
+            if (rc == FDR_OK) rc = frames_sum(p, p->frames.acc, ws, n, i0 == 0, s);
         }
         if (rc == FDR_OK)                                                                        // ... u = max(u wgt g, 0)
-            rc = frames_rows_inv(p, p->fr_acc, ROW_OUT_RL_UPDATE_W, kPassFrUpdate, p->fr_u, N, wgt, p->fr_u, N, M, N, s);
+            rc = frames_rows_inv(p, p->frames.acc, ROW_OUT_RL_UPDATE_W, kPassFrUpdate, p->frames.u, N, wgt, p->frames.u, N, M, N, s);
     }
     if (rc != FDR_OK) return rc;
-    return rlfree_finish(p, fn, p->fr_u, a.out, a.out_stride, free_params(prm), s);
+    return rlfree_finish(p, fn, p->frames.u, a.out, a.out_stride, free_params(prm), s);
 }
 
 int set_frame_psfs_impl(fdr_plan* p, const char* fn, const float* d_psfs, size_t pitch, int count, int prows, int pcols, int pstride, hipStream_t s) {
-    if (p->fr_cap < count) {
-        float2* t = nullptr;
-        if (hipMalloc((void**)&t, 2 * (size_t)count * p->ws_elems * sizeof(float2)) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(FDR_ERR_ALLOC, std::string(fn) + ": hipMalloc of the frame tables failed");
-        }
-        if (p->fr_tables) (void)hipFree(p->fr_tables);  // (waits for the device: nothing queued still uses it)
-        p->fr_tables = t;
-        p->fr_cap = count;
-    }
-    p->fr_count = 0;  // (a HIP error below leaves no half-built set behind)
-    ++p->fr_gen;      // (the solve table of fdr_tv_deconv_frames_f32*, if tv_T holds it, is of the old set)
+    const int rc_tables = ensure_workspace(p->frames.tables_ws, fn, "frame tables", count,
+                                           [p](auto& c, int n) { layout(c, p->frames.tables, 2 * (size_t)n * p->ws_elems, 16); });
+    if (rc_tables != FDR_OK) return rc_tables;
+    p->frames.count = 0;  // (a HIP error below leaves no half-built set behind)
+    ++p->frames.gen;      // (the solve table of fdr_tv_deconv_frames_f32*, if tv.T holds it, is of the old set)
     for (int k = 0; k < count; ++k) {
-        float2* h = p->fr_tables + 2 * (size_t)k * p->ws_elems;
+        float2* h = p->frames.tables + 2 * (size_t)k * p->ws_elems;
         const int rc = build_operator_tables(p, d_psfs + (size_t)k * pitch, prows, pcols, pstride, h, h + p->ws_elems, s);
         if (rc != FDR_OK) return rc;
     }
-    p->fr_count = count;
+    p->frames.count = count;
     return FDR_OK;
 }
 
@@ -262,7 +237,7 @@ int fdr_set_frame_psfs(fdr_plan* p, const float* psfs_host, size_t psf_pitch, in
 
 int fdr_frame_count(fdr_plan* p, int* count) {
     if (!p || !count) return null_arg("fdr_frame_count");
-    *count = p->fr_count;
+    *count = p->frames.count;
     return FDR_OK;
 }
 
@@ -292,8 +267,8 @@ int fdr_blur_frames_f32_dev(fdr_plan* p, const float* d_in, size_t in_pitch, int
     if (!p || !d_in || !d_out) return null_arg(fn);
     int rc = check_window(p, fn, NEED_OPERATOR, rows, cols, stride, out_stride);
     if (rc != FDR_OK) return rc;
-    if (p->fr_count == 0) return fail(FDR_ERR_STATE, std::string(fn) + ": no frame PSFs set on this plan (call fdr_set_frame_psfs* first)");
-    if (count != p->fr_count) return fail(FDR_ERR_ARG, std::string(fn) + ": count is not the number of frame PSFs set (fdr_frame_count)");
+    if (p->frames.count == 0) return fail(FDR_ERR_STATE, std::string(fn) + ": no frame PSFs set on this plan (call fdr_set_frame_psfs* first)");
+    if (count != p->frames.count) return fail(FDR_ERR_ARG, std::string(fn) + ": count is not the number of frame PSFs set (fdr_frame_count)");
     if (count > 1 && (adjoint ? in_pitch < window_span(rows, cols, stride) : out_pitch < window_span(rows, cols, out_stride)))
         return fail(FDR_ERR_ARG, std::string(fn) + ": the frames' windows overlap each other (pitch)");
     if (ranges_overlap(window_range(d_in, rows, cols, stride, adjoint ? count : 1, in_pitch),

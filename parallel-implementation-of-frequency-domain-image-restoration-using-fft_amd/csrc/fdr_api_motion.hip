@@ -16,19 +16,12 @@ constexpr size_t kMotionMaxTable = (size_t)1 << 26;
 
 // the table (device and host) and the trig table for `a`, grown when a larger one is asked for
 int ensure_motion_table(fdr_plan* p, const char* fn, const MotionArgs& a) {
-    const size_t nt = (size_t)a.n_angles * a.n_lengths, ng = 2 * (size_t)a.n_angles;
-    if (p->mo_table_cap < nt) {
-        (void)hipFree(p->mo_table); p->mo_table = nullptr; p->mo_table_cap = 0;
-        if (hipMalloc((void**)&p->mo_table, nt * sizeof(float)) != hipSuccess) return fail(FDR_ERR_ALLOC, std::string(fn) + ": hipMalloc of the table failed");
-        p->mo_table_cap = nt;
-    }
-    if (p->mo_trig_cap < ng) {
-        (void)hipFree(p->mo_trig); p->mo_trig = nullptr; p->mo_trig_cap = 0;
-        if (hipMalloc((void**)&p->mo_trig, ng * sizeof(double)) != hipSuccess) return fail(FDR_ERR_ALLOC, std::string(fn) + ": hipMalloc of the table failed");
-        p->mo_trig_cap = ng;
-    }
-    if (p->mo_table_host.size() < nt) p->mo_table_host.resize(nt);
-    return FDR_OK;
+    const size_t nt = (size_t)a.n_angles * a.n_lengths;  // (at most kMotionMaxTable: motion_args)
+    int rc = ensure_workspace(p->motion.table_ws, fn, "table", (int)nt, [p](auto& c, int n) { layout(c, p->motion.table, (size_t)n, 4); });
+    if (rc == FDR_OK)
+        rc = ensure_workspace(p->motion.trig_ws, fn, "table", 2 * a.n_angles, [p](auto& c, int n) { layout(c, p->motion.trig, (size_t)n, 8); });
+    if (rc == FDR_OK && p->motion.table_host.size() < nt) p->motion.table_host.resize(nt);
+    return rc;
 }
 
 }  // namespace
@@ -56,26 +49,18 @@ int motion_args(const fdr_plan* p, const char* fn, int rows, int cols, int strid
 }
 
 int ensure_motion_workspace(fdr_plan* p, const char* fn) {
-    if (p->mo_block) return FDR_OK;
-    const size_t plane = (size_t)p->M * p->N * sizeof(float2);
-    const size_t part = ((size_t)motion_pad_partials(p->M, p->N) + 1) * sizeof(double);
-    const size_t hann = ((size_t)p->M + p->N) * sizeof(float);
-    char* b = nullptr;
-    if (hipMalloc((void**)&b, plane + part + hann) != hipSuccess) return fail(FDR_ERR_ALLOC, std::string(fn) + ": hipMalloc of the workspace failed");
-    p->mo_block = b;
-    p->mo_plane = reinterpret_cast<float2*>(b);
-    p->mo_part = reinterpret_cast<double*>(b + plane);
-    p->mo_hann = reinterpret_cast<float*>(b + plane + part);
-    return FDR_OK;
+    return ensure_workspace(p->motion.ws, fn, "workspace", 1, [p](auto& c, int) {
+        layout(c, p->motion, (size_t)p->M, (size_t)p->N, (size_t)motion_pad_partials(p->M, p->N));
+    });
 }
 
 int motion_cepstrum_plane(fdr_plan* p, const float* d_img, int rows, int cols, int stride, hipStream_t s) {
     ScopedPass t(p, s, "cepstrum");
-    FDR_HIP(launch_motion_window(d_img, rows, cols, stride, p->mo_hann, p->mo_plane, p->M, p->N, p->mo_part, s));
-    int rc = dft2d_dev(p, p->mo_plane, p->slots[0].work2, false, s);
+    FDR_HIP(launch_motion_window(d_img, rows, cols, stride, p->motion.hann, p->motion.plane, p->M, p->N, p->motion.part, s));
+    int rc = dft2d_dev(p, p->motion.plane, p->slots[0].work2, false, s);
     if (rc != FDR_OK) return rc;
-    FDR_HIP(launch_motion_log(p->mo_plane, p->M, p->N, p->mo_part + motion_pad_partials(p->M, p->N), s));
-    return dft2d_dev(p, p->mo_plane, p->slots[0].work2, true, s);
+    FDR_HIP(launch_motion_log(p->motion.plane, p->M, p->N, p->motion.part + motion_pad_partials(p->M, p->N), s));
+    return dft2d_dev(p, p->motion.plane, p->slots[0].work2, true, s);
 }
 
 double median_of(std::vector<double>& v) {
@@ -91,22 +76,22 @@ int motion_search_prepare(fdr_plan* p, const char* fn, const MotionArgs& a, hipS
     const int rc = ensure_motion_table(p, fn, a);
     if (rc != FDR_OK) return rc;
     const double pi = 3.14159265358979323846;
-    p->mo_trig_host.resize(2 * (size_t)a.n_angles);
+    p->motion.trig_host.resize(2 * (size_t)a.n_angles);
     for (int k = 0; k < a.n_angles; ++k) {
         const double th = (double)k * a.step * (pi / 180.0);
-        p->mo_trig_host[k] = std::cos(th);
-        p->mo_trig_host[(size_t)a.n_angles + k] = std::sin(th);
+        p->motion.trig_host[k] = std::cos(th);
+        p->motion.trig_host[(size_t)a.n_angles + k] = std::sin(th);
     }
-    FDR_HIP(hipMemcpyAsync(p->mo_trig, p->mo_trig_host.data(), p->mo_trig_host.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    FDR_HIP(hipMemcpyAsync(p->motion.trig, p->motion.trig_host.data(), p->motion.trig_host.size() * sizeof(double), hipMemcpyHostToDevice, s));
     return FDR_OK;
 }
 
 int motion_search_launch(fdr_plan* p, const MotionArgs& a, float* d_scores, hipStream_t s) {
     const size_t nt = (size_t)a.n_angles * a.n_lengths;
     ScopedPass t(p, s, "motion score");
-    FDR_HIP(launch_motion_score(p->mo_plane, p->M, p->N, p->mo_trig, a.n_angles, a.min_length, a.n_lengths, p->mo_table, s));
-    if (d_scores) FDR_HIP(hipMemcpyAsync(d_scores, p->mo_table, nt * sizeof(float), hipMemcpyDeviceToDevice, s));
-    FDR_HIP(hipMemcpyAsync(p->mo_table_host.data(), p->mo_table, nt * sizeof(float), hipMemcpyDeviceToHost, s));
+    FDR_HIP(launch_motion_score(p->motion.plane, p->M, p->N, p->motion.trig, a.n_angles, a.min_length, a.n_lengths, p->motion.table, s));
+    if (d_scores) FDR_HIP(hipMemcpyAsync(d_scores, p->motion.table, nt * sizeof(float), hipMemcpyDeviceToDevice, s));
+    FDR_HIP(hipMemcpyAsync(p->motion.table_host.data(), p->motion.table, nt * sizeof(float), hipMemcpyDeviceToHost, s));
     return FDR_OK;
 }
 
@@ -114,7 +99,7 @@ void motion_search_pick(const fdr_plan* p, const MotionArgs& a, double sum, fdr_
     const size_t nt = (size_t)a.n_angles * a.n_lengths;
     *est = fdr_motion_estimate{0, 0.0, 0.f, 0.f, a.n_angles, a.n_lengths};
     if (!(sum > 0.0)) return;  // an all-zero window: the defined zero result (the table is all zeros)
-    const float* S = p->mo_table_host.data();
+    const float* S = p->motion.table_host.data();
     size_t kmin = 0;
     for (size_t k = 1; k < nt; ++k)
         if (S[k] < S[kmin]) kmin = k;  // strict: exact ties keep the lowest flat index
@@ -137,7 +122,7 @@ int cepstrum_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows,
     int rc = ensure_motion_workspace(p, fn);
     if (rc == FDR_OK) rc = motion_cepstrum_plane(p, d_img, rows, cols, stride, s);
     if (rc != FDR_OK) return rc;
-    FDR_HIP(launch_real_part(p->mo_plane, d_out, (size_t)p->M * p->N, s));
+    FDR_HIP(launch_real_part(p->motion.plane, d_out, (size_t)p->M * p->N, s));
     return FDR_OK;
 }
 
@@ -150,7 +135,7 @@ int estimate_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows,
     if (rc == FDR_OK) rc = motion_search_launch(p, a, d_scores, s);
     if (rc != FDR_OK) return rc;
     double sum = 0.0;
-    FDR_HIP(hipMemcpyAsync(&sum, p->mo_part + motion_pad_partials(p->M, p->N), sizeof(double), hipMemcpyDeviceToHost, s));
+    FDR_HIP(hipMemcpyAsync(&sum, p->motion.part + motion_pad_partials(p->M, p->N), sizeof(double), hipMemcpyDeviceToHost, s));
     FDR_HIP(hipStreamSynchronize(s));
     motion_search_pick(p, a, sum, est);
     return FDR_OK;
@@ -203,7 +188,7 @@ int fdr_estimate_motion_f32(fdr_plan* p, const float* img_host, int rows, int co
         return estimate_dev_impl(p, fn, d_in, rows, cols, cols, a, est, nullptr, nullptr);
     });
     if (rc != FDR_OK) return rc;
-    if (scores_host) std::memcpy(scores_host, p->mo_table_host.data(), (size_t)a.n_angles * a.n_lengths * sizeof(float));
+    if (scores_host) std::memcpy(scores_host, p->motion.table_host.data(), (size_t)a.n_angles * a.n_lengths * sizeof(float));
     return FDR_OK;
 }
 

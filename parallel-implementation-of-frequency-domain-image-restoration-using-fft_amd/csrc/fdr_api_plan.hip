@@ -491,11 +491,7 @@ int fdr_plan_destroy(fdr_plan* p) {
     p->timer.destroy();
     (void)hipFree(p->filt); (void)hipFree(p->psf_dev); (void)hipFree(p->lap); (void)hipFree(p->op_h);
     (void)hipFree(p->stage_in); (void)hipFree(p->stage_out);
-    (void)hipFree(p->mo_block); (void)hipFree(p->mo_table); (void)hipFree(p->mo_trig); (void)hipFree(p->df_block); (void)hipFree(p->tv_block);
-    (void)hipFree(p->rf_block); (void)hipFree(p->rt_block); (void)hipFree(p->ra_block); (void)hipFree(p->rg_block);
-    (void)hipFree(p->bl_block); (void)hipFree(p->bl_w); (void)hipFree(p->tf_block); (void)hipFree(p->ta_block);
-    (void)hipFree(p->rs_block); (void)hipFree(p->rs_trace); (void)hipFree(p->rs_planes);
-    (void)hipFree(p->fr_tables); (void)hipFree(p->fr_block); (void)hipFree(p->tm_block);
+    for (fdr::Workspace* w : p->workspaces()) w->free_with(device_free);
     delete p;
     return FDR_OK;
 }

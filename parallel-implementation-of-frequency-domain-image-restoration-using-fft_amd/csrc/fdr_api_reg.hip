@@ -20,30 +20,18 @@ constexpr int kRegMinNoise = 3;  // the mask needs one interior pixel
 
 // the first call of a plan: the power plane, the partials, the candidate and result arrays in one allocation
 int ensure_reg_workspace(fdr_plan* p, const char* fn) {
-    if (p->rg_block) return FDR_OK;
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t power = up((p->ws_elems + 2) * sizeof(float));
-    const size_t part = up((size_t)reg_curve_partials(p->M, p->npanels) * 2 * kRegCandidates * sizeof(double));
-    const size_t noise = up(((size_t)kRegMaxPartials + 1) * sizeof(double));
-    const size_t pairs = up((size_t)kRegMaxCurve * 2 * sizeof(double));
-    char* b = nullptr;
-    if (hipMalloc((void**)&b, power + part + noise + 2 * pairs) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(FDR_ERR_ALLOC, std::string(fn) + ": hipMalloc of the workspace failed");
-    }
+    bool made = false;
+    const int rc = ensure_workspace(p->reg.ws, fn, "workspace", 1, [p](auto& c, int) {
+        layout(c, p->reg, p->ws_elems, (size_t)reg_curve_partials(p->M, p->npanels) * 2 * kRegCandidates, (size_t)kRegMaxPartials + 1, (size_t)kRegMaxCurve);
+    }, &made);
+    if (rc != FDR_OK || !made) return rc;
     try {
-        p->rg_cand_host.assign((size_t)kRegMaxCurve * 2, 0.0);
-        p->rg_res_host.assign((size_t)kRegMaxCurve * 2, 0.0);
+        p->reg.cand_host.assign((size_t)kRegMaxCurve * 2, 0.0);
+        p->reg.res_host.assign((size_t)kRegMaxCurve * 2, 0.0);
     } catch (const std::bad_alloc&) {
-        (void)hipFree(b);
+        p->reg.ws.free_with(device_free);
         return fail(FDR_ERR_ALLOC, std::string(fn) + ": out of host memory");
     }
-    p->rg_block = b;
-    p->rg_power = reinterpret_cast<float*>(b);
-    p->rg_part = reinterpret_cast<double*>(b + power);
-    p->rg_noise = reinterpret_cast<double*>(b + power + part);
-    p->rg_cand = reinterpret_cast<double*>(b + power + part + noise);
-    p->rg_res = reinterpret_cast<double*>(b + power + part + noise + pairs);
     return FDR_OK;
 }
 
@@ -83,7 +71,7 @@ int noise_window_check(const char* fn, int rows, int cols, int stride) {
 
 namespace {
 
-// pass A and the power pass: P of the window into rg_power
+// pass A and the power pass: P of the window into reg.power
 int reg_power_dev(fdr_plan* p, const float* d_img, int rows, int cols, int stride, hipStream_t s) {
     const int rc = op_rows_fwd(p, d_img, rows, cols, stride, s);
     if (rc != FDR_OK) return rc;
@@ -91,23 +79,23 @@ int reg_power_dev(fdr_plan* p, const float* d_img, int rows, int cols, int strid
     ColArgs ca = panel_col_args(p);
     ca.data = p->slots[0].work;
     ca.nvalid = (rows + 3) & ~3;  // <= M (M is a multiple of 8 on this path): the rows below are zero and not read
-    FDR_HIP(launch_cols_panel_power(p->logM, ca, p->rg_power, p->rg_power + p->ws_elems, p->tw_col_f, s));
+    FDR_HIP(launch_cols_panel_power(p->logM, ca, p->reg.power, p->reg.power + p->ws_elems, p->tw_col_f, s));
     return FDR_OK;
 }
 
-// rho and trace of the n pairs in rg_cand_host into rg_res_host (pairs (rho, trace)); synchronous.  The pairs up to the next
+// rho and trace of the n pairs in reg.cand_host into reg.res_host (pairs (rho, trace)); synchronous.  The pairs up to the next
 // multiple of kRegCandidates are zero: the last sweep evaluates and drops them.
 int reg_eval(fdr_plan* p, int n, hipStream_t s) {
     const int padded = (n + kRegCandidates - 1) / kRegCandidates * kRegCandidates;
-    for (int k = 2 * n; k < 2 * padded; ++k) p->rg_cand_host[k] = 0.0;
-    FDR_HIP(hipMemcpyAsync(p->rg_cand, p->rg_cand_host.data(), (size_t)padded * 2 * sizeof(double), hipMemcpyHostToDevice, s));
+    for (int k = 2 * n; k < 2 * padded; ++k) p->reg.cand_host[k] = 0.0;
+    FDR_HIP(hipMemcpyAsync(p->reg.cand, p->reg.cand_host.data(), (size_t)padded * 2 * sizeof(double), hipMemcpyHostToDevice, s));
     for (int at = 0; at < n; at += kRegCandidates) {
         ScopedPass t(p, s, kPassRegSweep);
         const int nc = n - at < kRegCandidates ? n - at : kRegCandidates;
-        FDR_HIP(launch_reg_curve(p->op_h, p->rg_power, p->rg_power + p->ws_elems, p->lap, p->rg_cand + 2 * at, nc, p->M, p->N, p->pstride,
-                                 p->npanels, p->rg_part, p->rg_res + 2 * at, s));
+        FDR_HIP(launch_reg_curve(p->op_h, p->reg.power, p->reg.power + p->ws_elems, p->lap, p->reg.cand + 2 * at, nc, p->M, p->N, p->pstride,
+                                 p->npanels, p->reg.part, p->reg.res + 2 * at, s));
     }
-    FDR_HIP(hipMemcpyAsync(p->rg_res_host.data(), p->rg_res, (size_t)n * 2 * sizeof(double), hipMemcpyDeviceToHost, s));
+    FDR_HIP(hipMemcpyAsync(p->reg.res_host.data(), p->reg.res, (size_t)n * 2 * sizeof(double), hipMemcpyDeviceToHost, s));
     FDR_HIP(hipStreamSynchronize(s));
     return FDR_OK;
 }
@@ -127,10 +115,10 @@ int curve_dev_impl(fdr_plan* p, const float* d_img, int rows, int cols, int stri
                    double* residual, double* trace, hipStream_t s) {
     int rc = reg_power_dev(p, d_img, rows, cols, stride, s);
     if (rc != FDR_OK) return rc;
-    for (int i = 0; i < n; ++i) { p->rg_cand_host[2 * i] = K[i]; p->rg_cand_host[2 * i + 1] = gamma[i]; }
+    for (int i = 0; i < n; ++i) { p->reg.cand_host[2 * i] = K[i]; p->reg.cand_host[2 * i + 1] = gamma[i]; }
     rc = reg_eval(p, n, s);
     if (rc != FDR_OK) return rc;
-    for (int i = 0; i < n; ++i) { residual[i] = p->rg_res_host[2 * i]; trace[i] = p->rg_res_host[2 * i + 1]; }
+    for (int i = 0; i < n; ++i) { residual[i] = p->reg.res_host[2 * i]; trace[i] = p->reg.res_host[2 * i + 1]; }
     return FDR_OK;
 }
 
@@ -174,7 +162,7 @@ int choose_dev_impl(fdr_plan* p, const float* d_img, int rows, int cols, int str
     int rc = FDR_OK;
     if (a.estimate) {
         ScopedPass t(p, s, kPassRegNoise);
-        rc = noise_sigma_dev(d_img, rows, cols, stride, p->rg_noise, &sigma, s);
+        rc = noise_sigma_dev(d_img, rows, cols, stride, p->reg.noise, &sigma, s);
         if (rc != FDR_OK) return rc;
     }
     rc = reg_power_dev(p, d_img, rows, cols, stride, s);
@@ -185,13 +173,13 @@ int choose_dev_impl(fdr_plan* p, const float* d_img, int rows, int cols, int str
     auto sweep = [&](double lo, double hi) {
         log_grid(lo, hi, n, v);
         for (int i = 0; i < n; ++i) {
-            p->rg_cand_host[2 * i] = a.param == FDR_REG_PARAM_K ? v[i] : a.fixed;
-            p->rg_cand_host[2 * i + 1] = a.param == FDR_REG_PARAM_K ? a.fixed : v[i];
+            p->reg.cand_host[2 * i] = a.param == FDR_REG_PARAM_K ? v[i] : a.fixed;
+            p->reg.cand_host[2 * i + 1] = a.param == FDR_REG_PARAM_K ? a.fixed : v[i];
         }
         evaluations += n;
         return reg_eval(p, n, s);
     };
-    const double* res = p->rg_res_host.data();  // (rho, trace) of candidate i at 2 i
+    const double* res = p->reg.res_host.data();  // (rho, trace) of candidate i at 2 i
     auto finish = [&](double value, int nearest, int flags) {
         const double rho = res[2 * nearest], tr = res[2 * nearest + 1];
         *out = fdr_reg_choice{value, sigma, rho, tr, gcv_of(rho, tr, mn), flags, evaluations};

@@ -23,29 +23,12 @@ const char* const kPassRfNorm = "E RLF minmax+normalize";
 
 namespace fdr {
 
-// The workspace of the free-boundary calls: 1 + 2 g planes of M x N floats (wgt; u and dw of g images) and the double partials of
-// the two sums, once per image.  The first call of a plan makes the three planes of one image; a batched call on groups of g images
-// grows it to 1 + 2 g planes on its first use.  The new block is had before the old one is let go: on FDR_ERR_ALLOC the plan and the
-// workspace it had stay as they were.  Plane order: u_0, wgt, dw_0, then u_k, dw_k for k = 1 .. g - 1.
+// The workspace of the free-boundary calls: the first call of a plan makes the three planes of one image; a batched call on groups
+// of g images grows it to 1 + 2 g planes on its first use.
 int ensure_rlfree_workspace(fdr_plan* p, const char* fn, int group) {
-    if (p->rf_block && p->rf_group >= group) return FDR_OK;
-    const size_t P = (size_t)p->M * p->N;
-    const size_t n_part = 2 * (size_t)rlfree_partials(p->M, p->N) + 2;
-    const size_t planes = 1 + 2 * (size_t)group;
-    char* blk = nullptr;
-    if (hipMalloc((void**)&blk, planes * P * sizeof(float) + (size_t)group * n_part * sizeof(double)) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(FDR_ERR_ALLOC, std::string(fn) + ": hipMalloc of the free-boundary workspace failed");
-    }
-    if (p->rf_block) (void)hipFree(p->rf_block);  // (waits for the device: nothing queued still uses it)
-    float* base = reinterpret_cast<float*>(blk);
-    p->rf_block = blk;
-    p->rf_group = group;
-    p->rf_u = base;
-    p->rf_wgt = base + P;
-    p->rf_dw = base + 2 * P;
-    p->rf_part = reinterpret_cast<double*>(base + planes * P);  // a multiple of 8 bytes in (P >= 256)
-    return FDR_OK;
+    return ensure_workspace(p->rlfree.ws, fn, "free-boundary workspace", group, [p](auto& c, int g) {
+        layout(c, p->rlfree, (size_t)p->M * p->N, 2 * (size_t)rlfree_partials(p->M, p->N) + 2, g);
+    });
 }
 
 }  // namespace fdr
@@ -53,9 +36,9 @@ int ensure_rlfree_workspace(fdr_plan* p, const char* fn, int group) {
 namespace {
 
 // image k of a group: its dense M x N estimate, its dw and the partials of its sums
-float* rlfree_u_plane(const fdr_plan* p, int k) { return k == 0 ? p->rf_u : p->rf_u + (size_t)(1 + 2 * k) * p->M * p->N; }
-float* rlfree_dw_plane(const fdr_plan* p, int k) { return k == 0 ? p->rf_dw : p->rf_u + (size_t)(2 + 2 * k) * p->M * p->N; }
-double* rlfree_part(const fdr_plan* p, int k) { return p->rf_part + (size_t)k * (2 * (size_t)rlfree_partials(p->M, p->N) + 2); }
+float* rlfree_u_plane(const fdr_plan* p, int k) { return k == 0 ? p->rlfree.u : p->rlfree.u + (size_t)(1 + 2 * k) * p->M * p->N; }
+float* rlfree_dw_plane(const fdr_plan* p, int k) { return k == 0 ? p->rlfree.dw : p->rlfree.u + (size_t)(2 + 2 * k) * p->M * p->N; }
+double* rlfree_part(const fdr_plan* p, int k) { return p->rlfree.part + (size_t)k * (2 * (size_t)rlfree_partials(p->M, p->N) + 2); }
 
 // setup: dw and W = pad(m) dense into `dw` and `W` (W also to keep_w when that is not null), the two sums behind the partials at
 // `part`; *sums is where the device holds (sum dw, sum W).  d_w may be W's plane itself.
@@ -100,7 +83,7 @@ int rlfree_check(const fdr_plan* p, const char* fn, const float* img, int rows, 
 }
 
 int stage_weights(fdr_plan* p, const float* weights_host, int rows, int cols, int wstride) {
-    FDR_HIP(hipMemcpy2D(p->rf_u, (size_t)cols * sizeof(float), weights_host, (size_t)wstride * sizeof(float), (size_t)cols * sizeof(float),
+    FDR_HIP(hipMemcpy2D(p->rlfree.u, (size_t)cols * sizeof(float), weights_host, (size_t)wstride * sizeof(float), (size_t)cols * sizeof(float),
                         (size_t)rows, hipMemcpyHostToDevice));
     return FDR_OK;
 }
@@ -129,9 +112,9 @@ int rlfree_step(fdr_plan* p, fdr_plan::Slot* const* ws, int n, const float* cons
 int rlfree_begin(fdr_plan* p, const float* d_img, int rows, int cols, int stride, const float* d_w, int wstride, float sigma, float* keep_w,
                  const double** sums, hipStream_t s) {
     const double* sm = nullptr;
-    int rc = rlfree_setup_image(p, d_img, rows, cols, stride, d_w, wstride, p->rf_dw, p->rf_u, p->rf_part, keep_w, &sm, s);
-    if (rc == FDR_OK) rc = blur_window_dev(p, p->rf_u, rows, cols, cols, p->rf_wgt, p->N, p->M, p->N, 1, s);  // alpha over the whole plan
-    if (rc == FDR_OK) rc = rlfree_start_image(p, p->rf_wgt, p->rf_u, sigma, sm, s);
+    int rc = rlfree_setup_image(p, d_img, rows, cols, stride, d_w, wstride, p->rlfree.dw, p->rlfree.u, p->rlfree.part, keep_w, &sm, s);
+    if (rc == FDR_OK) rc = blur_window_dev(p, p->rlfree.u, rows, cols, cols, p->rlfree.wgt, p->N, p->M, p->N, 1, s);  // alpha over the whole plan
+    if (rc == FDR_OK) rc = rlfree_start_image(p, p->rlfree.wgt, p->rlfree.u, sigma, sm, s);
     if (sums) *sums = sm;
     return rc;
 }
@@ -155,7 +138,7 @@ int rlfree_batch_dev(fdr_plan* p, const char* fn, const float* d_imgs, size_t im
                      float* keep_w, bool accel, float* d_alphas, size_t alpha_pitch, const RlTvPrior* tv) {
     if (accel && hooks) return fail(FDR_ERR_STATE, "rlfree_batch_dev: the accelerated recursion takes no hooks");
     const int group = launch_group(p, count);
-    if (tv && (accel || hooks || group == 1 || p->rt_group < group))
+    if (tv && (accel || hooks || group == 1 || p->rltv.ws.count < group))
         return fail(FDR_ERR_STATE, "rlfree_batch_dev: the prior takes launch groups of several images, plain steps and its workspace");
     const size_t P = (size_t)p->M * p->N;
     int rc = FDR_OK;
@@ -167,18 +150,18 @@ int rlfree_batch_dev(fdr_plan* p, const char* fn, const float* d_imgs, size_t im
     }
     rc = rlfree_begin(p, d_imgs, rows, cols, stride, d_w, wstride, prm.sigma, keep_w, nullptr, s);
     if (rc == FDR_OK && tv)  // the prior's estimates lie one pitch apart, in its own workspace: image 0's start goes there
-        FDR_HIP(hipMemcpyAsync(p->rt_u, p->rf_u, P * sizeof(float), hipMemcpyDeviceToDevice, s));
+        FDR_HIP(hipMemcpyAsync(p->rltv.u, p->rlfree.u, P * sizeof(float), hipMemcpyDeviceToDevice, s));
     for (int i0 = 0; i0 < count && rc == FDR_OK; i0 += group) {
         const LaunchGroup g(p, i0, count, d_imgs, img_pitch, d_out, out_pitch);
         float* us[kMaxGroup];
         const float* dws[kMaxGroup];
         for (int k = 0; k < g.n && rc == FDR_OK; ++k) {
-            us[k] = tv ? p->rt_u + (size_t)k * P : rlfree_u_plane(p, k); dws[k] = rlfree_dw_plane(p, k);
+            us[k] = tv ? p->rltv.u + (size_t)k * P : rlfree_u_plane(p, k); dws[k] = rlfree_dw_plane(p, k);
             if (i0 + k == 0) continue;  // begun above
             const double* sums = nullptr;
             rc = rlfree_setup_image(p, g.ins[k], rows, cols, stride, d_w, wstride, rlfree_dw_plane(p, k), us[k], rlfree_part(p, k), nullptr, &sums, s);
             if (rc != FDR_OK) break;
-            FDR_HIP(hipMemcpyAsync(g.ws[k]->raw, p->rf_wgt, (size_t)p->M * p->N * sizeof(float), hipMemcpyDeviceToDevice, s));
+            FDR_HIP(hipMemcpyAsync(g.ws[k]->raw, p->rlfree.wgt, (size_t)p->M * p->N * sizeof(float), hipMemcpyDeviceToDevice, s));
             rc = rlfree_start_image(p, g.ws[k]->raw, us[k], 0.f, sums, s);
         }
         float* fin[kMaxGroup];  // where u_n lies
@@ -189,12 +172,12 @@ int rlfree_batch_dev(fdr_plan* p, const char* fn, const float* d_imgs, size_t im
             const int strides[2] = {p->N, p->N};
             rc = rl_accel_loop(p, g.n, prm.iterations, p->M, p->N, U, strides, 0, nullptr, 0, d_alphas ? d_alphas + (size_t)i0 * alpha_pitch : nullptr,
                                alpha_pitch, s, [&](const float* const* ys, int, float* const* outs, int) {
-                                   return rlfree_step(p, g.ws, g.n, ys, outs, dws, p->rf_wgt, rows, cols, s);
+                                   return rlfree_step(p, g.ws, g.n, ys, outs, dws, p->rlfree.wgt, rows, cols, s);
                                }, fin);
         }
         for (int it = 0; it < prm.iterations && rc == FDR_OK && !accel; ++it) {
-            if (tv) rc = rltv_factor_group(p, g.n, p->M, p->N, p->N, p->rf_wgt, *tv, s);  // factor_k = wgt / g_k from the u_k that enter the step
-            if (rc == FDR_OK) rc = rlfree_step(p, g.ws, g.n, us, us, dws, tv ? p->rt_f : p->rf_wgt, rows, cols, s, nullptr, hooks, it, tv ? P : 0);
+            if (tv) rc = rltv_factor_group(p, g.n, p->M, p->N, p->N, p->rlfree.wgt, *tv, s);  // factor_k = wgt / g_k from the u_k that enter the step
+            if (rc == FDR_OK) rc = rlfree_step(p, g.ws, g.n, us, us, dws, tv ? p->rltv.f : p->rlfree.wgt, rows, cols, s, nullptr, hooks, it, tv ? P : 0);
             if (rc == FDR_OK && hooks && hooks->after_step) rc = hooks->after_step(it);
         }
         for (int k = 0; k < g.n && rc == FDR_OK; ++k) rc = rlfree_finish(p, fn, fin[k], g.outs[k], out_stride, prm, s);
@@ -245,7 +228,7 @@ int rlfree_host_entry(fdr_plan* p, const char* fn, const float* img_host, int ro
         if (rc2 != FDR_OK) return rc2;
         return host_image_call(p, fn, img_host, rows, cols, stride, out_host, prm.out_rows, prm.out_cols, out_stride,
                                [&](const float* d_in, float* d_out) {
-                                   return rlfree_dev_impl(p, fn, d_in, rows, cols, cols, weights_host ? p->rf_u : nullptr, cols, d_out, prm.out_cols,
+                                   return rlfree_dev_impl(p, fn, d_in, rows, cols, cols, weights_host ? p->rlfree.u : nullptr, cols, d_out, prm.out_cols,
                                                           prm, accel, d_alphas, nullptr);
                                });
     });

@@ -74,39 +74,20 @@ int auto_check(const fdr_plan* p, const char* fn, const float* img, int rows, in
 
 // the partials (first call), the two planes of the weighted free form (its first call) and room for `steps` steps in the internal trace
 int ensure_rlstop_workspace(fdr_plan* p, const char* fn, bool free_form, int steps) {
-    if (!p->rs_block) {
+    if (!p->rlstop.ws.block) {
         const int n_part = rows4_minmax_partials(p->logN, p->M, 1, 1);
         if (n_part <= 0) return fail(FDR_ERR_STATE, std::string(fn) + ": no inverse row pass for this plan");
-        char* b = nullptr;
-        if (hipMalloc((void**)&b, ((size_t)n_part * 2 + kRegMaxPartials + 1) * sizeof(double)) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(FDR_ERR_ALLOC, std::string(fn) + ": hipMalloc of the workspace failed");
-        }
-        p->rs_block = b;
-        p->rs_part = reinterpret_cast<double*>(b);
-        p->rs_noise = p->rs_part + (size_t)n_part * 2;
-        p->rs_n_part = n_part;
+        const int rc = ensure_workspace(p->rlstop.ws, fn, "workspace", 1,
+                                        [p, n_part](auto& c, int) { layout(c, p->rlstop, (size_t)n_part, (size_t)kRegMaxPartials + 1); });
+        if (rc != FDR_OK) return rc;
+        p->rlstop.n_part = n_part;
     }
-    const int want = steps > kRsTraceSteps ? steps : kRsTraceSteps;
-    if (want > p->rs_trace_cap) {  // a grown trace: only calls that wait for their own end use it, so nothing in flight reads the old one
-        double* t = nullptr;
-        if (hipMalloc((void**)&t, (size_t)want * 2 * sizeof(double)) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(FDR_ERR_ALLOC, std::string(fn) + ": hipMalloc of the trace failed");
-        }
-        (void)hipFree(p->rs_trace);
-        p->rs_trace = t;
-        p->rs_trace_cap = want;
-    }
-    if (free_form && !p->rs_planes) {
-        float* t = nullptr;
-        if (hipMalloc((void**)&t, 2 * (size_t)p->M * p->N * sizeof(float)) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(FDR_ERR_ALLOC, std::string(fn) + ": hipMalloc of the weight planes failed");
-        }
-        p->rs_planes = t;
-    }
-    return FDR_OK;
+    // a grown trace: only calls that wait for their own end use it, so nothing in flight reads the old one
+    int rc = ensure_workspace(p->rlstop.trace_ws, fn, "trace", steps > kRsTraceSteps ? steps : kRsTraceSteps,
+                              [p](auto& c, int n) { layout(c, p->rlstop.trace, 2 * (size_t)n, 8); });
+    if (rc == FDR_OK && free_form)
+        rc = ensure_workspace(p->rlstop.planes_ws, fn, "weight planes", 1, [p](auto& c, int) { layout(c, p->rlstop.planes, 2 * (size_t)p->M * p->N, 16); });
+    return rc;
 }
 
 // The whole call on `s`.  tr: where the device writes the trace (the caller's, the internal one, or null for none).  With a rule
@@ -119,21 +100,21 @@ int auto_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, int
     int rc = FDR_OK;
     if (a.estimate) {
         ScopedPass t(p, s, kPassRsNoise);
-        rc = noise_sigma_dev(d_img, rows, cols, stride, p->rs_noise, &sigma, s);
+        rc = noise_sigma_dev(d_img, rows, cols, stride, p->rlstop.noise, &sigma, s);
         if (rc != FDR_OK) return rc;
     }
     // the start of the form; cur = the plane of u_k (row stride cs), U / us = the two planes of the accelerated estimate
     // free-boundary form with weights: the ratio pass reads d and W (dense copies) and forms dw itself.  Without weights W = 1 and
     // dw = d+: the pass reads the stored dw as its datum and nothing else (max(dw, 0) = dw, the same bits).
     const bool weighted = a.free_form && d_w != nullptr;
-    float* W = weighted ? p->rs_planes : nullptr;
-    const float* D = weighted ? p->rs_planes + (size_t)M * N : p->rf_dw;
+    float* W = weighted ? p->rlstop.planes : nullptr;
+    const float* D = weighted ? p->rlstop.planes + (size_t)M * N : p->rlfree.dw;
     double S = (double)rows * (double)cols;
     float* cur;
     if (a.free_form) {
         const double* sums = nullptr;
         if (weighted)
-            FDR_HIP(hipMemcpy2DAsync(p->rs_planes + (size_t)M * N, (size_t)cols * sizeof(float), d_img, (size_t)stride * sizeof(float),
+            FDR_HIP(hipMemcpy2DAsync(p->rlstop.planes + (size_t)M * N, (size_t)cols * sizeof(float), d_img, (size_t)stride * sizeof(float),
                                      (size_t)cols * sizeof(float), (size_t)rows, hipMemcpyDeviceToDevice, s));
         rc = rlfree_begin(p, d_img, rows, cols, stride, d_w, wstride, a.fp.sigma, W, &sums, s);
         if (rc != FDR_OK) return rc;
@@ -141,25 +122,25 @@ int auto_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, int
             FDR_HIP(hipMemcpyAsync(&S, sums + 1, sizeof(double), hipMemcpyDeviceToHost, s));
             FDR_HIP(hipStreamSynchronize(s));
         }
-        cur = p->rf_u;
+        cur = p->rlfree.u;
     } else {
         rc = rl_init_estimate(p, d_img, rows, cols, stride, d_out, out_stride, s);
         if (rc != FDR_OK) return rc;
         cur = d_out;
     }
-    float* const U[1][2] = {{cur, a.accel ? p->ra_u : cur}};  // a group of one image for rl_accel_steps
+    float* const U[1][2] = {{cur, a.accel ? p->rlaccel.u : cur}};  // a group of one image for rl_accel_steps
     const int us[2] = {a.free_form ? N : out_stride, a.free_form ? N : (a.accel ? cols : out_stride)};
     const int R = a.free_form ? M : rows, C = a.free_form ? N : cols;  // the window the estimate lives on
 
-    const RlFit fit{W, p->rs_part};
+    const RlFit fit{W, p->rlstop.part};
     fdr_plan::Slot* w0 = &p->slots[0];
     int k = 0;  // the step about to run
     auto step = [&](const float* y, int ys, float* out, int os) {
-        int rc2 = a.free_form ? rlfree_step(p, &w0, 1, &y, &out, &D, p->rf_wgt, rows, cols, s, &fit)
+        int rc2 = a.free_form ? rlfree_step(p, &w0, 1, &y, &out, &D, p->rlfree.wgt, rows, cols, s, &fit)
                               : rl_step(p, &w0, 1, &d_img, stride, &y, ys, &out, os, rows, cols, s, &fit);
         if (rc2 == FDR_OK && tr) {
             ScopedPass t(p, s, kPassRsFold);
-            FDR_HIP(launch_rlstop_fold(p->rs_part, p->rs_n_part, tr + 2 * (size_t)k, s));
+            FDR_HIP(launch_rlstop_fold(p->rlstop.part, p->rlstop.n_part, tr + 2 * (size_t)k, s));
         }
         ++k;
         return rc2;
@@ -235,7 +216,7 @@ int fdr_richardson_lucy_auto_f32_dev(fdr_plan* p, const float* d_img, int rows, 
     const bool internal = !d_trace && a.rule != FDR_RL_STOP_NONE;
     rc = auto_prepare(p, fn, a, d_weights != nullptr, internal);
     if (rc != FDR_OK) return rc;
-    return auto_dev_impl(p, fn, d_img, rows, cols, stride, d_weights, wstride, d_out, out_stride, a, d_trace ? d_trace : (internal ? p->rs_trace : nullptr),
+    return auto_dev_impl(p, fn, d_img, rows, cols, stride, d_weights, wstride, d_out, out_stride, a, d_trace ? d_trace : (internal ? p->rlstop.trace : nullptr),
                          result, (hipStream_t)stream);
 }
 
@@ -255,11 +236,11 @@ int fdr_richardson_lucy_auto_f32(fdr_plan* p, const float* img_host, int rows, i
     if (rc != FDR_OK) return rc;
     rc = host_image_call(p, fn, img_host, rows, cols, stride, out_host, a.fp.out_rows, a.fp.out_cols, out_stride,
                          [&](const float* d_in, float* d_out) {
-                             return auto_dev_impl(p, fn, d_in, rows, cols, cols, a.free_form && weights_host ? p->rf_u : nullptr, cols, d_out,
-                                                  a.fp.out_cols, a, internal ? p->rs_trace : nullptr, result, nullptr);
+                             return auto_dev_impl(p, fn, d_in, rows, cols, cols, a.free_form && weights_host ? p->rlfree.u : nullptr, cols, d_out,
+                                                  a.fp.out_cols, a, internal ? p->rlstop.trace : nullptr, result, nullptr);
                          });
     if (rc == FDR_OK && trace_host && result->iterations_done > 0)
-        FDR_HIP(hipMemcpy(trace_host, p->rs_trace, (size_t)result->iterations_done * 2 * sizeof(double), hipMemcpyDeviceToHost));
+        FDR_HIP(hipMemcpy(trace_host, p->rlstop.trace, (size_t)result->iterations_done * 2 * sizeof(double), hipMemcpyDeviceToHost));
     return rc;
 }
 

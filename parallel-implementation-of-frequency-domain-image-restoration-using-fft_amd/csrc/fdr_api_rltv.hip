@@ -23,28 +23,14 @@ const char* const kPassRtFactorCoupled = "RLTV factor (coupled): w / (1 - lambda
 
 namespace fdr {
 
-// 2 g M x N planes (g factors, then g estimates), made by the first call with lambda > 0 for one image and grown by the first batched
-// call on groups of g.  The new block is had before the old one is let go: when it cannot be had the sticky HIP error is cleared and
-// the plan and the workspace it had stay as they were.
+// made by the first call with lambda > 0 for one image and grown by the first batched call on groups of g
 int ensure_rltv_workspace(fdr_plan* p, const char* fn, int group) {
-    if (p->rt_block && p->rt_group >= group) return FDR_OK;
-    const size_t P = (size_t)p->M * p->N;
-    void* blk = nullptr;
-    if (hipMalloc(&blk, 2 * (size_t)group * P * sizeof(float)) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(FDR_ERR_ALLOC, std::string(fn) + ": hipMalloc of the RLTV workspace failed");
-    }
-    if (p->rt_block) (void)hipFree(p->rt_block);  // (waits for the device: nothing queued still uses it)
-    p->rt_block = blk;
-    p->rt_group = group;
-    p->rt_f = static_cast<float*>(blk);
-    p->rt_u = p->rt_f + (size_t)group * P;
-    return FDR_OK;
+    return ensure_workspace(p->rltv.ws, fn, "RLTV workspace", group, [p](auto& c, int g) { layout(c, p->rltv, (size_t)p->M * p->N, g); });
 }
 
 int rltv_factor(fdr_plan* p, const float* u, int rows, int cols, int stride, const float* w, float lambda, float eps, hipStream_t s) {
     ScopedPass t(p, s, kPassRtFactor);
-    FDR_HIP(launch_rltv_factor(u, rows, cols, stride, w, lambda, eps, p->rt_f, stride, s));
+    FDR_HIP(launch_rltv_factor(u, rows, cols, stride, w, lambda, eps, p->rltv.f, stride, s));
     return FDR_OK;
 }
 
@@ -80,7 +66,7 @@ int rltv_check(const fdr_plan* p, const char* fn, const float* img, int rows, in
     return rc;
 }
 
-// the plain form on a launch group of n > 1 images: image k's estimate dense in rt_u + k M N beside its factor in rt_f + k M N, the
+// the plain form on a launch group of n > 1 images: image k's estimate dense in rltv.u + k M N beside its factor in rltv.f + k M N, the
 // routing of rltv_plain_dev per image, one factor launch and one step for the group per iteration
 int rltv_plain_group_dev(fdr_plan* p, const char* fn, const LaunchGroup& g, int rows, int cols, int stride, int out_stride,
                          const fdr_rl_tv_batch_params& prm, const RlTvPrior& tv, hipStream_t s) {
@@ -89,21 +75,21 @@ int rltv_plain_group_dev(fdr_plan* p, const char* fn, const LaunchGroup& g, int 
     const bool norm = prm.norm_area != FDR_NORM_NONE;
     const int fs = norm ? cols : out_stride;
     float *fin[kMaxGroup], *us[kMaxGroup];
-    for (int k = 0; k < g.n; ++k) { fin[k] = norm ? g.ws[k]->raw : g.outs[k]; us[k] = p->rt_u + (size_t)k * P; }
+    for (int k = 0; k < g.n; ++k) { fin[k] = norm ? g.ws[k]->raw : g.outs[k]; us[k] = p->rltv.u + (size_t)k * P; }
     int rc = FDR_OK;
     for (int k = 0; k < g.n && rc == FDR_OK; ++k) rc = rl_init_estimate(p, g.ins[k], rows, cols, stride, n == 0 ? fin[k] : us[k], n == 0 ? fs : cols, s);
     for (int it = 0; it < n && rc == FDR_OK; ++it) {
         const bool last = it == n - 1;
         rc = rltv_factor_group(p, g.n, rows, cols, cols, nullptr, tv, s);
         if (rc == FDR_OK)
-            rc = rl_step(p, g.ws, g.n, g.ins, stride, us, cols, last ? fin : us, last ? fs : cols, rows, cols, s, nullptr, nullptr, it, p->rt_f, P);
+            rc = rl_step(p, g.ws, g.n, g.ins, stride, us, cols, last ? fin : us, last ? fs : cols, rows, cols, s, nullptr, nullptr, it, p->rltv.f, P);
     }
     for (int k = 0; k < g.n && rc == FDR_OK && norm; ++k) rc = rl_normalize(p, fn, fin[k], fs, rows, cols, prm.norm_area, g.outs[k], out_stride, s);
     return rc;
 }
 
-// The plain form.  The weighted update reads the factor at the row stride of u, so u lives dense (row stride cols) in rt_u beside
-// the factor in rt_f; the last update (or, for no iterations, the start) goes to the output, or under a normalisation to the raw
+// The plain form.  The weighted update reads the factor at the row stride of u, so u lives dense (row stride cols) in rltv.u beside
+// the factor in rltv.f; the last update (or, for no iterations, the start) goes to the output, or under a normalisation to the raw
 // plane, from where the normalise pass writes the output: the routing of rl_group_dev.
 int rltv_plain_dev(fdr_plan* p, const char* fn, const float* d_img, int rows, int cols, int stride, float* d_out, int out_stride,
                    const fdr_rl_tv_params& prm, float eps, hipStream_t s) {
@@ -112,31 +98,31 @@ int rltv_plain_dev(fdr_plan* p, const char* fn, const float* d_img, int rows, in
     const bool norm = prm.norm_area != FDR_NORM_NONE;
     float* fin = norm ? w->raw : d_out;
     const int fs = norm ? cols : out_stride;
-    float* u = p->rt_u;
+    float* u = p->rltv.u;
     const float* y = u;
     int rc = rl_init_estimate(p, d_img, rows, cols, stride, n == 0 ? fin : u, n == 0 ? fs : cols, s);
     for (int it = 0; it < n && rc == FDR_OK; ++it) {
         const bool last = it == n - 1;
         float* out = last ? fin : u;
         rc = rltv_factor(p, u, rows, cols, cols, nullptr, prm.lambda, eps, s);
-        if (rc == FDR_OK) rc = rl_step(p, &w, 1, &d_img, stride, &y, cols, &out, last ? fs : cols, rows, cols, s, nullptr, nullptr, it, p->rt_f);
+        if (rc == FDR_OK) rc = rl_step(p, &w, 1, &d_img, stride, &y, cols, &out, last ? fs : cols, rows, cols, s, nullptr, nullptr, it, p->rltv.f);
     }
     if (rc != FDR_OK || !norm) return rc;
     return rl_normalize(p, fn, fin, fs, rows, cols, prm.norm_area, d_out, out_stride, s);
 }
 
-// The free-boundary form: begin and finish of that form, the steps in place in rf_u with factor = wgt / g in the place of wgt.
+// The free-boundary form: begin and finish of that form, the steps in place in rlfree.u with factor = wgt / g in the place of wgt.
 int rltv_free_dev(fdr_plan* p, const char* fn, const float* d_img, int rows, int cols, int stride, const float* d_w, int wstride, float* d_out,
                   int out_stride, const fdr_rl_tv_params& prm, float eps, hipStream_t s) {
     fdr_plan::Slot* w = &p->slots[0];
     const fdr_rlfree_params f = free_params(prm);
     int rc = rlfree_begin(p, d_img, rows, cols, stride, d_w, wstride, f.sigma, nullptr, nullptr, s);
-    float* u = p->rf_u;
+    float* u = p->rlfree.u;
     const float* y = u;
-    const float* dw = p->rf_dw;
+    const float* dw = p->rlfree.dw;
     for (int it = 0; it < prm.iterations && rc == FDR_OK; ++it) {
-        rc = rltv_factor(p, u, p->M, p->N, p->N, p->rf_wgt, prm.lambda, eps, s);
-        if (rc == FDR_OK) rc = rlfree_step(p, &w, 1, &y, &u, &dw, p->rt_f, rows, cols, s);
+        rc = rltv_factor(p, u, p->M, p->N, p->N, p->rlfree.wgt, prm.lambda, eps, s);
+        if (rc == FDR_OK) rc = rlfree_step(p, &w, 1, &y, &u, &dw, p->rltv.f, rows, cols, s);
     }
     if (rc != FDR_OK) return rc;
     return rlfree_finish(p, fn, u, d_out, out_stride, f, s);
@@ -220,9 +206,9 @@ namespace fdr {
 
 int rltv_factor_group(fdr_plan* p, int n, int rows, int cols, int stride, const float* w, const RlTvPrior& tv, hipStream_t s) {
     const size_t P = (size_t)p->M * p->N;
-    if (n < 1 || n > p->rt_group) return fail(FDR_ERR_STATE, "rltv_factor_group: the workspace does not hold the group");
+    if (n < 1 || n > p->rltv.ws.count) return fail(FDR_ERR_STATE, "rltv_factor_group: the workspace does not hold the group");
     ScopedPass t(p, s, tv.coupled ? kPassRtFactorCoupled : kPassRtFactorGroup);
-    FDR_HIP(launch_rltv_factor_group(p->rt_u, P, n, rows, cols, stride, w, tv.lambda, tv.eps, p->rt_f, P, stride, tv.coupled, s));
+    FDR_HIP(launch_rltv_factor_group(p->rltv.u, P, n, rows, cols, stride, w, tv.lambda, tv.eps, p->rltv.f, P, stride, tv.coupled, s));
     return FDR_OK;
 }
 
@@ -257,7 +243,7 @@ int fdr_richardson_lucy_tv_f32(fdr_plan* p, const float* img_host, int rows, int
     if (rc != FDR_OK) return rc;
     const int orows = free_form ? prm.out_rows : rows, ocols = free_form ? prm.out_cols : cols;
     return host_image_call(p, fn, img_host, rows, cols, stride, out_host, orows, ocols, out_stride, [&](const float* d_in, float* d_out) {
-        return rltv_dev_impl(p, fn, d_in, rows, cols, cols, free_form && weights_host ? p->rf_u : nullptr, cols, d_out, ocols, prm, nullptr);
+        return rltv_dev_impl(p, fn, d_in, rows, cols, cols, free_form && weights_host ? p->rlfree.u : nullptr, cols, d_out, ocols, prm, nullptr);
     });
 }
 

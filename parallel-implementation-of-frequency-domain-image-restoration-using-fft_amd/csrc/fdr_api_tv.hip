@@ -26,31 +26,17 @@ const TvPassNames kTvPasses = {
 
 namespace fdr {
 
-// The first TV call of a plan, or the first on a larger group: T (ws_elems float2, zeroed once: the padding between panels is never
-// written) and six M x N planes per image of the group -- x, b and the two pairs of duals of image 0, then those of image 1, ..  For
-// one image this is the block the single-image calls have always had.  The new block is had before the old one is let go (nothing
-// it holds outlives a call but T, which the next call builds again).
+// The first TV call of a plan, or the first on a larger group.  T is zeroed once per block (the padding between panels is never
+// written) and built again by the next call; for one image this is the block the single-image calls have always had.
 int ensure_tv_workspace(fdr_plan* p, const char* fn, int group) {
-    if (p->tv_block && p->tv_group >= group) return FDR_OK;
-    const size_t P = (size_t)p->M * p->N;
-    const size_t t_bytes = (p->ws_elems * sizeof(float2) + 255) & ~(size_t)255;
-    char* blk = nullptr;
-    if (hipMalloc((void**)&blk, t_bytes + (size_t)group * 6 * P * sizeof(float)) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(FDR_ERR_ALLOC, std::string(fn) + ": hipMalloc of the TV workspace failed");
-    }
-    const hipError_t e = hipMemset(blk, 0, t_bytes);
-    if (e != hipSuccess) { (void)hipFree(blk); FDR_HIP(e); }
-    if (p->tv_block) (void)hipFree(p->tv_block);  // (waits for the device: nothing queued still uses it)
-    float* planes = reinterpret_cast<float*>(blk + t_bytes);
-    p->tv_block = blk;
-    p->tv_group = group;
-    p->tv_T = reinterpret_cast<float2*>(blk);
-    p->tv_x = planes;
-    p->tv_b = planes + P;
-    p->tv_w[0][0] = planes + 2 * P; p->tv_w[0][1] = planes + 3 * P;
-    p->tv_w[1][0] = planes + 4 * P; p->tv_w[1][1] = planes + 5 * P;
-    p->tv_gen = 0; p->tv_fr_gen = 0;
+    bool made = false;
+    const int rc = ensure_workspace(p->tv.ws, fn, "TV workspace", group,
+                                    [p](auto& c, int g) { layout(c, p->tv, (size_t)p->M * p->N, p->ws_elems, g); }, &made);
+    if (rc != FDR_OK || !made) return rc;
+    p->tv.gen = 0; p->tv.fr_gen = 0;
+    const hipError_t e = hipMemset(p->tv.T, 0, p->ws_elems * sizeof(float2));
+    if (e != hipSuccess) p->tv.ws.free_with(device_free);  // (no block rather than one whose padding was never cleared)
+    FDR_HIP(e);
     return FDR_OK;
 }
 
@@ -77,12 +63,12 @@ int tv_prepare(fdr_plan* p, const char* fn, int group) {
 // ---- the stages the periodic driver below and the free-boundary driver (fdr_api_tvfree.hip) share, under the form's pass names ----
 
 // T for the data weight `weight` (mu, or nu in the free forms) and rho, unless the plan holds it for this operator PSF already (a
-// table of the frame set, which fdr_tv_deconv_frames_f32* left with tv_gen = 0, is never taken for it)
+// table of the frame set, which fdr_tv_deconv_frames_f32* left with tv.gen = 0, is never taken for it)
 int tv_solve_table(fdr_plan* p, const TvPassNames& names, float weight, float rho, hipStream_t s) {
-    if (p->tv_gen == p->op_gen && p->tv_fr_gen == 0 && p->tv_mu == weight && p->tv_rho == rho) return FDR_OK;
+    if (p->tv.gen == p->op_gen && p->tv.fr_gen == 0 && p->tv.mu == weight && p->tv.rho == rho) return FDR_OK;
     ScopedPass t(p, s, names.table);
-    FDR_HIP(launch_tv_table(p->op_h, p->tv_T, p->lap, p->M, p->N, p->pstride, p->npanels, (double)weight, (double)rho, s));
-    p->tv_gen = p->op_gen; p->tv_fr_gen = 0; p->tv_mu = weight; p->tv_rho = rho;
+    FDR_HIP(launch_tv_table(p->op_h, p->tv.T, p->lap, p->M, p->N, p->pstride, p->npanels, (double)weight, (double)rho, s));
+    p->tv.gen = p->op_gen; p->tv.fr_gen = 0; p->tv.mu = weight; p->tv.rho = rho;
     return FDR_OK;
 }
 
@@ -93,15 +79,15 @@ int tv_prior_half_step(fdr_plan* p, const TvPassNames& names, fdr_plan::Slot* co
     const int M = p->M, N = p->N;
     const size_t step = tv_image_stride(p);
     float *x[kMaxGroup], *rhs[kMaxGroup];
-    for (int k = 0; k < n; ++k) { x[k] = p->tv_x + k * step; rhs[k] = ws[k]->raw; }
-    float* const* w = p->tv_w[it & 1];
-    float* const* nw = p->tv_w[(it + 1) & 1];
+    for (int k = 0; k < n; ++k) { x[k] = p->tv.x + k * step; rhs[k] = ws[k]->raw; }
+    float* const* w = p->tv.w[it & 1];
+    float* const* nw = p->tv.w[(it + 1) & 1];
     {
         ScopedPass t(p, s, coupled ? names.spatial_joint : names.spatial);
-        FDR_HIP(launch_tv_spatial_n(n, p->tv_x, w[0], w[1], p->tv_b, nw[0], nw[1], step, rhs, M, N, weight, rho, anisotropic, coupled, s));
+        FDR_HIP(launch_tv_spatial_n(n, p->tv.x, w[0], w[1], p->tv.b, nw[0], nw[1], step, rhs, M, N, weight, rho, anisotropic, coupled, s));
     }
     int rc = op_rows_fwd_n(p, ws, n, rhs, M, N, N, s);
-    if (rc == FDR_OK) rc = op_cols_table_n(p, ws, n, p->tv_T, names.solve, s);
+    if (rc == FDR_OK) rc = op_cols_table_n(p, ws, n, p->tv.T, names.solve, s);
     if (rc == FDR_OK) rc = op_rows_inv_n(p, ws, n, ROW_OUT_BLUR, names.x, nullptr, 0, nullptr, x, N, M, N, s);
     return rc;
 }
@@ -113,7 +99,7 @@ int tv_output_tail(fdr_plan* p, const char* fn, const TvPassNames& names, fdr_pl
     const size_t step = tv_image_stride(p);
     const float* x[kMaxGroup];
     float* rhs[kMaxGroup];
-    for (int k = 0; k < n; ++k) { x[k] = p->tv_x + k * step; rhs[k] = ws[k]->raw; }
+    for (int k = 0; k < n; ++k) { x[k] = p->tv.x + k * step; rhs[k] = ws[k]->raw; }
     if (norm_area == FDR_NORM_NONE) {
         ScopedPass t(p, s, names.out);
         FDR_HIP(launch_tv_output_n(n, x, N, d_outs, rows, cols, out_stride, nonneg, s));
@@ -133,12 +119,12 @@ int tv_output_tail(fdr_plan* p, const char* fn, const TvPassNames& names, fdr_pl
 // periodic plan.  d is read by the first launches alone (b and the start), so for one image d_out may be d_img.
 int tv_group_dev(fdr_plan* p, const char* fn, fdr_plan::Slot* const* ws, int n, const float* const* d_imgs, int rows, int cols, int stride,
                  float* const* d_outs, int out_stride, const fdr_tv_params& prm, bool coupled, hipStream_t s) {
-    if (n < 1 || n > kMaxGroup || n > p->tv_group) return fail(FDR_ERR_STATE, std::string(fn) + ": the TV workspace does not hold the group");
+    if (n < 1 || n > kMaxGroup || n > p->tv.ws.count) return fail(FDR_ERR_STATE, std::string(fn) + ": the TV workspace does not hold the group");
     const int M = p->M, N = p->N, iters = prm.iterations;
     const size_t step = tv_image_stride(p);
     float *x[kMaxGroup], *b[kMaxGroup], *w0x[kMaxGroup], *w0y[kMaxGroup];
     for (int k = 0; k < n; ++k) {
-        x[k] = p->tv_x + k * step; b[k] = p->tv_b + k * step; w0x[k] = p->tv_w[0][0] + k * step; w0y[k] = p->tv_w[0][1] + k * step;
+        x[k] = p->tv.x + k * step; b[k] = p->tv.b + k * step; w0x[k] = p->tv.w[0][0] + k * step; w0y[k] = p->tv.w[0][1] + k * step;
     }
     int rc = FDR_OK;
     if (iters > 0) {  // T, and b = blur^T(pad(d)) over the whole plan (mu is applied where b is read)

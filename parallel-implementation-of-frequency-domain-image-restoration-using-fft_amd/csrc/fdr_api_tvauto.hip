@@ -49,26 +49,11 @@ int tvauto_check(const fdr_plan* p, const char* fn, const float* img, int rows, 
     return FDR_OK;
 }
 
-// The first auto call of a plan, or the first on a larger group: per image of the group the partials of the three sums, the last
-// step's sums and mu_k, and the partials of the noise estimate once, in a block of its own.  The new block is had before the old one
-// is let go (nothing it holds outlives a call), so on FDR_ERR_ALLOC the plan is what it was.
+// the first auto call of a plan, or the first on a larger group
 int ensure_tvauto_workspace(fdr_plan* p, const char* fn, int group) {
-    if (p->ta_block && p->ta_group >= group) return FDR_OK;
-    const size_t n_part = (size_t)group * 3 * (size_t)tvauto_max_partials(p->M, p->N);
-    const size_t doubles = n_part + 4 * (size_t)group + (size_t)kRegMaxPartials + 1;
-    char* blk = nullptr;
-    if (hipMalloc((void**)&blk, doubles * sizeof(double) + (size_t)group * sizeof(float)) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(FDR_ERR_ALLOC, std::string(fn) + ": hipMalloc of the noise-constrained TV workspace failed");
-    }
-    if (p->ta_block) (void)hipFree(p->ta_block);  // (waits for the device: nothing queued still uses it)
-    p->ta_block = blk;
-    p->ta_group = group;
-    p->ta_part = reinterpret_cast<double*>(blk);
-    p->ta_stat = p->ta_part + n_part;
-    p->ta_noise = p->ta_stat + 4 * (size_t)group;
-    p->ta_mu = reinterpret_cast<float*>(p->ta_noise + kRegMaxPartials + 1);
-    return FDR_OK;
+    return ensure_workspace(p->tvauto.ws, fn, "noise-constrained TV workspace", group, [p](auto& c, int g) {
+        layout(c, p->tvauto, (size_t)tvauto_max_partials(p->M, p->N), (size_t)kRegMaxPartials + 1, g);
+    });
 }
 
 // the free call's workspaces first, then the block of this call
@@ -81,7 +66,7 @@ int tvauto_prepare(fdr_plan* p, const char* fn, int group) {
 // the noise level of one window, as fdr_noise_sigma_f32 estimates it: one launch and one read-back (waits for `s`)
 int tvauto_noise_dev(fdr_plan* p, const float* d_img, int rows, int cols, int stride, double* sigma, hipStream_t s) {
     ScopedPass t(p, s, kPassTaNoise);
-    return noise_sigma_dev(d_img, rows, cols, stride, p->ta_noise, sigma, s);
+    return noise_sigma_dev(d_img, rows, cols, stride, p->tvauto.noise, sigma, s);
 }
 
 }  // namespace fdr
@@ -146,7 +131,7 @@ int fdr_tv_deconv_auto_f32(fdr_plan* p, const float* img_host, int rows, int col
     if (trace_host && n > 0) FDR_HIP(hipMemcpy(trace_host, d_tr.ptr, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost));
     if (result) {
         double st[4] = {0.0, 0.0, 0.0, 0.0};  // (res_c, res_e, mu_k, S) of the last step
-        if (n > 0) FDR_HIP(hipMemcpy(st, p->ta_stat, sizeof st, hipMemcpyDeviceToHost));
+        if (n > 0) FDR_HIP(hipMemcpy(st, p->tvauto.stat, sizeof st, hipMemcpyDeviceToHost));
         *result = fdr_tv_auto_result{sigma, a.tau * sigma * sigma * st[3], st[2], st[0], st[3]};
     }
     return FDR_OK;

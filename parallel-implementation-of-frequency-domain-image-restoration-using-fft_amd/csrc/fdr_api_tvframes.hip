@@ -39,8 +39,8 @@ int tvframes_check(const fdr_plan* p, const char* fn, const TvFramesArgs& a, con
     if (!std::isfinite(prm->background) || prm->background < 0.f) return fail(FDR_ERR_ARG, std::string(fn) + ": background must be finite and >= 0");
     if (prm->data_term == FDR_TV_FRAMES_LEAST_SQUARES && prm->background != 0.f)
         return fail(FDR_ERR_ARG, std::string(fn) + ": background must be 0 with the least-squares data term");
-    if (p->fr_count == 0) return fail(FDR_ERR_STATE, std::string(fn) + ": no frame PSFs set on this plan (call fdr_set_frame_psfs* first)");
-    if (a.count != p->fr_count) return fail(FDR_ERR_ARG, std::string(fn) + ": count is not the number of frame PSFs set (fdr_frame_count)");
+    if (p->frames.count == 0) return fail(FDR_ERR_STATE, std::string(fn) + ": no frame PSFs set on this plan (call fdr_set_frame_psfs* first)");
+    if (a.count != p->frames.count) return fail(FDR_ERR_ARG, std::string(fn) + ": count is not the number of frame PSFs set (fdr_frame_count)");
     if (a.count > 1 && a.img_pitch < window_span(a.rows, a.cols, a.stride)) return fail(FDR_ERR_ARG, std::string(fn) + ": the frames overlap each other (img_pitch)");
     if (a.weights && a.weight_pitch != 0 && a.weight_pitch < window_span(a.rows, a.cols, a.wstride))
         return fail(FDR_ERR_ARG, std::string(fn) + ": weight_pitch must be 0 (one plane for all frames) or at least a window's span");
@@ -52,25 +52,10 @@ int tvframes_check(const fdr_plan* p, const char* fn, const TvFramesArgs& a, con
     return FDR_OK;
 }
 
-// The workspace for `count` frames: the accumulator first (16-byte aligned for the sum kernel), the q planes together, then the
-// c / r planes.  The new block is had before the old one is let go: when it cannot be had the sticky HIP error is cleared and the
-// plan and the workspace it had stay as they were.
+// the workspace for `count` frames
 int ensure_tvframes_workspace(fdr_plan* p, const char* fn, int count) {
-    if (p->tm_block && p->tm_count >= count) return FDR_OK;
-    const size_t P = (size_t)p->M * p->N;
-    const size_t acc_bytes = (p->ws_elems * sizeof(float2) + 255) & ~(size_t)255;
-    char* blk = nullptr;
-    if (hipMalloc((void**)&blk, acc_bytes + 2 * (size_t)count * P * sizeof(float)) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(FDR_ERR_ALLOC, std::string(fn) + ": hipMalloc of the multi-frame TV workspace failed");
-    }
-    if (p->tm_block) (void)hipFree(p->tm_block);  // (waits for the device: nothing queued still uses it)
-    p->tm_block = blk;
-    p->tm_count = count;
-    p->tm_acc = reinterpret_cast<float2*>(blk);
-    p->tm_q = reinterpret_cast<float*>(blk + acc_bytes);
-    p->tm_c = p->tm_q + (size_t)count * P;
-    return FDR_OK;
+    return ensure_workspace(p->tvframes.ws, fn, "multi-frame TV workspace", count,
+                            [p](auto& c, int n) { layout(c, p->tvframes, (size_t)p->M * p->N, p->ws_elems, n); });
 }
 
 // the new block first (nothing old is let go before it is had), then the TV workspace of one image and the Laplacian table
@@ -82,12 +67,12 @@ int tvframes_prepare(fdr_plan* p, const char* fn, int count) {
 
 // T from the K frame tables for nu and rho, unless the plan holds it for this frame set already
 int tvframes_table(fdr_plan* p, int count, float nu, float rho, hipStream_t s) {
-    if (p->tv_fr_gen != 0 && p->tv_fr_gen == p->fr_gen && p->tv_mu == nu && p->tv_rho == rho) return FDR_OK;
+    if (p->tv.fr_gen != 0 && p->tv.fr_gen == p->frames.gen && p->tv.mu == nu && p->tv.rho == rho) return FDR_OK;
     ScopedPass t(p, s, kPassTmTable);
     FrameTables tabs{};
     for (int k = 0; k < count; ++k) tabs.p[k] = frame_table(p, k, false);
-    FDR_HIP(launch_tv_frames_table(tabs, count, p->tv_T, p->lap, p->M, p->N, p->pstride, p->npanels, (double)nu, (double)rho, s));
-    p->tv_gen = 0; p->tv_fr_gen = p->fr_gen; p->tv_mu = nu; p->tv_rho = rho;  // (tv_gen 0: the operator's calls build theirs again)
+    FDR_HIP(launch_tv_frames_table(tabs, count, p->tv.T, p->lap, p->M, p->N, p->pstride, p->npanels, (double)nu, (double)rho, s));
+    p->tv.gen = 0; p->tv.fr_gen = p->frames.gen; p->tv.mu = nu; p->tv.rho = rho;  // (tv.gen 0: the operator's calls build theirs again)
     return FDR_OK;
 }
 
@@ -98,7 +83,7 @@ int tvframes_dev(fdr_plan* p, const char* fn, const TvFramesArgs& a, const fdr_t
     const int M = p->M, N = p->N, rows = a.rows, cols = a.cols, count = a.count, iters = prm.iterations;
     const size_t P = (size_t)M * N;
     const float nu = prm.nu > 0.f ? prm.nu : prm.rho;
-    if (count > p->tm_count || p->tv_group < 1) return fail(FDR_ERR_STATE, std::string(fn) + ": the multi-frame TV workspaces do not hold the frames");
+    if (count > p->tvframes.ws.count || p->tv.ws.count < 1) return fail(FDR_ERR_STATE, std::string(fn) + ": the multi-frame TV workspaces do not hold the frames");
     TvPassNames names = kTfPasses;
     names.table = kPassTmTable;
     fdr_plan::Slot* w0 = &p->slots[0];
@@ -108,8 +93,8 @@ int tvframes_dev(fdr_plan* p, const char* fn, const TvFramesArgs& a, const fdr_t
     {
         ScopedPass t(p, s, kPassTfInit);
         const float* d0 = a.imgs;
-        FDR_HIP(launch_tv_init_n(1, &d0, rows, cols, a.stride, &p->tv_x, &p->tv_w[0][0], &p->tv_w[0][1], M, N, s));
-        if (iters > 0) FDR_HIP(hipMemsetAsync(p->tm_q, 0, (size_t)count * P * sizeof(float), s));  // the frames' q planes lie together
+        FDR_HIP(launch_tv_init_n(1, &d0, rows, cols, a.stride, &p->tv.x, &p->tv.w[0][0], &p->tv.w[0][1], M, N, s));
+        if (iters > 0) FDR_HIP(hipMemsetAsync(p->tvframes.q, 0, (size_t)count * P * sizeof(float), s));  // the frames' q planes lie together
     }
     const int group = launch_group(p, count);
     for (int it = 0; it < iters && rc == FDR_OK; ++it) {
@@ -119,8 +104,8 @@ int tvframes_dev(fdr_plan* p, const char* fn, const TvFramesArgs& a, const fdr_t
             const float *xs[kMaxGroup], *ds[kMaxGroup], *cc[kMaxGroup], *wk[kMaxGroup];
             float *c[kMaxGroup], *q[kMaxGroup];
             for (int k = 0; k < n; ++k) {
-                ws[k] = &p->slots[k]; xs[k] = p->tv_x; ds[k] = a.imgs + (size_t)(i0 + k) * a.img_pitch;
-                c[k] = p->tm_c + (size_t)(i0 + k) * P; q[k] = p->tm_q + (size_t)(i0 + k) * P; cc[k] = c[k];
+                ws[k] = &p->slots[k]; xs[k] = p->tv.x; ds[k] = a.imgs + (size_t)(i0 + k) * a.img_pitch;
+                c[k] = p->tvframes.c + (size_t)(i0 + k) * P; q[k] = p->tvframes.q + (size_t)(i0 + k) * P; cc[k] = c[k];
                 wk[k] = a.weights ? a.weights + (size_t)(i0 + k) * a.weight_pitch : nullptr;
             }
             rc = op_rows_fwd_n(p, ws, n, xs, M, N, N, s);                                         // c_k = blur_k(x) ...
@@ -142,9 +127,9 @@ int tvframes_dev(fdr_plan* p, const char* fn, const TvFramesArgs& a, const fdr_t
             }
             rc = op_rows_fwd_n(p, ws, n, cc, M, N, N, s);                                         // ... b = sum_k blur_k^T(r_k)
             if (rc == FDR_OK) rc = frames_cols(p, ws, n, i0, true, s);
-            if (rc == FDR_OK) rc = frames_sum(p, p->tm_acc, ws, n, i0 == 0, s);
+            if (rc == FDR_OK) rc = frames_sum(p, p->tvframes.acc, ws, n, i0 == 0, s);
         }
-        if (rc == FDR_OK) rc = frames_rows_inv(p, p->tm_acc, ROW_OUT_BLUR, kPassFrBlur, nullptr, 0, nullptr, p->tv_b, N, M, N, s);
+        if (rc == FDR_OK) rc = frames_rows_inv(p, p->tvframes.acc, ROW_OUT_BLUR, kPassFrBlur, nullptr, 0, nullptr, p->tv.b, N, M, N, s);
         if (rc == FDR_OK) rc = tv_prior_half_step(p, names, &w0, 1, it, nu, prm.rho, prm.anisotropic, false, s);
     }
     if (rc != FDR_OK) return rc;

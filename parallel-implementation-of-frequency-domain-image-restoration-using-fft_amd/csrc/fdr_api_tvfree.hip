@@ -65,7 +65,7 @@ int tvfree_prepare(fdr_plan* p, const char* fn, int group) {
 int tvfree_group_dev(fdr_plan* p, const char* fn, fdr_plan::Slot* const* ws, int n, const float* const* d_imgs, int rows, int cols, int stride,
                      const float* d_w, int wstride, float* const* d_outs, int out_stride, const fdr_tv_free_params& prm, bool coupled, hipStream_t s,
                      const TvDataStep& data) {
-    if (n < 1 || n > kMaxGroup || n > p->tv_group || n > p->tf_group || (data.kind == TvDataStep::AUTO && n > p->ta_group))
+    if (n < 1 || n > kMaxGroup || n > p->tv.ws.count || n > p->tvfree.ws.count || (data.kind == TvDataStep::AUTO && n > p->tvauto.ws.count))
         return fail(FDR_ERR_STATE, std::string(fn) + ": the free-boundary TV workspaces do not hold the group");
     const int M = p->M, N = p->N, iters = prm.iterations;
     const size_t P = (size_t)M * N, step = tv_image_stride(p);
@@ -73,8 +73,8 @@ int tvfree_group_dev(fdr_plan* p, const char* fn, fdr_plan::Slot* const* ws, int
     float *x[kMaxGroup], *b[kMaxGroup], *w0x[kMaxGroup], *w0y[kMaxGroup], *q[kMaxGroup], *c[kMaxGroup];
     const float *xc[kMaxGroup], *cc[kMaxGroup], *qc[kMaxGroup];
     for (int k = 0; k < n; ++k) {
-        x[k] = p->tv_x + k * step; b[k] = p->tv_b + k * step; w0x[k] = p->tv_w[0][0] + k * step; w0y[k] = p->tv_w[0][1] + k * step;
-        q[k] = p->tf_q + k * P; c[k] = p->tf_c + k * P;
+        x[k] = p->tv.x + k * step; b[k] = p->tv.b + k * step; w0x[k] = p->tv.w[0][0] + k * step; w0y[k] = p->tv.w[0][1] + k * step;
+        q[k] = p->tvfree.q + k * P; c[k] = p->tvfree.c + k * P;
         xc[k] = x[k]; cc[k] = c[k]; qc[k] = q[k];
     }
     int rc = FDR_OK;
@@ -84,7 +84,7 @@ int tvfree_group_dev(fdr_plan* p, const char* fn, fdr_plan::Slot* const* ws, int
     {
         ScopedPass t(p, s, kPassTfInit);
         FDR_HIP(launch_tv_init_n(n, d_imgs, rows, cols, stride, x, w0x, w0y, M, N, s));
-        if (iters > 0) FDR_HIP(hipMemsetAsync(p->tf_q, 0, (size_t)n * P * sizeof(float), s));  // the group's q planes lie together
+        if (iters > 0) FDR_HIP(hipMemsetAsync(p->tvfree.q, 0, (size_t)n * P * sizeof(float), s));  // the group's q planes lie together
     }
     for (int it = 0; it < iters && rc == FDR_OK; ++it) {
         rc = blur_window_dev_n(p, ws, n, xc, M, N, N, c, N, 0, s, M, N);  // c = blur(x)
@@ -95,11 +95,11 @@ int tvfree_group_dev(fdr_plan* p, const char* fn, fdr_plan::Slot* const* ws, int
                 ScopedPass t(p, s, kPassTaNorm);
                 double* tr[kMaxGroup];
                 for (int k = 0; k < n; ++k) tr[k] = data.trace[k] ? data.trace[k] + 3 * (size_t)it : nullptr;
-                FDR_HIP(launch_tvauto_norm_n(n, cc, qc, d_imgs, stride, d_w, wstride, rows, cols, M, N, p->ta_part, s));
-                FDR_HIP(launch_tvauto_mu_n(n, p->ta_part, tvauto_partials(rows, cols), data.sigma, data.tau, nu, p->ta_mu, p->ta_stat, tr, s));
+                FDR_HIP(launch_tvauto_norm_n(n, cc, qc, d_imgs, stride, d_w, wstride, rows, cols, M, N, p->tvauto.part, s));
+                FDR_HIP(launch_tvauto_mu_n(n, p->tvauto.part, tvauto_partials(rows, cols), data.sigma, data.tau, nu, p->tvauto.mu, p->tvauto.stat, tr, s));
             }
             ScopedPass t(p, s, kPassTaData);
-            FDR_HIP(launch_tvauto_data_n(n, c, q, d_imgs, stride, d_w, wstride, rows, cols, M, N, p->ta_mu, nu, s));
+            FDR_HIP(launch_tvauto_data_n(n, c, q, d_imgs, stride, d_w, wstride, rows, cols, M, N, p->tvauto.mu, nu, s));
             break;
         }
         case TvDataStep::POISSON: {  // the Poisson likelihood: another step on the same window, planes and bytes
@@ -126,23 +126,10 @@ int tvfree_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, i
     return tvfree_group_dev(p, fn, &w, 1, &d_img, rows, cols, stride, d_w, wstride, &d_out, out_stride, prm, false, s, data);
 }
 
-// The first free-boundary TV call of a plan, or the first on a larger group: q and c / r, two M x N planes per image of the group
-// in a block of their own, the q planes first.  The new block is had before the old one is let go (nothing it holds outlives a
-// call), so on FDR_ERR_ALLOC the plan is what it was.
+// the first free-boundary TV call of a plan, or the first on a larger group
 int ensure_tvfree_workspace(fdr_plan* p, const char* fn, int group) {
-    if (p->tf_block && p->tf_group >= group) return FDR_OK;
-    const size_t P = (size_t)p->M * p->N;
-    float* blk = nullptr;
-    if (hipMalloc((void**)&blk, (size_t)group * 2 * P * sizeof(float)) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(FDR_ERR_ALLOC, std::string(fn) + ": hipMalloc of the free-boundary TV workspace failed");
-    }
-    if (p->tf_block) (void)hipFree(p->tf_block);  // (waits for the device: nothing queued still uses it)
-    p->tf_block = blk;
-    p->tf_group = group;
-    p->tf_q = blk;
-    p->tf_c = blk + (size_t)group * P;
-    return FDR_OK;
+    return ensure_workspace(p->tvfree.ws, fn, "free-boundary TV workspace", group,
+                            [p](auto& c, int g) { layout(c, p->tvfree, (size_t)p->M * p->N, g); });
 }
 
 }  // namespace fdr

@@ -124,7 +124,7 @@ int auto_batch_run(fdr_plan* p, const char* fn, const float* d_imgs, size_t img_
         if (rc != FDR_OK) break;
         rc = tvfree_group_dev(p, fn, g.ws, g.n, g.ins, rows, cols, stride, d_w, wstride, g.outs, out_stride, a.fp, coupled, s, au);
         if (rc == FDR_OK && stats && iters > 0) {
-            FDR_HIP(hipMemcpyAsync(stats + 4 * (size_t)i0, p->ta_stat, 4 * (size_t)g.n * sizeof(double), hipMemcpyDeviceToHost, s));
+            FDR_HIP(hipMemcpyAsync(stats + 4 * (size_t)i0, p->tvauto.stat, 4 * (size_t)g.n * sizeof(double), hipMemcpyDeviceToHost, s));
             FDR_HIP(hipStreamSynchronize(s));
         }
     }

@@ -75,7 +75,7 @@ hipError_t frames_sum_n(float* dst, const FrameSrcs& srcs, size_t n_floats, bool
 }  // namespace
 
 hipError_t launch_frames_sum(float* dst, const FrameSrcs& srcs, int n, size_t n_floats, bool accumulate, hipStream_t s) {
-    // (the 16-byte requests need 16-byte aligned bases: the library's own operands, slot spectra and fr_acc, are hipMalloc bases)
+    // (the 16-byte requests need 16-byte aligned bases: the library's own operands, slot spectra and frames.acc, are hipMalloc bases)
     if (!dst || ((uintptr_t)dst & 15) != 0 || n < 1 || n > kMaxGroup || n_floats < 2 || (n_floats & 1) != 0) return hipErrorInvalidValue;
     for (int k = 0; k < n; ++k)
         if (!srcs.p[k] || ((uintptr_t)srcs.p[k] & 15) != 0) return hipErrorInvalidValue;

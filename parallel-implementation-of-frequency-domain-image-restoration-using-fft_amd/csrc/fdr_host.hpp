@@ -5,8 +5,10 @@
 #pragma once
 #include "../../include/fdr.h"
 #include "fdr_kernels.hpp"
+#include "fdr_workspace.hpp"
 
 #include <hip/hip_runtime.h>
+#include <array>
 #include <cstdint>
 #include <cstdio>
 #include <functional>
@@ -91,6 +93,69 @@ struct PassTimer {
     }
 };
 
+// ---- the on-demand workspaces of a plan.  fdr_workspace.hpp has the handle, and per block its pointers and its layout; here one
+// struct per feature adds the handle of every block the feature owns and what the plan remembers about their contents.  Each is
+// made by the feature's first call and kept until fdr_plan_destroy; a block for a group (or for frames) grows on the first use with
+// a larger count, `ws.count` = the images (frames) it holds, and nothing it held outlives the call that grew it.
+inline void* device_alloc(size_t bytes) {
+    void* b = nullptr;
+    if (hipMalloc(&b, bytes) == hipSuccess) return b;
+    (void)hipGetLastError();  // (the failure is reported as FDR_ERR_ALLOC: no sticky error is left behind)
+    return nullptr;
+}
+inline void device_free(void* b) { (void)hipFree(b); }  // (waits for the device: nothing queued still uses an outgrown block)
+// The one routine of every ensure_*: ws for `n` by `layout(carver, n)`, from hipMalloc.  The new block is had before the old one is
+// let go: FDR_ERR_ALLOC, "<fn>: hipMalloc of the <noun> failed", leaves the plan and the block it had intact.  *made: a new block.
+template <class Layout>
+int ensure_workspace(Workspace& ws, const char* fn, const char* noun, int n, Layout&& layout, bool* made = nullptr) {
+    const Workspace::Grown g = ws.grow(n, layout, device_alloc, device_free);
+    if (made) *made = g == Workspace::MADE;
+    if (g == Workspace::NO_MEMORY) return fail(FDR_ERR_ALLOC, std::string(fn) + ": hipMalloc of the " + noun + " failed");
+    if (g == Workspace::BAD_LAYOUT) return fail(FDR_ERR_STATE, std::string(fn) + ": the " + noun + " does not meet the alignments of its layout");
+    return FDR_OK;
+}
+// T was built for (mu, rho) and the operator tables of generation `gen` (0 = not built) or, fr_gen != 0, for the frame tables of
+// that generation (gen is 0 then, so the operator's calls build theirs again); rhs lives in slot k's `raw`
+struct TvWorkspace : TvLayout<float2> { Workspace ws; float mu = 0.f, rho = 0.f; unsigned gen = 0, fr_gen = 0; };
+struct TvFreeWorkspace : TvFreeLayout { Workspace ws; };    // beside the TV workspace, which it shares; its table is tv.T with mu = nu
+struct TvAutoWorkspace : TvAutoLayout { Workspace ws; };    // beside the workspaces of the free form, which it shares
+struct TvFramesWorkspace : TvFramesLayout<float2> { Workspace ws; };  // beside the TV workspace of one image, which it shares
+struct RlFreeWorkspace : RlFreeLayout { Workspace ws; };    // (r lives in slot k's `raw`)
+struct RlAccelWorkspace : RlAccelLayout { Workspace ws; };
+struct RlTvWorkspace : RlTvLayout { Workspace ws; };        // made by the first call with lambda > 0
+// n_part: the workgroups of the plan's inverse row grid; trace: the internal trace, 2 doubles per step of trace_ws.count steps (it
+// grows only when a call with a rule and without the caller's trace asks for more); planes, free-boundary form with weights only:
+// the dense weights W and the dense copy of d that the ratio pass reads beside them
+struct RlStopWorkspace : RlStopLayout {
+    Workspace ws, trace_ws, planes_ws;
+    int n_part = 0;
+    double* trace = nullptr;
+    float* planes = nullptr;
+};
+// tables: made or regrown by fdr_set_frame_psfs* alone, for tables_ws.count frames: frame k's H_k / (M N) at tables + 2 k ws_elems,
+// its conj(H_k) / (M N) ws_elems behind (layout of `filt`); count = the frames of the last set, gen counts the sets.  Only the
+// multi-frame calls read them, nothing else writes them, and they touch neither op_h / op_c, filt nor op_gen.  The block of the
+// calls is made for one frame by fdr_blur_frames_f32_dev, which needs acc only.
+struct FramesWorkspace : FramesLayout<float2> {
+    Workspace ws, tables_ws;
+    float2* tables = nullptr;
+    int count = 0;
+    unsigned gen = 0;
+};
+// w, made by the first free-boundary blind call: the dense weights W (M x N floats), which the coverage of every new PSF and the PSF
+// step's denominator are computed from
+struct BlindWorkspace : BlindLayout<float2> { Workspace ws, w_ws; float* w = nullptr; };
+struct RegWorkspace : RegLayout { Workspace ws; std::vector<double> cand_host, res_host; };  // host copies of cand and res
+// the score table and the per-angle (cos, sin) table grow on demand (their counts: entries); host copies of both
+struct MotionWorkspace : MotionLayout<float2> {
+    Workspace ws, table_ws, trig_ws;
+    float* table = nullptr;
+    double* trig = nullptr;
+    std::vector<float> table_host;
+    std::vector<double> trig_host;
+};
+struct DefocusWorkspace : DefocusLayout { Workspace ws; std::vector<double> trig_host; std::vector<float> profile_host; };  // beside the motion workspace
+
 }  // namespace fdr
 
 struct fdr_plan {
@@ -122,143 +187,26 @@ struct fdr_plan {
     float2* op_c = nullptr;
     bool have_op = false;
     unsigned op_gen = 0;  // counts the fdr_set_operator_psf* calls that rebuilt the tables
-    // total-variation deconvolution (fdr_tv_deconv_f32*): made by the first such call, kept until fdr_plan_destroy -- one allocation
-    // holding the solve table T (ws_elems, layout of `filt`) and six M x N real planes: x, b and two pairs of duals (rhs lives in slot 0's `raw`).
-    // T was built for (tv_mu, tv_rho) and the operator tables of generation tv_gen; tv_gen 0 = not built.  A batched call on groups of
-    // g images (fdr_tv_deconv_batch_f32*) grows it to one T and 6 g planes: tv_group = the images it holds, the six planes of image k
-    // lie 6 k M N floats behind those of image 0 (ensure_tv_workspace, tv_image_stride), its rhs in slot k's `raw`.
-    void* tv_block = nullptr;
-    int tv_group = 0;
-    float2* tv_T = nullptr;
-    float *tv_x = nullptr, *tv_b = nullptr, *tv_w[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};  // tv_w[pair][0 = wx, 1 = wy]
-    float tv_mu = 0.f, tv_rho = 0.f;
-    unsigned tv_gen = 0;
-    // free-boundary TV deconvolution (fdr_tv_deconv_free_f32*): beside the TV workspace for one image, which it shares, one allocation
-    // of two M x N real planes made by the first such call, kept until fdr_plan_destroy: the dual q of the splitting s = blur(x) and
-    // c = blur(x), which the data step turns into r in place.  Its solve table is tv_T with tv_mu = nu.  A batched call on groups of g
-    // images (fdr_tv_deconv_free_batch_f32*) grows it to 2 g planes: tf_group = the images it holds, the g planes q first (image k's
-    // at tf_q + k M N, so that one memset clears a group's), then the g planes c / r (image k's at tf_c + k M N).
-    void* tf_block = nullptr;
-    int tf_group = 0;
-    float *tf_q = nullptr, *tf_c = nullptr;
-    // noise-constrained TV deconvolution (fdr_tv_deconv_auto_f32*): beside the workspaces of the free form, which it shares, one small
-    // allocation made by the first such call, kept until fdr_plan_destroy: the 3 tvauto_max_partials(M, N) double partials of the
-    // norm kernel, the (res_c, res_e, mu_k, S) of the last step, the partials of the noise estimate and the device scalar mu_k.  A
-    // batched call on groups of g images (fdr_tv_deconv_auto_batch_f32*) grows it to g sets: ta_group = the images it holds, image k's
-    // partials at ta_part + k 3 n (n = tvauto_partials of the window), its sums at ta_stat + 4 k, its mu_k at ta_mu + k; the noise
-    // estimate runs one image at a time on the one ta_noise.
-    void* ta_block = nullptr;
-    int ta_group = 0;
-    double* ta_part = nullptr;
-    double* ta_stat = nullptr;   // 4 doubles
-    double* ta_noise = nullptr;  // kRegMaxPartials + 1 doubles
-    float* ta_mu = nullptr;
-    // motion-blur estimate (fdr_cepstrum_f32*, fdr_estimate_motion_f32*): made by the first such call, kept until fdr_plan_destroy --
-    // one allocation holding the M x N complex plane, the pad partials + their sum, the Hann tables (M + N); the score table and the
-    // per-angle (cos, sin) table grow on demand.  Host copies of the table and the trig table are kept here too.
-    void* mo_block = nullptr;
-    float2* mo_plane = nullptr;
-    double* mo_part = nullptr;  // motion_pad_partials(M, N) partials, then their sum
-    float* mo_hann = nullptr;
-    float* mo_table = nullptr;
-    double* mo_trig = nullptr;
-    size_t mo_table_cap = 0, mo_trig_cap = 0;  // elements
-    std::vector<float> mo_table_host;
-    std::vector<double> mo_trig_host;
-    // defocus estimate (fdr_estimate_defocus_f32*, fdr_estimate_blur_f32*): beside the motion workspace, which it shares, one allocation
-    // of fixed size made by the first such call: the trig table (2 kDefocusMaxAngles doubles), then the profile T (kDefocusMaxDiameters floats)
-    void* df_block = nullptr;
-    double* df_trig = nullptr;
-    float* df_profile = nullptr;
-    std::vector<double> df_trig_host;
-    std::vector<float> df_profile_host;
-    // free-boundary Richardson-Lucy (fdr_richardson_lucy_free_f32*): made by the first such call, kept until fdr_plan_destroy -- one
-    // allocation holding three M x N real planes (the estimate u, wgt = 1 / coverage, dw = weights . max(d, 0) on the window) and the
-    // 2 rlfree_partials(M, N) + 2 double partials of the two sums (r lives in slot 0's `raw`).  A batched call on groups of g images
-    // (fdr_richardson_lucy_batch_f32*) grows it to 1 + 2 g planes and g sets of partials: rf_group = the images it holds
-    // (ensure_rlfree_workspace; rlfree_u_plane, rlfree_dw_plane, rlfree_part for image k > 0)
-    void* rf_block = nullptr;
-    int rf_group = 0;
-    float *rf_u = nullptr, *rf_wgt = nullptr, *rf_dw = nullptr;
-    double* rf_part = nullptr;
-    // accelerated Richardson-Lucy, both forms (fdr_richardson_lucy_accel_f32*, fdr_richardson_lucy_free_accel_f32*): made by the
-    // first such call, kept until fdr_plan_destroy -- one allocation holding three M x N real planes (the extrapolated point y, the
-    // second plane of the estimate, the direction g), the 2 rlaccel_partials(M, N) double partials and alpha.  A batched call on groups
-    // of g images (fdr_richardson_lucy_batch_accel_f32*) grows it to g of each: ra_group = the images it holds; the partials and the
-    // alphas of the group follow ra_part and ra_alpha, the planes of image k > 0 lie at ra_more (rlaccel_y_plane, _u_plane, _g_plane)
-    void* ra_block = nullptr;
-    int ra_group = 0;
-    float* ra_more = nullptr;
-    float *ra_y = nullptr, *ra_u = nullptr, *ra_g = nullptr;
-    double* ra_part = nullptr;
-    float* ra_alpha = nullptr;
-    // Richardson-Lucy with a total-variation prior (fdr_richardson_lucy_tv_f32*): made by the first such call with lambda > 0, kept until
-    // fdr_plan_destroy -- one allocation of two M x N float planes: the factor w / g of the step and the plain form's estimate (dense
-    // rows x cols; the free-boundary form keeps its estimate in rf_u).  A batched call on groups of g images
-    // (fdr_richardson_lucy_tv_batch_f32*) grows it to 2 g planes: rt_group = the images it holds, the g factor planes first (image k's
-    // at rt_f + k M N), then the g estimates (image k's at rt_u + k M N, in both forms: a group's estimates lie one pitch apart)
-    void* rt_block = nullptr;
-    int rt_group = 0;
-    float *rt_f = nullptr, *rt_u = nullptr;
-    // multi-frame Richardson-Lucy (fdr_set_frame_psfs*, fdr_blur_frames_f32_dev, fdr_richardson_lucy_frames_f32*).  fr_tables: one
-    // allocation of 2 fr_cap ws_elems float2, made or regrown by the setter alone: frame k's H_k / (M N) at fr_tables + 2 k ws_elems,
-    // its conj(H_k) / (M N) ws_elems behind (layout of `filt`); fr_count = the frames of the last set.  Only the multi-frame calls
-    // read them (these and fdr_tv_deconv_frames_f32*), nothing else writes them, and they touch neither op_h / op_c, filt nor
-    // op_gen (a new set outdates a TV table built from the old one: fr_gen below).  fr_block: the workspace of the calls, made on first
-    // use and grown for a larger count (fr_ws_count = the frames it holds): the accumulator spectrum fr_acc (ws_elems), the planes
-    // fr_u, fr_wgt (M x N) and fr_ws_count planes dw (frame k's at fr_dw + k M N), then per frame the 2 rlfree_partials(M, N) + 2
-    // doubles of its sums (frames_part) and the folded pair fr_sums.  fdr_blur_frames_f32_dev needs fr_acc only and makes the block
-    // for one frame.
-    float2* fr_tables = nullptr;
-    int fr_cap = 0, fr_count = 0;
-    void* fr_block = nullptr;
-    int fr_ws_count = 0;
-    float2* fr_acc = nullptr;
-    float *fr_u = nullptr, *fr_wgt = nullptr, *fr_dw = nullptr;
-    double *fr_part = nullptr, *fr_sums = nullptr;
-    // multi-frame TV deconvolution (fdr_tv_deconv_frames_f32*): beside the TV workspace of one image, which it shares (x, b, the duals
-    // and T), one allocation made on first use and grown for a larger count (tm_count = the frames it holds): the accumulator spectrum
-    // tm_acc (ws_elems), then the tm_count planes q (frame k's at tm_q + k M N, so that one memset clears them), then the tm_count
-    // planes c / r (frame k's at tm_c + k M N).  fr_gen counts the fdr_set_frame_psfs* calls; tv_fr_gen says whose table tv_T holds:
-    // 0 the operator's (then tv_gen, tv_mu and tv_rho describe it), else the frame tables' of generation tv_fr_gen, built for nu =
-    // tv_mu and tv_rho (tv_gen is 0 then, so the operator's calls build theirs again).
-    unsigned fr_gen = 0, tv_fr_gen = 0;
-    void* tm_block = nullptr;
-    int tm_count = 0;
-    float2* tm_acc = nullptr;
-    float *tm_q = nullptr, *tm_c = nullptr;
-    // stopping Richardson-Lucy from the data (fdr_richardson_lucy_auto_f32*): made by the first such call, kept until fdr_plan_destroy
-    // -- rs_block holds the (res, kl) partials of the ratio pass (one double2 per workgroup of the plan's inverse row grid) and the
-    // partials of the noise estimate; rs_trace the internal trace (2 rs_trace_cap doubles; it grows only when a call with a rule and
-    // without the caller's trace asks for more steps); rs_planes, free-boundary form with weights only, two M x N planes: the dense weights W
-    // and the dense copy of d that the ratio pass reads beside them
-    void* rs_block = nullptr;
-    double* rs_part = nullptr;
-    double* rs_noise = nullptr;  // kRegMaxPartials + 1 doubles
-    int rs_n_part = 0;
-    double* rs_trace = nullptr;
-    int rs_trace_cap = 0;
-    float* rs_planes = nullptr;
-    // blind Richardson-Lucy (fdr_richardson_lucy_blind_f32*): made by the first such call, kept until fdr_plan_destroy -- bl_block holds
-    // the table conj(U) / (M N) of the image (ws_elems, layout of `filt`), four PSF planes of kBlindMaxPsf floats (the PSF p_k, num, den
-    // and the staging of the host form's PSF) and the status word; bl_w, made by the first free-boundary blind call, the dense weights
-    // W (M x N floats), which the coverage of every new PSF and the PSF step's denominator are computed from
-    void* bl_block = nullptr;
-    float2* bl_table = nullptr;
-    float *bl_p = nullptr, *bl_num = nullptr, *bl_den = nullptr, *bl_stage = nullptr;
-    int* bl_status = nullptr;
-    float* bl_w = nullptr;
-    // choosing the regularisation weight (fdr_reg_curve_f32*, fdr_choose_reg_f32*): made by the first such call, kept until
-    // fdr_plan_destroy -- one allocation holding the power plane (ws_elems floats in the layout of `filt`, one float per bin, then the
-    // two extra floats of the packed column), the partials of the sweep and of the noise sum, and the candidate and result arrays
-    // (kRegMaxCurve pairs each); host copies of the last two are kept here too
-    void* rg_block = nullptr;
-    float* rg_power = nullptr;  // ws_elems + 2 floats
-    double* rg_part = nullptr;  // reg_curve_partials(M, npanels) * 2 kRegCandidates doubles
-    double* rg_noise = nullptr; // kRegMaxPartials + 1 doubles
-    double* rg_cand = nullptr;  // kRegMaxCurve (K, gamma) pairs
-    double* rg_res = nullptr;   // kRegMaxCurve (rho, trace) pairs
-    std::vector<double> rg_cand_host, rg_res_host;
+    // the on-demand workspaces, one member per feature (the structs above; fdr_workspace.hpp says what each block holds)
+    fdr::TvWorkspace tv;              // fdr_tv_deconv_f32*, and x, b, the duals and T of every other TV form
+    fdr::TvFreeWorkspace tvfree;      // fdr_tv_deconv_free_f32*
+    fdr::TvAutoWorkspace tvauto;      // fdr_tv_deconv_auto_f32*
+    fdr::TvFramesWorkspace tvframes;  // fdr_tv_deconv_frames_f32*
+    fdr::RlFreeWorkspace rlfree;      // fdr_richardson_lucy_free_f32*
+    fdr::RlAccelWorkspace rlaccel;    // fdr_richardson_lucy_accel_f32*, fdr_richardson_lucy_free_accel_f32*
+    fdr::RlTvWorkspace rltv;          // fdr_richardson_lucy_tv_f32*
+    fdr::RlStopWorkspace rlstop;      // fdr_richardson_lucy_auto_f32*
+    fdr::FramesWorkspace frames;      // fdr_set_frame_psfs*, fdr_blur_frames_f32_dev, fdr_richardson_lucy_frames_f32*
+    fdr::BlindWorkspace blind;        // fdr_richardson_lucy_blind_f32*
+    fdr::RegWorkspace reg;            // fdr_reg_curve_f32*, fdr_choose_reg_f32*
+    fdr::MotionWorkspace motion;      // fdr_cepstrum_f32*, fdr_estimate_motion_f32*
+    fdr::DefocusWorkspace defocus;    // fdr_estimate_defocus_f32*, fdr_estimate_blur_f32*
+    // every block of the members above, for fdr_plan_destroy: a block that a feature gains is added here, beside its member
+    std::array<fdr::Workspace*, 19> workspaces() {
+        return {&tv.ws, &tvfree.ws, &tvauto.ws, &tvframes.ws, &rlfree.ws, &rlaccel.ws, &rltv.ws, &rlstop.ws,
+                &rlstop.trace_ws, &rlstop.planes_ws, &frames.ws, &frames.tables_ws, &blind.ws, &blind.w_ws, &reg.ws,
+                &motion.ws, &motion.table_ws, &motion.trig_ws, &defocus.ws};
+    }
     // sectioned restoration (fdr_restore_tiled_f32*): the host copy of the last call's weight tables (one entry per picture row, then one
     // per picture column), kept here while the upload may still read it; everything else of such a call lies in the caller's workspace
     std::vector<fdr::TiledCover> tl_tab_host;
@@ -485,7 +433,7 @@ int rl_group_dev(fdr_plan* p, const char* fn, fdr_plan::Slot* const* ws, int n, 
 // d_alphas + k alpha_pitch when d_alphas is not null.
 int rl_group_accel_dev(fdr_plan* p, const char* fn, fdr_plan::Slot* const* ws, int n, const float* const* d_imgs, int rows, int cols, int stride,
                        float* const* d_outs, int out_stride, int iterations, int norm_area, float* d_alphas, size_t alpha_pitch, hipStream_t s);
-// the free-boundary workspace for `group` images (1 + 2 group planes); FDR_ERR_ALLOC leaves the plan and the workspace it had intact
+// the free-boundary workspace for `group` images (ensure_workspace)
 int ensure_rlfree_workspace(fdr_plan* p, const char* fn, int group = 1);
 int rlfree_check(const fdr_plan* p, const char* fn, const float* img, int rows, int cols, int stride, const float* weights, int wstride,
                  const float* out, int out_stride, const fdr_rlfree_params* prm, PlanNeed need = NEED_OPERATOR_PSF);
@@ -498,16 +446,16 @@ int stage_weights(fdr_plan* p, const float* weights_host, int rows, int cols, in
 int rlfree_step(fdr_plan* p, fdr_plan::Slot* const* ws, int n, const float* const* ys, float* const* outs, const float* const* datums,
                 const float* wgt, int rows, int cols, hipStream_t s, const RlFit* fit = nullptr, const RlHooks* hooks = nullptr, int it = 0,
                 size_t wgt_pitch = 0);
-// begin, image 0 of a call: the setup (dw into rf_dw, W = pad(m) into rf_u, copied dense to keep_w when that is not null), the
-// coverage alpha = fullblur^T(W) and the start (rf_wgt = 1 / alpha, u_0 in rf_u); *sums, when not null, is where the device holds
-// (sum dw, sum W).  d_w may be rf_u itself (stage_weights).
+// begin, image 0 of a call: the setup (dw into rlfree.dw, W = pad(m) into rlfree.u, copied dense to keep_w when that is not null), the
+// coverage alpha = fullblur^T(W) and the start (rlfree.wgt = 1 / alpha, u_0 in rlfree.u); *sums, when not null, is where the device holds
+// (sum dw, sum W).  d_w may be rlfree.u itself (stage_weights).
 int rlfree_begin(fdr_plan* p, const float* d_img, int rows, int cols, int stride, const float* d_w, int wstride, float sigma, float* keep_w,
                  const double** sums, hipStream_t s);
 // finish: the output window of the dense M x N estimate u, cropped or normalised, into d_out
 int rlfree_finish(fdr_plan* p, const char* fn, const float* u, float* d_out, int out_stride, const fdr_rlfree_params& prm, hipStream_t s);
 // `tv` of rlfree_batch_dev, the TV prior of fdr_api_rltv.hip (launch groups of more than one image, no hooks, not accelerated; needs
-// the prior's workspace for the group): image k's estimate lives in rt_u + k M N, and every step is preceded by one factor launch for
-// the group and takes factor_k = wgt / g_k, at rt_f + k M N, in the place of wgt.  `coupled`: the images are the channels of one
+// the prior's workspace for the group): image k's estimate lives in rltv.u + k M N, and every step is preceded by one factor launch for
+// the group and takes factor_k = wgt / g_k, at rltv.f + k M N, in the place of wgt.  `coupled`: the images are the channels of one
 // picture and share the prior's norm.
 struct RlTvPrior { float lambda, eps; bool coupled; };
 // the free-boundary form on a checked batch of `count` images with its workspace (for launch_group(p, count) images): begin, steps in
@@ -519,10 +467,10 @@ int rlfree_batch_dev(fdr_plan* p, const char* fn, const float* d_imgs, size_t im
                      const RlHooks* hooks = nullptr, float* keep_w = nullptr, bool accel = false, float* d_alphas = nullptr,
                      size_t alpha_pitch = 0, const RlTvPrior* tv = nullptr);
 // ---- the TV prior of Richardson-Lucy (fdr_api_rltv.hip) ----
-// the factor launch of a group: the n planes rows x cols (row stride `stride`) at rt_u + k M N to rt_f + k M N (same stride), w the group's
+// the factor launch of a group: the n planes rows x cols (row stride `stride`) at rltv.u + k M N to rltv.f + k M N (same stride), w the group's
 int rltv_factor_group(fdr_plan* p, int n, int rows, int cols, int stride, const float* w, const RlTvPrior& tv, hipStream_t s);
 // what the multi-frame call (fdr_api_frames.hip) shares with the single one: the prior's workspace (2 group planes; it grows as the
-// others do), the refusal of a bad lambda or eps, and the factor launch of one image: u (rows x cols, row stride `stride`) and w to rt_f
+// others do), the refusal of a bad lambda or eps, and the factor launch of one image: u (rows x cols, row stride `stride`) and w to rltv.f
 int ensure_rltv_workspace(fdr_plan* p, const char* fn, int group = 1);
 int prior_check(const char* fn, float lambda, float eps);
 int rltv_factor(fdr_plan* p, const float* u, int rows, int cols, int stride, const float* w, float lambda, float eps, hipStream_t s);
@@ -538,9 +486,7 @@ int rl_batch_run(fdr_plan* p, const char* fn, const float* d_imgs, size_t img_pi
 int noise_sigma_dev(const float* d_img, int rows, int cols, int stride, double* part, double* sigma, hipStream_t s);
 int noise_window_check(const char* fn, int rows, int cols, int stride);
 // ---- accelerated Richardson-Lucy (fdr_api_rlaccel.hip), shared by the plain and the free-boundary form ----
-// the workspace of the accelerated calls for `group` images: per image three M x N planes, 2 rlaccel_partials(M, N) doubles and one
-// alpha.  It grows on the first use with a larger group; FDR_ERR_ALLOC, sticky HIP error cleared, leaves the plan and the workspace
-// it had intact.  Image 0's planes, partials and alpha are ra_y, ra_u, ra_g, ra_part and ra_alpha.
+// the workspace of the accelerated calls for `group` images (ensure_workspace)
 int ensure_rlaccel_workspace(fdr_plan* p, const char* fn, int group = 1);
 // image k of a group: the extrapolated point y, the second plane of its estimate, its direction g
 float* rlaccel_y_plane(const fdr_plan* p, int k);
@@ -571,9 +517,8 @@ static_assert(kRegMaxCurve % kRegCandidates == 0, "the last sweep reads kRegCand
 // everything a TV call refuses for one image, before any device work
 int tv_check(const fdr_plan* p, const char* fn, int rows, int cols, int stride, int out_stride, const fdr_tv_params* prm,
              PlanNeed need = NEED_OPERATOR_PSF);
-// the TV workspace for `group` images (T and 6 group planes) and the Laplacian table, both synchronous and on first use only.  The
-// workspace grows on the first use with a larger group (T is then built again by the next call); FDR_ERR_ALLOC, sticky HIP error
-// cleared, leaves the plan and the workspace it had intact.
+// the TV workspace for `group` images (ensure_workspace; a new block's T is built again by the next call) and the Laplacian table,
+// both synchronous and on first use only
 int ensure_tv_workspace(fdr_plan* p, const char* fn, int group = 1);
 int tv_prepare(fdr_plan* p, const char* fn, int group = 1);
 inline size_t tv_image_stride(const fdr_plan* p) { return (size_t)6 * p->M * p->N; }
@@ -599,8 +544,7 @@ int tv_group_dev(fdr_plan* p, const char* fn, fdr_plan::Slot* const* ws, int n, 
 int tv_dev_impl(fdr_plan* p, const char* fn, const float* d_img, int rows, int cols, int stride, float* d_out, int out_stride,
                 const fdr_tv_params& prm, hipStream_t s);
 // ---- free-boundary TV deconvolution (fdr_api_tvfree.hip) ----
-// the 2 group planes of the free form (grows on the first use with a larger group, the new block had before the old one is let
-// go); FDR_ERR_ALLOC, sticky HIP error cleared, leaves the plan as it was
+// the 2 group planes of the free form (ensure_workspace)
 int ensure_tvfree_workspace(fdr_plan* p, const char* fn, int group = 1);
 // everything a free-boundary TV call refuses, before any device work; the workspaces of a call (the two planes first, then the
 // periodic call's for one image and the Laplacian table)
@@ -626,7 +570,7 @@ struct TvDataStep {
 };
 inline TvDataStep tv_data_auto(double tau) { TvDataStep d{}; d.kind = TvDataStep::AUTO; d.tau = tau; return d; }
 inline TvDataStep tv_data_poisson(float background) { TvDataStep d{}; d.kind = TvDataStep::POISSON; d.background = background; return d; }
-// the workspaces of an auto call for `group` images: the free call's, then the ta_ block (ensure_tvauto_workspace: it grows as the
+// the workspaces of an auto call for `group` images: the free call's, then the auto block (ensure_tvauto_workspace: it grows as the
 // free call's does); the auto call's own arguments (sigma, tau, nu) checked and nu resolved into *fp, the free call's parameters
 struct TvAutoArgs {
     fdr_tv_free_params fp;  // the free call's, with nu resolved; mu is a placeholder
@@ -644,7 +588,7 @@ int tvauto_noise_dev(fdr_plan* p, const float* d_img, int rows, int cols, int st
 // windows by every data step.  Per iteration one blur, the window launches, one adjoint blur, one spatial launch and the three solve
 // passes, each over the n images; then the output (and the per-image normalisation).  `data` selects the data step, each kind
 // under its own pass name; every other pass, workspace and table is the same for all.  The AUTO step takes image k's weight from the
-// norm and mu launches before it, and the ta_ block must hold the group.  `coupled`: the images are the channels of one picture and
+// norm and mu launches before it, and the auto block must hold the group.  `coupled`: the images are the channels of one picture and
 // share the shrinkage (isotropic only); everything else stays per image.  One image, uncoupled, makes the launches and the bits the
 // single-image calls have always made.
 int tvfree_group_dev(fdr_plan* p, const char* fn, fdr_plan::Slot* const* ws, int n, const float* const* d_imgs, int rows, int cols, int stride,
@@ -680,7 +624,7 @@ int motion_args(const fdr_plan* p, const char* fn, int rows, int cols, int strid
                 const char* what = "length");
 // the fixed part of the workspace (first call on the plan)
 int ensure_motion_workspace(fdr_plan* p, const char* fn);
-// c (scaled by 1 / (M N) already) in the real parts of mo_plane, and sum |x| in mo_part[motion_pad_partials]
+// c (scaled by 1 / (M N) already) in the real parts of motion.plane, and sum |x| in motion.part[motion_pad_partials]
 int motion_cepstrum_plane(fdr_plan* p, const float* d_img, int rows, int cols, int stride, hipStream_t s);
 // the search on the plane, in three steps around the cepstrum: prepare (before it: the table grown to `a`, the trig table uploaded),
 // launch (after it: the score gather, the table to d_scores when that is not null and to the host copy, asynchronous on `s`) and,
