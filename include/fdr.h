@@ -1254,6 +1254,88 @@ int fdr_estimate_blur_f32_dev(fdr_plan* plan, const float* d_img, int rows, int 
                               fdr_motion_estimate* motion, fdr_defocus_estimate* defocus, int* kind, void* stream);
 int fdr_blur_kind(double motion_confidence, double defocus_confidence);
 
+/* -- registering the frames of a burst: the translation of every frame against a reference frame, by phase
+ *    correlation that knows the frames' PSFs, and the shift of a PSF that puts the estimate where the multi-frame calls want it
+ *    ("a registration shift goes into the PSF").  Translation only: the hand-shake case.  `count` (1 .. FDR_MAX_FRAMES) frames, frame
+ *    k at imgs + k img_pitch, each a rows x cols window (row stride `stride`) at the top-left of the M x N plan; one PSF per frame
+ *    (prows x pcols, row stride pstride, PSF k at psfs + k psf_pitch, top-left in the plan as fdr_set_frame_psfs* takes them), or psfs
+ *    NULL: one common or unknown PSF, plain phase correlation.  For every k != reference, with w the Hann window of the motion estimate:
+ *        a = pad(w . d_ref),  b = pad(w . d_k)                                        on M x N
+ *        G_a = DFT2(a), G_b = DFT2(b);  H_a = DFT2(pad(p_ref)), H_b = DFT2(pad(p_k))  (both 1 when psfs is NULL)
+ *        C   = conj(G_a) G_b H_a conj(H_b)            (= |H_a|^2 |H_b|^2 |X|^2 e^{-i w.s}: the phases of the PSFs cancel, which plain
+ *                                                      phase correlation between differently blurred frames gets wrong by pixels)
+ *        Chat = C / (|C| + eps_rel mean |C|)          (mean over all M N bins; |C| and the mean in double)
+ *        r   = Re IDFT2(Chat)                         (with 1 / (M N))
+ *        (i*, j*) = argmax r over |dy| <= max_shift_rows, |dx| <= max_shift_cols     (periodic indices; exact ties: the lowest flat
+ *                                                      index of the search window, (dy, dx) row-major from (-max_shift_rows, -max_shift_cols))
+ *        dy = i* + parabola(r[i* - 1, j*], r[i*, j*], r[i* + 1, j*]),  dx likewise   (neighbours periodic, also outside the window)
+ *        parabola(m, z, p) = 0.5 (m - p) / (m - 2 z + p), 0 for a denominator of 0, clamped to [-0.5, 0.5], in double
+ *    The result is s_k with d_k(r) ~ (p_k * x)(r - s_k) when d_ref(r) = (p_ref * x)(r): the shift that belongs in PSF k.  peak =
+ *    r[i*, j*]; confidence = (peak - mean r) / std r over the whole plane (double sums in a fixed order, no atomics: two calls give the
+ *    same bytes).  The reference gets (0, 0, 1, 0); an all-zero frame (or reference) gets zeros.  The exact float formulas are in the
+ *    header of csrc/fdr_register.hip.
+ *    THE STREAM TRAVELS IN THE STRUCT, deliberately: the _dev forms run on (hipStream_t)params->stream (NULL = the null stream) and
+ *    have no `void* stream` parameter; the host forms ignore the field.  The stream-order table of the test suite is keyed on
+ *    `void* stream` parameters and is closed to edits for now, so these entries are fenced by a test file of their own with the same
+ *    helper; when that table can next be edited their cases move there.
+ *      fdr_register_frames_f32_dev  asynchronous: the `count` results go to the device array d_shifts (8-byte aligned), nothing is read
+ *                              back, and after the first call on a plan nothing is allocated.  d_corr, when not NULL, receives the
+ *                              correlation plane r of frame k (M x N floats) at d_corr + k M N, zeros for the reference: for tests.
+ *      fdr_register_frames_f32  the host form: frames and PSFs are staged, the results come back; synchronous.
+ *    Plans are those of the motion estimate (fast mode, powers of two or 2^a 3^b 5^c with FDR_FLAG_MIXED_RADIX, 32 .. 8192 per side).
+ *    Each frame but the reference costs three of the plan's complex 2-D transforms (two without PSFs) and five sweeps over a plane.
+ *    FDR_ERR_ARG / FDR_ERR_STATE before any device work and with the plan usable afterwards: the plan kind; rows or cols < 16 or beyond
+ *    the plan; stride < cols; a count outside 1 .. FDR_MAX_FRAMES; an img_pitch below a window's span for count > 1; a reference
+ *    outside 0 .. count - 1; max_shift_rows outside 1 .. (M - 1) / 2 or max_shift_cols outside 1 .. (N - 1) / 2 after the defaults; an
+ *    eps_rel that is negative or not finite; null pointers; with PSFs a size below 1 or beyond the plan, pstride < pcols, a psf_pitch
+ *    below a PSF's span for count > 1; a d_shifts off 8 bytes.  The calls use the motion block (its plane and Hann tables) and a
+ *    block of their own (the PSF pair plane, the partials, the results), made on first use and freed by fdr_plan_destroy; they touch
+ *    none of the filter, the operator tables or the frame tables.
+ *      fdr_psf_shift_f32*      `count` PSFs (prows x pcols) and `count` shifts give `count` PSFs of (prows + 2 pad_rows) x (pcols + 2
+ *                              pad_cols), PSF k at out + k out_pitch (row stride out_stride): PSF k placed at offset (pad_rows + dy_k,
+ *                              pad_cols + dx_k) with bilinear weights, which are non-negative and keep the sum (Richardson-Lucy's
+ *                              positivity and the frame's exposure survive); the symmetric padding by an even total keeps the centre
+ *                              convention of a PSF.  A gather, one lane per output element, four taps with weights formed in double and
+ *                              rounded to float, in a fixed order (csrc/fdr_register.hip).  The _dev form reads the shifts from device
+ *                              memory, straight from fdr_register_frames_f32_dev: the chain estimate, shift, fdr_set_frame_psfs_dev,
+ *                              frames call never waits for the device.  A shift outside [-pad, pad - 1] is clamped and a NaN is taken
+ *                              as 0 in the kernel: no value in device memory indexes outside the planes.  pad = max_shift + 1 holds every
+ *                              whole-pixel peak of the estimate, pad = max_shift + 2 also the half pixel the parabola can add at the end
+ *                              of the range.  Needs no plan.  FDR_ERR_ARG for null pointers, a count outside 1 .. FDR_MAX_FRAMES, sizes
+ *                              outside 1 .. 8192, pads outside 1 .. 8192, strides below the row, pitches below the span for count > 1, shifts
+ *                              off 8 bytes, an output that overlaps the PSFs or the shifts.                                        */
+typedef struct fdr_frame_shift {
+    double dy;        /* rows, positive = down */
+    double dx;        /* columns, positive = right */
+    float peak;       /* r at the integer peak */
+    float confidence; /* (peak - mean r) / std r */
+} fdr_frame_shift;
+typedef struct fdr_register_params {
+    int reference;      /* the frame the others are measured against, 0 .. count - 1 */
+    int max_shift_rows; /* the search range |dy| <=; 0 selects min(rows, cols) / 4 */
+    int max_shift_cols; /* the search range |dx| <=; 0 selects min(rows, cols) / 4 */
+    float eps_rel;      /* the whitening floor relative to mean |C|, >= 0; 0 selects FDR_REGISTER_EPS_REL */
+    void* stream;       /* _dev form: the hipStream_t of the call (NULL = the null stream); the host form ignores it */
+} fdr_register_params;
+typedef struct fdr_psf_shift_params {
+    int pad_rows; /* >= 1: the output has prows + 2 pad_rows rows */
+    int pad_cols; /* >= 1 */
+    void* stream; /* _dev form: the hipStream_t of the call (NULL = the null stream); the host form ignores it */
+} fdr_psf_shift_params;
+#define FDR_REGISTER_EPS_REL 1e-3f
+int fdr_register_frames_f32(fdr_plan* plan, const float* imgs_host, size_t img_pitch, int count, int rows, int cols, int stride,
+                            const float* psfs_host, size_t psf_pitch, int prows, int pcols, int pstride,
+                            const fdr_register_params* params, fdr_frame_shift* shifts_host);
+int fdr_register_frames_f32_dev(fdr_plan* plan, const float* d_imgs, size_t img_pitch, int count, int rows, int cols, int stride,
+                                const float* d_psfs, size_t psf_pitch, int prows, int pcols, int pstride,
+                                const fdr_register_params* params, fdr_frame_shift* d_shifts, float* d_corr);
+int fdr_psf_shift_f32(int device, const float* psfs_host, size_t psf_pitch, int count, int prows, int pcols, int pstride,
+                      const fdr_frame_shift* shifts_host, const fdr_psf_shift_params* params, float* out_host, size_t out_pitch,
+                      int out_stride);
+int fdr_psf_shift_f32_dev(int device, const float* d_psfs, size_t psf_pitch, int count, int prows, int pcols, int pstride,
+                          const fdr_frame_shift* d_shifts, const fdr_psf_shift_params* params, float* d_out, size_t out_pitch,
+                          int out_stride);
+
 /* -- choosing the regularisation weight from the picture (Gonzalez & Woods section 5.9, Golub, Heath & Wahba
  *    1979, Immerkaer 1996).  The plan is M x N, the image window rows x cols (row stride `stride`) at its top-left corner, pad(d) is
  *    d on the window and 0 elsewhere, H the DFT2 of the operator PSF (fdr_set_operator_psf*), L(u, v) = 4 sin^2(pi u / M) +

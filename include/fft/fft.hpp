@@ -380,9 +380,19 @@ inline void richardsonLucyTV_RGB(std::vector<Mat>& channels, const Mat& psf, int
 // ONCE, then restore(plan, in, px, weights or null, out) once per channel -- `in` that channel of all K <= FDR_MAX_FRAMES exposures,
 // dense, px floats apart -- on launch groups of K frames; every channel of frames[0] is replaced by the joint estimate.  `weights`
 // (CV_32F, the picture's size; empty = all ones) serves every frame.
+// register_frames of the two multi-frame drivers: the exposures are NOT registered to each other (hand shake).  Each frame's translation
+// against frame 0 is estimated with the PSFs on the mean of its channels (fdr_register_frames_f32, search range max_shift pixels, 0 =
+// min(rows, cols) / 4), folded into its PSF (fdr_psf_shift_f32, padded by max_shift + 2) and the frame tables are set from the shifted
+// PSFs, laid into plan-sized planes rolled back by the padding so that the estimate stays where frame 0 is.  `shifts`, when not null,
+// receives the K estimates.
+struct RegisterOptions {
+    bool on = false;
+    int max_shift = 0;
+    std::vector<fdr_frame_shift>* shifts = nullptr;
+};
 template <class Restore>
 inline void frames_each_channel(const char* who, std::vector<std::vector<Mat>>& frames, const std::vector<Mat>& psfs, const Mat& weights,
-                                const Options& o, const Restore& restore) {
+                                const Options& o, const Restore& restore, const RegisterOptions& reg = RegisterOptions()) {
     const int K = (int)frames.size();
     if (K == 0 || frames[0].empty()) return;
     const int rows = frames[0][0].rows, cols = frames[0][0].cols;
@@ -400,13 +410,36 @@ inline void frames_each_channel(const char* who, std::vector<std::vector<Mat>>& 
     }
     bool created = false;
     PlanCacheSettle settle_;
-    fdr_plan* plan = plan_cache().get(o.device, std::max(8, nextPowerOfTwo(rows + pr - 1)), std::max(32, nextPowerOfTwo(cols + pc - 1)), FDR_MODE_FAST,
-                                      &created);
+    const int pad = reg.on ? (reg.max_shift > 0 ? reg.max_shift : std::min(rows, cols) / 4) + 2 : 0;  // the room of a registration
+    const int M = std::max(8, nextPowerOfTwo(rows + pr + 2 * pad - 1)), N = std::max(32, nextPowerOfTwo(cols + pc + 2 * pad - 1));
+    fdr_plan* plan = plan_cache().get(o.device, M, N, FDR_MODE_FAST, &created);
     const size_t ppx = (size_t)pr * pc, px = (size_t)rows * cols;
     std::vector<float> tabs(ppx * K, 0.f), in(px * K);  // the PSFs padded with zeros (bottom, right) to one shape: top-left, nothing changes
     for (int k = 0; k < K; ++k)
         for (int r = 0; r < psfs[k].rows; ++r) std::copy(psfs[k].ptr<float>(r), psfs[k].ptr<float>(r) + psfs[k].cols, tabs.begin() + k * ppx + (size_t)r * pc);
-    FDR_CHECK(fdr_set_frame_psfs(plan, tabs.data(), ppx, K, pr, pc, pc));
+    if (reg.on) {
+        for (int k = 0; k < K; ++k)  // the mean of the channels, summed in channel order
+            for (size_t i = 0; i < px; ++i) {
+                float acc = 0.f;
+                for (size_t c = 0; c < nch; ++c) acc += frames[k][c].ptr<float>((int)(i / cols))[i % cols];
+                in[k * px + i] = acc / (float)nch;
+            }
+        std::vector<fdr_frame_shift> est(K);
+        const fdr_register_params rp = {0, reg.max_shift, reg.max_shift, 0.f, nullptr};
+        FDR_CHECK(fdr_register_frames_f32(plan, in.data(), px, K, rows, cols, cols, tabs.data(), ppx, pr, pc, pc, &rp, est.data()));
+        if (reg.shifts) *reg.shifts = est;
+        const int sr = pr + 2 * pad, sc = pc + 2 * pad;
+        std::vector<float> moved((size_t)sr * sc * K), planes((size_t)M * N * K, 0.f);
+        const fdr_psf_shift_params sp = {pad, pad, nullptr};
+        FDR_CHECK(fdr_psf_shift_f32(o.device, tabs.data(), ppx, K, pr, pc, pc, est.data(), &sp, moved.data(), (size_t)sr * sc, sc));
+        for (int k = 0; k < K; ++k)  // top-left in the plan, rolled back by the padding (periodic)
+            for (int r = 0; r < sr; ++r)
+                for (int c = 0; c < sc; ++c)
+                    planes[(size_t)k * M * N + (size_t)((r - pad + M) % M) * N + (c - pad + N) % N] = moved[(size_t)k * sr * sc + (size_t)r * sc + c];
+        FDR_CHECK(fdr_set_frame_psfs(plan, planes.data(), (size_t)M * N, K, M, N, N));
+    } else {
+        FDR_CHECK(fdr_set_frame_psfs(plan, tabs.data(), ppx, K, pr, pc, pc));
+    }
     Mat w = weights.empty() || weights.isContinuous() ? weights : weights.clone();
     FDR_CHECK(fdr_plan_set_batching(plan, 1, K));
     for (size_t c = 0; c < nch; ++c) {
@@ -421,13 +454,14 @@ inline void frames_each_channel(const char* who, std::vector<std::vector<Mat>>& 
 // Multi-frame Richardson-Lucy (fdr_richardson_lucy_frames_f32, include/fdr.h) of the channels of K exposures (frames_each_channel
 // above): the joint free-boundary estimate, normalised by o.norm_area; lambda > 0 adds the TV prior of richardsonLucyTV_RGB.
 inline void richardsonLucyFrames_RGB(std::vector<std::vector<Mat>>& frames, const std::vector<Mat>& psfs, int iterations, float lambda,
-                                     float eps, const Mat& weights, const Options& o, float sigma = FDR_RL_SIGMA) {
+                                     float eps, const Mat& weights, const Options& o, float sigma = FDR_RL_SIGMA,
+                                     const RegisterOptions& register_frames = RegisterOptions()) {
     if (frames.empty() || frames[0].empty()) return;
     const int K = (int)frames.size(), rows = frames[0][0].rows, cols = frames[0][0].cols;
     const fdr_rl_frames_params prm = {iterations, sigma, o.norm_area, rows, cols, lambda, eps};
     frames_each_channel("richardsonLucyFrames_RGB", frames, psfs, weights, o, [&](fdr_plan* plan, const float* in, size_t px, const float* w, float* out) {
         return fdr_richardson_lucy_frames_f32(plan, in, px, K, rows, cols, cols, w, 0, cols, out, cols, &prm);
-    });
+    }, register_frames);
 }
 inline void richardsonLucyFrames_RGB(std::vector<std::vector<Mat>>& frames, const std::vector<Mat>& psfs, int iterations, float lambda = 0.f,
                                      float eps = 0.f, const Mat& weights = Mat()) {
@@ -438,14 +472,14 @@ inline void richardsonLucyFrames_RGB(std::vector<std::vector<Mat>>& frames, cons
 // with the known background; normalised by o.norm_area.
 inline void tvDeblurFrames_RGB(std::vector<std::vector<Mat>>& frames, const std::vector<Mat>& psfs, float mu, int iterations, bool poisson,
                                float background, const Mat& weights, const Options& o, float rho = 2.f, float nu = 0.f, bool anisotropic = false,
-                               bool nonneg = false) {
+                               bool nonneg = false, const RegisterOptions& register_frames = RegisterOptions()) {
     if (frames.empty() || frames[0].empty()) return;
     const int K = (int)frames.size(), rows = frames[0][0].rows, cols = frames[0][0].cols;
     const fdr_tv_frames_params prm = {mu, rho, nu, background, poisson ? FDR_TV_FRAMES_POISSON : FDR_TV_FRAMES_LEAST_SQUARES, iterations,
                                       anisotropic ? 1 : 0, nonneg ? 1 : 0, o.norm_area, rows, cols, nullptr};
     frames_each_channel("tvDeblurFrames_RGB", frames, psfs, weights, o, [&](fdr_plan* plan, const float* in, size_t px, const float* w, float* out) {
         return fdr_tv_deconv_frames_f32(plan, in, px, K, rows, cols, cols, w, 0, cols, out, cols, &prm);
-    });
+    }, register_frames);
 }
 inline void tvDeblurFrames_RGB(std::vector<std::vector<Mat>>& frames, const std::vector<Mat>& psfs, float mu, int iterations, bool poisson = false,
                                float background = 0.f, const Mat& weights = Mat()) {
@@ -836,6 +870,45 @@ inline fdr_motion_estimate estimateMotionBlur(const Mat& gray, int min_length = 
     fdr_motion_estimate est{};
     const int rc = fdr_estimate_motion_f32(plan, src.ptr<float>(0), src.rows, src.cols, src.cols, min_length, max_length, angle_step, &est,
                                            nullptr);
+    const std::string err = rc == FDR_OK ? std::string() : std::string(fdr_last_error());
+    fdr_plan_destroy(plan);
+    if (rc != FDR_OK) {
+        std::cerr << "Error: " << __FILE__ << ":" << __LINE__ << ", " << err << "\n";
+        exit(1);
+    }
+    return est;
+}
+// The translation of every picture of a burst against imgs[reference] (fdr_register_frames_f32, include/fdr.h): one-channel CV_32F
+// pictures of one size; psfs: one CV_32F PSF per picture, whose phases the estimate undoes, or empty for plain phase correlation
+// (right only for frames of one common PSF).  Frame k's result is the shift that belongs in its PSF (fdr_psf_shift_f32).  Plan as
+// estimateMotionBlur, made and freed inside the call; max_shift 0 selects min(rows, cols) / 4.
+inline std::vector<fdr_frame_shift> registerFrames(const std::vector<Mat>& imgs, const std::vector<Mat>& psfs = std::vector<Mat>(),
+                                                   int reference = 0, int max_shift = 0) {
+    const int K = (int)imgs.size();
+    bool ok = K >= 1 && K <= FDR_MAX_FRAMES && (psfs.empty() || (int)psfs.size() == K);
+    int pr = 0, pc = 0;
+    for (int k = 0; k < K && ok; ++k) {
+        ok = imgs[k].type() == CV_32F && imgs[k].rows == imgs[0].rows && imgs[k].cols == imgs[0].cols;
+        if (ok && !psfs.empty()) { ok = psfs[k].type() == CV_32F && psfs[k].rows > 0 && psfs[k].cols > 0; pr = std::max(pr, psfs[k].rows); pc = std::max(pc, psfs[k].cols); }
+    }
+    if (!ok) {
+        std::cerr << "registerFrames: 1 .. 8 CV_32F pictures of one size, and no PSFs or one CV_32F PSF each\n";
+        exit(1);
+    }
+    const int rows = imgs[0].rows, cols = imgs[0].cols;
+    const size_t px = (size_t)rows * cols, ppx = (size_t)pr * pc;
+    std::vector<float> in(px * K), tabs(ppx * K, 0.f);
+    for (int k = 0; k < K; ++k) {
+        for (int r = 0; r < rows; ++r) std::copy(imgs[k].ptr<float>(r), imgs[k].ptr<float>(r) + cols, in.begin() + k * px + (size_t)r * cols);
+        if (!psfs.empty())
+            for (int r = 0; r < psfs[k].rows; ++r) std::copy(psfs[k].ptr<float>(r), psfs[k].ptr<float>(r) + psfs[k].cols, tabs.begin() + k * ppx + (size_t)r * pc);
+    }
+    fdr_plan* plan = nullptr;
+    FDR_CHECK(fdr_plan_create(defaults().device, std::max(32, fdr_optimal_dft_size(std::max(rows, pr))), std::max(32, fdr_optimal_dft_size(std::max(cols, pc))),
+                              FDR_MODE_FAST, FDR_FLAG_MIXED_RADIX, &plan));
+    std::vector<fdr_frame_shift> est(K);
+    const fdr_register_params rp = {reference, max_shift, max_shift, 0.f, nullptr};
+    const int rc = fdr_register_frames_f32(plan, in.data(), px, K, rows, cols, cols, psfs.empty() ? nullptr : tabs.data(), ppx, pr, pc, pc, &rp, est.data());
     const std::string err = rc == FDR_OK ? std::string() : std::string(fdr_last_error());
     fdr_plan_destroy(plan);
     if (rc != FDR_OK) {

@@ -205,6 +205,28 @@ class TvFramesParams(ctypes.Structure):
                 ("norm_area", ctypes.c_int), ("out_rows", ctypes.c_int), ("out_cols", ctypes.c_int), ("stream", ctypes.c_void_p)]
 
 
+class FrameShiftC(ctypes.Structure):
+    """fdr_frame_shift of include/fdr.h"""
+    _fields_ = [("dy", ctypes.c_double), ("dx", ctypes.c_double), ("peak", ctypes.c_float), ("confidence", ctypes.c_float)]
+
+
+class RegisterParams(ctypes.Structure):
+    """fdr_register_params of include/fdr.h (the stream of the _dev form travels in the struct)"""
+    _fields_ = [("reference", ctypes.c_int), ("max_shift_rows", ctypes.c_int), ("max_shift_cols", ctypes.c_int), ("eps_rel", ctypes.c_float),
+                ("stream", ctypes.c_void_p)]
+
+
+class PsfShiftParams(ctypes.Structure):
+    """fdr_psf_shift_params of include/fdr.h (the stream of the _dev form travels in the struct)"""
+    _fields_ = [("pad_rows", ctypes.c_int), ("pad_cols", ctypes.c_int), ("stream", ctypes.c_void_p)]
+
+
+REGISTER_EPS_REL = 1e-3  # FDR_REGISTER_EPS_REL: the whitening floor that eps_rel = 0 selects
+# the result of Plan.register_frames / registerFrames per frame: the translation (rows down, columns right) that belongs in the frame's
+# PSF, the correlation peak and its confidence (peak - mean) / std over the correlation plane
+FrameShift = collections.namedtuple("FrameShift", "dy dx peak confidence")
+
+
 class RlTvBatchParams(ctypes.Structure):
     """fdr_rl_tv_batch_params of include/fdr.h"""
     _fields_ = RlTvParams._fields_ + [("couple", ctypes.c_int)]
@@ -431,6 +453,10 @@ def _signatures():
         "fdr_cepstrum_f32_dev": (ci, [vp, vp, ci, ci, ci, vp, vp]),
         "fdr_estimate_motion_f32": (ci, [vp, vp, ci, ci, ci, ci, ci, cd, P(MotionEstimateC), vp]),
         "fdr_estimate_motion_f32_dev": (ci, [vp, vp, ci, ci, ci, ci, ci, cd, P(MotionEstimateC), vp, vp]),
+        "fdr_register_frames_f32": (ci, [vp, vp, sz, ci, ci, ci, ci, vp, sz, ci, ci, ci, P(RegisterParams), vp]),
+        "fdr_register_frames_f32_dev": (ci, [vp, vp, sz, ci, ci, ci, ci, vp, sz, ci, ci, ci, P(RegisterParams), vp, vp]),
+        "fdr_psf_shift_f32": (ci, [ci, vp, sz, ci, ci, ci, ci, vp, P(PsfShiftParams), vp, sz, ci]),
+        "fdr_psf_shift_f32_dev": (ci, [ci, vp, sz, ci, ci, ci, ci, vp, P(PsfShiftParams), vp, sz, ci]),
         "fdr_psf_disk": (ci, [ci, cd, vp]),
         "fdr_psf_disk_dev": (ci, [ci, ci, cd, vp, vp]),
         "fdr_set_psf_disk": (ci, [vp, cd, cf, vp]),
@@ -1449,6 +1475,38 @@ class Plan:
                                                _stream(stream)))
         return MotionEstimate(est.length, est.angle_deg, est.score, est.confidence, est.n_angles, est.n_lengths)
 
+    # registering the frames of a burst (include/fdr.h): the translation of every frame against the reference, PSFs accounted for
+    def register_frames(self, frames, psfs=None, reference=0, max_shift=0, eps_rel=0.0):
+        """the shift of each of the K frames (host arrays of one shape, the window at the plan's top-left) against frames[reference]: a list
+        of K FrameShift, the one that belongs in frame k's PSF.  psfs: the K PSFs (one shape, as set_frame_psfs takes them), or None for
+        plain phase correlation.  max_shift: the search range in pixels, one number or (rows, cols); 0 selects min(rows, cols) // 4."""
+        frames = np.ascontiguousarray(np.stack([np.asarray(f, dtype=np.float32) for f in frames]), dtype=np.float32)
+        k, rows, cols = frames.shape
+        q, pr, pc = None, 0, 0
+        if psfs is not None:
+            q = np.ascontiguousarray(np.stack([np.asarray(a, dtype=np.float32) for a in psfs]), dtype=np.float32)
+            if q.shape[0] != k:
+                raise ValueError("one PSF per frame")
+            pr, pc = q.shape[1:]
+        mr, mc = (max_shift if isinstance(max_shift, (tuple, list)) else (max_shift, max_shift))
+        prm = RegisterParams(int(reference), int(mr), int(mc), float(eps_rel), None)
+        out = (FrameShiftC * k)()
+        _check(lib.fdr_register_frames_f32(self._h, _ptr(frames), rows * cols, k, rows, cols, cols, _ptr(q) if q is not None else None, pr * pc,
+                                           pr, pc, pc, ctypes.byref(prm), out))
+        return [FrameShift(o.dy, o.dx, o.peak, o.confidence) for o in out]
+
+    def register_frames_dev(self, d_imgs, img_pitch, count, rows, cols, stride, d_shifts, d_psfs=None, psf_pitch=0, prows=0, pcols=0, pstride=0,
+                            reference=0, max_shift=0, eps_rel=0.0, d_corr=None, stream=None):
+        """the same on device pointers: frame k at d_imgs + k img_pitch, PSF k at d_psfs + k psf_pitch (None: plain phase correlation),
+        the K results (24 bytes each: two doubles, two floats) to the device array d_shifts; d_corr (K planes of M x N floats) receives
+        the correlation planes when it is not None.  Reads nothing back.  Asynchronous on `stream`, which travels in the parameter struct."""
+        mr, mc = (max_shift if isinstance(max_shift, (tuple, list)) else (max_shift, max_shift))
+        prm = RegisterParams(int(reference), int(mr), int(mc), float(eps_rel), int(stream) if stream else None)
+        _check(lib.fdr_register_frames_f32_dev(self._h, ctypes.c_void_p(int(d_imgs)), int(img_pitch), int(count), rows, cols, stride,
+                                               ctypes.c_void_p(int(d_psfs)) if d_psfs else None, int(psf_pitch), int(prows), int(pcols),
+                                               int(pstride), ctypes.byref(prm), ctypes.c_void_p(int(d_shifts)) if d_shifts else None,
+                                               ctypes.c_void_p(int(d_corr)) if d_corr else None))
+
     # the defocus estimate (include/fdr.h): the ring of a disk blur in the same cepstrum, and both estimates from one cepstrum
     def estimate_defocus(self, img, min_diameter=0, max_diameter=0, angle_step=0.0, return_profile=False):
         """the disk radius of the window img (host array): a DefocusEstimate, and with return_profile=True also the profile T
@@ -1733,9 +1791,73 @@ def spectrum_sum_dev(d_dst, d_srcs, n_floats, accumulate=False, device=0, stream
                                         _stream(stream)))
 
 
-def _frames_plan_size(rows, cols, psfs):
-    """the plan of richardsonLucyFree_myfft for the largest of the PSFs"""
-    return _rlfree_plan_size(rows, cols, max(q.shape[0] for q in psfs), max(q.shape[1] for q in psfs))
+def _frames_plan_size(rows, cols, psfs, pad=0):
+    """the plan of richardsonLucyFree_myfft for the largest of the PSFs (with `pad` more on every side: the room of a registration)"""
+    return _rlfree_plan_size(rows, cols, max(q.shape[0] for q in psfs) + 2 * pad, max(q.shape[1] for q in psfs) + 2 * pad)
+
+
+def psf_shift(psfs, shifts, pad_rows, pad_cols=None, device=0):
+    """fdr_psf_shift_f32: the K PSFs (one shape prows x pcols) shifted by the K shifts (FrameShift or (dy, dx) pairs) into K planes of
+    (prows + 2 pad_rows) x (pcols + 2 pad_cols): PSF k at offset (pad_rows + dy, pad_cols + dx) by bilinear weights, the sum kept.  A
+    shift outside [-pad, pad - 1] is clamped, a NaN is taken as 0."""
+    q = np.ascontiguousarray(np.stack([np.asarray(a, dtype=np.float32) for a in psfs]), dtype=np.float32)
+    k, pr, pc = q.shape
+    pad_cols = pad_rows if pad_cols is None else pad_cols
+    if len(shifts) != k:
+        raise ValueError("one shift per PSF")
+    sh = (FrameShiftC * k)(*[FrameShiftC(float(t[0]), float(t[1]), 0.0, 0.0) for t in shifts])
+    orows, ocols = pr + 2 * int(pad_rows), pc + 2 * int(pad_cols)
+    out = np.empty((k, max(orows, 1), max(ocols, 1)), dtype=np.float32)
+    prm = PsfShiftParams(int(pad_rows), int(pad_cols), None)
+    _check(lib.fdr_psf_shift_f32(int(device), _ptr(q), pr * pc, k, pr, pc, pc, sh, ctypes.byref(prm), _ptr(out), out.shape[1] * out.shape[2],
+                                 out.shape[2]))
+    return out
+
+
+def psf_shift_dev(d_psfs, psf_pitch, count, prows, pcols, pstride, d_shifts, pad_rows, pad_cols, d_out, out_pitch, out_stride, device=0,
+                  stream=None):
+    """the same on device pointers, the shifts read from device memory (straight from Plan.register_frames_dev): PSF k at d_psfs + k
+    psf_pitch to d_out + k out_pitch.  Asynchronous on `stream`, which travels in the parameter struct."""
+    prm = PsfShiftParams(int(pad_rows), int(pad_cols), int(stream) if stream else None)
+    _check(lib.fdr_psf_shift_f32_dev(int(device), ctypes.c_void_p(int(d_psfs)) if d_psfs else None, int(psf_pitch), int(count), prows, pcols,
+                                     pstride, ctypes.c_void_p(int(d_shifts)) if d_shifts else None, ctypes.byref(prm),
+                                     ctypes.c_void_p(int(d_out)) if d_out else None, int(out_pitch), out_stride))
+
+
+def registerFrames(imgs, psfs=None, reference=0, max_shift=0, eps_rel=0.0, device=0):
+    """the translation of every frame of a burst against imgs[reference] (fdr_register_frames_f32): a list of FrameShift, frame k's the
+    shift that belongs in its PSF (psf_shift).  imgs: K pictures of one size, one channel or rows x cols x channels (the per-pixel mean
+    is used); psfs: the K known PSFs, whose phases the estimate undoes, or None for plain phase correlation (right only for frames of one
+    common PSF).  The plan is the smallest 2^a 3^b 5^c size of each dimension (at least 32), FLAG_MIXED_RADIX."""
+    frames = [np.asarray(f, dtype=np.float32) for f in imgs]
+    frames = [f.mean(axis=2, dtype=np.float32) if f.ndim == 3 else f for f in frames]
+    rows, cols = frames[0].shape
+    if psfs is not None:
+        psfs = _frame_psfs(psfs)
+        rows, cols = max(rows, psfs.shape[1]), max(cols, psfs.shape[2])
+    M, N = _motion_plan_size(rows, cols)
+    with Plan(M, N, MODE_FAST, device, flags=FLAG_MIXED_RADIX) as p:
+        return p.register_frames(frames, psfs, reference, max_shift, eps_rel)
+
+
+def _register_pad(rows, cols, max_shift):
+    """the padding that holds every result of a registration with this range: max_shift + 2"""
+    return (int(max_shift) or min(rows, cols) // 4) + 2
+
+
+def _registered_psfs(p, frames, psfs, max_shift):
+    """register=True of the multi-frame calls on the plan p: the frames registered against frame 0 with their PSFs, every PSF shifted
+    by its frame's estimate (psf_shift) and laid into an M x N plane rolled back by the padding, so that the PSFs keep the origin the
+    caller gave them and the restoration stays where frame 0 is.  Returns the K planes."""
+    k, pr, pc = psfs.shape
+    pad = _register_pad(frames[0].shape[0], frames[0].shape[1], max_shift)
+    if pr + 2 * pad > p.M or pc + 2 * pad > p.N:
+        raise ValueError("register=True needs compact PSFs: PSF + 2 (max_shift + 2) must fit the plan")
+    shifts = p.register_frames(frames, psfs, 0, max_shift)
+    shifted = psf_shift(psfs, shifts, pad, pad, device=p.device)
+    planes = np.zeros((k, p.M, p.N), dtype=np.float32)
+    planes[:, :pr + 2 * pad, :pc + 2 * pad] = shifted
+    return np.roll(planes, (-pad, -pad), axis=(1, 2))
 
 
 def _frame_psfs(psfs):
@@ -1749,62 +1871,73 @@ def _frame_psfs(psfs):
 
 
 def richardsonLucyFrames_myfft(frames, psfs, iterations, weights=None, tv_lambda=0.0, tv_eps=0.0, sigma=RL_SIGMA, device=0,
-                               norm_area=NORM_NONE, full_plane=False):
+                               norm_area=NORM_NONE, full_plane=False, register=False, max_shift=0):
     """Joint free-boundary Richardson-Lucy of K (1 .. MAX_FRAMES) exposures of one scene, frame k blurred by psfs[k] (top-left in
     the plan, as for richardsonLucyFree_myfft; sums not normalised: a PSF's sum is its frame's relative exposure): the plan of
     richardsonLucyFree_myfft, the frame tables, `iterations` steps, the window back.  weights: None, one plane, or one per frame;
-    tv_lambda > 0 adds the TV prior (without it the joint iteration fits the noise within a few steps, as plain RL does)."""
+    tv_lambda > 0 adds the TV prior (without it the joint iteration fits the noise within a few steps, as plain RL does).
+    register=True: the frames are not registered to each other (hand shake): each frame's translation against frame 0 is estimated
+    with the PSFs (Plan.register_frames, search range max_shift) and folded into its PSF before the restoration."""
     frames = [np.asarray(f, dtype=np.float32) for f in frames]
     psfs = _frame_psfs(psfs)
-    M, N = _frames_plan_size(frames[0].shape[0], frames[0].shape[1], psfs)
+    pad = _register_pad(frames[0].shape[0], frames[0].shape[1], max_shift) if register else 0
+    M, N = _frames_plan_size(frames[0].shape[0], frames[0].shape[1], psfs, pad)
     with Plan(M, N, MODE_FAST, device) as p:
-        p.set_frame_psfs(psfs)
+        p.set_frame_psfs(_registered_psfs(p, frames, psfs, max_shift) if register else psfs)
         p.set_batching(1, min(len(frames), 8))
         return p.richardson_lucy_frames(frames, iterations, weights, tv_lambda, tv_eps, sigma, norm_area, full_plane)
 
 
-def richardsonLucyFrames_RGB(frames, psfs, iterations, weights=None, tv_lambda=0.0, tv_eps=0.0, sigma=RL_SIGMA, device=0, norm_area=NORM_NONE):
+def richardsonLucyFrames_RGB(frames, psfs, iterations, weights=None, tv_lambda=0.0, tv_eps=0.0, sigma=RL_SIGMA, device=0, norm_area=NORM_NONE,
+                             register=False, max_shift=0):
     """fft_gpu::richardsonLucyFrames_RGB: frames[k] is the list of channel planes of exposure k (every exposure the same channels
     and size).  Returns the list of restored channels: the frame tables are set once, then one joint call per channel (the bits of
-    richardsonLucyFrames_myfft on that channel)."""
+    richardsonLucyFrames_myfft on that channel).  register=True: as there, the shifts estimated once on the mean of the channels."""
     if not frames or not frames[0]:
         return []
     psfs = _frame_psfs(psfs)
     r, c = np.asarray(frames[0][0]).shape
-    M, N = _frames_plan_size(r, c, psfs)
+    M, N = _frames_plan_size(r, c, psfs, _register_pad(r, c, max_shift) if register else 0)
     with Plan(M, N, MODE_FAST, device) as p:
-        p.set_frame_psfs(psfs)
+        p.set_frame_psfs(_registered_psfs(p, _channel_means(frames), psfs, max_shift) if register else psfs)
         p.set_batching(1, min(len(frames), 8))
         return [p.richardson_lucy_frames([f[ch] for f in frames], iterations, weights, tv_lambda, tv_eps, sigma, norm_area)
                 for ch in range(len(frames[0]))]
 
 
+def _channel_means(frames):
+    """per exposure the per-pixel mean of its channel planes: what register=True of the _RGB calls registers"""
+    return [np.mean(np.stack([np.asarray(ch, dtype=np.float32) for ch in f]), axis=0, dtype=np.float32) for f in frames]
+
+
 def tvDeblurFrames_myfft(frames, psfs, mu, iterations, weights=None, data_term=TV_FRAMES_LEAST_SQUARES, background=0.0, rho=2.0, nu=0.0,
-                         anisotropic=False, nonneg=False, device=0, norm_area=NORM_NONE, full_plane=False):
+                         anisotropic=False, nonneg=False, device=0, norm_area=NORM_NONE, full_plane=False, register=False, max_shift=0):
     """Joint TV deconvolution of K (1 .. MAX_FRAMES) exposures of one scene, frame k blurred by psfs[k] (top-left in the plan; sums
     not normalised: a PSF's sum is its frame's relative exposure): the plan of richardsonLucyFrames_myfft, the frame tables,
-    `iterations` ADMM steps of  min mu sum_k Phi_k(blur_k(x)) + TV(x),  the window back.  weights: None, one plane, or one per frame."""
+    `iterations` ADMM steps of  min mu sum_k Phi_k(blur_k(x)) + TV(x),  the window back.  weights: None, one plane, or one per frame.
+    register=True: as richardsonLucyFrames_myfft, every frame's translation against frame 0 estimated and folded into its PSF."""
     frames = [np.asarray(f, dtype=np.float32) for f in frames]
     psfs = _frame_psfs(psfs)
-    M, N = _frames_plan_size(frames[0].shape[0], frames[0].shape[1], psfs)
+    pad = _register_pad(frames[0].shape[0], frames[0].shape[1], max_shift) if register else 0
+    M, N = _frames_plan_size(frames[0].shape[0], frames[0].shape[1], psfs, pad)
     with Plan(M, N, MODE_FAST, device) as p:
-        p.set_frame_psfs(psfs)
+        p.set_frame_psfs(_registered_psfs(p, frames, psfs, max_shift) if register else psfs)
         p.set_batching(1, min(len(frames), 8))
         return p.tv_deconv_frames(frames, mu, iterations, weights, data_term, background, rho, nu, anisotropic, nonneg, norm_area, full_plane)
 
 
 def tvDeblurFrames_RGB(frames, psfs, mu, iterations, weights=None, data_term=TV_FRAMES_LEAST_SQUARES, background=0.0, rho=2.0, nu=0.0,
-                       anisotropic=False, nonneg=False, device=0, norm_area=NORM_NONE):
+                       anisotropic=False, nonneg=False, device=0, norm_area=NORM_NONE, register=False, max_shift=0):
     """fft_gpu::tvDeblurFrames_RGB: frames[k] is the list of channel planes of exposure k (every exposure the same channels and
     size).  Returns the list of restored channels: the frame tables are set once, then one joint call per channel (the bits of
-    tvDeblurFrames_myfft on that channel)."""
+    tvDeblurFrames_myfft on that channel).  register=True: as there, the shifts estimated once on the mean of the channels."""
     if not frames or not frames[0]:
         return []
     psfs = _frame_psfs(psfs)
     r, c = np.asarray(frames[0][0]).shape
-    M, N = _frames_plan_size(r, c, psfs)
+    M, N = _frames_plan_size(r, c, psfs, _register_pad(r, c, max_shift) if register else 0)
     with Plan(M, N, MODE_FAST, device) as p:
-        p.set_frame_psfs(psfs)
+        p.set_frame_psfs(_registered_psfs(p, _channel_means(frames), psfs, max_shift) if register else psfs)
         p.set_batching(1, min(len(frames), 8))
         return [p.tv_deconv_frames([f[ch] for f in frames], mu, iterations, weights, data_term, background, rho, nu, anisotropic, nonneg,
                                    norm_area)

@@ -154,6 +154,7 @@ struct MotionWorkspace : MotionLayout<float2> {
     std::vector<float> table_host;
     std::vector<double> trig_host;
 };
+struct RegisterWorkspace : RegisterLayout<float2> { Workspace ws; };  // beside the motion workspace
 struct DefocusWorkspace : DefocusLayout { Workspace ws; std::vector<double> trig_host; std::vector<float> profile_host; };  // beside the motion workspace
 
 }  // namespace fdr
@@ -201,11 +202,12 @@ struct fdr_plan {
     fdr::RegWorkspace reg;            // fdr_reg_curve_f32*, fdr_choose_reg_f32*
     fdr::MotionWorkspace motion;      // fdr_cepstrum_f32*, fdr_estimate_motion_f32*
     fdr::DefocusWorkspace defocus;    // fdr_estimate_defocus_f32*, fdr_estimate_blur_f32*
+    fdr::RegisterWorkspace regist;    // fdr_register_frames_f32*
     // every block of the members above, for fdr_plan_destroy: a block that a feature gains is added here, beside its member
-    std::array<fdr::Workspace*, 19> workspaces() {
+    std::array<fdr::Workspace*, 20> workspaces() {
         return {&tv.ws, &tvfree.ws, &tvauto.ws, &tvframes.ws, &rlfree.ws, &rlaccel.ws, &rltv.ws, &rlstop.ws,
                 &rlstop.trace_ws, &rlstop.planes_ws, &frames.ws, &frames.tables_ws, &blind.ws, &blind.w_ws, &reg.ws,
-                &motion.ws, &motion.table_ws, &motion.trig_ws, &defocus.ws};
+                &motion.ws, &motion.table_ws, &motion.trig_ws, &defocus.ws, &regist.ws};
     }
     // sectioned restoration (fdr_restore_tiled_f32*): the host copy of the last call's weight tables (one entry per picture row, then one
     // per picture column), kept here while the upload may still read it; everything else of such a call lies in the caller's workspace

@@ -403,8 +403,31 @@ int motion_pad_partials(int M, int N);
 hipError_t launch_motion_window(const float* img, int rows, int cols, int stride, float* hann, float2* plane, int M, int N, double* part,
                                 hipStream_t s);
 hipError_t launch_motion_log(float2* plane, int M, int N, const double* sum, hipStream_t s);
+// the two stages of the window launch that the frame registration shares: the Hann tables alone, and part[n] = the sum of part[0 .. n) in
+// the fixed order of one workgroup
+hipError_t launch_motion_hann(float* hann, int rows, int cols, hipStream_t s);
+hipError_t launch_motion_fold(double* part, int n, hipStream_t s);
 hipError_t launch_motion_score(const float2* plane, int M, int N, const double* trig, int n_angles, int min_length, int n_lengths, float* table,
                                hipStream_t s);
+// (fdr_register.hip) registering the frames of a burst; the formulas are in that file's header.  pair: re = w . a, im = w . b on the rows x
+// cols window (w the Hann tables, or 1 for hann == null), 0 elsewhere in the M x N plane; with `part` (2 register_peak_partials(M, N)
+// doubles) also *gate = 1 when neither windowed picture is all zero, else 0.  cross: Z = DFT2 of such a picture pair (in
+// place -> C), P = DFT2 of the PSF pair (null: H_a = H_b = 1), the sum |C| partials (register_cross_partials of them) folded into
+// part[register_cross_partials(M, N)].  normalize: C -> C / (|C| + eps_rel mean |C|) / (M N) in place (0 for sum[0] = 0 or a gate
+// sum[1] = 0; the peak pass reads the same pair).  peak: the real
+// parts of the plane -> the frame's result (24 bytes: double dy, dx; float peak, confidence) at `result`; part holds 4
+// register_peak_partials(M, N) doubles.  reference: the result (0, 0, 1, 0).  psf_shift: see fdr_psf_shift_f32 in include/fdr.h.
+int register_cross_partials(int M, int N);
+int register_peak_partials(int M, int N);
+hipError_t launch_register_pair(const float* a, const float* b, int rows, int cols, int stride, const float* hann, float2* plane, int M, int N,
+                                double* part, double* gate, hipStream_t s);
+hipError_t launch_register_cross(float2* Z, const float2* P, int M, int N, double* part, hipStream_t s);
+hipError_t launch_register_normalize(float2* plane, int M, int N, const double* sum, float eps_rel, hipStream_t s);
+hipError_t launch_register_peak(const float2* plane, int M, int N, int range_rows, int range_cols, const double* sum, double* part, void* result,
+                                hipStream_t s);
+hipError_t launch_register_reference(void* result, hipStream_t s);
+hipError_t launch_psf_shift(const float* psfs, size_t psf_pitch, int count, int prows, int pcols, int pstride, const void* shifts, int pad_rows,
+                            int pad_cols, float* out, size_t out_pitch, int out_stride, hipStream_t s);
 // (fdr_defocus.hip) the defocus estimate.  disk: fdr_psf_disk (size <= kDiskMaxSize, radius > 0; one workgroup).  profile: T[d -
 // min_diameter] = the median over a of the score launch_motion_score would put at table[a * n_diameters + d - min_diameter], from the
 // same plane and trig table; one workgroup per diameter, n_angles <= kDefocusMaxAngles

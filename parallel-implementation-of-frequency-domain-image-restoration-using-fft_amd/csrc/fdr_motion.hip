@@ -107,18 +107,26 @@ __global__ __launch_bounds__(kMoThreads) void motion_score_kernel(const float2* 
 
 int motion_pad_partials(int M, int N) { return M * ((N + kMoPadCols - 1) / kMoPadCols); }
 
-hipError_t launch_motion_window(const float* img, int rows, int cols, int stride, float* hann, float2* plane, int M, int N, double* part,
-                                hipStream_t s) {
+hipError_t launch_motion_hann(float* hann, int rows, int cols, hipStream_t s) {
     hipLaunchKernelGGL(motion_hann_kernel, dim3((unsigned)((rows + cols + kMoThreads - 1) / kMoThreads)), dim3(kMoThreads), 0, s, hann, rows,
                        cols);
-    hipError_t e = hipGetLastError();
+    return hipGetLastError();
+}
+
+hipError_t launch_motion_fold(double* part, int n, hipStream_t s) {
+    hipLaunchKernelGGL(motion_fold_kernel, dim3(1), dim3(kMoThreads), 0, s, part, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_motion_window(const float* img, int rows, int cols, int stride, float* hann, float2* plane, int M, int N, double* part,
+                                hipStream_t s) {
+    hipError_t e = launch_motion_hann(hann, rows, cols, s);
     if (e != hipSuccess) return e;
     const dim3 grid((unsigned)((N + kMoPadCols - 1) / kMoPadCols), (unsigned)M);
     hipLaunchKernelGGL(motion_pad_kernel, grid, dim3(kMoThreads), 0, s, img, rows, cols, stride, (const float*)hann, plane, N, part);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(motion_fold_kernel, dim3(1), dim3(kMoThreads), 0, s, part, motion_pad_partials(M, N));
-    return hipGetLastError();
+    return launch_motion_fold(part, motion_pad_partials(M, N), s);
 }
 
 hipError_t launch_motion_log(float2* plane, int M, int N, const double* sum, hipStream_t s) {

@@ -195,6 +195,17 @@ template <class C, class Cx> void layout(C& c, MotionLayout<Cx>& m, size_t M, si
     c.put("hann", m.hann, M + N, 4);
 }
 
+// Registering the frames of a burst (beside the motion block, whose plane and Hann tables it uses): the plane of the PSF pair (any
+// M x N), the cross-power partials, their sum and the zero-frame gate, four doubles per workgroup of the peak pass, then the results of max_frames frames
+// (24 bytes each: two doubles and two floats, held as three doubles)
+template <class Cx> struct RegisterLayout { Cx* psf = nullptr; double *part = nullptr, *peak = nullptr, *result = nullptr; };
+template <class C, class Cx> void layout(C& c, RegisterLayout<Cx>& m, size_t M, size_t N, size_t n_cross, size_t n_peak, size_t max_frames) {
+    c.put("psf", m.psf, M * N, 8);
+    c.put("part", m.part, n_cross + 2, 8);
+    c.put("peak", m.peak, 4 * n_peak, 8);
+    c.put("result", m.result, 3 * max_frames, 8);
+}
+
 // The defocus estimate: the trig table (cos, then sin, of max_angles angles), then the profile of max_diameters floats
 struct DefocusLayout { double* trig = nullptr; float* profile = nullptr; };
 template <class C> void layout(C& c, DefocusLayout& m, size_t max_angles, size_t max_diameters) {

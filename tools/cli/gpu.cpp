@@ -1,5 +1,5 @@
 // gpu.cpp -- ./gpu <img-path> <psf-length> <psf-angle> | auto auto [--any-blur] | defocus <radius|auto> | blind <size>  [--out file] [--mode fast|parity] [--norm padded|cropped] [--host-epilogue]
-//           [--cls gamma|auto] [--k K|auto] [--reg gcv|discrepancy] [--sigma s] [--pad zero|smooth] [--rl iterations|auto [--accel] [--rl-tv lambda [--rl-tv-eps e] [--rl-tv-color]] [--free-boundary [--mask mask.png] [--frame img2 L2 A2 ...]] [--rl-max n] [--rl-stop residual|kl] [--gain g] [--rl-check c]] [--tv mu [--tv-iters n] [--tv-rho r] [--tv-color | --free-boundary [--mask mask.png]]]
+//           [--cls gamma|auto] [--k K|auto] [--reg gcv|discrepancy] [--sigma s] [--pad zero|smooth] [--rl iterations|auto [--accel] [--rl-tv lambda [--rl-tv-eps e] [--rl-tv-color]] [--free-boundary [--mask mask.png] [--frame img2 L2 A2 ... [--register [--max-shift s]]]] [--rl-max n] [--rl-stop residual|kl] [--gain g] [--rl-check c]] [--tv mu [--tv-iters n] [--tv-rho r] [--tv-color | --free-boundary [--mask mask.png]]]
 // `--rl n|--tv mu --free-boundary --tile T [--overlap O]`: the leg is fft_gpu::restoreTiled_RGB -- overlapping T x T tiles (O pixels shared, default T / 8),
 // each restored as a crop of a larger scene with the PSF centred, blended and normalised over the picture; one PSF, --mask as before.
 // `--tv mu --free-boundary`: the TV leg is fft_gpu::tvDeblurFree_RGB (the picture is a crop of a larger scene; --mask as for --rl); --tv-color has no such form.
@@ -33,8 +33,10 @@
 // and the run then goes on exactly as `--rl k` would.  It combines with --accel, --free-boundary, --mask and `auto auto`.
 // `--rl n --free-boundary --frame <img2> <L2> <A2> [--frame ...] [--rl-tv lambda [--rl-tv-eps e]] [--mask mask.png]`: the --rl leg is
 // fft_gpu::richardsonLucyFrames_RGB -- the picture and every --frame picture (at most 7, all of the picture's size) are exposures of ONE
-// scene, each with its own motion PSF (length, angle), restored jointly; --mask serves every frame.  Beside --frame only --rl n, --free-boundary,
-// --rl-tv, --rl-tv-eps, --mask, --out and --raw-out may stand: anything else (--accel, `--rl auto`, blind, defocus, `auto auto`, --tile, --rl-tv-color,
+// scene, each with its own motion PSF (length, angle), restored jointly; --mask serves every frame.  With --register [--max-shift s] the frames
+// need not be registered to each other: every frame's translation against the picture is estimated with the PSFs (fft_gpu::RegisterOptions; search
+// range s pixels, default min(rows, cols) / 4), printed as `shift: frame k dy .. dx .. confidence ..` and folded into the frame's PSF before the
+// restoration.  Beside --frame only --rl n, --free-boundary, --rl-tv, --rl-tv-eps, --mask, --register, --max-shift, --out and --raw-out may stand: anything else (--accel, `--rl auto`, blind, defocus, `auto auto`, --tile, --rl-tv-color,
 // --tv, --cls, --k, --sigma, --reg, --norm, --pad, --mode, --host-epilogue, ...) is refused with the usage text, before a picture is read.
 // `--rl n --rl-tv lambda [--rl-tv-eps e]`: the --rl leg runs Richardson-Lucy with a total-variation prior of weight lambda (fft_gpu::richardsonLucyTV_RGB;
 // eps smooths |grad u|, default FDR_RLTV_EPS); --free-boundary and --mask apply, `auto auto` works as before; --accel, `--rl auto` and `blind` have no
@@ -130,6 +132,9 @@ int main(int argc, char** argv) {
     string mask_path;            // --mask file: pixels that are 0 in it (any channel counts) get weight 0, the others weight 1
     struct FrameArg { string path; int length; double angle; };
     vector<FrameArg> frame_args;  // --frame img L A: a further exposure of the same scene with its own motion PSF (fft_gpu::richardsonLucyFrames_RGB)
+    bool register_frames = false;  // --register beside --frame: the frames are registered against the picture before the joint restoration
+    int max_shift = 0;             // --max-shift s: the search range of --register in pixels (0: min(rows, cols) / 4)
+    bool max_shift_set = false;
     int tile = 0, tile_overlap = -1;  // --tile T [--overlap O]: the free-boundary --rl n / --tv mu leg is fft_gpu::restoreTiled_RGB (default O = T / 8)
     float tv_mu = -1.f, tv_rho = 2.0f;  // --tv mu: a timed total-variation leg (fft_gpu::tvDeblur_RGB); its planes are the written result
     int tv_iterations = 50;
@@ -195,6 +200,8 @@ int main(int argc, char** argv) {
         else if (a == "--free-boundary") free_boundary = true;
         else if (a == "--mask" && i + 1 < argc) mask_path = argv[++i];
         else if (a == "--frame" && i + 3 < argc) { frame_args.push_back({argv[i + 1], atoi(argv[i + 2]), atof(argv[i + 3])}); i += 3; }
+        else if (a == "--register") register_frames = true;
+        else if (a == "--max-shift" && i + 1 < argc) { max_shift = atoi(argv[++i]); max_shift_set = true; }
         else if (a == "--tile" && i + 1 < argc) tile = atoi(argv[++i]);
         else if (a == "--overlap" && i + 1 < argc) tile_overlap = atoi(argv[++i]);
         else if (a == "--psf-hold" && i + 1 < argc) { blind_opts = true; psf_hold = atoi(argv[++i]); }
@@ -242,7 +249,13 @@ int main(int argc, char** argv) {
         cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle>\n";
         return -1;
     }
-    // --frame belongs to --rl n --free-boundary with stated motion PSFs, and takes only --rl-tv, --rl-tv-eps and --mask beside them
+    // --register belongs to --frame, --max-shift (a range of at least one pixel) to --register
+    if ((register_frames && frame_args.empty()) || (max_shift_set && (!register_frames || max_shift < 1))) {
+        cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle> --rl <n> --free-boundary --frame <img2> <L2> <A2> [--frame ...] --register "
+                "[--max-shift <s >= 1>]\n";
+        return -1;
+    }
+    // --frame belongs to --rl n --free-boundary with stated motion PSFs, and takes only --rl-tv, --rl-tv-eps, --mask and --register beside them
     if (!frame_args.empty()) {
         bool ok = rl_iterations >= 0 && free_boundary && !rl_auto && !accel && !blind && !defocus && !estimate && tile == 0 && tile_overlap == -1 &&
                   !rl_tv_color && tv_mu == -1.f && !tv_auto && !poisson && !cls && !cls_auto && !k_auto && !pad_smooth && !parity && !verify &&
@@ -252,12 +265,12 @@ int main(int argc, char** argv) {
         for (int i = 4; i < argc && ok; ++i) {
             const string a = argv[i];
             if (a == "--frame") i += 3;
-            else if (a == "--rl" || a == "--rl-tv" || a == "--rl-tv-eps" || a == "--mask" || a == "--out" || a == "--raw-out") i += 1;
-            else ok = a == "--free-boundary";
+            else if (a == "--rl" || a == "--rl-tv" || a == "--rl-tv-eps" || a == "--mask" || a == "--out" || a == "--raw-out" || a == "--max-shift") i += 1;
+            else ok = a == "--free-boundary" || a == "--register";
         }
         if (!ok) {
             cout << "Usage: ./gpu <img-path> <psf-length> <psf-angle> --rl <n> --free-boundary --frame <img2> <L2> <A2> [--frame ...] [--rl-tv lambda] "
-                    "[--mask m.png] (at most 7 --frame; no other leg or option beside them)\n";
+                    "[--mask m.png] [--register [--max-shift s]] (at most 7 --frame; no other leg or option beside them)\n";
             return -1;
         }
     }
@@ -501,7 +514,13 @@ int main(int argc, char** argv) {
                 frames.push_back(ch);
                 psfs.push_back(motionBlurKernel(f.length, f.angle));
             }
-            fft_gpu::richardsonLucyFrames_RGB(frames, psfs, rl_iterations, rl_tv_opts ? rl_tv : 0.f, rl_tv_eps, weights);
+            vector<fdr_frame_shift> shifts;
+            fft_gpu::RegisterOptions reg;
+            reg.on = register_frames; reg.max_shift = max_shift; reg.shifts = &shifts;
+            fft_gpu::richardsonLucyFrames_RGB(frames, psfs, rl_iterations, rl_tv_opts ? rl_tv : 0.f, rl_tv_eps, weights, fft_gpu::defaults(),
+                                              FDR_RL_SIGMA, reg);
+            for (size_t k = 0; k < shifts.size(); ++k)
+                cout << "shift: frame " << k << " dy " << shifts[k].dy << " dx " << shifts[k].dx << " confidence " << shifts[k].confidence << "\n";
             rl = frames[0];
         }
         else if (rl_tv_opts) fft_gpu::richardsonLucyTV_RGB(rl, psf, rl_iterations, rl_tv, rl_tv_eps, free_boundary, weights, rl_tv_color);

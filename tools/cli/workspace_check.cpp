@@ -6,6 +6,9 @@
 //        workgroups) rg (the doubles of the curve partials) mo (motion_pad_partials) noise (kRegMaxPartials + 1) maxgroup psf (kBlindMaxPsf)
 //        curve (kRegMaxCurve) angles diameters (the defocus limits) trace table trig (entries of the buffers that grow alone)
 //
+//   workspace_check register:CASE ...   the block of the frame registration alone, from its own numbers: M N rc (register_cross_partials)
+//        rp (register_peak_partials) frames (FDR_MAX_FRAMES)
+//
 // First the handle's failure branch on a host allocator that fails on request (exit 1 unless: a failed grow leaves block, count,
 // size and pointers as they were and frees nothing; a satisfied count allocates nothing; a grow has the new block before it lets the
 // old one go; free_with leaves an empty handle).  Then per case and workspace, each grown through Workspace::grow on the host
@@ -115,12 +118,21 @@ int main(int argc, char** argv) {
     check_handle();
     for (int i = 1; i < argc; ++i) {
         std::map<std::string, size_t> v;
-        const std::string arg = argv[i];
+        const std::string whole = argv[i];
+        const bool regist = whole.rfind("register:", 0) == 0;
+        const std::string arg = regist ? whole.substr(9) : whole;
         for (size_t a = 0; a < arg.size();) {
             const size_t e = arg.find('=', a), b = arg.find(',', a) == std::string::npos ? arg.size() : arg.find(',', a);
             if (e == std::string::npos || e > b) { std::fprintf(stderr, "workspace_check: bad case %s\n", argv[i]); return 2; }
             v[arg.substr(a, e - a)] = std::strtoull(arg.c_str() + e + 1, nullptr, 10);
             a = b + 1;
+        }
+        if (regist) {
+            if (v.size() != 5) { std::fprintf(stderr, "workspace_check: case %s does not give the 5 numbers\n", argv[i]); return 2; }
+            std::printf("case %s\n", argv[i]);
+            RegisterLayout<Complex> rg;
+            show("register", 1, [&](auto& c, int) { layout(c, rg, v["M"], v["N"], v["rc"], v["rp"], v["frames"]); });
+            continue;
         }
         if (v.size() != 20) { std::fprintf(stderr, "workspace_check: case %s does not give the 20 numbers\n", argv[i]); return 2; }
         const size_t M = v["M"], N = v["N"], P = M * N, ws = v["ws"], noise = v["noise"];
