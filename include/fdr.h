@@ -137,6 +137,12 @@ int fdr_plan_dims(const fdr_plan* plan, int* M, int* N, int* mode);
                                       fdr_wiener_batch_f32 and fdr_wiener_batch_ptrs_f32, with a Wiener or a CLS filter.  Leave a margin
                                       of at least the PSF's reach (M >= rows + prows - 1, N >= cols + pcols - 1) for the continuation
                                       to take up the blur that crosses the border.
+                                      Not defined: the normalised output of a restored area that is constant.  The flat test that
+                                      turns such an area into zeros is exact (max - min below 2.2e-16), a float32 plane that is
+                                      constant in exact arithmetic is constant only up to rounding, and (x - min) / (max - min) of
+                                      rounding noise is arbitrary in [0, 1].  A constant picture does this on every path and with
+                                      either padding; a one-pixel window under FDR_PAD_SMOOTH does it under FDR_NORM_PADDED, because
+                                      its continuation is the constant plane (FDR_NORM_CROPPED of one pixel is exactly 0).
                                       Plans: FDR_MODE_FAST on the panel path -- M, N powers of two, 8 .. 8192, with or without
                                       FDR_FLAG_FULL_SPECTRUM.  Parity mode, FDR_FLAG_SIMPLE_PATH, FDR_FLAG_ANY_SIZE sizes, mixed-radix
                                       sizes, FDR_FLAG_TABLES_ONLY and dimensions below 8 or above 8192 return FDR_ERR_ARG before any
@@ -499,7 +505,9 @@ int fdr_richardson_lucy_auto_f32_dev(fdr_plan* plan, const float* d_img, int row
  *    Plans, refusals, overlap rules and phases are those of the underlying form.  FDR_ERR_ARG, before any device work and with the
  *    plan usable afterwards, also for: a null params or PSF pointer, psf_hold < 0, a PSF that is empty, larger than the plan or of
  *    more than FDR_BLIND_MAX_PSF entries, pstride < pcols, weights in the plain form, a plain-form output window other than 0, 0 or
- *    rows, cols, a PSF range that overlaps the input, the weights or the output, and -- host form -- a start PSF with a negative
+ *    rows, cols, a PSF range that overlaps the input, the weights or the output, a free-boundary window smaller than the PSF (the
+ *    minimum is prows x pcols: under a smaller one the shifted window of a tap's den can lie wholly where the coverage is below
+ *    sigma, u = 0 there, and the sign of den -- the tap itself -- would be rounding noise), and -- host form -- a start PSF with a negative
  *    entry or a sum that is not finite and > 0.  The _dev form checks the start PSF in its first kernel instead: a bad one sets the
  *    plan's status word to 1, the PSF is then never updated or written, and the image of that call is meaningless;
  *    fdr_richardson_lucy_blind_status synchronises the device and reads the word of the last call (0 = the start was good).

@@ -1078,7 +1078,8 @@ class Plan:
         """`iterations` blind Richardson-Lucy steps on the window img (host arrays) from the start PSF psf_start: the plain form, or
         with free_boundary the free-boundary, weighted one (weights, cov_sigma and full_plane as Plan.richardson_lucy_free).  The
         PSF is kept for the first psf_hold steps.  Returns (image, psf); the plan's operator PSF is then the returned one.  The call
-        refines a PSF: a flat start does not move and zeros of the start stay zeros."""
+        refines a PSF: a flat start does not move and zeros of the start stay zeros.  The free-boundary form needs a window of at
+        least the PSF's size (rows >= prows, cols >= pcols): a smaller one is refused (FdrError, FDR_ERR_ARG; include/fdr.h)."""
         img = np.ascontiguousarray(img, dtype=np.float32)
         psf = np.array(psf_start, dtype=np.float32, order="C", ndmin=2)
         rows, cols = img.shape
@@ -1098,7 +1099,8 @@ class Plan:
                                   free_boundary=False, d_weights=None, wstride=0, psf_hold=0, cov_sigma=RL_SIGMA, norm_area=NORM_NONE,
                                   out_rows=None, out_cols=None, stream=None):
         """the same on device pointers, asynchronous: d_psf holds the start PSF and receives the refined one; out_rows x out_cols
-        (free form; default rows x cols, up to M x N) is the output window.  A bad start PSF shows in blind_status()."""
+        (free form; default rows x cols, up to M x N) is the output window.  A bad start PSF shows in blind_status().  A
+        free-boundary window smaller than the PSF (rows < prows or cols < pcols) is refused before any device work (FDR_ERR_ARG)."""
         prm = BlindParams(int(iterations), int(bool(free_boundary)), int(psf_hold), int(norm_area), float(cov_sigma),
                           int(rows if out_rows is None else out_rows), int(cols if out_cols is None else out_cols))
         _check(lib.fdr_richardson_lucy_blind_f32_dev(self._h, ctypes.c_void_p(int(d_img)), rows, cols, stride,

@@ -56,6 +56,11 @@ int blind_check(const fdr_plan* p, const char* fn, const float* img, int rows, i
     if (prows <= 0 || pcols <= 0 || pstride < pcols) return fail(FDR_ERR_ARG, std::string(fn) + ": bad PSF shape");
     if (prows > p->M || pcols > p->N) return fail(FDR_ERR_ARG, std::string(fn) + ": PSF larger than the padded image");
     if ((size_t)prows * pcols > (size_t)kBlindMaxPsf) return fail(FDR_ERR_ARG, std::string(fn) + ": a PSF of more than 65536 entries");
+    // den = corr_u(W) of a tap sums u over the window shifted by the tap.  Under a window smaller than the PSF that shifted window can
+    // lie wholly where the coverage is below sigma, u = 0 there, and den is 0 up to the transform's rounding: its sign, and with it the
+    // tap, would be noise.  A window of the PSF's size always reaches covered pixels.
+    if (prm->free_boundary && (rows < prows || cols < pcols))
+        return fail(FDR_ERR_ARG, std::string(fn) + ": the free-boundary form needs a window of at least the PSF's size, prows x pcols");
     const ByteRange f = window_range(psf, prows, pcols, pstride);
     if (ranges_overlap(f, window_range(img, rows, cols, stride))) return fail(FDR_ERR_ARG, std::string(fn) + ": the PSF overlaps the input");
     if (weights && ranges_overlap(f, window_range(weights, rows, cols, wstride))) return fail(FDR_ERR_ARG, std::string(fn) + ": the PSF overlaps the weights");
